@@ -13,9 +13,17 @@ MPS construction (the reference's `simulate` loop, the step before the path) hap
 the timed region and is reported separately, like the reference's `r0_circ_sim`.
 
 Rank 0 prints ONE JSON line (contract in the task statement), with `roofline` (dominant
-kernel = the sweep kernel the engine selected, named in the line; fp64 MFMA bound) and, at N=1,
-`cpu_baseline` (the oracle's C restatement of the ITensors `inner` loop on BLAS zgemm, timed on this
-host's cores over a bounded sample; the hand-written loop is timed beside it).
+kernel = the sweep kernel the engine selected, named in the line; fp64 MFMA bound).
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds, at N=1, the
+legs that cost runs of their own: the device MPS builder on the same circuits (and the Gram of its
+states against the timed one), the cold Gram through the C ABI, and `cpu_baseline` (the oracle's C
+restatement of the ITensors `inner` loop on BLAS zgemm, timed on this host's cores over a bounded
+sample; the hand-written loop is timed beside it).
+
+`--dump-outputs DIR` writes the Gram of the last timed step as DIR/K.npy (float64); a Gram larger
+than 64 MB is written as the block of a fixed, seeded sample of its rows and columns, with the
+sampled indices in DIR/K_index.npy.
 """
 from __future__ import annotations
 
@@ -230,6 +238,21 @@ def cpu_baseline(states, pairs, total_unique, npts, seconds, gpu_vals, threads):
     }
 
 
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, K):
+    """K as DIR/K.npy (float64).  Above DUMP_MAX_BYTES: the block K[idx, idx] of 2048 indices drawn with a fixed seed, and
+    idx (as float64) in DIR/K_index.npy, so that runs with the same arguments write the same entries."""
+    os.makedirs(dirname, exist_ok=True)
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    if K.nbytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(K.shape[0], 2048, replace=False))
+        np.save(os.path.join(dirname, "K_index.npy"), idx.astype(np.float64))
+        K = K[np.ix_(idx, idx)]
+    np.save(os.path.join(dirname, "K.npy"), K)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -239,13 +262,16 @@ def main():
     ap.add_argument("--gamma", type=float, default=None, help="default 1.0 (0.1 for cfg5, whose bonds explode at larger gamma)")
     ap.add_argument("--points", type=int, default=0, help="override the number of data points")
     ap.add_argument("--seed", type=int, default=5)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline budget (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline budget of a --full run (0 = skip)")
     ap.add_argument("--workers", type=int, default=0, help="host processes for MPS building (0 = all cores / ranks)")
     ap.add_argument("--max-bond", type=int, default=0,
                     help="bond cap chi (the `chi` of pytket-cutensornet's Config, ref gpu_backend/kernel_state_ansatz.py:141-144; 0 = none, like the reference): "
                     "the states are then built by the DEVICE builder, truncating at chi -- what makes cfg5 runnable beyond gamma = 0.1")
     ap.add_argument("--precision", default="f64", choices=["f64", "f32"],
                     help="f64 = the reference's precision and the headline metric; f32 = the complex64 sweep (SURVEY 8f N4), a supplementary line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline (one GPU): device MPS builder, cold Gram through the C ABI, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the Gram of the last timed step to DIR/K.npy")
     args = ap.parse_args()
     if args.gamma is None:
         args.gamma = 0.1 if args.config == "cfg5" else 1.0
@@ -333,9 +359,9 @@ def main():
         xset = x64.to_f32()
         x64.close()
         info = xset.info()
-    # the device MPS builder on the same circuits (rank 0, one GPU; QK_BENCH_DEVICE_BUILD=0 skips it): reported beside the host pool
+    # the device MPS builder on the same circuits (--full, rank 0, one GPU; QK_BENCH_DEVICE_BUILD=0 skips it): reported beside the host pool
     dev_build, K_dev = None, None
-    if world == 1 and args.precision == "f64" and not args.max_bond and os.environ.get("QK_BENCH_DEVICE_BUILD", "1") != "0":
+    if args.full and world == 1 and args.precision == "f64" and not args.max_bond and os.environ.get("QK_BENCH_DEVICE_BUILD", "1") != "0":
         dev_build, K_dev = device_build_leg(ctx, binfo["ansatz"], binfo["X"], states, lambda t: log(rank, t))
         if "error" not in dev_build:
             log(rank, f"device MPS builder: {npts} states in {dev_build['device_kernel_s']:.2f} s (wall {dev_build['device_wall_s']:.2f} s); host pool: {binfo['cpu_s_per_state'] * npts / workers:.1f} s on {workers} workers")
@@ -404,11 +430,13 @@ def main():
     ms_per_step = 1e3 * elapsed / max(1, args.steps)
     kms = float(np.mean(kernel_ms)) if kernel_ms else float("nan")
     kernel_name = kernel_name or ctx.stats()["kernel_name"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, host_K.numpy())
 
     # the cold Gram through the C ABI's one-call route (qk_gram_host: what build_kernel_matrix runs on one rank, gpu_backend/kernel_state_ansatz.py):
-    # a fresh set again -- fresh plan, fresh derived images, its own buffers -> K in host memory; rank 0, after the timed region
+    # a fresh set again -- fresh plan, fresh derived images, its own buffers -> K in host memory; --full, rank 0, after the timed region
     cold_abi = None
-    if world == 1 and states is not None:
+    if args.full and world == 1 and states is not None:
         x2 = ctx.upload(states) if args.precision == "f64" else None
         if x2 is not None:
             torch.cuda.synchronize()
@@ -580,7 +608,7 @@ def main():
                 "launches": launches,
             },
         }
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             pairs = job.plan.pairs()
             gpu_vals = job.my_vals.cpu().numpy()[: pairs.shape[0]]
             threads = default_workers()

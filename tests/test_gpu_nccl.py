@@ -112,11 +112,11 @@ def test_four_rank_bench_rehearsal(built, tmp_path):
 
 @pytest.mark.timeout(600)
 def test_bench_line_contract(built, tmp_path):
-    """`python bench.py` on one GPU (a reduced workload: 60 points of cfg4, whose states differ enough for the split sweep):
+    """`python bench.py --full` on one GPU (a reduced workload: 60 points of cfg4, whose states differ enough for the split sweep):
     ONE JSON line with the driver's keys, the roofline object of the whole sweep (its launches listed beside it),
     the CPU baseline timed on a bounded sample and checked against the GPU values."""
     env = dict(os.environ, QK_CACHE_DIR=str(tmp_path / "cache"))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--points", "60", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--points", "60", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=550, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -156,3 +156,32 @@ def test_bench_line_contract(built, tmp_path):
         assert key in cb, key
     assert cb["kind"] in ("port", "reference") and cb["cores"] >= 1 and cb["value"] > 0 and cb["parity_max_abs_err_vs_gpu"] < 1e-10
     assert d["config"]["diag_err"] < 1e-11 and d["config"]["sym_err"] == 0.0
+
+
+@pytest.mark.timeout(300)
+def test_plain_bench_line_and_dumped_gram(built, tmp_path):
+    """A plain `python bench.py` runs the headline alone: its line carries the headline keys and none of the --full legs, and
+    --dump-outputs writes the Gram of the last timed step, which is the oracle's Gram of the same states."""
+    import qml_cutensornet_amd as Q
+    from oracle import restatement as R
+    from qml_cutensornet_amd.data import synthetic_features
+
+    env = dict(os.environ, QK_CACHE_DIR=str(tmp_path / "cache"))
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg2", "--points", "12", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=250, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "entries/s" and d["higher_is_better"] is True and d["dtype"] == "f64 (complex128)"
+    assert abs(d["value"] - 12 * 12 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert "cpu_baseline" not in d and d["cold_c_abi_ms"] is None and "device_kernel_s" not in d["config"]["mps_build"]
+    assert sorted(os.listdir(out)) == ["K.npy"]
+    K = np.load(out / "K.npy")
+    assert K.dtype == np.float64 and K.shape == (12, 12)
+    ans = Q.KernelStateAnsatz(20, 2, 1.0, Q.entanglement_graph(20, 1))  # cfg2: 20 qubits x 2 layers, d=1, gamma 1, seed 5
+    states = [Q.simulate(ans.circuit_for_data(x), 1 - 1e-16) for x in synthetic_features(12, 20, 5)]
+    assert np.abs(K - R.gram_from_mps([m.tensors for m in states])).max() < 1e-11

@@ -721,6 +721,28 @@ def test_bench_quotes_pmc_figures_only_for_the_sources_they_were_taken_on(monkey
     assert per_kernel is None and "no committed summary" in why
 
 
+def test_bench_dump_outputs_caps_the_written_gram(tmp_path):
+    """bench.py --dump-outputs: the Gram as K.npy in float64; one above 64 MB as the block of a seeded sample of 2048 rows and
+    columns, the same from run to run, with the sampled indices beside it."""
+    import sys
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = np.random.default_rng(1).random((50, 50))
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert sorted(os.listdir(tmp_path / "s")) == ["K.npy"] and np.array_equal(np.load(tmp_path / "s" / "K.npy"), small)
+    big = np.random.default_rng(2).random((2900, 2900))
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), big)
+    k, idx = np.load(tmp_path / "a" / "K.npy"), np.load(tmp_path / "a" / "K_index.npy")
+    assert k.dtype == idx.dtype == np.float64 and k.shape == (2048, 2048)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES
+    i = idx.astype(np.int64)
+    assert np.all(np.diff(i) > 0) and np.array_equal(k, big[np.ix_(i, i)])
+    assert np.array_equal(np.load(tmp_path / "b" / "K.npy"), k) and np.array_equal(np.load(tmp_path / "b" / "K_index.npy"), idx)
+
+
 def test_experiment_switches_are_off_in_the_product(built):
     """The sweep sources carry experiment switches for lab builds (ablations with WRONG results, the quad form, timing probes:
     lab/tools/build_variants.py).  Their defaults must be the shipped code, build() must not define any of them, and the product
