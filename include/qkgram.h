@@ -326,7 +326,9 @@ int qk_selftest_mfma(qk_ctx* ctx);
 /* ---- device MPS builder ------------------------------------------------------------
  * Replaces simulate(libhandle, circ, SimulationAlgorithm.MPSxGate, config) (G:141-144, 221, 263) for the
  * ansatz gate program: all data points share the gate structure (op, q0: n_ops entries; 0 = H, 1 = Rz,
- * 2 = XXPhase on (q0, q0+1), 3 = SWAP on (q0, q0+1)) and differ in the half-turn angles alpha[n_states][n_ops].
+ * 2 = XXPhase on (q0, q0+1), 3 = SWAP on (q0, q0+1), 4 = Rx, 5 = Ry, 6 = YYPhase on (q0, q0+1), 7 = ZZPhase on
+ * (q0, q0+1); TKET matrices, theta = pi alpha / 2) and differ in the half-turn angles alpha[n_states][n_ops].
+ * Any other op code is QK_EINVAL before anything runs.
  * One persistent launch; per two-qubit gate a one-sided Jacobi SVD and the truncation rule of the host builder:
  * drop the trailing singular values whose squared weight stays <= trunc_budget (= 1 - truncation_fidelity,
  * G:141-144; criterion as KernelPkg.jl:68), values <= value_of_zero never count.  max_bond bounds every bond

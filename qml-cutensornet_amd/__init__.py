@@ -8,7 +8,7 @@ gfx950 HIP kernels behind a C ABI (``include/qkgram.h``).
 The directory is named ``qml-cutensornet_amd`` (not an identifier); import it as
 ``qml_cutensornet_amd`` through the one-file shim at the repository root.
 """
-from .ansatz import KernelStateAnsatz, entanglement_graph  # noqa: F401
+from .ansatz import BoundCircuit, CircuitAnsatz, KernelStateAnsatz, entanglement_graph  # noqa: F401
 from .mps import MPS, random_mps, simulate  # noqa: F401
 
-__all__ = ["KernelStateAnsatz", "entanglement_graph", "MPS", "simulate", "random_mps"]
+__all__ = ["KernelStateAnsatz", "CircuitAnsatz", "BoundCircuit", "entanglement_graph", "MPS", "simulate", "random_mps"]

@@ -15,6 +15,10 @@ reference:
 
 Angles are pytket half-turns (theta = pi*alpha/2), the convention spelled out in
 /root/reference/KernelPkg/src/KernelPkg.jl:8-32.
+
+Custom feature maps (``CircuitAnsatz``, ``BoundCircuit.from_gates``) add Rx, Ry,
+YYPhase and ZZPhase (op codes 4-7) to the four gates above; the matrices are
+TKET's, as in KernelPkg.jl and the reference's CPU gate list.
 """
 from __future__ import annotations
 
@@ -23,7 +27,25 @@ from dataclasses import dataclass
 import numpy as np
 
 OP_H, OP_RZ, OP_XX, OP_SWAP = 0, 1, 2, 3
-_OP_NAMES = {OP_H: "H", OP_RZ: "Rz", OP_XX: "XXPhase", OP_SWAP: "SWAP"}
+OP_RX, OP_RY, OP_YY, OP_ZZ = 4, 5, 6, 7  # custom feature maps (CircuitAnsatz, BoundCircuit.from_gates)
+N_OPS = 8  # codes 0 .. N_OPS-1 are valid; every builder rejects any other
+_OP_NAMES = {OP_H: "H", OP_RZ: "Rz", OP_XX: "XXPhase", OP_SWAP: "SWAP", OP_RX: "Rx", OP_RY: "Ry", OP_YY: "YYPhase", OP_ZZ: "ZZPhase"}
+_OP_CODES = {name: code for code, name in _OP_NAMES.items()}
+_TWO_QUBIT = (OP_XX, OP_SWAP, OP_YY, OP_ZZ)
+_PARAMETRISED = (OP_RZ, OP_XX, OP_RX, OP_RY, OP_YY, OP_ZZ)
+
+
+def is_two_qubit(o) -> bool:
+    """Does op code ``o`` act on the pair (q0, q0+1)?  XXPhase, SWAP, YYPhase and ZZPhase do."""
+    return o in _TWO_QUBIT
+
+
+def check_op_codes(op) -> None:
+    """``ValueError`` unless every code of ``op`` is one of the N_OPS gates."""
+    op = np.asarray(op)
+    bad = (op < 0) | (op >= N_OPS)
+    if bad.any():
+        raise ValueError(f"unknown gate op code {int(op[bad][0])} (valid: 0..{N_OPS - 1})")
 
 
 def entanglement_graph(nq: int, nn: int) -> list[tuple[int, int]]:
@@ -64,17 +86,72 @@ class BoundCircuit:
     def as_tuples(self):
         """(name, qubits, params) triples in the shape of the reference's CPU gate list
         (/root/reference/cpu_backend/kernel_state_ansatz.py:113-131)."""
+        check_op_codes(self.op)
         out = []
         for o, q, a in zip(self.op.tolist(), self.q0.tolist(), self.alpha.tolist()):
-            if o in (OP_H,):
-                out.append((_OP_NAMES[o], [q], []))
-            elif o == OP_RZ:
-                out.append((_OP_NAMES[o], [q], [a]))
-            elif o == OP_XX:
-                out.append((_OP_NAMES[o], [q, q + 1], [a]))
-            else:
-                out.append((_OP_NAMES[o], [q, q + 1], []))
+            qubits = [q, q + 1] if is_two_qubit(o) else [q]
+            out.append((_OP_NAMES[o], qubits, [a] if o in _PARAMETRISED else []))
         return out
+
+    @classmethod
+    def from_gates(cls, n_qubits, gates) -> "BoundCircuit":
+        """A gate list in the shape of the reference's CPU backend -- ``(name, qubits, params)`` with the names of
+        ``_OP_NAMES`` and ``params`` the half-turn angle in a one-element list (empty for H and SWAP) -- as a program.
+        A two-qubit gate on non-adjacent or reversed qubits is routed like KernelStateAnsatz's XXPhase: SWAP chain up,
+        the gate on (hi-1, hi), the chain back (exact: every two-qubit gate here is symmetric in its qubits)."""
+        n = int(n_qubits)
+        op, q0, alpha = [], [], []
+        for g in gates:
+            name, qubits, params = g
+            code = _gate_code(name)
+            qubits = [int(q) for q in qubits]
+            if params is None:
+                params = []
+            elif np.ndim(params) == 0:
+                params = [params]
+            if _arity(code) != len(qubits):
+                raise ValueError(f"{name} acts on {_arity(code)} qubit(s), got {qubits}")
+            if len(params) != (1 if code in _PARAMETRISED else 0):
+                raise ValueError(f"{name}: expected {1 if code in _PARAMETRISED else 0} parameter(s), got {list(params)}")
+            a = float(params[0]) if params else 0.0
+            for o, q, k in _route(code, qubits, n):
+                op.append(o), q0.append(q), alpha.append(a if k else 0.0)
+        return cls(n, np.asarray(op, dtype=np.int8), np.asarray(q0, dtype=np.int32), np.asarray(alpha, dtype=np.float64))
+
+
+def _arity(o) -> int:
+    return 2 if is_two_qubit(o) else 1
+
+
+def _gate_code(name) -> int:
+    try:
+        return _OP_CODES[name]
+    except KeyError:
+        raise ValueError(f"unknown gate {name!r} (supported: {', '.join(_OP_CODES)})") from None
+
+
+def _route(code, qubits, n):
+    """The adjacent-pair program of one gate: [(op, q0, is_the_gate)].  A two-qubit gate on (a, b) becomes a SWAP chain
+    bringing min(a, b) next to max(a, b), the gate on (hi-1, hi), and the chain back (KernelStateAnsatz's routing)."""
+    if not all(0 <= q < n for q in qubits):
+        raise ValueError(f"gate on qubits {qubits} outside a register of {n}")
+    if not is_two_qubit(code):
+        return [(code, qubits[0], True)]
+    a, b = qubits
+    if a == b:
+        raise ValueError(f"two-qubit gate on ({a}, {b})")
+    lo, hi = (a, b) if a < b else (b, a)
+    return ([(OP_SWAP, q, False) for q in range(lo, hi - 1)] + [(code, hi - 1, True)]
+            + [(OP_SWAP, q, False) for q in range(hi - 2, lo - 1, -1)])
+
+
+def as_bound_circuit(circuit, ansatz) -> BoundCircuit:
+    """What ``ansatz.circuit_for_data`` returned, as a program: a reference-style gate list ``(name, qubits, params)``
+    through ``BoundCircuit.from_gates`` with ``n_qubits`` from ``ansatz.ansatz_circ.n_qubits`` (as reference G:147); a
+    BoundCircuit as it is."""
+    if isinstance(circuit, (list, tuple)):
+        return BoundCircuit.from_gates(ansatz.ansatz_circ.n_qubits, circuit)
+    return circuit
 
 
 class GateProgram:
@@ -146,6 +223,87 @@ class KernelStateAnsatz:
 
     def circuit_for_data(self, feature_values) -> BoundCircuit:
         """Bind one data point.  ``RuntimeError`` on a length mismatch, as ref :96-97."""
+        if len(feature_values) != len(self.feature_symbol_list):
+            raise RuntimeError("The number of values must match the number of symbols.")
+        return self.ansatz_circ.bind(np.asarray(feature_values, dtype=np.float64))
+
+
+class CircuitProgram:
+    """The compiled (unbound) gate program of a ``CircuitAnsatz``: per routed gate an op code, a pair / qubit and the
+    angle form alpha = s (c_a + d_a x[a]) (c_b + d_b x[b]) (s = 0 for H and SWAP; c = 1, d = 0 for an absent factor)."""
+
+    def __init__(self, n_qubits, op, q0, s, fa, ca, da, fb, cb, db):
+        self.n_qubits = int(n_qubits)
+        self.op, self.q0 = op, q0
+        self.s, self.fa, self.ca, self.da, self.fb, self.cb, self.db = s, fa, ca, da, fb, cb, db
+
+    @property
+    def n_gates(self) -> int:
+        return int(self.op.shape[0])
+
+    def bind(self, x: np.ndarray) -> BoundCircuit:
+        alpha = self.s * (self.ca + self.da * x[self.fa]) * (self.cb + self.db * x[self.fb])
+        return BoundCircuit(self.n_qubits, self.op, self.q0, alpha)
+
+
+def _factor(spec, n_features):
+    a, c, d = spec
+    if not 0 <= int(a) < n_features:
+        raise ValueError(f"feature index {a} outside 0..{n_features - 1}")
+    return int(a), float(c), float(d)
+
+
+class CircuitAnsatz:
+    """A custom feature map: a gate template compiled once, bound per data point by one vectorised expression.
+
+    ``gates`` is a list of ``(name, qubits, angle)`` with the names of ``BoundCircuit.from_gates`` (H, Rz, Rx, Ry, XXPhase,
+    YYPhase, ZZPhase, SWAP), angles in half-turns (theta = pi alpha / 2).  ``angle`` is
+      * ``None`` for H and SWAP;
+      * a number: a constant angle;
+      * ``(s, (a, c_a, d_a))``: alpha = s (c_a + d_a x[a]);
+      * ``(s, (a, c_a, d_a), (b, c_b, d_b))``: alpha = s (c_a + d_a x[a]) (c_b + d_b x[b]).
+    The reference ansatz is Rz ``((2/pi) gamma, (i, 0, 1))`` and XXPhase ``(gamma^2, (a, 1, -1), (b, 1, -1))``; a
+    Havlicek-style ZZ map is ZZPhase ``(s, (a, pi, -1), (b, pi, -1))``.  Two-qubit gates on non-adjacent or reversed
+    qubits are routed as in ``BoundCircuit.from_gates``.  ``num_features`` defaults to ``num_qubits`` (one feature per
+    qubit, as the reference's ``feature_symbol_list``).  Picklable: plain numpy arrays only."""
+
+    def __init__(self, num_qubits, gates, num_features=None):
+        n = int(num_qubits)
+        nf = n if num_features is None else int(num_features)
+        if nf < 1:
+            raise ValueError("a feature map needs at least one feature")
+        self.num_qubits, self.num_features = n, nf
+        self.feature_symbol_list = [f"f_{i}" for i in range(nf)]
+        cols = {k: [] for k in ("op", "q0", "s", "fa", "ca", "da", "fb", "cb", "db")}
+        for name, qubits, angle in gates:
+            code = _gate_code(name)
+            qubits = [int(q) for q in (qubits if np.ndim(qubits) else [qubits])]
+            if _arity(code) != len(qubits):
+                raise ValueError(f"{name} acts on {_arity(code)} qubit(s), got {qubits}")
+            one = (0, 1.0, 0.0)
+            if code not in _PARAMETRISED:
+                if angle is not None:
+                    raise ValueError(f"{name} takes no angle, got {angle!r}")
+                s, fa, fb = 0.0, one, one
+            elif angle is None:
+                raise ValueError(f"{name} needs an angle")
+            elif not isinstance(angle, (tuple, list)):
+                s, fa, fb = float(angle), one, one
+            else:
+                if len(angle) not in (2, 3):
+                    raise ValueError(f"{name}: angle {angle!r} is not (s, (a, c_a, d_a)[, (b, c_b, d_b)])")
+                s, fa = float(angle[0]), _factor(angle[1], nf)
+                fb = _factor(angle[2], nf) if len(angle) == 3 else one
+            for o, q, is_gate in _route(code, qubits, n):
+                row = (o, q, s, *fa, *fb) if is_gate else (o, q, 0.0, *one, *one)
+                for k, v in zip(cols, row):
+                    cols[k].append(v)
+        dt = {"op": np.int8, "q0": np.int32, "fa": np.int32, "fb": np.int32}
+        arr = {k: np.asarray(v, dtype=dt.get(k, np.float64)) for k, v in cols.items()}
+        self.ansatz_circ = CircuitProgram(n, **arr)
+
+    def circuit_for_data(self, feature_values) -> BoundCircuit:
+        """Bind one data point.  ``RuntimeError`` on a length mismatch, as reference G:96-97."""
         if len(feature_values) != len(self.feature_symbol_list):
             raise RuntimeError("The number of values must match the number of symbols.")
         return self.ansatz_circ.bind(np.asarray(feature_values, dtype=np.float64))

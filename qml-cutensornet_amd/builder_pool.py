@@ -13,6 +13,7 @@ import time
 
 import numpy as np
 
+from .ansatz import as_bound_circuit
 from .mps import MPS, simulate
 
 _G = {}
@@ -32,7 +33,8 @@ def _init(ansatz, fidelity, max_bond=None):
 
 def _one(x):
     t0 = time.perf_counter()
-    m = simulate(_G["ansatz"].circuit_for_data(x), _G["fid"], max_bond=_G.get("chi"))
+    ansatz = _G["ansatz"]
+    m = simulate(as_bound_circuit(ansatz.circuit_for_data(x), ansatz), _G["fid"], max_bond=_G.get("chi"))
     return m.tensors, m.fidelity, time.perf_counter() - t0
 
 

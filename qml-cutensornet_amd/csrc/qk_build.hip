@@ -1,7 +1,7 @@
 // qk_build.hip -- device MPS builder: the input producer of the Gram path on the GPU.
 // Replaces simulate(libhandle, circ, SimulationAlgorithm.MPSxGate, config) of the reference
 // (gpu_backend/kernel_state_ansatz.py:141-144, 221, 263; truncation criterion as KernelPkg.jl:68) for the ansatz gate
-// program (H, Rz, XXPhase, SWAP on adjacent qubits: qml-cutensornet_amd/ansatz.py).  Same algorithm as the host
+// program (H, Rz, Rx, Ry; XXPhase, YYPhase, ZZPhase, SWAP on adjacent qubits: qml-cutensornet_amd/ansatz.py).  Same algorithm as the host
 // builder (csrc/qk_builder.cpp, mps.py:_simulate) -- orthogonality centre carried along, one SVD per two-qubit gate,
 // fewest singular values whose weight keeps the fidelity -- restated for the device:
 //   * all data points share ONE gate structure and differ only in the angles, so the whole list is one persistent
@@ -31,9 +31,11 @@ typedef double cd __attribute__((ext_vector_type(2)));  // complex128 as (re, im
 
 constexpr int MAX_SWEEPS = 40;
 
-enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3 };  // ansatz.py
+enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8 };  // ansatz.py
 
-enum { ERR_BOND = 1, ERR_HEAP = 2, ERR_SWEEPS = 4, ERR_GATE = 8 };
+__host__ __device__ inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ; }
+
+enum { ERR_BOND = 1, ERR_HEAP = 2, ERR_SWEEPS = 4, ERR_GATE = 8, ERR_OP = 16 };
 
 struct BuildArgs {
   int n_states, n_qubits, n_ops, cap;
@@ -120,6 +122,8 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
   if (!c || !op || !q0 || !alpha || !out) return qk_fail(QK_EINVAL, "qk_build_mps: null argument");
   if (n_states <= 0 || n_qubits <= 0 || n_ops < 0) return qk_fail(QK_EINVAL, "qk_build_mps: empty problem (%d states, %d qubits, %d gates)", n_states, n_qubits, n_ops);
   if (max_bond < 2 || max_bond > 1024) return qk_fail(QK_EINVAL, "qk_build_mps: max_bond %d outside 2..1024", max_bond);
+  for (int i = 0; i < n_ops; ++i)
+    if (op[i] < 0 || op[i] >= N_OPS) return qk_fail(QK_EINVAL, "qk_build_mps: unknown gate op code %d at position %d (valid: 0..%d)", (int)op[i], i, N_OPS - 1);
   *out = nullptr;
   QkRangeGuard range_("qk:build");
   HIP_TRY(hipSetDevice(c->device));
@@ -223,13 +227,13 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
   BUILD_TRY(hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), c->stream));
   BUILD_TRY(hipMemsetAsync(d_err, 0, 32 * sizeof(int), c->stream));
   // Queue order: longest expected first.  The cost of a state grows with its bonds, and those with the entangling power
-  // of its XXPhase gates, sin^2(pi alpha) summed over the gates -- a cheap proxy that keeps the tail of the launch short.
+  // of its XXPhase / YYPhase / ZZPhase gates, sin^2(pi alpha) summed over the gates -- a cheap proxy that keeps the tail of the launch short.
   std::vector<int32_t> order(n_states);
   {
     std::vector<double> proxy(n_states, 0.0);
     for (int s = 0; s < n_states; ++s)
       for (int i = 0; i < n_ops; ++i)
-        if (op[i] == OP_XX) {
+        if (op[i] == OP_XX || op[i] == OP_YY || op[i] == OP_ZZ) {
           const double sn = std::sin(M_PI * alpha[(size_t)s * n_ops + i]);
           proxy[s] += sn * sn;
         }
@@ -316,6 +320,7 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
   if (err) {
     (void)hipFree(heap);
     delete b;
+    if (err & ERR_OP) return qk_fail(QK_EINVAL, "qk_build_mps: unknown gate op code (valid: 0..%d)", N_OPS - 1);
     if (err & ERR_GATE) return qk_fail(QK_EINVAL, "qk_build_mps: gate on a qubit outside the register");
     if (err & ERR_BOND) return qk_fail(QK_EINVAL, "qk_build_mps: a bond grew beyond max_bond = %d", cap);
     if (err & ERR_HEAP) return qk_fail(QK_EDEVICE, "qk_build_mps: the packed states need %llu complex numbers, the heap holds %zu", ctr[1], heap_cap);

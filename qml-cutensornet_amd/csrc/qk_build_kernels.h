@@ -1100,7 +1100,11 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
     bool outgrown = false;
     for (int i = 0; i < g.n_ops && !outgrown; ++i) {
       const int o = g.op[i], q = g.q0[i];
-      if (q < 0 || q >= n || (o >= OP_XX && q + 1 >= n) || o < 0 || o > OP_SWAP) {
+      if (o < 0 || o >= N_OPS) {
+        if (tid == 0) atomicOr(g.error, ERR_OP);
+        continue;
+      }
+      if (q < 0 || q >= n || (is_two_qubit(o) && q + 1 >= n)) {
         if (tid == 0) atomicOr(g.error, ERR_GATE);
         continue;
       }
@@ -1118,6 +1122,25 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
           } else {
             t[(a * 2) * r + c] = cmul(t0, cd{ph.x, -ph.y});
             t[(a * 2 + 1) * r + c] = cmul(t1, ph);
+          }
+        }
+        __syncthreads();
+        continue;
+      }
+      if (!is_two_qubit(o)) {  // Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
+        cd* t = sites + q * slot;
+        const int l = dims[q], r = dims[q + 1];
+        const double th = 0.5 * M_PI * alpha[i];
+        const double cs = cos(th), sn = sin(th);
+        for (int e = tid; e < l * r; e += BT) {
+          const int a = e / r, c = e - a * r;
+          const cd t0 = t[(a * 2) * r + c], t1 = t[(a * 2 + 1) * r + c];
+          if (o == OP_RX) {  // -i sn * (x + i y) = sn y - i sn x
+            t[(a * 2) * r + c] = cd{cs * t0.x + sn * t1.y, cs * t0.y - sn * t1.x};
+            t[(a * 2 + 1) * r + c] = cd{cs * t1.x + sn * t0.y, cs * t1.y - sn * t0.x};
+          } else {
+            t[(a * 2) * r + c] = cd{cs * t0.x - sn * t1.x, cs * t0.y - sn * t1.y};
+            t[(a * 2 + 1) * r + c] = cd{sn * t0.x + cs * t1.x, sn * t0.y + cs * t1.y};
           }
         }
         __syncthreads();
@@ -1229,6 +1252,16 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
           if (o == OP_SWAP) {
             *p01 = t10;
             *p10 = t01;
+          } else if (o == OP_YY) {  // YYPhase: cos(th) 1 - i sin(th) Y(x)Y ;  +i sn on 00 <-> 11, -i sn on 01 <-> 10
+            *p00 = cd{cs * t00.x - sn * t11.y, cs * t00.y + sn * t11.x};
+            *p01 = cd{cs * t01.x + sn * t10.y, cs * t01.y - sn * t10.x};
+            *p10 = cd{cs * t10.x + sn * t01.y, cs * t10.y - sn * t01.x};
+            *p11 = cd{cs * t11.x - sn * t00.y, cs * t11.y + sn * t00.x};
+          } else if (o == OP_ZZ) {  // ZZPhase: diag(e^-i th, e^i th, e^i th, e^-i th)
+            *p00 = cmul(t00, cd{cs, -sn});
+            *p01 = cmul(t01, cd{cs, sn});
+            *p10 = cmul(t10, cd{cs, sn});
+            *p11 = cmul(t11, cd{cs, -sn});
           } else {  // XXPhase: cos(th) 1 - i sin(th) X(x)X ;  -i sn * (x + i y) = sn y - i sn x
             *p00 = cd{cs * t00.x + sn * t11.y, cs * t00.y - sn * t11.x};
             *p01 = cd{cs * t01.x + sn * t10.y, cs * t01.y - sn * t10.x};
@@ -1254,7 +1287,7 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
       }
       int nxt = q;
       for (int j2 = i + 1; j2 < g.n_ops; ++j2)
-        if (g.op[j2] >= OP_XX) {
+        if (is_two_qubit(g.op[j2])) {
           nxt = g.q0[j2];
           break;
         }

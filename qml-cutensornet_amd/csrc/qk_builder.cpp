@@ -33,7 +33,9 @@ zgeqrf_t p_zgeqrf = nullptr;
 zungqr_t p_zungqr = nullptr;
 zgemm_t p_zgemm = nullptr;
 
-enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3 };  // ansatz.py
+enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8 };  // ansatz.py
+
+inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ; }
 
 // row-major C[m x n] = A[m x k] * B[k x n]  (as column-major C^T = B^T A^T)
 void gemm_rm(int m, int n, int k, const cd* A, const cd* B, cd* C) {
@@ -131,6 +133,8 @@ int qkb_init(const char* openblas_path) {
 // MPS of circuit |0...0>.  op/q0/alpha: the bound gate program (ansatz.py: BoundCircuit).  On success fills
 // dims_out[n_qubits + 1] and *tensors_out: ONE malloc'd block holding the site tensors back to back, complex128
 // [l][2][r] row-major (free it with qkb_free), and *fidelity.  Returns 0, or a negative code with qkb_last_error().
+// Op codes: 0 H, 1 Rz, 2 XXPhase, 3 SWAP, 4 Rx, 5 Ry, 6 YYPhase, 7 ZZPhase (two-qubit gates on (q0, q0+1)); any other
+// code fails the call with -7 before a gate is applied.
 int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
                      double value_of_zero, int32_t max_bond, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out, double* fidelity_out);
 int qkb_simulate(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
@@ -146,11 +150,16 @@ int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const in
     return -1;
   }
   const int n = n_qubits;
+  for (int i = 0; i < n_ops; ++i)
+    if (op[i] < 0 || op[i] >= N_OPS) {
+      g_err = "unknown gate op code " + std::to_string((int)op[i]) + " (valid: 0.." + std::to_string(N_OPS - 1) + ")";
+      return -7;
+    }
   std::vector<Tensor> A(n);
   for (auto& t : A) t.v = {cd(1, 0), cd(0, 0)};
   std::vector<int> two_q_pos;
   for (int i = 0; i < n_ops; ++i)
-    if (op[i] == OP_XX || op[i] == OP_SWAP) two_q_pos.push_back(q0[i]);
+    if (is_two_qubit(op[i])) two_q_pos.push_back(q0[i]);
   double fidelity = 1.0;
   int centre = 0;  // sites < centre are left-orthonormal, sites > centre right-orthonormal
   size_t g2 = 0;
@@ -161,7 +170,7 @@ int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const in
 
   for (int i = 0; i < n_ops; ++i) {
     const int o = op[i], q = q0[i];
-    if (q < 0 || q >= n || ((o == OP_XX || o == OP_SWAP) && q + 1 >= n)) {
+    if (q < 0 || q >= n || (is_two_qubit(o) && q + 1 >= n)) {
       g_err = "gate on a qubit outside the register";
       return -3;
     }
@@ -183,6 +192,19 @@ int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const in
         for (int c = 0; c < t.r; ++c) {
           t.at(a, 0, c) *= std::conj(ph);
           t.at(a, 1, c) *= ph;
+        }
+      continue;
+    }
+    if (!is_two_qubit(o)) {  // Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
+      const double th = 0.5 * M_PI * alpha[i];
+      const double cs = std::cos(th), sn = std::sin(th);
+      const cd m01 = o == OP_RX ? cd(0.0, -sn) : cd(-sn, 0.0), m10 = o == OP_RX ? cd(0.0, -sn) : cd(sn, 0.0);
+      Tensor& t = A[q];
+      for (int a = 0; a < t.l; ++a)
+        for (int c = 0; c < t.r; ++c) {
+          const cd t0 = t.at(a, 0, c), t1 = t.at(a, 1, c);
+          t.at(a, 0, c) = cs * t0 + m01 * t1;
+          t.at(a, 1, c) = m10 * t0 + cs * t1;
         }
       continue;
     }
@@ -240,6 +262,28 @@ int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const in
     if (o == OP_SWAP) {
       for (int a = 0; a < l; ++a)
         for (int c = 0; c < r; ++c) std::swap(TH(a, 0, 1, c), TH(a, 1, 0, c));
+    } else if (o == OP_YY) {  // YYPhase: cos(th) 1 - i sin(th) Y(x)Y
+      const double th = 0.5 * M_PI * alpha[i];
+      const double cs = std::cos(th), sn = std::sin(th);
+      const cd pis(0.0, sn), mis(0.0, -sn);
+      for (int a = 0; a < l; ++a)
+        for (int c = 0; c < r; ++c) {
+          const cd t00 = TH(a, 0, 0, c), t01 = TH(a, 0, 1, c), t10 = TH(a, 1, 0, c), t11 = TH(a, 1, 1, c);
+          TH(a, 0, 0, c) = cs * t00 + pis * t11;
+          TH(a, 0, 1, c) = cs * t01 + mis * t10;
+          TH(a, 1, 0, c) = cs * t10 + mis * t01;
+          TH(a, 1, 1, c) = cs * t11 + pis * t00;
+        }
+    } else if (o == OP_ZZ) {  // ZZPhase: diag(e^-i th, e^i th, e^i th, e^-i th)
+      const double th = 0.5 * M_PI * alpha[i];
+      const cd ph(std::cos(th), std::sin(th)), phc = std::conj(ph);
+      for (int a = 0; a < l; ++a)
+        for (int c = 0; c < r; ++c) {
+          TH(a, 0, 0, c) *= phc;
+          TH(a, 0, 1, c) *= ph;
+          TH(a, 1, 0, c) *= ph;
+          TH(a, 1, 1, c) *= phc;
+        }
     } else {  // XXPhase: cos(th) 1 - i sin(th) X(x)X
       const double th = 0.5 * M_PI * alpha[i];
       const double cs = std::cos(th), sn = std::sin(th);

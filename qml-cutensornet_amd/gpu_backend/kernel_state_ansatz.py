@@ -26,13 +26,13 @@ from statistics import mean, median
 import numpy as np
 
 try:  # normal case: imported as qml_cutensornet_amd.gpu_backend.kernel_state_ansatz
-    from ..ansatz import KernelStateAnsatz  # noqa: F401
+    from ..ansatz import OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit  # noqa: F401
     from .. import engine as _engine
     from ..dist import assemble_gram, comm_allgather, exchange_sets
     from ..mps import MPS, simulate, simulate_many  # noqa: F401
 except ImportError:  # imported top-level as gpu_backend.kernel_state_ansatz
     import qml_cutensornet_amd as _pkg  # noqa: F401
-    from qml_cutensornet_amd.ansatz import KernelStateAnsatz  # noqa: F401
+    from qml_cutensornet_amd.ansatz import OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit  # noqa: F401
     from qml_cutensornet_amd import engine as _engine
     from qml_cutensornet_amd.dist import assemble_gram, comm_allgather, exchange_sets
     from qml_cutensornet_amd.mps import MPS, simulate, simulate_many  # noqa: F401
@@ -50,9 +50,10 @@ _PILOT_MIN_STATES = 24  # below this a share goes to the device builder as a who
 
 
 def _entangling_weight(circuit):
-    """Cost proxy of a circuit: sum of sin^2(pi alpha) over its XXPhase gates (alpha in half-turns: 0 and 1 do not
-    entangle).  The device builder orders its queue by the same quantity; it tracks the bonds a state will reach."""
-    xx = np.asarray(circuit.op) == 2
+    """Cost proxy of a circuit: sum of sin^2(pi alpha) over its XXPhase, YYPhase and ZZPhase gates (alpha in half-turns:
+    0 and 1 do not entangle).  The device builder orders its queue by the same quantity; it tracks the bonds a state will
+    reach."""
+    xx = np.isin(np.asarray(circuit.op), (OP_XX, OP_YY, OP_ZZ))
     return float((np.sin(np.pi * np.asarray(circuit.alpha)[xx]) ** 2).sum())
 
 
@@ -180,7 +181,8 @@ def _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, dev
     chi = int(os.environ.get("QK_MAX_BOND", "0")) or None
     which = os.environ.get("QK_BUILDER", "auto") if want_set else "host"  # auto | device | hybrid | host
     forced = which  # what the caller asked for: only a FORCED device build may fail the call
-    circuits = [ansatz.circuit_for_data(points[k, :]) for k in range(lo, hi)] if hi > lo else []
+    # an ansatz may return a BoundCircuit or a reference-style gate list (name, qubits, params)
+    circuits = [as_bound_circuit(ansatz.circuit_for_data(points[k, :]), ansatz) for k in range(lo, hi)] if hi > lo else []
     if which == "auto":
         try:
             which = _auto_builder(circuits, host_workers)

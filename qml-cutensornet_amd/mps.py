@@ -22,9 +22,10 @@ import numpy as np
 from scipy.linalg import qr as _qr
 from scipy.linalg import svd as _svd
 
-from .ansatz import OP_H, OP_RZ, OP_SWAP, OP_XX, BoundCircuit
+from .ansatz import OP_H, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_op_codes, is_two_qubit
 
 _SQRT_HALF = 0.7071067811865476
+_YY_SIGN = np.array([[1.0, -1.0], [-1.0, 1.0]])[None, :, :, None]  # c 1 - i s Y(x)Y: +i s on |00>,|11>, -i s on |01>,|10>
 
 
 class MPS:
@@ -164,6 +165,8 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
     block, count, fid = C.c_void_p(), C.c_int64(), C.c_double()
     rc = lib.qkb_simulate_chi(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
                               float(value_of_zero), int(max_bond or 0), dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid))
+    if rc == -7:  # an op code outside 0..7
+        raise ValueError(f"native MPS builder: {lib.qkb_last_error().decode()}")
     if rc != 0:
         raise RuntimeError(f"native MPS builder failed: {lib.qkb_last_error().decode()}")
     try:
@@ -324,6 +327,7 @@ def _use_native() -> bool:
 
 def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: float, max_bond: int | None = None) -> MPS:
     n = circuit.n_qubits
+    check_op_codes(circuit.op)
     budget = max(0.0, 1.0 - float(truncation_fidelity))
     A = []
     for _ in range(n):
@@ -333,7 +337,7 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
     ops = circuit.op.tolist()
     qs = circuit.q0.tolist()
     alphas = circuit.alpha.tolist()
-    two_q_pos = [q for o, q in zip(ops, qs) if o in (OP_XX, OP_SWAP)]
+    two_q_pos = [q for o, q in zip(ops, qs) if is_two_qubit(o)]
     fidelity = 1.0
     centre = 0  # sites < centre are left-orthonormal, sites > centre right-orthonormal
     g2 = 0  # running index into two_q_pos
@@ -350,6 +354,13 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             t[:, 0] *= ph.conjugate()
             t[:, 1] *= ph
             A[q] = t
+            continue
+        if not is_two_qubit(o):  # Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
+            th = 0.5 * np.pi * a
+            c, sn = np.cos(th), np.sin(th)
+            m01, m10 = (-1j * sn, -1j * sn) if o == OP_RX else (-sn, sn)
+            t = A[q]
+            A[q] = np.stack((c * t[:, 0] + m01 * t[:, 1], m10 * t[:, 0] + c * t[:, 1]), axis=1)
             continue
 
         # ---- two-qubit gate on (q, q+1): bring the orthogonality centre onto the pair
@@ -371,6 +382,13 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
         theta = np.tensordot(A[q], A[q + 1], axes=(2, 0))  # [l, p, p', r]
         if o == OP_SWAP:
             theta = theta.transpose(0, 2, 1, 3)
+        elif o == OP_YY:  # cos(th) 1 - i sin(th) Y(x)Y
+            th = 0.5 * np.pi * a
+            theta = np.cos(th) * theta + 1j * np.sin(th) * _YY_SIGN * theta[:, ::-1, ::-1, :]
+        elif o == OP_ZZ:  # diag(e^-i th, e^i th, e^i th, e^-i th)
+            th = 0.5 * np.pi * a
+            ph = np.exp(1j * th)
+            theta = theta * np.array([[ph.conjugate(), ph], [ph, ph.conjugate()]])[None, :, :, None]
         else:  # XXPhase: cos(th) 1 - i sin(th) X(x)X
             th = 0.5 * np.pi * a
             theta = np.cos(th) * theta - 1j * np.sin(th) * theta[:, ::-1, ::-1, :]
