@@ -22,8 +22,6 @@ struct QkRangeGuard {  // a roctx range (qk_range_push / qk_range_pop) that clos
     if (e_ != hipSuccess) return qk_fail(QK_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));  \
   } while (0)
 
-static constexpr int GMAX = 4;  // pairs per group of the group-sweep lab kernel (sizes its X/T scratch)
-
 struct qk_ctx {
   int device = 0;
   int num_cus = 0;
@@ -37,19 +35,8 @@ struct qk_ctx {
   size_t scratch_bytes = 0;
   unsigned long long* counter = nullptr;  // work-queue heads (QK_NQ_MAX of them, QK_QSTRIDE apart) + 2 x 4 tail clocks behind them
   bool tail_pending = false;
-  bool merge_sites = true;  // QK_MERGE (0 disables): the site-fused sweep walks the chain in merged steps of two sites (qk_device.h: SweepArgs.merge_steps)
   unsigned long long* prof = nullptr;  // 8 cycle sums of the diagnostic variant
-  int variant = 20;    // 20 = the shipped kernels.  Anything else exists only in libqklab.so (QK_VARIANT there: 17 = lean register-staged
-                       // sweep; 0, 2, 12, 13, 14, 16, 21, 23 = other kernels kept for A/B; 9, 19 = instrumented)
-  int wgs_per_cu = 2;  // resident workgroups per CU (QK_WGS_PER_CU)
-  bool wave_path = true;   // fp64 sets whose bonds are all <= 16 use the one-wave-per-pair register sweep (QK_WAVE=0 opts out)
-  bool wave2_ring = true;  // ... with its k-step groups prefetched through a per-wave LDS ring (QK_WAVE2=2: plain loads)
-  bool wave2_path = true;  // fp64 sets whose bonds are all <= 32 use the one-wave-per-pair sweep with 2 x 2 register tiles (QK_WAVE2=0 opts out)
-  bool small_path = true;  // sets whose bonds are all <= 32 use the LDS-resident small-bond sweep (QK_SMALL=0 opts out)
-  int fused_split = 1;  // sweep the plan's two runs of pairs with the two shapes of the site-fused kernel: 1 = when the share is long enough for two launches (default), 2 = always, 0 = one shape (QK_FUSED_SPLIT)
-  int fused_wgs = 0;       // workgroups per CU of the site-fused sweep: 0 = chosen per launch from the plan, 1 / 2 forced (QK_FUSED_WGS)
-  bool deterministic = false;  // QK_DETERMINISTIC=1: only kernels that add in a fixed order (no LDS atomics)
-  int fused_path = 1;      // fp64 sets with a bond > 32 use the site-fused sweep (QK_FUSED=0: ring sweep instead; 2: also for bonds 17..32)
+  QkSweepPolicy policy;  // the switches of the sweep's choice of kernels (qk_plan.h), set by ctx_init
   qk_stats last{};
   // the device MPS builder's per-workgroup arena and workspace, kept between calls (qk_build.hip)
   void* build_arena = nullptr;

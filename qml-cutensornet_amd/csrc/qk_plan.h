@@ -1,10 +1,13 @@
-// qk_plan.h -- the host-side plan of a Gram share (struct qk_plan) and the constants the planner shares with the launches.
+// qk_plan.h -- the host-side plan of a Gram share (struct qk_plan), the constants the planner shares with the launches, and the
+// choice of the sweep's launches for a plan (qk_choose_sweep).
 // Plain C++: no HIP type appears here, so the planner (qk_planner.cpp) also builds as a host-only translation unit
-// (tests/host_san: -fsanitize=address,undefined).
+// (tests/host_san: -fsanitize=address,undefined), and the choice is tested on the CPU (tests/host_san/choice_main.cpp).
 #pragma once
 #include "../../include/qkgram.h"
 
+#include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <vector>
 
 int qk_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));  // sets qk_last_error(), returns code
@@ -21,6 +24,7 @@ int qk_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3))
 static constexpr int QKF_XCAP_ONE = QKF_XCAP_ONE_V, QKF_XCAP_TWO = QKF_XCAP_TWO_V;  // elements of the fused sweep's LDS X buffer with one / two workgroups per CU
 static constexpr int QK_TILE = 16;                                        // M/N granule of v_mfma_f64_16x16x4_f64
 static inline int qk_pad16(int x) { return (x + QK_TILE - 1) / QK_TILE * QK_TILE; }
+static constexpr int GMAX = 4;  // pairs per group of the group-sweep lab kernel (sizes its X/T scratch)
 
 struct qk_ctx;
 
@@ -50,3 +54,142 @@ struct qk_plan {
   int32_t* d_pairs = nullptr;
   int32_t* d_groups = nullptr;
 };
+
+// ----------------------------------------------------------------------------------------
+// The choice of the sweep's launches (qk_gram_values).  Inline and static on purpose: experiment builds recompile qkgram.hip alone with
+// other QKF_XCAP_* / QKF_TWO_WGS, and the choice must see the constants of the translation unit that launches.
+// ----------------------------------------------------------------------------------------
+// the context's switches, read from the environment once per context (ctx_init) -- fused_dual and gang once per call (qk_gram_values)
+struct QkSweepPolicy {
+  int variant = 20;        // 20 = the shipped kernels.  Anything else exists only in libqklab.so (QK_VARIANT there: 17 = lean register-staged sweep; 0, 2, 12, 13, 14, 16, 21, 23 = other kernels kept for A/B; 9, 19 = instrumented)
+  int wgs_per_cu = 2;      // resident workgroups per CU (QK_WGS_PER_CU)
+  bool wave_path = true;   // fp64 sets whose bonds are all <= 16 use the one-wave-per-pair register sweep (QK_WAVE=0 opts out)
+  bool wave2_ring = true;  // ... with its k-step groups prefetched through a per-wave LDS ring (QK_WAVE2=2: plain loads)
+  bool wave2_path = true;  // fp64 sets whose bonds are all <= 32 use the one-wave-per-pair sweep with 2 x 2 register tiles (QK_WAVE2=0 opts out)
+  bool small_path = true;  // sets whose bonds are all <= 32 use the LDS-resident small-bond sweep (QK_SMALL=0 opts out)
+  int fused_path = 1;      // fp64 sets with a bond > 32 use the site-fused sweep (QK_FUSED=0: ring sweep instead; 2: also for bonds 17..32)
+  int fused_split = 1;     // sweep the plan's two runs of pairs with the two shapes of the site-fused kernel: 1 = when the share is long enough for two launches (default), 2 = always, 0 = one shape (QK_FUSED_SPLIT)
+  int fused_wgs = 0;       // workgroups per CU of the site-fused sweep: 0 = chosen per launch from the plan, 1 / 2 forced (QK_FUSED_WGS)
+  bool deterministic = false;  // QK_DETERMINISTIC=1: only kernels that add in a fixed order (no LDS atomics)
+  bool merge_sites = true;     // QK_MERGE (0 disables): the site-fused sweep walks the chain in merged steps of two sites (qk_device.h: SweepArgs.merge_steps)
+  bool fused_dual = true;      // QK_FUSED_DUAL (0: single tiles): the 12-wave site-fused shape in its dual form (pairs of tiles per wave)
+  bool gang = false;           // QK_GANG=1: gang start of the site-fused launches (qk_device.h: qk_gang_sync)
+};
+
+struct QkSetShape {  // what the choice needs of a set: its largest padded bond, bits of a real, sites
+  int max_pad = 0, precision = 64, n_sites = 0;
+};
+
+struct QkSweepRun {  // one launch
+  int kernel = QK_KERNEL_NONE;
+  long long grid = 0;
+  size_t lds = 0;                  // dynamic LDS bytes
+  long long first = 0, count = 0;  // pairs [first, first + count) of the plan's list
+  int nq = 1, gang_n = 0;          // SweepArgs
+  bool gang2 = false;              // its gang words lie behind the first launch's (the second launch of a split sweep)
+};
+
+struct QkSweepChoice {
+  int rc = QK_OK;  // else no launch, and err says why
+  char err[192] = {};
+  int n_runs = 0;  // 2: the plan's second class of pairs swept by a launch of its own, right behind the first (a split or mixed sweep)
+  QkSweepRun run[2];
+  long long launched_grid = 0;  // qk_stats.grid (a split or mixed sweep reports the whole share's grid)
+  long long x_plane = 0, t_plane = 0;  // SweepArgs
+  int turn_ints = 0;                   // SweepArgs
+  size_t scratch_bytes = 0;            // global X / T buffers of the launches
+  bool interleaved = false;   // the sweep reads the sets' interleaved images
+  bool fused_images = false;  // ... and the site-fused sweep's edge blocks and merged steps (as far as the plan's edge_k and merge_sites ask)
+  int queues = 1;             // qk_stats.queues (8: the plan's XCD queues)
+  bool tails = false;         // the launches record tail clocks
+};
+
+static inline QkSweepChoice qk_choose_sweep(const QkSweepPolicy& p, const qk_plan& plan, const QkSetShape& x, const QkSetShape& y, const int num_cus) {
+  QkSweepChoice ch;
+  const long long np = (long long)plan.pairs.size() / 2;
+  const bool f32 = x.precision == 32, quad = plan.quad, det = p.deterministic;
+  const int n = x.n_sites, max_pad = std::max(x.max_pad, y.max_pad);
+  // X/T scratch: the group sweep (lab) stacks GMAX pairs in one buffer, the duo sweep (lab) keeps two buffer sets, the quad kernel 2 stacked sets
+  const bool grouped = p.variant == 14 && !f32 && !quad, duo = p.variant == 16 && !f32 && !quad;
+  const long long chains = quad ? 4 : (duo ? 2 : 1);
+  const long long units = quad ? np / 4 : grouped ? (long long)plan.groups.size() / 2 : (duo ? (np + 1) / 2 : np);
+  ch.x_plane = (grouped ? GMAX : 1) * (long long)x.max_pad * y.max_pad, ch.t_plane = 2 * ch.x_plane;
+  // The site-fused sweep (qk_fused.h), fp64.  Two shapes: one 12-wave workgroup per CU (three waves per SIMD, two T slots each) with an 8192-element X buffer, or
+  // two 8-wave workgroups (four waves per SIMD, one slot) with 4608 elements each.  The second workgroup fills the first one's barriers and per-site set-up (+24 %
+  // on the 40-qubit x 4-layer set), but every site that does not fit the smaller buffer runs in strips from a global X.  A 16-row strip of X' must fit: bonds <= XCAP / 16.
+  ch.turn_ints = det ? (y.max_pad / QK_TILE) * (x.max_pad / QK_TILE) : 0;  // DET forms: turn counters per set = blocks of b' x blocks of a' of the largest site
+  const size_t lds_meta = 16 + 256 + (size_t)n * (48 + 16) + (det ? (size_t)(2 * ch.turn_ints + 2) * sizeof(int) : 0);  // queue slot, the overlap's accumulator, per-site records and tensor offsets, two sets of turn counters
+  const bool can_one = max_pad <= QKF_XCAP_ONE / QK_TILE && (size_t)QKF_XCAP_ONE * 16 + lds_meta <= 160 * 1024;
+  const bool can_two = max_pad <= QKF_XCAP_TWO / QK_TILE && (size_t)QKF_XCAP_TWO * 16 + lds_meta <= 160 * 1024 / QKF_TWO_WGS;
+  const bool fused = p.variant == 20 && !f32 && !quad && p.fused_path != 0 && max_pad > (p.fused_path >= 2 ? 16 : 32) && (can_one || can_two);
+  const bool second_class = fused && plan.n_first > 0 && plan.n_first < np;
+  // split: the plan's two runs of pairs with the two shapes (see qk_plan_create), only when the launch is free to choose its shape and the share is long enough -- a
+  // short launch ends with a tail of its own (a 1/8 share of the 60-qubit x 6-layer Gram, 61 pairs per CU: two launches 47.2 ms, ONE launch of the 12-wave dual shape
+  // 47.1 ms: profiles/r04/share_times_cfg4.txt), so below 100 pairs per CU the share is one launch
+  const bool split = second_class && can_one && can_two && p.fused_wgs == 0 && p.fused_split != 0 && !plan.second_wave2 && (p.fused_split == 2 || np >= 100ll * num_cus);
+  // mixed: the plan's second run holds the pairs of two small states (every bond <= 32) for the one-wave sweep
+  const bool mixed = second_class && plan.second_wave2 && p.wave2_path && p.wave2_ring;
+  // one class of pairs: the two-workgroup shape when the work sits in sites that fit its buffer AND most of it in sites of at most the narrow
+  // size -- from about 4 x 4 tiles per site the 12-wave dual shape is the faster one although the site would still fit (tools/uniform_ab.py)
+  const bool fused_two = fused && can_two && !split && (!can_one || p.fused_wgs == 2 || (p.fused_wgs == 0 && plan.fit_two >= 0.75 && plan.fit_narrow >= 0.5));
+  // the dual form (pairs of tiles per wave) against single tiles, uniform bonds 48 / 64 / 96 / 128 / 256: +2 / +4 / +7 / +12 / +19 %
+  const bool dual = fused && !fused_two && p.fused_dual;
+  const int wgs = fused ? (fused_two ? QKF_TWO_WGS : 1) : p.wgs_per_cu;
+  const long long grid = std::min(units, (long long)wgs * num_cus);
+  ch.scratch_bytes = (size_t)(split ? 2ll * num_cus : grid) * (size_t)chains * 2 * (size_t)(ch.x_plane + ch.t_plane) * sizeof(double);
+  // per-pair site metadata in LDS behind the ring's three slots or the small-bond sweep's X and T: 4 (n+1) ints + 2 n int64 (+ alignment)
+  const size_t site_meta = 16 + (size_t)(4 * (n + 1) + 2) * sizeof(int) + (size_t)2 * n * sizeof(long long);
+  const size_t lds_ring = 3 * 16 * 1024 + site_meta;
+  const size_t esz = f32 ? sizeof(float) : sizeof(double), lds_small = (size_t)(3 * 2 * (64 / esz) * 64 + 6 * 32 * 32) * esz + site_meta;
+  if (lds_ring > 80 * 1024)
+    return ch.rc = QK_EINVAL, snprintf(ch.err, sizeof ch.err, "qk_gram_values: %d sites need %zu bytes of LDS per workgroup (limit 80 KiB for 2 workgroups per CU)", n, lds_ring), ch;
+  QkSweepRun& r = ch.run[0];
+  ch.n_runs = 1, ch.launched_grid = r.grid = grid, r.count = np;
+  if (quad) {  // 2x2 blocks of pairs per workgroup (QK_PLAN_QUADS plans): an experimental kernel of the lab library
+#ifdef QK_LAB
+    r.kernel = QK_KERNEL_LAB;
+#else
+    ch.rc = QK_EINVAL, snprintf(ch.err, sizeof ch.err, "qk_gram_values: QK_PLAN_QUADS plans are swept by an experimental kernel that only libqklab.so contains");
+#endif
+  } else if (p.variant == 20 && p.wave_path && !f32 && max_pad <= 16) {
+    // every bond <= 16: a pair lives in the registers of one wavefront (qk_sweep_wave_kernel); 16 waves per CU
+    r.kernel = QK_KERNEL_WAVE, ch.launched_grid = r.grid = std::min(np, 16ll * num_cus);
+  } else if (!fused && p.variant == 20 && p.wave2_path && (!f32 || p.wave2_ring) && max_pad <= 32) {
+    // every bond <= 32: a pair lives in the registers of one wavefront as 2 x 2 tiles (qk_sweep_wave2_kernel); 8 waves per CU
+    r.kernel = (f32 || p.wave2_ring) ? QK_KERNEL_WAVE2 : QK_KERNEL_WAVE2_PLAIN, ch.launched_grid = r.grid = std::min(np, 8ll * num_cus);
+    ch.interleaved = ch.tails = true, ch.queues = plan.nq > 1 ? 8 : 1, r.nq = plan.nq;
+  } else if (!fused && p.variant == 20 && p.small_path && max_pad <= 32 && lds_small <= 80 * 1024) {
+    // every bond <= 32: X and T stay in LDS, only the site tensors stream (qk_sweep_small_kernel); longer chains (several hundred sites) take the ring kernel below
+    r.kernel = QK_KERNEL_SMALL, r.lds = lds_small;
+  } else if (fused) {
+    // X in LDS, T in registers, site tensors read straight into MFMA fragments from the interleaved image
+    ch.interleaved = ch.fused_images = ch.tails = true, ch.queues = plan.nq > 1 ? 8 : 1, r.nq = plan.nq;
+    r.kernel = fused_two ? (det ? QK_KERNEL_FUSED2_DET : QK_KERNEL_FUSED2) : dual ? (det ? QK_KERNEL_FUSED_DUAL_DET : QK_KERNEL_FUSED_DUAL) : (det ? QK_KERNEL_FUSED1_DET : QK_KERNEL_FUSED1);
+    r.lds = (size_t)(fused_two ? QKF_XCAP_TWO : QKF_XCAP_ONE) * 16 + lds_meta;
+    // gang start: the workgroups of an XCD begin their pairs together; workgroups per XCD = grid / 8 (round-robin dispatch)
+    auto gang_of = [&](const long long g) { return p.gang && plan.nq > 1 && g >= 16 && g % 8 == 0 ? (int)(g / 8) : 0; };
+    if (split || mixed) {  // the first class with the shape above, then the second class, back to back on the stream; 8 queues per class
+      QkSweepRun& r2 = ch.run[1];
+      ch.n_runs = 2;
+      r.count = plan.n_first, r2.first = plan.n_first, r2.count = np - plan.n_first;
+      r.nq = r2.nq = plan.nq > 1 ? 8 : plan.nq;
+      r.grid = std::min(r.count, (long long)wgs * num_cus);
+      if (split) {  // pairs whose sites fit the smaller LDS buffer: two 8-wave workgroups per CU
+        r2.kernel = det ? QK_KERNEL_FUSED2_DET : QK_KERNEL_FUSED2, r2.grid = std::min(r2.count, (long long)QKF_TWO_WGS * num_cus);
+        r2.lds = (size_t)QKF_XCAP_TWO * 16 + lds_meta, r2.gang_n = gang_of(r2.grid), r2.gang2 = true;
+      } else {  // pairs of two small states: the one-wave sweep
+        r2.kernel = QK_KERNEL_WAVE2, r2.grid = std::min(r2.count, 8ll * num_cus);
+      }
+    }
+    r.gang_n = gang_of(r.grid);
+  } else if (f32 || p.variant == 20) {  // the ring sweep: LDS-DMA staging ring (K-tile 8, three slots) + 3M complex product; complex64 sets too
+    r.kernel = QK_KERNEL_RING, r.lds = lds_ring;
+  } else {  // experimental / diagnostic kernels (qk_lab.hip, libqklab.so only)
+#ifdef QK_LAB
+    r.kernel = QK_KERNEL_LAB;
+#else
+    ch.rc = QK_EINVAL, snprintf(ch.err, sizeof ch.err, "qk_gram_values: no kernel for this call");
+#endif
+  }
+  return ch;
+}

@@ -179,31 +179,10 @@ extern "C" int qk_pack_state(int32_t n_sites, const int32_t* bond_dims, const do
 #define QKF_KERNEL_ONE_DET qk_sweep_fused_kernel<QKF_ONE_NW, QKF_ONE_S, QKF_XCAP_ONE, QKF_ONE_WPS, true>
 #define QKF_KERNEL_TWO_DET qk_sweep_fused_kernel<QKF_TWO_NW, QKF_TWO_S, QKF_XCAP_TWO, QKF_TWO_WPS, true>
 #define QKF_KERNEL_DUAL_DET qk_sweep_fused_dual_kernel<QKF_DUAL_NW, QKF_XCAP_ONE, QKF_DUAL_WPS, true>
-// launch one of the three shapes in its plain or DET form
-#define QKF_LAUNCH_ONE(det, grid_, lds_, args_)                                                                      \
-  do {                                                                                                               \
-    if (det) QKF_KERNEL_ONE_DET<<<dim3((unsigned)(grid_)), dim3(64 * QKF_ONE_NW), (lds_), c->stream>>>(args_);       \
-    else QKF_KERNEL_ONE<<<dim3((unsigned)(grid_)), dim3(64 * QKF_ONE_NW), (lds_), c->stream>>>(args_);               \
-  } while (0)
-#define QKF_LAUNCH_TWO(det, grid_, lds_, args_)                                                                      \
-  do {                                                                                                               \
-    if (det) QKF_KERNEL_TWO_DET<<<dim3((unsigned)(grid_)), dim3(64 * QKF_TWO_NW), (lds_), c->stream>>>(args_);       \
-    else QKF_KERNEL_TWO<<<dim3((unsigned)(grid_)), dim3(64 * QKF_TWO_NW), (lds_), c->stream>>>(args_);               \
-  } while (0)
 #if QKF_QUAD  // (lab builds: lab/qk_quad.h, 2 x 2 tiles per wave, 8 waves at two per SIMD)
 #define QKF_QUAD_NW 8
-#define QKF_QUAD_WPS 2
-#define QKF_KERNEL_QUAD qk_sweep_fused_quad_kernel<QKF_QUAD_NW, QKF_XCAP_ONE, QKF_QUAD_WPS>
-#else
-#define QKF_QUAD_NW QKF_DUAL_NW
-#define QKF_KERNEL_QUAD QKF_KERNEL_DUAL
+#define QKF_KERNEL_QUAD qk_sweep_fused_quad_kernel<QKF_QUAD_NW, QKF_XCAP_ONE, 2>
 #endif
-#define QKF_LAUNCH_DUAL(det, grid_, lds_, args_)                                                                     \
-  do {                                                                                                               \
-    if (det) QKF_KERNEL_DUAL_DET<<<dim3((unsigned)(grid_)), dim3(64 * QKF_DUAL_NW), (lds_), c->stream>>>(args_);     \
-    else if (QKF_QUAD) QKF_KERNEL_QUAD<<<dim3((unsigned)(grid_)), dim3(64 * QKF_QUAD_NW), (lds_), c->stream>>>(args_); \
-    else QKF_KERNEL_DUAL<<<dim3((unsigned)(grid_)), dim3(64 * QKF_DUAL_NW), (lds_), c->stream>>>(args_);             \
-  } while (0)
 
 extern "C" int qk_plan_destroy(qk_plan* plan) {
   if (!plan) return QK_OK;
@@ -423,38 +402,37 @@ static int ctx_init(qk_ctx* c, int device_id, int num_cus) {
   HIP_TRY(hipMalloc(&c->counter, (QK_NQ_MAX * QK_QSTRIDE + 8 + 2 * 8 * QK_QSTRIDE) * sizeof(unsigned long long)));  // queue heads (8 per launch of a split sweep), tail clocks
   HIP_TRY(hipMalloc(&c->prof, 8 * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(c->prof, 0, 8 * sizeof(unsigned long long)));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qk_sweep_ring_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qk_sweep_ring_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qk_sweep_small_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qk_sweep_small_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(QKF_KERNEL_ONE), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(QKF_KERNEL_TWO), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / QKF_TWO_WGS));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(QKF_KERNEL_DUAL), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  // the dynamic LDS the sweep kernels may ask for: 80 KiB (two workgroups per CU), a whole CU's 160 KiB, or its share per workgroup of the small-site shape
+  for (const void* k : {(const void*)qk_sweep_ring_kernel<float>, (const void*)qk_sweep_ring_kernel<double>, (const void*)qk_sweep_small_kernel<double>, (const void*)qk_sweep_small_kernel<float>})
+    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+  for (const void* k : {(const void*)QKF_KERNEL_ONE, (const void*)QKF_KERNEL_DUAL, (const void*)QKF_KERNEL_ONE_DET, (const void*)QKF_KERNEL_DUAL_DET})
+    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  for (const void* k : {(const void*)QKF_KERNEL_TWO, (const void*)QKF_KERNEL_TWO_DET}) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / QKF_TWO_WGS));
+#if QKF_QUAD
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(QKF_KERNEL_QUAD), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(QKF_KERNEL_ONE_DET), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(QKF_KERNEL_TWO_DET), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / QKF_TWO_WGS));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(QKF_KERNEL_DUAL_DET), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#endif
+  QkSweepPolicy& p = c->policy;
 #ifdef QK_LAB  // libqklab.so only: the experimental kernels of qk_lab.hip, selectable with QK_VARIANT
   {
     const int rc = qk_lab_init(c);
     if (rc != QK_OK) return rc;
   }
-  if (const char* v = std::getenv("QK_VARIANT")) c->variant = std::atoi(v);
+  if (const char* v = std::getenv("QK_VARIANT")) p.variant = std::atoi(v);
 #endif
-  if (const char* v = std::getenv("QK_SMALL")) c->small_path = std::atoi(v) != 0;
-  if (const char* v = std::getenv("QK_WAVE")) c->wave_path = std::atoi(v) != 0;
-  if (const char* v = std::getenv("QK_WAVE2")) c->wave2_path = std::atoi(v) != 0, c->wave2_ring = std::atoi(v) != 2;
-  if (const char* v = std::getenv("QK_FUSED")) c->fused_path = std::atoi(v);
-  if (const char* v = std::getenv("QK_MERGE")) c->merge_sites = std::atoi(v) != 0;
+  if (const char* v = std::getenv("QK_SMALL")) p.small_path = std::atoi(v) != 0;
+  if (const char* v = std::getenv("QK_WAVE")) p.wave_path = std::atoi(v) != 0;
+  if (const char* v = std::getenv("QK_WAVE2")) p.wave2_path = std::atoi(v) != 0, p.wave2_ring = std::atoi(v) != 2;
+  if (const char* v = std::getenv("QK_FUSED")) p.fused_path = std::atoi(v);
+  if (const char* v = std::getenv("QK_MERGE")) p.merge_sites = std::atoi(v) != 0;
   // QK_DETERMINISTIC=1: bit-reproducible Grams.  By default the site-fused sweep sums the tiles of a column with LDS atomics in arrival
   // order (two launches on the same inputs differ in the last bits, <= 9e-16); in this mode it takes its DET forms, which add in a fixed
   // order (qk_fused.h: qkf_turn_add); the ring sweep, the small-bond sweep and the one-wave sweeps add in a fixed order anyway.  The order
   // in which workgroups pull pairs never matters (a pair's result does not depend on the workgroup that sweeps it).
   if (const char* v = std::getenv("QK_DETERMINISTIC"))
-    if (std::atoi(v) != 0) c->deterministic = true;
-  if (const char* v = std::getenv("QK_FUSED_SPLIT")) c->fused_split = std::max(0, std::min(2, std::atoi(v)));
-  if (const char* v = std::getenv("QK_FUSED_WGS")) c->fused_wgs = std::max(0, std::min(2, std::atoi(v)));
-  if (const char* v = std::getenv("QK_WGS_PER_CU")) c->wgs_per_cu = std::max(1, std::min(4, std::atoi(v)));
+    if (std::atoi(v) != 0) p.deterministic = true;
+  if (const char* v = std::getenv("QK_FUSED_SPLIT")) p.fused_split = std::max(0, std::min(2, std::atoi(v)));
+  if (const char* v = std::getenv("QK_FUSED_WGS")) p.fused_wgs = std::max(0, std::min(2, std::atoi(v)));
+  if (const char* v = std::getenv("QK_WGS_PER_CU")) p.wgs_per_cu = std::max(1, std::min(4, std::atoi(v)));
   return QK_OK;
 }
 
@@ -813,20 +791,76 @@ static int ensure_merged(qk_ctx* c, qk_mps_set* m, const int k) {
 
 static int ensure_plan_uploaded(qk_ctx* c, qk_plan* p) {
   if (p->d_pairs && p->up_ctx == c) return QK_OK;
-  if (p->d_pairs) {
-    (void)hipFree(p->d_pairs);
-    p->d_pairs = nullptr;
-  }
-  if (p->d_groups) {
-    (void)hipFree(p->d_groups);
-    p->d_groups = nullptr;
-  }
+  if (p->d_pairs) (void)hipFree(p->d_pairs);
+  if (p->d_groups) (void)hipFree(p->d_groups);
+  p->d_pairs = nullptr, p->d_groups = nullptr;
   if (p->pairs.empty()) return QK_OK;
   HIP_TRY(hipMalloc(&p->d_pairs, p->pairs.size() * sizeof(int32_t)));
   HIP_TRY(hipMemcpy(p->d_pairs, p->pairs.data(), p->pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMalloc(&p->d_groups, p->groups.size() * sizeof(int32_t)));
   HIP_TRY(hipMemcpy(p->d_groups, p->groups.data(), p->groups.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   p->up_ctx = c;
+  return QK_OK;
+}
+
+// the site-fused sweep's derived images of the two sets (edge blocks, merged steps) as the plan asks for them, into the launch's arguments
+static int derive_fused_images(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set* ys, const qk_plan* plan, const bool merge_sites, SweepArgs& a) {
+  // the ends of the chain from the sets' edge blocks: k chosen by the planner -- unless a set already holds blocks for another k
+  // (made for an earlier plan, e.g. the training Gram before the test Gram on the same X): any k gives the same overlaps and the
+  // model's choices lie within 0.5 % of each other, so the set keeps the k of its first use instead of being rebuilt per call
+  int ek = plan->edge_k, rc = QK_OK;
+  if (ek > 0) {
+    if (xs->edge_k > 0 && (ys == xs || ys->edge_k == 0 || ys->edge_k == xs->edge_k)) ek = xs->edge_k;
+    else if (xs->edge_k == 0 && ys->edge_k > 0) ek = ys->edge_k;
+    for (const qk_mps_set* m : {xs, ys})
+      if ((rc = ensure_edges(c, const_cast<qk_mps_set*>(m), ek)) != QK_OK) return rc;
+    a.xedge = xs->d_edge, a.xedge_offs = xs->d_edge_offs, a.yedge = ys->d_edge, a.yedge_offs = ys->d_edge_offs, a.edge_k = ek;
+  }
+  if (merge_sites && xs->n_sites - 2 * ek >= 2) {  // the chain's sites contracted in twos: a workgroup picks per pair and step
+    for (const qk_mps_set* m : {xs, ys})
+      if ((rc = ensure_merged(c, const_cast<qk_mps_set*>(m), ek)) != QK_OK) return rc;
+    a.xmg = xs->d_mg, a.xmg_offs = xs->d_mg_offs, a.ymg = ys->d_mg, a.ymg_offs = ys->d_mg_offs, a.merge_steps = xs->mg_steps;
+  }
+#ifdef QK_LAB  // TIMING EXPERIMENT (wrong results): every tensor read from the first MiB of its image -- what would perfect L2 hits buy?
+  if (const char* v = std::getenv("QK_DEBUG_ALIAS")) {
+    const long long win = std::atoll(v);  // window in doubles (e.g. 131072 = 1 MiB)
+    if (win > 0) {
+      auto fold = [&](const int64_t* src, const long long n) -> const int64_t* {
+        int64_t* dst = nullptr;
+        if (hipMalloc(&dst, (size_t)n * sizeof(int64_t)) != hipSuccess) return src;  // (leaked: experiment)
+        qk_lab_fold_kernel<<<dim3(256), dim3(256), 0, c->stream>>>(src, dst, n, win);
+        return dst;
+      };
+      a.xoffs = fold(a.xoffs, (long long)xs->n_states * xs->n_sites), a.yoffs = fold(a.yoffs, (long long)ys->n_states * ys->n_sites);
+      if (a.merge_steps > 0)
+        a.xmg_offs = fold(a.xmg_offs, (long long)xs->n_states * xs->mg_steps), a.ymg_offs = fold(a.ymg_offs, (long long)ys->n_states * ys->mg_steps);
+    }
+  }
+#endif
+  return QK_OK;
+}
+
+// one launch of a product sweep kernel (QK_KERNEL_*; f32: the set's planes are complex64)
+static int launch_sweep(const int kernel, const bool f32, const long long grid_, const size_t lds, const hipStream_t s, const SweepArgs& a) {
+  const dim3 grid((unsigned)grid_);
+  switch (kernel) {
+    case QK_KERNEL_WAVE: qk_sweep_wave_kernel<0><<<grid, dim3(64), lds, s>>>(a); break;
+    case QK_KERNEL_WAVE2: if (f32) qk_sweep_wave2_kernel<3, float><<<grid, dim3(64), lds, s>>>(a); else qk_sweep_wave2_kernel<3, double><<<grid, dim3(64), lds, s>>>(a); break;  // (an fp32 set: complex64 storage, fp64 arithmetic)
+    case QK_KERNEL_WAVE2_PLAIN: qk_sweep_wave2_kernel<0, double><<<grid, dim3(64), lds, s>>>(a); break;
+    case QK_KERNEL_SMALL: if (f32) qk_sweep_small_kernel<float><<<grid, dim3(512), lds, s>>>(a); else qk_sweep_small_kernel<double><<<grid, dim3(512), lds, s>>>(a); break;
+    case QK_KERNEL_RING: if (f32) qk_sweep_ring_kernel<float><<<grid, dim3(512), lds, s>>>(a); else qk_sweep_ring_kernel<double><<<grid, dim3(512), lds, s>>>(a); break;  // (complex64 sweep of an fp32 set: SURVEY 8f N4)
+    case QK_KERNEL_FUSED1: QKF_KERNEL_ONE<<<grid, dim3(64 * QKF_ONE_NW), lds, s>>>(a); break;
+    case QK_KERNEL_FUSED1_DET: QKF_KERNEL_ONE_DET<<<grid, dim3(64 * QKF_ONE_NW), lds, s>>>(a); break;
+    case QK_KERNEL_FUSED2: QKF_KERNEL_TWO<<<grid, dim3(64 * QKF_TWO_NW), lds, s>>>(a); break;
+    case QK_KERNEL_FUSED2_DET: QKF_KERNEL_TWO_DET<<<grid, dim3(64 * QKF_TWO_NW), lds, s>>>(a); break;
+#if QKF_QUAD  // lab builds: the quad form stands in for the plain dual form
+    case QK_KERNEL_FUSED_DUAL: QKF_KERNEL_QUAD<<<grid, dim3(64 * QKF_QUAD_NW), lds, s>>>(a); break;
+#else
+    case QK_KERNEL_FUSED_DUAL: QKF_KERNEL_DUAL<<<grid, dim3(64 * QKF_DUAL_NW), lds, s>>>(a); break;
+#endif
+    case QK_KERNEL_FUSED_DUAL_DET: QKF_KERNEL_DUAL_DET<<<grid, dim3(64 * QKF_DUAL_NW), lds, s>>>(a); break;
+    default: return fail(QK_EINVAL, "qk_gram_values: no kernel for this call");
+  }
   return QK_OK;
 }
 
@@ -841,252 +875,83 @@ extern "C" int qk_gram_values(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set*
   HIP_TRY(hipSetDevice(c->device));
   const long long np = (long long)plan->pairs.size() / 2;
   c->last = plan->stats;
-  c->split_pending = false;
+  c->split_pending = c->tail_pending = false;
   c->last.max_bond = std::max(xs->max_pad, ys->max_pad);
-  c->last.kernel_ms = 0;
-  c->last.grid = 0;
-  c->last.kernel = QK_KERNEL_NONE;
-  c->last.precision = xs->precision;
+  c->last.kernel_ms = 0, c->last.grid = 0, c->last.kernel = QK_KERNEL_NONE, c->last.precision = xs->precision;
   if (np == 0) return QK_OK;
   int rc = ensure_plan_uploaded(c, plan);
   if (rc != QK_OK) return rc;
-
   if (xs->precision != ys->precision) return fail(QK_EINVAL, "qk_gram_values: the two sets differ in precision (fp%d, fp%d)", xs->precision, ys->precision);
   const bool f32 = (xs->precision == 32);
   if (f32) c->last.bytes *= 0.5;  // complex64 planes
-  const bool quad = plan->quad;
-  const bool grouped = (c->variant == 14) && !f32 && !quad;
-  const bool duo = (c->variant == 16) && !f32 && !quad;
-  const long long members = grouped ? GMAX : 1;        // pairs stacked in one X/T buffer (the quad kernel doubles the planes itself)
-  const long long chains = quad ? 4 : (duo ? 2 : 1);  // X/T buffer sets per workgroup (quad: 2 stacked sets = 4 single ones)
-  const long long x_plane = members * xs->max_pad * ys->max_pad;
-  const long long t_plane = 2 * x_plane;
-  const long long units = quad ? np / 4 : grouped ? (long long)plan->groups.size() / 2 : (duo ? (np + 1) / 2 : np);
-  const int max_pad = std::max(xs->max_pad, ys->max_pad);
-  // the site-fused sweep (qk_fused.h), fp64.  Two shapes: one 12-wave workgroup per CU (three waves per SIMD, two T slots
-  // each) with an 8192-element X buffer, or two 8-wave workgroups (four waves per SIMD, one slot) with 4608 elements each.  The second workgroup fills the first one's barriers and per-site set-up
-  // (+24 % on the 40-qubit x 4-layer set), but every site that does not fit the smaller buffer runs in strips from a global
-  // X: on the 60-qubit x 6-layer headline set (57 % of the work fits) the two shapes are within 2 % in time while the
-  // smaller buffer moves 3.2 instead of 1.9 TB through the fabric -- so two workgroups only when >= 75 % of the padded
-  // work fits.  A 16-row strip of X' must fit the buffer: bonds <= XCAP / 16.
-  const bool det = c->deterministic;
-  const int turn_ints = det ? (ys->max_pad / TILE) * (xs->max_pad / TILE) : 0;  // DET forms: turn counters per set = blocks of b' x blocks of a' of the largest site
-  const size_t lds_meta = 16 + 256 + (size_t)xs->n_sites * (48 + 16) + (det ? (size_t)(2 * turn_ints + 2) * sizeof(int) : 0);  // queue slot, the overlap's accumulator, per-site records and tensor offsets, two sets of turn counters
-  const bool fused_ok = c->variant == 20 && !f32 && !quad && c->fused_path != 0 && max_pad > (c->fused_path >= 2 ? 16 : 32);
-  const bool can_one = max_pad <= QKF_XCAP_ONE / TILE && (size_t)QKF_XCAP_ONE * 16 + lds_meta <= 160 * 1024;
-  const bool can_two = max_pad <= QKF_XCAP_TWO / TILE && (size_t)QKF_XCAP_TWO * 16 + lds_meta <= 160 * 1024 / QKF_TWO_WGS;
-  const bool fused = fused_ok && (can_one || can_two);
-  // two runs of pairs, two shapes (see qk_plan_create): only when the launch is free to choose its shape
-  // ... and the share is long enough: a short launch ends with a tail of its own (at a 1/8 share of the 60-qubit x 6-layer Gram, 61 pairs per
-  // CU: two launches 47.2 ms with 2.3 % of the sweep spent draining -- 1.5 % / 7.3 % of the two launches --, ONE launch of the 12-wave dual
-  // shape 47.1 ms with 0.6 %: profiles/r04/share_times_cfg4.txt), so below 100 pairs per CU the whole share is one launch
-  const bool two_runs = fused && can_one && can_two && c->fused_wgs == 0 && c->fused_split != 0 && !plan->second_wave2 && plan->n_first > 0 && plan->n_first < np && (c->fused_split == 2 || np >= 100ll * c->num_cus);
-  // a mixed set: the plan's second run holds the pairs of two small states (every bond <= 32) for the one-wave sweep
-  const bool mixed = fused && plan->second_wave2 && c->wave2_path && c->wave2_ring && plan->n_first > 0 && plan->n_first < np;
-  // One class of pairs: the two-workgroup shape when the work sits in sites that fit its buffer AND most of it in sites of at most
-  // the narrow size -- from about 4 x 4 tiles per site on the 12-wave dual shape is the faster one although the site would still fit
-  // (uniform chains of bond 64, i.e. what a bond cap of 64 produces: dual against two workgroups measured in tools/uniform_ab.py)
-  const bool fused_two = fused && can_two && !two_runs && (!can_one || c->fused_wgs == 2 || (c->fused_wgs == 0 && plan->fit_two >= 0.75 && plan->fit_narrow >= 0.5));
-  const size_t lds_fused = (size_t)(fused_two ? QKF_XCAP_TWO : QKF_XCAP_ONE) * 16 + lds_meta;
-  const int grid = (int)std::min<long long>(units, (long long)(fused ? (fused_two ? QKF_TWO_WGS : 1) : c->wgs_per_cu) * c->num_cus);
-  const char* dual_env = std::getenv("QK_FUSED_DUAL");
-  // the 12-wave shape comes in two forms; the dual one (pairs of tiles per wave) is the default (QK_FUSED_DUAL=0: single tiles)
-  const bool dual = fused && !fused_two && (dual_env ? std::atoi(dual_env) != 0 : true);
-  const bool split = two_runs;
-  const size_t need = (size_t)(split ? 2 * c->num_cus : grid) * (size_t)chains * 2 * (size_t)(x_plane + t_plane) * sizeof(double);
-  if (need > c->scratch_bytes) {
+
+  QkSweepPolicy pol = c->policy;  // two of the switches are read per call
+  if (const char* v = std::getenv("QK_FUSED_DUAL")) pol.fused_dual = std::atoi(v) != 0;
+  if (const char* v = std::getenv("QK_GANG")) pol.gang = std::atoi(v) != 0;
+  const QkSweepChoice ch = qk_choose_sweep(pol, *plan, {xs->max_pad, xs->precision, xs->n_sites}, {ys->max_pad, ys->precision, ys->n_sites}, c->num_cus);
+  if (ch.rc != QK_OK) return fail(ch.rc, "%s", ch.err);
+  c->last.queues = ch.queues, c->last.tail_frac = c->last.second_tail_frac = 0;
+  if (ch.scratch_bytes > c->scratch_bytes) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->scratch) HIP_TRY(hipFree(c->scratch));
     c->scratch = nullptr, c->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&c->scratch, need));
-    c->scratch_bytes = need;
+    HIP_TRY(hipMalloc(&c->scratch, ch.scratch_bytes));
+    c->scratch_bytes = ch.scratch_bytes;
   }
-  SweepArgs a;
+  SweepArgs a{};  // (what is not set here is null / zero)
   a.xdata = xs->d_data, a.xdims = xs->d_dims, a.xtrue = xs->d_true, a.xoffs = xs->d_offs;
   a.ydata = ys->d_data, a.ydims = ys->d_dims, a.ytrue = ys->d_true, a.yoffs = ys->d_offs;
   a.n_sites = xs->n_sites;
   a.pairs = plan->d_pairs, a.npairs = np;
   a.groups = plan->d_groups, a.ngroups = (long long)plan->groups.size() / 2;
   a.values = values_dev, a.z = z_dev;
-  a.scratch = c->scratch, a.x_plane = x_plane, a.t_plane = t_plane;
-  a.xedge = a.yedge = nullptr, a.xedge_offs = a.yedge_offs = nullptr, a.edge_k = 0;
-  a.xmg = a.ymg = nullptr, a.xmg_offs = a.ymg_offs = nullptr, a.merge_steps = 0;
-  a.turn_ints = turn_ints;
-  a.counter = c->counter;
-  a.nq = 1;  // kernels with XCD queues (site-fused, wave2) get the plan's queues below
+  a.scratch = c->scratch, a.x_plane = ch.x_plane, a.t_plane = ch.t_plane, a.turn_ints = ch.turn_ints;
+  a.counter = c->counter, a.prof = c->prof;
   for (int s_ = 0; s_ <= QK_NQ_MAX; ++s_) a.qstart[s_] = plan->nq > 1 ? plan->qstart[s_] : (s_ == 0 ? 0 : np);
-  // device clocks for the tail accounting, behind the queue heads: launch 1 uses [0] [1] [4], launch 2 [2] [3] [6]
-  unsigned long long* const tail = c->counter + QK_NQ_MAX * QK_QSTRIDE;
-  a.tail = tail;
-  a.err = tail + 7;
-  a.prof = c->prof;
-  a.debug_flags = 0, a.prio_mode = 0;
-  a.gang = c->counter + QK_NQ_MAX * QK_QSTRIDE + 8, a.gang_n = 0;  // (the gang start of the site-fused launches: set where they are launched)
+  // device clocks for the tail accounting behind the queue heads (launch 1 uses [0] [1] [4], launch 2 [2] [3] [6]), the DET error word, the gang words
+  a.tail = c->counter + QK_NQ_MAX * QK_QSTRIDE, a.err = a.tail + 7, a.gang = a.tail + 8;
 #ifdef QK_LAB  // timing experiments of the lab kernels (they give wrong results by construction): libqklab.so only
   if (const char* v = std::getenv("QK_DEBUG_FLAGS")) a.debug_flags = std::atoi(v);
   if (const char* v = std::getenv("QK_PRIO")) a.prio_mode = std::atoi(v);
 #endif
   HIP_TRY(hipEventRecord(c->ev_d, c->stream));
   HIP_TRY(hipMemsetAsync(c->counter, 0, (QK_NQ_MAX * QK_QSTRIDE + 8 + 2 * 8 * QK_QSTRIDE) * sizeof(unsigned long long), c->stream));
-  HIP_TRY(hipMemsetAsync(tail, 0xFF, 4 * sizeof(unsigned long long), c->stream));  // the four minima
-  c->last.queues = 1, c->last.tail_frac = c->last.second_tail_frac = 0;
-  c->tail_pending = false;
+  HIP_TRY(hipMemsetAsync(a.tail, 0xFF, 4 * sizeof(unsigned long long), c->stream));  // the four minima
+  // the sets' derived images (made on their first use): between ev_d and ev0, not part of the sweep
+  if (ch.interleaved) {
+    for (const qk_mps_set* m : {xs, ys})
+      if ((rc = ensure_interleaved(c, const_cast<qk_mps_set*>(m))) != QK_OK) return rc;
+    a.xdata = xs->d_il, a.ydata = ys->d_il;
+  }
+  if (ch.fused_images && (rc = derive_fused_images(c, xs, ys, plan, pol.merge_sites, a)) != QK_OK) return rc;
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  int launched_grid = grid;
-  // per-pair site metadata in LDS behind the three ring slots: 4 (n+1) ints + 2 n int64 (+ alignment)
-  const size_t lds_ring = 3 * 16 * 1024 + 16 + (size_t)(4 * (xs->n_sites + 1) + 2) * sizeof(int) + (size_t)2 * xs->n_sites * sizeof(long long);
-  if (lds_ring > 80 * 1024) return fail(QK_EINVAL, "qk_gram_values: %d sites need %zu bytes of LDS per workgroup (limit 80 KiB for 2 workgroups per CU)", xs->n_sites, lds_ring);
-  const size_t esz = f32 ? sizeof(float) : sizeof(double);
-  const size_t lds_small = (size_t)(3 * 2 * (64 / esz) * 64 + 6 * 32 * 32) * esz + 16 + (size_t)(4 * (xs->n_sites + 1) + 2) * sizeof(int) + (size_t)2 * xs->n_sites * sizeof(long long);
-  if (quad) {  // 2x2 blocks of pairs per workgroup (QK_PLAN_QUADS plans): an experimental kernel of the lab library
-#ifdef QK_LAB
-    const int rc_quad = qk_lab_launch_quad(c, a, grid, xs->n_sites, f32);
-    if (rc_quad != QK_OK) return rc_quad;
-    c->last.kernel = QK_KERNEL_LAB;
-#else
-    return fail(QK_EINVAL, "qk_gram_values: QK_PLAN_QUADS plans are swept by an experimental kernel that only libqklab.so contains");
-#endif
-  } else if (c->variant == 20 && c->wave_path && !f32 && std::max(xs->max_pad, ys->max_pad) <= 16) {
-    // every bond <= 16: a pair lives in the registers of one wavefront (qk_sweep_wave_kernel); 16 waves per CU
-    const int wgrid = (int)std::min<long long>(np, 16ll * c->num_cus);
-    qk_sweep_wave_kernel<0><<<dim3(wgrid), dim3(64), 0, c->stream>>>(a);
-    launched_grid = wgrid, c->last.kernel = QK_KERNEL_WAVE;
-  } else if (!fused && c->variant == 20 && c->wave2_path && (!f32 || c->wave2_ring) && std::max(xs->max_pad, ys->max_pad) <= 32) {
-    // every bond <= 32, fp64: a pair lives in the registers of one wavefront as 2 x 2 tiles (qk_sweep_wave2_kernel); 8 waves per CU
-    for (const qk_mps_set* m : {xs, ys}) {
-      const int rc_il = ensure_interleaved(c, const_cast<qk_mps_set*>(m));
-      if (rc_il != QK_OK) return rc_il;
-    }
-    a.xdata = xs->d_il, a.ydata = ys->d_il;
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));  // the conversion above is not part of the sweep
-    const int wgrid = (int)std::min<long long>(np, 8ll * c->num_cus);
-    a.nq = plan->nq, c->last.queues = plan->nq > 1 ? 8 : 1, c->tail_pending = true;
-    if (f32) qk_sweep_wave2_kernel<3, float><<<dim3(wgrid), dim3(64), 0, c->stream>>>(a);  // complex64 storage, fp64 arithmetic
-    else if (c->wave2_ring) qk_sweep_wave2_kernel<3, double><<<dim3(wgrid), dim3(64), 0, c->stream>>>(a);
-    else qk_sweep_wave2_kernel<0, double><<<dim3(wgrid), dim3(64), 0, c->stream>>>(a);
-    launched_grid = wgrid, c->last.kernel = (f32 || c->wave2_ring) ? QK_KERNEL_WAVE2 : QK_KERNEL_WAVE2_PLAIN;
-  } else if (!fused && c->variant == 20 && c->small_path && std::max(xs->max_pad, ys->max_pad) <= 32 && lds_small <= 80 * 1024) {
-    // every bond <= 32: X and T stay in LDS, only the site tensors stream (qk_sweep_small_kernel); chains too long for
-    // its LDS budget (several hundred sites) take the ring kernel below
-    if (f32) qk_sweep_small_kernel<float><<<dim3(grid), dim3(512), lds_small, c->stream>>>(a);
-    else qk_sweep_small_kernel<double><<<dim3(grid), dim3(512), lds_small, c->stream>>>(a);
-    c->last.kernel = QK_KERNEL_SMALL;
-  } else if (fused) {
-    // X in LDS, T in registers, site tensors read straight into MFMA fragments from the interleaved image
-    for (const qk_mps_set* m : {xs, ys}) {
-      const int rc_il = ensure_interleaved(c, const_cast<qk_mps_set*>(m));
-      if (rc_il != QK_OK) return rc_il;
-    }
-    a.xdata = xs->d_il, a.ydata = ys->d_il;
-    // the ends of the chain from the sets' edge blocks: k chosen by the planner -- unless a set already holds blocks for another k
-    // (made for an earlier plan, e.g. the training Gram before the test Gram on the same X): any k gives the same overlaps and the
-    // model's choices lie within 0.5 % of each other, so the set keeps the k of its first use instead of being rebuilt per call
-    int ek = plan->edge_k;
-    if (ek > 0) {
-      if (xs->edge_k > 0 && (ys == xs || ys->edge_k == 0 || ys->edge_k == xs->edge_k)) ek = xs->edge_k;
-      else if (xs->edge_k == 0 && ys->edge_k > 0) ek = ys->edge_k;
-      for (const qk_mps_set* m : {xs, ys}) {
-        const int rc_e = ensure_edges(c, const_cast<qk_mps_set*>(m), ek);
-        if (rc_e != QK_OK) return rc_e;
-      }
-      a.xedge = xs->d_edge, a.xedge_offs = xs->d_edge_offs, a.yedge = ys->d_edge, a.yedge_offs = ys->d_edge_offs, a.edge_k = ek;
-    }
-    if (c->merge_sites && xs->n_sites - 2 * ek >= 2) {  // the chain's sites contracted in twos: a workgroup picks per pair and step
-      for (const qk_mps_set* m : {xs, ys}) {
-        const int rc_m = ensure_merged(c, const_cast<qk_mps_set*>(m), ek);
-        if (rc_m != QK_OK) return rc_m;
-      }
-      a.xmg = xs->d_mg, a.xmg_offs = xs->d_mg_offs, a.ymg = ys->d_mg, a.ymg_offs = ys->d_mg_offs, a.merge_steps = xs->mg_steps;
-    }
-#ifdef QK_LAB  // TIMING EXPERIMENT (wrong results): every tensor read from the first MiB of its image -- what would perfect L2 hits buy?
-    if (const char* v = std::getenv("QK_DEBUG_ALIAS")) {
-      const long long win = std::atoll(v);  // window in doubles (e.g. 131072 = 1 MiB)
-      if (win > 0) {
-        auto fold = [&](const int64_t* src, const long long n) -> const int64_t* {
-          int64_t* dst = nullptr;
-          if (hipMalloc(&dst, (size_t)n * sizeof(int64_t)) != hipSuccess) return src;  // (leaked: experiment)
-          qk_lab_fold_kernel<<<dim3(256), dim3(256), 0, c->stream>>>(src, dst, n, win);
-          return dst;
-        };
-        a.xoffs = fold(a.xoffs, (long long)xs->n_states * xs->n_sites), a.yoffs = fold(a.yoffs, (long long)ys->n_states * ys->n_sites);
-        if (a.merge_steps > 0)
-          a.xmg_offs = fold(a.xmg_offs, (long long)xs->n_states * xs->mg_steps), a.ymg_offs = fold(a.ymg_offs, (long long)ys->n_states * ys->mg_steps);
-      }
-    }
-#endif
-    a.x_plane = (long long)xs->max_pad * ys->max_pad;  // complex elements per global X buffer (two per workgroup)
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));        // the conversion above is not part of the sweep
-    a.nq = plan->nq, c->last.queues = plan->nq > 1 ? 8 : 1, c->tail_pending = true;
-    // gang start (QK_GANG=1, qk_device.h: qk_gang_sync): the workgroups of an XCD begin their pairs together; workgroups per XCD = grid / 8 (round-robin dispatch)
-    const bool gang_on = plan->nq > 1 && std::getenv("QK_GANG") && std::atoi(std::getenv("QK_GANG")) != 0;
-    auto gang_of = [&](const long long grid_) { return gang_on && grid_ >= 16 && grid_ % 8 == 0 ? (int)(grid_ / 8) : 0; };
-    a.gang_n = gang_of(grid);
-    // the dual form (pairs of tiles per wave: half the A and X fragments per matrix instruction) against single tiles, same box:
-    // uniform bonds 48 / 64 / 96 / 128 / 256: +2 / +4 / +7 / +12 / +19 %; first run of the headline set's split sweep: 255 against 264 ms
-    if (mixed) {
-      SweepArgs a1 = a, a2 = a;
-      a1.npairs = plan->n_first;
-      a2.pairs = a.pairs + 2 * plan->n_first, a2.npairs = np - plan->n_first;
-      a2.values = a.values + plan->n_first, a2.z = a.z ? a.z + 2 * plan->n_first : nullptr;
-      a2.counter = c->counter + 8 * QK_QSTRIDE, a2.tail = tail + 2;
-      if (plan->nq > 1) {
-        a1.nq = a2.nq = 8;
-        for (int s_ = 0; s_ <= 8; ++s_) a2.qstart[s_] = plan->qstart[8 + s_] - plan->n_first;
-      }
-      const unsigned g1 = (unsigned)std::min<long long>(a1.npairs, (long long)(fused_two ? QKF_TWO_WGS : 1) * c->num_cus);
-      a1.gang_n = gang_of(g1), a2.gang_n = 0;
-      if (fused_two) QKF_LAUNCH_TWO(det, g1, lds_fused, a1);
-      else if (dual) QKF_LAUNCH_DUAL(det, g1, lds_fused, a1);
-      else QKF_LAUNCH_ONE(det, g1, lds_fused, a1);
+  for (int i = 0; i < ch.n_runs; ++i) {
+    const QkSweepRun& r = ch.run[i];
+    SweepArgs ar = a;
+    ar.npairs = r.count, ar.nq = r.nq, ar.gang_n = r.gang_n;
+    if (i == 1) {  // the second class of pairs: its part of the list, and queue heads, tail clocks (and gang words) behind the first launch's
       HIP_TRY(hipEventRecord(c->ev_mid, c->stream));
-      qk_sweep_wave2_kernel<3, double><<<dim3((unsigned)std::min<long long>(a2.npairs, 8ll * c->num_cus)), dim3(64), 0, c->stream>>>(a2);
+      ar.pairs = a.pairs + 2 * r.first, ar.values = a.values + r.first, ar.z = a.z ? a.z + 2 * r.first : nullptr;
+      ar.counter = c->counter + 8 * QK_QSTRIDE, ar.tail = a.tail + 2;
+      if (plan->nq > 1)
+        for (int s_ = 0; s_ <= 8; ++s_) ar.qstart[s_] = plan->qstart[8 + s_] - r.first;
+      if (r.gang2) ar.gang = a.gang + 8 * QK_QSTRIDE;
       c->last.second_pairs = plan->second.pairs, c->last.second_flops = plan->second.flops, c->last.second_padded_flops = plan->second.padded_flops;
-      c->last.second_bytes = plan->second.bytes, c->last.second_kernel = QK_KERNEL_WAVE2;
+      c->last.second_bytes = plan->second.bytes, c->last.second_kernel = r.kernel;
       c->split_pending = true;
-    } else if (fused_two) QKF_LAUNCH_TWO(det, grid, lds_fused, a);
-    else if (dual && !split) QKF_LAUNCH_DUAL(det, grid, lds_fused, a);
-    else if (split) {
-      // the plan lists the pairs whose sites fit the smaller LDS buffer behind the others: one 12-wave workgroup per CU for
-      // the first run, two 8-wave workgroups per CU for the second, back to back on the stream
-      SweepArgs a1 = a, a2 = a;
-      a1.npairs = plan->n_first;
-      a2.pairs = a.pairs + 2 * plan->n_first, a2.npairs = np - plan->n_first;
-      a2.values = a.values + plan->n_first, a2.z = a.z ? a.z + 2 * plan->n_first : nullptr;
-      a2.counter = c->counter + 8 * QK_QSTRIDE, a2.tail = tail + 2;
-      if (plan->nq > 1) {  // 8 queues per run
-        a1.nq = a2.nq = 8;
-        for (int s_ = 0; s_ <= 8; ++s_) a2.qstart[s_] = plan->qstart[8 + s_] - plan->n_first;
-      }
-      a1.gang_n = gang_of(std::min<long long>(a1.npairs, c->num_cus));
-      a2.gang = a.gang + 8 * QK_QSTRIDE, a2.gang_n = gang_of(std::min<long long>(a2.npairs, (long long)QKF_TWO_WGS * c->num_cus));
-      if (dual) QKF_LAUNCH_DUAL(det, std::min<long long>(a1.npairs, c->num_cus), lds_fused, a1);
-      else QKF_LAUNCH_ONE(det, std::min<long long>(a1.npairs, c->num_cus), lds_fused, a1);
-      HIP_TRY(hipEventRecord(c->ev_mid, c->stream));
-      QKF_LAUNCH_TWO(det, std::min<long long>(a2.npairs, (long long)QKF_TWO_WGS * c->num_cus), (size_t)QKF_XCAP_TWO * 16 + lds_meta, a2);
-      c->last.second_pairs = plan->second.pairs, c->last.second_flops = plan->second.flops, c->last.second_padded_flops = plan->second.padded_flops;
-      c->last.second_bytes = plan->second.bytes, c->last.second_kernel = det ? QK_KERNEL_FUSED2_DET : QK_KERNEL_FUSED2;
-      c->split_pending = true;
-    } else QKF_LAUNCH_ONE(det, grid, lds_fused, a);
-    c->last.kernel = fused_two ? (det ? QK_KERNEL_FUSED2_DET : QK_KERNEL_FUSED2) : dual ? (det ? QK_KERNEL_FUSED_DUAL_DET : QK_KERNEL_FUSED_DUAL) : (det ? QK_KERNEL_FUSED1_DET : QK_KERNEL_FUSED1);
-  } else if (f32) {  // complex64 sweep: the ring kernel on fp32 planes; QK_VARIANT does not apply
-    qk_sweep_ring_kernel<float><<<dim3(grid), dim3(512), lds_ring, c->stream>>>(a);
-    c->last.kernel = QK_KERNEL_RING;
-  } else if (c->variant == 20) {  // the ring sweep: LDS-DMA staging ring (K-tile 8, three slots) + 3M complex product
-    qk_sweep_ring_kernel<double><<<dim3(grid), dim3(512), lds_ring, c->stream>>>(a);
-    c->last.kernel = QK_KERNEL_RING;
-  } else {  // experimental / diagnostic kernels (qk_lab.hip, libqklab.so only)
+    }
 #ifdef QK_LAB
-    const int rc_lab = qk_lab_launch(c, c->variant, a, grid, xs->n_sites);
-    if (rc_lab != QK_OK) return rc_lab;
-    c->last.kernel = QK_KERNEL_LAB;
-#else
-    return fail(QK_EINVAL, "qk_gram_values: no kernel for this call");
+    if (r.kernel == QK_KERNEL_LAB) rc = plan->quad ? qk_lab_launch_quad(c, ar, (int)r.grid, xs->n_sites, f32) : qk_lab_launch(c, pol.variant, ar, (int)r.grid, xs->n_sites);
+    else
 #endif
+      rc = launch_sweep(r.kernel, f32, r.grid, r.lds, c->stream, ar);
+    if (rc != QK_OK) return rc;
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   c->ev_pending = true;
-  c->last.grid = launched_grid;
+  c->last.kernel = ch.run[0].kernel, c->last.grid = (int)ch.launched_grid;
+  c->tail_pending = ch.tails;
   return QK_OK;
 }
 
