@@ -283,6 +283,27 @@ int qk_overlaps_host(qk_ctx* ctx, const qk_mps_set* xset, const qk_mps_set* yset
 
 int qk_get_stats(qk_ctx* ctx, qk_stats* out);
 
+/* ---- projected quantum kernel (Huang et al., Nat. Commun. 12, 2631 (2021)) ----------------------------------------------
+ * Local Bloch vectors of every state of a set, synchronous on the context's stream.  Site k is qubit k, physical index 0 = |0>;
+ * states need not be normalised:
+ *     rho_k[s][s'] = sum over all other sites of psi(..s..) conj(psi(..s'..)) / <psi|psi>
+ *     out[state][k] = (<X_k>, <Y_k>, <Z_k>) = (2 Re rho_k[0][1], -2 Im rho_k[0][1], rho_k[0][0] - rho_k[1][1])
+ *     norms[state]  = <psi|psi> from the same sweep (norms may be NULL)
+ * One environment sweep per state (left environments and those of the reversed chain), spread over the chip; every
+ * state's result is bit-identical whatever the rest of the set and from run to run.  fp64 sets only (a complex64 set is
+ * QK_EINVAL).  Device scratch is kept on the context (qk_ctx_trim releases it), bounded by a quarter of the free memory;
+ * the Gram statistics (qk_get_stats) are not touched.                                                                     */
+int qk_local_paulis_host(qk_ctx* ctx, const qk_mps_set* set, double* out /* [n_states][n_sites][3] */,
+                         double* norms /* [n_states], may be NULL */);
+
+/* The projected-kernel Gram from Bloch vectors (host arrays [n][n_sites][3]), synchronous:
+ *     out[j * ld + i] = exp(-g/2 * sum_k sum_c (fx[i][k][c] - fy[j][k][c])^2)  = exp(-g sum_k ||rho_k(x_i) - rho_k(y_j)||_F^2)
+ * Rows are Y, columns are X (as qk_gram_host); fy = NULL means Y is X (then ny must equal nx).  Each entry is summed over the
+ * 3 n_sites terms in one fixed order: a symmetric Gram is exactly symmetric with a diagonal of exactly 1.0.
+ * QK_EINVAL: g <= 0 or not finite, ld < nx, n_sites < 1, nx or ny < 1.                                                       */
+int qk_projected_gram_host(qk_ctx* ctx, int32_t n_sites, int32_t nx, const double* fx /* [nx][n_sites][3] */,
+                           int32_t ny, const double* fy /* NULL: Y is X */, double g, double* out, int64_t ld);
+
 /* ---- profiler ranges -----------------------------------------------------------------------------------------
  * roctx ranges (rocprofv3 --marker-trace) named "qk:build", "qk:upload", "qk:sweep", "qk:scatter", "qk:allgather_values",
  * "qk:allgather_sets" are opened by the library around its own phases -- the reference's MPI.Wtime() sites G:209-231

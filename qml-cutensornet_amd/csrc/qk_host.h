@@ -1,6 +1,7 @@
 // qk_host.h -- host-side state shared by the translation units:
 //   qkgram.hip    the C ABI, the planner and the shipped sweep kernels      } libqkgram.so
 //   qk_build.hip  the device MPS builder                                    }
+//   qk_local.hip  local Bloch vectors and the projected-kernel Gram          }
 //   qk_lab.hip    experimental / diagnostic kernels for A/B measurements: only in lab/libqklab.so (-DQK_LAB, lab/tools)
 #pragma once
 #include "../../include/qkgram.h"
@@ -46,6 +47,9 @@ struct qk_ctx {
   // scratch of the workgroups that make a set's edge blocks (qk_edge_kernel), kept between calls
   void* derive_tmp = nullptr;
   size_t derive_tmp_bytes = 0;
+  // the local sweep's tables, rho partial sums and per-state environments (qk_local.hip), kept between calls
+  void* local_scratch = nullptr;
+  size_t local_scratch_bytes = 0;
 };
 
 uint64_t qk_next_uid();

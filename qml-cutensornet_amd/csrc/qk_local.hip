@@ -1,0 +1,464 @@
+// qk_local.hip -- per-qubit reduced density matrices of every state of a set (their Bloch vectors) and the projected quantum
+// kernel (PQK) Gram built from them.  Part of libqkgram.so; entry points qk_local_paulis_host and qk_projected_gram_host
+// (include/qkgram.h).
+//
+// Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
+// normalised):
+//     rho_k[s][s'] = sum over every other site of psi(..s..) conj(psi(..s'..)) / <psi|psi>
+//     F[k] = (<X_k>, <Y_k>, <Z_k>) = (2 Re rho_k[0][1], -2 Im rho_k[0][1], rho_k[0][0] - rho_k[1][1])
+//     K_P[j][i] = exp(-g/2 sum_k sum_c (Fx[i][k][c] - Fy[j][k][c])^2)      (= exp(-g sum_k ||rho_k(x_i) - rho_k(y_j)||_F^2))
+//
+// The local sweep.  A_k = site k of the set as a [a][(s, a')] matrix (split re/im planes, padded bonds), environments in the ring
+// sweep's X[ket][bra] orientation (qk_ring.h):
+//     L_0 = 1
+//     T_k[a][(s, b')]       = sum_b L_k[b][a] A_k[b][(s, b')]                  (the ring sweep's first GEMM with y = x)
+//     W_{k,s}[b'][(s', a')] = sum_a T_k[(a, s)][b'] conj(A_k[a][(s', a')])     (s = 0, 1: the T rows of one s, row stride 2 pad(b'))
+//     rho_k[s][s']          = sum_{b', a'} W_{k,s}[b'][(s', a')] R_{k+1}[b'][a']
+//     L_{k+1}[b'][a']       = W_{k,0}[b'][(0, a')] + W_{k,1}[b'][(1, a')]
+//     <psi|psi>             = L_n[0][0]
+// The right environments R_k are the left environments of the reversed chain (sites n-1 .. 0, left and right bonds exchanged),
+// R_n = 1: a permutation kernel makes that reversed image once per call, the same two-GEMM recurrence runs on it and every R_k
+// (k = 1 .. n) is kept.
+//
+// Work is spread over the chip: ONE launch per step for every state of a batch, ordered by the stream.  The tasks of a GEMM launch
+// are (state, 64 x 64 output block), listed by the host from the bond tables; a workgroup computes its block with the ring GEMM
+// (zgemm_ring3, fixed K order).  The rho sums are split into 16-row chunks, one workgroup each, with a fixed-order reduction; the
+// chunks are added in a fixed order at the end.  No grid-wide barrier, no spin wait, no atomics: a state's features are the same
+// bits whatever its batch, its neighbours or the run.
+#include "qk_host.h"
+#include "qk_ring.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+namespace {
+
+constexpr int LOC_KTL = 8, LOC_NSLOT = 3;                           // the ring GEMM's fp64 shape (K-tile 8, three 16-KiB slots)
+constexpr int LOC_LDS_DOUBLES = LOC_NSLOT * (4 * LOC_KTL * 64);     // 48 KiB
+constexpr int LOC_RED_THREADS = 256;                                // workgroup of the rho / L_{k+1} step
+constexpr int LOC_CHUNK = 16;                                       // rows of b' per reduction task
+
+enum LocKind : int {
+  LOC_REV_T = 0,   // reversed chain: T = Lr^T Ar_j              (Lr_j = R_{o+1}, o = n-1-j)
+  LOC_REV_X = 1,   // reversed chain: R_o = T^T conj(Ar_j)
+  LOC_FWD_T = 2,   // T_k = L_k^T A_k
+  LOC_FWD_W = 3,   // W_{k,s} = T_k[(., s)]^T conj(A_k), both s in one launch
+};
+
+// Per-state scratch (doubles, every matrix as a re plane then an im plane), P = the state's largest padded bond:
+//   L [P x P] at 0 | T [P x 2P] at 2P^2 | W_0 [P x 2P] at 6P^2 | W_1 at 10P^2 | R_1 .. R_n at 14P^2 + roff[k] (pad_k^2 per plane)
+struct LocArgs {
+  const double* data;     // the set's planes
+  const double* rev;      // the reversed image: site o of a state transposed to [pad_{o+1}][2][pad_o], at the set's offset of site o
+  const int32_t* dims;    // padded bonds [n_states][n_sites + 1]
+  const int32_t* tru;     // true bonds
+  const int64_t* offs;    // re-plane offsets [n_states][n_sites]
+  const int32_t* states;  // batch entry -> state of the set
+  const int32_t* pmax;    // batch entry -> P
+  const int64_t* sbase;   // batch entry -> first double of its scratch
+  const int64_t* roff;    // [batch][n_sites + 1]: R_k at sbase + 14 P^2 + roff[k]
+  const int2* tasks;      // this launch: (batch entry, block)
+  double* scratch;
+  double* part;           // rho partial sums [batch][n_sites][max chunks][4]
+  int n_sites;
+  int max_chunks;
+  int step;               // reversed-chain step j (LOC_REV_*) or site k (forward)
+};
+
+__device__ __forceinline__ long long uni64(const long long v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// One 64 x 64 output block of one state's GEMM of this step.  CONJB: the LOC_REV_X / LOC_FWD_W products (conjugated site tensor).
+template <bool CONJB>
+__global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, const int kind) {
+  __shared__ __attribute__((aligned(16))) double lds[LOC_LDS_DOUBLES];
+  const int2 t = g.tasks[blockIdx.x];
+  const int i = __builtin_amdgcn_readfirstlane(t.x), blk = __builtin_amdgcn_readfirstlane(t.y);
+  const int n = g.n_sites, n1 = n + 1;
+  const long long st = __builtin_amdgcn_readfirstlane(g.states[i]);
+  const int* pd = g.dims + st * n1;
+  const int* td = g.tru + st * n1;
+  const long long P = __builtin_amdgcn_readfirstlane(g.pmax[i]);
+  double* const S = g.scratch + uni64(g.sbase[i]);
+  const long long P2 = P * P;
+  double* const Tre = S + 2 * P2;
+  const long long tpl = 2 * P2;  // T and W planes
+  const double *Are, *Aim, *Bre, *Bim;
+  double *Cre, *Cim;
+  int lda, ldb, ldc, M, N, K;
+  if (kind == LOC_REV_T || kind == LOC_REV_X) {
+    const int o = n - 1 - g.step;
+    const int al = __builtin_amdgcn_readfirstlane(pd[o + 1]), ar = __builtin_amdgcn_readfirstlane(pd[o]);
+    const int at = __builtin_amdgcn_readfirstlane(td[o + 1]);
+    Bre = g.rev + uni64(g.offs[st * n + o]);
+    Bim = Bre + (long long)al * 2 * ar;
+    if (kind == LOC_REV_T) {
+      Are = S + 14 * P2 + uni64(g.roff[(long long)i * n1 + o + 1]);
+      Aim = Are + (long long)al * al;
+      Cre = Tre, Cim = Tre + tpl;
+      lda = al, ldb = 2 * ar, ldc = 2 * ar, M = al, N = 2 * ar, K = at;
+    } else {
+      Are = Tre, Aim = Tre + tpl;
+      Cre = S + 14 * P2 + uni64(g.roff[(long long)i * n1 + o]);
+      Cim = Cre + (long long)ar * ar;
+      lda = ar, ldb = ar, ldc = ar, M = ar, N = ar, K = 2 * at;
+    }
+  } else {
+    const int k = g.step;
+    const int l = __builtin_amdgcn_readfirstlane(pd[k]), r = __builtin_amdgcn_readfirstlane(pd[k + 1]);
+    const int lt = __builtin_amdgcn_readfirstlane(td[k]);
+    Bre = g.data + uni64(g.offs[st * n + k]);
+    Bim = Bre + (long long)l * 2 * r;
+    if (kind == LOC_FWD_T) {
+      Are = S, Aim = S + P2;
+      Cre = Tre, Cim = Tre + tpl;
+      lda = l, ldb = 2 * r, ldc = 2 * r, M = l, N = 2 * r, K = lt;
+    } else {
+      M = r, N = 2 * r;
+      const int per_s = ((M + 63) / 64) * ((N + 63) / 64);
+      const int s = blk >= per_s;
+      Are = Tre + s * r, Aim = Are + tpl;
+      Cre = S + 6 * P2 + s * 2 * tpl, Cim = Cre + tpl;
+      lda = 2 * r, ldb = 2 * r, ldc = 2 * r, K = lt;
+    }
+  }
+  const int npm = (M + 63) / 64;
+  const int b = (kind == LOC_FWD_W) ? blk % (npm * ((N + 63) / 64)) : blk;
+  const int m0 = 64 * (b % npm), n0 = 64 * (b / npm);
+  zgemm_ring3<CONJB, LOC_KTL, LOC_NSLOT, true, 8, 64, double, 7>(Cre + (long long)m0 * ldc + n0, Cim + (long long)m0 * ldc + n0, ldc, Are + m0, Aim + m0, lda,
+                                                                  Bre + n0, Bim + n0, ldb, min(64, M - m0), min(64, N - n0), K, lds);
+}
+
+// rho_k partial sums of one 16-row chunk of b' and the same rows of L_{k+1} = W_0[.][(0, .)] + W_1[.][(1, .)].
+// part[(i, k, chunk)] = (Re rho00, Re rho11, Re rho01, Im rho01), unnormalised.
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_rho_kernel(const LocArgs g) {
+  __shared__ double red[4][LOC_RED_THREADS];
+  const int2 t = g.tasks[blockIdx.x];
+  const int i = t.x, c = t.y;
+  const int n = g.n_sites, n1 = n + 1, k = g.step;
+  const long long st = g.states[i];
+  const int r = g.dims[st * n1 + k + 1];
+  const long long P = g.pmax[i], P2 = P * P, tpl = 2 * P2;
+  double* const S = g.scratch + g.sbase[i];
+  const double* W0 = S + 6 * P2;
+  const double* W1 = W0 + 2 * tpl;
+  const double* R = S + 14 * P2 + g.roff[(long long)i * n1 + k + 1];
+  const long long rpl = (long long)r * r;
+  double a00 = 0, a11 = 0, a01r = 0, a01i = 0;
+  const int rows = LOC_CHUNK * r;
+  for (int e = threadIdx.x; e < rows; e += LOC_RED_THREADS) {
+    const int bp = c * LOC_CHUNK + e / r, ap = e % r;
+    const long long w = (long long)bp * 2 * r + ap;
+    const double w00r = W0[w], w00i = W0[w + tpl], w01r = W0[w + r], w01i = W0[w + r + tpl];
+    const double w11r = W1[w + r], w11i = W1[w + r + tpl];
+    const long long q = (long long)bp * r + ap;
+    const double rr = R[q], ri = R[q + rpl];
+    a00 += w00r * rr - w00i * ri;
+    a11 += w11r * rr - w11i * ri;
+    a01r += w01r * rr - w01i * ri;
+    a01i += w01r * ri + w01i * rr;
+    S[q] = w00r + w11r;  // L_{k+1}[b'][a'], ld r
+    S[q + P2] = w00i + w11i;
+  }
+  red[0][threadIdx.x] = a00, red[1][threadIdx.x] = a11, red[2][threadIdx.x] = a01r, red[3][threadIdx.x] = a01i;
+  __syncthreads();
+  for (int h = LOC_RED_THREADS / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h)
+      for (int v = 0; v < 4; ++v) red[v][threadIdx.x] += red[v][threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) g.part[(((long long)i * n + k) * g.max_chunks + c) * 4 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// L_0 = 1 and R_n = 1 (16 x 16, [0][0] = 1) of every state of the batch.
+__global__ __launch_bounds__(256) void qk_local_init_kernel(const LocArgs g, const int nb) {
+  const int i = blockIdx.x;
+  if (i >= nb) return;
+  const long long P = g.pmax[i], P2 = P * P;
+  double* const S = g.scratch + g.sbase[i];
+  double* const Rn = S + 14 * P2 + g.roff[(long long)i * (g.n_sites + 1) + g.n_sites];
+  const int e = threadIdx.x;  // 256 = 16 x 16
+  const double v = (e == 0) ? 1.0 : 0.0;
+  S[e] = v, S[P2 + e] = 0.0;
+  Rn[e] = v, Rn[256 + e] = 0.0;
+}
+
+// The reversed image of the batch's states: site o of state st, [a][s][b] -> [b][s][a] in both planes, at the same offset.
+__global__ __launch_bounds__(256) void qk_local_reverse_kernel(const LocArgs g, double* rev) {
+  const int i = blockIdx.x, o = blockIdx.y, n = g.n_sites, n1 = n + 1;
+  const long long st = g.states[i];
+  const int l = g.dims[st * n1 + o], r = g.dims[st * n1 + o + 1];
+  const long long off = g.offs[st * n + o], pl = (long long)l * 2 * r;
+  const double* src = g.data + off;
+  double* dst = rev + off;
+  for (long long e = threadIdx.x; e < 2 * pl; e += 256) {
+    const long long p = e >= pl, f = e - p * pl;
+    const int a = (int)(f / (2 * r)), rem = (int)(f % (2 * r)), s = rem / r, bb = rem % r;
+    dst[p * pl + (long long)bb * 2 * l + s * l + a] = src[e];
+  }
+}
+
+// Bloch vectors and norms: the chunk sums of each (state, site) in a fixed order, normalised by L_n[0][0].
+__global__ __launch_bounds__(256) void qk_local_features_kernel(const LocArgs g, const int nb, double* out, double* norms) {
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int n = g.n_sites, n1 = n + 1;
+  if (id >= (long long)nb * n) return;
+  const int i = (int)(id / n), k = (int)(id % n);
+  const long long st = g.states[i];
+  const double nrm = g.scratch[g.sbase[i]];  // L_n[0][0]
+  const int chunks = g.dims[st * n1 + k + 1] / LOC_CHUNK;
+  const double* p = g.part + ((long long)i * n + k) * g.max_chunks * 4;
+  double a00 = 0, a11 = 0, a01r = 0, a01i = 0;
+  for (int c = 0; c < chunks; ++c) a00 += p[4 * c], a11 += p[4 * c + 1], a01r += p[4 * c + 2], a01i += p[4 * c + 3];
+  double* f = out + (st * n + k) * 3;
+  f[0] = 2.0 * a01r / nrm;
+  f[1] = -2.0 * a01i / nrm;
+  f[2] = (a00 - a11) / nrm;
+  if (norms && k == 0) norms[st] = nrm;
+}
+
+// The PQK Gram: K[j][i] = exp(-g/2 sum_d (fx[i][d] - fy[j][d])^2), d = 3 n_sites.  A 64 x 64 tile per workgroup (4 x 4 entries per
+// thread), features staged in LDS in 32-wide slices of d.  Each entry adds its d terms in ascending order into one accumulator: the
+// differences of (i, j) and (j, i) are negatives of each other, so a symmetric Gram is exactly symmetric and its diagonal exactly 1.
+constexpr int PG_T = 64, PG_D = 32;
+__global__ __launch_bounds__(256) void qk_projected_gram_kernel(const double* fx, int nx, const double* fy, int ny, int D, double half_g, double* K, long long ld) {
+  __shared__ double sx[PG_D][PG_T + 1], sy[PG_D][PG_T + 1];
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int i0 = blockIdx.x * PG_T, j0 = blockIdx.y * PG_T;
+  double acc[4][4] = {};
+  for (int d0 = 0; d0 < D; d0 += PG_D) {
+    for (int e = threadIdx.x; e < PG_T * PG_D; e += 256) {
+      const int row = e / PG_D, d = e % PG_D;
+      const bool dv = d0 + d < D;
+      sx[d][row] = (dv && i0 + row < nx) ? fx[(long long)(i0 + row) * D + d0 + d] : 0.0;
+      sy[d][row] = (dv && j0 + row < ny) ? fy[(long long)(j0 + row) * D + d0 + d] : 0.0;
+    }
+    __syncthreads();
+    const int dn = min(PG_D, D - d0);
+    for (int d = 0; d < dn; ++d) {
+      double xv[4], yv[4];
+      for (int u = 0; u < 4; ++u) xv[u] = sx[d][tx + 16 * u], yv[u] = sy[d][ty + 16 * u];
+      for (int a = 0; a < 4; ++a)
+        for (int u = 0; u < 4; ++u) {
+          const double diff = xv[u] - yv[a];
+          acc[a][u] = __fma_rn(diff, diff, acc[a][u]);
+        }
+    }
+    __syncthreads();
+  }
+  for (int a = 0; a < 4; ++a)
+    for (int u = 0; u < 4; ++u) {
+      const int i = i0 + tx + 16 * u, j = j0 + ty + 16 * a;
+      if (i < nx && j < ny) K[(long long)j * ld + i] = exp(-half_g * acc[a][u]);
+    }
+}
+
+struct DevMem {  // a device allocation released on every exit path
+  void* p = nullptr;
+  ~DevMem() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+#define LOC_TRY(expr, what)                                                                                  \
+  do {                                                                                                       \
+    hipError_t e_ = (expr);                                                                                  \
+    if (e_ != hipSuccess) return qk_fail(QK_EDEVICE, "%s: %s failed: %s", what, #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+int ensure_buffer(void** p, size_t* have, size_t want) {
+  if (*have >= want) return QK_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr, *have = 0;
+  const hipError_t e = hipMalloc(p, want);
+  if (e != hipSuccess) {
+    *p = nullptr;
+    return qk_fail(QK_EDEVICE, "qk_local_paulis_host: hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
+  }
+  *have = want;
+  return QK_OK;
+}
+
+inline int pad16h(int x) { return (x + 15) / 16 * 16; }
+inline long long blocks64(long long m, long long n) { return ((m + 63) / 64) * ((n + 63) / 64); }
+
+}  // namespace
+
+extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* out, double* norms) {
+  static const char* what = "qk_local_paulis_host";
+  if (!c || !set || !out) return qk_fail(QK_EINVAL, "%s: null argument", what);
+  if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: the set belongs to another context", what);
+  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: complex64 sets are not supported; local Paulis need an fp64 set", what);
+  const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: empty set", what);
+  QkRangeGuard range_("qk:local_paulis");
+  LOC_TRY(hipSetDevice(c->device), what);
+  LOC_TRY(hipStreamSynchronize(c->stream), what);
+  std::vector<int64_t> offs((size_t)ns * n);
+  LOC_TRY(hipMemcpy(offs.data(), set->d_offs, offs.size() * sizeof(int64_t), hipMemcpyDeviceToHost), what);
+  const int32_t* tru = set->dims_true.data();
+  std::vector<int32_t> pad((size_t)ns * n1);
+  std::vector<int> pmax(ns);
+  std::vector<long long> need(ns);  // scratch doubles of each state
+  for (int s = 0; s < ns; ++s) {
+    int p = 16;
+    long long rsum = 0;
+    for (int k = 0; k <= n; ++k) {
+      pad[(size_t)s * n1 + k] = pad16h(tru[(size_t)s * n1 + k]);
+      p = std::max(p, pad[(size_t)s * n1 + k]);
+      if (k >= 1) rsum += 2ll * pad[(size_t)s * n1 + k] * pad[(size_t)s * n1 + k];
+    }
+    pmax[s] = p;
+    need[s] = 14ll * p * p + rsum;
+  }
+  const int max_chunks = set->max_pad / LOC_CHUNK;
+  const long long part_per_state = (long long)n * max_chunks * 4;
+  // memory bound of the per-state scratch: a quarter of what is free once the reversed image and the outputs exist
+  DevMem rev, dout, dnorm;
+  LOC_TRY(hipMalloc(&rev.p, (size_t)set->bytes), what);
+  LOC_TRY(hipMalloc(&dout.p, (size_t)ns * n * 3 * sizeof(double)), what);
+  LOC_TRY(hipMalloc(&dnorm.p, (size_t)ns * sizeof(double)), what);
+  size_t free_b = 0, total_b = 0;
+  LOC_TRY(hipMemGetInfo(&free_b, &total_b), what);
+  const long long budget = (long long)((free_b + c->local_scratch_bytes) / 4 / sizeof(double));
+  // batches: consecutive states while their scratch and rho partials fit the budget (at least one state per batch)
+  std::vector<int> bstart{0};
+  for (long long acc = 0, s = 0; s < ns; ++s) {
+    const long long w = need[s] + part_per_state;
+    if (acc > 0 && acc + w > budget) bstart.push_back((int)s), acc = 0;
+    acc += w;
+  }
+  bstart.push_back(ns);
+  const int n_rev = n - 1;  // reversed-chain steps: R_{n-1} .. R_1 (R_0 is not needed)
+  std::vector<int2> tasks;
+  std::vector<long long> first;  // per launch: first task
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+    // tables of the batch: states, P, scratch bases, R offsets
+    std::vector<int32_t> h_states(nb), h_pmax(nb);
+    std::vector<int64_t> h_sbase(nb), h_roff((size_t)nb * n1);
+    long long tot = 0;
+    for (int i = 0; i < nb; ++i) {
+      const int s = s0 + i;
+      h_states[i] = s, h_pmax[i] = pmax[s], h_sbase[i] = tot;
+      long long ro = 0;
+      for (int k = 0; k <= n; ++k) {
+        h_roff[(size_t)i * n1 + k] = ro;
+        if (k >= 1) ro += 2ll * pad[(size_t)s * n1 + k] * pad[(size_t)s * n1 + k];
+      }
+      tot += need[s];
+    }
+    // task lists of every launch of the batch, in launch order: reversed T / X per step, then forward T / W / rho per site
+    tasks.clear(), first.clear();
+    auto add_launch = [&](auto blocks_of) {
+      first.push_back((long long)tasks.size());
+      for (int i = 0; i < nb; ++i) {
+        const int* p = &pad[(size_t)(s0 + i) * n1];
+        const int nbk = blocks_of(p);
+        for (int b = 0; b < nbk; ++b) tasks.push_back(int2{i, b});
+      }
+    };
+    for (int j = 0; j < n_rev; ++j) {
+      const int o = n - 1 - j;
+      add_launch([&](const int* p) { return (int)blocks64(p[o + 1], 2ll * p[o]); });
+      add_launch([&](const int* p) { return (int)blocks64(p[o], p[o]); });
+    }
+    for (int k = 0; k < n; ++k) {
+      add_launch([&](const int* p) { return (int)blocks64(p[k], 2ll * p[k + 1]); });
+      add_launch([&](const int* p) { return (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); });
+      add_launch([&](const int* p) { return p[k + 1] / LOC_CHUNK; });
+    }
+    first.push_back((long long)tasks.size());
+    // one device buffer for the batch: [tables | tasks | partials | per-state scratch]
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_states = al(nb * sizeof(int32_t)), b_pmax = al(nb * sizeof(int32_t)), b_sbase = al(nb * sizeof(int64_t));
+    const size_t b_roff = al(h_roff.size() * sizeof(int64_t)), b_tasks = al(tasks.size() * sizeof(int2));
+    const size_t b_part = al((size_t)nb * part_per_state * sizeof(double)), b_scr = (size_t)tot * sizeof(double);
+    const size_t b_tab = b_states + b_pmax + b_sbase + b_roff + b_tasks;
+    {
+      const int rc = ensure_buffer(&c->local_scratch, &c->local_scratch_bytes, b_tab + b_part + b_scr);
+      if (rc != QK_OK) return rc;
+    }
+    char* base = static_cast<char*>(c->local_scratch);
+    std::vector<char> stage(b_tab);
+    size_t at = 0;
+    auto put = [&](const void* src, size_t bytes, size_t span) {
+      std::memcpy(stage.data() + at, src, bytes);
+      const size_t here = at;
+      at += span;
+      return base + here;
+    };
+    LocArgs g{};
+    g.data = set->d_data;
+    g.rev = static_cast<const double*>(rev.p);
+    g.dims = set->d_dims;
+    g.tru = set->d_true;
+    g.offs = set->d_offs;
+    g.states = reinterpret_cast<const int32_t*>(put(h_states.data(), nb * sizeof(int32_t), b_states));
+    g.pmax = reinterpret_cast<const int32_t*>(put(h_pmax.data(), nb * sizeof(int32_t), b_pmax));
+    g.sbase = reinterpret_cast<const int64_t*>(put(h_sbase.data(), nb * sizeof(int64_t), b_sbase));
+    g.roff = reinterpret_cast<const int64_t*>(put(h_roff.data(), h_roff.size() * sizeof(int64_t), b_roff));
+    const int2* d_tasks = reinterpret_cast<const int2*>(put(tasks.data(), tasks.size() * sizeof(int2), b_tasks));
+    g.part = reinterpret_cast<double*>(base + b_tab);
+    g.scratch = reinterpret_cast<double*>(base + b_tab + b_part);
+    g.n_sites = n;
+    g.max_chunks = max_chunks;
+    LOC_TRY(hipMemcpyAsync(base, stage.data(), b_tab, hipMemcpyHostToDevice, c->stream), what);
+    qk_local_reverse_kernel<<<dim3(nb, n), dim3(256), 0, c->stream>>>(g, static_cast<double*>(rev.p));
+    qk_local_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, nb);
+    LOC_TRY(hipGetLastError(), what);
+    size_t li = 0;
+    auto launch = [&](const int kind, const int step) {
+      g.tasks = d_tasks + first[li];
+      g.step = step;
+      const long long grid = first[li + 1] - first[li];
+      ++li;
+      if (grid <= 0) return;
+      if (kind == LOC_REV_X || kind == LOC_FWD_W) qk_local_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
+      else if (kind >= 0) qk_local_gemm_kernel<false><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
+      else qk_local_rho_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
+    };
+    for (int j = 0; j < n_rev; ++j) launch(LOC_REV_T, j), launch(LOC_REV_X, j);
+    for (int k = 0; k < n; ++k) launch(LOC_FWD_T, k), launch(LOC_FWD_W, k), launch(-1, k);
+    LOC_TRY(hipGetLastError(), what);
+    const long long nf = (long long)nb * n;
+    qk_local_features_kernel<<<dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, static_cast<double*>(dout.p), static_cast<double*>(dnorm.p));
+    LOC_TRY(hipGetLastError(), what);
+    LOC_TRY(hipStreamSynchronize(c->stream), what);  // the staged tables are reused by the next batch
+  }
+  LOC_TRY(hipMemcpy(out, dout.p, (size_t)ns * n * 3 * sizeof(double), hipMemcpyDeviceToHost), what);
+  if (norms) LOC_TRY(hipMemcpy(norms, dnorm.p, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost), what);
+  return QK_OK;
+}
+
+extern "C" int qk_projected_gram_host(qk_ctx* c, int32_t n_sites, int32_t nx, const double* fx, int32_t ny, const double* fy, double g, double* out, int64_t ld) {
+  static const char* what = "qk_projected_gram_host";
+  if (!c || !fx || !out) return qk_fail(QK_EINVAL, "%s: null argument", what);
+  if (n_sites < 1) return qk_fail(QK_EINVAL, "%s: n_sites must be >= 1 (got %d)", what, n_sites);
+  if (nx < 1 || ny < 1) return qk_fail(QK_EINVAL, "%s: empty feature set (nx %d, ny %d)", what, nx, ny);
+  if (!fy && ny != nx) return qk_fail(QK_EINVAL, "%s: Y is X (fy NULL) but ny %d != nx %d", what, ny, nx);
+  if (!(g > 0.0) || !std::isfinite(g)) return qk_fail(QK_EINVAL, "%s: g must be > 0 and finite (got %g)", what, g);
+  if (ld < nx) return qk_fail(QK_EINVAL, "%s: ld %lld is smaller than the %d columns", what, (long long)ld, nx);
+  QkRangeGuard range_("qk:projected_gram");
+  LOC_TRY(hipSetDevice(c->device), what);
+  const int D = 3 * n_sites;
+  const size_t bx = (size_t)nx * D * sizeof(double), by = fy ? (size_t)ny * D * sizeof(double) : 0, bk = (size_t)ny * nx * sizeof(double);
+  DevMem buf;
+  LOC_TRY(hipMalloc(&buf.p, bx + by + bk), what);
+  double* dx = static_cast<double*>(buf.p);
+  double* dy = fy ? dx + (size_t)nx * D : dx;
+  double* dk = dx + (size_t)nx * D + (fy ? (size_t)ny * D : 0);
+  LOC_TRY(hipMemcpyAsync(dx, fx, bx, hipMemcpyHostToDevice, c->stream), what);
+  if (fy) LOC_TRY(hipMemcpyAsync(dy, fy, by, hipMemcpyHostToDevice, c->stream), what);
+  qk_projected_gram_kernel<<<dim3((nx + PG_T - 1) / PG_T, (ny + PG_T - 1) / PG_T), dim3(256), 0, c->stream>>>(dx, nx, dy, ny, D, 0.5 * g, dk, nx);
+  LOC_TRY(hipGetLastError(), what);
+  LOC_TRY(hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), dk, (size_t)nx * sizeof(double), (size_t)nx * sizeof(double), (size_t)ny, hipMemcpyDeviceToHost, c->stream), what);
+  LOC_TRY(hipStreamSynchronize(c->stream), what);
+  return QK_OK;
+}

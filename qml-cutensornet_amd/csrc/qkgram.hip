@@ -444,6 +444,7 @@ extern "C" int qk_ctx_destroy(qk_ctx* c) {
   if (c->build_arena) (void)hipFree(c->build_arena);
   if (c->build_work) (void)hipFree(c->build_work);
   if (c->derive_tmp) (void)hipFree(c->derive_tmp);
+  if (c->local_scratch) (void)hipFree(c->local_scratch);
   if (c->counter) (void)hipFree(c->counter);
   if (c->prof) (void)hipFree(c->prof);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -463,7 +464,9 @@ extern "C" int qk_ctx_trim(qk_ctx* c) {
   if (c->build_arena) (void)hipFree(c->build_arena);
   if (c->build_work) (void)hipFree(c->build_work);
   if (c->derive_tmp) (void)hipFree(c->derive_tmp);
+  if (c->local_scratch) (void)hipFree(c->local_scratch);
   c->derive_tmp = nullptr, c->derive_tmp_bytes = 0;
+  c->local_scratch = nullptr, c->local_scratch_bytes = 0;
   c->scratch = nullptr, c->scratch_bytes = 0;
   c->build_arena = nullptr, c->build_arena_bytes = 0;
   c->build_work = nullptr, c->build_work_bytes = 0;

@@ -94,6 +94,8 @@ _SIGNATURES = [
     ("qk_gram_host", C.c_int, [_P, _P, _P, _P, C.c_int64]),
     ("qk_overlaps_host", C.c_int, [_P, _P, _P, _P]),
     ("qk_get_stats", C.c_int, [_P, C.POINTER(QkStats)]),
+    ("qk_local_paulis_host", C.c_int, [_P, _P, _P, _P]),
+    ("qk_projected_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
@@ -189,6 +191,15 @@ def range_push(name: str) -> None:
 
 def range_pop() -> None:
     lib().qk_range_pop()
+
+
+def projected_gamma(gamma, n_sites: int) -> float:
+    """The bandwidth g of the projected quantum kernel: ``gamma``, or ``1 / n_sites`` for ``None`` (sum_k ||rho_k - sigma_k||_F^2
+    grows like n, and 1/n keeps the exponent O(1)).  Raises ``ValueError`` unless g > 0 and finite."""
+    g = 1.0 / int(n_sites) if gamma is None else float(gamma)
+    if not (g > 0.0 and np.isfinite(g)):
+        raise ValueError(f"the projected-kernel bandwidth must be > 0 and finite (got {gamma!r})")
+    return g
 
 
 def _dims_table(states) -> np.ndarray:
@@ -642,6 +653,33 @@ class Context:
         out = np.zeros((ny, nx, 2), dtype=np.float64)
         _check(lib().qk_overlaps_host(self._h, xset.handle, None if yset is None else yset.handle, out.ctypes.data), "qk_overlaps_host")
         return out[..., 0] + 1j * out[..., 1]
+
+    def local_paulis(self, mps_set: MpsSet, norms: bool = False):
+        """Bloch vectors of every state of an fp64 set: F[state, k] = (<X_k>, <Y_k>, <Z_k>) of qubit k, float64 of shape
+        (n_states, n_sites, 3); with ``norms=True`` also <psi|psi> of each state, as ``(F, norms)``.  Synchronous."""
+        info = mps_set.info()
+        F = np.zeros((info["n_states"], info["n_sites"], 3), dtype=np.float64)
+        nrm = np.zeros(info["n_states"], dtype=np.float64)
+        _check(lib().qk_local_paulis_host(self._h, mps_set.handle, F.ctypes.data, nrm.ctypes.data), "qk_local_paulis_host")
+        return (F, nrm) if norms else F
+
+    def projected_gram(self, fx, fy=None, gamma=None) -> np.ndarray:
+        """Projected quantum kernel K[j, i] = exp(-gamma/2 sum_k |Fx[i, k] - Fy[j, k]|^2) of Bloch vectors (``local_paulis``):
+        shape (ny, nx), rows = Y (or X).  ``gamma=None`` means 1 / n_sites.  Synchronous."""
+        fx = np.ascontiguousarray(fx, dtype=np.float64)
+        if fx.ndim != 3 or fx.shape[2] != 3:
+            raise ValueError(f"features must have shape (n_states, n_sites, 3), got {fx.shape}")
+        nx, n = fx.shape[0], fx.shape[1]
+        g = projected_gamma(gamma, n)
+        if fy is not None:
+            fy = np.ascontiguousarray(fy, dtype=np.float64)
+            if fy.ndim != 3 or fy.shape[1:] != fx.shape[1:]:
+                raise ValueError(f"Y features of shape {fy.shape} do not match X features of shape {fx.shape}")
+        ny = nx if fy is None else fy.shape[0]
+        out = np.zeros((ny, nx), dtype=np.float64)
+        _check(lib().qk_projected_gram_host(self._h, n, nx, fx.ctypes.data, ny, None if fy is None else fy.ctypes.data, g, out.ctypes.data, nx),
+               "qk_projected_gram_host")
+        return out
 
     def stats(self) -> dict:
         st = QkStats()

@@ -387,3 +387,100 @@ def build_kernel_matrix(mpi_comm, ansatz, X, Y=None, info_file=None, truncation_
         with open(info_file + ".json", "w") as fp:
             json.dump(prof, fp, indent=4)
     return kernel_mat
+
+
+def _gather_features(comm, lo, F, total):
+    """All-gather of every rank's (first index, Bloch vectors of its share) -> the (total, n, 3) array in data-set order."""
+    shares = comm_allgather(comm, (int(lo), np.ascontiguousarray(F, dtype=np.float64)))
+    out = np.zeros((total,) + tuple(F.shape[1:]), dtype=np.float64)
+    for s_lo, s_F in shares:
+        out[s_lo : s_lo + s_F.shape[0]] = s_F
+    return out
+
+
+def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30):
+    """Projected quantum kernel (Huang et al., Nat. Commun. 12, 2631 (2021)) of the same states as ``build_kernel_matrix``:
+        K[j, i] = exp(-g sum_k ||rho_k(X_i) - rho_k(Y_j)||_F^2) = exp(-g/2 sum_k |F(X_i)[k] - F(Y_j)[k]|^2),
+    rho_k = the one-qubit reduced density matrix of qubit k, F[k] = its Bloch vector (<X_k>, <Y_k>, <Z_k>); ``Y=None`` means
+    ``Y = X``, ``pqk_gamma=None`` means g = 1 / n_qubits.  Each rank builds its share of the states (the builder policy of
+    ``build_kernel_matrix``), computes their Bloch vectors on its device and all-gathers them (3 n reals per state, never an
+    MPS); rank 0 computes K on its GPU and returns the ``len(Y) x len(X)`` matrix, the other ranks return ``None``."""
+    if Y is not None and len(X) < len(Y):
+        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    if pqk_gamma is not None:
+        _engine.projected_gamma(pqk_gamma, 1)  # ValueError unless > 0 and finite
+    X = np.asarray(X, dtype=np.float64)
+    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
+    fidelity = 1.0 - float(truncation_error)
+
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: the projected kernel has no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    n_qubits = int(ansatz.num_qubits)
+    prof = {}
+    t_start = time.perf_counter()
+    if is_root:
+        prof["n_procs"] = [n_procs, "gpus"]
+        prof["lenX"] = [len(X), "entries"]
+        prof["lenY"] = [None if Y is None else len(Y), "entries"]
+
+    ctx = _engine.default_context(device_id)
+    shares, sim_secs, fids, chis, feat_secs = [], [], [], [], 0.0
+    for label, points in (("X", X), ("Y", Y)):
+        if points is None:
+            continue
+        _say(is_root, f"\nContracting the MPS of the circuits from the {label} dataset...")
+        lo, local, secs, fid = _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, device_id, host_workers)
+        sim_secs += secs
+        fids += fid
+        ctx.trim()  # the device builder's arena goes back before the local sweep needs memory
+        t0 = time.perf_counter()
+        if local is None:
+            F, chi = np.zeros((0, n_qubits, 3), dtype=np.float64), np.zeros(0)
+        else:
+            F, chi = ctx.local_paulis(local), local.dims.max(axis=1)
+            local.close()
+        feat_secs += time.perf_counter() - t0
+        shares.append((lo, F, len(points)))
+        chis.append(chi)
+
+    t0 = time.perf_counter()
+    feats = [_gather_features(mpi_comm, lo, F, total) for lo, F, total in shares]
+    chi_all = [np.concatenate([np.asarray(c, dtype=np.float64) for c in comm_allgather(mpi_comm, chi)]) for chi in chis]
+    gather_secs = time.perf_counter() - t0
+    if not is_root:
+        return None
+    g = _engine.projected_gamma(pqk_gamma, n_qubits)
+    _say(True, "\nFinished contracting all MPS.\n\nCalculating projected kernel matrix...")
+    t0 = time.perf_counter()
+    kernel_mat = ctx.projected_gram(feats[0], None if Y is None else feats[1], g)
+    tiles = time.perf_counter() - t0
+
+    prof["r0_circ_gen"] = [0.0, "seconds"]
+    prof["r0_circ_sim"] = [sum(sim_secs), "seconds"]
+    if sim_secs:
+        prof["avg_circ_sim"] = [mean(sim_secs), "seconds"]
+        prof["median_circ_sim"] = [median(sim_secs), "seconds"]
+        prof["q1_circ_sim"] = [float(np.percentile(sim_secs, 25)), "seconds"]
+        prof["q3_circ_sim"] = [float(np.percentile(sim_secs, 75)), "seconds"]
+    prof["avg_fidelity"] = [sum(fids) / max(1, len(fids)), ""]
+    prof["ave max chi x"] = (float(chi_all[0].mean()) if chi_all[0].size else 0.0, "chi x")
+    chi_y = chi_all[-1] if Y is not None else chi_all[0]
+    prof["ave max chi y"] = (float(chi_y.mean()) if chi_y.size else 0.0, "chi y")
+    prof["r0_RR_recv"] = [gather_secs, "seconds"]  # the all-gather of the Bloch vectors
+    prof["pqk_gamma"] = [g, ""]
+    prof["pqk_features_time"] = [feat_secs, "seconds"]
+    prof["kernel_mat_time"] = [tiles, "seconds"]
+    prof["total_time"] = [time.perf_counter() - t_start, "seconds"]
+    if info_file is not None:
+        with open(info_file + ".json", "w") as fp:
+            json.dump(prof, fp, indent=4)
+    return kernel_mat

@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""Time the projected quantum kernel against the fidelity Gram on one MI355X, in one process: the config's states built by the
+device builder, then (each after a warm-up) ctx.gram(xs), ctx.local_paulis(xs) and ctx.projected_gram(F).  Prints one JSON line
+with the three times, the local sweep's algorithmic flops and its achieved TFLOP/s.
+usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+import qml_cutensornet_amd as Q  # noqa: E402
+from qml_cutensornet_amd import engine  # noqa: E402
+from qml_cutensornet_amd.data import synthetic_features  # noqa: E402
+
+
+def local_sweep_flops(dims):
+    """Algorithmic flops of the local sweep from the true bonds (8 per complex multiply-add).  Per site, l = chi_k, r = chi_k+1:
+    the T-shaped GEMM of each direction (forward: l x 2r over l; reversed: r x 2l over r) and three of the second shape (the
+    reversed chain's environment update, l x l over 2r, and the two W_s, r x 2r over l)."""
+    d = np.asarray(dims, dtype=np.float64)
+    l, r = d[:, :-1], d[:, 1:]
+    return float((8 * (l * 2 * r * l + r * 2 * l * r) + 8 * (l * l * 2 * r + 2 * r * 2 * r * l)).sum())
+
+
+def timed(fn, reps):
+    fn()  # warm-up
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append(time.perf_counter() - t0)
+    return out, 1e3 * float(np.median(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="cfg4", choices=("cfg3", "cfg4", "cfg5"))
+    ap.add_argument("--gamma", type=float, default=None, help="default 1.0 (0.1 for cfg5)")
+    ap.add_argument("--reps", type=int, default=3)
+    args = ap.parse_args()
+    gamma = args.gamma if args.gamma is not None else (0.1 if args.config == "cfg5" else 1.0)
+    n, reps, d, npts = bench.CONFIGS[args.config]
+    X = synthetic_features(npts, n, 5)
+    ans = Q.KernelStateAnsatz(n, reps, gamma, Q.entanglement_graph(n, d))
+    ctx = engine.Context(0)
+    t0 = time.perf_counter()
+    xs, states, info = ctx.build_share([ans.circuit_for_data(x) for x in X], 1.0 - 1e-16, max_bond=320)
+    if xs is None:
+        raise SystemExit(f"{len(info['dropped'])} states outgrew the device builder's bond cap")
+    build_s = time.perf_counter() - t0
+    ctx.trim()
+    K, gram_ms = timed(lambda: ctx.gram(xs), args.reps)
+    F, local_ms = timed(lambda: ctx.local_paulis(xs), args.reps)
+    KP, pgram_ms = timed(lambda: ctx.projected_gram(F), args.reps)
+    flops = local_sweep_flops(info["dims"])
+    off = ~np.eye(npts, dtype=bool)
+    print(json.dumps({
+        "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
+        "max_bond": int(info["dims"].max()), "build_s": round(build_s, 3),
+        "gram_ms": round(gram_ms, 3), "local_paulis_ms": round(local_ms, 3), "projected_gram_ms": round(pgram_ms, 3),
+        "local_over_gram": round(local_ms / gram_ms, 4),
+        "local_flops": flops, "local_tflops": round(flops / (local_ms * 1e-3) / 1e12, 3),
+        "median_offdiag_fidelity_K": float(np.median(K[off])), "median_offdiag_pqk": float(np.median(KP[off])),
+    }), flush=True)
+    xs.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
