@@ -1799,7 +1799,7 @@ int qk_lab_launch(qk_ctx* c, int variant, const SweepArgs& a, int grid, int n_si
       qk_sweep_flat_kernel<64, 16, false><<<dim3(grid), dim3(WG_THREADS), lds_b, c->stream>>>(a);
       break;
     case 9:  // diagnostic: instrumented flat pipeline (qk_debug_profile)
-      HIP_TRY(hipMemsetAsync(c->prof, 0, 8 * sizeof(unsigned long long), c->stream));
+      HIP_TRY(hipMemsetAsync(c->prof.get(), 0, 8 * sizeof(unsigned long long), c->stream));
       qk_sweep_flat_kernel<64, 16, true><<<dim3(grid), dim3(WG_THREADS), lds_b, c->stream>>>(a);
       break;
     case 14: {  // group sweep: up to GMAX pairs sharing the x state per workgroup
@@ -1817,7 +1817,7 @@ int qk_lab_launch(qk_ctx* c, int variant, const SweepArgs& a, int grid, int n_si
       break;
     }
     case 19:  // diagnostic: instrumented shipped kernel
-      HIP_TRY(hipMemsetAsync(c->prof, 0, 8 * sizeof(unsigned long long), c->stream));
+      HIP_TRY(hipMemsetAsync(c->prof.get(), 0, 8 * sizeof(unsigned long long), c->stream));
       qk_sweep_deep_kernel<64, 16, 4, 8, 64, true><<<dim3(grid), dim3(512), lds_deep, c->stream>>>(a);
       break;
     case 12:  // two-step-deep prefetch, 4 waves
@@ -1848,7 +1848,7 @@ extern "C" int qk_debug_profile(qk_ctx* c, unsigned long long* out8) {
   if (!c || !out8) return fail(QK_EINVAL, "qk_debug_profile: null argument");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(out8, c->prof, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out8, c->prof.get(), 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return QK_OK;
 }
 

@@ -25,6 +25,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
+#include <new>
 
 namespace {
 typedef double cd __attribute__((ext_vector_type(2)));  // complex128 as (re, im); a native vector so that LDS-typed pointers work
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(256) void qk_pack_built_kernel(const cd* __restrict
 struct qk_built {
   qk_ctx* ctx = nullptr;
   int n_states = 0, n_qubits = 0;
-  cd* heap = nullptr;
+  QkDevBuf heap;  // cd: the packed states
   std::vector<int32_t> dims;
   std::vector<double> fidelity;
   std::vector<double> secs;  // workgroup time per state
@@ -119,6 +121,7 @@ struct qk_built {
 
 extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
                             const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, qk_built** out) {
+  static const char* what = "qk_build_mps";
   if (!c || !op || !q0 || !alpha || !out) return qk_fail(QK_EINVAL, "qk_build_mps: null argument");
   if (n_states <= 0 || n_qubits <= 0 || n_ops < 0) return qk_fail(QK_EINVAL, "qk_build_mps: empty problem (%d states, %d qubits, %d gates)", n_states, n_qubits, n_ops);
   if (max_bond < 2 || max_bond > 1024) return qk_fail(QK_EINVAL, "qk_build_mps: max_bond %d outside 2..1024", max_bond);
@@ -169,63 +172,28 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
   if (const char* v = std::getenv("QK_BUILD_HEAP_GB")) heap_lim = std::min(0.45 * (double)free_b, std::atof(v) * 1073741824.0) / (double)sizeof(cd);
   const size_t heap_cap = (size_t)std::max(1024.0, std::min(heap_want, heap_lim));
   const double t_host0 = (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-6;
-  cd *arena = nullptr, *work = nullptr, *heap = nullptr;
-  int8_t* d_op = nullptr;
-  int32_t* d_q0 = nullptr;
-  double *d_alpha = nullptr, *d_fid = nullptr, *d_secs = nullptr;
-  int32_t* d_dims = nullptr;
-  long long* d_offs = nullptr;
-  unsigned long long* d_ctr = nullptr;  // [0] state counter, [1] heap top
-  int* d_err = nullptr;
-  int32_t* d_order = nullptr;
-  auto release = [&]() {
-    (void)hipFree(d_op), (void)hipFree(d_q0), (void)hipFree(d_alpha), (void)hipFree(d_fid), (void)hipFree(d_secs);
-    (void)hipFree(d_dims), (void)hipFree(d_offs), (void)hipFree(d_ctr), (void)hipFree(d_err), (void)hipFree(d_order);
-  };
-#define BUILD_TRY(expr)                                                                                   \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess) {                                                                               \
-      release();                                                                                          \
-      (void)hipFree(heap);                                                                                \
-      return qk_fail(QK_EDEVICE, "qk_build_mps: %s failed: %s", #expr, hipGetErrorString(e_));            \
-    }                                                                                                     \
-  } while (0)
   // the per-workgroup arena and workspace (tens of GB at large bond caps: allocating and releasing them costs seconds) stay with
   // the context between calls -- build_kernel_matrix builds the X and the Y share one after the other -- and go with it
-  {
-    const size_t arena_b = (size_t)grid * n_qubits * 2 * cap * cap * sizeof(cd), work_b = (size_t)grid * (4 * wslot + wtab) * sizeof(cd);
-    if (c->build_arena_bytes < arena_b) {
-      if (c->build_arena) (void)hipFree(c->build_arena);
-      c->build_arena = nullptr, c->build_arena_bytes = 0;
-      BUILD_TRY(hipMalloc(&c->build_arena, arena_b));
-      c->build_arena_bytes = arena_b;
-    }
-    if (c->build_work_bytes < work_b) {
-      if (c->build_work) (void)hipFree(c->build_work);
-      c->build_work = nullptr, c->build_work_bytes = 0;
-      BUILD_TRY(hipMalloc(&c->build_work, work_b));
-      c->build_work_bytes = work_b;
-    }
-    arena = static_cast<cd*>(c->build_arena), work = static_cast<cd*>(c->build_work);
-  }
-  BUILD_TRY(hipMalloc(&heap, heap_cap * sizeof(cd)));
-  BUILD_TRY(hipMalloc(&d_op, std::max(1, n_ops)));
-  BUILD_TRY(hipMalloc(&d_q0, (size_t)std::max(1, n_ops) * sizeof(int32_t)));
-  BUILD_TRY(hipMalloc(&d_alpha, (size_t)n_states * std::max(1, n_ops) * sizeof(double)));
-  BUILD_TRY(hipMalloc(&d_fid, (size_t)n_states * sizeof(double)));
-  BUILD_TRY(hipMalloc(&d_secs, (size_t)n_states * sizeof(double)));
-  BUILD_TRY(hipMalloc(&d_dims, (size_t)n_states * (n_qubits + 1) * sizeof(int32_t)));
-  BUILD_TRY(hipMalloc(&d_offs, (size_t)n_states * sizeof(long long)));
-  BUILD_TRY(hipMalloc(&d_ctr, 2 * sizeof(unsigned long long)));
-  BUILD_TRY(hipMalloc(&d_err, 32 * sizeof(int)));
+  HIP_TRY_AS(what, c->build_arena.ensure((size_t)grid * n_qubits * 2 * cap * cap * sizeof(cd)));
+  HIP_TRY_AS(what, c->build_work.ensure((size_t)grid * (4 * wslot + wtab) * sizeof(cd)));
+  QkDevBuf heap, d_op, d_q0, d_alpha, d_fid, d_secs, d_dims, d_offs, d_ctr, d_err, d_order;  // d_ctr: [0] state counter, [1] heap top
+  HIP_TRY_AS(what, heap.alloc(heap_cap * sizeof(cd)));
+  HIP_TRY_AS(what, d_op.alloc(std::max(1, n_ops)));
+  HIP_TRY_AS(what, d_q0.alloc((size_t)std::max(1, n_ops) * sizeof(int32_t)));
+  HIP_TRY_AS(what, d_alpha.alloc((size_t)n_states * std::max(1, n_ops) * sizeof(double)));
+  HIP_TRY_AS(what, d_fid.alloc((size_t)n_states * sizeof(double)));
+  HIP_TRY_AS(what, d_secs.alloc((size_t)n_states * sizeof(double)));
+  HIP_TRY_AS(what, d_dims.alloc((size_t)n_states * (n_qubits + 1) * sizeof(int32_t)));
+  HIP_TRY_AS(what, d_offs.alloc((size_t)n_states * sizeof(long long)));
+  HIP_TRY_AS(what, d_ctr.alloc(2 * sizeof(unsigned long long)));
+  HIP_TRY_AS(what, d_err.alloc(32 * sizeof(int)));
   if (n_ops > 0) {
-    BUILD_TRY(hipMemcpyAsync(d_op, op, n_ops, hipMemcpyHostToDevice, c->stream));
-    BUILD_TRY(hipMemcpyAsync(d_q0, q0, (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    BUILD_TRY(hipMemcpyAsync(d_alpha, alpha, (size_t)n_states * n_ops * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_op.get(), op, n_ops, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_q0.get(), q0, (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_alpha.get(), alpha, (size_t)n_states * n_ops * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
-  BUILD_TRY(hipMemsetAsync(d_ctr, 0, 2 * sizeof(unsigned long long), c->stream));
-  BUILD_TRY(hipMemsetAsync(d_err, 0, 32 * sizeof(int), c->stream));
+  HIP_TRY_AS(what, hipMemsetAsync(d_ctr.get(), 0, 2 * sizeof(unsigned long long), c->stream));
+  HIP_TRY_AS(what, hipMemsetAsync(d_err.get(), 0, 32 * sizeof(int), c->stream));
   // Queue order: longest expected first.  The cost of a state grows with its bonds, and those with the entangling power
   // of its XXPhase / YYPhase / ZZPhase gates, sin^2(pi alpha) summed over the gates -- a cheap proxy that keeps the tail of the launch short.
   std::vector<int32_t> order(n_states);
@@ -240,27 +208,29 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
     for (int s = 0; s < n_states; ++s) order[s] = s;
     if (!std::getenv("QK_BUILD_NO_ORDER")) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return proxy[x] > proxy[y]; });
   }
-  BUILD_TRY(hipMalloc(&d_order, (size_t)n_states * sizeof(int32_t)));
-  BUILD_TRY(hipMemcpyAsync(d_order, order.data(), (size_t)n_states * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY_AS(what, d_order.alloc((size_t)n_states * sizeof(int32_t)));
+  HIP_TRY_AS(what, hipMemcpyAsync(d_order.get(), order.data(), (size_t)n_states * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   BuildArgs a;
-  a.order = d_order;
+  a.order = d_order.get<int32_t>();
   a.n_states = n_states, a.n_qubits = n_qubits, a.n_ops = n_ops, a.cap = cap;
-  a.op = d_op, a.q0 = d_q0, a.alpha = d_alpha;
+  a.op = d_op.get<int8_t>(), a.q0 = d_q0.get<int32_t>(), a.alpha = d_alpha.get<double>();
   a.budget = trunc_budget, a.zero = value_of_zero;
-  a.arena = arena, a.work = work, a.heap = heap, a.heap_cap = heap_cap, a.heap_top = d_ctr + 1;
-  a.dims_out = d_dims, a.fid_out = d_fid, a.secs_out = d_secs, a.offs_out = d_offs, a.counter = d_ctr, a.error = d_err;
+  a.arena = c->build_arena.get<cd>(), a.work = c->build_work.get<cd>(), a.heap = heap.get<cd>(), a.heap_cap = heap_cap;
+  a.counter = d_ctr.get<unsigned long long>(), a.heap_top = a.counter + 1;
+  a.dims_out = d_dims.get<int32_t>(), a.fid_out = d_fid.get<double>(), a.secs_out = d_secs.get<double>(), a.offs_out = d_offs.get<long long>(), a.error = d_err.get<int>();
   a.jl_offset = (int)(lds_meta / sizeof(double)), a.jl_elems = jl_elems;
   a.partial = (flags & QK_BUILD_PARTIAL) ? 1 : 0;
   a.truncate = (flags & QK_BUILD_TRUNCATE) ? 1 : 0;
   a.block = 1;
   if (const char* v = std::getenv("QK_BUILD_BLOCK")) a.block = std::atoi(v) != 0;
-  BUILD_TRY(hipEventRecord(c->ev0, c->stream));
+  HIP_TRY_AS(what, hipEventRecord(c->ev0, c->stream));
   if (wgs_variant == 4) qkb256::qk_build_kernel<4><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
   else if (wgs_variant == 2) qkb256::qk_build_kernel<2><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
   else qkb512::qk_build_kernel<1><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
-  BUILD_TRY(hipGetLastError());
-  BUILD_TRY(hipEventRecord(c->ev1, c->stream));
-  qk_built* b = new qk_built;
+  HIP_TRY_AS(what, hipGetLastError());
+  HIP_TRY_AS(what, hipEventRecord(c->ev1, c->stream));
+  std::unique_ptr<qk_built> b(new (std::nothrow) qk_built);
+  if (!b) return qk_fail(QK_ENOMEM, "qk_build_mps: out of memory");
   b->ctx = c, b->n_states = n_states, b->n_qubits = n_qubits;
   b->dims.resize((size_t)n_states * (n_qubits + 1));
   b->fidelity.resize(n_states);
@@ -269,26 +239,21 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
   int errv[32] = {0};
   unsigned long long ctr[2] = {0, 0};
   hipError_t e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipMemcpy(b->dims.data(), d_dims, b->dims.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(b->fidelity.data(), d_fid, (size_t)n_states * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(b->dims.data(), d_dims.get(), b->dims.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(b->fidelity.data(), d_fid.get(), (size_t)n_states * sizeof(double), hipMemcpyDeviceToHost);
   b->secs.resize(n_states);
-  if (e == hipSuccess) e = hipMemcpy(b->secs.data(), d_secs, (size_t)n_states * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(offs.data(), d_offs, (size_t)n_states * sizeof(long long), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(errv, d_err, sizeof(errv), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(b->secs.data(), d_secs.get(), (size_t)n_states * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(offs.data(), d_offs.get(), (size_t)n_states * sizeof(long long), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(errv, d_err.get(), sizeof(errv), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ctr, d_ctr.get(), sizeof(ctr), hipMemcpyDeviceToHost);
   float ms = 0;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
-  release();
   if (std::getenv("QK_BUILD_DEBUG")) {
     const double t_host1 = (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-6;
-    std::fprintf(stderr, "[qk_build_mps] host wall %.2f s for a %.2f s launch (arena %.1f GB, heap %.1f GB: allocation, upload, download, release)\n", t_host1 - t_host0, ms / 1e3,
+    std::fprintf(stderr, "[qk_build_mps] host wall %.2f s for a %.2f s launch (arena %.1f GB, heap %.1f GB: allocation, upload, download)\n", t_host1 - t_host0, ms / 1e3,
                  (double)grid * (double)per_wg / 1e9, (double)heap_cap * sizeof(cd) / 1e9);
   }
-  if (e != hipSuccess) {
-    (void)hipFree(heap);
-    delete b;
-    return qk_fail(QK_EDEVICE, "qk_build_mps: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return qk_fail(QK_EDEVICE, "qk_build_mps: %s", hipGetErrorString(e));
   const int err = errv[0];
   if (std::getenv("QK_BUILD_DEBUG"))
     std::fprintf(stderr, "[qk_build_mps] %d states, grid %lld x %d threads, %.1f ms; Jacobi: %d factorisations, %.2f sweeps on average, %d at most, %d unconverged, %d in LDS / %d from L2; error bits %d\n",
@@ -318,8 +283,6 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
                  steps ? (double)ticks / 100.0 / (double)steps : 0.0, steps);
   }
   if (err) {
-    (void)hipFree(heap);
-    delete b;
     if (err & ERR_OP) return qk_fail(QK_EINVAL, "qk_build_mps: unknown gate op code (valid: 0..%d)", N_OPS - 1);
     if (err & ERR_GATE) return qk_fail(QK_EINVAL, "qk_build_mps: gate on a qubit outside the register");
     if (err & ERR_BOND) return qk_fail(QK_EINVAL, "qk_build_mps: a bond grew beyond max_bond = %d", cap);
@@ -327,10 +290,10 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
     return qk_fail(QK_EDEVICE, "qk_build_mps: a Jacobi factorisation did not converge in %d sweeps", MAX_SWEEPS);
   }
   for (int s = 0; s < n_states; ++s) b->offsets[s] = offs[s];
-  b->heap = heap;
+  b->heap = std::move(heap);
   b->total = (int64_t)ctr[1];
   b->kernel_ms = ms;
-  *out = b;
+  *out = b.release();
   return QK_OK;
 }
 
@@ -347,7 +310,7 @@ extern "C" int qk_built_info(const qk_built* b, int32_t* dims, double* fidelity,
 extern "C" int qk_built_download(const qk_built* b, double* host) {
   if (!b || !host) return qk_fail(QK_EINVAL, "qk_built_download: null argument");
   HIP_TRY(hipSetDevice(b->ctx->device));
-  HIP_TRY(hipMemcpy(host, b->heap, (size_t)b->total * sizeof(cd), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(host, b->heap.get(), (size_t)b->total * sizeof(cd), hipMemcpyDeviceToHost));
   return QK_OK;
 }
 
@@ -376,31 +339,26 @@ extern "C" int qk_mps_set_from_built(qk_ctx* c, const qk_built* b, qk_mps_set** 
       total += 2ll * pad[(size_t)s * stride + k] * 2 * pad[(size_t)s * stride + k + 1];
     }
   }
-  qk_mps_set* m = new qk_mps_set;
-  m->ctx = c, m->n_states = ns, m->n_sites = n, m->max_pad = max_pad;
+  qk_mps_set* m = nullptr;
+  const int rc = qk_mps_set_alloc(c, ns, n, total * (long long)sizeof(double), 64, &m, "qk_mps_set_from_built");
+  if (rc != QK_OK) return rc;
+  m->max_pad = max_pad;
   m->dims_true = b->dims;
-  m->bytes = total * (long long)sizeof(double);
-  long long* d_src = nullptr;
-  hipError_t e = hipMalloc(&m->d_data, (size_t)m->bytes);
-  if (e == hipSuccess) e = hipMemsetAsync(m->d_data, 0, (size_t)m->bytes, c->stream);
-  if (e == hipSuccess) e = hipMalloc(&m->d_dims, pad.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&m->d_true, pad.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&m->d_offs, dst.size() * sizeof(int64_t));
-  if (e == hipSuccess) e = hipMalloc(&d_src, src.size() * sizeof(long long));
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_dims, pad.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_true, b->dims.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_offs, dst.data(), dst.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_src, src.data(), src.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream);
+  QkDevBuf d_src;
+  hipError_t e = hipMemsetAsync(m->d_data.get(), 0, (size_t)m->bytes, c->stream);
+  if (e == hipSuccess) e = d_src.alloc(src.size() * sizeof(long long));
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_dims.get(), pad.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_true.get(), b->dims.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_offs.get(), dst.data(), dst.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_src.get(), src.data(), src.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
-    qk_pack_built_kernel<<<dim3((unsigned)(ns * n)), dim3(256), 0, c->stream>>>(b->heap, d_src, reinterpret_cast<const long long*>(m->d_offs), m->d_true,
-                                                                              m->d_dims, n, m->d_data);
+    qk_pack_built_kernel<<<dim3((unsigned)(ns * n)), dim3(256), 0, c->stream>>>(b->heap.get<cd>(), d_src.get<long long>(), m->d_offs.get<long long>(), m->d_true.get<int32_t>(),
+                                                                              m->d_dims.get<int32_t>(), n, m->d_data.get<double>());
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_src);
   if (e != hipSuccess) {
-    (void)hipFree(m->d_data), (void)hipFree(m->d_dims), (void)hipFree(m->d_true), (void)hipFree(m->d_offs);
-    delete m;
+    qk_mps_set_destroy(m);
     return qk_fail(QK_EDEVICE, "qk_mps_set_from_built: %s", hipGetErrorString(e));
   }
   *out = m;
@@ -409,7 +367,6 @@ extern "C" int qk_mps_set_from_built(qk_ctx* c, const qk_built* b, qk_mps_set** 
 
 extern "C" int qk_built_destroy(qk_built* b) {
   if (!b) return QK_OK;
-  if (b->heap) (void)hipFree(b->heap);
   delete b;
   return QK_OK;
 }
@@ -418,45 +375,40 @@ extern "C" int qk_debug_jacobi_precond(qk_ctx* c, int32_t p, int32_t q, double* 
   if (!c || !a_inout || !v_out || !sig_out || !ord_out) return qk_fail(QK_EINVAL, "qk_debug_jacobi_precond: null argument");
   if (p < 1 || q < 16 || q > 1024 || p > 64 * qkb256::MGS_R) return qk_fail(QK_EINVAL, "qk_debug_jacobi_precond: bad shape %d x %d (16 <= q <= 1024, p <= %d)", p, q, 64 * qkb256::MGS_R);
   HIP_TRY(hipSetDevice(c->device));
-  struct Bufs {
-    cd *dA = nullptr, *dV = nullptr, *dS = nullptr, *dL = nullptr;
-    double* dSig = nullptr;
-    int *dO = nullptr, *dE = nullptr, *dC = nullptr;
-    ~Bufs() { (void)hipFree(dA), (void)hipFree(dV), (void)hipFree(dS), (void)hipFree(dL), (void)hipFree(dSig), (void)hipFree(dO), (void)hipFree(dE), (void)hipFree(dC); }
-  } b;
+  QkDevBuf dA, dV, dS, dL, dSig, dO, dE, dC;  // cd: A, V, S, L; double: Sig; int: O, E, C
   const size_t lrows = (size_t)(q + 31) / 32 * 32, qpad = (size_t)(q + 15) / 16 * 16;
-  HIP_TRY(hipMalloc(&b.dA, (size_t)p * q * sizeof(cd)));
-  HIP_TRY(hipMalloc(&b.dV, (size_t)q * q * sizeof(cd)));
-  HIP_TRY(hipMalloc(&b.dS, (size_t)p * q * sizeof(cd)));
-  HIP_TRY(hipMalloc(&b.dL, lrows * qpad * sizeof(cd)));
-  HIP_TRY(hipMalloc(&b.dSig, (size_t)q * sizeof(double)));
-  HIP_TRY(hipMalloc(&b.dO, (size_t)q * sizeof(int)));
-  HIP_TRY(hipMalloc(&b.dE, 32 * sizeof(int)));
-  HIP_TRY(hipMalloc(&b.dC, (qpad / 8) * (qpad / 8) * sizeof(int)));
-  HIP_TRY(hipMemset(b.dE, 0, 32 * sizeof(int)));
-  HIP_TRY(hipMemcpy(b.dA, a_inout, (size_t)p * q * sizeof(cd), hipMemcpyHostToDevice));
+  HIP_TRY(dA.alloc((size_t)p * q * sizeof(cd)));
+  HIP_TRY(dV.alloc((size_t)q * q * sizeof(cd)));
+  HIP_TRY(dS.alloc((size_t)p * q * sizeof(cd)));
+  HIP_TRY(dL.alloc(lrows * qpad * sizeof(cd)));
+  HIP_TRY(dSig.alloc((size_t)q * sizeof(double)));
+  HIP_TRY(dO.alloc((size_t)q * sizeof(int)));
+  HIP_TRY(dE.alloc(32 * sizeof(int)));
+  HIP_TRY(dC.alloc((qpad / 8) * (qpad / 8) * sizeof(int)));
+  HIP_TRY(hipMemset(dE.get(), 0, 32 * sizeof(int)));
+  HIP_TRY(hipMemcpy(dA.get(), a_inout, (size_t)p * q * sizeof(cd), hipMemcpyHostToDevice));
   const size_t lds_head = (size_t)(((q * 12 + 15) / 16) * 2 + 2) * sizeof(double);
   const bool wide = std::getenv("QK_BUILD_WGS") && std::atoi(std::getenv("QK_BUILD_WGS")) <= 1;  // the 512-thread variant of the builder
   const size_t lds = (wide ? 152 : 72) * 1024;
   const int lds_elems = (int)((lds - lds_head) / sizeof(cd));
   const size_t need = lds_head + (size_t)(wide ? qkb512::NWV * qkb512::BLK_LDS : qkb256::NWV * qkb256::BLK_LDS) * sizeof(cd);
   if (need > lds) return qk_fail(QK_EINVAL, "qk_debug_jacobi_precond: q = %d needs %zu bytes of LDS", q, need);
-  int* const chk = std::getenv("QK_BUILD_NO_SKIP") ? nullptr : b.dC;
+  int* const chk = std::getenv("QK_BUILD_NO_SKIP") ? nullptr : dC.get<int>();
   if (wide) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb512::qk_jacobi_precond_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-    qkb512::qk_jacobi_precond_kernel<<<dim3(1), dim3(512), lds, c->stream>>>(b.dA, p, q, b.dV, b.dSig, b.dO, b.dE, b.dS, b.dL, lds_elems, chk);
+    qkb512::qk_jacobi_precond_kernel<<<dim3(1), dim3(512), lds, c->stream>>>(dA.get<cd>(), p, q, dV.get<cd>(), dSig.get<double>(), dO.get<int>(), dE.get<int>(), dS.get<cd>(), dL.get<cd>(), lds_elems, chk);
   } else {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb256::qk_jacobi_precond_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 76 * 1024));
-    qkb256::qk_jacobi_precond_kernel<<<dim3(1), dim3(256), lds, c->stream>>>(b.dA, p, q, b.dV, b.dSig, b.dO, b.dE, b.dS, b.dL, lds_elems, chk);
+    qkb256::qk_jacobi_precond_kernel<<<dim3(1), dim3(256), lds, c->stream>>>(dA.get<cd>(), p, q, dV.get<cd>(), dSig.get<double>(), dO.get<int>(), dE.get<int>(), dS.get<cd>(), dL.get<cd>(), lds_elems, chk);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(a_inout, b.dA, (size_t)p * q * sizeof(cd), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(v_out, b.dV, (size_t)q * q * sizeof(cd), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(sig_out, b.dSig, (size_t)q * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(ord_out, b.dO, (size_t)q * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(a_inout, dA.get(), (size_t)p * q * sizeof(cd), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(v_out, dV.get(), (size_t)q * q * sizeof(cd), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(sig_out, dSig.get(), (size_t)q * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ord_out, dO.get(), (size_t)q * sizeof(int), hipMemcpyDeviceToHost));
   int errv[32] = {0};
-  HIP_TRY(hipMemcpy(errv, b.dE, sizeof errv, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(errv, dE.get(), sizeof errv, hipMemcpyDeviceToHost));
   if (stats_out) {  // [0] sweeps, then 100 MHz ticks (low words): [1] all, [2] sort + copy, [3] Gram-Schmidt, [4] sweeps, [5] V and W = A V
     stats_out[0] = errv[2];
     stats_out[1] = errv[14], stats_out[2] = errv[16], stats_out[3] = errv[18], stats_out[4] = errv[20], stats_out[5] = errv[22];
@@ -469,26 +421,23 @@ extern "C" int qk_debug_jacobi(qk_ctx* c, int32_t p, int32_t q, double* a_inout,
   if (!c || !a_inout || !v_out || !sig_out || !ord_out) return qk_fail(QK_EINVAL, "qk_debug_jacobi: null argument");
   if (p < 1 || q < 1 || q > 2048) return qk_fail(QK_EINVAL, "qk_debug_jacobi: bad shape %d x %d", p, q);
   HIP_TRY(hipSetDevice(c->device));
-  cd *dA = nullptr, *dV = nullptr;
-  double* dS = nullptr;
-  int *dO = nullptr, *dE = nullptr;
-  HIP_TRY(hipMalloc(&dA, (size_t)p * q * sizeof(cd)));
-  HIP_TRY(hipMalloc(&dV, (size_t)q * q * sizeof(cd)));
-  HIP_TRY(hipMalloc(&dS, (size_t)q * sizeof(double)));
-  HIP_TRY(hipMalloc(&dO, (size_t)q * sizeof(int)));
-  HIP_TRY(hipMalloc(&dE, 32 * sizeof(int)));
-  HIP_TRY(hipMemset(dE, 0, 32 * sizeof(int)));
-  HIP_TRY(hipMemcpy(dA, a_inout, (size_t)p * q * sizeof(cd), hipMemcpyHostToDevice));
-  qkb256::qk_jacobi_kernel<<<dim3(1), dim3(256), (size_t)q * (sizeof(double) + sizeof(int)) + 16, c->stream>>>(dA, p, q, dV, dS, dO, dE);
+  QkDevBuf dA, dV, dS, dO, dE;  // cd: A, V; double: S; int: O, E
+  HIP_TRY(dA.alloc((size_t)p * q * sizeof(cd)));
+  HIP_TRY(dV.alloc((size_t)q * q * sizeof(cd)));
+  HIP_TRY(dS.alloc((size_t)q * sizeof(double)));
+  HIP_TRY(dO.alloc((size_t)q * sizeof(int)));
+  HIP_TRY(dE.alloc(32 * sizeof(int)));
+  HIP_TRY(hipMemset(dE.get(), 0, 32 * sizeof(int)));
+  HIP_TRY(hipMemcpy(dA.get(), a_inout, (size_t)p * q * sizeof(cd), hipMemcpyHostToDevice));
+  qkb256::qk_jacobi_kernel<<<dim3(1), dim3(256), (size_t)q * (sizeof(double) + sizeof(int)) + 16, c->stream>>>(dA.get<cd>(), p, q, dV.get<cd>(), dS.get<double>(), dO.get<int>(), dE.get<int>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(a_inout, dA, (size_t)p * q * sizeof(cd), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(v_out, dV, (size_t)q * q * sizeof(cd), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(sig_out, dS, (size_t)q * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(ord_out, dO, (size_t)q * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(a_inout, dA.get(), (size_t)p * q * sizeof(cd), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(v_out, dV.get(), (size_t)q * q * sizeof(cd), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(sig_out, dS.get(), (size_t)q * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ord_out, dO.get(), (size_t)q * sizeof(int), hipMemcpyDeviceToHost));
   int err = 0;
-  HIP_TRY(hipMemcpy(&err, dE, sizeof(int), hipMemcpyDeviceToHost));
-  (void)hipFree(dA), (void)hipFree(dV), (void)hipFree(dS), (void)hipFree(dO), (void)hipFree(dE);
+  HIP_TRY(hipMemcpy(&err, dE.get(), sizeof(int), hipMemcpyDeviceToHost));
   if (err) return qk_fail(QK_EDEVICE, "qk_debug_jacobi: no convergence in %d sweeps", MAX_SWEEPS);
   return QK_OK;
 }

@@ -60,28 +60,23 @@ Rccl& rccl() {
     if (r_ != ncclSuccess) return qk_fail(QK_EDEVICE, "%s failed: %s", #expr, rccl().GetErrorString(r_));       \
   } while (0)
 
-struct DevMem {  // device memory of one rank, released with the communicator or when the job changes
+struct RankMem {  // device memory of one rank, kept and regrown like the context's buffers; its device is made current before it is allocated or freed
   int device = 0;
-  void* p = nullptr;
-  size_t bytes = 0;
+  QkGrowBuf buf;
+  RankMem() = default;
+  RankMem(RankMem&&) = default;
+  ~RankMem() {
+    if (buf.buf) (void)hipSetDevice(device);  // (buf frees after this body)
+  }
   int ensure(const int dev, const size_t need) {
-    if (need <= bytes) return QK_OK;
-    release();
+    if (need <= buf.bytes) return QK_OK;
     device = dev;
     HIP_TRY(hipSetDevice(dev));
-    HIP_TRY(hipMalloc(&p, need));
-    bytes = need;
+    HIP_TRY(buf.ensure(need));
     return QK_OK;
   }
-  void release() {
-    if (p) {
-      (void)hipSetDevice(device);
-      (void)hipFree(p);
-    }
-    p = nullptr, bytes = 0;
-  }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
+  template <typename T = void>
+  T* get() const { return buf.get<T>(); }
 };
 
 }  // namespace
@@ -95,7 +90,7 @@ struct qk_comm {
   std::vector<const qk_mps_set*> job_x, job_y;
   std::vector<uint64_t> job_xid, job_yid;  // their uids: a destroyed set's address may be reused by another set
   std::vector<qk_plan*> plans;
-  std::vector<DevMem> vals, all_vals, all_pairs, k;
+  std::vector<RankMem> vals, all_vals, all_pairs, k;
   int64_t maxp = 0;
   qk_stats last_stats[16];
   double gather_ms = 0;
@@ -112,8 +107,6 @@ extern "C" int qk_comm_destroy(qk_comm* c) {
   for (int r = 0; r < (int)c->ctx.size(); ++r)
     if (c->ctx[(size_t)r]) (void)qk_ctx_synchronize(c->ctx[(size_t)r]);
   drop_job(c);
-  for (auto* v : {&c->vals, &c->all_vals, &c->all_pairs, &c->k})
-    for (DevMem& m : *v) m.release();
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   for (ncclComm_t nc : c->nccl)
@@ -204,34 +197,23 @@ extern "C" int qk_mps_set_allgather(qk_comm* c, qk_mps_set* const* local, const 
   for (int s = 0; s < total; ++s)
     if (dims[(size_t)s * stride] != 1) return qk_fail(QK_EINVAL, "qk_mps_set_allgather: state %d belongs to no share", s);
   // send / receive buffers, the collective, the assembly
-  std::vector<DevMem> send((size_t)n), recv((size_t)n);
+  std::vector<RankMem> send((size_t)n), recv((size_t)n);
   int rc = QK_OK;
   for (int r = 0; r < n && rc == QK_OK; ++r) {
     rc = send[(size_t)r].ensure(c->devices[(size_t)r], (size_t)mx * sizeof(double));
     if (rc == QK_OK) rc = recv[(size_t)r].ensure(c->devices[(size_t)r], (size_t)n * mx * sizeof(double));
-    if (rc == QK_OK && local[r]) rc = qk_mps_set_copy_image(local[r], send[(size_t)r].as<double>(), mx);  // returns after the copy
+    if (rc == QK_OK && local[r]) rc = qk_mps_set_copy_image(local[r], send[(size_t)r].get<double>(), mx);  // returns after the copy
   }
-  auto cleanup = [&] {
-    for (DevMem& m : send) m.release();
-    for (DevMem& m : recv) m.release();
-  };
-  if (rc != QK_OK) {
-    cleanup();
-    return rc;
-  }
+  if (rc != QK_OK) return rc;
   qk_range_push("qk:allgather_sets");
   ncclResult_t nr = rccl().GroupStart();
-  for (int r = 0; r < n && nr == ncclSuccess; ++r) nr = rccl().AllGather(send[(size_t)r].p, recv[(size_t)r].p, (size_t)mx, ncclDouble, c->nccl[(size_t)r], c->ctx[(size_t)r]->stream);
+  for (int r = 0; r < n && nr == ncclSuccess; ++r) nr = rccl().AllGather(send[(size_t)r].get(), recv[(size_t)r].get(), (size_t)mx, ncclDouble, c->nccl[(size_t)r], c->ctx[(size_t)r]->stream);
   const ncclResult_t ne = rccl().GroupEnd();
   if (nr == ncclSuccess) nr = ne;
   for (int r = 0; r < n; ++r) (void)qk_ctx_synchronize(c->ctx[(size_t)r]);
   qk_range_pop();
-  if (nr != ncclSuccess) {
-    cleanup();
-    return qk_fail(QK_EDEVICE, "qk_mps_set_allgather: ncclAllGather failed: %s", rccl().GetErrorString(nr));
-  }
-  for (int r = 0; r < n && rc == QK_OK; ++r) rc = qk_mps_set_from_packed(c->ctx[(size_t)r], total, n_sites, dims.data(), offs.data(), recv[(size_t)r].as<double>(), (int64_t)n * mx, &full_out[r]);
-  cleanup();
+  if (nr != ncclSuccess) return qk_fail(QK_EDEVICE, "qk_mps_set_allgather: ncclAllGather failed: %s", rccl().GetErrorString(nr));
+  for (int r = 0; r < n && rc == QK_OK; ++r) rc = qk_mps_set_from_packed(c->ctx[(size_t)r], total, n_sites, dims.data(), offs.data(), recv[(size_t)r].get<double>(), (int64_t)n * mx, &full_out[r]);
   if (rc != QK_OK)
     for (int r = 0; r < n; ++r) {
       qk_mps_set_destroy(full_out[r]);
@@ -290,8 +272,8 @@ static int prepare_job(qk_comm* c, qk_mps_set* const* xs, qk_mps_set* const* ys)
       return rc;
     }
     hipError_t e = hipSetDevice(d);
-    if (e == hipSuccess) e = hipMemcpy(c->all_pairs[(size_t)r].p, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(c->vals[(size_t)r].p, 0, (size_t)c->maxp * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(c->all_pairs[(size_t)r].get(), all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(c->vals[(size_t)r].get(), 0, (size_t)c->maxp * sizeof(double));
     if (e != hipSuccess) {
       drop_job(c);
       return qk_fail(QK_EDEVICE, "qk_gram_sharded: pair table of device %d: %s", d, hipGetErrorString(e));
@@ -328,8 +310,8 @@ extern "C" int qk_gram_sharded(qk_comm* c, qk_mps_set* const* xsets, qk_mps_set*
     QkRangeGuard range_("qk:sharded_sweep");
     for (int r = 0; r < n && rc == QK_OK; ++r) {
       rc = hip_ok(hipSetDevice(c->devices[(size_t)r]), "hipSetDevice");
-      if (rc == QK_OK) rc = hip_ok(hipMemsetAsync(c->k[(size_t)r].p, 0, (size_t)nx * ny * sizeof(double), c->ctx[(size_t)r]->stream), "hipMemsetAsync");
-      if (rc == QK_OK) rc = qk_gram_values(c->ctx[(size_t)r], xsets[r], sym ? nullptr : ysets[r], c->plans[(size_t)r], c->vals[(size_t)r].as<double>(), nullptr);
+      if (rc == QK_OK) rc = hip_ok(hipMemsetAsync(c->k[(size_t)r].get(), 0, (size_t)nx * ny * sizeof(double), c->ctx[(size_t)r]->stream), "hipMemsetAsync");
+      if (rc == QK_OK) rc = qk_gram_values(c->ctx[(size_t)r], xsets[r], sym ? nullptr : ysets[r], c->plans[(size_t)r], c->vals[(size_t)r].get<double>(), nullptr);
     }
   }
   if (rc != QK_OK) return sharded_fail(c, rc);
@@ -341,7 +323,7 @@ extern "C" int qk_gram_sharded(qk_comm* c, qk_mps_set* const* xsets, qk_mps_set*
     if (rc != QK_OK) return sharded_fail(c, rc);
     ncclResult_t nr = rccl().GroupStart();
     for (int r = 0; r < n && nr == ncclSuccess; ++r)
-      nr = rccl().AllGather(c->vals[(size_t)r].p, c->all_vals[(size_t)r].p, (size_t)c->maxp, ncclDouble, c->nccl[(size_t)r], c->ctx[(size_t)r]->stream);
+      nr = rccl().AllGather(c->vals[(size_t)r].get(), c->all_vals[(size_t)r].get(), (size_t)c->maxp, ncclDouble, c->nccl[(size_t)r], c->ctx[(size_t)r]->stream);
     const ncclResult_t ne = rccl().GroupEnd();
     if (nr == ncclSuccess) nr = ne;
     if (nr != ncclSuccess) return sharded_fail(c, qk_fail(QK_EDEVICE, "qk_gram_sharded: ncclAllGather failed: %s", rccl().GetErrorString(nr)));
@@ -351,11 +333,11 @@ extern "C" int qk_gram_sharded(qk_comm* c, qk_mps_set* const* xsets, qk_mps_set*
   }
   // 3. every device fills (and mirrors) its own dense K; rank 0's goes to the caller
   for (int r = 0; r < n && rc == QK_OK; ++r)
-    rc = qk_scatter(c->ctx[(size_t)r], c->all_pairs[(size_t)r].as<int32_t>(), c->all_vals[(size_t)r].as<double>(), (int64_t)n * c->maxp, c->k[(size_t)r].as<double>(), nx, sym ? 1 : 0);
+    rc = qk_scatter(c->ctx[(size_t)r], c->all_pairs[(size_t)r].get<int32_t>(), c->all_vals[(size_t)r].get<double>(), (int64_t)n * c->maxp, c->k[(size_t)r].get<double>(), nx, sym ? 1 : 0);
   if (rc == QK_OK && out_host) {
     rc = hip_ok(hipSetDevice(c->devices[0]), "hipSetDevice");
     if (rc == QK_OK)
-      rc = hip_ok(hipMemcpy2DAsync(out_host, (size_t)ld * sizeof(double), c->k[0].p, (size_t)nx * sizeof(double), (size_t)nx * sizeof(double), (size_t)ny, hipMemcpyDeviceToHost, c->ctx[0]->stream),
+      rc = hip_ok(hipMemcpy2DAsync(out_host, (size_t)ld * sizeof(double), c->k[0].get(), (size_t)nx * sizeof(double), (size_t)nx * sizeof(double), (size_t)ny, hipMemcpyDeviceToHost, c->ctx[0]->stream),
                   "hipMemcpy2DAsync");
   }
   if (rc != QK_OK) return sharded_fail(c, rc);
@@ -374,7 +356,7 @@ extern "C" int qk_gram_sharded(qk_comm* c, qk_mps_set* const* xsets, qk_mps_set*
 
 extern "C" int qk_comm_device_gram(qk_comm* c, int32_t rank, const double** k_dev) {
   if (!c || rank < 0 || rank >= c->n || !k_dev) return qk_fail(QK_EINVAL, "qk_comm_device_gram: bad argument");
-  *k_dev = c->k[(size_t)rank].as<double>();
+  *k_dev = c->k[(size_t)rank].get<double>();
   return QK_OK;
 }
 

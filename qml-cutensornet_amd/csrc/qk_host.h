@@ -2,12 +2,18 @@
 //   qkgram.hip    the C ABI, the planner and the shipped sweep kernels      } libqkgram.so
 //   qk_build.hip  the device MPS builder                                    }
 //   qk_local.hip  local Bloch vectors and the projected-kernel Gram          }
+//   qk_comm.hip   the multi-GPU entry points                                 }
 //   qk_lab.hip    experimental / diagnostic kernels for A/B measurements: only in lab/libqklab.so (-DQK_LAB, lab/tools)
+// Device memory has one kind of owner (qk_devmem.h): a QkDevBuf frees in its destructor, a QkGrowBuf is kept and regrown.  The
+// context and the sets below hold their device memory as such members, so no destroy / trim function keeps a list of pointers,
+// and a call's temporaries are local QkDevBufs: HIP_TRY may return from anywhere.  Kernels still take raw pointers (get<T>()).
 #pragma once
 #include "../../include/qkgram.h"
 #include "qk_plan.h"
 
 #include <hip/hip_runtime.h>
+
+#include "qk_devmem.h"
 
 #include <cstdint>
 #include <vector>
@@ -22,6 +28,11 @@ struct QkRangeGuard {  // a roctx range (qk_range_push / qk_range_pop) that clos
     hipError_t e_ = (expr);                                                                           \
     if (e_ != hipSuccess) return qk_fail(QK_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));  \
   } while (0)
+#define HIP_TRY_AS(what, expr) /* the same, with the entry point's name in front */                             \
+  do {                                                                                                          \
+    hipError_t e_ = (expr);                                                                                     \
+    if (e_ != hipSuccess) return qk_fail(QK_EDEVICE, "%s: %s failed: %s", what, #expr, hipGetErrorString(e_));  \
+  } while (0)
 
 struct qk_ctx {
   int device = 0;
@@ -32,24 +43,18 @@ struct qk_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mid = nullptr;  // ev_mid: between the two launches of a split sweep
   hipEvent_t ev_d = nullptr;  // at the start of qk_gram_values: what runs between it and ev0 are the kernels that make a set's derived images (first Gram of a set)
   bool ev_pending = false;
-  double* scratch = nullptr;
-  size_t scratch_bytes = 0;
-  unsigned long long* counter = nullptr;  // work-queue heads (QK_NQ_MAX of them, QK_QSTRIDE apart) + 2 x 4 tail clocks behind them
+  QkGrowBuf scratch;  // the sweep's per-workgroup X / T planes, kept between calls (qk_gram_values)
+  QkDevBuf counter;   // unsigned long long: work-queue heads (QK_NQ_MAX of them, QK_QSTRIDE apart) + 2 x 4 tail clocks behind them
   bool tail_pending = false;
-  unsigned long long* prof = nullptr;  // 8 cycle sums of the diagnostic variant
+  QkDevBuf prof;  // unsigned long long: 8 cycle sums of the diagnostic variant
   QkSweepPolicy policy;  // the switches of the sweep's choice of kernels (qk_plan.h), set by ctx_init
   qk_stats last{};
   // the device MPS builder's per-workgroup arena and workspace, kept between calls (qk_build.hip)
-  void* build_arena = nullptr;
-  size_t build_arena_bytes = 0;
-  void* build_work = nullptr;
-  size_t build_work_bytes = 0;
+  QkGrowBuf build_arena, build_work;
   // scratch of the workgroups that make a set's edge blocks (qk_edge_kernel), kept between calls
-  void* derive_tmp = nullptr;
-  size_t derive_tmp_bytes = 0;
+  QkGrowBuf derive_tmp;
   // the local sweep's tables, rho partial sums and per-state environments (qk_local.hip), kept between calls
-  void* local_scratch = nullptr;
-  size_t local_scratch_bytes = 0;
+  QkGrowBuf local_scratch;
 };
 
 uint64_t qk_next_uid();
@@ -59,28 +64,32 @@ struct qk_mps_set {
   uint64_t uid = qk_next_uid();  // unique per set of this process: caches keyed on a set's address also compare this (a freed address may come back)
   int n_states = 0, n_sites = 0, max_pad = 0;
   int precision = 64;         // bits of a real: 64 (complex128 planes) or 32 (complex64 planes, same element offsets)
-  double* d_data = nullptr;   // the planes; floats when precision == 32
-  double* d_il = nullptr;     // fp64 only, made on first use by the site-fused sweep: the same image with re/im interleaved (complex128), same offsets
-  int32_t* d_dims = nullptr;  // padded bonds [n_states][n_sites+1]
-  int32_t* d_true = nullptr;  // true bonds   [n_states][n_sites+1]
-  int64_t* d_offs = nullptr;  // re-plane offsets (doubles) [n_states][n_sites]
+  QkDevBuf d_data;  // double: the planes; floats when precision == 32
+  QkDevBuf d_il;    // double: made on first use by the site-fused sweep: the same image with re/im interleaved (complex128; complex64 of an fp32 set), same offsets
+  QkDevBuf d_dims;  // int32_t: padded bonds [n_states][n_sites+1]
+  QkDevBuf d_true;  // int32_t: true bonds   [n_states][n_sites+1]
+  QkDevBuf d_offs;  // int64_t: re-plane offsets (doubles) [n_states][n_sites]
   std::vector<int32_t> dims_true;
   int64_t bytes = 0;
   // edge blocks of the site-fused sweep (made on first use for the plan's edge_k; qk_device.h: SweepArgs.edge_k)
-  double* d_edge = nullptr;        // interleaved complex: per state the left block [2^k][pad(chi_k)], then the right block [2^k][pad(chi_{n-k})]
-  long long* d_edge_offs = nullptr;  // [n_states][2] element offsets
+  QkDevBuf d_edge;       // double: interleaved complex: per state the left block [2^k][pad(chi_k)], then the right block [2^k][pad(chi_{n-k})]
+  QkDevBuf d_edge_offs;  // long long: [n_states][2] element offsets
   int edge_k = 0;
   int64_t edge_bytes = 0;
   // merged image of the site-fused sweep (SweepArgs.merge_steps; made on first use for the plan's edge_k): the chain's sites [k, n - k)
   // contracted in twos, interleaved complex [l][4][r]
-  double* d_mg = nullptr;
-  int64_t* d_mg_offs = nullptr;  // offsets in doubles [n_states][mg_steps]
-  long long* d_mg_units = nullptr;  // first 16 x 16 block of each (state, step) in the numbering of qk_merge_kernel's units [n_states * mg_steps + 1]
+  QkDevBuf d_mg;        // double
+  QkDevBuf d_mg_offs;   // int64_t: offsets in doubles [n_states][mg_steps]
+  QkDevBuf d_mg_units;  // long long: first 16 x 16 block of each (state, step) in the numbering of qk_merge_kernel's units [n_states * mg_steps + 1]
   std::vector<long long> h_edge_offs, h_mg_units;  // host staging of the tables above (they outlive the asynchronous copies)
   std::vector<int64_t> h_mg_offs;
   int mg_k = -1, mg_steps = 0;
   int64_t mg_bytes = 0;
 };
+
+// the one allocator of a set (qkgram.hip): the object and its four device arrays (d_data of `data_bytes`, d_dims, d_true, d_offs),
+// nothing uploaded.  `who` names the entry point in the error text.  A constructor that fails later calls qk_mps_set_destroy.
+int qk_mps_set_alloc(qk_ctx* c, int n_states, int n_sites, int64_t data_bytes, int precision, qk_mps_set** out, const char* who);
 
 struct SweepArgs;
 // qk_lab.hip: raise the LDS limit of the lab kernels; launch lab variant `variant` (returns QK_EINVAL if it is not one)

@@ -259,32 +259,6 @@ __global__ __launch_bounds__(256) void qk_projected_gram_kernel(const double* fx
     }
 }
 
-struct DevMem {  // a device allocation released on every exit path
-  void* p = nullptr;
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-#define LOC_TRY(expr, what)                                                                                  \
-  do {                                                                                                       \
-    hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess) return qk_fail(QK_EDEVICE, "%s: %s failed: %s", what, #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-int ensure_buffer(void** p, size_t* have, size_t want) {
-  if (*have >= want) return QK_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr, *have = 0;
-  const hipError_t e = hipMalloc(p, want);
-  if (e != hipSuccess) {
-    *p = nullptr;
-    return qk_fail(QK_EDEVICE, "qk_local_paulis_host: hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
-  }
-  *have = want;
-  return QK_OK;
-}
-
 inline int pad16h(int x) { return (x + 15) / 16 * 16; }
 inline long long blocks64(long long m, long long n) { return ((m + 63) / 64) * ((n + 63) / 64); }
 
@@ -298,10 +272,10 @@ extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* ou
   const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
   if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: empty set", what);
   QkRangeGuard range_("qk:local_paulis");
-  LOC_TRY(hipSetDevice(c->device), what);
-  LOC_TRY(hipStreamSynchronize(c->stream), what);
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   std::vector<int64_t> offs((size_t)ns * n);
-  LOC_TRY(hipMemcpy(offs.data(), set->d_offs, offs.size() * sizeof(int64_t), hipMemcpyDeviceToHost), what);
+  HIP_TRY_AS(what, hipMemcpy(offs.data(), set->d_offs.get<int64_t>(), offs.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
   const int32_t* tru = set->dims_true.data();
   std::vector<int32_t> pad((size_t)ns * n1);
   std::vector<int> pmax(ns);
@@ -320,13 +294,13 @@ extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* ou
   const int max_chunks = set->max_pad / LOC_CHUNK;
   const long long part_per_state = (long long)n * max_chunks * 4;
   // memory bound of the per-state scratch: a quarter of what is free once the reversed image and the outputs exist
-  DevMem rev, dout, dnorm;
-  LOC_TRY(hipMalloc(&rev.p, (size_t)set->bytes), what);
-  LOC_TRY(hipMalloc(&dout.p, (size_t)ns * n * 3 * sizeof(double)), what);
-  LOC_TRY(hipMalloc(&dnorm.p, (size_t)ns * sizeof(double)), what);
+  QkDevBuf rev, dout, dnorm;
+  HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
+  HIP_TRY_AS(what, dout.alloc((size_t)ns * n * 3 * sizeof(double)));
+  HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
   size_t free_b = 0, total_b = 0;
-  LOC_TRY(hipMemGetInfo(&free_b, &total_b), what);
-  const long long budget = (long long)((free_b + c->local_scratch_bytes) / 4 / sizeof(double));
+  HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
+  const long long budget = (long long)((free_b + c->local_scratch.bytes) / 4 / sizeof(double));
   // batches: consecutive states while their scratch and rho partials fit the budget (at least one state per batch)
   std::vector<int> bstart{0};
   for (long long acc = 0, s = 0; s < ns; ++s) {
@@ -381,11 +355,8 @@ extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* ou
     const size_t b_roff = al(h_roff.size() * sizeof(int64_t)), b_tasks = al(tasks.size() * sizeof(int2));
     const size_t b_part = al((size_t)nb * part_per_state * sizeof(double)), b_scr = (size_t)tot * sizeof(double);
     const size_t b_tab = b_states + b_pmax + b_sbase + b_roff + b_tasks;
-    {
-      const int rc = ensure_buffer(&c->local_scratch, &c->local_scratch_bytes, b_tab + b_part + b_scr);
-      if (rc != QK_OK) return rc;
-    }
-    char* base = static_cast<char*>(c->local_scratch);
+    HIP_TRY_AS(what, c->local_scratch.ensure(b_tab + b_part + b_scr));
+    char* base = c->local_scratch.get<char>();
     std::vector<char> stage(b_tab);
     size_t at = 0;
     auto put = [&](const void* src, size_t bytes, size_t span) {
@@ -395,11 +366,11 @@ extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* ou
       return base + here;
     };
     LocArgs g{};
-    g.data = set->d_data;
-    g.rev = static_cast<const double*>(rev.p);
-    g.dims = set->d_dims;
-    g.tru = set->d_true;
-    g.offs = set->d_offs;
+    g.data = set->d_data.get<double>();
+    g.rev = rev.get<double>();
+    g.dims = set->d_dims.get<int32_t>();
+    g.tru = set->d_true.get<int32_t>();
+    g.offs = set->d_offs.get<int64_t>();
     g.states = reinterpret_cast<const int32_t*>(put(h_states.data(), nb * sizeof(int32_t), b_states));
     g.pmax = reinterpret_cast<const int32_t*>(put(h_pmax.data(), nb * sizeof(int32_t), b_pmax));
     g.sbase = reinterpret_cast<const int64_t*>(put(h_sbase.data(), nb * sizeof(int64_t), b_sbase));
@@ -409,10 +380,10 @@ extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* ou
     g.scratch = reinterpret_cast<double*>(base + b_tab + b_part);
     g.n_sites = n;
     g.max_chunks = max_chunks;
-    LOC_TRY(hipMemcpyAsync(base, stage.data(), b_tab, hipMemcpyHostToDevice, c->stream), what);
-    qk_local_reverse_kernel<<<dim3(nb, n), dim3(256), 0, c->stream>>>(g, static_cast<double*>(rev.p));
+    HIP_TRY_AS(what, hipMemcpyAsync(base, stage.data(), b_tab, hipMemcpyHostToDevice, c->stream));
+    qk_local_reverse_kernel<<<dim3(nb, n), dim3(256), 0, c->stream>>>(g, rev.get<double>());
     qk_local_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, nb);
-    LOC_TRY(hipGetLastError(), what);
+    HIP_TRY_AS(what, hipGetLastError());
     size_t li = 0;
     auto launch = [&](const int kind, const int step) {
       g.tasks = d_tasks + first[li];
@@ -426,14 +397,14 @@ extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* ou
     };
     for (int j = 0; j < n_rev; ++j) launch(LOC_REV_T, j), launch(LOC_REV_X, j);
     for (int k = 0; k < n; ++k) launch(LOC_FWD_T, k), launch(LOC_FWD_W, k), launch(-1, k);
-    LOC_TRY(hipGetLastError(), what);
+    HIP_TRY_AS(what, hipGetLastError());
     const long long nf = (long long)nb * n;
-    qk_local_features_kernel<<<dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, static_cast<double*>(dout.p), static_cast<double*>(dnorm.p));
-    LOC_TRY(hipGetLastError(), what);
-    LOC_TRY(hipStreamSynchronize(c->stream), what);  // the staged tables are reused by the next batch
+    qk_local_features_kernel<<<dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, dout.get<double>(), dnorm.get<double>());
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
   }
-  LOC_TRY(hipMemcpy(out, dout.p, (size_t)ns * n * 3 * sizeof(double), hipMemcpyDeviceToHost), what);
-  if (norms) LOC_TRY(hipMemcpy(norms, dnorm.p, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost), what);
+  HIP_TRY_AS(what, hipMemcpy(out, dout.get(), (size_t)ns * n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (norms) HIP_TRY_AS(what, hipMemcpy(norms, dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
   return QK_OK;
 }
 
@@ -446,19 +417,19 @@ extern "C" int qk_projected_gram_host(qk_ctx* c, int32_t n_sites, int32_t nx, co
   if (!(g > 0.0) || !std::isfinite(g)) return qk_fail(QK_EINVAL, "%s: g must be > 0 and finite (got %g)", what, g);
   if (ld < nx) return qk_fail(QK_EINVAL, "%s: ld %lld is smaller than the %d columns", what, (long long)ld, nx);
   QkRangeGuard range_("qk:projected_gram");
-  LOC_TRY(hipSetDevice(c->device), what);
+  HIP_TRY_AS(what, hipSetDevice(c->device));
   const int D = 3 * n_sites;
   const size_t bx = (size_t)nx * D * sizeof(double), by = fy ? (size_t)ny * D * sizeof(double) : 0, bk = (size_t)ny * nx * sizeof(double);
-  DevMem buf;
-  LOC_TRY(hipMalloc(&buf.p, bx + by + bk), what);
-  double* dx = static_cast<double*>(buf.p);
+  QkDevBuf buf;
+  HIP_TRY_AS(what, buf.alloc(bx + by + bk));
+  double* dx = buf.get<double>();
   double* dy = fy ? dx + (size_t)nx * D : dx;
   double* dk = dx + (size_t)nx * D + (fy ? (size_t)ny * D : 0);
-  LOC_TRY(hipMemcpyAsync(dx, fx, bx, hipMemcpyHostToDevice, c->stream), what);
-  if (fy) LOC_TRY(hipMemcpyAsync(dy, fy, by, hipMemcpyHostToDevice, c->stream), what);
+  HIP_TRY_AS(what, hipMemcpyAsync(dx, fx, bx, hipMemcpyHostToDevice, c->stream));
+  if (fy) HIP_TRY_AS(what, hipMemcpyAsync(dy, fy, by, hipMemcpyHostToDevice, c->stream));
   qk_projected_gram_kernel<<<dim3((nx + PG_T - 1) / PG_T, (ny + PG_T - 1) / PG_T), dim3(256), 0, c->stream>>>(dx, nx, dy, ny, D, 0.5 * g, dk, nx);
-  LOC_TRY(hipGetLastError(), what);
-  LOC_TRY(hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), dk, (size_t)nx * sizeof(double), (size_t)nx * sizeof(double), (size_t)ny, hipMemcpyDeviceToHost, c->stream), what);
-  LOC_TRY(hipStreamSynchronize(c->stream), what);
+  HIP_TRY_AS(what, hipGetLastError());
+  HIP_TRY_AS(what, hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), dk, (size_t)nx * sizeof(double), (size_t)nx * sizeof(double), (size_t)ny, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   return QK_OK;
 }

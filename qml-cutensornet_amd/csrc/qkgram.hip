@@ -104,17 +104,6 @@ extern "C" int qk_range_pop(void) {
 
 static inline int pad16(int x) { return (x + TILE - 1) / TILE * TILE; }
 
-// a device allocation that is released on every exit path (HIP_TRY returns early)
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
 // ----------------------------------------------------------------------------------------
 // host: packing one MPS into the padded planar device image
 // ----------------------------------------------------------------------------------------
@@ -364,7 +353,6 @@ extern "C" int qk_device_count(void) {
 }
 
 static int ctx_init(qk_ctx* c, int device_id, int num_cus);
-static void free_merged(qk_mps_set* m);
 
 extern "C" int qk_ctx_create(int device_id, qk_ctx** out) {
   if (!out) return fail(QK_EINVAL, "qk_ctx_create: null out");
@@ -399,9 +387,9 @@ static int ctx_init(qk_ctx* c, int device_id, int num_cus) {
   HIP_TRY(hipEventCreate(&c->ev1));
   HIP_TRY(hipEventCreate(&c->ev_mid));
   HIP_TRY(hipEventCreate(&c->ev_d));
-  HIP_TRY(hipMalloc(&c->counter, (QK_NQ_MAX * QK_QSTRIDE + 8 + 2 * 8 * QK_QSTRIDE) * sizeof(unsigned long long)));  // queue heads (8 per launch of a split sweep), tail clocks
-  HIP_TRY(hipMalloc(&c->prof, 8 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemset(c->prof, 0, 8 * sizeof(unsigned long long)));
+  HIP_TRY(c->counter.alloc((QK_NQ_MAX * QK_QSTRIDE + 8 + 2 * 8 * QK_QSTRIDE) * sizeof(unsigned long long)));  // queue heads (8 per launch of a split sweep), tail clocks
+  HIP_TRY(c->prof.alloc(8 * sizeof(unsigned long long)));
+  HIP_TRY(hipMemset(c->prof.get(), 0, 8 * sizeof(unsigned long long)));
   // the dynamic LDS the sweep kernels may ask for: 80 KiB (two workgroups per CU), a whole CU's 160 KiB, or its share per workgroup of the small-site shape
   for (const void* k : {(const void*)qk_sweep_ring_kernel<float>, (const void*)qk_sweep_ring_kernel<double>, (const void*)qk_sweep_small_kernel<double>, (const void*)qk_sweep_small_kernel<float>})
     HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
@@ -440,19 +428,12 @@ extern "C" int qk_ctx_destroy(qk_ctx* c) {
   if (!c) return QK_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->scratch) (void)hipFree(c->scratch);
-  if (c->build_arena) (void)hipFree(c->build_arena);
-  if (c->build_work) (void)hipFree(c->build_work);
-  if (c->derive_tmp) (void)hipFree(c->derive_tmp);
-  if (c->local_scratch) (void)hipFree(c->local_scratch);
-  if (c->counter) (void)hipFree(c->counter);
-  if (c->prof) (void)hipFree(c->prof);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev_mid) (void)hipEventDestroy(c->ev_mid);
   if (c->ev_d) (void)hipEventDestroy(c->ev_d);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;  // its buffers go with it (qk_devmem.h)
   return QK_OK;
 }
 
@@ -460,16 +441,7 @@ extern "C" int qk_ctx_trim(qk_ctx* c) {
   if (!c) return fail(QK_EINVAL, "qk_ctx_trim: null context");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->scratch) (void)hipFree(c->scratch);
-  if (c->build_arena) (void)hipFree(c->build_arena);
-  if (c->build_work) (void)hipFree(c->build_work);
-  if (c->derive_tmp) (void)hipFree(c->derive_tmp);
-  if (c->local_scratch) (void)hipFree(c->local_scratch);
-  c->derive_tmp = nullptr, c->derive_tmp_bytes = 0;
-  c->local_scratch = nullptr, c->local_scratch_bytes = 0;
-  c->scratch = nullptr, c->scratch_bytes = 0;
-  c->build_arena = nullptr, c->build_arena_bytes = 0;
-  c->build_work = nullptr, c->build_work_bytes = 0;
+  for (QkGrowBuf* b : {&c->scratch, &c->build_arena, &c->build_work, &c->derive_tmp, &c->local_scratch}) b->reset();
   return QK_OK;
 }
 
@@ -489,6 +461,23 @@ extern "C" int qk_ctx_synchronize(qk_ctx* c) {
   if (!c) return fail(QK_EINVAL, "qk_ctx_synchronize: null context");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return QK_OK;
+}
+
+int qk_mps_set_alloc(qk_ctx* c, int n_states, int n_sites, int64_t data_bytes, int precision, qk_mps_set** out, const char* who) {
+  qk_mps_set* m = new (std::nothrow) qk_mps_set;
+  if (!m) return fail(QK_ENOMEM, "%s: out of memory", who);
+  m->ctx = c, m->n_states = n_states, m->n_sites = n_sites, m->precision = precision, m->bytes = data_bytes;
+  const size_t nd = (size_t)n_states * (n_sites + 1), no = (size_t)n_states * n_sites;
+  hipError_t e = m->d_data.alloc((size_t)data_bytes);
+  if (e == hipSuccess) e = m->d_dims.alloc(nd * sizeof(int32_t));
+  if (e == hipSuccess) e = m->d_true.alloc(nd * sizeof(int32_t));
+  if (e == hipSuccess) e = m->d_offs.alloc(no * sizeof(int64_t));
+  if (e != hipSuccess) {
+    qk_mps_set_destroy(m);
+    return fail(QK_EDEVICE, "%s: hipMalloc of a set of %lld bytes and its tables failed: %s", who, (long long)data_bytes, hipGetErrorString(e));
+  }
+  *out = m;
   return QK_OK;
 }
 
@@ -513,42 +502,32 @@ extern "C" int qk_mps_set_create(qk_ctx* c, int32_t n_states, int32_t n_sites, c
     }
     state_off[s + 1] = state_off[s] + qk_pack_state_size(n_sites, d);
   }
-  qk_mps_set* m = new (std::nothrow) qk_mps_set;
-  if (!m) return fail(QK_ENOMEM, "qk_mps_set_create: out of memory");
-  m->ctx = c, m->n_states = n_states, m->n_sites = n_sites, m->max_pad = max_pad;
+  qk_mps_set* m = nullptr;
+  int rc = qk_mps_set_alloc(c, n_states, n_sites, state_off[n_states] * (int64_t)sizeof(double), 64, &m, "qk_mps_set_create");
+  if (rc != QK_OK) return rc;
+  m->max_pad = max_pad;
   m->dims_true.assign(bond_dims, bond_dims + (size_t)n_states * stride);
-  const int64_t total = state_off[n_states];
-  m->bytes = total * (int64_t)sizeof(double);
-  hipError_t e = hipMalloc(&m->d_data, (size_t)m->bytes);
-  if (e != hipSuccess) {
-    delete m;
-    return fail(QK_EDEVICE, "qk_mps_set_create: hipMalloc of %lld bytes failed: %s", (long long)m->bytes, hipGetErrorString(e));
-  }
+  hipError_t e = hipSuccess;
   std::vector<double> stage;
   std::vector<int64_t> so(n_sites);
   for (int s = 0; s < n_states; ++s) {
     const int64_t sz = state_off[s + 1] - state_off[s];
     stage.resize((size_t)sz);
-    int rc = qk_pack_state(n_sites, bond_dims + (size_t)s * stride, site_tensors + (size_t)s * n_sites, layout, stage.data(), so.data());
+    rc = qk_pack_state(n_sites, bond_dims + (size_t)s * stride, site_tensors + (size_t)s * n_sites, layout, stage.data(), so.data());
     if (rc != QK_OK) {
-      (void)hipFree(m->d_data);
-      delete m;
+      qk_mps_set_destroy(m);
       return rc;
     }
     for (int k = 0; k < n_sites; ++k) offs[(size_t)s * n_sites + k] = state_off[s] + so[k];
-    e = hipMemcpy(m->d_data + state_off[s], stage.data(), (size_t)sz * sizeof(double), hipMemcpyHostToDevice);
+    e = hipMemcpy(m->d_data.get<double>() + state_off[s], stage.data(), (size_t)sz * sizeof(double), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-      (void)hipFree(m->d_data);
-      delete m;
+      qk_mps_set_destroy(m);
       return fail(QK_EDEVICE, "qk_mps_set_create: upload failed: %s", hipGetErrorString(e));
     }
   }
-  e = hipMalloc(&m->d_dims, pad.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&m->d_offs, offs.size() * sizeof(int64_t));
-  if (e == hipSuccess) e = hipMalloc(&m->d_true, pad.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMemcpy(m->d_dims, pad.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(m->d_true, bond_dims, pad.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(m->d_offs, offs.data(), offs.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+  e = hipMemcpy(m->d_dims.get(), pad.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(m->d_true.get(), bond_dims, pad.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(m->d_offs.get(), offs.data(), offs.size() * sizeof(int64_t), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     qk_mps_set_destroy(m);
     return fail(QK_EDEVICE, "qk_mps_set_create: table upload failed: %s", hipGetErrorString(e));
@@ -561,15 +540,7 @@ extern "C" int qk_mps_set_destroy(qk_mps_set* m) {
   if (!m) return QK_OK;
   (void)hipSetDevice(m->ctx->device);
   (void)hipStreamSynchronize(m->ctx->stream);
-  if (m->d_data) (void)hipFree(m->d_data);
-  if (m->d_il) (void)hipFree(m->d_il);
-  if (m->d_edge) (void)hipFree(m->d_edge);
-  if (m->d_edge_offs) (void)hipFree(m->d_edge_offs);
-  free_merged(m);
-  if (m->d_dims) (void)hipFree(m->d_dims);
-  if (m->d_true) (void)hipFree(m->d_true);
-  if (m->d_offs) (void)hipFree(m->d_offs);
-  delete m;
+  delete m;  // its images and tables go with it (qk_devmem.h)
   return QK_OK;
 }
 
@@ -588,12 +559,12 @@ extern "C" int qk_mps_set_image(const qk_mps_set* m, int64_t* n_doubles, const d
   if (!m) return fail(QK_EINVAL, "qk_mps_set_image: null set");
   if (m->precision != 64) return fail(QK_EINVAL, "qk_mps_set_image: only fp64 sets are exchanged");
   if (n_doubles) *n_doubles = m->bytes / (int64_t)sizeof(double);
-  if (planes_dev) *planes_dev = m->d_data;
+  if (planes_dev) *planes_dev = m->d_data.get<double>();
   if (dims_true) std::memcpy(dims_true, m->dims_true.data(), m->dims_true.size() * sizeof(int32_t));
   if (offsets) {
     HIP_TRY(hipSetDevice(m->ctx->device));
     HIP_TRY(hipStreamSynchronize(m->ctx->stream));
-    HIP_TRY(hipMemcpy(offsets, m->d_offs, (size_t)m->n_states * m->n_sites * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(offsets, m->d_offs.get<int64_t>(), (size_t)m->n_states * m->n_sites * sizeof(int64_t), hipMemcpyDeviceToHost));
   }
   return QK_OK;
 }
@@ -603,7 +574,7 @@ extern "C" int qk_mps_set_copy_image(const qk_mps_set* m, double* dst, int64_t n
   if (m->precision != 64) return fail(QK_EINVAL, "qk_mps_set_copy_image: only fp64 sets are exchanged");
   if (n_doubles * (int64_t)sizeof(double) < m->bytes) return fail(QK_EINVAL, "qk_mps_set_copy_image: destination holds %lld doubles, the image has %lld", (long long)n_doubles, (long long)(m->bytes / 8));
   HIP_TRY(hipSetDevice(m->ctx->device));
-  HIP_TRY(hipMemcpyAsync(dst, m->d_data, (size_t)m->bytes, hipMemcpyDefault, m->ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dst, m->d_data.get<double>(), (size_t)m->bytes, hipMemcpyDefault, m->ctx->stream));
   HIP_TRY(hipStreamSynchronize(m->ctx->stream));
   return QK_OK;
 }
@@ -629,19 +600,15 @@ extern "C" int qk_mps_set_from_packed(qk_ctx* c, int32_t n_states, int32_t n_sit
     }
   }
   HIP_TRY(hipSetDevice(c->device));
-  qk_mps_set* m = new (std::nothrow) qk_mps_set;
-  if (!m) return fail(QK_ENOMEM, "qk_mps_set_from_packed: out of memory");
-  m->ctx = c, m->n_states = n_states, m->n_sites = n_sites, m->max_pad = max_pad;
+  qk_mps_set* m = nullptr;
+  const int rc = qk_mps_set_alloc(c, n_states, n_sites, n_doubles * (int64_t)sizeof(double), 64, &m, "qk_mps_set_from_packed");
+  if (rc != QK_OK) return rc;
+  m->max_pad = max_pad;
   m->dims_true.assign(dims_true, dims_true + (size_t)n_states * stride);
-  m->bytes = n_doubles * (int64_t)sizeof(double);
-  hipError_t e = hipMalloc(&m->d_data, (size_t)m->bytes);
-  if (e == hipSuccess) e = hipMalloc(&m->d_dims, pad.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&m->d_true, pad.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&m->d_offs, (size_t)n_states * n_sites * sizeof(int64_t));
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_data, planes_dev, (size_t)m->bytes, hipMemcpyDefault, c->stream);  // device or host source
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_dims, pad.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_true, dims_true, pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_offs, offsets, (size_t)n_states * n_sites * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
+  hipError_t e = hipMemcpyAsync(m->d_data.get(), planes_dev, (size_t)m->bytes, hipMemcpyDefault, c->stream);  // device or host source
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_dims.get(), pad.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_true.get(), dims_true, pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_offs.get(), offsets, (size_t)n_states * n_sites * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) {
     qk_mps_set_destroy(m);
@@ -656,22 +623,18 @@ extern "C" int qk_mps_set_to_f32(qk_ctx* c, const qk_mps_set* src, qk_mps_set** 
   if (src->ctx != c) return fail(QK_EINVAL, "qk_mps_set_to_f32: the set belongs to another context");
   if (src->precision != 64) return fail(QK_EINVAL, "qk_mps_set_to_f32: the source set is not fp64");
   HIP_TRY(hipSetDevice(c->device));
-  qk_mps_set* m = new (std::nothrow) qk_mps_set;
-  if (!m) return fail(QK_ENOMEM, "qk_mps_set_to_f32: out of memory");
-  m->ctx = c, m->n_states = src->n_states, m->n_sites = src->n_sites, m->max_pad = src->max_pad, m->precision = 32;
-  m->dims_true = src->dims_true;
   const long long n = src->bytes / (long long)sizeof(double);
-  m->bytes = n * (long long)sizeof(float);
+  qk_mps_set* m = nullptr;
+  const int rc = qk_mps_set_alloc(c, src->n_states, src->n_sites, n * (long long)sizeof(float), 32, &m, "qk_mps_set_to_f32");
+  if (rc != QK_OK) return rc;
+  m->max_pad = src->max_pad;
+  m->dims_true = src->dims_true;
   const size_t nd = (size_t)src->n_states * (src->n_sites + 1), no = (size_t)src->n_states * src->n_sites;
-  hipError_t e = hipMalloc(&m->d_data, (size_t)m->bytes);
-  if (e == hipSuccess) e = hipMalloc(&m->d_dims, nd * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&m->d_true, nd * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&m->d_offs, no * sizeof(int64_t));
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_dims, src->d_dims, nd * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_true, src->d_true, nd * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_offs, src->d_offs, no * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream);
+  hipError_t e = hipMemcpyAsync(m->d_dims.get(), src->d_dims.get(), nd * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_true.get(), src->d_true.get(), nd * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_offs.get(), src->d_offs.get(), no * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream);
   if (e == hipSuccess) {
-    qk_convert_f32_kernel<<<dim3(4 * c->num_cus), dim3(256), 0, c->stream>>>(src->d_data, reinterpret_cast<float*>(m->d_data), n);
+    qk_convert_f32_kernel<<<dim3(4 * c->num_cus), dim3(256), 0, c->stream>>>(src->d_data.get<double>(), m->d_data.get<float>(), n);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -686,16 +649,15 @@ extern "C" int qk_mps_set_to_f32(qk_ctx* c, const qk_mps_set* src, qk_mps_set** 
 // the interleaved complex128 image of a set, made once on the device from the split planes
 static int ensure_interleaved(qk_ctx* c, qk_mps_set* m) {
   if (m->d_il) return QK_OK;
-  DevBuf il;  // published only after the conversion has been launched without error (released otherwise)
+  QkDevBuf il;  // published only after the conversion has been launched without error (released otherwise)
   HIP_TRY(il.alloc((size_t)m->bytes));
   const long long nt = (long long)m->n_states * m->n_sites;
   const dim3 grid((unsigned)std::min<long long>(nt, 64ll * c->num_cus));
-  if (m->precision == 64) qk_interleave_kernel<double><<<grid, dim3(256), 0, c->stream>>>(m->d_data, il.as<double>(), m->d_dims, m->d_offs, m->n_sites, nt);
+  if (m->precision == 64) qk_interleave_kernel<double><<<grid, dim3(256), 0, c->stream>>>(m->d_data.get<double>(), il.get<double>(), m->d_dims.get<int32_t>(), m->d_offs.get<int64_t>(), m->n_sites, nt);
   else  // complex64 image of an fp32 set (same offsets, counted in floats)
-    qk_interleave_kernel<float><<<grid, dim3(256), 0, c->stream>>>(reinterpret_cast<const float*>(m->d_data), il.as<float>(), m->d_dims, m->d_offs, m->n_sites, nt);
+    qk_interleave_kernel<float><<<grid, dim3(256), 0, c->stream>>>(m->d_data.get<float>(), il.get<float>(), m->d_dims.get<int32_t>(), m->d_offs.get<int64_t>(), m->n_sites, nt);
   HIP_TRY(hipGetLastError());
-  m->d_il = il.as<double>();
-  il.p = nullptr;
+  m->d_il = std::move(il);
   return QK_OK;
 }
 
@@ -705,9 +667,7 @@ static int ensure_interleaved(qk_ctx* c, qk_mps_set* m) {
 static int ensure_edges(qk_ctx* c, qk_mps_set* m, const int k) {
   if (k <= 0 || (m->d_edge && m->edge_k == k)) return QK_OK;
   if (m->d_edge || m->d_edge_offs) HIP_TRY(hipStreamSynchronize(c->stream));  // (a plan with another k: the old blocks may still be read)
-  if (m->d_edge) (void)hipFree(m->d_edge);
-  if (m->d_edge_offs) (void)hipFree(m->d_edge_offs);
-  m->d_edge = nullptr, m->d_edge_offs = nullptr, m->edge_k = 0, m->edge_bytes = 0;
+  m->d_edge.reset(), m->d_edge_offs.reset(), m->edge_k = 0, m->edge_bytes = 0;
   const int n = m->n_sites, stride = n + 1;
   std::vector<long long>& offs = m->h_edge_offs;
   offs.assign((size_t)m->n_states * 2, 0);
@@ -724,31 +684,22 @@ static int ensure_edges(qk_ctx* c, qk_mps_set* m, const int k) {
   const long long tmp_elems = (long long)std::max(1 << (k - 1), 16) * maxld;  // the largest intermediate block (at least one 16-row tile)
   const int grid = (int)std::min<long long>(2ll * m->n_states, 4ll * c->num_cus);
   const size_t tmp_bytes = (size_t)grid * 2 * tmp_elems * 2 * sizeof(double);
-  if (tmp_bytes > c->derive_tmp_bytes) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->derive_tmp) (void)hipFree(c->derive_tmp);
-    c->derive_tmp = nullptr, c->derive_tmp_bytes = 0;
-    HIP_TRY(hipMalloc(&c->derive_tmp, tmp_bytes));
-    c->derive_tmp_bytes = tmp_bytes;
-  }
-  DevBuf eb, ob;
+  if (tmp_bytes > c->derive_tmp.bytes) HIP_TRY(hipStreamSynchronize(c->stream));  // (the old one may still be in use)
+  HIP_TRY(c->derive_tmp.ensure(tmp_bytes));
+  QkDevBuf eb, ob;
   HIP_TRY(eb.alloc((size_t)total * 2 * sizeof(double)));
   HIP_TRY(ob.alloc(offs.size() * sizeof(long long)));
-  HIP_TRY(hipMemcpyAsync(ob.p, offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-  qk_edge_kernel<<<dim3(grid), dim3(256), 0, c->stream>>>(reinterpret_cast<const qk_v2d*>(m->d_il), m->d_dims, m->d_true, m->d_offs, n, k, m->n_states, eb.as<qk_v2d>(), ob.as<long long>(),
-                                                          static_cast<qk_v2d*>(c->derive_tmp), tmp_elems);
+  HIP_TRY(hipMemcpyAsync(ob.get(), offs.data(), offs.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  qk_edge_kernel<<<dim3(grid), dim3(256), 0, c->stream>>>(m->d_il.get<qk_v2d>(), m->d_dims.get<int32_t>(), m->d_true.get<int32_t>(), m->d_offs.get<int64_t>(), n, k, m->n_states, eb.get<qk_v2d>(),
+                                                          ob.get<long long>(), c->derive_tmp.get<qk_v2d>(), tmp_elems);
   HIP_TRY(hipGetLastError());
-  m->d_edge = eb.as<double>(), m->d_edge_offs = ob.as<long long>();
-  eb.p = nullptr, ob.p = nullptr;
+  m->d_edge = std::move(eb), m->d_edge_offs = std::move(ob);
   m->edge_k = k, m->edge_bytes = total * 2 * (long long)sizeof(double);
   return QK_OK;
 }
 
 static void free_merged(qk_mps_set* m) {
-  if (m->d_mg) (void)hipFree(m->d_mg);
-  if (m->d_mg_offs) (void)hipFree(m->d_mg_offs);
-  if (m->d_mg_units) (void)hipFree(m->d_mg_units);
-  m->d_mg = nullptr, m->d_mg_offs = nullptr, m->d_mg_units = nullptr, m->mg_k = -1, m->mg_steps = 0, m->mg_bytes = 0;
+  m->d_mg.reset(), m->d_mg_offs.reset(), m->d_mg_units.reset(), m->mg_k = -1, m->mg_steps = 0, m->mg_bytes = 0;
 }
 
 // the merged image of a set for a chain that starts `k` sites in (made once per set and k; fp64 sets; needs the interleaved image).
@@ -775,19 +726,18 @@ static int ensure_merged(qk_ctx* c, qk_mps_set* m, const int k) {
     }
   }
   us.back() = units;
-  DevBuf ib, ob, ub;
+  QkDevBuf ib, ob, ub;
   HIP_TRY(ib.alloc((size_t)total * 2 * sizeof(double)));
   HIP_TRY(ob.alloc(mo.size() * sizeof(int64_t)));
   HIP_TRY(ub.alloc(us.size() * sizeof(long long)));
-  HIP_TRY(hipMemcpyAsync(ob.p, mo.data(), mo.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(ub.p, us.data(), us.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(ob.get(), mo.data(), mo.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(ub.get(), us.data(), us.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
   const long long tasks = (long long)m->n_states * steps;
   const unsigned grid = (unsigned)std::min<long long>((units + 3) / 4, 4ll * c->num_cus);  // 4 wavefronts per workgroup, two workgroups per SIMD row
-  qk_merge_kernel<<<dim3(grid), dim3(256), 0, c->stream>>>(reinterpret_cast<const qk_v2d*>(m->d_il), m->d_dims, m->d_true, m->d_offs, n, k, steps, tasks, ub.as<long long>(), ib.as<qk_v2d>(),
-                                                          ob.as<int64_t>());
+  qk_merge_kernel<<<dim3(grid), dim3(256), 0, c->stream>>>(m->d_il.get<qk_v2d>(), m->d_dims.get<int32_t>(), m->d_true.get<int32_t>(), m->d_offs.get<int64_t>(), n, k, steps, tasks, ub.get<long long>(),
+                                                          ib.get<qk_v2d>(), ob.get<int64_t>());
   HIP_TRY(hipGetLastError());
-  m->d_mg = ib.as<double>(), m->d_mg_offs = ob.as<int64_t>(), m->d_mg_units = ub.as<long long>();
-  ib.p = ob.p = ub.p = nullptr;
+  m->d_mg = std::move(ib), m->d_mg_offs = std::move(ob), m->d_mg_units = std::move(ub);
   m->mg_k = k, m->mg_steps = steps, m->mg_bytes = total * 2 * (long long)sizeof(double);
   return QK_OK;
 }
@@ -796,13 +746,14 @@ static int ensure_plan_uploaded(qk_ctx* c, qk_plan* p) {
   if (p->d_pairs && p->up_ctx == c) return QK_OK;
   if (p->d_pairs) (void)hipFree(p->d_pairs);
   if (p->d_groups) (void)hipFree(p->d_groups);
-  p->d_pairs = nullptr, p->d_groups = nullptr;
+  p->d_pairs = nullptr, p->d_groups = nullptr, p->up_ctx = nullptr;
   if (p->pairs.empty()) return QK_OK;
-  HIP_TRY(hipMalloc(&p->d_pairs, p->pairs.size() * sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(p->d_pairs, p->pairs.data(), p->pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&p->d_groups, p->groups.size() * sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(p->d_groups, p->groups.data(), p->groups.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  p->up_ctx = c;
+  QkDevBuf pairs, groups;  // published together, once both copies are on the device (the plan keeps raw pointers: qk_plan.h has no HIP type)
+  HIP_TRY(pairs.alloc(p->pairs.size() * sizeof(int32_t)));
+  HIP_TRY(hipMemcpy(pairs.get(), p->pairs.data(), p->pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(groups.alloc(p->groups.size() * sizeof(int32_t)));
+  HIP_TRY(hipMemcpy(groups.get(), p->groups.data(), p->groups.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  p->d_pairs = static_cast<int32_t*>(pairs.release()), p->d_groups = static_cast<int32_t*>(groups.release()), p->up_ctx = c;
   return QK_OK;
 }
 
@@ -817,20 +768,21 @@ static int derive_fused_images(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set
     else if (xs->edge_k == 0 && ys->edge_k > 0) ek = ys->edge_k;
     for (const qk_mps_set* m : {xs, ys})
       if ((rc = ensure_edges(c, const_cast<qk_mps_set*>(m), ek)) != QK_OK) return rc;
-    a.xedge = xs->d_edge, a.xedge_offs = xs->d_edge_offs, a.yedge = ys->d_edge, a.yedge_offs = ys->d_edge_offs, a.edge_k = ek;
+    a.xedge = xs->d_edge.get<double>(), a.xedge_offs = xs->d_edge_offs.get<long long>(), a.yedge = ys->d_edge.get<double>(), a.yedge_offs = ys->d_edge_offs.get<long long>(), a.edge_k = ek;
   }
   if (merge_sites && xs->n_sites - 2 * ek >= 2) {  // the chain's sites contracted in twos: a workgroup picks per pair and step
     for (const qk_mps_set* m : {xs, ys})
       if ((rc = ensure_merged(c, const_cast<qk_mps_set*>(m), ek)) != QK_OK) return rc;
-    a.xmg = xs->d_mg, a.xmg_offs = xs->d_mg_offs, a.ymg = ys->d_mg, a.ymg_offs = ys->d_mg_offs, a.merge_steps = xs->mg_steps;
+    a.xmg = xs->d_mg.get<double>(), a.xmg_offs = xs->d_mg_offs.get<int64_t>(), a.ymg = ys->d_mg.get<double>(), a.ymg_offs = ys->d_mg_offs.get<int64_t>(), a.merge_steps = xs->mg_steps;
   }
 #ifdef QK_LAB  // TIMING EXPERIMENT (wrong results): every tensor read from the first MiB of its image -- what would perfect L2 hits buy?
   if (const char* v = std::getenv("QK_DEBUG_ALIAS")) {
     const long long win = std::atoll(v);  // window in doubles (e.g. 131072 = 1 MiB)
     if (win > 0) {
       auto fold = [&](const int64_t* src, const long long n) -> const int64_t* {
-        int64_t* dst = nullptr;
-        if (hipMalloc(&dst, (size_t)n * sizeof(int64_t)) != hipSuccess) return src;  // (leaked: experiment)
+        QkDevBuf buf;
+        if (buf.alloc((size_t)n * sizeof(int64_t)) != hipSuccess) return src;
+        int64_t* dst = static_cast<int64_t*>(buf.release());  // (leaked: experiment)
         qk_lab_fold_kernel<<<dim3(256), dim3(256), 0, c->stream>>>(src, dst, n, win);
         return dst;
       };
@@ -894,37 +846,33 @@ extern "C" int qk_gram_values(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set*
   const QkSweepChoice ch = qk_choose_sweep(pol, *plan, {xs->max_pad, xs->precision, xs->n_sites}, {ys->max_pad, ys->precision, ys->n_sites}, c->num_cus);
   if (ch.rc != QK_OK) return fail(ch.rc, "%s", ch.err);
   c->last.queues = ch.queues, c->last.tail_frac = c->last.second_tail_frac = 0;
-  if (ch.scratch_bytes > c->scratch_bytes) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->scratch) HIP_TRY(hipFree(c->scratch));
-    c->scratch = nullptr, c->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&c->scratch, ch.scratch_bytes));
-    c->scratch_bytes = ch.scratch_bytes;
-  }
+  if (ch.scratch_bytes > c->scratch.bytes) HIP_TRY(hipStreamSynchronize(c->stream));  // (the old one may still be in use)
+  HIP_TRY(c->scratch.ensure(ch.scratch_bytes));
   SweepArgs a{};  // (what is not set here is null / zero)
-  a.xdata = xs->d_data, a.xdims = xs->d_dims, a.xtrue = xs->d_true, a.xoffs = xs->d_offs;
-  a.ydata = ys->d_data, a.ydims = ys->d_dims, a.ytrue = ys->d_true, a.yoffs = ys->d_offs;
+  a.xdata = xs->d_data.get<double>(), a.xdims = xs->d_dims.get<int32_t>(), a.xtrue = xs->d_true.get<int32_t>(), a.xoffs = xs->d_offs.get<int64_t>();
+  a.ydata = ys->d_data.get<double>(), a.ydims = ys->d_dims.get<int32_t>(), a.ytrue = ys->d_true.get<int32_t>(), a.yoffs = ys->d_offs.get<int64_t>();
   a.n_sites = xs->n_sites;
   a.pairs = plan->d_pairs, a.npairs = np;
   a.groups = plan->d_groups, a.ngroups = (long long)plan->groups.size() / 2;
   a.values = values_dev, a.z = z_dev;
-  a.scratch = c->scratch, a.x_plane = ch.x_plane, a.t_plane = ch.t_plane, a.turn_ints = ch.turn_ints;
-  a.counter = c->counter, a.prof = c->prof;
+  a.scratch = c->scratch.get<double>(), a.x_plane = ch.x_plane, a.t_plane = ch.t_plane, a.turn_ints = ch.turn_ints;
+  unsigned long long* const counter = c->counter.get<unsigned long long>();
+  a.counter = counter, a.prof = c->prof.get<unsigned long long>();
   for (int s_ = 0; s_ <= QK_NQ_MAX; ++s_) a.qstart[s_] = plan->nq > 1 ? plan->qstart[s_] : (s_ == 0 ? 0 : np);
   // device clocks for the tail accounting behind the queue heads (launch 1 uses [0] [1] [4], launch 2 [2] [3] [6]), the DET error word, the gang words
-  a.tail = c->counter + QK_NQ_MAX * QK_QSTRIDE, a.err = a.tail + 7, a.gang = a.tail + 8;
+  a.tail = counter + QK_NQ_MAX * QK_QSTRIDE, a.err = a.tail + 7, a.gang = a.tail + 8;
 #ifdef QK_LAB  // timing experiments of the lab kernels (they give wrong results by construction): libqklab.so only
   if (const char* v = std::getenv("QK_DEBUG_FLAGS")) a.debug_flags = std::atoi(v);
   if (const char* v = std::getenv("QK_PRIO")) a.prio_mode = std::atoi(v);
 #endif
   HIP_TRY(hipEventRecord(c->ev_d, c->stream));
-  HIP_TRY(hipMemsetAsync(c->counter, 0, (QK_NQ_MAX * QK_QSTRIDE + 8 + 2 * 8 * QK_QSTRIDE) * sizeof(unsigned long long), c->stream));
+  HIP_TRY(hipMemsetAsync(counter, 0, (QK_NQ_MAX * QK_QSTRIDE + 8 + 2 * 8 * QK_QSTRIDE) * sizeof(unsigned long long), c->stream));
   HIP_TRY(hipMemsetAsync(a.tail, 0xFF, 4 * sizeof(unsigned long long), c->stream));  // the four minima
   // the sets' derived images (made on their first use): between ev_d and ev0, not part of the sweep
   if (ch.interleaved) {
     for (const qk_mps_set* m : {xs, ys})
       if ((rc = ensure_interleaved(c, const_cast<qk_mps_set*>(m))) != QK_OK) return rc;
-    a.xdata = xs->d_il, a.ydata = ys->d_il;
+    a.xdata = xs->d_il.get<double>(), a.ydata = ys->d_il.get<double>();
   }
   if (ch.fused_images && (rc = derive_fused_images(c, xs, ys, plan, pol.merge_sites, a)) != QK_OK) return rc;
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
@@ -935,7 +883,7 @@ extern "C" int qk_gram_values(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set*
     if (i == 1) {  // the second class of pairs: its part of the list, and queue heads, tail clocks (and gang words) behind the first launch's
       HIP_TRY(hipEventRecord(c->ev_mid, c->stream));
       ar.pairs = a.pairs + 2 * r.first, ar.values = a.values + r.first, ar.z = a.z ? a.z + 2 * r.first : nullptr;
-      ar.counter = c->counter + 8 * QK_QSTRIDE, ar.tail = a.tail + 2;
+      ar.counter = counter + 8 * QK_QSTRIDE, ar.tail = a.tail + 2;
       if (plan->nq > 1)
         for (int s_ = 0; s_ <= 8; ++s_) ar.qstart[s_] = plan->qstart[8 + s_] - r.first;
       if (r.gang2) ar.gang = a.gang + 8 * QK_QSTRIDE;
@@ -963,13 +911,13 @@ extern "C" int qk_gram_values_host(qk_ctx* c, const qk_mps_set* xs, const qk_mps
   const int64_t np = qk_plan_num_pairs(plan);
   if (np == 0) return QK_OK;
   HIP_TRY(hipSetDevice(c->device));
-  DevBuf vals, z;  // released on every exit path
+  QkDevBuf vals, z;  // released on every exit path
   HIP_TRY(vals.alloc((size_t)np * sizeof(double)));
   if (z_host) HIP_TRY(z.alloc((size_t)np * 2 * sizeof(double)));
-  const int rc = qk_gram_values(c, xs, ys, plan, vals.as<double>(), z.as<double>());
+  const int rc = qk_gram_values(c, xs, ys, plan, vals.get<double>(), z.get<double>());
   if (rc != QK_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(values_host, vals.p, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (z_host) HIP_TRY(hipMemcpyAsync(z_host, z.p, (size_t)np * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(values_host, vals.get(), (size_t)np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (z_host) HIP_TRY(hipMemcpyAsync(z_host, z.get(), (size_t)np * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return QK_OK;
 }
@@ -1020,7 +968,7 @@ extern "C" int qk_get_stats(qk_ctx* c, qk_stats* out) {
     c->last.derive_ms = ms;  // device time ahead of the sweep: the derived images of the sets (interleaved, edge blocks, merged steps) on their first Gram
     if (c->tail_pending) {  // device clocks of the launch(es): share of the duration during which the chip was draining
       unsigned long long t[8];
-      HIP_TRY(hipMemcpy(t, c->counter + QK_NQ_MAX * QK_QSTRIDE, sizeof t, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(t, c->counter.get<unsigned long long>() + QK_NQ_MAX * QK_QSTRIDE, sizeof t, hipMemcpyDeviceToHost));
       auto frac = [](const unsigned long long start, const unsigned long long first_exit, const unsigned long long last_exit) {
         return (last_exit > start && first_exit <= last_exit && first_exit >= start) ? (double)(last_exit - first_exit) / (double)(last_exit - start) : 0.0;
       };
@@ -1038,8 +986,8 @@ extern "C" int qk_get_stats(qk_ctx* c, qk_stats* out) {
 #ifdef QKF_PROF  // experiment builds: the section sums of the launch(es) since the last call (wave cycles, all waves)
     {
       unsigned long long pf[8];
-      HIP_TRY(hipMemcpy(pf, c->prof, sizeof pf, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemset(c->prof, 0, sizeof pf));
+      HIP_TRY(hipMemcpy(pf, c->prof.get(), sizeof pf, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemset(c->prof.get(), 0, sizeof pf));
       const double tot = pf[7] > 0 ? (double)pf[7] : 1.0;
       fprintf(stderr, "[qkf_prof] pair set-up %.3f  step set-up %.3f  phase1 %.3f  wait1 %.3f  phase2 %.3f  wait2 %.3f  tail %.3f  (of %.3e wave cycles)\n", pf[0] / tot, pf[1] / tot, pf[2] / tot,
               pf[3] / tot, pf[4] / tot, pf[5] / tot, pf[6] / tot, tot);
@@ -1071,15 +1019,15 @@ extern "C" int qk_gram_host(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set* y
   int rc = plan_for_sets(xs, ys, &plan.p);
   if (rc != QK_OK) return rc;
   const int64_t np = qk_plan_num_pairs(plan.p);
-  DevBuf vals, k;
+  QkDevBuf vals, k;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(vals.alloc((size_t)np * sizeof(double)));
   HIP_TRY(k.alloc((size_t)ny * nx * sizeof(double)));
-  HIP_TRY(hipMemsetAsync(k.p, 0, (size_t)ny * nx * sizeof(double), c->stream));
-  rc = qk_gram_values(c, xs, ys, plan.p, vals.as<double>(), nullptr);
-  if (rc == QK_OK) rc = qk_scatter(c, plan.p->d_pairs, vals.as<double>(), np, k.as<double>(), nx, sym ? 1 : 0);
+  HIP_TRY(hipMemsetAsync(k.get(), 0, (size_t)ny * nx * sizeof(double), c->stream));
+  rc = qk_gram_values(c, xs, ys, plan.p, vals.get<double>(), nullptr);
+  if (rc == QK_OK) rc = qk_scatter(c, plan.p->d_pairs, vals.get<double>(), np, k.get<double>(), nx, sym ? 1 : 0);
   if (rc != QK_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), k.p, (size_t)nx * sizeof(double), (size_t)nx * sizeof(double), (size_t)ny, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), k.get(), (size_t)nx * sizeof(double), (size_t)nx * sizeof(double), (size_t)ny, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return QK_OK;
 }
@@ -1092,14 +1040,14 @@ extern "C" int qk_overlaps_host(qk_ctx* c, const qk_mps_set* xs, const qk_mps_se
   int rc = qk_plan_create(xs->n_sites, nx, xs->dims_true.data(), ny, ys->dims_true.data(), 0u, 1, 0, 16, &plan.p);
   if (rc != QK_OK) return rc;
   const int64_t np = qk_plan_num_pairs(plan.p);
-  DevBuf vals, zd;
+  QkDevBuf vals, zd;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(vals.alloc((size_t)np * sizeof(double)));
   HIP_TRY(zd.alloc((size_t)np * 2 * sizeof(double)));
-  rc = qk_gram_values(c, xs, ys, plan.p, vals.as<double>(), zd.as<double>());
+  rc = qk_gram_values(c, xs, ys, plan.p, vals.get<double>(), zd.get<double>());
   if (rc != QK_OK) return rc;
   std::vector<double> z((size_t)np * 2);
-  HIP_TRY(hipMemcpyAsync(z.data(), zd.p, z.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(z.data(), zd.get(), z.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   const int32_t* pr = qk_plan_pairs(plan.p);
   for (int64_t t = 0; t < np; ++t) {
@@ -1124,11 +1072,11 @@ extern "C" int qk_selftest_mfma(qk_ctx* c) {
       for (int k = 0; k < 16; ++k) s += hp[k * 16 + m] * hq[k * 16 + n];
       ref[m * 16 + n] = s;
     }
-  DevBuf bp, bq, bc;
+  QkDevBuf bp, bq, bc;
   HIP_TRY(bp.alloc(sizeof hp));
   HIP_TRY(bq.alloc(sizeof hq));
   HIP_TRY(bc.alloc(sizeof hc));
-  double *dp = bp.as<double>(), *dq = bq.as<double>(), *dc = bc.as<double>();
+  double *dp = bp.get<double>(), *dq = bq.get<double>(), *dc = bc.get<double>();
   HIP_TRY(hipMemcpy(dp, hp, sizeof hp, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dq, hq, sizeof hq, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(qk_selftest_kernel, dim3(1), dim3(64), 0, c->stream, dp, dq, dc);
@@ -1141,11 +1089,11 @@ extern "C" int qk_selftest_mfma(qk_ctx* c) {
   // the same product through v_mfma_f32_16x16x4_f32 (operands are exact in fp32; sums of 16 such products too)
   float fp[256], fq[256], fc[256];
   for (int e = 0; e < 256; ++e) fp[e] = (float)hp[e], fq[e] = (float)hq[e];
-  DevBuf be, bf, bg;
+  QkDevBuf be, bf, bg;
   HIP_TRY(be.alloc(sizeof fp));
   HIP_TRY(bf.alloc(sizeof fq));
   HIP_TRY(bg.alloc(sizeof fc));
-  float *ep = be.as<float>(), *eq = bf.as<float>(), *ec = bg.as<float>();
+  float *ep = be.get<float>(), *eq = bf.get<float>(), *ec = bg.get<float>();
   HIP_TRY(hipMemcpy(ep, fp, sizeof fp, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(eq, fq, sizeof fq, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(qk_selftest_f32_kernel, dim3(1), dim3(64), 0, c->stream, ep, eq, ec);
