@@ -9,7 +9,14 @@
 //     workgroup's X buffer (98.7 % of the sites and 88 % of the matrix work of the 60-qubit x 6-layer headline workload
 //     at 8192 elements).  When X and X' fit side by side, X' is built at the other end of the buffer (zeroed while the
 //     previous site's result is consumed); otherwise it overwrites X after a barrier;
-//   * the unit of work is an ITEM (ta, tb, p): one 16 x 16 tile T[ta, p, tb], dealt round-robin to the waves.
+//   * the unit of work is an ITEM (ta, tb, p): one 16 x 16 tile T[ta, p, tb], dealt to the waves in rounds of consecutive indices.
+//     The order of the indices (qk_unit_decode, qk_plan.h: p slowest, ta fastest) decides what the waves of a round share: a round
+//     lies inside one p and covers a few column blocks tb with all their ta, so an A block (ta, p) is used by the tb of the round at
+//     the same time and a B block (p, tb) by its ta.  With p fastest (the order of the DET forms and of the dual kernel) a round takes
+//     ONE tb with all (ta, p): each A block has one user per round and comes back a whole round later, once per tb.  Operand blocks
+//     asked for per round, summed over a step of 4 x 4 tiles at 8 waves: 24 against 40, of 16 distinct ones (tests/host_san/
+//     units_main.cpp holds the model for every shape).  Measured on the small-site launch of the headline set: - 7 % (lab/NOTES_r05.md);
+//     the same order in the dual kernel: + 2 %, so that kernel keeps p fastest.
 //     Phase 1: the wave computes its tile (K = b) and KEEPS it in registers -- the C/D layout of v_mfma_f64_16x16x4_f64
 //     (register r of lane (q, j) = C[q + 4r][j]) is the A-operand layout of a k-major operand with k-step r, so the
 //     tile is fed straight back as the A operand of phase 2:
@@ -18,7 +25,9 @@
 //   * site tensors are read straight from the set image into B-operand fragments: one 16-byte load per lane and k-step
 //     (complex128 interleaved image, rows of 16 elements = 256 contiguous bytes), four k-steps in flight per wave.  The
 //     stream never drains: the last group of a tile loads the first group of the wave's next tile, of its first
-//     phase-2 group, or of its first tile of the NEXT site, across the barriers.  No staging ring, no per-K-tile
+//     phase-2 group, or of its first tile of the NEXT site, across the barriers.  In the one-tile kernel rows of zero padding are not
+//     fetched: the k-steps of a group at or above the true bond ask for the address of the last k-step below it (QkfStream: - 5 % on
+//     the small-site launch; the dual kernel, where it measured nothing, loads whole groups).  No staging ring, no per-K-tile
 //     barrier: a wave runs its items autonomously and the workgroup meets at two or three barriers per site.  The
 //     fragments that several items share are re-read through the caches (which catch a fifth to a quarter of them: the rest comes
 //     back over the fabric -- DESIGN.md, cache counters);
@@ -43,6 +52,7 @@
 // fp64 only: the f32 MFMA's C layout (C[4q + r][j]) is not an operand layout (the complex64 sweep stays on qk_ring.h).
 #pragma once
 #include "qk_device.h"
+#include "qk_plan.h"  // the order of a step's units (qk_unit_decode)
 
 // Wave priority: a wave that is NOT in a matrix block (tile tails with their adds and LDS atomics, item set-up, barriers)
 // runs at raised priority, so that it gets the issue slots ahead of the other wave's matrix stream and is back at its own
@@ -117,16 +127,47 @@ __device__ __forceinline__ v2d qkf_ldg_b(const v2d* __restrict__ base, const uns
 __device__ __forceinline__ v2d qkf_ldx(const v2d* __restrict__ base, const unsigned off) { return qkf_ldg(base, off); }
 __device__ __forceinline__ v2d qkf_ldx(const lds_v2d* base, const unsigned off) { return base[off]; }
 
-// A fragment stream: k-step i of the current group is element base + off + i * step (base wave-uniform, off this lane's)
+// A fragment stream: k-step i of the current group is element base + off + i * step (base wave-uniform, off this lane's).
+// No row of padding is fetched: of a group that holds the end of the true bond only `lim` k-steps are needed (the matrix instructions of the
+// others are not issued), and the others are asked for at the address of the last one needed -- the same cache lines, so the request ends in
+// the L1 and costs no byte over the fabric (a bond of 84 is padded to 96 rows: an eighth of both streams).  The four addresses of a group are
+// wave-uniform bases (qkf_kbase: scalar min / multiply / add where a stream starts or changes), the lane offset is shared, so the matrix
+// blocks hold the same vector instructions as with unconditional loads.  `lim` of a stream is that of its FIRST group: min(4, k-steps of b)
+// for a B stream, the k-steps below the true bond of its block of rows for an A stream (whose groups all cover the same rows).  The
+// streams of the dual kernel leave it at 4: they load whole groups (rows up to the padded bond exist and are zero).  X from the global
+// buffer (strip path) is loaded whole as well: its four k-steps are immediate offsets of ONE vector address, and an address per k-step
+// would cost the steady block a vector instruction each.
 struct QkfStream {
   const v2d* base;
   unsigned off;
   int step;
+  int lim = 4;
 };
+__device__ __forceinline__ const v2d* qkf_kbase(const v2d* const base, const int step, const int i, const int lim) { return base + max(min(i, lim - 1), 0) * step; }
 __device__ __forceinline__ void qkf_load4(v2d (&fr)[4], const QkfStream& st) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) fr[i] = qkf_ldg(st.base + i * st.step, st.off);
+  for (int i = 0; i < 4; ++i) fr[i] = qkf_ldg(qkf_kbase(st.base, st.step, i, st.lim), st.off);
 }
+// ... with the lane offset in BYTES (phase 1 keeps its two running offsets in the unit the instructions take: one addition per group each)
+__device__ __forceinline__ v2d qkf_ldgb(const v2d* __restrict__ base, const unsigned boff) {
+  const v2d* const at = reinterpret_cast<const v2d*>(reinterpret_cast<const char*>(base) + (size_t)boff);
+  return QKF_NT_B ? __builtin_nontemporal_load(at) : *at;  // (the phase-1 B stream: the QKF_NT_B experiment applies)
+}
+// this lane's running position in the X operand of phase 1: an LDS address, or a byte offset on the (wave-uniform) global buffer -- one
+// addition per group of k-steps either way, the four k-steps of a group are immediate offsets
+struct QkfXLds {
+  const lds_v2d* p;
+  __device__ __forceinline__ void advance() { p += 4 * QKF_XSTEP; }
+  __device__ __forceinline__ v2d kstep(const int i) const { return p[i * QKF_XSTEP]; }
+};
+struct QkfXGlobal {
+  const v2d* base;
+  unsigned bo;
+  __device__ __forceinline__ void advance() { bo += 4 * QKF_XSTEP * 16u; }
+  __device__ __forceinline__ v2d kstep(const int i) const { return *reinterpret_cast<const v2d*>(reinterpret_cast<const char*>(base + i * QKF_XSTEP) + (size_t)bo); }
+};
+__device__ __forceinline__ QkfXLds qkf_xcursor(const lds_v2d* xp, const unsigned xoff) { return QkfXLds{xp + xoff}; }
+__device__ __forceinline__ QkfXGlobal qkf_xcursor(const v2d* xp, const unsigned xoff) { return QkfXGlobal{xp, xoff * 16u}; }
 
 // Phase 1, one tile (= one item): T[ta, p, tb] = sum_{l < 4 nks} X[l][16 ta + .] * B[l][p][16 tb + .].
 //   B operand: stream `cur` (step = one k-step = 4 rows of b); its first group is already in `fr` when `primed`;
@@ -134,23 +175,31 @@ __device__ __forceinline__ void qkf_load4(v2d (&fr)[4], const QkfStream& st) {
 // Four k-steps of fragments are in flight: the registers of a k-step are reloaded for k-step + 4 right after its
 // MFMAs (sched_barrier keeps that order); in the LAST group they are reloaded with the first group of stream `nxt`
 // -- the wave's next tile, or its first phase-2 group -- so the stream never drains between tiles or across the
-// barriers.  Loads are unconditional (rows up to the padded bond exist and are zero), MFMAs are issued only for the
-// k-steps below the true bond.
+// barriers.  MFMAs are issued only for the k-steps below the true bond, and the rows of padding above it are not
+// fetched: the group that holds the end of the bond (`last` k-steps) is loaded from bases of its own (QkfStream), which
+// the steady loop takes over for its final trip -- the loop runs in two passes over ONE body, the bases change between them.
 template <typename XPtr>
 __device__ __forceinline__ void qkf_p1_tile(QkfTile& t, v2d (&fr)[4], const bool primed, QkfStream cur, XPtr xp, unsigned xoff, const int nks, const QkfStream nxt) {
   v4d p1 = {0, 0, 0, 0}, p2 = {0, 0, 0, 0}, p3 = {0, 0, 0, 0};
   v2d fx[4];
+  const int ng = (nks + 3) >> 2, last = nks - 4 * (ng - 1);  // k-steps of the last group: 1..4
   if (!primed) qkf_load4(fr, cur);
 #pragma unroll
   for (int i = 0; i < 4; ++i) fx[i] = qkf_ldx(xp + i * QKF_XSTEP, xoff);
-  const int ng = (nks + 3) >> 2, last = nks - 4 * (ng - 1);  // k-steps of the last group: 1..4
+  // the bases the NEXT group is loaded from: whole groups, but the last group only up to the bond
+  const v2d* cb[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) cb[i] = qkf_kbase(cur.base, cur.step, i, ng == 2 ? last : 4);
+  unsigned bo = cur.off * 16u;  // this lane's byte offset into the B stream, and its X address: the two running values of the loops
+  const unsigned bs = (unsigned)(4 * cur.step) * 16u;
+  auto xq = qkf_xcursor(xp, xoff);
   QKF_PRIO_LO();
   int gq = 0;
   // the first k-step of a chain of more than four k-steps STARTS the accumulators (literal zero as the C operand): no register moves to zero
   // them -- on gfx950 every vector instruction takes time from the matrix pipe (lab/tools/mfma_rate.hip)
   if (ng >= 2) {
     gq = 1;
-    cur.off += 4 * cur.step, xoff += 4 * QKF_XSTEP;
+    bo += bs, xq.advance();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (i == 0) {
@@ -161,26 +210,33 @@ __device__ __forceinline__ void qkf_p1_tile(QkfTile& t, v2d (&fr)[4], const bool
       } else {
         qkf_kstep<false>(p1, p2, p3, fx[i].x, fx[i].y, fr[i].x, fr[i].y);
       }
-      if (!(QKF_ABL & 2)) fr[i] = qkf_ldg_b(cur.base + i * cur.step, cur.off);
-      if (!(QKF_ABL & 8)) fx[i] = qkf_ldx(xp + i * QKF_XSTEP, xoff);
+      if (!(QKF_ABL & 2)) fr[i] = qkf_ldgb(cb[i], bo);
+      if (!(QKF_ABL & 8)) fx[i] = xq.kstep(i);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
+  // pass 0: the groups that are followed by a whole group; pass 1: the one trip that loads the last group, from its own bases
 #pragma unroll 1
-  for (; gq + 1 < ng; ++gq) {
-    cur.off += 4 * cur.step, xoff += 4 * QKF_XSTEP;
+  for (int pass = 0; pass < 2; ++pass) {
+    const int end = ng - 2 + pass;
+#pragma unroll 1
+    for (; gq < end; ++gq) {
+      bo += bs, xq.advance();
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      qkf_kstep<false>(p1, p2, p3, fx[i].x, fx[i].y, fr[i].x, fr[i].y);
-      if (!(QKF_ABL & 2)) fr[i] = qkf_ldg_b(cur.base + i * cur.step, cur.off);
-      if (!(QKF_ABL & 8)) fx[i] = qkf_ldx(xp + i * QKF_XSTEP, xoff);
-      __builtin_amdgcn_sched_barrier(0);
+      for (int i = 0; i < 4; ++i) {
+        qkf_kstep<false>(p1, p2, p3, fx[i].x, fx[i].y, fr[i].x, fr[i].y);
+        if (!(QKF_ABL & 2)) fr[i] = qkf_ldgb(cb[i], bo);
+        if (!(QKF_ABL & 8)) fx[i] = xq.kstep(i);
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cb[i] = qkf_kbase(cur.base, cur.step, i, last);
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     if (i < last) qkf_kstep<false>(p1, p2, p3, fx[i].x, fx[i].y, fr[i].x, fr[i].y);
-    if (!(QKF_ABL & 2)) fr[i] = qkf_ldg(nxt.base + i * nxt.step, nxt.off);
+    if (!(QKF_ABL & 2)) fr[i] = qkf_ldg(qkf_kbase(nxt.base, nxt.step, i, nxt.lim), nxt.off);
     __builtin_amdgcn_sched_barrier(0);
   }
   QKF_PRIO_HI();
@@ -248,13 +304,13 @@ __device__ __forceinline__ void qkf_p2_item(const QkfTile& t, v2d (&fr)[4], cons
     v4d p1 = {0, 0, 0, 0}, p2 = {0, 0, 0, 0}, p3 = {0, 0, 0, 0};
     const bool fin = tn + 1 == nn;
     const v2d* const rb = fin ? nxt.base : cur.base;
-    const int rs = fin ? nxt.step : cur.step;
+    const int rs = fin ? nxt.step : cur.step, rl = fin ? nxt.lim : FULL ? 4 : kmax;  // (the k-steps at or above the bond: the address of the last one below it)
     cur.off = fin ? nxt.off : cur.off + TILE;
     QKF_PRIO_LO();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (FULL || i < kmax) qkf_kstep<true>(p1, p2, p3, t.re[i], t.im[i], fr[i].x, fr[i].y);
-      if (!(QKF_ABL & 2)) fr[i] = qkf_ldg_a(rb + i * rs, cur.off);
+      if (!(QKF_ABL & 2)) fr[i] = qkf_ldg_a(qkf_kbase(rb, rs, i, rl), cur.off);
       __builtin_amdgcn_sched_barrier(0);
     }
     QKF_PRIO_HI();
@@ -369,7 +425,7 @@ __device__ __forceinline__ void qkf_edge_suffix(const SweepArgs& g, const int xi
 
 // What a site needs: bonds, tile counts, where its X / X' live and how its items are cut into strips.
 struct QkfSite {
-  int a, a2, b, b2, at, nks, mt, nt, nn, W, inv, pd, ps, next;  // next = the table entry of the step after this one; pd = physical dimension of the step (2, or 4 for two merged sites), ps = log2 pd; inv = ceil(2^20 / mt): u / mt == (u * inv) >> 20 for u < 2048, mt <= 32 (checked exhaustively)
+  int a, a2, b, b2, at, nks, mt, nt, nn, W, inv, inv2, pd, ps, next;  // inv2 = the two reciprocals of the strips' column units (qk_unit_recips); next = the table entry of the step after this one; pd = physical dimension of the step (2, or 4 for two merged sites), ps = log2 pd; inv = ceil(2^20 / mt): u / mt == (u * inv) >> 20 for u < 2048, mt <= 32 (checked exhaustively)
   bool small;
   const v2d *Ak, *Bk;
 };
@@ -377,7 +433,8 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4i lds_v4i;
 
 // The step table of a pair, built by all threads at pair set-up: per step 12 ints (48 bytes)
-//   [0] a  [1] a2  [2] b  [3] b2  [4] true a  [5] k-steps of b  [6] W  [7] small  [8] ceil(2^20 / mt)  [9] log2 pd  [10] next step  [11] -
+//   [0] a  [1] a2  [2] b  [3] b2  [4] true a  [5] k-steps of b  [6] W  [7] small  [8] ceil(2^20 / mt)  [9] log2 pd  [10] next step
+//   [11] ITEM_RECIPS (the one-tile kernel's order of items): ceil(2^15 / column blocks) of a full strip | of the last strip << 16 (qk_unit_recips)
 // and the addresses of the step's two tensors ([a][pd][a2] of x, [b][pd][b2] of y) in a second table.  A step is one site (pd = 2,
 // entry = the site's index, next = + 1) or, with a merged image (SweepArgs.merge_steps), two sites contracted into one tensor of
 // physical dimension 4 (entry = the first site's index, next = + 2).  The merged step does the same matrix work as its two sites when
@@ -385,7 +442,7 @@ typedef __attribute__((address_space(3))) v4i lds_v4i;
 // unless it would push an LDS-resident pair of sites out of the LDS (its 4 mt nt items no longer fit one round, and X and X' do not
 // fit side by side) or cost more padded work than the two sites (a dip of the bond between them).  `one_round(pd * mt, nt)`:
 // the kernel's test that a single round holds all items of a step.
-template <int XCAP, int NT, typename OneRound>
+template <int XCAP, int NT, bool ITEM_RECIPS = false, typename OneRound>
 __device__ __forceinline__ void qkf_step_table(const SweepArgs& g, const int xi, const int yj, lds_v4i* const rec, long long* const m_off, const int tid, const OneRound one_round) {
   const int ns = g.n_sites, n1 = ns + 1;
   const int32_t* const xd = g.xdims + (long long)xi * n1;
@@ -403,7 +460,7 @@ __device__ __forceinline__ void qkf_step_table(const SweepArgs& g, const int xi,
     const int W = small ? nt : max(1, min(nt, XCAP / (TILE * a2)));  // X' in strips of W blocks of b' (the strip's rows must fit the LDS)
     rec[3 * e] = (v4i){a, a2, b, b2};
     rec[3 * e + 1] = (v4i){xt[e], (yt[e] + 3) >> 2, W, small ? 1 : 0};
-    rec[3 * e + 2] = (v4i){((1 << 20) + mt - 1) / mt, ps, next, 0};
+    rec[3 * e + 2] = (v4i){qk_recip20(mt), ps, next, ITEM_RECIPS ? qk_unit_recips(nt, W, false) : 0};
     // (as element offsets from the sets' plain images, whatever buffer the tensor lives in: the kernels add them to their pointer
     //  ARGUMENTS, which keeps the fragment loads global_load -- an address that comes out of the table as an integer makes them
     //  flat_load, whose waits cover the LDS counter as well)
@@ -495,21 +552,26 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
     QkfSite s;
     s.a = rfl(r0.x), s.a2 = rfl(r0.y), s.b = rfl(r0.z), s.b2 = rfl(r0.w);
     s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.small = rfl(r1.w) != 0;
-    s.inv = rfl(r2.x);
+    s.inv = rfl(r2.x), s.inv2 = rfl(r2.w);
     s.ps = rfl(r2.y), s.pd = 1 << s.ps, s.next = rfl(r2.z);
     s.mt = s.a / TILE, s.nt = s.b2 / TILE, s.nn = s.a2 / TILE;
     s.Ak = xdata + ldl(m_off + 2 * k);      // [a][pd][a2]
     s.Bk = ydata + ldl(m_off + 2 * k + 1);  // [b][pd][b2]
     return s;
   };
-  // the streams of item `it` of a strip starting at block s0 (it = 2 (tbl * mt + ta) + p)
-  auto b_stream = [&](const QkfSite& s, const int s0, const int it) __attribute__((always_inline)) {
-    const int pp = it & (s.pd - 1), u = it >> s.ps, tbl = (u * s.inv) >> 20;
-    return QkfStream{s.Bk + pp * s.b2, (unsigned)((q * s.pd) * s.b2 + (s0 + tbl) * TILE + j), 4 * s.pd * s.b2};
+  // item `it` of a strip of w column blocks as (ta, tc = block of the strip, p): the order of qk_plan.h -- p slowest, so that the waves of a
+  // round share both operands; the ordered form keeps p fastest (its turn index rises along `it`)
+  auto item_of = [&](const QkfSite& s, const int w, const int it) __attribute__((always_inline)) {
+    return DET ? qk_unit_decode_ordered(it, s.ps, s.mt, s.inv) : qk_unit_decode(it, s.mt, w, s.inv, qk_unit_recip_of(s.inv2, w == s.W));
   };
-  auto a_stream = [&](const QkfSite& s, const int it) __attribute__((always_inline)) {
-    const int pp = it & (s.pd - 1), u = it >> s.ps, tbl = (u * s.inv) >> 20, ta = u - tbl * s.mt;
-    return QkfStream{s.Ak + pp * s.a2, (unsigned)(((ta * TILE + q) * s.pd) * s.a2 + j), 4 * s.pd * s.a2};
+  // the streams of item `it` of a strip of w blocks starting at block s0
+  auto b_stream = [&](const QkfSite& s, const int s0, const int w, const int it) __attribute__((always_inline)) {
+    const QkUnit un = item_of(s, w, it);
+    return QkfStream{s.Bk + un.p * s.b2, (unsigned)((q * s.pd) * s.b2 + (s0 + un.tc) * TILE + j), 4 * s.pd * s.b2, min(4, s.nks)};
+  };
+  auto a_stream = [&](const QkfSite& s, const int w, const int it) __attribute__((always_inline)) {
+    const QkUnit un = item_of(s, w, it);
+    return QkfStream{s.Ak + un.p * s.a2, (unsigned)(((un.ta * TILE + q) * s.pd) * s.a2 + j), 4 * s.pd * s.a2, min(4, (s.at - un.ta * TILE + 3) >> 2)};
   };
   QKF_PROF_DECL();
   const int xcc = qk_xcc_id();
@@ -529,7 +591,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
     // an item is (ta, tb, p): pd mt nt of them.  LDS-resident step: X and X' fit the buffer and either ONE round holds all items
     // (X' may then overwrite X) or X and X' fit side by side (any number of rounds: X stays intact);
     // otherwise X' is built in strips of W blocks of b' (the strip's rows must fit the LDS), items in rounds of NW * S
-    qkf_step_table<XCAP, NT>(g, xi, yj, rec, m_off, tid, [](const int pmt, const int nt) { return pmt * nt <= NW * S; });
+    qkf_step_table<XCAP, NT, true>(g, xi, yj, rec, m_off, tid, [](const int pmt, const int nt) { return pmt * nt <= NW * S; });
     const int ek = g.edge_k, k_hi = ns - ek;  // the chain runs over the sites [ek, k_hi): the ends are in the edge blocks
     const bool edges = ek > 0;
     if (!edges)
@@ -600,10 +662,10 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
               if (multi) qkf_rotate<S>(T, L);
               const int it = it0 + NW * s;
               if (it < items) {
-                const int u = it >> sc.ps, tbl = (u * sc.inv) >> 20, ta = u - tbl * mt;
+                const int ta = item_of(sc, w, it).ta;
                 const bool more = s + 1 < L && it + NW < items;  // another tile follows in this phase; else phase 2 starts with item it0
-                const QkfStream nxt = more ? b_stream(sc, s0, it + NW) : a_stream(sc, it0);
-                qkf_p1_tile(T[S - 1], fr, primed, b_stream(sc, s0, it), xbase, (unsigned)(ta * (b * TILE) + q * TILE + j), sc.nks, nxt);
+                const QkfStream nxt = more ? b_stream(sc, s0, w, it + NW) : a_stream(sc, w, it0);
+                qkf_p1_tile(T[S - 1], fr, primed, b_stream(sc, s0, w, it), xbase, (unsigned)(ta * (b * TILE) + q * TILE + j), sc.nks, nxt);
                 primed = true;
               }
             }
@@ -626,16 +688,18 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
             const int it = it0 + NW * s;
             if (it >= items) break;
             if (multi) qkf_rotate<S>(T, L);
-            const int u = it >> sc.ps, tbl = (u * sc.inv) >> 20, ta = u - tbl * mt;
+            const QkUnit un = item_of(sc, w, it);
+            const int ta = un.ta, tbl = un.tc;
             const int kmax = min(4, (sc.at - ta * TILE + 3) >> 2);
             const bool more = s + 1 < S && it + NW < items;
             // after the wave's last item of the site: its first tile of the next site (strip 0, round 0), if it has one
-            const bool chain = !more && last_round && k < k_hi && wave < sn.pd * sn.mt * min(sn.W, sn.nt);
-            const QkfStream nxt = more ? a_stream(sc, it + NW) : chain ? b_stream(sn, 0, wave) : a_stream(sc, it);
-            const int tix = sc.pd * ta + (it & (sc.pd - 1));  // this contribution's place in the order of its block of rows
+            const int wn = min(sn.W, sn.nt);
+            const bool chain = !more && last_round && k < k_hi && wave < sn.pd * sn.mt * wn;
+            const QkfStream nxt = more ? a_stream(sc, w, it + NW) : chain ? b_stream(sn, 0, wn, wave) : a_stream(sc, w, it);
+            const int tix = sc.pd * ta + un.p;  // (ordered form) this contribution's place in the order of its block of rows
             const QkfTurn turn{tcur + tbl * sc.nn, tix, tbroken, g.err};
-            if (kmax == 4) qkf_p2_item<true, DET>(T[S - 1], fr, primed, a_stream(sc, it), w * QKF_XBLOCK, sc.nn, 4, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
-            else qkf_p2_item<false, DET>(T[S - 1], fr, primed, a_stream(sc, it), w * QKF_XBLOCK, sc.nn, kmax, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
+            if (kmax == 4) qkf_p2_item<true, DET>(T[S - 1], fr, primed, a_stream(sc, w, it), w * QKF_XBLOCK, sc.nn, 4, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
+            else qkf_p2_item<false, DET>(T[S - 1], fr, primed, a_stream(sc, w, it), w * QKF_XBLOCK, sc.nn, kmax, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
             primed = more || chain;
           }
           QKF_STAMP(4);  // phase 2
@@ -970,10 +1034,14 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
     s.Bk = ydata + ldl(m_off + 2 * k + 1);
     return s;
   };
-  // the streams of pair `v` of a strip starting at block s0 (v = 2 (tp * mt + ta) + p; column blocks s0 + 2 tp, + 1)
+  // pair `v` of a strip as (ta, tc = tp: column blocks 2 tp, 2 tp + 1 of the strip, p).  This kernel keeps the order with p fastest in BOTH
+  // its forms (qk_unit_decode_ordered, qk_plan.h): with p slowest -- the order of the one-tile kernel, fewer operand blocks per round -- it
+  // measured 2 % SLOWER on the headline set (lab/NOTES_r05.md), and fetching no padding did not pay here either
+  auto pair_of = [&](const QkfSite& s, const int v) __attribute__((always_inline)) { return qk_unit_decode_ordered(v, s.ps, s.mt, s.inv); };
+  // the streams of pair `v` of a strip starting at block s0 (column blocks s0 + 2 tp, + 1)
   auto b_stream = [&](const QkfSite& s, const int s0, const int v, const int half) __attribute__((always_inline)) {
-    const int pp = v & (s.pd - 1), u = v >> s.ps, tp = (u * s.inv) >> 20;
-    return QkfStream{s.Bk + pp * s.b2, (unsigned)((q * s.pd) * s.b2 + (s0 + 2 * tp + half) * TILE + j), 4 * s.pd * s.b2};
+    const QkUnit un = pair_of(s, v);
+    return QkfStream{s.Bk + un.p * s.b2, (unsigned)((q * s.pd) * s.b2 + (s0 + 2 * un.tc + half) * TILE + j), 4 * s.pd * s.b2};
   };
   // What this wave does in the round that starts at unit r0 of a strip of w blocks with `units` pairs of tiles: pair r0 + wave
   // -- or, when the units left fill at most half of the waves, ONE tile of a pair (column block 2 tp or 2 tp + 1):
@@ -989,15 +1057,15 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
     // (first tiles to waves 0 .. left - 1, second tiles to the next `left` waves: consecutive waves sit on different SIMDs)
     un.half = (halves && wave >= left) ? 1 : 0;
     un.v = r0 + wave - (un.half ? left : 0);
-    const int tp = ((un.v >> s.ps) * s.inv) >> 20;
+    const int tp = pair_of(s, un.v).tc;
     const bool second = 2 * tp + 1 < w;  // the pair has a second tile
     un.mine = un.v < units && (un.half == 0 || second);
     un.has1 = !halves && second;
     return un;
   };
   auto a_stream = [&](const QkfSite& s, const int v) __attribute__((always_inline)) {
-    const int pp = v & (s.pd - 1), u = v >> s.ps, tp = (u * s.inv) >> 20, ta = u - tp * s.mt;
-    return QkfStream{s.Ak + pp * s.a2, (unsigned)(((ta * TILE + q) * s.pd) * s.a2 + j), 4 * s.pd * s.a2};
+    const QkUnit un = pair_of(s, v);
+    return QkfStream{s.Ak + un.p * s.a2, (unsigned)(((un.ta * TILE + q) * s.pd) * s.a2 + j), 4 * s.pd * s.a2};
   };
   QKF_PROF_DECL();
   const int xcc = qk_xcc_id();
@@ -1075,7 +1143,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
           const Unit un = unit_of(sc, w, units, r0);
           const int v = un.v;
           const bool mine = un.mine, has1 = un.has1;
-          const int u = v >> sc.ps, tp = (u * sc.inv) >> 20, ta = u - tp * mt;
+          const QkUnit pr = pair_of(sc, v);
+          const int tp = pr.tc, ta = pr.ta;
           if (mine) {
             const QkfStream bs = b_stream(sc, s0, v, un.half), as = a_stream(sc, v);
             const unsigned xoff = (unsigned)(ta * (b * TILE) + q * TILE + j);
@@ -1117,7 +1186,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
             const unsigned nd1 = 0;
             lds_v2d* const xo = XL + ob + (2 * tp + un.half) * QKF_XBLOCK;
             // the turn counters of this block of rows and this contribution's place in their order
-            const QkfTurn tp_turn{tcur + (2 * tp + un.half) * sc.nn, sc.pd * ta + (v & (sc.pd - 1)), tbroken, g.err};
+            const QkfTurn tp_turn{tcur + (2 * tp + un.half) * sc.nn, sc.pd * ta + pr.p, tbroken, g.err};
             if (has1) {
               if (kmax == 4) qkf_p2_dual<true, true, DET>(T0, T1, fr, fs, a_stream(sc, v), w * QKF_XBLOCK, sc.nn, 4, xo, q, j, nxt, np1, nd1, tp_turn);
               else qkf_p2_dual<false, true, DET>(T0, T1, fr, fs, a_stream(sc, v), w * QKF_XBLOCK, sc.nn, kmax, xo, q, j, nxt, np1, nd1, tp_turn);

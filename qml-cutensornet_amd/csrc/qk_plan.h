@@ -26,6 +26,52 @@ static constexpr int QK_TILE = 16;                                        // M/N
 static inline int qk_pad16(int x) { return (x + QK_TILE - 1) / QK_TILE * QK_TILE; }
 static constexpr int GMAX = 4;  // pairs per group of the group-sweep lab kernel (sizes its X/T scratch)
 
+// ----------------------------------------------------------------------------------------
+// The order of a step's units in the site-fused sweep (qk_fused.h).  A step has pd * mt * wc units (ta, tc, p): ta = block of 16 rows of
+// A_k (mt of them), p = physical index (pd = 2, or 4 for a merged step), tc = column unit of the strip of X' at hand -- a PAIR of column
+// blocks (2 tc, 2 tc + 1) in the dual kernel, wc = ceil(w / 2), one column block in the one-tile kernel, wc = w (qk_unit_cols).  The units
+// are dealt to the NW waves of a workgroup in rounds of NW consecutive indices v, so the order decides which operands the waves of a round
+// share: unit (ta, tc, p) reads the A block (ta, p) and the B blocks (p, its column blocks).
+//   qk_unit_decode:          v = (p * wc + tc) * mt + ta -- p slowest, ta fastest.  A round then lies inside one p (two at a seam) and covers
+//                            a few tc with all their ta: the waves that run together share BOTH operands (an A block between the tc of the
+//                            round, a B block between its ta).  The plain (arrival-order) form of the one-tile kernel uses it.
+//   qk_unit_decode_ordered:  v = pd * (tc * mt + ta) + p -- p fastest, tc slowest: every round takes one or two tc with all their (ta, p), so
+//                            an A block is wanted again a whole round later, once per tc.  The ordered (DET) kernels keep it: their turn
+//                            index pd * ta + p must rise along v inside a block of rows (qkf_turn_add).  So does the dual kernel in its
+//                            plain form: it measured 2 % slower with p slowest (lab/NOTES_r05.md).
+// Both are pure functions of the index, host and device, and are checked on the CPU (tests/host_san/units_main.cpp: every unit exactly once,
+// the reciprocals against the divisions, and the count of operand blocks per round of the two orders).
+// The divisions are multiplications by reciprocals from the step record: inv_mt = ceil(2^20 / mt) (v / mt for v < 4096, mt <= 32) and
+// inv_wc = ceil(2^15 / wc) (c / wc for c < 128, wc <= 32): a step has up to two strip widths (W and a shorter last strip), so two 16-bit
+// reciprocals share one word of the record (qk_unit_recips).
+// ----------------------------------------------------------------------------------------
+#if defined(__HIPCC__)
+#define QK_HD __host__ __device__
+#else
+#define QK_HD
+#endif
+struct QkUnit {
+  int ta, tc, p;
+};
+QK_HD static inline int qk_unit_cols(const int w, const bool dual) { return dual ? (w + 1) >> 1 : w; }
+QK_HD static inline int qk_recip20(const int d) { return ((1 << 20) + d - 1) / d; }  // n / d == (n * qk_recip20(d)) >> 20 for n < 4096, d <= 32
+QK_HD static inline int qk_recip15(const int d) { return ((1 << 15) + d - 1) / d; }  // n / d == (n * qk_recip15(d)) >> 15 for n < 128, d <= 32
+// the record's word [11] of a step with nt column blocks in strips of W: the reciprocal of the column units of a full strip in the low half,
+// of the last strip (nt - W * floor((nt - 1) / W) blocks; the same when W divides nt) in the high half
+QK_HD static inline int qk_unit_recips(const int nt, const int W, const bool dual) {
+  const int wl = nt - (nt - 1) / W * W;
+  return qk_recip15(qk_unit_cols(W, dual)) | (qk_recip15(qk_unit_cols(wl, dual)) << 16);
+}
+QK_HD static inline int qk_unit_recip_of(const int recips, const bool full_strip) { return full_strip ? (recips & 0xffff) : (int)((unsigned)recips >> 16); }
+QK_HD static inline QkUnit qk_unit_decode(const int v, const int mt, const int wc, const int inv_mt, const int inv_wc) {
+  const int c = (v * inv_mt) >> 20, p = (c * inv_wc) >> 15;
+  return QkUnit{v - c * mt, c - p * wc, p};
+}
+QK_HD static inline QkUnit qk_unit_decode_ordered(const int v, const int ps, const int mt, const int inv_mt) {
+  const int u = v >> ps, tc = (u * inv_mt) >> 20;
+  return QkUnit{u - tc * mt, tc, v & ((1 << ps) - 1)};
+}
+
 struct qk_ctx;
 
 struct qk_plan {
