@@ -304,6 +304,26 @@ int qk_local_paulis_host(qk_ctx* ctx, const qk_mps_set* set, double* out /* [n_s
 int qk_projected_gram_host(qk_ctx* ctx, int32_t n_sites, int32_t nx, const double* fx /* [nx][n_sites][3] */,
                            int32_t ny, const double* fy /* NULL: Y is X */, double g, double* out, int64_t ld);
 
+/* Pauli correlators of neighbouring qubits: the two-qubit reduced density matrices of the pairs (k, k+1), k = 0 .. n_sites - 2,
+ * of every state of a set, synchronous on the context's stream.  P_0..P_3 = I, X, Y, Z:
+ *     rho_{k,k+1}[(s,t)][(s',t')] = sum over all other sites of psi(..s,t..) conj(psi(..s',t'..)) / <psi|psi>
+ *     out2[state][k][p][q] = <P_p on k, P_q on k+1> = sum rho_{k,k+1}[(s,t)][(s',t')] P_p[s'][s] P_q[t'][t]      (real)
+ * so rho_{k,k+1} = 1/4 sum_{p,q} out2[k][p][q] P_p (x) P_q.  out2[k][0][0] is exactly 1.0; out2[k][p][0] and out2[k][0][q] are the
+ * Bloch vectors of qubits k and k+1 (to rounding).  out1 and norms, when given, are what qk_local_paulis_host returns for the same
+ * set, bit for bit: the sweep is that call's with two more GEMMs per site (the open right environment of site k+1), and shares its
+ * guarantees -- every state's result is bit-identical whatever the rest of the set and from run to run.  fp64 sets only (a complex64
+ * set is QK_EINVAL); n_sites < 2 is QK_EINVAL.  Device scratch as qk_local_paulis_host (26 instead of 14 P^2 doubles per state).  */
+int qk_local_pair_paulis_host(qk_ctx* ctx, const qk_mps_set* set, double* out2 /* [n_states][n_sites-1][4][4] */,
+                              double* out1 /* [n_states][n_sites][3], may be NULL */, double* norms /* [n_states], may be NULL */);
+
+/* The two-qubit projected-kernel Gram from Pauli correlators (host arrays [n][n_sites-1][4][4]), synchronous:
+ *     out[j * ld + i] = exp(-g/4 * sum_k sum_{p,q} (tx[i][k][p][q] - ty[j][k][p][q])^2)
+ *                     = exp(-g sum_k ||rho_{k,k+1}(x_i) - rho_{k,k+1}(y_j)||_F^2)
+ * Rows, columns, ty = NULL, the fixed summation order (exact symmetry, unit diagonal) and the argument errors are those of
+ * qk_projected_gram_host, except that n_sites < 2 is QK_EINVAL.                                                              */
+int qk_projected_pair_gram_host(qk_ctx* ctx, int32_t n_sites, int32_t nx, const double* tx /* [nx][n_sites-1][4][4] */,
+                                int32_t ny, const double* ty /* NULL: Y is X */, double g, double* out, int64_t ld);
+
 /* ---- profiler ranges -----------------------------------------------------------------------------------------
  * roctx ranges (rocprofv3 --marker-trace) named "qk:build", "qk:upload", "qk:sweep", "qk:scatter", "qk:allgather_values",
  * "qk:allgather_sets" are opened by the library around its own phases -- the reference's MPI.Wtime() sites G:209-231

@@ -1,6 +1,7 @@
-// qk_local.hip -- per-qubit reduced density matrices of every state of a set (their Bloch vectors) and the projected quantum
-// kernel (PQK) Gram built from them.  Part of libqkgram.so; entry points qk_local_paulis_host and qk_projected_gram_host
-// (include/qkgram.h).
+// qk_local.hip -- per-qubit reduced density matrices of every state of a set (their Bloch vectors), the two-qubit reduced density
+// matrices of neighbouring qubits (their Pauli correlators) and the projected quantum kernel (PQK) Grams built from either.  Part of
+// libqkgram.so; entry points qk_local_paulis_host, qk_projected_gram_host, qk_local_pair_paulis_host and
+// qk_projected_pair_gram_host (include/qkgram.h).
 //
 // Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
 // normalised):
@@ -25,6 +26,18 @@
 // (zgemm_ring3, fixed K order).  The rho sums are split into 16-row chunks, one workgroup each, with a fixed-order reduction; the
 // chunks are added in a fixed order at the end.  No grid-wide barrier, no spin wait, no atomics: a state's features are the same
 // bits whatever its batch, its neighbours or the run.
+//
+// The pair sweep (qk_local_pair_paulis_host).  P_0..P_3 = I, X, Y, Z:
+//     rho_{k,k+1}[(s,t)][(s',t')] = sum over every other site of psi(..s,t..) conj(psi(..s',t'..)) / <psi|psi>
+//     T[k][p][q] = <P_p on k, P_q on k+1> = sum rho_{k,k+1}[(s,t)][(s',t')] P_p[s'][s] P_q[t'][t]         (k = 0 .. n-2, real)
+//     K_2[j][i]  = exp(-g/4 sum_k sum_{p,q} (Tx[i][k][p][q] - Ty[j][k][p][q])^2)   (= exp(-g sum_k ||rho_{k,k+1}(x_i) - rho_{k,k+1}(y_j)||_F^2))
+// It is the local sweep with two more GEMMs per site: the mirror image of W at site k+1, open on its physical index,
+//     T'_{k+1}[d'][(t, b')]     = sum_c' R_{k+2}[c'][d'] A_{k+1}[b'][t][c']              (the LOC_REV_T shape on the reversed image)
+//     V_{k+1,t}[b'][(t', a')]   = sum_d' T'_{k+1}[d'][(t, b')] conj(A_{k+1}[a'][t'][d']) (the LOC_FWD_W shape on the reversed image)
+//     rho_{k,k+1}[(s,t)][(s',t')] = sum_{b', a'} W_{k,s}[b'][(s', a')] V_{k+1,t}[b'][(t', a')]
+// (R_{k+1} = V_0[.][(0, .)] + V_1[.][(1, .)]).  V is made in the forward pass from the stored R_{k+2}, one site at a time: keeping
+// every V of the reverse pass would cost four times the R storage.  The reverse pass and the forward T / W / rho launches are the
+// one-qubit sweep's, in its order, so the Bloch vectors and norms of a pair call are the bits qk_local_paulis_host returns.
 #include "qk_host.h"
 #include "qk_ring.h"
 
@@ -46,10 +59,17 @@ enum LocKind : int {
   LOC_REV_X = 1,   // reversed chain: R_o = T^T conj(Ar_j)
   LOC_FWD_T = 2,   // T_k = L_k^T A_k
   LOC_FWD_W = 3,   // W_{k,s} = T_k[(., s)]^T conj(A_k), both s in one launch
+  LOC_PAIR_T = 4,  // pair sweep, site o = k+1 of the reversed image: T' = R_{o+1}^T Ar_o
+  LOC_PAIR_V = 5,  // pair sweep: V_{o,t} = T'[(., t)]^T conj(Ar_o), both t in one launch
+  LOC_RHO = -1,    // qk_local_rho_kernel
+  LOC_PAIR_RHO = -2,  // qk_local_pair_rho_kernel
 };
 
 // Per-state scratch (doubles, every matrix as a re plane then an im plane), P = the state's largest padded bond:
-//   L [P x P] at 0 | T [P x 2P] at 2P^2 | W_0 [P x 2P] at 6P^2 | W_1 at 10P^2 | R_1 .. R_n at 14P^2 + roff[k] (pad_k^2 per plane)
+//   L [P x P] at 0 | T [P x 2P] at 2P^2 | W_0 [P x 2P] at 6P^2 | W_1 at 10P^2 | R_1 .. R_n at rmul P^2 + roff[k] (pad_k^2 per plane)
+// rmul = 14 for the one-qubit sweep; the pair sweep has T' at 14P^2, V_0 at 18P^2, V_1 at 22P^2 and rmul = 26.
+constexpr int LOC_RMUL = 14, LOC_RMUL_PAIR = 26;
+constexpr int LOC_PAIR_VALS = 16;                                   // reals of a Hermitian 4 x 4 matrix
 struct LocArgs {
   const double* data;     // the set's planes
   const double* rev;      // the reversed image: site o of a state transposed to [pad_{o+1}][2][pad_o], at the set's offset of site o
@@ -59,13 +79,15 @@ struct LocArgs {
   const int32_t* states;  // batch entry -> state of the set
   const int32_t* pmax;    // batch entry -> P
   const int64_t* sbase;   // batch entry -> first double of its scratch
-  const int64_t* roff;    // [batch][n_sites + 1]: R_k at sbase + 14 P^2 + roff[k]
+  const int64_t* roff;    // [batch][n_sites + 1]: R_k at sbase + rmul P^2 + roff[k]
   const int2* tasks;      // this launch: (batch entry, block)
   double* scratch;
   double* part;           // rho partial sums [batch][n_sites][max chunks][4]
+  double* part2;          // pair sweep: rho_{k,k+1} partial sums [batch][n_sites - 1][max chunks][16]
+  int rmul;
   int n_sites;
   int max_chunks;
-  int step;               // reversed-chain step j (LOC_REV_*) or site k (forward)
+  int step;               // reversed-chain step j (LOC_REV_*) or site k (forward, LOC_PAIR_*: the pair (k, k+1))
 };
 
 __device__ __forceinline__ long long uni64(const long long v) {
@@ -74,7 +96,7 @@ __device__ __forceinline__ long long uni64(const long long v) {
   return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
-// One 64 x 64 output block of one state's GEMM of this step.  CONJB: the LOC_REV_X / LOC_FWD_W products (conjugated site tensor).
+// One 64 x 64 output block of one state's GEMM of this step.  CONJB: the LOC_REV_X / LOC_FWD_W / LOC_PAIR_V products (conjugated site tensor).
 template <bool CONJB>
 __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, const int kind) {
   __shared__ __attribute__((aligned(16))) double lds[LOC_LDS_DOUBLES];
@@ -92,20 +114,26 @@ __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, con
   const double *Are, *Aim, *Bre, *Bim;
   double *Cre, *Cim;
   int lda, ldb, ldc, M, N, K;
-  if (kind == LOC_REV_T || kind == LOC_REV_X) {
-    const int o = n - 1 - g.step;
+  if (kind == LOC_REV_T || kind == LOC_REV_X || kind == LOC_PAIR_T || kind == LOC_PAIR_V) {
+    const int o = (kind == LOC_REV_T || kind == LOC_REV_X) ? n - 1 - g.step : g.step + 1;
     const int al = __builtin_amdgcn_readfirstlane(pd[o + 1]), ar = __builtin_amdgcn_readfirstlane(pd[o]);
     const int at = __builtin_amdgcn_readfirstlane(td[o + 1]);
     Bre = g.rev + uni64(g.offs[st * n + o]);
     Bim = Bre + (long long)al * 2 * ar;
-    if (kind == LOC_REV_T) {
-      Are = S + 14 * P2 + uni64(g.roff[(long long)i * n1 + o + 1]);
+    if (kind == LOC_REV_T || kind == LOC_PAIR_T) {
+      Are = S + g.rmul * P2 + uni64(g.roff[(long long)i * n1 + o + 1]);
       Aim = Are + (long long)al * al;
-      Cre = Tre, Cim = Tre + tpl;
+      Cre = (kind == LOC_REV_T) ? Tre : S + 14 * P2, Cim = Cre + tpl;
       lda = al, ldb = 2 * ar, ldc = 2 * ar, M = al, N = 2 * ar, K = at;
+    } else if (kind == LOC_PAIR_V) {
+      M = ar, N = 2 * ar;
+      const int t = blk >= ((M + 63) / 64) * ((N + 63) / 64);
+      Are = S + 14 * P2 + t * ar, Aim = Are + tpl;
+      Cre = S + 18 * P2 + t * 2 * tpl, Cim = Cre + tpl;
+      lda = 2 * ar, ldb = 2 * ar, ldc = 2 * ar, K = at;
     } else {
       Are = Tre, Aim = Tre + tpl;
-      Cre = S + 14 * P2 + uni64(g.roff[(long long)i * n1 + o]);
+      Cre = S + g.rmul * P2 + uni64(g.roff[(long long)i * n1 + o]);
       Cim = Cre + (long long)ar * ar;
       lda = ar, ldb = ar, ldc = ar, M = ar, N = ar, K = 2 * at;
     }
@@ -129,7 +157,7 @@ __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, con
     }
   }
   const int npm = (M + 63) / 64;
-  const int b = (kind == LOC_FWD_W) ? blk % (npm * ((N + 63) / 64)) : blk;
+  const int b = (kind == LOC_FWD_W || kind == LOC_PAIR_V) ? blk % (npm * ((N + 63) / 64)) : blk;
   const int m0 = 64 * (b % npm), n0 = 64 * (b / npm);
   zgemm_ring3<CONJB, LOC_KTL, LOC_NSLOT, true, 8, 64, double, 7>(Cre + (long long)m0 * ldc + n0, Cim + (long long)m0 * ldc + n0, ldc, Are + m0, Aim + m0, lda,
                                                                   Bre + n0, Bim + n0, ldb, min(64, M - m0), min(64, N - n0), K, lds);
@@ -148,7 +176,7 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_rho_kernel(const Loc
   double* const S = g.scratch + g.sbase[i];
   const double* W0 = S + 6 * P2;
   const double* W1 = W0 + 2 * tpl;
-  const double* R = S + 14 * P2 + g.roff[(long long)i * n1 + k + 1];
+  const double* R = S + g.rmul * P2 + g.roff[(long long)i * n1 + k + 1];
   const long long rpl = (long long)r * r;
   double a00 = 0, a11 = 0, a01r = 0, a01i = 0;
   const int rows = LOC_CHUNK * r;
@@ -176,13 +204,68 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_rho_kernel(const Loc
   if (threadIdx.x < 4) g.part[(((long long)i * n + k) * g.max_chunks + c) * 4 + threadIdx.x] = red[threadIdx.x][0];
 }
 
+// rho_{k,k+1} partial sums of one 16-row chunk of b': the products W_{k,s}[b'][(s', a')] V_{k+1,t}[b'][(t', a')] over the chunk's
+// rows and every a'.  The matrix is Hermitian (row 2s + t, column 2s' + t'), so a chunk keeps its 16 reals, unnormalised:
+//     part2[(i, k, chunk)] = Re rho[0][0], [1][1], [2][2], [3][3], then (Re, Im) of rho[0][1], [0][2], [0][3], [1][2], [1][3], [2][3]
+// LDS: red[16][256] doubles = 32 KiB, five workgroups (20 waves) per CU -- the kernel waits on its 16 global loads per element,
+// not on occupancy.  Every access is red[v][thread]: the 32 lanes that a ds_read_b64 / ds_write_b64 serves together touch 32
+// consecutive doubles, each of the 64 banks once, so the layout is conflict-free like the 4-value one of qk_local_rho_kernel.
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_pair_rho_kernel(const LocArgs g) {
+  __shared__ double red[LOC_PAIR_VALS][LOC_RED_THREADS];
+  const int2 t = g.tasks[blockIdx.x];
+  const int i = t.x, c = t.y;
+  const int n = g.n_sites, n1 = n + 1, k = g.step;
+  const long long st = g.states[i];
+  const int r = g.dims[st * n1 + k + 1];
+  const long long P = g.pmax[i], P2 = P * P, tpl = 2 * P2;
+  const double* const S = g.scratch + g.sbase[i];
+  const double* W[2] = {S + 6 * P2, S + 6 * P2 + 2 * tpl};
+  const double* V[2] = {S + 18 * P2, S + 18 * P2 + 2 * tpl};
+  double acc[LOC_PAIR_VALS] = {};
+  const int rows = LOC_CHUNK * r;
+  for (int e = threadIdx.x; e < rows; e += LOC_RED_THREADS) {
+    const int bp = c * LOC_CHUNK + e / r, ap = e % r;
+    const long long w = (long long)bp * 2 * r + ap;
+    double wr[2][2], wi[2][2], vr[2][2], vi[2][2];  // [s][s'] and [t][t']
+    for (int s = 0; s < 2; ++s)
+      for (int sp = 0; sp < 2; ++sp) {
+        wr[s][sp] = W[s][w + sp * r], wi[s][sp] = W[s][w + sp * r + tpl];
+        vr[s][sp] = V[s][w + sp * r], vi[s][sp] = V[s][w + sp * r + tpl];
+      }
+    int m = 4;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = a; b < 4; ++b) {
+        const int s = a >> 1, tt = a & 1, sp = b >> 1, tp = b & 1;
+        const double re = wr[s][sp] * vr[tt][tp] - wi[s][sp] * vi[tt][tp];
+        if (a == b) {
+          acc[a] += re;
+        } else {
+          acc[m] += re;
+          acc[m + 1] += wr[s][sp] * vi[tt][tp] + wi[s][sp] * vr[tt][tp];
+          m += 2;
+        }
+      }
+  }
+  for (int v = 0; v < LOC_PAIR_VALS; ++v) red[v][threadIdx.x] = acc[v];
+  __syncthreads();
+  for (int h = LOC_RED_THREADS / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h)
+      for (int v = 0; v < LOC_PAIR_VALS; ++v) red[v][threadIdx.x] += red[v][threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x < LOC_PAIR_VALS)
+    g.part2[(((long long)i * (n - 1) + k) * g.max_chunks + c) * LOC_PAIR_VALS + threadIdx.x] = red[threadIdx.x][0];
+}
+
 // L_0 = 1 and R_n = 1 (16 x 16, [0][0] = 1) of every state of the batch.
 __global__ __launch_bounds__(256) void qk_local_init_kernel(const LocArgs g, const int nb) {
   const int i = blockIdx.x;
   if (i >= nb) return;
   const long long P = g.pmax[i], P2 = P * P;
   double* const S = g.scratch + g.sbase[i];
-  double* const Rn = S + 14 * P2 + g.roff[(long long)i * (g.n_sites + 1) + g.n_sites];
+  double* const Rn = S + g.rmul * P2 + g.roff[(long long)i * (g.n_sites + 1) + g.n_sites];
   const int e = threadIdx.x;  // 256 = 16 x 16
   const double v = (e == 0) ? 1.0 : 0.0;
   S[e] = v, S[P2 + e] = 0.0;
@@ -223,7 +306,44 @@ __global__ __launch_bounds__(256) void qk_local_features_kernel(const LocArgs g,
   if (norms && k == 0) norms[st] = nrm;
 }
 
-// The PQK Gram: K[j][i] = exp(-g/2 sum_d (fx[i][d] - fy[j][d])^2), d = 3 n_sites.  A 64 x 64 tile per workgroup (4 x 4 entries per
+// Pauli correlators of neighbouring qubits: the chunk sums of each (state, pair) in a fixed order, then
+//     T[p][q] = sum_{s,t} rho[(s,t)][(s ^ f_p, t ^ f_q)] i^(e_p(s) + e_q(t)) / L_n[0][0]
+// -- a Pauli matrix has one entry per column: P_p[s ^ f_p][s] = i^e_p(s), f = (0, 1, 1, 0), e_I = e_X = (0, 0), e_Y = (1, 3),
+// e_Z = (0, 2); the imaginary parts cancel between (s, t) and its image, so only Re is summed.  T[0][0] is written as exactly 1.
+__global__ __launch_bounds__(256) void qk_local_pair_features_kernel(const LocArgs g, const int nb, double* out) {
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int n = g.n_sites, n1 = n + 1, np = n - 1;
+  if (id >= (long long)nb * np) return;
+  const int i = (int)(id / np), k = (int)(id % np);
+  const long long st = g.states[i];
+  const double nrm = g.scratch[g.sbase[i]];  // L_n[0][0]
+  const int chunks = g.dims[st * n1 + k + 1] / LOC_CHUNK;
+  const double* p = g.part2 + ((long long)i * np + k) * g.max_chunks * LOC_PAIR_VALS;
+  double v[LOC_PAIR_VALS] = {};
+  for (int c = 0; c < chunks; ++c)
+    for (int e = 0; e < LOC_PAIR_VALS; ++e) v[e] += p[LOC_PAIR_VALS * c + e];
+  double re[4][4], im[4][4];
+  int m = 4;
+  for (int a = 0; a < 4; ++a) {
+    re[a][a] = v[a], im[a][a] = 0.0;
+    for (int b = a + 1; b < 4; ++b, m += 2) re[a][b] = re[b][a] = v[m], im[a][b] = v[m + 1], im[b][a] = -v[m + 1];
+  }
+  double* f = out + (st * np + k) * 16;
+  for (int pp = 0; pp < 4; ++pp)
+    for (int q = 0; q < 4; ++q) {
+      const int fp = (pp == 1 || pp == 2), fq = (q == 1 || q == 2);
+      double acc = 0.0;
+      for (int s = 0; s < 2; ++s)
+        for (int t = 0; t < 2; ++t) {
+          const int ep = (pp == 2) ? 1 + 2 * s : (pp == 3) ? 2 * s : 0, eq = (q == 2) ? 1 + 2 * t : (q == 3) ? 2 * t : 0;
+          const int a = 2 * s + t, b = 2 * (s ^ fp) + (t ^ fq), e = (ep + eq) & 3;
+          acc += (e == 0) ? re[a][b] : (e == 1) ? -im[a][b] : (e == 2) ? -re[a][b] : im[a][b];
+        }
+      f[4 * pp + q] = (pp == 0 && q == 0) ? 1.0 : acc / nrm;
+    }
+}
+
+// The PQK Gram: K[j][i] = exp(-g/2 sum_d (fx[i][d] - fy[j][d])^2), d = 3 n_sites (pair form: -g/4, d = 16 (n_sites - 1)).  A 64 x 64 tile per workgroup (4 x 4 entries per
 // thread), features staged in LDS in 32-wide slices of d.  Each entry adds its d terms in ascending order into one accumulator: the
 // differences of (i, j) and (j, i) are negatives of each other, so a symmetric Gram is exactly symmetric and its diagonal exactly 1.
 constexpr int PG_T = 64, PG_D = 32;
@@ -262,16 +382,18 @@ __global__ __launch_bounds__(256) void qk_projected_gram_kernel(const double* fx
 inline int pad16h(int x) { return (x + 15) / 16 * 16; }
 inline long long blocks64(long long m, long long n) { return ((m + 63) / 64) * ((n + 63) / 64); }
 
-}  // namespace
-
-extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* out, double* norms) {
-  static const char* what = "qk_local_paulis_host";
-  if (!c || !set || !out) return qk_fail(QK_EINVAL, "%s: null argument", what);
+// The local sweep of a set.  out1 = Bloch vectors [n_states][n_sites][3] (may be NULL when out2 is given), norms (may be NULL);
+// out2 = Pauli correlators of neighbouring qubits [n_states][n_sites - 1][4][4] (NULL: the one-qubit sweep alone).
+int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* range, double* out1, double* norms, double* out2) {
+  const bool pair = out2 != nullptr;
+  if (!c || !set || (!out1 && !out2)) return qk_fail(QK_EINVAL, "%s: null argument", what);
   if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: the set belongs to another context", what);
   if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: complex64 sets are not supported; local Paulis need an fp64 set", what);
   const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
   if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: empty set", what);
-  QkRangeGuard range_("qk:local_paulis");
+  if (pair && n < 2) return qk_fail(QK_EINVAL, "%s: pairs of neighbouring qubits need n_sites >= 2 (got %d)", what, n);
+  QkRangeGuard range_(range);
+  const int rmul = pair ? LOC_RMUL_PAIR : LOC_RMUL;
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   std::vector<int64_t> offs((size_t)ns * n);
@@ -289,15 +411,17 @@ extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* ou
       if (k >= 1) rsum += 2ll * pad[(size_t)s * n1 + k] * pad[(size_t)s * n1 + k];
     }
     pmax[s] = p;
-    need[s] = 14ll * p * p + rsum;
+    need[s] = (long long)rmul * p * p + rsum;
   }
   const int max_chunks = set->max_pad / LOC_CHUNK;
-  const long long part_per_state = (long long)n * max_chunks * 4;
+  const long long part1_per_state = (long long)n * max_chunks * 4;
+  const long long part_per_state = part1_per_state + (pair ? (long long)(n - 1) * max_chunks * LOC_PAIR_VALS : 0);
   // memory bound of the per-state scratch: a quarter of what is free once the reversed image and the outputs exist
-  QkDevBuf rev, dout, dnorm;
+  QkDevBuf rev, dout, dnorm, dout2;
   HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
   HIP_TRY_AS(what, dout.alloc((size_t)ns * n * 3 * sizeof(double)));
   HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
+  if (pair) HIP_TRY_AS(what, dout2.alloc((size_t)ns * (n - 1) * 16 * sizeof(double)));
   size_t free_b = 0, total_b = 0;
   HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
   const long long budget = (long long)((free_b + c->local_scratch.bytes) / 4 / sizeof(double));
@@ -310,6 +434,16 @@ extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* ou
   }
   bstart.push_back(ns);
   const int n_rev = n - 1;  // reversed-chain steps: R_{n-1} .. R_1 (R_0 is not needed)
+  // the launches of a batch, in stream order: reversed T / X per step, then per site forward T / W, the pair sweep's T' / V of
+  // site k+1, rho (which also makes L_{k+1}) and the pair rho
+  std::vector<std::pair<int, int>> plan;  // (kind, step)
+  for (int j = 0; j < n_rev; ++j) plan.push_back({LOC_REV_T, j}), plan.push_back({LOC_REV_X, j});
+  for (int k = 0; k < n; ++k) {
+    plan.push_back({LOC_FWD_T, k}), plan.push_back({LOC_FWD_W, k});
+    if (pair && k + 1 < n) plan.push_back({LOC_PAIR_T, k}), plan.push_back({LOC_PAIR_V, k});
+    plan.push_back({LOC_RHO, k});
+    if (pair && k + 1 < n) plan.push_back({LOC_PAIR_RHO, k});
+  }
   std::vector<int2> tasks;
   std::vector<long long> first;  // per launch: first task
   for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
@@ -328,25 +462,25 @@ extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* ou
       }
       tot += need[s];
     }
-    // task lists of every launch of the batch, in launch order: reversed T / X per step, then forward T / W / rho per site
+    // task lists of every launch of the batch, in launch order
     tasks.clear(), first.clear();
-    auto add_launch = [&](auto blocks_of) {
+    for (const auto& [kind, step] : plan) {
       first.push_back((long long)tasks.size());
       for (int i = 0; i < nb; ++i) {
         const int* p = &pad[(size_t)(s0 + i) * n1];
-        const int nbk = blocks_of(p);
+        const int o = n - 1 - step, k = step;
+        int nbk = 0;
+        switch (kind) {
+          case LOC_REV_T: nbk = (int)blocks64(p[o + 1], 2ll * p[o]); break;
+          case LOC_REV_X: nbk = (int)blocks64(p[o], p[o]); break;
+          case LOC_FWD_T: nbk = (int)blocks64(p[k], 2ll * p[k + 1]); break;
+          case LOC_FWD_W: nbk = (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); break;
+          case LOC_PAIR_T: nbk = (int)blocks64(p[k + 2], 2ll * p[k + 1]); break;
+          case LOC_PAIR_V: nbk = (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); break;
+          default: nbk = p[k + 1] / LOC_CHUNK; break;  // LOC_RHO, LOC_PAIR_RHO
+        }
         for (int b = 0; b < nbk; ++b) tasks.push_back(int2{i, b});
       }
-    };
-    for (int j = 0; j < n_rev; ++j) {
-      const int o = n - 1 - j;
-      add_launch([&](const int* p) { return (int)blocks64(p[o + 1], 2ll * p[o]); });
-      add_launch([&](const int* p) { return (int)blocks64(p[o], p[o]); });
-    }
-    for (int k = 0; k < n; ++k) {
-      add_launch([&](const int* p) { return (int)blocks64(p[k], 2ll * p[k + 1]); });
-      add_launch([&](const int* p) { return (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); });
-      add_launch([&](const int* p) { return p[k + 1] / LOC_CHUNK; });
     }
     first.push_back((long long)tasks.size());
     // one device buffer for the batch: [tables | tasks | partials | per-state scratch]
@@ -377,48 +511,50 @@ extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* ou
     g.roff = reinterpret_cast<const int64_t*>(put(h_roff.data(), h_roff.size() * sizeof(int64_t), b_roff));
     const int2* d_tasks = reinterpret_cast<const int2*>(put(tasks.data(), tasks.size() * sizeof(int2), b_tasks));
     g.part = reinterpret_cast<double*>(base + b_tab);
+    g.part2 = g.part + (size_t)nb * part1_per_state;
     g.scratch = reinterpret_cast<double*>(base + b_tab + b_part);
+    g.rmul = rmul;
     g.n_sites = n;
     g.max_chunks = max_chunks;
     HIP_TRY_AS(what, hipMemcpyAsync(base, stage.data(), b_tab, hipMemcpyHostToDevice, c->stream));
     qk_local_reverse_kernel<<<dim3(nb, n), dim3(256), 0, c->stream>>>(g, rev.get<double>());
     qk_local_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, nb);
     HIP_TRY_AS(what, hipGetLastError());
-    size_t li = 0;
-    auto launch = [&](const int kind, const int step) {
+    for (size_t li = 0; li < plan.size(); ++li) {
+      const int kind = plan[li].first;
       g.tasks = d_tasks + first[li];
-      g.step = step;
+      g.step = plan[li].second;
       const long long grid = first[li + 1] - first[li];
-      ++li;
-      if (grid <= 0) return;
-      if (kind == LOC_REV_X || kind == LOC_FWD_W) qk_local_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
+      if (grid <= 0) continue;
+      if (kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V) qk_local_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
       else if (kind >= 0) qk_local_gemm_kernel<false><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
-      else qk_local_rho_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
-    };
-    for (int j = 0; j < n_rev; ++j) launch(LOC_REV_T, j), launch(LOC_REV_X, j);
-    for (int k = 0; k < n; ++k) launch(LOC_FWD_T, k), launch(LOC_FWD_W, k), launch(-1, k);
+      else if (kind == LOC_RHO) qk_local_rho_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
+      else qk_local_pair_rho_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
+    }
     HIP_TRY_AS(what, hipGetLastError());
     const long long nf = (long long)nb * n;
     qk_local_features_kernel<<<dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, dout.get<double>(), dnorm.get<double>());
+    if (pair) qk_local_pair_features_kernel<<<dim3((unsigned)(((long long)nb * (n - 1) + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, dout2.get<double>());
     HIP_TRY_AS(what, hipGetLastError());
     HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
   }
-  HIP_TRY_AS(what, hipMemcpy(out, dout.get(), (size_t)ns * n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (out1) HIP_TRY_AS(what, hipMemcpy(out1, dout.get(), (size_t)ns * n * 3 * sizeof(double), hipMemcpyDeviceToHost));
   if (norms) HIP_TRY_AS(what, hipMemcpy(norms, dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+  if (pair) HIP_TRY_AS(what, hipMemcpy(out2, dout2.get(), (size_t)ns * (n - 1) * 16 * sizeof(double), hipMemcpyDeviceToHost));
   return QK_OK;
 }
 
-extern "C" int qk_projected_gram_host(qk_ctx* c, int32_t n_sites, int32_t nx, const double* fx, int32_t ny, const double* fy, double g, double* out, int64_t ld) {
-  static const char* what = "qk_projected_gram_host";
+// The PQK Gram of host feature arrays [n][D]: out[j * ld + i] = exp(-factor sum_d (fx[i][d] - fy[j][d])^2).
+int projected_gram(qk_ctx* c, const char* what, const char* range, int32_t n_sites, int min_sites, int D, double factor, int32_t nx, const double* fx,
+                   int32_t ny, const double* fy, double g, double* out, int64_t ld) {
   if (!c || !fx || !out) return qk_fail(QK_EINVAL, "%s: null argument", what);
-  if (n_sites < 1) return qk_fail(QK_EINVAL, "%s: n_sites must be >= 1 (got %d)", what, n_sites);
+  if (n_sites < min_sites) return qk_fail(QK_EINVAL, "%s: n_sites must be >= %d (got %d)", what, min_sites, n_sites);
   if (nx < 1 || ny < 1) return qk_fail(QK_EINVAL, "%s: empty feature set (nx %d, ny %d)", what, nx, ny);
   if (!fy && ny != nx) return qk_fail(QK_EINVAL, "%s: Y is X (fy NULL) but ny %d != nx %d", what, ny, nx);
   if (!(g > 0.0) || !std::isfinite(g)) return qk_fail(QK_EINVAL, "%s: g must be > 0 and finite (got %g)", what, g);
   if (ld < nx) return qk_fail(QK_EINVAL, "%s: ld %lld is smaller than the %d columns", what, (long long)ld, nx);
-  QkRangeGuard range_("qk:projected_gram");
+  QkRangeGuard range_(range);
   HIP_TRY_AS(what, hipSetDevice(c->device));
-  const int D = 3 * n_sites;
   const size_t bx = (size_t)nx * D * sizeof(double), by = fy ? (size_t)ny * D * sizeof(double) : 0, bk = (size_t)ny * nx * sizeof(double);
   QkDevBuf buf;
   HIP_TRY_AS(what, buf.alloc(bx + by + bk));
@@ -427,9 +563,31 @@ extern "C" int qk_projected_gram_host(qk_ctx* c, int32_t n_sites, int32_t nx, co
   double* dk = dx + (size_t)nx * D + (fy ? (size_t)ny * D : 0);
   HIP_TRY_AS(what, hipMemcpyAsync(dx, fx, bx, hipMemcpyHostToDevice, c->stream));
   if (fy) HIP_TRY_AS(what, hipMemcpyAsync(dy, fy, by, hipMemcpyHostToDevice, c->stream));
-  qk_projected_gram_kernel<<<dim3((nx + PG_T - 1) / PG_T, (ny + PG_T - 1) / PG_T), dim3(256), 0, c->stream>>>(dx, nx, dy, ny, D, 0.5 * g, dk, nx);
+  qk_projected_gram_kernel<<<dim3((nx + PG_T - 1) / PG_T, (ny + PG_T - 1) / PG_T), dim3(256), 0, c->stream>>>(dx, nx, dy, ny, D, factor * g, dk, nx);
   HIP_TRY_AS(what, hipGetLastError());
   HIP_TRY_AS(what, hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), dk, (size_t)nx * sizeof(double), (size_t)nx * sizeof(double), (size_t)ny, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   return QK_OK;
+}
+
+}  // namespace
+
+extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* out, double* norms) {
+  static const char* what = "qk_local_paulis_host";
+  if (!out) return qk_fail(QK_EINVAL, "%s: null argument", what);
+  return local_sweep(c, set, what, "qk:local_paulis", out, norms, nullptr);
+}
+
+extern "C" int qk_local_pair_paulis_host(qk_ctx* c, const qk_mps_set* set, double* out2, double* out1, double* norms) {
+  static const char* what = "qk_local_pair_paulis_host";
+  if (!out2) return qk_fail(QK_EINVAL, "%s: null argument", what);
+  return local_sweep(c, set, what, "qk:local_pair_paulis", out1, norms, out2);
+}
+
+extern "C" int qk_projected_gram_host(qk_ctx* c, int32_t n_sites, int32_t nx, const double* fx, int32_t ny, const double* fy, double g, double* out, int64_t ld) {
+  return projected_gram(c, "qk_projected_gram_host", "qk:projected_gram", n_sites, 1, 3 * n_sites, 0.5, nx, fx, ny, fy, g, out, ld);
+}
+
+extern "C" int qk_projected_pair_gram_host(qk_ctx* c, int32_t n_sites, int32_t nx, const double* tx, int32_t ny, const double* ty, double g, double* out, int64_t ld) {
+  return projected_gram(c, "qk_projected_pair_gram_host", "qk:projected_pair_gram", n_sites, 2, 16 * (n_sites - 1), 0.25, nx, tx, ny, ty, g, out, ld);
 }

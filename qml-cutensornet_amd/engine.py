@@ -96,6 +96,8 @@ _SIGNATURES = [
     ("qk_get_stats", C.c_int, [_P, C.POINTER(QkStats)]),
     ("qk_local_paulis_host", C.c_int, [_P, _P, _P, _P]),
     ("qk_projected_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
+    ("qk_local_pair_paulis_host", C.c_int, [_P, _P, _P, _P, _P]),
+    ("qk_projected_pair_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
@@ -679,6 +681,39 @@ class Context:
         out = np.zeros((ny, nx), dtype=np.float64)
         _check(lib().qk_projected_gram_host(self._h, n, nx, fx.ctypes.data, ny, None if fy is None else fy.ctypes.data, g, out.ctypes.data, nx),
                "qk_projected_gram_host")
+        return out
+
+    def local_pair_paulis(self, mps_set: MpsSet, singles: bool = False, norms: bool = False):
+        """Pauli correlators of neighbouring qubits of every state of an fp64 set: T[state, k, p, q] = <P_p on qubit k, P_q on
+        qubit k+1>, P = (I, X, Y, Z), float64 of shape (n_states, n_sites - 1, 4, 4) -- the two-qubit reduced density matrix of the
+        pair is 1/4 sum T[p, q] P_p (x) P_q.  ``singles=True`` adds the Bloch vectors and ``norms=True`` <psi|psi>, both the bits
+        ``local_paulis`` returns: the result is ``T``, or the tuple ``(T[, F][, norms])``.  Synchronous."""
+        info = mps_set.info()
+        ns, n = info["n_states"], info["n_sites"]
+        T = np.zeros((ns, max(0, n - 1), 4, 4), dtype=np.float64)
+        F = np.zeros((ns, n, 3), dtype=np.float64) if singles else None
+        nrm = np.zeros(ns, dtype=np.float64) if norms else None
+        _check(lib().qk_local_pair_paulis_host(self._h, mps_set.handle, T.ctypes.data, None if F is None else F.ctypes.data,
+                                               None if nrm is None else nrm.ctypes.data), "qk_local_pair_paulis_host")
+        out = (T,) + ((F,) if singles else ()) + ((nrm,) if norms else ())
+        return out if len(out) > 1 else T
+
+    def projected_pair_gram(self, tx, ty=None, gamma=None) -> np.ndarray:
+        """Two-qubit projected quantum kernel K[j, i] = exp(-gamma/4 sum_k sum_pq (Tx[i, k, p, q] - Ty[j, k, p, q])^2) of Pauli
+        correlators (``local_pair_paulis``): shape (ny, nx), rows = Y (or X).  ``gamma=None`` means 1 / n_sites.  Synchronous."""
+        tx = np.ascontiguousarray(tx, dtype=np.float64)
+        if tx.ndim != 4 or tx.shape[1] < 1 or tx.shape[2:] != (4, 4):
+            raise ValueError(f"features must have shape (n_states, n_sites - 1, 4, 4), got {tx.shape}")
+        nx, n = tx.shape[0], tx.shape[1] + 1
+        g = projected_gamma(gamma, n)
+        if ty is not None:
+            ty = np.ascontiguousarray(ty, dtype=np.float64)
+            if ty.ndim != 4 or ty.shape[1:] != tx.shape[1:]:
+                raise ValueError(f"Y features of shape {ty.shape} do not match X features of shape {tx.shape}")
+        ny = nx if ty is None else ty.shape[0]
+        out = np.zeros((ny, nx), dtype=np.float64)
+        _check(lib().qk_projected_pair_gram_host(self._h, n, nx, tx.ctypes.data, ny, None if ty is None else ty.ctypes.data, g, out.ctypes.data, nx),
+               "qk_projected_pair_gram_host")
         return out
 
     def stats(self) -> dict:

@@ -390,7 +390,8 @@ def build_kernel_matrix(mpi_comm, ansatz, X, Y=None, info_file=None, truncation_
 
 
 def _gather_features(comm, lo, F, total):
-    """All-gather of every rank's (first index, Bloch vectors of its share) -> the (total, n, 3) array in data-set order."""
+    """All-gather of every rank's (first index, features of its share: Bloch vectors (m, n, 3) or neighbour-pair correlators
+    (m, n - 1, 4, 4)) -> the (total, ...) array in data-set order."""
     shares = comm_allgather(comm, (int(lo), np.ascontiguousarray(F, dtype=np.float64)))
     out = np.zeros((total,) + tuple(F.shape[1:]), dtype=np.float64)
     for s_lo, s_F in shares:
@@ -398,13 +399,22 @@ def _gather_features(comm, lo, F, total):
     return out
 
 
-def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30):
+def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30, rdm=1):
     """Projected quantum kernel (Huang et al., Nat. Commun. 12, 2631 (2021)) of the same states as ``build_kernel_matrix``:
         K[j, i] = exp(-g sum_k ||rho_k(X_i) - rho_k(Y_j)||_F^2) = exp(-g/2 sum_k |F(X_i)[k] - F(Y_j)[k]|^2),
     rho_k = the one-qubit reduced density matrix of qubit k, F[k] = its Bloch vector (<X_k>, <Y_k>, <Z_k>); ``Y=None`` means
     ``Y = X``, ``pqk_gamma=None`` means g = 1 / n_qubits.  Each rank builds its share of the states (the builder policy of
     ``build_kernel_matrix``), computes their Bloch vectors on its device and all-gathers them (3 n reals per state, never an
-    MPS); rank 0 computes K on its GPU and returns the ``len(Y) x len(X)`` matrix, the other ranks return ``None``."""
+    MPS); rank 0 computes K on its GPU and returns the ``len(Y) x len(X)`` matrix, the other ranks return ``None``.
+
+    ``rdm=2`` is the two-qubit form on neighbouring qubits, the first projected kernel that sees correlations between qubits:
+        K_2[j, i] = exp(-g sum_k ||rho_{k,k+1}(X_i) - rho_{k,k+1}(Y_j)||_F^2) = exp(-g/4 sum_k sum_pq (T(X_i)[k,p,q] - T(Y_j)[k,p,q])^2),
+    T[k, p, q] = <P_p on qubit k, P_q on qubit k+1>, P = (I, X, Y, Z), k = 0 .. n_qubits - 2: 16 (n - 1) reals per state are
+    all-gathered instead of 3 n.  It needs at least two qubits."""
+    if rdm not in (1, 2):
+        raise ValueError(f"rdm must be 1 (one-qubit reduced density matrices) or 2 (neighbouring pairs), got {rdm!r}")
+    if rdm == 2 and int(ansatz.num_qubits) < 2:
+        raise ValueError("rdm=2 compares reduced density matrices of neighbouring qubit pairs: the ansatz needs at least 2 qubits")
     if Y is not None and len(X) < len(Y):
         raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
     if truncation_error is None:
@@ -444,9 +454,9 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         ctx.trim()  # the device builder's arena goes back before the local sweep needs memory
         t0 = time.perf_counter()
         if local is None:
-            F, chi = np.zeros((0, n_qubits, 3), dtype=np.float64), np.zeros(0)
+            F, chi = np.zeros((0, n_qubits, 3) if rdm == 1 else (0, n_qubits - 1, 4, 4), dtype=np.float64), np.zeros(0)
         else:
-            F, chi = ctx.local_paulis(local), local.dims.max(axis=1)
+            F, chi = (ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local)), local.dims.max(axis=1)
             local.close()
         feat_secs += time.perf_counter() - t0
         shares.append((lo, F, len(points)))
@@ -461,7 +471,8 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     g = _engine.projected_gamma(pqk_gamma, n_qubits)
     _say(True, "\nFinished contracting all MPS.\n\nCalculating projected kernel matrix...")
     t0 = time.perf_counter()
-    kernel_mat = ctx.projected_gram(feats[0], None if Y is None else feats[1], g)
+    gram_of = ctx.projected_gram if rdm == 1 else ctx.projected_pair_gram
+    kernel_mat = gram_of(feats[0], None if Y is None else feats[1], g)
     tiles = time.perf_counter() - t0
 
     prof["r0_circ_gen"] = [0.0, "seconds"]
@@ -477,6 +488,7 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     prof["ave max chi y"] = (float(chi_y.mean()) if chi_y.size else 0.0, "chi y")
     prof["r0_RR_recv"] = [gather_secs, "seconds"]  # the all-gather of the Bloch vectors
     prof["pqk_gamma"] = [g, ""]
+    prof["pqk_rdm"] = [rdm, "qubits"]
     prof["pqk_features_time"] = [feat_secs, "seconds"]
     prof["kernel_mat_time"] = [tiles, "seconds"]
     prof["total_time"] = [time.perf_counter() - t_start, "seconds"]

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time the projected quantum kernel against the fidelity Gram on one MI355X, in one process: the config's states built by the
-device builder, then (each after a warm-up) ctx.gram(xs), ctx.local_paulis(xs) and ctx.projected_gram(F).  Prints one JSON line
-with the three times, the local sweep's algorithmic flops and its achieved TFLOP/s.
+device builder, then (each after a warm-up) ctx.gram(xs), ctx.local_paulis(xs), ctx.projected_gram(F) and the two-qubit form,
+ctx.local_pair_paulis(xs) and ctx.projected_pair_gram(T).  Prints one JSON line with the five times, the algorithmic flops of the
+two local sweeps and their achieved TFLOP/s.
 usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N]"""
 import argparse
 import json
@@ -25,6 +26,14 @@ def local_sweep_flops(dims):
     d = np.asarray(dims, dtype=np.float64)
     l, r = d[:, :-1], d[:, 1:]
     return float((8 * (l * 2 * r * l + r * 2 * l * r) + 8 * (l * l * 2 * r + 2 * r * 2 * r * l)).sum())
+
+
+def pair_sweep_flops(dims):
+    """The pair sweep adds, for every site but the first (l = chi_k, r = chi_k+1), a second T-shaped GEMM on the reversed image
+    (r x 2l over r) and the two V_t (l x 2l over r)."""
+    d = np.asarray(dims, dtype=np.float64)
+    l, r = d[:, 1:-1], d[:, 2:]
+    return local_sweep_flops(dims) + float((8 * (r * 2 * l * r) + 8 * (2 * l * 2 * l * r)).sum())
 
 
 def timed(fn, reps):
@@ -57,15 +66,20 @@ def main():
     K, gram_ms = timed(lambda: ctx.gram(xs), args.reps)
     F, local_ms = timed(lambda: ctx.local_paulis(xs), args.reps)
     KP, pgram_ms = timed(lambda: ctx.projected_gram(F), args.reps)
-    flops = local_sweep_flops(info["dims"])
+    T, pair_ms = timed(lambda: ctx.local_pair_paulis(xs), args.reps)
+    KP2, pgram2_ms = timed(lambda: ctx.projected_pair_gram(T), args.reps)
+    flops, flops2 = local_sweep_flops(info["dims"]), pair_sweep_flops(info["dims"])
     off = ~np.eye(npts, dtype=bool)
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
         "max_bond": int(info["dims"].max()), "build_s": round(build_s, 3),
         "gram_ms": round(gram_ms, 3), "local_paulis_ms": round(local_ms, 3), "projected_gram_ms": round(pgram_ms, 3),
-        "local_over_gram": round(local_ms / gram_ms, 4),
+        "local_pair_paulis_ms": round(pair_ms, 3), "projected_pair_gram_ms": round(pgram2_ms, 3),
+        "local_over_gram": round(local_ms / gram_ms, 4), "pair_over_local": round(pair_ms / local_ms, 4),
         "local_flops": flops, "local_tflops": round(flops / (local_ms * 1e-3) / 1e12, 3),
+        "pair_flops": flops2, "pair_tflops": round(flops2 / (pair_ms * 1e-3) / 1e12, 3),
         "median_offdiag_fidelity_K": float(np.median(K[off])), "median_offdiag_pqk": float(np.median(KP[off])),
+        "median_offdiag_pqk2": float(np.median(KP2[off])),
     }), flush=True)
     xs.close()
     ctx.close()
