@@ -324,6 +324,28 @@ int qk_local_pair_paulis_host(qk_ctx* ctx, const qk_mps_set* set, double* out2 /
 int qk_projected_pair_gram_host(qk_ctx* ctx, int32_t n_sites, int32_t nx, const double* tx /* [nx][n_sites-1][4][4] */,
                                 int32_t ny, const double* ty /* NULL: Y is X */, double g, double* out, int64_t ld);
 
+/* Pauli correlators of every pair of qubits up to distance max_dist = D, 1 <= D <= n_sites - 1: the pairs (k, k+d), d = 1 .. D,
+ * k = 0 .. n_sites - 1 - d, listed distance-major,
+ *     index(d, k) = sum_{e=1}^{d-1} (n_sites - e) + k,      n_pairs = D n_sites - D (D + 1) / 2
+ *     out2[state][index(d, k)][p][q] = <P_p on k, P_q on k+d>                    (out2[..][0][0] is exactly 1.0)
+ * with rho_{k,k+d} defined as rho_{k,k+1} above.  It is the neighbour sweep plus, per site, the four open left environments of each
+ * of the last D - 1 qubits carried one site further (two GEMM launches for all of them) and one more reduction launch.  The
+ * neighbour launches are untouched: out2[state][0 .. n_sites - 2] equals qk_local_pair_paulis_host's output bit for bit for every D,
+ * out1 and norms equal qk_local_paulis_host's, D = 1 is qk_local_pair_paulis_host, and every state's result is bit-identical
+ * whatever the rest of the set and from run to run.  QK_EINVAL when max_dist < 1 or max_dist > n_sites - 1; the other argument
+ * errors are qk_local_pair_paulis_host's.  Device scratch: 26 + 24 (D - 1) P^2 doubles per state (the window of D - 1 live qubits,
+ * 8 P^2 each, and the intermediates of their step, 16 P^2 each), counted by the batching rule and released by qk_ctx_trim.     */
+int qk_local_pair_paulis_dist_host(qk_ctx* ctx, const qk_mps_set* set, int32_t max_dist, double* out2 /* [n_states][n_pairs][4][4] */,
+                                   double* out1 /* [n_states][n_sites][3], may be NULL */, double* norms /* [n_states], may be NULL */);
+
+/* The two-qubit projected-kernel Gram over the pairs up to distance max_dist (host arrays [n][n_pairs][4][4]), synchronous:
+ *     out[j * ld + i] = exp(-g/4 * sum_pairs sum_{p,q} (tx[i][pair][p][q] - ty[j][pair][p][q])^2)
+ *                     = exp(-g sum_pairs ||rho_pair(x_i) - rho_pair(y_j)||_F^2)
+ * As qk_projected_pair_gram_host (max_dist = 1 is that call, bit for bit); QK_EINVAL also when max_dist < 1 or
+ * max_dist > n_sites - 1.                                                                                                     */
+int qk_projected_pair_gram_dist_host(qk_ctx* ctx, int32_t n_sites, int32_t max_dist, int32_t nx, const double* tx /* [nx][n_pairs][4][4] */,
+                                     int32_t ny, const double* ty /* NULL: Y is X */, double g, double* out, int64_t ld);
+
 /* ---- profiler ranges -----------------------------------------------------------------------------------------
  * roctx ranges (rocprofv3 --marker-trace) named "qk:build", "qk:upload", "qk:sweep", "qk:scatter", "qk:allgather_values",
  * "qk:allgather_sets" are opened by the library around its own phases -- the reference's MPI.Wtime() sites G:209-231

@@ -1,7 +1,8 @@
 // qk_local.hip -- per-qubit reduced density matrices of every state of a set (their Bloch vectors), the two-qubit reduced density
 // matrices of neighbouring qubits (their Pauli correlators) and the projected quantum kernel (PQK) Grams built from either.  Part of
-// libqkgram.so; entry points qk_local_paulis_host, qk_projected_gram_host, qk_local_pair_paulis_host and
-// qk_projected_pair_gram_host (include/qkgram.h).
+// libqkgram.so; entry points qk_local_paulis_host, qk_projected_gram_host, qk_local_pair_paulis_host,
+// qk_projected_pair_gram_host and their forms for pairs up to a chosen distance, qk_local_pair_paulis_dist_host and
+// qk_projected_pair_gram_dist_host (include/qkgram.h).
 //
 // Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
 // normalised):
@@ -38,6 +39,21 @@
 // (R_{k+1} = V_0[.][(0, .)] + V_1[.][(1, .)]).  V is made in the forward pass from the stored R_{k+2}, one site at a time: keeping
 // every V of the reverse pass would cost four times the R storage.  The reverse pass and the forward T / W / rho launches are the
 // one-qubit sweep's, in its order, so the Bloch vectors and norms of a pair call are the bits qk_local_paulis_host returns.
+//
+// Pairs up to distance D (qk_local_pair_paulis_dist_host): (k, k+d), d = 1 .. D, listed distance-major,
+//     index(d, k) = sum_{e=1}^{d-1} (n - e) + k,     n_pairs = D n - D (D + 1) / 2.
+// E_{o->k+1}[s][s'] = W_{o,s}[.][(s', .)] are the four open left environments of qubit o at bond o+1.  Carrying them across a
+// site k between the two qubits is the closed transfer step of L, the two GEMMs of the ring sweep:
+//     T''[a][(u, b')]          = sum_b E_{o->k}[s][s'][b][a] A_k[b][(u, b')]                 (LOC_DIST_T, the LOC_FWD_T shape)
+//     E_{o->k+1}[s][s'][b'][a'] = sum_{(a,u)} T''[(a, u)][b'] conj(A_k[(a, u)][a'])          (LOC_DIST_X: one product over K = 2 chi_k,
+//                                                                                          only the u = u' blocks exist)
+//     rho_{o,k+1}[(s,t)][(s',t')] = sum_{b', a'} E_{o->k+1}[s][s'][b'][a'] V_{k+1,t}[b'][(t', a')]
+// A state keeps a window of D - 1 slots in its scratch, origin o in slot o mod (D - 1), each in W's own layout, so the pair
+// reduction reads a slot exactly as it reads W.  At site k, after the neighbour launches: every live origin (k-D+1 .. k-1) goes
+// through site k in ONE T-shaped and ONE X-shaped launch (a task's block number also names the origin and (s, s')), then one
+// reduction launch makes rho_{o,k+1} of every live origin, then W_k is copied into the slot of the origin whose last distance was
+// just used.  The neighbour launches are untouched and come first: the distance-1 block, the Bloch vectors and the norms are the
+// bits of the neighbour call for every D, and D = 1 is the neighbour call.
 #include "qk_host.h"
 #include "qk_ring.h"
 
@@ -61,14 +77,21 @@ enum LocKind : int {
   LOC_FWD_W = 3,   // W_{k,s} = T_k[(., s)]^T conj(A_k), both s in one launch
   LOC_PAIR_T = 4,  // pair sweep, site o = k+1 of the reversed image: T' = R_{o+1}^T Ar_o
   LOC_PAIR_V = 5,  // pair sweep: V_{o,t} = T'[(., t)]^T conj(Ar_o), both t in one launch
+  LOC_DIST_T = 6,  // distant pairs, site k: T''_(o,s,s') = E_{o->k}[s][s']^T A_k for every live origin o, in one launch
+  LOC_DIST_X = 7,  // distant pairs: E_{o->k+1}[s][s'] = T''_(o,s,s')^T conj(A_k) over K = (a, u), back into the origin's slot
   LOC_RHO = -1,    // qk_local_rho_kernel
-  LOC_PAIR_RHO = -2,  // qk_local_pair_rho_kernel
+  LOC_PAIR_RHO = -2,  // qk_local_pair_rho_kernel<false>
+  LOC_DIST_RHO = -3,  // qk_local_pair_rho_kernel<true>: rho_{o,k+1} of every live origin from its window slot
+  LOC_ADMIT = -4,  // qk_local_admit_kernel: W_k into the window
 };
 
 // Per-state scratch (doubles, every matrix as a re plane then an im plane), P = the state's largest padded bond:
 //   L [P x P] at 0 | T [P x 2P] at 2P^2 | W_0 [P x 2P] at 6P^2 | W_1 at 10P^2 | R_1 .. R_n at rmul P^2 + roff[k] (pad_k^2 per plane)
-// rmul = 14 for the one-qubit sweep; the pair sweep has T' at 14P^2, V_0 at 18P^2, V_1 at 22P^2 and rmul = 26.
-constexpr int LOC_RMUL = 14, LOC_RMUL_PAIR = 26;
+// rmul = 14 for the one-qubit sweep; the pair sweep has T' at 14P^2, V_0 at 18P^2, V_1 at 22P^2 and rmul = 26.  Pairs up to
+// distance D add, between V_1 and the R_k, the window -- D - 1 slots of 8P^2, slot e at (26 + 8e)P^2 holding (W_0 | W_1) of its
+// origin carried to the current bond -- and the 4 (D - 1) intermediates T'' of 4P^2 at (26 + 8(D-1) + 4w)P^2,
+// w = 4 (k - 1 - o) + 2s + s': rmul = 26 + 24 (D - 1).
+constexpr int LOC_RMUL = 14, LOC_RMUL_PAIR = 26, LOC_RMUL_DIST = 24;
 constexpr int LOC_PAIR_VALS = 16;                                   // reals of a Hermitian 4 x 4 matrix
 struct LocArgs {
   const double* data;     // the set's planes
@@ -83,8 +106,10 @@ struct LocArgs {
   const int2* tasks;      // this launch: (batch entry, block)
   double* scratch;
   double* part;           // rho partial sums [batch][n_sites][max chunks][4]
-  double* part2;          // pair sweep: rho_{k,k+1} partial sums [batch][n_sites - 1][max chunks][16]
+  double* part2;          // pair sweep: rho_{k,k+d} partial sums [batch][n_pairs][max chunks][16], pairs in index(d, k) order
   int rmul;
+  int max_dist;           // D of the pair sweep (1: neighbours only)
+  int n_pairs;
   int n_sites;
   int max_chunks;
   int step;               // reversed-chain step j (LOC_REV_*) or site k (forward, LOC_PAIR_*: the pair (k, k+1))
@@ -96,12 +121,13 @@ __device__ __forceinline__ long long uni64(const long long v) {
   return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
-// One 64 x 64 output block of one state's GEMM of this step.  CONJB: the LOC_REV_X / LOC_FWD_W / LOC_PAIR_V products (conjugated site tensor).
+// One 64 x 64 output block of one state's GEMM of this step.  CONJB: the LOC_REV_X / LOC_FWD_W / LOC_PAIR_V / LOC_DIST_X products (conjugated site tensor).
 template <bool CONJB>
 __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, const int kind) {
   __shared__ __attribute__((aligned(16))) double lds[LOC_LDS_DOUBLES];
   const int2 t = g.tasks[blockIdx.x];
-  const int i = __builtin_amdgcn_readfirstlane(t.x), blk = __builtin_amdgcn_readfirstlane(t.y);
+  const int i = __builtin_amdgcn_readfirstlane(t.x);
+  int blk = __builtin_amdgcn_readfirstlane(t.y);
   const int n = g.n_sites, n1 = n + 1;
   const long long st = __builtin_amdgcn_readfirstlane(g.states[i]);
   const int* pd = g.dims + st * n1;
@@ -143,7 +169,23 @@ __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, con
     const int lt = __builtin_amdgcn_readfirstlane(td[k]);
     Bre = g.data + uni64(g.offs[st * n + k]);
     Bim = Bre + (long long)l * 2 * r;
-    if (kind == LOC_FWD_T) {
+    if (kind == LOC_DIST_T || kind == LOC_DIST_X) {
+      // block number = (w, block of the product), w = 4 (k - 1 - o) + 2s + s' for the live origin o
+      const int per = (kind == LOC_DIST_T) ? ((l + 63) / 64) * ((2 * r + 63) / 64) : ((r + 63) / 64) * ((r + 63) / 64);
+      const int w = blk / per, o = k - 1 - (w >> 2), s = (w >> 1) & 1, sp = w & 1;
+      double* const E = S + (LOC_RMUL_PAIR + 8 * (o % (g.max_dist - 1))) * P2 + s * 2 * tpl;  // E[s][.][(s', .)] of origin o
+      double* const Tw = S + (LOC_RMUL_PAIR + 8 * (g.max_dist - 1) + 4 * w) * P2;
+      blk -= w * per;
+      if (kind == LOC_DIST_T) {
+        Are = E + sp * l, Aim = Are + tpl;
+        Cre = Tw, Cim = Tw + tpl;
+        lda = 2 * l, ldb = 2 * r, ldc = 2 * r, M = l, N = 2 * r, K = lt;
+      } else {
+        Are = Tw, Aim = Tw + tpl;
+        Cre = E + sp * r, Cim = Cre + tpl;
+        lda = r, ldb = r, ldc = 2 * r, M = r, N = r, K = 2 * lt;
+      }
+    } else if (kind == LOC_FWD_T) {
       Are = S, Aim = S + P2;
       Cre = Tre, Cim = Tre + tpl;
       lda = l, ldb = 2 * r, ldc = 2 * r, M = l, N = 2 * r, K = lt;
@@ -210,16 +252,22 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_rho_kernel(const Loc
 // LDS: red[16][256] doubles = 32 KiB, five workgroups (20 waves) per CU -- the kernel waits on its 16 global loads per element,
 // not on occupancy.  Every access is red[v][thread]: the 32 lanes that a ds_read_b64 / ds_write_b64 serves together touch 32
 // consecutive doubles, each of the 64 banks once, so the layout is conflict-free like the 4-value one of qk_local_rho_kernel.
+// DIST: the pairs (o, k+1) of the live origins o = k-1, k-2, ..: a task is (batch entry, (k - 1 - o) chunks + chunk) and the left
+// operand is the origin's window slot, which has W's layout; the LDS layout, the accesses and the tree are the same, so the
+// argument above holds for both forms.
+template <bool DIST>
 __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_pair_rho_kernel(const LocArgs g) {
   __shared__ double red[LOC_PAIR_VALS][LOC_RED_THREADS];
   const int2 t = g.tasks[blockIdx.x];
-  const int i = t.x, c = t.y;
+  const int i = t.x;
   const int n = g.n_sites, n1 = n + 1, k = g.step;
   const long long st = g.states[i];
   const int r = g.dims[st * n1 + k + 1];
+  const int age = DIST ? t.y / (r / LOC_CHUNK) : 0, c = t.y - age * (r / LOC_CHUNK);
   const long long P = g.pmax[i], P2 = P * P, tpl = 2 * P2;
   const double* const S = g.scratch + g.sbase[i];
-  const double* W[2] = {S + 6 * P2, S + 6 * P2 + 2 * tpl};
+  const double* const W0 = DIST ? S + (LOC_RMUL_PAIR + 8 * ((k - 1 - age) % (g.max_dist - 1))) * P2 : S + 6 * P2;
+  const double* W[2] = {W0, W0 + 2 * tpl};
   const double* V[2] = {S + 18 * P2, S + 18 * P2 + 2 * tpl};
   double acc[LOC_PAIR_VALS] = {};
   const int rows = LOC_CHUNK * r;
@@ -255,8 +303,28 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_pair_rho_kernel(cons
       for (int v = 0; v < LOC_PAIR_VALS; ++v) red[v][threadIdx.x] += red[v][threadIdx.x + h];
     __syncthreads();
   }
+  // pair (k, k+1) is index k; pair (o, k+1) at distance d = age + 2 is index (d - 1) n - (d - 1) d / 2 + o
+  const long long pi = DIST ? (long long)(age + 1) * n - (age + 1) * (age + 2) / 2 + (k - 1 - age) : k;
   if (threadIdx.x < LOC_PAIR_VALS)
-    g.part2[(((long long)i * (n - 1) + k) * g.max_chunks + c) * LOC_PAIR_VALS + threadIdx.x] = red[threadIdx.x][0];
+    g.part2[(((long long)i * g.n_pairs + pi) * g.max_chunks + c) * LOC_PAIR_VALS + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// W_k = (W_0 | W_1) of site k, rows b' of one 16-row chunk, into window slot k mod (D - 1): the new origin of the distant pairs.
+// Both have the same layout, so it is a plain copy of the rows' 2 pad(b') columns in the four planes.
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_admit_kernel(const LocArgs g) {
+  const int2 t = g.tasks[blockIdx.x];
+  const int i = t.x, c = t.y;
+  const int n1 = g.n_sites + 1, k = g.step;
+  const long long st = g.states[i];
+  const int r = g.dims[st * n1 + k + 1];
+  const long long P = g.pmax[i], P2 = P * P;
+  double* const S = g.scratch + g.sbase[i];
+  const double* const W = S + 6 * P2;
+  double* const E = S + (LOC_RMUL_PAIR + 8 * (k % (g.max_dist - 1))) * P2;
+  const long long row0 = (long long)c * LOC_CHUNK * 2 * r;
+  const int cnt = LOC_CHUNK * 2 * r;
+  for (int e = threadIdx.x; e < cnt; e += LOC_RED_THREADS)
+    for (int pl = 0; pl < 4; ++pl) E[pl * 2 * P2 + row0 + e] = W[pl * 2 * P2 + row0 + e];
 }
 
 // L_0 = 1 and R_n = 1 (16 x 16, [0][0] = 1) of every state of the batch.
@@ -306,18 +374,20 @@ __global__ __launch_bounds__(256) void qk_local_features_kernel(const LocArgs g,
   if (norms && k == 0) norms[st] = nrm;
 }
 
-// Pauli correlators of neighbouring qubits: the chunk sums of each (state, pair) in a fixed order, then
+// Pauli correlators of the pairs (neighbours, or every pair up to distance D): the chunk sums of each (state, pair) in a fixed order, then
 //     T[p][q] = sum_{s,t} rho[(s,t)][(s ^ f_p, t ^ f_q)] i^(e_p(s) + e_q(t)) / L_n[0][0]
 // -- a Pauli matrix has one entry per column: P_p[s ^ f_p][s] = i^e_p(s), f = (0, 1, 1, 0), e_I = e_X = (0, 0), e_Y = (1, 3),
 // e_Z = (0, 2); the imaginary parts cancel between (s, t) and its image, so only Re is summed.  T[0][0] is written as exactly 1.
 __global__ __launch_bounds__(256) void qk_local_pair_features_kernel(const LocArgs g, const int nb, double* out) {
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int n = g.n_sites, n1 = n + 1, np = n - 1;
+  const int n = g.n_sites, n1 = n + 1, np = g.n_pairs;
   if (id >= (long long)nb * np) return;
-  const int i = (int)(id / np), k = (int)(id % np);
+  const int i = (int)(id / np), k = (int)(id % np);  // k = index(d, o) of the pair (o, o + d)
   const long long st = g.states[i];
   const double nrm = g.scratch[g.sbase[i]];  // L_n[0][0]
-  const int chunks = g.dims[st * n1 + k + 1] / LOC_CHUNK;
+  int second = k + 1;  // the pair's second qubit: its partial sums are over the chunks of that qubit's left bond
+  for (int d = 1; second > n - 1; ++d) second -= n - d - 1;
+  const int chunks = g.dims[st * n1 + second] / LOC_CHUNK;
   const double* p = g.part2 + ((long long)i * np + k) * g.max_chunks * LOC_PAIR_VALS;
   double v[LOC_PAIR_VALS] = {};
   for (int c = 0; c < chunks; ++c)
@@ -383,8 +453,8 @@ inline int pad16h(int x) { return (x + 15) / 16 * 16; }
 inline long long blocks64(long long m, long long n) { return ((m + 63) / 64) * ((n + 63) / 64); }
 
 // The local sweep of a set.  out1 = Bloch vectors [n_states][n_sites][3] (may be NULL when out2 is given), norms (may be NULL);
-// out2 = Pauli correlators of neighbouring qubits [n_states][n_sites - 1][4][4] (NULL: the one-qubit sweep alone).
-int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* range, double* out1, double* norms, double* out2) {
+// out2 = Pauli correlators of the pairs up to distance max_dist [n_states][n_pairs][4][4] (NULL: the one-qubit sweep alone).
+int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* range, double* out1, double* norms, double* out2, const int max_dist) {
   const bool pair = out2 != nullptr;
   if (!c || !set || (!out1 && !out2)) return qk_fail(QK_EINVAL, "%s: null argument", what);
   if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: the set belongs to another context", what);
@@ -392,8 +462,11 @@ int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* 
   const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
   if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: empty set", what);
   if (pair && n < 2) return qk_fail(QK_EINVAL, "%s: pairs of neighbouring qubits need n_sites >= 2 (got %d)", what, n);
+  if (pair && (max_dist < 1 || max_dist > n - 1)) return qk_fail(QK_EINVAL, "%s: max_dist must be in 1 .. n_sites - 1 = %d (got %d)", what, n - 1, max_dist);
   QkRangeGuard range_(range);
-  const int rmul = pair ? LOC_RMUL_PAIR : LOC_RMUL;
+  const int D = pair ? max_dist : 1;
+  const int n_pairs = pair ? D * n - D * (D + 1) / 2 : 0;
+  const int rmul = pair ? LOC_RMUL_PAIR + LOC_RMUL_DIST * (D - 1) : LOC_RMUL;  // the window and its intermediates count in need[s]
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   std::vector<int64_t> offs((size_t)ns * n);
@@ -415,13 +488,13 @@ int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* 
   }
   const int max_chunks = set->max_pad / LOC_CHUNK;
   const long long part1_per_state = (long long)n * max_chunks * 4;
-  const long long part_per_state = part1_per_state + (pair ? (long long)(n - 1) * max_chunks * LOC_PAIR_VALS : 0);
+  const long long part_per_state = part1_per_state + (long long)n_pairs * max_chunks * LOC_PAIR_VALS;
   // memory bound of the per-state scratch: a quarter of what is free once the reversed image and the outputs exist
   QkDevBuf rev, dout, dnorm, dout2;
   HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
   HIP_TRY_AS(what, dout.alloc((size_t)ns * n * 3 * sizeof(double)));
   HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
-  if (pair) HIP_TRY_AS(what, dout2.alloc((size_t)ns * (n - 1) * 16 * sizeof(double)));
+  if (pair) HIP_TRY_AS(what, dout2.alloc((size_t)ns * n_pairs * 16 * sizeof(double)));
   size_t free_b = 0, total_b = 0;
   HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
   const long long budget = (long long)((free_b + c->local_scratch.bytes) / 4 / sizeof(double));
@@ -435,7 +508,8 @@ int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* 
   bstart.push_back(ns);
   const int n_rev = n - 1;  // reversed-chain steps: R_{n-1} .. R_1 (R_0 is not needed)
   // the launches of a batch, in stream order: reversed T / X per step, then per site forward T / W, the pair sweep's T' / V of
-  // site k+1, rho (which also makes L_{k+1}) and the pair rho
+  // site k+1, rho (which also makes L_{k+1}) and the pair rho; with D > 1 then the live origins k-D+1 .. k-1 through site k, their
+  // rho_{o,k+1}, and W_k into the window for the sites after k+1
   std::vector<std::pair<int, int>> plan;  // (kind, step)
   for (int j = 0; j < n_rev; ++j) plan.push_back({LOC_REV_T, j}), plan.push_back({LOC_REV_X, j});
   for (int k = 0; k < n; ++k) {
@@ -443,6 +517,8 @@ int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* 
     if (pair && k + 1 < n) plan.push_back({LOC_PAIR_T, k}), plan.push_back({LOC_PAIR_V, k});
     plan.push_back({LOC_RHO, k});
     if (pair && k + 1 < n) plan.push_back({LOC_PAIR_RHO, k});
+    if (D > 1 && k >= 1 && k + 1 < n) plan.push_back({LOC_DIST_T, k}), plan.push_back({LOC_DIST_X, k}), plan.push_back({LOC_DIST_RHO, k});
+    if (D > 1 && k + 2 < n) plan.push_back({LOC_ADMIT, k});
   }
   std::vector<int2> tasks;
   std::vector<long long> first;  // per launch: first task
@@ -469,6 +545,7 @@ int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* 
       for (int i = 0; i < nb; ++i) {
         const int* p = &pad[(size_t)(s0 + i) * n1];
         const int o = n - 1 - step, k = step;
+        const int live = std::min(k, D - 1);  // origins in the window at site k
         int nbk = 0;
         switch (kind) {
           case LOC_REV_T: nbk = (int)blocks64(p[o + 1], 2ll * p[o]); break;
@@ -477,7 +554,10 @@ int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* 
           case LOC_FWD_W: nbk = (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); break;
           case LOC_PAIR_T: nbk = (int)blocks64(p[k + 2], 2ll * p[k + 1]); break;
           case LOC_PAIR_V: nbk = (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); break;
-          default: nbk = p[k + 1] / LOC_CHUNK; break;  // LOC_RHO, LOC_PAIR_RHO
+          case LOC_DIST_T: nbk = (int)(4 * live * blocks64(p[k], 2ll * p[k + 1])); break;
+          case LOC_DIST_X: nbk = (int)(4 * live * blocks64(p[k + 1], p[k + 1])); break;
+          case LOC_DIST_RHO: nbk = live * (p[k + 1] / LOC_CHUNK); break;
+          default: nbk = p[k + 1] / LOC_CHUNK; break;  // LOC_RHO, LOC_PAIR_RHO, LOC_ADMIT
         }
         for (int b = 0; b < nbk; ++b) tasks.push_back(int2{i, b});
       }
@@ -514,6 +594,8 @@ int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* 
     g.part2 = g.part + (size_t)nb * part1_per_state;
     g.scratch = reinterpret_cast<double*>(base + b_tab + b_part);
     g.rmul = rmul;
+    g.max_dist = D;
+    g.n_pairs = n_pairs;
     g.n_sites = n;
     g.max_chunks = max_chunks;
     HIP_TRY_AS(what, hipMemcpyAsync(base, stage.data(), b_tab, hipMemcpyHostToDevice, c->stream));
@@ -526,21 +608,23 @@ int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* 
       g.step = plan[li].second;
       const long long grid = first[li + 1] - first[li];
       if (grid <= 0) continue;
-      if (kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V) qk_local_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
+      if (kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V || kind == LOC_DIST_X) qk_local_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
       else if (kind >= 0) qk_local_gemm_kernel<false><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
       else if (kind == LOC_RHO) qk_local_rho_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
-      else qk_local_pair_rho_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
+      else if (kind == LOC_PAIR_RHO) qk_local_pair_rho_kernel<false><<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
+      else if (kind == LOC_DIST_RHO) qk_local_pair_rho_kernel<true><<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
+      else qk_local_admit_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
     }
     HIP_TRY_AS(what, hipGetLastError());
     const long long nf = (long long)nb * n;
     qk_local_features_kernel<<<dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, dout.get<double>(), dnorm.get<double>());
-    if (pair) qk_local_pair_features_kernel<<<dim3((unsigned)(((long long)nb * (n - 1) + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, dout2.get<double>());
+    if (pair) qk_local_pair_features_kernel<<<dim3((unsigned)(((long long)nb * n_pairs + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, dout2.get<double>());
     HIP_TRY_AS(what, hipGetLastError());
     HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
   }
   if (out1) HIP_TRY_AS(what, hipMemcpy(out1, dout.get(), (size_t)ns * n * 3 * sizeof(double), hipMemcpyDeviceToHost));
   if (norms) HIP_TRY_AS(what, hipMemcpy(norms, dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
-  if (pair) HIP_TRY_AS(what, hipMemcpy(out2, dout2.get(), (size_t)ns * (n - 1) * 16 * sizeof(double), hipMemcpyDeviceToHost));
+  if (pair) HIP_TRY_AS(what, hipMemcpy(out2, dout2.get(), (size_t)ns * n_pairs * 16 * sizeof(double), hipMemcpyDeviceToHost));
   return QK_OK;
 }
 
@@ -575,13 +659,19 @@ int projected_gram(qk_ctx* c, const char* what, const char* range, int32_t n_sit
 extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* out, double* norms) {
   static const char* what = "qk_local_paulis_host";
   if (!out) return qk_fail(QK_EINVAL, "%s: null argument", what);
-  return local_sweep(c, set, what, "qk:local_paulis", out, norms, nullptr);
+  return local_sweep(c, set, what, "qk:local_paulis", out, norms, nullptr, 1);
 }
 
 extern "C" int qk_local_pair_paulis_host(qk_ctx* c, const qk_mps_set* set, double* out2, double* out1, double* norms) {
   static const char* what = "qk_local_pair_paulis_host";
   if (!out2) return qk_fail(QK_EINVAL, "%s: null argument", what);
-  return local_sweep(c, set, what, "qk:local_pair_paulis", out1, norms, out2);
+  return local_sweep(c, set, what, "qk:local_pair_paulis", out1, norms, out2, 1);
+}
+
+extern "C" int qk_local_pair_paulis_dist_host(qk_ctx* c, const qk_mps_set* set, int32_t max_dist, double* out2, double* out1, double* norms) {
+  static const char* what = "qk_local_pair_paulis_dist_host";
+  if (!out2) return qk_fail(QK_EINVAL, "%s: null argument", what);
+  return local_sweep(c, set, what, "qk:local_pair_paulis_dist", out1, norms, out2, max_dist);
 }
 
 extern "C" int qk_projected_gram_host(qk_ctx* c, int32_t n_sites, int32_t nx, const double* fx, int32_t ny, const double* fy, double g, double* out, int64_t ld) {
@@ -590,4 +680,13 @@ extern "C" int qk_projected_gram_host(qk_ctx* c, int32_t n_sites, int32_t nx, co
 
 extern "C" int qk_projected_pair_gram_host(qk_ctx* c, int32_t n_sites, int32_t nx, const double* tx, int32_t ny, const double* ty, double g, double* out, int64_t ld) {
   return projected_gram(c, "qk_projected_pair_gram_host", "qk:projected_pair_gram", n_sites, 2, 16 * (n_sites - 1), 0.25, nx, tx, ny, ty, g, out, ld);
+}
+
+extern "C" int qk_projected_pair_gram_dist_host(qk_ctx* c, int32_t n_sites, int32_t max_dist, int32_t nx, const double* tx, int32_t ny, const double* ty, double g, double* out,
+                                                int64_t ld) {
+  static const char* what = "qk_projected_pair_gram_dist_host";
+  if (n_sites >= 2 && (max_dist < 1 || max_dist > n_sites - 1))
+    return qk_fail(QK_EINVAL, "%s: max_dist must be in 1 .. n_sites - 1 = %d (got %d)", what, n_sites - 1, max_dist);
+  const int n_pairs = n_sites >= 2 ? max_dist * n_sites - max_dist * (max_dist + 1) / 2 : 0;
+  return projected_gram(c, what, "qk:projected_pair_gram_dist", n_sites, 2, 16 * n_pairs, 0.25, nx, tx, ny, ty, g, out, ld);
 }

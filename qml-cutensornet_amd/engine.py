@@ -98,6 +98,8 @@ _SIGNATURES = [
     ("qk_projected_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_local_pair_paulis_host", C.c_int, [_P, _P, _P, _P, _P]),
     ("qk_projected_pair_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
+    ("qk_local_pair_paulis_dist_host", C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
+    ("qk_projected_pair_gram_dist_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
@@ -202,6 +204,25 @@ def projected_gamma(gamma, n_sites: int) -> float:
     if not (g > 0.0 and np.isfinite(g)):
         raise ValueError(f"the projected-kernel bandwidth must be > 0 and finite (got {gamma!r})")
     return g
+
+
+def pair_table(n_sites: int, max_dist: int = 1) -> np.ndarray:
+    """The qubit pairs of the two-qubit projected kernel, in the order of ``local_pair_paulis(max_dist=...)``: an int array
+    (n_pairs, 2) of (k, k + d), d = 1 .. max_dist, k = 0 .. n_sites - 1 - d, distance-major (row ``sum_{e<d} (n_sites - e) + k``);
+    n_pairs = D n - D (D + 1) / 2.  For an entanglement map, ``max_dist = max(abs(a - b) for a, b in pairs)``."""
+    n, D = int(n_sites), int(max_dist)
+    if n < 2 or not 1 <= D <= n - 1:
+        raise ValueError(f"max_dist must be in 1 .. n_sites - 1 (got n_sites {n_sites!r}, max_dist {max_dist!r})")
+    return np.array([(k, k + d) for d in range(1, D + 1) for k in range(n - d)], dtype=np.int64)
+
+
+def _pair_sites(n_pairs: int, max_dist: int):
+    """n_sites of a feature array with ``n_pairs`` pairs up to distance ``max_dist``, or None if no chain fits."""
+    D = int(max_dist)
+    if D < 1:
+        return None
+    n, rem = divmod(int(n_pairs) + D * (D + 1) // 2, D)
+    return n if rem == 0 and n >= D + 1 else None
 
 
 def _dims_table(states) -> np.ndarray:
@@ -683,37 +704,56 @@ class Context:
                "qk_projected_gram_host")
         return out
 
-    def local_pair_paulis(self, mps_set: MpsSet, singles: bool = False, norms: bool = False):
+    def local_pair_paulis(self, mps_set: MpsSet, singles: bool = False, norms: bool = False, max_dist: int = 1):
         """Pauli correlators of neighbouring qubits of every state of an fp64 set: T[state, k, p, q] = <P_p on qubit k, P_q on
         qubit k+1>, P = (I, X, Y, Z), float64 of shape (n_states, n_sites - 1, 4, 4) -- the two-qubit reduced density matrix of the
         pair is 1/4 sum T[p, q] P_p (x) P_q.  ``singles=True`` adds the Bloch vectors and ``norms=True`` <psi|psi>, both the bits
-        ``local_paulis`` returns: the result is ``T``, or the tuple ``(T[, F][, norms])``.  Synchronous."""
+        ``local_paulis`` returns: the result is ``T``, or the tuple ``(T[, F][, norms])``.  Synchronous.
+
+        ``max_dist=D`` (1 <= D <= n_sites - 1) takes every pair (k, k+d), d = 1 .. D, in the order of ``pair_table(n_sites, D)``:
+        T has shape (n_states, n_pairs, 4, 4), and its first n_sites - 1 rows are the bits of ``max_dist=1``."""
         info = mps_set.info()
         ns, n = info["n_states"], info["n_sites"]
-        T = np.zeros((ns, max(0, n - 1), 4, 4), dtype=np.float64)
+        D = int(max_dist)
+        n_pairs = D * n - D * (D + 1) // 2 if 1 <= D <= n - 1 else max(0, n - 1)  # (the library rejects a bad max_dist)
+        T = np.zeros((ns, n_pairs, 4, 4), dtype=np.float64)
         F = np.zeros((ns, n, 3), dtype=np.float64) if singles else None
         nrm = np.zeros(ns, dtype=np.float64) if norms else None
-        _check(lib().qk_local_pair_paulis_host(self._h, mps_set.handle, T.ctypes.data, None if F is None else F.ctypes.data,
-                                               None if nrm is None else nrm.ctypes.data), "qk_local_pair_paulis_host")
+        if D == 1:
+            _check(lib().qk_local_pair_paulis_host(self._h, mps_set.handle, T.ctypes.data, None if F is None else F.ctypes.data,
+                                                   None if nrm is None else nrm.ctypes.data), "qk_local_pair_paulis_host")
+        else:
+            _check(lib().qk_local_pair_paulis_dist_host(self._h, mps_set.handle, D, T.ctypes.data, None if F is None else F.ctypes.data,
+                                                        None if nrm is None else nrm.ctypes.data), "qk_local_pair_paulis_dist_host")
         out = (T,) + ((F,) if singles else ()) + ((nrm,) if norms else ())
         return out if len(out) > 1 else T
 
-    def projected_pair_gram(self, tx, ty=None, gamma=None) -> np.ndarray:
+    def projected_pair_gram(self, tx, ty=None, gamma=None, max_dist: int = 1) -> np.ndarray:
         """Two-qubit projected quantum kernel K[j, i] = exp(-gamma/4 sum_k sum_pq (Tx[i, k, p, q] - Ty[j, k, p, q])^2) of Pauli
-        correlators (``local_pair_paulis``): shape (ny, nx), rows = Y (or X).  ``gamma=None`` means 1 / n_sites.  Synchronous."""
+        correlators (``local_pair_paulis``): shape (ny, nx), rows = Y (or X).  ``gamma=None`` means 1 / n_sites.  Synchronous.
+
+        ``max_dist=D`` is the kernel over the pairs up to distance D (features of ``local_pair_paulis(max_dist=D)``): n_sites is
+        inferred from n_pairs = D n - D (D + 1) / 2, and ``gamma=None`` means 1 / (n_sites D)."""
         tx = np.ascontiguousarray(tx, dtype=np.float64)
         if tx.ndim != 4 or tx.shape[1] < 1 or tx.shape[2:] != (4, 4):
             raise ValueError(f"features must have shape (n_states, n_sites - 1, 4, 4), got {tx.shape}")
-        nx, n = tx.shape[0], tx.shape[1] + 1
-        g = projected_gamma(gamma, n)
+        D = int(max_dist)
+        nx, n = tx.shape[0], _pair_sites(tx.shape[1], D)
+        if n is None:
+            raise ValueError(f"features of shape {tx.shape} are not (n_states, n_pairs, 4, 4) of any chain with pairs up to max_dist {max_dist!r}")
+        g = projected_gamma(gamma, n * D)
         if ty is not None:
             ty = np.ascontiguousarray(ty, dtype=np.float64)
             if ty.ndim != 4 or ty.shape[1:] != tx.shape[1:]:
                 raise ValueError(f"Y features of shape {ty.shape} do not match X features of shape {tx.shape}")
         ny = nx if ty is None else ty.shape[0]
         out = np.zeros((ny, nx), dtype=np.float64)
-        _check(lib().qk_projected_pair_gram_host(self._h, n, nx, tx.ctypes.data, ny, None if ty is None else ty.ctypes.data, g, out.ctypes.data, nx),
-               "qk_projected_pair_gram_host")
+        if D == 1:
+            _check(lib().qk_projected_pair_gram_host(self._h, n, nx, tx.ctypes.data, ny, None if ty is None else ty.ctypes.data, g, out.ctypes.data, nx),
+                   "qk_projected_pair_gram_host")
+        else:
+            _check(lib().qk_projected_pair_gram_dist_host(self._h, n, D, nx, tx.ctypes.data, ny, None if ty is None else ty.ctypes.data, g,
+                                                          out.ctypes.data, nx), "qk_projected_pair_gram_dist_host")
         return out
 
     def stats(self) -> dict:

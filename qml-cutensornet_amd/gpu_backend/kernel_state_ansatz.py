@@ -390,8 +390,8 @@ def build_kernel_matrix(mpi_comm, ansatz, X, Y=None, info_file=None, truncation_
 
 
 def _gather_features(comm, lo, F, total):
-    """All-gather of every rank's (first index, features of its share: Bloch vectors (m, n, 3) or neighbour-pair correlators
-    (m, n - 1, 4, 4)) -> the (total, ...) array in data-set order."""
+    """All-gather of every rank's (first index, features of its share: Bloch vectors (m, n, 3) or pair correlators
+    (m, n_pairs, 4, 4)) -> the (total, ...) array in data-set order."""
     shares = comm_allgather(comm, (int(lo), np.ascontiguousarray(F, dtype=np.float64)))
     out = np.zeros((total,) + tuple(F.shape[1:]), dtype=np.float64)
     for s_lo, s_F in shares:
@@ -399,7 +399,7 @@ def _gather_features(comm, lo, F, total):
     return out
 
 
-def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30, rdm=1):
+def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30, rdm=1, pair_distance=1):
     """Projected quantum kernel (Huang et al., Nat. Commun. 12, 2631 (2021)) of the same states as ``build_kernel_matrix``:
         K[j, i] = exp(-g sum_k ||rho_k(X_i) - rho_k(Y_j)||_F^2) = exp(-g/2 sum_k |F(X_i)[k] - F(Y_j)[k]|^2),
     rho_k = the one-qubit reduced density matrix of qubit k, F[k] = its Bloch vector (<X_k>, <Y_k>, <Z_k>); ``Y=None`` means
@@ -410,11 +410,23 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     ``rdm=2`` is the two-qubit form on neighbouring qubits, the first projected kernel that sees correlations between qubits:
         K_2[j, i] = exp(-g sum_k ||rho_{k,k+1}(X_i) - rho_{k,k+1}(Y_j)||_F^2) = exp(-g/4 sum_k sum_pq (T(X_i)[k,p,q] - T(Y_j)[k,p,q])^2),
     T[k, p, q] = <P_p on qubit k, P_q on qubit k+1>, P = (I, X, Y, Z), k = 0 .. n_qubits - 2: 16 (n - 1) reals per state are
-    all-gathered instead of 3 n.  It needs at least two qubits."""
+    all-gathered instead of 3 n.  It needs at least two qubits.
+
+    ``pair_distance=D`` (with ``rdm=2``, 1 <= D <= n_qubits - 1) compares every pair (k, k+d), d = 1 .. D, in the order of
+    ``engine.pair_table(n_qubits, D)``: for an ansatz whose entanglement map reaches distance D these are the pairs its gates
+    touch (D = max(abs(a - b)) over the map).  16 n_pairs reals per state are all-gathered, n_pairs = D n - D (D + 1) / 2, and
+    ``pqk_gamma=None`` means g = 1 / (n_qubits D)."""
     if rdm not in (1, 2):
         raise ValueError(f"rdm must be 1 (one-qubit reduced density matrices) or 2 (neighbouring pairs), got {rdm!r}")
     if rdm == 2 and int(ansatz.num_qubits) < 2:
         raise ValueError("rdm=2 compares reduced density matrices of neighbouring qubit pairs: the ansatz needs at least 2 qubits")
+    if isinstance(pair_distance, bool) or not isinstance(pair_distance, (int, np.integer)):
+        raise ValueError(f"pair_distance must be an int (the largest distance between the two qubits of a pair), got {pair_distance!r}")
+    if pair_distance < 1 or pair_distance > max(1, int(ansatz.num_qubits) - 1):
+        raise ValueError(f"pair_distance must be in 1 .. n_qubits - 1 = {int(ansatz.num_qubits) - 1}, got {pair_distance!r}")
+    if rdm == 1 and pair_distance != 1:
+        raise ValueError(f"pair_distance={pair_distance!r} needs rdm=2: the one-qubit form has no pairs")
+    pair_distance = int(pair_distance)
     if Y is not None and len(X) < len(Y):
         raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
     if truncation_error is None:
@@ -435,6 +447,7 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
 
     host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
     n_qubits = int(ansatz.num_qubits)
+    n_pairs = pair_distance * n_qubits - pair_distance * (pair_distance + 1) // 2  # n_qubits - 1 at distance 1
     prof = {}
     t_start = time.perf_counter()
     if is_root:
@@ -454,9 +467,9 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         ctx.trim()  # the device builder's arena goes back before the local sweep needs memory
         t0 = time.perf_counter()
         if local is None:
-            F, chi = np.zeros((0, n_qubits, 3) if rdm == 1 else (0, n_qubits - 1, 4, 4), dtype=np.float64), np.zeros(0)
+            F, chi = np.zeros((0, n_qubits, 3) if rdm == 1 else (0, n_pairs, 4, 4), dtype=np.float64), np.zeros(0)
         else:
-            F, chi = (ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local)), local.dims.max(axis=1)
+            F, chi = (ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local, max_dist=pair_distance)), local.dims.max(axis=1)
             local.close()
         feat_secs += time.perf_counter() - t0
         shares.append((lo, F, len(points)))
@@ -468,11 +481,13 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     gather_secs = time.perf_counter() - t0
     if not is_root:
         return None
-    g = _engine.projected_gamma(pqk_gamma, n_qubits)
+    g = _engine.projected_gamma(pqk_gamma, n_qubits * pair_distance)
     _say(True, "\nFinished contracting all MPS.\n\nCalculating projected kernel matrix...")
     t0 = time.perf_counter()
-    gram_of = ctx.projected_gram if rdm == 1 else ctx.projected_pair_gram
-    kernel_mat = gram_of(feats[0], None if Y is None else feats[1], g)
+    if rdm == 1:
+        kernel_mat = ctx.projected_gram(feats[0], None if Y is None else feats[1], g)
+    else:
+        kernel_mat = ctx.projected_pair_gram(feats[0], None if Y is None else feats[1], g, max_dist=pair_distance)
     tiles = time.perf_counter() - t0
 
     prof["r0_circ_gen"] = [0.0, "seconds"]
@@ -489,6 +504,8 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     prof["r0_RR_recv"] = [gather_secs, "seconds"]  # the all-gather of the Bloch vectors
     prof["pqk_gamma"] = [g, ""]
     prof["pqk_rdm"] = [rdm, "qubits"]
+    if rdm == 2:
+        prof["pqk_pair_distance"] = [pair_distance, "sites"]
     prof["pqk_features_time"] = [feat_secs, "seconds"]
     prof["kernel_mat_time"] = [tiles, "seconds"]
     prof["total_time"] = [time.perf_counter() - t_start, "seconds"]

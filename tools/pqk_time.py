@@ -2,8 +2,9 @@
 """Time the projected quantum kernel against the fidelity Gram on one MI355X, in one process: the config's states built by the
 device builder, then (each after a warm-up) ctx.gram(xs), ctx.local_paulis(xs), ctx.projected_gram(F) and the two-qubit form,
 ctx.local_pair_paulis(xs) and ctx.projected_pair_gram(T).  Prints one JSON line with the five times, the algorithmic flops of the
-two local sweeps and their achieved TFLOP/s.
-usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N]"""
+two local sweeps and their achieved TFLOP/s.  ``--pair-distance D`` (D > 1) adds the pairs up to distance D:
+ctx.local_pair_paulis(xs, max_dist=D) and ctx.projected_pair_gram(T, max_dist=D), their times, flops and median entry.
+usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D]"""
 import argparse
 import json
 import os
@@ -36,6 +37,18 @@ def pair_sweep_flops(dims):
     return local_sweep_flops(dims) + float((8 * (r * 2 * l * r) + 8 * (2 * l * 2 * l * r)).sum())
 
 
+def dist_sweep_flops(dims, D):
+    """Pairs up to distance D add, at every site k = 1 .. n-2 (l = chi_k, r = chi_k+1) and for each of the min(k, D - 1) live
+    origins, four T-shaped GEMMs (l x 2r over l) and four closing ones (r x r over 2l)."""
+    d = np.asarray(dims, dtype=np.float64)
+    n = d.shape[1] - 1
+    total = pair_sweep_flops(dims)
+    for k in range(1, n - 1):
+        l, r = d[:, k], d[:, k + 1]
+        total += float((min(k, D - 1) * 4 * 8 * (l * 2 * r * l + r * r * 2 * l)).sum())
+    return total
+
+
 def timed(fn, reps):
     fn()  # warm-up
     ts = []
@@ -51,6 +64,7 @@ def main():
     ap.add_argument("--config", default="cfg4", choices=("cfg3", "cfg4", "cfg5"))
     ap.add_argument("--gamma", type=float, default=None, help="default 1.0 (0.1 for cfg5)")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--pair-distance", type=int, default=1, help="also time the pairs up to this distance (default 1: neighbours only)")
     args = ap.parse_args()
     gamma = args.gamma if args.gamma is not None else (0.1 if args.config == "cfg5" else 1.0)
     n, reps, d, npts = bench.CONFIGS[args.config]
@@ -70,6 +84,19 @@ def main():
     KP2, pgram2_ms = timed(lambda: ctx.projected_pair_gram(T), args.reps)
     flops, flops2 = local_sweep_flops(info["dims"]), pair_sweep_flops(info["dims"])
     off = ~np.eye(npts, dtype=bool)
+    dist = {}
+    if args.pair_distance > 1:
+        D = args.pair_distance
+        TD, dist_ms = timed(lambda: ctx.local_pair_paulis(xs, max_dist=D), args.reps)
+        KPD, pgramd_ms = timed(lambda: ctx.projected_pair_gram(TD, max_dist=D), args.reps)
+        flopsd = dist_sweep_flops(info["dims"], D)
+        dist = {
+            "pair_distance": D, "n_pairs": int(TD.shape[1]), "local_pair_dist_ms": round(dist_ms, 3),
+            "projected_pair_dist_gram_ms": round(pgramd_ms, 3), "dist_over_pair": round(dist_ms / pair_ms, 4),
+            "dist_flops": flopsd, "dist_tflops": round(flopsd / (dist_ms * 1e-3) / 1e12, 3),
+            "dist_block_one_is_pair_bits": bool(np.array_equal(TD[:, : n - 1], T)),
+            "median_offdiag_pqk2_dist": float(np.median(KPD[off])),
+        }
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
         "max_bond": int(info["dims"].max()), "build_s": round(build_s, 3),
@@ -79,7 +106,7 @@ def main():
         "local_flops": flops, "local_tflops": round(flops / (local_ms * 1e-3) / 1e12, 3),
         "pair_flops": flops2, "pair_tflops": round(flops2 / (pair_ms * 1e-3) / 1e12, 3),
         "median_offdiag_fidelity_K": float(np.median(K[off])), "median_offdiag_pqk": float(np.median(KP[off])),
-        "median_offdiag_pqk2": float(np.median(KP2[off])),
+        "median_offdiag_pqk2": float(np.median(KP2[off])), **dist,
     }), flush=True)
     xs.close()
     ctx.close()
