@@ -321,8 +321,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_quad_kernel(const
     if (edges) {  // X behind the left edge: one product of the two left blocks
       const v4i r0 = rec[3 * ek];
       const int a_e = rfl(r0.x), b_e = rfl(r0.z);
-      if (a_e * b_e <= XCAP) qkf_edge_prefix<NW>(g, xi, yj, a_e, b_e, XL, wave, q, j);
-      else qkf_edge_prefix<NW>(g, xi, yj, a_e, b_e, G0, wave, q, j), xg = true;
+      xg = a_e * b_e > XCAP;
+      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, xi, yj, a_e, b_e, XL, G0, xg, wave, q, j);
       __syncthreads();
     }
     v2d fr[4], fs[4];
@@ -444,8 +444,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_quad_kernel(const
     if (edges) {  // the overlap: X against the product of the two right blocks
       const v4i r0 = rec[3 * (k_hi - 1)];
       const int a_e = rfl(r0.y), b_e = rfl(r0.w);
-      if (xg) qkf_edge_suffix<NW>(g, xi, yj, a_e, b_e, (const v2d*)(G0 + (long long)cur * g.x_plane), zacc, wave, q, j);
-      else qkf_edge_suffix<NW>(g, xi, yj, a_e, b_e, (const lds_v2d*)(XL + xb), zacc, wave, q, j);
+      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, xi, yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), xg, zacc, wave, q, j);
       __syncthreads();
     }
     if (tid == 0) {

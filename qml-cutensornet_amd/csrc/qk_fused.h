@@ -365,57 +365,175 @@ __device__ __forceinline__ void qkf_rotate(QkfTile (&T)[S], const int L) {  // t
 // each, as much as the matrix work of a 64 x 64 site); likewise at the right end, where the overlap is sum_{b,a} X[b][a] R[b][a]
 // with R = Ry^T conj(Rx).  On the 60-qubit x 6-layer set the model picks k = 8: 16 of 60 sites go.
 // ----------------------------------------------------------------------------------------
-// One 16 x 16 tile of  Ay^T conj(Ax)  (K = ks4 k-steps of 4 rows): Ay / Ax point at this lane's element of k-step 0 (row q, column
-// 16 t + j), ldy / ldx = elements per row.
-__device__ __forceinline__ void qkf_edge_tile(QkfTile& t, const v2d* __restrict__ Ay, const int ldy, const v2d* __restrict__ Ax, const int ldx, const int ks4) {
-  v4d p1 = {0, 0, 0, 0}, p2 = {0, 0, 0, 0}, p3 = {0, 0, 0, 0};
-  v2d fy[4], fx[4];
+// An edge product is streamed like the site loops (qkf_edge_unit): the two blocks are addressed from WAVE-UNIFORM bases, one per k-step of a
+// trip, and a lane byte offset that advances once per trip -- no address arithmetic inside a k-step (the earlier form built
+// (long)(4 * k-step) * ld per k-step in 64-bit vector arithmetic) --, and SETS register sets of one group (four k-steps) each are in flight:
+// the registers of a k-step are reloaded for k-step + 4 SETS right behind its matrix instructions.  Measured per launch of the 60-qubit x
+// 6-layer Gram, parent's library against builds of this code alternating in one call (lab/NOTES_r06.md, profiles/r06/):
+//   12-wave dual launch, 298.4 ms (the two forms below with the dual kernel's pull-ahead loop; single tiles with the parent's loop: 292.2):
+//                                   single tiles, two sets (8 k-steps in flight)  288.2   <- shipped in the 168-register shapes
+//                                   PAIRS of tiles (a unit = two neighbouring column blocks of the y block: the x fragment and its operand sum
+//                                   feed both, 3 loads per 6 matrix instructions), one set  290.5 -- the two sets of a pair (96 fragment
+//                                   registers + 48 of accumulators) do not fit beside the kernel's live state: they spill INSIDE the loop
+//   8-wave launch, 50.0 ms:         single tiles, two sets  49.9 (a tie)  <- NOT shipped: the 128-register shape keeps one set, the depth it had
+//                                   single tiles, one set  49.15   <- shipped there
+// The pair form stays in the source for experiment builds (-DQKF_EDGE_PAIRS_V=1; its units: qk_edge_unit, qk_plan.h).
+#ifdef QKF_EDGE_PAIRS_V
+#define QKF_EDGE_PAIRS(WPS) (QKF_EDGE_PAIRS_V != 0)
+#else
+#define QKF_EDGE_PAIRS(WPS) false
+#endif
+// register sets of a SINGLE tile's streams, by the kernel's waves per SIMD; a pair always runs one set (experiment builds: -DQKF_EDGE_SETS_V=1 | 2)
+#ifdef QKF_EDGE_SETS_V
+#define QKF_EDGE_SETS(WPS) (QKF_EDGE_SETS_V)
+#else
+#define QKF_EDGE_SETS(WPS) ((WPS) <= 3 ? 2 : 1)
+#endif
+// One UNIT of  Ay^T conj(Ax)  (K = 16 ng rows, ng a power of two): the tile of column block `oy` of Ay and, with HAS1, of the column block
+// behind it, against ONE column block of Ax.  Ay / Ax are wave-uniform, oy / ox this lane's element of k-step 0 (row q, column 16 t + j),
+// ldy / ldx = elements per row.  K = 16 is one group (a second set is never loaded), K = 32 one group per set: the steady loop runs for neither.
+__device__ __forceinline__ v2d qkf_lde(const v2d* __restrict__ base, const unsigned boff, const int col = 0) {
+  return reinterpret_cast<const v2d*>(reinterpret_cast<const char*>(base) + (size_t)boff)[col];
+}
+template <bool HAS1, bool MORE>
+__device__ __forceinline__ void qkf_edge_group(v4d (&acc)[6], v2d (&fy)[4], v2d (&fz)[4], v2d (&fx)[4], const v2d* const* const by, const v2d* const* const bx, const unsigned boy,
+                                               const unsigned box) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) fy[i] = Ay[(long)(4 * i) * ldy], fx[i] = Ax[(long)(4 * i) * ldx];  // (ks4 >= 4: K = 2^k >= 16)
-  for (int s0 = 0; s0 < ks4; s0 += 4) {
-    const bool more = s0 + 4 < ks4;
+  for (int i = 0; i < 4; ++i) {
+    const double sb = QKF_DIF(fx[i].x, fx[i].y);  // (conjugated operand)
+    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fy[i].x, fx[i].x, acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fy[i].y, fx[i].y, acc[1], 0, 0, 0);
+    acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(QKF_SUM(fy[i].x, fy[i].y), sb, acc[2], 0, 0, 0);
+    if (HAS1) {
+      acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(fz[i].x, fx[i].x, acc[3], 0, 0, 0);
+      acc[4] = __builtin_amdgcn_mfma_f64_16x16x4f64(fz[i].y, fx[i].y, acc[4], 0, 0, 0);
+      acc[5] = __builtin_amdgcn_mfma_f64_16x16x4f64(QKF_SUM(fz[i].x, fz[i].y), sb, acc[5], 0, 0, 0);
+    }
+    if (MORE) {
+      fy[i] = qkf_lde(by[i], boy);
+      if (HAS1) fz[i] = qkf_lde(by[i], boy, TILE);
+      fx[i] = qkf_lde(bx[i], box);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+template <bool HAS1, int SETS>
+__device__ __forceinline__ void qkf_edge_unit(QkfTile& t0, QkfTile& t1, const v2d* __restrict__ Ay, const unsigned oy, const int ldy, const v2d* __restrict__ Ax, const unsigned ox, const int ldx,
+                                              const int ng) {
+  static_assert(SETS == 1 || SETS == 2, "one or two groups of k-steps in flight");
+  v4d acc[6];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      qkf_kstep<true>(p1, p2, p3, fy[i].x, fy[i].y, fx[i].x, fx[i].y);
-      if (more) fy[i] = Ay[(long)(4 * (s0 + 4 + i)) * ldy], fx[i] = Ax[(long)(4 * (s0 + 4 + i)) * ldx];
+  for (int e = 0; e < 6; ++e) acc[e] = (v4d){0, 0, 0, 0};
+  v2d fy[SETS][4], fz[SETS][4], fx[SETS][4];
+  const v2d *by[4 * SETS], *bx[4 * SETS];  // k-step i of a trip: rows 4 i + q
+#pragma unroll
+  for (int i = 0; i < 4 * SETS; ++i) by[i] = Ay + 4 * i * ldy, bx[i] = Ax + 4 * i * ldx;
+  unsigned boy = oy * 16u, box = ox * 16u;  // this lane's byte offsets: the two running values of the loop
+  const unsigned sy = (unsigned)(SETS * TILE * ldy) * 16u, sx = (unsigned)(SETS * TILE * ldx) * 16u;
+  const bool two = SETS == 2 && ng > 1;
+#pragma unroll
+  for (int s = 0; s < SETS; ++s) {
+    if (s == 0 || two) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        fy[s][i] = qkf_lde(by[4 * s + i], boy);
+        if (HAS1) fz[s][i] = qkf_lde(by[4 * s + i], boy, TILE);
+        fx[s][i] = qkf_lde(bx[4 * s + i], box);
+      }
     }
   }
-  t.re = p1 + p2, t.im = p3 - p1 + p2;
+  QKF_PRIO_LO();
+#pragma unroll 1
+  for (int g = SETS; g < ng; g += SETS) {  // the trips that are followed by another one
+    boy += sy, box += sx;
+#pragma unroll
+    for (int s = 0; s < SETS; ++s) qkf_edge_group<HAS1, true>(acc, fy[s], fz[s], fx[s], by + 4 * s, bx + 4 * s, boy, box);
+  }
+  qkf_edge_group<HAS1, false>(acc, fy[0], fz[0], fx[0], by, bx, boy, box);
+  if constexpr (SETS == 2) {
+    if (two) qkf_edge_group<HAS1, false>(acc, fy[1], fz[1], fx[1], by + 4, bx + 4, boy, box);
+  }
+  QKF_PRIO_HI();
+  t0.re = acc[0] + acc[1], t0.im = acc[2] - acc[0] + acc[1];
+  if (HAS1) t1.re = acc[3] + acc[4], t1.im = acc[5] - acc[3] + acc[4];
+}
+// a 64-bit value that is the same in every lane, moved to scalar registers (the bases of the edge streams)
+__device__ __forceinline__ long long qkf_uniform(const long long v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
-// The environment behind the left edge: X[b][a] = sum_s Ly[s][b] conj(Lx[s][a]), b x a (padded bonds of site edge_k), written
-// row-major with stride a to `xo` (LDS or the global X buffer); tiles dealt round-robin to the NW wavefronts.
-template <int NW, typename XOut>
-__device__ __forceinline__ void qkf_edge_prefix(const SweepArgs& g, const int xi, const int yj, const int a, const int b, XOut xo, const int wave, const int q, const int j) {
-  const v2d* const Lx = reinterpret_cast<const v2d*>(g.xedge) + g.xedge_offs[2 * (long long)xi];
-  const v2d* const Ly = reinterpret_cast<const v2d*>(g.yedge) + g.yedge_offs[2 * (long long)yj];
-  const int mt = a / TILE, nt = b / TILE, ks4 = (1 << g.edge_k) >> 2;
-  for (int t = wave; t < mt * nt; t += NW) {
-    const int tb = t / mt, ta = t - tb * mt;
-    QkfTile T;
-    qkf_edge_tile(T, Ly + (long)q * b + tb * TILE + j, b, Lx + (long)q * a + ta * TILE + j, a, ks4);
+// unit u of a product of mt x nt tiles: single tiles with ta fastest (the shipped kernels), or pairs (qk_edge_unit, qk_plan.h)
+template <int NW, bool PAIRS>
+__device__ __forceinline__ QkEdgeUnit qkf_edge_unit_of(const int u, const int mt, const int nt, const int inv) {
+  if constexpr (PAIRS) return qk_edge_unit(u, mt, nt, NW, inv);
+  const int tb = (u * inv) >> 20;
+  return QkEdgeUnit{u - tb * mt, tb, false, true};
+}
+// The environment behind the left edge: X[b][a] = sum_s Ly[s][b] conj(Lx[s][a]), b x a (padded bonds of site edge_k), written in panels of
+// 16 columns to LDS (`xl`) or, when it does not fit, to the global X buffer (`xg`); units dealt round-robin to the NW wavefronts.
+template <int NW, bool PAIRS, int SETS>
+__device__ __forceinline__ void qkf_edge_prefix(const SweepArgs& g, const int xi, const int yj, const int a, const int b, lds_v2d* const xl, v2d* const xg, const bool to_global, const int wave,
+                                                const int q, const int j) {
+  const v2d* const Lx = reinterpret_cast<const v2d*>(g.xedge) + qkf_uniform(g.xedge_offs[2 * (long long)xi]);
+  const v2d* const Ly = reinterpret_cast<const v2d*>(g.yedge) + qkf_uniform(g.yedge_offs[2 * (long long)yj]);
+  const int mt = a / TILE, nt = b / TILE, ng = (1 << g.edge_k) >> 4, inv = qk_recip20(mt), units = PAIRS ? qk_edge_units(mt, nt, NW) : mt * nt;  // (K = 2^k >= 16)
+  for (int u = wave; u < units; u += NW) {
+    const QkEdgeUnit un = qkf_edge_unit_of<NW, PAIRS>(u, mt, nt, inv);
+    if (!un.mine) continue;
+    QkfTile T0, T1;
+    const unsigned oy = (unsigned)(q * b + un.tb0 * TILE + j), ox = (unsigned)(q * a + un.ta * TILE + j);
+    if (un.has1) qkf_edge_unit<true, 1>(T0, T1, Ly, oy, b, Lx, ox, a, ng);
+    else qkf_edge_unit<false, SETS>(T0, T1, Ly, oy, b, Lx, ox, a, ng);
+    const int at = un.ta * (b * TILE) + (un.tb0 * TILE + q) * TILE + j;  // (panels of 16 columns)
+    if (to_global) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) xo[ta * (b * TILE) + (tb * TILE + q + 4 * r) * TILE + j] = (v2d){T.re[r], T.im[r]};  // (panels of 16 columns)
+      for (int r = 0; r < 4; ++r) xg[at + r * QKF_XSTEP] = (v2d){T0.re[r], T0.im[r]};
+      if (un.has1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xg[at + QKF_XBLOCK + r * QKF_XSTEP] = (v2d){T1.re[r], T1.im[r]};
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) xl[at + r * QKF_XSTEP] = (v2d){T0.re[r], T0.im[r]};
+      if (un.has1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xl[at + QKF_XBLOCK + r * QKF_XSTEP] = (v2d){T1.re[r], T1.im[r]};
+      }
+    }
   }
 }
 
-// The overlap at the right edge: z = sum_{b,a} X[b][a] R[b][a], R = Ry^T conj(Rx); X row-major with stride a at `xin`.  Every
-// wavefront leaves its tiles' share in its own two doubles of `zacc` (LDS, [NW][2]); the caller adds them up in wavefront order behind a barrier.
-template <int NW, typename XIn>
-__device__ __forceinline__ void qkf_edge_suffix(const SweepArgs& g, const int xi, const int yj, const int a, const int b, XIn xin, __attribute__((address_space(3))) double* zacc, const int wave,
-                                                const int q, const int j) {
-  const v2d* const Rx = reinterpret_cast<const v2d*>(g.xedge) + g.xedge_offs[2 * (long long)xi + 1];
-  const v2d* const Ry = reinterpret_cast<const v2d*>(g.yedge) + g.yedge_offs[2 * (long long)yj + 1];
-  const int mt = a / TILE, nt = b / TILE, ks4 = (1 << g.edge_k) >> 2;
+// The overlap at the right edge: z = sum_{b,a} X[b][a] R[b][a], R = Ry^T conj(Rx); X in panels of 16 columns in LDS (`xl`) or in the global
+// buffer (`xg`).  Every wavefront leaves its units' share in its own two doubles of `zacc` (LDS, [NW][2]); the caller adds them up in
+// wavefront order behind a barrier.  Which tiles a wavefront takes is a pure function of the shape (qk_edge_unit), so the sum is reproducible.
+template <int NW, bool PAIRS, int SETS>
+__device__ __forceinline__ void qkf_edge_suffix(const SweepArgs& g, const int xi, const int yj, const int a, const int b, const lds_v2d* const xl, const v2d* const xg, const bool from_global,
+                                                __attribute__((address_space(3))) double* zacc, const int wave, const int q, const int j) {
+  const v2d* const Rx = reinterpret_cast<const v2d*>(g.xedge) + qkf_uniform(g.xedge_offs[2 * (long long)xi + 1]);
+  const v2d* const Ry = reinterpret_cast<const v2d*>(g.yedge) + qkf_uniform(g.yedge_offs[2 * (long long)yj + 1]);
+  const int mt = a / TILE, nt = b / TILE, ng = (1 << g.edge_k) >> 4, inv = qk_recip20(mt), units = PAIRS ? qk_edge_units(mt, nt, NW) : mt * nt;
   double zr = 0, zi = 0;
-  for (int t = wave; t < mt * nt; t += NW) {
-    const int tb = t / mt, ta = t - tb * mt;
-    QkfTile T;
-    qkf_edge_tile(T, Ry + (long)q * b + tb * TILE + j, b, Rx + (long)q * a + ta * TILE + j, a, ks4);
+  for (int u = wave; u < units; u += NW) {
+    const QkEdgeUnit un = qkf_edge_unit_of<NW, PAIRS>(u, mt, nt, inv);
+    if (!un.mine) continue;
+    QkfTile T0, T1;
+    const unsigned oy = (unsigned)(q * b + un.tb0 * TILE + j), ox = (unsigned)(q * a + un.ta * TILE + j);
+    if (un.has1) qkf_edge_unit<true, 1>(T0, T1, Ry, oy, b, Rx, ox, a, ng);
+    else qkf_edge_unit<false, SETS>(T0, T1, Ry, oy, b, Rx, ox, a, ng);
+    const int at = un.ta * (b * TILE) + (un.tb0 * TILE + q) * TILE + j;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const v2d x = xin[ta * (b * TILE) + (tb * TILE + q + 4 * r) * TILE + j];
-      zr += x.x * T.re[r] - x.y * T.im[r], zi += x.x * T.im[r] + x.y * T.re[r];
+      const v2d x = from_global ? xg[at + r * QKF_XSTEP] : (v2d)xl[at + r * QKF_XSTEP];
+      zr += x.x * T0.re[r] - x.y * T0.im[r], zi += x.x * T0.im[r] + x.y * T0.re[r];
+    }
+    if (un.has1) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const v2d x = from_global ? xg[at + QKF_XBLOCK + r * QKF_XSTEP] : (v2d)xl[at + QKF_XBLOCK + r * QKF_XSTEP];
+        zr += x.x * T1.re[r] - x.y * T1.im[r], zi += x.x * T1.im[r] + x.y * T1.re[r];
+      }
     }
   }
 #pragma unroll
@@ -521,6 +639,15 @@ __device__ __forceinline__ void qkf_step_table(const SweepArgs& g, const int xi,
 #define QKF_PROF_FLUSH()
 #endif
 
+// (dual kernel) The workgroup's next pair into a word of its queue slot: called by ONE lane -- lane 0 of the LAST wavefront, which has the fewest units of
+// a ragged round of the right edge (units are dealt from wavefront 0 up), so the queue's atomic mostly waits while that wavefront would idle.
+#define QKF_PULLER(NT) ((NT) - 64)
+__device__ __forceinline__ void qkf_pull_next(const SweepArgs& g, const int xcc, int& gang_round, long long* const word) {
+  const long long pp = qk_pull(g, xcc);  // this XCD's queue first: the workgroups that share an L2 stream the same few states
+  qk_gang_sync(g, xcc, pp >= 0, gang_round);
+  *word = pp;
+}
+
 template <int NW, int S, int XCAP, int WPS, bool DET = false>  // waves per workgroup; T slots per wave (a round holds NW * S items); elements of the LDS X buffer; waves per SIMD (register budget); ordered accumulation (bit-reproducible)
 __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const SweepArgs g) {
   constexpr int NT = 64 * NW;
@@ -605,8 +732,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
     if (edges) {  // X behind the left edge: one product of the two left blocks
       const v4i r0 = rec[3 * ek];
       const int a_e = rfl(r0.x), b_e = rfl(r0.z);
-      if (a_e * b_e <= XCAP) qkf_edge_prefix<NW>(g, xi, yj, a_e, b_e, XL, wave, q, j);
-      else qkf_edge_prefix<NW>(g, xi, yj, a_e, b_e, G0, wave, q, j), xg = true;
+      xg = a_e * b_e > XCAP;
+      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, xi, yj, a_e, b_e, XL, G0, xg, wave, q, j);
       __syncthreads();
     }
     QKF_STAMP(0);  // pair set-up
@@ -724,8 +851,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
     if (edges) {  // the overlap: X against the product of the two right blocks
       const v4i r0 = rec[3 * (k_hi - 1)];
       const int a_e = rfl(r0.y), b_e = rfl(r0.w);
-      if (xg) qkf_edge_suffix<NW>(g, xi, yj, a_e, b_e, (const v2d*)(G0 + (long long)cur * g.x_plane), zacc, wave, q, j);
-      else qkf_edge_suffix<NW>(g, xi, yj, a_e, b_e, (const lds_v2d*)(XL + xb), zacc, wave, q, j);
+      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, xi, yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), xg, zacc, wave, q, j);
       __syncthreads();
     }
     if (tid == 0) {
@@ -1071,20 +1197,26 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
   const int xcc = qk_xcc_id();
   int gang_round = 0;  // (gang start: this workgroup's pairs so far)
   if (tid == 0) qk_tail_start(g);
-  for (;;) {
-    if (tid == 0) {
-      const long long pp_ = qk_pull(g, xcc);
-      qk_gang_sync(g, xcc, pp_ >= 0, gang_round);
-      *slot = pp_;
-    }  // this XCD's queue first: the workgroups that share an L2 stream the same few states
-    __syncthreads();
-    const long long p = *slot;
-    __syncthreads();
-    if (p < 0) break;
+  // The queue is pulled ONE PAIR AHEAD (qkf_pull_next): the pair after the current one while the waves run the current pair's right edge,
+  // its step table behind that edge's barrier -- the table of the pair that just ended is dead by then, so one table serves.  The two
+  // words of `slot` alternate per pair.  A workgroup still never pulls a pair it does not run.  Against the loop of the one-tile kernel
+  // (pull, barrier, read, barrier, table in front of every pair, a barrier behind it): the atomic's latency leaves the critical path and
+  // two barriers per pair go.  60-qubit x 6-layer Gram, this launch: 292.2 -> 288.4 ms; the 8-wave launch of the one-tile kernel measured
+  // 49.15 -> 48.90 ms, inside its noise margin, so that kernel keeps its loop (lab/NOTES_r06.md).
+  if (tid == QKF_PULLER(NT)) qkf_pull_next(g, xcc, gang_round, slot);
+  __syncthreads();
+  long long p = slot[0];
+  int psel = 0;  // the word of `slot` that holds p
+  auto table_of = [&](const long long pp) __attribute__((always_inline)) {
+    if (pp < 0) return;
+    const int xi_ = g.pairs[2 * pp], yj_ = g.pairs[2 * pp + 1];
+    qkf_step_table<XCAP, NT>(g, xi_, yj_, rec, m_off, tid, [](const int pmt, const int nt) { return pmt * ((nt + 1) / 2) <= NW; });
+  };
+  table_of(p);
+  while (p >= 0) {
     const int xi = g.pairs[2 * p], yj = g.pairs[2 * p + 1];
     // a unit is (ta, tp, p): pd mt ceil(nt / 2) pairs of tiles.  LDS-resident step: X and X' fit the buffer and ONE round holds
     // all pairs, or they fit side by side; otherwise X' is built in strips of W blocks of b', pairs in rounds of NW
-    qkf_step_table<XCAP, NT>(g, xi, yj, rec, m_off, tid, [](const int pmt, const int nt) { return pmt * ((nt + 1) / 2) <= NW; });
     const int ek = g.edge_k, k_hi = ns - ek;  // the chain runs over the sites [ek, k_hi): the ends are in the edge blocks
     const bool edges = ek > 0;
     if (!edges)
@@ -1098,8 +1230,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
     if (edges) {  // X behind the left edge: one product of the two left blocks
       const v4i r0 = rec[3 * ek];
       const int a_e = rfl(r0.x), b_e = rfl(r0.z);
-      if (a_e * b_e <= XCAP) qkf_edge_prefix<NW>(g, xi, yj, a_e, b_e, XL, wave, q, j);
-      else qkf_edge_prefix<NW>(g, xi, yj, a_e, b_e, G0, wave, q, j), xg = true;
+      xg = a_e * b_e > XCAP;
+      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, xi, yj, a_e, b_e, XL, G0, xg, wave, q, j);
       __syncthreads();
     }
     QKF_STAMP(0);  // pair set-up (queue, step table, left edge)
@@ -1214,13 +1346,14 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
         xb = ob;
       }
     }
+    if (tid == QKF_PULLER(NT)) qkf_pull_next(g, xcc, gang_round, slot + (psel ^ 1));  // the next pair, while the other wavefronts run the right edge
     if (edges) {  // the overlap: X against the product of the two right blocks
       const v4i r0 = rec[3 * (k_hi - 1)];
       const int a_e = rfl(r0.y), b_e = rfl(r0.w);
-      if (xg) qkf_edge_suffix<NW>(g, xi, yj, a_e, b_e, (const v2d*)(G0 + (long long)cur * g.x_plane), zacc, wave, q, j);
-      else qkf_edge_suffix<NW>(g, xi, yj, a_e, b_e, (const lds_v2d*)(XL + xb), zacc, wave, q, j);
-      __syncthreads();
+      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, xi, yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), xg, zacc, wave, q, j);
     }
+    __syncthreads();  // the partial sums and the next pair's index are in LDS; nobody reads this pair's step table any more
+    const long long pn = slot[psel ^ 1];
     if (tid == 0) {
       v2d zz = {0.0, 0.0};
       if (edges)
@@ -1232,8 +1365,10 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
         g.z[2 * p + 1] = zz.y;
       }
     }
-    __syncthreads();
-    QKF_STAMP(6);  // right edge, result
+    table_of(pn);  // (the barrier that opens the next pair publishes it)
+    if (!edges) __syncthreads();  // thread 0 has read the result from X: the next pair's X_0 may now be written
+    p = pn, psel ^= 1;
+    QKF_STAMP(6);  // right edge, result, the next pair's step table
   }
   if (tid == 0) qk_tail_exit(g);
   QKF_PROF_FLUSH();

@@ -72,6 +72,35 @@ QK_HD static inline QkUnit qk_unit_decode_ordered(const int v, const int ps, con
   return QkUnit{u - tc * mt, tc, v & ((1 << ps) - 1)};
 }
 
+// ----------------------------------------------------------------------------------------
+// The units of an EDGE product (qk_fused.h: qkf_edge_prefix / qkf_edge_suffix).  The product has mt x nt tiles (ta = block of 16 columns of
+// the x block, tb = block of 16 columns of the y block).  A unit is (ta, tb0, has1): the tile (ta, tb0) and, with has1, its neighbour
+// (ta, tb0 + 1) -- one fragment of the x block feeds both.  Pair v = tp * mt + ta (ta fastest) covers the column blocks 2 tp, 2 tp + 1; the
+// last pair of an odd nt is a single tile.  Units are dealt to the NW waves in rounds of NW consecutive indices u.  When the pairs left for
+// the last round fill at most half of the waves, that round is dealt as single tiles (the rule of the dual kernel's rounds): index
+// r0 + w is the first tile of pair r0 + w, index r0 + left + w its second one, so the round takes half as long.
+//   qk_edge_units: how many indices u a product has (indices without a tile -- `mine` false -- occur only in a round of singles);
+//   qk_edge_unit:  index u -> unit.  inv_mt = qk_recip20(mt).
+// Pure functions, host and device; checked on the CPU for every mt, nt <= 16 (tests/host_san/edge_units_main.cpp).  The shipped kernels take
+// single tiles (they measured faster than pairs at the same matrix work in flight: lab/NOTES_r06.md); the pairs run in builds with
+// -DQKF_EDGE_PAIRS_V=1.
+// ----------------------------------------------------------------------------------------
+struct QkEdgeUnit {
+  int ta, tb0;
+  bool has1, mine;
+};
+QK_HD static inline int qk_edge_units(const int mt, const int nt, const int NW) {
+  const int pairs = mt * ((nt + 1) >> 1), r0 = (pairs - 1) / NW * NW, left = pairs - r0;
+  return 2 * left <= NW ? r0 + 2 * left : pairs;
+}
+QK_HD static inline QkEdgeUnit qk_edge_unit(const int u, const int mt, const int nt, const int NW, const int inv_mt) {
+  const int pairs = mt * ((nt + 1) >> 1), r0 = (pairs - 1) / NW * NW, left = pairs - r0;
+  const bool halves = 2 * left <= NW, single = halves && u >= r0, half = halves && u >= r0 + left;
+  const int v = u - (half ? left : 0), tp = (v * inv_mt) >> 20;
+  const bool second = 2 * tp + 1 < nt;
+  return QkEdgeUnit{v - tp * mt, 2 * tp + (half ? 1 : 0), !single && second, u < (halves ? r0 + 2 * left : pairs) && (!half || second)};
+}
+
 struct qk_ctx;
 
 struct qk_plan {
