@@ -346,6 +346,35 @@ int qk_local_pair_paulis_dist_host(qk_ctx* ctx, const qk_mps_set* set, int32_t m
 int qk_projected_pair_gram_dist_host(qk_ctx* ctx, int32_t n_sites, int32_t max_dist, int32_t nx, const double* tx /* [nx][n_pairs][4][4] */,
                                      int32_t ny, const double* ty /* NULL: Y is X */, double g, double* out, int64_t ld);
 
+/* Expectation values of Pauli strings for every state of a set, synchronous on the context's stream.  P_0..P_3 = I, X, Y, Z; a
+ * string is c[0 .. n_sites - 1] with codes 0..3 (site k = qubit k, physical index 0 = |0>; the states need not be normalised):
+ *     out[state][m] = <psi| P_c[0] (x) ... (x) P_c[n-1] |psi> / <psi|psi>                                        (real)
+ *                   = sum psi(..s_k..) conj(psi(..s'_k..)) prod_k P_c[k][s'_k][s_k] / <psi|psi>
+ * the convention of out2[k][p][q] above.  The support of a string is [a, b], its first and last non-identity sites: the left
+ * environment L_a, one closed transfer step per site of [a, b] with the Pauli on the ket index (two GEMMs, as one step of the
+ * sweep, and an elementwise pass where the site is not I), and one reduction against the right environment R_{b+1}.  A string
+ * costs work on its support only; every L_k and R_k of a state is made once per call.  An all-identity string is written as
+ * exactly 1.0; duplicates are allowed.  n_sites = 1 is valid.  norms, when given, are the bits qk_local_paulis_host returns.
+ * The value of a (state, string) is the same bits whatever the other states of the set, the other strings of the call and their
+ * order, however the call was cut into batches, and from run to run.  Agreement with qk_local_paulis_host and the pair
+ * correlators is to rounding.
+ * Device scratch: per state the sweep's planes and every L_k and R_k, and 6 P^2 doubles per (state, string) of a batch (P = the
+ * state's largest padded bond), counted by the batching rule of qk_local_paulis_host (the strings of a state go in several
+ * batches when they do not fit) and released by qk_ctx_trim.  QK_STRINGS_BATCH=<k> (read per call) caps the (state, string)
+ * chains of a batch at k.
+ * QK_EINVAL: a null ctx, set, strings or out; a set of another context; a complex64 set; n_strings < 1; a code above 3.       */
+int qk_pauli_strings_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_strings,
+                          const uint8_t* strings /* [n_strings][n_sites], codes 0..3 = I, X, Y, Z */,
+                          double* out /* [n_states][n_strings] */, double* norms /* [n_states], may be NULL */);
+
+/* The Gram of any real feature columns (host arrays [n][n_features], for instance qk_pauli_strings_host's output), synchronous:
+ *     out[j * ld + i] = exp(-g * sum_m (fx[i][m] - fy[j][m])^2)
+ * Rows, columns, fy = NULL, the fixed summation order (exact symmetry, unit diagonal) and the argument errors are those of
+ * qk_projected_gram_host; n_features < 1 is QK_EINVAL.  With the 3 n_sites Bloch components as columns it is
+ * qk_projected_gram_host at 2 g.                                                                                              */
+int qk_feature_gram_host(qk_ctx* ctx, int32_t n_features, int32_t nx, const double* fx /* [nx][n_features] */,
+                         int32_t ny, const double* fy /* NULL: Y is X */, double g, double* out, int64_t ld);
+
 /* ---- profiler ranges -----------------------------------------------------------------------------------------
  * roctx ranges (rocprofv3 --marker-trace) named "qk:build", "qk:upload", "qk:sweep", "qk:scatter", "qk:allgather_values",
  * "qk:allgather_sets" are opened by the library around its own phases -- the reference's MPI.Wtime() sites G:209-231

@@ -2,7 +2,8 @@
 // matrices of neighbouring qubits (their Pauli correlators) and the projected quantum kernel (PQK) Grams built from either.  Part of
 // libqkgram.so; entry points qk_local_paulis_host, qk_projected_gram_host, qk_local_pair_paulis_host,
 // qk_projected_pair_gram_host and their forms for pairs up to a chosen distance, qk_local_pair_paulis_dist_host and
-// qk_projected_pair_gram_dist_host (include/qkgram.h).
+// qk_projected_pair_gram_dist_host, and the general form, expectation values of Pauli strings and the Gram of any feature columns,
+// qk_pauli_strings_host and qk_feature_gram_host (include/qkgram.h).
 //
 // Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
 // normalised):
@@ -54,6 +55,22 @@
 // reduction launch makes rho_{o,k+1} of every live origin, then W_k is copied into the slot of the origin whose last distance was
 // just used.  The neighbour launches are untouched and come first: the distance-1 block, the Bloch vectors and the norms are the
 // bits of the neighbour call for every D, and D = 1 is the neighbour call.
+//
+// Pauli strings (qk_pauli_strings_host).  A string is c[0 .. n-1], codes 0..3 = I, X, Y, Z, with support [a, b] (its first and last
+// non-identity sites); P[s ^ f][s] = i^e(s) as in qk_local_pair_features_kernel:
+//     E_a = L_a
+//     E_{k+1}[b'][a'] = sum_s i^{e_k(s)} sum_{b,a} E_k[b][a] A_k[b][s][b'] conj(A_k[a][s ^ f_k][a'])        (k = a .. b)
+//     value = Re sum_{b', a'} E_{b+1}[b'][a'] R_{b+1}[b'][a'] / L_n[0][0]
+// An environment pass per state batch -- the reversed chain and the forward T / W launches of the one-qubit sweep, then L_{k+1} from
+// W by the sum the rho kernel makes, so the norms are that sweep's bits -- keeps every R_k and every L_k.  A chain is one
+// (state, string) with its own slot (E and the intermediate T, 6 P^2 doubles).  At site k every live chain (a <= k <= b) of the chain
+// batch goes through ONE T-shaped launch (the LOC_DIST_T shape; a chain that starts at k reads the kept L_k in place of its slot),
+// ONE elementwise launch over T for the chains whose code at k is not I (T[(a, s ^ f)] <- i^e(s) T[(a, s)]: the product below pairs
+// row (a, u) of T with conj(A_k[(a, u)]), so the Pauli costs no matrix work), ONE X-shaped launch (LOC_DIST_X: one product over
+// K = 2 chi_k) and, for the chains with b = k, one closing reduction against R_{k+1} in 16-row chunks.  A task's block number also
+// names the chain.  4 n_sites launches per chain batch, whatever the number of strings; a string costs work on its support only.  The
+// chunk sums of a chain are added in a fixed order and nothing of a chain depends on another chain, so a value is the same bits
+// whatever the other states and strings, their order and the cut of the batches (QK_STRINGS_BATCH caps the chains of one).
 #include "qk_host.h"
 #include "qk_ring.h"
 
@@ -654,7 +671,465 @@ int projected_gram(qk_ctx* c, const char* what, const char* range, int32_t n_sit
   return QK_OK;
 }
 
+// ---- Pauli strings (qk_pauli_strings_host) ------------------------------------------------------------------------------------
+// A chain is one (state, string) with a non-identity site; its support is [a, b].  Its slot (doubles, P = the state's largest
+// padded bond): E [P x P] at 0 (re plane, im plane at P^2, ld = the current padded bond) | T [P x 2P] at 2P^2 (im plane at 4P^2).
+enum StrKind : int {
+  STR_T = 0,       // T[a][(s, b')] = sum_b E_k[b][a] A_k[b][(s, b')] of every live chain (the LOC_DIST_T shape); E_a is read from the stored L_a
+  STR_X = 1,       // E_{k+1}[b'][a'] = sum_{(a,u)} T[(a, u)][b'] conj(A_k[(a, u)][a']) over K = 2 chi_k (the LOC_DIST_X shape)
+  STR_PAULI = -1,  // qk_str_pauli_kernel: T[a][(s ^ f, b')] <- i^e(s) T[a][(s, b')] of the chains whose code at site k is not I
+  STR_CLOSE = -2,  // qk_str_close_kernel: sum E_{b+1} R_{b+1} of the chains whose support ends at site k
+  STR_LNEXT = -3,  // qk_str_lnext_kernel (environment pass): L_{k+1} = W_0[.][(0, .)] + W_1[.][(1, .)], kept
+};
+struct StrArgs {
+  const double* data;     // the set's planes and tables, as LocArgs
+  const int32_t* dims;
+  const int32_t* tru;
+  const int64_t* offs;
+  const int32_t* states;  // the state batch's tables, as LocArgs
+  const int32_t* pmax;
+  const int64_t* sbase;
+  const int64_t* roff;
+  const int64_t* loff;    // [batch][n_sites + 1]: the kept L_k (k = 0 .. n_sites - 1) at sbase + LOC_RMUL P^2 + loff[k], pad_k^2 per plane
+  const double* env;      // the state batch's scratch (LocArgs.scratch): sweep planes, every R_k, every L_k
+  const int32_t* cent;    // chain -> batch entry
+  const int32_t* cstr;    // chain -> string
+  const int64_t* cbase;   // chain -> first double of its slot
+  const uint8_t* strings; // [n_strings][n_sites]
+  const int32_t* supp;    // [n_strings][2]: a, b
+  const int2* tasks;      // this launch: (chain, block)
+  double* slots;
+  double* part;           // closing partial sums [chain][max chunks]
+  int n_sites;
+  int max_chunks;
+  int step;               // site k
+};
+
+// One 64 x 64 output block of one chain's GEMM at site k.  CONJB = false: STR_T, true: STR_X.
+template <bool CONJB>
+__global__ __launch_bounds__(512) void qk_str_gemm_kernel(const StrArgs g) {
+  __shared__ __attribute__((aligned(16))) double lds[LOC_LDS_DOUBLES];
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = __builtin_amdgcn_readfirstlane(t.x);
+  const int blk = __builtin_amdgcn_readfirstlane(t.y);
+  const int i = __builtin_amdgcn_readfirstlane(g.cent[ch]);
+  const int n = g.n_sites, n1 = n + 1, k = g.step;
+  const long long st = __builtin_amdgcn_readfirstlane(g.states[i]);
+  const int l = __builtin_amdgcn_readfirstlane(g.dims[st * n1 + k]), r = __builtin_amdgcn_readfirstlane(g.dims[st * n1 + k + 1]);
+  const int lt = __builtin_amdgcn_readfirstlane(g.tru[st * n1 + k]);
+  const long long P = __builtin_amdgcn_readfirstlane(g.pmax[i]), P2 = P * P;
+  double* const E = g.slots + uni64(g.cbase[ch]);
+  double* const T = E + 2 * P2;
+  const double* Bre = g.data + uni64(g.offs[st * n + k]);
+  const double* Bim = Bre + (long long)l * 2 * r;
+  const double *Are, *Aim;
+  double *Cre, *Cim;
+  int lda, ldb, ldc, M, N, K;
+  if (!CONJB) {
+    const int a = __builtin_amdgcn_readfirstlane(g.supp[2 * __builtin_amdgcn_readfirstlane(g.cstr[ch])]);
+    if (a == k) {  // the chain starts here: E_a = L_a
+      Are = g.env + uni64(g.sbase[i]) + LOC_RMUL * P2 + uni64(g.loff[(long long)i * n1 + k]);
+      Aim = Are + (long long)l * l;
+    } else {
+      Are = E, Aim = E + P2;
+    }
+    Cre = T, Cim = T + 2 * P2;
+    lda = l, ldb = 2 * r, ldc = 2 * r, M = l, N = 2 * r, K = lt;
+  } else {
+    Are = T, Aim = T + 2 * P2;
+    Cre = E, Cim = E + P2;
+    lda = r, ldb = r, ldc = r, M = r, N = r, K = 2 * lt;
+  }
+  const int npm = (M + 63) / 64;
+  const int m0 = 64 * (blk % npm), n0 = 64 * (blk / npm);
+  zgemm_ring3<CONJB, LOC_KTL, LOC_NSLOT, true, 8, 64, double, 8>(Cre + (long long)m0 * ldc + n0, Cim + (long long)m0 * ldc + n0, ldc, Are + m0, Aim + m0, lda,
+                                                                  Bre + n0, Bim + n0, ldb, min(64, M - m0), min(64, N - n0), K, lds);
+}
+
+// The Pauli of site k on the ket index of T, in place, rows a of one 16-row chunk: P[s ^ f][s] = i^e(s), so the row (a, s ^ f)
+// that the X-shaped product pairs with conj(A_k[(a, s ^ f)]) becomes i^e(s) T[(a, s)].  X: the halves swap; Y: (T_0, T_1) <-
+// (-i T_1, i T_0); Z: T_1 <- -T_1.
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_pauli_kernel(const StrArgs g) {
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = t.x, c = t.y;
+  const int i = g.cent[ch], m = g.cstr[ch];
+  const int n = g.n_sites, n1 = n + 1, k = g.step;
+  const long long st = g.states[i];
+  const int r = g.dims[st * n1 + k + 1];
+  const int code = g.strings[(long long)m * n + k];
+  const long long P = g.pmax[i], P2 = P * P, tpl = 2 * P2;
+  double* const T = g.slots + g.cbase[ch] + 2 * P2;
+  const int cnt = LOC_CHUNK * r;
+  for (int e = threadIdx.x; e < cnt; e += LOC_RED_THREADS) {
+    const long long q0 = (long long)(c * LOC_CHUNK + e / r) * 2 * r + e % r, q1 = q0 + r;
+    const double r0 = T[q0], i0 = T[q0 + tpl], r1 = T[q1], i1 = T[q1 + tpl];
+    const bool x = code == 1, y = code == 2;
+    T[q0] = x ? r1 : y ? i1 : r0;
+    T[q0 + tpl] = x ? i1 : y ? -r1 : i0;
+    T[q1] = x ? r0 : y ? -i0 : -r1;
+    T[q1 + tpl] = x ? i0 : y ? r0 : -i1;
+  }
+}
+
+// Re sum_{b', a'} E_{b+1}[b'][a'] R_{b+1}[b'][a'] over one 16-row chunk of b', unnormalised: part[(chain, chunk)].
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_close_kernel(const StrArgs g) {
+  __shared__ double red[LOC_RED_THREADS];
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = t.x, c = t.y;
+  const int i = g.cent[ch];
+  const int n1 = g.n_sites + 1, k = g.step;
+  const long long st = g.states[i];
+  const int r = g.dims[st * n1 + k + 1];
+  const long long P = g.pmax[i], P2 = P * P, rpl = (long long)r * r;
+  const double* const E = g.slots + g.cbase[ch];
+  const double* const R = g.env + g.sbase[i] + LOC_RMUL * P2 + g.roff[(long long)i * n1 + k + 1];
+  double acc = 0;
+  const int rows = LOC_CHUNK * r;
+  for (int e = threadIdx.x; e < rows; e += LOC_RED_THREADS) {
+    const long long q = (long long)c * rows + e;
+    acc += E[q] * R[q] - E[q + P2] * R[q + rpl];
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int h = LOC_RED_THREADS / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) g.part[(long long)ch * g.max_chunks + c] = red[0];
+}
+
+// Environment pass, rows b' of one 16-row chunk: L_{k+1} = W_0[.][(0, .)] + W_1[.][(1, .)] -- the sum qk_local_rho_kernel makes,
+// so L_n[0][0] is that sweep's norm bit for bit -- into the sweep's L plane and, for k + 1 < n_sites, into the kept L_{k+1}.
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_lnext_kernel(const LocArgs g, const int64_t* loff) {
+  const int2 t = g.tasks[blockIdx.x];
+  const int i = t.x, c = t.y;
+  const int n = g.n_sites, n1 = n + 1, k = g.step;
+  const long long st = g.states[i];
+  const int r = g.dims[st * n1 + k + 1];
+  const long long P = g.pmax[i], P2 = P * P, tpl = 2 * P2, rpl = (long long)r * r;
+  double* const S = g.scratch + g.sbase[i];
+  const double* W0 = S + 6 * P2;
+  const double* W1 = W0 + 2 * tpl;
+  double* const Lk = (k + 1 < n) ? S + LOC_RMUL * P2 + loff[(long long)i * n1 + k + 1] : nullptr;
+  const int rows = LOC_CHUNK * r;
+  for (int e = threadIdx.x; e < rows; e += LOC_RED_THREADS) {
+    const int bp = c * LOC_CHUNK + e / r, ap = e % r;
+    const long long w = (long long)bp * 2 * r + ap, q = (long long)bp * r + ap;
+    const double re = W0[w] + W1[w + r], im = W0[w + tpl] + W1[w + r + tpl];
+    S[q] = re, S[q + P2] = im;
+    if (Lk) Lk[q] = re, Lk[q + rpl] = im;
+  }
+}
+
+// The kept L_0 = 1 (16 x 16, [0][0] = 1) of every state of the batch.
+__global__ __launch_bounds__(256) void qk_str_init_kernel(const LocArgs g, const int64_t* loff) {
+  const int i = blockIdx.x;
+  const long long P = g.pmax[i];
+  double* const L0 = g.scratch + g.sbase[i] + LOC_RMUL * P * P + loff[(long long)i * (g.n_sites + 1)];
+  L0[threadIdx.x] = (threadIdx.x == 0) ? 1.0 : 0.0, L0[256 + threadIdx.x] = 0.0;
+}
+
+__global__ __launch_bounds__(256) void qk_str_norms_kernel(const LocArgs g, const int nb, double* norms) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < nb) norms[g.states[i]] = g.scratch[g.sbase[i]];  // L_n[0][0]
+}
+
+// The values of a chain batch: the chunk sums of each chain in a fixed order, normalised by L_n[0][0].
+__global__ __launch_bounds__(256) void qk_str_values_kernel(const StrArgs g, const int nc, const int n_strings, double* out) {
+  const int ch = blockIdx.x * 256 + threadIdx.x;
+  if (ch >= nc) return;
+  const int i = g.cent[ch], m = g.cstr[ch];
+  const long long st = g.states[i];
+  const int chunks = g.dims[st * (g.n_sites + 1) + g.supp[2 * m + 1] + 1] / LOC_CHUNK;
+  const double* p = g.part + (long long)ch * g.max_chunks;
+  double v = 0;
+  for (int c = 0; c < chunks; ++c) v += p[c];
+  out[st * n_strings + m] = v / g.env[g.sbase[i]];
+}
+
+int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, const uint8_t* strings, double* out, double* norms) {
+  static const char* what = "qk_pauli_strings_host";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!set) return qk_fail(QK_EINVAL, "%s: set is null", what);
+  if (!strings) return qk_fail(QK_EINVAL, "%s: strings is null", what);
+  if (!out) return qk_fail(QK_EINVAL, "%s: out is null", what);
+  if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
+  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; Pauli strings need an fp64 set", what);
+  if (n_strings < 1) return qk_fail(QK_EINVAL, "%s: n_strings must be >= 1 (got %d)", what, n_strings);
+  const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
+  std::vector<int32_t> supp((size_t)2 * n_strings, -1);  // a, b of each string; -1: all identity
+  for (int m = 0; m < n_strings; ++m)
+    for (int k = 0; k < n; ++k) {
+      const int code = strings[(size_t)m * n + k];
+      if (code > 3) return qk_fail(QK_EINVAL, "%s: strings[%d][%d] = %d is not a Pauli code (0..3 = I, X, Y, Z)", what, m, k, code);
+      if (code && supp[2 * m] < 0) supp[2 * m] = k;
+      if (code) supp[2 * m + 1] = k;
+    }
+  long long cap = 0;  // chains per batch; 0: the memory rule alone
+  if (const char* v = std::getenv("QK_STRINGS_BATCH")) {
+    cap = std::atoll(v);
+    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_STRINGS_BATCH must be >= 1 (got \"%s\")", what, v);
+  }
+  QkRangeGuard range_("qk:pauli_strings");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  std::vector<int64_t> offs((size_t)ns * n);
+  HIP_TRY_AS(what, hipMemcpy(offs.data(), set->d_offs.get<int64_t>(), offs.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  const int32_t* tru = set->dims_true.data();
+  std::vector<int32_t> pad((size_t)ns * n1);
+  std::vector<int> pmax(ns);
+  std::vector<long long> need(ns);  // environment doubles of each state: the sweep's planes, R_1 .. R_n, L_0 .. L_{n-1}
+  for (int s = 0; s < ns; ++s) {
+    int p = 16;
+    long long esum = 0;
+    for (int k = 0; k <= n; ++k) {
+      const int d = pad[(size_t)s * n1 + k] = pad16h(tru[(size_t)s * n1 + k]);
+      p = std::max(p, d);
+      esum += (k >= 1 ? 2ll * d * d : 0) + (k < n ? 2ll * d * d : 0);
+    }
+    pmax[s] = p;
+    need[s] = (long long)LOC_RMUL * p * p + esum;
+  }
+  const int max_chunks = set->max_pad / LOC_CHUNK;
+  // tasks of the chain (state s, string m): per site of [a, b] the blocks of the two GEMMs and the Pauli's chunks, then the closing chunks
+  auto chain_tasks = [&](const int s, const int m) {
+    const int* p = &pad[(size_t)s * n1];
+    long long nt = p[supp[2 * m + 1] + 1] / LOC_CHUNK;
+    for (int k = supp[2 * m]; k <= supp[2 * m + 1]; ++k)
+      nt += blocks64(p[k], 2ll * p[k + 1]) + blocks64(p[k + 1], p[k + 1]) + (strings[(size_t)m * n + k] ? p[k] / LOC_CHUNK : 0);
+    return nt;
+  };
+  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t b_str = al((size_t)n_strings * n), b_supp = al(supp.size() * sizeof(int32_t));
+  QkDevBuf rev, dout, dnorm, dstr;
+  HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
+  HIP_TRY_AS(what, dout.alloc((size_t)ns * n_strings * sizeof(double)));
+  HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
+  HIP_TRY_AS(what, dstr.alloc(b_str + b_supp));
+  HIP_TRY_AS(what, hipMemcpy(dstr.get<char>(), strings, (size_t)n_strings * n, hipMemcpyHostToDevice));
+  HIP_TRY_AS(what, hipMemcpy(dstr.get<char>() + b_str, supp.data(), supp.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
+  // memory bound of a state batch (environments and the slots of its live chains): a quarter of what is free; the environments
+  // of a batch take at most half of that (at least one state per batch), the chains of a batch the rest (at least one chain)
+  const long long budget = (long long)((free_b + c->local_scratch.bytes) / 4 / sizeof(double));
+  std::vector<int> bstart{0};
+  for (long long acc = 0, s = 0; s < ns; ++s) {
+    if (acc > 0 && acc + need[s] > budget / 2) bstart.push_back((int)s), acc = 0;
+    acc += need[s];
+  }
+  bstart.push_back(ns);
+  // the launches of the environment pass, in stream order: the reversed chain as in local_sweep, then per site forward T / W and L_{k+1}
+  std::vector<std::pair<int, int>> plan;  // (kind, step)
+  for (int j = 0; j < n - 1; ++j) plan.push_back({LOC_REV_T, j}), plan.push_back({LOC_REV_X, j});
+  for (int k = 0; k < n; ++k) plan.push_back({LOC_FWD_T, k}), plan.push_back({LOC_FWD_W, k}), plan.push_back({STR_LNEXT, k});
+  static const int chain_kinds[4] = {STR_T, STR_PAULI, STR_X, STR_CLOSE};  // the launches of a site of the chain pass, in stream order
+  std::vector<int2> tasks;
+  std::vector<long long> first;
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+    std::vector<int32_t> h_states(nb), h_pmax(nb);
+    std::vector<int64_t> h_sbase(nb), h_roff((size_t)nb * n1), h_loff((size_t)nb * n1);
+    long long tot = 0;
+    for (int i = 0; i < nb; ++i) {
+      const int s = s0 + i;
+      h_states[i] = s, h_pmax[i] = pmax[s], h_sbase[i] = tot;
+      long long ro = 0;
+      for (int k = 0; k <= n; ++k) {
+        h_roff[(size_t)i * n1 + k] = ro;
+        if (k >= 1) ro += 2ll * pad[(size_t)s * n1 + k] * pad[(size_t)s * n1 + k];
+      }
+      for (int k = 0; k <= n; ++k) {  // the L_k behind the R_k
+        h_loff[(size_t)i * n1 + k] = ro;
+        ro += 2ll * pad[(size_t)s * n1 + k] * pad[(size_t)s * n1 + k];
+      }
+      tot += need[s];
+    }
+    tasks.clear(), first.clear();
+    for (const auto& [kind, step] : plan) {
+      first.push_back((long long)tasks.size());
+      for (int i = 0; i < nb; ++i) {
+        const int* p = &pad[(size_t)(s0 + i) * n1];
+        const int o = n - 1 - step, k = step;
+        int nbk = 0;
+        switch (kind) {
+          case LOC_REV_T: nbk = (int)blocks64(p[o + 1], 2ll * p[o]); break;
+          case LOC_REV_X: nbk = (int)blocks64(p[o], p[o]); break;
+          case LOC_FWD_T: nbk = (int)blocks64(p[k], 2ll * p[k + 1]); break;
+          case LOC_FWD_W: nbk = (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); break;
+          default: nbk = p[k + 1] / LOC_CHUNK; break;  // STR_LNEXT
+        }
+        for (int b = 0; b < nbk; ++b) tasks.push_back(int2{i, b});
+      }
+    }
+    first.push_back((long long)tasks.size());
+    // the chains of the state batch, state-major in string order, cut into chain batches: consecutive chains while their slots,
+    // partial sums and tasks fit what the environments leave, and at most QK_STRINGS_BATCH of them
+    std::vector<int32_t> h_cent, h_cstr;
+    std::vector<long long> cweight, ctasks;
+    for (int i = 0; i < nb; ++i)
+      for (int m = 0; m < n_strings; ++m)
+        if (supp[2 * m] >= 0) {
+          h_cent.push_back(i), h_cstr.push_back(m);
+          ctasks.push_back(chain_tasks(s0 + i, m));
+          cweight.push_back(6ll * pmax[s0 + i] * pmax[s0 + i] + max_chunks + ctasks.back() + 2);
+        }
+    const size_t nch = h_cent.size();
+    const long long room = budget - tot;
+    std::vector<size_t> cstart{0};
+    long long acc = 0;
+    for (size_t ch = 0; ch < nch; ++ch) {
+      if (acc > 0 && (acc + cweight[ch] > room || (cap > 0 && (long long)(ch - cstart.back()) >= cap))) cstart.push_back(ch), acc = 0;
+      acc += cweight[ch];
+    }
+    cstart.push_back(nch);
+    struct ChainBytes { size_t cent, cstr, cbase, tasks, part, slots; size_t tab() const { return cent + cstr + cbase + tasks; } };
+    auto chain_bytes = [&](const size_t c0, const size_t c1) {
+      long long nt = 0, sl = 0;
+      for (size_t ch = c0; ch < c1; ++ch) nt += ctasks[ch], sl += 6ll * pmax[s0 + h_cent[ch]] * pmax[s0 + h_cent[ch]];
+      const size_t nc = c1 - c0;
+      return ChainBytes{al(nc * sizeof(int32_t)), al(nc * sizeof(int32_t)), al(nc * sizeof(int64_t)), al((size_t)nt * sizeof(int2)),
+                        al(nc * max_chunks * sizeof(double)), (size_t)sl * sizeof(double)};
+    };
+    size_t b_chain = 0;
+    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
+      const ChainBytes cbz = chain_bytes(cstart[cb], cstart[cb + 1]);
+      b_chain = std::max(b_chain, cbz.tab() + cbz.part + cbz.slots);
+    }
+    // one device buffer for the state batch: [tables | tasks | environments] then the chain batch's [tables | tasks | partials | slots]
+    const size_t b_states = al(nb * sizeof(int32_t)), b_pmax = al(nb * sizeof(int32_t)), b_sbase = al(nb * sizeof(int64_t));
+    const size_t b_roff = al(h_roff.size() * sizeof(int64_t)), b_tasks = al(tasks.size() * sizeof(int2));
+    const size_t b_tab = b_states + b_pmax + b_sbase + 2 * b_roff + b_tasks, b_env = al((size_t)tot * sizeof(double));
+    HIP_TRY_AS(what, c->local_scratch.ensure(b_tab + b_env + b_chain));
+    char* base = c->local_scratch.get<char>();
+    std::vector<char> stage(b_tab);
+    size_t at = 0;
+    auto put = [&](const void* src, size_t bytes, size_t span) {
+      std::memcpy(stage.data() + at, src, bytes);
+      const size_t here = at;
+      at += span;
+      return base + here;
+    };
+    LocArgs g{};
+    g.data = set->d_data.get<double>();
+    g.rev = rev.get<double>();
+    g.dims = set->d_dims.get<int32_t>();
+    g.tru = set->d_true.get<int32_t>();
+    g.offs = set->d_offs.get<int64_t>();
+    g.states = reinterpret_cast<const int32_t*>(put(h_states.data(), nb * sizeof(int32_t), b_states));
+    g.pmax = reinterpret_cast<const int32_t*>(put(h_pmax.data(), nb * sizeof(int32_t), b_pmax));
+    g.sbase = reinterpret_cast<const int64_t*>(put(h_sbase.data(), nb * sizeof(int64_t), b_sbase));
+    g.roff = reinterpret_cast<const int64_t*>(put(h_roff.data(), h_roff.size() * sizeof(int64_t), b_roff));
+    const int64_t* d_loff = reinterpret_cast<const int64_t*>(put(h_loff.data(), h_loff.size() * sizeof(int64_t), b_roff));
+    const int2* d_tasks = reinterpret_cast<const int2*>(put(tasks.data(), tasks.size() * sizeof(int2), b_tasks));
+    g.scratch = reinterpret_cast<double*>(base + b_tab);
+    g.rmul = LOC_RMUL;
+    g.max_dist = 1;
+    g.n_sites = n;
+    g.max_chunks = max_chunks;
+    HIP_TRY_AS(what, hipMemcpyAsync(base, stage.data(), b_tab, hipMemcpyHostToDevice, c->stream));
+    qk_local_reverse_kernel<<<dim3(nb, n), dim3(256), 0, c->stream>>>(g, rev.get<double>());
+    qk_local_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, nb);
+    qk_str_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, d_loff);
+    HIP_TRY_AS(what, hipGetLastError());
+    for (size_t li = 0; li < plan.size(); ++li) {
+      const int kind = plan[li].first;
+      g.tasks = d_tasks + first[li];
+      g.step = plan[li].second;
+      const long long grid = first[li + 1] - first[li];
+      if (grid <= 0) continue;
+      if (kind == LOC_REV_X || kind == LOC_FWD_W) qk_local_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
+      else if (kind >= 0) qk_local_gemm_kernel<false><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
+      else qk_str_lnext_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g, d_loff);
+    }
+    qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(g, nb, dnorm.get<double>());
+    HIP_TRY_AS(what, hipGetLastError());
+    StrArgs q{};
+    q.data = g.data, q.dims = g.dims, q.tru = g.tru, q.offs = g.offs;
+    q.states = g.states, q.pmax = g.pmax, q.sbase = g.sbase, q.roff = g.roff, q.loff = d_loff, q.env = g.scratch;
+    q.strings = dstr.get<uint8_t>();
+    q.supp = reinterpret_cast<const int32_t*>(dstr.get<char>() + b_str);
+    q.n_sites = n;
+    q.max_chunks = max_chunks;
+    char* const cbase0 = base + b_tab + b_env;
+    std::vector<char> cstage;
+    std::vector<int64_t> h_cbase;
+    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
+      const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
+      if (nc == 0) continue;
+      const ChainBytes cbz = chain_bytes(c0, c0 + nc);
+      h_cbase.resize(nc);
+      long long sl = 0;
+      for (size_t e = 0; e < nc; ++e) h_cbase[e] = sl, sl += 6ll * pmax[s0 + h_cent[c0 + e]] * pmax[s0 + h_cent[c0 + e]];
+      // task lists of every launch of the chain batch: per site the live chains' T blocks, Pauli chunks, X blocks and closing chunks
+      tasks.clear(), first.clear();
+      for (int k = 0; k < n; ++k)
+        for (const int kind : chain_kinds) {
+          first.push_back((long long)tasks.size());
+          for (size_t e = 0; e < nc; ++e) {
+            const int m = h_cstr[c0 + e];
+            if (k < supp[2 * m] || k > supp[2 * m + 1]) continue;
+            const int* p = &pad[(size_t)(s0 + h_cent[c0 + e]) * n1];
+            int nbk = 0;
+            switch (kind) {
+              case STR_T: nbk = (int)blocks64(p[k], 2ll * p[k + 1]); break;
+              case STR_X: nbk = (int)blocks64(p[k + 1], p[k + 1]); break;
+              case STR_PAULI: nbk = strings[(size_t)m * n + k] ? p[k] / LOC_CHUNK : 0; break;
+              default: nbk = (k == supp[2 * m + 1]) ? p[k + 1] / LOC_CHUNK : 0; break;  // STR_CLOSE
+            }
+            for (int b = 0; b < nbk; ++b) tasks.push_back(int2{(int)e, b});
+          }
+        }
+      first.push_back((long long)tasks.size());
+      cstage.resize(cbz.tab());
+      std::memcpy(cstage.data(), h_cent.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + cbz.cent, h_cstr.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + cbz.cent + cbz.cstr, h_cbase.data(), nc * sizeof(int64_t));
+      std::memcpy(cstage.data() + cbz.cent + cbz.cstr + cbz.cbase, tasks.data(), tasks.size() * sizeof(int2));
+      q.cent = reinterpret_cast<const int32_t*>(cbase0);
+      q.cstr = reinterpret_cast<const int32_t*>(cbase0 + cbz.cent);
+      q.cbase = reinterpret_cast<const int64_t*>(cbase0 + cbz.cent + cbz.cstr);
+      const int2* d_ctasks = reinterpret_cast<const int2*>(cbase0 + cbz.cent + cbz.cstr + cbz.cbase);
+      q.part = reinterpret_cast<double*>(cbase0 + cbz.tab());
+      q.slots = reinterpret_cast<double*>(cbase0 + cbz.tab() + cbz.part);
+      HIP_TRY_AS(what, hipMemcpyAsync(cbase0, cstage.data(), cbz.tab(), hipMemcpyHostToDevice, c->stream));
+      for (size_t li = 0; li + 1 < first.size(); ++li) {
+        const int kind = chain_kinds[li % 4];
+        q.tasks = d_ctasks + first[li];
+        q.step = (int)(li / 4);
+        const long long grid = first[li + 1] - first[li];
+        if (grid <= 0) continue;
+        if (kind == STR_T) qk_str_gemm_kernel<false><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(q);
+        else if (kind == STR_X) qk_str_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(q);
+        else if (kind == STR_PAULI) qk_str_pauli_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+        else qk_str_close_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+      }
+      qk_str_values_kernel<<<dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)nc, n_strings, dout.get<double>());
+      HIP_TRY_AS(what, hipGetLastError());
+      HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
+    }
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  }
+  HIP_TRY_AS(what, hipMemcpy(out, dout.get(), (size_t)ns * n_strings * sizeof(double), hipMemcpyDeviceToHost));
+  if (norms) HIP_TRY_AS(what, hipMemcpy(norms, dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+  for (int m = 0; m < n_strings; ++m)  // an all-identity string is exactly 1
+    if (supp[2 * m] < 0)
+      for (int s = 0; s < ns; ++s) out[(size_t)s * n_strings + m] = 1.0;
+  return QK_OK;
+}
+
 }  // namespace
+
+extern "C" int qk_pauli_strings_host(qk_ctx* c, const qk_mps_set* set, int32_t n_strings, const uint8_t* strings, double* out, double* norms) {
+  return pauli_strings(c, set, n_strings, strings, out, norms);
+}
+
+extern "C" int qk_feature_gram_host(qk_ctx* c, int32_t n_features, int32_t nx, const double* fx, int32_t ny, const double* fy, double g, double* out, int64_t ld) {
+  static const char* what = "qk_feature_gram_host";
+  if (n_features < 1) return qk_fail(QK_EINVAL, "%s: n_features must be >= 1 (got %d)", what, n_features);
+  return projected_gram(c, what, "qk:feature_gram", 1, 1, n_features, 1.0, nx, fx, ny, fy, g, out, ld);
+}
 
 extern "C" int qk_local_paulis_host(qk_ctx* c, const qk_mps_set* set, double* out, double* norms) {
   static const char* what = "qk_local_paulis_host";

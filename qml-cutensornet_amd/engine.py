@@ -100,6 +100,8 @@ _SIGNATURES = [
     ("qk_projected_pair_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_local_pair_paulis_dist_host", C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     ("qk_projected_pair_gram_dist_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
+    ("qk_pauli_strings_host", C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
+    ("qk_feature_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
@@ -223,6 +225,50 @@ def _pair_sites(n_pairs: int, max_dist: int):
         return None
     n, rem = divmod(int(n_pairs) + D * (D + 1) // 2, D)
     return n if rem == 0 and n >= D + 1 else None
+
+
+def pauli_strings(n_sites: int, specs) -> np.ndarray:
+    """Pauli strings as the uint8 code table (m, n_sites) of ``Context.pauli_expectations`` (0..3 = I, X, Y, Z on qubit k).  A spec
+    is a ``str`` of length ``n_sites`` over ``IXYZ`` (``"IZXXZI"``), a pair ``(paulis, qubits)`` with distinct qubits in range
+    (``("ZXZ", (3, 4, 5))``, identity elsewhere), or an integer row of ``n_sites`` codes; an integer array (m, n_sites) is a
+    list of rows.  Raises ``ValueError`` that names the offending spec otherwise."""
+    n = int(n_sites)
+    if n < 1:
+        raise ValueError(f"n_sites must be >= 1 (got {n_sites!r})")
+    if isinstance(specs, str) or (isinstance(specs, tuple) and len(specs) == 2 and isinstance(specs[0], str) and not isinstance(specs[1], str)):
+        raise ValueError(f"pauli_strings takes a list of specs, got the single spec {specs!r}")
+    letters = {"I": 0, "X": 1, "Y": 2, "Z": 3}
+    rows = []
+    for spec in specs:
+        bad = ValueError(f"bad Pauli string {spec!r}: want a str of length {n} over IXYZ, a pair (paulis, qubits) with distinct qubits "
+                         f"in 0 .. {n - 1}, or {n} integer codes 0..3")
+        row = np.zeros(n, dtype=np.uint8)
+        if isinstance(spec, str):
+            if len(spec) != n or any(ch not in letters for ch in spec):
+                raise bad
+            row[:] = [letters[ch] for ch in spec]
+        elif isinstance(spec, tuple) and len(spec) == 2 and isinstance(spec[0], str):
+            paulis, qubits = spec
+            try:
+                qubits = [int(q) for q in qubits]
+            except (TypeError, ValueError):
+                raise bad from None
+            if len(qubits) != len(paulis) or len(set(qubits)) != len(qubits) or any(ch not in letters for ch in paulis) or any(not 0 <= q < n for q in qubits):
+                raise bad
+            for ch, q in zip(paulis, qubits):
+                row[q] = letters[ch]
+        else:
+            try:
+                codes = np.asarray(spec)
+            except (TypeError, ValueError):
+                raise bad from None
+            if codes.dtype.kind not in "iu" or codes.shape != (n,) or codes.min() < 0 or codes.max() > 3:
+                raise bad
+            row[:] = codes
+        rows.append(row)
+    if not rows:
+        raise ValueError("the list of Pauli strings is empty")
+    return np.ascontiguousarray(np.stack(rows))
 
 
 def _dims_table(states) -> np.ndarray:
@@ -754,6 +800,37 @@ class Context:
         else:
             _check(lib().qk_projected_pair_gram_dist_host(self._h, n, D, nx, tx.ctypes.data, ny, None if ty is None else ty.ctypes.data, g,
                                                           out.ctypes.data, nx), "qk_projected_pair_gram_dist_host")
+        return out
+
+    def pauli_expectations(self, mps_set: MpsSet, strings, norms: bool = False):
+        """Expectation values <psi|P|psi> / <psi|psi> of Pauli strings for every state of an fp64 set: float64 of shape (n_states, m),
+        column j the j-th string; with ``norms=True`` also <psi|psi> of each state (the bits of ``local_paulis``), as ``(V, norms)``.
+        ``strings`` is anything ``pauli_strings(n_sites, ...)`` takes.  A string costs work on its support only; a value is the same
+        bits whatever the other states and strings of the call.  Synchronous."""
+        info = mps_set.info()
+        ns, n = info["n_states"], info["n_sites"]
+        S = pauli_strings(n, strings)
+        V = np.zeros((ns, S.shape[0]), dtype=np.float64)
+        nrm = np.zeros(ns, dtype=np.float64)
+        _check(lib().qk_pauli_strings_host(self._h, mps_set.handle, S.shape[0], S.ctypes.data, V.ctypes.data, nrm.ctypes.data), "qk_pauli_strings_host")
+        return (V, nrm) if norms else V
+
+    def feature_gram(self, fx, fy=None, gamma=None) -> np.ndarray:
+        """Gram of real feature columns (``pauli_expectations``): K[j, i] = exp(-gamma sum_m (fx[i, m] - fy[j, m])^2), shape (ny, nx),
+        rows = Y (or X).  ``gamma=None`` means 1 / n_features.  Synchronous."""
+        fx = np.ascontiguousarray(fx, dtype=np.float64)
+        if fx.ndim != 2 or fx.shape[1] < 1:
+            raise ValueError(f"features must have shape (n_states, n_features) with n_features >= 1, got {fx.shape}")
+        nx, m = fx.shape
+        g = projected_gamma(gamma, m)
+        if fy is not None:
+            fy = np.ascontiguousarray(fy, dtype=np.float64)
+            if fy.ndim != 2 or fy.shape[1] != m:
+                raise ValueError(f"Y features of shape {fy.shape} do not match X features of shape {fx.shape}")
+        ny = nx if fy is None else fy.shape[0]
+        out = np.zeros((ny, nx), dtype=np.float64)
+        _check(lib().qk_feature_gram_host(self._h, m, nx, fx.ctypes.data, ny, None if fy is None else fy.ctypes.data, g, out.ctypes.data, nx),
+               "qk_feature_gram_host")
         return out
 
     def stats(self) -> dict:

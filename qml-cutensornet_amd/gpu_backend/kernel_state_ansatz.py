@@ -399,7 +399,7 @@ def _gather_features(comm, lo, F, total):
     return out
 
 
-def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30, rdm=1, pair_distance=1):
+def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30, rdm=1, pair_distance=1, observables=None):
     """Projected quantum kernel (Huang et al., Nat. Commun. 12, 2631 (2021)) of the same states as ``build_kernel_matrix``:
         K[j, i] = exp(-g sum_k ||rho_k(X_i) - rho_k(Y_j)||_F^2) = exp(-g/2 sum_k |F(X_i)[k] - F(Y_j)[k]|^2),
     rho_k = the one-qubit reduced density matrix of qubit k, F[k] = its Bloch vector (<X_k>, <Y_k>, <Z_k>); ``Y=None`` means
@@ -415,7 +415,17 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     ``pair_distance=D`` (with ``rdm=2``, 1 <= D <= n_qubits - 1) compares every pair (k, k+d), d = 1 .. D, in the order of
     ``engine.pair_table(n_qubits, D)``: for an ansatz whose entanglement map reaches distance D these are the pairs its gates
     touch (D = max(abs(a - b)) over the map).  16 n_pairs reals per state are all-gathered, n_pairs = D n - D (D + 1) / 2, and
-    ``pqk_gamma=None`` means g = 1 / (n_qubits D)."""
+    ``pqk_gamma=None`` means g = 1 / (n_qubits D).
+
+    ``observables=[...]`` (Pauli strings, anything ``engine.pauli_strings(n_qubits, ...)`` takes) is the kernel on chosen observables,
+        K[j, i] = exp(-g sum_m (<O_m>(X_i) - <O_m>(Y_j))^2),
+    with ``pqk_gamma=None`` meaning g = 1 / len(observables): m reals per state are all-gathered.  It excludes ``rdm`` and
+    ``pair_distance`` (leave them at 1)."""
+    strings = None
+    if observables is not None:
+        if rdm != 1 or pair_distance != 1:
+            raise ValueError(f"observables chooses the features itself: leave rdm and pair_distance at 1 (got rdm={rdm!r}, pair_distance={pair_distance!r})")
+        strings = _engine.pauli_strings(int(ansatz.num_qubits), observables)  # ValueError: empty list, bad spec
     if rdm not in (1, 2):
         raise ValueError(f"rdm must be 1 (one-qubit reduced density matrices) or 2 (neighbouring pairs), got {rdm!r}")
     if rdm == 2 and int(ansatz.num_qubits) < 2:
@@ -467,9 +477,14 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         ctx.trim()  # the device builder's arena goes back before the local sweep needs memory
         t0 = time.perf_counter()
         if local is None:
-            F, chi = np.zeros((0, n_qubits, 3) if rdm == 1 else (0, n_pairs, 4, 4), dtype=np.float64), np.zeros(0)
+            shape = (0, len(strings)) if strings is not None else (0, n_qubits, 3) if rdm == 1 else (0, n_pairs, 4, 4)
+            F, chi = np.zeros(shape, dtype=np.float64), np.zeros(0)
         else:
-            F, chi = (ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local, max_dist=pair_distance)), local.dims.max(axis=1)
+            if strings is not None:
+                F = ctx.pauli_expectations(local, strings)
+            else:
+                F = ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local, max_dist=pair_distance)
+            chi = local.dims.max(axis=1)
             local.close()
         feat_secs += time.perf_counter() - t0
         shares.append((lo, F, len(points)))
@@ -481,10 +496,12 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     gather_secs = time.perf_counter() - t0
     if not is_root:
         return None
-    g = _engine.projected_gamma(pqk_gamma, n_qubits * pair_distance)
+    g = _engine.projected_gamma(pqk_gamma, len(strings) if strings is not None else n_qubits * pair_distance)
     _say(True, "\nFinished contracting all MPS.\n\nCalculating projected kernel matrix...")
     t0 = time.perf_counter()
-    if rdm == 1:
+    if strings is not None:
+        kernel_mat = ctx.feature_gram(feats[0], None if Y is None else feats[1], g)
+    elif rdm == 1:
         kernel_mat = ctx.projected_gram(feats[0], None if Y is None else feats[1], g)
     else:
         kernel_mat = ctx.projected_pair_gram(feats[0], None if Y is None else feats[1], g, max_dist=pair_distance)
@@ -503,7 +520,10 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     prof["ave max chi y"] = (float(chi_y.mean()) if chi_y.size else 0.0, "chi y")
     prof["r0_RR_recv"] = [gather_secs, "seconds"]  # the all-gather of the Bloch vectors
     prof["pqk_gamma"] = [g, ""]
-    prof["pqk_rdm"] = [rdm, "qubits"]
+    if strings is not None:
+        prof["pqk_observables"] = [len(strings), "strings"]
+    else:
+        prof["pqk_rdm"] = [rdm, "qubits"]
     if rdm == 2:
         prof["pqk_pair_distance"] = [pair_distance, "sites"]
     prof["pqk_features_time"] = [feat_secs, "seconds"]

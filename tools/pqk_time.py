@@ -4,7 +4,9 @@ device builder, then (each after a warm-up) ctx.gram(xs), ctx.local_paulis(xs), 
 ctx.local_pair_paulis(xs) and ctx.projected_pair_gram(T).  Prints one JSON line with the five times, the algorithmic flops of the
 two local sweeps and their achieved TFLOP/s.  ``--pair-distance D`` (D > 1) adds the pairs up to distance D:
 ctx.local_pair_paulis(xs, max_dist=D) and ctx.projected_pair_gram(T, max_dist=D), their times, flops and median entry.
-usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D]"""
+``--strings N`` (N sparse Pauli strings: weight 1..4 inside a window of 6 sites, seeded) or ``--strings-file F`` (one string over
+IXYZ per line) adds ctx.pauli_expectations(xs, strings) and ctx.feature_gram(V): pauli_strings_ms, n_strings, sum_support.
+usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F]"""
 import argparse
 import json
 import os
@@ -49,6 +51,17 @@ def dist_sweep_flops(dims, D):
     return total
 
 
+def sparse_strings(n, count, seed=0):
+    """``count`` sparse strings on n qubits: weight 1..4 inside a window of 6 sites at a random position, random codes X, Y, Z."""
+    rng = np.random.default_rng(seed)
+    S = np.zeros((count, n), dtype=np.uint8)
+    w = min(6, n)
+    for row in S:
+        sites = rng.integers(0, n - w + 1) + rng.choice(w, size=rng.integers(1, min(4, w) + 1), replace=False)
+        row[sites] = rng.integers(1, 4, size=len(sites))
+    return S
+
+
 def timed(fn, reps):
     fn()  # warm-up
     ts = []
@@ -65,6 +78,8 @@ def main():
     ap.add_argument("--gamma", type=float, default=None, help="default 1.0 (0.1 for cfg5)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--pair-distance", type=int, default=1, help="also time the pairs up to this distance (default 1: neighbours only)")
+    ap.add_argument("--strings", type=int, default=0, help="also time pauli_expectations on this many sparse Pauli strings")
+    ap.add_argument("--strings-file", default=None, help="also time pauli_expectations on the strings of this file (one per line over IXYZ)")
     args = ap.parse_args()
     gamma = args.gamma if args.gamma is not None else (0.1 if args.config == "cfg5" else 1.0)
     n, reps, d, npts = bench.CONFIGS[args.config]
@@ -97,6 +112,20 @@ def main():
             "dist_block_one_is_pair_bits": bool(np.array_equal(TD[:, : n - 1], T)),
             "median_offdiag_pqk2_dist": float(np.median(KPD[off])),
         }
+    if args.strings > 0 or args.strings_file:
+        if args.strings_file:
+            with open(args.strings_file) as fh:
+                S = engine.pauli_strings(n, [line.strip() for line in fh if line.strip()])
+        else:
+            S = sparse_strings(n, args.strings)
+        V, strings_ms = timed(lambda: ctx.pauli_expectations(xs, S), args.reps)
+        KO, fgram_ms = timed(lambda: ctx.feature_gram(V), args.reps)
+        support = [int(np.flatnonzero(c)[-1] - np.flatnonzero(c)[0] + 1) if c.any() else 0 for c in S]
+        dist.update({
+            "n_strings": int(len(S)), "sum_support": int(sum(support)), "pauli_strings_ms": round(strings_ms, 3),
+            "feature_gram_ms": round(fgram_ms, 3), "strings_over_local": round(strings_ms / local_ms, 4),
+            "median_offdiag_feature_K": float(np.median(KO[off])),
+        })
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
         "max_bond": int(info["dims"].max()), "build_s": round(build_s, 3),
