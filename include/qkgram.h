@@ -375,6 +375,39 @@ int qk_pauli_strings_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_strings,
 int qk_feature_gram_host(qk_ctx* ctx, int32_t n_features, int32_t nx, const double* fx /* [nx][n_features] */,
                          int32_t ny, const double* fy /* NULL: Y is X */, double g, double* out, int64_t ld);
 
+/* Entanglement across the bonds of every state of a set, synchronous on the context's stream.  The conventions above: site k =
+ * qubit k, states need not be normalised, environments in the sweep's X[ket][bra] orientation (L_0 = R_n = 1, L_n[0][0] =
+ * <psi|psi>).  Bond k, k = 1 .. n_sites - 1, cuts the chain between sites k-1 and k:
+ *     N_k      = R_k L_k^T / <psi|psi>           (plain transpose; chi_k x chi_k; tr N_k = 1)
+ *     lambda_k = the eigenvalues of N_k, descending, >= 0: the Schmidt weights of the cut, sum = 1
+ *     purity_k = tr(N_k^2) = sum_i lambda_k[i]^2
+ * N_k is not Hermitian but similar to one: with L_k^T = U S U^H and F = S^{1/2} U^H, H_k = F R_k F^H / <psi|psi> is Hermitian,
+ * positive semi-definite and has the eigenvalues of N_k.  The values are properties of the state: in exact arithmetic they do not
+ * change under a gauge change on any bond or a global factor.  As computed here the invariance holds to about 1e-15 cond(G)^2
+ * for a gauge matrix G on the bond: the environments are Gram matrices of the gauge, so every weight carries that absolute error
+ * and weights below it are rounding noise (cond = 1 for the builders' canonical forms; random Gaussian gauges of bond 64 reach
+ * 1e-11 .. 1e-8); negative noise is clipped to 0.
+ *
+ * qk_bond_purities_host: out[state][k - 1] = purity_k.  The environment pass of qk_pauli_strings_host (every L_k and R_k of a
+ * state, made once), then per bond one GEMM launch for all states (tasks (state, 64 x 64 block)) and one reduction launch in
+ * 16-row chunks, the chunk sums added in a fixed order.
+ * qk_bond_spectra_host: out[state][k - 1][i] = lambda_k[i] for i < min(chi_k, max_values), zero beyond the true bond; a bond of
+ * true dimension 1 has the single weight 1.0 exactly; max_values below a bond returns that bond's largest weights.  The same
+ * environment pass, then one workgroup per (state, bond) in one launch per state batch: L_k^T is factorised by the device builder's
+ * Jacobi primitive (in LDS below 48 columns, preconditioned block Jacobi on the f64 matrix cores from 48 on), H_k is formed by
+ * two workgroup GEMMs and its eigenvalues come from the same primitive.  A factorisation that does not converge is QK_EDEVICE.
+ * norms, when given, are the bits qk_local_paulis_host returns.  n_sites = 1 is valid (nothing is written to out).  A value is
+ * the same bits whatever the other states of the set, however the call was cut into batches, and from run to run.
+ * Device scratch: per state the sweep's planes and every L_k and R_k, for the spectra also a workspace of about 5 chi^2 complex
+ * numbers per resident workgroup (chi = the batch's largest bond); counted by the batching rule of qk_local_paulis_host (a quarter
+ * of the free memory; the states go in several batches when they do not fit) and released by qk_ctx_trim.
+ * QK_EINVAL: a null ctx, set or out; a set of another context; a complex64 set; max_values < 1; for the spectra a true bond above
+ * 512 (the factorisation's bookkeeping in LDS is reserved for that bond whatever the set holds, so that a state's path -- and its
+ * bits -- do not depend on the other bonds of its batch).                               */
+int qk_bond_purities_host(qk_ctx* ctx, const qk_mps_set* set, double* out /* [n_states][n_sites - 1] */, double* norms /* [n_states], may be NULL */);
+int qk_bond_spectra_host(qk_ctx* ctx, const qk_mps_set* set, int32_t max_values, double* out /* [n_states][n_sites - 1][max_values] */,
+                         double* norms /* [n_states], may be NULL */);
+
 /* ---- profiler ranges -----------------------------------------------------------------------------------------
  * roctx ranges (rocprofv3 --marker-trace) named "qk:build", "qk:upload", "qk:sweep", "qk:scatter", "qk:allgather_values",
  * "qk:allgather_sets" are opened by the library around its own phases -- the reference's MPI.Wtime() sites G:209-231

@@ -107,6 +107,106 @@ __global__ __launch_bounds__(256) void qk_pack_built_kernel(const cd* __restrict
 #undef QKB_NS
 #undef QK_BUILD_BT
 
+// ---- entanglement spectra of a bond (qk_bond_spectra_host, qk_local.hip) ------------------------------------------------------
+// One (state, bond k) per workgroup at a time, true bond q >= 2.  With the kept environments L_k, R_k (X[ket][bra] orientation,
+// split re/im planes of the padded bond) and nrm = L_n[0][0]:
+//   1. the true-bond corners become interleaved: A = L_k^T (Hermitian, positive semi-definite), Rm = R_k;
+//   2. A V = W by the builder's Jacobi primitive (jacobi_auto: in LDS below 48 columns, preconditioned block Jacobi on the matrix
+//      cores from 48 on): L_k^T = V S V^H with S = diag(sig);
+//   3. F = S^{1/2} V^H and H_k = F R_k F^H / nrm by two workgroup GEMMs on the matrix cores: Hermitian, the eigenvalues of
+//      N_k = R_k L_k^T / nrm;
+//   4. the same primitive on H_k: its singular values are the eigenvalues (>= 0 by construction), written in descending order.
+// The block path drops what lies below `cut` ||A||_F^2: the builder's 1e-22 would cost 1e-11 of a weight (oracle/jacobi_model.py:
+// 1.5e-12 on a graded 48 x 48 matrix); 1e-30 leaves rounding alone (3e-16 on the same matrix, one or two sweeps more).
+// The sweeps run until nothing is rotated (early = 0): step 3 needs L_k^T = V S V^H, and the builder's early exit leaves nearly
+// degenerate columns (L_k = 1 + 1e-11 of a device-built state) 1e-11 from orthogonal -- measured as 2e-11 on a weight of cfg4.
+constexpr double SPEC_CUT = 1e-30;
+constexpr size_t SPEC_LDS = 76 * 1024;
+// The LDS head (sig and ord) is reserved for the largest bond the entry point takes, whatever the batch holds: what is left for the
+// Jacobi working set decides the path of a factorisation (LDS below 48 columns: 94 x 47 = 4418 elements) and the width of a
+// Gram-Schmidt panel, and a state's bits must not depend on the other bonds of its batch.
+constexpr int SPEC_QMAX = 512;
+inline int spec_pad(int x, int m) { return (x + m - 1) / m * m; }
+constexpr int SPEC_HEAD_DOUBLES = ((SPEC_QMAX * 12 + 15) / 16) * 2 + 2;  // sig and ord, 16-byte aligned
+constexpr int SPEC_LDS_ELEMS = (int)((SPEC_LDS - SPEC_HEAD_DOUBLES * sizeof(double)) / (2 * sizeof(double)));
+static_assert(SPEC_LDS_ELEMS >= 94 * 47, "a 47-column factorisation must fit the LDS working set");
+inline long spec_lbuf_elems(int q) { return (long)spec_pad(q, 32) * spec_pad(q, 16); }
+
+__global__ __launch_bounds__(256, 2) void qk_bond_spectra_kernel(const QkSpectraArgs g, const long lbuf_elems) {
+  using namespace qkb256;
+  extern __shared__ double sh_raw[];
+  __shared__ WgShared sh;
+  const int tid = threadIdx.x, n = g.n_sites, n1 = n + 1;
+  const long Q2 = (long)g.qmax * g.qmax;
+  double* const sig = sh_raw;
+  int* const ord = reinterpret_cast<int*>(sig + SPEC_QMAX);
+  cd* const lds = reinterpret_cast<cd*>(sh_raw + SPEC_HEAD_DOUBLES);
+  constexpr int lds_elems = SPEC_LDS_ELEMS;
+  cd* const A = reinterpret_cast<cd*>(g.work + (long long)blockIdx.x * g.work_bytes);
+  cd* const V = A + Q2;
+  cd* const Rm = V + Q2;
+  cd* const S = Rm + Q2;
+  cd* const LB = S + Q2;  // the block layout of the preconditioned path, the table of clean block pairs behind it
+  for (int t = blockIdx.x; t < g.n_tasks; t += gridDim.x) {
+    const int i = g.tasks[t].x, k = g.tasks[t].y;
+    const long long st = g.states[i];
+    const int q = g.tru[st * n1 + k], pk = g.dims[st * n1 + k];
+    const long long P = g.pmax[i], P2 = P * P;
+    const double* const E = g.env + g.sbase[i];
+    const double nrm = E[0];  // L_n[0][0]
+    const double* const Lre = E + g.rmul * P2 + g.loff[(long long)i * n1 + k];
+    const double* const Rre = E + g.rmul * P2 + g.roff[(long long)i * n1 + k];
+    const long long pl = (long long)pk * pk;
+    for (int e = tid; e < q * q; e += 256) {
+      const int a = e / q, b = e - a * q;
+      A[e] = cd{Lre[(long long)b * pk + a], Lre[pl + (long long)b * pk + a]};
+      Rm[e] = cd{Rre[(long long)a * pk + b], Rre[pl + (long long)a * pk + b]};
+    }
+    __syncthreads();
+    for (int pass = 0; pass < 2; ++pass) {
+      jacobi_auto<2>(A, q, 1, q, q, V, sig, ord, &sh, g.error, lds, lds_elems, S, LB, lbuf_elems, SPEC_CUT, 0.0);
+      __syncthreads();
+      if (pass == 0) {
+        wg_gemm_mfma(S, q, q, q, Rm, q, 1, V, q, 1);  // R V
+        for (int e = tid; e < q * q; e += 256) {
+          const int j = e / q, a = e - j * q;
+          const cd v = V[(long)a * q + j];
+          const double f = sqrt(sig[j]);
+          Rm[e] = cd{f * v.x, -f * v.y};  // F[j][a] = sqrt(s_j) conj(V[a][j])
+        }
+        for (int e = tid; e < q * q; e += 256) {
+          const double f = sqrt(sig[e % q]) / nrm;
+          S[e] = cd{S[e].x * f, S[e].y * f};  // R V S^{1/2} / nrm
+        }
+        __syncthreads();
+        wg_gemm_mfma(A, q, q, q, Rm, q, 1, S, q, 1);  // H_k
+      }
+    }
+    double* const o = g.out + (st * (n - 1) + (k - 1)) * g.max_values;
+    for (int e = tid; e < min(q, g.max_values); e += 256) o[e] = sig[ord[e]];
+    __syncthreads();
+  }
+}
+
+size_t qk_bond_spectra_work_bytes(const int qmax) {
+  const size_t q2 = (size_t)qmax * qmax, nbk = (size_t)spec_pad(qmax, 16) / 8;
+  return ((4 * q2 + (size_t)spec_lbuf_elems(qmax)) * sizeof(cd) + nbk * nbk * sizeof(int) + 255) / 256 * 256;
+}
+
+int qk_bond_spectra_launch(qk_ctx* c, QkSpectraArgs a, const int grid, const char* what) {
+  static_assert(SPEC_LDS_ELEMS >= qkb256::NWV * qkb256::BLK_LDS, "the block Jacobi's LDS matrices must fit");
+  if (a.qmax > SPEC_QMAX) return qk_fail(QK_EINVAL, "%s: a bond of %d is beyond the %d the factorisation's LDS bookkeeping holds", what, a.qmax, SPEC_QMAX);
+  HIP_TRY_AS(what, hipMemsetAsync(a.error, 0, 32 * sizeof(int), c->stream));
+  HIP_TRY_AS(what, hipFuncSetAttribute(reinterpret_cast<const void*>(qk_bond_spectra_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS));
+  qk_bond_spectra_kernel<<<dim3((unsigned)grid), dim3(256), SPEC_LDS, c->stream>>>(a, spec_lbuf_elems(a.qmax));
+  HIP_TRY_AS(what, hipGetLastError());
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  int errv[32] = {0};
+  HIP_TRY_AS(what, hipMemcpy(errv, a.error, sizeof errv, hipMemcpyDeviceToHost));
+  if (errv[0]) return qk_fail(QK_EDEVICE, "%s: a Jacobi factorisation did not converge in %d sweeps", what, MAX_SWEEPS);
+  return QK_OK;
+}
+
 struct qk_built {
   qk_ctx* ctx = nullptr;
   int n_states = 0, n_qubits = 0;

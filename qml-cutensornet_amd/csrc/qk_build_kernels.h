@@ -40,7 +40,7 @@ typedef __attribute__((address_space(3))) cd* lds_cd_ptr;  // LDS-typed: ds_read
 // once and the rotation does not read the columns a second time; R = 0 is the general loop.
 template <typename P, int R = 0>  // P = cd* (L2-resident workspace) or lds_cd_ptr
 __device__ void jacobi_orth(P A, const long rs, const long cs, const int p, const int q, P V, const int vrs, const int vcs,
-                            double* sig, int* ord, WgShared* sh, int* error, const bool init_v = true) {
+                            double* sig, int* ord, WgShared* sh, int* error, const bool init_v = true, const double early = 1e-20) {
   const int tid = threadIdx.x, gl = tid % GL;
 #ifdef QK_BUILD_SPREAD  // consecutive pairs go to different wavefronts
   const int grp = ((tid % 64) / GL) * (BT / 64) + tid / 64;
@@ -177,8 +177,11 @@ __device__ void jacobi_orth(P A, const long rs, const long cs, const int p, cons
       const double worst = __longlong_as_double((long long)sh->worst);
       __syncthreads();
       // done when nothing was rotated -- or only pairs that were already orthogonal to 1e-10: a rotation leaves a residue
-      // of the order of the square of what it removed, far below the test, so the checking sweep can be skipped
-      if (!f || worst <= 1e-20) {
+      // of the order of the square of what it removed, far below the test, so the checking sweep can be skipped -- for small
+      // rotation angles: columns of nearly equal norm (A = 1 + 1e-11 noise) turn by angles of order one and end the sweep as far
+      // from orthogonal as they began, which costs a caller that needs A = V S V^H, not only singular values, 1e-11; such a
+      // caller passes early = 0 and the sweeps end when nothing was rotated
+      if (!f || worst <= early) {
         done = true;
         ++sweep;
         break;
@@ -542,7 +545,7 @@ __device__ __forceinline__ bool blk_visit(cd* __restrict__ AB, const long astrid
 // blocks' last change is still clean -- in the last sweeps that is most of them, and the visit's Gram product is saved too.
 constexpr int BLK_NB_MAX = 160;  // blocks of 8 columns: bonds up to 640 on the factorised side
 __device__ void blk_sweeps(cd* AB, const long astride, const int arows, cd* VB, const long vstride, const int vrows, const int ncols, const double tol2, const double floor2, WgShared* sh, cd* lds,
-                           int* error, int* chk) {
+                           int* error, int* chk, const double early = 1e-20) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nb = ncols / NBC, nr = nb - 1, half = nb / 2;  // nb is even
@@ -595,7 +598,7 @@ __device__ void blk_sweeps(cd* AB, const long astride, const int arows, cd* VB, 
     const int f = sh->flag;
     const double worst_all = __longlong_as_double((long long)sh->worst);
     __syncthreads();
-    if (!f || worst_all <= 1e-20) {
+    if (!f || worst_all <= early) {
       done = true;
       ++sweep;
       break;
@@ -759,13 +762,15 @@ __device__ void mgs_panels(cd* S, const int p, const int q, const int nbp, const
 //      L = R^H is written straight into the block layout (q rows, column k in block k / 8);
 //   3. the columns of L (rows of R) with squared norm below CUT ||A||_F^2 are dropped: six orders of magnitude below the
 //      truncation budget (they would perturb the smallest kept singular value by 1e-6 of itself), and what is left has full
-//      numerical rank, so the rotation test below is purely relative;
+//      numerical rank, so the rotation test below is purely relative (`cut`: the builder's PRECOND_CUT; the bond spectra
+//      (qk_bond_spectra_kernel) need singular values to 1e-13 ||A|| and pass 1e-30);
 //   4. block Jacobi on L (q x r): 6-8 sweeps -- L's columns are nearly orthogonal already -- WITHOUT accumulating rotations;
 //   5. L V_L = U_L Sigma: the right singular vectors of A are V = (normalised columns of L V_L), rows back in A's column order,
 //      and W = A V (one product on the original A).
 // S: p x q complex scratch (column-major), LB: pad32(q) x pad16(q) complex (block layout), lds: NWV * BLK_LDS complex.
 template <int MINWG>  // (instantiated for the two-workgroups-per-CU kernel only: 256 VGPRs, 76 KiB of LDS)
-__device__ __noinline__ void jacobi_precond(cd* A, const long rs, const long cs, const int p, const int q, cd* V, double* sig, int* ord, WgShared* sh, int* error, cd* lds, const int lds_elems, cd* S, cd* LB, int* chk) {
+__device__ __noinline__ void jacobi_precond(cd* A, const long rs, const long cs, const int p, const int q, cd* V, double* sig, int* ord, WgShared* sh, int* error, cd* lds, const int lds_elems, cd* S, cd* LB, int* chk,
+                                          const double cut = PRECOND_CUT, const double early = 1e-20) {
   const int tid = threadIdx.x, gl = tid % GL, grp = tid / GL, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lrows = pad_to(q, 32), qpad = pad_to(q, 16);
@@ -827,7 +832,7 @@ __device__ __noinline__ void jacobi_precond(cd* A, const long rs, const long cs,
   if (tid == 0) {
     int rk = 1;
     for (int c = 0; c < q; ++c)
-      if (sig[c] > PRECOND_CUT * frob) rk = c + 1;
+      if (sig[c] > cut * frob) rk = c + 1;
     sh->keep = rk;
   }
   __syncthreads();
@@ -835,7 +840,7 @@ __device__ __noinline__ void jacobi_precond(cd* A, const long rs, const long cs,
   __syncthreads();
   // (columns rk .. rpad - 1 of L take part in the sweeps as they are: at most 15 columns below the cut)
   // ---- 4. block Jacobi on L, rotations not accumulated
-  if (rpad >= 16) blk_sweeps(LB, lstride, lrows, nullptr, 0, 0, rpad, 1e-29 * (double)max(q, 10), PRECOND_CUT * frob, sh, lds, error, chk);
+  if (rpad >= 16) blk_sweeps(LB, lstride, lrows, nullptr, 0, 0, rpad, 1e-29 * (double)max(q, 10), cut * frob, sh, lds, error, chk, early);
   const long long t_sweeps = wall_clock64();
   // ---- 5. sig, V = normalised columns of L V_L with the rows back in A's column order, W = A V
   for (int c = grp; c < q; c += NG) {
@@ -921,14 +926,14 @@ __device__ void mgs2_qr(const cd* A, const long rs, const long cs, const int p, 
 constexpr int g_precond_from = 48;  // columns from which a factorisation takes the preconditioned block path
 template <int MINWG>
 __device__ __forceinline__ void jacobi_auto(cd* A, const long rs, const long cs, const int p, const int q, cd* V, double* sig, int* ord, WgShared* sh,
-                                            int* error, cd* lds, const int lds_elems, cd* scratch, cd* lbuf, const long lbuf_elems) {
+                                            int* error, cd* lds, const int lds_elems, cd* scratch, cd* lbuf, const long lbuf_elems, const double cut = PRECOND_CUT, const double early = 1e-20) {
   const int ld = q | 1;
   // from 48 columns on the preconditioned block factorisation is the faster one even where the scalar one would fit the LDS
   // (a graded 78 x 66 theta: 0.9 against 1.8 ms; 64 x 48: equal)
   const bool blocked = MINWG <= 2 && lbuf && q >= g_precond_from && p <= 64 * MGS_R && lds_elems >= NWV * BLK_LDS;
   if (threadIdx.x == 0) atomicAdd(error + ((!blocked && (long)(p + q) * ld <= lds_elems) ? 5 : 6), 1);  // statistics: scalar in LDS / the rest
   if (blocked) {
-    if constexpr (MINWG <= 2) jacobi_precond<MINWG>(A, rs, cs, p, q, V, sig, ord, sh, error, lds, lds_elems, scratch, lbuf, reinterpret_cast<int*>(lbuf + lbuf_elems));
+    if constexpr (MINWG <= 2) jacobi_precond<MINWG>(A, rs, cs, p, q, V, sig, ord, sh, error, lds, lds_elems, scratch, lbuf, reinterpret_cast<int*>(lbuf + lbuf_elems), cut, early);
   } else if ((long)(p + q) * ld <= lds_elems) {
     cd* LA = lds;
     cd* LV = lds + (long)p * ld;
@@ -969,12 +974,12 @@ __device__ __forceinline__ void jacobi_auto(cd* A, const long rs, const long cs,
       const lds_cd_ptr la = (lds_cd_ptr)LA, lv = (lds_cd_ptr)LV;
       const int rows = (max(p, q) + GL - 1) / GL;  // rows of a column per lane
 #ifndef QK_BUILD_NO_REGS
-      if (rows <= 2) jacobi_orth<lds_cd_ptr, 2>(la, ld, 1, p, q, lv, ld, 1, sig, ord, sh, error, false);
-      else if (rows <= 4) jacobi_orth<lds_cd_ptr, 4>(la, ld, 1, p, q, lv, ld, 1, sig, ord, sh, error, false);
-      else if (MINWG <= 2 && rows <= 8) jacobi_orth<lds_cd_ptr, (MINWG <= 2 ? 8 : 4)>(la, ld, 1, p, q, lv, ld, 1, sig, ord, sh, error, false);
+      if (rows <= 2) jacobi_orth<lds_cd_ptr, 2>(la, ld, 1, p, q, lv, ld, 1, sig, ord, sh, error, false, early);
+      else if (rows <= 4) jacobi_orth<lds_cd_ptr, 4>(la, ld, 1, p, q, lv, ld, 1, sig, ord, sh, error, false, early);
+      else if (MINWG <= 2 && rows <= 8) jacobi_orth<lds_cd_ptr, (MINWG <= 2 ? 8 : 4)>(la, ld, 1, p, q, lv, ld, 1, sig, ord, sh, error, false, early);
       else
 #endif
-        jacobi_orth<lds_cd_ptr, 0>(la, ld, 1, p, q, lv, ld, 1, sig, ord, sh, error, false);
+        jacobi_orth<lds_cd_ptr, 0>(la, ld, 1, p, q, lv, ld, 1, sig, ord, sh, error, false, early);
     }
 #else
     for (int e = threadIdx.x; e < p * q; e += BT) {
@@ -1007,7 +1012,7 @@ __device__ __forceinline__ void jacobi_auto(cd* A, const long rs, const long cs,
       __syncthreads();
       S = scratch, srs = 1, scs = p;
     }
-    jacobi_orth(S, srs, scs, p, q, V, 1, q, sig, ord, sh, error);
+    jacobi_orth(S, srs, scs, p, q, V, 1, q, sig, ord, sh, error, true, early);
     if (rs != 1) {
       for (int e = threadIdx.x; e < p * q; e += BT) {
         const int i = e / q, jc = e - i * q;

@@ -1,6 +1,6 @@
 // qk_host.h -- host-side state shared by the translation units:
 //   qkgram.hip    the C ABI, the planner and the shipped sweep kernels      } libqkgram.so
-//   qk_build.hip  the device MPS builder                                    }
+//   qk_build.hip  the device MPS builder, the bond spectra's factorisation  }
 //   qk_local.hip  local Bloch vectors and the projected-kernel Gram          }
 //   qk_comm.hip   the multi-GPU entry points                                 }
 //   qk_lab.hip    experimental / diagnostic kernels for A/B measurements: only in lab/libqklab.so (-DQK_LAB, lab/tools)
@@ -90,6 +90,30 @@ struct qk_mps_set {
 // the one allocator of a set (qkgram.hip): the object and its four device arrays (d_data of `data_bytes`, d_dims, d_true, d_offs),
 // nothing uploaded.  `who` names the entry point in the error text.  A constructor that fails later calls qk_mps_set_destroy.
 int qk_mps_set_alloc(qk_ctx* c, int n_states, int n_sites, int64_t data_bytes, int precision, qk_mps_set** out, const char* who);
+
+// the bond spectra (qk_local.hip makes the environments, qk_build.hip owns the factorisation primitive): the (state, bond) tasks of a
+// state batch, taken in turn by `grid` workgroups with one workspace each
+struct QkSpectraArgs {
+  const double* env;      // the batch's environments (qk_local.hip: LocArgs.scratch) and its tables
+  const int32_t* dims;    // padded bonds [n_states][n_sites + 1]
+  const int32_t* tru;     // true bonds
+  const int32_t* states;  // batch entry -> state of the set
+  const int32_t* pmax;    // batch entry -> P
+  const int64_t* sbase;   // batch entry -> first double of its environments
+  const int64_t* roff;    // [batch][n_sites + 1]: R_k at sbase + rmul P^2 + roff[k]
+  const int64_t* loff;    // likewise L_k
+  const int2* tasks;      // (batch entry, bond k), true bond >= 2
+  int n_tasks;
+  char* work;             // workgroup w: work + w * work_bytes
+  long long work_bytes;
+  int qmax;               // largest true bond of the tasks
+  double* out;            // [n_states][n_sites - 1][max_values], zero-filled
+  int n_sites, max_values, rmul;
+  int* error;             // 32 ints of the caller, zeroed by the launcher: [0] error bits, then the Jacobi statistics
+};
+size_t qk_bond_spectra_work_bytes(int qmax);
+// launches, waits and turns a factorisation that did not converge into QK_EDEVICE
+int qk_bond_spectra_launch(qk_ctx* c, QkSpectraArgs a, int grid, const char* what);
 
 struct SweepArgs;
 // qk_lab.hip: raise the LDS limit of the lab kernels; launch lab variant `variant` (returns QK_EINVAL if it is not one)

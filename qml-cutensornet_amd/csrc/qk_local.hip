@@ -3,7 +3,8 @@
 // libqkgram.so; entry points qk_local_paulis_host, qk_projected_gram_host, qk_local_pair_paulis_host,
 // qk_projected_pair_gram_host and their forms for pairs up to a chosen distance, qk_local_pair_paulis_dist_host and
 // qk_projected_pair_gram_dist_host, and the general form, expectation values of Pauli strings and the Gram of any feature columns,
-// qk_pauli_strings_host and qk_feature_gram_host (include/qkgram.h).
+// qk_pauli_strings_host and qk_feature_gram_host, and the entanglement across every bond of a state from the same environments,
+// qk_bond_purities_host and qk_bond_spectra_host (definitions above bond_call below) (include/qkgram.h).
 //
 // Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
 // normalised):
@@ -96,10 +97,12 @@ enum LocKind : int {
   LOC_PAIR_V = 5,  // pair sweep: V_{o,t} = T'[(., t)]^T conj(Ar_o), both t in one launch
   LOC_DIST_T = 6,  // distant pairs, site k: T''_(o,s,s') = E_{o->k}[s][s']^T A_k for every live origin o, in one launch
   LOC_DIST_X = 7,  // distant pairs: E_{o->k+1}[s][s'] = T''_(o,s,s')^T conj(A_k) over K = (a, u), back into the origin's slot
+  LOC_BOND_M = 8,  // bond purities: M_k = L_k^T R_k (= N_k^H) of bond k = step, from the kept environments into the T planes
   LOC_RHO = -1,    // qk_local_rho_kernel
   LOC_PAIR_RHO = -2,  // qk_local_pair_rho_kernel<false>
   LOC_DIST_RHO = -3,  // qk_local_pair_rho_kernel<true>: rho_{o,k+1} of every live origin from its window slot
   LOC_ADMIT = -4,  // qk_local_admit_kernel: W_k into the window
+  LOC_BOND_TR = -5,  // qk_bond_trace_kernel: tr(M_k^2) of bond k = step in 16-row chunks
 };
 
 // Per-state scratch (doubles, every matrix as a re plane then an im plane), P = the state's largest padded bond:
@@ -120,6 +123,7 @@ struct LocArgs {
   const int32_t* pmax;    // batch entry -> P
   const int64_t* sbase;   // batch entry -> first double of its scratch
   const int64_t* roff;    // [batch][n_sites + 1]: R_k at sbase + rmul P^2 + roff[k]
+  const int64_t* loff;    // environment pass (env_run): the kept L_k at sbase + LOC_RMUL P^2 + loff[k]; NULL in the local sweeps
   const int2* tasks;      // this launch: (batch entry, block)
   double* scratch;
   double* part;           // rho partial sums [batch][n_sites][max chunks][4]
@@ -157,7 +161,16 @@ __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, con
   const double *Are, *Aim, *Bre, *Bim;
   double *Cre, *Cim;
   int lda, ldb, ldc, M, N, K;
-  if (kind == LOC_REV_T || kind == LOC_REV_X || kind == LOC_PAIR_T || kind == LOC_PAIR_V) {
+  if (kind == LOC_BOND_M) {  // M_k[a][a'] = sum_b L_k[b][a] R_k[b][a'] over the true bond
+    const int k = g.step;
+    const int pk = __builtin_amdgcn_readfirstlane(pd[k]);
+    Are = S + g.rmul * P2 + uni64(g.loff[(long long)i * n1 + k]);
+    Aim = Are + (long long)pk * pk;
+    Bre = S + g.rmul * P2 + uni64(g.roff[(long long)i * n1 + k]);
+    Bim = Bre + (long long)pk * pk;
+    Cre = Tre, Cim = Tre + tpl;
+    lda = pk, ldb = pk, ldc = pk, M = pk, N = pk, K = __builtin_amdgcn_readfirstlane(td[k]);
+  } else if (kind == LOC_REV_T || kind == LOC_REV_X || kind == LOC_PAIR_T || kind == LOC_PAIR_V) {
     const int o = (kind == LOC_REV_T || kind == LOC_REV_X) ? n - 1 - g.step : g.step + 1;
     const int al = __builtin_amdgcn_readfirstlane(pd[o + 1]), ar = __builtin_amdgcn_readfirstlane(pd[o]);
     const int at = __builtin_amdgcn_readfirstlane(td[o + 1]);
@@ -847,6 +860,193 @@ __global__ __launch_bounds__(256) void qk_str_values_kernel(const StrArgs g, con
   out[st * n_strings + m] = v / g.env[g.sbase[i]];
 }
 
+// tr(M_k^2) = sum_{a, a'} M_k[a][a'] M_k[a'][a] over one 16-row chunk of a (the imaginary parts cancel between (a, a') and its
+// image, so only Re is summed), unnormalised: part[(i, k, chunk)].  M_k is in the T planes, ld = the padded bond.
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_bond_trace_kernel(const LocArgs g) {
+  __shared__ double red[LOC_RED_THREADS];
+  const int2 t = g.tasks[blockIdx.x];
+  const int i = t.x, c = t.y;
+  const int n = g.n_sites, n1 = n + 1, k = g.step;
+  const long long st = g.states[i];
+  const int pk = g.dims[st * n1 + k];
+  const long long P = g.pmax[i], P2 = P * P;
+  const double* const Mre = g.scratch + g.sbase[i] + 2 * P2;
+  const double* const Mim = Mre + 2 * P2;
+  double acc = 0;
+  const int cnt = LOC_CHUNK * pk;
+  for (int e = threadIdx.x; e < cnt; e += LOC_RED_THREADS) {
+    const int a = c * LOC_CHUNK + e / pk, ap = e % pk;
+    const long long q = (long long)a * pk + ap, qt = (long long)ap * pk + a;
+    acc += Mre[q] * Mre[qt] - Mim[q] * Mim[qt];
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int h = LOC_RED_THREADS / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) g.part[((long long)i * n + k) * g.max_chunks + c] = red[0];
+}
+
+// Purities of a state batch: the chunk sums of each (state, bond) in a fixed order, divided by L_n[0][0]^2.
+__global__ __launch_bounds__(256) void qk_bond_purities_kernel(const LocArgs g, const int nb, double* out) {
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int n = g.n_sites, n1 = n + 1;
+  if (id >= (long long)nb * (n - 1)) return;
+  const int i = (int)(id / (n - 1)), k = 1 + (int)(id % (n - 1));
+  const long long st = g.states[i];
+  const double nrm = g.scratch[g.sbase[i]];  // L_n[0][0]
+  const int chunks = g.dims[st * n1 + k] / LOC_CHUNK;
+  const double* p = g.part + ((long long)i * n + k) * g.max_chunks;
+  double v = 0;
+  for (int c = 0; c < chunks; ++c) v += p[c];
+  out[st * (n - 1) + k - 1] = v / (nrm * nrm);
+}
+
+// ---- the environment pass, shared by qk_pauli_strings_host and the bond entry points -----------------------------------------
+// Per state batch: the reversed chain and the forward T / W launches of the one-qubit sweep, then L_{k+1} from W by the sum the rho
+// kernel makes (so L_n[0][0] is that sweep's norm bit for bit); every R_k (k = 1 .. n) and every L_k (k = 0 .. n-1) is kept.
+struct EnvSizes {
+  std::vector<int32_t> pad;     // padded bonds [n_states][n_sites + 1]
+  std::vector<int> pmax;        // P of each state
+  std::vector<long long> need;  // environment doubles of each state: the sweep's planes, R_1 .. R_n, L_0 .. L_{n-1}
+  int max_chunks = 0;
+};
+void env_sizes(const qk_mps_set* set, EnvSizes& z) {
+  const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
+  const int32_t* tru = set->dims_true.data();
+  z.pad.resize((size_t)ns * n1), z.pmax.resize(ns), z.need.resize(ns);
+  for (int s = 0; s < ns; ++s) {
+    int p = 16;
+    long long esum = 0;
+    for (int k = 0; k <= n; ++k) {
+      const int d = z.pad[(size_t)s * n1 + k] = pad16h(tru[(size_t)s * n1 + k]);
+      p = std::max(p, d);
+      esum += (k >= 1 ? 2ll * d * d : 0) + (k < n ? 2ll * d * d : 0);
+    }
+    z.pmax[s] = p;
+    z.need[s] = (long long)LOC_RMUL * p * p + esum;
+  }
+  z.max_chunks = set->max_pad / LOC_CHUNK;
+}
+// the launches of the environment pass, in stream order: the reversed chain as in local_sweep, then per site forward T / W and L_{k+1}
+std::vector<std::pair<int, int>> env_plan(const int n) {
+  std::vector<std::pair<int, int>> plan;  // (kind, step)
+  for (int j = 0; j < n - 1; ++j) plan.push_back({LOC_REV_T, j}), plan.push_back({LOC_REV_X, j});
+  for (int k = 0; k < n; ++k) plan.push_back({LOC_FWD_T, k}), plan.push_back({LOC_FWD_W, k}), plan.push_back({STR_LNEXT, k});
+  return plan;
+}
+struct EnvBatch {
+  int s0 = 0, nb = 0;
+  long long tot = 0;  // environment doubles of the batch
+  std::vector<int32_t> h_states, h_pmax;
+  std::vector<int64_t> h_sbase, h_roff, h_loff;
+  std::vector<int2> tasks;
+  std::vector<long long> first;
+  std::vector<char> stage;  // host image of the tables: alive until the stream has taken it (the caller synchronises per batch)
+  size_t b_states = 0, b_pmax = 0, b_sbase = 0, b_roff = 0, b_tasks = 0, b_part = 0, b_tab = 0, b_env = 0;
+  LocArgs g{};
+  char* base = nullptr;  // the batch's device buffer: [tables | tasks | partial sums | environments | `extra` bytes of the caller]
+  size_t used() const { return b_tab + b_part + b_env; }
+};
+inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+// host tables and task lists of the states [s0, s0 + nb) for `plan` (the environment pass, then what the caller appended)
+void env_tables(const qk_mps_set* set, const EnvSizes& z, const std::vector<std::pair<int, int>>& plan, const int s0, const int nb, const long long part_per_state, EnvBatch& eb) {
+  const int n = set->n_sites, n1 = n + 1;
+  eb.s0 = s0, eb.nb = nb, eb.tot = 0;
+  eb.h_states.resize(nb), eb.h_pmax.resize(nb), eb.h_sbase.resize(nb), eb.h_roff.resize((size_t)nb * n1), eb.h_loff.resize((size_t)nb * n1);
+  for (int i = 0; i < nb; ++i) {
+    const int s = s0 + i;
+    eb.h_states[i] = s, eb.h_pmax[i] = z.pmax[s], eb.h_sbase[i] = eb.tot;
+    long long ro = 0;
+    for (int k = 0; k <= n; ++k) {
+      eb.h_roff[(size_t)i * n1 + k] = ro;
+      if (k >= 1) ro += 2ll * z.pad[(size_t)s * n1 + k] * z.pad[(size_t)s * n1 + k];
+    }
+    for (int k = 0; k <= n; ++k) {  // the L_k behind the R_k
+      eb.h_loff[(size_t)i * n1 + k] = ro;
+      ro += 2ll * z.pad[(size_t)s * n1 + k] * z.pad[(size_t)s * n1 + k];
+    }
+    eb.tot += z.need[s];
+  }
+  eb.tasks.clear(), eb.first.clear();
+  for (const auto& [kind, step] : plan) {
+    eb.first.push_back((long long)eb.tasks.size());
+    for (int i = 0; i < nb; ++i) {
+      const int* p = &z.pad[(size_t)(s0 + i) * n1];
+      const int o = n - 1 - step, k = step;
+      int nbk = 0;
+      switch (kind) {
+        case LOC_REV_T: nbk = (int)blocks64(p[o + 1], 2ll * p[o]); break;
+        case LOC_REV_X: nbk = (int)blocks64(p[o], p[o]); break;
+        case LOC_FWD_T: nbk = (int)blocks64(p[k], 2ll * p[k + 1]); break;
+        case LOC_FWD_W: nbk = (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); break;
+        case LOC_BOND_M: nbk = (int)blocks64(p[k], p[k]); break;
+        case LOC_BOND_TR: nbk = p[k] / LOC_CHUNK; break;
+        default: nbk = p[k + 1] / LOC_CHUNK; break;  // STR_LNEXT
+      }
+      for (int b = 0; b < nbk; ++b) eb.tasks.push_back(int2{i, b});
+    }
+  }
+  eb.first.push_back((long long)eb.tasks.size());
+  eb.b_states = al256(nb * sizeof(int32_t)), eb.b_pmax = al256(nb * sizeof(int32_t)), eb.b_sbase = al256(nb * sizeof(int64_t));
+  eb.b_roff = al256(eb.h_roff.size() * sizeof(int64_t)), eb.b_tasks = al256(eb.tasks.size() * sizeof(int2));
+  eb.b_part = al256((size_t)nb * part_per_state * sizeof(double));
+  eb.b_tab = eb.b_states + eb.b_pmax + eb.b_sbase + 2 * eb.b_roff + eb.b_tasks, eb.b_env = al256((size_t)eb.tot * sizeof(double));
+}
+// upload the tables and enqueue the launches of `plan` on the context's stream; eb.g describes the batch afterwards
+int env_run(qk_ctx* c, const qk_mps_set* set, const char* what, double* rev, const EnvSizes& z, const std::vector<std::pair<int, int>>& plan, EnvBatch& eb, const size_t extra) {
+  const int n = set->n_sites, nb = eb.nb;
+  HIP_TRY_AS(what, c->local_scratch.ensure(eb.used() + extra));
+  char* base = eb.base = c->local_scratch.get<char>();
+  std::vector<char>& stage = eb.stage;
+  stage.assign(eb.b_tab, 0);
+  size_t at = 0;
+  auto put = [&](const void* src, size_t bytes, size_t span) {
+    std::memcpy(stage.data() + at, src, bytes);
+    const size_t here = at;
+    at += span;
+    return base + here;
+  };
+  LocArgs& g = eb.g;
+  g = LocArgs{};
+  g.data = set->d_data.get<double>();
+  g.rev = rev;
+  g.dims = set->d_dims.get<int32_t>();
+  g.tru = set->d_true.get<int32_t>();
+  g.offs = set->d_offs.get<int64_t>();
+  g.states = reinterpret_cast<const int32_t*>(put(eb.h_states.data(), nb * sizeof(int32_t), eb.b_states));
+  g.pmax = reinterpret_cast<const int32_t*>(put(eb.h_pmax.data(), nb * sizeof(int32_t), eb.b_pmax));
+  g.sbase = reinterpret_cast<const int64_t*>(put(eb.h_sbase.data(), nb * sizeof(int64_t), eb.b_sbase));
+  g.roff = reinterpret_cast<const int64_t*>(put(eb.h_roff.data(), eb.h_roff.size() * sizeof(int64_t), eb.b_roff));
+  g.loff = reinterpret_cast<const int64_t*>(put(eb.h_loff.data(), eb.h_loff.size() * sizeof(int64_t), eb.b_roff));
+  const int2* d_tasks = reinterpret_cast<const int2*>(put(eb.tasks.data(), eb.tasks.size() * sizeof(int2), eb.b_tasks));
+  g.part = reinterpret_cast<double*>(base + eb.b_tab);
+  g.scratch = reinterpret_cast<double*>(base + eb.b_tab + eb.b_part);
+  g.rmul = LOC_RMUL;
+  g.max_dist = 1;
+  g.n_sites = n;
+  g.max_chunks = z.max_chunks;
+  HIP_TRY_AS(what, hipMemcpyAsync(base, stage.data(), eb.b_tab, hipMemcpyHostToDevice, c->stream));
+  qk_local_reverse_kernel<<<dim3(nb, n), dim3(256), 0, c->stream>>>(g, rev);
+  qk_local_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, nb);
+  qk_str_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, g.loff);
+  HIP_TRY_AS(what, hipGetLastError());
+  for (size_t li = 0; li < plan.size(); ++li) {
+    const int kind = plan[li].first;
+    g.tasks = d_tasks + eb.first[li];
+    g.step = plan[li].second;
+    const long long grid = eb.first[li + 1] - eb.first[li];
+    if (grid <= 0) continue;
+    if (kind == LOC_REV_X || kind == LOC_FWD_W) qk_local_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
+    else if (kind >= 0) qk_local_gemm_kernel<false><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
+    else if (kind == LOC_BOND_TR) qk_bond_trace_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
+    else qk_str_lnext_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g, g.loff);
+  }
+  HIP_TRY_AS(what, hipGetLastError());
+  return QK_OK;
+}
+
 int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, const uint8_t* strings, double* out, double* norms) {
   static const char* what = "qk_pauli_strings_host";
   if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
@@ -874,24 +1074,12 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
   QkRangeGuard range_("qk:pauli_strings");
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
-  std::vector<int64_t> offs((size_t)ns * n);
-  HIP_TRY_AS(what, hipMemcpy(offs.data(), set->d_offs.get<int64_t>(), offs.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-  const int32_t* tru = set->dims_true.data();
-  std::vector<int32_t> pad((size_t)ns * n1);
-  std::vector<int> pmax(ns);
-  std::vector<long long> need(ns);  // environment doubles of each state: the sweep's planes, R_1 .. R_n, L_0 .. L_{n-1}
-  for (int s = 0; s < ns; ++s) {
-    int p = 16;
-    long long esum = 0;
-    for (int k = 0; k <= n; ++k) {
-      const int d = pad[(size_t)s * n1 + k] = pad16h(tru[(size_t)s * n1 + k]);
-      p = std::max(p, d);
-      esum += (k >= 1 ? 2ll * d * d : 0) + (k < n ? 2ll * d * d : 0);
-    }
-    pmax[s] = p;
-    need[s] = (long long)LOC_RMUL * p * p + esum;
-  }
-  const int max_chunks = set->max_pad / LOC_CHUNK;
+  EnvSizes z;
+  env_sizes(set, z);
+  const std::vector<int32_t>& pad = z.pad;
+  const std::vector<int>& pmax = z.pmax;
+  const std::vector<long long>& need = z.need;
+  const int max_chunks = z.max_chunks;
   // tasks of the chain (state s, string m): per site of [a, b] the blocks of the two GEMMs and the Pauli's chunks, then the closing chunks
   auto chain_tasks = [&](const int s, const int m) {
     const int* p = &pad[(size_t)s * n1];
@@ -920,50 +1108,15 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
     acc += need[s];
   }
   bstart.push_back(ns);
-  // the launches of the environment pass, in stream order: the reversed chain as in local_sweep, then per site forward T / W and L_{k+1}
-  std::vector<std::pair<int, int>> plan;  // (kind, step)
-  for (int j = 0; j < n - 1; ++j) plan.push_back({LOC_REV_T, j}), plan.push_back({LOC_REV_X, j});
-  for (int k = 0; k < n; ++k) plan.push_back({LOC_FWD_T, k}), plan.push_back({LOC_FWD_W, k}), plan.push_back({STR_LNEXT, k});
+  const std::vector<std::pair<int, int>> plan = env_plan(n);
   static const int chain_kinds[4] = {STR_T, STR_PAULI, STR_X, STR_CLOSE};  // the launches of a site of the chain pass, in stream order
   std::vector<int2> tasks;
   std::vector<long long> first;
+  EnvBatch eb;
   for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
     const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
-    std::vector<int32_t> h_states(nb), h_pmax(nb);
-    std::vector<int64_t> h_sbase(nb), h_roff((size_t)nb * n1), h_loff((size_t)nb * n1);
-    long long tot = 0;
-    for (int i = 0; i < nb; ++i) {
-      const int s = s0 + i;
-      h_states[i] = s, h_pmax[i] = pmax[s], h_sbase[i] = tot;
-      long long ro = 0;
-      for (int k = 0; k <= n; ++k) {
-        h_roff[(size_t)i * n1 + k] = ro;
-        if (k >= 1) ro += 2ll * pad[(size_t)s * n1 + k] * pad[(size_t)s * n1 + k];
-      }
-      for (int k = 0; k <= n; ++k) {  // the L_k behind the R_k
-        h_loff[(size_t)i * n1 + k] = ro;
-        ro += 2ll * pad[(size_t)s * n1 + k] * pad[(size_t)s * n1 + k];
-      }
-      tot += need[s];
-    }
-    tasks.clear(), first.clear();
-    for (const auto& [kind, step] : plan) {
-      first.push_back((long long)tasks.size());
-      for (int i = 0; i < nb; ++i) {
-        const int* p = &pad[(size_t)(s0 + i) * n1];
-        const int o = n - 1 - step, k = step;
-        int nbk = 0;
-        switch (kind) {
-          case LOC_REV_T: nbk = (int)blocks64(p[o + 1], 2ll * p[o]); break;
-          case LOC_REV_X: nbk = (int)blocks64(p[o], p[o]); break;
-          case LOC_FWD_T: nbk = (int)blocks64(p[k], 2ll * p[k + 1]); break;
-          case LOC_FWD_W: nbk = (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); break;
-          default: nbk = p[k + 1] / LOC_CHUNK; break;  // STR_LNEXT
-        }
-        for (int b = 0; b < nbk; ++b) tasks.push_back(int2{i, b});
-      }
-    }
-    first.push_back((long long)tasks.size());
+    env_tables(set, z, plan, s0, nb, 0, eb);
+    const long long tot = eb.tot;
     // the chains of the state batch, state-major in string order, cut into chain batches: consecutive chains while their slots,
     // partial sums and tasks fit what the environments leave, and at most QK_STRINGS_BATCH of them
     std::vector<int32_t> h_cent, h_cstr;
@@ -998,51 +1151,11 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
       b_chain = std::max(b_chain, cbz.tab() + cbz.part + cbz.slots);
     }
     // one device buffer for the state batch: [tables | tasks | environments] then the chain batch's [tables | tasks | partials | slots]
-    const size_t b_states = al(nb * sizeof(int32_t)), b_pmax = al(nb * sizeof(int32_t)), b_sbase = al(nb * sizeof(int64_t));
-    const size_t b_roff = al(h_roff.size() * sizeof(int64_t)), b_tasks = al(tasks.size() * sizeof(int2));
-    const size_t b_tab = b_states + b_pmax + b_sbase + 2 * b_roff + b_tasks, b_env = al((size_t)tot * sizeof(double));
-    HIP_TRY_AS(what, c->local_scratch.ensure(b_tab + b_env + b_chain));
-    char* base = c->local_scratch.get<char>();
-    std::vector<char> stage(b_tab);
-    size_t at = 0;
-    auto put = [&](const void* src, size_t bytes, size_t span) {
-      std::memcpy(stage.data() + at, src, bytes);
-      const size_t here = at;
-      at += span;
-      return base + here;
-    };
-    LocArgs g{};
-    g.data = set->d_data.get<double>();
-    g.rev = rev.get<double>();
-    g.dims = set->d_dims.get<int32_t>();
-    g.tru = set->d_true.get<int32_t>();
-    g.offs = set->d_offs.get<int64_t>();
-    g.states = reinterpret_cast<const int32_t*>(put(h_states.data(), nb * sizeof(int32_t), b_states));
-    g.pmax = reinterpret_cast<const int32_t*>(put(h_pmax.data(), nb * sizeof(int32_t), b_pmax));
-    g.sbase = reinterpret_cast<const int64_t*>(put(h_sbase.data(), nb * sizeof(int64_t), b_sbase));
-    g.roff = reinterpret_cast<const int64_t*>(put(h_roff.data(), h_roff.size() * sizeof(int64_t), b_roff));
-    const int64_t* d_loff = reinterpret_cast<const int64_t*>(put(h_loff.data(), h_loff.size() * sizeof(int64_t), b_roff));
-    const int2* d_tasks = reinterpret_cast<const int2*>(put(tasks.data(), tasks.size() * sizeof(int2), b_tasks));
-    g.scratch = reinterpret_cast<double*>(base + b_tab);
-    g.rmul = LOC_RMUL;
-    g.max_dist = 1;
-    g.n_sites = n;
-    g.max_chunks = max_chunks;
-    HIP_TRY_AS(what, hipMemcpyAsync(base, stage.data(), b_tab, hipMemcpyHostToDevice, c->stream));
-    qk_local_reverse_kernel<<<dim3(nb, n), dim3(256), 0, c->stream>>>(g, rev.get<double>());
-    qk_local_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, nb);
-    qk_str_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, d_loff);
-    HIP_TRY_AS(what, hipGetLastError());
-    for (size_t li = 0; li < plan.size(); ++li) {
-      const int kind = plan[li].first;
-      g.tasks = d_tasks + first[li];
-      g.step = plan[li].second;
-      const long long grid = first[li + 1] - first[li];
-      if (grid <= 0) continue;
-      if (kind == LOC_REV_X || kind == LOC_FWD_W) qk_local_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
-      else if (kind >= 0) qk_local_gemm_kernel<false><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
-      else qk_str_lnext_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g, d_loff);
-    }
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, b_chain)) return rc;
+    const LocArgs& g = eb.g;
+    const int64_t* const d_loff = g.loff;
+    char* const base = eb.base;
+    const size_t b_tab = eb.b_tab, b_env = eb.b_env;
     qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(g, nb, dnorm.get<double>());
     HIP_TRY_AS(what, hipGetLastError());
     StrArgs q{};
@@ -1119,7 +1232,115 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
   return QK_OK;
 }
 
+// ---- bond purities and entanglement spectra (qk_bond_purities_host, qk_bond_spectra_host) --------------------------------------
+// Bond k (k = 1 .. n-1) cuts the chain between sites k-1 and k.  With the kept environments of the pass above,
+//     N_k = R_k L_k^T / <psi|psi>     (chi_k x chi_k, tr N_k = 1; its eigenvalues are the Schmidt weights of the cut)
+//     purity_k = tr(N_k^2)
+// L_k and R_k are Hermitian in the sweep's X[ket][bra] orientation, so the product the ring GEMM makes from them as they lie,
+// M_k = L_k^T R_k, is N_k^H <psi|psi>: the same eigenvalues and the same tr(M^2).  Purities: per bond ONE GEMM launch (LOC_BOND_M,
+// tasks (state, 64 x 64 block), into the T planes, which the pass no longer needs) and ONE reduction launch in 16-row chunks
+// (qk_bond_trace_kernel); the chunk sums are added in a fixed order.  Spectra: one workgroup per (state, bond) of true bond >= 2
+// factorises L_k^T and takes the eigenvalues of the Hermitian H_k = F R_k F^H / <psi|psi> (qk_build.hip: qk_bond_spectra_kernel).
+// No atomics on values, no spin wait, no grid barrier: a value is the same bits whatever the other states, the batch cut and the run.
+int bond_call(qk_ctx* c, const qk_mps_set* set, const char* what, const char* range, const int32_t max_values, double* out, double* norms) {
+  const bool spectra = max_values != 0;
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!set) return qk_fail(QK_EINVAL, "%s: set is null", what);
+  if (!out) return qk_fail(QK_EINVAL, "%s: out is null", what);
+  if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
+  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; bond spectra and purities need an fp64 set", what);
+  if (spectra && max_values < 1) return qk_fail(QK_EINVAL, "%s: max_values must be >= 1 (got %d)", what, max_values);
+  const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
+  QkRangeGuard range_(range);
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  EnvSizes z;
+  env_sizes(set, z);
+  const int32_t* tru = set->dims_true.data();
+  const int m = spectra ? max_values : 1;
+  const size_t n_out = (size_t)ns * (n - 1) * m;
+  QkDevBuf rev, dout, dnorm, derr;
+  if (spectra) HIP_TRY_AS(what, derr.alloc(32 * sizeof(int)));
+  HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
+  HIP_TRY_AS(what, dout.alloc(std::max<size_t>(1, n_out) * sizeof(double)));
+  HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
+  HIP_TRY_AS(what, hipMemsetAsync(dout.get(), 0, std::max<size_t>(1, n_out) * sizeof(double), c->stream));
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
+  // memory bound of a state batch: a quarter of what is free (at least one state per batch); with the spectra the environments take
+  // at most half of it and the factorisation workspaces the rest (at least one workgroup)
+  const long long budget = (long long)((free_b + c->local_scratch.bytes) / 4 / sizeof(double));
+  const long long part_per_state = spectra ? 0 : (long long)n * z.max_chunks;
+  std::vector<int> bstart{0};
+  for (long long acc = 0, s = 0; s < ns; ++s) {
+    const long long w = z.need[s] + part_per_state;
+    if (acc > 0 && acc + w > (spectra ? budget / 2 : budget)) bstart.push_back((int)s), acc = 0;
+    acc += w;
+  }
+  bstart.push_back(ns);
+  std::vector<std::pair<int, int>> plan = env_plan(n);
+  if (!spectra)
+    for (int k = 1; k < n; ++k) plan.push_back({LOC_BOND_M, k}), plan.push_back({LOC_BOND_TR, k});
+  EnvBatch eb;
+  std::vector<int2> stasks;
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+    env_tables(set, z, plan, s0, nb, part_per_state, eb);
+    size_t extra = 0;
+    int grid = 0, qmax = 0;
+    size_t per_wg = 0;
+    if (spectra) {  // the (state, bond) tasks of the batch and the workspaces of the workgroups that take them in turn
+      stasks.clear();
+      for (int i = 0; i < nb; ++i)
+        for (int k = 1; k < n; ++k) {
+          const int q = tru[(size_t)(s0 + i) * n1 + k];
+          if (q >= 2) stasks.push_back(int2{i, k}), qmax = std::max(qmax, q);
+        }
+      if (!stasks.empty()) {
+        per_wg = qk_bond_spectra_work_bytes(qmax);
+        const long long room = (budget - eb.tot) * (long long)sizeof(double);
+        grid = (int)std::max<long long>(1, std::min<long long>({(long long)stasks.size(), 2ll * c->num_cus, room / (long long)per_wg}));
+        extra = al256(stasks.size() * sizeof(int2)) + (size_t)grid * per_wg;
+      }
+    }
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, extra)) return rc;
+    const LocArgs& g = eb.g;
+    qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(g, nb, dnorm.get<double>());
+    if (!spectra && n > 1) qk_bond_purities_kernel<<<dim3((unsigned)(((long long)nb * (n - 1) + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, dout.get<double>());
+    HIP_TRY_AS(what, hipGetLastError());
+    if (grid > 0) {
+      char* const x0 = eb.base + eb.used();
+      HIP_TRY_AS(what, hipMemcpyAsync(x0, stasks.data(), stasks.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+      QkSpectraArgs a{};
+      a.env = g.scratch, a.dims = g.dims, a.tru = g.tru, a.states = g.states, a.pmax = g.pmax, a.sbase = g.sbase, a.roff = g.roff, a.loff = g.loff;
+      a.tasks = reinterpret_cast<const int2*>(x0), a.n_tasks = (int)stasks.size();
+      a.work = x0 + al256(stasks.size() * sizeof(int2)), a.work_bytes = (long long)per_wg, a.qmax = qmax;
+      a.out = dout.get<double>(), a.n_sites = n, a.max_values = m, a.rmul = LOC_RMUL, a.error = derr.get<int>();
+      if (const int rc = qk_bond_spectra_launch(c, a, grid, what)) return rc;  // synchronises and reads the error word
+    }
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
+  }
+  if (n_out) HIP_TRY_AS(what, hipMemcpy(out, dout.get(), n_out * sizeof(double), hipMemcpyDeviceToHost));
+  if (norms) HIP_TRY_AS(what, hipMemcpy(norms, dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+  if (spectra)  // a bond of true dimension 1 has the single weight 1 exactly
+    for (int s = 0; s < ns; ++s)
+      for (int k = 1; k < n; ++k)
+        if (tru[(size_t)s * n1 + k] < 2) out[((size_t)s * (n - 1) + k - 1) * m] = 1.0;
+  return QK_OK;
+}
+
 }  // namespace
+
+extern "C" int qk_bond_purities_host(qk_ctx* c, const qk_mps_set* set, double* out, double* norms) {
+  return bond_call(c, set, "qk_bond_purities_host", "qk:bond_purities", 0, out, norms);
+}
+
+extern "C" int qk_bond_spectra_host(qk_ctx* c, const qk_mps_set* set, int32_t max_values, double* out, double* norms) {
+  static const char* what = "qk_bond_spectra_host";
+  if (max_values < 1) return qk_fail(QK_EINVAL, "%s: max_values must be >= 1 (got %d)", what, max_values);
+  return bond_call(c, set, what, "qk:bond_spectra", max_values, out, norms);
+}
 
 extern "C" int qk_pauli_strings_host(qk_ctx* c, const qk_mps_set* set, int32_t n_strings, const uint8_t* strings, double* out, double* norms) {
   return pauli_strings(c, set, n_strings, strings, out, norms);

@@ -102,6 +102,8 @@ _SIGNATURES = [
     ("qk_projected_pair_gram_dist_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_pauli_strings_host", C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     ("qk_feature_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
+    ("qk_bond_purities_host", C.c_int, [_P, _P, _P, _P]),
+    ("qk_bond_spectra_host", C.c_int, [_P, _P, C.c_int32, _P, _P]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
@@ -269,6 +271,43 @@ def pauli_strings(n_sites: int, specs) -> np.ndarray:
     if not rows:
         raise ValueError("the list of Pauli strings is empty")
     return np.ascontiguousarray(np.stack(rows))
+
+
+def _spectra_array(spectra) -> np.ndarray:
+    w = np.asarray(spectra, dtype=np.float64)
+    if w.ndim < 1:
+        raise ValueError(f"spectra must be an array (..., max_values) of Schmidt weights, got shape {w.shape}")
+    return w
+
+
+def bond_entropies(spectra, alpha: float = 1.0) -> np.ndarray:
+    """Entanglement entropies of Schmidt weights (``Context.bond_spectra``) along the last axis, natural logarithm: the von
+    Neumann entropy S_1 = -sum lambda log lambda at ``alpha=1``, otherwise the Renyi entropy S_alpha = log(sum lambda^alpha) /
+    (1 - alpha) (S_2 = -log purity).  ``alpha`` must be > 0; zero weights (the fill beyond a bond) contribute 0."""
+    a = float(alpha)
+    if not (a > 0.0 and np.isfinite(a)):
+        raise ValueError(f"alpha must be > 0 and finite (got {alpha!r})")
+    w = _spectra_array(spectra)
+    pos = w > 0.0
+    safe = np.where(pos, w, 1.0)
+    if a == 1.0:
+        return -(np.where(pos, w * np.log(safe), 0.0)).sum(axis=-1)
+    return np.log(np.where(pos, safe ** a, 0.0).sum(axis=-1)) / (1.0 - a)
+
+
+def cap_cost(spectra, chi: int) -> np.ndarray:
+    """What a bond cap at ``chi`` discards at each bond: eps_k(chi) = sum_{i >= chi} lambda_k[i] of descending Schmidt weights
+    (``Context.bond_spectra`` with every weight, the default), shape ``spectra.shape[:-1]``.  For a normalised state
+    ||psi - psi_chi||^2 <= 2 sum_k eps_k(chi).  ``chi`` must be >= 1."""
+    if int(chi) != chi or int(chi) < 1:
+        raise ValueError(f"chi must be an integer >= 1 (got {chi!r})")
+    w = _spectra_array(spectra)
+    return w[..., int(chi):][..., ::-1].sum(axis=-1)  # from the small end
+
+
+def schmidt_rank(spectra, tol: float) -> np.ndarray:
+    """Number of Schmidt weights above ``tol`` at each bond (weights below about 1e-15 are rounding noise of the environments)."""
+    return np.count_nonzero(_spectra_array(spectra) > float(tol), axis=-1)
 
 
 def _dims_table(states) -> np.ndarray:
@@ -814,6 +853,38 @@ class Context:
         nrm = np.zeros(ns, dtype=np.float64)
         _check(lib().qk_pauli_strings_host(self._h, mps_set.handle, S.shape[0], S.ctypes.data, V.ctypes.data, nrm.ctypes.data), "qk_pauli_strings_host")
         return (V, nrm) if norms else V
+
+    def bond_purities(self, mps_set: MpsSet, norms: bool = False):
+        """Purity tr(rho^2) of the reduced state left of every bond, for every state of an fp64 set: float64 of shape (n_states,
+        n_sites - 1), column k - 1 the bond between qubits k - 1 and k (S_2 = -log purity); with ``norms=True`` also <psi|psi> (the
+        bits of ``local_paulis``), as ``(purities, norms)``.  A one-site chain has a zero-length bond axis.  Synchronous."""
+        info = mps_set.info()
+        ns, n = info["n_states"], info["n_sites"]
+        out = np.zeros((ns, max(n - 1, 1)), dtype=np.float64)  # (one spare element for a one-site chain: the pointer stays valid)
+        nrm = np.zeros(ns, dtype=np.float64)
+        _check(lib().qk_bond_purities_host(self._h, mps_set.handle, out.ctypes.data, nrm.ctypes.data), "qk_bond_purities_host")
+        out = out[:, : n - 1]
+        return (out, nrm) if norms else out
+
+    def bond_spectra(self, mps_set: MpsSet, max_values: int | None = None, norms: bool = False):
+        """Entanglement spectra of every state of an fp64 set: the Schmidt weights (eigenvalues of the reduced state, descending, sum
+        1) across every bond, float64 of shape (n_states, n_sites - 1, m), zero beyond a bond's true dimension.  ``max_values=m``
+        keeps the m largest weights of each bond; the default is the set's largest true bond (every weight).  ``norms=True``
+        adds <psi|psi> (the bits of ``local_paulis``).  ``bond_entropies``, ``cap_cost`` and ``schmidt_rank`` read the result.
+        Weights below about 1e-15 are rounding noise.  Synchronous."""
+        info = mps_set.info()
+        ns, n = info["n_states"], info["n_sites"]
+        if max_values is None:
+            m = int(np.asarray(mps_set.dims)[:, 1:n].max()) if n > 1 else 1
+        else:
+            if isinstance(max_values, bool) or not isinstance(max_values, (int, np.integer)):
+                raise ValueError(f"max_values must be an int >= 1 or None (every weight), got {max_values!r}")
+            m = int(max_values)
+        out = np.zeros((ns, max(n - 1, 1), max(m, 1)), dtype=np.float64)
+        nrm = np.zeros(ns, dtype=np.float64)
+        _check(lib().qk_bond_spectra_host(self._h, mps_set.handle, m, out.ctypes.data, nrm.ctypes.data), "qk_bond_spectra_host")
+        out = out[:, : n - 1]
+        return (out, nrm) if norms else out
 
     def feature_gram(self, fx, fy=None, gamma=None) -> np.ndarray:
         """Gram of real feature columns (``pauli_expectations``): K[j, i] = exp(-gamma sum_m (fx[i, m] - fy[j, m])^2), shape (ny, nx),

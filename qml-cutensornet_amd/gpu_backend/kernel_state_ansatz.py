@@ -533,3 +533,59 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         with open(info_file + ".json", "w") as fp:
             json.dump(prof, fp, indent=4)
     return kernel_mat
+
+
+def build_entanglement_profile(mpi_comm, ansatz, X, truncation_error=None, max_values=None, info_file=None, loglevel=30):
+    """Entanglement across every bond of the states of ``X``, from the same states as ``build_projected_kernel_matrix``: each rank
+    builds its share (same builders, same ``QK_BUILDER`` rules), takes the Schmidt weights and purities of every bond on its
+    device (``Context.bond_spectra``, ``Context.bond_purities``) and all-gathers (n - 1) m reals per state, never an MPS.
+    ``max_values=m`` keeps the m largest weights of a bond; the default is the largest bond of the whole data set (agreed across
+    ranks), so that every weight is there.  Every rank returns the dict
+        spectra    (len(X), n - 1, m)   descending Schmidt weights of bond k (between qubits k and k+1), zero-filled
+        purities   (len(X), n - 1)      sum of their squares
+        norms      (len(X),)            <psi|psi>
+        bond_dims  (len(X), n + 1)      true bond dimensions
+    ``engine.bond_entropies``, ``engine.cap_cost`` and ``engine.schmidt_rank`` read ``spectra``."""
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    if max_values is not None and (isinstance(max_values, bool) or not isinstance(max_values, (int, np.integer)) or max_values < 1):
+        raise ValueError(f"max_values must be an int >= 1 or None (every weight), got {max_values!r}")
+    X = np.asarray(X, dtype=np.float64)
+    fidelity = 1.0 - float(truncation_error)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: the entanglement profile has no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    n_qubits = int(ansatz.num_qubits)
+    t_start = time.perf_counter()
+    ctx = _engine.default_context(device_id)
+    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
+    lo, local, sim_secs, fids = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers)
+    ctx.trim()  # the device builder's arena goes back before the environments need memory
+    dims = np.zeros((0, n_qubits + 1), dtype=np.float64) if local is None else np.asarray(local.dims, dtype=np.float64)
+    widest = int(dims[:, 1:n_qubits].max()) if dims.size and n_qubits > 1 else 1
+    m = int(max_values) if max_values is not None else max(int(w) for w in comm_allgather(mpi_comm, widest))
+    t0 = time.perf_counter()
+    if local is None:
+        spectra, purities, norms = np.zeros((0, n_qubits - 1, m)), np.zeros((0, n_qubits - 1)), np.zeros(0)
+    else:
+        spectra, norms = ctx.bond_spectra(local, max_values=m, norms=True)
+        purities = ctx.bond_purities(local)
+        local.close()
+    feat_secs = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    out = {"spectra": _gather_features(mpi_comm, lo, spectra, len(X)), "purities": _gather_features(mpi_comm, lo, purities, len(X)),
+           "norms": _gather_features(mpi_comm, lo, norms, len(X)), "bond_dims": _gather_features(mpi_comm, lo, dims, len(X)).astype(np.int32)}
+    gather_secs = time.perf_counter() - t0
+    if is_root and info_file is not None:
+        prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "r0_circ_gen": [0.0, "seconds"], "r0_circ_sim": [sum(sim_secs), "seconds"],
+                "avg_fidelity": [sum(fids) / max(1, len(fids)), ""], "r0_RR_recv": [gather_secs, "seconds"],
+                "pqk_bond_values": [m, "weights"], "pqk_entanglement_time": [feat_secs, "seconds"], "total_time": [time.perf_counter() - t_start, "seconds"]}
+        with open(info_file + ".json", "w") as fp:
+            json.dump(prof, fp, indent=4)
+    return out

@@ -70,6 +70,30 @@ class MPS:
         arrays here and device residency is owned by the engine's MPS sets."""
         self._handle = handle
 
+    def bond_spectra(self) -> list:
+        """Schmidt weights across every interior bond, on the host: a list of n - 1 float64 arrays, entry k - 1 the descending
+        weights lambda_k[0 .. chi_k - 1] (sum 1) of the cut between sites k - 1 and k -- the eigenvalues of N_k = R_k L_k^T /
+        <psi|psi> that ``Context.bond_spectra`` returns.  By canonicalisation: the chain is right-orthonormalised by QR, then one
+        SVD per bond carries the centre to the right; weights below the bond's rank are zero.  Independent of the gauge of the
+        bonds and of the norm of the state."""
+        n = len(self.tensors)
+        ts = [np.asarray(t, dtype=np.complex128) for t in self.tensors]
+        for k in range(n - 1, 0, -1):
+            l, _, r = ts[k].shape
+            q, rr = np.linalg.qr(ts[k].reshape(l, 2 * r).T)  # (2r, l) = q (2r, m) rr (m, l)
+            ts[k] = q.T.reshape(-1, 2, r)
+            ts[k - 1] = np.tensordot(ts[k - 1], rr.T, axes=(2, 0))
+        out = []
+        centre = ts[0]
+        for k in range(1, n):
+            l, _, r = centre.shape
+            _, s, vh = np.linalg.svd(centre.reshape(l * 2, r), full_matrices=False)
+            w = np.zeros(self.tensors[k].shape[0], dtype=np.float64)
+            w[: min(s.size, w.size)] = (s * s)[: w.size] / float((s * s).sum())
+            out.append(w)
+            centre = np.tensordot(s[:, None] * vh, ts[k], axes=(1, 0))
+        return out
+
     def vdot(self, other: "MPS") -> complex:
         """<self|other> through the HIP engine (single pair; the Gram path is batch-first)."""
         from .engine import default_context

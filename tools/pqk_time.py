@@ -6,7 +6,9 @@ two local sweeps and their achieved TFLOP/s.  ``--pair-distance D`` (D > 1) adds
 ctx.local_pair_paulis(xs, max_dist=D) and ctx.projected_pair_gram(T, max_dist=D), their times, flops and median entry.
 ``--strings N`` (N sparse Pauli strings: weight 1..4 inside a window of 6 sites, seeded) or ``--strings-file F`` (one string over
 IXYZ per line) adds ctx.pauli_expectations(xs, strings) and ctx.feature_gram(V): pauli_strings_ms, n_strings, sum_support.
-usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F]"""
+``--entanglement`` adds ctx.bond_purities(xs) and ctx.bond_spectra(xs): bond_purities_ms, bond_spectra_ms, and what a bond cap
+would discard, ``cap_cost`` summed over the bonds of a state at chi = 16, 32, 64, 128 (the mean and the largest over the states).
+usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement]"""
 import argparse
 import json
 import os
@@ -80,6 +82,7 @@ def main():
     ap.add_argument("--pair-distance", type=int, default=1, help="also time the pairs up to this distance (default 1: neighbours only)")
     ap.add_argument("--strings", type=int, default=0, help="also time pauli_expectations on this many sparse Pauli strings")
     ap.add_argument("--strings-file", default=None, help="also time pauli_expectations on the strings of this file (one per line over IXYZ)")
+    ap.add_argument("--entanglement", action="store_true", help="also time bond_purities and bond_spectra and print the cost of a bond cap")
     args = ap.parse_args()
     gamma = args.gamma if args.gamma is not None else (0.1 if args.config == "cfg5" else 1.0)
     n, reps, d, npts = bench.CONFIGS[args.config]
@@ -125,6 +128,18 @@ def main():
             "n_strings": int(len(S)), "sum_support": int(sum(support)), "pauli_strings_ms": round(strings_ms, 3),
             "feature_gram_ms": round(fgram_ms, 3), "strings_over_local": round(strings_ms / local_ms, 4),
             "median_offdiag_feature_K": float(np.median(KO[off])),
+        })
+    if args.entanglement:
+        P, pur_ms = timed(lambda: ctx.bond_purities(xs), args.reps)
+        S, spec_ms = timed(lambda: ctx.bond_spectra(xs), args.reps)
+        s1 = engine.bond_entropies(S)
+        costs = {chi: engine.cap_cost(S, chi).sum(axis=1) for chi in (16, 32, 64, 128)}
+        dist.update({
+            "bond_purities_ms": round(pur_ms, 3), "bond_spectra_ms": round(spec_ms, 3), "spectra_values": int(S.shape[2]),
+            "purity_minus_sum_sq": float(np.abs(P - (S * S).sum(-1)).max()), "max_entropy_S1": float(s1.max()),
+            "median_max_entropy_S1": float(np.median(s1.max(axis=1))),
+            "median_weights_above_1e-3": float(np.median(engine.schmidt_rank(S, 1e-3).max(axis=1))),
+            "cap_cost": {str(chi): {"mean": float(c.mean()), "max": float(c.max())} for chi, c in costs.items()},
         })
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
