@@ -31,7 +31,10 @@
 //     barrier: a wave runs its items autonomously and the workgroup meets at two or three barriers per site.  The
 //     fragments that several items share are re-read through the caches (which catch a fifth to a quarter of them: the rest comes
 //     back over the fabric -- DESIGN.md, cache counters);
-//   * K is walked in units of 4 up to the TRUE bond; the complex product is the 3M form of the ring kernel;
+//   * K is walked in units of 4 up to the TRUE bond; the complex product is the 3M form of the ring kernel.  In phase 2 of the plain
+//     forms the three partial products are not re-combined by vector additions: k1 = sum (tr + ti) Ar is formed first and the chains of
+//     re = k1 + sum ti (Ai - Ar) and im = k1 - sum tr (Ar + Ai) START on it (the C operand of their first matrix instruction), so a
+//     column block ends in its ds_add_f64 with no v_add_f64 behind the matrix instructions (qkf_p2_block; lab/NOTES_r07.md);
 //   * sites too large for the LDS run in STRIPS: X is read from a per-workgroup global buffer (A-operand fragments
 //     loaded like the site tensors), X' is accumulated a block of b' rows at a time (as many as fit the LDS), items in
 //     rounds of (waves x slots), and written to the other global buffer;
@@ -83,7 +86,7 @@ static constexpr int QKF_XBLOCK = TILE * TILE;    // elements of a block of 16 r
 #define QKF_P2_PROBE 0
 #endif
 // ABLATION builds of the dual kernel (timing only, WRONG results; lab/tools/r04_run18.sh): bit 0 = no operand sums inside the matrix loops, bit 1 = no global
-// loads inside them, bit 2 = no s_barrier in the step loop, bit 3 = no LDS reads of X inside the loops of phase 1; one-wave sweep (qk_sweep_wave2_kernel): bit 4 = no LDS-DMA, bit 5 = no LDS reads of the fragments, bit 6 = no additions behind a T tile; one-tile kernel (qk_sweep_fused_kernel): bits 0-3 as in the dual kernel, bit 7 = no additions behind a block of phase 2, bit 8 = no LDS adds there
+// loads inside them, bit 2 = no s_barrier in the step loop, bit 3 = no LDS reads of X inside the loops of phase 1; one-wave sweep (qk_sweep_wave2_kernel): bit 4 = no LDS-DMA, bit 5 = no LDS reads of the fragments, bit 6 = no additions behind a T tile; one-tile kernel (qk_sweep_fused_kernel): bits 0-3 as in the dual kernel (bits 7 and 8, the tail of a block of phase 2, went with that tail)
 #ifndef QKF_ABL
 #define QKF_ABL 0
 #endif
@@ -299,6 +302,50 @@ __device__ __forceinline__ void qkf_p2_item(const QkfTile& t, v2d (&fr)[4], cons
                                             const int j, const QkfStream nxt, const QkfTurn turn = QkfTurn{nullptr, 0, nullptr, nullptr}) {
   if (!primed) qkf_load4(fr, cur);
   __attribute__((address_space(3))) double* d = (__attribute__((address_space(3))) double*)(xo + q * TILE + j);
+  if constexpr (!DET) {
+    // The plain form: k1 = sum (tr + ti) Ar first, then the chains of re = k1 + sum ti (Ai - Ar) and im = k1 - sum tr (Ar + Ai) START on it
+    // (qkf_p2_block has the reasoning): 8 v_add_f64 per column block -- the operand sums, formed while k1 runs so that the registers of a
+    // k-step are reloaded right behind its k1 -- instead of 17; the sums tr + ti are taken once per item (the register allocator of the
+    // 128-register shape keeps seven of the eight registers and forms the last sum again per block: 9 per block there).
+    const v4d z = {0, 0, 0, 0};
+    const v4d s = t.re + t.im;
+#pragma unroll 1
+    for (int tn = 0; tn < nn; ++tn) {
+      v4d p1 = z, re, im;
+      double sp[4], sm[4];
+      const bool fin = tn + 1 == nn;
+      const v2d* const rb = fin ? nxt.base : cur.base;
+      const int rs = fin ? nxt.step : cur.step, rl = fin ? nxt.lim : FULL ? 4 : kmax;  // (the k-steps at or above the bond: the address of the last one below it)
+      cur.off = fin ? nxt.off : cur.off + TILE;
+      QKF_PRIO_LO();
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (FULL || i == 0 || i < kmax) {
+          p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(s[i], fr[i].x, i == 0 ? z : p1, 0, 0, 0);
+          sp[i] = QKF_DIF(-fr[i].x, fr[i].y), sm[i] = QKF_DIF(fr[i].y, fr[i].x);
+        }
+        if (!(QKF_ABL & 2)) fr[i] = qkf_ldg_a(qkf_kbase(rb, rs, i, rl), cur.off);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (FULL || i == 0 || i < kmax) {
+          re = __builtin_amdgcn_mfma_f64_16x16x4f64(t.im[i], sm[i], i == 0 ? p1 : re, 0, 0, 0);
+          im = __builtin_amdgcn_mfma_f64_16x16x4f64(t.re[i], sp[i], i == 0 ? p1 : im, 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      QKF_PRIO_HI();
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        __hip_atomic_fetch_add(d + r * 2 * QKF_XSTEP, re[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(d + r * 2 * QKF_XSTEP + 1, im[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      d += 2 * ps;  // the next panel
+    }
+    return;
+  }
+  // the ordered form keeps the product's first 3M form and its additions: deterministic Grams keep their bits
 #pragma unroll 1
   for (int tn = 0; tn < nn; ++tn) {
     v4d p1 = {0, 0, 0, 0}, p2 = {0, 0, 0, 0}, p3 = {0, 0, 0, 0};
@@ -314,18 +361,8 @@ __device__ __forceinline__ void qkf_p2_item(const QkfTile& t, v2d (&fr)[4], cons
       __builtin_amdgcn_sched_barrier(0);
     }
     QKF_PRIO_HI();
-    const v4d re = (QKF_ABL & 128) ? p1 : p1 + p2, im = (QKF_ABL & 128) ? p3 : p3 - p1 + p2;
-    if constexpr (DET) qkf_turn_add(d, (long)2 * QKF_XSTEP, re, im, turn, tn);
-    else if (QKF_ABL & 256) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) asm volatile("" ::"v"(re[r]), "v"(im[r]));
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        __hip_atomic_fetch_add(d + r * 2 * QKF_XSTEP, re[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(d + r * 2 * QKF_XSTEP + 1, im[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-    }
+    const v4d re = p1 + p2, im = p3 - p1 + p2;
+    qkf_turn_add(d, (long)2 * QKF_XSTEP, re, im, turn, tn);
     d += 2 * ps;  // the next panel
   }
 }
@@ -956,99 +993,61 @@ __device__ __forceinline__ void qkf_p1_dual(QkfTile& t0, QkfTile& t1, v2d (&fr)[
 // last block, which reloads the registers with the first group of `nxt`, stands behind it; the product's second 3M form saves a third of
 // the additions behind a block.  cfg4, one box, step by step: 374.4 -> 370.6 (this loop) -> 368.0 (3M form) -> 364.3 (phase 1 started by its
 // first k-step) -> 363.9 ms (the same in the one-tile kernel).
+// The additions BEHIND a block are gone altogether (lab/NOTES_r07.md): with  k1 = (tr + ti) Ar,  k2 = tr (Ar + Ai),  k3 = ti (Ar - Ai)  the
+// product is re = k1 - k3, im = k1 - k2, and a matrix instruction adds its C operand for nothing.  So k1 of the block's k-steps is formed
+// first (chain started on the literal zero), and the chains of re = k1 + sum ti (Ai - Ar) and im = k1 - sum tr (Ar + Ai) START on it: the
+// first matrix instruction of `re` reads k1 as its C operand and writes other registers, `im` goes on in k1's registers -- three accumulator
+// sets per tile, as before.  The signs ride on the operand sums (source modifiers of the v_add_f64), which are formed while k1 runs, so the
+// registers of a k-step are reloaded right behind its k1: the loads keep their distance of a whole block.  Per block of a pair: 24 matrix
+// instructions, 8 v_add_f64 (16 tail additions gone), 16 ds_add_f64.
 typedef __attribute__((address_space(3))) double lds_double;
-// one column block: the matrix instructions of the k-steps in `fr`, each followed by the reload of its registers from (b_i, off), then the
+// one column block: k1 of the k-steps in `fr`, each followed by the reload of its registers from (b_i, off); the chains of re and im; then the
 // results added to X' at d (and d1 for the second tile)
 template <bool FULL, bool HAS1>
 __device__ __forceinline__ void qkf_p2_block(const QkfTile& t0, const QkfTile& t1, const v4d& s0, const v4d& s1, v2d (&fr)[4], const int kmax, const v2d* const b0, const v2d* const b1,
                                              const v2d* const b2, const v2d* const b3, const unsigned off, lds_double* const d, lds_double* const d1, const long rs) {
-  v4d p1 = {0, 0, 0, 0}, p2 = {0, 0, 0, 0}, p3 = {0, 0, 0, 0}, r1 = {0, 0, 0, 0}, r2 = {0, 0, 0, 0}, r3 = {0, 0, 0, 0};
+  const v4d z = {0, 0, 0, 0};
+  v4d p1 = z, r1 = z, re, im, re1, im1;
+  double sp[4], sm[4];
   QKF_PRIO_LO();
+  // k1 of the block's k-steps (k-step 0 always lies below the bond and starts the chain on the literal zero)
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    if (FULL || i < kmax) {
-      // the 3M product in the form  k1 = (ar + ai) br,  k2 = ar (br + bi),  k3 = ai (br - bi):  re = k1 - k3,  im = k1 - k2 -- two additions per
-      // element behind the block instead of three (and two per fragment, shared by both tiles, instead of one)
-#if QKF_LDS3M  // (the LDS takes the product's last two additions: p2 = - k2, p3 = - k3 -- the signs ride on the operand sums as source modifiers)
-      const double sp = -fr[i].x - fr[i].y, sm = fr[i].y - fr[i].x;
-#else
-      const double sp = QKF_SUM(fr[i].x, fr[i].y), sm = QKF_DIF(fr[i].x, fr[i].y);
-#endif
-      p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(s0[i], fr[i].x, p1, 0, 0, 0);
-      p2 = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.re[i], sp, p2, 0, 0, 0);
-      p3 = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.im[i], sm, p3, 0, 0, 0);
-      if (HAS1) {
-        r1 = __builtin_amdgcn_mfma_f64_16x16x4f64(s1[i], fr[i].x, r1, 0, 0, 0);
-        r2 = __builtin_amdgcn_mfma_f64_16x16x4f64(t1.re[i], sp, r2, 0, 0, 0);
-        r3 = __builtin_amdgcn_mfma_f64_16x16x4f64(t1.im[i], sm, r3, 0, 0, 0);
-      }
+    if (FULL || i == 0 || i < kmax) {
+      p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(s0[i], fr[i].x, i == 0 ? z : p1, 0, 0, 0);
+      if (HAS1) r1 = __builtin_amdgcn_mfma_f64_16x16x4f64(s1[i], fr[i].x, i == 0 ? z : r1, 0, 0, 0);
+      sp[i] = QKF_DIF(-fr[i].x, fr[i].y), sm[i] = QKF_DIF(fr[i].y, fr[i].x);
     }
     if (!(QKF_ABL & 2)) fr[i] = qkf_ldg_a(i == 0 ? b0 : i == 1 ? b1 : i == 2 ? b2 : b3, off);
     __builtin_amdgcn_sched_barrier(0);
   }
-  QKF_PRIO_HI();
-#if QKF_LDS3M
-  // re = k1 - k3 and im = k1 - k2 are not formed in registers: the three accumulators go to X' as they are (k1 to both parts), 16 LDS adds per
-  // tile in place of 8 vector additions + 8 LDS adds -- an LDS instruction costs the matrix pipe 1.8 cycles, a v_add_f64 9.2
+  // re = k1 + sum ti (Ai - Ar), im = k1 - sum tr (Ar + Ai): both chains START on k1 (the first matrix instruction of `re` reads p1 as its C
+  // operand and writes other registers, `im` goes on in p1's), the signs ride on the operand sums as source modifiers
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    __hip_atomic_fetch_add(d + r * rs, p1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __hip_atomic_fetch_add(d + r * rs + 1, p1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __hip_atomic_fetch_add(d + r * rs, p3[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __hip_atomic_fetch_add(d + r * rs + 1, p2[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-  if (HAS1) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      __hip_atomic_fetch_add(d1 + r * rs, r1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(d1 + r * rs + 1, r1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(d1 + r * rs, r3[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(d1 + r * rs + 1, r2[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-  }
-#elif QKF_P2_PROBE  // TIMING PROBES (wrong results): 1 = the adds at conflict-free addresses (a lane's re and im 2 KiB apart, lanes 8 bytes apart), 2 = plain stores instead
-                    // of adds, 3 = no LDS instruction at all, 4 = neither the additions nor the LDS instructions
-  {
-    const v4d re = p1 - p3, im = p1 - p2, re1 = r1 - r3, im1 = r1 - r2;
-    lds_double* const e = d - (threadIdx.x & 63);  // the block's base + q * 16 + j (d is 2 (q * 16 + j) doubles into the block)
-    lds_double* const e1 = e + 2 * QKF_XBLOCK;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (QKF_P2_PROBE == 1) {
-        __hip_atomic_fetch_add(e + r * 64, re[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(e + r * 64 + 256, im[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (HAS1) {
-          __hip_atomic_fetch_add(e1 + r * 64, re1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_add(e1 + r * 64 + 256, im1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      } else if (QKF_P2_PROBE == 2) {
-        *(lds_v2d*)(d + r * rs) = (v2d){re[r], im[r]};
-        if (HAS1) *(lds_v2d*)(d1 + r * rs) = (v2d){re1[r], im1[r]};
-      } else if (QKF_P2_PROBE == 3) {
-        asm volatile("" ::"v"(re[r]), "v"(im[r]), "v"(re1[r]), "v"(im1[r]));
-      } else {
-        asm volatile("" ::"v"(p1[r]), "v"(p2[r]), "v"(p3[r]), "v"(r1[r]), "v"(r2[r]), "v"(r3[r]));
+  for (int i = 0; i < 4; ++i) {
+    if (FULL || i == 0 || i < kmax) {
+      re = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.im[i], sm[i], i == 0 ? p1 : re, 0, 0, 0);
+      im = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.re[i], sp[i], i == 0 ? p1 : im, 0, 0, 0);
+      if (HAS1) {
+        re1 = __builtin_amdgcn_mfma_f64_16x16x4f64(t1.im[i], sm[i], i == 0 ? r1 : re1, 0, 0, 0);
+        im1 = __builtin_amdgcn_mfma_f64_16x16x4f64(t1.re[i], sp[i], i == 0 ? r1 : im1, 0, 0, 0);
       }
     }
+    __builtin_amdgcn_sched_barrier(0);
   }
-#else
-  {
-    const v4d re = p1 - p3, im = p1 - p2;
+  QKF_PRIO_HI();
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      __hip_atomic_fetch_add(d + r * rs, re[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(d + r * rs + 1, im[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
+  for (int r = 0; r < 4; ++r) {
+    __hip_atomic_fetch_add(d + r * rs, re[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(d + r * rs + 1, im[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
   if (HAS1) {
-    const v4d re = r1 - r3, im = r1 - r2;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      __hip_atomic_fetch_add(d1 + r * rs, re[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(d1 + r * rs + 1, im[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(d1 + r * rs, re1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(d1 + r * rs + 1, im1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
   }
-#endif
 }
 // the loop of the DET forms (ordered accumulation): one body for every column block, the last one selecting `nxt`, the product in its first 3M
 // form (measured: the split loop of the plain form makes the ordered form 3.5 % slower)
