@@ -408,6 +408,36 @@ int qk_bond_purities_host(qk_ctx* ctx, const qk_mps_set* set, double* out /* [n_
 int qk_bond_spectra_host(qk_ctx* ctx, const qk_mps_set* set, int32_t max_values, double* out /* [n_states][n_sites - 1][max_values] */,
                          double* norms /* [n_states], may be NULL */);
 
+/* ---- compressing a set: one canonical truncation sweep per state -------------------------------------------------------------
+ * qk_mps_set_compress: *out = a new fp64 set of the same context that owns its memory, every state of src truncated ONCE on its
+ * final tensors; src is left untouched.  One workgroup per state (workgroup b takes states b, b + grid, ...), two passes over the
+ * site tensors themselves -- no environments, so amplitudes are kept to rounding:
+ *   pass 1, right to left, no truncation: site k as a chi_k x 2 chi_{k+1} matrix = carry x (row-orthonormal Q); the carry goes into
+ *           site k - 1.  Singular values <= value_of_zero ||site||_F go: a bond whose rank is below its dimension shrinks to it.
+ *   pass 2, left to right: the centre as a 2 chi'_k x chi_{k+1} matrix = U S V^H, sigma descending, total = sum sigma^2:
+ *           1. sigma_i <= value_of_zero sqrt(total) go;  2. from the small end, values go while their summed weight stays
+ *           <= max_discard total;  3. if max_bond > 0 at most max_bond stay;  4. at least one stays.
+ *           Site k = U_m (an isometry), (S_m V_m^H) sqrt(total / kept) goes into site k + 1.
+ * <psi'|psi'> = <psi|psi>, the norm sits in the last site, sites 0 .. n_sites - 2 are left isometries.
+ * discarded[state][k - 1] = 1 - kept / total at bond k (the dropped weights summed from the small end); fidelity[state] = the
+ * product over the bonds, in bond order, of kept / total = |<psi|psi'>|^2 / (<psi|psi> <psi'|psi'>) (the projectors of pass 2 are
+ * nested).  By Eckart-Young 1 - fidelity >= max_k sum_{i >= chi'_k} lambda_k[i], lambda the spectra of the ORIGINAL state.
+ * Every factorisation is the device builder's Jacobi primitive on the smaller side of the matrix (in LDS below 48 columns,
+ * preconditioned block Jacobi on the f64 matrix cores from 48 on), every product a workgroup GEMM on the matrix cores.  The compact
+ * sites are written into a staging buffer whose slots are sized by the input bonds (new bonds never exceed old ones); the host
+ * reads the new bonds and a pack kernel writes the padded split planes of the new set (the layout of qk_mps_set_create).
+ * A state's result -- image, fidelity, discarded -- is the same bits alone, in any set, under any batch cut and from run to run.
+ * Device scratch: the staging buffer (the true-bond corners of a batch, interleaved) and about 6 chi^2 complex numbers per
+ * resident workgroup (chi = the batch's largest bond), by the batching rule of qk_local_paulis_host (a quarter of the free
+ * memory; the states go in several batches when they do not fit); all of it is released before the call returns, so qk_ctx_trim
+ * has nothing of it to give back.
+ * A one-site chain is copied (fidelity 1).  QK_EINVAL: a null ctx, src or out; a set of another context; a complex64 set;
+ * max_bond < 0; a negative or non-finite max_discard or value_of_zero; a true bond above 512.  QK_EDEVICE: a factorisation that
+ * does not converge; a state of norm 0 (named in the message).                                                            */
+int qk_mps_set_compress(qk_ctx* ctx, const qk_mps_set* src, int32_t max_bond /* 0: no cap */, double max_discard /* >= 0 */,
+                        double value_of_zero /* >= 0 */, qk_mps_set** out,
+                        double* fidelity /* [n_states], may be NULL */, double* discarded /* [n_states][n_sites-1], may be NULL */);
+
 /* ---- profiler ranges -----------------------------------------------------------------------------------------
  * roctx ranges (rocprofv3 --marker-trace) named "qk:build", "qk:upload", "qk:sweep", "qk:scatter", "qk:allgather_values",
  * "qk:allgather_sets" are opened by the library around its own phases -- the reference's MPI.Wtime() sites G:209-231

@@ -37,7 +37,7 @@ enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY 
 
 __host__ __device__ inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ; }
 
-enum { ERR_BOND = 1, ERR_HEAP = 2, ERR_SWEEPS = 4, ERR_GATE = 8, ERR_OP = 16 };
+enum { ERR_BOND = 1, ERR_HEAP = 2, ERR_SWEEPS = 4, ERR_GATE = 8, ERR_OP = 16, ERR_NORM0 = 32 };
 
 struct BuildArgs {
   int n_states, n_qubits, n_ops, cap;
@@ -204,6 +204,337 @@ int qk_bond_spectra_launch(qk_ctx* c, QkSpectraArgs a, const int grid, const cha
   int errv[32] = {0};
   HIP_TRY_AS(what, hipMemcpy(errv, a.error, sizeof errv, hipMemcpyDeviceToHost));
   if (errv[0]) return qk_fail(QK_EDEVICE, "%s: a Jacobi factorisation did not converge in %d sweeps", what, MAX_SWEEPS);
+  return QK_OK;
+}
+
+// ---- compressing a set (qk_mps_set_compress below) ------------------------------------------------------------------------------
+// One state per workgroup at a time, in the mould of the spectra kernel: the true-bond corners of the state's padded split planes
+// become interleaved sites in the state's slots of the staging buffer (sized by the INPUT bonds: no bond grows, so every
+// intermediate fits its slot and the offsets are known before the launch), and two passes work on them in place:
+//   pass 1, k = n-1 .. 1: site k ([l][2 r], r already reduced) = carry (l x m) x Q (m x 2 r, orthonormal rows); site k-1 <- site k-1 x carry;
+//   pass 2, k = 0 .. n-2: the centre ([2 l'][r]) = U S V^H, wg_kept chooses m; site k <- U_m, site k+1 <- (S_m V_m^H) f x site k+1
+//           with f = sqrt(total / kept).
+// Every factorisation is jacobi_auto on the SMALLER side of the matrix (columns <= rows, as the builder takes a gate's theta), with
+// the spectra's settings: cut 1e-30 and sweeps that run until nothing rotates -- the sites of the result are isometries to rounding
+// and its weights agree with the host mirror's LAPACK values to 1e-12.  The LDS head and working set are the spectra's constants
+// (SPEC_QMAX): a state's path and bits do not depend on its batch.  The norm sits in the last site.
+__global__ __launch_bounds__(256, 2) void qk_compress_kernel(const QkCompressArgs g, const long lbuf_elems) {
+  using namespace qkb256;
+  extern __shared__ double sh_raw[];
+  __shared__ WgShared sh;
+  const int tid = threadIdx.x, n = g.n_sites, n1 = n + 1;
+  const long Q2 = (long)g.qmax * g.qmax;
+  double* const sig = sh_raw;
+  int* const ord = reinterpret_cast<int*>(sig + SPEC_QMAX);
+  cd* const lds = reinterpret_cast<cd*>(sh_raw + SPEC_HEAD_DOUBLES);
+  constexpr int lds_elems = SPEC_LDS_ELEMS;
+  cd* const VV = reinterpret_cast<cd*>(g.work + (long long)blockIdx.x * g.work_bytes);  // V of a factorisation
+  cd* const CM = VV + Q2;        // the matrix that goes into the neighbour: the carry, or S V^H
+  cd* const TMP = CM + Q2;       // the factorisation's scratch, then the site's new tensor
+  cd* const TH = TMP + 2 * Q2;   // the neighbour's new tensor
+  cd* const LB = TH + 2 * Q2;    // the block layout of the preconditioned path, the table of clean block pairs behind it
+  cd* const stage = reinterpret_cast<cd*>(g.stage);
+  for (int i = blockIdx.x; i < g.n_batch; i += gridDim.x) {
+    const long long st = (long long)g.s0 + i;
+    const int32_t* const tru = g.tru + st * n1;
+    const int32_t* const pad = g.pad + st * n1;
+    const long long* const so = g.stage_offs + (long long)i * n;
+    int32_t* const dn = g.dims_new + st * n1;
+    for (int k = 0; k < n; ++k) {
+      const int l = tru[k], r = tru[k + 1], pr = pad[k + 1];
+      const double* const re = g.planes + g.offs[st * n + k];
+      const double* const im = re + (long long)pad[k] * 2 * pr;
+      cd* const dst = stage + so[k];
+      for (int e = tid; e < l * 2 * r; e += 256) {
+        const int row = e / r, c = e - row * r;
+        dst[e] = cd{re[(long long)row * pr + c], im[(long long)row * pr + c]};
+      }
+    }
+    for (int k = tid; k <= n; k += 256) dn[k] = tru[k];
+    __syncthreads();
+    bool bad = false;  // a state of norm 0: uniform over the workgroup
+    // ---- pass 1: right to left, the ranks
+    int r = 1;
+    for (int k = n - 1; k >= 1; --k) {
+      cd* const t = stage + so[k];
+      cd* const d = stage + so[k - 1];
+      const int l = tru[k], l0 = tru[k - 1], w = 2 * r;
+      const bool cols = l <= w;  // t^T (w x l) has the fewer columns; otherwise t (l x w) is factorised as it lies
+      const int q = cols ? l : w;
+      if (cols) jacobi_auto<2>(t, 1, w, w, l, VV, sig, ord, &sh, g.error, lds, lds_elems, TMP, LB, lbuf_elems, SPEC_CUT, 0.0);
+      else jacobi_auto<2>(t, w, 1, l, w, VV, sig, ord, &sh, g.error, lds, lds_elems, TMP, LB, lbuf_elems, SPEC_CUT, 0.0);
+      __syncthreads();
+      if (tid == 0) {
+        double tot = 0;
+        for (int j = 0; j < q; ++j) tot += sig[j] * sig[j];
+        sh.nrm = tot;
+      }
+      __syncthreads();
+      const double tot = sh.nrm;
+      __syncthreads();
+      if (!(tot > 0.0)) {
+        bad = true;
+        break;
+      }
+      wg_kept(sig, ord, q, 0.0, g.zero * sqrt(tot), &sh);
+      const int m = sh.keep;
+      // cols: t^T = W V^H, so t = [s conj(V)] [W / s]^T;  rows: t = W V^H
+      for (int e = tid; e < m * w; e += 256) {  // the new site Q[jj][(p, c)]
+        const int jj = e / w, ii = e - jj * w, c = ord[jj];
+        if (cols) {
+          const double inv = 1.0 / sig[c];
+          const cd x = t[(long)c * w + ii];
+          TMP[e] = cd{x.x * inv, x.y * inv};
+        } else {
+          const cd v = VV[(long)ii * w + c];
+          TMP[e] = cd{v.x, -v.y};
+        }
+      }
+      for (int e = tid; e < l * m; e += 256) {  // the carry [a][jj]
+        const int a = e / m, jj = e - a * m, c = ord[jj];
+        if (cols) {
+          const double s = sig[c];
+          const cd v = VV[(long)a * l + c];
+          CM[e] = cd{s * v.x, -s * v.y};
+        } else {
+          CM[e] = t[(long)a * w + c];
+        }
+      }
+      __syncthreads();
+      wg_gemm_mfma(TH, 2 * l0, m, l, d, l, 1, CM, m, 1);  // carry x site: site k-1 ([2 l0][l]) x carry
+      wg_copy(t, TMP, (long)m * w);
+      wg_copy(d, TH, (long)2 * l0 * m);
+      if (tid == 0) dn[k] = m;
+      r = m;
+      __syncthreads();
+    }
+    // ---- pass 2: left to right, the cut
+    double fid = 1.0;
+    int lp = 1;
+    for (int k = 0; k < n - 1 && !bad; ++k) {
+      cd* const t = stage + so[k];
+      cd* const u = stage + so[k + 1];
+      const int rr = dn[k + 1], r2 = dn[k + 2], m2 = 2 * lp;
+      const bool cols = rr <= m2;  // the centre t ([m2][rr]) as it lies; otherwise its transpose
+      const int q = cols ? rr : m2;
+      if (cols) jacobi_auto<2>(t, rr, 1, m2, rr, VV, sig, ord, &sh, g.error, lds, lds_elems, TMP, LB, lbuf_elems, SPEC_CUT, 0.0);
+      else jacobi_auto<2>(t, 1, rr, rr, m2, VV, sig, ord, &sh, g.error, lds, lds_elems, TMP, LB, lbuf_elems, SPEC_CUT, 0.0);
+      __syncthreads();
+      if (tid == 0) {
+        double tot = 0;
+        for (int j = 0; j < q; ++j) tot += sig[j] * sig[j];
+        sh.nrm = tot;
+      }
+      __syncthreads();
+      const double tot = sh.nrm;
+      __syncthreads();
+      if (!(tot > 0.0)) {
+        bad = true;
+        break;
+      }
+      wg_kept(sig, ord, q, g.budget, g.zero * sqrt(tot), &sh, g.cap);
+      const int keep = sh.keep;
+      if (tid == 0) {  // what the cut drops, summed from the small end
+        double tail = 0;
+        for (int j = q - 1; j >= keep; --j) tail += sig[ord[j]] * sig[ord[j]];
+        sh.frac = tail / tot;
+      }
+      __syncthreads();
+      const double disc = sh.frac;
+      const double f = 1.0 / sqrt(1.0 - disc);
+      // cols: t = W V^H = [W / s] [s V^H];  rows: t^T = W V^H, so t = conj(V) W^T
+      for (int e = tid; e < m2 * keep; e += 256) {  // U[(a, p)][jj]
+        const int row = e / keep, jj = e - row * keep, c = ord[jj];
+        if (cols) {
+          const double inv = 1.0 / sig[c];
+          const cd x = t[(long)row * rr + c];
+          TMP[e] = cd{x.x * inv, x.y * inv};
+        } else {
+          const cd v = VV[(long)row * m2 + c];
+          TMP[e] = cd{v.x, -v.y};
+        }
+      }
+      for (int e = tid; e < keep * rr; e += 256) {  // (S V^H) f [jj][c]
+        const int jj = e / rr, col = e - jj * rr, c = ord[jj];
+        if (cols) {
+          const double s = sig[c] * f;
+          const cd v = VV[(long)col * rr + c];
+          CM[e] = cd{s * v.x, -s * v.y};
+        } else {
+          const cd x = t[(long)c * rr + col];
+          CM[e] = cd{x.x * f, x.y * f};
+        }
+      }
+      __syncthreads();
+      wg_gemm_mfma(TH, keep, 2 * r2, rr, CM, rr, 1, u, 2 * r2, 1);  // S V^H x next site ([rr][2 r2])
+      wg_copy(t, TMP, (long)m2 * keep);
+      wg_copy(u, TH, (long)keep * 2 * r2);
+      if (tid == 0) {
+        dn[k + 1] = keep;
+        g.discarded[st * (n - 1) + k] = disc;
+      }
+      fid *= 1.0 - disc;
+      lp = keep;
+      __syncthreads();
+    }
+    if (tid == 0) {
+      g.fidelity[st] = bad ? -1.0 : fid;
+      if (bad) {
+        atomicOr(g.error, ERR_NORM0);
+        atomicMax(g.error + 25, (int)st + 1);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+size_t qk_compress_work_bytes(const int qmax) {
+  const size_t q2 = (size_t)qmax * qmax, nbk = (size_t)spec_pad(qmax, 16) / 8;
+  return ((6 * q2 + (size_t)spec_lbuf_elems(qmax)) * sizeof(cd) + nbk * nbk * sizeof(int) + 255) / 256 * 256;
+}
+
+int qk_compress_launch(qk_ctx* c, QkCompressArgs a, const int grid, const char* what) {
+  if (a.qmax > SPEC_QMAX) return qk_fail(QK_EINVAL, "%s: a bond of %d is beyond the %d the factorisation's LDS bookkeeping holds", what, a.qmax, SPEC_QMAX);
+  HIP_TRY_AS(what, hipMemsetAsync(a.error, 0, 32 * sizeof(int), c->stream));
+  HIP_TRY_AS(what, hipFuncSetAttribute(reinterpret_cast<const void*>(qk_compress_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS));
+  qk_compress_kernel<<<dim3((unsigned)grid), dim3(256), SPEC_LDS, c->stream>>>(a, spec_lbuf_elems(a.qmax));
+  HIP_TRY_AS(what, hipGetLastError());
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  int errv[32] = {0};
+  HIP_TRY_AS(what, hipMemcpy(errv, a.error, sizeof errv, hipMemcpyDeviceToHost));
+  if (errv[0] & ERR_NORM0) return qk_fail(QK_EDEVICE, "%s: state %d has norm 0 (a site or a centre of the sweep is all zeros): nothing to compress", what, errv[25] - 1);
+  if (errv[0]) return qk_fail(QK_EDEVICE, "%s: a Jacobi factorisation did not converge in %d sweeps", what, MAX_SWEEPS);
+  return QK_OK;
+}
+
+extern "C" int qk_mps_set_compress(qk_ctx* c, const qk_mps_set* src, int32_t max_bond, double max_discard, double value_of_zero, qk_mps_set** out, double* fidelity,
+                                   double* discarded) {
+  static const char* what = "qk_mps_set_compress";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!src) return qk_fail(QK_EINVAL, "%s: src is null", what);
+  if (!out) return qk_fail(QK_EINVAL, "%s: out is null", what);
+  *out = nullptr;
+  if (src->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
+  if (src->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; compressing needs an fp64 set", what);
+  if (max_bond < 0) return qk_fail(QK_EINVAL, "%s: max_bond must be >= 0 (0: no cap), got %d", what, max_bond);
+  if (!(max_discard >= 0.0) || !std::isfinite(max_discard)) return qk_fail(QK_EINVAL, "%s: max_discard must be >= 0 and finite (got %g)", what, max_discard);
+  if (!(value_of_zero >= 0.0) || !std::isfinite(value_of_zero)) return qk_fail(QK_EINVAL, "%s: value_of_zero must be >= 0 and finite (got %g)", what, value_of_zero);
+  const int ns = src->n_states, n = src->n_sites, n1 = n + 1;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
+  const int32_t* tru = src->dims_true.data();
+  int qall = 1;
+  for (size_t e = 0; e < (size_t)ns * n1; ++e) qall = std::max(qall, (int)tru[e]);
+  if (qall > SPEC_QMAX) return qk_fail(QK_EINVAL, "%s: a bond of %d is beyond the %d the factorisation's LDS bookkeeping holds", what, qall, SPEC_QMAX);
+  QkRangeGuard range_("qk:compress");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  auto pad16 = [](int x) { return (x + 15) / 16 * 16; };
+  // a state's slots of the staging buffer (complex elements, by its input bonds); batches by the quarter-of-free-memory rule: the
+  // staging buffer takes at most half of it (at least one state), the workgroups' workspaces the rest (at least one workgroup)
+  std::vector<long long> need(ns, 0);
+  for (int s = 0; s < ns; ++s)
+    for (int k = 0; k < n; ++k) need[s] += 2ll * tru[(size_t)s * n1 + k] * tru[(size_t)s * n1 + k + 1];
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
+  const long long budget = (long long)(free_b / 4);
+  std::vector<int> bstart{0};
+  for (long long acc = 0, s = 0; s < ns; ++s) {
+    const long long w = need[s] * (long long)sizeof(cd);
+    if (acc > 0 && acc + w > budget / 2) bstart.push_back((int)s), acc = 0;
+    acc += w;
+  }
+  bstart.push_back(ns);
+  QkDevBuf d_new, d_fid, d_disc, d_err, d_so, d_dst, d_pad;
+  const size_t n_disc = std::max<size_t>(1, (size_t)ns * (n - 1));
+  HIP_TRY_AS(what, d_new.alloc((size_t)ns * n1 * sizeof(int32_t)));
+  HIP_TRY_AS(what, d_fid.alloc((size_t)ns * sizeof(double)));
+  HIP_TRY_AS(what, d_disc.alloc(n_disc * sizeof(double)));
+  HIP_TRY_AS(what, d_err.alloc(32 * sizeof(int)));
+  HIP_TRY_AS(what, d_so.alloc((size_t)ns * n * sizeof(long long)));
+  HIP_TRY_AS(what, d_dst.alloc((size_t)ns * n * sizeof(long long)));
+  HIP_TRY_AS(what, d_pad.alloc((size_t)ns * n1 * sizeof(int32_t)));
+  HIP_TRY_AS(what, hipMemsetAsync(d_disc.get(), 0, n_disc * sizeof(double), c->stream));
+  std::vector<long long> so((size_t)ns * n), dst((size_t)ns * n);
+  std::vector<int32_t> dims_new((size_t)ns * n1), pad_new((size_t)ns * n1);
+  std::vector<QkDevBuf> chunks(bstart.size() - 1);  // the packed planes of each batch, until the new set is put together
+  std::vector<long long> chunk_doubles(bstart.size() - 1, 0);
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+    long long stage_elems = 0;
+    int qmax = 1;
+    for (int s = s0; s < s0 + nb; ++s)
+      for (int k = 0; k < n; ++k) {
+        so[(size_t)s * n + k] = stage_elems;
+        stage_elems += 2ll * tru[(size_t)s * n1 + k] * tru[(size_t)s * n1 + k + 1];
+        qmax = std::max(qmax, (int)tru[(size_t)s * n1 + k]);
+      }
+    const size_t per_wg = qk_compress_work_bytes(qmax);
+    const long long room = budget - stage_elems * (long long)sizeof(cd);
+    const int grid = (int)std::max<long long>(1, std::min<long long>({(long long)nb, 2ll * c->num_cus, room / (long long)per_wg}));
+    QkDevBuf stage, work;
+    HIP_TRY_AS(what, stage.alloc((size_t)stage_elems * sizeof(cd)));
+    HIP_TRY_AS(what, work.alloc((size_t)grid * per_wg));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_so.get<long long>() + (size_t)s0 * n, so.data() + (size_t)s0 * n, (size_t)nb * n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    QkCompressArgs a{};
+    a.planes = src->d_data.get<double>(), a.pad = src->d_dims.get<int32_t>(), a.tru = src->d_true.get<int32_t>(), a.offs = src->d_offs.get<int64_t>();
+    a.s0 = s0, a.n_batch = nb, a.n_sites = n;
+    a.stage = stage.get<double>(), a.stage_offs = d_so.get<long long>() + (size_t)s0 * n;
+    a.dims_new = d_new.get<int32_t>(), a.fidelity = d_fid.get<double>(), a.discarded = d_disc.get<double>();
+    a.cap = max_bond, a.budget = max_discard, a.zero = value_of_zero;
+    a.work = work.get<char>(), a.work_bytes = (long long)per_wg, a.qmax = qmax, a.error = d_err.get<int>();
+    if (const int rc = qk_compress_launch(c, a, grid, what)) return rc;  // synchronises and reads the error word
+    // the new bonds of the batch -> its padded planes
+    HIP_TRY_AS(what, hipMemcpy(dims_new.data() + (size_t)s0 * n1, d_new.get<int32_t>() + (size_t)s0 * n1, (size_t)nb * n1 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    long long doubles = 0;
+    for (int s = s0; s < s0 + nb; ++s) {
+      for (int k = 0; k <= n; ++k) {
+        const int32_t x = dims_new[(size_t)s * n1 + k];
+        if (x < 1 || x > tru[(size_t)s * n1 + k]) return qk_fail(QK_EDEVICE, "%s: state %d came back with bond %d of %d (was %d)", what, s, k, (int)x, (int)tru[(size_t)s * n1 + k]);
+        pad_new[(size_t)s * n1 + k] = pad16(x);
+      }
+      for (int k = 0; k < n; ++k) {
+        dst[(size_t)s * n + k] = doubles;
+        doubles += 2ll * pad_new[(size_t)s * n1 + k] * 2 * pad_new[(size_t)s * n1 + k + 1];
+      }
+    }
+    chunk_doubles[bi] = doubles;
+    HIP_TRY_AS(what, chunks[bi].alloc((size_t)doubles * sizeof(double)));
+    HIP_TRY_AS(what, hipMemsetAsync(chunks[bi].get(), 0, (size_t)doubles * sizeof(double), c->stream));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_dst.get<long long>() + (size_t)s0 * n, dst.data() + (size_t)s0 * n, (size_t)nb * n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_pad.get<int32_t>() + (size_t)s0 * n1, pad_new.data() + (size_t)s0 * n1, (size_t)nb * n1 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    qk_pack_built_kernel<<<dim3((unsigned)(nb * n)), dim3(256), 0, c->stream>>>(stage.get<cd>(), d_so.get<long long>() + (size_t)s0 * n, d_dst.get<long long>() + (size_t)s0 * n,
+                                                                              d_new.get<int32_t>() + (size_t)s0 * n1, d_pad.get<int32_t>() + (size_t)s0 * n1, n, chunks[bi].get<double>());
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staging buffer and the workspaces go before the next batch
+  }
+  long long total = 0;
+  int max_pad = 0;
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {  // offsets within a batch's planes -> offsets within the set
+    for (size_t e = (size_t)bstart[bi] * n; e < (size_t)bstart[bi + 1] * n; ++e) dst[e] += total;
+    total += chunk_doubles[bi];
+  }
+  for (int32_t x : pad_new) max_pad = std::max(max_pad, (int)x);
+  qk_mps_set* m = nullptr;
+  if (const int rc = qk_mps_set_alloc(c, ns, n, total * (long long)sizeof(double), 64, &m, what)) return rc;
+  m->max_pad = max_pad;
+  m->dims_true = dims_new;
+  hipError_t e = hipSuccess;
+  long long pos = 0;
+  for (size_t bi = 0; bi + 1 < bstart.size() && e == hipSuccess; ++bi) {
+    e = hipMemcpyAsync(m->d_data.get<double>() + pos, chunks[bi].get(), (size_t)chunk_doubles[bi] * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+    pos += chunk_doubles[bi];
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_dims.get(), pad_new.data(), pad_new.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_true.get(), dims_new.data(), dims_new.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_offs.get(), dst.data(), dst.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess && fidelity) e = hipMemcpy(fidelity, d_fid.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && discarded && n > 1) e = hipMemcpy(discarded, d_disc.get(), (size_t)ns * (n - 1) * sizeof(double), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    qk_mps_set_destroy(m);
+    return qk_fail(QK_EDEVICE, "%s: %s", what, hipGetErrorString(e));
+  }
+  *out = m;
   return QK_OK;
 }
 

@@ -115,6 +115,30 @@ size_t qk_bond_spectra_work_bytes(int qmax);
 // launches, waits and turns a factorisation that did not converge into QK_EDEVICE
 int qk_bond_spectra_launch(qk_ctx* c, QkSpectraArgs a, int grid, const char* what);
 
+// the compress sweep (qk_build.hip: qk_compress_kernel, qk_mps_set_compress): the states of a batch, taken in turn by `grid`
+// workgroups with one workspace each; a state's sites live in its slots of the staging buffer from the first read to the pack
+struct QkCompressArgs {
+  const double* planes;   // the source set's padded split planes and its tables
+  const int32_t* pad;     // padded bonds [n_states][n_sites + 1]
+  const int32_t* tru;     // true bonds
+  const int64_t* offs;    // re-plane offsets (doubles) [n_states][n_sites]
+  int s0, n_batch, n_sites;
+  double* stage;              // interleaved complex: site (s0 + i, k) at stage + 2 * stage_offs[i * n_sites + k], sized by the input bonds
+  const long long* stage_offs;
+  int32_t* dims_new;      // [n_states][n_sites + 1]: after pass 1 the ranks, after pass 2 the new bonds
+  double* fidelity;       // [n_states]
+  double* discarded;      // [n_states][n_sites - 1]
+  int cap;                // 0: no cap
+  double budget, zero;
+  char* work;             // workgroup w: work + w * work_bytes
+  long long work_bytes;
+  int qmax;               // largest true bond of the batch
+  int* error;             // 32 ints, zeroed by the launcher: [0] error bits, the Jacobi statistics, [25] 1 + a state of norm 0
+};
+size_t qk_compress_work_bytes(int qmax);
+// launches, waits and turns a factorisation that did not converge or a state of norm 0 into QK_EDEVICE
+int qk_compress_launch(qk_ctx* c, QkCompressArgs a, int grid, const char* what);
+
 struct SweepArgs;
 // qk_lab.hip: raise the LDS limit of the lab kernels; launch lab variant `variant` (returns QK_EINVAL if it is not one)
 int qk_lab_init(qk_ctx* c);

@@ -74,6 +74,7 @@ _SIGNATURES = [
     ("qk_mps_set_from_packed", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.POINTER(_P)]),
     ("qk_mps_set_precision", C.c_int, [_P]),
     ("qk_mps_set_to_f32", C.c_int, [_P, _P, C.POINTER(_P)]),
+    ("qk_mps_set_compress", C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.POINTER(_P), _P, _P]),
     ("qk_pack_state_size", C.c_int64, [C.c_int32, _P]),
     ("qk_pack_state", C.c_int, [C.c_int32, _P, _P, C.c_int32, _P, _P]),
     ("qk_plan_create", C.c_int, [C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
@@ -328,6 +329,28 @@ def pack_state(mps, layout=QK_LAYOUT_LPR):
     return out, offs
 
 
+def unpack_state(planes, dims, offsets) -> list:
+    """Host-only, pure numpy, the inverse of ``pack_state``: the site tensors ``[left bond, 2, right bond]`` (complex128) of one
+    state from a padded split-plane image.  ``planes``: the doubles of the image; ``dims``: the state's true bonds chi[0..n];
+    ``offsets``: the re-plane offset of every site in doubles (the im plane follows its re plane)."""
+    planes = np.asarray(planes, dtype=np.float64).reshape(-1)
+    dims = [int(d) for d in np.asarray(dims).reshape(-1)]
+    offsets = [int(o) for o in np.asarray(offsets).reshape(-1)]
+    if len(offsets) != len(dims) - 1:
+        raise ValueError(f"{len(dims)} bond dimensions need {len(dims) - 1} site offsets, got {len(offsets)}")
+    tensors = []
+    for k, off in enumerate(offsets):
+        l, r = dims[k], dims[k + 1]
+        pl, pr = (l + 15) // 16 * 16, (r + 15) // 16 * 16
+        plane = pl * 2 * pr
+        if l < 1 or r < 1 or off < 0 or off + 2 * plane > planes.size:
+            raise ValueError(f"site {k}: bonds ({l}, {r}) at offset {off} do not lie inside an image of {planes.size} doubles")
+        re = planes[off : off + plane].reshape(pl, 2, pr)[:l, :, :r]
+        im = planes[off + plane : off + 2 * plane].reshape(pl, 2, pr)[:l, :, :r]
+        tensors.append(re + 1j * im)
+    return tensors
+
+
 class Plan:
     """Ordered share of the Gram's (x, y) pairs for one rank (host object)."""
 
@@ -467,6 +490,15 @@ class MpsSet:
     def copy_image(self, dst_ptr: int, n_doubles: int):
         """Copy the planes into a device or host buffer of ``n_doubles`` doubles (the send buffer of the all-gather)."""
         _check(lib().qk_mps_set_copy_image(self._h, _P(dst_ptr), int(n_doubles)), "qk_mps_set_copy_image")
+
+    def download(self) -> list:
+        """The states of an fp64 set back on the host, as ``list[MPS]``: the true-bond corners of the device image."""
+        from .mps import MPS
+
+        n_doubles, _, dims, offs = self.image()
+        planes = np.empty(n_doubles, dtype=np.float64)
+        self.copy_image(planes.ctypes.data, n_doubles)
+        return [MPS(unpack_state(planes, dims[s], offs[s])) for s in range(dims.shape[0])]
 
     @property
     def precision(self) -> int:
@@ -885,6 +917,30 @@ class Context:
         _check(lib().qk_bond_spectra_host(self._h, mps_set.handle, m, out.ctypes.data, nrm.ctypes.data), "qk_bond_spectra_host")
         out = out[:, : n - 1]
         return (out, nrm) if norms else out
+
+    def compress(self, mps_set: MpsSet, max_bond: int | None = None, max_discard: float = 0.0, value_of_zero: float = 1e-16, info: bool = False):
+        """A new fp64 set with every state of ``mps_set`` truncated once, in canonical form (the device twin of ``MPS.compress``,
+        which documents the rule): at most ``max_bond`` values per bond (``None`` or 0: no cap), at most ``max_discard`` of the weight
+        dropped per bond, singular values <= ``value_of_zero`` sqrt(weight) dropped.  Norms are kept, sites 0 .. n-2 of the result
+        are left isometries, its ``.dims`` is the new bond table; ``mps_set`` is left untouched.  ``info=True`` returns ``(set,
+        {"fidelity": (n_states,), "discarded": (n_states, n_sites - 1), "bond_dims": (n_states, n_sites + 1)})`` with fidelity =
+        |<psi|psi'>|^2 / (<psi|psi> <psi'|psi'>), the product over the bonds of 1 - discarded.  A state's result is the same bits
+        whatever the other states of the set.  Synchronous."""
+        cap = 0 if max_bond is None else max_bond
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)):
+            raise ValueError(f"max_bond must be an int >= 0 or None (no cap), got {max_bond!r}")
+        st = mps_set.info()
+        ns, n = st["n_states"], st["n_sites"]
+        fid = np.zeros(ns, dtype=np.float64)
+        disc = np.zeros((ns, max(n - 1, 1)), dtype=np.float64)
+        h = _P()
+        _check(lib().qk_mps_set_compress(self._h, mps_set.handle, int(cap), float(max_discard), float(value_of_zero), C.byref(h), fid.ctypes.data, disc.ctypes.data),
+               "qk_mps_set_compress")
+        out = MpsSet(self, h, np.zeros((ns, n + 1), dtype=np.int32))
+        out.dims = out.image()[2]
+        if not info:
+            return out
+        return out, {"fidelity": fid, "discarded": disc[:, : n - 1], "bond_dims": out.dims.copy()}
 
     def feature_gram(self, fx, fy=None, gamma=None) -> np.ndarray:
         """Gram of real feature columns (``pauli_expectations``): K[j, i] = exp(-gamma sum_m (fx[i, m] - fy[j, m])^2), shape (ny, nx),

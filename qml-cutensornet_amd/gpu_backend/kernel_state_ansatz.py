@@ -589,3 +589,100 @@ def build_entanglement_profile(mpi_comm, ansatz, X, truncation_error=None, max_v
         with open(info_file + ".json", "w") as fp:
             json.dump(prof, fp, indent=4)
     return out
+
+
+def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64), max_discard=0.0, truncation_error=None, info_file=None, loglevel=30):
+    """The Gram ``K`` of ``build_kernel_matrix`` and, from the SAME states, the Gram under each bond cap of ``caps``: one build, then
+    per cap every rank compresses its share on its device (``Context.compress``: one canonical truncation sweep per state, at
+    most ``max_discard`` of the weight dropped per bond besides the cap), the compressed shares are exchanged like the full ones
+    and the Gram is swept again.  Rank 0 returns the dict
+        K          (len(Y), len(X))                 the Gram of the states as built
+        K_capped   {cap: (len(Y), len(X))}          the Gram of the states compressed to the cap
+        fidelity   {cap: (len(X) [+ len(Y)],)}      |<psi|psi'>|^2 of every state and its compressed twin, X first
+        bond_dims  {cap: (len(X) [+ len(Y)], n+1)}  the new bond table
+    and the other ranks ``None``.  |K_capped - K| is bounded absolutely, not relatively: for normalised states by d (2 + d), d =
+    delta_i + delta_j + delta_i delta_j, delta = sqrt(2 - 2 sqrt(fidelity))."""
+    if Y is not None and len(X) < len(Y):
+        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    caps = [c for c in caps]
+    if not caps or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 1 for c in caps) or len(set(caps)) != len(caps):
+        raise ValueError(f"caps must be distinct ints >= 1, got {caps!r}")
+    if not (float(max_discard) >= 0.0 and np.isfinite(float(max_discard))):
+        raise ValueError(f"max_discard must be >= 0 and finite, got {max_discard!r}")
+    X = np.asarray(X, dtype=np.float64)
+    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
+    fidelity = 1.0 - float(truncation_error)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    n_qubits = int(ansatz.num_qubits)
+    t_start = time.perf_counter()
+    ctx = _engine.default_context(device_id)
+    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
+    shares = [(len(X),) + tuple(_simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers))]
+    if Y is not None:
+        _say(is_root, "\nContracting the MPS of the circuits from the Y dataset...")
+        shares.append((len(Y),) + tuple(_simulate_share(ansatz, Y, rank, n_procs, fidelity, is_root, "Y", device_id, host_workers)))
+    ctx.trim()
+    build_secs = time.perf_counter() - t_start
+
+    def gram_of(local_sets):
+        """exchange the shares, sweep, close what the exchange made"""
+        full = [exchange_sets(mpi_comm, ctx, loc, lo, total)[0] for loc, (total, lo, _, _, _) in zip(local_sets, shares)]
+        try:
+            K, _ = _gram_on_device(mpi_comm, rank, n_procs, ctx, full[0], full[1] if len(full) > 1 else None)
+        finally:
+            for f, loc in zip(full, local_sets):
+                if f is not loc:
+                    f.close()
+        return K
+
+    locals_ = [s[2] for s in shares]
+    out = {"K": None, "K_capped": {}, "fidelity": {}, "bond_dims": {}}
+    secs = {}
+    try:
+        out["K"] = gram_of(locals_)
+        for cap in caps:
+            t0 = time.perf_counter()
+            small, fids, dims = [], [], []
+            try:
+                for (total, lo, loc, _, _) in shares:
+                    if loc is None:
+                        small.append(None)
+                        fid_s, dims_s = np.zeros(0), np.zeros((0, n_qubits + 1))
+                    else:
+                        cs, info = ctx.compress(loc, max_bond=int(cap), max_discard=float(max_discard), info=True)
+                        small.append(cs)
+                        fid_s, dims_s = info["fidelity"], info["bond_dims"].astype(np.float64)
+                    fids.append(_gather_features(mpi_comm, lo, fid_s, total))
+                    dims.append(_gather_features(mpi_comm, lo, dims_s, total))
+                secs[cap] = time.perf_counter() - t0
+                out["K_capped"][cap] = gram_of(small)
+            finally:
+                for cs in small:
+                    if cs is not None:
+                        cs.close()
+            out["fidelity"][cap] = np.concatenate(fids)
+            out["bond_dims"][cap] = np.concatenate(dims).astype(np.int32)
+    finally:
+        for loc in locals_:
+            if loc is not None:
+                loc.close()
+    if not is_root:
+        return None
+    if info_file is not None:
+        prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"],
+                "r0_circ_sim": [build_secs, "seconds"], "caps": [[int(c) for c in caps], "chi"],
+                "r0_compress": [[secs[c] for c in caps], "seconds"], "min_fidelity": [[float(out["fidelity"][c].min()) for c in caps], ""],
+                "total_time": [time.perf_counter() - t_start, "seconds"]}
+        with open(info_file + ".json", "w") as fp:
+            json.dump(prof, fp, indent=4)
+    return out

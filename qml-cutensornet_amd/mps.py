@@ -94,6 +94,58 @@ class MPS:
             centre = np.tensordot(s[:, None] * vh, ts[k], axes=(1, 0))
         return out
 
+    def compress(self, max_bond: int | None = None, max_discard: float = 0.0, value_of_zero: float = 1e-16):
+        """The state truncated once, in canonical form: ``(MPS, discarded)``, the host mirror of ``Context.compress``.  The
+        ``bond_spectra`` sweep with a cut: the chain is right-orthonormalised from the last site (a bond keeps its singular values
+        above ``value_of_zero`` times the Frobenius norm of the site's matrix, so a rank-deficient bond shrinks to its rank), then the centre moves to the right with one
+        SVD per bond.  At bond k, with the singular values descending and total = sum sigma^2: values <= ``value_of_zero``
+        sqrt(total) go, then the smallest ones while their summed weight stays <= ``max_discard`` total (``_kept``), then whatever
+        exceeds ``max_bond``; at least one stays.  What is kept is scaled by sqrt(total / kept), so <psi'|psi'> = <psi|psi>: the norm
+        sits in the last site and sites 0 .. n-2 are left isometries.  ``discarded[k - 1]`` = 1 - kept / total at bond k (the
+        dropped weights summed from the small end) and ``.fidelity`` of the result is the product of kept / total in bond order --
+        which is |<psi|psi'>|^2 / (<psi|psi> <psi'|psi'>), because the projectors of successive bonds are nested."""
+        out, discarded, _ = self._compress(max_bond, max_discard, value_of_zero)
+        return out, discarded
+
+    def _compress(self, max_bond, max_discard, value_of_zero):
+        """``compress`` and, third, the singular values the cut of every bond was made on (descending, before the cut)."""
+        cap = 0 if max_bond is None else int(max_bond)
+        budget, zero = float(max_discard), float(value_of_zero)
+        if cap < 0 or (max_bond is not None and cap != max_bond):
+            raise ValueError(f"max_bond must be an int >= 1, or None / 0 for no cap (got {max_bond!r})")
+        if not (budget >= 0.0 and np.isfinite(budget)) or not (zero >= 0.0 and np.isfinite(zero)):
+            raise ValueError(f"max_discard and value_of_zero must be >= 0 and finite (got {max_discard!r}, {value_of_zero!r})")
+        n = len(self.tensors)
+        ts = [np.array(t, dtype=np.complex128) for t in self.tensors]
+        for k in range(n - 1, 0, -1):
+            l, _, r = ts[k].shape
+            u, s, vh = np.linalg.svd(ts[k].reshape(l, 2 * r).T, full_matrices=False)  # (2r, l) = u s vh
+            total = float((s * s).sum())
+            if not total > 0.0:
+                raise ValueError("compress: the state has norm 0")
+            m = max(int(np.count_nonzero(s > zero * np.sqrt(total))), 1)
+            ts[k] = u[:, :m].T.reshape(m, 2, r)
+            ts[k - 1] = np.tensordot(ts[k - 1], (s[:m, None] * vh[:m]).T, axes=(2, 0))
+        discarded = np.zeros(n - 1, dtype=np.float64)
+        fidelity, sigmas = 1.0, []
+        for k in range(n - 1):
+            l, _, r = ts[k].shape
+            u, s, vh = np.linalg.svd(ts[k].reshape(l * 2, r), full_matrices=False)
+            w = s * s
+            total = float(w.sum())
+            sigmas.append(s)
+            if not total > 0.0:
+                raise ValueError("compress: the state has norm 0")
+            m, _ = _kept(s, budget, zero * np.sqrt(total))
+            if cap > 0:
+                m = min(m, cap)
+            d = float(w[m:][::-1].sum()) / total
+            discarded[k] = d
+            fidelity *= 1.0 - d
+            ts[k] = u[:, :m].reshape(l, 2, m)
+            ts[k + 1] = np.tensordot((s[:m, None] * vh[:m]) / np.sqrt(1.0 - d), ts[k + 1], axes=(1, 0))
+        return MPS(ts, fidelity), discarded, sigmas
+
     def vdot(self, other: "MPS") -> complex:
         """<self|other> through the HIP engine (single pair; the Gram path is batch-first)."""
         from .engine import default_context

@@ -8,7 +8,9 @@ ctx.local_pair_paulis(xs, max_dist=D) and ctx.projected_pair_gram(T, max_dist=D)
 IXYZ per line) adds ctx.pauli_expectations(xs, strings) and ctx.feature_gram(V): pauli_strings_ms, n_strings, sum_support.
 ``--entanglement`` adds ctx.bond_purities(xs) and ctx.bond_spectra(xs): bond_purities_ms, bond_spectra_ms, and what a bond cap
 would discard, ``cap_cost`` summed over the bonds of a state at chi = 16, 32, 64, 128 (the mean and the largest over the states).
-usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement]"""
+``--compress CHI`` adds ctx.compress(xs, max_bond=CHI) and the Gram of the compressed set: compress_ms, compressed_gram_ms,
+compressed_max_bond, min_fidelity and max_abs_dK = max |K(compressed) - K|.
+usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement] [--compress CHI]"""
 import argparse
 import json
 import os
@@ -83,6 +85,7 @@ def main():
     ap.add_argument("--strings", type=int, default=0, help="also time pauli_expectations on this many sparse Pauli strings")
     ap.add_argument("--strings-file", default=None, help="also time pauli_expectations on the strings of this file (one per line over IXYZ)")
     ap.add_argument("--entanglement", action="store_true", help="also time bond_purities and bond_spectra and print the cost of a bond cap")
+    ap.add_argument("--compress", type=int, default=0, metavar="CHI", help="also time compress(max_bond=CHI) and the Gram of the compressed set")
     args = ap.parse_args()
     gamma = args.gamma if args.gamma is not None else (0.1 if args.config == "cfg5" else 1.0)
     n, reps, d, npts = bench.CONFIGS[args.config]
@@ -140,6 +143,20 @@ def main():
             "median_max_entropy_S1": float(np.median(s1.max(axis=1))),
             "median_weights_above_1e-3": float(np.median(engine.schmidt_rank(S, 1e-3).max(axis=1))),
             "cap_cost": {str(chi): {"mean": float(c.mean()), "max": float(c.max())} for chi, c in costs.items()},
+        })
+    if args.compress > 0:
+        def squeeze():
+            cs, cinfo = ctx.compress(xs, max_bond=args.compress, info=True)
+            cs.close()
+            return cinfo
+
+        cinfo, compress_ms = timed(squeeze, args.reps)
+        with ctx.compress(xs, max_bond=args.compress) as cs:
+            KC, cgram_ms = timed(lambda: ctx.gram(cs), args.reps)
+        dist.update({
+            "compress_chi": int(args.compress), "compress_ms": round(compress_ms, 3), "compressed_gram_ms": round(cgram_ms, 3),
+            "compressed_max_bond": int(cinfo["bond_dims"].max()), "min_fidelity": float(cinfo["fidelity"].min()),
+            "max_abs_dK": float(np.abs(KC - K).max()),
         })
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
