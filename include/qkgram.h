@@ -507,6 +507,29 @@ int qk_built_download(const qk_built* built, double* host /* 2 * total_complex d
  * device: nothing crosses PCIe between the builder and the sweep.  The set is independent of `built` afterwards.  */
 int qk_mps_set_from_built(qk_ctx* ctx, const qk_built* built, qk_mps_set** out);
 int qk_built_destroy(qk_built* built);
+/* Snapshots and resume, for scans over the depth of a circuit.  qk_build_mps_scan is qk_build_mps that ALSO keeps the state after
+ * checkpoints[j] gates (counted from 1), j = 0 .. n_checkpoints-1: strictly increasing, each in 1..n_ops, the last one n_ops.  A
+ * snapshot is a copy: the run does the arithmetic of a run without checkpoints, and its last snapshot is the result of qk_build_mps
+ * (whose accessors above read the last snapshot).  A snapshot is in mixed-canonical gauge, with its orthogonality centre recorded.
+ * All snapshots share the one heap, so it is sized for n_checkpoints states per state (QK_EDEVICE if it turns out too small).
+ * `initial` (may be NULL) resumes: every state starts as snapshot `initial_snapshot` of `initial` -- same context, n_states and
+ * n_qubits, no dropped state, no bond above max_bond, else QK_EINVAL -- instead of |0...0>, and op / q0 / alpha are the gates that
+ * FOLLOW it; the fidelity goes on from the snapshot's.  `initial` is only read.  Resuming snapshot j of a run with that run's gates
+ * from checkpoints[j] on is gate for gate the arithmetic of the uninterrupted run.  QK_BUILD_PARTIAL with more than one
+ * checkpoint or with `initial` is QK_EINVAL.                                                                                      */
+int qk_build_mps_scan(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
+                      const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
+                      int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
+                      qk_built** out);
+int qk_built_num_snapshots(const qk_built* built);                        /* 1 for qk_build_mps */
+int qk_built_checkpoints(const qk_built* built, int32_t* checkpoints);    /* [num_snapshots] gates done at each snapshot */
+/* Snapshot j: dims[n_states][n_qubits+1], fidelity so far [n_states], offsets[n_states] into the one heap (complex elements),
+ * centre[n_states] (site of the orthogonality centre), complex elements of the snapshot's states together; any may be NULL */
+int qk_built_info_at(const qk_built* built, int32_t j, int32_t* dims, double* fidelity, int64_t* offsets, int32_t* centre,
+                     int64_t* total_complex);
+/* The states of snapshot j, packed back to back in state order (2 * total_complex doubles of qk_built_info_at) */
+int qk_built_download_at(const qk_built* built, int32_t j, double* host);
+int qk_mps_set_from_built_at(qk_ctx* ctx, const qk_built* built, int32_t j, qk_mps_set** out); /* qk_mps_set_from_built of snapshot j */
 /* Diagnostic: the builder's Jacobi primitive on one host matrix a[p][q] (complex128 row-major, overwritten by A V);
  * v_out[q][q], sig_out[q] = column norms of A V, ord_out[q] = columns by decreasing norm.                          */
 int qk_debug_jacobi(qk_ctx* ctx, int32_t p, int32_t q, double* a_inout, double* v_out, double* sig_out, int32_t* ord_out);

@@ -93,6 +93,14 @@ class BoundCircuit:
             out.append((_OP_NAMES[o], qubits, [a] if o in _PARAMETRISED else []))
         return out
 
+    def sliced(self, a, b) -> "BoundCircuit":
+        """The same qubits with gates a .. b-1 of the program (0 <= a <= b <= n_gates): ``sliced(0, c)`` is the circuit a checkpoint
+        at c gates has run, ``sliced(c, n_gates)`` what a build resumed from that snapshot still has to run."""
+        a, b = int(a), int(b)
+        if not 0 <= a <= b <= self.n_gates:
+            raise ValueError(f"sliced({a}, {b}): want 0 <= a <= b <= {self.n_gates} gates")
+        return BoundCircuit(self.n_qubits, self.op[a:b], self.q0[a:b], self.alpha[a:b])
+
     @classmethod
     def from_gates(cls, n_qubits, gates) -> "BoundCircuit":
         """A gate list in the shape of the reference's CPU backend -- ``(name, qubits, params)`` with the names of
@@ -117,6 +125,36 @@ class BoundCircuit:
             for o, q, k in _route(code, qubits, n):
                 op.append(o), q0.append(q), alpha.append(a if k else 0.0)
         return cls(n, np.asarray(op, dtype=np.int8), np.asarray(q0, dtype=np.int32), np.asarray(alpha, dtype=np.float64))
+
+
+def check_checkpoints(checkpoints, n_gates) -> list:
+    """The checkpoints of a scan build as a list of ints, or ``ValueError``: gate counts, strictly increasing, each in 1 .. n_gates,
+    the last one ``n_gates`` (the finished circuit is always the last snapshot)."""
+    try:
+        cps = [int(c) for c in checkpoints]
+        exact = all(c == k for c, k in zip(checkpoints, cps))
+    except (TypeError, ValueError):
+        raise ValueError(f"checkpoints must be a list of gate counts, got {checkpoints!r}") from None
+    if not cps:
+        raise ValueError("checkpoints is empty: a scan needs at least the finished circuit")
+    if not exact or any(not 1 <= c <= int(n_gates) for c in cps):
+        raise ValueError(f"checkpoints must be ints in 1 .. {int(n_gates)} (gates done), got {list(checkpoints)!r}")
+    if any(b <= a for a, b in zip(cps, cps[1:])):
+        raise ValueError(f"checkpoints must be strictly increasing, got {cps!r}")
+    if cps[-1] != int(n_gates):
+        raise ValueError(f"the last checkpoint must be the whole program ({int(n_gates)} gates), got {cps[-1]}")
+    return cps
+
+
+def check_depths(depths, reps) -> list:
+    """The depths of a depth scan as a list of ints, or ``ValueError``: distinct, each in 1 .. ``reps``."""
+    try:
+        ds = list(depths)
+    except TypeError:
+        raise ValueError(f"depths must be a list of layer counts, got {depths!r}") from None
+    if not ds or any(isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 1 <= d <= int(reps) for d in ds) or len(set(ds)) != len(ds):
+        raise ValueError(f"depths must be distinct ints in 1 .. reps = {int(reps)}, got {ds!r}")
+    return [int(d) for d in ds]
 
 
 def _arity(o) -> int:
@@ -212,6 +250,7 @@ class KernelStateAnsatz:
                 emit(OP_XX, hi - 1, a, b, xx_scale)
                 for q in range(hi - 2, lo - 1, -1):  # and back
                     emit(OP_SWAP, q)
+        self._n_head = n if self.hadamard_init else 0
         self.ansatz_circ = GateProgram(
             n,
             np.asarray(op, dtype=np.int8),
@@ -220,6 +259,14 @@ class KernelStateAnsatz:
             np.asarray(fb, dtype=np.int32),
             np.asarray(sc, dtype=np.float64),
         )
+
+    def layer_ends(self) -> list:
+        """Gate counts after layers 1 .. reps: ``[n_h + r L]`` with n_h the Hadamards in front and L the gates of one layer.  The
+        ansatz emits the same layer ``reps`` times, so the first ``layer_ends()[r - 1]`` gates of a bound circuit ARE the bound
+        circuit of the ansatz with r layers: the checkpoints of a depth scan."""
+        total = self.ansatz_circ.n_gates
+        per_layer = (total - self._n_head) // self.reps if self.reps > 0 else 0
+        return [self._n_head + r * per_layer for r in range(1, self.reps + 1)]
 
     def circuit_for_data(self, feature_values) -> BoundCircuit:
         """Bind one data point.  ``RuntimeError`` on a length mismatch, as ref :96-97."""
@@ -301,6 +348,11 @@ class CircuitAnsatz:
         dt = {"op": np.int8, "q0": np.int32, "fa": np.int32, "fb": np.int32}
         arr = {k: np.asarray(v, dtype=dt.get(k, np.float64)) for k, v in cols.items()}
         self.ansatz_circ = CircuitProgram(n, **arr)
+
+    def layer_ends(self) -> list:
+        """A custom gate template has no layer structure of its own: one entry, the whole program.  A scan build
+        (``Context.build_mps_scan``, ``simulate(..., checkpoints=)``) takes any gate counts as checkpoints."""
+        return [self.ansatz_circ.n_gates]
 
     def circuit_for_data(self, feature_values) -> BoundCircuit:
         """Bind one data point.  ``RuntimeError`` on a length mismatch, as reference G:96-97."""

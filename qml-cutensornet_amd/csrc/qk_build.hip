@@ -51,10 +51,18 @@ struct BuildArgs {
   cd* heap;
   unsigned long long heap_cap;
   unsigned long long* heap_top;
-  int32_t* dims_out;    // [n_states][n_qubits + 1]
-  double* fid_out;      // [n_states]
-  double* secs_out;     // [n_states] seconds of workgroup time the state took (device clock)
-  long long* offs_out;  // [n_states] complex elements into heap
+  int n_ckpt;              // snapshots per state: after ckpt[j] gates (strictly increasing, the last one n_ops)
+  const int32_t* ckpt;     // [n_ckpt]
+  int32_t* dims_out;       // [n_ckpt][n_states][n_qubits + 1]
+  double* fid_out;         // [n_ckpt][n_states] the fidelity product so far
+  double* secs_out;        // [n_states] seconds of workgroup time the state took (device clock)
+  long long* offs_out;     // [n_ckpt][n_states] complex elements into heap
+  int32_t* centre_out;     // [n_ckpt][n_states] the site of the orthogonality centre
+  const cd* init_heap;     // a resumed build: the heap of the source (null: every state starts as |0...0>), and of its snapshot ...
+  const long long* init_offs;   // [n_states] ... the offsets,
+  const int32_t* init_dims;     // [n_states][n_qubits + 1] the bond tables (<= cap),
+  const double* init_fid;       // [n_states] the fidelities
+  const int32_t* init_centre;   // [n_states] and the centres
   unsigned long long* counter;
   int* error;     // [0] error bits, [1..4] Jacobi statistics: factorisations, sweeps, most sweeps, unconverged
   int jl_offset;  // doubles from the start of the dynamic LDS to the Jacobi working set
@@ -541,30 +549,71 @@ extern "C" int qk_mps_set_compress(qk_ctx* c, const qk_mps_set* src, int32_t max
 struct qk_built {
   qk_ctx* ctx = nullptr;
   int n_states = 0, n_qubits = 0;
-  QkDevBuf heap;  // cd: the packed states
-  std::vector<int32_t> dims;
+  QkDevBuf heap;  // cd: the packed states, every snapshot of every state (a slot each, in the order the workgroups took them)
+  std::vector<int32_t> checkpoints;  // gates done at each snapshot; the last one is the whole program
+  // per snapshot j and state s at [j * n_states + s]: bond table, fidelity so far, offset into the heap, orthogonality centre
+  std::vector<int32_t> all_dims;
+  std::vector<double> all_fidelity;
+  std::vector<int64_t> all_offsets;
+  std::vector<int32_t> all_centre;
+  std::vector<int32_t> dims;  // the last snapshot, the finished states: what qk_built_info and qk_mps_set_from_built read
   std::vector<double> fidelity;
   std::vector<double> secs;  // workgroup time per state
   std::vector<int64_t> offsets;
-  int64_t total = 0;
+  int64_t total = 0;  // complex elements of the heap in use
   double kernel_ms = 0;
+  int n_snapshots() const { return (int)checkpoints.size(); }
 };
+
+static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, qk_built** out);
 
 extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
                             const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, qk_built** out) {
-  static const char* what = "qk_build_mps";
-  if (!c || !op || !q0 || !alpha || !out) return qk_fail(QK_EINVAL, "qk_build_mps: null argument");
-  if (n_states <= 0 || n_qubits <= 0 || n_ops < 0) return qk_fail(QK_EINVAL, "qk_build_mps: empty problem (%d states, %d qubits, %d gates)", n_states, n_qubits, n_ops);
-  if (max_bond < 2 || max_bond > 1024) return qk_fail(QK_EINVAL, "qk_build_mps: max_bond %d outside 2..1024", max_bond);
+  const int32_t last = n_ops;  // the one-checkpoint scan: a snapshot after the whole program
+  return build_impl("qk_build_mps", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, 1, &last, nullptr, 0, out);
+}
+
+extern "C" int qk_build_mps_scan(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                                 double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                                 int32_t initial_snapshot, qk_built** out) {
+  static const char* what = "qk_build_mps_scan";
+  if (!checkpoints || n_checkpoints < 1) return qk_fail(QK_EINVAL, "%s: no checkpoints", what);
+  for (int j = 0; j < n_checkpoints; ++j)
+    if (checkpoints[j] < 1 || checkpoints[j] > n_ops || (j > 0 && checkpoints[j] <= checkpoints[j - 1]))
+      return qk_fail(QK_EINVAL, "%s: checkpoints must be strictly increasing gate counts in 1..%d (checkpoint %d is %d)", what, n_ops, j, (int)checkpoints[j]);
+  if (checkpoints[n_checkpoints - 1] != n_ops) return qk_fail(QK_EINVAL, "%s: the last checkpoint must be the whole program (%d gates), got %d", what, n_ops, (int)checkpoints[n_checkpoints - 1]);
+  if ((flags & QK_BUILD_PARTIAL) && (n_checkpoints > 1 || initial))
+    return qk_fail(QK_EINVAL, "%s: QK_BUILD_PARTIAL goes with one checkpoint and no initial snapshot (a dropped state has no snapshots)", what);
+  return build_impl(what, c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot, out);
+}
+
+static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, qk_built** out) {
+  if (!c || !op || !q0 || !alpha || !out) return qk_fail(QK_EINVAL, "%s: null argument", what);
+  if (n_states <= 0 || n_qubits <= 0 || n_ops < 0) return qk_fail(QK_EINVAL, "%s: empty problem (%d states, %d qubits, %d gates)", what, n_states, n_qubits, n_ops);
+  if (max_bond < 2 || max_bond > 1024) return qk_fail(QK_EINVAL, "%s: max_bond %d outside 2..1024", what, max_bond);
   for (int i = 0; i < n_ops; ++i)
-    if (op[i] < 0 || op[i] >= N_OPS) return qk_fail(QK_EINVAL, "qk_build_mps: unknown gate op code %d at position %d (valid: 0..%d)", (int)op[i], i, N_OPS - 1);
+    if (op[i] < 0 || op[i] >= N_OPS) return qk_fail(QK_EINVAL, "%s: unknown gate op code %d at position %d (valid: 0..%d)", what, (int)op[i], i, N_OPS - 1);
+  if (init) {  // a resumed build starts from snapshot init_j of `init`, which is only read
+    if (init->ctx != c) return qk_fail(QK_EINVAL, "%s: the initial snapshot was built in another context", what);
+    if (init_j < 0 || init_j >= init->n_snapshots()) return qk_fail(QK_EINVAL, "%s: initial snapshot %d outside 0..%d", what, init_j, init->n_snapshots() - 1);
+    if (init->n_states != n_states || init->n_qubits != n_qubits)
+      return qk_fail(QK_EINVAL, "%s: the initial snapshot holds %d states of %d qubits, the call has %d of %d", what, init->n_states, init->n_qubits, n_states, n_qubits);
+    for (int s = 0; s < n_states; ++s)
+      if (init->all_fidelity[(size_t)init_j * n_states + s] < 0) return qk_fail(QK_EINVAL, "%s: state %d of the initial snapshot was dropped (QK_BUILD_PARTIAL)", what, s);
+    for (size_t e = 0; e < (size_t)n_states * (n_qubits + 1); ++e) {
+      const int d = init->all_dims[(size_t)init_j * n_states * (n_qubits + 1) + e];
+      if (d > max_bond) return qk_fail(QK_EINVAL, "%s: the initial snapshot has a bond of %d, beyond max_bond = %d", what, d, max_bond);
+    }
+  }
   *out = nullptr;
   QkRangeGuard range_("qk:build");
   HIP_TRY(hipSetDevice(c->device));
   const int cap = max_bond;
   size_t lds_meta = (size_t)2 * cap * sizeof(double) + (size_t)2 * cap * sizeof(int) + (size_t)(n_qubits + 1) * sizeof(int);
   lds_meta = (lds_meta + 15) / 16 * 16;
-  if (lds_meta > 24 * 1024) return qk_fail(QK_EINVAL, "qk_build_mps: %d qubits at max_bond %d need %zu bytes of LDS", n_qubits, cap, lds_meta);
+  if (lds_meta > 24 * 1024) return qk_fail(QK_EINVAL, "%s: %d qubits at max_bond %d need %zu bytes of LDS", what, n_qubits, cap, lds_meta);
   // Two workgroups per CU with 76 KiB of LDS each (what the bookkeeping leaves is the Jacobi working set: A and V of a
   // factorisation up to ~(p + q) q = 4500 complex numbers, e.g. 74 x 37; larger ones run from L2) -- or, when the caller
   // bounds the bonds by 32, four with 38 KiB and half the registers each: more latency hiding for small factorisations
@@ -594,11 +643,11 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
   const size_t per_wg = ((size_t)n_qubits * 2 * cap * cap + 4 * wslot + wtab) * sizeof(cd);
   long long grid = std::min<long long>(n_states, (long long)wgs_per_cu * c->num_cus);
   grid = std::min<long long>(grid, (long long)(0.35 * (double)free_b / (double)per_wg));
-  if (grid < 1) return qk_fail(QK_EDEVICE, "qk_build_mps: not enough device memory for one workgroup's arena (%zu bytes)", per_wg);
-  // heap: every finished state, packed; bounded by the arena size of all states and by the free memory
+  if (grid < 1) return qk_fail(QK_EDEVICE, "%s: not enough device memory for one workgroup's arena (%zu bytes)", what, per_wg);
+  // heap: every snapshot of every state, packed; bounded by the arena size of all states and by the free memory
   // (worst case = every bond at the cap; real data sets need a few per cent of that, and allocating -- and freeing -- a hundred GB
   // costs seconds: a twelfth of the free memory unless QK_BUILD_HEAP_GB says otherwise; a heap that turns out too small fails loudly)
-  const double heap_want = (double)n_states * (double)n_qubits * 2.0 * cap * cap;
+  const double heap_want = (double)n_ckpt * (double)n_states * (double)n_qubits * 2.0 * cap * cap;
   double heap_lim = 0.08 * (double)free_b / (double)sizeof(cd);
   if (const char* v = std::getenv("QK_BUILD_HEAP_GB")) heap_lim = std::min(0.45 * (double)free_b, std::atof(v) * 1073741824.0) / (double)sizeof(cd);
   const size_t heap_cap = (size_t)std::max(1024.0, std::min(heap_want, heap_lim));
@@ -608,14 +657,31 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
   HIP_TRY_AS(what, c->build_arena.ensure((size_t)grid * n_qubits * 2 * cap * cap * sizeof(cd)));
   HIP_TRY_AS(what, c->build_work.ensure((size_t)grid * (4 * wslot + wtab) * sizeof(cd)));
   QkDevBuf heap, d_op, d_q0, d_alpha, d_fid, d_secs, d_dims, d_offs, d_ctr, d_err, d_order;  // d_ctr: [0] state counter, [1] heap top
+  QkDevBuf d_ckpt, d_centre, d_ioffs, d_idims, d_ifid, d_icentre;
+  const size_t n_rec = (size_t)n_ckpt * n_states;  // (snapshot, state) records
   HIP_TRY_AS(what, heap.alloc(heap_cap * sizeof(cd)));
   HIP_TRY_AS(what, d_op.alloc(std::max(1, n_ops)));
   HIP_TRY_AS(what, d_q0.alloc((size_t)std::max(1, n_ops) * sizeof(int32_t)));
   HIP_TRY_AS(what, d_alpha.alloc((size_t)n_states * std::max(1, n_ops) * sizeof(double)));
-  HIP_TRY_AS(what, d_fid.alloc((size_t)n_states * sizeof(double)));
+  HIP_TRY_AS(what, d_fid.alloc(n_rec * sizeof(double)));
   HIP_TRY_AS(what, d_secs.alloc((size_t)n_states * sizeof(double)));
-  HIP_TRY_AS(what, d_dims.alloc((size_t)n_states * (n_qubits + 1) * sizeof(int32_t)));
-  HIP_TRY_AS(what, d_offs.alloc((size_t)n_states * sizeof(long long)));
+  HIP_TRY_AS(what, d_dims.alloc(n_rec * (n_qubits + 1) * sizeof(int32_t)));
+  HIP_TRY_AS(what, d_offs.alloc(n_rec * sizeof(long long)));
+  HIP_TRY_AS(what, d_centre.alloc(n_rec * sizeof(int32_t)));
+  HIP_TRY_AS(what, d_ckpt.alloc((size_t)n_ckpt * sizeof(int32_t)));
+  HIP_TRY_AS(what, hipMemcpy(d_ckpt.get(), ckpt, (size_t)n_ckpt * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (init) {
+    const size_t r0 = (size_t)init_j * n_states;
+    std::vector<long long> ioffs(init->all_offsets.begin() + r0, init->all_offsets.begin() + r0 + n_states);
+    HIP_TRY_AS(what, d_ioffs.alloc((size_t)n_states * sizeof(long long)));
+    HIP_TRY_AS(what, d_idims.alloc((size_t)n_states * (n_qubits + 1) * sizeof(int32_t)));
+    HIP_TRY_AS(what, d_ifid.alloc((size_t)n_states * sizeof(double)));
+    HIP_TRY_AS(what, d_icentre.alloc((size_t)n_states * sizeof(int32_t)));
+    HIP_TRY_AS(what, hipMemcpy(d_ioffs.get(), ioffs.data(), (size_t)n_states * sizeof(long long), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_idims.get(), init->all_dims.data() + r0 * (n_qubits + 1), (size_t)n_states * (n_qubits + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_ifid.get(), init->all_fidelity.data() + r0, (size_t)n_states * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_icentre.get(), init->all_centre.data() + r0, (size_t)n_states * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
   HIP_TRY_AS(what, d_ctr.alloc(2 * sizeof(unsigned long long)));
   HIP_TRY_AS(what, d_err.alloc(32 * sizeof(int)));
   if (n_ops > 0) {
@@ -650,6 +716,9 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
   a.counter = d_ctr.get<unsigned long long>(), a.heap_top = a.counter + 1;
   a.dims_out = d_dims.get<int32_t>(), a.fid_out = d_fid.get<double>(), a.secs_out = d_secs.get<double>(), a.offs_out = d_offs.get<long long>(), a.error = d_err.get<int>();
   a.jl_offset = (int)(lds_meta / sizeof(double)), a.jl_elems = jl_elems;
+  a.n_ckpt = n_ckpt, a.ckpt = d_ckpt.get<int32_t>(), a.centre_out = d_centre.get<int32_t>();
+  a.init_heap = init ? init->heap.get<cd>() : nullptr;
+  a.init_offs = d_ioffs.get<long long>(), a.init_dims = d_idims.get<int32_t>(), a.init_fid = d_ifid.get<double>(), a.init_centre = d_icentre.get<int32_t>();
   a.partial = (flags & QK_BUILD_PARTIAL) ? 1 : 0;
   a.truncate = (flags & QK_BUILD_TRUNCATE) ? 1 : 0;
   a.block = 1;
@@ -661,20 +730,23 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
   HIP_TRY_AS(what, hipGetLastError());
   HIP_TRY_AS(what, hipEventRecord(c->ev1, c->stream));
   std::unique_ptr<qk_built> b(new (std::nothrow) qk_built);
-  if (!b) return qk_fail(QK_ENOMEM, "qk_build_mps: out of memory");
+  if (!b) return qk_fail(QK_ENOMEM, "%s: out of memory", what);
   b->ctx = c, b->n_states = n_states, b->n_qubits = n_qubits;
-  b->dims.resize((size_t)n_states * (n_qubits + 1));
-  b->fidelity.resize(n_states);
-  b->offsets.resize(n_states);
-  std::vector<long long> offs(n_states);
+  b->checkpoints.assign(ckpt, ckpt + n_ckpt);
+  b->all_dims.resize(n_rec * (n_qubits + 1));
+  b->all_fidelity.resize(n_rec);
+  b->all_offsets.resize(n_rec);
+  b->all_centre.resize(n_rec);
+  std::vector<long long> offs(n_rec);
   int errv[32] = {0};
   unsigned long long ctr[2] = {0, 0};
   hipError_t e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipMemcpy(b->dims.data(), d_dims.get(), b->dims.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(b->fidelity.data(), d_fid.get(), (size_t)n_states * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(b->all_dims.data(), d_dims.get(), b->all_dims.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(b->all_fidelity.data(), d_fid.get(), n_rec * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(b->all_centre.data(), d_centre.get(), n_rec * sizeof(int32_t), hipMemcpyDeviceToHost);
   b->secs.resize(n_states);
   if (e == hipSuccess) e = hipMemcpy(b->secs.data(), d_secs.get(), (size_t)n_states * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(offs.data(), d_offs.get(), (size_t)n_states * sizeof(long long), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(offs.data(), d_offs.get(), n_rec * sizeof(long long), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(errv, d_err.get(), sizeof(errv), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(ctr, d_ctr.get(), sizeof(ctr), hipMemcpyDeviceToHost);
   float ms = 0;
@@ -684,7 +756,7 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
     std::fprintf(stderr, "[qk_build_mps] host wall %.2f s for a %.2f s launch (arena %.1f GB, heap %.1f GB: allocation, upload, download)\n", t_host1 - t_host0, ms / 1e3,
                  (double)grid * (double)per_wg / 1e9, (double)heap_cap * sizeof(cd) / 1e9);
   }
-  if (e != hipSuccess) return qk_fail(QK_EDEVICE, "qk_build_mps: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return qk_fail(QK_EDEVICE, "%s: %s", what, hipGetErrorString(e));
   const int err = errv[0];
   if (std::getenv("QK_BUILD_DEBUG"))
     std::fprintf(stderr, "[qk_build_mps] %d states, grid %lld x %d threads, %.1f ms; Jacobi: %d factorisations, %.2f sweeps on average, %d at most, %d unconverged, %d in LDS / %d from L2; error bits %d\n",
@@ -714,13 +786,17 @@ extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32
                  steps ? (double)ticks / 100.0 / (double)steps : 0.0, steps);
   }
   if (err) {
-    if (err & ERR_OP) return qk_fail(QK_EINVAL, "qk_build_mps: unknown gate op code (valid: 0..%d)", N_OPS - 1);
-    if (err & ERR_GATE) return qk_fail(QK_EINVAL, "qk_build_mps: gate on a qubit outside the register");
-    if (err & ERR_BOND) return qk_fail(QK_EINVAL, "qk_build_mps: a bond grew beyond max_bond = %d", cap);
-    if (err & ERR_HEAP) return qk_fail(QK_EDEVICE, "qk_build_mps: the packed states need %llu complex numbers, the heap holds %zu", ctr[1], heap_cap);
-    return qk_fail(QK_EDEVICE, "qk_build_mps: a Jacobi factorisation did not converge in %d sweeps", MAX_SWEEPS);
+    if (err & ERR_OP) return qk_fail(QK_EINVAL, "%s: unknown gate op code (valid: 0..%d)", what, N_OPS - 1);
+    if (err & ERR_GATE) return qk_fail(QK_EINVAL, "%s: gate on a qubit outside the register", what);
+    if (err & ERR_BOND) return qk_fail(QK_EINVAL, "%s: a bond grew beyond max_bond = %d", what, cap);
+    if (err & ERR_HEAP) return qk_fail(QK_EDEVICE, "%s: the packed states (%d snapshots each) need %llu complex numbers, the heap holds %zu", what, n_ckpt, ctr[1], heap_cap);
+    return qk_fail(QK_EDEVICE, "%s: a Jacobi factorisation did not converge in %d sweeps", what, MAX_SWEEPS);
   }
-  for (int s = 0; s < n_states; ++s) b->offsets[s] = offs[s];
+  for (size_t r = 0; r < n_rec; ++r) b->all_offsets[r] = offs[r];
+  const size_t last = (size_t)(n_ckpt - 1) * n_states;
+  b->dims.assign(b->all_dims.begin() + last * (n_qubits + 1), b->all_dims.end());
+  b->fidelity.assign(b->all_fidelity.begin() + last, b->all_fidelity.end());
+  b->offsets.assign(b->all_offsets.begin() + last, b->all_offsets.end());
   b->heap = std::move(heap);
   b->total = (int64_t)ctr[1];
   b->kernel_ms = ms;
@@ -745,11 +821,80 @@ extern "C" int qk_built_download(const qk_built* b, double* host) {
   return QK_OK;
 }
 
+extern "C" int qk_built_num_snapshots(const qk_built* b) { return b ? b->n_snapshots() : 0; }
+
+extern "C" int qk_built_checkpoints(const qk_built* b, int32_t* checkpoints) {
+  if (!b || !checkpoints) return qk_fail(QK_EINVAL, "qk_built_checkpoints: null argument");
+  std::copy(b->checkpoints.begin(), b->checkpoints.end(), checkpoints);
+  return QK_OK;
+}
+
+static int snapshot_index(const qk_built* b, int32_t j, const char* what) {
+  if (!b) return qk_fail(QK_EINVAL, "%s: null handle", what);
+  if (j < 0 || j >= b->n_snapshots()) return qk_fail(QK_EINVAL, "%s: snapshot %d outside 0..%d", what, j, b->n_snapshots() - 1);
+  return QK_OK;
+}
+
+static int64_t state_elems(const qk_built* b, int32_t j, int s) {  // complex elements of state s in snapshot j (0 for a dropped state)
+  const size_t r = (size_t)j * b->n_states + s;
+  if (b->all_fidelity[r] < 0) return 0;
+  const int32_t* d = b->all_dims.data() + r * (b->n_qubits + 1);
+  int64_t t = 0;
+  for (int k = 0; k < b->n_qubits; ++k) t += 2ll * d[k] * d[k + 1];
+  return t;
+}
+
+extern "C" int qk_built_info_at(const qk_built* b, int32_t j, int32_t* dims, double* fidelity, int64_t* offsets, int32_t* centre, int64_t* total_complex) {
+  if (const int rc = snapshot_index(b, j, "qk_built_info_at")) return rc;
+  const size_t ns = b->n_states, n1 = b->n_qubits + 1, r0 = (size_t)j * ns;
+  if (dims) std::copy(b->all_dims.begin() + r0 * n1, b->all_dims.begin() + (r0 + ns) * n1, dims);
+  if (fidelity) std::copy(b->all_fidelity.begin() + r0, b->all_fidelity.begin() + r0 + ns, fidelity);
+  if (offsets) std::copy(b->all_offsets.begin() + r0, b->all_offsets.begin() + r0 + ns, offsets);
+  if (centre) std::copy(b->all_centre.begin() + r0, b->all_centre.begin() + r0 + ns, centre);
+  if (total_complex) {
+    int64_t t = 0;
+    for (int s = 0; s < b->n_states; ++s) t += state_elems(b, j, s);
+    *total_complex = t;
+  }
+  return QK_OK;
+}
+
+extern "C" int qk_built_download_at(const qk_built* b, int32_t j, double* host) {
+  if (const int rc = snapshot_index(b, j, "qk_built_download_at")) return rc;
+  if (!host) return qk_fail(QK_EINVAL, "qk_built_download_at: null argument");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  cd* dst = reinterpret_cast<cd*>(host);
+  for (int s = 0; s < b->n_states; ++s) {  // a snapshot's states lie where their workgroups' bumps put them: one copy each, packed in state order
+    const int64_t cnt = state_elems(b, j, s), off = b->all_offsets[(size_t)j * b->n_states + s];
+    if (cnt == 0) continue;
+    if (off < 0 || off + cnt > b->total) return qk_fail(QK_EDEVICE, "qk_built_download_at: state %d of snapshot %d lies outside the heap", s, j);
+    HIP_TRY(hipMemcpy(dst, b->heap.get<cd>() + off, (size_t)cnt * sizeof(cd), hipMemcpyDeviceToHost));
+    dst += cnt;
+  }
+  return QK_OK;
+}
+
+static int set_from_snapshot(qk_ctx* c, const qk_built* b, int32_t j, qk_mps_set** out, const char* what);
+
 extern "C" int qk_mps_set_from_built(qk_ctx* c, const qk_built* b, qk_mps_set** out) {
   if (!c || !b || !out) return qk_fail(QK_EINVAL, "qk_mps_set_from_built: null argument");
-  if (b->ctx != c) return qk_fail(QK_EINVAL, "qk_mps_set_from_built: the states were built in another context");
+  return set_from_snapshot(c, b, b->n_snapshots() - 1, out, "qk_mps_set_from_built");
+}
+
+extern "C" int qk_mps_set_from_built_at(qk_ctx* c, const qk_built* b, int32_t j, qk_mps_set** out) {
+  if (!c || !b || !out) return qk_fail(QK_EINVAL, "qk_mps_set_from_built_at: null argument");
+  if (const int rc = snapshot_index(b, j, "qk_mps_set_from_built_at")) return rc;
+  return set_from_snapshot(c, b, j, out, "qk_mps_set_from_built_at");
+}
+
+// qk_pack_built_kernel with the offsets and bond tables of snapshot j
+static int set_from_snapshot(qk_ctx* c, const qk_built* b, const int32_t j, qk_mps_set** out, const char* what) {
+  if (b->ctx != c) return qk_fail(QK_EINVAL, "%s: the states were built in another context", what);
+  const size_t r0 = (size_t)j * b->n_states;
+  const int32_t* const bdims = b->all_dims.data() + r0 * (b->n_qubits + 1);
+  const int64_t* const boffs = b->all_offsets.data() + r0;
   for (int s = 0; s < b->n_states; ++s)
-    if (b->fidelity[s] < 0) return qk_fail(QK_EINVAL, "qk_mps_set_from_built: state %d outgrew max_bond and was dropped (QK_BUILD_PARTIAL)", s);
+    if (b->all_fidelity[r0 + s] < 0) return qk_fail(QK_EINVAL, "%s: state %d outgrew max_bond and was dropped (QK_BUILD_PARTIAL)", what, s);
   HIP_TRY(hipSetDevice(c->device));
   const int ns = b->n_states, n = b->n_qubits, stride = n + 1;
   auto pad16 = [](int x) { return (x + 15) / 16 * 16; };
@@ -758,28 +903,28 @@ extern "C" int qk_mps_set_from_built(qk_ctx* c, const qk_built* b, qk_mps_set** 
   long long total = 0;
   int max_pad = 0;
   for (int s = 0; s < ns; ++s) {
-    long long pos = b->offsets[s];
+    long long pos = boffs[s];
     for (int k = 0; k <= n; ++k) {
-      pad[(size_t)s * stride + k] = pad16(b->dims[(size_t)s * stride + k]);
+      pad[(size_t)s * stride + k] = pad16(bdims[(size_t)s * stride + k]);
       max_pad = std::max(max_pad, pad[(size_t)s * stride + k]);
     }
     for (int k = 0; k < n; ++k) {
       src[(size_t)s * n + k] = pos;
       dst[(size_t)s * n + k] = total;
-      pos += 2ll * b->dims[(size_t)s * stride + k] * b->dims[(size_t)s * stride + k + 1];
+      pos += 2ll * bdims[(size_t)s * stride + k] * bdims[(size_t)s * stride + k + 1];
       total += 2ll * pad[(size_t)s * stride + k] * 2 * pad[(size_t)s * stride + k + 1];
     }
   }
   qk_mps_set* m = nullptr;
-  const int rc = qk_mps_set_alloc(c, ns, n, total * (long long)sizeof(double), 64, &m, "qk_mps_set_from_built");
+  const int rc = qk_mps_set_alloc(c, ns, n, total * (long long)sizeof(double), 64, &m, what);
   if (rc != QK_OK) return rc;
   m->max_pad = max_pad;
-  m->dims_true = b->dims;
+  m->dims_true.assign(bdims, bdims + (size_t)ns * stride);
   QkDevBuf d_src;
   hipError_t e = hipMemsetAsync(m->d_data.get(), 0, (size_t)m->bytes, c->stream);
   if (e == hipSuccess) e = d_src.alloc(src.size() * sizeof(long long));
   if (e == hipSuccess) e = hipMemcpyAsync(m->d_dims.get(), pad.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(m->d_true.get(), b->dims.data(), pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_true.get(), bdims, pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(m->d_offs.get(), dst.data(), dst.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_src.get(), src.data(), src.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
@@ -790,7 +935,7 @@ extern "C" int qk_mps_set_from_built(qk_ctx* c, const qk_built* b, qk_mps_set** 
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) {
     qk_mps_set_destroy(m);
-    return qk_fail(QK_EDEVICE, "qk_mps_set_from_built: %s", hipGetErrorString(e));
+    return qk_fail(QK_EDEVICE, "%s: %s", what, hipGetErrorString(e));
   }
   *out = m;
   return QK_OK;

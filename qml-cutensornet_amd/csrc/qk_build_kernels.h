@@ -1064,6 +1064,55 @@ __device__ void wg_kept(const double* sig, const int* ord, const int n, const do
   __syncthreads();
 }
 
+// A snapshot of the workgroup's state: its sites, packed, go into a slot of the heap taken with one atomic bump; the bond table,
+// the fidelity so far, the slot's offset and the position of the orthogonality centre are recorded.  The arena is only read.  A
+// dropped state (QK_BUILD_PARTIAL) gets fidelity -1 and no tensors.  Kept out of line: the gate loop of the kernel is cut to a register
+// budget, and this code must not take part in its allocation.
+__device__ __noinline__ void wg_snapshot(cd* heap, const unsigned long long heap_cap, unsigned long long* heap_top, int* error, int32_t* dims_out, double* fid_out, long long* offs_out,
+                                         int32_t* centre_out, const int* dims, const cd* sites, const long slot, const int n, const double fidelity, const int centre, const bool dropped,
+                                         WgShared* sh) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long total = 0;
+    if (!dropped)
+      for (int k = 0; k < n; ++k) total += 2ull * dims[k] * dims[k + 1];
+    const unsigned long long off = atomicAdd(heap_top, total);
+    sh->off = off;
+    sh->flag = (off + total <= heap_cap);
+    if (!sh->flag) atomicOr(error, ERR_HEAP);
+    *offs_out = (long long)off;
+    *fid_out = dropped ? -1.0 : fidelity;
+    *centre_out = centre;
+  }
+  __syncthreads();
+  for (int k = tid; k <= n; k += BT) dims_out[k] = dims[k];
+  if (sh->flag && !dropped) {
+    unsigned long long pos = sh->off;
+    for (int k = 0; k < n; ++k) {
+      const long cnt = 2L * dims[k] * dims[k + 1];
+      const cd* src = sites + k * slot;
+      for (long e = tid; e < cnt; e += BT) heap[pos + e] = src[e];
+      pos += cnt;
+    }
+  }
+  __syncthreads();
+}
+
+// The inverse, for a resumed build: the bond table and the packed sites of one state of a snapshot go into the workgroup's arena.
+__device__ __noinline__ void wg_load_snapshot(const cd* src, const int32_t* src_dims, int* dims, cd* sites, const long slot, const int n) {
+  const int tid = threadIdx.x;
+  for (int k = tid; k <= n; k += BT) dims[k] = src_dims[k];
+  __syncthreads();
+  for (int k = 0; k < n; ++k) {
+    const long cnt = 2L * dims[k] * dims[k + 1];
+    cd* dst = sites + k * slot;
+    for (long e = tid; e < cnt; e += BT) dst[e] = src[e];
+    src += cnt;
+  }
+  __syncthreads();
+}
+
 template <int MINWG>  // resident workgroups per CU the register budget is cut for: 256 threads: 2 (76 KiB of LDS each) or 4 (38 KiB); 512 threads: 1 (152 KiB)
 __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) {
   extern __shared__ double sh_raw[];
@@ -1092,18 +1141,30 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
       if (tid == 0) atomicAdd(reinterpret_cast<unsigned long long*>(g.error + 12), (unsigned long long)(wall_clock64() - wg_begin));  // busy ticks
       break;
     }
-    for (int k = tid; k <= n; k += BT) dims[k] = 1;
-    for (int k = tid; k < n; k += BT) {
-      sites[k * slot] = cd{1.0, 0.0};
-      sites[k * slot + 1] = cd{0.0, 0.0};
+    double fidelity = 1.0;
+    int centre = 0;
+    if (g.init_heap) {  // resume: the state starts as a snapshot of an earlier build (bonds <= cap: checked by the host)
+      wg_load_snapshot(g.init_heap + g.init_offs[st], g.init_dims + (long)st * (n + 1), dims, sites, slot, n);
+      fidelity = g.init_fid[st], centre = g.init_centre[st];
+    } else {
+      for (int k = tid; k <= n; k += BT) dims[k] = 1;
+      for (int k = tid; k < n; k += BT) {
+        sites[k * slot] = cd{1.0, 0.0};
+        sites[k * slot + 1] = cd{0.0, 0.0};
+      }
     }
     __syncthreads();
     const long long st_begin = wall_clock64();
     const double* alpha = g.alpha + (long)st * g.n_ops;
-    double fidelity = 1.0;
-    int centre = 0;
     bool outgrown = false;
+    int ck = 0;  // the next checkpoint; the last one (after the whole program) is the pack behind the loop
     for (int i = 0; i < g.n_ops && !outgrown; ++i) {
+      if (ck + 1 < g.n_ckpt && g.ckpt[ck] == i) {  // i gates done: a copy of the sites as they stand, nothing else changes
+        const long rec = (long)ck * g.n_states + st;
+        wg_snapshot(g.heap, g.heap_cap, g.heap_top, g.error, g.dims_out + rec * (n + 1), g.fid_out + rec, g.offs_out + rec, g.centre_out + rec, dims, sites, slot, n, fidelity, centre,
+                    false, &sh);
+        ++ck;
+      }
       const int o = g.op[i], q = g.q0[i];
       if (o < 0 || o >= N_OPS) {
         if (tid == 0) atomicOr(g.error, ERR_OP);
@@ -1332,32 +1393,13 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
       __syncthreads();
       centre = centre_right ? q + 1 : q;
     }
-    // ---- pack the finished state into the heap
-    if (tid == 0) {
-      unsigned long long total = 0;
-      if (outgrown) fidelity = -1.0;  // marks a dropped state; it gets no tensors
-      else
-        for (int k = 0; k < n; ++k) total += 2ull * dims[k] * dims[k + 1];
-      const unsigned long long off = atomicAdd(g.heap_top, total);
-      sh.off = off;
-      sh.flag = (off + total <= g.heap_cap);
-      if (!sh.flag) atomicOr(g.error, ERR_HEAP);
-      g.offs_out[st] = (long long)off;
-      g.fid_out[st] = fidelity;
-      g.secs_out[st] = (double)(wall_clock64() - st_begin) * 1e-8;
+    // ---- pack the finished state into the heap: the last checkpoint
+    {
+      const long rec = (long)(g.n_ckpt - 1) * g.n_states + st;
+      wg_snapshot(g.heap, g.heap_cap, g.heap_top, g.error, g.dims_out + rec * (n + 1), g.fid_out + rec, g.offs_out + rec, g.centre_out + rec, dims, sites, slot, n, fidelity, centre,
+                  outgrown, &sh);
+      if (tid == 0) g.secs_out[st] = (double)(wall_clock64() - st_begin) * 1e-8;
     }
-    __syncthreads();
-    for (int k = tid; k <= n; k += BT) g.dims_out[(long)st * (n + 1) + k] = dims[k];
-    if (sh.flag && !outgrown) {
-      unsigned long long pos = sh.off;
-      for (int k = 0; k < n; ++k) {
-        const long cnt = 2L * dims[k] * dims[k + 1];
-        const cd* src = sites + k * slot;
-        for (long e = tid; e < cnt; e += BT) g.heap[pos + e] = src[e];
-        pos += cnt;
-      }
-    }
-    __syncthreads();
   }
 }
 

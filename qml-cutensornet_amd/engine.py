@@ -112,6 +112,12 @@ _SIGNATURES = [
     ("qk_built_download", C.c_int, [_P, _P]),
     ("qk_built_destroy", C.c_int, [_P]),
     ("qk_mps_set_from_built", C.c_int, [_P, _P, C.POINTER(_P)]),
+    ("qk_build_mps_scan", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.POINTER(_P)]),
+    ("qk_built_num_snapshots", C.c_int, [_P]),
+    ("qk_built_checkpoints", C.c_int, [_P, _P]),
+    ("qk_built_info_at", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    ("qk_built_download_at", C.c_int, [_P, C.c_int32, _P]),
+    ("qk_mps_set_from_built_at", C.c_int, [_P, _P, C.c_int32, C.POINTER(_P)]),
     ("qk_debug_jacobi", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("qk_debug_jacobi_precond", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("qk_range_push", C.c_int, [C.c_char_p]),
@@ -530,6 +536,98 @@ class MpsSet:
             pass
 
 
+class BuiltScan:
+    """The snapshots of ``Context.build_mps_scan``: owns the builder's handle (one device heap with every snapshot of every state)
+    until ``close()``; a context manager.  ``checkpoints[j]`` gates were done at snapshot j; the last snapshot is the finished
+    circuit.  ``set(j)`` / ``states(j)`` are independent of the scan afterwards."""
+
+    def __init__(self, ctx, handle, n_states, n_qubits):
+        self.ctx, self._h, self.n_states, self.n_qubits = ctx, handle, int(n_states), int(n_qubits)
+        ns = int(lib().qk_built_num_snapshots(handle))
+        cps = np.zeros(ns, dtype=np.int32)
+        _check(lib().qk_built_checkpoints(handle, cps.ctypes.data), "qk_built_checkpoints")
+        self.checkpoints = [int(c) for c in cps]
+        ms = C.c_double()
+        _check(lib().qk_built_info(handle, None, None, None, None, C.byref(ms)), "qk_built_info")
+        self.kernel_ms = ms.value
+        ctx._adopt(self)  # closed with the context: the heap lives on its device
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return len(self.checkpoints)
+
+    def _index(self, j) -> int:
+        if self._h is None:
+            raise QkError("the scan is closed")
+        k = int(j)
+        if k < 0:
+            k += len(self.checkpoints)
+        if not 0 <= k < len(self.checkpoints):
+            raise IndexError(f"snapshot {j!r} outside 0 .. {len(self.checkpoints) - 1}")
+        return k
+
+    def _info(self, j):
+        j = self._index(j)
+        dims = np.zeros((self.n_states, self.n_qubits + 1), dtype=np.int32)
+        fid = np.zeros(self.n_states, dtype=np.float64)
+        offs = np.zeros(self.n_states, dtype=np.int64)
+        centre = np.zeros(self.n_states, dtype=np.int32)
+        total = C.c_int64()
+        _check(lib().qk_built_info_at(self._h, j, dims.ctypes.data, fid.ctypes.data, offs.ctypes.data, centre.ctypes.data, C.byref(total)), "qk_built_info_at")
+        return j, dims, fid, offs, centre, int(total.value)
+
+    def info(self, j) -> dict:
+        """Snapshot j: {"dims": bond tables (n_states, n_qubits + 1), "fidelity": the fidelity product so far (n_states,),
+        "centre": site of the orthogonality centre (n_states,), "heap_bytes": bytes of the snapshot's tensors in the heap}."""
+        _, dims, fid, _, centre, total = self._info(j)
+        return {"dims": dims, "fidelity": fid, "centre": centre, "heap_bytes": 16 * total}
+
+    def set(self, j) -> "MpsSet":
+        """Snapshot j as a device-resident set (packed on the device: nothing is downloaded); feeds ``gram``, ``local_paulis``,
+        ``compress`` ... like any set."""
+        j, dims, *_ = self._info(j)
+        hs = _P()
+        _check(lib().qk_mps_set_from_built_at(self.ctx.handle, self._h, j, C.byref(hs)), "qk_mps_set_from_built_at")
+        return MpsSet(self.ctx, hs, dims)
+
+    def states(self, j) -> list:
+        """Snapshot j on the host: ``list[MPS]``, each with its fidelity so far."""
+        from .mps import MPS
+
+        j, dims, fid, _, _, total = self._info(j)
+        flat = np.empty(max(total, 1), dtype=np.complex128)
+        _check(lib().qk_built_download_at(self._h, j, flat.ctypes.data), "qk_built_download_at")
+        out, pos = [], 0
+        for s_ in range(self.n_states):
+            tensors = []
+            for k in range(self.n_qubits):
+                sz = int(dims[s_, k]) * 2 * int(dims[s_, k + 1])
+                tensors.append(flat[pos : pos + sz].reshape(int(dims[s_, k]), 2, int(dims[s_, k + 1])).copy())
+                pos += sz
+            out.append(MPS(tensors, float(fid[s_])))
+        return out
+
+    def close(self):
+        if self._h:
+            lib().qk_built_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One engine context per device (what ``CuTensorNetHandle(device_id)`` is to the reference,
     /root/reference/gpu_backend/kernel_state_ansatz.py:213)."""
@@ -677,6 +775,44 @@ class Context:
         finally:
             lib().qk_built_destroy(h)
         return MpsSet(self, hs, dims), {"kernel_ms": ms.value, "dims": dims, "fidelity": fid}
+
+    def build_mps_scan(self, circuits, checkpoints, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, truncate: bool = False,
+                       initial=None, partial: bool = False) -> BuiltScan:
+        """``build_mps_set`` that also keeps every state after ``checkpoints[j]`` gates (gate counts: strictly increasing, in
+        1 .. n_gates, the last one n_gates; ``KernelStateAnsatz.layer_ends()`` for a scan over depth): ONE launch, the snapshots are
+        copies and the run does the arithmetic of a run without them, so the last snapshot is what ``build_mps`` returns.  Returns a
+        ``BuiltScan`` (``.checkpoints``, ``.kernel_ms``, ``.info(j)``, ``.set(j)``, ``.states(j)``; close it, or use ``with``).  A
+        snapshot is in mixed-canonical gauge; all snapshots share one device heap.
+
+        ``initial=(scan, j)`` resumes: the states start as snapshot j of an earlier scan of this context (same number of states and
+        qubits, no bond above ``max_bond``) and ``circuits`` are the gates that follow it -- ``c.sliced(scan.checkpoints[j],
+        c.n_gates)`` continues the same circuits, gate for gate the arithmetic of the uninterrupted run.  ``scan`` is left untouched.
+        ``ValueError`` for bad checkpoints; ``partial`` goes with one checkpoint and no ``initial`` only (``QkError`` otherwise)."""
+        from .ansatz import check_checkpoints
+
+        circuits = list(circuits)
+        if not circuits:
+            raise QkError("build_mps_scan needs at least one circuit")
+        c0 = circuits[0]
+        op = np.ascontiguousarray(c0.op, dtype=np.int8)
+        q0 = np.ascontiguousarray(c0.q0, dtype=np.int32)
+        cps = np.ascontiguousarray(check_checkpoints(checkpoints, int(op.shape[0])), dtype=np.int32)
+        for c in circuits[1:]:
+            if c.n_qubits != c0.n_qubits or not np.array_equal(c.op, c0.op) or not np.array_equal(c.q0, c0.q0):
+                raise QkError("build_mps_scan: the circuits of one call must share their gate structure")
+        alpha = np.ascontiguousarray(np.stack([np.asarray(c.alpha, dtype=np.float64) for c in circuits]))
+        n, ns = int(c0.n_qubits), len(circuits)
+        src, src_j = None, 0
+        if initial is not None:
+            scan, j = initial
+            if not isinstance(scan, BuiltScan):
+                raise ValueError(f"initial must be (BuiltScan, snapshot index), got {initial!r}")
+            src, src_j = scan.handle, scan._index(j)
+        h = _P()
+        _check(lib().qk_build_mps_scan(self._h, ns, n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
+                                       float(value_of_zero), int(max_bond), (1 if partial else 0) | (2 if truncate else 0), int(cps.shape[0]), cps.ctypes.data, src, src_j, C.byref(h)),
+               "qk_build_mps_scan")
+        return BuiltScan(self, h, ns, n)
 
     def set_from_packed(self, dims_true, offsets, planes_ptr: int, n_doubles: int) -> MpsSet:
         """A set assembled from packed images (``MpsSet.image`` of several ranks, gathered into one buffer on the device or

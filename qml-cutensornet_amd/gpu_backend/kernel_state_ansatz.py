@@ -26,13 +26,13 @@ from statistics import mean, median
 import numpy as np
 
 try:  # normal case: imported as qml_cutensornet_amd.gpu_backend.kernel_state_ansatz
-    from ..ansatz import OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit  # noqa: F401
+    from ..ansatz import OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit, check_depths  # noqa: F401
     from .. import engine as _engine
     from ..dist import assemble_gram, comm_allgather, exchange_sets
     from ..mps import MPS, simulate, simulate_many  # noqa: F401
 except ImportError:  # imported top-level as gpu_backend.kernel_state_ansatz
     import qml_cutensornet_amd as _pkg  # noqa: F401
-    from qml_cutensornet_amd.ansatz import OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit  # noqa: F401
+    from qml_cutensornet_amd.ansatz import OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit, check_depths  # noqa: F401
     from qml_cutensornet_amd import engine as _engine
     from qml_cutensornet_amd.dist import assemble_gram, comm_allgather, exchange_sets
     from qml_cutensornet_amd.mps import MPS, simulate, simulate_many  # noqa: F401
@@ -683,6 +683,116 @@ def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64),
                 "r0_circ_sim": [build_secs, "seconds"], "caps": [[int(c) for c in caps], "chi"],
                 "r0_compress": [[secs[c] for c in caps], "seconds"], "min_fidelity": [[float(out["fidelity"][c].min()) for c in caps], ""],
                 "total_time": [time.perf_counter() - t_start, "seconds"]}
+        with open(info_file + ".json", "w") as fp:
+            json.dump(prof, fp, indent=4)
+    return out
+
+
+def _depth_scan_share(ctx, ansatz, points, rank, n_procs, fidelity, depths, ends, is_root, label, host_workers):
+    """This rank's slice of ``points`` (the chunks of ``_simulate_share``) at every depth of ``depths`` (ascending): (first index,
+    {depth: packed device set, or None for an empty share}, {depth: fidelities}).  One launch of the device builder to the deepest
+    depth with checkpoints at the layer ends; if the device gives up, one host build per depth on the sliced circuits."""
+    import os
+
+    per_rank = -(-len(points) // n_procs)
+    lo = min(len(points), rank * per_rank)
+    hi = min(len(points), lo + per_rank)
+    if hi <= lo:
+        return lo, {r: None for r in depths}, {r: [] for r in depths}
+    deepest = ends[depths[-1] - 1]
+    circuits = [as_bound_circuit(ansatz.circuit_for_data(points[k, :]), ansatz).sliced(0, deepest) for k in range(lo, hi)]
+    chi = int(os.environ.get("QK_MAX_BOND", "0")) or None
+    cap = chi or int(os.environ.get("QK_BUILDER_MAX_BOND", "320"))
+    sets, fids = {}, {}
+    try:
+        with ctx.build_mps_scan(circuits, [ends[r - 1] for r in depths], fidelity, max_bond=cap, truncate=chi is not None) as scan:
+            for j, r in enumerate(depths):
+                sets[r], fids[r] = scan.set(j), [float(f) for f in scan.info(j)["fidelity"]]
+    except _engine.QkError as exc:
+        for m in sets.values():
+            m.close()
+        _say(is_root, f"{label}: device builder gave up on the depth scan ({exc}); one host build per depth")
+        sets, fids = {}, {}
+        for r in depths:
+            states, _ = simulate_many([c.sliced(0, ends[r - 1]) for c in circuits], fidelity, workers=host_workers, max_bond=chi)
+            sets[r], fids[r] = ctx.upload(states), [m.fidelity for m in states]
+    _say(is_root, f"{label}: 100%")
+    return lo, sets, fids
+
+
+def build_depth_scan_kernel_matrices(mpi_comm, ansatz, X, Y=None, depths=(1,), truncation_error=None, info_file=None, loglevel=30):
+    """The Gram of ``build_kernel_matrix`` at several depths of the ansatz from ONE build: ``depths`` are distinct layer counts in
+    1 .. ``ansatz.reps``.  The ansatz repeats one layer, so the circuit of depth r is a prefix of the deeper ones: each rank builds
+    its share to ``max(depths)`` in one launch of the device builder with checkpoints at the layer ends (``ansatz.layer_ends()``,
+    ``Context.build_mps_scan``); per depth the shares are exchanged and swept like any set.  Rank 0 returns the dict
+        depths     the depths, ascending
+        K          {r: (len(Y), len(X))}            the Gram of the ansatz with r layers
+        fidelity   {r: (len(X) [+ len(Y)],)}        the builder's fidelity of every state at that depth, X first
+        bond_dims  {r: (len(X) [+ len(Y)], n+1)}    the bond tables
+    and the other ranks ``None``.  QK_MAX_BOND (a bond cap) and QK_BUILDER_MAX_BOND (the largest bond the device builder holds,
+    320) mean what they mean for ``build_kernel_matrix``'s device builder; a state that outgrows the latter, or any other device
+    failure, sends the share to the host builder, one build per depth (the log says so)."""
+    if Y is not None and len(X) < len(Y):
+        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    depths = sorted(check_depths(depths, ansatz.reps))
+    ends = [int(e) for e in ansatz.layer_ends()]
+    X = np.asarray(X, dtype=np.float64)
+    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
+    fidelity = 1.0 - float(truncation_error)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    t_start = time.perf_counter()
+    ctx = _engine.default_context(device_id)
+    shares = []  # (total, first index, {depth: set}, {depth: fidelities})
+    for label, points in (("X", X), ("Y", Y)):
+        if points is None:
+            continue
+        _say(is_root, f"\nContracting the MPS of the circuits from the {label} dataset at depths {depths}...")
+        shares.append((len(points),) + tuple(_depth_scan_share(ctx, ansatz, points, rank, n_procs, fidelity, depths, ends, is_root, label, host_workers)))
+    ctx.trim()
+    build_secs = time.perf_counter() - t_start
+    out = {"depths": list(depths), "K": {}, "fidelity": {}, "bond_dims": {}}
+    gram_secs = {}
+    n_qubits = int(ansatz.num_qubits)
+    try:
+        for r in depths:
+            t0 = time.perf_counter()
+            fids, dims, full = [], [], []
+            try:
+                for total, lo, sets, fid in shares:
+                    loc = sets[r]
+                    fids.append(_gather_features(mpi_comm, lo, np.asarray(fid[r], dtype=np.float64), total))
+                    d = np.zeros((0, n_qubits + 1)) if loc is None else np.asarray(loc.dims, dtype=np.float64)
+                    dims.append(_gather_features(mpi_comm, lo, d, total))
+                    full.append(exchange_sets(mpi_comm, ctx, loc, lo, total)[0])
+                out["K"][r], _ = _gram_on_device(mpi_comm, rank, n_procs, ctx, full[0], full[1] if len(full) > 1 else None)
+            finally:
+                for f, (_, _, sets, _) in zip(full, shares):
+                    if f is not sets[r]:
+                        f.close()
+            out["fidelity"][r] = np.concatenate(fids)
+            out["bond_dims"][r] = np.concatenate(dims).astype(np.int32)
+            gram_secs[r] = time.perf_counter() - t0
+    finally:
+        for _, _, sets, _ in shares:
+            for m in sets.values():
+                if m is not None:
+                    m.close()
+    if not is_root:
+        return None
+    if info_file is not None:
+        prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"],
+                "depths": [list(depths), "layers"], "r0_circ_sim": [build_secs, "seconds"], "kernel_mat_time": [[gram_secs[r] for r in depths], "seconds"],
+                "max_chi": [[int(out["bond_dims"][r].max()) for r in depths], "chi"], "total_time": [time.perf_counter() - t_start, "seconds"]}
         with open(info_file + ".json", "w") as fp:
             json.dump(prof, fp, indent=4)
     return out

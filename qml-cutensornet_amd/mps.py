@@ -22,7 +22,7 @@ import numpy as np
 from scipy.linalg import qr as _qr
 from scipy.linalg import svd as _svd
 
-from .ansatz import OP_H, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_op_codes, is_two_qubit
+from .ansatz import OP_H, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_checkpoints, check_op_codes, is_two_qubit
 
 _SQRT_HALF = 0.7071067811865476
 _YY_SIGN = np.array([[1.0, -1.0], [-1.0, 1.0]])[None, :, :, None]  # c 1 - i s Y(x)Y: +i s on |00>,|11>, -i s on |01>,|10>
@@ -257,19 +257,28 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
     return MPS(tensors, fid.value)
 
 
-def simulate(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None) -> MPS:
+def simulate(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None, checkpoints=None):
     """MPS of circuit|0...0>, "MPSxGate" style: one SVD per two-qubit gate (ref :221).  ``max_bond``: at most that many singular
     values survive a gate -- the ``chi`` of pytket-cutensornet's ``Config`` (ref :141-144 is where it would go); the weight it
     costs goes into ``fidelity`` like any other truncation.
 
+    ``checkpoints=[c_0, ..., n_gates]`` (gate counts: strictly increasing, in 1 .. n_gates, the last one n_gates) is the host mirror
+    of ``Context.build_mps_scan``: the result is a ``list[MPS]``, entry j a copy of the state after c_j gates with its fidelity so
+    far, in the mixed-canonical gauge the run left it in; the last entry is ``simulate(circuit)`` of the numpy loop bit for bit.  It
+    always runs the numpy loop (the native builder keeps no snapshots), whatever QK_NATIVE_BUILDER says.
+
     The matrices are small (tens to a few hundred rows): a multi-threaded BLAS spends its time waking
     threads (measured 24 s instead of 0.9 s per 60-qubit state on 8 cores), so the LAPACK calls run
     single-threaded here; parallelism is across states (``builder_pool.build_states``)."""
+    if checkpoints is not None:
+        checkpoints = check_checkpoints(checkpoints, circuit.n_gates)
     try:
         from threadpoolctl import threadpool_limits
     except ImportError:  # pragma: no cover - optional dependency
-        return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond)
+        return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, checkpoints)
     with threadpool_limits(limits=1):
+        if checkpoints is not None:
+            return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, checkpoints)
         if _use_native():
             return simulate_native(circuit, truncation_fidelity, value_of_zero, max_bond)
         return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond)
@@ -401,7 +410,9 @@ def _use_native() -> bool:
     return os.environ.get("QK_NATIVE_BUILDER", "1") != "0" and _native_builder() is not None
 
 
-def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: float, max_bond: int | None = None) -> MPS:
+def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: float, max_bond: int | None = None, checkpoints=None):
+    """The numpy loop.  With ``checkpoints`` (validated gate counts) the return value is the list of snapshots: copies, the run itself
+    is the one without them."""
     n = circuit.n_qubits
     check_op_codes(circuit.op)
     budget = max(0.0, 1.0 - float(truncation_fidelity))
@@ -417,8 +428,11 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
     fidelity = 1.0
     centre = 0  # sites < centre are left-orthonormal, sites > centre right-orthonormal
     g2 = 0  # running index into two_q_pos
+    snaps, marks = [], set(checkpoints or ())
 
-    for o, q, a in zip(ops, qs, alphas):
+    for i, (o, q, a) in enumerate(zip(ops, qs, alphas)):
+        if i in marks:  # i gates done
+            snaps.append(MPS([t.copy() for t in A], fidelity))
         if o == OP_H:
             t = A[q]
             A[q] = np.stack((t[:, 0] + t[:, 1], t[:, 0] - t[:, 1]), axis=1) * _SQRT_HALF
@@ -493,4 +507,6 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             A[q] = (u[:, :keep] * s[None, :]).reshape(l, 2, keep)
             A[q + 1] = vh[:keep].reshape(keep, 2, r)
             centre = q
+    if checkpoints is not None:
+        return snaps + [MPS(A, fidelity)]
     return MPS(A, fidelity)
