@@ -100,7 +100,7 @@ struct QkSpectraArgs {
   const int32_t* states;  // batch entry -> state of the set
   const int32_t* pmax;    // batch entry -> P
   const int64_t* sbase;   // batch entry -> first double of its environments
-  const int64_t* roff;    // [batch][n_sites + 1]: R_k at sbase + rmul P^2 + roff[k]
+  const int64_t* roff;    // [batch][n_sites + 1]: R_k at sbase + rmul P^2 + roff[k] (the layout is described in qk_local_plan.h)
   const int64_t* loff;    // likewise L_k
   const int2* tasks;      // (batch entry, bond k), true bond >= 2
   int n_tasks;

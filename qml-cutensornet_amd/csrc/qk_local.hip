@@ -64,7 +64,7 @@
 //     value = Re sum_{b', a'} E_{b+1}[b'][a'] R_{b+1}[b'][a'] / L_n[0][0]
 // An environment pass per state batch -- the reversed chain and the forward T / W launches of the one-qubit sweep, then L_{k+1} from
 // W by the sum the rho kernel makes, so the norms are that sweep's bits -- keeps every R_k and every L_k.  A chain is one
-// (state, string) with its own slot (E and the intermediate T, 6 P^2 doubles).  At site k every live chain (a <= k <= b) of the chain
+// (state, string) with its own slot (E and the intermediate T).  At site k every live chain (a <= k <= b) of the chain
 // batch goes through ONE T-shaped launch (the LOC_DIST_T shape; a chain that starts at k reads the kept L_k in place of its slot),
 // ONE elementwise launch over T for the chains whose code at k is not I (T[(a, s ^ f)] <- i^e(s) T[(a, s)]: the product below pairs
 // row (a, u) of T with conj(A_k[(a, u)]), so the Pauli costs no matrix work), ONE X-shaped launch (LOC_DIST_X: one product over
@@ -72,7 +72,12 @@
 // names the chain.  4 n_sites launches per chain batch, whatever the number of strings; a string costs work on its support only.  The
 // chunk sums of a chain are added in a fixed order and nothing of a chain depends on another chain, so a value is the same bits
 // whatever the other states and strings, their order and the cut of the batches (QK_STRINGS_BATCH caps the chains of one).
+//
+// The launch kinds, the layout of a state's scratch and of a chain's slot, the pair index, the sizes, the cut into batches and the
+// task lists are host-side planning, in qk_local_plan.h (tested on the CPU).  Every entry point runs on one driver: env_sizes,
+// env_tables (the batch's tables and the task lists of its plan) and env_run (upload, reverse, init, then the plan on the stream).
 #include "qk_host.h"
+#include "qk_local_plan.h"
 #include "qk_ring.h"
 
 #include <algorithm>
@@ -83,35 +88,13 @@
 
 namespace {
 
+using namespace qkl;
+static_assert(at_L() == 0 && chain_E() == 0, "the kernels address L and a chain's E at the base of the scratch / slot");
+static_assert(sizeof(Task2) == sizeof(int2) && offsetof(Task2, x) == offsetof(int2, x) && offsetof(Task2, y) == offsetof(int2, y), "Task2 is the host image of int2");
+
 constexpr int LOC_KTL = 8, LOC_NSLOT = 3;                           // the ring GEMM's fp64 shape (K-tile 8, three 16-KiB slots)
 constexpr int LOC_LDS_DOUBLES = LOC_NSLOT * (4 * LOC_KTL * 64);     // 48 KiB
 constexpr int LOC_RED_THREADS = 256;                                // workgroup of the rho / L_{k+1} step
-constexpr int LOC_CHUNK = 16;                                       // rows of b' per reduction task
-
-enum LocKind : int {
-  LOC_REV_T = 0,   // reversed chain: T = Lr^T Ar_j              (Lr_j = R_{o+1}, o = n-1-j)
-  LOC_REV_X = 1,   // reversed chain: R_o = T^T conj(Ar_j)
-  LOC_FWD_T = 2,   // T_k = L_k^T A_k
-  LOC_FWD_W = 3,   // W_{k,s} = T_k[(., s)]^T conj(A_k), both s in one launch
-  LOC_PAIR_T = 4,  // pair sweep, site o = k+1 of the reversed image: T' = R_{o+1}^T Ar_o
-  LOC_PAIR_V = 5,  // pair sweep: V_{o,t} = T'[(., t)]^T conj(Ar_o), both t in one launch
-  LOC_DIST_T = 6,  // distant pairs, site k: T''_(o,s,s') = E_{o->k}[s][s']^T A_k for every live origin o, in one launch
-  LOC_DIST_X = 7,  // distant pairs: E_{o->k+1}[s][s'] = T''_(o,s,s')^T conj(A_k) over K = (a, u), back into the origin's slot
-  LOC_BOND_M = 8,  // bond purities: M_k = L_k^T R_k (= N_k^H) of bond k = step, from the kept environments into the T planes
-  LOC_RHO = -1,    // qk_local_rho_kernel
-  LOC_PAIR_RHO = -2,  // qk_local_pair_rho_kernel<false>
-  LOC_DIST_RHO = -3,  // qk_local_pair_rho_kernel<true>: rho_{o,k+1} of every live origin from its window slot
-  LOC_ADMIT = -4,  // qk_local_admit_kernel: W_k into the window
-  LOC_BOND_TR = -5,  // qk_bond_trace_kernel: tr(M_k^2) of bond k = step in 16-row chunks
-};
-
-// Per-state scratch (doubles, every matrix as a re plane then an im plane), P = the state's largest padded bond:
-//   L [P x P] at 0 | T [P x 2P] at 2P^2 | W_0 [P x 2P] at 6P^2 | W_1 at 10P^2 | R_1 .. R_n at rmul P^2 + roff[k] (pad_k^2 per plane)
-// rmul = 14 for the one-qubit sweep; the pair sweep has T' at 14P^2, V_0 at 18P^2, V_1 at 22P^2 and rmul = 26.  Pairs up to
-// distance D add, between V_1 and the R_k, the window -- D - 1 slots of 8P^2, slot e at (26 + 8e)P^2 holding (W_0 | W_1) of its
-// origin carried to the current bond -- and the 4 (D - 1) intermediates T'' of 4P^2 at (26 + 8(D-1) + 4w)P^2,
-// w = 4 (k - 1 - o) + 2s + s': rmul = 26 + 24 (D - 1).
-constexpr int LOC_RMUL = 14, LOC_RMUL_PAIR = 26, LOC_RMUL_DIST = 24;
 constexpr int LOC_PAIR_VALS = 16;                                   // reals of a Hermitian 4 x 4 matrix
 struct LocArgs {
   const double* data;     // the set's planes
@@ -123,7 +106,7 @@ struct LocArgs {
   const int32_t* pmax;    // batch entry -> P
   const int64_t* sbase;   // batch entry -> first double of its scratch
   const int64_t* roff;    // [batch][n_sites + 1]: R_k at sbase + rmul P^2 + roff[k]
-  const int64_t* loff;    // environment pass (env_run): the kept L_k at sbase + LOC_RMUL P^2 + loff[k]; NULL in the local sweeps
+  const int64_t* loff;    // [batch][n_sites + 1]: the kept L_k at sbase + rmul P^2 + loff[k]; NULL where they are not kept (the local sweeps)
   const int2* tasks;      // this launch: (batch entry, block)
   double* scratch;
   double* part;           // rho partial sums [batch][n_sites][max chunks][4]
@@ -156,7 +139,7 @@ __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, con
   const long long P = __builtin_amdgcn_readfirstlane(g.pmax[i]);
   double* const S = g.scratch + uni64(g.sbase[i]);
   const long long P2 = P * P;
-  double* const Tre = S + 2 * P2;
+  double* const Tre = S + at_T() * P2;
   const long long tpl = 2 * P2;  // T and W planes
   const double *Are, *Aim, *Bre, *Bim;
   double *Cre, *Cim;
@@ -179,13 +162,13 @@ __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, con
     if (kind == LOC_REV_T || kind == LOC_PAIR_T) {
       Are = S + g.rmul * P2 + uni64(g.roff[(long long)i * n1 + o + 1]);
       Aim = Are + (long long)al * al;
-      Cre = (kind == LOC_REV_T) ? Tre : S + 14 * P2, Cim = Cre + tpl;
+      Cre = (kind == LOC_REV_T) ? Tre : S + at_Tp() * P2, Cim = Cre + tpl;
       lda = al, ldb = 2 * ar, ldc = 2 * ar, M = al, N = 2 * ar, K = at;
     } else if (kind == LOC_PAIR_V) {
       M = ar, N = 2 * ar;
       const int t = blk >= ((M + 63) / 64) * ((N + 63) / 64);
-      Are = S + 14 * P2 + t * ar, Aim = Are + tpl;
-      Cre = S + 18 * P2 + t * 2 * tpl, Cim = Cre + tpl;
+      Are = S + at_Tp() * P2 + t * ar, Aim = Are + tpl;
+      Cre = S + at_V(t) * P2, Cim = Cre + tpl;
       lda = 2 * ar, ldb = 2 * ar, ldc = 2 * ar, K = at;
     } else {
       Are = Tre, Aim = Tre + tpl;
@@ -203,8 +186,8 @@ __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, con
       // block number = (w, block of the product), w = 4 (k - 1 - o) + 2s + s' for the live origin o
       const int per = (kind == LOC_DIST_T) ? ((l + 63) / 64) * ((2 * r + 63) / 64) : ((r + 63) / 64) * ((r + 63) / 64);
       const int w = blk / per, o = k - 1 - (w >> 2), s = (w >> 1) & 1, sp = w & 1;
-      double* const E = S + (LOC_RMUL_PAIR + 8 * (o % (g.max_dist - 1))) * P2 + s * 2 * tpl;  // E[s][.][(s', .)] of origin o
-      double* const Tw = S + (LOC_RMUL_PAIR + 8 * (g.max_dist - 1) + 4 * w) * P2;
+      double* const E = S + window_slot(o, g.max_dist) * P2 + s * 2 * tpl;  // E[s][.][(s', .)] of origin o
+      double* const Tw = S + window_tmp(w, g.max_dist) * P2;
       blk -= w * per;
       if (kind == LOC_DIST_T) {
         Are = E + sp * l, Aim = Are + tpl;
@@ -224,7 +207,7 @@ __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, con
       const int per_s = ((M + 63) / 64) * ((N + 63) / 64);
       const int s = blk >= per_s;
       Are = Tre + s * r, Aim = Are + tpl;
-      Cre = S + 6 * P2 + s * 2 * tpl, Cim = Cre + tpl;
+      Cre = S + at_W(s) * P2, Cim = Cre + tpl;
       lda = 2 * r, ldb = 2 * r, ldc = 2 * r, K = lt;
     }
   }
@@ -233,6 +216,22 @@ __global__ __launch_bounds__(512) void qk_local_gemm_kernel(const LocArgs g, con
   const int m0 = 64 * (b % npm), n0 = 64 * (b / npm);
   zgemm_ring3<CONJB, LOC_KTL, LOC_NSLOT, true, 8, 64, double, 7>(Cre + (long long)m0 * ldc + n0, Cim + (long long)m0 * ldc + n0, ldc, Are + m0, Aim + m0, lda,
                                                                   Bre + n0, Bim + n0, ldb, min(64, M - m0), min(64, N - n0), K, lds);
+}
+
+// The sum of NV values per thread over the 256 threads of a workgroup, into red[v][0]: a fixed-order tree, halving from 128, the
+// same order whatever NV, so a result is the same bits as when each reduction kernel wrote its own loop.
+// LDS: red[NV][256] doubles -- 32 KiB at NV = 16 (qk_local_pair_rho_kernel), five workgroups (20 waves) per CU: that kernel waits on
+// its 16 global loads per element, not on occupancy.  Every access is red[v][thread]: the 32 lanes that a ds_read_b64 /
+// ds_write_b64 serves together touch 32 consecutive doubles, each of the 64 banks once, so the layout is conflict-free for every NV.
+template <int NV>
+__device__ __forceinline__ void tree_sum(double (&red)[NV][LOC_RED_THREADS], const double (&acc)[NV]) {
+  for (int v = 0; v < NV; ++v) red[v][threadIdx.x] = acc[v];
+  __syncthreads();
+  for (int h = LOC_RED_THREADS / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h)
+      for (int v = 0; v < NV; ++v) red[v][threadIdx.x] += red[v][threadIdx.x + h];
+    __syncthreads();
+  }
 }
 
 // rho_k partial sums of one 16-row chunk of b' and the same rows of L_{k+1} = W_0[.][(0, .)] + W_1[.][(1, .)].
@@ -246,8 +245,8 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_rho_kernel(const Loc
   const int r = g.dims[st * n1 + k + 1];
   const long long P = g.pmax[i], P2 = P * P, tpl = 2 * P2;
   double* const S = g.scratch + g.sbase[i];
-  const double* W0 = S + 6 * P2;
-  const double* W1 = W0 + 2 * tpl;
+  const double* W0 = S + at_W(0) * P2;
+  const double* W1 = S + at_W(1) * P2;
   const double* R = S + g.rmul * P2 + g.roff[(long long)i * n1 + k + 1];
   const long long rpl = (long long)r * r;
   double a00 = 0, a11 = 0, a01r = 0, a01i = 0;
@@ -266,25 +265,17 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_rho_kernel(const Loc
     S[q] = w00r + w11r;  // L_{k+1}[b'][a'], ld r
     S[q + P2] = w00i + w11i;
   }
-  red[0][threadIdx.x] = a00, red[1][threadIdx.x] = a11, red[2][threadIdx.x] = a01r, red[3][threadIdx.x] = a01i;
-  __syncthreads();
-  for (int h = LOC_RED_THREADS / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h)
-      for (int v = 0; v < 4; ++v) red[v][threadIdx.x] += red[v][threadIdx.x + h];
-    __syncthreads();
-  }
+  const double acc[4] = {a00, a11, a01r, a01i};
+  tree_sum(red, acc);
   if (threadIdx.x < 4) g.part[(((long long)i * n + k) * g.max_chunks + c) * 4 + threadIdx.x] = red[threadIdx.x][0];
 }
 
 // rho_{k,k+1} partial sums of one 16-row chunk of b': the products W_{k,s}[b'][(s', a')] V_{k+1,t}[b'][(t', a')] over the chunk's
 // rows and every a'.  The matrix is Hermitian (row 2s + t, column 2s' + t'), so a chunk keeps its 16 reals, unnormalised:
 //     part2[(i, k, chunk)] = Re rho[0][0], [1][1], [2][2], [3][3], then (Re, Im) of rho[0][1], [0][2], [0][3], [1][2], [1][3], [2][3]
-// LDS: red[16][256] doubles = 32 KiB, five workgroups (20 waves) per CU -- the kernel waits on its 16 global loads per element,
-// not on occupancy.  Every access is red[v][thread]: the 32 lanes that a ds_read_b64 / ds_write_b64 serves together touch 32
-// consecutive doubles, each of the 64 banks once, so the layout is conflict-free like the 4-value one of qk_local_rho_kernel.
+// The 16 sums go through tree_sum (red[16][256] doubles of LDS).
 // DIST: the pairs (o, k+1) of the live origins o = k-1, k-2, ..: a task is (batch entry, (k - 1 - o) chunks + chunk) and the left
-// operand is the origin's window slot, which has W's layout; the LDS layout, the accesses and the tree are the same, so the
-// argument above holds for both forms.
+// operand is the origin's window slot, which has W's layout; the LDS layout, the accesses and the tree are the same for both forms.
 template <bool DIST>
 __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_pair_rho_kernel(const LocArgs g) {
   __shared__ double red[LOC_PAIR_VALS][LOC_RED_THREADS];
@@ -296,9 +287,9 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_pair_rho_kernel(cons
   const int age = DIST ? t.y / (r / LOC_CHUNK) : 0, c = t.y - age * (r / LOC_CHUNK);
   const long long P = g.pmax[i], P2 = P * P, tpl = 2 * P2;
   const double* const S = g.scratch + g.sbase[i];
-  const double* const W0 = DIST ? S + (LOC_RMUL_PAIR + 8 * ((k - 1 - age) % (g.max_dist - 1))) * P2 : S + 6 * P2;
+  const double* const W0 = S + (DIST ? window_slot(k - 1 - age, g.max_dist) : at_W(0)) * P2;
   const double* W[2] = {W0, W0 + 2 * tpl};
-  const double* V[2] = {S + 18 * P2, S + 18 * P2 + 2 * tpl};
+  const double* V[2] = {S + at_V(0) * P2, S + at_V(1) * P2};
   double acc[LOC_PAIR_VALS] = {};
   const int rows = LOC_CHUNK * r;
   for (int e = threadIdx.x; e < rows; e += LOC_RED_THREADS) {
@@ -326,15 +317,8 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_pair_rho_kernel(cons
         }
       }
   }
-  for (int v = 0; v < LOC_PAIR_VALS; ++v) red[v][threadIdx.x] = acc[v];
-  __syncthreads();
-  for (int h = LOC_RED_THREADS / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h)
-      for (int v = 0; v < LOC_PAIR_VALS; ++v) red[v][threadIdx.x] += red[v][threadIdx.x + h];
-    __syncthreads();
-  }
-  // pair (k, k+1) is index k; pair (o, k+1) at distance d = age + 2 is index (d - 1) n - (d - 1) d / 2 + o
-  const long long pi = DIST ? (long long)(age + 1) * n - (age + 1) * (age + 2) / 2 + (k - 1 - age) : k;
+  tree_sum(red, acc);
+  const long long pi = DIST ? pair_index(age + 2, k - 1 - age, n) : k;  // the pair (o, k+1) of origin o = k - 1 - age
   if (threadIdx.x < LOC_PAIR_VALS)
     g.part2[(((long long)i * g.n_pairs + pi) * g.max_chunks + c) * LOC_PAIR_VALS + threadIdx.x] = red[threadIdx.x][0];
 }
@@ -349,15 +333,15 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_local_admit_kernel(const L
   const int r = g.dims[st * n1 + k + 1];
   const long long P = g.pmax[i], P2 = P * P;
   double* const S = g.scratch + g.sbase[i];
-  const double* const W = S + 6 * P2;
-  double* const E = S + (LOC_RMUL_PAIR + 8 * (k % (g.max_dist - 1))) * P2;
+  const double* const W = S + at_W(0) * P2;
+  double* const E = S + window_slot(k, g.max_dist) * P2;
   const long long row0 = (long long)c * LOC_CHUNK * 2 * r;
   const int cnt = LOC_CHUNK * 2 * r;
   for (int e = threadIdx.x; e < cnt; e += LOC_RED_THREADS)
     for (int pl = 0; pl < 4; ++pl) E[pl * 2 * P2 + row0 + e] = W[pl * 2 * P2 + row0 + e];
 }
 
-// L_0 = 1 and R_n = 1 (16 x 16, [0][0] = 1) of every state of the batch.
+// L_0 = 1 and R_n = 1 (16 x 16, [0][0] = 1) of every state of the batch, and the kept L_0 where the L_k are kept.
 __global__ __launch_bounds__(256) void qk_local_init_kernel(const LocArgs g, const int nb) {
   const int i = blockIdx.x;
   if (i >= nb) return;
@@ -368,6 +352,10 @@ __global__ __launch_bounds__(256) void qk_local_init_kernel(const LocArgs g, con
   const double v = (e == 0) ? 1.0 : 0.0;
   S[e] = v, S[P2 + e] = 0.0;
   Rn[e] = v, Rn[256 + e] = 0.0;
+  if (g.loff) {
+    double* const L0 = S + g.rmul * P2 + g.loff[(long long)i * (g.n_sites + 1)];
+    L0[e] = v, L0[256 + e] = 0.0;
+  }
 }
 
 // The reversed image of the batch's states: site o of state st, [a][s][b] -> [b][s][a] in both planes, at the same offset.
@@ -415,9 +403,7 @@ __global__ __launch_bounds__(256) void qk_local_pair_features_kernel(const LocAr
   const int i = (int)(id / np), k = (int)(id % np);  // k = index(d, o) of the pair (o, o + d)
   const long long st = g.states[i];
   const double nrm = g.scratch[g.sbase[i]];  // L_n[0][0]
-  int second = k + 1;  // the pair's second qubit: its partial sums are over the chunks of that qubit's left bond
-  for (int d = 1; second > n - 1; ++d) second -= n - d - 1;
-  const int chunks = g.dims[st * n1 + second] / LOC_CHUNK;
+  const int chunks = g.dims[st * n1 + pair_second(k, n)] / LOC_CHUNK;  // the partial sums are over the chunks of the second qubit's left bond
   const double* p = g.part2 + ((long long)i * np + k) * g.max_chunks * LOC_PAIR_VALS;
   double v[LOC_PAIR_VALS] = {};
   for (int c = 0; c < chunks; ++c)
@@ -479,185 +465,6 @@ __global__ __launch_bounds__(256) void qk_projected_gram_kernel(const double* fx
     }
 }
 
-inline int pad16h(int x) { return (x + 15) / 16 * 16; }
-inline long long blocks64(long long m, long long n) { return ((m + 63) / 64) * ((n + 63) / 64); }
-
-// The local sweep of a set.  out1 = Bloch vectors [n_states][n_sites][3] (may be NULL when out2 is given), norms (may be NULL);
-// out2 = Pauli correlators of the pairs up to distance max_dist [n_states][n_pairs][4][4] (NULL: the one-qubit sweep alone).
-int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* range, double* out1, double* norms, double* out2, const int max_dist) {
-  const bool pair = out2 != nullptr;
-  if (!c || !set || (!out1 && !out2)) return qk_fail(QK_EINVAL, "%s: null argument", what);
-  if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: the set belongs to another context", what);
-  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: complex64 sets are not supported; local Paulis need an fp64 set", what);
-  const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
-  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: empty set", what);
-  if (pair && n < 2) return qk_fail(QK_EINVAL, "%s: pairs of neighbouring qubits need n_sites >= 2 (got %d)", what, n);
-  if (pair && (max_dist < 1 || max_dist > n - 1)) return qk_fail(QK_EINVAL, "%s: max_dist must be in 1 .. n_sites - 1 = %d (got %d)", what, n - 1, max_dist);
-  QkRangeGuard range_(range);
-  const int D = pair ? max_dist : 1;
-  const int n_pairs = pair ? D * n - D * (D + 1) / 2 : 0;
-  const int rmul = pair ? LOC_RMUL_PAIR + LOC_RMUL_DIST * (D - 1) : LOC_RMUL;  // the window and its intermediates count in need[s]
-  HIP_TRY_AS(what, hipSetDevice(c->device));
-  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
-  std::vector<int64_t> offs((size_t)ns * n);
-  HIP_TRY_AS(what, hipMemcpy(offs.data(), set->d_offs.get<int64_t>(), offs.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-  const int32_t* tru = set->dims_true.data();
-  std::vector<int32_t> pad((size_t)ns * n1);
-  std::vector<int> pmax(ns);
-  std::vector<long long> need(ns);  // scratch doubles of each state
-  for (int s = 0; s < ns; ++s) {
-    int p = 16;
-    long long rsum = 0;
-    for (int k = 0; k <= n; ++k) {
-      pad[(size_t)s * n1 + k] = pad16h(tru[(size_t)s * n1 + k]);
-      p = std::max(p, pad[(size_t)s * n1 + k]);
-      if (k >= 1) rsum += 2ll * pad[(size_t)s * n1 + k] * pad[(size_t)s * n1 + k];
-    }
-    pmax[s] = p;
-    need[s] = (long long)rmul * p * p + rsum;
-  }
-  const int max_chunks = set->max_pad / LOC_CHUNK;
-  const long long part1_per_state = (long long)n * max_chunks * 4;
-  const long long part_per_state = part1_per_state + (long long)n_pairs * max_chunks * LOC_PAIR_VALS;
-  // memory bound of the per-state scratch: a quarter of what is free once the reversed image and the outputs exist
-  QkDevBuf rev, dout, dnorm, dout2;
-  HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
-  HIP_TRY_AS(what, dout.alloc((size_t)ns * n * 3 * sizeof(double)));
-  HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
-  if (pair) HIP_TRY_AS(what, dout2.alloc((size_t)ns * n_pairs * 16 * sizeof(double)));
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
-  const long long budget = (long long)((free_b + c->local_scratch.bytes) / 4 / sizeof(double));
-  // batches: consecutive states while their scratch and rho partials fit the budget (at least one state per batch)
-  std::vector<int> bstart{0};
-  for (long long acc = 0, s = 0; s < ns; ++s) {
-    const long long w = need[s] + part_per_state;
-    if (acc > 0 && acc + w > budget) bstart.push_back((int)s), acc = 0;
-    acc += w;
-  }
-  bstart.push_back(ns);
-  const int n_rev = n - 1;  // reversed-chain steps: R_{n-1} .. R_1 (R_0 is not needed)
-  // the launches of a batch, in stream order: reversed T / X per step, then per site forward T / W, the pair sweep's T' / V of
-  // site k+1, rho (which also makes L_{k+1}) and the pair rho; with D > 1 then the live origins k-D+1 .. k-1 through site k, their
-  // rho_{o,k+1}, and W_k into the window for the sites after k+1
-  std::vector<std::pair<int, int>> plan;  // (kind, step)
-  for (int j = 0; j < n_rev; ++j) plan.push_back({LOC_REV_T, j}), plan.push_back({LOC_REV_X, j});
-  for (int k = 0; k < n; ++k) {
-    plan.push_back({LOC_FWD_T, k}), plan.push_back({LOC_FWD_W, k});
-    if (pair && k + 1 < n) plan.push_back({LOC_PAIR_T, k}), plan.push_back({LOC_PAIR_V, k});
-    plan.push_back({LOC_RHO, k});
-    if (pair && k + 1 < n) plan.push_back({LOC_PAIR_RHO, k});
-    if (D > 1 && k >= 1 && k + 1 < n) plan.push_back({LOC_DIST_T, k}), plan.push_back({LOC_DIST_X, k}), plan.push_back({LOC_DIST_RHO, k});
-    if (D > 1 && k + 2 < n) plan.push_back({LOC_ADMIT, k});
-  }
-  std::vector<int2> tasks;
-  std::vector<long long> first;  // per launch: first task
-  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
-    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
-    // tables of the batch: states, P, scratch bases, R offsets
-    std::vector<int32_t> h_states(nb), h_pmax(nb);
-    std::vector<int64_t> h_sbase(nb), h_roff((size_t)nb * n1);
-    long long tot = 0;
-    for (int i = 0; i < nb; ++i) {
-      const int s = s0 + i;
-      h_states[i] = s, h_pmax[i] = pmax[s], h_sbase[i] = tot;
-      long long ro = 0;
-      for (int k = 0; k <= n; ++k) {
-        h_roff[(size_t)i * n1 + k] = ro;
-        if (k >= 1) ro += 2ll * pad[(size_t)s * n1 + k] * pad[(size_t)s * n1 + k];
-      }
-      tot += need[s];
-    }
-    // task lists of every launch of the batch, in launch order
-    tasks.clear(), first.clear();
-    for (const auto& [kind, step] : plan) {
-      first.push_back((long long)tasks.size());
-      for (int i = 0; i < nb; ++i) {
-        const int* p = &pad[(size_t)(s0 + i) * n1];
-        const int o = n - 1 - step, k = step;
-        const int live = std::min(k, D - 1);  // origins in the window at site k
-        int nbk = 0;
-        switch (kind) {
-          case LOC_REV_T: nbk = (int)blocks64(p[o + 1], 2ll * p[o]); break;
-          case LOC_REV_X: nbk = (int)blocks64(p[o], p[o]); break;
-          case LOC_FWD_T: nbk = (int)blocks64(p[k], 2ll * p[k + 1]); break;
-          case LOC_FWD_W: nbk = (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); break;
-          case LOC_PAIR_T: nbk = (int)blocks64(p[k + 2], 2ll * p[k + 1]); break;
-          case LOC_PAIR_V: nbk = (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); break;
-          case LOC_DIST_T: nbk = (int)(4 * live * blocks64(p[k], 2ll * p[k + 1])); break;
-          case LOC_DIST_X: nbk = (int)(4 * live * blocks64(p[k + 1], p[k + 1])); break;
-          case LOC_DIST_RHO: nbk = live * (p[k + 1] / LOC_CHUNK); break;
-          default: nbk = p[k + 1] / LOC_CHUNK; break;  // LOC_RHO, LOC_PAIR_RHO, LOC_ADMIT
-        }
-        for (int b = 0; b < nbk; ++b) tasks.push_back(int2{i, b});
-      }
-    }
-    first.push_back((long long)tasks.size());
-    // one device buffer for the batch: [tables | tasks | partials | per-state scratch]
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_states = al(nb * sizeof(int32_t)), b_pmax = al(nb * sizeof(int32_t)), b_sbase = al(nb * sizeof(int64_t));
-    const size_t b_roff = al(h_roff.size() * sizeof(int64_t)), b_tasks = al(tasks.size() * sizeof(int2));
-    const size_t b_part = al((size_t)nb * part_per_state * sizeof(double)), b_scr = (size_t)tot * sizeof(double);
-    const size_t b_tab = b_states + b_pmax + b_sbase + b_roff + b_tasks;
-    HIP_TRY_AS(what, c->local_scratch.ensure(b_tab + b_part + b_scr));
-    char* base = c->local_scratch.get<char>();
-    std::vector<char> stage(b_tab);
-    size_t at = 0;
-    auto put = [&](const void* src, size_t bytes, size_t span) {
-      std::memcpy(stage.data() + at, src, bytes);
-      const size_t here = at;
-      at += span;
-      return base + here;
-    };
-    LocArgs g{};
-    g.data = set->d_data.get<double>();
-    g.rev = rev.get<double>();
-    g.dims = set->d_dims.get<int32_t>();
-    g.tru = set->d_true.get<int32_t>();
-    g.offs = set->d_offs.get<int64_t>();
-    g.states = reinterpret_cast<const int32_t*>(put(h_states.data(), nb * sizeof(int32_t), b_states));
-    g.pmax = reinterpret_cast<const int32_t*>(put(h_pmax.data(), nb * sizeof(int32_t), b_pmax));
-    g.sbase = reinterpret_cast<const int64_t*>(put(h_sbase.data(), nb * sizeof(int64_t), b_sbase));
-    g.roff = reinterpret_cast<const int64_t*>(put(h_roff.data(), h_roff.size() * sizeof(int64_t), b_roff));
-    const int2* d_tasks = reinterpret_cast<const int2*>(put(tasks.data(), tasks.size() * sizeof(int2), b_tasks));
-    g.part = reinterpret_cast<double*>(base + b_tab);
-    g.part2 = g.part + (size_t)nb * part1_per_state;
-    g.scratch = reinterpret_cast<double*>(base + b_tab + b_part);
-    g.rmul = rmul;
-    g.max_dist = D;
-    g.n_pairs = n_pairs;
-    g.n_sites = n;
-    g.max_chunks = max_chunks;
-    HIP_TRY_AS(what, hipMemcpyAsync(base, stage.data(), b_tab, hipMemcpyHostToDevice, c->stream));
-    qk_local_reverse_kernel<<<dim3(nb, n), dim3(256), 0, c->stream>>>(g, rev.get<double>());
-    qk_local_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, nb);
-    HIP_TRY_AS(what, hipGetLastError());
-    for (size_t li = 0; li < plan.size(); ++li) {
-      const int kind = plan[li].first;
-      g.tasks = d_tasks + first[li];
-      g.step = plan[li].second;
-      const long long grid = first[li + 1] - first[li];
-      if (grid <= 0) continue;
-      if (kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V || kind == LOC_DIST_X) qk_local_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
-      else if (kind >= 0) qk_local_gemm_kernel<false><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
-      else if (kind == LOC_RHO) qk_local_rho_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
-      else if (kind == LOC_PAIR_RHO) qk_local_pair_rho_kernel<false><<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
-      else if (kind == LOC_DIST_RHO) qk_local_pair_rho_kernel<true><<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
-      else qk_local_admit_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
-    }
-    HIP_TRY_AS(what, hipGetLastError());
-    const long long nf = (long long)nb * n;
-    qk_local_features_kernel<<<dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, dout.get<double>(), dnorm.get<double>());
-    if (pair) qk_local_pair_features_kernel<<<dim3((unsigned)(((long long)nb * n_pairs + 255) / 256)), dim3(256), 0, c->stream>>>(g, nb, dout2.get<double>());
-    HIP_TRY_AS(what, hipGetLastError());
-    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
-  }
-  if (out1) HIP_TRY_AS(what, hipMemcpy(out1, dout.get(), (size_t)ns * n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-  if (norms) HIP_TRY_AS(what, hipMemcpy(norms, dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
-  if (pair) HIP_TRY_AS(what, hipMemcpy(out2, dout2.get(), (size_t)ns * n_pairs * 16 * sizeof(double), hipMemcpyDeviceToHost));
-  return QK_OK;
-}
-
 // The PQK Gram of host feature arrays [n][D]: out[j * ld + i] = exp(-factor sum_d (fx[i][d] - fy[j][d])^2).
 int projected_gram(qk_ctx* c, const char* what, const char* range, int32_t n_sites, int min_sites, int D, double factor, int32_t nx, const double* fx,
                    int32_t ny, const double* fy, double g, double* out, int64_t ld) {
@@ -685,26 +492,9 @@ int projected_gram(qk_ctx* c, const char* what, const char* range, int32_t n_sit
 }
 
 // ---- Pauli strings (qk_pauli_strings_host) ------------------------------------------------------------------------------------
-// A chain is one (state, string) with a non-identity site; its support is [a, b].  Its slot (doubles, P = the state's largest
-// padded bond): E [P x P] at 0 (re plane, im plane at P^2, ld = the current padded bond) | T [P x 2P] at 2P^2 (im plane at 4P^2).
-enum StrKind : int {
-  STR_T = 0,       // T[a][(s, b')] = sum_b E_k[b][a] A_k[b][(s, b')] of every live chain (the LOC_DIST_T shape); E_a is read from the stored L_a
-  STR_X = 1,       // E_{k+1}[b'][a'] = sum_{(a,u)} T[(a, u)][b'] conj(A_k[(a, u)][a']) over K = 2 chi_k (the LOC_DIST_X shape)
-  STR_PAULI = -1,  // qk_str_pauli_kernel: T[a][(s ^ f, b')] <- i^e(s) T[a][(s, b')] of the chains whose code at site k is not I
-  STR_CLOSE = -2,  // qk_str_close_kernel: sum E_{b+1} R_{b+1} of the chains whose support ends at site k
-  STR_LNEXT = -3,  // qk_str_lnext_kernel (environment pass): L_{k+1} = W_0[.][(0, .)] + W_1[.][(1, .)], kept
-};
+// A chain is one (state, string) with a non-identity site; its support is [a, b].  Its slot is laid out in qk_local_plan.h.
 struct StrArgs {
-  const double* data;     // the set's planes and tables, as LocArgs
-  const int32_t* dims;
-  const int32_t* tru;
-  const int64_t* offs;
-  const int32_t* states;  // the state batch's tables, as LocArgs
-  const int32_t* pmax;
-  const int64_t* sbase;
-  const int64_t* roff;
-  const int64_t* loff;    // [batch][n_sites + 1]: the kept L_k (k = 0 .. n_sites - 1) at sbase + LOC_RMUL P^2 + loff[k], pad_k^2 per plane
-  const double* env;      // the state batch's scratch (LocArgs.scratch): sweep planes, every R_k, every L_k
+  LocArgs e;              // the set and the state batch of the environment pass: e.scratch holds the sweep planes, every R_k, every L_k
   const int32_t* cent;    // chain -> batch entry
   const int32_t* cstr;    // chain -> string
   const int64_t* cbase;   // chain -> first double of its slot
@@ -713,8 +503,6 @@ struct StrArgs {
   const int2* tasks;      // this launch: (chain, block)
   double* slots;
   double* part;           // closing partial sums [chain][max chunks]
-  int n_sites;
-  int max_chunks;
   int step;               // site k
 };
 
@@ -726,14 +514,14 @@ __global__ __launch_bounds__(512) void qk_str_gemm_kernel(const StrArgs g) {
   const int ch = __builtin_amdgcn_readfirstlane(t.x);
   const int blk = __builtin_amdgcn_readfirstlane(t.y);
   const int i = __builtin_amdgcn_readfirstlane(g.cent[ch]);
-  const int n = g.n_sites, n1 = n + 1, k = g.step;
-  const long long st = __builtin_amdgcn_readfirstlane(g.states[i]);
-  const int l = __builtin_amdgcn_readfirstlane(g.dims[st * n1 + k]), r = __builtin_amdgcn_readfirstlane(g.dims[st * n1 + k + 1]);
-  const int lt = __builtin_amdgcn_readfirstlane(g.tru[st * n1 + k]);
-  const long long P = __builtin_amdgcn_readfirstlane(g.pmax[i]), P2 = P * P;
+  const int n = g.e.n_sites, n1 = n + 1, k = g.step;
+  const long long st = __builtin_amdgcn_readfirstlane(g.e.states[i]);
+  const int l = __builtin_amdgcn_readfirstlane(g.e.dims[st * n1 + k]), r = __builtin_amdgcn_readfirstlane(g.e.dims[st * n1 + k + 1]);
+  const int lt = __builtin_amdgcn_readfirstlane(g.e.tru[st * n1 + k]);
+  const long long P = __builtin_amdgcn_readfirstlane(g.e.pmax[i]), P2 = P * P;
   double* const E = g.slots + uni64(g.cbase[ch]);
-  double* const T = E + 2 * P2;
-  const double* Bre = g.data + uni64(g.offs[st * n + k]);
+  double* const T = E + chain_T() * P2;
+  const double* Bre = g.e.data + uni64(g.e.offs[st * n + k]);
   const double* Bim = Bre + (long long)l * 2 * r;
   const double *Are, *Aim;
   double *Cre, *Cim;
@@ -741,7 +529,7 @@ __global__ __launch_bounds__(512) void qk_str_gemm_kernel(const StrArgs g) {
   if (!CONJB) {
     const int a = __builtin_amdgcn_readfirstlane(g.supp[2 * __builtin_amdgcn_readfirstlane(g.cstr[ch])]);
     if (a == k) {  // the chain starts here: E_a = L_a
-      Are = g.env + uni64(g.sbase[i]) + LOC_RMUL * P2 + uni64(g.loff[(long long)i * n1 + k]);
+      Are = g.e.scratch + uni64(g.e.sbase[i]) + g.e.rmul * P2 + uni64(g.e.loff[(long long)i * n1 + k]);
       Aim = Are + (long long)l * l;
     } else {
       Are = E, Aim = E + P2;
@@ -766,12 +554,12 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_pauli_kernel(const Str
   const int2 t = g.tasks[blockIdx.x];
   const int ch = t.x, c = t.y;
   const int i = g.cent[ch], m = g.cstr[ch];
-  const int n = g.n_sites, n1 = n + 1, k = g.step;
-  const long long st = g.states[i];
-  const int r = g.dims[st * n1 + k + 1];
+  const int n = g.e.n_sites, n1 = n + 1, k = g.step;
+  const long long st = g.e.states[i];
+  const int r = g.e.dims[st * n1 + k + 1];
   const int code = g.strings[(long long)m * n + k];
-  const long long P = g.pmax[i], P2 = P * P, tpl = 2 * P2;
-  double* const T = g.slots + g.cbase[ch] + 2 * P2;
+  const long long P = g.e.pmax[i], P2 = P * P, tpl = 2 * P2;
+  double* const T = g.slots + g.cbase[ch] + chain_T() * P2;
   const int cnt = LOC_CHUNK * r;
   for (int e = threadIdx.x; e < cnt; e += LOC_RED_THREADS) {
     const long long q0 = (long long)(c * LOC_CHUNK + e / r) * 2 * r + e % r, q1 = q0 + r;
@@ -786,34 +574,29 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_pauli_kernel(const Str
 
 // Re sum_{b', a'} E_{b+1}[b'][a'] R_{b+1}[b'][a'] over one 16-row chunk of b', unnormalised: part[(chain, chunk)].
 __global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_close_kernel(const StrArgs g) {
-  __shared__ double red[LOC_RED_THREADS];
+  __shared__ double red[1][LOC_RED_THREADS];
   const int2 t = g.tasks[blockIdx.x];
   const int ch = t.x, c = t.y;
   const int i = g.cent[ch];
-  const int n1 = g.n_sites + 1, k = g.step;
-  const long long st = g.states[i];
-  const int r = g.dims[st * n1 + k + 1];
-  const long long P = g.pmax[i], P2 = P * P, rpl = (long long)r * r;
+  const int n1 = g.e.n_sites + 1, k = g.step;
+  const long long st = g.e.states[i];
+  const int r = g.e.dims[st * n1 + k + 1];
+  const long long P = g.e.pmax[i], P2 = P * P, rpl = (long long)r * r;
   const double* const E = g.slots + g.cbase[ch];
-  const double* const R = g.env + g.sbase[i] + LOC_RMUL * P2 + g.roff[(long long)i * n1 + k + 1];
-  double acc = 0;
+  const double* const R = g.e.scratch + g.e.sbase[i] + g.e.rmul * P2 + g.e.roff[(long long)i * n1 + k + 1];
+  double acc[1] = {};
   const int rows = LOC_CHUNK * r;
   for (int e = threadIdx.x; e < rows; e += LOC_RED_THREADS) {
     const long long q = (long long)c * rows + e;
-    acc += E[q] * R[q] - E[q + P2] * R[q + rpl];
+    acc[0] += E[q] * R[q] - E[q + P2] * R[q + rpl];
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int h = LOC_RED_THREADS / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) g.part[(long long)ch * g.max_chunks + c] = red[0];
+  tree_sum(red, acc);
+  if (threadIdx.x == 0) g.part[(long long)ch * g.e.max_chunks + c] = red[0][0];
 }
 
 // Environment pass, rows b' of one 16-row chunk: L_{k+1} = W_0[.][(0, .)] + W_1[.][(1, .)] -- the sum qk_local_rho_kernel makes,
 // so L_n[0][0] is that sweep's norm bit for bit -- into the sweep's L plane and, for k + 1 < n_sites, into the kept L_{k+1}.
-__global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_lnext_kernel(const LocArgs g, const int64_t* loff) {
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_lnext_kernel(const LocArgs g) {
   const int2 t = g.tasks[blockIdx.x];
   const int i = t.x, c = t.y;
   const int n = g.n_sites, n1 = n + 1, k = g.step;
@@ -821,9 +604,9 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_lnext_kernel(const Loc
   const int r = g.dims[st * n1 + k + 1];
   const long long P = g.pmax[i], P2 = P * P, tpl = 2 * P2, rpl = (long long)r * r;
   double* const S = g.scratch + g.sbase[i];
-  const double* W0 = S + 6 * P2;
-  const double* W1 = W0 + 2 * tpl;
-  double* const Lk = (k + 1 < n) ? S + LOC_RMUL * P2 + loff[(long long)i * n1 + k + 1] : nullptr;
+  const double* W0 = S + at_W(0) * P2;
+  const double* W1 = S + at_W(1) * P2;
+  double* const Lk = (k + 1 < n) ? S + g.rmul * P2 + g.loff[(long long)i * n1 + k + 1] : nullptr;
   const int rows = LOC_CHUNK * r;
   for (int e = threadIdx.x; e < rows; e += LOC_RED_THREADS) {
     const int bp = c * LOC_CHUNK + e / r, ap = e % r;
@@ -832,14 +615,6 @@ __global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_lnext_kernel(const Loc
     S[q] = re, S[q + P2] = im;
     if (Lk) Lk[q] = re, Lk[q + rpl] = im;
   }
-}
-
-// The kept L_0 = 1 (16 x 16, [0][0] = 1) of every state of the batch.
-__global__ __launch_bounds__(256) void qk_str_init_kernel(const LocArgs g, const int64_t* loff) {
-  const int i = blockIdx.x;
-  const long long P = g.pmax[i];
-  double* const L0 = g.scratch + g.sbase[i] + LOC_RMUL * P * P + loff[(long long)i * (g.n_sites + 1)];
-  L0[threadIdx.x] = (threadIdx.x == 0) ? 1.0 : 0.0, L0[256 + threadIdx.x] = 0.0;
 }
 
 __global__ __launch_bounds__(256) void qk_str_norms_kernel(const LocArgs g, const int nb, double* norms) {
@@ -852,40 +627,35 @@ __global__ __launch_bounds__(256) void qk_str_values_kernel(const StrArgs g, con
   const int ch = blockIdx.x * 256 + threadIdx.x;
   if (ch >= nc) return;
   const int i = g.cent[ch], m = g.cstr[ch];
-  const long long st = g.states[i];
-  const int chunks = g.dims[st * (g.n_sites + 1) + g.supp[2 * m + 1] + 1] / LOC_CHUNK;
-  const double* p = g.part + (long long)ch * g.max_chunks;
+  const long long st = g.e.states[i];
+  const int chunks = g.e.dims[st * (g.e.n_sites + 1) + g.supp[2 * m + 1] + 1] / LOC_CHUNK;
+  const double* p = g.part + (long long)ch * g.e.max_chunks;
   double v = 0;
   for (int c = 0; c < chunks; ++c) v += p[c];
-  out[st * n_strings + m] = v / g.env[g.sbase[i]];
+  out[st * n_strings + m] = v / g.e.scratch[g.e.sbase[i]];
 }
 
 // tr(M_k^2) = sum_{a, a'} M_k[a][a'] M_k[a'][a] over one 16-row chunk of a (the imaginary parts cancel between (a, a') and its
 // image, so only Re is summed), unnormalised: part[(i, k, chunk)].  M_k is in the T planes, ld = the padded bond.
 __global__ __launch_bounds__(LOC_RED_THREADS) void qk_bond_trace_kernel(const LocArgs g) {
-  __shared__ double red[LOC_RED_THREADS];
+  __shared__ double red[1][LOC_RED_THREADS];
   const int2 t = g.tasks[blockIdx.x];
   const int i = t.x, c = t.y;
   const int n = g.n_sites, n1 = n + 1, k = g.step;
   const long long st = g.states[i];
   const int pk = g.dims[st * n1 + k];
   const long long P = g.pmax[i], P2 = P * P;
-  const double* const Mre = g.scratch + g.sbase[i] + 2 * P2;
+  const double* const Mre = g.scratch + g.sbase[i] + at_T() * P2;
   const double* const Mim = Mre + 2 * P2;
-  double acc = 0;
+  double acc[1] = {};
   const int cnt = LOC_CHUNK * pk;
   for (int e = threadIdx.x; e < cnt; e += LOC_RED_THREADS) {
     const int a = c * LOC_CHUNK + e / pk, ap = e % pk;
     const long long q = (long long)a * pk + ap, qt = (long long)ap * pk + a;
-    acc += Mre[q] * Mre[qt] - Mim[q] * Mim[qt];
+    acc[0] += Mre[q] * Mre[qt] - Mim[q] * Mim[qt];
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int h = LOC_RED_THREADS / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) g.part[((long long)i * n + k) * g.max_chunks + c] = red[0];
+  tree_sum(red, acc);
+  if (threadIdx.x == 0) g.part[((long long)i * n + k) * g.max_chunks + c] = red[0][0];
 }
 
 // Purities of a state batch: the chunk sums of each (state, bond) in a fixed order, divided by L_n[0][0]^2.
@@ -903,99 +673,14 @@ __global__ __launch_bounds__(256) void qk_bond_purities_kernel(const LocArgs g, 
   out[st * (n - 1) + k - 1] = v / (nrm * nrm);
 }
 
-// ---- the environment pass, shared by qk_pauli_strings_host and the bond entry points -----------------------------------------
-// Per state batch: the reversed chain and the forward T / W launches of the one-qubit sweep, then L_{k+1} from W by the sum the rho
-// kernel makes (so L_n[0][0] is that sweep's norm bit for bit); every R_k (k = 1 .. n) and every L_k (k = 0 .. n-1) is kept.
-struct EnvSizes {
-  std::vector<int32_t> pad;     // padded bonds [n_states][n_sites + 1]
-  std::vector<int> pmax;        // P of each state
-  std::vector<long long> need;  // environment doubles of each state: the sweep's planes, R_1 .. R_n, L_0 .. L_{n-1}
-  int max_chunks = 0;
-};
-void env_sizes(const qk_mps_set* set, EnvSizes& z) {
-  const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
-  const int32_t* tru = set->dims_true.data();
-  z.pad.resize((size_t)ns * n1), z.pmax.resize(ns), z.need.resize(ns);
-  for (int s = 0; s < ns; ++s) {
-    int p = 16;
-    long long esum = 0;
-    for (int k = 0; k <= n; ++k) {
-      const int d = z.pad[(size_t)s * n1 + k] = pad16h(tru[(size_t)s * n1 + k]);
-      p = std::max(p, d);
-      esum += (k >= 1 ? 2ll * d * d : 0) + (k < n ? 2ll * d * d : 0);
-    }
-    z.pmax[s] = p;
-    z.need[s] = (long long)LOC_RMUL * p * p + esum;
-  }
-  z.max_chunks = set->max_pad / LOC_CHUNK;
-}
-// the launches of the environment pass, in stream order: the reversed chain as in local_sweep, then per site forward T / W and L_{k+1}
-std::vector<std::pair<int, int>> env_plan(const int n) {
-  std::vector<std::pair<int, int>> plan;  // (kind, step)
-  for (int j = 0; j < n - 1; ++j) plan.push_back({LOC_REV_T, j}), plan.push_back({LOC_REV_X, j});
-  for (int k = 0; k < n; ++k) plan.push_back({LOC_FWD_T, k}), plan.push_back({LOC_FWD_W, k}), plan.push_back({STR_LNEXT, k});
-  return plan;
-}
-struct EnvBatch {
-  int s0 = 0, nb = 0;
-  long long tot = 0;  // environment doubles of the batch
-  std::vector<int32_t> h_states, h_pmax;
-  std::vector<int64_t> h_sbase, h_roff, h_loff;
-  std::vector<int2> tasks;
-  std::vector<long long> first;
+// ---- the driver of a state batch, shared by every entry point -------------------------------------------------------------------
+struct EnvBatch : EnvTables {
   std::vector<char> stage;  // host image of the tables: alive until the stream has taken it (the caller synchronises per batch)
-  size_t b_states = 0, b_pmax = 0, b_sbase = 0, b_roff = 0, b_tasks = 0, b_part = 0, b_tab = 0, b_env = 0;
   LocArgs g{};
-  char* base = nullptr;  // the batch's device buffer: [tables | tasks | partial sums | environments | `extra` bytes of the caller]
-  size_t used() const { return b_tab + b_part + b_env; }
+  char* base = nullptr;  // the batch's device buffer
 };
-inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-// host tables and task lists of the states [s0, s0 + nb) for `plan` (the environment pass, then what the caller appended)
-void env_tables(const qk_mps_set* set, const EnvSizes& z, const std::vector<std::pair<int, int>>& plan, const int s0, const int nb, const long long part_per_state, EnvBatch& eb) {
-  const int n = set->n_sites, n1 = n + 1;
-  eb.s0 = s0, eb.nb = nb, eb.tot = 0;
-  eb.h_states.resize(nb), eb.h_pmax.resize(nb), eb.h_sbase.resize(nb), eb.h_roff.resize((size_t)nb * n1), eb.h_loff.resize((size_t)nb * n1);
-  for (int i = 0; i < nb; ++i) {
-    const int s = s0 + i;
-    eb.h_states[i] = s, eb.h_pmax[i] = z.pmax[s], eb.h_sbase[i] = eb.tot;
-    long long ro = 0;
-    for (int k = 0; k <= n; ++k) {
-      eb.h_roff[(size_t)i * n1 + k] = ro;
-      if (k >= 1) ro += 2ll * z.pad[(size_t)s * n1 + k] * z.pad[(size_t)s * n1 + k];
-    }
-    for (int k = 0; k <= n; ++k) {  // the L_k behind the R_k
-      eb.h_loff[(size_t)i * n1 + k] = ro;
-      ro += 2ll * z.pad[(size_t)s * n1 + k] * z.pad[(size_t)s * n1 + k];
-    }
-    eb.tot += z.need[s];
-  }
-  eb.tasks.clear(), eb.first.clear();
-  for (const auto& [kind, step] : plan) {
-    eb.first.push_back((long long)eb.tasks.size());
-    for (int i = 0; i < nb; ++i) {
-      const int* p = &z.pad[(size_t)(s0 + i) * n1];
-      const int o = n - 1 - step, k = step;
-      int nbk = 0;
-      switch (kind) {
-        case LOC_REV_T: nbk = (int)blocks64(p[o + 1], 2ll * p[o]); break;
-        case LOC_REV_X: nbk = (int)blocks64(p[o], p[o]); break;
-        case LOC_FWD_T: nbk = (int)blocks64(p[k], 2ll * p[k + 1]); break;
-        case LOC_FWD_W: nbk = (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1])); break;
-        case LOC_BOND_M: nbk = (int)blocks64(p[k], p[k]); break;
-        case LOC_BOND_TR: nbk = p[k] / LOC_CHUNK; break;
-        default: nbk = p[k + 1] / LOC_CHUNK; break;  // STR_LNEXT
-      }
-      for (int b = 0; b < nbk; ++b) eb.tasks.push_back(int2{i, b});
-    }
-  }
-  eb.first.push_back((long long)eb.tasks.size());
-  eb.b_states = al256(nb * sizeof(int32_t)), eb.b_pmax = al256(nb * sizeof(int32_t)), eb.b_sbase = al256(nb * sizeof(int64_t));
-  eb.b_roff = al256(eb.h_roff.size() * sizeof(int64_t)), eb.b_tasks = al256(eb.tasks.size() * sizeof(int2));
-  eb.b_part = al256((size_t)nb * part_per_state * sizeof(double));
-  eb.b_tab = eb.b_states + eb.b_pmax + eb.b_sbase + 2 * eb.b_roff + eb.b_tasks, eb.b_env = al256((size_t)eb.tot * sizeof(double));
-}
-// upload the tables and enqueue the launches of `plan` on the context's stream; eb.g describes the batch afterwards
-int env_run(qk_ctx* c, const qk_mps_set* set, const char* what, double* rev, const EnvSizes& z, const std::vector<std::pair<int, int>>& plan, EnvBatch& eb, const size_t extra) {
+// upload the tables, then enqueue reverse, init and the launches of `plan` on the context's stream; eb.g describes the batch afterwards
+int env_run(qk_ctx* c, const qk_mps_set* set, const char* what, double* rev, const EnvSizes& z, const Plan& plan, EnvBatch& eb, const size_t extra) {
   const int n = set->n_sites, nb = eb.nb;
   HIP_TRY_AS(what, c->local_scratch.ensure(eb.used() + extra));
   char* base = eb.base = c->local_scratch.get<char>();
@@ -1019,34 +704,96 @@ int env_run(qk_ctx* c, const qk_mps_set* set, const char* what, double* rev, con
   g.pmax = reinterpret_cast<const int32_t*>(put(eb.h_pmax.data(), nb * sizeof(int32_t), eb.b_pmax));
   g.sbase = reinterpret_cast<const int64_t*>(put(eb.h_sbase.data(), nb * sizeof(int64_t), eb.b_sbase));
   g.roff = reinterpret_cast<const int64_t*>(put(eb.h_roff.data(), eb.h_roff.size() * sizeof(int64_t), eb.b_roff));
-  g.loff = reinterpret_cast<const int64_t*>(put(eb.h_loff.data(), eb.h_loff.size() * sizeof(int64_t), eb.b_roff));
+  if (z.keep_l) g.loff = reinterpret_cast<const int64_t*>(put(eb.h_loff.data(), eb.h_loff.size() * sizeof(int64_t), eb.b_roff));
   const int2* d_tasks = reinterpret_cast<const int2*>(put(eb.tasks.data(), eb.tasks.size() * sizeof(int2), eb.b_tasks));
   g.part = reinterpret_cast<double*>(base + eb.b_tab);
+  if (z.n_pairs) g.part2 = g.part + (size_t)nb * n * z.max_chunks * 4;  // behind the one-qubit partial sums
   g.scratch = reinterpret_cast<double*>(base + eb.b_tab + eb.b_part);
-  g.rmul = LOC_RMUL;
-  g.max_dist = 1;
+  g.rmul = z.rmul;
+  g.max_dist = z.max_dist;
+  g.n_pairs = z.n_pairs;
   g.n_sites = n;
   g.max_chunks = z.max_chunks;
   HIP_TRY_AS(what, hipMemcpyAsync(base, stage.data(), eb.b_tab, hipMemcpyHostToDevice, c->stream));
   qk_local_reverse_kernel<<<dim3(nb, n), dim3(256), 0, c->stream>>>(g, rev);
   qk_local_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, nb);
-  qk_str_init_kernel<<<dim3(nb), dim3(256), 0, c->stream>>>(g, g.loff);
   HIP_TRY_AS(what, hipGetLastError());
   for (size_t li = 0; li < plan.size(); ++li) {
     const int kind = plan[li].first;
     g.tasks = d_tasks + eb.first[li];
     g.step = plan[li].second;
-    const long long grid = eb.first[li + 1] - eb.first[li];
-    if (grid <= 0) continue;
-    if (kind == LOC_REV_X || kind == LOC_FWD_W) qk_local_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
-    else if (kind >= 0) qk_local_gemm_kernel<false><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(g, kind);
-    else if (kind == LOC_BOND_TR) qk_bond_trace_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g);
-    else qk_str_lnext_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(g, g.loff);
+    if (eb.first[li + 1] <= eb.first[li]) continue;
+    const dim3 grid((unsigned)(eb.first[li + 1] - eb.first[li])), red(LOC_RED_THREADS);
+    if (kind >= 0 && conj_b(kind)) qk_local_gemm_kernel<true><<<grid, dim3(512), 0, c->stream>>>(g, kind);
+    else if (kind >= 0) qk_local_gemm_kernel<false><<<grid, dim3(512), 0, c->stream>>>(g, kind);
+    else if (kind == LOC_RHO) qk_local_rho_kernel<<<grid, red, 0, c->stream>>>(g);
+    else if (kind == LOC_PAIR_RHO) qk_local_pair_rho_kernel<false><<<grid, red, 0, c->stream>>>(g);
+    else if (kind == LOC_DIST_RHO) qk_local_pair_rho_kernel<true><<<grid, red, 0, c->stream>>>(g);
+    else if (kind == LOC_ADMIT) qk_local_admit_kernel<<<grid, red, 0, c->stream>>>(g);
+    else if (kind == LOC_BOND_TR) qk_bond_trace_kernel<<<grid, red, 0, c->stream>>>(g);
+    else qk_str_lnext_kernel<<<grid, red, 0, c->stream>>>(g);
   }
   HIP_TRY_AS(what, hipGetLastError());
   return QK_OK;
 }
+// doubles of a quarter of the device memory that is free, counting the context's own scratch: the memory bound of a state batch
+int quarter_of_free(qk_ctx* c, const char* what, long long& budget) {
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
+  budget = (long long)((free_b + c->local_scratch.bytes) / 4 / sizeof(double));
+  return QK_OK;
+}
 
+// The local sweep of a set.  out1 = Bloch vectors [n_states][n_sites][3] (may be NULL when out2 is given), norms (may be NULL);
+// out2 = Pauli correlators of the pairs up to distance max_dist [n_states][n_pairs][4][4] (NULL: the one-qubit sweep alone).
+int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* range, double* out1, double* norms, double* out2, const int max_dist) {
+  const bool pair = out2 != nullptr;
+  if (!c || !set || (!out1 && !out2)) return qk_fail(QK_EINVAL, "%s: null argument", what);
+  if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: the set belongs to another context", what);
+  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: complex64 sets are not supported; local Paulis need an fp64 set", what);
+  const int ns = set->n_states, n = set->n_sites;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: empty set", what);
+  if (pair && n < 2) return qk_fail(QK_EINVAL, "%s: pairs of neighbouring qubits need n_sites >= 2 (got %d)", what, n);
+  if (pair && (max_dist < 1 || max_dist > n - 1)) return qk_fail(QK_EINVAL, "%s: max_dist must be in 1 .. n_sites - 1 = %d (got %d)", what, n - 1, max_dist);
+  QkRangeGuard range_(range);
+  const int D = pair ? max_dist : 1;
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  EnvSizes z;
+  env_sizes(set->dims_true.data(), ns, n, set->max_pad, rmul(pair, D), false, z);  // the window and its intermediates count in need[s]
+  z.max_dist = D, z.n_pairs = pair ? n_pairs(D, n) : 0;
+  const int np = z.n_pairs;
+  const long long part_per_state = (long long)n * z.max_chunks * 4 + (long long)np * z.max_chunks * LOC_PAIR_VALS;
+  // memory bound of the per-state scratch: a quarter of what is free once the reversed image and the outputs exist
+  QkDevBuf rev, dout, dnorm, dout2;
+  HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
+  HIP_TRY_AS(what, dout.alloc((size_t)ns * n * 3 * sizeof(double)));
+  HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
+  if (pair) HIP_TRY_AS(what, dout2.alloc((size_t)ns * np * 16 * sizeof(double)));
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  const std::vector<int> bstart = batch_cut(z.need, part_per_state, budget);  // scratch and rho partial sums of a state
+  const Plan plan = local_plan(n, pair, D);
+  EnvBatch eb;
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+    env_tables(z, plan, s0, nb, part_per_state, eb);
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, 0)) return rc;
+    const long long nf = (long long)nb * n;
+    qk_local_features_kernel<<<dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream>>>(eb.g, nb, dout.get<double>(), dnorm.get<double>());
+    if (pair) qk_local_pair_features_kernel<<<dim3((unsigned)(((long long)nb * np + 255) / 256)), dim3(256), 0, c->stream>>>(eb.g, nb, dout2.get<double>());
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
+  }
+  if (out1) HIP_TRY_AS(what, hipMemcpy(out1, dout.get(), (size_t)ns * n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (norms) HIP_TRY_AS(what, hipMemcpy(norms, dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+  if (pair) HIP_TRY_AS(what, hipMemcpy(out2, dout2.get(), (size_t)ns * np * 16 * sizeof(double), hipMemcpyDeviceToHost));
+  return QK_OK;
+}
+
+// Pauli strings.  Per state batch the environment pass -- the reversed chain and the forward T / W launches of the one-qubit sweep,
+// then L_{k+1} from W by the sum the rho kernel makes (so L_n[0][0] is that sweep's norm bit for bit), every R_k (k = 1 .. n) and
+// every L_k (k = 0 .. n-1) kept -- then its chains in chain batches (qk_local_plan.h: list_chains, chain_cut, chain_lists).
 int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, const uint8_t* strings, double* out, double* norms) {
   static const char* what = "qk_pauli_strings_host";
   if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
@@ -1056,16 +803,11 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
   if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
   if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; Pauli strings need an fp64 set", what);
   if (n_strings < 1) return qk_fail(QK_EINVAL, "%s: n_strings must be >= 1 (got %d)", what, n_strings);
-  const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
+  const int ns = set->n_states, n = set->n_sites;
   if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
-  std::vector<int32_t> supp((size_t)2 * n_strings, -1);  // a, b of each string; -1: all identity
-  for (int m = 0; m < n_strings; ++m)
-    for (int k = 0; k < n; ++k) {
-      const int code = strings[(size_t)m * n + k];
-      if (code > 3) return qk_fail(QK_EINVAL, "%s: strings[%d][%d] = %d is not a Pauli code (0..3 = I, X, Y, Z)", what, m, k, code);
-      if (code && supp[2 * m] < 0) supp[2 * m] = k;
-      if (code) supp[2 * m + 1] = k;
-    }
+  std::vector<int32_t> supp;  // a, b of each string; -1: all identity
+  if (const long long bad = string_supports(strings, n_strings, n, supp); bad >= 0)
+    return qk_fail(QK_EINVAL, "%s: strings[%d][%d] = %d is not a Pauli code (0..3 = I, X, Y, Z)", what, (int)(bad / n), (int)(bad % n), strings[bad]);
   long long cap = 0;  // chains per batch; 0: the memory rule alone
   if (const char* v = std::getenv("QK_STRINGS_BATCH")) {
     cap = std::atoll(v);
@@ -1075,21 +817,9 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   EnvSizes z;
-  env_sizes(set, z);
-  const std::vector<int32_t>& pad = z.pad;
-  const std::vector<int>& pmax = z.pmax;
-  const std::vector<long long>& need = z.need;
+  env_sizes(set->dims_true.data(), ns, n, set->max_pad, LOC_RMUL, true, z);
   const int max_chunks = z.max_chunks;
-  // tasks of the chain (state s, string m): per site of [a, b] the blocks of the two GEMMs and the Pauli's chunks, then the closing chunks
-  auto chain_tasks = [&](const int s, const int m) {
-    const int* p = &pad[(size_t)s * n1];
-    long long nt = p[supp[2 * m + 1] + 1] / LOC_CHUNK;
-    for (int k = supp[2 * m]; k <= supp[2 * m + 1]; ++k)
-      nt += blocks64(p[k], 2ll * p[k + 1]) + blocks64(p[k + 1], p[k + 1]) + (strings[(size_t)m * n + k] ? p[k] / LOC_CHUNK : 0);
-    return nt;
-  };
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_str = al((size_t)n_strings * n), b_supp = al(supp.size() * sizeof(int32_t));
+  const size_t b_str = al256((size_t)n_strings * n), b_supp = al256(supp.size() * sizeof(int32_t));
   QkDevBuf rev, dout, dnorm, dstr;
   HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
   HIP_TRY_AS(what, dout.alloc((size_t)ns * n_strings * sizeof(double)));
@@ -1097,53 +827,30 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
   HIP_TRY_AS(what, dstr.alloc(b_str + b_supp));
   HIP_TRY_AS(what, hipMemcpy(dstr.get<char>(), strings, (size_t)n_strings * n, hipMemcpyHostToDevice));
   HIP_TRY_AS(what, hipMemcpy(dstr.get<char>() + b_str, supp.data(), supp.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
   // memory bound of a state batch (environments and the slots of its live chains): a quarter of what is free; the environments
   // of a batch take at most half of that (at least one state per batch), the chains of a batch the rest (at least one chain)
-  const long long budget = (long long)((free_b + c->local_scratch.bytes) / 4 / sizeof(double));
-  std::vector<int> bstart{0};
-  for (long long acc = 0, s = 0; s < ns; ++s) {
-    if (acc > 0 && acc + need[s] > budget / 2) bstart.push_back((int)s), acc = 0;
-    acc += need[s];
-  }
-  bstart.push_back(ns);
-  const std::vector<std::pair<int, int>> plan = env_plan(n);
-  static const int chain_kinds[4] = {STR_T, STR_PAULI, STR_X, STR_CLOSE};  // the launches of a site of the chain pass, in stream order
-  std::vector<int2> tasks;
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  const std::vector<int> bstart = batch_cut(z.need, 0, budget / 2);
+  const Plan plan = env_plan(n);
+  std::vector<Task2> tasks;
   std::vector<long long> first;
   EnvBatch eb;
   for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
     const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
-    env_tables(set, z, plan, s0, nb, 0, eb);
-    const long long tot = eb.tot;
-    // the chains of the state batch, state-major in string order, cut into chain batches: consecutive chains while their slots,
-    // partial sums and tasks fit what the environments leave, and at most QK_STRINGS_BATCH of them
-    std::vector<int32_t> h_cent, h_cstr;
-    std::vector<long long> cweight, ctasks;
-    for (int i = 0; i < nb; ++i)
-      for (int m = 0; m < n_strings; ++m)
-        if (supp[2 * m] >= 0) {
-          h_cent.push_back(i), h_cstr.push_back(m);
-          ctasks.push_back(chain_tasks(s0 + i, m));
-          cweight.push_back(6ll * pmax[s0 + i] * pmax[s0 + i] + max_chunks + ctasks.back() + 2);
-        }
-    const size_t nch = h_cent.size();
-    const long long room = budget - tot;
-    std::vector<size_t> cstart{0};
-    long long acc = 0;
-    for (size_t ch = 0; ch < nch; ++ch) {
-      if (acc > 0 && (acc + cweight[ch] > room || (cap > 0 && (long long)(ch - cstart.back()) >= cap))) cstart.push_back(ch), acc = 0;
-      acc += cweight[ch];
-    }
-    cstart.push_back(nch);
+    env_tables(z, plan, s0, nb, 0, eb);
+    // the chains of the state batch, cut into chain batches: consecutive chains while their slots, partial sums and tasks fit
+    // what the environments leave, and at most QK_STRINGS_BATCH of them
+    const Chains ch = list_chains(z, s0, nb, n_strings, strings, supp);
+    const std::vector<size_t> cstart = chain_cut(ch.weight, budget - eb.tot, cap);
     struct ChainBytes { size_t cent, cstr, cbase, tasks, part, slots; size_t tab() const { return cent + cstr + cbase + tasks; } };
+    auto slot = [&](const size_t e) { return (long long)chain_size() * z.pmax[s0 + ch.cent[e]] * z.pmax[s0 + ch.cent[e]]; };
     auto chain_bytes = [&](const size_t c0, const size_t c1) {
       long long nt = 0, sl = 0;
-      for (size_t ch = c0; ch < c1; ++ch) nt += ctasks[ch], sl += 6ll * pmax[s0 + h_cent[ch]] * pmax[s0 + h_cent[ch]];
+      for (size_t e = c0; e < c1; ++e) nt += ch.ntasks[e], sl += slot(e);
       const size_t nc = c1 - c0;
-      return ChainBytes{al(nc * sizeof(int32_t)), al(nc * sizeof(int32_t)), al(nc * sizeof(int64_t)), al((size_t)nt * sizeof(int2)),
-                        al(nc * max_chunks * sizeof(double)), (size_t)sl * sizeof(double)};
+      return ChainBytes{al256(nc * sizeof(int32_t)), al256(nc * sizeof(int32_t)), al256(nc * sizeof(int64_t)), al256((size_t)nt * sizeof(int2)),
+                        al256(nc * max_chunks * sizeof(double)), (size_t)sl * sizeof(double)};
     };
     size_t b_chain = 0;
     for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
@@ -1152,20 +859,13 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
     }
     // one device buffer for the state batch: [tables | tasks | environments] then the chain batch's [tables | tasks | partials | slots]
     if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, b_chain)) return rc;
-    const LocArgs& g = eb.g;
-    const int64_t* const d_loff = g.loff;
-    char* const base = eb.base;
-    const size_t b_tab = eb.b_tab, b_env = eb.b_env;
-    qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(g, nb, dnorm.get<double>());
+    qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(eb.g, nb, dnorm.get<double>());
     HIP_TRY_AS(what, hipGetLastError());
     StrArgs q{};
-    q.data = g.data, q.dims = g.dims, q.tru = g.tru, q.offs = g.offs;
-    q.states = g.states, q.pmax = g.pmax, q.sbase = g.sbase, q.roff = g.roff, q.loff = d_loff, q.env = g.scratch;
+    q.e = eb.g;
     q.strings = dstr.get<uint8_t>();
     q.supp = reinterpret_cast<const int32_t*>(dstr.get<char>() + b_str);
-    q.n_sites = n;
-    q.max_chunks = max_chunks;
-    char* const cbase0 = base + b_tab + b_env;
+    char* const cbase0 = eb.base + eb.used();
     std::vector<char> cstage;
     std::vector<int64_t> h_cbase;
     for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
@@ -1174,30 +874,11 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
       const ChainBytes cbz = chain_bytes(c0, c0 + nc);
       h_cbase.resize(nc);
       long long sl = 0;
-      for (size_t e = 0; e < nc; ++e) h_cbase[e] = sl, sl += 6ll * pmax[s0 + h_cent[c0 + e]] * pmax[s0 + h_cent[c0 + e]];
-      // task lists of every launch of the chain batch: per site the live chains' T blocks, Pauli chunks, X blocks and closing chunks
-      tasks.clear(), first.clear();
-      for (int k = 0; k < n; ++k)
-        for (const int kind : chain_kinds) {
-          first.push_back((long long)tasks.size());
-          for (size_t e = 0; e < nc; ++e) {
-            const int m = h_cstr[c0 + e];
-            if (k < supp[2 * m] || k > supp[2 * m + 1]) continue;
-            const int* p = &pad[(size_t)(s0 + h_cent[c0 + e]) * n1];
-            int nbk = 0;
-            switch (kind) {
-              case STR_T: nbk = (int)blocks64(p[k], 2ll * p[k + 1]); break;
-              case STR_X: nbk = (int)blocks64(p[k + 1], p[k + 1]); break;
-              case STR_PAULI: nbk = strings[(size_t)m * n + k] ? p[k] / LOC_CHUNK : 0; break;
-              default: nbk = (k == supp[2 * m + 1]) ? p[k + 1] / LOC_CHUNK : 0; break;  // STR_CLOSE
-            }
-            for (int b = 0; b < nbk; ++b) tasks.push_back(int2{(int)e, b});
-          }
-        }
-      first.push_back((long long)tasks.size());
+      for (size_t e = 0; e < nc; ++e) h_cbase[e] = sl, sl += slot(c0 + e);
+      chain_lists(z, s0, ch, c0, nc, strings, supp, tasks, first);
       cstage.resize(cbz.tab());
-      std::memcpy(cstage.data(), h_cent.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + cbz.cent, h_cstr.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data(), ch.cent.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + cbz.cent, ch.cstr.data() + c0, nc * sizeof(int32_t));
       std::memcpy(cstage.data() + cbz.cent + cbz.cstr, h_cbase.data(), nc * sizeof(int64_t));
       std::memcpy(cstage.data() + cbz.cent + cbz.cstr + cbz.cbase, tasks.data(), tasks.size() * sizeof(int2));
       q.cent = reinterpret_cast<const int32_t*>(cbase0);
@@ -1208,15 +889,15 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
       q.slots = reinterpret_cast<double*>(cbase0 + cbz.tab() + cbz.part);
       HIP_TRY_AS(what, hipMemcpyAsync(cbase0, cstage.data(), cbz.tab(), hipMemcpyHostToDevice, c->stream));
       for (size_t li = 0; li + 1 < first.size(); ++li) {
-        const int kind = chain_kinds[li % 4];
+        const int kind = CHAIN_KINDS[li % 4];
         q.tasks = d_ctasks + first[li];
         q.step = (int)(li / 4);
-        const long long grid = first[li + 1] - first[li];
-        if (grid <= 0) continue;
-        if (kind == STR_T) qk_str_gemm_kernel<false><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(q);
-        else if (kind == STR_X) qk_str_gemm_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, c->stream>>>(q);
-        else if (kind == STR_PAULI) qk_str_pauli_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
-        else qk_str_close_kernel<<<dim3((unsigned)grid), dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+        if (first[li + 1] <= first[li]) continue;
+        const dim3 grid((unsigned)(first[li + 1] - first[li]));
+        if (kind == STR_T) qk_str_gemm_kernel<false><<<grid, dim3(512), 0, c->stream>>>(q);
+        else if (kind == STR_X) qk_str_gemm_kernel<true><<<grid, dim3(512), 0, c->stream>>>(q);
+        else if (kind == STR_PAULI) qk_str_pauli_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+        else qk_str_close_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
       }
       qk_str_values_kernel<<<dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)nc, n_strings, dout.get<double>());
       HIP_TRY_AS(what, hipGetLastError());
@@ -1233,7 +914,7 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
 }
 
 // ---- bond purities and entanglement spectra (qk_bond_purities_host, qk_bond_spectra_host) --------------------------------------
-// Bond k (k = 1 .. n-1) cuts the chain between sites k-1 and k.  With the kept environments of the pass above,
+// Bond k (k = 1 .. n-1) cuts the chain between sites k-1 and k.  With the kept environments of the environment pass,
 //     N_k = R_k L_k^T / <psi|psi>     (chi_k x chi_k, tr N_k = 1; its eigenvalues are the Schmidt weights of the cut)
 //     purity_k = tr(N_k^2)
 // L_k and R_k are Hermitian in the sweep's X[ket][bra] orientation, so the product the ring GEMM makes from them as they lie,
@@ -1255,9 +936,9 @@ int bond_call(qk_ctx* c, const qk_mps_set* set, const char* what, const char* ra
   QkRangeGuard range_(range);
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
-  EnvSizes z;
-  env_sizes(set, z);
   const int32_t* tru = set->dims_true.data();
+  EnvSizes z;
+  env_sizes(tru, ns, n, set->max_pad, LOC_RMUL, true, z);
   const int m = spectra ? max_values : 1;
   const size_t n_out = (size_t)ns * (n - 1) * m;
   QkDevBuf rev, dout, dnorm, derr;
@@ -1266,27 +947,22 @@ int bond_call(qk_ctx* c, const qk_mps_set* set, const char* what, const char* ra
   HIP_TRY_AS(what, dout.alloc(std::max<size_t>(1, n_out) * sizeof(double)));
   HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
   HIP_TRY_AS(what, hipMemsetAsync(dout.get(), 0, std::max<size_t>(1, n_out) * sizeof(double), c->stream));
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
   // memory bound of a state batch: a quarter of what is free (at least one state per batch); with the spectra the environments take
   // at most half of it and the factorisation workspaces the rest (at least one workgroup)
-  const long long budget = (long long)((free_b + c->local_scratch.bytes) / 4 / sizeof(double));
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
   const long long part_per_state = spectra ? 0 : (long long)n * z.max_chunks;
-  std::vector<int> bstart{0};
-  for (long long acc = 0, s = 0; s < ns; ++s) {
-    const long long w = z.need[s] + part_per_state;
-    if (acc > 0 && acc + w > (spectra ? budget / 2 : budget)) bstart.push_back((int)s), acc = 0;
-    acc += w;
+  const std::vector<int> bstart = batch_cut(z.need, part_per_state, spectra ? budget / 2 : budget);
+  Plan plan = env_plan(n);
+  if (!spectra) {
+    const Plan tail = bond_tail(n);
+    plan.insert(plan.end(), tail.begin(), tail.end());
   }
-  bstart.push_back(ns);
-  std::vector<std::pair<int, int>> plan = env_plan(n);
-  if (!spectra)
-    for (int k = 1; k < n; ++k) plan.push_back({LOC_BOND_M, k}), plan.push_back({LOC_BOND_TR, k});
   EnvBatch eb;
   std::vector<int2> stasks;
   for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
     const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
-    env_tables(set, z, plan, s0, nb, part_per_state, eb);
+    env_tables(z, plan, s0, nb, part_per_state, eb);
     size_t extra = 0;
     int grid = 0, qmax = 0;
     size_t per_wg = 0;
@@ -1316,7 +992,7 @@ int bond_call(qk_ctx* c, const qk_mps_set* set, const char* what, const char* ra
       a.env = g.scratch, a.dims = g.dims, a.tru = g.tru, a.states = g.states, a.pmax = g.pmax, a.sbase = g.sbase, a.roff = g.roff, a.loff = g.loff;
       a.tasks = reinterpret_cast<const int2*>(x0), a.n_tasks = (int)stasks.size();
       a.work = x0 + al256(stasks.size() * sizeof(int2)), a.work_bytes = (long long)per_wg, a.qmax = qmax;
-      a.out = dout.get<double>(), a.n_sites = n, a.max_values = m, a.rmul = LOC_RMUL, a.error = derr.get<int>();
+      a.out = dout.get<double>(), a.n_sites = n, a.max_values = m, a.rmul = z.rmul, a.error = derr.get<int>();
       if (const int rc = qk_bond_spectra_launch(c, a, grid, what)) return rc;  // synchronises and reads the error word
     }
     HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
@@ -1383,6 +1059,6 @@ extern "C" int qk_projected_pair_gram_dist_host(qk_ctx* c, int32_t n_sites, int3
   static const char* what = "qk_projected_pair_gram_dist_host";
   if (n_sites >= 2 && (max_dist < 1 || max_dist > n_sites - 1))
     return qk_fail(QK_EINVAL, "%s: max_dist must be in 1 .. n_sites - 1 = %d (got %d)", what, n_sites - 1, max_dist);
-  const int n_pairs = n_sites >= 2 ? max_dist * n_sites - max_dist * (max_dist + 1) / 2 : 0;
-  return projected_gram(c, what, "qk:projected_pair_gram_dist", n_sites, 2, 16 * n_pairs, 0.25, nx, tx, ny, ty, g, out, ld);
+  const int np = n_sites >= 2 ? n_pairs(max_dist, n_sites) : 0;
+  return projected_gram(c, what, "qk:projected_pair_gram_dist", n_sites, 2, 16 * np, 0.25, nx, tx, ny, ty, g, out, ld);
 }

@@ -1,0 +1,301 @@
+// qk_local_plan.h -- the host-side plan of the local sweeps (qk_local.hip): the launch kinds, the scratch layout, the pair index, the
+// sizes and the cut into state batches, the tables and task lists of a batch, the plans of the entry points and the chain side of the
+// Pauli strings.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
+// -fsanitize=address,undefined); the few functions the kernels also call are QK_HD.
+#pragma once
+#include "qk_plan.h"
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+namespace qkl {
+
+constexpr int LOC_CHUNK = 16;  // rows per reduction task
+
+// Every launch kind of qk_local.hip.  Kinds >= 0 are GEMM launches (64 x 64 output blocks), the others elementwise or reductions
+// in 16-row chunks.  LOC_*: tasks (batch entry, block), qk_local_gemm_kernel; STR_*: tasks (chain, block), qk_str_gemm_kernel.
+enum LocKind : int {
+  LOC_REV_T = 0,   // reversed chain: T = Lr^T Ar_j              (Lr_j = R_{o+1}, o = n-1-j)
+  LOC_REV_X = 1,   // reversed chain: R_o = T^T conj(Ar_j)
+  LOC_FWD_T = 2,   // T_k = L_k^T A_k
+  LOC_FWD_W = 3,   // W_{k,s} = T_k[(., s)]^T conj(A_k), both s in one launch
+  LOC_PAIR_T = 4,  // pair sweep, site o = k+1 of the reversed image: T' = R_{o+1}^T Ar_o
+  LOC_PAIR_V = 5,  // pair sweep: V_{o,t} = T'[(., t)]^T conj(Ar_o), both t in one launch
+  LOC_DIST_T = 6,  // distant pairs, site k: T''_(o,s,s') = E_{o->k}[s][s']^T A_k for every live origin o, in one launch
+  LOC_DIST_X = 7,  // distant pairs: E_{o->k+1}[s][s'] = T''_(o,s,s')^T conj(A_k) over K = (a, u), back into the origin's slot
+  LOC_BOND_M = 8,  // bond purities: M_k = L_k^T R_k (= N_k^H) of bond k = step, from the kept environments into the T planes
+  STR_T = 9,       // T[a][(s, b')] = sum_b E_k[b][a] A_k[b][(s, b')] of every live chain (the LOC_DIST_T shape); E_a is read from the kept L_a
+  STR_X = 10,      // E_{k+1}[b'][a'] = sum_{(a,u)} T[(a, u)][b'] conj(A_k[(a, u)][a']) over K = 2 chi_k (the LOC_DIST_X shape)
+  LOC_RHO = -1,       // qk_local_rho_kernel
+  LOC_PAIR_RHO = -2,  // qk_local_pair_rho_kernel<false>
+  LOC_DIST_RHO = -3,  // qk_local_pair_rho_kernel<true>: rho_{o,k+1} of every live origin from its window slot
+  LOC_ADMIT = -4,     // qk_local_admit_kernel: W_k into the window
+  LOC_BOND_TR = -5,   // qk_bond_trace_kernel: tr(M_k^2) of bond k = step in 16-row chunks
+  STR_LNEXT = -6,     // qk_str_lnext_kernel (environment pass): L_{k+1} = W_0[.][(0, .)] + W_1[.][(1, .)], kept
+  STR_PAULI = -7,     // qk_str_pauli_kernel: T[a][(s ^ f, b')] <- i^e(s) T[a][(s, b')] of the chains whose code at site k is not I
+  STR_CLOSE = -8,     // qk_str_close_kernel: sum E_{b+1} R_{b+1} of the chains whose support ends at site k
+};
+QK_HD constexpr bool conj_b(const int kind) { return kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V || kind == LOC_DIST_X || kind == STR_X; }
+
+// ---- the scratch layout ---------------------------------------------------------------------------------------------------------
+// Per-state scratch (doubles, every matrix as a re plane then an im plane), P = the state's largest padded bond, offsets in units
+// of P^2:
+//   L [P x P] at at_L() = 0 | T [P x 2P] at at_T() = 2 | W_s [P x 2P] at at_W(s) = 6 + 4s | kept environments from rmul on
+// The pair sweep has T' at at_Tp() = 14 and V_t at at_V(t) = 18 + 4t before the kept environments.  Pairs up to distance D add the
+// window -- D - 1 slots of 8, origin o in window_slot(o, D) = 26 + 8 (o mod (D - 1)), holding (W_0 | W_1) of its origin carried to
+// the current bond -- and the 4 (D - 1) intermediates T'' of 4 at window_tmp(w, D) = 26 + 8 (D - 1) + 4w, w = 4 (k - 1 - o) + 2s + s'.
+// The kept environments start at rmul(pair, D) = 14 (one-qubit sweep and the environment pass), 26 + 24 (D - 1) (pair sweeps):
+// R_k (k = 1 .. n) at rmul P^2 + roff[k], pad_k^2 per plane, and -- where the L_k are kept -- L_k (k = 0 .. n-1) at rmul P^2 + loff[k].
+// A chain of the Pauli strings has a slot of chain_size() = 6: E [P x P] at chain_E() = 0 (ld = the current padded bond) | T [P x 2P]
+// at chain_T() = 2.
+QK_HD constexpr int at_L() { return 0; }
+QK_HD constexpr int at_T() { return 2; }
+QK_HD constexpr int at_W(const int s) { return 6 + 4 * s; }
+QK_HD constexpr int at_Tp() { return 14; }
+QK_HD constexpr int at_V(const int t) { return 18 + 4 * t; }
+QK_HD constexpr int window_slot(const int o, const int D) { return 26 + 8 * (o % (D - 1)); }
+QK_HD constexpr int window_tmp(const int w, const int D) { return 26 + 8 * (D - 1) + 4 * w; }
+QK_HD constexpr int rmul(const bool pair, const int D) { return pair ? 26 + 24 * (D - 1) : 14; }
+constexpr int LOC_RMUL = rmul(false, 1);  // the environment pass
+QK_HD constexpr int chain_E() { return 0; }
+QK_HD constexpr int chain_T() { return 2; }
+QK_HD constexpr int chain_size() { return 6; }
+
+// ---- the pairs (k, k + d), d = 1 .. D, listed distance-major -----------------------------------------------------------------------
+QK_HD constexpr long long pair_index(const int d, const int k, const int n) { return (long long)(d - 1) * n - (d - 1) * d / 2 + k; }
+QK_HD constexpr int n_pairs(const int D, const int n) { return D * n - D * (D + 1) / 2; }
+// the second qubit k + d of the pair with this index: the distance-d block has n - d pairs, second qubits d .. n-1
+QK_HD constexpr int pair_second(const int index, const int n) {
+  int second = index + 1;
+  for (int d = 1; second > n - 1; ++d) second -= n - d - 1;
+  return second;
+}
+
+// ---- sizes and state batches ----------------------------------------------------------------------------------------------------
+inline long long blocks64(const long long m, const long long n) { return ((m + 63) / 64) * ((n + 63) / 64); }
+inline size_t al256(const size_t b) { return (b + 255) / 256 * 256; }
+
+struct EnvSizes {
+  int n_states = 0, n_sites = 0;
+  int rmul = LOC_RMUL;          // start of the kept environments
+  bool keep_l = false;          // the L_k are kept behind the R_k
+  int max_dist = 1, n_pairs = 0;  // the pair sweeps (set by local_sweep)
+  std::vector<int32_t> pad;     // padded bonds [n_states][n_sites + 1]
+  std::vector<int> pmax;        // P of each state
+  std::vector<long long> need;  // scratch doubles of each state: rmul P^2, R_1 .. R_n and, if kept, L_0 .. L_{n-1}
+  int max_chunks = 0;
+};
+inline void env_sizes(const int32_t* tru, const int ns, const int n, const int max_pad, const int rmul, const bool keep_l, EnvSizes& z) {
+  const int n1 = n + 1;
+  z.n_states = ns, z.n_sites = n, z.rmul = rmul, z.keep_l = keep_l;
+  z.pad.resize((size_t)ns * n1), z.pmax.resize(ns), z.need.resize(ns);
+  for (int s = 0; s < ns; ++s) {
+    int p = 16;
+    long long esum = 0;
+    for (int k = 0; k <= n; ++k) {
+      const int d = z.pad[(size_t)s * n1 + k] = qk_pad16(tru[(size_t)s * n1 + k]);
+      p = std::max(p, d);
+      esum += (k >= 1 ? 2ll * d * d : 0) + (keep_l && k < n ? 2ll * d * d : 0);
+    }
+    z.pmax[s] = p;
+    z.need[s] = (long long)rmul * p * p + esum;
+  }
+  z.max_chunks = max_pad / LOC_CHUNK;
+}
+
+// The cut into batches: consecutive states while their weights (weight[s] + each) fit the budget, at least one state per batch.
+// Returns the first state of every batch, then the number of states.
+inline std::vector<int> batch_cut(const std::vector<long long>& weight, const long long each, const long long budget) {
+  std::vector<int> bstart{0};
+  long long acc = 0;
+  for (size_t s = 0; s < weight.size(); ++s) {
+    const long long w = weight[s] + each;
+    if (acc > 0 && acc + w > budget) bstart.push_back((int)s), acc = 0;
+    acc += w;
+  }
+  bstart.push_back((int)weight.size());
+  return bstart;
+}
+
+// ---- plans: the launches of a batch as (kind, step), in stream order ------------------------------------------------------------------
+using Plan = std::vector<std::pair<int, int>>;
+// the reversed chain, steps j = 0 .. n-2: R_{n-1} .. R_1 (R_0 is not needed)
+inline void plan_reverse(const int n, Plan& plan) {
+  for (int j = 0; j < n - 1; ++j) plan.push_back({LOC_REV_T, j}), plan.push_back({LOC_REV_X, j});
+}
+// the environment pass: the reversed chain, then per site forward T / W and L_{k+1}
+inline Plan env_plan(const int n) {
+  Plan plan;
+  plan_reverse(n, plan);
+  for (int k = 0; k < n; ++k) plan.push_back({LOC_FWD_T, k}), plan.push_back({LOC_FWD_W, k}), plan.push_back({STR_LNEXT, k});
+  return plan;
+}
+// the local sweep: the reversed chain, then per site forward T / W, the pair sweep's T' / V of site k+1, rho (which also makes
+// L_{k+1}) and the pair rho; with D > 1 then the live origins k-D+1 .. k-1 through site k, their rho_{o,k+1}, and W_k into the
+// window for the sites after k+1
+inline Plan local_plan(const int n, const bool pair, const int D) {
+  Plan plan;
+  plan_reverse(n, plan);
+  for (int k = 0; k < n; ++k) {
+    plan.push_back({LOC_FWD_T, k}), plan.push_back({LOC_FWD_W, k});
+    if (pair && k + 1 < n) plan.push_back({LOC_PAIR_T, k}), plan.push_back({LOC_PAIR_V, k});
+    plan.push_back({LOC_RHO, k});
+    if (pair && k + 1 < n) plan.push_back({LOC_PAIR_RHO, k});
+    if (D > 1 && k >= 1 && k + 1 < n) plan.push_back({LOC_DIST_T, k}), plan.push_back({LOC_DIST_X, k}), plan.push_back({LOC_DIST_RHO, k});
+    if (D > 1 && k + 2 < n) plan.push_back({LOC_ADMIT, k});
+  }
+  return plan;
+}
+// the bond purities, after the environment pass: per bond k = 1 .. n-1 the product M_k and its trace
+inline Plan bond_tail(const int n) {
+  Plan plan;
+  for (int k = 1; k < n; ++k) plan.push_back({LOC_BOND_M, k}), plan.push_back({LOC_BOND_TR, k});
+  return plan;
+}
+
+// ---- tasks and tables of a batch ----------------------------------------------------------------------------------------------------
+// The blocks of one state (p = its padded bonds [n + 1]) in a launch: 64 x 64 output blocks of a GEMM kind, 16-row chunks otherwise.
+// step = reversed-chain step j (LOC_REV_*: site o = n-1-j), site k (forward, STR_*; LOC_PAIR_*: the pair (k, k+1)) or bond k
+// (LOC_BOND_*).  The STR_* counts are those of a chain that takes part in the launch (chain_lists decides which do).
+inline int task_count(const int kind, const int step, const int32_t* p, const int n, const int D) {
+  const int o = n - 1 - step, k = step;
+  const int live = std::min(k, D - 1);  // origins in the window at site k
+  switch (kind) {
+    case LOC_REV_T: return (int)blocks64(p[o + 1], 2ll * p[o]);
+    case LOC_REV_X: return (int)blocks64(p[o], p[o]);
+    case LOC_FWD_T: case STR_T: return (int)blocks64(p[k], 2ll * p[k + 1]);
+    case LOC_FWD_W: case LOC_PAIR_V: return (int)(2 * blocks64(p[k + 1], 2ll * p[k + 1]));
+    case LOC_PAIR_T: return (int)blocks64(p[k + 2], 2ll * p[k + 1]);
+    case LOC_DIST_T: return (int)(4 * live * blocks64(p[k], 2ll * p[k + 1]));
+    case LOC_DIST_X: return (int)(4 * live * blocks64(p[k + 1], p[k + 1]));
+    case LOC_DIST_RHO: return live * (p[k + 1] / LOC_CHUNK);
+    case LOC_BOND_M: return (int)blocks64(p[k], p[k]);
+    case STR_X: return (int)blocks64(p[k + 1], p[k + 1]);
+    case LOC_BOND_TR: case STR_PAULI: return p[k] / LOC_CHUNK;
+    default: return p[k + 1] / LOC_CHUNK;  // LOC_RHO, LOC_PAIR_RHO, LOC_ADMIT, STR_LNEXT, STR_CLOSE
+  }
+}
+
+struct Task2 {  // int2 of the device: (batch entry or chain, block)
+  int x, y;
+};
+struct EnvTables {
+  int s0 = 0, nb = 0;
+  long long tot = 0;  // scratch doubles of the batch
+  std::vector<int32_t> h_states, h_pmax;   // batch entry -> state of the set, P
+  std::vector<int64_t> h_sbase;            // batch entry -> first double of its scratch
+  std::vector<int64_t> h_roff, h_loff;     // [batch][n_sites + 1]: R_k, L_k behind rmul P^2 (h_loff empty unless the L_k are kept)
+  std::vector<Task2> tasks;                // of every launch of the plan, in launch order
+  std::vector<long long> first;            // per launch: first task; then the number of tasks
+  // the batch's device buffer: [tables | tasks | partial sums | scratch | `extra` bytes of the caller]
+  size_t b_states = 0, b_pmax = 0, b_sbase = 0, b_roff = 0, b_tasks = 0, b_part = 0, b_tab = 0, b_env = 0;
+  size_t used() const { return b_tab + b_part + b_env; }
+};
+// host tables and task lists of the states [s0, s0 + nb) for `plan`
+inline void env_tables(const EnvSizes& z, const Plan& plan, const int s0, const int nb, const long long part_per_state, EnvTables& eb) {
+  const int n = z.n_sites, n1 = n + 1;
+  eb.s0 = s0, eb.nb = nb, eb.tot = 0;
+  eb.h_states.resize(nb), eb.h_pmax.resize(nb), eb.h_sbase.resize(nb), eb.h_roff.resize((size_t)nb * n1), eb.h_loff.resize(z.keep_l ? (size_t)nb * n1 : 0);
+  for (int i = 0; i < nb; ++i) {
+    const int s = s0 + i;
+    const int32_t* p = &z.pad[(size_t)s * n1];
+    eb.h_states[i] = s, eb.h_pmax[i] = z.pmax[s], eb.h_sbase[i] = eb.tot;
+    long long ro = 0;
+    for (int k = 0; k <= n; ++k) {
+      eb.h_roff[(size_t)i * n1 + k] = ro;
+      if (k >= 1) ro += 2ll * p[k] * p[k];
+    }
+    for (int k = 0; z.keep_l && k <= n; ++k) {  // the L_k behind the R_k
+      eb.h_loff[(size_t)i * n1 + k] = ro;
+      ro += 2ll * p[k] * p[k];
+    }
+    eb.tot += z.need[s];
+  }
+  eb.tasks.clear(), eb.first.clear();
+  for (const auto& [kind, step] : plan) {
+    eb.first.push_back((long long)eb.tasks.size());
+    for (int i = 0; i < nb; ++i) {
+      const int nbk = task_count(kind, step, &z.pad[(size_t)(s0 + i) * n1], n, z.max_dist);
+      for (int b = 0; b < nbk; ++b) eb.tasks.push_back(Task2{i, b});
+    }
+  }
+  eb.first.push_back((long long)eb.tasks.size());
+  eb.b_states = al256(nb * sizeof(int32_t)), eb.b_pmax = al256(nb * sizeof(int32_t)), eb.b_sbase = al256(nb * sizeof(int64_t));
+  eb.b_roff = al256(eb.h_roff.size() * sizeof(int64_t)), eb.b_tasks = al256(eb.tasks.size() * sizeof(Task2));
+  eb.b_part = al256((size_t)nb * part_per_state * sizeof(double));
+  eb.b_tab = eb.b_states + eb.b_pmax + eb.b_sbase + (z.keep_l ? 2 : 1) * eb.b_roff + eb.b_tasks, eb.b_env = al256((size_t)eb.tot * sizeof(double));
+}
+
+// ---- the chains of the Pauli strings --------------------------------------------------------------------------------------------------
+// A string is codes[0 .. n-1], 0..3 = I, X, Y, Z; its support [a, b] = its first and last non-identity sites.  A chain is one
+// (state, string) with a non-identity site.
+// supp[2m], supp[2m + 1] = a, b of string m (-1, -1: all identity).  Returns -1, or the index m n + k of the first code above 3.
+inline long long string_supports(const uint8_t* strings, const int n_strings, const int n, std::vector<int32_t>& supp) {
+  supp.assign((size_t)2 * n_strings, -1);
+  for (int m = 0; m < n_strings; ++m)
+    for (int k = 0; k < n; ++k) {
+      const int code = strings[(size_t)m * n + k];
+      if (code > 3) return (long long)m * n + k;
+      if (code && supp[2 * m] < 0) supp[2 * m] = k;
+      if (code) supp[2 * m + 1] = k;
+    }
+  return -1;
+}
+constexpr int CHAIN_KINDS[4] = {STR_T, STR_PAULI, STR_X, STR_CLOSE};  // the launches of a site of the chain pass, in stream order
+// the blocks of a chain (p = its state's padded bonds, codes = its string, [a, b] its support) in the launch `kind` of site k
+inline int chain_task_count(const int kind, const int k, const int32_t* p, const uint8_t* codes, const int a, const int b, const int n) {
+  if (k < a || k > b || (kind == STR_PAULI && !codes[k]) || (kind == STR_CLOSE && k != b)) return 0;
+  return task_count(kind, k, p, n, 1);
+}
+struct Chains {  // the chains of a state batch, state-major in string order
+  std::vector<int32_t> cent, cstr;       // chain -> batch entry, string
+  std::vector<long long> ntasks, weight;  // its tasks over all launches; its doubles: slot, partial sums, tasks and table entries
+};
+inline Chains list_chains(const EnvSizes& z, const int s0, const int nb, const int n_strings, const uint8_t* strings, const std::vector<int32_t>& supp) {
+  const int n = z.n_sites;
+  Chains c;
+  for (int i = 0; i < nb; ++i)
+    for (int m = 0; m < n_strings; ++m)
+      if (supp[2 * m] >= 0) {
+        long long nt = 0;
+        for (int k = supp[2 * m]; k <= supp[2 * m + 1]; ++k)
+          for (const int kind : CHAIN_KINDS) nt += chain_task_count(kind, k, &z.pad[(size_t)(s0 + i) * (n + 1)], strings + (size_t)m * n, supp[2 * m], supp[2 * m + 1], n);
+        c.cent.push_back(i), c.cstr.push_back(m), c.ntasks.push_back(nt);
+        c.weight.push_back((long long)chain_size() * z.pmax[s0 + i] * z.pmax[s0 + i] + z.max_chunks + nt + 2);
+      }
+  return c;
+}
+// The cut into chain batches: consecutive chains while their weights fit `room`, and at most `cap` of them (cap 0: the room
+// alone); at least one chain per batch.  Returns the first chain of every batch, then the number of chains.
+inline std::vector<size_t> chain_cut(const std::vector<long long>& weight, const long long room, const long long cap) {
+  std::vector<size_t> cstart{0};
+  long long acc = 0;
+  for (size_t ch = 0; ch < weight.size(); ++ch) {
+    if (acc > 0 && (acc + weight[ch] > room || (cap > 0 && (long long)(ch - cstart.back()) >= cap))) cstart.push_back(ch), acc = 0;
+    acc += weight[ch];
+  }
+  cstart.push_back(weight.size());
+  return cstart;
+}
+// Task lists (chain of the batch, block) of the chains [c0, c0 + nc): launch 4k + j is CHAIN_KINDS[j] at site k -- the live chains'
+// T blocks, the Pauli chunks of those with a code at k, the X blocks, the closing chunks of those that end at k.
+inline void chain_lists(const EnvSizes& z, const int s0, const Chains& c, const size_t c0, const size_t nc, const uint8_t* strings, const std::vector<int32_t>& supp,
+                        std::vector<Task2>& tasks, std::vector<long long>& first) {
+  const int n = z.n_sites;
+  tasks.clear(), first.clear();
+  for (int k = 0; k < n; ++k)
+    for (const int kind : CHAIN_KINDS) {
+      first.push_back((long long)tasks.size());
+      for (size_t e = 0; e < nc; ++e) {
+        const int m = c.cstr[c0 + e];
+        const int nbk = chain_task_count(kind, k, &z.pad[(size_t)(s0 + c.cent[c0 + e]) * (n + 1)], strings + (size_t)m * n, supp[2 * m], supp[2 * m + 1], n);
+        for (int b = 0; b < nbk; ++b) tasks.push_back(Task2{(int)e, b});
+      }
+    }
+  first.push_back((long long)tasks.size());
+}
+
+}  // namespace qkl
