@@ -408,6 +408,47 @@ int qk_bond_purities_host(qk_ctx* ctx, const qk_mps_set* set, double* out /* [n_
 int qk_bond_spectra_host(qk_ctx* ctx, const qk_mps_set* set, int32_t max_values, double* out /* [n_states][n_sites - 1][max_values] */,
                          double* norms /* [n_states], may be NULL */);
 
+/* ---- block kernels: reduced-state overlaps of the first or last w qubits --------------------------------------------------------
+ * The projected kernel of Huang et al. for a subsystem A that is a block at either end of the chain.  Site k is qubit k, states
+ * need not be normalised, environments are in the sweep's X[ket][bra] orientation, rows are Y and columns X, yset = NULL means Y is X.
+ *     side = 0 (left):   A = qubits 0 .. w-1,       cut at bond w
+ *     side = 1 (right):  A = qubits n-w .. n-1,     cut at bond m = n - w            width w = 1 .. n
+ *     rho_A(psi) = tr_{not A} |psi><psi| / <psi|psi>
+ *     O_w[j][i]  = tr(rho_A(x_i) rho_A(y_j))         real, 0 <= O <= sqrt(S_w(x_i) S_w(y_j)) <= 1
+ *     S_w(psi)   = tr(rho_A(psi)^2)                  the self overlap = the purity of the cut
+ * Left, at bond w, with E_0 = 1 and E_{k+1}[b'][a'] = sum_s sum_{b,a} E_k[b][a] Ay_k[b][s][b'] conj(Ax_k[a][s][a']) (the mixed left
+ * environment the fidelity sweep carries) and the self right environments Rx_w, Ry_w:
+ *     O_w <x|x> <y|y> = sum_{a,a',b,b'} Rx_w[a][a'] Ry_w[b][b'] E_w[b][a'] conj(E_w[b'][a])
+ * Right, at bond m, with F_n = 1, F_k[b][a] = sum_s sum_{b',a'} Ay_k[b][s][b'] F_{k+1}[b'][a'] conj(Ax_k[a][s][a']) and the self left
+ * environments Lx_m, Ly_m:
+ *     O_w <x|x> <y|y> = sum_{a,a',b,b'} Lx_m[a][a'] Ly_m[b][b'] F_m[b][a'] conj(F_m[b'][a])
+ * (the left form on the reversed images the local sweeps make).  Identities: O_n = |<x|y>|^2 / (<x|x> <y|y>) for both sides; left
+ * O_1 = (1 + F_x[0] . F_y[0]) / 2 with the Bloch vectors of qk_local_paulis_host (right: qubit n-1); S_w = the purity of
+ * qk_bond_purities_host at bond w (left) or n - w (right) for w < n, S_n = 1; O_w(x, y) = O_w(y, x).
+ * Kernels from O are host arithmetic: "overlap" K = O_w; "normalized" K = O_w[j][i] / sqrt(S_w(x_i) S_w(y_j)); "rbf"
+ * K = exp(-g (S_w(x_i) + S_w(y_j) - 2 O_w[j][i])) = exp(-g ||rho_A(x_i) - rho_A(y_j)||_F^2), g > 0.
+ *
+ * qk_block_values_host: values_host[wi][p] = O_w of width widths[wi] for pair p of the plan's list, (x state, y state) as
+ * qk_plan_pairs lists them.  One pair chain along the chain gives every width at once: per step two GEMM launches for all pair
+ * chains of a batch (tasks (chain, 64 x 64 block)), per chosen width three more (V = Ry^T E, W = E^T conj(V), and the reduction
+ * Re sum Rx conj(W) in 16-row chunks added in a fixed order); the chain stops at the largest width.  The self environments come
+ * from the environment pass of qk_pauli_strings_host, run once per set; those of the chosen cuts are kept for every state of both
+ * sets in one compact buffer.  qk_block_self_host: out[wi][s] = S_w of state s, the pairs (s, s) through the same route, so the
+ * diagonal of a symmetric call and S_w are the same bits; norms, when given, are the bits qk_local_paulis_host returns.
+ * A (pair, width) value is the same bits whatever the other pairs of the plan, the other widths asked for, the cut into batches
+ * and the run: no atomics, no grid barrier, no spin wait.  QK_BLOCK_BATCH=k (read per call) caps the pair chains of a batch.
+ * Both calls are synchronous and leave the Gram statistics (qk_get_stats) alone.  Device scratch: the kept environments and the
+ * reversed images for the length of the call; per state batch the environments, per pair batch a slot of 6 P^2 doubles per chain
+ * (P = the pair's largest padded bond), each bounded by a quarter of the free memory and released by qk_ctx_trim.
+ * QK_EINVAL: a null argument (yset and norms may be NULL); a set of another context; a complex64 set; two sets whose numbers of
+ * sites differ; a plan whose pair indices exceed the sets; side not 0 or 1; n_widths < 1; widths not strictly increasing or
+ * outside 1 .. n_sites.  QK_EDEVICE: the kept environments do not fit a quarter of the free memory (the message names the bytes). */
+int qk_block_values_host(qk_ctx* ctx, const qk_mps_set* xset, const qk_mps_set* yset /* NULL: Y is X */, const qk_plan* plan,
+                         int32_t side /* 0 left, 1 right */, int32_t n_widths, const int32_t* widths /* strictly increasing, 1..n_sites */,
+                         double* values_host /* [n_widths][num_pairs]: O_w of the plan's pairs as listed */);
+int qk_block_self_host(qk_ctx* ctx, const qk_mps_set* set, int32_t side, int32_t n_widths, const int32_t* widths,
+                       double* out /* [n_widths][n_states]: S_w */, double* norms /* may be NULL; the bits of qk_local_paulis_host */);
+
 /* ---- compressing a set: one canonical truncation sweep per state -------------------------------------------------------------
  * qk_mps_set_compress: *out = a new fp64 set of the same context that owns its memory, every state of src truncated ONCE on its
  * final tensors; src is left untouched.  One workgroup per state (workgroup b takes states b, b + grid, ...), two passes over the

@@ -4,7 +4,9 @@
 // qk_projected_pair_gram_host and their forms for pairs up to a chosen distance, qk_local_pair_paulis_dist_host and
 // qk_projected_pair_gram_dist_host, and the general form, expectation values of Pauli strings and the Gram of any feature columns,
 // qk_pauli_strings_host and qk_feature_gram_host, and the entanglement across every bond of a state from the same environments,
-// qk_bond_purities_host and qk_bond_spectra_host (definitions above bond_call below) (include/qkgram.h).
+// qk_bond_purities_host and qk_bond_spectra_host (definitions above bond_call below), and the block kernels -- reduced-state
+// overlaps of the first or last w qubits for every pair of two sets -- qk_block_values_host and qk_block_self_host (definitions
+// above BlkSet below) (include/qkgram.h).
 //
 // Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
 // normalised):
@@ -1006,7 +1008,336 @@ int bond_call(qk_ctx* c, const qk_mps_set* set, const char* what, const char* ra
   return QK_OK;
 }
 
+// ---- block kernels: reduced-state overlaps of the first or last w qubits (qk_block_values_host, qk_block_self_host) -------------
+// A = the first w qubits (side 0, cut at bond w) or the last w (side 1, cut at bond m = n - w).  For a pair (x_i, y_j), with the
+// mixed left environment E_w[b][a] = <l^x_a | l^y_b> of the fidelity sweep (X[ket][bra]) and the self right environments of the
+// environment pass,
+//     tr(rho_A(x) rho_A(y)) <x|x> <y|y> = sum_{a,a',b,b'} Rx_w[a][a'] Ry_w[b][b'] E_w[b][a'] conj(E_w[b'][a])
+// and the mirror image for side 1: the same chain on the reversed images (LocArgs.rev) against the self LEFT environments L_m.
+// Per call: the environment pass of each set in state batches (env_plan; every L_k and R_k of a batch), from which the
+// environments of the chosen cuts are copied into one compact buffer (qk_local_plan.h: blk_kept_offsets) and the norms taken; then
+// the pairs in pair batches.  A pair chain has the string chain's slot (E | T).  Per step ONE BLK_T and ONE BLK_X launch for every
+// chain of the batch (the two GEMMs of the ring sweep, A_k of the y state then conj(A_k) of the x state); behind the step of a
+// chosen width three more: V = Ry^T E and W = E^T conj(V) into the T region (dead between two steps) and the reduction
+// Re sum Rx[a][a'] conj(W[a][a']) in 16-row chunks.  A chain starts from the unit matrix at the head of the kept buffer.  The chunk
+// sums are added in a fixed order, nothing of a chain depends on another chain, no atomics, no grid barrier, no spin wait: a
+// (pair, width) value is the same bits whatever the other pairs, the other widths, the cut into batches (QK_BLOCK_BATCH caps the
+// chains of one) and the run.
+struct BlkSet {
+  const double* data;     // the set's planes (side 0) or their reversed image (side 1)
+  const int32_t* dims;    // padded bonds [n_states][n_sites + 1]
+  const int32_t* tru;     // true bonds
+  const int64_t* offs;    // re-plane offsets [n_states][n_sites]
+  const int64_t* koff;    // [n_states][n_widths]: the kept environment of (state, cut) in `kept`
+  const double* norms;    // [n_states]: <psi|psi>
+};
+struct BlkArgs {
+  BlkSet x, y;
+  const int32_t* pairs;   // chain -> (x state, y state)
+  const int32_t* cpm;     // chain -> P = max(P_x, P_y)
+  const int64_t* cbase;   // chain -> first double of its slot
+  const int32_t* widths;  // [n_widths]
+  const int2* tasks;      // this launch: (chain, block)
+  const double* kept;     // the unit matrix, then the environments of the chosen cuts
+  double* slots;
+  double* part;           // partial sums [chain][n_widths][max chunks]
+  int n_sites, side, n_widths, max_chunks;
+  int step;               // step j of the chain
+  int cut;                // index of the width (BLK_V, BLK_W, BLK_RED)
+};
+
+// One 64 x 64 output block of one pair chain's GEMM.  CONJB = false: BLK_T, BLK_V; true: BLK_X, BLK_W.
+template <bool CONJB>
+__global__ __launch_bounds__(512) void qk_blk_gemm_kernel(const BlkArgs g, const int kind) {
+  __shared__ __attribute__((aligned(16))) double lds[LOC_LDS_DOUBLES];
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = __builtin_amdgcn_readfirstlane(t.x);
+  const int blk = __builtin_amdgcn_readfirstlane(t.y);
+  const long long xi = __builtin_amdgcn_readfirstlane(g.pairs[2 * ch]), yj = __builtin_amdgcn_readfirstlane(g.pairs[2 * ch + 1]);
+  const int n = g.n_sites, n1 = n + 1, j = g.step;
+  const int site = blk_site(g.side, j, n), in = blk_in(g.side, j, n), out = blk_out(g.side, j, n);
+  const int xl = __builtin_amdgcn_readfirstlane(g.x.dims[xi * n1 + in]), xr = __builtin_amdgcn_readfirstlane(g.x.dims[xi * n1 + out]);
+  const int yl = __builtin_amdgcn_readfirstlane(g.y.dims[yj * n1 + in]), yr = __builtin_amdgcn_readfirstlane(g.y.dims[yj * n1 + out]);
+  const long long P = __builtin_amdgcn_readfirstlane(g.cpm[ch]), P2 = P * P;
+  double* const E = g.slots + uni64(g.cbase[ch]);
+  double* const T = E + chain_T() * P2;
+  const double *Are, *Aim, *Bre, *Bim;
+  double *Cre, *Cim;
+  int lda, ldb, ldc, M, N, K;
+  if (kind == BLK_T) {
+    if (j == 0) {  // the chain starts here: E = 1
+      Are = g.kept, Aim = g.kept + 256;
+    } else {
+      Are = E, Aim = E + P2;
+    }
+    Bre = g.y.data + uni64(g.y.offs[yj * n + site]);
+    Bim = Bre + (long long)yl * 2 * yr;
+    Cre = T, Cim = T + 2 * P2;
+    lda = xl, ldb = 2 * yr, ldc = 2 * yr, M = xl, N = 2 * yr, K = __builtin_amdgcn_readfirstlane(g.y.tru[yj * n1 + in]);
+  } else if (kind == BLK_X) {
+    Are = T, Aim = T + 2 * P2;
+    Bre = g.x.data + uni64(g.x.offs[xi * n + site]);
+    Bim = Bre + (long long)xl * 2 * xr;
+    Cre = E, Cim = E + P2;
+    lda = yr, ldb = xr, ldc = xr, M = yr, N = xr, K = 2 * __builtin_amdgcn_readfirstlane(g.x.tru[xi * n1 + in]);
+  } else {
+    double* const V = E + blk_V() * P2;
+    const int yt = __builtin_amdgcn_readfirstlane(g.y.tru[yj * n1 + out]);
+    if (kind == BLK_V) {  // V[b'][a'] = sum_b Ry[b][b'] E[b][a']
+      Are = g.kept + uni64(g.y.koff[yj * g.n_widths + g.cut]);
+      Aim = Are + (long long)yr * yr;
+      Bre = E, Bim = E + P2;
+      Cre = V, Cim = V + P2;
+      lda = yr, ldb = xr, ldc = xr, M = yr, N = xr, K = yt;
+    } else {  // W[a][a'] = sum_b' E[b'][a] conj(V[b'][a'])
+      double* const W = E + blk_W() * P2;
+      Are = E, Aim = E + P2;
+      Bre = V, Bim = V + P2;
+      Cre = W, Cim = W + P2;
+      lda = xr, ldb = xr, ldc = xr, M = xr, N = xr, K = yt;
+    }
+  }
+  const int npm = (M + 63) / 64;
+  const int m0 = 64 * (blk % npm), n0 = 64 * (blk / npm);
+  zgemm_ring3<CONJB, LOC_KTL, LOC_NSLOT, true, 8, 64, double, 9>(Cre + (long long)m0 * ldc + n0, Cim + (long long)m0 * ldc + n0, ldc, Are + m0, Aim + m0, lda,
+                                                                  Bre + n0, Bim + n0, ldb, min(64, M - m0), min(64, N - n0), K, lds);
+}
+
+// Re sum_{a, a'} Rx[a][a'] conj(W[a][a']) over one 16-row chunk of a, unnormalised: part[(chain, cut, chunk)].
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_blk_reduce_kernel(const BlkArgs g) {
+  __shared__ double red[1][LOC_RED_THREADS];
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = t.x, c = t.y;
+  const long long xi = g.pairs[2 * ch];
+  const int n = g.n_sites;
+  const int r = g.x.dims[xi * (n + 1) + blk_out(g.side, g.step, n)];
+  const long long P = g.cpm[ch], P2 = P * P, rpl = (long long)r * r;
+  const double* const W = g.slots + g.cbase[ch] + blk_W() * P2;
+  const double* const R = g.kept + g.x.koff[xi * g.n_widths + g.cut];
+  double acc[1] = {};
+  const int rows = LOC_CHUNK * r;
+  for (int e = threadIdx.x; e < rows; e += LOC_RED_THREADS) {
+    const long long q = (long long)c * rows + e;
+    acc[0] += R[q] * W[q] + R[q + rpl] * W[q + P2];
+  }
+  tree_sum(red, acc);
+  if (threadIdx.x == 0) g.part[((long long)ch * g.n_widths + g.cut) * g.max_chunks + c] = red[0][0];
+}
+
+// The values of a pair batch: the chunk sums of each (chain, cut) in a fixed order, divided by the two norms.
+__global__ __launch_bounds__(256) void qk_blk_values_kernel(const BlkArgs g, const int nc, const long long pair0, const long long n_pairs, double* out) {
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (long long)nc * g.n_widths) return;
+  const int ch = (int)(id / g.n_widths), ci = (int)(id % g.n_widths);
+  const long long xi = g.pairs[2 * ch], yj = g.pairs[2 * ch + 1];
+  const int n = g.n_sites;
+  const int chunks = g.x.dims[xi * (n + 1) + blk_cut_bond(g.side, g.widths[ci], n)] / LOC_CHUNK;
+  const double* p = g.part + ((long long)ch * g.n_widths + ci) * g.max_chunks;
+  double v = 0;
+  for (int c = 0; c < chunks; ++c) v += p[c];
+  out[ci * n_pairs + pair0 + ch] = v / (g.x.norms[xi] * g.y.norms[yj]);
+}
+
+// The environments of the chosen cuts of a state batch, out of the environment pass into the kept buffer: R of the cut's bond
+// (side 0) or L (side 1), both planes.
+__global__ __launch_bounds__(256) void qk_blk_keep_kernel(const LocArgs g, const int side, const int n_widths, const int32_t* widths, const int64_t* koff, double* kept) {
+  const int i = blockIdx.x, ci = blockIdx.y;
+  const int n = g.n_sites, n1 = n + 1;
+  const long long st = g.states[i];
+  const int bond = blk_cut_bond(side, widths[ci], n);
+  const long long d = g.dims[st * n1 + bond], P = g.pmax[i];
+  const double* const src = g.scratch + g.sbase[i] + g.rmul * P * P + (side ? g.loff : g.roff)[(long long)i * n1 + bond];
+  double* const dst = kept + koff[st * n_widths + ci];
+  for (long long e = threadIdx.x; e < 2 * d * d; e += 256) dst[e] = src[e];
+}
+
+// what a set brings to a block call: its environment pass into `kept`, its norms and its reversed image
+struct BlkHostSet {
+  const qk_mps_set* set = nullptr;
+  EnvSizes z;
+  std::vector<int64_t> koff;
+  QkDevBuf rev, dnorm;
+  const int64_t* d_koff = nullptr;
+};
+int blk_env_pass(qk_ctx* c, const char* what, BlkHostSet& h, const int side, const int nw, const int32_t* d_widths, double* kept, const long long budget) {
+  const int n = h.set->n_sites;
+  const std::vector<int> bstart = batch_cut(h.z.need, 0, budget);
+  const Plan plan = env_plan(n);
+  EnvBatch eb;
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+    env_tables(h.z, plan, s0, nb, 0, eb);
+    if (const int rc = env_run(c, h.set, what, h.rev.get<double>(), h.z, plan, eb, 0)) return rc;
+    qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(eb.g, nb, h.dnorm.get<double>());
+    qk_blk_keep_kernel<<<dim3(nb, nw), dim3(256), 0, c->stream>>>(eb.g, side, nw, d_widths, h.d_koff, kept);
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
+  }
+  return QK_OK;
+}
+
+// values_host[n_widths][n_pairs] = O_w of the pairs (x state, y state) as listed; norms_host (may be NULL) = <psi|psi> of the x set
+int block_run(qk_ctx* c, const char* what, const qk_mps_set* xset, const qk_mps_set* yset, const long long n_pairs, const int32_t* pairs, const int side, const int nw,
+              const int32_t* widths, double* values_host, double* norms_host) {
+  const int n = xset->n_sites;
+  long long cap = 0;  // pair chains per batch; 0: the memory rule alone
+  if (const char* v = std::getenv("QK_BLOCK_BATCH")) {
+    cap = std::atoll(v);
+    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_BLOCK_BATCH must be >= 1 (got \"%s\")", what, v);
+  }
+  if (n_pairs == 0) return QK_OK;
+  QkRangeGuard range_("qk:block_values");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  const bool sym = !yset || yset == xset;
+  BlkHostSet hx, hy_;
+  BlkHostSet& hy = sym ? hx : hy_;
+  hx.set = xset, hy.set = sym ? xset : yset;
+  long long kept_doubles = blk_kept_unit();
+  for (BlkHostSet* h : {&hx, &hy_}) {
+    if (h == &hy_ && sym) break;
+    env_sizes(h->set->dims_true.data(), h->set->n_states, n, h->set->max_pad, LOC_RMUL, true, h->z);
+    kept_doubles = blk_kept_offsets(h->z, side, nw, widths, kept_doubles, h->koff);
+    HIP_TRY_AS(what, h->rev.alloc((size_t)h->set->bytes));
+    HIP_TRY_AS(what, h->dnorm.alloc((size_t)h->set->n_states * sizeof(double)));
+  }
+  const int max_chunks = std::max(hx.z.max_chunks, hy.z.max_chunks);
+  // the call's small tables: [widths | koff of x | koff of y]
+  const size_t b_w = al256(nw * sizeof(int32_t)), b_kx = al256(hx.koff.size() * sizeof(int64_t)), b_ky = sym ? 0 : al256(hy.koff.size() * sizeof(int64_t));
+  QkDevBuf dtab, dout, kept;
+  HIP_TRY_AS(what, dtab.alloc(b_w + b_kx + b_ky));
+  HIP_TRY_AS(what, dout.alloc((size_t)nw * n_pairs * sizeof(double)));
+  HIP_TRY_AS(what, hipMemcpy(dtab.get<char>(), widths, nw * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY_AS(what, hipMemcpy(dtab.get<char>() + b_w, hx.koff.data(), hx.koff.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  if (!sym) HIP_TRY_AS(what, hipMemcpy(dtab.get<char>() + b_w + b_kx, hy.koff.data(), hy.koff.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  const int32_t* d_widths = dtab.get<int32_t>();
+  hx.d_koff = reinterpret_cast<const int64_t*>(dtab.get<char>() + b_w);
+  hy.d_koff = sym ? hx.d_koff : reinterpret_cast<const int64_t*>(dtab.get<char>() + b_w + b_kx);
+  // the kept environments of the chosen cuts, for every state of both sets: they must fit a quarter of what is free
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  if (kept_doubles > budget)
+    return qk_fail(QK_EDEVICE, "%s: the environments of the %d chosen cuts need %lld bytes, more than a quarter of the free device memory (%lld bytes)", what, nw,
+                   kept_doubles * (long long)sizeof(double), budget * (long long)sizeof(double));
+  HIP_TRY_AS(what, kept.alloc((size_t)kept_doubles * sizeof(double)));
+  {
+    std::vector<double> unit((size_t)blk_kept_unit(), 0.0);
+    unit[0] = 1.0;
+    HIP_TRY_AS(what, hipMemcpy(kept.get(), unit.data(), unit.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  // memory bound of a state batch and of a pair batch: a quarter of what is free now (at least one state / one chain per batch)
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  if (const int rc = blk_env_pass(c, what, hx, side, nw, d_widths, kept.get<double>(), budget)) return rc;
+  if (!sym)
+    if (const int rc = blk_env_pass(c, what, hy, side, nw, d_widths, kept.get<double>(), budget)) return rc;
+
+  const std::vector<BlkLaunch> plan = blk_plan(nw, widths);
+  const BlkChains chains = list_blk_chains(hx.z, hy.z, n_pairs, pairs, side, plan, nw);
+  const std::vector<size_t> cstart = chain_cut(chains.weight, budget, cap);
+  BlkArgs q{};
+  auto side_of = [&](const BlkHostSet& h) {
+    return BlkSet{side ? h.rev.get<double>() : h.set->d_data.get<double>(), h.set->d_dims.get<int32_t>(), h.set->d_true.get<int32_t>(), h.set->d_offs.get<int64_t>(), h.d_koff,
+                  h.dnorm.get<double>()};
+  };
+  q.x = side_of(hx), q.y = side_of(hy);
+  q.widths = d_widths, q.kept = kept.get<double>();
+  q.n_sites = n, q.side = side, q.n_widths = nw, q.max_chunks = max_chunks;
+  std::vector<Task2> tasks;
+  std::vector<long long> first;
+  std::vector<char> stage;
+  std::vector<int32_t> h_cpm;
+  std::vector<int64_t> h_cbase;
+  for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
+    const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
+    if (nc == 0) continue;
+    h_cpm.resize(nc), h_cbase.resize(nc);
+    long long sl = 0;
+    for (size_t e = 0; e < nc; ++e) {
+      h_cpm[e] = std::max(hx.z.pmax[pairs[2 * (c0 + e)]], hy.z.pmax[pairs[2 * (c0 + e) + 1]]);
+      h_cbase[e] = sl, sl += chains.slot[c0 + e];
+    }
+    blk_lists(hx.z, hy.z, pairs, c0, nc, side, plan, tasks, first);
+    // one device buffer for the pair batch: [pairs | P | slot bases | tasks | partial sums | slots]
+    const size_t b_pairs = al256(2 * nc * sizeof(int32_t)), b_cpm = al256(nc * sizeof(int32_t)), b_cbase = al256(nc * sizeof(int64_t));
+    const size_t b_tasks = al256(tasks.size() * sizeof(int2)), b_tab = b_pairs + b_cpm + b_cbase + b_tasks;
+    const size_t b_part = al256(nc * (size_t)nw * max_chunks * sizeof(double)), b_slots = (size_t)sl * sizeof(double);
+    HIP_TRY_AS(what, c->local_scratch.ensure(b_tab + b_part + b_slots));
+    char* const base = c->local_scratch.get<char>();
+    stage.assign(b_tab, 0);
+    std::memcpy(stage.data(), pairs + 2 * c0, 2 * nc * sizeof(int32_t));
+    std::memcpy(stage.data() + b_pairs, h_cpm.data(), nc * sizeof(int32_t));
+    std::memcpy(stage.data() + b_pairs + b_cpm, h_cbase.data(), nc * sizeof(int64_t));
+    std::memcpy(stage.data() + b_pairs + b_cpm + b_cbase, tasks.data(), tasks.size() * sizeof(int2));
+    q.pairs = reinterpret_cast<const int32_t*>(base);
+    q.cpm = reinterpret_cast<const int32_t*>(base + b_pairs);
+    q.cbase = reinterpret_cast<const int64_t*>(base + b_pairs + b_cpm);
+    const int2* d_tasks = reinterpret_cast<const int2*>(base + b_pairs + b_cpm + b_cbase);
+    q.part = reinterpret_cast<double*>(base + b_tab);
+    q.slots = reinterpret_cast<double*>(base + b_tab + b_part);
+    HIP_TRY_AS(what, hipMemcpyAsync(base, stage.data(), b_tab, hipMemcpyHostToDevice, c->stream));
+    for (size_t li = 0; li < plan.size(); ++li) {
+      const int kind = plan[li].kind;
+      q.tasks = d_tasks + first[li];
+      q.step = plan[li].step, q.cut = plan[li].cut;
+      if (first[li + 1] <= first[li]) continue;
+      const dim3 grid((unsigned)(first[li + 1] - first[li]));
+      if (kind == BLK_RED) qk_blk_reduce_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+      else if (conj_b(kind)) qk_blk_gemm_kernel<true><<<grid, dim3(512), 0, c->stream>>>(q, kind);
+      else qk_blk_gemm_kernel<false><<<grid, dim3(512), 0, c->stream>>>(q, kind);
+    }
+    qk_blk_values_kernel<<<dim3((unsigned)((nc * nw + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)nc, (long long)c0, n_pairs, dout.get<double>());
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
+  }
+  HIP_TRY_AS(what, hipMemcpy(values_host, dout.get(), (size_t)nw * n_pairs * sizeof(double), hipMemcpyDeviceToHost));
+  if (norms_host) HIP_TRY_AS(what, hipMemcpy(norms_host, hx.dnorm.get(), (size_t)xset->n_states * sizeof(double), hipMemcpyDeviceToHost));
+  return QK_OK;
+}
+
+// the checks both entry points share, before anything runs on the device
+int block_check(qk_ctx* c, const char* what, const qk_mps_set* xset, const qk_mps_set* yset, const int side, const int nw, const int32_t* widths) {
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!xset) return qk_fail(QK_EINVAL, "%s: set is null", what);
+  if (!widths) return qk_fail(QK_EINVAL, "%s: widths is null", what);
+  for (const qk_mps_set* s : {xset, yset}) {
+    if (!s) continue;
+    if (s->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
+    if (s->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; block overlaps need an fp64 set", what);
+    if (s->n_sites < 1 || s->n_states < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
+  }
+  if (yset && yset->n_sites != xset->n_sites) return qk_fail(QK_EINVAL, "%s: site counts differ (%d, %d)", what, xset->n_sites, yset->n_sites);
+  if (side != 0 && side != 1) return qk_fail(QK_EINVAL, "%s: side must be 0 (left) or 1 (right) (got %d)", what, side);
+  if (nw < 1) return qk_fail(QK_EINVAL, "%s: n_widths must be >= 1 (got %d)", what, nw);
+  if (const int bad = blk_bad_width(nw, widths, xset->n_sites); bad >= 0)
+    return qk_fail(QK_EINVAL, "%s: widths[%d] = %d: widths must be strictly increasing in 1 .. n_sites = %d", what, bad, widths[bad], xset->n_sites);
+  return QK_OK;
+}
+
 }  // namespace
+
+extern "C" int qk_block_values_host(qk_ctx* c, const qk_mps_set* xset, const qk_mps_set* yset, const qk_plan* plan, int32_t side, int32_t n_widths, const int32_t* widths,
+                                    double* values_host) {
+  static const char* what = "qk_block_values_host";
+  if (!plan) return qk_fail(QK_EINVAL, "%s: plan is null", what);
+  if (!values_host) return qk_fail(QK_EINVAL, "%s: values_host is null", what);
+  if (const int rc = block_check(c, what, xset, yset, side, n_widths, widths)) return rc;
+  const long long np = (long long)plan->pairs.size() / 2;
+  const int nx = xset->n_states, ny = yset ? yset->n_states : nx;
+  for (long long e = 0; e < np; ++e) {
+    const int i = plan->pairs[2 * e], j = plan->pairs[2 * e + 1];
+    if (i < 0 || i >= nx || j < 0 || j >= ny) return qk_fail(QK_EINVAL, "%s: pair %lld of the plan is (%d, %d), the sets hold %d x %d states", what, e, i, j, nx, ny);
+  }
+  return block_run(c, what, xset, yset, np, plan->pairs.data(), side, n_widths, widths, values_host, nullptr);
+}
+
+extern "C" int qk_block_self_host(qk_ctx* c, const qk_mps_set* set, int32_t side, int32_t n_widths, const int32_t* widths, double* out, double* norms) {
+  static const char* what = "qk_block_self_host";
+  if (!out) return qk_fail(QK_EINVAL, "%s: out is null", what);
+  if (const int rc = block_check(c, what, set, nullptr, side, n_widths, widths)) return rc;
+  std::vector<int32_t> pairs((size_t)2 * set->n_states);
+  for (int s = 0; s < set->n_states; ++s) pairs[2 * s] = pairs[2 * s + 1] = s;
+  return block_run(c, what, set, nullptr, set->n_states, pairs.data(), side, n_widths, widths, out, norms);
+}
 
 extern "C" int qk_bond_purities_host(qk_ctx* c, const qk_mps_set* set, double* out, double* norms) {
   return bond_call(c, set, "qk_bond_purities_host", "qk:bond_purities", 0, out, norms);

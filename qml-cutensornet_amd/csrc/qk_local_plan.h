@@ -16,7 +16,8 @@ namespace qkl {
 constexpr int LOC_CHUNK = 16;  // rows per reduction task
 
 // Every launch kind of qk_local.hip.  Kinds >= 0 are GEMM launches (64 x 64 output blocks), the others elementwise or reductions
-// in 16-row chunks.  LOC_*: tasks (batch entry, block), qk_local_gemm_kernel; STR_*: tasks (chain, block), qk_str_gemm_kernel.
+// in 16-row chunks.  LOC_*: tasks (batch entry, block), qk_local_gemm_kernel; STR_*: tasks (chain, block), qk_str_gemm_kernel;
+// BLK_*: tasks (pair chain, block), qk_blk_gemm_kernel.
 enum LocKind : int {
   LOC_REV_T = 0,   // reversed chain: T = Lr^T Ar_j              (Lr_j = R_{o+1}, o = n-1-j)
   LOC_REV_X = 1,   // reversed chain: R_o = T^T conj(Ar_j)
@@ -29,6 +30,10 @@ enum LocKind : int {
   LOC_BOND_M = 8,  // bond purities: M_k = L_k^T R_k (= N_k^H) of bond k = step, from the kept environments into the T planes
   STR_T = 9,       // T[a][(s, b')] = sum_b E_k[b][a] A_k[b][(s, b')] of every live chain (the LOC_DIST_T shape); E_a is read from the kept L_a
   STR_X = 10,      // E_{k+1}[b'][a'] = sum_{(a,u)} T[(a, u)][b'] conj(A_k[(a, u)][a']) over K = 2 chi_k (the LOC_DIST_X shape)
+  BLK_T = 11,      // pair chain (x_i, y_j), step j: T[a][(s, b')] = sum_b E[b][a] Ay[b][(s, b')] (the STR_T shape, A from the y state)
+  BLK_X = 12,      // pair chain: E'[b'][a'] = sum_{(a,u)} T[(a, u)][b'] conj(Ax[(a, u)][a']) (the STR_X shape, A from the x state)
+  BLK_V = 13,      // pair chain at a chosen cut: V = Ry^T E
+  BLK_W = 14,      // pair chain at a chosen cut: W = E^T conj(V)
   LOC_RHO = -1,       // qk_local_rho_kernel
   LOC_PAIR_RHO = -2,  // qk_local_pair_rho_kernel<false>
   LOC_DIST_RHO = -3,  // qk_local_pair_rho_kernel<true>: rho_{o,k+1} of every live origin from its window slot
@@ -37,8 +42,9 @@ enum LocKind : int {
   STR_LNEXT = -6,     // qk_str_lnext_kernel (environment pass): L_{k+1} = W_0[.][(0, .)] + W_1[.][(1, .)], kept
   STR_PAULI = -7,     // qk_str_pauli_kernel: T[a][(s ^ f, b')] <- i^e(s) T[a][(s, b')] of the chains whose code at site k is not I
   STR_CLOSE = -8,     // qk_str_close_kernel: sum E_{b+1} R_{b+1} of the chains whose support ends at site k
+  BLK_RED = -9,       // qk_blk_reduce_kernel: Re sum Rx[a][a'] conj(W[a][a']) of a chosen cut in 16-row chunks
 };
-QK_HD constexpr bool conj_b(const int kind) { return kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V || kind == LOC_DIST_X || kind == STR_X; }
+QK_HD constexpr bool conj_b(const int kind) { return kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V || kind == LOC_DIST_X || kind == STR_X || kind == BLK_X || kind == BLK_W; }
 
 // ---- the scratch layout ---------------------------------------------------------------------------------------------------------
 // Per-state scratch (doubles, every matrix as a re plane then an im plane), P = the state's largest padded bond, offsets in units
@@ -295,6 +301,106 @@ inline void chain_lists(const EnvSizes& z, const int s0, const Chains& c, const 
         for (int b = 0; b < nbk; ++b) tasks.push_back(Task2{(int)e, b});
       }
     }
+  first.push_back((long long)tasks.size());
+}
+
+// ---- the pair chains of the block kernels (qk_block_values_host) ------------------------------------------------------------------
+// side 0 (left): the block is qubits 0 .. w-1; step j takes site j, enters by bond j and leaves by bond j + 1.  side 1 (right): the
+// block is qubits n-w .. n-1; step j takes site n-1-j of the reversed image, enters by bond n - j and leaves by bond n-1-j.  After
+// step j the chain's E is the mixed environment at the bond it left by: the cut of width j + 1.
+QK_HD constexpr int blk_site(const int side, const int j, const int n) { return side ? n - 1 - j : j; }
+QK_HD constexpr int blk_in(const int side, const int j, const int n) { return side ? n - j : j; }
+QK_HD constexpr int blk_out(const int side, const int j, const int n) { return side ? n - 1 - j : j + 1; }
+QK_HD constexpr int blk_cut_bond(const int side, const int width, const int n) { return side ? n - width : width; }
+// A pair chain is one (x state i, y state j); its slot is the string chain's, P = max(P_x, P_y): E [pad_y x pad_x] at chain_E()
+// (ld = the padded x bond) | T [pad_x x 2 pad_y] at chain_T().  Between two sites T is dead, so the products of a cut live there:
+// V [pad_y x pad_x] at blk_V() and W [pad_x x pad_x] at blk_W(), each a re plane then an im plane of P^2.
+QK_HD constexpr int blk_V() { return chain_T(); }
+QK_HD constexpr int blk_W() { return chain_T() + 2; }
+static_assert(blk_V() >= chain_T() && blk_W() + 2 <= chain_size() && blk_V() + 2 <= blk_W(), "V and W lie inside T and do not overlap");
+
+// the blocks of a pair chain (px, py = the padded bonds [n + 1] of its two states) in the launch `kind` of step j
+inline int blk_task_count(const int kind, const int side, const int j, const int32_t* px, const int32_t* py, const int n) {
+  const int in = blk_in(side, j, n), out = blk_out(side, j, n);
+  switch (kind) {
+    case BLK_T: return (int)blocks64(px[in], 2ll * py[out]);
+    case BLK_X: case BLK_V: return (int)blocks64(py[out], px[out]);
+    case BLK_W: return (int)blocks64(px[out], px[out]);
+    default: return px[out] / LOC_CHUNK;  // BLK_RED
+  }
+}
+struct BlkLaunch {
+  int kind, step, cut;  // cut: index into the width list (BLK_V, BLK_W, BLK_RED), else -1
+};
+// The launches of a pair batch in stream order: per step T and X, and behind the step whose width was asked for V, W and the
+// reduction.  The chain stops at the largest width: 2 widths[n_widths - 1] + 3 n_widths launches.
+inline std::vector<BlkLaunch> blk_plan(const int n_widths, const int32_t* widths) {
+  std::vector<BlkLaunch> plan;
+  int ci = 0;
+  for (int j = 0; ci < n_widths; ++j) {
+    plan.push_back({BLK_T, j, -1}), plan.push_back({BLK_X, j, -1});
+    if (widths[ci] == j + 1) {
+      plan.push_back({BLK_V, j, ci}), plan.push_back({BLK_W, j, ci}), plan.push_back({BLK_RED, j, ci});
+      ++ci;
+    }
+  }
+  return plan;
+}
+// widths must be strictly increasing in 1 .. n: returns -1, or the index of the first offender
+inline int blk_bad_width(const int n_widths, const int32_t* widths, const int n) {
+  for (int i = 0; i < n_widths; ++i)
+    if (widths[i] < 1 || widths[i] > n || (i > 0 && widths[i] <= widths[i - 1])) return i;
+  return -1;
+}
+
+// The kept environments: a compact buffer of doubles that starts with the 16 x 16 unit matrix (blk_kept_unit() doubles: E of a
+// chain before its first step), then for every state of a set and every chosen cut, state-major in width order, the self environment
+// of the cut (R of the bond, or L for side 1), pad^2 per plane.  koff[s * n_widths + ci] = its first double.  `at` = where the
+// set's environments start; returns where they end.
+constexpr long long blk_kept_unit() { return 2 * 16 * 16; }
+inline long long blk_kept_offsets(const EnvSizes& z, const int side, const int n_widths, const int32_t* widths, long long at, std::vector<int64_t>& koff) {
+  const int n = z.n_sites;
+  koff.resize((size_t)z.n_states * n_widths);
+  for (int s = 0; s < z.n_states; ++s)
+    for (int ci = 0; ci < n_widths; ++ci) {
+      const long long d = z.pad[(size_t)s * (n + 1) + blk_cut_bond(side, widths[ci], n)];
+      koff[(size_t)s * n_widths + ci] = at;
+      at += 2 * d * d;
+    }
+  return at;
+}
+
+struct BlkChains {  // the pair chains of a call, in the order of its pair list
+  std::vector<long long> slot, ntasks, weight;  // doubles of its slot; its tasks over all launches; slot, partial sums, tasks and table entries
+};
+inline BlkChains list_blk_chains(const EnvSizes& zx, const EnvSizes& zy, const long long n_pairs, const int32_t* pairs, const int side,
+                                 const std::vector<BlkLaunch>& plan, const int n_widths) {
+  const int n = zx.n_sites, max_chunks = std::max(zx.max_chunks, zy.max_chunks);
+  BlkChains c;
+  c.slot.resize(n_pairs), c.ntasks.resize(n_pairs), c.weight.resize(n_pairs);
+  for (long long e = 0; e < n_pairs; ++e) {
+    const int i = pairs[2 * e], j = pairs[2 * e + 1];
+    const long long P = std::max(zx.pmax[i], zy.pmax[j]);
+    long long nt = 0;
+    for (const BlkLaunch& l : plan) nt += blk_task_count(l.kind, side, l.step, &zx.pad[(size_t)i * (n + 1)], &zy.pad[(size_t)j * (n + 1)], n);
+    c.slot[e] = chain_size() * P * P, c.ntasks[e] = nt;
+    c.weight[e] = c.slot[e] + (long long)n_widths * max_chunks + nt + 4;
+  }
+  return c;
+}
+// Task lists (chain of the batch, block) of the pair chains [c0, c0 + nc) for every launch of `plan`
+inline void blk_lists(const EnvSizes& zx, const EnvSizes& zy, const int32_t* pairs, const size_t c0, const size_t nc, const int side, const std::vector<BlkLaunch>& plan,
+                      std::vector<Task2>& tasks, std::vector<long long>& first) {
+  const int n = zx.n_sites;
+  tasks.clear(), first.clear();
+  for (const BlkLaunch& l : plan) {
+    first.push_back((long long)tasks.size());
+    for (size_t e = 0; e < nc; ++e) {
+      const int i = pairs[2 * (c0 + e)], j = pairs[2 * (c0 + e) + 1];
+      const int nbk = blk_task_count(l.kind, side, l.step, &zx.pad[(size_t)i * (n + 1)], &zy.pad[(size_t)j * (n + 1)], n);
+      for (int b = 0; b < nbk; ++b) tasks.push_back(Task2{(int)e, b});
+    }
+  }
   first.push_back((long long)tasks.size());
 }
 

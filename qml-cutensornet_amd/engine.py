@@ -105,6 +105,8 @@ _SIGNATURES = [
     ("qk_feature_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_bond_purities_host", C.c_int, [_P, _P, _P, _P]),
     ("qk_bond_spectra_host", C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    ("qk_block_values_host", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    ("qk_block_self_host", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
@@ -315,6 +317,62 @@ def cap_cost(spectra, chi: int) -> np.ndarray:
 def schmidt_rank(spectra, tol: float) -> np.ndarray:
     """Number of Schmidt weights above ``tol`` at each bond (weights below about 1e-15 are rounding noise of the environments)."""
     return np.count_nonzero(_spectra_array(spectra) > float(tol), axis=-1)
+
+
+def _block_side(side) -> int:
+    """'left' / 'right' -> 0 / 1; an int goes to the library as it is (which rejects anything but 0 and 1)."""
+    if isinstance(side, str):
+        if side not in ("left", "right"):
+            raise ValueError(f"side must be 'left' or 'right', got {side!r}")
+        return 0 if side == "left" else 1
+    if isinstance(side, bool) or not isinstance(side, (int, np.integer)):
+        raise ValueError(f"side must be 'left' or 'right', got {side!r}")
+    return int(side)
+
+
+def _block_widths(widths, n_sites: int) -> np.ndarray:
+    """The width list as int32; ``None`` means 1 .. n_sites.  (The library rejects widths that are not strictly increasing in
+    1 .. n_sites.)"""
+    if widths is None:
+        return np.arange(1, n_sites + 1, dtype=np.int32)
+    w = np.asarray(widths)
+    if w.ndim != 1 or (w.size and not np.issubdtype(w.dtype, np.integer)) or w.dtype == np.bool_:
+        raise ValueError(f"widths must be a list of ints, got {widths!r}")
+    return np.ascontiguousarray(w, dtype=np.int32)
+
+
+def block_kernel(O, Sx, Sy=None, form: str = "rbf", gamma=None) -> np.ndarray:
+    """A kernel from reduced-state overlaps (``Context.block_overlaps``), pure numpy.  ``O`` has shape (..., ny, nx), ``Sx`` (..., nx)
+    and ``Sy`` (..., ny) the self overlaps (purities); ``Sy=None`` means Y is X.
+        "overlap"     K = O
+        "normalized"  K = O[j, i] / sqrt(Sx[i] Sy[j])
+        "rbf"         K = exp(-gamma (Sx[i] + Sy[j] - 2 O[j, i])) = exp(-gamma ||rho_A(x_i) - rho_A(y_j)||_F^2), gamma > 0 (default 1)
+    With ``Sy=None`` the result is exactly symmetric (the upper triangle is mirrored) and "normalized" and "rbf" have a diagonal of
+    exactly 1.0."""
+    if form not in ("overlap", "normalized", "rbf"):
+        raise ValueError(f"form must be 'overlap', 'normalized' or 'rbf', got {form!r}")
+    g = 1.0 if gamma is None else float(gamma)
+    if not (g > 0.0 and np.isfinite(g)):
+        raise ValueError(f"gamma must be > 0 and finite, got {gamma!r}")
+    O = np.asarray(O, dtype=np.float64)
+    Sx = np.asarray(Sx, dtype=np.float64)
+    sym = Sy is None
+    Sy = Sx if sym else np.asarray(Sy, dtype=np.float64)
+    if O.ndim < 2 or Sx.shape != O.shape[:-2] + O.shape[-1:] or Sy.shape != O.shape[:-2] + O.shape[-2:-1]:
+        raise ValueError(f"O of shape {O.shape} needs Sx of shape (..., nx) and Sy of shape (..., ny), got {Sx.shape} and {Sy.shape}")
+    if form == "overlap":
+        K = O.copy()
+    elif form == "normalized":
+        K = O / np.sqrt(Sx[..., None, :] * Sy[..., :, None])
+    else:
+        K = np.exp(-g * ((Sx[..., None, :] + Sy[..., :, None]) - 2.0 * O))
+    if sym:
+        iu = np.triu_indices(O.shape[-1], 1)
+        K[..., iu[1], iu[0]] = K[..., iu[0], iu[1]]
+        if form != "overlap":
+            d = np.arange(O.shape[-1])
+            K[..., d, d] = 1.0
+    return K
 
 
 def _dims_table(states) -> np.ndarray:
@@ -1033,6 +1091,56 @@ class Context:
         _check(lib().qk_bond_purities_host(self._h, mps_set.handle, out.ctypes.data, nrm.ctypes.data), "qk_bond_purities_host")
         out = out[:, : n - 1]
         return (out, nrm) if norms else out
+
+    def block_values_host(self, xset: MpsSet, yset: MpsSet | None, plan: Plan, widths, side="left") -> np.ndarray:
+        """Reduced-state overlaps O_w = tr(rho_A(x_i) rho_A(y_j)) of ``plan``'s pairs, A = the first (``side="left"``) or last
+        (``"right"``) w qubits, for every w of ``widths`` (strictly increasing, 1 .. n_sites): float64 of shape (n_widths,
+        plan.num_pairs), pairs as ``plan.pairs()`` lists them.  One pair chain gives every width at once; a (pair, width) value is
+        the same bits whatever the other pairs and widths of the call.  fp64 sets only.  Synchronous."""
+        n = xset.info()["n_sites"]
+        w = _block_widths(widths, n)
+        vals = np.zeros((max(w.size, 1), max(plan.num_pairs, 1)), dtype=np.float64)  # (spare elements: the pointers stay valid)
+        wp = w if w.size else np.zeros(1, dtype=np.int32)
+        _check(lib().qk_block_values_host(self._h, xset.handle, None if yset is None else yset.handle, plan.handle, _block_side(side), int(w.size), wp.ctypes.data,
+                                          vals.ctypes.data), "qk_block_values_host")
+        return np.ascontiguousarray(vals[: w.size, : plan.num_pairs])
+
+    def block_self(self, mps_set: MpsSet, widths=None, side="left", norms: bool = False):
+        """Self overlaps S_w = tr(rho_A(psi)^2) -- the purity of the cut -- of every state of an fp64 set, through the route of
+        ``block_values_host`` (the pairs (s, s)): float64 of shape (n_widths, n_states); ``widths=None`` means 1 .. n_sites.  With
+        ``norms=True`` also <psi|psi> (the bits of ``local_paulis``), as ``(S, norms)``.  Synchronous."""
+        info = mps_set.info()
+        ns, n = info["n_states"], info["n_sites"]
+        w = _block_widths(widths, n)
+        out = np.zeros((max(w.size, 1), ns), dtype=np.float64)
+        nrm = np.zeros(ns, dtype=np.float64)
+        wp = w if w.size else np.zeros(1, dtype=np.int32)
+        _check(lib().qk_block_self_host(self._h, mps_set.handle, _block_side(side), int(w.size), wp.ctypes.data, out.ctypes.data, nrm.ctypes.data), "qk_block_self_host")
+        out = np.ascontiguousarray(out[: w.size])
+        return (out, nrm) if norms else out
+
+    def block_overlaps(self, xs: MpsSet, ys: MpsSet | None = None, widths=None, side="left"):
+        """``(O, Sx, Sy)``: the reduced-state overlaps O[w, j, i] = tr(rho_A(x_i) rho_A(y_j)) of every pair, shape (n_widths, ny,
+        nx), rows = Y (or X), and the self overlaps Sx (n_widths, nx), Sy (n_widths, ny) -- what ``block_kernel`` takes.
+        ``widths=None`` means 1 .. n_sites.  A symmetric call (``ys=None``) computes the pairs i <= j, mirrors them, takes Sx from
+        the diagonal (the bits of ``block_self``) and returns ``Sy = Sx``.  Synchronous."""
+        sym = ys is None
+        nx = len(xs)
+        ny = nx if sym else len(ys)
+        plan = Plan(xs.dims, None if sym else ys.dims, orient=False)
+        try:
+            vals = self.block_values_host(xs, ys, plan, widths, side)
+            pairs = plan.pairs()
+        finally:
+            plan.close()
+        O = np.zeros((vals.shape[0], ny, nx), dtype=np.float64)
+        O[:, pairs[:, 1], pairs[:, 0]] = vals
+        if sym:
+            O[:, pairs[:, 0], pairs[:, 1]] = vals
+            d = np.arange(nx)
+            Sx = np.ascontiguousarray(O[:, d, d])
+            return O, Sx, Sx
+        return O, self.block_self(xs, widths, side), self.block_self(ys, widths, side)
 
     def bond_spectra(self, mps_set: MpsSet, max_values: int | None = None, norms: bool = False):
         """Entanglement spectra of every state of an fp64 set: the Schmidt weights (eigenvalues of the reduced state, descending, sum

@@ -688,6 +688,99 @@ def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64),
     return out
 
 
+def build_block_kernel_matrices(mpi_comm, ansatz, X, Y=None, widths=None, side="left", form="rbf", block_gamma=None, truncation_error=None, info_file=None,
+                                loglevel=30):
+    """Block kernels: from ONE build of the states, the projected kernel of the reduced state of the first (``side="left"``) or last
+    (``"right"``) w qubits, for every w of ``widths`` (strictly increasing ints in 1 .. num_qubits; ``None``: every width).  One pair
+    sweep gives the whole family between the one-qubit kernel (w = 1) and the fidelity kernel (w = n).  Rank 0 returns the dict
+        widths    [w, ...]
+        K         {w: (len(Y), len(X))}    the kernel of ``form``: "overlap", "normalized" or "rbf" (``engine.block_kernel``;
+                                           ``block_gamma`` is the rbf's gamma, default 1)
+        overlap   {w: (len(Y), len(X))}    O_w[j, i] = tr(rho_A(x_i) rho_A(y_j))
+        self_x    (n_widths, len(X))       S_w(x_i) = tr(rho_A(x_i)^2)
+        self_y    (n_widths, len(Y))       (``self_x`` when Y is None)
+    and the other ranks ``None``.  The shares are built and exchanged as in ``build_capped_kernel_matrices``; each rank sweeps its
+    share of the pairs (``Context.block_values_host``) and the shares meet in one all-gather on the communicator.  The self
+    overlaps are linear work: every rank computes them for all states."""
+    if Y is not None and len(X) < len(Y):
+        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    n_qubits = int(ansatz.num_qubits)
+    if widths is None:
+        widths = range(1, n_qubits + 1)
+    widths = [w for w in widths]
+    if (not widths or any(isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 1 <= w <= n_qubits for w in widths)
+            or any(b <= a for a, b in zip(widths, widths[1:]))):
+        raise ValueError(f"widths must be strictly increasing ints in 1 .. {n_qubits}, got {widths!r}")
+    widths = [int(w) for w in widths]
+    if side not in ("left", "right"):
+        raise ValueError(f"side must be 'left' or 'right', got {side!r}")
+    if form not in ("overlap", "normalized", "rbf"):
+        raise ValueError(f"form must be 'overlap', 'normalized' or 'rbf', got {form!r}")
+    if block_gamma is not None and not (float(block_gamma) > 0.0 and np.isfinite(float(block_gamma))):
+        raise ValueError(f"block_gamma must be > 0 and finite, got {block_gamma!r}")
+    X = np.asarray(X, dtype=np.float64)
+    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
+    fidelity = 1.0 - float(truncation_error)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    t_start = time.perf_counter()
+    ctx = _engine.default_context(device_id)
+    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
+    shares = [(len(X),) + tuple(_simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers))]
+    if Y is not None:
+        _say(is_root, "\nContracting the MPS of the circuits from the Y dataset...")
+        shares.append((len(Y),) + tuple(_simulate_share(ansatz, Y, rank, n_procs, fidelity, is_root, "Y", device_id, host_workers)))
+    ctx.trim()
+    build_secs = time.perf_counter() - t_start
+    locals_ = [s[2] for s in shares]
+    full = []
+    try:
+        full = [exchange_sets(mpi_comm, ctx, loc, lo, total)[0] for loc, (total, lo, _, _, _) in zip(locals_, shares)]
+        xset, yset = full[0], full[1] if len(full) > 1 else None
+        t0 = time.perf_counter()
+        # (orient=False: a symmetric plan lists i <= j for every world size, so a value is the same bits however many ranks share the pairs)
+        plan = _engine.Plan(xset.dims, None if yset is None else yset.dims, n_procs, rank, orient=False)
+        try:
+            vals = ctx.block_values_host(xset, yset, plan, widths, side)
+            parts = comm_allgather(mpi_comm, (plan.pairs(), vals))
+        finally:
+            plan.close()
+        self_x = ctx.block_self(xset, widths, side)
+        self_y = self_x if yset is None else ctx.block_self(yset, widths, side)
+        sweep_secs = time.perf_counter() - t0
+    finally:
+        for f, loc in zip(full, locals_):
+            if f is not loc:
+                f.close()
+        for loc in locals_:
+            if loc is not None:
+                loc.close()
+    if not is_root:
+        return None
+    ny = len(X) if Y is None else len(Y)
+    out = {"widths": widths, "K": {}, "overlap": {}, "self_x": self_x, "self_y": self_y}
+    for wi, w in enumerate(widths):
+        O = assemble_gram(ny, len(X), [p[0] for p in parts], [p[1][wi] for p in parts], Y is None)
+        out["overlap"][w] = O
+        out["K"][w] = _engine.block_kernel(O, self_x[wi], None if Y is None else self_y[wi], form=form, gamma=block_gamma)
+    if info_file is not None:
+        prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"],
+                "r0_circ_sim": [build_secs, "seconds"], "widths": [widths, "qubits"], "side": [side, ""], "r0_block_sweep": [sweep_secs, "seconds"],
+                "total_time": [time.perf_counter() - t_start, "seconds"]}
+        with open(info_file + ".json", "w") as fp:
+            json.dump(prof, fp, indent=4)
+    return out
+
+
 def _depth_scan_share(ctx, ansatz, points, rank, n_procs, fidelity, depths, ends, is_root, label, host_workers):
     """This rank's slice of ``points`` (the chunks of ``_simulate_share``) at every depth of ``depths`` (ascending): (first index,
     {depth: packed device set, or None for an empty share}, {depth: fidelities}).  One launch of the device builder to the deepest

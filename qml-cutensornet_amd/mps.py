@@ -146,6 +146,43 @@ class MPS:
             ts[k + 1] = np.tensordot((s[:m, None] * vh[:m]) / np.sqrt(1.0 - d), ts[k + 1], axes=(1, 0))
         return MPS(ts, fidelity), discarded, sigmas
 
+    def block_overlap(self, other: "MPS", width: int, side: str = "left") -> float:
+        """Overlap of the reduced states of a block at one end of the chain, on the host: ``tr(rho_A(self) rho_A(other))`` with
+        ``rho_A(psi) = tr_{not A} |psi><psi| / <psi|psi>`` and A the first ``width`` qubits (``side="left"``) or the last
+        (``side="right"``) -- the numpy mirror of ``Context.block_overlaps``.  One environment loop: the mixed left environment
+        ``E_w[b][a] = <l^x_a | l^y_b>`` of the fidelity sweep and the self right environments ``R_w`` of both states, then
+        ``sum Rx[a][a'] Ry[b][b'] E[b][a'] conj(E[b'][a]) / (<x|x> <y|y>)``.  The right block is the left block of the reversed
+        chains.  ``other=self`` gives the purity of the cut; ``width = n`` the normalised fidelity."""
+        n = len(self.tensors)
+        if len(other) != n:
+            raise ValueError("the two MPS must have the same number of sites")
+        if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or not 1 <= width <= n:
+            raise ValueError(f"width must be an int in 1 .. {n}, got {width!r}")
+        if side not in ("left", "right"):
+            raise ValueError(f"side must be 'left' or 'right', got {side!r}")
+        w = int(width)
+        chains = []
+        for m in (self, other):
+            ts = [np.asarray(t, dtype=np.complex128) for t in m.tensors]
+            chains.append([t.transpose(2, 1, 0) for t in reversed(ts)] if side == "right" else ts)
+        x, y = chains
+        E = np.ones((1, 1), dtype=np.complex128)  # E[b][a]: ket of y, bra of x
+        for k in range(w):
+            E = np.einsum("ba,bsc,asd->cd", E, y[k], x[k].conj(), optimize=True)
+        envs, norms = [], []
+        for ts in (x, y):  # R[ket][bra] at bond w, and <psi|psi> = R_0[0][0]
+            R = np.ones((1, 1), dtype=np.complex128)
+            Rw = R
+            for k in range(n - 1, -1, -1):
+                R = np.einsum("asc,cd,bsd->ab", ts[k], R, ts[k].conj(), optimize=True)
+                if k == w:
+                    Rw = R
+            envs.append(Rw)
+            norms.append(float(R[0, 0].real))
+        V = envs[1].T @ E           # V[b'][a'] = sum_b Ry[b][b'] E[b][a']
+        W = E.T @ V.conj()          # W[a][a'] = sum_b' E[b'][a] conj(V[b'][a'])
+        return float((envs[0] * W.conj()).sum().real) / (norms[0] * norms[1])
+
     def vdot(self, other: "MPS") -> complex:
         """<self|other> through the HIP engine (single pair; the Gram path is batch-first)."""
         from .engine import default_context

@@ -10,7 +10,11 @@ IXYZ per line) adds ctx.pauli_expectations(xs, strings) and ctx.feature_gram(V):
 would discard, ``cap_cost`` summed over the bonds of a state at chi = 16, 32, 64, 128 (the mean and the largest over the states).
 ``--compress CHI`` adds ctx.compress(xs, max_bond=CHI) and the Gram of the compressed set: compress_ms, compressed_gram_ms,
 compressed_max_bond, min_fidelity and max_abs_dK = max |K(compressed) - K|.
-usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement] [--compress CHI]"""
+``--block-widths 10,20,30,60`` adds the block kernels of the first w qubits: ctx.block_values_host on the symmetric plan of all
+pairs and ctx.block_self(xs, widths): block_values_ms, block_self_ms, n_widths, block_over_gram and, per width, the median
+off-diagonal entry of the "normalized" kernel.
+usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement] [--compress CHI]
+                                [--block-widths W1,W2,...]"""
 import argparse
 import json
 import os
@@ -86,6 +90,7 @@ def main():
     ap.add_argument("--strings-file", default=None, help="also time pauli_expectations on the strings of this file (one per line over IXYZ)")
     ap.add_argument("--entanglement", action="store_true", help="also time bond_purities and bond_spectra and print the cost of a bond cap")
     ap.add_argument("--compress", type=int, default=0, metavar="CHI", help="also time compress(max_bond=CHI) and the Gram of the compressed set")
+    ap.add_argument("--block-widths", default=None, metavar="W1,W2,...", help="also time the block kernels of the first w qubits for these widths")
     args = ap.parse_args()
     gamma = args.gamma if args.gamma is not None else (0.1 if args.config == "cfg5" else 1.0)
     n, reps, d, npts = bench.CONFIGS[args.config]
@@ -157,6 +162,20 @@ def main():
             "compress_chi": int(args.compress), "compress_ms": round(compress_ms, 3), "compressed_gram_ms": round(cgram_ms, 3),
             "compressed_max_bond": int(cinfo["bond_dims"].max()), "min_fidelity": float(cinfo["fidelity"].min()),
             "max_abs_dK": float(np.abs(KC - K).max()),
+        })
+    if args.block_widths:
+        widths = [int(w) for w in args.block_widths.split(",")]
+        plan = engine.Plan(xs.dims, orient=False)
+        vals, block_ms = timed(lambda: ctx.block_values_host(xs, None, plan, widths), args.reps)
+        Sw, self_ms = timed(lambda: ctx.block_self(xs, widths), args.reps)
+        pairs = plan.pairs()
+        plan.close()
+        offd = pairs[:, 0] != pairs[:, 1]
+        norm = vals / np.sqrt(Sw[:, pairs[:, 0]] * Sw[:, pairs[:, 1]])
+        dist.update({
+            "block_widths": widths, "n_widths": len(widths), "block_values_ms": round(block_ms, 3), "block_self_ms": round(self_ms, 3),
+            "block_over_gram": round(block_ms / gram_ms, 4),
+            "median_offdiag_block_normalized": {str(w): float(np.median(norm[wi][offd])) for wi, w in enumerate(widths)},
         })
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
