@@ -449,6 +449,30 @@ int qk_block_values_host(qk_ctx* ctx, const qk_mps_set* xset, const qk_mps_set* 
 int qk_block_self_host(qk_ctx* ctx, const qk_mps_set* set, int32_t side, int32_t n_widths, const int32_t* widths,
                        double* out /* [n_widths][n_states]: S_w */, double* norms /* may be NULL; the bits of qk_local_paulis_host */);
 
+/* ---- measurement shots: perfect sampling of every state of a set -----------------------------------------------------------------
+ * qk_sample_host: bits[s][shot][k] = the outcome of measuring qubit k of state s in the Pauli basis bases[shot][k] (1..3 = X, Y, Z;
+ * bit 0 = eigenvalue +1), n_shots independent shots per state; logp[s][shot], when given, = the log of the exact probability of
+ * the drawn string in the drawn bases, |<b| U_bases |psi>|^2 / <psi|psi>.  One shot: v = [1] over the left bond, for k = 0 .. n-1
+ *     W_t = v A_k[.][t][.] (t = 0, 1);   Z: W' = W;  X: W'_0,1 = (W_0 +- W_1)/sqrt2;  Y: W'_0,1 = (W_0 -+ i W_1)/sqrt2
+ *     p_o = max(0, Re W'_o R_{k+1} W'_o^H),  tot = p_0 + p_1,  u = uniform(seed, first_state + s, shot, k) in [0, 1)
+ *     bit = 1 if (p_1 > 0 and u tot >= p_0) else 0;   logp += log(p_bit / tot);   v = W'_bit / sqrt(p_bit)
+ * with the right environments R_k of qk_local_paulis_host (X[ket][bra], R_n = 1).  The uniform is Philox4x32-10 written out in
+ * this library: counter (k, shot, first_state + s, 0), key (seed & 0xffffffff, seed >> 32), u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53.
+ * Per state batch the reversed chain keeps every R_k; a shot chain is one (state, tile of 64 shots); at site k every chain of a
+ * chain batch goes through one launch each of two GEMMs on the f64 matrix cores (shot rows as M, 3-product complex form, fixed K
+ * order), the basis rotation and the draw: 4 n_sites launches per chain batch whatever n_shots.  The bits and logp of a
+ * (state, shot) depend only on seed, first_state + s, the shot index, that shot's bases and that state's tensors -- not on the other
+ * states or shots, the cut into batches and tiles, or the run: no atomics, no grid barrier.  QK_SAMPLE_BATCH=k (read per call)
+ * caps the shot chains of a batch.  Synchronous; leaves the Gram statistics alone.  Device scratch: the reversed image, the bits
+ * and logp for the length of the call; per state batch the environments, per chain batch a slot of 14 P R doubles per chain (P = the
+ * state's largest padded bond, R = its shots padded to 16), each bounded by a quarter of the free memory, released by qk_ctx_trim.
+ * QK_EINVAL (the message names the argument): a null ctx, set or bits; a set of another context; a complex64 set; n_shots < 1; a
+ * basis code outside 1..3; first_state < 0 or first_state + n_states > 2^32.  QK_EDEVICE: a shot whose tot is 0 or not finite, as
+ * for a state of norm 0 (the message names the state).                                                                            */
+int qk_sample_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_shots, const uint8_t* bases /* [n_shots][n_sites], NULL: all Z */,
+                   uint64_t seed, int64_t first_state /* global index of state 0 */, uint8_t* bits /* [n_states][n_shots][n_sites] */,
+                   double* logp /* [n_states][n_shots], may be NULL */);
+
 /* ---- compressing a set: one canonical truncation sweep per state -------------------------------------------------------------
  * qk_mps_set_compress: *out = a new fp64 set of the same context that owns its memory, every state of src truncated ONCE on its
  * final tensors; src is left untouched.  One workgroup per state (workgroup b takes states b, b + grid, ...), two passes over the

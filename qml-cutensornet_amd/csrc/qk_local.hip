@@ -6,7 +6,8 @@
 // qk_pauli_strings_host and qk_feature_gram_host, and the entanglement across every bond of a state from the same environments,
 // qk_bond_purities_host and qk_bond_spectra_host (definitions above bond_call below), and the block kernels -- reduced-state
 // overlaps of the first or last w qubits for every pair of two sets -- qk_block_values_host and qk_block_self_host (definitions
-// above BlkSet below) (include/qkgram.h).
+// above BlkSet below), and measurement shots of every state of a set, each shot and qubit in its own Pauli basis, qk_sample_host
+// (definitions above SmpArgs below) (include/qkgram.h).
 //
 // Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
 // normalised):
@@ -1313,7 +1314,308 @@ int block_check(qk_ctx* c, const char* what, const qk_mps_set* xset, const qk_mp
   return QK_OK;
 }
 
+// ---- measurement shots (qk_sample_host) -----------------------------------------------------------------------------------------
+// Perfect sampling of every state of a set, each shot and qubit in its own Pauli basis (codes 1..3 = X, Y, Z; outcome bit 0 =
+// eigenvalue +1).  One shot, v = [1] a row vector over the left bond, for k = 0 .. n-1:
+//     W_t[b']  = sum_b v[b] A_k[b][t][b']                                   t = 0, 1
+//     Z: W'_0 = W_0, W'_1 = W_1;   X: W'_0 = (W_0 + W_1)/sqrt2, W'_1 = (W_0 - W_1)/sqrt2;   Y: W'_0 = (W_0 - i W_1)/sqrt2, W'_1 = (W_0 + i W_1)/sqrt2
+//     p_o      = max(0, Re sum_{b',a'} W'_o[b'] R_{k+1}[b'][a'] conj(W'_o[a'])),   tot = p_0 + p_1
+//     u        = smp_uniform(seed, global state index, shot, k)
+//     bit      = 1 if (p_1 > 0 and u tot >= p_0) else 0;   logp += log(p_bit / tot);   v = W'_bit / sqrt(p_bit)
+// exp(logp) is the probability of the drawn string in the drawn bases.  Per state batch the reversed chain keeps every R_k
+// (sample_env_plan); a shot chain is one (state, tile of SMP_TILE shots) with its own slot (qk_local_plan.h).  At site k every chain
+// of the chain batch goes through ONE launch of each of: SMP_W (GEMM, shot rows as M), SMP_ROT (the rotation by each row's code,
+// written as the stacked K-major operand), SMP_Q (GEMM, the stacked rows as M) and SMP_DRAW (one wave per row: the two sums over
+// the true bond in a fixed order, the uniform, the bit, log p and the next v).  4 n_sites launches per chain batch, whatever the
+// number of shots.  A row of a GEMM is a sum over K in the ring GEMM's fixed order whatever its block, nothing of a row depends on
+// another row, no atomics, no grid barrier: the bits and log p of a (state, shot) are the same whatever the other states and shots,
+// the cut into batches and tiles (QK_SAMPLE_BATCH caps the chains of a batch) and the run.  Only the columns below the true bond
+// enter a probability.
+struct SmpArgs {
+  LocArgs e;              // the set and the state batch of the environment pass: e.scratch holds every R_k
+  const int32_t* cent;    // chain -> batch entry
+  const int32_t* shot0;   // chain -> its first shot
+  const int32_t* rows;    // chain -> its shots
+  const int64_t* cbase;   // chain -> first double of its slot
+  const uint8_t* bases;   // [n_shots][n_sites], NULL: all Z
+  const int2* tasks;      // this launch: (chain, block)
+  double* slots;
+  uint8_t* bits;          // [n_states][n_shots][n_sites]
+  double* logp;           // [n_states][n_shots]
+  int32_t* bad;           // [chain]: 1 where a row's tot was 0 or not finite
+  unsigned long long seed;
+  long long first_state;  // global index of state 0 of the set
+  int n_shots;
+  int step;               // site k
+};
+
+// One 64 x 64 output block of one shot chain's GEMM at site k (SMP_W or SMP_Q).
+__global__ __launch_bounds__(512) void qk_smp_gemm_kernel(const SmpArgs g, const int kind) {
+  __shared__ __attribute__((aligned(16))) double lds[LOC_LDS_DOUBLES];
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = __builtin_amdgcn_readfirstlane(t.x);
+  const int blk = __builtin_amdgcn_readfirstlane(t.y);
+  const int i = __builtin_amdgcn_readfirstlane(g.cent[ch]);
+  const int n = g.e.n_sites, n1 = n + 1, k = g.step;
+  const long long st = __builtin_amdgcn_readfirstlane(g.e.states[i]);
+  const int l = __builtin_amdgcn_readfirstlane(g.e.dims[st * n1 + k]), r = __builtin_amdgcn_readfirstlane(g.e.dims[st * n1 + k + 1]);
+  const long long P = __builtin_amdgcn_readfirstlane(g.e.pmax[i]);
+  const int R = smp_rows_pad(__builtin_amdgcn_readfirstlane(g.rows[ch]));
+  const long long PR = P * R;
+  double* const slot = g.slots + uni64(g.cbase[ch]);
+  const double *Are, *Aim, *Bre, *Bim;
+  double *Cre, *Cim;
+  int lda, ldb, ldc, M, N, K;
+  if (kind == SMP_W) {
+    Are = slot + smp_V() * PR, Aim = Are + PR;
+    Bre = g.e.data + uni64(g.e.offs[st * n + k]);
+    Bim = Bre + (long long)l * 2 * r;
+    Cre = slot + smp_W() * PR, Cim = Cre + 2 * PR;
+    lda = R, ldb = 2 * r, ldc = 2 * r, M = R, N = 2 * r, K = __builtin_amdgcn_readfirstlane(g.e.tru[st * n1 + k]);
+  } else {
+    Are = slot + smp_Ws() * PR, Aim = Are + 2 * PR;
+    Bre = g.e.scratch + uni64(g.e.sbase[i]) + g.e.rmul * P * P + uni64(g.e.roff[(long long)i * n1 + k + 1]);
+    Bim = Bre + (long long)r * r;
+    Cre = slot + smp_Q() * PR, Cim = Cre + 2 * PR;
+    lda = 2 * R, ldb = r, ldc = r, M = 2 * R, N = r, K = __builtin_amdgcn_readfirstlane(g.e.tru[st * n1 + k + 1]);
+  }
+  const int npm = (M + 63) / 64;
+  const int m0 = 64 * (blk % npm), n0 = 64 * (blk / npm);
+  zgemm_ring3<false, LOC_KTL, LOC_NSLOT, true, 8, 64, double, 10>(Cre + (long long)m0 * ldc + n0, Cim + (long long)m0 * ldc + n0, ldc, Are + m0, Aim + m0, lda,
+                                                                   Bre + n0, Bim + n0, ldb, min(64, M - m0), min(64, N - n0), K, lds);
+}
+
+// (W'_0, W'_1) of (W_0, W_1) in the basis `code` (1..3 = X, Y, Z)
+__device__ __forceinline__ void smp_rotate(const int code, const double w0r, const double w0i, const double w1r, const double w1i, double& a0r, double& a0i, double& a1r,
+                                           double& a1i) {
+  constexpr double h = 0.70710678118654752440;
+  if (code == 1) a0r = (w0r + w1r) * h, a0i = (w0i + w1i) * h, a1r = (w0r - w1r) * h, a1i = (w0i - w1i) * h;
+  else if (code == 2) a0r = (w0r + w1i) * h, a0i = (w0i - w1r) * h, a1r = (w0r - w1i) * h, a1i = (w0i + w1r) * h;
+  else a0r = w0r, a0i = w0i, a1r = w1r, a1i = w1i;
+}
+__device__ __forceinline__ int smp_code(const SmpArgs& g, const int ch, const int row) {
+  return (g.bases && row < g.rows[ch]) ? g.bases[(long long)(g.shot0[ch] + row) * g.e.n_sites + g.step] : 3;
+}
+
+// v = [1] of every shot of a chain: V[0][row] = 1, the rest of the first 16 bond rows (pad_0 = 16) and the pad rows 0.
+__global__ __launch_bounds__(256) void qk_smp_init_kernel(const SmpArgs g) {
+  const int ch = blockIdx.x;
+  const int rows = g.rows[ch], R = smp_rows_pad(rows);
+  const long long PR = (long long)g.e.pmax[g.cent[ch]] * R;
+  double* const V = g.slots + g.cbase[ch] + smp_V() * PR;
+  for (int e = threadIdx.x; e < LOC_CHUNK * R; e += 256) V[e] = (e < rows) ? 1.0 : 0.0, V[PR + e] = 0.0;
+  if (threadIdx.x == 0) g.bad[ch] = 0;
+}
+
+// The rotation of one 16-row chunk of shots: W[row][(t, b')] -> the stacked operand W'[b'][(o, row)], every padded column (zero
+// from the true bond on).
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_smp_rotate_kernel(const SmpArgs g) {
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = t.x, c = t.y;
+  const int i = g.cent[ch];
+  const int n1 = g.e.n_sites + 1, k = g.step;
+  const long long st = g.e.states[i];
+  const int r = g.e.dims[st * n1 + k + 1], rt = g.e.tru[st * n1 + k + 1];
+  const int R = smp_rows_pad(g.rows[ch]);
+  const long long PR = (long long)g.e.pmax[i] * R;
+  double* const slot = g.slots + g.cbase[ch];
+  const double* const W = slot + smp_W() * PR;
+  double* const Ws = slot + smp_Ws() * PR;
+  for (int e = threadIdx.x; e < LOC_CHUNK * r; e += LOC_RED_THREADS) {
+    const int row = c * LOC_CHUNK + (e & (LOC_CHUNK - 1)), bp = e / LOC_CHUNK;
+    double a0r = 0, a0i = 0, a1r = 0, a1i = 0;
+    if (bp < rt) {
+      const long long w = (long long)row * 2 * r + bp;
+      smp_rotate(smp_code(g, ch, row), W[w], W[w + 2 * PR], W[w + r], W[w + r + 2 * PR], a0r, a0i, a1r, a1i);
+    }
+    const long long q = (long long)bp * 2 * R + row;
+    Ws[q] = a0r, Ws[q + 2 * PR] = a0i, Ws[q + R] = a1r, Ws[q + R + 2 * PR] = a1i;
+  }
+}
+
+// The draw of one 16-row chunk of shots, one wave per row (four rows each): p_o = Re sum_{a'} Q[(o, row)][a'] conj(W'_o[row][a'])
+// over the true bond -- lane j adds a' = j, j + 64, .. in order, then the lanes in a fixed butterfly -- the uniform, the bit,
+// log p, and the next v = W'_bit / sqrt(p_bit) into V (K-major; zero from the true bond on, and for a pad row).
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_smp_draw_kernel(const SmpArgs g) {
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = t.x, c = t.y;
+  const int i = g.cent[ch];
+  const int n = g.e.n_sites, n1 = n + 1, k = g.step;
+  const long long st = g.e.states[i];
+  const int r = g.e.dims[st * n1 + k + 1], rt = g.e.tru[st * n1 + k + 1];
+  const int rows = g.rows[ch], R = smp_rows_pad(rows);
+  const long long PR = (long long)g.e.pmax[i] * R;
+  double* const slot = g.slots + g.cbase[ch];
+  const double* const W = slot + smp_W() * PR;
+  const double* const Q = slot + smp_Q() * PR;
+  double* const V = slot + smp_V() * PR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int j = 0; j < LOC_CHUNK / 4; ++j) {
+    const int row = c * LOC_CHUNK + 4 * wave + j;
+    const bool valid = row < rows;
+    const int code = smp_code(g, ch, row);
+    const double* const Wrow = W + (long long)row * 2 * r;
+    const double* const Q0 = Q + (long long)row * r;
+    const double* const Q1 = Q + (long long)(R + row) * r;
+    double p0 = 0, p1 = 0;
+    for (int a = lane; a < rt; a += 64) {
+      double a0r, a0i, a1r, a1i;
+      smp_rotate(code, Wrow[a], Wrow[a + 2 * PR], Wrow[a + r], Wrow[a + r + 2 * PR], a0r, a0i, a1r, a1i);
+      p0 += Q0[a] * a0r + Q0[a + 2 * PR] * a0i;
+      p1 += Q1[a] * a1r + Q1[a + 2 * PR] * a1i;
+    }
+    for (int m = 32; m > 0; m >>= 1) p0 += __shfl_xor(p0, m), p1 += __shfl_xor(p1, m);
+    p0 = fmax(0.0, p0), p1 = fmax(0.0, p1);
+    const double tot = p0 + p1;
+    const bool ok = valid && tot > 0.0 && isfinite(tot);
+    const long long shot = g.shot0[ch] + row;
+    const double u = smp_uniform(g.seed, (uint32_t)(g.first_state + st), (uint32_t)shot, (uint32_t)k);
+    const int bit = (ok && p1 > 0.0 && u * tot >= p0) ? 1 : 0;
+    const double pb = bit ? p1 : p0;
+    if (valid && lane == 0) {
+      const long long o = st * g.n_shots + shot;
+      g.bits[o * n + k] = (uint8_t)bit;
+      g.logp[o] = (k ? g.logp[o] : 0.0) + (ok ? log(pb / tot) : 0.0);
+      if (!ok) g.bad[ch] = 1;
+    }
+    if (k + 1 < n) {
+      const double s = sqrt(pb);
+      for (int a = lane; a < r; a += 64) {
+        double vr = 0, vi = 0;
+        if (ok && a < rt) {
+          double a0r, a0i, a1r, a1i;
+          smp_rotate(code, Wrow[a], Wrow[a + 2 * PR], Wrow[a + r], Wrow[a + r + 2 * PR], a0r, a0i, a1r, a1i);
+          vr = (bit ? a1r : a0r) / s, vi = (bit ? a1i : a0i) / s;
+        }
+        V[(long long)a * R + row] = vr, V[(long long)a * R + row + PR] = vi;
+      }
+    }
+  }
+}
+
+int sample_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_shots, const uint8_t* bases, const uint64_t seed, const int64_t first_state, uint8_t* bits, double* logp) {
+  static const char* what = "qk_sample_host";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!set) return qk_fail(QK_EINVAL, "%s: set is null", what);
+  if (!bits) return qk_fail(QK_EINVAL, "%s: bits is null", what);
+  if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
+  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; sampling needs an fp64 set", what);
+  if (n_shots < 1) return qk_fail(QK_EINVAL, "%s: n_shots must be >= 1 (got %d)", what, n_shots);
+  const int ns = set->n_states, n = set->n_sites;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
+  if (first_state < 0 || first_state + ns > (1ll << 32))
+    return qk_fail(QK_EINVAL, "%s: first_state must be >= 0 and first_state + n_states <= 2^32 (got %lld)", what, (long long)first_state);
+  if (bases)
+    if (const long long bad = smp_bad_basis(bases, (long long)n_shots * n); bad >= 0)
+      return qk_fail(QK_EINVAL, "%s: bases[%lld][%lld] = %d is not a basis code (1..3 = X, Y, Z)", what, bad / n, bad % n, bases[bad]);
+  long long cap = 0;  // shot chains per batch; 0: the memory rule alone
+  if (const char* v = std::getenv("QK_SAMPLE_BATCH")) {
+    cap = std::atoll(v);
+    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_SAMPLE_BATCH must be >= 1 (got \"%s\")", what, v);
+  }
+  QkRangeGuard range_("qk:sample");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  EnvSizes z;
+  env_sizes(set->dims_true.data(), ns, n, set->max_pad, LOC_RMUL, false, z);
+  const size_t n_rows = (size_t)ns * n_shots, b_bits = al256(n_rows * n), b_bases = bases ? al256((size_t)n_shots * n) : 0;
+  QkDevBuf rev, dbits, dlogp, dbases;
+  HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
+  HIP_TRY_AS(what, dbits.alloc(b_bits));
+  HIP_TRY_AS(what, dlogp.alloc(n_rows * sizeof(double)));
+  if (bases) {
+    HIP_TRY_AS(what, dbases.alloc(b_bases));
+    HIP_TRY_AS(what, hipMemcpy(dbases.get(), bases, (size_t)n_shots * n, hipMemcpyHostToDevice));
+  }
+  // memory bound of a state batch (its right environments and the slots of its shot chains): a quarter of what is free; the
+  // environments of a batch take at most half of that (at least one state per batch), the chains of a batch the rest (at least one)
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  const std::vector<int> bstart = batch_cut(z.need, 0, budget / 2);
+  const Plan plan = sample_env_plan(n);
+  std::vector<Task2> tasks;
+  std::vector<long long> first;
+  std::vector<char> cstage;
+  std::vector<int64_t> h_cbase;
+  std::vector<int32_t> h_bad;
+  EnvBatch eb;
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+    env_tables(z, plan, s0, nb, 0, eb);
+    const SmpChains ch = list_smp_chains(z, s0, nb, n_shots, SMP_TILE);
+    const std::vector<size_t> cstart = chain_cut(ch.weight, budget - eb.tot, cap);
+    struct ChainBytes { size_t i32, cbase, tasks, slots; size_t tab() const { return 4 * i32 + cbase + tasks; } };  // cent | shot0 | rows | bad | cbase | tasks
+    auto chain_bytes = [&](const size_t c0, const size_t c1) {
+      long long nt = 0, sl = 0;
+      for (size_t e = c0; e < c1; ++e) nt += ch.ntasks[e], sl += ch.slot[e];
+      return ChainBytes{al256((c1 - c0) * sizeof(int32_t)), al256((c1 - c0) * sizeof(int64_t)), al256((size_t)nt * sizeof(int2)), (size_t)sl * sizeof(double)};
+    };
+    size_t b_chain = 0;
+    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
+      const ChainBytes cbz = chain_bytes(cstart[cb], cstart[cb + 1]);
+      b_chain = std::max(b_chain, cbz.tab() + cbz.slots);
+    }
+    // one device buffer for the state batch: [tables | tasks | environments] then the chain batch's [tables | tasks | slots]
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, b_chain)) return rc;
+    SmpArgs q{};
+    q.e = eb.g;
+    q.bases = bases ? dbases.get<uint8_t>() : nullptr;
+    q.bits = dbits.get<uint8_t>(), q.logp = dlogp.get<double>();
+    q.seed = seed, q.first_state = first_state, q.n_shots = n_shots;
+    char* const cbase0 = eb.base + eb.used();
+    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
+      const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
+      if (nc == 0) continue;
+      const ChainBytes cbz = chain_bytes(c0, c0 + nc);
+      h_cbase.resize(nc);
+      long long sl = 0;
+      for (size_t e = 0; e < nc; ++e) h_cbase[e] = sl, sl += ch.slot[c0 + e];
+      smp_lists(z, s0, ch, c0, nc, tasks, first);
+      cstage.assign(cbz.tab(), 0);
+      std::memcpy(cstage.data(), ch.cent.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + cbz.i32, ch.shot0.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + 2 * cbz.i32, ch.rows.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + 4 * cbz.i32, h_cbase.data(), nc * sizeof(int64_t));
+      std::memcpy(cstage.data() + 4 * cbz.i32 + cbz.cbase, tasks.data(), tasks.size() * sizeof(int2));
+      q.cent = reinterpret_cast<const int32_t*>(cbase0);
+      q.shot0 = reinterpret_cast<const int32_t*>(cbase0 + cbz.i32);
+      q.rows = reinterpret_cast<const int32_t*>(cbase0 + 2 * cbz.i32);
+      q.bad = reinterpret_cast<int32_t*>(cbase0 + 3 * cbz.i32);
+      q.cbase = reinterpret_cast<const int64_t*>(cbase0 + 4 * cbz.i32);
+      const int2* d_ctasks = reinterpret_cast<const int2*>(cbase0 + 4 * cbz.i32 + cbz.cbase);
+      q.slots = reinterpret_cast<double*>(cbase0 + cbz.tab());
+      HIP_TRY_AS(what, hipMemcpyAsync(cbase0, cstage.data(), cbz.tab(), hipMemcpyHostToDevice, c->stream));
+      qk_smp_init_kernel<<<dim3((unsigned)nc), dim3(256), 0, c->stream>>>(q);
+      for (size_t li = 0; li + 1 < first.size(); ++li) {
+        const int kind = SMP_KINDS[li % 4];
+        q.tasks = d_ctasks + first[li];
+        q.step = (int)(li / 4);
+        if (first[li + 1] <= first[li]) continue;
+        const dim3 grid((unsigned)(first[li + 1] - first[li]));
+        if (kind >= 0) qk_smp_gemm_kernel<<<grid, dim3(512), 0, c->stream>>>(q, kind);
+        else if (kind == SMP_ROT) qk_smp_rotate_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+        else qk_smp_draw_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+      }
+      HIP_TRY_AS(what, hipGetLastError());
+      h_bad.resize(nc);
+      HIP_TRY_AS(what, hipMemcpyAsync(h_bad.data(), q.bad, nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
+      for (size_t e = 0; e < nc; ++e)
+        if (h_bad[e])
+          return qk_fail(QK_EDEVICE, "%s: state %d has a shot whose outcome probabilities sum to 0 or are not finite (a state of norm 0?)", what, s0 + ch.cent[c0 + e]);
+    }
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  }
+  HIP_TRY_AS(what, hipMemcpy(bits, dbits.get(), n_rows * n, hipMemcpyDeviceToHost));
+  if (logp) HIP_TRY_AS(what, hipMemcpy(logp, dlogp.get(), n_rows * sizeof(double), hipMemcpyDeviceToHost));
+  return QK_OK;
+}
+
 }  // namespace
+
+extern "C" int qk_sample_host(qk_ctx* c, const qk_mps_set* set, int32_t n_shots, const uint8_t* bases, uint64_t seed, int64_t first_state, uint8_t* bits, double* logp) {
+  return sample_run(c, set, n_shots, bases, seed, first_state, bits, logp);
+}
 
 extern "C" int qk_block_values_host(qk_ctx* c, const qk_mps_set* xset, const qk_mps_set* yset, const qk_plan* plan, int32_t side, int32_t n_widths, const int32_t* widths,
                                     double* values_host) {

@@ -17,7 +17,7 @@ constexpr int LOC_CHUNK = 16;  // rows per reduction task
 
 // Every launch kind of qk_local.hip.  Kinds >= 0 are GEMM launches (64 x 64 output blocks), the others elementwise or reductions
 // in 16-row chunks.  LOC_*: tasks (batch entry, block), qk_local_gemm_kernel; STR_*: tasks (chain, block), qk_str_gemm_kernel;
-// BLK_*: tasks (pair chain, block), qk_blk_gemm_kernel.
+// BLK_*: tasks (pair chain, block), qk_blk_gemm_kernel; SMP_*: tasks (shot chain, block), qk_smp_gemm_kernel.
 enum LocKind : int {
   LOC_REV_T = 0,   // reversed chain: T = Lr^T Ar_j              (Lr_j = R_{o+1}, o = n-1-j)
   LOC_REV_X = 1,   // reversed chain: R_o = T^T conj(Ar_j)
@@ -43,6 +43,10 @@ enum LocKind : int {
   STR_PAULI = -7,     // qk_str_pauli_kernel: T[a][(s ^ f, b')] <- i^e(s) T[a][(s, b')] of the chains whose code at site k is not I
   STR_CLOSE = -8,     // qk_str_close_kernel: sum E_{b+1} R_{b+1} of the chains whose support ends at site k
   BLK_RED = -9,       // qk_blk_reduce_kernel: Re sum Rx[a][a'] conj(W[a][a']) of a chosen cut in 16-row chunks
+  SMP_W = 15,         // shot chain (state, shot tile), site k: W[row][(t, b')] = sum_b V[b][row] A_k[b][(t, b')], shot rows as M
+  SMP_Q = 16,         // shot chain: Q[(o, row)][a'] = sum_b' W'_o[row][b'] R_{k+1}[b'][a'], the stacked operand [W'_0 ; W'_1] as M
+  SMP_ROT = -10,      // qk_smp_rotate_kernel: W -> the stacked operand by each row's basis code, in 16-row chunks
+  SMP_DRAW = -11,     // qk_smp_draw_kernel: p_0, p_1 of a row, its uniform, its bit, log p and the next V, one wave per row
 };
 QK_HD constexpr bool conj_b(const int kind) { return kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V || kind == LOC_DIST_X || kind == STR_X || kind == BLK_X || kind == BLK_W; }
 
@@ -402,6 +406,98 @@ inline void blk_lists(const EnvSizes& zx, const EnvSizes& zy, const int32_t* pai
     }
   }
   first.push_back((long long)tasks.size());
+}
+
+// ---- measurement shots (qk_sample_host) -----------------------------------------------------------------------------------------
+// Philox4x32-10, counter (site, shot, global state index, stream), key = the two halves of the seed.  Stream 0 draws outcomes,
+// stream 1 the random bases.  The device and the host mirror run this text, so they agree bit for bit.
+struct Philox4 {
+  uint32_t x[4];
+};
+QK_HD inline Philox4 smp_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+  for (int r = 0; r < 10; ++r) {
+    if (r > 0) k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+    c0 = n0, c1 = n1, c2 = n2, c3 = n3;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+// the uniform of (seed, state, shot, site) in [0, 1): 53 bits from the first two words
+QK_HD inline double smp_uniform(const uint64_t seed, const uint32_t state, const uint32_t shot, const uint32_t site) {
+  const Philox4 r = smp_philox(site, shot, state, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return (double)(((uint64_t)(r.x[0] >> 5) << 26) + (uint64_t)(r.x[1] >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+// A shot chain is one (state, shot tile): `tile` = 16 m consecutive shots of a state, the last tile of a state ragged.  Its rows
+// are padded to R = a multiple of 16 and its slot is smp_size() P R doubles, P = the state's largest padded bond, every matrix as a
+// re plane then an im plane, offsets in units of P R:
+//   V  [P][R]   at smp_V()  = 0   the row vectors of the shots, K-major (bond index first): the A operand of SMP_W, ld = R
+//   W  [R][2P]  at smp_W()  = 2   (W_0 | W_1) of the rows, ld = 2 pad_{k+1}
+//   W' [P][2R]  at smp_Ws() = 6   the stacked operand [W'_0 ; W'_1], K-major: the A operand of SMP_Q, ld = 2 R
+//   Q  [2R][P]  at smp_Q()  = 10  ld = pad_{k+1}
+constexpr int SMP_TILE = 64;  // shots per tile (m = 4): one 64-row block of the ring GEMM
+QK_HD constexpr int smp_rows_pad(const int rows) { return (rows + LOC_CHUNK - 1) / LOC_CHUNK * LOC_CHUNK; }
+QK_HD constexpr int smp_V() { return 0; }
+QK_HD constexpr int smp_W() { return 2; }
+QK_HD constexpr int smp_Ws() { return 6; }
+QK_HD constexpr int smp_Q() { return 10; }
+QK_HD constexpr int smp_size() { return 14; }
+inline int smp_tiles(const int n_shots, const int tile) { return (n_shots + tile - 1) / tile; }
+// the environment pass of a sampling call: the reversed chain alone, every R_k kept (env_sizes with keep_l = false)
+inline Plan sample_env_plan(const int n) {
+  Plan plan;
+  plan_reverse(n, plan);
+  return plan;
+}
+constexpr int SMP_KINDS[4] = {SMP_W, SMP_ROT, SMP_Q, SMP_DRAW};  // the launches of a site, in stream order
+// the blocks of a shot chain of R padded rows (p = its state's padded bonds) in the launch `kind` of site k
+inline int smp_task_count(const int kind, const int k, const int32_t* p, const int R) {
+  switch (kind) {
+    case SMP_W: return (int)blocks64(R, 2ll * p[k + 1]);
+    case SMP_Q: return (int)blocks64(2ll * R, p[k + 1]);
+    default: return R / LOC_CHUNK;  // SMP_ROT, SMP_DRAW
+  }
+}
+struct SmpChains {  // the shot chains of a state batch, state-major in shot order
+  std::vector<int32_t> cent, shot0, rows;       // chain -> batch entry, first shot, shots
+  std::vector<long long> slot, ntasks, weight;  // doubles of its slot; its tasks over all launches; slot, tasks and table entries
+};
+inline SmpChains list_smp_chains(const EnvSizes& z, const int s0, const int nb, const int n_shots, const int tile) {
+  const int n = z.n_sites;
+  SmpChains c;
+  for (int i = 0; i < nb; ++i)
+    for (int t = 0; t < smp_tiles(n_shots, tile); ++t) {
+      const int rows = std::min(tile, n_shots - t * tile), R = smp_rows_pad(rows);
+      long long nt = 0;
+      for (int k = 0; k < n; ++k)
+        for (const int kind : SMP_KINDS) nt += smp_task_count(kind, k, &z.pad[(size_t)(s0 + i) * (n + 1)], R);
+      c.cent.push_back(i), c.shot0.push_back(t * tile), c.rows.push_back(rows);
+      c.slot.push_back((long long)smp_size() * z.pmax[s0 + i] * R), c.ntasks.push_back(nt);
+      c.weight.push_back(c.slot.back() + nt + 4);
+    }
+  return c;
+}
+// Task lists (chain of the batch, block) of the shot chains [c0, c0 + nc): launch 4k + j is SMP_KINDS[j] at site k.  The cut into
+// chain batches is chain_cut (QK_SAMPLE_BATCH caps the chains of one).
+inline void smp_lists(const EnvSizes& z, const int s0, const SmpChains& c, const size_t c0, const size_t nc, std::vector<Task2>& tasks, std::vector<long long>& first) {
+  const int n = z.n_sites;
+  tasks.clear(), first.clear();
+  for (int k = 0; k < n; ++k)
+    for (const int kind : SMP_KINDS) {
+      first.push_back((long long)tasks.size());
+      for (size_t e = 0; e < nc; ++e) {
+        const int nbk = smp_task_count(kind, k, &z.pad[(size_t)(s0 + c.cent[c0 + e]) * (n + 1)], smp_rows_pad(c.rows[c0 + e]));
+        for (int b = 0; b < nbk; ++b) tasks.push_back(Task2{(int)e, b});
+      }
+    }
+  first.push_back((long long)tasks.size());
+}
+// the first basis code outside 1..3 = X, Y, Z: its index, or -1
+inline long long smp_bad_basis(const uint8_t* bases, const long long count) {
+  for (long long e = 0; e < count; ++e)
+    if (bases[e] < 1 || bases[e] > 3) return e;
+  return -1;
 }
 
 }  // namespace qkl

@@ -107,6 +107,7 @@ _SIGNATURES = [
     ("qk_bond_spectra_host", C.c_int, [_P, _P, C.c_int32, _P, _P]),
     ("qk_block_values_host", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("qk_block_self_host", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("qk_sample_host", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint64, C.c_int64, _P, _P]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
@@ -236,6 +237,132 @@ def _pair_sites(n_pairs: int, max_dist: int):
         return None
     n, rem = divmod(int(n_pairs) + D * (D + 1) // 2, D)
     return n if rem == 0 and n >= D + 1 else None
+
+
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+BASIS_CODES = {"X": 1, "Y": 2, "Z": 3}
+
+
+def philox4x32(counter, key) -> np.ndarray:
+    """Philox4x32-10, vectorised: ``counter`` (..., 4) and ``key`` (..., 2) of 32-bit words (broadcast against each other over the
+    leading axes) give the four output words, uint32 of shape (..., 4).  Written out here, as in the library's kernels, so that the
+    host mirror and the device draw the same bits: ten rounds of
+        hi0:lo0 = 0xD2511F53 c0,  hi1:lo1 = 0xCD9E8D57 c2,  (c0, c1, c2, c3) <- (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0)
+    with (k0, k1) += (0x9E3779B9, 0xBB67AE85) mod 2^32 before each round after the first."""
+    c = np.asarray(counter, dtype=np.uint64)
+    k = np.asarray(key, dtype=np.uint64)
+    if c.shape[-1:] != (4,) or k.shape[-1:] != (2,):
+        raise ValueError(f"counter must end in 4 words and key in 2 (got shapes {c.shape}, {k.shape})")
+    mask = np.uint64(0xFFFFFFFF)
+    sh = np.uint64(32)
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., j] & mask, shape) for j in range(4))
+    k0, k1 = (np.broadcast_to(k[..., j] & mask, shape) for j in range(2))
+    for r in range(10):
+        if r > 0:
+            k0, k1 = (k0 + np.uint64(_PHILOX_W0)) & mask, (k1 + np.uint64(_PHILOX_W1)) & mask
+        p0, p1 = np.uint64(_PHILOX_M0) * c0, np.uint64(_PHILOX_M1) * c2
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ k0, p1 & mask, (p0 >> sh) ^ c3 ^ k1, p0 & mask
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def _seed_key(seed):
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"seed must be an int in 0 .. 2^64 - 1 (got {seed!r})")
+    return np.array([int(seed) & 0xFFFFFFFF, int(seed) >> 32], dtype=np.uint64)
+
+
+def _philox_stream(seed, state, shot, site, stream):
+    state, shot, site = np.broadcast_arrays(np.asarray(state, dtype=np.uint64), np.asarray(shot, dtype=np.uint64), np.asarray(site, dtype=np.uint64))
+    counter = np.stack([site, shot, state, np.full(site.shape, stream, dtype=np.uint64)], axis=-1)
+    return philox4x32(counter, _seed_key(seed))
+
+
+def sample_uniform(seed, state, shot, site):
+    """The uniform in [0, 1) that decides the outcome of qubit ``site`` in shot ``shot`` of the state with global index ``state``
+    (arrays broadcast): Philox counter (site, shot, state, 0), key (seed & 0xffffffff, seed >> 32),
+    u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 from the first two output words."""
+    x = _philox_stream(seed, state, shot, site, 0).astype(np.uint64)
+    return ((x[..., 0] >> np.uint64(5)) * np.uint64(1 << 26) + (x[..., 1] >> np.uint64(6))).astype(np.float64) * 2.0 ** -53
+
+
+def random_bases(shots: int, n_qubits: int, seed=0) -> np.ndarray:
+    """Random measurement bases of a randomised-measurement protocol: uint8 of shape (shots, n_qubits), codes 1..3 = X, Y, Z,
+    ``1 + (x0 % 3)`` of Philox stream 1 with counter (site, shot, 0, 1).  The first rows of a longer table are the shorter table."""
+    if int(shots) < 1 or int(n_qubits) < 1:
+        raise ValueError(f"shots and n_qubits must be >= 1 (got {shots!r}, {n_qubits!r})")
+    x = _philox_stream(seed, 0, np.arange(int(shots))[:, None], np.arange(int(n_qubits))[None, :], 1)
+    return (1 + x[..., 0] % np.uint32(3)).astype(np.uint8)
+
+
+def bases_table(bases, shots: int, n_qubits: int) -> np.ndarray:
+    """The uint8 table (shots, n_qubits) of basis codes that ``Context.sample`` and ``MPS.sample`` take: ``None`` is all Z, a string
+    over ``XYZ`` or a row of ``n_qubits`` codes is shared by every shot, an array (shots, n_qubits) is taken as it is.  Raises
+    ``ValueError`` that names ``bases`` for any other shape or letter; the codes themselves are checked where they are used."""
+    S, n = int(shots), int(n_qubits)
+    if bases is None:
+        return np.full((S, n), 3, dtype=np.uint8)
+    if isinstance(bases, str):
+        if len(bases) != n or any(ch not in BASIS_CODES for ch in bases.upper()):
+            raise ValueError(f"bases {bases!r} is not a string of {n} letters over XYZ")
+        bases = [BASIS_CODES[ch] for ch in bases.upper()]
+    b = np.asarray(bases)
+    if b.dtype.kind not in "iu" or b.shape not in ((n,), (S, n)):
+        raise ValueError(f"bases must be None, a string or integer row of length {n}, or an integer array of shape ({S}, {n}); got shape {b.shape}, dtype {b.dtype}")
+    if b.size and (b.min() < 0 or b.max() > 255):
+        raise ValueError(f"bases holds a code outside 1..3 = X, Y, Z ({int(b.min() if b.min() < 0 else b.max())})")
+    return np.ascontiguousarray(np.broadcast_to(b.astype(np.uint8), (S, n)))
+
+
+def _bits_and_bases(bits, bases):
+    bits = np.asarray(bits)
+    if bits.ndim != 3:
+        raise ValueError(f"bits must have shape (n_states, shots, n_qubits), got {bits.shape}")
+    B = bases_table(bases, bits.shape[1], bits.shape[2])
+    if B.size and (B.min() < 1 or B.max() > 3):
+        raise ValueError("bases holds a code outside 1..3 = X, Y, Z")
+    return 1 - 2 * bits.astype(np.int64), B
+
+
+def estimate_paulis(bits, bases):
+    """Bloch vectors estimated from measurement shots: ``(F_hat, counts)``.  ``bits`` is (n_states, shots, n_qubits) of
+    ``Context.sample`` and ``bases`` what it was drawn in.  ``F_hat[s, k, c]`` (n_states, n_qubits, 3) is the mean of ``1 - 2 bit``
+    over the shots with ``bases[shot, k] == c + 1``, and 0.0 where no shot has that basis; ``counts[k, c]`` (n_qubits, 3) is the
+    number of those shots.  The sums are integers, so the estimate does not depend on the order of the shots."""
+    sign, B = _bits_and_bases(bits, bases)
+    ns, _, n = sign.shape
+    F = np.zeros((ns, n, 3), dtype=np.float64)
+    counts = np.zeros((n, 3), dtype=np.int64)
+    for c in range(3):
+        mask = B == c + 1
+        counts[:, c] = mask.sum(axis=0)
+        tot = (sign * mask[None]).sum(axis=1)
+        F[:, :, c] = np.where(counts[:, c] > 0, tot / np.maximum(counts[:, c], 1), 0.0)
+    return F, counts
+
+
+def estimate_pair_paulis(bits, bases, max_dist: int = 1) -> np.ndarray:
+    """Pauli correlators estimated from measurement shots, in ``pair_table(n_qubits, max_dist)`` order: ``T_hat`` of shape
+    (n_states, n_pairs, 4, 4).  ``T[0][0] = 1.0`` exactly; ``T[p][0]`` and ``T[0][q]`` are the entries of ``estimate_paulis``;
+    ``T[p][q]`` is the mean of the product of the two signs over the shots whose bases on the two qubits are (p, q), and 0.0
+    where there is none."""
+    sign, B = _bits_and_bases(bits, bases)
+    ns, _, n = sign.shape
+    F, _ = estimate_paulis(bits, B)
+    pairs = pair_table(n, max_dist)
+    T = np.zeros((ns, len(pairs), 4, 4), dtype=np.float64)
+    for pi, (a, b) in enumerate(pairs):
+        T[:, pi, 0, 0] = 1.0
+        T[:, pi, 1:, 0] = F[:, a]
+        T[:, pi, 0, 1:] = F[:, b]
+        prod = sign[:, :, a] * sign[:, :, b]
+        for p in range(1, 4):
+            for q in range(1, 4):
+                mask = (B[:, a] == p) & (B[:, b] == q)
+                cnt = int(mask.sum())
+                if cnt:
+                    T[:, pi, p, q] = (prod * mask[None]).sum(axis=1) / cnt
+    return T
 
 
 def pauli_strings(n_sites: int, specs) -> np.ndarray:
@@ -1079,6 +1206,28 @@ class Context:
         nrm = np.zeros(ns, dtype=np.float64)
         _check(lib().qk_pauli_strings_host(self._h, mps_set.handle, S.shape[0], S.ctypes.data, V.ctypes.data, nrm.ctypes.data), "qk_pauli_strings_host")
         return (V, nrm) if norms else V
+
+    def sample(self, xs: MpsSet, shots: int, bases=None, seed: int = 0, first_state: int = 0, logp: bool = False):
+        """Measurement shots of every state of an fp64 set, by perfect sampling along the chain: ``bits``, uint8 of shape
+        (n_states, shots, n_sites), bit 0 = eigenvalue +1 of the Pauli the qubit was measured in.  ``bases`` is anything
+        ``bases_table`` takes (``None``: all Z; a string such as ``"ZZXY"`` or a row shared by every shot; an array (shots, n_sites)
+        of codes 1..3 = X, Y, Z, as ``random_bases`` makes).  With ``logp=True`` also the log of the exact probability of each
+        drawn string in its bases, float64 (n_states, shots), as ``(bits, logp)``.  The uniforms are ``sample_uniform(seed,
+        first_state + s, shot, site)``: the bits of a (state, shot) depend only on the seed, the state's global index, the shot, that
+        shot's bases and the state's tensors -- the first shots of a longer call are the shorter call, and a share of a data set
+        sampled with its offset as ``first_state`` gives the bits of the whole.  Synchronous."""
+        info = xs.info()
+        ns, n = info["n_states"], info["n_sites"]
+        if isinstance(shots, bool) or not isinstance(shots, (int, np.integer)):
+            raise ValueError(f"shots must be an int >= 1 (got {shots!r})")
+        S = int(shots)
+        B = None if bases is None else bases_table(bases, max(S, 0), n)
+        key = _seed_key(seed)
+        bits = np.zeros((ns, max(S, 0), n), dtype=np.uint8)
+        lp = np.zeros((ns, max(S, 0)), dtype=np.float64)
+        _check(lib().qk_sample_host(self._h, xs.handle, S, None if B is None else B.ctypes.data, int(key[0]) | (int(key[1]) << 32), int(first_state),
+                                    bits.ctypes.data, lp.ctypes.data), "qk_sample_host")
+        return (bits, lp) if logp else bits
 
     def bond_purities(self, mps_set: MpsSet, norms: bool = False):
         """Purity tr(rho^2) of the reduced state left of every bond, for every state of an fp64 set: float64 of shape (n_states,

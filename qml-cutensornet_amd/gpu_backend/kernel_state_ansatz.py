@@ -399,7 +399,8 @@ def _gather_features(comm, lo, F, total):
     return out
 
 
-def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30, rdm=1, pair_distance=1, observables=None):
+def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30, rdm=1, pair_distance=1, observables=None,
+                                  shots=None, shot_seed=0):
     """Projected quantum kernel (Huang et al., Nat. Commun. 12, 2631 (2021)) of the same states as ``build_kernel_matrix``:
         K[j, i] = exp(-g sum_k ||rho_k(X_i) - rho_k(Y_j)||_F^2) = exp(-g/2 sum_k |F(X_i)[k] - F(Y_j)[k]|^2),
     rho_k = the one-qubit reduced density matrix of qubit k, F[k] = its Bloch vector (<X_k>, <Y_k>, <Z_k>); ``Y=None`` means
@@ -420,8 +421,21 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     ``observables=[...]`` (Pauli strings, anything ``engine.pauli_strings(n_qubits, ...)`` takes) is the kernel on chosen observables,
         K[j, i] = exp(-g sum_m (<O_m>(X_i) - <O_m>(Y_j))^2),
     with ``pqk_gamma=None`` meaning g = 1 / len(observables): m reals per state are all-gathered.  It excludes ``rdm`` and
-    ``pair_distance`` (leave them at 1)."""
+    ``pair_distance`` (leave them at 1).
+
+    ``shots=S`` (with ``rdm=1`` or ``rdm=2``, any ``pair_distance``) is the kernel at S measurement shots per state instead of exact
+    expectation values: each rank samples its share in the random bases ``engine.random_bases(S, n_qubits, shot_seed)`` with
+    ``Context.sample(..., seed=shot_seed, first_state=<the share's offset>)`` (the states of Y are indexed after those of X) and
+    estimates the Bloch vectors (``engine.estimate_paulis``) or the correlators (``engine.estimate_pair_paulis``) from the bits; the
+    rest of the route is the same, and K is the same bits for any number of ranks.  ``shots=None`` is the exact kernel.
+    ``observables`` together with ``shots`` is a ``ValueError``."""
     strings = None
+    if shots is not None:
+        if observables is not None:
+            raise ValueError("shots together with observables is not supported: sample with rdm=1 or rdm=2")
+        if isinstance(shots, bool) or not isinstance(shots, (int, np.integer)) or shots < 1:
+            raise ValueError(f"shots must be None or an int >= 1 (got {shots!r})")
+        shots = int(shots)
     if observables is not None:
         if rdm != 1 or pair_distance != 1:
             raise ValueError(f"observables chooses the features itself: leave rdm and pair_distance at 1 (got rdm={rdm!r}, pair_distance={pair_distance!r})")
@@ -482,6 +496,10 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         else:
             if strings is not None:
                 F = ctx.pauli_expectations(local, strings)
+            elif shots is not None:
+                shot_bases = _engine.random_bases(shots, n_qubits, shot_seed)
+                bits = ctx.sample(local, shots, bases=shot_bases, seed=shot_seed, first_state=int(lo) + (0 if label == "X" else len(X)))
+                F = _engine.estimate_paulis(bits, shot_bases)[0] if rdm == 1 else _engine.estimate_pair_paulis(bits, shot_bases, pair_distance)
             else:
                 F = ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local, max_dist=pair_distance)
             chi = local.dims.max(axis=1)
@@ -526,6 +544,8 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         prof["pqk_rdm"] = [rdm, "qubits"]
     if rdm == 2:
         prof["pqk_pair_distance"] = [pair_distance, "sites"]
+    if shots is not None:
+        prof["pqk_shots"] = [shots, "shots"]
     prof["pqk_features_time"] = [feat_secs, "seconds"]
     prof["kernel_mat_time"] = [tiles, "seconds"]
     prof["total_time"] = [time.perf_counter() - t_start, "seconds"]

@@ -183,6 +183,56 @@ class MPS:
         W = E.T @ V.conj()          # W[a][a'] = sum_b' E[b'][a] conj(V[b'][a'])
         return float((envs[0] * W.conj()).sum().real) / (norms[0] * norms[1])
 
+    def sample(self, shots: int, bases=None, seed: int = 0, state_index: int = 0, logp: bool = False, margin: bool = False):
+        """Measurement shots of the state on the host, the numpy mirror of ``Context.sample``: ``bits`` uint8 (shots, n), bit 0 =
+        eigenvalue +1 of the Pauli (``bases``, anything ``engine.bases_table`` takes; codes 1..3 = X, Y, Z) the qubit was measured
+        in.  The right environments ``R_k`` come from the loop of the other mirrors; then per shot, v = [1], for k = 0 .. n-1:
+        ``W_t = v A_k[:, t, :]``, rotated into the basis (Z: as it is; X: (W_0 +- W_1)/sqrt2; Y: (W_0 -+ i W_1)/sqrt2),
+        ``p_o = max(0, Re W'_o R_{k+1} W'_o^H)``, ``bit = 1 if p_1 > 0 and u (p_0 + p_1) >= p_0`` with ``u =
+        engine.sample_uniform(seed, state_index, shot, k)``, ``v = W'_bit / sqrt(p_bit)``.  ``logp=True`` adds the log of the exact
+        probability of each drawn string, ``margin=True`` the smallest ``|u tot - p_0| / tot`` over all draws (how far the nearest
+        draw sat from its threshold): the result is ``bits`` or the tuple ``(bits[, logp][, margin])``.  A state of norm 0 raises
+        ``ValueError``."""
+        from .engine import bases_table, sample_uniform
+
+        n = len(self.tensors)
+        if isinstance(shots, bool) or not isinstance(shots, (int, np.integer)) or shots < 1:
+            raise ValueError(f"shots must be an int >= 1 (got {shots!r})")
+        S = int(shots)
+        B = bases_table(bases, S, n)
+        if B.min() < 1 or B.max() > 3:
+            raise ValueError("bases holds a code outside 1..3 = X, Y, Z")
+        ts = [np.asarray(t, dtype=np.complex128) for t in self.tensors]
+        R = [None] * (n + 1)  # R[ket][bra] at bond k
+        R[n] = np.ones((1, 1), dtype=np.complex128)
+        for k in range(n - 1, 0, -1):
+            R[k] = np.einsum("asc,cd,bsd->ab", ts[k], R[k + 1], ts[k].conj(), optimize=True)
+        u = sample_uniform(seed, state_index, np.arange(S)[:, None], np.arange(n)[None, :])
+        h = 0.70710678118654752440
+        v = np.ones((S, 1), dtype=np.complex128)
+        bits = np.zeros((S, n), dtype=np.uint8)
+        lp = np.zeros(S, dtype=np.float64)
+        worst = np.inf
+        for k in range(n):
+            W = np.einsum("rb,btc->rtc", v, ts[k])
+            W0, W1 = W[:, 0], W[:, 1]
+            code = B[:, k][:, None]
+            A0 = np.where(code == 1, (W0 + W1) * h, np.where(code == 2, (W0 - 1j * W1) * h, W0))
+            A1 = np.where(code == 1, (W0 - W1) * h, np.where(code == 2, (W0 + 1j * W1) * h, W1))
+            p0 = np.maximum(0.0, np.einsum("rb,ba,ra->r", A0, R[k + 1], A0.conj()).real)
+            p1 = np.maximum(0.0, np.einsum("rb,ba,ra->r", A1, R[k + 1], A1.conj()).real)
+            tot = p0 + p1
+            if not (np.all(tot > 0.0) and np.all(np.isfinite(tot))):
+                raise ValueError(f"sample: the outcome probabilities of site {k} sum to 0 or are not finite (a state of norm 0?)")
+            bit = (p1 > 0.0) & (u[:, k] * tot >= p0)
+            worst = min(worst, float(np.min(np.abs(u[:, k] * tot - p0) / tot)))
+            pb = np.where(bit, p1, p0)
+            lp += np.log(pb / tot)
+            v = np.where(bit[:, None], A1, A0) / np.sqrt(pb)[:, None]
+            bits[:, k] = bit
+        out = (bits,) + ((lp,) if logp else ()) + ((worst,) if margin else ())
+        return out if len(out) > 1 else bits
+
     def vdot(self, other: "MPS") -> complex:
         """<self|other> through the HIP engine (single pair; the Gram path is batch-first)."""
         from .engine import default_context

@@ -13,8 +13,10 @@ compressed_max_bond, min_fidelity and max_abs_dK = max |K(compressed) - K|.
 ``--block-widths 10,20,30,60`` adds the block kernels of the first w qubits: ctx.block_values_host on the symmetric plan of all
 pairs and ctx.block_self(xs, widths): block_values_ms, block_self_ms, n_widths, block_over_gram and, per width, the median
 off-diagonal entry of the "normalized" kernel.
+``--shots S`` adds ctx.sample(xs, S, bases=engine.random_bases(S, n, 0)): sample_ms, shots, sample_flops (the two GEMMs of every
+site for every shot, from the true bonds) and sample_tflops, and the median off-diagonal entry of the kernel estimated from the shots.
 usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement] [--compress CHI]
-                                [--block-widths W1,W2,...]"""
+                                [--block-widths W1,W2,...] [--shots S]"""
 import argparse
 import json
 import os
@@ -59,6 +61,14 @@ def dist_sweep_flops(dims, D):
     return total
 
 
+def sample_flops(dims, shots):
+    """Algorithmic flops of sampling ``shots`` shots of every state from the true bonds (8 per complex multiply-add).  Per site and
+    shot, l = chi_k, r = chi_k+1: the row of W = V (A^0 | A^1) (1 x 2r over l) and the two rows of Q = [W'_0 ; W'_1] R (2 x r over r)."""
+    d = np.asarray(dims, dtype=np.float64)
+    l, r = d[:, :-1], d[:, 1:]
+    return float(shots * (8 * (2 * r * l) + 8 * (2 * r * r)).sum())
+
+
 def sparse_strings(n, count, seed=0):
     """``count`` sparse strings on n qubits: weight 1..4 inside a window of 6 sites at a random position, random codes X, Y, Z."""
     rng = np.random.default_rng(seed)
@@ -91,6 +101,7 @@ def main():
     ap.add_argument("--entanglement", action="store_true", help="also time bond_purities and bond_spectra and print the cost of a bond cap")
     ap.add_argument("--compress", type=int, default=0, metavar="CHI", help="also time compress(max_bond=CHI) and the Gram of the compressed set")
     ap.add_argument("--block-widths", default=None, metavar="W1,W2,...", help="also time the block kernels of the first w qubits for these widths")
+    ap.add_argument("--shots", type=int, default=0, metavar="S", help="also time sample() with S shots per state in random bases")
     args = ap.parse_args()
     gamma = args.gamma if args.gamma is not None else (0.1 if args.config == "cfg5" else 1.0)
     n, reps, d, npts = bench.CONFIGS[args.config]
@@ -176,6 +187,16 @@ def main():
             "block_widths": widths, "n_widths": len(widths), "block_values_ms": round(block_ms, 3), "block_self_ms": round(self_ms, 3),
             "block_over_gram": round(block_ms / gram_ms, 4),
             "median_offdiag_block_normalized": {str(w): float(np.median(norm[wi][offd])) for wi, w in enumerate(widths)},
+        })
+    if args.shots > 0:
+        bases = engine.random_bases(args.shots, n, 0)
+        bits, sample_ms = timed(lambda: ctx.sample(xs, args.shots, bases=bases, seed=0), args.reps)
+        sflops = sample_flops(info["dims"], args.shots)
+        KS = ctx.projected_gram(engine.estimate_paulis(bits, bases)[0])
+        dist.update({
+            "shots": int(args.shots), "sample_ms": round(sample_ms, 3), "sample_flops": sflops,
+            "sample_tflops": round(sflops / (sample_ms * 1e-3) / 1e12, 3), "sample_over_local": round(sample_ms / local_ms, 4),
+            "median_offdiag_pqk_shots": float(np.median(KS[off])),
         })
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
