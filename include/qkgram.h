@@ -473,6 +473,42 @@ int qk_sample_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_shots, const ui
                    uint64_t seed, int64_t first_state /* global index of state 0 */, uint8_t* bits /* [n_states][n_shots][n_sites] */,
                    double* logp /* [n_states][n_shots], may be NULL */);
 
+/* ---- block overlaps at finite shots: the randomised-measurement estimator -------------------------------------------------------
+ * qk_shot_block_sums_host: the integer sums of the randomised-measurement overlap (Elben et al., PRL 124, 010504 (2020)) of two
+ * outcome tables, for the first (side 0) or last (side 1) w qubits and every w of widths, from the same shot pairs.  It needs no
+ * MPS set: it works on any outcome tables, such as the bits of qk_sample_host.
+ * Shots.  There are U settings of M shots each.  The shot index is u M + a.  All M shots of setting u were measured in the same
+ * bases (row u of the caller's bases table), and every state of X and Y in the same table.
+ * Packed word of a shot.  It holds the block's qubits, at most 32 of them.  side = left: bit k of the word is bits[k], for
+ * k < min(n, 32).  side = right: bit k is bits[n-1-k].  Other bits of the word are 0.  Widths are 1 <= w <= min(n, 32), strictly
+ * increasing.
+ *     D_w(s, s')  = popcount((s xor s') & (2^w - 1))                 (w = 32: the whole word; no shift by 32)
+ *     term_w      = (-1)^D_w 2^(w - D_w)                             an integer in [-2^(w-1), 2^w]
+ *     S_u[w][p]   = sum_{a,b < M} term_w(X[i][uM+a], Y[j][uM+b])  -  [p is a self pair] M 2^w
+ *     sums[w][p]  = sum_u S_u[w][p]                                  int64, exact
+ *     N           = M^2  (cross pair),   M (M - 1)  (self pair: Y is X and i == j; the a == b terms are removed)
+ *     O^_w        = sums / (U N)
+ *     stderr_w    = std over u of S_u / N (ddof = 1) / sqrt(U)       (U >= 2, else nan)
+ * E[O^_w] = O_w = tr(rho_A(x_i) rho_A(y_j)) exactly for bases drawn uniformly from X, Y, Z per setting and qubit: averaging Z(x)Z
+ * over the three gives (XX + YY + ZZ) / 3, so the per-qubit weight (1 + 3 z z') / 2 averages to SWAP.  A self pair needs M >= 2.  In
+ * a call with bits_y given, equal indices are not a self pair.
+ * Overflow rule: U M^2 2^w_max <= 2^62, else QK_EINVAL.
+ * A pack kernel makes the words (one lane per (state, shot)); the sums kernel takes one workgroup per (pair, chunk of settings),
+ * x words in registers, y words staged in LDS, and writes S_u; a second kernel adds over the settings.  Everything is integer
+ * arithmetic: the result is exact and does not depend on any order, batch cut or run.  Device scratch: the words (4 bytes per
+ * shot), and per pair batch n_widths U int64 per pair in the context's local scratch (qk_ctx_trim releases it), by the batching rule
+ * of qk_local_paulis_host (a quarter of the free memory; pairs go in batches when they do not fit).  Synchronous; leaves the Gram
+ * statistics alone.
+ * QK_EINVAL: a null ctx, bits_x, pairs, widths or sums; n_sites, n_settings, shots_per_setting, nx, ny, n_pairs or n_widths below 1;
+ * bits_y NULL with ny != nx; a pair index outside its table; a self pair with shots_per_setting 1; side not 0 or 1; widths not
+ * strictly increasing in 1 .. min(n_sites, 32); the overflow rule (the message names the three numbers); a byte other than 0 or 1
+ * among the block's qubits (the message names bits_x or bits_y).                                                                  */
+int qk_shot_block_sums_host(qk_ctx* ctx, int32_t n_sites, int32_t n_settings, int32_t shots_per_setting,
+                            int32_t nx, const uint8_t* bits_x /* [nx][U*M][n_sites] */, int32_t ny, const uint8_t* bits_y /* NULL: Y is X */,
+                            int64_t n_pairs, const int32_t* pairs /* [n_pairs][2] = (x index, y index), any order, duplicates allowed */,
+                            int32_t side, int32_t n_widths, const int32_t* widths,
+                            int64_t* sums /* [n_widths][n_pairs] */, int64_t* per_setting /* [n_widths][n_pairs][U], may be NULL */);
+
 /* ---- compressing a set: one canonical truncation sweep per state -------------------------------------------------------------
  * qk_mps_set_compress: *out = a new fp64 set of the same context that owns its memory, every state of src truncated ONCE on its
  * final tensors; src is left untouched.  One workgroup per state (workgroup b takes states b, b + grid, ...), two passes over the

@@ -7,7 +7,8 @@
 // qk_bond_purities_host and qk_bond_spectra_host (definitions above bond_call below), and the block kernels -- reduced-state
 // overlaps of the first or last w qubits for every pair of two sets -- qk_block_values_host and qk_block_self_host (definitions
 // above BlkSet below), and measurement shots of every state of a set, each shot and qubit in its own Pauli basis, qk_sample_host
-// (definitions above SmpArgs below) (include/qkgram.h).
+// (definitions above SmpArgs below), and the block overlaps estimated from such shots, qk_shot_block_sums_host (above SbkArgs below)
+// (include/qkgram.h).
 //
 // Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
 // normalised):
@@ -1611,7 +1612,247 @@ int sample_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_shots, const ui
   return QK_OK;
 }
 
+// ---- block overlaps from measurement shots (qk_shot_block_sums_host) -----------------------------------------------------------------
+// The randomised-measurement overlap (Elben et al., PRL 124, 010504 (2020)) of outcome tables bits[state][u M + a][site], U settings
+// of M shots: all integer arithmetic, definitions in include/qkgram.h, host side in qk_local_plan.h (sbk_*).
+//   qk_sbk_pack_kernel  one lane per (state, shot): the block's bytes into one word (sbk_pack); a byte that is neither 0 nor 1 raises *bad.
+//   qk_sbk_sums_kernel  one workgroup (four waves) per task = (pair, chunk of settings).  The y words of the chunk are staged in
+//       LDS, a row per setting.  Inside a setting a wave takes (block of 64 x words, piece of the y row) units: each lane keeps its
+//       x word in a register and every lane reads the same y words (ds_read_b128 of one address: a broadcast, conflict-free).
+//       Per (a, b, width): one bit operation for the agreeing bits, v_bcnt (which adds the exponent bias), two more for the high word
+//       of the term as a double (sbk_agree_hi) and one v_add_f64 -- exact, because a lane's partial sum is moved into its int64
+//       total before 2^20 terms of at most 2^32 have gone into it.  Accumulating int64 terms instead (a 64-bit shift, a select and
+//       a two-instruction add) measured 1.44 times slower on the MI355X at M = 64 and four widths, with the same sums.  At the end of a
+//       setting the lane totals are added across the wave (shuffles), the four wave sums meet in LDS, and after the chunk one
+//       thread per (setting, width) adds them and writes S_u, less M 2^w for a self pair.
+//   qk_sbk_total_kernel one thread per (width, pair): the sum of its S_u over the settings.
+// Integer sums are exact and order-free; nothing is atomic, no workgroup waits for another.
+constexpr int SBK_THREADS = 256, SBK_WAVES = SBK_THREADS / 64;
+struct SbkArgs {
+  const uint32_t* xw;    // packed words [nx][U M]
+  const uint32_t* yw;    // [ny][U M]; the x words when Y is X
+  const int32_t* pairs;  // the batch's pairs (x index, y index)
+  long long* S;          // per-setting sums of the batch [n_widths][nb][U]
+  uint32_t mask[SBK_GROUP];  // of this launch's widths
+  int32_t width[SBK_GROUP];
+  int w0;                // index of the launch's first width in the call's list
+  int self;              // Y is X: a pair (i, i) is a self pair
+  int U, M, chunk;
+  long long nb, task0;   // pairs of the batch; first task of the launch
+};
+
+__global__ __launch_bounds__(256) void qk_sbk_pack_kernel(const uint8_t* bits, const long long count, const int n, const int side, uint32_t* words, int32_t* bad) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= count) return;
+  bool b = false;
+  words[e] = sbk_pack(bits + e * n, n, side, b);
+  if (b) *bad = 1;
+}
+
+template <int NW>
+__global__ __launch_bounds__(SBK_THREADS) void qk_sbk_sums_kernel(const SbkArgs g) {
+  __shared__ __attribute__((aligned(16))) uint32_t ys[SBK_STAGE_WORDS];
+  __shared__ long long red[SBK_MAX_CHUNK][SBK_WAVES][NW];
+  long long pair;
+  int u0, u1;
+  sbk_task(g.task0 + blockIdx.x, g.U, g.chunk, pair, u0, u1);
+  const int M = g.M, nset = u1 - u0;
+  const long long UM = (long long)g.U * M;
+  const int xi = g.pairs[2 * pair], yj = g.pairs[2 * pair + 1];
+  const uint32_t* const X = g.xw + xi * UM;
+  const uint32_t* const Y = g.yw + yj * UM;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int row = min(M, SBK_STAGE_WORDS), ldr = sbk_round4(row);  // staged words of a setting at a time (nset == 1 when M is longer)
+  const int parts = sbk_parts(M), units = sbk_a_blocks(M) * parts;
+  long long tot[NW];
+  double acc[NW];
+  int since = 0;  // terms in acc since it was last moved into tot (the same for every lane of the wave)
+  for (int b0 = 0; b0 < M; b0 += SBK_STAGE_WORDS) {
+    const int bn = min(SBK_STAGE_WORDS, M - b0);
+    __syncthreads();
+    for (int e = threadIdx.x; e < nset * bn; e += SBK_THREADS) ys[(e / bn) * ldr + e % bn] = Y[(long long)(u0 + e / bn) * M + b0 + e % bn];
+    __syncthreads();
+    for (int s = 0; s < nset; ++s) {
+      if (b0 == 0) {
+#pragma unroll
+        for (int v = 0; v < NW; ++v) tot[v] = 0, acc[v] = 0.0;
+      }
+      const uint32_t* const yr = ys + s * ldr;
+      for (int unit = wv; unit < units; unit += SBK_WAVES) {
+        const int a = (unit / parts) * 64 + lane, pc = unit % parts;
+        const int lo = sbk_part_lo(pc, parts, bn), hi = sbk_part_lo(pc + 1, parts, bn);
+        if (since + SBK_STAGE_WORDS > (1 << 20)) {
+#pragma unroll
+          for (int v = 0; v < NW; ++v) tot[v] += (long long)acc[v], acc[v] = 0.0;
+          since = 0;
+        }
+        since += hi - lo;
+        if (a < M) {
+          const uint32_t x = X[(long long)(u0 + s) * M + a];
+          auto add = [&](const uint32_t y) {
+            const uint32_t same = ~(x ^ y);
+#pragma unroll
+            for (int v = 0; v < NW; ++v) acc[v] += __hiloint2double((int)sbk_agree_hi(__popc(same & g.mask[v]) + 1023u), 0);
+          };
+          int b = lo;
+          for (; b + 4 <= hi; b += 4) {
+            const uint4 y4 = *reinterpret_cast<const uint4*>(yr + b);
+            add(y4.x), add(y4.y), add(y4.z), add(y4.w);
+          }
+          for (; b < hi; ++b) add(yr[b]);
+        }
+      }
+      if (b0 + bn == M) {  // the setting is complete: lane totals -> wave sum
+#pragma unroll
+        for (int v = 0; v < NW; ++v) {
+          long long t = tot[v] + (long long)acc[v];
+          for (int h = 32; h > 0; h >>= 1) t += __shfl_xor(t, h, 64);
+          if (lane == 0) red[s][wv][v] = sbk_agree_sign(g.width[v]) * t;
+        }
+        since = 0;
+      }
+    }
+  }
+  __syncthreads();
+  const bool self_pair = g.self && xi == yj;
+  for (int e = threadIdx.x; e < nset * NW; e += SBK_THREADS) {
+    const int s = e / NW, v = e % NW;
+    long long t = 0;
+    for (int k = 0; k < SBK_WAVES; ++k) t += red[s][k][v];
+    if (self_pair) t -= (long long)M << g.width[v];
+    g.S[((long long)(g.w0 + v) * g.nb + pair) * g.U + u0 + s] = t;
+  }
+}
+
+__global__ __launch_bounds__(256) void qk_sbk_total_kernel(const long long* S, const int nw, const long long nb, const int U, const long long pair0, const long long n_pairs,
+                                                           long long* sums) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= nw * nb) return;
+  const long long v = e / nb, p = e % nb;
+  const long long* s = S + e * U;
+  long long t = 0;
+  for (int u = 0; u < U; ++u) t += s[u];
+  sums[v * n_pairs + pair0 + p] = t;
+}
+
+template <int NW>
+void sbk_launch(const SbkArgs& q, const unsigned grid, hipStream_t stream) {
+  qk_sbk_sums_kernel<NW><<<dim3(grid), dim3(SBK_THREADS), 0, stream>>>(q);
+}
+
+// the packed words of one outcome table, uploaded in pieces of whole states that fit `room` bytes (at least one state)
+int sbk_pack_table(qk_ctx* c, const char* what, const char* name, const uint8_t* bits, const int ns, const long long UM, const int n, const int side, const long long room,
+                   uint32_t* words, int32_t* d_bad) {
+  const long long per_state = UM * n, piece = std::max(1ll, std::min((long long)ns, room / per_state));
+  QkDevBuf stage;
+  HIP_TRY_AS(what, stage.alloc((size_t)(piece * per_state)));
+  for (long long s0 = 0; s0 < ns; s0 += piece) {
+    const long long cnt = std::min(piece, ns - s0) * UM;
+    HIP_TRY_AS(what, hipMemcpyAsync(stage.get(), bits + s0 * per_state, (size_t)(cnt * n), hipMemcpyHostToDevice, c->stream));
+    qk_sbk_pack_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream>>>(stage.get<uint8_t>(), cnt, n, side, words + s0 * UM, d_bad);
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the stage is reused by the next piece
+  }
+  int32_t bad = 0;
+  HIP_TRY_AS(what, hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost));
+  if (bad) return qk_fail(QK_EINVAL, "%s: %s holds a bit other than 0 or 1 among the block's qubits", what, name);
+  return QK_OK;
+}
+
+int shot_block_sums(qk_ctx* c, const int32_t n, const int32_t U, const int32_t M, const int32_t nx, const uint8_t* bits_x, const int32_t ny, const uint8_t* bits_y,
+                    const int64_t n_pairs, const int32_t* pairs, const int32_t side, const int32_t nw, const int32_t* widths, int64_t* sums, int64_t* per_setting) {
+  static const char* what = "qk_shot_block_sums_host";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!bits_x) return qk_fail(QK_EINVAL, "%s: bits_x is null", what);
+  if (!pairs) return qk_fail(QK_EINVAL, "%s: pairs is null", what);
+  if (!widths) return qk_fail(QK_EINVAL, "%s: widths is null", what);
+  if (!sums) return qk_fail(QK_EINVAL, "%s: sums is null", what);
+  if (n < 1) return qk_fail(QK_EINVAL, "%s: n_sites must be >= 1 (got %d)", what, n);
+  if (U < 1) return qk_fail(QK_EINVAL, "%s: n_settings must be >= 1 (got %d)", what, U);
+  if (M < 1) return qk_fail(QK_EINVAL, "%s: shots_per_setting must be >= 1 (got %d)", what, M);
+  if (nx < 1) return qk_fail(QK_EINVAL, "%s: nx must be >= 1 (got %d)", what, nx);
+  if (ny < 1) return qk_fail(QK_EINVAL, "%s: ny must be >= 1 (got %d)", what, ny);
+  if (!bits_y && ny != nx) return qk_fail(QK_EINVAL, "%s: Y is X (bits_y is null) but ny %d != nx %d", what, ny, nx);
+  if (n_pairs < 1) return qk_fail(QK_EINVAL, "%s: n_pairs must be >= 1 (got %lld)", what, (long long)n_pairs);
+  if (side != 0 && side != 1) return qk_fail(QK_EINVAL, "%s: side must be 0 (left) or 1 (right) (got %d)", what, side);
+  if (nw < 1) return qk_fail(QK_EINVAL, "%s: n_widths must be >= 1 (got %d)", what, nw);
+  if (const int bad = sbk_bad_width(nw, widths, n); bad >= 0)
+    return qk_fail(QK_EINVAL, "%s: widths[%d] = %d: widths must be strictly increasing in 1 .. min(n_sites, 32) = %d", what, bad, widths[bad], std::min(n, SBK_MAX_WIDTH));
+  if (!sbk_fits(U, M, widths[nw - 1]))
+    return qk_fail(QK_EINVAL, "%s: n_settings %d x shots_per_setting %d ^2 x 2^%d (the largest of widths) exceeds 2^62: the sums would not fit an int64", what, U, M,
+                   widths[nw - 1]);
+  const bool self = !bits_y;
+  for (long long e = 0; e < n_pairs; ++e) {
+    const int i = pairs[2 * e], j = pairs[2 * e + 1];
+    if (i < 0 || i >= nx || j < 0 || j >= ny) return qk_fail(QK_EINVAL, "%s: pairs[%lld] is (%d, %d), the tables hold %d x %d states", what, e, i, j, nx, ny);
+    if (self && i == j && M < 2) return qk_fail(QK_EINVAL, "%s: pairs[%lld] is the self pair (%d, %d): it needs shots_per_setting >= 2", what, e, i, j);
+  }
+  QkRangeGuard range_("qk:shot_block_sums");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  const long long UM = (long long)U * M;
+  QkDevBuf words, dsums, dbad;
+  HIP_TRY_AS(what, words.alloc((size_t)((long long)(nx + (self ? 0 : ny)) * UM) * sizeof(uint32_t)));
+  HIP_TRY_AS(what, dsums.alloc((size_t)nw * n_pairs * sizeof(int64_t)));
+  HIP_TRY_AS(what, dbad.alloc(sizeof(int32_t)));
+  HIP_TRY_AS(what, hipMemset(dbad.get(), 0, sizeof(int32_t)));
+  // memory bound of the staged outcome bytes and of a pair batch: a quarter of what is free once the words and the sums exist
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  const long long room = budget * (long long)sizeof(double);
+  uint32_t* const xw = words.get<uint32_t>();
+  uint32_t* const yw = self ? xw : xw + (long long)nx * UM;
+  if (const int rc = sbk_pack_table(c, what, "bits_x", bits_x, nx, UM, n, side, room, xw, dbad.get<int32_t>())) return rc;
+  if (!self)
+    if (const int rc = sbk_pack_table(c, what, "bits_y", bits_y, ny, UM, n, side, room, yw, dbad.get<int32_t>())) return rc;
+
+  const int chunk = sbk_chunk(U, M, n_pairs), nchunks = sbk_n_chunks(U, chunk);
+  const long long batch = std::min((long long)n_pairs, sbk_batch_pairs(room, nw, U));
+  SbkArgs q{};
+  q.xw = xw, q.yw = yw, q.self = self, q.U = U, q.M = M, q.chunk = chunk;
+  for (long long p0 = 0; p0 < n_pairs; p0 += batch) {
+    const long long nb = std::min(batch, n_pairs - p0);
+    // one device buffer for the pair batch: [pairs | per-setting sums]
+    const size_t b_pairs = al256((size_t)(2 * nb) * sizeof(int32_t)), b_S = (size_t)nw * nb * U * sizeof(int64_t);
+    HIP_TRY_AS(what, c->local_scratch.ensure(b_pairs + b_S));
+    char* const base = c->local_scratch.get<char>();
+    q.pairs = reinterpret_cast<const int32_t*>(base);
+    q.S = reinterpret_cast<long long*>(base + b_pairs);
+    q.nb = nb;
+    HIP_TRY_AS(what, hipMemcpyAsync(base, pairs + 2 * p0, (size_t)(2 * nb) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    for (int at = 0; at < nw; at += sbk_group(nw, at)) {
+      const int cnt = sbk_group(nw, at);
+      q.w0 = at;
+      for (int v = 0; v < cnt; ++v) q.mask[v] = sbk_mask(widths[at + v]), q.width[v] = widths[at + v];
+      for (long long t0 = 0; t0 < nb * nchunks; t0 += SBK_LAUNCH_TASKS) {
+        q.task0 = t0;
+        const unsigned grid = (unsigned)std::min((long long)SBK_LAUNCH_TASKS, nb * nchunks - t0);
+        if (cnt == 8) sbk_launch<8>(q, grid, c->stream);
+        else if (cnt == 4) sbk_launch<4>(q, grid, c->stream);
+        else if (cnt == 2) sbk_launch<2>(q, grid, c->stream);
+        else sbk_launch<1>(q, grid, c->stream);
+      }
+      HIP_TRY_AS(what, hipGetLastError());
+    }
+    qk_sbk_total_kernel<<<dim3((unsigned)((nw * nb + 255) / 256)), dim3(256), 0, c->stream>>>(q.S, nw, nb, U, p0, n_pairs, dsums.get<long long>());
+    HIP_TRY_AS(what, hipGetLastError());
+    if (per_setting)
+      for (int v = 0; v < nw; ++v)
+        HIP_TRY_AS(what, hipMemcpyAsync(per_setting + ((long long)v * n_pairs + p0) * U, q.S + (long long)v * nb * U, (size_t)(nb * U) * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                        c->stream));
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the batch's buffer is reused by the next batch
+  }
+  HIP_TRY_AS(what, hipMemcpy(sums, dsums.get(), (size_t)nw * n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost));
+  return QK_OK;
+}
+
 }  // namespace
+
+extern "C" int qk_shot_block_sums_host(qk_ctx* c, int32_t n_sites, int32_t n_settings, int32_t shots_per_setting, int32_t nx, const uint8_t* bits_x, int32_t ny,
+                                       const uint8_t* bits_y, int64_t n_pairs, const int32_t* pairs, int32_t side, int32_t n_widths, const int32_t* widths, int64_t* sums,
+                                       int64_t* per_setting) {
+  return shot_block_sums(c, n_sites, n_settings, shots_per_setting, nx, bits_x, ny, bits_y, n_pairs, pairs, side, n_widths, widths, sums, per_setting);
+}
 
 extern "C" int qk_sample_host(qk_ctx* c, const qk_mps_set* set, int32_t n_shots, const uint8_t* bases, uint64_t seed, int64_t first_state, uint8_t* bits, double* logp) {
   return sample_run(c, set, n_shots, bases, seed, first_state, bits, logp);

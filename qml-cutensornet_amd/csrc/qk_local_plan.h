@@ -1,6 +1,6 @@
 // qk_local_plan.h -- the host-side plan of the local sweeps (qk_local.hip): the launch kinds, the scratch layout, the pair index, the
-// sizes and the cut into state batches, the tables and task lists of a batch, the plans of the entry points and the chain side of the
-// Pauli strings.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
+// sizes and the cut into state batches, the tables and task lists of a batch, the plans of the entry points, the chain side of the
+// Pauli strings and the integer side of the shot-based block overlaps.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
 // -fsanitize=address,undefined); the few functions the kernels also call are QK_HD.
 #pragma once
 #include "qk_plan.h"
@@ -498,6 +498,71 @@ inline long long smp_bad_basis(const uint8_t* bases, const long long count) {
   for (long long e = 0; e < count; ++e)
     if (bases[e] < 1 || bases[e] > 3) return e;
   return -1;
+}
+
+// ---- block overlaps from measurement shots (qk_shot_block_sums_host) -----------------------------------------------------------------
+// U settings of M shots, shot u M + a in setting u; a shot's block bits are packed into one 32-bit word, and a pair's sums are
+//     D_w(s, s') = popcount((s xor s') & mask(w)),   term_w = (-1)^D_w 2^(w - D_w),   S_u[w] = sum_{a, b < M} term_w(x[u M + a], y[u M + b])
+// less M 2^w for a self pair (definitions in include/qkgram.h).  A task is one pair and a chunk of consecutive settings.
+constexpr int SBK_MAX_WIDTH = 32;      // qubits of a packed word
+constexpr int SBK_STAGE_WORDS = 4096;  // y words a workgroup stages in LDS at a time (16 KiB)
+constexpr int SBK_MAX_CHUNK = 64;      // settings of a task: bounds the workgroup's table of per-setting wave sums
+constexpr int SBK_GROUP = 8;           // widths of one launch
+constexpr int SBK_LAUNCH_TASKS = 2048; // tasks of one launch: eight workgroups per CU, so no launch runs long on a shared device
+QK_HD constexpr uint32_t sbk_mask(const int w) { return w >= 32 ? 0xffffffffu : (1u << w) - 1u; }  // (no shift by 32)
+QK_HD constexpr long long sbk_term(const int D, const int w) { return (D & 1) ? -(1ll << (w - D)) : (1ll << (w - D)); }
+// The kernel counts the agreeing bits A = w - D = popcount(~(s xor s') & mask(w)) and adds doubles built from E = 1023 + A alone:
+// the high word (E << 20) | (E << 31) (low word 0) is the double (-1)^E 2^A = -(-1)^A 2^A, and term_w = sbk_agree_sign(w) times it.
+QK_HD constexpr uint32_t sbk_agree_hi(const uint32_t E) { return E << 20 | E << 31; }
+QK_HD constexpr int sbk_agree_sign(const int w) { return (w & 1) ? 1 : -1; }
+QK_HD constexpr int sbk_round4(const int v) { return (v + 3) & ~3; }
+// The packed word of a shot: bit k = bits[k] (side 0) or bits[n - 1 - k] (side 1), k < min(n, 32).  bad is set where a byte read
+// is neither 0 nor 1.
+QK_HD inline uint32_t sbk_pack(const uint8_t* bits, const int n, const int side, bool& bad) {
+  uint32_t word = 0;
+  const int nb = n < SBK_MAX_WIDTH ? n : SBK_MAX_WIDTH;
+  for (int k = 0; k < nb; ++k) {
+    const uint32_t b = bits[side ? n - 1 - k : k];
+    if (b > 1) bad = true;
+    word |= (b & 1u) << k;
+  }
+  return word;
+}
+// the overflow rule: U M^2 2^w_max <= 2^62, so that every sum and every partial sum fits an int64
+inline bool sbk_fits(const long long U, const long long M, const int w_max) { return (unsigned __int128)U * M * M <= ((unsigned __int128)1 << (62 - w_max)); }
+// widths must be strictly increasing in 1 .. min(n, 32): returns -1, or the index of the first offender
+inline int sbk_bad_width(const int n_widths, const int32_t* widths, const int n) { return blk_bad_width(n_widths, widths, n < SBK_MAX_WIDTH ? n : SBK_MAX_WIDTH); }
+// Settings per task: what the staged y words of a chunk (rows of M rounded up to 4 words; a longer row is staged in pieces, one
+// setting at a time) and the table of wave sums allow, and no more than leaves about SBK_LAUNCH_TASKS tasks in the call.
+inline int sbk_chunk(const int U, const int M, const long long n_pairs) {
+  const long long lds = M >= SBK_STAGE_WORDS ? 1 : SBK_STAGE_WORDS / sbk_round4(M);
+  const long long fill = std::max(1ll, (long long)U * n_pairs / SBK_LAUNCH_TASKS);
+  return (int)std::max(1ll, std::min({lds, (long long)SBK_MAX_CHUNK, (long long)U, fill}));
+}
+QK_HD constexpr int sbk_n_chunks(const int U, const int chunk) { return (U + chunk - 1) / chunk; }
+// task t of a pair batch: pair t / n_chunks of the batch and the settings [u0, u1)
+QK_HD inline void sbk_task(const long long t, const int U, const int chunk, long long& pair, int& u0, int& u1) {
+  const int nc = sbk_n_chunks(U, chunk);
+  pair = t / nc;
+  u0 = (int)(t % nc) * chunk;
+  u1 = u0 + chunk < U ? u0 + chunk : U;
+}
+// The work of a wave inside a setting: the M x words in blocks of 64 (one per lane) times `parts` pieces of the staged y row, so that
+// four waves have work when M is small.  Piece p of a row of bn words is [sbk_part_lo(p), sbk_part_lo(p + 1)), bounds in fours.
+QK_HD constexpr int sbk_a_blocks(const int M) { return (M + 63) / 64; }
+QK_HD constexpr int sbk_parts(const int M) { return sbk_a_blocks(M) == 1 ? 4 : sbk_a_blocks(M) == 2 ? 2 : 1; }
+QK_HD constexpr int sbk_part_lo(const int p, const int parts, const int bn) {
+  const int per = sbk_round4((bn + parts - 1) / parts);
+  return p * per < bn ? p * per : bn;
+}
+// the widths of a call in launches of 8, 4, 2 or 1: the size of the group that starts at width index `at`
+QK_HD constexpr int sbk_group(const int n_widths, const int at) {
+  const int left = n_widths - at;
+  return left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1;
+}
+// Pairs per batch: their per-setting sums [n_widths][pairs][U] (int64) and their pair entries within `room` bytes, at least one.
+inline long long sbk_batch_pairs(const long long room, const int n_widths, const int U) {
+  return std::max(1ll, room / ((long long)n_widths * U * 8 + 8));
 }
 
 }  // namespace qkl

@@ -108,6 +108,7 @@ _SIGNATURES = [
     ("qk_block_values_host", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("qk_block_self_host", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_sample_host", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint64, C.c_int64, _P, _P]),
+    ("qk_shot_block_sums_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
@@ -295,6 +296,110 @@ def random_bases(shots: int, n_qubits: int, seed=0) -> np.ndarray:
     return (1 + x[..., 0] % np.uint32(3)).astype(np.uint8)
 
 
+def setting_bases(settings: int, shots_per_setting: int, n_qubits: int, seed=0) -> np.ndarray:
+    """The bases table of a randomised-measurement protocol with U = ``settings`` random settings of M = ``shots_per_setting`` shots
+    each: ``np.repeat(random_bases(U, n_qubits, seed), M, axis=0)``, uint8 of shape (U M, n_qubits).  Shot ``u M + a`` is shot a of
+    setting u; ``Context.sample`` draws its M shots independently (its uniforms differ per shot)."""
+    if isinstance(shots_per_setting, bool) or not isinstance(shots_per_setting, (int, np.integer)) or int(shots_per_setting) < 1:
+        raise ValueError(f"shots_per_setting must be an int >= 1 (got {shots_per_setting!r})")
+    return np.repeat(random_bases(settings, n_qubits, seed), int(shots_per_setting), axis=0)
+
+
+_POPCOUNT8 = np.array([bin(v).count("1") for v in range(256)], dtype=np.int64)
+SHOT_BLOCK_MAX_WIDTH = 32
+
+
+def _shot_bits(bits, name: str) -> np.ndarray:
+    b = np.asarray(bits)
+    if b.ndim != 3 or b.dtype.kind not in "iub" or b.shape[2] < 1:
+        raise ValueError(f"{name} must be an integer array of shape (n_states, shots, n_qubits), got shape {b.shape}, dtype {b.dtype}")
+    return b
+
+
+def pack_block_words(bits, side="left") -> np.ndarray:
+    """The packed word of every shot of ``bits`` (..., n_qubits): uint32 of shape (...), bit k = ``bits[..., k]`` (``side="left"``) or
+    ``bits[..., n - 1 - k]`` (``"right"``) for k < min(n, 32), the other bits 0.  Raises ``ValueError`` if one of those entries is
+    neither 0 nor 1."""
+    b = np.asarray(bits)
+    if b.ndim < 1 or b.shape[-1] < 1 or b.dtype.kind not in "iub":
+        raise ValueError(f"bits must be an integer array whose last axis is the qubits, got shape {b.shape}, dtype {b.dtype}")
+    nb = min(b.shape[-1], SHOT_BLOCK_MAX_WIDTH)
+    blk = (b[..., ::-1] if _block_side(side) else b)[..., :nb].astype(np.int64)
+    if blk.size and (blk.min() < 0 or blk.max() > 1):
+        raise ValueError("bits holds a value other than 0 or 1 among the block's qubits")
+    return (blk << np.arange(nb, dtype=np.int64)).sum(axis=-1).astype(np.uint32)
+
+
+def _shot_widths(widths, n: int) -> np.ndarray:
+    w = _block_widths(widths, min(n, SHOT_BLOCK_MAX_WIDTH))
+    if w.size < 1 or w[0] < 1 or w[-1] > min(n, SHOT_BLOCK_MAX_WIDTH) or np.any(np.diff(w) <= 0):
+        raise ValueError(f"widths must be strictly increasing ints in 1 .. min(n_qubits, 32) = {min(n, SHOT_BLOCK_MAX_WIDTH)}, got {widths!r}")
+    return w
+
+
+def _shot_split(shots: int, settings) -> tuple:
+    if isinstance(settings, bool) or not isinstance(settings, (int, np.integer)) or int(settings) < 1 or shots < 1 or shots % int(settings):
+        raise ValueError(f"settings must be an int >= 1 that divides the {shots} shots of the tables (got {settings!r})")
+    return int(settings), shots // int(settings)
+
+
+def shot_block_sums(bits_x, bits_y, settings, pairs, widths, side="left", per_setting=False):
+    """The integer sums of the randomised-measurement overlap (Elben et al., PRL 124, 010504 (2020)) in plain numpy -- the mirror of
+    ``Context.shot_block_sums_host``, the same integers from xor and a popcount table.  ``bits_x`` (nx, U M, n) and ``bits_y``
+    (ny, U M, n; ``None``: Y is X) are outcome tables of U = ``settings`` settings of M shots, shot u M + a in setting u; ``pairs``
+    (n_pairs, 2) lists (x index, y index).  With s, s' the packed words (``pack_block_words``):
+        D_w(s, s')  = popcount((s xor s') & (2^w - 1))
+        term_w      = (-1)^D_w 2^(w - D_w)
+        S_u[w][p]   = sum_{a,b < M} term_w(X[i][uM+a], Y[j][uM+b])  -  [p is a self pair] M 2^w
+        sums[w][p]  = sum_u S_u[w][p]
+    A self pair is i == j with ``bits_y=None`` (the a == b terms are removed; it needs M >= 2).  Returns ``sums``, int64 of shape
+    (n_widths, n_pairs), and with ``per_setting=True`` also S, int64 (n_widths, n_pairs, U).  ``ValueError`` if U M^2 2^w_max > 2^62."""
+    bx = _shot_bits(bits_x, "bits_x")
+    by = bx if bits_y is None else _shot_bits(bits_y, "bits_y")
+    if by.shape[1:] != bx.shape[1:]:
+        raise ValueError(f"bits_x and bits_y differ in shots or qubits: {bx.shape} and {by.shape}")
+    U, M = _shot_split(bx.shape[1], settings)
+    w = _shot_widths(widths, bx.shape[2])
+    if U * M * M > (1 << (62 - int(w[-1]))):
+        raise ValueError(f"settings {U} x shots_per_setting {M}^2 x 2^{int(w[-1])} exceeds 2^62: the sums would not fit an int64")
+    P = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if P.size and (P.min() < 0 or P[:, 0].max() >= bx.shape[0] or P[:, 1].max() >= by.shape[0]):
+        raise ValueError(f"pairs holds an index outside the {bx.shape[0]} x {by.shape[0]} states")
+    wx = pack_block_words(bx, side).reshape(bx.shape[0], U, M)
+    wy = wx if bits_y is None else pack_block_words(by, side).reshape(by.shape[0], U, M)
+    S = np.zeros((w.size, len(P), U), dtype=np.int64)
+    for e, (i, j) in enumerate(P):
+        self_pair = bits_y is None and i == j
+        if self_pair and M < 2:
+            raise ValueError(f"pairs[{e}] is the self pair ({i}, {j}): it needs shots_per_setting >= 2")
+        d = wx[i][:, :, None] ^ wy[j][:, None, :]  # (U, M, M)
+        for wi, wd in enumerate(w):
+            m = d & np.uint32(0xFFFFFFFF if wd >= 32 else (1 << int(wd)) - 1)
+            D = _POPCOUNT8[m & np.uint32(255)] + _POPCOUNT8[(m >> np.uint32(8)) & np.uint32(255)] + _POPCOUNT8[(m >> np.uint32(16)) & np.uint32(255)] + _POPCOUNT8[m >> np.uint32(24)]
+            term = (np.int64(1) << (int(wd) - D)) * (1 - 2 * (D & 1))
+            S[wi, e] = term.sum(axis=(1, 2)) - (M << int(wd) if self_pair else 0)
+    sums = S.sum(axis=2)
+    return (sums, S) if per_setting else sums
+
+
+def shot_block_estimate(sums, per_setting, settings, shots_per_setting, self_mask):
+    """``(O_hat, stderr)`` from the sums of ``shot_block_sums``: with N = M^2 for a cross pair and M (M - 1) for a self pair
+    (``self_mask`` over the pairs axis, broadcast),
+        O_hat  = sums / (U N)
+        stderr = std over the settings of S_u / N (ddof = 1) / sqrt(U)       (nan when U < 2 or ``per_setting`` is None)
+    ``sums`` is (..., n_pairs) and ``per_setting`` (..., n_pairs, U).  The spread from setting to setting is what the standard error
+    measures: the shots of one setting share their bases."""
+    U, M = int(settings), int(shots_per_setting)
+    sums = np.asarray(sums)
+    N = np.where(np.asarray(self_mask, dtype=bool), M * (M - 1), M * M).astype(np.float64)
+    N = np.broadcast_to(N, sums.shape)
+    O = sums.astype(np.float64) / (U * N)
+    if per_setting is None or U < 2:
+        return O, np.full(O.shape, np.nan)
+    S = np.asarray(per_setting).astype(np.float64) / N[..., None]
+    return O, S.std(axis=-1, ddof=1) / np.sqrt(U)
+
+
 def bases_table(bases, shots: int, n_qubits: int) -> np.ndarray:
     """The uint8 table (shots, n_qubits) of basis codes that ``Context.sample`` and ``MPS.sample`` take: ``None`` is all Z, a string
     over ``XYZ`` or a row of ``n_qubits`` codes is shared by every shot, an array (shots, n_qubits) is taken as it is.  Raises
@@ -472,10 +577,11 @@ def block_kernel(O, Sx, Sy=None, form: str = "rbf", gamma=None) -> np.ndarray:
     """A kernel from reduced-state overlaps (``Context.block_overlaps``), pure numpy.  ``O`` has shape (..., ny, nx), ``Sx`` (..., nx)
     and ``Sy`` (..., ny) the self overlaps (purities); ``Sy=None`` means Y is X.
         "overlap"     K = O
-        "normalized"  K = O[j, i] / sqrt(Sx[i] Sy[j])
+        "normalized"  K = O[j, i] / sqrt(Sx[i] Sy[j])   (nan where Sx[i] Sy[j] <= 0)
         "rbf"         K = exp(-gamma (Sx[i] + Sy[j] - 2 O[j, i])) = exp(-gamma ||rho_A(x_i) - rho_A(y_j)||_F^2), gamma > 0 (default 1)
     With ``Sy=None`` the result is exactly symmetric (the upper triangle is mirrored) and "normalized" and "rbf" have a diagonal of
-    exactly 1.0."""
+    exactly 1.0.  Estimates from shots (``Context.shot_block_overlaps``) are taken as they are: an estimated purity can be <= 0, and
+    "normalized" is then nan in that state's row and column, off the diagonal."""
     if form not in ("overlap", "normalized", "rbf"):
         raise ValueError(f"form must be 'overlap', 'normalized' or 'rbf', got {form!r}")
     g = 1.0 if gamma is None else float(gamma)
@@ -490,7 +596,9 @@ def block_kernel(O, Sx, Sy=None, form: str = "rbf", gamma=None) -> np.ndarray:
     if form == "overlap":
         K = O.copy()
     elif form == "normalized":
-        K = O / np.sqrt(Sx[..., None, :] * Sy[..., :, None])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            prod = Sx[..., None, :] * Sy[..., :, None]
+            K = np.where(prod > 0.0, O / np.sqrt(np.where(prod > 0.0, prod, 1.0)), np.nan)
     else:
         K = np.exp(-g * ((Sx[..., None, :] + Sy[..., :, None]) - 2.0 * O))
     if sym:
@@ -1290,6 +1398,68 @@ class Context:
             Sx = np.ascontiguousarray(O[:, d, d])
             return O, Sx, Sx
         return O, self.block_self(xs, widths, side), self.block_self(ys, widths, side)
+
+    def shot_block_sums_host(self, bits_x, bits_y, settings, pairs, widths, side="left", per_setting: bool = False):
+        """``engine.shot_block_sums`` on the device (``qk_shot_block_sums_host``): the same int64 sums, bit for bit, for outcome tables
+        ``bits_x`` (nx, U M, n) and ``bits_y`` (ny, U M, n; ``None``: Y is X) of U = ``settings`` settings, the pairs (x index, y
+        index) of ``pairs`` in any order and the strictly increasing ``widths`` in 1 .. min(n, 32) (``None``: all of them).  Returns
+        ``sums`` (n_widths, n_pairs), with ``per_setting=True`` also S (n_widths, n_pairs, U).  It needs no MPS set.  Synchronous."""
+        bx = np.ascontiguousarray(_shot_bits(bits_x, "bits_x"), dtype=np.uint8)
+        by = None if bits_y is None else np.ascontiguousarray(_shot_bits(bits_y, "bits_y"), dtype=np.uint8)
+        if by is not None and by.shape[1:] != bx.shape[1:]:
+            raise ValueError(f"bits_x and bits_y differ in shots or qubits: {bx.shape} and {by.shape}")
+        nx, shots, n = bx.shape
+        U, M = _shot_split(shots, settings)
+        w = _block_widths(widths, min(n, SHOT_BLOCK_MAX_WIDTH))
+        P = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), dtype=np.int32)
+        sums = np.zeros((max(w.size, 1), max(len(P), 1)), dtype=np.int64)  # (spare elements: the pointers stay valid)
+        S = np.zeros(sums.shape + (U,), dtype=np.int64) if per_setting else None
+        wp = w if w.size else np.zeros(1, dtype=np.int32)
+        pp = P if len(P) else np.zeros((1, 2), dtype=np.int32)
+        _check(lib().qk_shot_block_sums_host(self._h, n, U, M, nx, bx.ctypes.data, nx if by is None else by.shape[0], None if by is None else by.ctypes.data, len(P),
+                                             pp.ctypes.data, _block_side(side), int(w.size), wp.ctypes.data, sums.ctypes.data, None if S is None else S.ctypes.data),
+               "qk_shot_block_sums_host")
+        sums = np.ascontiguousarray(sums[: w.size, : len(P)])
+        return (sums, np.ascontiguousarray(S[: w.size, : len(P)])) if per_setting else sums
+
+    def shot_block_overlaps(self, bits_x, bits_y=None, settings=1, widths=None, side="left", stderr: bool = False):
+        """``(O_hat, Sx_hat, Sy_hat)``: ``block_overlaps`` estimated from measurement shots by the randomised-measurement protocol --
+        O_hat[w, j, i] estimates tr(rho_A(x_i) rho_A(y_j)), shape (n_widths, ny, nx), Sx_hat (n_widths, nx) and Sy_hat (n_widths, ny) the
+        purities, what ``block_kernel`` takes.  ``bits_x`` (nx, U M, n) and ``bits_y`` are the bits ``Context.sample`` drew in
+        ``setting_bases(U, M, n)`` with U = ``settings`` (every state in the same table); ``widths=None`` means 1 .. min(n, 32).  The
+        estimate is unbiased for every width; its error is set by the spread from setting to setting, so spend shots on settings.
+        A symmetric call (``bits_y=None``) computes the pairs i <= j and mirrors them; its diagonal is the purity estimate (the a == b
+        shot pairs removed, M >= 2), the same bits as Sx_hat, and ``Sy_hat = Sx_hat``.  ``stderr=True`` also returns the standard
+        errors ``(eO, eSx, eSy)`` in the same shapes (nan when U < 2).  Synchronous."""
+        bx = _shot_bits(bits_x, "bits_x")
+        nx = bx.shape[0]
+        U, M = _shot_split(bx.shape[1], settings)
+
+        def self_of(b):
+            d = np.arange(b.shape[0])
+            out = self.shot_block_sums_host(b, None, U, np.stack([d, d], axis=1), widths, side, per_setting=stderr)
+            return shot_block_estimate(out[0] if stderr else out, out[1] if stderr else None, U, M, True)
+
+        if bits_y is None:
+            iu = np.triu_indices(nx)
+            pairs = np.stack([iu[0], iu[1]], axis=1)  # i <= j
+            out = self.shot_block_sums_host(bx, None, U, pairs, widths, side, per_setting=stderr)
+            vals, errs = shot_block_estimate(out[0] if stderr else out, out[1] if stderr else None, U, M, pairs[:, 0] == pairs[:, 1])
+            O, E = np.zeros((vals.shape[0], nx, nx)), np.zeros((vals.shape[0], nx, nx))
+            for dst, src in ((O, vals), (E, errs)):
+                dst[:, pairs[:, 1], pairs[:, 0]] = src
+                dst[:, pairs[:, 0], pairs[:, 1]] = src
+            d = np.arange(nx)
+            Sx, Ex = np.ascontiguousarray(O[:, d, d]), np.ascontiguousarray(E[:, d, d])
+            return ((O, Sx, Sx), (E, Ex, Ex)) if stderr else (O, Sx, Sx)
+        by = _shot_bits(bits_y, "bits_y")
+        ny = by.shape[0]
+        jj, ii = np.divmod(np.arange(ny * nx), nx)
+        out = self.shot_block_sums_host(bx, by, U, np.stack([ii, jj], axis=1), widths, side, per_setting=stderr)
+        vals, errs = shot_block_estimate(out[0] if stderr else out, out[1] if stderr else None, U, M, False)
+        O, E = vals.reshape(-1, ny, nx), errs.reshape(-1, ny, nx)
+        (Sx, Ex), (Sy, Ey) = self_of(bx), self_of(by)
+        return ((O, Sx, Sy), (E, Ex, Ey)) if stderr else (O, Sx, Sy)
 
     def bond_spectra(self, mps_set: MpsSet, max_values: int | None = None, norms: bool = False):
         """Entanglement spectra of every state of an fp64 set: the Schmidt weights (eigenvalues of the reduced state, descending, sum

@@ -708,8 +708,53 @@ def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64),
     return out
 
 
+def _shot_block_share(mpi_comm, ctx, shares, n_qubits, n_procs, rank, widths, side, shots, shot_seed):
+    """The finite-shot route of ``build_block_kernel_matrices``: (parts, self_x, self_y, err_x, err_y) with parts the all-gathered
+    (pairs, estimates, standard errors) of every rank.  Each rank samples its share of the states, the packed words of the block (4
+    bytes per shot) and the bond tables are all-gathered, and each rank estimates its share of the pairs of ``Plan(orient=False)``."""
+    U, M = shots
+    bases = _engine.setting_bases(U, M, n_qubits, shot_seed)
+    nbits = min(n_qubits, _engine.SHOT_BLOCK_MAX_WIDTH)
+    tables, dims, first = [], [], 0
+    for total, lo, loc, _, _ in shares:  # X, then Y: the states of Y are indexed after those of X
+        if loc is None:
+            words, d = np.zeros((0, U * M), dtype=np.uint32), np.zeros((0, n_qubits + 1), dtype=np.int32)
+        else:
+            bits = ctx.sample(loc, U * M, bases=bases, seed=shot_seed, first_state=first + int(lo))
+            words, d = _engine.pack_block_words(bits, side), np.asarray(loc.dims, dtype=np.int32)
+        full_w, full_d = np.zeros((total, U * M), dtype=np.uint32), np.zeros((total, n_qubits + 1), dtype=np.int32)
+        for s_lo, s_w, s_d in comm_allgather(mpi_comm, (int(lo), words, d)):
+            full_w[s_lo : s_lo + len(s_w)], full_d[s_lo : s_lo + len(s_d)] = s_w, s_d
+        # the words as outcome tables of the block alone: bit k of a word is qubit k of a left block
+        tables.append(np.ascontiguousarray(((full_w[..., None] >> np.arange(nbits, dtype=np.uint32)) & np.uint32(1)).astype(np.uint8)))
+        dims.append(full_d)
+        first += total
+    bx, by = tables[0], tables[1] if len(tables) > 1 else None
+    plan = _engine.Plan(dims[0], None if by is None else dims[1], n_procs, rank, orient=False)
+    try:
+        pairs = plan.pairs()
+    finally:
+        plan.close()
+    if len(pairs):
+        sums, S = ctx.shot_block_sums_host(bx, by, U, pairs, widths, "left", per_setting=True)
+        vals, errs = _engine.shot_block_estimate(sums, S, U, M, (pairs[:, 0] == pairs[:, 1]) if by is None else False)
+    else:
+        vals = errs = np.zeros((len(widths), 0))
+    parts = comm_allgather(mpi_comm, (pairs, vals, errs))
+
+    def self_of(b):
+        d = np.arange(b.shape[0])
+        sums, S = ctx.shot_block_sums_host(b, None, U, np.stack([d, d], axis=1), widths, "left", per_setting=True)
+        return _engine.shot_block_estimate(sums, S, U, M, True)
+
+    if by is None:
+        return parts, None, None, None, None
+    (self_x, err_x), (self_y, err_y) = self_of(bx), self_of(by)
+    return parts, self_x, self_y, err_x, err_y
+
+
 def build_block_kernel_matrices(mpi_comm, ansatz, X, Y=None, widths=None, side="left", form="rbf", block_gamma=None, truncation_error=None, info_file=None,
-                                loglevel=30):
+                                loglevel=30, shots=None, shot_seed=0):
     """Block kernels: from ONE build of the states, the projected kernel of the reduced state of the first (``side="left"``) or last
     (``"right"``) w qubits, for every w of ``widths`` (strictly increasing ints in 1 .. num_qubits; ``None``: every width).  One pair
     sweep gives the whole family between the one-qubit kernel (w = 1) and the fidelity kernel (w = n).  Rank 0 returns the dict
@@ -721,7 +766,19 @@ def build_block_kernel_matrices(mpi_comm, ansatz, X, Y=None, widths=None, side="
         self_y    (n_widths, len(Y))       (``self_x`` when Y is None)
     and the other ranks ``None``.  The shares are built and exchanged as in ``build_capped_kernel_matrices``; each rank sweeps its
     share of the pairs (``Context.block_values_host``) and the shares meet in one all-gather on the communicator.  The self
-    overlaps are linear work: every rank computes them for all states."""
+    overlaps are linear work: every rank computes them for all states.
+
+    ``shots=(U, M)`` is the family at finite shots, by the randomised-measurement protocol (Elben et al., PRL 124, 010504 (2020)):
+    U random settings of M shots each.  Each rank samples its share in ``engine.setting_bases(U, M, num_qubits, shot_seed)`` with
+    ``Context.sample(..., seed=shot_seed, first_state=<the share's offset>)`` (the states of Y are indexed after those of X), the
+    packed words of the block (4 bytes per shot) are all-gathered instead of the states, and each rank estimates its share of the
+    pairs of the same plan (``Context.shot_block_sums_host``, ``engine.shot_block_estimate``).  ``overlap``, ``K``, ``self_x`` and
+    ``self_y`` then hold the estimates -- in a symmetric call the diagonal of ``overlap`` is the purity estimate ``self_x`` -- and the
+    dict gains
+        shots     (U, M)
+        stderr    {"overlap": {w: (len(Y), len(X))}, "self_x": (n_widths, len(X)), "self_y": (n_widths, len(Y))}
+    The sums are integers, so ``K`` is the same bits for any number of ranks.  A width above 32 together with ``shots`` is a
+    ``ValueError``.  ``shots=None`` is the exact family."""
     if Y is not None and len(X) < len(Y):
         raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
     if truncation_error is None:
@@ -740,6 +797,15 @@ def build_block_kernel_matrices(mpi_comm, ansatz, X, Y=None, widths=None, side="
         raise ValueError(f"form must be 'overlap', 'normalized' or 'rbf', got {form!r}")
     if block_gamma is not None and not (float(block_gamma) > 0.0 and np.isfinite(float(block_gamma))):
         raise ValueError(f"block_gamma must be > 0 and finite, got {block_gamma!r}")
+    if shots is not None:
+        if (not isinstance(shots, (tuple, list)) or len(shots) != 2
+                or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 for v in shots)):
+            raise ValueError(f"shots must be None or (settings, shots_per_setting), two ints >= 1 (got {shots!r})")
+        shots = (int(shots[0]), int(shots[1]))
+        if widths[-1] > _engine.SHOT_BLOCK_MAX_WIDTH:
+            raise ValueError(f"shots: a packed word holds {_engine.SHOT_BLOCK_MAX_WIDTH} qubits, so widths stop there (got {widths[-1]})")
+        if Y is None and shots[1] < 2:
+            raise ValueError("shots: the purity estimates of a symmetric call need shots_per_setting >= 2")
     X = np.asarray(X, dtype=np.float64)
     Y = None if Y is None else np.asarray(Y, dtype=np.float64)
     fidelity = 1.0 - float(truncation_error)
@@ -762,6 +828,36 @@ def build_block_kernel_matrices(mpi_comm, ansatz, X, Y=None, widths=None, side="
     ctx.trim()
     build_secs = time.perf_counter() - t_start
     locals_ = [s[2] for s in shares]
+    if shots is not None:
+        try:
+            t0 = time.perf_counter()
+            parts, self_x, self_y, err_x, err_y = _shot_block_share(mpi_comm, ctx, shares, n_qubits, n_procs, rank, widths, side, shots, shot_seed)
+            sweep_secs = time.perf_counter() - t0
+        finally:
+            for loc in locals_:
+                if loc is not None:
+                    loc.close()
+        if not is_root:
+            return None
+        ny = len(X) if Y is None else len(Y)
+        out = {"widths": widths, "K": {}, "overlap": {}, "self_x": self_x, "self_y": self_y, "shots": shots, "stderr": {"overlap": {}, "self_x": err_x, "self_y": err_y}}
+        for wi, w in enumerate(widths):
+            O = assemble_gram(ny, len(X), [p[0] for p in parts], [p[1][wi] for p in parts], Y is None)
+            out["overlap"][w] = O
+            out["stderr"]["overlap"][w] = assemble_gram(ny, len(X), [p[0] for p in parts], [p[2][wi] for p in parts], Y is None)
+        if Y is None:  # the diagonal of a symmetric call is the purity estimate
+            d = np.arange(len(X))
+            out["self_x"] = out["self_y"] = np.stack([out["overlap"][w][d, d] for w in widths])
+            out["stderr"]["self_x"] = out["stderr"]["self_y"] = np.stack([out["stderr"]["overlap"][w][d, d] for w in widths])
+        for wi, w in enumerate(widths):
+            out["K"][w] = _engine.block_kernel(out["overlap"][w], out["self_x"][wi], None if Y is None else out["self_y"][wi], form=form, gamma=block_gamma)
+        if info_file is not None:
+            prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"],
+                    "r0_circ_sim": [build_secs, "seconds"], "widths": [widths, "qubits"], "side": [side, ""], "block_shots": [list(shots), "settings, shots"],
+                    "r0_block_sweep": [sweep_secs, "seconds"], "total_time": [time.perf_counter() - t_start, "seconds"]}
+            with open(info_file + ".json", "w") as fp:
+                json.dump(prof, fp, indent=4)
+        return out
     full = []
     try:
         full = [exchange_sets(mpi_comm, ctx, loc, lo, total)[0] for loc, (total, lo, _, _, _) in zip(locals_, shares)]

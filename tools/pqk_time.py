@@ -15,8 +15,13 @@ pairs and ctx.block_self(xs, widths): block_values_ms, block_self_ms, n_widths, 
 off-diagonal entry of the "normalized" kernel.
 ``--shots S`` adds ctx.sample(xs, S, bases=engine.random_bases(S, n, 0)): sample_ms, shots, sample_flops (the two GEMMs of every
 site for every shot, from the true bonds) and sample_tflops, and the median off-diagonal entry of the kernel estimated from the shots.
+``--block-shots U,M`` (with ``--block-widths``, widths <= 32) adds the block overlaps at finite shots: ctx.sample in
+engine.setting_bases(U, M, n, 0), then ctx.shot_block_sums_host on the pairs of the same symmetric plan (the call uploads the
+outcome bytes, packs them and sums): shot_block_ms (the median; shot_block_ms_min and _max give the spread over the repetitions),
+shot_block_terms = pairs U M^2 n_widths, shot_block_terms_per_s, shot_block_over_block against block_values_ms of the same run, and per
+width the median off-diagonal estimate next to the exact one.
 usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement] [--compress CHI]
-                                [--block-widths W1,W2,...] [--shots S]"""
+                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S]"""
 import argparse
 import json
 import os
@@ -101,8 +106,11 @@ def main():
     ap.add_argument("--entanglement", action="store_true", help="also time bond_purities and bond_spectra and print the cost of a bond cap")
     ap.add_argument("--compress", type=int, default=0, metavar="CHI", help="also time compress(max_bond=CHI) and the Gram of the compressed set")
     ap.add_argument("--block-widths", default=None, metavar="W1,W2,...", help="also time the block kernels of the first w qubits for these widths")
+    ap.add_argument("--block-shots", default=None, metavar="U,M", help="with --block-widths: also time the block overlaps estimated from U settings of M shots")
     ap.add_argument("--shots", type=int, default=0, metavar="S", help="also time sample() with S shots per state in random bases")
     args = ap.parse_args()
+    if args.block_shots and not args.block_widths:
+        ap.error("--block-shots needs --block-widths")
     gamma = args.gamma if args.gamma is not None else (0.1 if args.config == "cfg5" else 1.0)
     n, reps, d, npts = bench.CONFIGS[args.config]
     X = synthetic_features(npts, n, 5)
@@ -188,6 +196,25 @@ def main():
             "block_over_gram": round(block_ms / gram_ms, 4),
             "median_offdiag_block_normalized": {str(w): float(np.median(norm[wi][offd])) for wi, w in enumerate(widths)},
         })
+        if args.block_shots:
+            U, M = (int(v) for v in args.block_shots.split(","))
+            bits = ctx.sample(xs, U * M, bases=engine.setting_bases(U, M, n, 0), seed=0)
+            ctx.shot_block_sums_host(bits, None, U, pairs, widths)  # warm-up
+            ts = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                sums = ctx.shot_block_sums_host(bits, None, U, pairs, widths)
+                ts.append(1e3 * (time.perf_counter() - t0))
+            shot_ms = float(np.median(ts))
+            est = engine.shot_block_estimate(sums, None, U, M, ~offd)[0]
+            terms = len(pairs) * U * M * M * len(widths)
+            dist.update({
+                "block_shots": [U, M], "shot_block_reps": args.reps, "shot_block_ms": round(shot_ms, 3), "shot_block_ms_min": round(min(ts), 3),
+                "shot_block_ms_max": round(max(ts), 3), "shot_block_terms": terms, "shot_block_terms_per_s": round(terms / (shot_ms * 1e-3), 1),
+                "shot_block_over_block": round(shot_ms / block_ms, 4),
+                "median_offdiag_block_shots": {str(w): float(np.median(est[wi][offd])) for wi, w in enumerate(widths)},
+                "median_offdiag_block_exact": {str(w): float(np.median(vals[wi][offd])) for wi, w in enumerate(widths)},
+            })
     if args.shots > 0:
         bases = engine.random_bases(args.shots, n, 0)
         bits, sample_ms = timed(lambda: ctx.sample(xs, args.shots, bases=bases, seed=0), args.reps)
