@@ -509,6 +509,44 @@ int qk_shot_block_sums_host(qk_ctx* ctx, int32_t n_sites, int32_t n_settings, in
                             int32_t side, int32_t n_widths, const int32_t* widths,
                             int64_t* sums /* [n_widths][n_pairs] */, int64_t* per_setting /* [n_widths][n_pairs][U], may be NULL */);
 
+/* ---- the classical-shadow kernel: exact shot-pair histograms ---------------------------------------------------------------------
+ * qk_shadow_hist_host: what the shadow kernel of Huang, Kueng, Torlai, Albert and Preskill (Science 377, eabk3333 (2022)) needs of
+ * two outcome tables.  It needs no MPS set: it works on any outcome tables, such as the bits of qk_sample_host, with the bases they
+ * were measured in (bit 0 = eigenvalue +1; codes 1, 2, 3 = X, Y, Z).  bases_*_per_state = 0: one table [shots][n_sites] shared by
+ * every state of that side; 1: a table per state [n][shots][n_sites].
+ * The single-qubit shadow of a shot is sigma = 3 |s><s| - I, and tr(sigma_k sigma'_k) of two shots is 5 (qubit k measured in the
+ * same basis, same outcome), -4 (same basis, other outcome) or 1/2 (other basis).  With a and b the numbers of qubits of the first
+ * and second kind,
+ *     sum_k tr(sigma_k sigma'_k) = n/2 + 4.5 d,      d = a - b  in [-n, n]
+ *     hist[p][d + n]  = #{(t, t') : d(X[i] shot t, Y[j] shot t') = d}      int64, exact;  sum_d hist[p][.] = shots_x shots_y
+ *     equal[p][d + n] = the same over the pairs t = t' alone               (shots_x == shots_y)
+ *     inner[p]        = sum_d hist[p][d + n] exp(gamma / n (n/2 + 4.5 d)) / (shots_x shots_y),   K_shadow[p] = exp(tau inner[p])
+ * The weights are applied on the host (engine.shadow_inner, shadow_kernel): one histogram serves every gamma, tau and f(d).  When
+ * both tables were measured in one shared bases table the pairs t = t' share their bases on every qubit and bias a cross-pair
+ * estimate at order 1/shots; hist - equal over shots (shots - 1) pairs is the estimate without them.  In a self pair they are a shot
+ * paired with itself, d = n.
+ * Packed record of a shot: per group of 32 qubits three uint32 planes; bit k % 32 of group k / 32 holds the outcome bit (plane 0),
+ * code & 1 (plane 1), code >> 1 (plane 2); pad bits 0.  Then
+ *     eq = ~(p1 ^ p1') & ~(p2 ^ p2') & (p1 | p2),      d = popcount(eq) - 2 popcount(eq & (p0 ^ p0'))      summed over the groups.
+ * A pack kernel makes the records (one lane per (state, shot)); the histogram kernel takes one workgroup per (pair, range of blocks
+ * of 64 x shots), x records in registers, y records staged in LDS, one LDS increment per shot pair into per-lane counters (or, up to
+ * 2^14 shot pairs per pair of states, into one histogram per wave), and writes an int64 row per task; a second kernel adds the
+ * tasks of a pair; a third counts the pairs t = t'.  Cost: n_pairs shots_x shots_y shot pairs of about 9 vector instructions per
+ * group each.  Everything is integer arithmetic: the result is exact and does not depend on any order, batch cut, launch cut or run.
+ * Device scratch: the records (12 bytes per 32 qubits per shot), and per pair batch (tasks per pair + 2) (2 n + 1) int64 per pair in
+ * the context's local scratch (qk_ctx_trim releases it), by the batching rule of qk_local_paulis_host (a quarter of the free memory;
+ * pairs go in batches when they do not fit; QK_SHADOW_BATCH=k caps the pairs of a batch).  Synchronous; leaves the Gram statistics
+ * alone.
+ * QK_EINVAL (the message names the argument): a null ctx, bits_x, bases_x, pairs or hist; n_sites, nx, shots_x, ny, shots_y or
+ * n_pairs below 1; n_sites > 128; bits_y NULL with ny != nx, with shots_y != shots_x or with bases_y non-NULL; bits_y given with
+ * bases_y NULL; a pair index outside its table; a *_per_state flag not 0 or 1; equal given with shots_x != shots_y; a bit other than
+ * 0 or 1 (names bits_x or bits_y); a basis code outside 1 .. 3 (names bases_x or bases_y).                                       */
+int qk_shadow_hist_host(qk_ctx* ctx, int32_t n_sites,
+                        int32_t nx, int32_t shots_x, const uint8_t* bits_x /* [nx][shots_x][n_sites] */, const uint8_t* bases_x, int32_t bases_x_per_state,
+                        int32_t ny, int32_t shots_y, const uint8_t* bits_y /* NULL: Y is X */, const uint8_t* bases_y, int32_t bases_y_per_state,
+                        int64_t n_pairs, const int32_t* pairs /* [n_pairs][2] = (x index, y index), any order, duplicates allowed */,
+                        int64_t* hist /* [n_pairs][2 n_sites + 1] */, int64_t* equal /* same shape, may be NULL */);
+
 /* ---- compressing a set: one canonical truncation sweep per state -------------------------------------------------------------
  * qk_mps_set_compress: *out = a new fp64 set of the same context that owns its memory, every state of src truncated ONCE on its
  * final tensors; src is left untouched.  One workgroup per state (workgroup b takes states b, b + grid, ...), two passes over the

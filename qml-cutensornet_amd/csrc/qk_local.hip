@@ -7,8 +7,8 @@
 // qk_bond_purities_host and qk_bond_spectra_host (definitions above bond_call below), and the block kernels -- reduced-state
 // overlaps of the first or last w qubits for every pair of two sets -- qk_block_values_host and qk_block_self_host (definitions
 // above BlkSet below), and measurement shots of every state of a set, each shot and qubit in its own Pauli basis, qk_sample_host
-// (definitions above SmpArgs below), and the block overlaps estimated from such shots, qk_shot_block_sums_host (above SbkArgs below)
-// (include/qkgram.h).
+// (definitions above SmpArgs below), the block overlaps estimated from such shots, qk_shot_block_sums_host (above SbkArgs below), and the
+// shot-pair histograms of the classical-shadow kernel, qk_shadow_hist_host (above ShkArgs below) (include/qkgram.h).
 //
 // Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
 // normalised):
@@ -1846,7 +1846,295 @@ int shot_block_sums(qk_ctx* c, const int32_t n, const int32_t U, const int32_t M
   return QK_OK;
 }
 
+// ---- the shadow kernel's shot-pair histograms (qk_shadow_hist_host) -------------------------------------------------------------------
+// The classical-shadow kernel of Huang et al. (Science 377, eabk3333 (2022)) needs of a pair of states only the histogram of
+// d = (qubits measured in the same basis with the same outcome) - (same basis, other outcome) over all its shot pairs: all integer
+// arithmetic, definitions in include/qkgram.h, host side in qk_local_plan.h (shk_*).
+//   qk_shk_pack_kernel  one lane per (state, shot): bits and bases into the record of three planes per 32 qubits (shk_pack); a bit
+//       that is neither 0 nor 1 raises bad[0], a code outside 1 .. 3 bad[1].
+//   qk_shk_hist_kernel  one workgroup per task = (pair, range of blocks of 64 x shots).  The y records are staged in LDS, 256 at a
+//       time, rows of 16-byte multiples.  A wave takes (x block, piece of the staged records) units: each lane keeps its x record in
+//       registers (3 to 12 words) and every lane reads the same y record (ds_read_b128 of one address: a broadcast, conflict-free).
+//       Per shot pair and group: three XORs, an OR, an AND-NOT and an AND, and two v_bcnt that add up over the groups (shk_d); then
+//       one increment, ds_add_u32 without a return value, so nothing waits for it.  Where it lands is the layout (shk_layout):
+//       private counters [bin][thread] -- the lanes of a wave hit 64 consecutive words, no two lanes ever share one, the LDS does
+//       the add in one pass -- or, for few shots, where clearing and adding up 256 copies of the histogram would cost more than the
+//       shot pairs themselves, one histogram per wave, the lanes that meet in a bin serialised by the LDS.  At the end of the task
+//       the copies of each bin are added into an int64 and written to the task's row.
+//   qk_shk_total_kernel one thread per (pair, bin): the sum of the rows of the pair's tasks.
+//   qk_shk_equal_kernel one workgroup per pair: the histogram of the shot pairs t = t' alone, one LDS histogram.
+// Counts are exact and order-free; no global atomic, no workgroup waits for another.
+struct ShkArgs {
+  const uint32_t* xr;    // records [nx][shots_x][3 groups]
+  const uint32_t* yr;    // [ny][shots_y][3 groups]; the x records when Y is X
+  const int32_t* pairs;  // the batch's pairs (x index, y index)
+  long long* rows;       // per-task histograms of the batch [nb pair_tasks][bins]
+  int n, shots_x, shots_y, task_blocks;
+  long long task0;       // first task of the launch
+};
+
+__global__ __launch_bounds__(256) void qk_shk_pack_kernel(const uint8_t* bits, const uint8_t* bases, const int per_state, const long long count, const int shots, const int n,
+                                                          uint32_t* recs, int32_t* bad) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= count) return;
+  bool bad_bit = false, bad_code = false;
+  uint32_t rec[3 * SHK_MAX_GROUPS];
+  shk_pack(bits + e * n, bases + (per_state ? e : e % shots) * n, n, rec, bad_bit, bad_code);
+  const int words = shk_words(n);
+  for (int k = 0; k < words; ++k) recs[e * words + k] = rec[k];
+  if (bad_bit) bad[0] = 1;
+  if (bad_code) bad[1] = 1;
+}
+
+template <int G, int LAYOUT>
+__global__ __launch_bounds__(256) void qk_shk_hist_kernel(const ShkArgs g) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t shk_lds[];
+  constexpr int W = 3 * G, LD = shk_stride(G);
+  uint32_t* const ys = shk_lds;                        // staged y records, LD words each
+  uint32_t* const cnt = shk_lds + SHK_STAGE_SHOTS * LD;  // the counters
+  const int threads = blockDim.x, waves = threads >> 6, lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: the loops over a wave's units run on the scalar unit
+  const int bins = shk_bins(g.n);
+  long long pair;
+  int b0, b1;
+  shk_task(g.task0 + blockIdx.x, g.shots_x, g.task_blocks, pair, b0, b1);
+  const int xi = g.pairs[2 * pair], yj = g.pairs[2 * pair + 1];
+  const uint32_t* const X = g.xr + (long long)xi * g.shots_x * W;
+  const uint32_t* const Y = g.yr + (long long)yj * g.shots_y * W;
+  const int ncnt = LAYOUT == SHK_PRIVATE ? bins * threads : bins * waves;
+  for (int e = threadIdx.x; e < ncnt; e += threads) cnt[e] = 0;
+  // this lane's counter of d = 0, and the words from one bin to the next
+  uint32_t* const mine = LAYOUT == SHK_PRIVATE ? cnt + g.n * threads + threadIdx.x : cnt + wv * bins + g.n;
+  const int step = LAYOUT == SHK_PRIVATE ? threads : 1;
+  const int parts = shk_parts(b1 - b0, waves), units = (b1 - b0) * parts;
+  for (int y0 = 0; y0 < g.shots_y; y0 += SHK_STAGE_SHOTS) {
+    const int bn = min(SHK_STAGE_SHOTS, g.shots_y - y0);
+    __syncthreads();  // the counters are cleared; the last pass's records are no longer read
+    for (int e = threadIdx.x; e < bn * W; e += threads) ys[(e / W) * LD + e % W] = Y[(long long)y0 * W + e];
+    __syncthreads();
+    for (int unit = wv; unit < units; unit += waves) {
+      const long long a = (long long)(b0 + unit / parts) * SHK_BLOCK + lane;  // this lane's x shot
+      const int pc = unit % parts;
+      const int lo = shk_part_lo(pc, parts, bn), hi = shk_part_lo(pc + 1, parts, bn);
+      if (a >= g.shots_x) continue;
+      uint32_t x[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) x[k] = X[a * W + k];
+      // four y records at a time, read before the four increments: the reads of one round are in flight together
+      auto count = [&](const uint32_t* y) { __hip_atomic_fetch_add(mine + shk_d(x, y, G) * step, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
+      auto fetch = [&](uint32_t* y, const int b) {
+#pragma unroll
+        for (int k = 0; k < LD; k += 4) {
+          const uint4 v = *reinterpret_cast<const uint4*>(ys + b * LD + k);
+          y[k] = v.x, y[k + 1] = v.y, y[k + 2] = v.z, y[k + 3] = v.w;
+        }
+      };
+      int b = lo;
+      for (; b + 4 <= hi; b += 4) {
+        uint32_t y[4][LD];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) fetch(y[u], b + u);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) count(y[u]);
+      }
+      for (; b < hi; ++b) {
+        uint32_t y[LD];
+        fetch(y, b);
+        count(y);
+      }
+    }
+  }
+  __syncthreads();
+  long long* const row = g.rows + (g.task0 + blockIdx.x) * bins;
+  if (LAYOUT == SHK_PRIVATE) {
+    for (int bin = wv; bin < bins; bin += waves) {  // a wave per bin: consecutive words, then across the lanes
+      long long t = 0;
+      for (int k = lane; k < threads; k += 64) t += cnt[bin * threads + k];
+      for (int h = 32; h > 0; h >>= 1) t += __shfl_xor(t, h, 64);
+      if (lane == 0) row[bin] = t;
+    }
+  } else {
+    for (int bin = threadIdx.x; bin < bins; bin += threads) {
+      long long t = 0;
+      for (int k = 0; k < waves; ++k) t += cnt[k * bins + bin];
+      row[bin] = t;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void qk_shk_total_kernel(const long long* rows, const long long nb, const int pair_tasks, const int bins, long long* hist) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= nb * bins) return;
+  const long long p = e / bins, bin = e % bins;
+  long long t = 0;
+  for (int k = 0; k < pair_tasks; ++k) t += rows[(p * pair_tasks + k) * bins + bin];
+  hist[e] = t;
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void qk_shk_equal_kernel(const uint32_t* xr, const uint32_t* yr, const int32_t* pairs, const long long pair0, const int n, const int shots,
+                                                           long long* equal) {
+  __shared__ uint32_t h[shk_bins(SHK_MAX_QUBITS)];
+  constexpr int W = 3 * G;
+  const long long pair = pair0 + blockIdx.x;
+  const int bins = shk_bins(n);
+  const uint32_t* const X = xr + (long long)pairs[2 * pair] * shots * W;
+  const uint32_t* const Y = yr + (long long)pairs[2 * pair + 1] * shots * W;
+  for (int e = threadIdx.x; e < bins; e += 256) h[e] = 0;
+  __syncthreads();
+  for (int t = threadIdx.x; t < shots; t += 256) {
+    uint32_t x[W], y[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) x[k] = X[(long long)t * W + k], y[k] = Y[(long long)t * W + k];
+    __hip_atomic_fetch_add(h + n + shk_d(x, y, G), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < bins; e += 256) equal[pair * bins + e] = h[e];
+}
+
+template <int G, int LAYOUT>
+int shk_launch(const ShkArgs& q, const unsigned grid, const int waves, const int lds, hipStream_t stream) {
+  if (q.task0 == 0 &&  // once per batch: the private counters may take most of a CU's LDS
+      hipFuncSetAttribute(reinterpret_cast<const void*>(qk_shk_hist_kernel<G, LAYOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, SHK_LDS_BYTES) != hipSuccess)
+    return 1;
+  qk_shk_hist_kernel<G, LAYOUT><<<dim3(grid), dim3(64 * waves), lds, stream>>>(q);
+  return 0;
+}
+template <int G>
+int shk_launch_g(const ShkLayout layout, const ShkArgs& q, const unsigned grid, const int waves, const int lds, hipStream_t stream) {
+  return layout == SHK_PRIVATE ? shk_launch<G, SHK_PRIVATE>(q, grid, waves, lds, stream) : shk_launch<G, SHK_SHARED>(q, grid, waves, lds, stream);
+}
+
+// the records of one outcome table, uploaded in pieces of whole states that fit `room` bytes (at least one state)
+int shk_pack_table(qk_ctx* c, const char* what, const char* bits_name, const char* bases_name, const uint8_t* bits, const uint8_t* bases, const int per_state, const int ns,
+                   const long long shots, const int n, const long long room, uint32_t* recs, int32_t* d_bad) {
+  const long long per = shots * n, piece = std::max(1ll, std::min((long long)ns, room / (per * (per_state ? 2 : 1))));
+  QkDevBuf stage, bstage;
+  HIP_TRY_AS(what, stage.alloc((size_t)(piece * per)));
+  HIP_TRY_AS(what, bstage.alloc((size_t)((per_state ? piece : 1) * per)));
+  if (!per_state) HIP_TRY_AS(what, hipMemcpyAsync(bstage.get(), bases, (size_t)per, hipMemcpyHostToDevice, c->stream));
+  for (long long s0 = 0; s0 < ns; s0 += piece) {
+    const long long cnt = std::min(piece, ns - s0) * shots;
+    HIP_TRY_AS(what, hipMemcpyAsync(stage.get(), bits + s0 * per, (size_t)(cnt * n), hipMemcpyHostToDevice, c->stream));
+    if (per_state) HIP_TRY_AS(what, hipMemcpyAsync(bstage.get(), bases + s0 * per, (size_t)(cnt * n), hipMemcpyHostToDevice, c->stream));
+    qk_shk_pack_kernel<<<dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream>>>(stage.get<uint8_t>(), bstage.get<uint8_t>(), per_state, cnt, (int)shots, n,
+                                                                                         recs + s0 * shots * shk_words(n), d_bad);
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the stages are reused by the next piece
+  }
+  int32_t bad[2] = {0, 0};
+  HIP_TRY_AS(what, hipMemcpy(bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost));
+  if (bad[0]) return qk_fail(QK_EINVAL, "%s: %s holds a bit other than 0 or 1", what, bits_name);
+  if (bad[1]) return qk_fail(QK_EINVAL, "%s: %s holds a basis code outside 1 .. 3 (1 = X, 2 = Y, 3 = Z)", what, bases_name);
+  return QK_OK;
+}
+
+int shadow_hist(qk_ctx* c, const int32_t n, const int32_t nx, const int32_t shots_x, const uint8_t* bits_x, const uint8_t* bases_x, const int32_t xps, const int32_t ny,
+                const int32_t shots_y, const uint8_t* bits_y, const uint8_t* bases_y, const int32_t yps, const int64_t n_pairs, const int32_t* pairs, int64_t* hist,
+                int64_t* equal) {
+  static const char* what = "qk_shadow_hist_host";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!bits_x) return qk_fail(QK_EINVAL, "%s: bits_x is null", what);
+  if (!bases_x) return qk_fail(QK_EINVAL, "%s: bases_x is null", what);
+  if (!pairs) return qk_fail(QK_EINVAL, "%s: pairs is null", what);
+  if (!hist) return qk_fail(QK_EINVAL, "%s: hist is null", what);
+  if (n < 1) return qk_fail(QK_EINVAL, "%s: n_sites must be >= 1 (got %d)", what, n);
+  if (n > SHK_MAX_QUBITS) return qk_fail(QK_EINVAL, "%s: n_sites must be <= %d (got %d)", what, SHK_MAX_QUBITS, n);
+  if (nx < 1) return qk_fail(QK_EINVAL, "%s: nx must be >= 1 (got %d)", what, nx);
+  if (shots_x < 1) return qk_fail(QK_EINVAL, "%s: shots_x must be >= 1 (got %d)", what, shots_x);
+  if (ny < 1) return qk_fail(QK_EINVAL, "%s: ny must be >= 1 (got %d)", what, ny);
+  if (shots_y < 1) return qk_fail(QK_EINVAL, "%s: shots_y must be >= 1 (got %d)", what, shots_y);
+  if (n_pairs < 1) return qk_fail(QK_EINVAL, "%s: n_pairs must be >= 1 (got %lld)", what, (long long)n_pairs);
+  if (xps != 0 && xps != 1) return qk_fail(QK_EINVAL, "%s: bases_x_per_state must be 0 or 1 (got %d)", what, xps);
+  if (yps != 0 && yps != 1) return qk_fail(QK_EINVAL, "%s: bases_y_per_state must be 0 or 1 (got %d)", what, yps);
+  const bool self = !bits_y;
+  if (self && ny != nx) return qk_fail(QK_EINVAL, "%s: Y is X (bits_y is null) but ny %d != nx %d", what, ny, nx);
+  if (self && shots_y != shots_x) return qk_fail(QK_EINVAL, "%s: Y is X (bits_y is null) but shots_y %d != shots_x %d", what, shots_y, shots_x);
+  if (self && bases_y) return qk_fail(QK_EINVAL, "%s: Y is X (bits_y is null) but bases_y is given", what);
+  if (!self && !bases_y) return qk_fail(QK_EINVAL, "%s: bits_y is given but bases_y is null", what);
+  if (equal && shots_x != shots_y) return qk_fail(QK_EINVAL, "%s: equal needs shots_x == shots_y (got %d and %d)", what, shots_x, shots_y);
+  for (long long e = 0; e < n_pairs; ++e) {
+    const int i = pairs[2 * e], j = pairs[2 * e + 1];
+    if (i < 0 || i >= nx || j < 0 || j >= ny) return qk_fail(QK_EINVAL, "%s: pairs[%lld] is (%d, %d), the tables hold %d x %d states", what, e, i, j, nx, ny);
+  }
+  long long cap = 0;  // pairs per batch; 0: the memory rule alone
+  if (const char* v = std::getenv("QK_SHADOW_BATCH")) {
+    cap = std::atoll(v);
+    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_SHADOW_BATCH must be >= 1 (got \"%s\")", what, v);
+  }
+  QkRangeGuard range_("qk:shadow_hist");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  const int groups = shk_groups(n), words = shk_words(n), bins = shk_bins(n);
+  const long long nrx = (long long)nx * shots_x, nry = self ? 0 : (long long)ny * shots_y;
+  QkDevBuf recs, dbad;
+  HIP_TRY_AS(what, recs.alloc((size_t)((nrx + nry) * words) * sizeof(uint32_t)));
+  HIP_TRY_AS(what, dbad.alloc(2 * sizeof(int32_t)));
+  HIP_TRY_AS(what, hipMemset(dbad.get(), 0, 2 * sizeof(int32_t)));
+  // memory bound of the staged outcome bytes and of a pair batch: a quarter of what is free once the records exist
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  const long long room = budget * (long long)sizeof(double);
+  uint32_t* const xr = recs.get<uint32_t>();
+  uint32_t* const yr = self ? xr : xr + nrx * words;
+  if (const int rc = shk_pack_table(c, what, "bits_x", "bases_x", bits_x, bases_x, xps, nx, shots_x, n, room, xr, dbad.get<int32_t>())) return rc;
+  if (!self)
+    if (const int rc = shk_pack_table(c, what, "bits_y", "bases_y", bits_y, bases_y, yps, ny, shots_y, n, room, yr, dbad.get<int32_t>())) return rc;
+
+  const ShkLayout layout = shk_layout(n, shots_x, shots_y);
+  const int waves = shk_waves(n, layout), lds = shk_lds_bytes(n, layout);
+  const int task_blocks = shk_task_blocks(layout, shots_x, shots_y, n_pairs), pair_tasks = shk_pair_tasks(shots_x, task_blocks);
+  long long batch = std::min((long long)n_pairs, shk_batch_pairs(room, n, pair_tasks));
+  if (cap) batch = std::min(batch, cap);
+  ShkArgs q{};
+  q.xr = xr, q.yr = yr, q.n = n, q.shots_x = shots_x, q.shots_y = shots_y, q.task_blocks = task_blocks;
+  for (long long p0 = 0; p0 < n_pairs; p0 += batch) {
+    const long long nb = std::min(batch, n_pairs - p0), tasks = nb * pair_tasks;
+    // one device buffer for the pair batch: [pairs | per-task rows | histograms | equal-shot histograms]
+    const size_t b_pairs = al256((size_t)(2 * nb) * sizeof(int32_t)), b_rows = (size_t)tasks * bins * sizeof(int64_t), b_hist = (size_t)nb * bins * sizeof(int64_t);
+    HIP_TRY_AS(what, c->local_scratch.ensure(b_pairs + b_rows + 2 * b_hist));
+    char* const base = c->local_scratch.get<char>();
+    q.pairs = reinterpret_cast<const int32_t*>(base);
+    q.rows = reinterpret_cast<long long*>(base + b_pairs);
+    long long* const d_hist = reinterpret_cast<long long*>(base + b_pairs + b_rows);
+    long long* const d_equal = reinterpret_cast<long long*>(base + b_pairs + b_rows + b_hist);
+    HIP_TRY_AS(what, hipMemcpyAsync(base, pairs + 2 * p0, (size_t)(2 * nb) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    for (long long t0 = 0; t0 < tasks; t0 += SHK_LAUNCH_TASKS) {
+      q.task0 = t0;
+      const unsigned grid = (unsigned)std::min((long long)SHK_LAUNCH_TASKS, tasks - t0);
+      const int rc = groups == 1 ? shk_launch_g<1>(layout, q, grid, waves, lds, c->stream)
+                   : groups == 2 ? shk_launch_g<2>(layout, q, grid, waves, lds, c->stream)
+                   : groups == 3 ? shk_launch_g<3>(layout, q, grid, waves, lds, c->stream)
+                                 : shk_launch_g<4>(layout, q, grid, waves, lds, c->stream);
+      if (rc) return qk_fail(QK_EDEVICE, "%s: the histogram kernel was refused %d bytes of LDS", what, lds);
+    }
+    HIP_TRY_AS(what, hipGetLastError());
+    qk_shk_total_kernel<<<dim3((unsigned)((nb * bins + 255) / 256)), dim3(256), 0, c->stream>>>(q.rows, nb, pair_tasks, bins, d_hist);
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipMemcpyAsync(hist + p0 * bins, d_hist, b_hist, hipMemcpyDeviceToHost, c->stream));
+    if (equal) {
+      for (long long e0 = 0; e0 < nb; e0 += 32 * SHK_LAUNCH_TASKS) {
+        const unsigned grid = (unsigned)std::min((long long)32 * SHK_LAUNCH_TASKS, nb - e0);
+        if (groups == 1) qk_shk_equal_kernel<1><<<dim3(grid), dim3(256), 0, c->stream>>>(xr, yr, q.pairs, e0, n, shots_x, d_equal);
+        else if (groups == 2) qk_shk_equal_kernel<2><<<dim3(grid), dim3(256), 0, c->stream>>>(xr, yr, q.pairs, e0, n, shots_x, d_equal);
+        else if (groups == 3) qk_shk_equal_kernel<3><<<dim3(grid), dim3(256), 0, c->stream>>>(xr, yr, q.pairs, e0, n, shots_x, d_equal);
+        else qk_shk_equal_kernel<4><<<dim3(grid), dim3(256), 0, c->stream>>>(xr, yr, q.pairs, e0, n, shots_x, d_equal);
+      }
+      HIP_TRY_AS(what, hipGetLastError());
+      HIP_TRY_AS(what, hipMemcpyAsync(equal + p0 * bins, d_equal, b_hist, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the batch's buffer is reused by the next batch
+  }
+  return QK_OK;
+}
+
 }  // namespace
+
+extern "C" int qk_shadow_hist_host(qk_ctx* c, int32_t n_sites, int32_t nx, int32_t shots_x, const uint8_t* bits_x, const uint8_t* bases_x, int32_t bases_x_per_state, int32_t ny,
+                                   int32_t shots_y, const uint8_t* bits_y, const uint8_t* bases_y, int32_t bases_y_per_state, int64_t n_pairs, const int32_t* pairs, int64_t* hist,
+                                   int64_t* equal) {
+  return shadow_hist(c, n_sites, nx, shots_x, bits_x, bases_x, bases_x_per_state, ny, shots_y, bits_y, bases_y, bases_y_per_state, n_pairs, pairs, hist, equal);
+}
 
 extern "C" int qk_shot_block_sums_host(qk_ctx* c, int32_t n_sites, int32_t n_settings, int32_t shots_per_setting, int32_t nx, const uint8_t* bits_x, int32_t ny,
                                        const uint8_t* bits_y, int64_t n_pairs, const int32_t* pairs, int32_t side, int32_t n_widths, const int32_t* widths, int64_t* sums,

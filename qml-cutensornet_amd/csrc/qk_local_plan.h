@@ -1,6 +1,6 @@
 // qk_local_plan.h -- the host-side plan of the local sweeps (qk_local.hip): the launch kinds, the scratch layout, the pair index, the
 // sizes and the cut into state batches, the tables and task lists of a batch, the plans of the entry points, the chain side of the
-// Pauli strings and the integer side of the shot-based block overlaps.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
+// Pauli strings, the integer side of the shot-based block overlaps and of the shadow kernel's shot-pair histograms.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
 // -fsanitize=address,undefined); the few functions the kernels also call are QK_HD.
 #pragma once
 #include "qk_plan.h"
@@ -563,6 +563,115 @@ QK_HD constexpr int sbk_group(const int n_widths, const int at) {
 // Pairs per batch: their per-setting sums [n_widths][pairs][U] (int64) and their pair entries within `room` bytes, at least one.
 inline long long sbk_batch_pairs(const long long room, const int n_widths, const int U) {
   return std::max(1ll, room / ((long long)n_widths * U * 8 + 8));
+}
+
+// ---- the shadow kernel's shot-pair histograms (qk_shadow_hist_host) -------------------------------------------------------------------
+// A shot is a record of three 32-bit planes per group of 32 qubits: bit k % 32 of group k / 32 holds the outcome bit (plane 0),
+// code & 1 (plane 1) and code >> 1 (plane 2) of qubit k, codes 1, 2, 3 = X, Y, Z; pad bits are 0 in all planes.  Two shots enter the
+// kernel through d = (qubits measured in the same basis with the same outcome) - (same basis, other outcome), and a pair of states
+// through the histogram of d over all its shot pairs (definitions in include/qkgram.h).  A task is one pair and a range of blocks of
+// 64 x shots (a block is what a wave holds in registers, one record per lane).
+constexpr int SHK_MAX_QUBITS = 128;
+constexpr int SHK_MAX_GROUPS = SHK_MAX_QUBITS / 32;
+constexpr int SHK_BLOCK = 64;            // x shots of a block: one per lane of a wave
+constexpr int SHK_STAGE_SHOTS = 256;     // y records a workgroup stages in LDS at a time
+constexpr int SHK_LAUNCH_TASKS = 2048;   // tasks of one launch: eight workgroups per CU, so no launch runs long on a shared device
+constexpr int SHK_LDS_BYTES = 160 * 1024;  // of a CU, and the most one workgroup may take
+constexpr long long SHK_COUNTER_MAX = 0xffffffffll;  // a counter in LDS is 32 bits wide
+constexpr long long SHK_SHARED_PAIRS = 1ll << 14;     // shot pairs of a pair of states up to which one histogram per wave is used
+enum ShkLayout : int {
+  SHK_PRIVATE = 0,  // counters [bin][thread]: every lane owns its counters, so an increment never meets another lane's
+  SHK_SHARED = 1,   // counters [wave][bin]: one histogram per wave; lanes that meet in a bin are serialised by the LDS
+};
+QK_HD constexpr int shk_groups(const int n) { return (n + 31) / 32; }
+QK_HD constexpr int shk_words(const int n) { return 3 * shk_groups(n); }                    // of a record in memory
+QK_HD constexpr int shk_stride(const int groups) { return (3 * groups + 3) & ~3; }          // of a staged record in LDS: 16-byte reads
+QK_HD constexpr int shk_bins(const int n) { return 2 * n + 1; }
+// The record of a shot: rec[3 g + plane].  bad_bit / bad_code are set where a bit is not 0 or 1 / a code is not in 1 .. 3 (the
+// offending entry contributes its low bits; the caller rejects the table).
+QK_HD inline void shk_pack(const uint8_t* bits, const uint8_t* bases, const int n, uint32_t* rec, bool& bad_bit, bool& bad_code) {
+  const int groups = shk_groups(n);
+  for (int g = 0; g < groups; ++g) {
+    uint32_t p0 = 0, p1 = 0, p2 = 0;
+    const int k1 = n - 32 * g < 32 ? n - 32 * g : 32;
+    for (int k = 0; k < k1; ++k) {
+      const uint32_t b = bits[32 * g + k], c = bases[32 * g + k];
+      if (b > 1) bad_bit = true;
+      if (c < 1 || c > 3) bad_code = true;
+      p0 |= (b & 1u) << k, p1 |= (c & 1u) << k, p2 |= ((c >> 1) & 1u) << k;
+    }
+    rec[3 * g] = p0, rec[3 * g + 1] = p1, rec[3 * g + 2] = p2;
+  }
+}
+QK_HD inline int shk_popc(const uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __popc(v);
+#else
+  return __builtin_popcount(v);
+#endif
+}
+// d of two records (strides sx, sy words between groups' planes: 3 in memory, and 3 in a staged record too): the one place it is defined.
+//     eq = same basis on a measured qubit,   d = popcount(eq) - 2 popcount(eq & (outcomes differ))
+QK_HD inline int shk_d(const uint32_t* x, const uint32_t* y, const int groups) {
+  int same = 0, differ = 0;
+  for (int g = 0; g < groups; ++g) {
+    const uint32_t eq = ~((x[3 * g + 1] ^ y[3 * g + 1]) | (x[3 * g + 2] ^ y[3 * g + 2])) & (x[3 * g + 1] | x[3 * g + 2]);
+    same += shk_popc(eq), differ += shk_popc(eq & (x[3 * g] ^ y[3 * g]));
+  }
+  return same - 2 * differ;
+}
+QK_HD constexpr int shk_x_blocks(const int shots_x) { return (shots_x - 1) / SHK_BLOCK + 1; }  // shots_x >= 1; no sum that could pass 2^31
+// The LDS layout, a pure function of n and the shots.  Private counters cost a task bins x threads words to clear and as many to
+// add up, whatever the shots; a histogram per wave costs bins words per wave but serialises the lanes that meet in a bin (d sits
+// within a few sqrt(n) of 0, so most of a wave does).  So: shared while a pair of states has at most SHK_SHARED_PAIRS shot pairs --
+// about what clearing and adding 256 private copies of a hundred bins costs -- and private beyond.
+QK_HD constexpr ShkLayout shk_layout(const int /*n*/, const long long shots_x, const long long shots_y) {
+  return shots_x * shots_y <= SHK_SHARED_PAIRS ? SHK_SHARED : SHK_PRIVATE;
+}
+QK_HD constexpr int shk_stage_bytes(const int n) { return SHK_STAGE_SHOTS * shk_stride(shk_groups(n)) * 4; }
+// Waves of a workgroup: four, or as many (at least two at n = 128) as the private counters leave room for next to the staged records.
+QK_HD constexpr int shk_waves(const int n, const ShkLayout layout) {
+  if (layout == SHK_SHARED) return 4;
+  const int fit = (SHK_LDS_BYTES - shk_stage_bytes(n)) / (shk_bins(n) * 64 * 4);
+  return fit < 4 ? fit : 4;
+}
+// dynamic LDS of the histogram kernel: [staged y records | counters]
+QK_HD constexpr int shk_lds_bytes(const int n, const ShkLayout layout) {
+  return shk_stage_bytes(n) + shk_bins(n) * 4 * shk_waves(n, layout) * (layout == SHK_SHARED ? 1 : 64);
+}
+// The counter bound: the most x blocks a task may take so that no 32-bit counter passes SHK_COUNTER_MAX before the task adds its
+// counters into int64.  A private counter takes at most one increment per (block of its wave, y shot); a wave's shared counter at
+// most 64 per (block, y shot).  shots_y < 2^31, so one block always fits a private counter; a shared layout has at most
+// SHK_SHARED_PAIRS increments in all.
+QK_HD constexpr long long shk_max_blocks(const ShkLayout layout, const long long shots_y) {
+  return SHK_COUNTER_MAX / (shots_y * (layout == SHK_SHARED ? SHK_BLOCK : 1));
+}
+// x blocks per task: all of a pair's when the call has pairs enough to fill launches, fewer when it has not, never more than the
+// counter bound allows, at least one.
+inline int shk_task_blocks(const ShkLayout layout, const int shots_x, const long long shots_y, const long long n_pairs) {
+  const long long nxb = shk_x_blocks(shots_x);
+  const long long fill = std::max(1ll, nxb * n_pairs / SHK_LAUNCH_TASKS);
+  return (int)std::max(1ll, std::min({nxb, fill, shk_max_blocks(layout, shots_y)}));
+}
+QK_HD constexpr int shk_pair_tasks(const int shots_x, const int task_blocks) { return (shk_x_blocks(shots_x) + task_blocks - 1) / task_blocks; }
+// task t of a pair batch: pair t / pair_tasks of the batch and the x blocks [b0, b1)
+QK_HD inline void shk_task(const long long t, const int shots_x, const int task_blocks, long long& pair, int& b0, int& b1) {
+  const int nt = shk_pair_tasks(shots_x, task_blocks), nxb = shk_x_blocks(shots_x);
+  pair = t / nt;
+  b0 = (int)(t % nt) * task_blocks;
+  b1 = b0 + task_blocks < nxb ? b0 + task_blocks : nxb;
+}
+// A wave's units inside a staging pass: (x block of the task, piece of the bn staged records), pieces so that every wave has a unit
+// when the task has fewer blocks than waves.
+QK_HD constexpr int shk_parts(const int blocks, const int waves) { return blocks >= waves ? 1 : (waves + blocks - 1) / blocks; }
+QK_HD constexpr int shk_part_lo(const int p, const int parts, const int bn) {
+  const int per = (bn + parts - 1) / parts;
+  return p * per < bn ? p * per : bn;
+}
+// Pairs per batch: per pair its entry (8 bytes), the per-task rows, the total row and the equal-shot row (bins int64 each) within
+// `room` bytes, at least one.
+inline long long shk_batch_pairs(const long long room, const int n, const int pair_tasks) {
+  return std::max(1ll, room / (8 + (long long)(pair_tasks + 2) * shk_bins(n) * 8));
 }
 
 }  // namespace qkl

@@ -109,6 +109,7 @@ _SIGNATURES = [
     ("qk_block_self_host", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_sample_host", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint64, C.c_int64, _P, _P]),
     ("qk_shot_block_sums_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("qk_shadow_hist_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
@@ -398,6 +399,133 @@ def shot_block_estimate(sums, per_setting, settings, shots_per_setting, self_mas
         return O, np.full(O.shape, np.nan)
     S = np.asarray(per_setting).astype(np.float64) / N[..., None]
     return O, S.std(axis=-1, ddof=1) / np.sqrt(U)
+
+
+SHADOW_MAX_QUBITS = 128
+
+
+def _popcount32(v: np.ndarray) -> np.ndarray:
+    """bits set in every element of a uint32 array, as int64 (sums of bit fields: no table, no wider temporary)"""
+    v = np.asarray(v, dtype=np.uint32)
+    v = v - ((v >> np.uint32(1)) & np.uint32(0x55555555))
+    v = (v & np.uint32(0x33333333)) + ((v >> np.uint32(2)) & np.uint32(0x33333333))
+    v = (v + (v >> np.uint32(4))) & np.uint32(0x0F0F0F0F)
+    return ((v * np.uint32(0x01010101)) >> np.uint32(24)).astype(np.int64)
+
+
+def pack_shadow_words(bits, bases) -> np.ndarray:
+    """The packed record of every shot of ``bits`` (..., n_qubits) measured in ``bases`` (broadcast against ``bits``; codes 1, 2, 3 =
+    X, Y, Z): uint32 of shape (..., groups, 3) with groups = ceil(n / 32).  Bit k % 32 of group k // 32 holds the outcome bit
+    (plane 0), ``code & 1`` (plane 1) and ``code >> 1`` (plane 2) of qubit k; pad bits are 0 in all planes.  Raises ``ValueError`` on
+    a bit other than 0 or 1 or a code outside 1..3."""
+    b = np.asarray(bits)
+    if b.ndim < 1 or b.shape[-1] < 1 or b.dtype.kind not in "iub":
+        raise ValueError(f"bits must be an integer array whose last axis is the qubits, got shape {b.shape}, dtype {b.dtype}")
+    c = np.asarray(bases)
+    if c.dtype.kind not in "iu":
+        raise ValueError(f"bases must be an integer array, got dtype {c.dtype}")
+    try:
+        c = np.broadcast_to(c, b.shape)
+    except ValueError:
+        raise ValueError(f"bases of shape {c.shape} do not broadcast against bits of shape {b.shape}") from None
+    n = b.shape[-1]
+    if n > SHADOW_MAX_QUBITS:
+        raise ValueError(f"a shadow record holds at most {SHADOW_MAX_QUBITS} qubits (got {n})")
+    b, c = b.astype(np.int64), c.astype(np.int64)
+    if b.size and (b.min() < 0 or b.max() > 1):
+        raise ValueError("bits holds a value other than 0 or 1")
+    if c.size and (c.min() < 1 or c.max() > 3):
+        raise ValueError("bases holds a code outside 1..3 = X, Y, Z")
+    groups = (n + 31) // 32
+    planes = np.zeros(b.shape[:-1] + (groups * 32, 3), dtype=np.int64)
+    planes[..., :n, 0], planes[..., :n, 1], planes[..., :n, 2] = b, c & 1, c >> 1
+    planes = planes.reshape(b.shape[:-1] + (groups, 32, 3))
+    return (planes << np.arange(32, dtype=np.int64)[:, None]).sum(axis=-2).astype(np.uint32)
+
+
+def _shadow_tables(bits, bases, name: str):
+    """(bits (ns, T, n), bases as given, per_state) of one side of a shadow call"""
+    b = _shot_bits(bits, "bits_" + name)
+    c = np.asarray(bases)
+    if c.dtype.kind not in "iu" or c.shape not in (b.shape[1:], b.shape):
+        raise ValueError(f"bases_{name} must be an integer array of shape {b.shape[1:]} (shared) or {b.shape} (per state), got shape {c.shape}, dtype {c.dtype}")
+    return b, c, int(c.ndim == 3)
+
+
+def _shadow_d(rx: np.ndarray, ry: np.ndarray) -> np.ndarray:
+    """d of records that broadcast against each other, (..., groups, 3) -> (...)"""
+    eq = ~(rx[..., 1] ^ ry[..., 1]) & ~(rx[..., 2] ^ ry[..., 2]) & (rx[..., 1] | rx[..., 2])
+    return (_popcount32(eq) - 2 * _popcount32(eq & (rx[..., 0] ^ ry[..., 0]))).sum(axis=-1)
+
+
+def shadow_hist(bits_x, bases_x, bits_y, bases_y, pairs, equal=False):
+    """The shot-pair histograms of the classical-shadow kernel (Huang et al., Science 377, eabk3333 (2022)) in plain numpy -- the
+    mirror of ``Context.shadow_hist_host``, the same integers from the packed records (``pack_shadow_words``) and a popcount table.
+    ``bits_x`` (nx, T_x, n) was measured in ``bases_x``, (T_x, n) shared by every state or (nx, T_x, n) per state; ``bits_y``,
+    ``bases_y`` likewise (both ``None``: Y is X); ``pairs`` (n_pairs, 2) lists (x index, y index).  Two shots enter through
+        d = #(qubits in the same basis with the same outcome) - #(same basis, other outcome),   sum_k tr(sigma_k sigma'_k) = n/2 + 4.5 d
+        H[p, d + n] = #{(t, t') : d(x_i shot t, y_j shot t') = d}          int64 (n_pairs, 2 n + 1), sum_d H[p] = T_x T_y
+    ``equal=True`` also returns the histogram over the pairs t = t' alone (it needs T_x == T_y)."""
+    bx, cx, _ = _shadow_tables(bits_x, bases_x, "x")
+    if bits_y is None:
+        if bases_y is not None:
+            raise ValueError("bases_y is given but bits_y is None (Y is X)")
+        by, cy = bx, cx
+    else:
+        if bases_y is None:
+            raise ValueError("bits_y is given but bases_y is None")
+        by, cy, _ = _shadow_tables(bits_y, bases_y, "y")
+    n = bx.shape[2]
+    if by.shape[2] != n:
+        raise ValueError(f"bits_x and bits_y differ in qubits: {bx.shape} and {by.shape}")
+    if equal and bx.shape[1] != by.shape[1]:
+        raise ValueError(f"equal needs as many shots in x as in y (got {bx.shape[1]} and {by.shape[1]})")
+    P = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if P.size and (P.min() < 0 or P[:, 0].max() >= bx.shape[0] or P[:, 1].max() >= by.shape[0]):
+        raise ValueError(f"pairs holds an index outside the {bx.shape[0]} x {by.shape[0]} states")
+    rx = pack_shadow_words(bx, cx)
+    ry = rx if bits_y is None else pack_shadow_words(by, cy)
+    H = np.zeros((len(P), 2 * n + 1), dtype=np.int64)
+    E = np.zeros_like(H) if equal else None
+    for e, (i, j) in enumerate(P):
+        rows = max(1, (1 << 21) // max(1, ry.shape[1] * ry.shape[2]))  # x shots at a time: temporaries of a few MiB
+        for t0 in range(0, rx.shape[1], rows):
+            H[e] += np.bincount((_shadow_d(rx[i][t0 : t0 + rows, None], ry[j][None, :]) + n).ravel(), minlength=2 * n + 1)
+        if equal:
+            E[e] = np.bincount(_shadow_d(rx[i], ry[j]) + n, minlength=2 * n + 1)
+    return (H, E) if equal else H
+
+
+def shadow_inner(H, n_qubits: int, gamma=1.0, equal=None, weights=None) -> np.ndarray:
+    """The weighted mean of a function of d over the shot pairs of a histogram ``H`` (..., 2 n + 1) of ``shadow_hist``:
+        inner = sum_d H[..., d + n] w(d) / sum_d H[..., d + n]
+    ``weights=None`` is the shadow kernel's inner sum, w(d) = exp(gamma / n (n/2 + 4.5 d)) = exp(gamma / n sum_k tr(sigma_k sigma'_k));
+    an array of 2 n + 1 weights (index d + n) or a callable of the integer array d is taken instead.  With ``equal`` (the histogram of
+    the pairs t = t') the mean is over ``H - equal``, the T (T - 1) pairs of different shots.  ``H`` alone keeps the Gram of a
+    symmetric call positive semi-definite exactly -- it is an inner product of mean feature vectors -- but carries the t = t' pairs,
+    which share their bases when the tables were measured in one shared bases table."""
+    n = int(n_qubits)
+    H = np.asarray(H)
+    if H.shape[-1] != 2 * n + 1:
+        raise ValueError(f"H must have 2 n + 1 = {2 * n + 1} bins on its last axis, got shape {H.shape}")
+    d = np.arange(-n, n + 1)
+    if weights is None:
+        w = np.exp(float(gamma) / n * (0.5 * n + 4.5 * d))
+    elif callable(weights):
+        w = np.asarray(weights(d), dtype=np.float64)
+    else:
+        w = np.asarray(weights, dtype=np.float64)
+    if w.shape != (2 * n + 1,):
+        raise ValueError(f"weights must give 2 n + 1 = {2 * n + 1} values, got shape {w.shape}")
+    if equal is not None:
+        H = H - np.asarray(equal)
+    return (H * w).sum(axis=-1) / H.sum(axis=-1)
+
+
+def shadow_kernel(H, n_qubits: int, gamma=1.0, tau=1.0, equal=None) -> np.ndarray:
+    """The shadow kernel from shot-pair histograms: ``exp(tau * shadow_inner(H, n_qubits, gamma, equal))`` (the paper: tau = gamma =
+    1), pure numpy, any leading shape (..., 2 n + 1)."""
+    return np.exp(float(tau) * shadow_inner(H, n_qubits, gamma, equal))
 
 
 def bases_table(bases, shots: int, n_qubits: int) -> np.ndarray:
@@ -1460,6 +1588,58 @@ class Context:
         O, E = vals.reshape(-1, ny, nx), errs.reshape(-1, ny, nx)
         (Sx, Ex), (Sy, Ey) = self_of(bx), self_of(by)
         return ((O, Sx, Sy), (E, Ex, Ey)) if stderr else (O, Sx, Sy)
+
+    def shadow_hist_host(self, bits_x, bases_x, bits_y=None, bases_y=None, pairs=(), equal: bool = False):
+        """``engine.shadow_hist`` on the device (``qk_shadow_hist_host``): the same int64 histograms, bit for bit.  ``bits_x``
+        (nx, T_x, n) with ``bases_x`` (T_x, n) shared or (nx, T_x, n) per state, ``bits_y``/``bases_y`` likewise (both ``None``: Y is
+        X), the pairs (x index, y index) of ``pairs`` in any order; n <= 128.  Returns H (n_pairs, 2 n + 1), with ``equal=True`` also
+        the histogram of the pairs t = t' (T_x == T_y).  It needs no MPS set.  Synchronous."""
+        bx, cx, xps = _shadow_tables(bits_x, bases_x, "x")
+        bx, cx = np.ascontiguousarray(bx, dtype=np.uint8), np.ascontiguousarray(cx, dtype=np.uint8)
+        by = cy = None
+        yps = 0
+        if bits_y is not None:
+            if bases_y is None:
+                raise ValueError("bits_y is given but bases_y is None")
+            by, cy, yps = _shadow_tables(bits_y, bases_y, "y")
+            by, cy = np.ascontiguousarray(by, dtype=np.uint8), np.ascontiguousarray(cy, dtype=np.uint8)
+            if by.shape[2] != bx.shape[2]:
+                raise ValueError(f"bits_x and bits_y differ in qubits: {bx.shape} and {by.shape}")
+        elif bases_y is not None:
+            cy = np.ascontiguousarray(np.asarray(bases_y), dtype=np.uint8)  # (rejected by the entry point: Y is X)
+        nx, tx, n = bx.shape
+        ny, ty = (nx, tx) if by is None else by.shape[:2]
+        P = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), dtype=np.int32)
+        H = np.zeros((max(len(P), 1), 2 * n + 1), dtype=np.int64)  # (a spare row: the pointers stay valid)
+        E = np.zeros_like(H) if equal else None
+        pp = P if len(P) else np.zeros((1, 2), dtype=np.int32)
+        _check(lib().qk_shadow_hist_host(self._h, n, nx, tx, bx.ctypes.data, cx.ctypes.data, xps, ny, ty, None if by is None else by.ctypes.data,
+                                         None if cy is None else cy.ctypes.data, yps, len(P), pp.ctypes.data, H.ctypes.data, None if E is None else E.ctypes.data),
+               "qk_shadow_hist_host")
+        H = np.ascontiguousarray(H[: len(P)])
+        return (H, np.ascontiguousarray(E[: len(P)])) if equal else H
+
+    def shadow_hists(self, bits_x, bases_x, bits_y=None, bases_y=None, equal: bool = False):
+        """The shot-pair histograms of every pair of two outcome tables, int64 of shape (ny, nx, 2 n + 1), what ``shadow_inner`` and
+        ``shadow_kernel`` take: ``H[j, i]`` is the histogram of (x_i, y_j).  A symmetric call (``bits_y=None``) computes the pairs
+        i <= j and mirrors them -- d is symmetric in its two shots -- and its diagonal holds the self pairs.  ``equal=True`` returns
+        ``(H, E)`` with E the histograms of the pairs t = t' in the same shape.  Synchronous."""
+        nx, n = _shot_bits(bits_x, "bits_x").shape[0], np.asarray(bits_x).shape[2]
+        if bits_y is None:
+            iu = np.triu_indices(nx)
+            pairs = np.stack([iu[0], iu[1]], axis=1)  # i <= j
+            out = self.shadow_hist_host(bits_x, bases_x, None, bases_y, pairs, equal)
+            res = []
+            for src in out if equal else (out,):
+                dst = np.zeros((nx, nx, 2 * n + 1), dtype=np.int64)
+                dst[pairs[:, 1], pairs[:, 0]] = src
+                dst[pairs[:, 0], pairs[:, 1]] = src
+                res.append(dst)
+            return tuple(res) if equal else res[0]
+        ny = _shot_bits(bits_y, "bits_y").shape[0]
+        jj, ii = np.divmod(np.arange(ny * nx), nx)
+        out = self.shadow_hist_host(bits_x, bases_x, bits_y, bases_y, np.stack([ii, jj], axis=1), equal)
+        return tuple(o.reshape(ny, nx, 2 * n + 1) for o in out) if equal else out.reshape(ny, nx, 2 * n + 1)
 
     def bond_spectra(self, mps_set: MpsSet, max_values: int | None = None, norms: bool = False):
         """Entanglement spectra of every state of an fp64 set: the Schmidt weights (eigenvalues of the reduced state, descending, sum

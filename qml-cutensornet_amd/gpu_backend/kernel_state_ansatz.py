@@ -897,6 +897,124 @@ def build_block_kernel_matrices(mpi_comm, ansatz, X, Y=None, widths=None, side="
     return out
 
 
+def _shadow_share(mpi_comm, ctx, shares, n_qubits, n_procs, rank, shots, shot_seed, bases):
+    """The pair share of ``build_shadow_kernel_matrix``: the all-gathered (pairs, histograms, equal-shot histograms) of every rank.
+    Each rank samples its share of the states, the packed records (12 bytes per 32 qubits per shot) and the bond tables are
+    all-gathered, and each rank counts its share of the pairs of ``Plan(orient=False)``."""
+    groups = (n_qubits + 31) // 32
+    tables, dims, first = [], [], 0
+    for total, lo, loc, _, _ in shares:  # X, then Y: the states of Y are indexed after those of X
+        if loc is None:
+            recs, d = np.zeros((0, shots, groups, 3), dtype=np.uint32), np.zeros((0, n_qubits + 1), dtype=np.int32)
+        else:
+            bits = ctx.sample(loc, shots, bases=bases, seed=shot_seed, first_state=first + int(lo))
+            recs, d = _engine.pack_shadow_words(bits, bases), np.asarray(loc.dims, dtype=np.int32)
+        full_r, full_d = np.zeros((total, shots, groups, 3), dtype=np.uint32), np.zeros((total, n_qubits + 1), dtype=np.int32)
+        for s_lo, s_r, s_d in comm_allgather(mpi_comm, (int(lo), recs, d)):
+            full_r[s_lo : s_lo + len(s_r)], full_d[s_lo : s_lo + len(s_d)] = s_r, s_d
+        # plane 0 of the records back as an outcome table: bit k % 32 of group k // 32 is qubit k
+        k = np.arange(n_qubits)
+        tables.append(np.ascontiguousarray(((full_r[:, :, k // 32, 0] >> (k % 32).astype(np.uint32)) & np.uint32(1)).astype(np.uint8)))
+        dims.append(full_d)
+        first += total
+    bx, by = tables[0], tables[1] if len(tables) > 1 else None
+    plan = _engine.Plan(dims[0], None if by is None else dims[1], n_procs, rank, orient=False)
+    try:
+        pairs = plan.pairs()
+    finally:
+        plan.close()
+    if len(pairs):
+        H, E = ctx.shadow_hist_host(bx, bases, by, None if by is None else bases, pairs, equal=True)
+    else:
+        H = E = np.zeros((0, 2 * n_qubits + 1), dtype=np.int64)
+    return comm_allgather(mpi_comm, (pairs, H, E))
+
+
+def build_shadow_kernel_matrix(mpi_comm, ansatz, X, Y=None, shots=None, shot_seed=0, shadow_gamma=1.0, shadow_tau=1.0, skip_equal_shots=True, truncation_error=None,
+                               info_file=None, return_hist=False):
+    """The classical-shadow kernel of Huang, Kueng, Torlai, Albert and Preskill (Science 377, eabk3333 (2022)) from ``shots``
+    randomised-measurement shots per state, all n qubits of every shot:
+        K[j, i] = exp(shadow_tau * mean over the shot pairs (t, t') of exp(shadow_gamma / n * sum_k tr(sigma_k(x_i, t) sigma_k(y_j, t'))))
+    with sigma = 3 |s><s| - I the single-qubit shadow of a shot (the paper: gamma = tau = 1).  A shot pair enters only through the
+    integer d = (qubits measured in the same basis with the same outcome) - (same basis, other outcome), so the device counts the
+    exact histogram of d for every pair of states (``Context.shadow_hist_host``) and the weights are applied on the host
+    (``engine.shadow_kernel``): a scan over gamma and tau needs the histograms once (``return_hist=True``).
+
+    Each rank builds its share of the states and samples it in ``engine.random_bases(shots, num_qubits, shot_seed)`` with
+    ``Context.sample(..., seed=shot_seed, first_state=<the share's offset>)`` (the states of Y are indexed after those of X); the
+    packed records (12 bytes per 32 qubits per shot) and the bond tables are all-gathered instead of the states, and each rank
+    counts its share of the pairs of ``Plan(orient=False)``.  Rank 0 returns K of shape (len(Y), len(X)) -- (len(X), len(X)) and
+    exactly symmetric when Y is None -- and with ``return_hist=True`` the tuple ``(K, {"hist": (ny, nx, 2 n + 1) int64, "equal":
+    the same shape})``; the other ranks return ``None``.  The counts are integers, so K is the same bits for any number of ranks.
+
+    Every state, of X and of Y, is measured in ONE shared bases table, because ``Context.sample`` takes one table for a whole set.
+    The shot pairs with t = t' therefore share their bases on every qubit (d has the full weight of n qubits instead of about n / 3)
+    and bias a cross-pair value at order 1 / shots.  ``skip_equal_shots=True`` (the default) removes exactly those ``shots`` pairs
+    from every entry, leaving the mean over the shots (shots - 1) pairs with t != t'; in a self pair they are a shot paired with
+    itself.  ``skip_equal_shots=False`` keeps every pair: the Gram of the inner mean is then positive semi-definite exactly (an inner
+    product of mean feature vectors).  Either way the diagonal of a symmetric K is the self pair's value, an estimate like the others,
+    not exactly 1 or any other constant.  ``shots`` must be an int >= 2; ``num_qubits > 128`` is a ``ValueError``."""
+    if Y is not None and len(X) < len(Y):
+        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    n_qubits = int(ansatz.num_qubits)
+    if n_qubits > _engine.SHADOW_MAX_QUBITS:
+        raise ValueError(f"the shadow kernel's records hold at most {_engine.SHADOW_MAX_QUBITS} qubits (num_qubits is {n_qubits})")
+    if isinstance(shots, bool) or not isinstance(shots, (int, np.integer)) or shots < 2:
+        raise ValueError(f"shots must be an int >= 2 (got {shots!r})")
+    shots = int(shots)
+    for name, v in (("shadow_gamma", shadow_gamma), ("shadow_tau", shadow_tau)):
+        if not np.isfinite(float(v)):
+            raise ValueError(f"{name} must be finite, got {v!r}")
+    X = np.asarray(X, dtype=np.float64)
+    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
+    fidelity = 1.0 - float(truncation_error)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    t_start = time.perf_counter()
+    ctx = _engine.default_context(device_id)
+    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
+    shares = [(len(X),) + tuple(_simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers))]
+    if Y is not None:
+        _say(is_root, "\nContracting the MPS of the circuits from the Y dataset...")
+        shares.append((len(Y),) + tuple(_simulate_share(ansatz, Y, rank, n_procs, fidelity, is_root, "Y", device_id, host_workers)))
+    ctx.trim()
+    build_secs = time.perf_counter() - t_start
+    try:
+        t0 = time.perf_counter()
+        parts = _shadow_share(mpi_comm, ctx, shares, n_qubits, n_procs, rank, shots, shot_seed, _engine.random_bases(shots, n_qubits, shot_seed))
+        sweep_secs = time.perf_counter() - t0
+    finally:
+        for s in shares:
+            if s[2] is not None:
+                s[2].close()
+    if not is_root:
+        return None
+    nx, ny = len(X), len(X) if Y is None else len(Y)
+    hist, equal = np.zeros((ny, nx, 2 * n_qubits + 1), dtype=np.int64), np.zeros((ny, nx, 2 * n_qubits + 1), dtype=np.int64)
+    for pairs, H, E in parts:
+        for dst, src in ((hist, H), (equal, E)):
+            dst[pairs[:, 1], pairs[:, 0]] = src
+            if Y is None:
+                dst[pairs[:, 0], pairs[:, 1]] = src
+    K = _engine.shadow_kernel(hist, n_qubits, shadow_gamma, shadow_tau, equal if skip_equal_shots else None)
+    if info_file is not None:
+        prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"],
+                "r0_circ_sim": [build_secs, "seconds"], "shadow_shots": [shots, "shots"], "r0_shadow_sweep": [sweep_secs, "seconds"],
+                "total_time": [time.perf_counter() - t_start, "seconds"]}
+        with open(info_file + ".json", "w") as fp:
+            json.dump(prof, fp, indent=4)
+    return (K, {"hist": hist, "equal": equal}) if return_hist else K
+
+
 def _depth_scan_share(ctx, ansatz, points, rank, n_procs, fidelity, depths, ends, is_root, label, host_workers):
     """This rank's slice of ``points`` (the chunks of ``_simulate_share``) at every depth of ``depths`` (ascending): (first index,
     {depth: packed device set, or None for an empty share}, {depth: fidelities}).  One launch of the device builder to the deepest

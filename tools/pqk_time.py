@@ -20,8 +20,13 @@ engine.setting_bases(U, M, n, 0), then ctx.shot_block_sums_host on the pairs of 
 outcome bytes, packs them and sums): shot_block_ms (the median; shot_block_ms_min and _max give the spread over the repetitions),
 shot_block_terms = pairs U M^2 n_widths, shot_block_terms_per_s, shot_block_over_block against block_values_ms of the same run, and per
 width the median off-diagonal estimate next to the exact one.
+``--shadow-shots T`` (with ``--shots``) adds the shot-pair histograms of the classical-shadow kernel: ctx.sample in
+engine.random_bases(T, n, 0), then ctx.shadow_hist_host on the pairs of the run's symmetric plan (the call uploads the outcome bytes,
+packs them, counts and downloads the histograms), after a warm-up: shadow_hist_ms (the median; shadow_hist_ms_min and _max give the
+spread over the repetitions), shadow_shot_pairs = pairs T^2, shadow_shot_pairs_per_s, shadow_over_sample against sample_ms of the same
+run, and the median off-diagonal entry of the shadow kernel at gamma = tau = 1.
 usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement] [--compress CHI]
-                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S]"""
+                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S [--shadow-shots T]]"""
 import argparse
 import json
 import os
@@ -108,9 +113,12 @@ def main():
     ap.add_argument("--block-widths", default=None, metavar="W1,W2,...", help="also time the block kernels of the first w qubits for these widths")
     ap.add_argument("--block-shots", default=None, metavar="U,M", help="with --block-widths: also time the block overlaps estimated from U settings of M shots")
     ap.add_argument("--shots", type=int, default=0, metavar="S", help="also time sample() with S shots per state in random bases")
+    ap.add_argument("--shadow-shots", type=int, default=0, metavar="T", help="with --shots: also time the shadow kernel's shot-pair histograms from T shots per state")
     args = ap.parse_args()
     if args.block_shots and not args.block_widths:
         ap.error("--block-shots needs --block-widths")
+    if args.shadow_shots and args.shots <= 0:
+        ap.error("--shadow-shots needs --shots (shadow_over_sample compares with its sample_ms)")
     gamma = args.gamma if args.gamma is not None else (0.1 if args.config == "cfg5" else 1.0)
     n, reps, d, npts = bench.CONFIGS[args.config]
     X = synthetic_features(npts, n, 5)
@@ -224,6 +232,28 @@ def main():
             "shots": int(args.shots), "sample_ms": round(sample_ms, 3), "sample_flops": sflops,
             "sample_tflops": round(sflops / (sample_ms * 1e-3) / 1e12, 3), "sample_over_local": round(sample_ms / local_ms, 4),
             "median_offdiag_pqk_shots": float(np.median(KS[off])),
+        })
+    if args.shadow_shots > 0:
+        T_sh = args.shadow_shots
+        sh_bases = engine.random_bases(T_sh, n, 0)
+        sh_bits = ctx.sample(xs, T_sh, bases=sh_bases, seed=0)
+        plan = engine.Plan(xs.dims, orient=False)
+        sh_pairs = plan.pairs()
+        plan.close()
+        ctx.shadow_hist_host(sh_bits, sh_bases, pairs=sh_pairs)  # warm-up
+        ts = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            H = ctx.shadow_hist_host(sh_bits, sh_bases, pairs=sh_pairs)
+            ts.append(1e3 * (time.perf_counter() - t0))
+        shadow_ms = float(np.median(ts))
+        shot_pairs = len(sh_pairs) * T_sh * T_sh
+        KSH = engine.shadow_kernel(H, n)
+        dist.update({
+            "shadow_shots": T_sh, "shadow_reps": args.reps, "shadow_pairs": int(len(sh_pairs)), "shadow_hist_ms": round(shadow_ms, 3),
+            "shadow_hist_ms_min": round(min(ts), 3), "shadow_hist_ms_max": round(max(ts), 3), "shadow_shot_pairs": shot_pairs,
+            "shadow_shot_pairs_per_s": round(shot_pairs / (shadow_ms * 1e-3), 1), "shadow_over_sample": round(shadow_ms / dist["sample_ms"], 4),
+            "median_offdiag_shadow": float(np.median(KSH[sh_pairs[:, 0] != sh_pairs[:, 1]])),
         })
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
