@@ -1,3 +1,4 @@
+import functools
 import os
 
 import numpy as np
@@ -84,6 +85,100 @@ def many_pair_symmetric(name, xs, ys):
     nx, ny = len(xs), len(ys)
     k = next(k for k in range(ny + 1) if (nx + k) * (nx + k + 1) // 2 >= nx * ny or k == ny)
     return xs + ys[:k]
+
+
+# ------------------------------------------------------------------ general-gauge states for the local sweeps and the sampler
+# ``random_mps`` is right-orthonormal (R_k = 1) and builder output is mixed-canonical (one of L_k, R_k is the identity, the other a
+# real diagonal), so neither tells a kernel that reads R transposed, conjugated or from the wrong plane from a right one.  The
+# twins below hold the same states in a gauge where every L_k and R_k is dense and complex (tests/test_gauge_inputs_host.py
+# asserts it), on bonds that cross the 16-row padding, the 64-wide blocks and, in ``gauge_set_300``, 300 (padded 304).
+PROFILES = [  # the 20-site profiles of tests/test_gpu_entanglement.py
+    [1, 2, 4, 8, 15, 16, 17, 32, 47, 48, 63, 64, 65, 128, 64, 32, 16, 8, 4, 2, 1],
+    [1, 2, 4, 8, 16, 31, 48, 64, 65, 33, 17, 9, 5, 3, 2, 1, 1, 1, 1, 1, 1],
+    [1, 2, 4, 8, 15, 8, 4, 2, 1, 1, 2, 3, 5, 9, 17, 16, 8, 4, 2, 2, 1],
+]
+PROFILE_300 = [1, 2, 4, 8, 16, 32, 64, 128, 200, 300, 150, 75, 38, 19, 10, 5, 3, 2, 1]
+
+
+def scrambled(mps, rng, scale=1.0, grow=0):
+    """The bounded gauge of tests/test_entanglement_host.py (G = U diag(d) V, d in [0.5, 2], cond <= 4) on every bond; with
+    ``grow`` the bond becomes that much wider than before (G is chi x (chi + grow), its pseudo-inverse goes into the next site)."""
+    import qml_cutensornet_amd as Q
+
+    ts = [np.array(t, dtype=np.complex128) for t in mps.tensors]
+    for k in range(1, len(ts)):
+        chi = ts[k].shape[0]
+        big = chi + grow
+        u, _ = np.linalg.qr(rng.standard_normal((chi, chi)) + 1j * rng.standard_normal((chi, chi)))
+        v, _ = np.linalg.qr(rng.standard_normal((big, big)) + 1j * rng.standard_normal((big, big)))
+        d = rng.uniform(0.5, 2.0, chi)
+        ts[k - 1] = np.tensordot(ts[k - 1], (u * d) @ v[:chi], axes=(2, 0))
+        ts[k] = np.tensordot(v[:chi].conj().T @ ((1.0 / d)[:, None] * u.conj().T), ts[k], axes=(1, 0))
+    ts[0] = ts[0] * scale
+    return Q.MPS(ts)
+
+
+@functools.lru_cache(maxsize=None)
+def gauge_sets(seed=135):
+    """(originals, twins): six ``random_mps(20, PROFILES[k % 3])`` and the same states gauge-scrambled, every second one scaled by
+    3.7.  One generator, state by state (original k, twin k, original k + 1, ...): with seed 135 the twins are the mixed set of
+    tests/test_gpu_compress.py."""
+    import qml_cutensornet_amd as Q
+
+    rng = np.random.default_rng(seed)
+    originals, twins = [], []
+    for k in range(6):
+        originals.append(Q.random_mps(20, PROFILES[k % 3], rng))
+        twins.append(scrambled(originals[-1], rng, scale=3.7 if k % 2 else 1.0))
+    return tuple(originals), tuple(twins)
+
+
+@functools.lru_cache(maxsize=None)
+def gauge_set_300(seed=300):
+    """(originals, twins): two ``random_mps`` on the 18-site PROFILE_300 and their scrambled twins, the second scaled by 3.7."""
+    import qml_cutensornet_amd as Q
+
+    rng = np.random.default_rng(seed)
+    originals, twins = [], []
+    for k in range(2):
+        originals.append(Q.random_mps(18, PROFILE_300, rng))
+        twins.append(scrambled(originals[-1], rng, scale=3.7 if k % 2 else 1.0))
+    return tuple(originals), tuple(twins)
+
+
+SHOTS = 70  # of the sampler's cases: one full tile of 64 shots and a ragged one of 6
+GAUGE_SAMPLE = {"g20": (41, 7), "g300": (45, 11)}  # name: (seed of the bases, seed of the draws), chosen on the CPU: see below
+
+
+def gauge_sample_case(name):
+    """(states, bases (SHOTS, n), seed, index of the first twin) of a sampler case: "g20" the six twins of ``gauge_sets``, "g300"
+    the two originals of ``gauge_set_300`` and then their twins.  State i is drawn with the global index i.  With these seeds no
+    draw of the host mirror sits within 1e-9 of its threshold, for the case and for the originals at the twins' indices
+    (tests/test_gauge_inputs_host.py asserts it; measured 5.6e-5 and 2.3e-4)."""
+    from qml_cutensornet_amd import engine
+
+    base_seed, seed = GAUGE_SAMPLE[name]
+    if name == "g20":
+        states, first = list(gauge_sets()[1]), 0
+    else:
+        originals, twins = gauge_set_300()
+        states, first = list(originals) + list(twins), len(originals)
+    return states, engine.random_bases(SHOTS, len(states[0]), base_seed), seed, first
+
+
+def environments(tensors):
+    """Plain einsum environments of one state: (L, R), lists of n + 1 matrices; L[k][ket][bra] of the sites before bond k, R[k] of
+    the sites after it."""
+    ts = [np.asarray(t, dtype=np.complex128) for t in tensors]
+    n = len(ts)
+    L, R = [None] * (n + 1), [None] * (n + 1)
+    L[0] = np.ones((1, 1), dtype=np.complex128)
+    R[n] = np.ones((1, 1), dtype=np.complex128)
+    for k in range(n):
+        L[k + 1] = np.einsum("lm,lsr,msq->rq", L[k], ts[k], ts[k].conj(), optimize=True)
+    for k in range(n - 1, -1, -1):
+        R[k] = np.einsum("lsr,rq,msq->lm", ts[k], R[k + 1], ts[k].conj(), optimize=True)
+    return L, R
 
 
 def capped_dims(n, caps):

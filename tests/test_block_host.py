@@ -41,6 +41,17 @@ def block_sets(seed=3, nx=5, ny=4):
     return out
 
 
+WIDE_X_BONDS = (1, 2, 4, 8, 16, 32, 64, 130, 150, 97, 48, 24, 12, 6, 3, 2, 1)
+WIDE_Y_BONDS = (1, 2, 4, 8, 16, 31, 63, 113, 129, 65, 33, 17, 9, 5, 3, 2, 1)
+
+
+def wide_block_sets(seed=3, nx=3, ny=2):
+    """A second pair of sets, on 16 sites: bonds up to 150 and 129 (padded 160 and 144: three 64-blocks a side, unequal pads, K
+    that is no multiple of 8), every state on the profile as given, factors as in ``block_sets``."""
+    rng = np.random.default_rng(seed)
+    return [[gaussian_mps(bonds, rng, float(rng.uniform(0.5, 2.0))) for _ in range(count)] for bonds, count in ((WIDE_X_BONDS, nx), (WIDE_Y_BONDS, ny))]
+
+
 def dense_block_overlap(px, py, n, w, side):
     """tr(rho_A(x) rho_A(y)) from dense vectors (qubit 0 = most significant axis).  M[A, B] is the state as a matrix, rho_A = M M^H /
     <psi|psi>; where A is the larger half the same trace is taken as ||Mx^H My||_F^2, so no matrix exceeds 2^(n/2) rows."""

@@ -1,7 +1,8 @@
 """Block kernels on the MI355X: qk_block_values_host / qk_block_self_host against the host mirror ``MPS.block_overlap`` on identical
 tensors (12-site sets whose bonds cross the 16 padding and the 64-block edge, with unequal pad_x / pad_y and K that is no multiple
-of the K-tile), the identities of the contract on the device, the bit guarantees (a pair alone, a width subset, the batches cut by
-QK_BLOCK_BATCH, two runs, the plans of two ranks), short chains, the rejections, and build_block_kernel_matrices end to end.
+of the K-tile; 16-site sets with bonds up to 150 against 129: three 64-blocks a side), the identities of the contract on the device,
+the bit guarantees (a pair alone, a width subset, the batches cut by QK_BLOCK_BATCH, two runs, the plans of two ranks), short
+chains, the rejections, and build_block_kernel_matrices end to end.
 
 Bounds: 1e-11 absolute for HIP against the host on identical tensors (the values are <= 1), 1e-9 for a builder against another
 builder or the state-vector oracle."""
@@ -12,7 +13,7 @@ import qml_cutensornet_amd as Q
 from oracle import restatement as R
 from qml_cutensornet_amd import engine
 from qml_cutensornet_amd.dist import SingleComm, assemble_gram
-from test_block_host import SIDES, block_sets, dense_block_overlap, gaussian_mps
+from test_block_host import SIDES, block_sets, dense_block_overlap, gaussian_mps, wide_block_sets
 
 pytestmark = pytest.mark.gpu
 N = 12
@@ -75,6 +76,46 @@ def test_symmetric_against_host(gpu_ctx, dev, host_ref, side):
     # the diagonal of a symmetric call is block_self, bit for bit
     S = gpu_ctx.block_self(dx, None, side)
     assert np.array_equal(O[:, np.arange(5), np.arange(5)], S) and np.array_equal(Sx, S)
+
+
+@pytest.fixture(scope="module")
+def wide(gpu_ctx):
+    """The 16-site sets of ``wide_block_sets`` (three 64-blocks a side), per side: the device's rectangular and symmetric results
+    over all 16 widths, block_self, and the host mirror of each, computed once."""
+    xs, ys = wide_block_sets()
+    widths = list(range(1, 17))
+    out = {}
+    with gpu_ctx.upload(xs) as dx, gpu_ctx.upload(ys) as dy:
+        assert int(np.asarray(dx.dims).max()) == 150 and int(np.asarray(dy.dims).max()) == 129
+        for side in SIDES:
+            rO = np.array([[[x.block_overlap(y, w, side) for x in xs] for y in ys] for w in widths])
+            rOxx = np.zeros((16, len(xs), len(xs)))
+            for i in range(len(xs)):
+                for j in range(i, len(xs)):
+                    for w in widths:
+                        rOxx[w - 1, j, i] = rOxx[w - 1, i, j] = xs[i].block_overlap(xs[j], w, side)
+            rSy = np.array([[y.block_overlap(y, w, side) for y in ys] for w in widths])
+            out[side] = (gpu_ctx.block_overlaps(dx, dy, None, side), gpu_ctx.block_overlaps(dx, None, None, side), gpu_ctx.block_self(dx, None, side),
+                         (rO, rOxx, rSy))
+    return out
+
+
+@pytest.mark.parametrize("side", SIDES)
+def test_three_blocks_a_side_against_host(wide, side):
+    """Bonds up to 150 against 129 on 16 sites: three 64-blocks a side where ``block_sets`` has two, pads of 160 against 144, K =
+    130, 97, 113, 129.  Measured on the MI355X: max |dO| = 2.8e-16 (rectangular) and 1.3e-15 (symmetric, purities included), the values from
+    1.4e-7 to 0.66, so the absolute bound still resolves the smallest."""
+    (O, Sx, Sy), (Oxx, Sxx, _), S, (rO, rOxx, rSy) = wide[side]
+    assert O.shape == (16, 2, 3) and Oxx.shape == (16, 3, 3)
+    rSx = rOxx[:, np.arange(3), np.arange(3)]
+    errs = [float(np.abs(a - b).max()) for a, b in ((O, rO), (Sx, rSx), (Sy, rSy), (Oxx, rOxx))]
+    print(f"block overlaps vs MPS.block_overlap ({side}, three blocks a side): max |dO| = {errs[0]:.3e}, |dSx| = {errs[1]:.3e}, |dSy| = {errs[2]:.3e}, "
+          f"symmetric |dO| = {errs[3]:.3e}; reference values from {min(rO.min(), rOxx.min()):.2e} to {rO.max():.2e}")
+    assert max(errs) <= 1e-11
+    assert min(rO.min(), rOxx.min()) >= 1e-7  # a condition on the inputs: the absolute bound is at most 1e-4 of the smallest value
+    assert np.array_equal(Oxx, np.swapaxes(Oxx, 1, 2))
+    # the diagonal of a symmetric call is block_self, bit for bit
+    assert np.array_equal(Oxx[:, np.arange(3), np.arange(3)], S) and np.array_equal(Sxx, S)
 
 
 # ---- 2. the identities on the device -----------------------------------------------------------------------------------------

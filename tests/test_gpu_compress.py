@@ -26,18 +26,13 @@ import numpy as np
 import pytest
 
 import qml_cutensornet_amd as Q
-from helpers import golden_mps_sets
+from helpers import PROFILES, golden_mps_sets, scrambled
 from oracle import restatement as R
 from qml_cutensornet_amd import engine
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-PROFILES = [  # tests/test_gpu_entanglement.py
-    [1, 2, 4, 8, 15, 16, 17, 32, 47, 48, 63, 64, 65, 128, 64, 32, 16, 8, 4, 2, 1],
-    [1, 2, 4, 8, 16, 31, 48, 64, 65, 33, 17, 9, 5, 3, 2, 1, 1, 1, 1, 1, 1],
-    [1, 2, 4, 8, 15, 8, 4, 2, 1, 1, 2, 3, 5, 9, 17, 16, 8, 4, 2, 2, 1],
-]
 CASES = {  # name: (max_bond, max_discard)
     "cap1": (1, 0.0), "cap8": (8, 0.0), "cap16": (16, 0.0), "cap17": (17, 0.0), "cap48": (48, 0.0), "cap200": (200, 0.0),
     "budget1e-3": (None, 1e-3), "budget1e-8": (None, 1e-8),
@@ -50,22 +45,6 @@ def dense_state(tensors) -> np.ndarray:
     for t in tensors[1:]:
         psi = np.tensordot(psi, t, axes=(psi.ndim - 1, 0))
     return psi.reshape(-1)
-
-
-def scrambled(mps, rng, scale=1.0, grow=0):
-    """The bounded gauge of tests/test_entanglement_host.py (G = U diag(d) V, d in [0.5, 2], cond <= 4) on every bond; with
-    ``grow`` the bond becomes that much wider than before (G is chi x (chi + grow), its pseudo-inverse goes into the next site)."""
-    ts = [np.array(t, dtype=np.complex128) for t in mps.tensors]
-    for k in range(1, len(ts)):
-        chi = ts[k].shape[0]
-        big = chi + grow
-        u, _ = np.linalg.qr(rng.standard_normal((chi, chi)) + 1j * rng.standard_normal((chi, chi)))
-        v, _ = np.linalg.qr(rng.standard_normal((big, big)) + 1j * rng.standard_normal((big, big)))
-        d = rng.uniform(0.5, 2.0, chi)
-        ts[k - 1] = np.tensordot(ts[k - 1], (u * d) @ v[:chi], axes=(2, 0))
-        ts[k] = np.tensordot(v[:chi].conj().T @ ((1.0 / d)[:, None] * u.conj().T), ts[k], axes=(1, 0))
-    ts[0] = ts[0] * scale
-    return Q.MPS(ts)
 
 
 @functools.lru_cache(maxsize=None)

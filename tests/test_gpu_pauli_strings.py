@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import qml_cutensornet_amd as Q
-from helpers import golden_mps_sets
+from helpers import gauge_set_300, gauge_sets, golden_mps_sets
 from oracle import restatement as R
 from qml_cutensornet_amd import engine
 from test_pauli_strings_host import pair_strings, pauli_strings_from_dense, ref_pauli_strings, sparse_strings, weight_one_strings
@@ -86,6 +86,23 @@ def test_host_built_bonds_across_tiles(gpu_ctx):
     states = [Q.simulate(ans.circuit_for_data(x), 1 - 1e-16) for x in R.synthetic_features(4, 14, 3)]
     assert max(m.max_bond() for m in states) >= 64
     _check_against_reference(gpu_ctx, states, case_strings(14, np.random.default_rng(6)), label="(host-built, 14 qubits)")
+
+
+@pytest.mark.parametrize("sets,seed", [(gauge_sets, 135), (gauge_set_300, 300)], ids=["20-sites", "bond-300"])
+def test_general_gauge_twins(gpu_ctx, sets, seed):
+    """Twins with dense complex L_k and R_k at every bond (tests/test_gauge_inputs_host.py) against the reference on their own
+    tensors, and against their right-orthonormal originals on the device (the references of the two drift by <= 1e-13).
+    Measured on the MI355X: max |dV| = 7.8e-16 (20 sites) and 2.8e-16 (bond 300) on the twins, 5.6e-16 and 2.8e-16 on the originals;
+    twin against original 1.0e-15."""
+    originals, twins = sets()
+    n = len(twins[0])
+    S = case_strings(n, np.random.default_rng(seed))
+    V, nrm = _check_against_reference(gpu_ctx, list(twins), S, label=f"(general gauge, bonds up to {max(m.max_bond() for m in twins)})")
+    Vo, no = _check_against_reference(gpu_ctx, list(originals), S, label="(their right-orthonormal originals)")
+    scale = np.array([3.7**2 if k % 2 else 1.0 for k in range(len(twins))])
+    dV, dn = float(np.abs(V - Vo).max()), float(np.abs(nrm / scale / no - 1.0).max())
+    print(f"twin vs original on the device: |dV| = {dV:.3e}, norms {dn:.3e}")
+    assert dV < 1e-12 + 1e-13 and dn < 1e-12 + 1e-13
 
 
 # ---- 2. short chains ----------------------------------------------------------------------------------------------------

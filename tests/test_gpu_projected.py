@@ -1,6 +1,6 @@
 """Projected quantum kernel on the MI355X: the device local sweep (qk_local_paulis_host) against the numpy reference of
-tests/test_projected_host.py and exact state vectors, its bit-reproducibility, the PQK Gram kernel, and
-build_projected_kernel_matrix with one and two ranks."""
+tests/test_projected_host.py and exact state vectors, on canonical and on general-gauge states, its bit-reproducibility, the
+PQK Gram kernel, and build_projected_kernel_matrix with one and two ranks."""
 import os
 import sys
 
@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import qml_cutensornet_amd as Q
-from helpers import golden_mps_sets
+from helpers import gauge_set_300, gauge_sets, golden_mps_sets
 from oracle import restatement as R
 from test_projected_host import bloch_from_dense, ref_local_paulis, ref_projected_gram
 
@@ -56,6 +56,35 @@ def test_ragged_random_up_to_300_and_short_chains(gpu_ctx):
         _check_against_reference(gpu_ctx, [Q.random_mps(len(prof) - 1, prof, rng) for _ in range(2)])
     _check_against_reference(gpu_ctx, [Q.random_mps(1, [1, 1], rng) for _ in range(3)])
     _check_against_reference(gpu_ctx, [Q.random_mps(2, [1, 2, 1], rng) for _ in range(3)])
+
+
+def _worst_against_reference(F, norms, states):
+    """(max |dF|, max relative |d norm|) against the numpy reference on the same tensors."""
+    refs = [ref_local_paulis(m.tensors) for m in states]
+    return (max(float(np.abs(f - fr).max()) for f, (fr, _) in zip(F, refs)),
+            max(abs(nrm - nr) / nr for nrm, (_, nr) in zip(norms, refs)))
+
+
+@pytest.mark.parametrize("sets,alone", [(gauge_sets, 3), (gauge_set_300, 1)], ids=["20-sites", "bond-300"])
+def test_general_gauge_twins(gpu_ctx, sets, alone):
+    """States whose L_k and R_k are dense and complex at every bond (tests/test_gauge_inputs_host.py), bonds across 16, 48, 64, 128
+    and up to 300: the twins against the reference on their own tensors, against their right-orthonormal originals on the device
+    (the references of the two drift by <= 1e-13), and one twin alone against itself in the set, bit for bit.  Measured on the
+    MI355X: max |dF| = 1.1e-15 (20 sites) and 5.6e-16 (bond 300) on the twins, 1.1e-15 and 4.5e-16 on the originals; twin against
+    original 1.7e-15."""
+    originals, twins = sets()
+    Fo, no = _device_features(gpu_ctx, list(originals))
+    with gpu_ctx.upload(list(twins)) as s:
+        F, nrm = gpu_ctx.local_paulis(s, norms=True)
+    (ef, en), (eo, _) = _worst_against_reference(F, nrm, twins), _worst_against_reference(Fo, no, originals)
+    scale = np.array([3.7**2 if k % 2 else 1.0 for k in range(len(twins))])
+    dF, dn = float(np.abs(F - Fo).max()), float(np.abs(nrm / scale / no - 1.0).max())
+    print(f"general gauge, {len(twins)} states, bonds up to {max(m.max_bond() for m in twins)}: max |dF| vs reference = {ef:.3e} on the twins "
+          f"({eo:.3e} on the originals), norms {en:.3e}; twin vs original on the device: |dF| = {dF:.3e}, norms {dn:.3e}")
+    assert ef < 1e-12 and eo < 1e-12 and en < 1e-12
+    assert dF < 1e-12 + 1e-13 and dn < 1e-12 + 1e-13
+    F1, n1 = _device_features(gpu_ctx, [twins[alone]])
+    assert np.array_equal(F1[0], F[alone]) and n1[0] == nrm[alone]
 
 
 def test_product_states(gpu_ctx):

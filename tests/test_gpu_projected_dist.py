@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import qml_cutensornet_amd as Q
-from helpers import golden_mps_sets
+from helpers import gauge_sets, golden_mps_sets
 from oracle import restatement as R
 from qml_cutensornet_amd import engine
 from test_projected_dist_host import pair_dist_from_dense, pair_index, ref_pair_paulis_dist
@@ -92,6 +92,26 @@ def test_ragged_random_up_to_300_and_short_chains(gpu_ctx):
         for m, t, nr in zip(states, T, nrm):
             tr, nref = ref_pair_paulis_dist(m.tensors, 1)
             assert np.abs(t - tr).max() < 1e-12 and abs(nr - nref) < 1e-12 * nref
+
+
+def test_general_gauge_twins(gpu_ctx):
+    """Two twins of ``gauge_sets`` (dense complex L_k and R_k, bonds up to 128 and 65, the second scaled by 3.7) at max_dist = 3
+    against the reference on their own tensors (seconds per state, hence two), against their originals on the device, and the
+    distance-1 rows, the Bloch vectors and the norms against the neighbour calls on the twins, bit for bit.  Measured on the
+    MI355X: max |dT| = 1.3e-15 on the twins (distance 3), 1.7e-15 twin against original."""
+    D, n = 3, 20
+    originals, twins = (list(s[:2]) for s in gauge_sets())
+    T, nrm = _check_against_reference(gpu_ctx, twins, D)
+    To, no = _device_features(gpu_ctx, originals, D)
+    dT, dn = float(np.abs(T - To).max()), float(np.abs(nrm / np.array([1.0, 3.7**2]) / no - 1.0).max())
+    print(f"general gauge, D = {D}: twin vs original on the device: |dT| = {dT:.3e}, norms {dn:.3e}")
+    assert dT < 1e-12 + 1e-13 and dn < 1e-12 + 1e-13
+    with gpu_ctx.upload(twins) as s:
+        F, nrm1 = gpu_ctx.local_paulis(s, norms=True)
+        Tn = gpu_ctx.local_pair_paulis(s)
+        T3, F3, nrm3 = gpu_ctx.local_pair_paulis(s, singles=True, norms=True, max_dist=D)
+    assert np.array_equal(T3, T) and np.array_equal(T3[:, : n - 1], Tn)
+    assert np.array_equal(F3, F) and np.array_equal(nrm3, nrm1) and np.array_equal(nrm3, nrm)
 
 
 def test_product_states(gpu_ctx):

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import qml_cutensornet_amd as Q
-from helpers import golden_mps_sets
+from helpers import gauge_set_300, gauge_sets, golden_mps_sets
 from oracle import restatement as R
 from test_projected_pair_host import pair_from_dense, ref_pair_gram, ref_pair_paulis
 
@@ -61,6 +61,35 @@ def test_ragged_random_up_to_300_and_short_chains(gpu_ctx):
         _check_against_reference(gpu_ctx, [Q.random_mps(len(prof) - 1, prof, rng) for _ in range(2)])
     _check_against_reference(gpu_ctx, [Q.random_mps(2, [1, 2, 1], rng) for _ in range(3)])
     _check_against_reference(gpu_ctx, [Q.random_mps(2, [1, 1, 1], rng) for _ in range(3)])
+
+
+def _worst_against_reference(T, norms, states):
+    """(max |dT|, max relative |d norm|) against the numpy reference on the same tensors."""
+    refs = [ref_pair_paulis(m.tensors) for m in states]
+    return (max(float(np.abs(t - tr).max()) for t, (tr, _) in zip(T, refs)),
+            max(abs(nrm - nr) / nr for nrm, (_, nr) in zip(norms, refs)))
+
+
+@pytest.mark.parametrize("sets,alone", [(gauge_sets, 3), (gauge_set_300, 1)], ids=["20-sites", "bond-300"])
+def test_general_gauge_twins(gpu_ctx, sets, alone):
+    """The case of tests/test_gpu_projected.py for the pair sweep: twins with dense complex L_k and R_k against the reference on
+    their own tensors, against their originals on the device, one twin alone against itself in the set.  Measured on the MI355X:
+    max |dT| = 1.0e-15 (20 sites) and 7.8e-16 (bond 300) on the twins, 1.0e-15 and 5.5e-16 on the originals; twin against original
+    1.7e-15."""
+    originals, twins = sets()
+    To, no = _device_features(gpu_ctx, list(originals))
+    with gpu_ctx.upload(list(twins)) as s:
+        T, nrm = gpu_ctx.local_pair_paulis(s, norms=True)
+    (et, en), (eo, _) = _worst_against_reference(T, nrm, twins), _worst_against_reference(To, no, originals)
+    scale = np.array([3.7**2 if k % 2 else 1.0 for k in range(len(twins))])
+    dT, dn = float(np.abs(T - To).max()), float(np.abs(nrm / scale / no - 1.0).max())
+    print(f"general gauge, {len(twins)} states, bonds up to {max(m.max_bond() for m in twins)}: max |dT| vs reference = {et:.3e} on the twins "
+          f"({eo:.3e} on the originals), norms {en:.3e}; twin vs original on the device: |dT| = {dT:.3e}, norms {dn:.3e}")
+    assert np.all(T[:, :, 0, 0] == 1.0)
+    assert et < 1e-12 and eo < 1e-12 and en < 1e-12
+    assert dT < 1e-12 + 1e-13 and dn < 1e-12 + 1e-13
+    T1, n1 = _device_features(gpu_ctx, [twins[alone]])
+    assert np.array_equal(T1[0], T[alone]) and n1[0] == nrm[alone]
 
 
 def test_product_states(gpu_ctx):

@@ -1,8 +1,9 @@
 """Measurement shots on the MI355X: qk_sample_host against the host mirror ``MPS.sample`` on identical tensors -- the log probability
 of every drawn string to 1e-11 and, where no draw of the mirror sits on a threshold, the bits exactly --, against the Born
-probability of the dense state vector, circuits whose outcomes are certain, the bit guarantees (a state alone, the cut into chain
-batches, fewer shots, two runs, a device-built set), the rejections, and ``build_projected_kernel_matrix(shots=...)`` against the
-pipeline spelled out by hand, on one rank and on two."""
+probability of the dense state vector, general-gauge states with bonds up to 300 (dense complex R_k, several column blocks),
+circuits whose outcomes are certain, the bit guarantees (a state alone, the cut into chain batches, fewer shots, two runs, a device-
+built set), the rejections, and ``build_projected_kernel_matrix(shots=...)`` against the pipeline spelled out by hand, on one rank
+and on two."""
 import functools
 import os
 import sys
@@ -11,26 +12,31 @@ import numpy as np
 import pytest
 
 import qml_cutensornet_amd as Q
+from helpers import GAUGE_SAMPLE, SHOTS, gauge_sample_case, gauge_set_300, gauge_sets
 from oracle import restatement as R
 from qml_cutensornet_amd import engine
 from test_sample_host import ansatz_states, dense_of_mps, dense_probability
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHOTS = 70  # one full tile of 64 and a ragged one of 6
 
 
 @functools.lru_cache(maxsize=None)
 def cases():
     """name -> (states, bases (SHOTS, n), seed).  The seeds were chosen on the CPU so that no draw of the host mirror sits within
-    1e-9 of its threshold (test_bits_equal_the_mirror asserts it): the smallest margin of these draws is about 1e-4."""
+    1e-9 of its threshold (test_bits_equal_the_mirror asserts it): the smallest margin of these draws is about 1e-4.
+
+    "g20" and "g300" are the general-gauge cases of tests/helpers.py: states whose R_k is dense and complex at every bond, which the
+    canonical ones above never give the sampler (their R_k is the identity or a real diagonal), on bonds that make SMP_Q take several
+    column blocks and the draw loop run more than once (test_general_gauge_cases_cross_the_blocks)."""
     a12, _ = ansatz_states(12, 3, 6, 1)
     a12 = [a12[i] for i in (0, 1, 2, 5)]  # largest bonds 50, 30, 41, 50: no multiple of 16, both sides of 48
     a9, _ = ansatz_states(9, 2, 3, 21)
     rng = np.random.default_rng(12)
     two = [Q.random_mps(2, [1, 2, 1], rng) for _ in range(3)]
     one = [Q.random_mps(1, [1, 1], rng) for _ in range(2)]
-    return {"a12": (a12, engine.random_bases(SHOTS, 12, 41), 7), "a9": (a9, engine.random_bases(SHOTS, 9, 42), 8),
+    gauge = {name: gauge_sample_case(name)[:3] for name in GAUGE_SAMPLE}
+    return {**gauge, "a12": (a12, engine.random_bases(SHOTS, 12, 41), 7), "a9": (a9, engine.random_bases(SHOTS, 9, 42), 8),
             "two": (two, engine.random_bases(SHOTS, 2, 43), 2**40 + 9), "one": (one, engine.random_bases(SHOTS, 1, 44), 10)}
 
 
@@ -52,7 +58,10 @@ def device(gpu_ctx):
     return out
 
 
-@pytest.mark.parametrize("name", ["a12", "a9", "two", "one"])
+NAMES = ["a12", "a9", "two", "one", "g20", "g300"]
+
+
+@pytest.mark.parametrize("name", NAMES)
 def test_logp_against_the_mirror_and_the_dense_vector(device, name):
     states, bases, _ = cases()[name]
     bits, lp = device[name]
@@ -63,17 +72,53 @@ def test_logp_against_the_mirror_and_the_dense_vector(device, name):
     hbits, hlp, _ = mirror(name)
     print(f"{name}: max |logp_hip - logp_mirror| = {np.abs(lp - hlp).max():.3e} over {lp.size} shots, {int((bits != hbits).sum())} bits differ")
     assert np.abs(lp - hlp).max() <= 1e-11
+    if n > 18:  # the dense checks stay at 18 qubits or fewer
+        return
     for i, m in enumerate(states):
         exact = dense_probability(dense_of_mps(m), bits[i], bases)
         assert np.all(np.abs(np.exp(lp[i]) - exact) <= 1e-8 * exact)
 
 
-@pytest.mark.parametrize("name", ["a12", "a9", "two", "one"])
+@pytest.mark.parametrize("name", NAMES)
 def test_bits_equal_the_mirror(device, name):
     hbits, _, margins = mirror(name)
     # a condition on the inputs, not a tolerance: no draw of the mirror is closer than 1e-9 to its threshold
     assert min(margins) >= 1e-9, margins
     assert np.array_equal(device[name][0], hbits)
+
+
+def test_general_gauge_cases_cross_the_blocks(gpu_ctx):
+    """From the sets' own bond tables: padded bonds of 64, 80 and of 128 or more ("g300": 304), so SMP_Q has two to five column
+    blocks, SMP_W up to ten, and the 64-wide loops of the draw kernel run more than once."""
+    for name, want in (("g20", (64, 80, 128)), ("g300", (64, 128, 208, 304))):
+        with gpu_ctx.upload(cases()[name][0]) as xs:
+            pads = set(((np.asarray(xs.dims) + 15) // 16 * 16).ravel().tolist())
+        assert all(w in pads for w in want), (name, sorted(pads))
+        assert max(pads) >= 128
+
+
+@pytest.mark.parametrize("name", list(GAUGE_SAMPLE))
+def test_general_gauge_twins_draw_their_originals_bits(gpu_ctx, device, name):
+    """A twin and its right-orthonormal original are one state, and under equal global indices they take equal uniforms: equal
+    bits (no draw of either mirror is within 1e-9 of its threshold: tests/test_gauge_inputs_host.py) and |d logp| <= 1e-11, the bound
+    of the device against its mirror (the mirrors of the two drift by 3e-14).  Measured on the MI355X: |d logp| = 2.3e-14 ("g20") and
+    4.3e-14 ("g300"); against the mirror the two cases are at 2.5e-14 and 3.2e-14, no bit differs."""
+    _, bases, seed, first = gauge_sample_case(name)
+    originals = list((gauge_sets if name == "g20" else gauge_set_300)()[0])
+    with gpu_ctx.upload(originals) as xs:
+        bits, lp = gpu_ctx.sample(xs, SHOTS, bases=bases, seed=seed, first_state=first, logp=True)
+    tb, tl = device[name][0][first:], device[name][1][first:]
+    print(f"{name}: twin vs original on the device: {int((bits != tb).sum())} bits differ, max |d logp| = {np.abs(lp - tl).max():.3e}")
+    assert np.array_equal(bits, tb)
+    assert np.abs(lp - tl).max() <= 1e-11
+
+
+def test_general_gauge_batches_of_one_chain(gpu_ctx, device, monkeypatch):
+    states, bases, seed = cases()["g20"]
+    monkeypatch.setenv("QK_SAMPLE_BATCH", "1")  # 12 chains, one per batch
+    with gpu_ctx.upload(states) as xs:
+        bits, lp = gpu_ctx.sample(xs, SHOTS, bases=bases, seed=seed, logp=True)
+    assert np.array_equal(bits, device["g20"][0]) and np.array_equal(lp, device["g20"][1])
 
 
 def test_one_shot(gpu_ctx, device):
