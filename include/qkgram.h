@@ -449,6 +449,43 @@ int qk_block_values_host(qk_ctx* ctx, const qk_mps_set* xset, const qk_mps_set* 
 int qk_block_self_host(qk_ctx* ctx, const qk_mps_set* set, int32_t side, int32_t n_widths, const int32_t* widths,
                        double* out /* [n_widths][n_states]: S_w */, double* norms /* may be NULL; the bits of qk_local_paulis_host */);
 
+/* ---- windows of k qubits: reduced density matrices of contiguous blocks at every position -----------------------------------------
+ * The projected kernel of Huang et al. for k-qubit reduced density matrices, and the overlaps, purities and Renyi-2 entropies of
+ * interior blocks.  Conventions of the other local sweeps: site k is qubit k, physical index 0 = |0>, states need not be normalised,
+ * environments in the sweep's X[ket][bra] orientation, L_0 = R_n = 1, L_n[0][0] = <psi|psi>; fp64 sets only.
+ * Window (a, w) = the qubits a .. a+w-1, b = a + w, 1 <= w <= min(n_sites, 6), 0 <= a <= n_sites - w; the row index of rho is
+ * s = sum_j s_{a+j} 2^(w-1-j), so qubit a is the most significant bit:
+ *     rho_{a,w}[s][s'] = sum over all other sites of psi(.. s ..) conj(psi(.. s' ..)) / <psi|psi>
+ *     M^s[alpha][gamma] = (A_a^{s_a} A_{a+1}^{s_{a+1}} ... A_{b-1}^{s_{b-1}})[alpha][gamma]                          chi_a x chi_b
+ *     rho_{a,w}[s][s'] <psi|psi> = sum_{alpha,alpha',gamma,gamma'} L_a[alpha][alpha'] M^s[alpha][gamma] R_b[gamma][gamma'] conj(M^{s'}[alpha'][gamma'])
+ * Route: G_0 = 1, Gr_0 = R_b, G_{j+1}[beta][(t, sigma, gamma)] = sum_beta' A_c[beta][t][beta'] G_j[beta'][(sigma, gamma)] with c = b-1-j
+ * (likewise Gr), H[alpha'][(s, gamma)] = sum_alpha L_a[alpha][alpha'] G_w[alpha][(s, gamma)], and
+ * rho[s][s'] <psi|psi> = sum_{alpha, gamma'} Gr_w[alpha][(s, gamma')] conj(H[alpha][(s', gamma')]): about 5 2^w chi^3 complex
+ * multiply-adds per window on the matrix cores (4^w chi^3 with open environments) and 4^w chi^2 / 2 in the closing sum.
+ * Derived quantities are host arithmetic: O_a[j][i] = tr(rho_a(x_i) rho_a(y_j)) = Re sum rho_a(x_i)[s][s'] conj(rho_a(y_j)[s][s']),
+ * the purity S_a = O_a(x, x), K_w[j][i] = exp(-g sum_a ||rho_a(x_i) - rho_a(y_j)||_F^2) = qk_feature_gram_host at g over the columns
+ * (Re rho, Im rho); the Pauli coefficients c[p_0 .. p_{w-1}] = tr(rho P_{p_0} (x) .. (x) P_{p_{w-1}}) are real, in the convention of
+ * out2[k][p][q] above, and rho = 2^-w sum c P.  w = 1 and w = 2 agree with qk_local_paulis_host and the pair correlators to rounding;
+ * the purity of the window (0, w) is qk_bond_purities_host's at bond w.
+ *
+ * qk_window_rdms_host: rho[state][i] = rho_{starts[i], width}, complex128 with re and im interleaved; starts = NULL means every
+ * window 0 .. n_sites - width (n_starts is then ignored).  Guarantees: rho is exactly Hermitian (s <= s' is computed and the
+ * conjugate mirrored; the diagonal's imaginary part is exactly 0.0); tr rho = 1 to rounding; pad rows and columns never reach a
+ * result; a (state, window) value is the same bits whatever the other states of the set, the other windows asked for, the cut
+ * into batches and the run; no atomics, no grid barrier, no spin wait.  norms, when given, are the bits qk_local_paulis_host returns.
+ * Per state batch the environment pass of qk_pauli_strings_host, then one chain per (state, window) in chain batches: per step
+ * one GEMM launch for every chain of the batch (tasks (chain, 64 x 64 block)), one for H, one closing launch over (chain, 16-row
+ * chunk) and one kernel that adds the chunks in a fixed order.
+ * Device scratch: per state the sweep's planes and every L_k and R_k, and 8 2^w P^2 doubles per (state, window) of a batch (P = the
+ * state's largest padded bond) plus its partial sums, counted by the batching rule of qk_local_paulis_host (a quarter of the free
+ * memory; the windows of a state go in several batches when they do not fit) and released by qk_ctx_trim.  QK_WINDOW_BATCH=<k>
+ * (read per call) caps the (state, window) chains of a batch at k; the result is the same bits for every k.
+ * QK_EINVAL, naming the argument: a null ctx, set or rho; a set of another context; a complex64 set; a width outside
+ * 1 .. min(n_sites, 6); a start outside 0 .. n_sites - width; starts that are not strictly increasing; n_starts < 1 when starts
+ * are given.  QK_EDEVICE, naming the state: a state of norm 0.                                                                   */
+int qk_window_rdms_host(qk_ctx* ctx, const qk_mps_set* set, int32_t width, int32_t n_starts, const int32_t* starts /* NULL: 0 .. n_sites - width */,
+                        double* rho /* [n_states][n_windows][2^w][2^w] complex128, re/im interleaved */, double* norms /* [n_states], may be NULL */);
+
 /* ---- measurement shots: perfect sampling of every state of a set -----------------------------------------------------------------
  * qk_sample_host: bits[s][shot][k] = the outcome of measuring qubit k of state s in the Pauli basis bases[shot][k] (1..3 = X, Y, Z;
  * bit 0 = eigenvalue +1), n_shots independent shots per state; logp[s][shot], when given, = the log of the exact probability of

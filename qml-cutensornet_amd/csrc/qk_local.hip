@@ -7,7 +7,8 @@
 // qk_bond_purities_host and qk_bond_spectra_host (definitions above bond_call below), and the block kernels -- reduced-state
 // overlaps of the first or last w qubits for every pair of two sets -- qk_block_values_host and qk_block_self_host (definitions
 // above BlkSet below), and measurement shots of every state of a set, each shot and qubit in its own Pauli basis, qk_sample_host
-// (definitions above SmpArgs below), the block overlaps estimated from such shots, qk_shot_block_sums_host (above SbkArgs below), and the
+// (definitions above SmpArgs below), the reduced density matrices of every window of k qubits, qk_window_rdms_host (above WinArgs
+// below), the block overlaps estimated from such shots, qk_shot_block_sums_host (above SbkArgs below), and the
 // shot-pair histograms of the classical-shadow kernel, qk_shadow_hist_host (above ShkArgs below) (include/qkgram.h).
 //
 // Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
@@ -1612,6 +1613,286 @@ int sample_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_shots, const ui
   return QK_OK;
 }
 
+// ---- windows of k qubits (qk_window_rdms_host) ------------------------------------------------------------------------------------
+// Window (a, w) = the qubits a .. a+w-1, b = a + w, 1 <= w <= min(n, 6), 0 <= a <= n - w; row index s = sum_j s_{a+j} 2^(w-1-j)
+// (qubit a is the most significant bit).  Site k = qubit k, physical index 0 = |0>, states not necessarily normalised,
+// environments X[ket][bra], L_0 = R_n = 1, L_n[0][0] = <psi|psi>:
+//     rho_{a,w}[s][s'] = sum over all other sites of psi(.. s ..) conj(psi(.. s' ..)) / <psi|psi>
+//     M^s[alpha][gamma] = (A_a^{s_a} A_{a+1}^{s_{a+1}} .. A_{b-1}^{s_{b-1}})[alpha][gamma]                              chi_a x chi_b
+//     rho_{a,w}[s][s'] <psi|psi> = sum_{alpha,alpha',gamma,gamma'} L_a[alpha][alpha'] M^s[alpha][gamma] R_b[gamma][gamma'] conj(M^{s'}[alpha'][gamma'])
+// The route (every product is the C = A^T B form of the ring GEMM, nothing is transposed): the product of the sites grows from the
+// right, the new site's index most significant, from two seeds,
+//     G_0 = 1 (chi_b x chi_b),   Gr_0 = R_b
+//     G_{j+1}[beta][(t, sigma, gamma)] = sum_beta' A_c[beta][t][beta'] G_j[beta'][(sigma, gamma)]      c = b-1-j   (same for Gr)
+// with the reversed image's site c, [beta'][(t, beta)], as the A operand; the rows (t, beta) of C are written with ldc = twice the
+// stacked width at column offset t times the stacked width, so the next step reads its B operand as it lies.  G_1 is the site b-1
+// itself and costs nothing.  Then
+//     H[alpha'][(s, gamma)] = sum_alpha L_a[alpha][alpha'] G_w[alpha][(s, gamma)]
+//     rho[s][s'] <psi|psi>  = sum_{alpha, gamma'} Gr_w[alpha][(s, gamma')] conj(H[alpha][(s', gamma')])          (L_a is Hermitian)
+// About 5 2^w chi^3 complex multiply-adds per window in the GEMMs and 4^w chi^2 / 2 in the closing sum.  Per state batch the
+// environment pass of the Pauli strings (every L_k and R_k kept, the norms the bits of qk_local_paulis_host), then its chains -- one
+// per (state, window) -- in chain batches: per step j ONE GEMM launch for every chain of the batch (a task's block number also names
+// the seed and t), one for H, one closing launch over (chain, 16-row chunk of alpha) that forms every s <= s' in a fixed order, and
+// one kernel that adds the chunks in a fixed order, divides by L_n[0][0], mirrors the conjugate and writes rho: exactly Hermitian,
+// the diagonal's imaginary part exactly 0.0.  Pad rows and columns are zeros that the GEMMs themselves made.  Nothing of a chain
+// depends on another chain, no atomics, no grid barrier, no spin wait: a (state, window) value is the same bits whatever the other
+// states, the other windows, the cut into batches (QK_WINDOW_BATCH caps the chains of one) and the run.
+struct WinArgs {
+  LocArgs e;              // the set and the state batch of the environment pass
+  const int32_t* cent;    // chain -> batch entry
+  const int32_t* cwin;    // chain -> window (index into starts)
+  const int64_t* cbase;   // chain -> first double of its slot
+  const int32_t* starts;  // [n_windows]
+  const int2* tasks;      // this launch: (chain, block)
+  double* slots;
+  double* part;           // closing partial sums [chain][max chunks][win_vals(width)]
+  int width, n_windows;
+  int step;               // step j of WIN_G
+};
+
+// One 64 x 64 output block of one window chain's GEMM: a product of step j (WIN_G) or H (WIN_H).
+__global__ __launch_bounds__(512) void qk_win_gemm_kernel(const WinArgs g, const int kind) {
+  __shared__ __attribute__((aligned(16))) double lds[LOC_LDS_DOUBLES];
+  const int2 tk = g.tasks[blockIdx.x];
+  const int ch = __builtin_amdgcn_readfirstlane(tk.x);
+  int blk = __builtin_amdgcn_readfirstlane(tk.y);
+  const int i = __builtin_amdgcn_readfirstlane(g.cent[ch]);
+  const int w = g.width, a = __builtin_amdgcn_readfirstlane(g.starts[__builtin_amdgcn_readfirstlane(g.cwin[ch])]), b = a + w;
+  const int n = g.e.n_sites, n1 = n + 1;
+  const long long st = __builtin_amdgcn_readfirstlane(g.e.states[i]);
+  const int* pd = g.e.dims + st * n1;
+  const int* td = g.e.tru + st * n1;
+  const long long P = __builtin_amdgcn_readfirstlane(g.e.pmax[i]), P2 = P * P, U = win_unit(P, w);
+  double* const slot = g.slots + uni64(g.cbase[ch]);
+  const double* const env = g.e.scratch + uni64(g.e.sbase[i]) + g.e.rmul * P2;
+  const int pb = __builtin_amdgcn_readfirstlane(pd[b]);
+  const double *Are, *Aim, *Bre, *Bim;
+  double *Cre, *Cim;
+  int lda, ldb, ldc, M, N, K;
+  if (kind == WIN_G) {
+    const int j = g.step, c = b - 1 - j;
+    const int pc = __builtin_amdgcn_readfirstlane(pd[c]), pc1 = __builtin_amdgcn_readfirstlane(pd[c + 1]);
+    M = pc, N = pb << j, K = __builtin_amdgcn_readfirstlane(td[c + 1]);
+    const int per = ((M + 63) / 64) * ((N + 63) / 64);
+    const int q = blk / per, seed = q >> 1, t = q & 1;  // seed 0 = Gr, 1 = G
+    blk -= q * per;
+    Are = g.e.rev + uni64(g.e.offs[st * n + c]) + t * pc, Aim = Are + (long long)pc1 * 2 * pc, lda = 2 * pc;
+    if (seed == 0 && j == 0) {  // Gr_0 = R_b
+      Bre = env + uni64(g.e.roff[(long long)i * n1 + b]), Bim = Bre + (long long)pb * pb, ldb = pb;
+    } else if (seed == 1 && j == 1) {  // G_1 = the site b-1
+      Bre = g.e.data + uni64(g.e.offs[st * n + b - 1]), Bim = Bre + (long long)pc1 * 2 * pb, ldb = 2 * pb;
+    } else {
+      Bre = slot + (seed ? win_G(j) : win_Gr(j)) * U, Bim = Bre + U, ldb = N;
+    }
+    Cre = slot + (seed ? win_G(j + 1) : win_Gr(j + 1)) * U + (long long)t * N, Cim = Cre + U, ldc = 2 * N;
+  } else {  // WIN_H
+    const int pa = __builtin_amdgcn_readfirstlane(pd[a]);
+    M = pa, N = pb << w, K = __builtin_amdgcn_readfirstlane(td[a]);
+    Are = env + uni64(g.e.loff[(long long)i * n1 + a]), Aim = Are + (long long)pa * pa, lda = pa;
+    if (w == 1) {  // G_1 = the site a
+      Bre = g.e.data + uni64(g.e.offs[st * n + a]), Bim = Bre + (long long)pa * 2 * pb, ldb = 2 * pb;
+    } else {
+      Bre = slot + win_G(w) * U, Bim = Bre + U, ldb = N;
+    }
+    Cre = slot + win_H(w) * U, Cim = Cre + U, ldc = N;
+  }
+  const int npm = (M + 63) / 64;
+  const int m0 = 64 * (blk % npm), n0 = 64 * (blk / npm);
+  zgemm_ring3<false, LOC_KTL, LOC_NSLOT, true, 8, 64, double, 11>(Cre + (long long)m0 * ldc + n0, Cim + (long long)m0 * ldc + n0, ldc, Are + m0, Aim + m0, lda,
+                                                                   Bre + n0, Bim + n0, ldb, min(64, M - m0), min(64, N - n0), K, lds);
+}
+
+// The closing sums of one 16-row chunk of alpha, unnormalised: for every s <= s'
+//     part[(chain, chunk)][2 p], [2 p + 1] = (Re, Im) sum_{alpha in chunk, gamma'} Gr_w[alpha][(s, gamma')] conj(H[alpha][(s', gamma')]),   p = win_pair(s, s')
+// The workgroup takes WIN_CLOSE_GROUP = 16 pairs at a time, 16 lanes per pair: lane l adds the columns gamma' = l, l + 16, .. of
+// the chunk's rows in ascending (row, column) order (16 consecutive doubles per pair and row: whole 128-byte lines), then one
+// thread per (pair, Re | Im) adds the 16 lane sums in ascending order -- a fixed order, on the vector ALU.
+// LDS: red[2][16][17] doubles (4.3 KiB; the pad column keeps the 16 lanes of the final sums on different banks).
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_win_close_kernel(const WinArgs g) {
+  __shared__ double red[2][WIN_CLOSE_GROUP][17];
+  static_assert(WIN_CLOSE_GROUP * 16 == LOC_RED_THREADS, "16 lanes per pair of a group");
+  const int2 tk = g.tasks[blockIdx.x];
+  const int ch = tk.x, c = tk.y;
+  const int i = g.cent[ch];
+  const int w = g.width, a = g.starts[g.cwin[ch]], b = a + w;
+  const int n1 = g.e.n_sites + 1;
+  const long long st = g.e.states[i];
+  const int pb = g.e.dims[st * n1 + b];
+  const long long P = g.e.pmax[i], U = win_unit(P, w), ld = (long long)pb << w;
+  const double* const Gr = g.slots + g.cbase[ch] + win_Gr(w) * U + (long long)c * LOC_CHUNK * ld;
+  const double* const H = g.slots + g.cbase[ch] + win_H(w) * U + (long long)c * LOC_CHUNK * ld;
+  double* const out = g.part + ((long long)ch * g.e.max_chunks + c) * win_vals(w);
+  const int np = win_pairs(w), lane = threadIdx.x & 15, slot = threadIdx.x >> 4;
+  for (int p0 = 0; p0 < np; p0 += WIN_CLOSE_GROUP) {
+    double re = 0, im = 0;
+    if (p0 + slot < np) {
+      int s, sp;
+      win_pair_of(p0 + slot, w, s, sp);
+      const double* const gs = Gr + (long long)s * pb;
+      const double* const hs = H + (long long)sp * pb;
+      for (int r = 0; r < LOC_CHUNK; ++r)
+        for (int col = lane; col < pb; col += 16) {
+          const long long q = r * ld + col;
+          const double gr = gs[q], gi = gs[q + U], hr = hs[q], hi = hs[q + U];
+          re += gr * hr + gi * hi;
+          im += gi * hr - gr * hi;
+        }
+    }
+    red[0][slot][lane] = re, red[1][slot][lane] = im;
+    __syncthreads();
+    if (threadIdx.x < 2 * WIN_CLOSE_GROUP) {
+      const int pp = threadIdx.x >> 1, comp = threadIdx.x & 1;
+      double v = 0;
+      for (int l = 0; l < 16; ++l) v += red[comp][pp][l];
+      if (p0 + pp < np) out[2 * (p0 + pp) + comp] = v;
+    }
+    __syncthreads();
+  }
+}
+
+// rho of a chain batch: the chunk sums of each (chain, s <= s') in ascending order, divided by L_n[0][0]; the entry and its mirror
+// image, the conjugate; the imaginary part of a diagonal entry is written as exactly 0.0.
+__global__ __launch_bounds__(256) void qk_win_rho_kernel(const WinArgs g, const long long nc, double* rho) {
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int w = g.width, np = win_pairs(w), D = win_dim(w);
+  if (id >= nc * np) return;
+  const int ch = (int)(id / np), p = (int)(id % np);
+  const int i = g.cent[ch], m = g.cwin[ch];
+  const long long st = g.e.states[i];
+  const int chunks = g.e.dims[st * (g.e.n_sites + 1) + g.starts[m]] / LOC_CHUNK;
+  const double nrm = g.e.scratch[g.e.sbase[i]];  // L_n[0][0]
+  const double* q = g.part + (long long)ch * g.e.max_chunks * win_vals(w) + 2 * p;
+  double re = 0, im = 0;
+  for (int c = 0; c < chunks; ++c) re += q[(long long)c * win_vals(w)], im += q[(long long)c * win_vals(w) + 1];
+  int s, sp;
+  win_pair_of(p, w, s, sp);
+  double* const R = rho + (st * g.n_windows + m) * 2ll * D * D;
+  R[2 * (s * D + sp)] = re / nrm;
+  R[2 * (s * D + sp) + 1] = (s == sp) ? 0.0 : im / nrm;
+  if (s != sp) R[2 * (sp * D + s)] = re / nrm, R[2 * (sp * D + s) + 1] = -(im / nrm);
+}
+
+int window_rdms(qk_ctx* c, const qk_mps_set* set, const int32_t width, const int32_t n_starts, const int32_t* starts_in, double* rho, double* norms) {
+  static const char* what = "qk_window_rdms_host";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!set) return qk_fail(QK_EINVAL, "%s: set is null", what);
+  if (!rho) return qk_fail(QK_EINVAL, "%s: rho is null", what);
+  if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
+  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; window RDMs need an fp64 set", what);
+  const int ns = set->n_states, n = set->n_sites, w = width;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
+  if (win_bad_width(w, n)) return qk_fail(QK_EINVAL, "%s: width must be in 1 .. min(n_sites, %d) = %d (got %d)", what, WIN_MAX_WIDTH, std::min(n, WIN_MAX_WIDTH), w);
+  std::vector<int32_t> starts;
+  if (starts_in) {
+    if (n_starts < 1) return qk_fail(QK_EINVAL, "%s: n_starts must be >= 1 when starts are given (got %d)", what, n_starts);
+    starts.assign(starts_in, starts_in + n_starts);
+    if (const int bad = win_bad_start(n_starts, starts_in, n, w); bad >= 0)
+      return qk_fail(QK_EINVAL, "%s: starts[%d] = %d: starts must be strictly increasing in 0 .. n_sites - width = %d", what, bad, starts_in[bad], n - w);
+  } else {
+    for (int a = 0; a + w <= n; ++a) starts.push_back(a);
+  }
+  const int nw = (int)starts.size();
+  long long cap = 0;  // chains per batch; 0: the memory rule alone
+  if (const char* v = std::getenv("QK_WINDOW_BATCH")) {
+    cap = std::atoll(v);
+    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_WINDOW_BATCH must be >= 1 (got \"%s\")", what, v);
+  }
+  QkRangeGuard range_("qk:window_rdms");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  EnvSizes z;
+  env_sizes(set->dims_true.data(), ns, n, set->max_pad, LOC_RMUL, true, z);
+  const int max_chunks = z.max_chunks, nvals = win_vals(w);
+  const size_t n_out = (size_t)ns * nw * 2 * win_dim(w) * win_dim(w);
+  QkDevBuf rev, dout, dnorm, dstarts;
+  HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
+  HIP_TRY_AS(what, dout.alloc(n_out * sizeof(double)));
+  HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
+  HIP_TRY_AS(what, dstarts.alloc(al256((size_t)nw * sizeof(int32_t))));
+  HIP_TRY_AS(what, hipMemcpy(dstarts.get<char>(), starts.data(), (size_t)nw * sizeof(int32_t), hipMemcpyHostToDevice));
+  // memory bound of a state batch (environments and the slots of its live chains): a quarter of what is free; the environments
+  // of a batch take at most half of that (at least one state per batch), the chains of a batch the rest (at least one chain)
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  const std::vector<int> bstart = batch_cut(z.need, 0, budget / 2);
+  const Plan plan = env_plan(n), wplan = win_plan(w);
+  std::vector<Task2> tasks;
+  std::vector<long long> first;
+  EnvBatch eb;
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+    env_tables(z, plan, s0, nb, 0, eb);
+    const WinChains ch = list_win_chains(z, s0, nb, w, nw, starts.data());
+    const std::vector<size_t> cstart = chain_cut(ch.weight, budget - eb.tot, cap);
+    struct ChainBytes { size_t cent, cwin, cbase, tasks, part, slots; size_t tab() const { return cent + cwin + cbase + tasks; } };
+    auto chain_bytes = [&](const size_t c0, const size_t c1) {
+      long long nt = 0, sl = 0;
+      for (size_t e = c0; e < c1; ++e) nt += ch.ntasks[e], sl += ch.slot[e];
+      const size_t nc = c1 - c0;
+      return ChainBytes{al256(nc * sizeof(int32_t)), al256(nc * sizeof(int32_t)), al256(nc * sizeof(int64_t)), al256((size_t)nt * sizeof(int2)),
+                        al256(nc * max_chunks * nvals * sizeof(double)), (size_t)sl * sizeof(double)};
+    };
+    size_t b_chain = 0;
+    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
+      const ChainBytes cbz = chain_bytes(cstart[cb], cstart[cb + 1]);
+      b_chain = std::max(b_chain, cbz.tab() + cbz.part + cbz.slots);
+    }
+    // one device buffer for the state batch: [tables | tasks | environments] then the chain batch's [tables | tasks | partials | slots]
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, b_chain)) return rc;
+    qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(eb.g, nb, dnorm.get<double>());
+    HIP_TRY_AS(what, hipGetLastError());
+    WinArgs q{};
+    q.e = eb.g;
+    q.starts = dstarts.get<int32_t>();
+    q.width = w, q.n_windows = nw;
+    char* const cbase0 = eb.base + eb.used();
+    std::vector<char> cstage;
+    std::vector<int64_t> h_cbase;
+    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
+      const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
+      if (nc == 0) continue;
+      const ChainBytes cbz = chain_bytes(c0, c0 + nc);
+      h_cbase.resize(nc);
+      long long sl = 0;
+      for (size_t e = 0; e < nc; ++e) h_cbase[e] = sl, sl += ch.slot[c0 + e];
+      win_lists(z, s0, ch, c0, nc, w, starts.data(), tasks, first);
+      cstage.assign(cbz.tab(), 0);
+      std::memcpy(cstage.data(), ch.cent.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + cbz.cent, ch.cwin.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + cbz.cent + cbz.cwin, h_cbase.data(), nc * sizeof(int64_t));
+      std::memcpy(cstage.data() + cbz.cent + cbz.cwin + cbz.cbase, tasks.data(), tasks.size() * sizeof(int2));
+      q.cent = reinterpret_cast<const int32_t*>(cbase0);
+      q.cwin = reinterpret_cast<const int32_t*>(cbase0 + cbz.cent);
+      q.cbase = reinterpret_cast<const int64_t*>(cbase0 + cbz.cent + cbz.cwin);
+      const int2* d_ctasks = reinterpret_cast<const int2*>(cbase0 + cbz.cent + cbz.cwin + cbz.cbase);
+      q.part = reinterpret_cast<double*>(cbase0 + cbz.tab());
+      q.slots = reinterpret_cast<double*>(cbase0 + cbz.tab() + cbz.part);
+      HIP_TRY_AS(what, hipMemcpyAsync(cbase0, cstage.data(), cbz.tab(), hipMemcpyHostToDevice, c->stream));
+      for (size_t li = 0; li < wplan.size(); ++li) {
+        const int kind = wplan[li].first;
+        q.tasks = d_ctasks + first[li];
+        q.step = wplan[li].second;
+        if (first[li + 1] <= first[li]) continue;
+        const dim3 grid((unsigned)(first[li + 1] - first[li]));
+        if (kind >= 0) qk_win_gemm_kernel<<<grid, dim3(512), 0, c->stream>>>(q, kind);
+        else qk_win_close_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+      }
+      const long long nv = (long long)nc * win_pairs(w);
+      qk_win_rho_kernel<<<dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream>>>(q, (long long)nc, dout.get<double>());
+      HIP_TRY_AS(what, hipGetLastError());
+      HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
+    }
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  }
+  std::vector<double> h_norm((size_t)ns);
+  HIP_TRY_AS(what, hipMemcpy(h_norm.data(), dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+  for (int s = 0; s < ns; ++s)
+    if (!(h_norm[s] > 0.0) || !std::isfinite(h_norm[s])) return qk_fail(QK_EDEVICE, "%s: state %d has norm 0 (or a norm that is not finite): its reduced density matrices are undefined", what, s);
+  HIP_TRY_AS(what, hipMemcpy(rho, dout.get(), n_out * sizeof(double), hipMemcpyDeviceToHost));
+  if (norms) std::memcpy(norms, h_norm.data(), (size_t)ns * sizeof(double));
+  return QK_OK;
+}
+
 // ---- block overlaps from measurement shots (qk_shot_block_sums_host) -----------------------------------------------------------------
 // The randomised-measurement overlap (Elben et al., PRL 124, 010504 (2020)) of outcome tables bits[state][u M + a][site], U settings
 // of M shots: all integer arithmetic, definitions in include/qkgram.h, host side in qk_local_plan.h (sbk_*).
@@ -2134,6 +2415,10 @@ extern "C" int qk_shadow_hist_host(qk_ctx* c, int32_t n_sites, int32_t nx, int32
                                    int32_t shots_y, const uint8_t* bits_y, const uint8_t* bases_y, int32_t bases_y_per_state, int64_t n_pairs, const int32_t* pairs, int64_t* hist,
                                    int64_t* equal) {
   return shadow_hist(c, n_sites, nx, shots_x, bits_x, bases_x, bases_x_per_state, ny, shots_y, bits_y, bases_y, bases_y_per_state, n_pairs, pairs, hist, equal);
+}
+
+extern "C" int qk_window_rdms_host(qk_ctx* c, const qk_mps_set* set, int32_t width, int32_t n_starts, const int32_t* starts, double* rho, double* norms) {
+  return window_rdms(c, set, width, n_starts, starts, rho, norms);
 }
 
 extern "C" int qk_shot_block_sums_host(qk_ctx* c, int32_t n_sites, int32_t n_settings, int32_t shots_per_setting, int32_t nx, const uint8_t* bits_x, int32_t ny,

@@ -1,6 +1,6 @@
 // qk_local_plan.h -- the host-side plan of the local sweeps (qk_local.hip): the launch kinds, the scratch layout, the pair index, the
 // sizes and the cut into state batches, the tables and task lists of a batch, the plans of the entry points, the chain side of the
-// Pauli strings, the integer side of the shot-based block overlaps and of the shadow kernel's shot-pair histograms.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
+// Pauli strings, of the block kernels, of the sampler and of the k-qubit windows, the integer side of the shot-based block overlaps and of the shadow kernel's shot-pair histograms.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
 // -fsanitize=address,undefined); the few functions the kernels also call are QK_HD.
 #pragma once
 #include "qk_plan.h"
@@ -17,7 +17,8 @@ constexpr int LOC_CHUNK = 16;  // rows per reduction task
 
 // Every launch kind of qk_local.hip.  Kinds >= 0 are GEMM launches (64 x 64 output blocks), the others elementwise or reductions
 // in 16-row chunks.  LOC_*: tasks (batch entry, block), qk_local_gemm_kernel; STR_*: tasks (chain, block), qk_str_gemm_kernel;
-// BLK_*: tasks (pair chain, block), qk_blk_gemm_kernel; SMP_*: tasks (shot chain, block), qk_smp_gemm_kernel.
+// BLK_*: tasks (pair chain, block), qk_blk_gemm_kernel; SMP_*: tasks (shot chain, block), qk_smp_gemm_kernel; WIN_*: tasks (window
+// chain, block), qk_win_gemm_kernel.
 enum LocKind : int {
   LOC_REV_T = 0,   // reversed chain: T = Lr^T Ar_j              (Lr_j = R_{o+1}, o = n-1-j)
   LOC_REV_X = 1,   // reversed chain: R_o = T^T conj(Ar_j)
@@ -47,6 +48,10 @@ enum LocKind : int {
   SMP_Q = 16,         // shot chain: Q[(o, row)][a'] = sum_b' W'_o[row][b'] R_{k+1}[b'][a'], the stacked operand [W'_0 ; W'_1] as M
   SMP_ROT = -10,      // qk_smp_rotate_kernel: W -> the stacked operand by each row's basis code, in 16-row chunks
   SMP_DRAW = -11,     // qk_smp_draw_kernel: p_0, p_1 of a row, its uniform, its bit, log p and the next V, one wave per row
+  WIN_G = 17,         // window chain (state, window [a, b)), step j, site c = b-1-j: G_{j+1}[beta][(t, sigma, gamma)] = sum_beta' A_c[beta][t][beta'] G_j[beta'][(sigma, gamma)]
+                      // of both seeds (G_0 = 1, Gr_0 = R_b) and both t in one launch; the reversed image's site c is the A operand
+  WIN_H = 18,         // window chain: H[alpha'][(s, gamma)] = sum_alpha L_a[alpha][alpha'] G_w[alpha][(s, gamma)] (the LOC_FWD_T shape, N = 2^w chi_b)
+  WIN_CLOSE = -12,    // qk_win_close_kernel: sum Gr_w[alpha][(s, gamma')] conj(H[alpha][(s', gamma')]) of every s <= s' in 16-row chunks of alpha
 };
 QK_HD constexpr bool conj_b(const int kind) { return kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V || kind == LOC_DIST_X || kind == STR_X || kind == BLK_X || kind == BLK_W; }
 
@@ -498,6 +503,92 @@ inline long long smp_bad_basis(const uint8_t* bases, const long long count) {
   for (long long e = 0; e < count; ++e)
     if (bases[e] < 1 || bases[e] > 3) return e;
   return -1;
+}
+
+// ---- windows of k qubits (qk_window_rdms_host) ------------------------------------------------------------------------------------
+// A window chain is one (state, window): the qubits a .. a+w-1 of the state, b = a + w, 1 <= w <= WIN_MAX_WIDTH.  The product of its
+// sites grows from the right, the new site's physical index most significant, from two seeds (definitions in qk_local.hip):
+// G_j, Gr_j [pad_{b-j}][2^j pad_b].  Its slot is win_size() U doubles, U = 2^w P^2 (P = the state's largest padded bond), every
+// matrix as a re plane then an im plane of U, offsets in units of U:
+//   G_j  at win_G(j)  = 0 | 2 (j even | odd), ld = 2^j pad_b; G_0 is never stored and G_1 is the site b-1 itself, read from the set
+//   Gr_j at win_Gr(j) = 4 | 6, ld = 2^j pad_b; Gr_0 = R_b is read from the kept environments
+//   H    at win_H(w)  = the G buffer that G_w does not lie in (G_{w-1} is dead once G_w exists), ld = 2^w pad_b
+// A step reads the buffer of one parity and writes the other, so no block of a launch reads what another block of it writes.
+constexpr int WIN_MAX_WIDTH = 6;
+QK_HD constexpr int win_dim(const int w) { return 1 << w; }
+QK_HD constexpr int win_G(const int j) { return 2 * (j & 1); }
+QK_HD constexpr int win_Gr(const int j) { return 4 + 2 * (j & 1); }
+QK_HD constexpr int win_H(const int w) { return win_G(w + 1); }
+QK_HD constexpr int win_size() { return 8; }
+QK_HD constexpr long long win_unit(const long long P, const int w) { return (P * P) << w; }
+// The closing sums of a chain: (Re, Im) of rho[s][s'] for every s <= s', pairs row-major, win_pairs(w) of them.
+QK_HD constexpr int win_pairs(const int w) { return win_dim(w) * (win_dim(w) + 1) / 2; }
+QK_HD constexpr int win_vals(const int w) { return 2 * win_pairs(w); }
+QK_HD constexpr int win_pair(const int s, const int sp, const int w) { return s * win_dim(w) - s * (s - 1) / 2 + (sp - s); }  // s <= sp
+QK_HD inline void win_pair_of(int p, const int w, int& s, int& sp) {
+  const int D = win_dim(w);
+  for (s = 0; p >= D - s; ++s) p -= D - s;
+  sp = s + p;
+}
+constexpr int WIN_CLOSE_GROUP = 16;  // pairs a workgroup of the closing kernel takes at a time (16 lanes each)
+// the width must be in 1 .. min(n, WIN_MAX_WIDTH)
+inline bool win_bad_width(const int w, const int n) { return w < 1 || w > n || w > WIN_MAX_WIDTH; }
+// starts must be strictly increasing in 0 .. n - w: returns -1, or the index of the first offender
+inline int win_bad_start(const int n_starts, const int32_t* starts, const int n, const int w) {
+  for (int i = 0; i < n_starts; ++i)
+    if (starts[i] < 0 || starts[i] > n - w || (i > 0 && starts[i] <= starts[i - 1])) return i;
+  return -1;
+}
+// The launches of a chain batch in stream order: the steps j = 0 .. w-1 (step 0 grows Gr alone), H, the closing sums.
+inline Plan win_plan(const int w) {
+  Plan plan;
+  for (int j = 0; j < w; ++j) plan.push_back({WIN_G, j});
+  plan.push_back({WIN_H, 0}), plan.push_back({WIN_CLOSE, 0});
+  return plan;
+}
+// the 64 x 64 blocks of one product of step j (one seed, one t): M = pad_c, N = 2^j pad_b
+inline long long win_step_blocks(const int j, const int32_t* p, const int a, const int w) { return blocks64(p[a + w - 1 - j], (long long)p[a + w] << j); }
+// The blocks of a window chain (p = its state's padded bonds) in the launch `kind` of step j.  WIN_G: block number = q per + block
+// of the product, q = 2 seed + t, seed 0 = Gr, 1 = G (step 0 has seed 0 only).
+inline int win_task_count(const int kind, const int j, const int32_t* p, const int a, const int w) {
+  switch (kind) {
+    case WIN_G: return (int)((j == 0 ? 2 : 4) * win_step_blocks(j, p, a, w));
+    case WIN_H: return (int)blocks64(p[a], (long long)p[a + w] << w);
+    default: return p[a] / LOC_CHUNK;  // WIN_CLOSE
+  }
+}
+struct WinChains {  // the window chains of a state batch, state-major in window order
+  std::vector<int32_t> cent, cwin;              // chain -> batch entry, window (index into the starts)
+  std::vector<long long> slot, ntasks, weight;  // doubles of its slot; its tasks over all launches; slot, partial sums, tasks and table entries
+};
+inline WinChains list_win_chains(const EnvSizes& z, const int s0, const int nb, const int w, const int n_windows, const int32_t* starts) {
+  const int n = z.n_sites;
+  const Plan plan = win_plan(w);
+  WinChains c;
+  for (int i = 0; i < nb; ++i)
+    for (int m = 0; m < n_windows; ++m) {
+      long long nt = 0;
+      for (const auto& [kind, j] : plan) nt += win_task_count(kind, j, &z.pad[(size_t)(s0 + i) * (n + 1)], starts[m], w);
+      c.cent.push_back(i), c.cwin.push_back(m);
+      c.slot.push_back(win_size() * win_unit(z.pmax[s0 + i], w)), c.ntasks.push_back(nt);
+      c.weight.push_back(c.slot.back() + (long long)z.max_chunks * win_vals(w) + nt + 2);
+    }
+  return c;
+}
+// Task lists (chain of the batch, block) of the window chains [c0, c0 + nc) for every launch of win_plan(w).  The cut into chain
+// batches is chain_cut (QK_WINDOW_BATCH caps the chains of one).
+inline void win_lists(const EnvSizes& z, const int s0, const WinChains& c, const size_t c0, const size_t nc, const int w, const int32_t* starts,
+                      std::vector<Task2>& tasks, std::vector<long long>& first) {
+  const int n = z.n_sites;
+  tasks.clear(), first.clear();
+  for (const auto& [kind, j] : win_plan(w)) {
+    first.push_back((long long)tasks.size());
+    for (size_t e = 0; e < nc; ++e) {
+      const int nbk = win_task_count(kind, j, &z.pad[(size_t)(s0 + c.cent[c0 + e]) * (n + 1)], starts[c.cwin[c0 + e]], w);
+      for (int b = 0; b < nbk; ++b) tasks.push_back(Task2{(int)e, b});
+    }
+  }
+  first.push_back((long long)tasks.size());
 }
 
 // ---- block overlaps from measurement shots (qk_shot_block_sums_host) -----------------------------------------------------------------

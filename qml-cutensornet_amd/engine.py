@@ -107,6 +107,7 @@ _SIGNATURES = [
     ("qk_bond_spectra_host", C.c_int, [_P, _P, C.c_int32, _P, _P]),
     ("qk_block_values_host", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("qk_block_self_host", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("qk_window_rdms_host", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_sample_host", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint64, C.c_int64, _P, _P]),
     ("qk_shot_block_sums_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_shadow_hist_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
@@ -736,6 +737,101 @@ def block_kernel(O, Sx, Sy=None, form: str = "rbf", gamma=None) -> np.ndarray:
             d = np.arange(O.shape[-1])
             K[..., d, d] = 1.0
     return K
+
+
+WINDOW_MAX_WIDTH = 6  # qubits of a window (qk_window_rdms_host)
+_PAULI = np.array([[[1, 0], [0, 1]], [[0, 1], [1, 0]], [[0, -1j], [1j, 0]], [[1, 0], [0, -1]]], dtype=np.complex128)  # I, X, Y, Z
+
+
+def _window_rdms(rho, name: str = "rho") -> tuple:
+    """``rho`` as complex128 of shape (n_states, n_windows, D, D), D = 2^w, and w."""
+    r = np.asarray(rho, dtype=np.complex128)
+    D = r.shape[-1] if r.ndim == 4 else 0
+    w = int(D).bit_length() - 1
+    if r.ndim != 4 or r.shape[2] != D or D < 2 or (1 << w) != D or r.shape[1] < 1:
+        raise ValueError(f"{name} must have shape (n_states, n_windows, 2^w, 2^w) with w >= 1, got {np.shape(rho)}")
+    return r, w
+
+
+def window_columns(rho) -> np.ndarray:
+    """The real feature columns of window RDMs: (n_states, n_windows, D, D) complex -> (n_states, 2 n_windows D^2) float64, all real
+    parts then all imaginary parts -- what ``projected_window_gram`` hands to ``feature_gram``."""
+    r, _ = _window_rdms(rho)
+    f = r.reshape(r.shape[0], -1)
+    return np.ascontiguousarray(np.concatenate([f.real, f.imag], axis=1))
+
+
+def window_overlaps(rx, ry=None):
+    """``(O, Sx, Sy)`` from window RDMs (``Context.window_rdms``), pure numpy, in the conventions of ``Context.block_overlaps``:
+    O[a, j, i] = tr(rho_a(x_i) rho_a(y_j)) = Re sum rho_a(x_i)[s][s'] conj(rho_a(y_j)[s][s']), shape (n_windows, ny, nx), rows = Y
+    (or X), and the purities Sx (n_windows, nx), Sy (n_windows, ny) -- what ``block_kernel(O[a], Sx[a], Sy[a], form=...)`` takes per
+    window.  A symmetric call (``ry=None``) computes the pairs i <= j, mirrors them, takes Sx from the diagonal and returns
+    ``Sy = Sx``: O is exactly symmetric and its diagonal is the bits of Sx."""
+    x, w = _window_rdms(rx, "rx")
+
+    def planes(r):  # (n_windows, n_states, 2 D^2) real: the overlap is a dot product of these rows
+        f = r.reshape(r.shape[0], r.shape[1], -1).transpose(1, 0, 2)
+        return np.ascontiguousarray(np.concatenate([f.real, f.imag], axis=2))
+
+    def purity(f):
+        return np.einsum("asd,asd->as", f, f)
+
+    fx = planes(x)
+    if ry is None:
+        O = np.einsum("ajd,aid->aji", fx, fx)
+        iu = np.triu_indices(fx.shape[1], 1)
+        O[:, iu[1], iu[0]] = O[:, iu[0], iu[1]]
+        d = np.arange(fx.shape[1])
+        Sx = purity(fx)
+        O[:, d, d] = Sx
+        return O, Sx, Sx
+    y, wy = _window_rdms(ry, "ry")
+    if wy != w or y.shape[1] != x.shape[1]:
+        raise ValueError(f"Y RDMs of shape {y.shape} do not match X RDMs of shape {x.shape}")
+    fy = planes(y)
+    return np.einsum("ajd,aid->aji", fy, fx), purity(fx), purity(fy)
+
+
+def rdm_paulis(rho) -> np.ndarray:
+    """Pauli coefficients of w-qubit density matrices, pure numpy: ``rho`` of shape (..., 2^w, 2^w) gives float64 of shape
+    (..., 4, ..., 4) with w axes of size 4, c[p_0 .. p_{w-1}] = tr(rho P_{p_0} (x) .. (x) P_{p_{w-1}}), P = (I, X, Y, Z), qubit 0 of
+    the window the first of them -- the convention of ``local_pair_paulis``'s T[k][p][q], so rho = 2^-w sum c P (``paulis_rdm``).
+    Real for a Hermitian rho (the imaginary part is dropped)."""
+    r = np.asarray(rho, dtype=np.complex128)
+    D = r.shape[-1] if r.ndim >= 2 else 0
+    w = int(D).bit_length() - 1
+    if r.ndim < 2 or r.shape[-2] != D or D < 2 or (1 << w) != D:
+        raise ValueError(f"rho must have shape (..., 2^w, 2^w) with w >= 1, got {np.shape(rho)}")
+    lead = r.shape[:-2]
+    nl = len(lead)
+    t = r.reshape(lead + (2,) * (2 * w))  # (.., s_0 .. s_{w-1}, s'_0 .. s'_{w-1})
+    for j in range(w):
+        # qubit j: its row axis s_j is nl + j (the axes before it are already p_0 .. p_{j-1}), its column axis s'_j is nl + w (the
+        # first column axis left); c[p] = sum rho[s][s'] P_p[s'][s], and p goes where s_j was
+        t = np.moveaxis(np.tensordot(t, _PAULI, axes=([nl + j, nl + w], [2, 1])), -1, nl + j)
+    return np.ascontiguousarray(t.real)
+
+
+def paulis_rdm(c, width=None) -> np.ndarray:
+    """The inverse of ``rdm_paulis``: coefficients of shape (..., 4, ..., 4) give rho = 2^-w sum c[p_0 .. p_{w-1}] P_{p_0} (x) .. (x)
+    P_{p_{w-1}}, complex128 of shape (..., 2^w, 2^w).  ``width=None`` takes every trailing axis of size 4 (at most 6) as a qubit;
+    give ``width`` when a leading axis happens to have size 4."""
+    t = np.asarray(c, dtype=np.float64)
+    if width is None:
+        w = 0
+        while w < min(t.ndim, WINDOW_MAX_WIDTH) and t.shape[t.ndim - 1 - w] == 4:
+            w += 1
+    else:
+        w = int(width)
+    if w < 1 or w > t.ndim or t.shape[t.ndim - w:] != (4,) * w:
+        raise ValueError(f"coefficients must have shape (..., 4, ..., 4) with w >= 1 trailing axes of size 4, got {np.shape(c)} (width {width!r})")
+    nl = t.ndim - w
+    t = t.astype(np.complex128)
+    for j in range(w):  # the first coefficient axis left, p_j -> (s_j, s'_j) = P_p[s_j][s'_j], appended at the end
+        t = np.tensordot(t, _PAULI, axes=([nl], [0]))
+    order = list(range(nl)) + [nl + 2 * j for j in range(w)] + [nl + 2 * j + 1 for j in range(w)]  # rows, then columns
+    D = 1 << w
+    return np.ascontiguousarray(t.transpose(order).reshape(t.shape[:nl] + (D, D))) / D
 
 
 def _dims_table(states) -> np.ndarray:
@@ -1684,6 +1780,48 @@ class Context:
         if not info:
             return out
         return out, {"fidelity": fid, "discarded": disc[:, : n - 1], "bond_dims": out.dims.copy()}
+
+    def window_rdms(self, xs: MpsSet, width: int, starts=None, norms: bool = False):
+        """Reduced density matrices of contiguous windows of ``width`` qubits (1 .. min(n_sites, 6)) of every state of an fp64
+        set: complex128 of shape (n_states, n_windows, 2^w, 2^w), window i = the qubits starts[i] .. starts[i] + width - 1, row index
+        s = sum_j s_{start+j} 2^(w-1-j).  ``starts=None`` means every window 0 .. n_sites - width; otherwise strictly increasing
+        ints in that range.  rho is exactly Hermitian, tr rho = 1 to rounding, and a (state, window) value is the same bits
+        whatever the other states and windows of the call.  With ``norms=True`` also <psi|psi> (the bits of ``local_paulis``), as
+        ``(rho, norms)``.  Synchronous."""
+        info = xs.info()
+        ns, n = info["n_states"], info["n_sites"]
+        if isinstance(width, bool) or not isinstance(width, (int, np.integer)):
+            raise ValueError(f"width must be an int, got {width!r}")
+        w = int(width)
+        st = None
+        if starts is not None:
+            st = np.asarray(starts)
+            if st.ndim != 1 or (st.size and not np.issubdtype(st.dtype, np.integer)) or st.dtype == np.bool_:
+                raise ValueError(f"starts must be a list of ints, got {starts!r}")
+            st = np.ascontiguousarray(st, dtype=np.int32)
+        ok = 1 <= w <= min(n, WINDOW_MAX_WIDTH)  # (the library rejects a bad width or start: spare elements keep the pointers valid)
+        nw = (n - w + 1 if ok else 1) if st is None else max(int(st.size), 1)
+        D = 1 << (w if ok else 1)
+        rho = np.zeros((ns, nw, D, D), dtype=np.complex128)
+        nrm = np.zeros(ns, dtype=np.float64)
+        sp = None if st is None else (st if st.size else np.zeros(1, dtype=np.int32))
+        _check(lib().qk_window_rdms_host(self._h, xs.handle, w, 0 if st is None else int(st.size), None if sp is None else sp.ctypes.data, rho.ctypes.data,
+                                         nrm.ctypes.data), "qk_window_rdms_host")
+        return (rho, nrm) if norms else rho
+
+    def projected_window_gram(self, rx, ry=None, gamma=None) -> np.ndarray:
+        """The k-qubit projected quantum kernel K[j, i] = exp(-gamma sum_a ||rho_a(x_i) - rho_a(y_j)||_F^2) of window RDMs
+        (``window_rdms``): shape (ny, nx), rows = Y (or X) -- ``feature_gram`` at gamma over the columns (Re rho, Im rho).
+        ``gamma=None`` means 1 / (n_windows + width - 1), which is 1 / n_sites when every window was taken.  Synchronous."""
+        x, w = _window_rdms(rx, "rx")
+        g = projected_gamma(gamma, x.shape[1] + w - 1)
+        fy = None
+        if ry is not None:
+            y, wy = _window_rdms(ry, "ry")
+            if wy != w or y.shape[1] != x.shape[1]:
+                raise ValueError(f"Y RDMs of shape {y.shape} do not match X RDMs of shape {x.shape}")
+            fy = window_columns(y)
+        return self.feature_gram(window_columns(x), fy, g)
 
     def feature_gram(self, fx, fy=None, gamma=None) -> np.ndarray:
         """Gram of real feature columns (``pauli_expectations``): K[j, i] = exp(-gamma sum_m (fx[i, m] - fy[j, m])^2), shape (ny, nx),

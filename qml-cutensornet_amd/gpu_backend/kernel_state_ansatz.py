@@ -400,7 +400,7 @@ def _gather_features(comm, lo, F, total):
 
 
 def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30, rdm=1, pair_distance=1, observables=None,
-                                  shots=None, shot_seed=0):
+                                  shots=None, shot_seed=0, window=False):
     """Projected quantum kernel (Huang et al., Nat. Commun. 12, 2631 (2021)) of the same states as ``build_kernel_matrix``:
         K[j, i] = exp(-g sum_k ||rho_k(X_i) - rho_k(Y_j)||_F^2) = exp(-g/2 sum_k |F(X_i)[k] - F(Y_j)[k]|^2),
     rho_k = the one-qubit reduced density matrix of qubit k, F[k] = its Bloch vector (<X_k>, <Y_k>, <Z_k>); ``Y=None`` means
@@ -428,8 +428,32 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     ``Context.sample(..., seed=shot_seed, first_state=<the share's offset>)`` (the states of Y are indexed after those of X) and
     estimates the Bloch vectors (``engine.estimate_paulis``) or the correlators (``engine.estimate_pair_paulis``) from the bits; the
     rest of the route is the same, and K is the same bits for any number of ranks.  ``shots=None`` is the exact kernel.
-    ``observables`` together with ``shots`` is a ``ValueError``."""
+    ``observables`` together with ``shots`` is a ``ValueError``.
+
+    ``rdm=k, window=True`` for 3 <= k <= min(6, n_qubits) is the window form, the k-qubit member of the series:
+        K_k[j, i] = exp(-g sum_a ||rho_{a,k}(X_i) - rho_{a,k}(Y_j)||_F^2),   a = 0 .. n_qubits - k,
+    rho_{a,k} = the reduced density matrix of the qubits a .. a+k-1 (``Context.window_rdms``).  Each rank takes the window RDMs of
+    its share; 2 (n - k + 1) 4^k reals per state are all-gathered and rank 0 calls ``Context.projected_window_gram``.  K is the
+    same bits for any number of ranks; ``pqk_gamma=None`` means g = 1 / n_qubits.  It takes neither ``pair_distance`` other than
+    1, nor ``shots``, nor ``observables`` (each a ``ValueError``): finite-shot window RDMs are out of scope.  ``window`` is the
+    switch of this form: ``rdm >= 3`` without it stays the ``ValueError`` it has always been, and ``window=True`` with ``rdm`` 1 or 2
+    is one too (those two keep their own routes)."""
     strings = None
+    if not isinstance(window, (bool, np.bool_)):
+        raise ValueError(f"window must be True or False (got {window!r})")
+    window = bool(window)
+    if window:
+        if isinstance(rdm, bool) or not isinstance(rdm, (int, np.integer)) or rdm < 3:
+            raise ValueError(f"window=True is the form of rdm = 3 .. min({_engine.WINDOW_MAX_WIDTH}, n_qubits), got rdm={rdm!r} (rdm=1 and rdm=2 take no window)")
+        if observables is not None:
+            raise ValueError(f"observables chooses the features itself: it cannot be combined with rdm={rdm!r}")
+        if shots is not None:
+            raise ValueError(f"shots with rdm={rdm!r} is not supported: finite-shot window RDMs are out of scope (sample with rdm=1 or rdm=2)")
+        if pair_distance != 1:
+            raise ValueError(f"pair_distance={pair_distance!r} needs rdm=2: rdm={rdm!r} compares contiguous windows (leave pair_distance at 1)")
+        if rdm > min(_engine.WINDOW_MAX_WIDTH, int(ansatz.num_qubits)):
+            raise ValueError(f"rdm with window=True must be in 3 .. min({_engine.WINDOW_MAX_WIDTH}, n_qubits) = {min(_engine.WINDOW_MAX_WIDTH, int(ansatz.num_qubits))}, got {rdm!r}")
+        rdm = int(rdm)
     if shots is not None:
         if observables is not None:
             raise ValueError("shots together with observables is not supported: sample with rdm=1 or rdm=2")
@@ -440,8 +464,8 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         if rdm != 1 or pair_distance != 1:
             raise ValueError(f"observables chooses the features itself: leave rdm and pair_distance at 1 (got rdm={rdm!r}, pair_distance={pair_distance!r})")
         strings = _engine.pauli_strings(int(ansatz.num_qubits), observables)  # ValueError: empty list, bad spec
-    if rdm not in (1, 2):
-        raise ValueError(f"rdm must be 1 (one-qubit reduced density matrices) or 2 (neighbouring pairs), got {rdm!r}")
+    if not window and rdm not in (1, 2):
+        raise ValueError(f"rdm must be 1 (one-qubit reduced density matrices), 2 (pairs) or, with window=True, 3 .. 6 (windows of that many qubits), got {rdm!r}")
     if rdm == 2 and int(ansatz.num_qubits) < 2:
         raise ValueError("rdm=2 compares reduced density matrices of neighbouring qubit pairs: the ansatz needs at least 2 qubits")
     if isinstance(pair_distance, bool) or not isinstance(pair_distance, (int, np.integer)):
@@ -492,9 +516,13 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         t0 = time.perf_counter()
         if local is None:
             shape = (0, len(strings)) if strings is not None else (0, n_qubits, 3) if rdm == 1 else (0, n_pairs, 4, 4)
+            if window:
+                shape = (0, n_qubits - rdm + 1, 1 << rdm, 1 << rdm, 2)
             F, chi = np.zeros(shape, dtype=np.float64), np.zeros(0)
         else:
-            if strings is not None:
+            if window:  # complex128 as (re, im) pairs of float64: the features travel as the other forms' do
+                F = np.ascontiguousarray(ctx.window_rdms(local, rdm)).view(np.float64).reshape(len(local), n_qubits - rdm + 1, 1 << rdm, 1 << rdm, 2)
+            elif strings is not None:
                 F = ctx.pauli_expectations(local, strings)
             elif shots is not None:
                 shot_bases = _engine.random_bases(shots, n_qubits, shot_seed)
@@ -514,10 +542,13 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     gather_secs = time.perf_counter() - t0
     if not is_root:
         return None
-    g = _engine.projected_gamma(pqk_gamma, len(strings) if strings is not None else n_qubits * pair_distance)
+    g = _engine.projected_gamma(pqk_gamma, len(strings) if strings is not None else n_qubits * pair_distance)  # (a window form has pair_distance 1)
     _say(True, "\nFinished contracting all MPS.\n\nCalculating projected kernel matrix...")
     t0 = time.perf_counter()
-    if strings is not None:
+    if window:
+        rdms = [np.ascontiguousarray(f).view(np.complex128)[..., 0] for f in feats]
+        kernel_mat = ctx.projected_window_gram(rdms[0], None if Y is None else rdms[1], g)
+    elif strings is not None:
         kernel_mat = ctx.feature_gram(feats[0], None if Y is None else feats[1], g)
     elif rdm == 1:
         kernel_mat = ctx.projected_gram(feats[0], None if Y is None else feats[1], g)

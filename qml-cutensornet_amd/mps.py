@@ -183,6 +183,35 @@ class MPS:
         W = E.T @ V.conj()          # W[a][a'] = sum_b' E[b'][a] conj(V[b'][a'])
         return float((envs[0] * W.conj()).sum().real) / (norms[0] * norms[1])
 
+    def window_rdm(self, start: int, width: int) -> np.ndarray:
+        """Reduced density matrix of the qubits ``start .. start + width - 1`` on the host, complex128 of shape (2^w, 2^w): the numpy
+        mirror of ``Context.window_rdms``.  ``rho[s][s'] = sum over all other sites of psi(.. s ..) conj(psi(.. s' ..)) / <psi|psi>``
+        with the row index ``s = sum_j s_{start+j} 2^(w-1-j)`` (qubit ``start`` is the most significant bit).  A plain environment
+        loop: L_a and R_b in the X[ket][bra] orientation, the product M^s of the window's sites, then
+        ``sum L_a[al][al'] M^s[al][ga] R_b[ga][ga'] conj(M^{s'}[al'][ga'])``.  The state need not be normalised; the result is
+        Hermitian to rounding.  1 <= width <= min(n, 6), 0 <= start <= n - width."""
+        n = len(self.tensors)
+        for name, v in (("start", start), ("width", width)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an int, got {v!r}")
+        a, w = int(start), int(width)
+        if not 1 <= w <= min(n, 6):
+            raise ValueError(f"width must be in 1 .. min(n, 6) = {min(n, 6)}, got {width!r}")
+        if not 0 <= a <= n - w:
+            raise ValueError(f"start must be in 0 .. n - width = {n - w}, got {start!r}")
+        ts = [np.asarray(t, dtype=np.complex128) for t in self.tensors]
+        L = np.ones((1, 1), dtype=np.complex128)  # L[ket][bra]
+        for k in range(a):
+            L = np.einsum("ab,asc,bsd->cd", L, ts[k], ts[k].conj(), optimize=True)
+        R = np.ones((1, 1), dtype=np.complex128)  # R[ket][bra]
+        for k in range(n - 1, a + w - 1, -1):
+            R = np.einsum("asc,cd,bsd->ab", ts[k], R, ts[k].conj(), optimize=True)
+        M = ts[a]  # M[al][s][ga], s growing to the right: the new site is the least significant bit
+        for k in range(a + 1, a + w):
+            M = np.tensordot(M, ts[k], axes=(2, 0)).reshape(M.shape[0], -1, ts[k].shape[2])
+        rho = np.einsum("ab,asc,cd,btd->st", L, M, R, M.conj(), optimize=True)
+        return rho / np.trace(rho).real
+
     def sample(self, shots: int, bases=None, seed: int = 0, state_index: int = 0, logp: bool = False, margin: bool = False):
         """Measurement shots of the state on the host, the numpy mirror of ``Context.sample``: ``bits`` uint8 (shots, n), bit 0 =
         eigenvalue +1 of the Pauli (``bases``, anything ``engine.bases_table`` takes; codes 1..3 = X, Y, Z) the qubit was measured

@@ -25,8 +25,16 @@ engine.random_bases(T, n, 0), then ctx.shadow_hist_host on the pairs of the run'
 packs them, counts and downloads the histograms), after a warm-up: shadow_hist_ms (the median; shadow_hist_ms_min and _max give the
 spread over the repetitions), shadow_shot_pairs = pairs T^2, shadow_shot_pairs_per_s, shadow_over_sample against sample_ms of the same
 run, and the median off-diagonal entry of the shadow kernel at gamma = tau = 1.
+``--window W`` (1 <= W <= 6) adds the k-qubit projected kernel: ctx.window_rdms(xs, W) on all n - W + 1 windows and
+ctx.projected_window_gram(rho), each after a warm-up: window_rdms_ms (the median; window_rdms_ms_min and _max give the spread over the
+repetitions), window_width, n_windows, window_flops and window_tflops, projected_window_gram_ms, window_over_pair against
+local_pair_paulis_ms of the same run, and median_offdiag_pqk_window.  window_flops, from the true bonds at 8 flops per complex
+multiply-add: the environment pass (the GEMMs of the one-qubit sweep, ``local_sweep_flops``) and, for every window [a, b = a + W) of
+every state, the steps j = 0 .. W-1 at site c = b-1-j -- two products (t = 0, 1) of chi_c x 2^j chi_b over chi_c+1 for the seed R_b
+and, from j = 1 on, for the seed 1 -- then H (chi_a x 2^W chi_b over chi_a) and the closing sum (2^W (2^W + 1) / 2 entries of chi_a
+chi_b terms).
 usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement] [--compress CHI]
-                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S [--shadow-shots T]]"""
+                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S [--shadow-shots T]] [--window W]"""
 import argparse
 import json
 import os
@@ -79,6 +87,21 @@ def sample_flops(dims, shots):
     return float(shots * (8 * (2 * r * l) + 8 * (2 * r * r)).sum())
 
 
+def window_flops(dims, w):
+    """Algorithmic flops of ``window_rdms(xs, w)`` on all windows, from the true bonds (the formula of the module docstring)."""
+    d = np.asarray(dims, dtype=np.float64)
+    n = d.shape[1] - 1
+    total = local_sweep_flops(dims)
+    D = 2.0**w
+    for a in range(n - w + 1):
+        b = a + w
+        for j in range(w):
+            c = b - 1 - j
+            total += float(((2 if j else 1) * 2 * 8 * d[:, c] * (2.0**j) * d[:, b] * d[:, c + 1]).sum())
+        total += float((8 * d[:, a] * D * d[:, b] * d[:, a] + 8 * (D * (D + 1) / 2) * d[:, a] * d[:, b]).sum())
+    return total
+
+
 def sparse_strings(n, count, seed=0):
     """``count`` sparse strings on n qubits: weight 1..4 inside a window of 6 sites at a random position, random codes X, Y, Z."""
     rng = np.random.default_rng(seed)
@@ -114,6 +137,7 @@ def main():
     ap.add_argument("--block-shots", default=None, metavar="U,M", help="with --block-widths: also time the block overlaps estimated from U settings of M shots")
     ap.add_argument("--shots", type=int, default=0, metavar="S", help="also time sample() with S shots per state in random bases")
     ap.add_argument("--shadow-shots", type=int, default=0, metavar="T", help="with --shots: also time the shadow kernel's shot-pair histograms from T shots per state")
+    ap.add_argument("--window", type=int, default=0, metavar="W", help="also time window_rdms on all windows of W qubits and projected_window_gram")
     args = ap.parse_args()
     if args.block_shots and not args.block_widths:
         ap.error("--block-shots needs --block-widths")
@@ -254,6 +278,23 @@ def main():
             "shadow_hist_ms_min": round(min(ts), 3), "shadow_hist_ms_max": round(max(ts), 3), "shadow_shot_pairs": shot_pairs,
             "shadow_shot_pairs_per_s": round(shot_pairs / (shadow_ms * 1e-3), 1), "shadow_over_sample": round(shadow_ms / dist["sample_ms"], 4),
             "median_offdiag_shadow": float(np.median(KSH[sh_pairs[:, 0] != sh_pairs[:, 1]])),
+        })
+    if args.window > 0:
+        W = args.window
+        ctx.window_rdms(xs, W)  # warm-up
+        ts = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            rho = ctx.window_rdms(xs, W)
+            ts.append(1e3 * (time.perf_counter() - t0))
+        win_ms = float(np.median(ts))
+        KW, wgram_ms = timed(lambda: ctx.projected_window_gram(rho), args.reps)
+        wflops = window_flops(info["dims"], W)
+        dist.update({
+            "window_width": W, "n_windows": int(rho.shape[1]), "window_reps": args.reps, "window_rdms_ms": round(win_ms, 3),
+            "window_rdms_ms_min": round(min(ts), 3), "window_rdms_ms_max": round(max(ts), 3), "window_flops": wflops,
+            "window_tflops": round(wflops / (win_ms * 1e-3) / 1e12, 3), "projected_window_gram_ms": round(wgram_ms, 3),
+            "window_over_pair": round(win_ms / pair_ms, 4), "median_offdiag_pqk_window": float(np.median(KW[off])),
         })
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
