@@ -510,6 +510,40 @@ int qk_sample_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_shots, const ui
                    uint64_t seed, int64_t first_state /* global index of state 0 */, uint8_t* bits /* [n_states][n_shots][n_sites] */,
                    double* logp /* [n_states][n_shots], may be NULL */);
 
+/* ---- amplitudes and outcome likelihoods of given strings ---------------------------------------------------------------------------
+ * qk_amplitudes_host: the amplitude <b| U_c |psi_s> of every given string under every state of a set -- strings the library did not
+ * draw, such as shots measured on hardware -- in the sampler's conventions (site k = qubit k, physical index 0 = |0>, states not
+ * necessarily normalised, codes 1..3 = X, Y, Z, outcome bit 0 = eigenvalue +1).  One string b in the bases c: v = [1], E = 0, for
+ * k = 0 .. n-1
+ *     W_t = v A_k[.][t][.] (t = 0, 1);   Z: W' = W;  X: W'_0,1 = (W_0 +- W_1)/sqrt2;  Y: W'_0,1 = (W_0 -+ i W_1)/sqrt2
+ *     u = W'_{b[k]} over the true bond;   m = max_a max(|Re u[a]|, |Im u[a]|)
+ *     m > 0: m = f 2^e with 0.5 <= f < 1 (frexp), v = u 2^-e (exact), E += e;   m == 0: v = 0, E = 0
+ *     amplitude = v_n[0] 2^E:   mant[s][j] = (Re, Im) of v_n[0],  expo[s][j] = E
+ *     logp[s][j] = 2 (log |v_n[0]| + E log 2) - log <psi_s|psi_s>          (-inf for a zero amplitude: not an error)
+ * The larger component of a mantissa is in [0.5, 1), or the mantissa is exactly 0 with E = 0.  The rescale is a power of two and
+ * the maximum has no order, so it costs no bits and amplitudes far below the smallest double (long or unnormalised chains) survive.
+ * <psi|psi> is L_n[0][0] of the environment pass of qk_pauli_strings_host -- the bits qk_local_paulis_host returns -- and is computed
+ * only when logp or norms is given.  bits_per_state = 0: one table [n_strings][n_sites] for every state; 1: a table per state
+ * (the shots of state s under state s; state s' x shots of state s is a call per s with the shared form).  bases are shared by
+ * every state, as the sampler's.
+ * An amplitude chain is one (state, tile of 64 strings), rows padded to 16; at site k every chain of a chain batch goes through one
+ * GEMM launch on the f64 matrix cores (string rows as M, K = the true left bond, fixed K order) and one launch that rotates, picks,
+ * takes the row maximum and scales: 2 n_sites + 1 launches per chain batch whatever n_strings -- half the sampler's, and no right
+ * environments.  mant and expo of a (state, string) are the same bits whatever the other states of the set, the other strings and
+ * their order, a shared or a per-state table, the cut into batches and the run: no atomics, no grid barrier, no spin wait.
+ * QK_AMP_BATCH=k (read per call) caps the chains of a batch; the result is the same bits for every k.  Synchronous; leaves the Gram
+ * statistics alone.  Device scratch: the reversed image, the tables and the results for the length of the call; per state batch
+ * the sweep's planes (and every L_k and R_k when <psi|psi> is asked for), per chain batch a slot of 6 P R doubles per chain (P = the
+ * state's largest padded bond, R = its strings padded to 16), each bounded by a quarter of the free memory, released by qk_ctx_trim.
+ * QK_EINVAL (the message names the argument): a null ctx, set, bits, mant or expo; a set of another context; a complex64 set;
+ * n_strings < 1; a byte of bits other than 0 or 1; a basis code outside 1..3; bits_per_state not 0 or 1.  QK_EDEVICE: a state of
+ * norm 0 when logp is asked for (the message names the state).                                                                      */
+int qk_amplitudes_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_strings,
+                       const uint8_t* bits, int32_t bits_per_state /* 0: [n_strings][n_sites] shared; 1: [n_states][n_strings][n_sites] */,
+                       const uint8_t* bases /* [n_strings][n_sites], NULL: all Z; shared by every state */,
+                       double* mant /* [n_states][n_strings][2] */, int32_t* expo /* [n_states][n_strings] */,
+                       double* logp /* [n_states][n_strings], may be NULL */, double* norms /* [n_states], may be NULL */);
+
 /* ---- block overlaps at finite shots: the randomised-measurement estimator -------------------------------------------------------
  * qk_shot_block_sums_host: the integer sums of the randomised-measurement overlap (Elben et al., PRL 124, 010504 (2020)) of two
  * outcome tables, for the first (side 0) or last (side 1) w qubits and every w of widths, from the same shot pairs.  It needs no

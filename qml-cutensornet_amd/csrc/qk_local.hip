@@ -7,7 +7,8 @@
 // qk_bond_purities_host and qk_bond_spectra_host (definitions above bond_call below), and the block kernels -- reduced-state
 // overlaps of the first or last w qubits for every pair of two sets -- qk_block_values_host and qk_block_self_host (definitions
 // above BlkSet below), and measurement shots of every state of a set, each shot and qubit in its own Pauli basis, qk_sample_host
-// (definitions above SmpArgs below), the reduced density matrices of every window of k qubits, qk_window_rdms_host (above WinArgs
+// (definitions above SmpArgs below), the amplitudes and outcome likelihoods of given strings, qk_amplitudes_host (above AmpArgs
+// below), the reduced density matrices of every window of k qubits, qk_window_rdms_host (above WinArgs
 // below), the block overlaps estimated from such shots, qk_shot_block_sums_host (above SbkArgs below), and the
 // shot-pair histograms of the classical-shadow kernel, qk_shadow_hist_host (above ShkArgs below) (include/qkgram.h).
 //
@@ -693,7 +694,7 @@ int env_run(qk_ctx* c, const qk_mps_set* set, const char* what, double* rev, con
   stage.assign(eb.b_tab, 0);
   size_t at = 0;
   auto put = [&](const void* src, size_t bytes, size_t span) {
-    std::memcpy(stage.data() + at, src, bytes);
+    if (bytes) std::memcpy(stage.data() + at, src, bytes);  // (an empty plan has no tasks)
     const size_t here = at;
     at += span;
     return base + here;
@@ -1613,6 +1614,265 @@ int sample_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_shots, const ui
   return QK_OK;
 }
 
+// ---- amplitudes of given strings (qk_amplitudes_host) -------------------------------------------------------------------------------
+// The sampler's chain without the draw: the outcome of every site is given.  One string b in the bases c, v = [1], E = 0, for
+// k = 0 .. n-1:
+//     W_t[b']  = sum_b v[b] A_k[b][t][b']                                   t = 0, 1
+//     W'       = smp_rotate(c[k], W)                                        (the sampler's rotation)
+//     u        = W'_{b[k]} over the true bond, zero beyond it
+//     m        = max_a max(|Re u[a]|, |Im u[a]|);   m > 0: m = f 2^e, 0.5 <= f < 1 (frexp), v = u 2^-e (exact), E += e
+//                                                   m == 0: v = 0, E = 0 (the amplitude is zero whatever follows)
+// <b| U_c |psi> = v_n[0] 2^E, returned as (Re, Im) of v_n[0] and E.  The rescale is a power of two and a maximum does not depend on
+// the order it is taken in, so it costs no bits and amplitudes far below the smallest double survive.  An amplitude chain is one
+// (state, tile of AMP_TILE strings) with a slot of its own (qk_local_plan.h); at site k every chain of the chain batch goes through
+// ONE launch of AMP_W (GEMM, string rows as M, K = the true left bond in the ring GEMM's fixed order) and ONE of AMP_PICK (one wave
+// per row): 2 n_sites + 1 launches per chain batch with the init kernel, whatever the number of strings.  Nothing of a row depends
+// on another row, no atomics, no grid barrier, no spin wait: mantissa and exponent of a (state, string) are the same bits whatever
+// the other states and strings, their order, a shared or a per-state table, the cut into batches (QK_AMP_BATCH caps the chains of
+// one) and the run.
+struct AmpArgs {
+  LocArgs e;              // the set and the state batch (the environment pass only when <psi|psi> is asked for)
+  const int32_t* cent;    // chain -> batch entry
+  const int32_t* str0;    // chain -> its first string
+  const int32_t* rows;    // chain -> its strings
+  const int64_t* cbase;   // chain -> first double of its slot
+  const uint8_t* bits;    // [n_strings][n_sites], or [n_states][n_strings][n_sites] with per_state
+  const uint8_t* bases;   // [n_strings][n_sites], NULL: all Z
+  const int2* tasks;      // this launch: (chain, block)
+  double* slots;
+  double* mant;           // [n_states][n_strings][2]
+  int32_t* expo;          // [n_states][n_strings]
+  int n_strings;
+  int per_state;
+  int step;               // site k
+};
+
+// One 64 x 64 output block of one amplitude chain's GEMM at site k: W = V^T A_k.
+__global__ __launch_bounds__(512) void qk_amp_gemm_kernel(const AmpArgs g) {
+  __shared__ __attribute__((aligned(16))) double lds[LOC_LDS_DOUBLES];
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = __builtin_amdgcn_readfirstlane(t.x);
+  const int blk = __builtin_amdgcn_readfirstlane(t.y);
+  const int i = __builtin_amdgcn_readfirstlane(g.cent[ch]);
+  const int n = g.e.n_sites, n1 = n + 1, k = g.step;
+  const long long st = __builtin_amdgcn_readfirstlane(g.e.states[i]);
+  const int l = __builtin_amdgcn_readfirstlane(g.e.dims[st * n1 + k]), r = __builtin_amdgcn_readfirstlane(g.e.dims[st * n1 + k + 1]);
+  const long long P = __builtin_amdgcn_readfirstlane(g.e.pmax[i]);
+  const int R = smp_rows_pad(__builtin_amdgcn_readfirstlane(g.rows[ch]));
+  const long long PR = P * R;
+  double* const slot = g.slots + uni64(g.cbase[ch]);
+  const double* const Are = slot + amp_V() * PR;
+  const double* const Aim = Are + PR;
+  const double* const Bre = g.e.data + uni64(g.e.offs[st * n + k]);
+  const double* const Bim = Bre + (long long)l * 2 * r;
+  double* const Cre = slot + amp_W() * PR;
+  double* const Cim = Cre + 2 * PR;
+  const int M = R, N = 2 * r, K = __builtin_amdgcn_readfirstlane(g.e.tru[st * n1 + k]);
+  const int npm = (M + 63) / 64;
+  const int m0 = 64 * (blk % npm), n0 = 64 * (blk / npm);
+  zgemm_ring3<false, LOC_KTL, LOC_NSLOT, true, 8, 64, double, 10>(Cre + (long long)m0 * N + n0, Cim + (long long)m0 * N + n0, N, Are + m0, Aim + m0, R, Bre + n0, Bim + n0, N,
+                                                                   min(64, M - m0), min(64, N - n0), K, lds);
+}
+
+// v = [1] and E = 0 of every string of a chain: V[0][row] = 1, the rest of the first 16 bond rows (pad_0 = 16) and the pad rows 0.
+__global__ __launch_bounds__(256) void qk_amp_init_kernel(const AmpArgs g) {
+  const int ch = blockIdx.x;
+  const int rows = g.rows[ch], R = smp_rows_pad(rows);
+  const int i = g.cent[ch];
+  const long long PR = (long long)g.e.pmax[i] * R;
+  double* const V = g.slots + g.cbase[ch] + amp_V() * PR;
+  for (int e = threadIdx.x; e < LOC_CHUNK * R; e += 256) V[e] = (e < rows) ? 1.0 : 0.0, V[PR + e] = 0.0;
+  const long long o = (long long)g.e.states[i] * g.n_strings + g.str0[ch];
+  for (int e = threadIdx.x; e < rows; e += 256) g.expo[o + e] = 0;
+}
+
+// The pick of one 16-row chunk of strings, one wave per row (four rows each): u = W'_{bit} of the row in its basis over the true
+// bond -- lane j takes a' = j, j + 64, .. --, the maximum of |Re u|, |Im u| over the lanes (a maximum has no order), its exponent e,
+// the next v = u 2^-e into V (K-major; zero from the true bond on, and for a pad row) and E += e; at the last site v[0] and E are
+// the result.
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_amp_pick_kernel(const AmpArgs g) {
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = t.x, c = t.y;
+  const int i = g.cent[ch];
+  const int n = g.e.n_sites, n1 = n + 1, k = g.step;
+  const long long st = g.e.states[i];
+  const int r = g.e.dims[st * n1 + k + 1], rt = g.e.tru[st * n1 + k + 1];
+  const int rows = g.rows[ch], R = smp_rows_pad(rows);
+  const long long PR = (long long)g.e.pmax[i] * R;
+  double* const slot = g.slots + g.cbase[ch];
+  const double* const W = slot + amp_W() * PR;
+  double* const V = slot + amp_V() * PR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int j = 0; j < LOC_CHUNK / 4; ++j) {
+    const int row = c * LOC_CHUNK + 4 * wave + j;
+    const bool valid = row < rows;
+    const long long str = g.str0[ch] + row;                  // of a valid row: below n_strings
+    const long long o = st * g.n_strings + str;
+    const long long brow = (g.per_state ? o : str) * n + k;  // read for a valid row only
+    const int code = (valid && g.bases) ? g.bases[str * n + k] : 3;
+    const int bit = valid ? g.bits[brow] : 0;
+    const double* const Wrow = W + (long long)row * 2 * r;
+    double m = 0.0;
+    for (int a = lane; valid && a < rt; a += 64) {
+      double a0r, a0i, a1r, a1i;
+      smp_rotate(code, Wrow[a], Wrow[a + 2 * PR], Wrow[a + r], Wrow[a + r + 2 * PR], a0r, a0i, a1r, a1i);
+      m = fmax(m, fmax(fabs(bit ? a1r : a0r), fabs(bit ? a1i : a0i)));
+    }
+    for (int s = 32; s > 0; s >>= 1) m = fmax(m, __shfl_xor(m, s));
+    int e = 0;
+    if (m > 0.0 && m < HUGE_VAL) (void)frexp(m, &e);
+    for (int a = lane; a < r; a += 64) {
+      double vr = 0, vi = 0;
+      if (valid && a < rt) {
+        double a0r, a0i, a1r, a1i;
+        smp_rotate(code, Wrow[a], Wrow[a + 2 * PR], Wrow[a + r], Wrow[a + r + 2 * PR], a0r, a0i, a1r, a1i);
+        vr = ldexp(bit ? a1r : a0r, -e), vi = ldexp(bit ? a1i : a0i, -e);
+      }
+      if (k + 1 < n) V[(long long)a * R + row] = vr, V[(long long)a * R + row + PR] = vi;
+      else if (valid && a == 0) g.mant[2 * o] = vr, g.mant[2 * o + 1] = vi;
+    }
+    if (valid && lane == 0) g.expo[o] = (m == 0.0) ? 0 : g.expo[o] + e;  // a zero amplitude is (0, 0) with E = 0, whatever came before
+  }
+}
+
+int amplitudes_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, const uint8_t* bits, const int32_t bits_per_state, const uint8_t* bases, double* mant,
+                   int32_t* expo, double* logp, double* norms) {
+  static const char* what = "qk_amplitudes_host";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!set) return qk_fail(QK_EINVAL, "%s: set is null", what);
+  if (!bits) return qk_fail(QK_EINVAL, "%s: bits is null", what);
+  if (!mant) return qk_fail(QK_EINVAL, "%s: mant is null", what);
+  if (!expo) return qk_fail(QK_EINVAL, "%s: expo is null", what);
+  if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
+  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; amplitudes need an fp64 set", what);
+  if (n_strings < 1) return qk_fail(QK_EINVAL, "%s: n_strings must be >= 1 (got %d)", what, n_strings);
+  if (bits_per_state != 0 && bits_per_state != 1) return qk_fail(QK_EINVAL, "%s: bits_per_state must be 0 (shared) or 1 (a table per state) (got %d)", what, bits_per_state);
+  const int ns = set->n_states, n = set->n_sites;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
+  const long long row_bytes = (long long)n_strings * n, n_bits = (bits_per_state ? ns : 1) * row_bytes;
+  if (const long long bad = amp_bad_bit(bits, n_bits); bad >= 0) {
+    if (bits_per_state) return qk_fail(QK_EINVAL, "%s: bits[%lld][%lld][%lld] = %d is not an outcome bit (0 or 1)", what, bad / row_bytes, bad % row_bytes / n, bad % n, bits[bad]);
+    return qk_fail(QK_EINVAL, "%s: bits[%lld][%lld] = %d is not an outcome bit (0 or 1)", what, bad / n, bad % n, bits[bad]);
+  }
+  if (bases)
+    if (const long long bad = smp_bad_basis(bases, row_bytes); bad >= 0)
+      return qk_fail(QK_EINVAL, "%s: bases[%lld][%lld] = %d is not a basis code (1..3 = X, Y, Z)", what, bad / n, bad % n, bases[bad]);
+  long long cap = 0;  // amplitude chains per batch; 0: the memory rule alone
+  if (const char* v = std::getenv("QK_AMP_BATCH")) {
+    cap = std::atoll(v);
+    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_AMP_BATCH must be >= 1 (got \"%s\")", what, v);
+  }
+  QkRangeGuard range_("qk:amplitudes");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  // <psi|psi> = L_n[0][0] of the environment pass of the Pauli strings (the bits of qk_local_paulis_host), only when it is asked
+  // for; otherwise a state batch is its tables alone (an empty plan)
+  const bool want_norm = logp || norms;
+  EnvSizes z;
+  env_sizes(set->dims_true.data(), ns, n, set->max_pad, LOC_RMUL, want_norm, z);
+  const size_t n_rows = (size_t)ns * n_strings;
+  QkDevBuf rev, dbits, dbases, dmant, dexpo, dnorm;
+  HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
+  HIP_TRY_AS(what, dbits.alloc(al256((size_t)n_bits)));
+  HIP_TRY_AS(what, hipMemcpy(dbits.get(), bits, (size_t)n_bits, hipMemcpyHostToDevice));
+  if (bases) {
+    HIP_TRY_AS(what, dbases.alloc(al256((size_t)row_bytes)));
+    HIP_TRY_AS(what, hipMemcpy(dbases.get(), bases, (size_t)row_bytes, hipMemcpyHostToDevice));
+  }
+  HIP_TRY_AS(what, dmant.alloc(n_rows * 2 * sizeof(double)));
+  HIP_TRY_AS(what, dexpo.alloc(al256(n_rows * sizeof(int32_t))));
+  if (want_norm) HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
+  // memory bound of a state batch (its scratch and the slots of its chains): a quarter of what is free; the scratch of a batch
+  // takes at most half of that (at least one state per batch), the chains of a batch the rest (at least one)
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  const std::vector<int> bstart = batch_cut(z.need, 0, budget / 2);
+  const Plan plan = want_norm ? env_plan(n) : Plan{};
+  std::vector<Task2> tasks;
+  std::vector<long long> first;
+  std::vector<char> cstage;
+  std::vector<int64_t> h_cbase;
+  EnvBatch eb;
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+    env_tables(z, plan, s0, nb, 0, eb);
+    const SmpChains ch = list_amp_chains(z, s0, nb, n_strings, AMP_TILE);
+    const std::vector<size_t> cstart = chain_cut(ch.weight, budget - eb.tot, cap);
+    struct ChainBytes { size_t i32, cbase, tasks, slots; size_t tab() const { return 3 * i32 + cbase + tasks; } };  // cent | str0 | rows | cbase | tasks
+    auto chain_bytes = [&](const size_t c0, const size_t c1) {
+      long long nt = 0, sl = 0;
+      for (size_t e = c0; e < c1; ++e) nt += ch.ntasks[e], sl += ch.slot[e];
+      return ChainBytes{al256((c1 - c0) * sizeof(int32_t)), al256((c1 - c0) * sizeof(int64_t)), al256((size_t)nt * sizeof(int2)), (size_t)sl * sizeof(double)};
+    };
+    size_t b_chain = 0;
+    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
+      const ChainBytes cbz = chain_bytes(cstart[cb], cstart[cb + 1]);
+      b_chain = std::max(b_chain, cbz.tab() + cbz.slots);
+    }
+    // one device buffer for the state batch: [tables | tasks | scratch] then the chain batch's [tables | tasks | slots]
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, b_chain)) return rc;
+    if (want_norm) qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(eb.g, nb, dnorm.get<double>());
+    HIP_TRY_AS(what, hipGetLastError());
+    AmpArgs q{};
+    q.e = eb.g;
+    q.bits = dbits.get<uint8_t>();
+    q.bases = bases ? dbases.get<uint8_t>() : nullptr;
+    q.mant = dmant.get<double>(), q.expo = dexpo.get<int32_t>();
+    q.n_strings = n_strings, q.per_state = bits_per_state;
+    char* const cbase0 = eb.base + eb.used();
+    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
+      const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
+      if (nc == 0) continue;
+      const ChainBytes cbz = chain_bytes(c0, c0 + nc);
+      h_cbase.resize(nc);
+      long long sl = 0;
+      for (size_t e = 0; e < nc; ++e) h_cbase[e] = sl, sl += ch.slot[c0 + e];
+      amp_lists(z, s0, ch, c0, nc, tasks, first);
+      cstage.assign(cbz.tab(), 0);
+      std::memcpy(cstage.data(), ch.cent.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + cbz.i32, ch.shot0.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + 2 * cbz.i32, ch.rows.data() + c0, nc * sizeof(int32_t));
+      std::memcpy(cstage.data() + 3 * cbz.i32, h_cbase.data(), nc * sizeof(int64_t));
+      std::memcpy(cstage.data() + 3 * cbz.i32 + cbz.cbase, tasks.data(), tasks.size() * sizeof(int2));
+      q.cent = reinterpret_cast<const int32_t*>(cbase0);
+      q.str0 = reinterpret_cast<const int32_t*>(cbase0 + cbz.i32);
+      q.rows = reinterpret_cast<const int32_t*>(cbase0 + 2 * cbz.i32);
+      q.cbase = reinterpret_cast<const int64_t*>(cbase0 + 3 * cbz.i32);
+      const int2* d_ctasks = reinterpret_cast<const int2*>(cbase0 + 3 * cbz.i32 + cbz.cbase);
+      q.slots = reinterpret_cast<double*>(cbase0 + cbz.tab());
+      HIP_TRY_AS(what, hipMemcpyAsync(cbase0, cstage.data(), cbz.tab(), hipMemcpyHostToDevice, c->stream));
+      qk_amp_init_kernel<<<dim3((unsigned)nc), dim3(256), 0, c->stream>>>(q);
+      for (size_t li = 0; li + 1 < first.size(); ++li) {
+        q.tasks = d_ctasks + first[li];
+        q.step = (int)(li / 2);
+        if (first[li + 1] <= first[li]) continue;
+        const dim3 grid((unsigned)(first[li + 1] - first[li]));
+        if (AMP_KINDS[li % 2] == AMP_W) qk_amp_gemm_kernel<<<grid, dim3(512), 0, c->stream>>>(q);
+        else qk_amp_pick_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+      }
+      HIP_TRY_AS(what, hipGetLastError());
+      HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
+    }
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  }
+  HIP_TRY_AS(what, hipMemcpy(mant, dmant.get(), n_rows * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY_AS(what, hipMemcpy(expo, dexpo.get(), n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (!want_norm) return QK_OK;
+  std::vector<double> h_norm(ns);
+  HIP_TRY_AS(what, hipMemcpy(h_norm.data(), dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+  if (norms) std::memcpy(norms, h_norm.data(), (size_t)ns * sizeof(double));
+  if (logp)
+    for (int s = 0; s < ns; ++s) {
+      if (!(h_norm[s] > 0.0) || !std::isfinite(h_norm[s])) return qk_fail(QK_EDEVICE, "%s: state %d has norm 0 (or a norm that is not finite): logp is not defined", what, s);
+      const double ln = std::log(h_norm[s]);
+      for (int m = 0; m < n_strings; ++m) {
+        const size_t o = (size_t)s * n_strings + m;
+        logp[o] = amp_logp(mant[2 * o], mant[2 * o + 1], expo[o], ln);
+      }
+    }
+  return QK_OK;
+}
+
 // ---- windows of k qubits (qk_window_rdms_host) ------------------------------------------------------------------------------------
 // Window (a, w) = the qubits a .. a+w-1, b = a + w, 1 <= w <= min(n, 6), 0 <= a <= n - w; row index s = sum_j s_{a+j} 2^(w-1-j)
 // (qubit a is the most significant bit).  Site k = qubit k, physical index 0 = |0>, states not necessarily normalised,
@@ -2425,6 +2685,11 @@ extern "C" int qk_shot_block_sums_host(qk_ctx* c, int32_t n_sites, int32_t n_set
                                        const uint8_t* bits_y, int64_t n_pairs, const int32_t* pairs, int32_t side, int32_t n_widths, const int32_t* widths, int64_t* sums,
                                        int64_t* per_setting) {
   return shot_block_sums(c, n_sites, n_settings, shots_per_setting, nx, bits_x, ny, bits_y, n_pairs, pairs, side, n_widths, widths, sums, per_setting);
+}
+
+extern "C" int qk_amplitudes_host(qk_ctx* c, const qk_mps_set* set, int32_t n_strings, const uint8_t* bits, int32_t bits_per_state, const uint8_t* bases, double* mant,
+                                  int32_t* expo, double* logp, double* norms) {
+  return amplitudes_run(c, set, n_strings, bits, bits_per_state, bases, mant, expo, logp, norms);
 }
 
 extern "C" int qk_sample_host(qk_ctx* c, const qk_mps_set* set, int32_t n_shots, const uint8_t* bases, uint64_t seed, int64_t first_state, uint8_t* bits, double* logp) {

@@ -1,13 +1,15 @@
 // qk_local_plan.h -- the host-side plan of the local sweeps (qk_local.hip): the launch kinds, the scratch layout, the pair index, the
 // sizes and the cut into state batches, the tables and task lists of a batch, the plans of the entry points, the chain side of the
-// Pauli strings, of the block kernels, of the sampler and of the k-qubit windows, the integer side of the shot-based block overlaps and of the shadow kernel's shot-pair histograms.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
+// Pauli strings, of the block kernels, of the sampler, of the amplitude chains and of the k-qubit windows, the integer side of the shot-based block overlaps and of the shadow kernel's shot-pair histograms.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
 // -fsanitize=address,undefined); the few functions the kernels also call are QK_HD.
 #pragma once
 #include "qk_plan.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <utility>
 #include <vector>
 
@@ -18,7 +20,7 @@ constexpr int LOC_CHUNK = 16;  // rows per reduction task
 // Every launch kind of qk_local.hip.  Kinds >= 0 are GEMM launches (64 x 64 output blocks), the others elementwise or reductions
 // in 16-row chunks.  LOC_*: tasks (batch entry, block), qk_local_gemm_kernel; STR_*: tasks (chain, block), qk_str_gemm_kernel;
 // BLK_*: tasks (pair chain, block), qk_blk_gemm_kernel; SMP_*: tasks (shot chain, block), qk_smp_gemm_kernel; WIN_*: tasks (window
-// chain, block), qk_win_gemm_kernel.
+// chain, block), qk_win_gemm_kernel; AMP_*: tasks (amplitude chain, block), qk_amp_gemm_kernel.
 enum LocKind : int {
   LOC_REV_T = 0,   // reversed chain: T = Lr^T Ar_j              (Lr_j = R_{o+1}, o = n-1-j)
   LOC_REV_X = 1,   // reversed chain: R_o = T^T conj(Ar_j)
@@ -52,6 +54,8 @@ enum LocKind : int {
                       // of both seeds (G_0 = 1, Gr_0 = R_b) and both t in one launch; the reversed image's site c is the A operand
   WIN_H = 18,         // window chain: H[alpha'][(s, gamma)] = sum_alpha L_a[alpha][alpha'] G_w[alpha][(s, gamma)] (the LOC_FWD_T shape, N = 2^w chi_b)
   WIN_CLOSE = -12,    // qk_win_close_kernel: sum Gr_w[alpha][(s, gamma')] conj(H[alpha][(s', gamma')]) of every s <= s' in 16-row chunks of alpha
+  AMP_W = 19,         // amplitude chain (state, string tile), site k: W[row][(t, b')] = sum_b V[b][row] A_k[b][(t, b')] (the SMP_W shape)
+  AMP_PICK = -13,     // qk_amp_pick_kernel: W'_{bit} of a row in its basis, its maximum, its exponent and the scaled next V, one wave per row
 };
 QK_HD constexpr bool conj_b(const int kind) { return kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V || kind == LOC_DIST_X || kind == STR_X || kind == BLK_X || kind == BLK_W; }
 
@@ -503,6 +507,67 @@ inline long long smp_bad_basis(const uint8_t* bases, const long long count) {
   for (long long e = 0; e < count; ++e)
     if (bases[e] < 1 || bases[e] > 3) return e;
   return -1;
+}
+
+// ---- amplitudes of given strings (qk_amplitudes_host) -------------------------------------------------------------------------------
+// An amplitude chain is one (state, string tile): `tile` = 16 m consecutive strings of the call, the last tile ragged, rows padded
+// to R as a shot chain's.  It needs no right environment and no draw, so its slot is amp_size() P R doubles, every matrix as a re
+// plane then an im plane, offsets in units of P R:
+//   V  [P][R]   at amp_V() = 0   the row vectors of the strings, K-major: the A operand of AMP_W, ld = R
+//   W  [R][2P]  at amp_W() = 2   (W_0 | W_1) of the rows, ld = 2 pad_{k+1}
+// The chains of a state batch are an SmpChains (shot0 = the chain's first string), cut by chain_cut (QK_AMP_BATCH caps the chains of
+// a batch).
+constexpr int AMP_TILE = SMP_TILE;  // strings per tile: one 64-row block of the ring GEMM
+QK_HD constexpr int amp_V() { return 0; }
+QK_HD constexpr int amp_W() { return 2; }
+QK_HD constexpr int amp_size() { return 6; }
+static_assert(amp_W() >= amp_V() + 2 && amp_size() >= amp_W() + 4, "V (2 planes of P R) and W (2 planes of 2 P R) do not overlap");
+constexpr int AMP_KINDS[2] = {AMP_W, AMP_PICK};  // the launches of a site, in stream order
+// the blocks of an amplitude chain of R padded rows (p = its state's padded bonds) in the launch `kind` of site k
+inline int amp_task_count(const int kind, const int k, const int32_t* p, const int R) {
+  return kind == AMP_W ? (int)blocks64(R, 2ll * p[k + 1]) : R / LOC_CHUNK;
+}
+// launches of a chain batch: the init kernel, then AMP_KINDS at every site
+inline int amp_launches(const int n) { return 2 * n + 1; }
+inline SmpChains list_amp_chains(const EnvSizes& z, const int s0, const int nb, const int n_strings, const int tile) {
+  const int n = z.n_sites;
+  SmpChains c;
+  for (int i = 0; i < nb; ++i)
+    for (int t = 0; t < smp_tiles(n_strings, tile); ++t) {
+      const int rows = std::min(tile, n_strings - t * tile), R = smp_rows_pad(rows);
+      long long nt = 0;
+      for (int k = 0; k < n; ++k)
+        for (const int kind : AMP_KINDS) nt += amp_task_count(kind, k, &z.pad[(size_t)(s0 + i) * (n + 1)], R);
+      c.cent.push_back(i), c.shot0.push_back(t * tile), c.rows.push_back(rows);
+      c.slot.push_back((long long)amp_size() * z.pmax[s0 + i] * R), c.ntasks.push_back(nt);
+      c.weight.push_back(c.slot.back() + nt + 4);
+    }
+  return c;
+}
+// Task lists (chain of the batch, block) of the amplitude chains [c0, c0 + nc): launch 2k + j is AMP_KINDS[j] at site k.
+inline void amp_lists(const EnvSizes& z, const int s0, const SmpChains& c, const size_t c0, const size_t nc, std::vector<Task2>& tasks, std::vector<long long>& first) {
+  const int n = z.n_sites;
+  tasks.clear(), first.clear();
+  for (int k = 0; k < n; ++k)
+    for (const int kind : AMP_KINDS) {
+      first.push_back((long long)tasks.size());
+      for (size_t e = 0; e < nc; ++e) {
+        const int nbk = amp_task_count(kind, k, &z.pad[(size_t)(s0 + c.cent[c0 + e]) * (n + 1)], smp_rows_pad(c.rows[c0 + e]));
+        for (int b = 0; b < nbk; ++b) tasks.push_back(Task2{(int)e, b});
+      }
+    }
+  first.push_back((long long)tasks.size());
+}
+// the first byte of an outcome table that is neither 0 nor 1: its index, or -1
+inline long long amp_bad_bit(const uint8_t* bits, const long long count) {
+  for (long long e = 0; e < count; ++e)
+    if (bits[e] > 1) return e;
+  return -1;
+}
+// log of |v 2^E|^2 / <psi|psi> from the mantissa v = (re, im), the exponent E and log <psi|psi>: -inf for a zero amplitude
+inline double amp_logp(const double re, const double im, const int32_t E, const double log_norm) {
+  const double a = std::hypot(re, im);
+  return a == 0.0 ? -std::numeric_limits<double>::infinity() : 2.0 * (std::log(a) + E * 0.69314718055994530942) - log_norm;
 }
 
 // ---- windows of k qubits (qk_window_rdms_host) ------------------------------------------------------------------------------------

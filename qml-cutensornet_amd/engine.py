@@ -109,6 +109,7 @@ _SIGNATURES = [
     ("qk_block_self_host", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_window_rdms_host", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_sample_host", C.c_int, [_P, _P, C.c_int32, _P, C.c_uint64, C.c_int64, _P, _P]),
+    ("qk_amplitudes_host", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("qk_shot_block_sums_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_shadow_hist_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
@@ -527,6 +528,24 @@ def shadow_kernel(H, n_qubits: int, gamma=1.0, tau=1.0, equal=None) -> np.ndarra
     """The shadow kernel from shot-pair histograms: ``exp(tau * shadow_inner(H, n_qubits, gamma, equal))`` (the paper: tau = gamma =
     1), pure numpy, any leading shape (..., 2 n + 1)."""
     return np.exp(float(tau) * shadow_inner(H, n_qubits, gamma, equal))
+
+
+def xeb_fidelity(logp, n_qubits: int, kind: str = "linear") -> np.ndarray:
+    """Cross-entropy benchmarking fidelity of measured strings under simulated states, per state: ``logp`` (..., n_strings) is the
+    log probability of each string (``Context.amplitudes(..., logp=True)``), the mean runs over the last axis.
+        kind="linear":  2^n mean(p) - 1                        (1 for strings drawn from a Porter-Thomas state, 0 for uniform ones)
+        kind="log":     n log 2 + gamma_Euler + mean(log p)    (likewise; -inf when a string has probability 0)"""
+    n = int(n_qubits)
+    lp = np.asarray(logp, dtype=np.float64)
+    if lp.ndim < 1 or lp.shape[-1] < 1:
+        raise ValueError(f"logp must have at least one string on its last axis, got shape {lp.shape}")
+    if n < 1:
+        raise ValueError(f"n_qubits must be >= 1 (got {n_qubits!r})")
+    if kind == "linear":
+        return np.ldexp(np.exp(lp), n).mean(axis=-1) - 1.0
+    if kind == "log":
+        return n * np.log(2.0) + float(np.euler_gamma) + lp.mean(axis=-1)
+    raise ValueError(f"kind must be 'linear' or 'log', got {kind!r}")
 
 
 def bases_table(bases, shots: int, n_qubits: int) -> np.ndarray:
@@ -1560,6 +1579,39 @@ class Context:
         _check(lib().qk_sample_host(self._h, xs.handle, S, None if B is None else B.ctypes.data, int(key[0]) | (int(key[1]) << 32), int(first_state),
                                     bits.ctypes.data, lp.ctypes.data), "qk_sample_host")
         return (bits, lp) if logp else bits
+
+    def amplitudes(self, xs: MpsSet, bits, bases=None, per_state: bool = False, logp: bool = False, scaled: bool = False, norms: bool = False):
+        """Amplitudes ``<b| U_bases |psi_s>`` of given outcome strings under every state of an fp64 set -- strings the library did
+        not draw, such as shots measured on hardware: complex128 of shape (n_states, n_strings).  ``bits`` is (n_strings, n_sites)
+        of 0 / 1, shared by every state, or with ``per_state=True`` (n_states, n_strings, n_sites), a table per state (the bits
+        ``sample`` returns); ``bases`` is anything ``bases_table`` takes, shared by every state (``None``: all Z; bit 0 = eigenvalue
+        +1).  The device returns a mantissa and a power of two per amplitude (``MPS.amplitude`` is the mirror of its loop); the
+        default result is ``ldexp(mant, expo)``, which may underflow to 0 for long or unnormalised chains -- ``scaled=True``
+        returns ``(mant complex128, expo int32)`` instead, the larger component of ``mant`` in [0.5, 1).  ``logp=True`` appends
+        the log of the probability ``|amplitude|^2 / <psi|psi>`` (-inf for a zero amplitude), float64 (n_states, n_strings), and
+        ``norms=True`` <psi|psi> of each state (the bits of ``local_paulis``).  A (state, string) value is the same bits whatever
+        the other states and strings, their order, the table's form and the run.  Synchronous."""
+        info = xs.info()
+        ns, n = info["n_states"], info["n_sites"]
+        b = np.asarray(bits)
+        want = 3 if per_state else 2
+        if b.dtype.kind not in "iub" or b.ndim != want or b.shape[-1] != n or (per_state and b.shape[0] != ns):
+            shape = f"({ns}, n_strings, {n})" if per_state else f"(n_strings, {n})"
+            raise ValueError(f"bits must be an integer array of shape {shape}; got shape {b.shape}, dtype {b.dtype}")
+        if b.size and (b.min() < 0 or b.max() > 255):
+            raise ValueError(f"bits holds a value that is not 0 or 1 ({int(b.min() if b.min() < 0 else b.max())})")
+        b = np.ascontiguousarray(b, dtype=np.uint8)
+        S = b.shape[-2]
+        B = None if bases is None else bases_table(bases, S, n)
+        mant = np.zeros((ns, S, 2), dtype=np.float64)
+        expo = np.zeros((ns, S), dtype=np.int32)
+        lp = np.zeros((ns, S), dtype=np.float64) if logp else None
+        nrm = np.zeros(ns, dtype=np.float64) if norms else None
+        _check(lib().qk_amplitudes_host(self._h, xs.handle, S, b.ctypes.data, 1 if per_state else 0, None if B is None else B.ctypes.data, mant.ctypes.data,
+                                        expo.ctypes.data, None if lp is None else lp.ctypes.data, None if nrm is None else nrm.ctypes.data), "qk_amplitudes_host")
+        m = mant[..., 0] + 1j * mant[..., 1]
+        out = ((m, expo) if scaled else (np.ldexp(mant[..., 0], expo) + 1j * np.ldexp(mant[..., 1], expo),)) + ((lp,) if logp else ()) + ((nrm,) if norms else ())
+        return out if len(out) > 1 else out[0]
 
     def bond_purities(self, mps_set: MpsSet, norms: bool = False):
         """Purity tr(rho^2) of the reduced state left of every bond, for every state of an fp64 set: float64 of shape (n_states,

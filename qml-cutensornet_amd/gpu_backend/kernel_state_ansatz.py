@@ -642,6 +642,50 @@ def build_entanglement_profile(mpi_comm, ansatz, X, truncation_error=None, max_v
     return out
 
 
+def build_outcome_likelihoods(mpi_comm, ansatz, X, bits, bases=None, per_state=False, truncation_error=None):
+    """Log likelihoods of given outcome strings under the states of ``X`` -- shots measured on hardware, or any list of strings:
+    ``logp[i, j] = log(|<b_j| U_bases |psi(x_i)>|^2 / <psi|psi>)``.  Each rank builds its share of the states (same builders, same
+    ``QK_BUILDER`` rules as ``build_projected_kernel_matrix``), computes the log likelihoods of its states on its device
+    (``Context.amplitudes(..., logp=True)``) and the rows are all-gathered, never an MPS.  ``bits`` is (n_strings, n_qubits) of
+    0 / 1, shared by every state -- the cross table "state x string" --, or with ``per_state=True`` (len(X), n_strings, n_qubits),
+    the strings of state i under state i; ``bases`` is anything ``engine.bases_table`` takes, shared by every state.  Rank 0
+    returns float64 (len(X), n_strings), the other ranks ``None``; a row is the same bits for any number of ranks.
+    ``engine.xeb_fidelity`` reads the result."""
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    X = np.asarray(X, dtype=np.float64)
+    n_qubits = int(ansatz.num_qubits)
+    bits = np.asarray(bits)
+    want = (len(X), n_qubits) if per_state else (n_qubits,)
+    if bits.dtype.kind not in "iub" or bits.ndim != len(want) + 1 or bits.shape[-1] != n_qubits or (per_state and bits.shape[0] != len(X)) or bits.shape[-2] < 1:
+        shape = f"({len(X)}, n_strings, {n_qubits})" if per_state else f"(n_strings, {n_qubits})"
+        raise ValueError(f"bits must be an integer array of shape {shape} with n_strings >= 1; got shape {bits.shape}, dtype {bits.dtype}")
+    n_strings = bits.shape[-2]
+    B = None if bases is None else _engine.bases_table(bases, n_strings, n_qubits)
+    fidelity = 1.0 - float(truncation_error)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: outcome likelihoods have no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    ctx = _engine.default_context(device_id)
+    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
+    lo, local, _, _ = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers)
+    ctx.trim()  # the device builder's arena goes back before the chains need memory
+    if local is None:
+        lp = np.zeros((0, n_strings), dtype=np.float64)
+    else:
+        share = bits[lo : lo + len(local)] if per_state else bits
+        lp = ctx.amplitudes(local, share, bases=B, per_state=per_state, logp=True)[1]
+        local.close()
+    out = _gather_features(mpi_comm, lo, lp, len(X))
+    return out if is_root else None
+
+
 def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64), max_discard=0.0, truncation_error=None, info_file=None, loglevel=30):
     """The Gram ``K`` of ``build_kernel_matrix`` and, from the SAME states, the Gram under each bond cap of ``caps``: one build, then
     per cap every rank compresses its share on its device (``Context.compress``: one canonical truncation sweep per state, at

@@ -262,6 +262,66 @@ class MPS:
         out = (bits,) + ((lp,) if logp else ()) + ((worst,) if margin else ())
         return out if len(out) > 1 else bits
 
+    def amplitude(self, bits, bases=None, scaled: bool = False, logp: bool = False, dtype=np.complex128):
+        """Amplitudes ``<b| U_bases |psi>`` of given outcome strings on the host, the numpy mirror of ``Context.amplitudes``:
+        ``bits`` is (n,) or (S, n) of 0 / 1 (bit 0 = eigenvalue +1), ``bases`` anything ``engine.bases_table`` takes (codes 1..3 =
+        X, Y, Z; ``None``: all Z).  Per string, v = [1], E = 0, for k = 0 .. n-1: ``W_t = v A_k[:, t, :]``, rotated into the basis
+        (Z: as it is; X: (W_0 +- W_1)/sqrt2; Y: (W_0 -+ i W_1)/sqrt2), ``u = W'_bit``, ``m = max_a max(|Re u[a]|, |Im u[a]|)``;
+        ``m > 0``: ``m = f 2^e`` with 0.5 <= f < 1 (frexp), ``v = u 2^-e`` (exact), ``E += e``; ``m == 0``: ``v = 0``, ``E = 0``.  The
+        amplitude is ``v_n[0] 2^E``: complex128 of shape (S,) (``()`` for a single string), which may underflow to 0;
+        ``scaled=True`` returns ``(mant, expo int32)`` instead, the larger component of ``mant`` in [0.5, 1) or ``mant`` exactly 0
+        with ``expo`` 0.  ``logp=True`` appends ``2 (log |mant| + expo log 2) - log <psi|psi>`` (-inf for a zero amplitude; a
+        state of norm 0 raises ``ValueError``).  ``dtype=np.clongdouble`` runs the same loop in extended precision (what the tests
+        measure the float64 loop against)."""
+        from .engine import bases_table
+
+        n = len(self.tensors)
+        b = np.asarray(bits)
+        single = b.ndim == 1
+        if single:
+            b = b[None, :]
+        if b.dtype.kind not in "iub" or b.ndim != 2 or b.shape[1] != n or b.shape[0] < 1:
+            raise ValueError(f"bits must be an integer array of shape ({n},) or (n_strings >= 1, {n}); got shape {np.shape(bits)}, dtype {b.dtype}")
+        if b.min() < 0 or b.max() > 1:
+            raise ValueError("bits holds a value that is not 0 or 1")
+        S = b.shape[0]
+        B = bases_table(bases, S, n)
+        if B.min() < 1 or B.max() > 3:
+            raise ValueError("bases holds a code outside 1..3 = X, Y, Z")
+        cdt = np.dtype(dtype)
+        rdt = np.empty(0, dtype=cdt).real.dtype
+        ts = [np.asarray(t, dtype=cdt) for t in self.tensors]
+        h = rdt.type(1) / np.sqrt(rdt.type(2)) if cdt != np.complex128 else rdt.type(0.70710678118654752440)
+        v = np.ones((S, 1), dtype=cdt)
+        E = np.zeros(S, dtype=np.int64)
+        for k in range(n):
+            W = np.einsum("rb,btc->rtc", v, ts[k])
+            W0, W1 = W[:, 0], W[:, 1]
+            code = B[:, k][:, None]
+            A0 = np.where(code == 1, (W0 + W1) * h, np.where(code == 2, (W0 - 1j * W1) * h, W0))
+            A1 = np.where(code == 1, (W0 - W1) * h, np.where(code == 2, (W0 + 1j * W1) * h, W1))
+            u = np.where(b[:, k][:, None] == 1, A1, A0)
+            m = np.maximum(np.abs(u.real), np.abs(u.imag)).max(axis=1)
+            e = np.where((m > 0) & np.isfinite(m), np.frexp(m)[1], 0).astype(np.int64)
+            v = (np.ldexp(u.real, -e[:, None]) + 1j * np.ldexp(u.imag, -e[:, None])).astype(cdt)
+            E = np.where(m == 0, 0, E + e)  # a zero amplitude is (0, 0) with E = 0, whatever came before
+        mant, expo = v[:, 0], E.astype(np.int32)
+        out = (mant, expo) if scaled else ((np.ldexp(mant.real, expo) + 1j * np.ldexp(mant.imag, expo)).astype(cdt),)
+        if logp:
+            R = np.ones((1, 1), dtype=np.complex128)
+            for t in reversed(self.tensors):
+                t = np.asarray(t, dtype=np.complex128)
+                R = np.einsum("asc,cd,bsd->ab", t, R, t.conj(), optimize=True)
+            norm = float(R[0, 0].real)
+            if not (norm > 0.0 and np.isfinite(norm)):
+                raise ValueError("amplitude: the state has norm 0 (or a norm that is not finite): logp is not defined")
+            a = np.abs(mant).astype(np.float64)
+            with np.errstate(divide="ignore"):
+                out += (np.where(a == 0.0, -np.inf, 2.0 * (np.log(a) + expo * np.log(2.0)) - np.log(norm)),)
+        if single:
+            out = tuple(o[0] for o in out)
+        return out if len(out) > 1 else out[0]
+
     def vdot(self, other: "MPS") -> complex:
         """<self|other> through the HIP engine (single pair; the Gram path is batch-first)."""
         from .engine import default_context

@@ -33,8 +33,15 @@ multiply-add: the environment pass (the GEMMs of the one-qubit sweep, ``local_sw
 every state, the steps j = 0 .. W-1 at site c = b-1-j -- two products (t = 0, 1) of chi_c x 2^j chi_b over chi_c+1 for the seed R_b
 and, from j = 1 on, for the seed 1 -- then H (chi_a x 2^W chi_b over chi_a) and the closing sum (2^W (2^W + 1) / 2 entries of chi_a
 chi_b terms).
+``--amplitudes S`` adds the amplitudes of given strings: S shots per state drawn with ctx.sample in engine.random_bases(S, n, 0)
+(timed like ``--shots``), then ctx.amplitudes(xs, bits, bases, per_state=True, logp=True) on them, after a warm-up: amplitudes_ms (the
+median; amplitudes_ms_min and _max give the spread over the repetitions), amp_strings = S, amp_flops and amp_tflops, amp_sample_ms
+and amp_over_sample = amplitudes_ms / amp_sample_ms of the same run, and max_abs_dlogp_amp_sample = max |logp_amplitudes -
+logp_sample|.  amp_flops, from the true bonds at 8 flops per complex multiply-add: per state, site and string the row of W = V (A^0 |
+A^1) (1 x 2 chi_k+1 over chi_k), i.e. S sum 8 (2 chi_k+1 chi_k), plus the environment pass that gives <psi|psi> for logp
+(``local_sweep_flops``).
 usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement] [--compress CHI]
-                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S [--shadow-shots T]] [--window W]"""
+                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S [--shadow-shots T]] [--window W] [--amplitudes S]"""
 import argparse
 import json
 import os
@@ -85,6 +92,15 @@ def sample_flops(dims, shots):
     d = np.asarray(dims, dtype=np.float64)
     l, r = d[:, :-1], d[:, 1:]
     return float(shots * (8 * (2 * r * l) + 8 * (2 * r * r)).sum())
+
+
+def amplitude_flops(dims, strings):
+    """Algorithmic flops of ``amplitudes(..., logp=True)`` on ``strings`` strings per state from the true bonds (8 per complex
+    multiply-add).  Per site and string, l = chi_k, r = chi_k+1: the row of W = V (A^0 | A^1) (1 x 2r over l); and once per state
+    the environment pass that gives <psi|psi> (``local_sweep_flops``)."""
+    d = np.asarray(dims, dtype=np.float64)
+    l, r = d[:, :-1], d[:, 1:]
+    return float(strings * (8 * (2 * r * l)).sum()) + local_sweep_flops(dims)
 
 
 def window_flops(dims, w):
@@ -138,6 +154,7 @@ def main():
     ap.add_argument("--shots", type=int, default=0, metavar="S", help="also time sample() with S shots per state in random bases")
     ap.add_argument("--shadow-shots", type=int, default=0, metavar="T", help="with --shots: also time the shadow kernel's shot-pair histograms from T shots per state")
     ap.add_argument("--window", type=int, default=0, metavar="W", help="also time window_rdms on all windows of W qubits and projected_window_gram")
+    ap.add_argument("--amplitudes", type=int, default=0, metavar="S", help="also time amplitudes() with logp on S shots per state drawn with sample()")
     args = ap.parse_args()
     if args.block_shots and not args.block_widths:
         ap.error("--block-shots needs --block-widths")
@@ -295,6 +312,24 @@ def main():
             "window_rdms_ms_min": round(min(ts), 3), "window_rdms_ms_max": round(max(ts), 3), "window_flops": wflops,
             "window_tflops": round(wflops / (win_ms * 1e-3) / 1e12, 3), "projected_window_gram_ms": round(wgram_ms, 3),
             "window_over_pair": round(win_ms / pair_ms, 4), "median_offdiag_pqk_window": float(np.median(KW[off])),
+        })
+    if args.amplitudes > 0:
+        S_amp = args.amplitudes
+        amp_bases = engine.random_bases(S_amp, n, 0)
+        (amp_bits, lp_sample), amp_sample_ms = timed(lambda: ctx.sample(xs, S_amp, bases=amp_bases, seed=0, logp=True), args.reps)
+        ctx.amplitudes(xs, amp_bits, bases=amp_bases, per_state=True, logp=True)  # warm-up
+        ts = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            _, lp_amp = ctx.amplitudes(xs, amp_bits, bases=amp_bases, per_state=True, logp=True)
+            ts.append(1e3 * (time.perf_counter() - t0))
+        amp_ms = float(np.median(ts))
+        aflops = amplitude_flops(info["dims"], S_amp)
+        dist.update({
+            "amp_strings": S_amp, "amp_reps": args.reps, "amplitudes_ms": round(amp_ms, 3), "amplitudes_ms_min": round(min(ts), 3),
+            "amplitudes_ms_max": round(max(ts), 3), "amp_flops": aflops, "amp_tflops": round(aflops / (amp_ms * 1e-3) / 1e12, 3),
+            "amp_sample_ms": round(amp_sample_ms, 3), "amp_over_sample": round(amp_ms / amp_sample_ms, 4),
+            "max_abs_dlogp_amp_sample": float(np.abs(lp_amp - lp_sample).max()),
         })
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
