@@ -618,6 +618,40 @@ int qk_shadow_hist_host(qk_ctx* ctx, int32_t n_sites,
                         int64_t n_pairs, const int32_t* pairs /* [n_pairs][2] = (x index, y index), any order, duplicates allowed */,
                         int64_t* hist /* [n_pairs][2 n_sites + 1] */, int64_t* equal /* same shape, may be NULL */);
 
+/* ---- Pauli strings estimated from measurement shots ---------------------------------------------------------------------------------
+ * qk_shot_strings_host: for every state of an outcome table and every Pauli string, how many shots were measured in the string's
+ * bases on its support, and the sum of their signs -- the finite-shot counterpart of qk_pauli_strings_host, and through the 4^w
+ * strings of a window of w qubits that of qk_window_rdms_host.  Like qk_shadow_hist_host it needs no MPS set and shares its
+ * conventions: qubit k = site k, bit 0 = eigenvalue +1, basis codes 1, 2, 3 = X, Y, Z, n_sites <= 128; bases_per_state = 0: one
+ * table [shots][n_sites] shared by every state, 1: a table per state.  A string is n_sites codes 0 .. 3 = I, X, Y, Z; its support
+ * is the qubits with a code other than 0.  For state s and string m:
+ *     match(t)      = bases[(s,) t][k] == strings[m][k] for every k of the support
+ *     counts[s][m]  = #{t : match(t)}
+ *     sums[s][m]    = sum over the matching t of prod_{k in support} (1 - 2 bits[s][t][k])              both int64, exact
+ *     value[s][m]   = sums / counts, 0.0 where counts == 0       (on the host: engine.string_values; the convention of estimate_paulis)
+ * The all-identity string has counts = sums = shots.
+ * Packed form: a shot is the record of qk_shadow_hist_host (planes p0, p1, p2 per group of 32 qubits); a string is two planes per
+ * group, s1 = code & 1 and s2 = code >> 1, I and pad bits 0 in both, packed on the host.  With supp = s1 | s2 a shot matches when
+ * supp & ((s1 ^ p1) | (s2 ^ p2)) == 0 in every group, and its sign is 1 - 2 (popcount(p0 & supp) summed over the groups & 1).
+ * The pack kernel of qk_shadow_hist_host makes the shot records; the estimator kernel takes one workgroup per (state, block of 64
+ * strings, range of shots): a string per lane with its record in registers, the shot records staged in LDS 256 at a time and read
+ * as a broadcast, about 7 vector instructions per (shot, string, group) and as many again per (shot, string); a task writes int32 partial sums and counts to a row of
+ * its own (a task's shots are capped so that neither can overflow), and a second kernel adds the rows of a (state, block of
+ * strings) into int64.  The result is exact and does not depend on any order, batch cut, launch cut or run; a (state, string)
+ * result does not depend on the other states or strings; no global atomic, no workgroup waits for another.
+ * Device scratch: the shot records (12 bytes per 32 qubits per shot), and per string batch the string records, the task rows and
+ * the int64 totals in the context's local scratch (qk_ctx_trim releases it), by the batching rule of qk_local_paulis_host (a
+ * quarter of the free memory; strings go in batches when the rows do not fit; QK_SHOT_STRINGS_BATCH=k, read per call, caps the
+ * strings of a batch).  A launch takes at most 2048 tasks.  Synchronous; leaves the Gram statistics alone.
+ * QK_EINVAL (the message names the argument): a null ctx, bits, bases, strings, sums or counts; n_sites, n_states, shots or
+ * n_strings below 1; n_sites > 128; bases_per_state not 0 or 1; a bit other than 0 or 1 (names bits); a basis code outside 1 .. 3
+ * (names bases); a string code above 3 (names strings and the string's index).                                                    */
+int qk_shot_strings_host(qk_ctx* ctx, int32_t n_sites, int32_t n_states, int32_t shots,
+                         const uint8_t* bits /* [n_states][shots][n_sites] */,
+                         const uint8_t* bases /* [shots][n_sites], or [n_states][shots][n_sites] */, int32_t bases_per_state,
+                         int32_t n_strings, const uint8_t* strings /* [n_strings][n_sites], codes 0..3 */,
+                         int64_t* sums /* [n_states][n_strings] */, int64_t* counts /* same shape */);
+
 /* ---- compressing a set: one canonical truncation sweep per state -------------------------------------------------------------
  * qk_mps_set_compress: *out = a new fp64 set of the same context that owns its memory, every state of src truncated ONCE on its
  * final tensors; src is left untouched.  One workgroup per state (workgroup b takes states b, b + grid, ...), two passes over the

@@ -10,7 +10,8 @@
 // (definitions above SmpArgs below), the amplitudes and outcome likelihoods of given strings, qk_amplitudes_host (above AmpArgs
 // below), the reduced density matrices of every window of k qubits, qk_window_rdms_host (above WinArgs
 // below), the block overlaps estimated from such shots, qk_shot_block_sums_host (above SbkArgs below), and the
-// shot-pair histograms of the classical-shadow kernel, qk_shadow_hist_host (above ShkArgs below) (include/qkgram.h).
+// shot-pair histograms of the classical-shadow kernel, qk_shadow_hist_host (above ShkArgs below), and Pauli strings estimated from
+// shots, qk_shot_strings_host (above SstArgs below) (include/qkgram.h).
 //
 // Definitions (the contract, also in README.md).  For a state psi (site k = qubit k, physical index 0 = |0>, not necessarily
 // normalised):
@@ -2669,7 +2670,169 @@ int shadow_hist(qk_ctx* c, const int32_t n, const int32_t nx, const int32_t shot
   return QK_OK;
 }
 
+// ---- Pauli strings estimated from shots (qk_shot_strings_host) -----------------------------------------------------------------------
+// For every (state, Pauli string): the number of shots whose bases equal the string on its support, and the sum of their signs.  All
+// integer arithmetic on the shadow kernel's shot records; definitions in include/qkgram.h, host side in qk_local_plan.h (sst_*).
+//   qk_sst_kernel        one workgroup of four waves per task = (state, block of 64 strings, range of shots).
+//       Layout: one string per lane, its record (two planes per group) and its support in registers for the whole task; the shot
+//       records staged in LDS, 256 at a time, rows of 16-byte multiples, and read as a broadcast (ds_read_b128 of one address in
+//       every lane: conflict-free) -- the shadow kernel's pattern.  It was taken over the other layout (a shot per lane, the strings
+//       wave-uniform, the match mask of a wave counted twice on the scalar unit) because a lane's count and sum then stay in two of
+//       its own registers for the whole task: no cross-lane step per (string, wave of shots), no scalar instruction per 64 tests --
+//       at one group that layout spends about as many scalar instructions as vector ones, and the scalar unit is shared by the
+//       waves of a CU -- and a ragged number of shots costs nothing (a ragged number of strings idles lanes of one wave instead).
+//       Per (shot, string, group): two XORs, an OR, an AND and an OR into the mismatch word, an AND and an XOR into the parity word
+//       (sst_test); per (shot, string) one compare, one v_bcnt and the two conditional adds.  The waves of the workgroup take the
+//       staged shots in turn; at the end the four partial (sum, count) of a lane are added through LDS and written to the task's row.
+//   qk_sst_total_kernel  one thread per (state, string): the sum of the rows of its tasks, int64.
+// Sums and counts are exact and order-free; no global atomic, no workgroup waits for another.
+struct SstArgs {
+  const uint32_t* recs;  // shot records [n_states][shots][3 groups]
+  const uint32_t* strs;  // string records of the batch [blocks * 64][2 groups], zero (identity) beyond the batch's strings
+  int32_t* rows;         // per-task rows of the batch [tasks][SST_ROW]
+  int shots, blocks, task_chunks;
+  long long task0;       // first task of the launch
+};
+
+template <int G>
+__global__ __launch_bounds__(256) void qk_sst_kernel(const SstArgs g) {
+  constexpr int W = 3 * G, LD = shk_stride(G);
+  __shared__ __attribute__((aligned(16))) uint32_t ys[SST_STAGE_SHOTS * LD];  // staged shot records, LD words each
+  __shared__ int32_t part[4][SST_ROW];                                        // the waves' partial sums and counts
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: the loop over the staged shots runs on the scalar unit
+  long long state;
+  int block, t0, t1;
+  sst_task(g.task0 + blockIdx.x, g.blocks, g.shots, g.task_chunks, state, block, t0, t1);
+  const uint32_t* const X = g.recs + state * g.shots * W;
+  uint32_t s[2 * G];
+#pragma unroll
+  for (int k = 0; k < 2 * G; ++k) s[k] = g.strs[((long long)block * SST_BLOCK + lane) * (2 * G) + k];
+  int sum = 0, cnt = 0;
+  for (int y0 = t0; y0 < t1; y0 += SST_STAGE_SHOTS) {
+    const int bn = min(SST_STAGE_SHOTS, t1 - y0);
+    __syncthreads();  // the last pass's records are no longer read
+    for (int e = threadIdx.x; e < bn * W; e += 256) ys[(e / W) * LD + e % W] = X[(long long)y0 * W + e];
+    __syncthreads();
+#pragma unroll 4
+    for (int b = wv; b < bn; b += 4) {
+      uint32_t y[LD];
+#pragma unroll
+      for (int k = 0; k < LD; k += 4) {
+        const uint4 v = *reinterpret_cast<const uint4*>(ys + b * LD + k);
+        y[k] = v.x, y[k + 1] = v.y, y[k + 2] = v.z, y[k + 3] = v.w;
+      }
+      bool match;
+      int sign;
+      sst_test(y, s, G, match, sign);
+      cnt += match ? 1 : 0, sum += match ? sign : 0;
+    }
+  }
+  part[wv][lane] = sum, part[wv][SST_BLOCK + lane] = cnt;
+  __syncthreads();
+  if (threadIdx.x < SST_ROW)
+    g.rows[(g.task0 + blockIdx.x) * SST_ROW + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
+// rows [(state, block, range)][SST_ROW] of a batch of mb strings -> sums, counts [n_states][mb]
+__global__ __launch_bounds__(256) void qk_sst_total_kernel(const int32_t* rows, const long long count, const int mb, const int blocks, const int ranges, long long* sums,
+                                                           long long* counts) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= count) return;
+  const long long state = e / mb;
+  const int j = (int)(e % mb);
+  const int32_t* const r = rows + ((state * blocks + j / SST_BLOCK) * ranges) * SST_ROW + j % SST_BLOCK;
+  long long a = 0, b = 0;
+  for (int k = 0; k < ranges; ++k) a += r[(long long)k * SST_ROW], b += r[(long long)k * SST_ROW + SST_BLOCK];
+  sums[e] = a, counts[e] = b;
+}
+
+int shot_strings(qk_ctx* c, const int32_t n, const int32_t ns, const int32_t shots, const uint8_t* bits, const uint8_t* bases, const int32_t per_state, const int32_t m,
+                 const uint8_t* strings, int64_t* sums, int64_t* counts) {
+  static const char* what = "qk_shot_strings_host";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!bits) return qk_fail(QK_EINVAL, "%s: bits is null", what);
+  if (!bases) return qk_fail(QK_EINVAL, "%s: bases is null", what);
+  if (!strings) return qk_fail(QK_EINVAL, "%s: strings is null", what);
+  if (!sums) return qk_fail(QK_EINVAL, "%s: sums is null", what);
+  if (!counts) return qk_fail(QK_EINVAL, "%s: counts is null", what);
+  if (n < 1) return qk_fail(QK_EINVAL, "%s: n_sites must be >= 1 (got %d)", what, n);
+  if (n > SHK_MAX_QUBITS) return qk_fail(QK_EINVAL, "%s: n_sites must be <= %d (got %d)", what, SHK_MAX_QUBITS, n);
+  if (ns < 1) return qk_fail(QK_EINVAL, "%s: n_states must be >= 1 (got %d)", what, ns);
+  if (shots < 1) return qk_fail(QK_EINVAL, "%s: shots must be >= 1 (got %d)", what, shots);
+  if (m < 1) return qk_fail(QK_EINVAL, "%s: n_strings must be >= 1 (got %d)", what, m);
+  if (per_state != 0 && per_state != 1) return qk_fail(QK_EINVAL, "%s: bases_per_state must be 0 or 1 (got %d)", what, per_state);
+  long long cap = 0;  // strings per batch; 0: the memory rule alone
+  if (const char* v = std::getenv("QK_SHOT_STRINGS_BATCH")) {
+    cap = std::atoll(v);
+    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_SHOT_STRINGS_BATCH must be >= 1 (got \"%s\")", what, v);
+  }
+  const int groups = shk_groups(n), words = shk_words(n), sw = sst_words(n);
+  // the string records, whole blocks of them: what lies beyond the last string is the identity
+  std::vector<uint32_t> srec((size_t)sst_blocks(m) * SST_BLOCK * sw, 0u);
+  for (int j = 0; j < m; ++j) {
+    bool bad = false;
+    sst_pack_string(strings + (size_t)j * n, n, srec.data() + (size_t)j * sw, bad);
+    if (bad) return qk_fail(QK_EINVAL, "%s: strings[%d] holds a code above 3 (0 .. 3 = I, X, Y, Z)", what, j);
+  }
+  QkRangeGuard range_("qk:shot_strings");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  QkDevBuf recs, dbad;
+  HIP_TRY_AS(what, recs.alloc((size_t)ns * shots * words * sizeof(uint32_t)));
+  HIP_TRY_AS(what, dbad.alloc(2 * sizeof(int32_t)));
+  HIP_TRY_AS(what, hipMemset(dbad.get(), 0, 2 * sizeof(int32_t)));
+  // memory bound of the staged outcome bytes and of a string batch: a quarter of what is free once the records exist
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  const long long room = budget * (long long)sizeof(double);
+  if (const int rc = shk_pack_table(c, what, "bits", "bases", bits, bases, per_state, ns, shots, n, room, recs.get<uint32_t>(), dbad.get<int32_t>())) return rc;
+
+  const int task_chunks = sst_task_chunks(shots, (long long)ns * sst_blocks(m)), ranges = sst_ranges(shots, task_chunks);
+  const long long batch = std::min((long long)m, sst_batch_strings(room, n, ns, ranges, cap));
+  SstArgs q{};
+  q.recs = recs.get<uint32_t>(), q.shots = shots, q.task_chunks = task_chunks;
+  for (long long m0 = 0; m0 < m; m0 += batch) {
+    const int mb = (int)std::min(batch, m - m0), blocks = sst_blocks(mb);
+    const long long tasks = (long long)ns * blocks * ranges, cells = (long long)ns * mb;
+    // one device buffer for the string batch: [string records | per-task rows | sums | counts]
+    const size_t b_strs = al256((size_t)blocks * SST_BLOCK * sw * sizeof(uint32_t)), b_rows = al256((size_t)tasks * SST_ROW * sizeof(int32_t)),
+                 b_out = al256((size_t)cells * sizeof(int64_t));
+    HIP_TRY_AS(what, c->local_scratch.ensure(b_strs + b_rows + 2 * b_out));
+    char* const base = c->local_scratch.get<char>();
+    q.strs = reinterpret_cast<const uint32_t*>(base);
+    q.rows = reinterpret_cast<int32_t*>(base + b_strs);
+    q.blocks = blocks;
+    long long* const d_sums = reinterpret_cast<long long*>(base + b_strs + b_rows);
+    long long* const d_counts = reinterpret_cast<long long*>(base + b_strs + b_rows + b_out);
+    // the batch's records and, where its last block is ragged, the identity behind them (srec is zero beyond string m)
+    HIP_TRY_AS(what, hipMemsetAsync(base, 0, b_strs, c->stream));
+    HIP_TRY_AS(what, hipMemcpyAsync(base, srec.data() + (size_t)m0 * sw, (size_t)mb * sw * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    for (long long t0 = 0; t0 < tasks; t0 += SST_LAUNCH_TASKS) {
+      q.task0 = t0;
+      const dim3 grid((unsigned)std::min((long long)SST_LAUNCH_TASKS, tasks - t0));
+      if (groups == 1) qk_sst_kernel<1><<<grid, dim3(256), 0, c->stream>>>(q);
+      else if (groups == 2) qk_sst_kernel<2><<<grid, dim3(256), 0, c->stream>>>(q);
+      else if (groups == 3) qk_sst_kernel<3><<<grid, dim3(256), 0, c->stream>>>(q);
+      else qk_sst_kernel<4><<<grid, dim3(256), 0, c->stream>>>(q);
+    }
+    HIP_TRY_AS(what, hipGetLastError());
+    qk_sst_total_kernel<<<dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream>>>(q.rows, cells, mb, blocks, ranges, d_sums, d_counts);
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+    // the batch is the columns m0 .. m0 + mb of the caller's tables
+    HIP_TRY_AS(what, hipMemcpy2D(sums + m0, (size_t)m * sizeof(int64_t), d_sums, (size_t)mb * sizeof(int64_t), (size_t)mb * sizeof(int64_t), (size_t)ns, hipMemcpyDeviceToHost));
+    HIP_TRY_AS(what, hipMemcpy2D(counts + m0, (size_t)m * sizeof(int64_t), d_counts, (size_t)mb * sizeof(int64_t), (size_t)mb * sizeof(int64_t), (size_t)ns, hipMemcpyDeviceToHost));
+  }
+  return QK_OK;
+}
+
 }  // namespace
+
+extern "C" int qk_shot_strings_host(qk_ctx* c, int32_t n_sites, int32_t n_states, int32_t shots, const uint8_t* bits, const uint8_t* bases, int32_t bases_per_state,
+                                    int32_t n_strings, const uint8_t* strings, int64_t* sums, int64_t* counts) {
+  return shot_strings(c, n_sites, n_states, shots, bits, bases, bases_per_state, n_strings, strings, sums, counts);
+}
 
 extern "C" int qk_shadow_hist_host(qk_ctx* c, int32_t n_sites, int32_t nx, int32_t shots_x, const uint8_t* bits_x, const uint8_t* bases_x, int32_t bases_x_per_state, int32_t ny,
                                    int32_t shots_y, const uint8_t* bits_y, const uint8_t* bases_y, int32_t bases_y_per_state, int64_t n_pairs, const int32_t* pairs, int64_t* hist,

@@ -1,6 +1,6 @@
 // qk_local_plan.h -- the host-side plan of the local sweeps (qk_local.hip): the launch kinds, the scratch layout, the pair index, the
 // sizes and the cut into state batches, the tables and task lists of a batch, the plans of the entry points, the chain side of the
-// Pauli strings, of the block kernels, of the sampler, of the amplitude chains and of the k-qubit windows, the integer side of the shot-based block overlaps and of the shadow kernel's shot-pair histograms.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
+// Pauli strings, of the block kernels, of the sampler, of the amplitude chains and of the k-qubit windows, the integer side of the shot-based block overlaps , of the shadow kernel's shot-pair histograms and of the Pauli strings estimated from shots.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
 // -fsanitize=address,undefined); the few functions the kernels also call are QK_HD.
 #pragma once
 #include "qk_plan.h"
@@ -828,6 +828,76 @@ QK_HD constexpr int shk_part_lo(const int p, const int parts, const int bn) {
 // `room` bytes, at least one.
 inline long long shk_batch_pairs(const long long room, const int n, const int pair_tasks) {
   return std::max(1ll, room / (8 + (long long)(pair_tasks + 2) * shk_bins(n) * 8));
+}
+
+// ---- Pauli strings estimated from shots (qk_shot_strings_host) -----------------------------------------------------------------------
+// The shots are the records of the shadow kernel (shk_pack).  A Pauli string is a record of two planes per group of 32 qubits:
+// rec[2 g] = s1 (code & 1), rec[2 g + 1] = s2 (code >> 1), codes 0 .. 3 = I, X, Y, Z; I and the pad bits are 0 in both, so
+// supp = s1 | s2 is the support.  A shot matches a string when its basis equals the string's code on every qubit of the support; its
+// sign is the parity of its outcome bits there (definitions in include/qkgram.h).  A task is one state, one block of 64 strings (a
+// string per lane of a wave) and a range of chunks of SST_STAGE_SHOTS shots (a chunk is what a workgroup stages in LDS at a time).
+constexpr int SST_BLOCK = 64;            // strings of a block: one per lane of a wave
+constexpr int SST_STAGE_SHOTS = 256;     // shot records a workgroup stages in LDS at a time: a chunk
+constexpr int SST_LAUNCH_TASKS = 2048;   // tasks of one launch, as SHK_LAUNCH_TASKS: no launch runs long on a shared device
+constexpr int SST_ROW = 2 * SST_BLOCK;   // int32 of a task's row: the 64 partial sums, then the 64 partial counts
+constexpr long long SST_PARTIAL_MAX = 0x7fffffffll;  // a partial sum or count is an int32
+QK_HD constexpr int sst_words(const int n) { return 2 * shk_groups(n); }  // of a string record
+// The record of a string; bad is set where a code is above 3 (it contributes its low bits; the caller rejects the table).
+QK_HD inline void sst_pack_string(const uint8_t* codes, const int n, uint32_t* rec, bool& bad) {
+  const int groups = shk_groups(n);
+  for (int g = 0; g < groups; ++g) {
+    uint32_t s1 = 0, s2 = 0;
+    const int k1 = n - 32 * g < 32 ? n - 32 * g : 32;
+    for (int k = 0; k < k1; ++k) {
+      const uint32_t c = codes[32 * g + k];
+      if (c > 3) bad = true;
+      s1 |= (c & 1u) << k, s2 |= ((c >> 1) & 1u) << k;
+    }
+    rec[2 * g] = s1, rec[2 * g + 1] = s2;
+  }
+}
+// One (shot record, string record): the one place match and sign are defined.  miss collects the qubits of the support whose basis
+// differs, odd the outcome bits on the support; the parity of a sum of popcounts is the parity of the XOR of the words.
+//     match = (supp & ((s1 ^ p1) | (s2 ^ p2))) == 0 in every group,     sign = 1 - 2 (popcount(p0 & supp) summed over the groups & 1)
+QK_HD inline void sst_test(const uint32_t* shot, const uint32_t* str, const int groups, bool& match, int& sign) {
+  uint32_t miss = 0, odd = 0;
+  for (int g = 0; g < groups; ++g) {
+    const uint32_t supp = str[2 * g] | str[2 * g + 1];
+    miss |= supp & ((str[2 * g] ^ shot[3 * g + 1]) | (str[2 * g + 1] ^ shot[3 * g + 2]));
+    odd ^= shot[3 * g] & supp;
+  }
+  match = miss == 0;
+  sign = 1 - 2 * (shk_popc(odd) & 1);
+}
+QK_HD constexpr int sst_blocks(const int n_strings) { return (n_strings - 1) / SST_BLOCK + 1; }    // n_strings >= 1
+QK_HD constexpr int sst_chunks(const int shots) { return (shots - 1) / SST_STAGE_SHOTS + 1; }      // shots >= 1
+// The overflow bound: a partial count is at most the shots of its task and a partial sum at most that in magnitude, so a task takes
+// at most this many chunks.
+QK_HD constexpr long long sst_max_chunks() { return SST_PARTIAL_MAX / SST_STAGE_SHOTS; }
+// Chunks per task: all the shots when the call has (state, string block) units enough to fill launches, fewer when it has not, never
+// more than the overflow bound allows, at least one.
+inline int sst_task_chunks(const int shots, const long long units) {
+  const long long nc = sst_chunks(shots);
+  const long long fill = units >= SST_LAUNCH_TASKS ? nc : std::max(1ll, nc * units / SST_LAUNCH_TASKS);  // (no product that could pass 2^63)
+  return (int)std::max(1ll, std::min({nc, fill, sst_max_chunks()}));
+}
+QK_HD constexpr int sst_ranges(const int shots, const int task_chunks) { return (sst_chunks(shots) + task_chunks - 1) / task_chunks; }
+// task t of a batch of `blocks` string blocks: state t / (blocks ranges), then the block, then the range, its shots [t0, t1)
+QK_HD inline void sst_task(const long long t, const int blocks, const int shots, const int task_chunks, long long& state, int& block, int& t0, int& t1) {
+  const int ranges = sst_ranges(shots, task_chunks);
+  const long long per = (long long)task_chunks * SST_STAGE_SHOTS, lo = (t % ranges) * per;
+  state = t / ((long long)blocks * ranges);
+  block = (int)((t / ranges) % blocks);
+  t0 = (int)lo;
+  t1 = (int)(lo + per < shots ? lo + per : shots);
+}
+// Strings per batch: per string its record, per state the task rows of its block (8 bytes of each row are the string's) and the two
+// int64 totals, within `room` bytes; whole blocks when there is room for one, at least one string, at most `cap` when cap > 0.
+inline long long sst_batch_strings(const long long room, const int n, const long long n_states, const int ranges, const long long cap) {
+  long long fit = room / (4ll * sst_words(n) + n_states * (8ll * ranges + 16));
+  if (fit >= SST_BLOCK) fit -= fit % SST_BLOCK;
+  fit = std::max(1ll, fit);
+  return cap > 0 ? std::min(fit, cap) : fit;
 }
 
 }  // namespace qkl

@@ -112,6 +112,7 @@ _SIGNATURES = [
     ("qk_amplitudes_host", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("qk_shot_block_sums_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_shadow_hist_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
+    ("qk_shot_strings_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
@@ -851,6 +852,147 @@ def paulis_rdm(c, width=None) -> np.ndarray:
     order = list(range(nl)) + [nl + 2 * j for j in range(w)] + [nl + 2 * j + 1 for j in range(w)]  # rows, then columns
     D = 1 << w
     return np.ascontiguousarray(t.transpose(order).reshape(t.shape[:nl] + (D, D))) / D
+
+
+def _string_table(n_sites: int, strings, checked: bool = True) -> np.ndarray:
+    """``strings`` as the uint8 code table (m, n_sites): an integer array of that shape is taken as it is (``checked=False`` leaves
+    codes of 4 .. 255 to the library), anything else goes through ``pauli_strings``."""
+    if isinstance(strings, np.ndarray) and strings.ndim == 2:
+        if strings.dtype.kind not in "iu" or strings.shape[0] < 1 or strings.shape[1] != n_sites:
+            raise ValueError(f"strings must be an integer code table of shape (m >= 1, {n_sites}), got shape {strings.shape}, dtype {strings.dtype}")
+        hi = 3 if checked else 255
+        bad = np.flatnonzero(((strings < 0) | (strings > hi)).any(axis=1))
+        if bad.size:
+            raise ValueError(f"strings[{int(bad[0])}] holds a code outside 0..3 = I, X, Y, Z")
+        return np.ascontiguousarray(strings, dtype=np.uint8)
+    return pauli_strings(n_sites, strings)
+
+
+def _string_tables(bits, bases):
+    """(bits (ns, T, n), bases as given, per_state) of a shot-string call"""
+    b = _shot_bits(bits, "bits")
+    c = np.asarray(bases)
+    if b.shape[0] < 1 or b.shape[1] < 1:
+        raise ValueError(f"bits must hold at least one state and one shot, got shape {b.shape}")
+    if c.dtype.kind not in "iu" or c.shape not in (b.shape[1:], b.shape):
+        raise ValueError(f"bases must be an integer array of shape {b.shape[1:]} (shared) or {b.shape} (per state), got shape {c.shape}, dtype {c.dtype}")
+    return b, c, int(c.ndim == 3)
+
+
+def pack_string_words(strings) -> np.ndarray:
+    """The packed record of every Pauli string of a code table (m, n_qubits), codes 0..3 = I, X, Y, Z: uint32 of shape
+    (m, groups, 2) with groups = ceil(n / 32).  Bit k % 32 of group k // 32 holds ``code & 1`` (plane 0) and ``code >> 1`` (plane 1) of
+    qubit k; I and the pad bits are 0 in both, so the OR of the planes is the string's support."""
+    s = np.asarray(strings)
+    if s.ndim != 2 or s.dtype.kind not in "iu" or s.shape[1] < 1 or s.shape[1] > SHADOW_MAX_QUBITS:
+        raise ValueError(f"strings must be an integer code table (m, n_qubits <= {SHADOW_MAX_QUBITS}), got shape {s.shape}, dtype {s.dtype}")
+    s = s.astype(np.int64)
+    if s.size and (s.min() < 0 or s.max() > 3):
+        raise ValueError("strings holds a code outside 0..3 = I, X, Y, Z")
+    m, n = s.shape
+    groups = (n + 31) // 32
+    planes = np.zeros((m, groups * 32, 2), dtype=np.int64)
+    planes[:, :n, 0], planes[:, :n, 1] = s & 1, s >> 1
+    planes = planes.reshape(m, groups, 32, 2)
+    return (planes << np.arange(32, dtype=np.int64)[:, None]).sum(axis=-2).astype(np.uint32)
+
+
+def shot_string_sums(bits, bases, strings):
+    """Pauli strings against measurement shots in plain numpy -- the mirror of ``Context.shot_string_sums_host``, the same integers
+    from the packed records (``pack_shadow_words``, ``pack_string_words``) and ``_popcount32``: ``(sums, counts)``, both int64 of
+    shape (n_states, m).  ``bits`` (n_states, shots, n) was measured in ``bases``, (shots, n) shared by every state or
+    (n_states, shots, n) per state, codes 1, 2, 3 = X, Y, Z; ``strings`` is anything ``pauli_strings(n, ...)`` takes, or a code
+    table (m, n).  A shot matches a string when its bases equal the string's codes on every qubit of the string's support;
+        counts[s, m] = #{matching shots},   sums[s, m] = sum over them of prod_{k in support} (1 - 2 bits[s, t, k]).
+    The all-identity string has counts = sums = shots.  Works in chunks: the temporaries stay at a few MiB."""
+    b, c, per_state = _string_tables(bits, bases)
+    ns, T, n = b.shape
+    S = pack_string_words(_string_table(n, strings))  # (m, G, 2)
+    m, G = S.shape[:2]
+    supp = S[..., 0] | S[..., 1]
+    sums, counts = np.zeros((ns, m), dtype=np.int64), np.zeros((ns, m), dtype=np.int64)
+    t_rows = max(1, (1 << 14) // G)  # shots packed at a time
+    for s in range(ns):
+        for t0 in range(0, T, t_rows):
+            r = pack_shadow_words(b[s, t0 : t0 + t_rows], c[s, t0 : t0 + t_rows] if per_state else c[t0 : t0 + t_rows])  # (t, G, 3)
+            m_rows = max(1, (1 << 18) // (r.shape[0] * G))  # strings at a time
+            for m0 in range(0, m, m_rows):
+                s1, s2, sp = S[None, m0 : m0 + m_rows, :, 0], S[None, m0 : m0 + m_rows, :, 1], supp[None, m0 : m0 + m_rows]
+                match = ~(sp & ((s1 ^ r[:, None, :, 1]) | (s2 ^ r[:, None, :, 2]))).any(axis=-1)
+                odd = np.bitwise_xor.reduce(r[:, None, :, 0] & sp, axis=-1)
+                sign = 1 - 2 * (_popcount32(odd) & 1)
+                counts[s, m0 : m0 + m_rows] += match.sum(axis=0)
+                sums[s, m0 : m0 + m_rows] += np.where(match, sign, 0).sum(axis=0)
+    return sums, counts
+
+
+def string_values(sums, counts) -> np.ndarray:
+    """The estimates of ``shot_string_sums``: ``sums / counts`` as float64, and 0.0 where ``counts == 0`` (the convention of
+    ``estimate_paulis``)."""
+    s, c = np.asarray(sums), np.asarray(counts)
+    if s.shape != c.shape or s.dtype.kind not in "iu" or c.dtype.kind not in "iu":
+        raise ValueError(f"sums and counts must be integer arrays of one shape, got {s.shape} ({s.dtype}) and {c.shape} ({c.dtype})")
+    return np.where(c > 0, s / np.maximum(c, 1), 0.0)
+
+
+def _window_width(width, n: int) -> int:
+    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or not 1 <= width <= min(int(n), WINDOW_MAX_WIDTH):
+        raise ValueError(f"width must be an int in 1 .. min(n_qubits, {WINDOW_MAX_WIDTH}) = {min(int(n), WINDOW_MAX_WIDTH)}, got {width!r}")
+    return int(width)
+
+
+def window_strings(n_qubits: int, width: int, starts=None) -> np.ndarray:
+    """The 4^width Pauli strings of every window of ``width`` contiguous qubits, as the code table uint8 (n_windows 4^width,
+    n_qubits): windows in the order of ``Context.window_rdms`` (``starts=None``: every window 0 .. n - width; otherwise strictly
+    increasing ints in that range), and inside a window the strings in the index order of ``rdm_paulis``, the window's first qubit
+    first -- string p_0 4^(w-1) + .. + p_{w-1} has P_{p_j} on qubit start + j.  Values of these strings reshaped to
+    ``(n_states, n_windows) + (4,) * width`` are what ``paulis_rdm(..., width=width)`` takes (give ``width``: with four windows the
+    window axis would pass for a qubit)."""
+    n = int(n_qubits)
+    if n < 1:
+        raise ValueError(f"n_qubits must be >= 1 (got {n_qubits!r})")
+    w = _window_width(width, n)
+    if starts is None:
+        st = np.arange(n - w + 1)
+    else:
+        st = np.asarray(starts)
+        if st.ndim != 1 or st.size < 1 or not np.issubdtype(st.dtype, np.integer) or st.dtype == np.bool_:
+            raise ValueError(f"starts must be a non-empty list of ints, got {starts!r}")
+        if st.min() < 0 or st.max() > n - w or (np.diff(st) <= 0).any():
+            raise ValueError(f"starts must be strictly increasing in 0 .. n_qubits - width = {n - w}, got {starts!r}")
+    codes = (np.arange(4 ** w)[:, None] >> (2 * (w - 1 - np.arange(w)))[None, :]) & 3  # (4^w, w): p_0 is the leading digit
+    out = np.zeros((len(st), 4 ** w, n), dtype=np.uint8)
+    for i, a in enumerate(st):
+        out[i, :, int(a) : int(a) + w] = codes
+    return out.reshape(len(st) * 4 ** w, n)
+
+
+def estimate_window_rdms(bits, bases, width: int, starts=None, sums=shot_string_sums):
+    """``Context.estimate_window_rdms`` with the integers from ``sums`` (the numpy mirror ``shot_string_sums`` unless the context
+    passes its device call): ``(rho_hat, counts)``, documented there."""
+    b = _shot_bits(bits, "bits")
+    n = b.shape[2]
+    w = _window_width(width, n)
+    S = window_strings(n, w, starts)
+    tot, counts = sums(b, bases, S)
+    shape = (b.shape[0], S.shape[0] >> (2 * w)) + (4,) * w
+    return paulis_rdm(string_values(tot, counts).reshape(shape), width=w), counts.reshape(shape)
+
+
+def window_settings(shots: int, n_qubits: int, width: int) -> np.ndarray:
+    """Designed measurement bases for the windows of ``width`` qubits: uint8 (shots, n_qubits), codes 1..3 = X, Y, Z.  Shot t uses
+    setting ``t % 3^width``, and qubit k gets ``1 +`` digit number ``k % width`` of the setting in base 3.  The ``width`` qubits of
+    any window have distinct residues, so they run through all 3^width basis choices together: every string of weight v >= 1 on any
+    window of that width matches exactly ``shots / 3^v`` shots when 3^width divides ``shots``."""
+    if isinstance(shots, bool) or not isinstance(shots, (int, np.integer)) or shots < 1:
+        raise ValueError(f"shots must be an int >= 1 (got {shots!r})")
+    n = int(n_qubits)
+    if n < 1:
+        raise ValueError(f"n_qubits must be >= 1 (got {n_qubits!r})")
+    w = _window_width(width, n)
+    setting = np.arange(int(shots)) % 3 ** w
+    digit = np.arange(n) % w
+    return (1 + (setting[:, None] // 3 ** digit[None, :]) % 3).astype(np.uint8)
 
 
 def _dims_table(states) -> np.ndarray:
@@ -1788,6 +1930,37 @@ class Context:
         jj, ii = np.divmod(np.arange(ny * nx), nx)
         out = self.shadow_hist_host(bits_x, bases_x, bits_y, bases_y, np.stack([ii, jj], axis=1), equal)
         return tuple(o.reshape(ny, nx, 2 * n + 1) for o in out) if equal else out.reshape(ny, nx, 2 * n + 1)
+
+    def shot_string_sums_host(self, bits, bases, strings):
+        """``engine.shot_string_sums`` on the device (``qk_shot_strings_host``): the same int64 ``(sums, counts)``, bit for bit, both
+        (n_states, m).  ``bits`` (n_states, shots, n) with ``bases`` (shots, n) shared or (n_states, shots, n) per state; ``strings``
+        anything ``pauli_strings(n, ...)`` takes, or a code table (m, n); n <= 128.  It needs no MPS set.  Synchronous."""
+        b, c, per_state = _string_tables(bits, bases)
+        b, c = np.ascontiguousarray(b, dtype=np.uint8), np.ascontiguousarray(c, dtype=np.uint8)
+        ns, T, n = b.shape
+        S = _string_table(n, strings, checked=False)  # (the library rejects a code above 3 by the string's index)
+        sums, counts = np.zeros((ns, S.shape[0]), dtype=np.int64), np.zeros((ns, S.shape[0]), dtype=np.int64)
+        _check(lib().qk_shot_strings_host(self._h, n, ns, T, b.ctypes.data, c.ctypes.data, per_state, S.shape[0], S.ctypes.data, sums.ctypes.data, counts.ctypes.data),
+               "qk_shot_strings_host")
+        return sums, counts
+
+    def estimate_pauli_strings(self, bits, bases, strings):
+        """Expectation values of Pauli strings estimated from measurement shots, the finite-shot counterpart of
+        ``pauli_expectations``: ``(values, counts)``, float64 and int64 of shape (n_states, m).  ``values[s, j]`` is the mean sign of
+        the shots of state s whose bases equal string j on its support (``string_values`` of ``shot_string_sums_host``: 0.0 where no
+        shot matches), ``counts[s, j]`` the number of those shots.  Arguments as ``shot_string_sums_host``.  Synchronous."""
+        sums, counts = self.shot_string_sums_host(bits, bases, strings)
+        return string_values(sums, counts), counts
+
+    def estimate_window_rdms(self, bits, bases, width: int, starts=None):
+        """Reduced density matrices of contiguous windows of ``width`` qubits (1 .. min(n, 6)) estimated from measurement shots, the
+        finite-shot counterpart of ``window_rdms``: ``(rho_hat, counts)``.  ``rho_hat`` is complex128 (n_states, n_windows, 2^w,
+        2^w), ``paulis_rdm`` of the estimated coefficients of the 4^w strings of each window (``window_strings``, windows as
+        ``starts`` of ``window_rdms``); ``counts`` is int64 (n_states, n_windows) + (4,) * w, the shots behind each coefficient.
+        ``rho_hat`` is exactly Hermitian with trace exactly 1 (the identity coefficient is exactly 1.0), but it is a linear
+        inversion: it is NOT positive semi-definite in general -- at few shots it has negative eigenvalues of the order of the
+        statistical error.  The projected kernels need only Frobenius distances, which stay meaningful.  Synchronous."""
+        return estimate_window_rdms(bits, bases, width, starts, self.shot_string_sums_host)
 
     def bond_spectra(self, mps_set: MpsSet, max_values: int | None = None, norms: bool = False):
         """Entanglement spectra of every state of an fp64 set: the Schmidt weights (eigenvalues of the reduced state, descending, sum

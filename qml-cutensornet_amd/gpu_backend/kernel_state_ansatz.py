@@ -586,6 +586,144 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     return kernel_mat
 
 
+def build_shot_feature_kernel_matrix(mpi_comm, ansatz, X, Y=None, observables=None, window=None, shots=None, shot_seed=0, settings="random", pqk_gamma=None,
+                                     truncation_error=None, info_file=None, loglevel=30):
+    """The projected kernel on chosen observables or on windows of k qubits at ``shots`` measurement shots per state -- the
+    finite-shot counterpart of ``build_projected_kernel_matrix(observables=...)`` and of its ``rdm=k, window=True`` form.  Exactly
+    one of the two forms is given:
+
+    ``observables=[...]`` (anything ``engine.pauli_strings(n_qubits, ...)`` takes):
+        K[j, i] = exp(-g sum_m (O_hat_m(X_i) - O_hat_m(Y_j))^2),
+    O_hat_m = the mean sign of the shots whose bases equal string m on its support (``Context.estimate_pauli_strings``; 0.0 where
+    no shot does), ``pqk_gamma=None`` meaning g = 1 / len(observables).
+
+    ``window=k`` (an int in 1 .. min(6, n_qubits)):
+        K_k[j, i] = exp(-g sum_a ||rho_hat_{a,k}(X_i) - rho_hat_{a,k}(Y_j)||_F^2),   a = 0 .. n_qubits - k,
+    rho_hat = the window RDMs rebuilt from the estimated coefficients of their 4^k strings (``Context.estimate_window_rdms``:
+    Hermitian with trace 1, not positive in general), ``pqk_gamma=None`` meaning g = 1 / n_qubits.
+
+    ``settings="random"`` measures in ``engine.random_bases(shots, n_qubits, shot_seed)``; ``settings="window"`` (with ``window``
+    only) in the designed bases ``engine.window_settings(shots, n_qubits, window)``, in which a string of weight v on a window is
+    seen by shots / 3^v shots; it needs ``shots >= 3^window``.  Each rank builds its share of the states, samples it with
+    ``Context.sample(..., seed=shot_seed, first_state=<the share's offset>)`` (the states of Y are indexed after those of X, as in
+    ``build_projected_kernel_matrix``), estimates on its device, and the values are all-gathered; rank 0 calls
+    ``Context.feature_gram`` or ``Context.projected_window_gram`` and returns the ``len(Y) x len(X)`` matrix, the other ranks
+    ``None``.  The estimates are ratios of integers, so K is the same bits for any number of ranks."""
+    if (observables is None) == (window is None):
+        raise ValueError("give exactly one of observables (a list of Pauli strings) and window (the qubits of a window)")
+    n_qubits = int(ansatz.num_qubits)
+    if isinstance(shots, bool) or not isinstance(shots, (int, np.integer)) or shots < 1:
+        raise ValueError(f"shots must be an int >= 1 (got {shots!r})")
+    shots = int(shots)
+    if settings not in ("random", "window"):
+        raise ValueError(f"settings must be 'random' or 'window' (got {settings!r})")
+    strings = None
+    if observables is not None:
+        if settings == "window":
+            raise ValueError("settings='window' designs the bases for the windows of window=k: it cannot be combined with observables")
+        strings = _engine.pauli_strings(n_qubits, observables)  # ValueError: empty list, bad spec
+    else:
+        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= window <= min(_engine.WINDOW_MAX_WIDTH, n_qubits):
+            raise ValueError(f"window must be an int in 1 .. min({_engine.WINDOW_MAX_WIDTH}, n_qubits) = {min(_engine.WINDOW_MAX_WIDTH, n_qubits)}, got {window!r}")
+        window = int(window)
+        if settings == "window" and shots < 3 ** window:
+            raise ValueError(f"settings='window' needs shots >= 3^window = {3 ** window} (got {shots})")
+    if Y is not None and len(X) < len(Y):
+        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    if pqk_gamma is not None:
+        _engine.projected_gamma(pqk_gamma, 1)  # ValueError unless > 0 and finite
+    X = np.asarray(X, dtype=np.float64)
+    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
+    fidelity = 1.0 - float(truncation_error)
+
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: the shot-feature kernel has no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    prof = {}
+    t_start = time.perf_counter()
+    if is_root:
+        prof["n_procs"] = [n_procs, "gpus"]
+        prof["lenX"] = [len(X), "entries"]
+        prof["lenY"] = [None if Y is None else len(Y), "entries"]
+
+    ctx = _engine.default_context(device_id)
+    shot_bases = _engine.window_settings(shots, n_qubits, window) if settings == "window" else _engine.random_bases(shots, n_qubits, shot_seed)
+    n_windows = 0 if strings is not None else n_qubits - window + 1
+    f_shape = (len(strings),) if strings is not None else (n_windows, 1 << window, 1 << window, 2)
+    shares, sim_secs, fids, chis, feat_secs = [], [], [], [], 0.0
+    for label, points in (("X", X), ("Y", Y)):
+        if points is None:
+            continue
+        _say(is_root, f"\nContracting the MPS of the circuits from the {label} dataset...")
+        lo, local, secs, fid = _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, device_id, host_workers)
+        sim_secs += secs
+        fids += fid
+        ctx.trim()  # the device builder's arena goes back before the sampler needs memory
+        t0 = time.perf_counter()
+        if local is None:
+            F, chi = np.zeros((0,) + f_shape, dtype=np.float64), np.zeros(0)
+        else:
+            bits = ctx.sample(local, shots, bases=shot_bases, seed=shot_seed, first_state=int(lo) + (0 if label == "X" else len(X)))
+            if strings is not None:
+                F = ctx.estimate_pauli_strings(bits, shot_bases, strings)[0]
+            else:  # complex128 as (re, im) pairs of float64: the features travel as the other forms' do
+                F = np.ascontiguousarray(ctx.estimate_window_rdms(bits, shot_bases, window)[0]).view(np.float64).reshape((len(local),) + f_shape)
+            chi = local.dims.max(axis=1)
+            local.close()
+        feat_secs += time.perf_counter() - t0
+        shares.append((lo, F, len(points)))
+        chis.append(chi)
+
+    t0 = time.perf_counter()
+    feats = [_gather_features(mpi_comm, lo, F, total) for lo, F, total in shares]
+    chi_all = [np.concatenate([np.asarray(c, dtype=np.float64) for c in comm_allgather(mpi_comm, chi)]) for chi in chis]
+    gather_secs = time.perf_counter() - t0
+    if not is_root:
+        return None
+    g = _engine.projected_gamma(pqk_gamma, len(strings) if strings is not None else n_qubits)
+    _say(True, "\nFinished contracting all MPS.\n\nCalculating the shot-feature kernel matrix...")
+    t0 = time.perf_counter()
+    if strings is not None:
+        kernel_mat = ctx.feature_gram(feats[0], None if Y is None else feats[1], g)
+    else:
+        rdms = [np.ascontiguousarray(f).view(np.complex128)[..., 0] for f in feats]
+        kernel_mat = ctx.projected_window_gram(rdms[0], None if Y is None else rdms[1], g)
+    tiles = time.perf_counter() - t0
+
+    prof["r0_circ_gen"] = [0.0, "seconds"]
+    prof["r0_circ_sim"] = [sum(sim_secs), "seconds"]
+    if sim_secs:
+        prof["avg_circ_sim"] = [mean(sim_secs), "seconds"]
+        prof["median_circ_sim"] = [median(sim_secs), "seconds"]
+    prof["avg_fidelity"] = [sum(fids) / max(1, len(fids)), ""]
+    prof["ave max chi x"] = (float(chi_all[0].mean()) if chi_all[0].size else 0.0, "chi x")
+    chi_y = chi_all[-1] if Y is not None else chi_all[0]
+    prof["ave max chi y"] = (float(chi_y.mean()) if chi_y.size else 0.0, "chi y")
+    prof["r0_RR_recv"] = [gather_secs, "seconds"]  # the all-gather of the estimates
+    prof["pqk_gamma"] = [g, ""]
+    if strings is not None:
+        prof["pqk_observables"] = [len(strings), "strings"]
+    else:
+        prof["pqk_rdm"] = [window, "qubits"]
+    prof["pqk_shots"] = [shots, "shots"]
+    prof["pqk_settings"] = [settings, ""]
+    prof["pqk_features_time"] = [feat_secs, "seconds"]
+    prof["kernel_mat_time"] = [tiles, "seconds"]
+    prof["total_time"] = [time.perf_counter() - t_start, "seconds"]
+    if info_file is not None:
+        with open(info_file + ".json", "w") as fp:
+            json.dump(prof, fp, indent=4)
+    return kernel_mat
+
+
 def build_entanglement_profile(mpi_comm, ansatz, X, truncation_error=None, max_values=None, info_file=None, loglevel=30):
     """Entanglement across every bond of the states of ``X``, from the same states as ``build_projected_kernel_matrix``: each rank
     builds its share (same builders, same ``QK_BUILDER`` rules), takes the Schmidt weights and purities of every bond on its

@@ -25,6 +25,12 @@ engine.random_bases(T, n, 0), then ctx.shadow_hist_host on the pairs of the run'
 packs them, counts and downloads the histograms), after a warm-up: shadow_hist_ms (the median; shadow_hist_ms_min and _max give the
 spread over the repetitions), shadow_shot_pairs = pairs T^2, shadow_shot_pairs_per_s, shadow_over_sample against sample_ms of the same
 run, and the median off-diagonal entry of the shadow kernel at gamma = tau = 1.
+``--shot-strings W`` (with ``--shots``, 1 <= W <= 6) adds the window RDMs estimated from those shots: ctx.estimate_window_rdms(bits,
+bases, W) on all n - W + 1 windows (the call uploads the outcome bytes, packs them, tests every shot against the (n - W + 1) 4^W
+strings and rebuilds the RDMs), after a warm-up: shot_strings_ms (the median; shot_strings_ms_min and _max give the spread over the
+repetitions), n_shot_strings, shot_string_tests = states x shots x strings, shot_string_tests_per_s, shot_strings_over_sample against
+sample_ms of the same run, and shot_strings_mirror_ms: the numpy mirror engine.estimate_window_rdms on the first 8 states of the same
+input (shot_strings_mirror_states; one run, not scaled up), with shot_strings_mirror_equal = the two agree bit for bit there.
 ``--window W`` (1 <= W <= 6) adds the k-qubit projected kernel: ctx.window_rdms(xs, W) on all n - W + 1 windows and
 ctx.projected_window_gram(rho), each after a warm-up: window_rdms_ms (the median; window_rdms_ms_min and _max give the spread over the
 repetitions), window_width, n_windows, window_flops and window_tflops, projected_window_gram_ms, window_over_pair against
@@ -41,7 +47,7 @@ logp_sample|.  amp_flops, from the true bonds at 8 flops per complex multiply-ad
 A^1) (1 x 2 chi_k+1 over chi_k), i.e. S sum 8 (2 chi_k+1 chi_k), plus the environment pass that gives <psi|psi> for logp
 (``local_sweep_flops``).
 usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement] [--compress CHI]
-                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S [--shadow-shots T]] [--window W] [--amplitudes S]"""
+                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S [--shadow-shots T] [--shot-strings W]] [--window W] [--amplitudes S]"""
 import argparse
 import json
 import os
@@ -153,6 +159,7 @@ def main():
     ap.add_argument("--block-shots", default=None, metavar="U,M", help="with --block-widths: also time the block overlaps estimated from U settings of M shots")
     ap.add_argument("--shots", type=int, default=0, metavar="S", help="also time sample() with S shots per state in random bases")
     ap.add_argument("--shadow-shots", type=int, default=0, metavar="T", help="with --shots: also time the shadow kernel's shot-pair histograms from T shots per state")
+    ap.add_argument("--shot-strings", type=int, default=0, metavar="W", help="with --shots: also time estimate_window_rdms at width W on the sampled shots")
     ap.add_argument("--window", type=int, default=0, metavar="W", help="also time window_rdms on all windows of W qubits and projected_window_gram")
     ap.add_argument("--amplitudes", type=int, default=0, metavar="S", help="also time amplitudes() with logp on S shots per state drawn with sample()")
     args = ap.parse_args()
@@ -160,6 +167,10 @@ def main():
         ap.error("--block-shots needs --block-widths")
     if args.shadow_shots and args.shots <= 0:
         ap.error("--shadow-shots needs --shots (shadow_over_sample compares with its sample_ms)")
+    if args.shot_strings and args.shots <= 0:
+        ap.error("--shot-strings needs --shots (it estimates from those shots, and shot_strings_over_sample compares with their sample_ms)")
+    if args.shot_strings and not 1 <= args.shot_strings <= engine.WINDOW_MAX_WIDTH:
+        ap.error(f"--shot-strings takes a width in 1 .. {engine.WINDOW_MAX_WIDTH}")
     gamma = args.gamma if args.gamma is not None else (0.1 if args.config == "cfg5" else 1.0)
     n, reps, d, npts = bench.CONFIGS[args.config]
     X = synthetic_features(npts, n, 5)
@@ -295,6 +306,28 @@ def main():
             "shadow_hist_ms_min": round(min(ts), 3), "shadow_hist_ms_max": round(max(ts), 3), "shadow_shot_pairs": shot_pairs,
             "shadow_shot_pairs_per_s": round(shot_pairs / (shadow_ms * 1e-3), 1), "shadow_over_sample": round(shadow_ms / dist["sample_ms"], 4),
             "median_offdiag_shadow": float(np.median(KSH[sh_pairs[:, 0] != sh_pairs[:, 1]])),
+        })
+    if args.shot_strings > 0:
+        W_ss = args.shot_strings
+        n_ss = (n - W_ss + 1) * 4**W_ss
+        ctx.estimate_window_rdms(bits, bases, W_ss)  # warm-up
+        ts = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            rho_hat, _ = ctx.estimate_window_rdms(bits, bases, W_ss)
+            ts.append(1e3 * (time.perf_counter() - t0))
+        ss_ms = float(np.median(ts))
+        t0 = time.perf_counter()
+        mirror_rho, _ = engine.estimate_window_rdms(bits[:8], bases, W_ss)
+        mirror_ms = 1e3 * (time.perf_counter() - t0)
+        tests = npts * args.shots * n_ss
+        KSS = ctx.projected_window_gram(rho_hat)
+        dist.update({
+            "shot_strings_width": W_ss, "n_shot_strings": n_ss, "shot_strings_reps": args.reps, "shot_strings_ms": round(ss_ms, 3),
+            "shot_strings_ms_min": round(min(ts), 3), "shot_strings_ms_max": round(max(ts), 3), "shot_string_tests": tests,
+            "shot_string_tests_per_s": round(tests / (ss_ms * 1e-3), 1), "shot_strings_over_sample": round(ss_ms / dist["sample_ms"], 4),
+            "shot_strings_mirror_ms": round(mirror_ms, 3), "shot_strings_mirror_states": int(min(8, npts)),
+            "shot_strings_mirror_equal": bool(np.array_equal(mirror_rho, rho_hat[:8])), "median_offdiag_pqk_shot_window": float(np.median(KSS[off])),
         })
     if args.window > 0:
         W = args.window
