@@ -231,13 +231,16 @@ int qk_plan_create_all(int32_t n_sites, int32_t nx, const int32_t* x_dims, int32
  * tile (8 x 8 pairs) it takes part in -- the tile-reuse lower bound of SURVEY 8d, beside qk_stats.bytes (every state read
  * once per PAIR).  Any out pointer may be NULL.                                                                          */
 int qk_plan_cost(const qk_plan* plan, double* plan_ms, int32_t* threads, double* tile_reuse_bytes);
-/* MERGED STEPS (no entry point: part of qk_gram_values; QK_MERGE=0 disables).  Between the edge blocks the site-fused sweep may walk
- * two neighbouring sites as ONE step: the set holds, beside its plain image, the chain's sites contracted in twos over the bond between
- * them (tensors [l][4][r], made once per set on first use and counted by qk_mps_set_info), and a workgroup decides per pair and step:
- * the merged tensor where that keeps an LDS-resident step in the LDS and costs no more padded work than the two sites, the two plain
- * sites otherwise (a dip of the bond).  Same matrix work where the bonds are level, half the barriers, set-ups and stream turn-arounds;
- * again a host-prepared choice of the contraction order (reference call site G:380).  qk_stats' algorithmic flops and bytes stay those
- * of the plain chain.                                                                                                          */
+/* MERGED STEPS (no entry point: part of qk_gram_values; QK_MERGE=0 disables, 1 = the fixed pairs only, 2 = default).  Between the edge
+ * blocks the site-fused sweep may walk two neighbouring sites as ONE step: the set holds, beside its plain image, neighbouring sites of
+ * the chain contracted in twos over the true bond between them (tensors [l][4][r], one per start site, made once per set on first use
+ * and counted by qk_mps_set_info; QK_MERGE=1, or a device too full for it: the even starts k + 2 t only).  Which steps of a pair are
+ * merged is decided once per plan, sets and launch shape by a small kernel on the sweep's stream (csrc/qk_plan.h: qk_segment_chain), a
+ * mask of 128 bits per pair that the plan keeps: a merge is admissible where it keeps an LDS-resident step in the LDS and costs no more
+ * padded work than the two sites; among the admissible segmentations the one with the fewest executed matrix instructions plus a fixed
+ * price per step is taken (QK_MERGE=1: every admissible merge of the fixed pairs (k + 2 t, k + 2 t + 1)).  A merged step neither pads
+ * its middle bond to 16 nor walks it, and saves the barriers, set-ups and stream turn-arounds of a step; again a host-prepared choice of
+ * the contraction order (reference call site G:380).  qk_stats' algorithmic flops and bytes stay those of the plain chain.          */
 
 /* ---- the hot path -----------------------------------------------------------
  * qk_gram_values: for every pair p of the plan compute z_p = <x_i|y_j> and write

@@ -310,7 +310,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_quad_kernel(const
     const int xi = g.pairs[2 * p], yj = g.pairs[2 * p + 1];
     // LDS-resident step: X and X' fit the buffer and ONE round holds all quads (X' may then overwrite X), or they fit side by side;
     // otherwise X' is built in strips of W blocks of b'.  (one round: no whole quad is dealt then, and the pieces are at most pd mt ceil(nt / 2))
-    qkf_step_table<XCAP, NT>(g, xi, yj, rec, m_off, tid, [](const int pmt, const int nt) { return pmt * ((nt + 1) / 2) <= NW; });
+    qkf_step_table<XCAP, NT>(g, xi, yj, p, rec, m_off, tid, QkSegRule{XCAP, NW, true});
     const int ek = g.edge_k, k_hi = ns - ek;
     const bool edges = ek > 0;
     if (!edges)

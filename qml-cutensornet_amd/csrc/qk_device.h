@@ -41,15 +41,18 @@ struct SweepArgs {
   const double* yedge;
   const long long* yedge_offs;
   int edge_k;
-  // MERGED STEPS (site-fused sweep; merge_steps = 0: none): xmg / ymg hold, per state, the chain's sites [edge_k, n - edge_k) contracted
-  // in twos -- tensors [l][4][r], physical index 2 p1 + p2, interleaved complex, offsets (doubles) in x/ymg_offs[state][merge_steps],
-  // merge_steps = (n - 2 edge_k) / 2.  A workgroup decides per pair and per step whether it walks the merged tensor (half the barriers,
-  // set-ups and load latencies for the same matrix work when the bonds are level) or the two plain sites (qk_fused.h: qkf_step_table).
+  // MERGED STEPS (site-fused sweep; seg = null: none): xmg / ymg hold, per state, neighbouring sites of the chain [edge_k, n - edge_k)
+  // contracted in twos -- tensors [l][4][r], physical index 2 p1 + p2, interleaved complex; the tensor of the sites s, s + 1 lies at
+  // offset (doubles) x/ymg_offs[state][merge_steps] entry s - edge_k, merge_steps = n - 2 edge_k - 1 (an image of the even starts only
+  // leaves the odd entries unused).  seg[2 pair], seg[2 pair + 1]: the pair's segmentation mask (qk_plan.h: qk_segment_chain, made per
+  // launch by qk_segment_kernel) -- bit i set = the step at site edge_k + i walks the merged tensor (half the barriers, set-ups and load
+  // latencies, and the middle bond neither padded nor walked), else the plain site (qk_fused.h: qkf_step_table).
   const double* xmg;
   const double* ymg;
   const int64_t* xmg_offs;
   const int64_t* ymg_offs;
   int merge_steps;
+  const unsigned long long* seg;
   int turn_ints;  // the DET forms of the site-fused kernels: turn counters per set = blocks of b' x blocks of a' of the largest site (qk_fused.h: qkf_turn_add)
   unsigned long long* tail;     // per-launch device clocks (s_memrealtime, 100 MHz): [0] first workgroup start, [1] first workgroup exit, [4] last workgroup exit
   unsigned long long* err;      // one word per sweep (both launches): set by a DET kernel whose ordered accumulation ran out of patience (qk_get_stats fails the call)

@@ -40,8 +40,8 @@
 //     rounds of (waves x slots), and written to the other global buffer;
 //   * the chain is walked in STEPS: the first and last k sites of both states come as edge blocks (one product each), a step in
 //     between is one site or two neighbouring sites contracted into one tensor of physical dimension 4 (merged image of the set),
-//     whichever costs less for the pair at hand; per-step control is a 48-byte record, the step table of the pair, built by all
-//     threads at pair set-up (qkf_step_table).
+//     as the pair's segmentation mask says (qk_plan.h: qk_segment_chain, made once per plan by qk_segment_kernel); per-step control
+//     is a 48-byte record, the step table of the pair, built by all threads at pair set-up (qkf_step_table).
 // Two launch shapes (chosen per launch -- or per run of pairs of a split plan -- in qkgram.hip): one 12-wave workgroup per CU
 // (three waves per SIMD at 168 VGPRs, two tiles per wave) with an 8192-element X buffer -- by default in its DUAL form
 // (qk_sweep_fused_dual_kernel below: the two tiles of a wave share the rows of X and of A, so every A and X fragment feeds
@@ -591,14 +591,14 @@ typedef __attribute__((address_space(3))) v4i lds_v4i;
 //   [0] a  [1] a2  [2] b  [3] b2  [4] true a  [5] k-steps of b  [6] W  [7] small  [8] ceil(2^20 / mt)  [9] log2 pd  [10] next step
 //   [11] ITEM_RECIPS (the one-tile kernel's order of items): ceil(2^15 / column blocks) of a full strip | of the last strip << 16 (qk_unit_recips)
 // and the addresses of the step's two tensors ([a][pd][a2] of x, [b][pd][b2] of y) in a second table.  A step is one site (pd = 2,
-// entry = the site's index, next = + 1) or, with a merged image (SweepArgs.merge_steps), two sites contracted into one tensor of
-// physical dimension 4 (entry = the first site's index, next = + 2).  The merged step does the same matrix work as its two sites when
-// the bond between them is as large as the bonds around them, with half the barriers, set-ups and stream turn-arounds; it is taken
-// unless it would push an LDS-resident pair of sites out of the LDS (its 4 mt nt items no longer fit one round, and X and X' do not
-// fit side by side) or cost more padded work than the two sites (a dip of the bond between them).  `one_round(pd * mt, nt)`:
-// the kernel's test that a single round holds all items of a step.
-template <int XCAP, int NT, bool ITEM_RECIPS = false, typename OneRound>
-__device__ __forceinline__ void qkf_step_table(const SweepArgs& g, const int xi, const int yj, lds_v4i* const rec, long long* const m_off, const int tid, const OneRound one_round) {
+// entry = the site's index, next = + 1) or, with a merged image, two sites contracted into one tensor of physical dimension 4 (entry =
+// the first site's index, next = + 2).  The merged step does the same matrix work as its two sites when the bond between them is as
+// large as the bonds around them, with half the barriers, set-ups and stream turn-arounds, and less where the true middle bond would
+// have been padded.  Which steps are merged is the pair's segmentation mask (SweepArgs.seg; qk_plan.h: qk_segment_chain, where the rule
+// lives): one thread per site, a site whose bit is set writes the merged entry, any other site the plain one (the second site of a
+// merged step is then never visited).  `rule`: the launch's shape, as the mask was made with -- here it tells the LDS-resident steps.
+template <int XCAP, int NT, bool ITEM_RECIPS = false>
+__device__ __forceinline__ void qkf_step_table(const SweepArgs& g, const int xi, const int yj, const long long pair, lds_v4i* const rec, long long* const m_off, const int tid, const QkSegRule rule) {
   const int ns = g.n_sites, n1 = ns + 1;
   const int32_t* const xd = g.xdims + (long long)xi * n1;
   const int32_t* const yd = g.ydims + (long long)yj * n1;
@@ -606,9 +606,6 @@ __device__ __forceinline__ void qkf_step_table(const SweepArgs& g, const int xi,
   const int32_t* const yt = g.ytrue + (long long)yj * n1;
   const v2d* const xdata = reinterpret_cast<const v2d*>(g.xdata);
   const v2d* const ydata = reinterpret_cast<const v2d*>(g.ydata);
-  auto is_small = [&](const int a, const int a2, const int b, const int b2, const int pd) __attribute__((always_inline)) {
-    return a * b <= XCAP && a2 * b2 <= XCAP && (one_round(pd * (a / TILE), b2 / TILE) || a * b + a2 * b2 <= XCAP);
-  };
   auto put = [&](const int e, const int a, const int a2, const int b, const int b2, const int ps, const int next, const bool small, const v2d* const A, const v2d* const B)
                  __attribute__((always_inline)) {
     const int mt = a / TILE, nt = b2 / TILE;
@@ -624,30 +621,21 @@ __device__ __forceinline__ void qkf_step_table(const SweepArgs& g, const int xi,
   };
   auto plain = [&](const int e, const int next) __attribute__((always_inline)) {
     const int a = xd[e], a2 = xd[e + 1], b = yd[e], b2 = yd[e + 1];
-    put(e, a, a2, b, b2, 1, next, is_small(a, a2, b, b2, 2), xdata + (g.xoffs[(long long)xi * ns + e] >> 1), ydata + (g.yoffs[(long long)yj * ns + e] >> 1));
+    put(e, a, a2, b, b2, 1, next, qk_seg_small(rule, a, a2, b, b2, 2), xdata + (g.xoffs[(long long)xi * ns + e] >> 1), ydata + (g.yoffs[(long long)yj * ns + e] >> 1));
   };
-  if (g.merge_steps == 0) {
+  if (g.seg == nullptr) {
     for (int e = tid; e < ns; e += NT) plain(e, e + 1);
     return;
   }
   const int ek = g.edge_k, k_hi = ns - ek;
-  for (int t = tid; 2 * t < k_hi - ek; t += NT) {
-    const int e = ek + 2 * t;
-    if (e + 1 >= k_hi) {  // the single last site of an odd chain
-      plain(e, e + 1);
-      continue;
-    }
-    const int a = xd[e], am = xd[e + 1], a2 = xd[e + 2], b = yd[e], bm = yd[e + 1], b2 = yd[e + 2];
-    const bool sm = is_small(a, a2, b, b2, 4);
-    const long long work_m = 4ll * a * b2 * (b + a2), work_p = 2ll * a * bm * (b + am) + 2ll * am * b2 * (bm + a2);
-    // (measured on the two headline sets, same box: allowing 1/8 or 1/4 more padded work per merged step loses what the saved barriers
-    // gain -- 397.4 / 400.0 against 395.7 ms; merging LDS-resident steps only when that saves 6 % of the work: 406 ms)
-    const bool merged = (sm || (!is_small(a, am, b, bm, 2) && !is_small(am, a2, bm, b2, 2))) && work_m <= work_p;
-    plain(e + 1, e + 2);
-    if (merged)
-      put(e, a, a2, b, b2, 2, e + 2, sm, reinterpret_cast<const v2d*>(g.xmg) + (g.xmg_offs[(long long)xi * g.merge_steps + t] >> 1),
-          reinterpret_cast<const v2d*>(g.ymg) + (g.ymg_offs[(long long)yj * g.merge_steps + t] >> 1));
-    else plain(e, e + 1);
+  const unsigned long long w0 = g.seg[2 * pair], w1 = g.seg[2 * pair + 1];
+  for (int e = ek + tid; e < k_hi; e += NT) {
+    const int i = e - ek;
+    if (qk_seg_bit(w0, w1, i) && e + 1 < k_hi) {
+      const int a = xd[e], a2 = xd[e + 2], b = yd[e], b2 = yd[e + 2];
+      put(e, a, a2, b, b2, 2, e + 2, qk_seg_small(rule, a, a2, b, b2, 4), reinterpret_cast<const v2d*>(g.xmg) + (g.xmg_offs[(long long)xi * g.merge_steps + i] >> 1),
+          reinterpret_cast<const v2d*>(g.ymg) + (g.ymg_offs[(long long)yj * g.merge_steps + i] >> 1));
+    } else plain(e, e + 1);
   }
 }
 
@@ -755,7 +743,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
     // an item is (ta, tb, p): pd mt nt of them.  LDS-resident step: X and X' fit the buffer and either ONE round holds all items
     // (X' may then overwrite X) or X and X' fit side by side (any number of rounds: X stays intact);
     // otherwise X' is built in strips of W blocks of b' (the strip's rows must fit the LDS), items in rounds of NW * S
-    qkf_step_table<XCAP, NT, true>(g, xi, yj, rec, m_off, tid, [](const int pmt, const int nt) { return pmt * nt <= NW * S; });
+    qkf_step_table<XCAP, NT, true>(g, xi, yj, p, rec, m_off, tid, QkSegRule{XCAP, NW * S, false});
     const int ek = g.edge_k, k_hi = ns - ek;  // the chain runs over the sites [ek, k_hi): the ends are in the edge blocks
     const bool edges = ek > 0;
     if (!edges)
@@ -1209,7 +1197,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
   auto table_of = [&](const long long pp) __attribute__((always_inline)) {
     if (pp < 0) return;
     const int xi_ = g.pairs[2 * pp], yj_ = g.pairs[2 * pp + 1];
-    qkf_step_table<XCAP, NT>(g, xi_, yj_, rec, m_off, tid, [](const int pmt, const int nt) { return pmt * ((nt + 1) / 2) <= NW; });
+    qkf_step_table<XCAP, NT>(g, xi_, yj_, pp, rec, m_off, tid, QkSegRule{XCAP, NW, true});
   };
   table_of(p);
   while (p >= 0) {

@@ -76,14 +76,16 @@ struct qk_mps_set {
   QkDevBuf d_edge_offs;  // long long: [n_states][2] element offsets
   int edge_k = 0;
   int64_t edge_bytes = 0;
-  // merged image of the site-fused sweep (SweepArgs.merge_steps; made on first use for the plan's edge_k): the chain's sites [k, n - k)
-  // contracted in twos, interleaved complex [l][4][r]
+  // merged image of the site-fused sweep (SweepArgs.merge_steps; made on first use for the plan's edge_k): neighbouring sites s, s + 1 of
+  // the chain [k, n - k) contracted in twos, interleaved complex [l][4][r] -- for every start s (mg_stride 1) or for the even starts
+  // s = k + 2 t only (mg_stride 2: QK_MERGE=1, or the full image did not fit the device)
   QkDevBuf d_mg;        // double
-  QkDevBuf d_mg_offs;   // int64_t: offsets in doubles [n_states][mg_steps]
-  QkDevBuf d_mg_units;  // long long: first 16 x 16 block of each (state, step) in the numbering of qk_merge_kernel's units [n_states * mg_steps + 1]
+  QkDevBuf d_mg_offs;   // int64_t: offsets in doubles [n_states][mg_steps], entry s - k
+  QkDevBuf d_mg_units;  // long long: first 16 x 16 block of each (state, start) in the numbering of qk_merge_kernel's units [n_states * starts per state + 1]
   std::vector<long long> h_edge_offs, h_mg_units;  // host staging of the tables above (they outlive the asynchronous copies)
   std::vector<int64_t> h_mg_offs;
-  int mg_k = -1, mg_steps = 0;
+  int mg_k = -1, mg_steps = 0, mg_stride = 0;
+  bool mg_full_failed = false;  // the image of every start did not fit once: not tried again for this set
   int64_t mg_bytes = 0;
 };
 

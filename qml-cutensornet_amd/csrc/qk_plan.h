@@ -1,5 +1,6 @@
-// qk_plan.h -- the host-side plan of a Gram share (struct qk_plan), the constants the planner shares with the launches, and the
-// choice of the sweep's launches for a plan (qk_choose_sweep).
+// qk_plan.h -- the host-side plan of a Gram share (struct qk_plan), the constants the planner shares with the launches, the pure
+// functions host and device share (the order of a step's units, the units of an edge product, the segmentation of a chain into plain and
+// merged steps), and the choice of the sweep's launches for a plan (qk_choose_sweep).
 // Plain C++: no HIP type appears here, so the planner (qk_planner.cpp) also builds as a host-only translation unit
 // (tests/host_san: -fsanitize=address,undefined), and the choice is tested on the CPU (tests/host_san/choice_main.cpp).
 #pragma once
@@ -101,6 +102,86 @@ QK_HD static inline QkEdgeUnit qk_edge_unit(const int u, const int mt, const int
   return QkEdgeUnit{v - tp * mt, 2 * tp + (half ? 1 : 0), !single && second, u < (halves ? r0 + 2 * left : pairs) && (!half || second)};
 }
 
+// ----------------------------------------------------------------------------------------
+// The segmentation of a pair's chain into steps of the site-fused sweep (qk_fused.h: qkf_step_table).  The chain's sites [ek, n - ek) are
+// walked one at a time (pd = 2) or two at a time through the sets' merged images (pd = 4: sites e, e + 1 contracted over their true middle
+// bond once per state, so the sweep neither pads that bond to 16 nor walks it).  A merge at site e is ADMISSIBLE (qk_merge_admissible) when
+// it keeps an LDS-resident pair of sites in the LDS of the launch's shape (QkSegRule: the shape's X buffer and its test that one round
+// holds all units of a step) and costs no more padded work than the two sites.  qk_segment_chain picks among the admissible merges:
+//   greedy  every admissible merge at an allowed start, walking forward (with even starts only: the fixed pairs (ek + 2 t, ek + 2 t + 1));
+//   else    the segmentation that minimises the matrix instructions the kernels execute for the steps (qk_step_instr: tiles of 16, K
+//           trimmed to the true bond in steps of 4, 3M product) plus QK_STEP_PRICE per step, by dynamic programming from the right end and
+//           a forward walk over the starts that are reached.  Ties go to fewer steps, then to the even start.
+// The result is a mask of 128 bits: bit i set = the step that starts at site ek + i takes site ek + i + 1 with it (sites beyond bit 127 are
+// walked singly).  Pure functions of the bond rows, host and device: the kernel that fills the launches' masks (qkgram.hip:
+// qk_segment_kernel), the step table, tools/merge_potential.py and the CPU tests (tests/host_san/segment_main.cpp) all call these.
+// ----------------------------------------------------------------------------------------
+static constexpr int QK_STEP_PRICE = 375;  // matrix instructions' worth of the fixed cost of a step: two barriers, set-up, load latencies = 2.5 us of a 12-wave workgroup (tools/site_overhead.py); qk_planner.cpp: choose_edge_k
+static constexpr int QK_SEG_BITS = 128;
+struct QkSegRule {  // a launch's shape: elements of its LDS X buffer; one round holds pd mt ceil(nt / 2) <= cap pairs of tiles (dual) or pd mt nt <= cap tiles
+  int xcap, cap;
+  bool dual;
+};
+struct QkSegMask {
+  unsigned long long w[2];
+};
+QK_HD static inline bool qk_seg_bit(const unsigned long long w0, const unsigned long long w1, const int i) { return i < QK_SEG_BITS && (((i < 64 ? w0 : w1) >> (i & 63)) & 1ull) != 0; }
+QK_HD static inline bool qk_seg_one_round(const QkSegRule& r, const int pmt, const int nt) { return pmt * (r.dual ? (nt + 1) / 2 : nt) <= r.cap; }
+// LDS-resident step: X and X' fit the buffer and either ONE round holds all units (X' may then overwrite X) or X and X' fit side by side
+QK_HD static inline bool qk_seg_small(const QkSegRule& r, const int a, const int a2, const int b, const int b2, const int pd) {
+  return a * b <= r.xcap && a2 * b2 <= r.xcap && (qk_seg_one_round(r, pd * (a / QK_TILE), b2 / QK_TILE) || a * b + a2 * b2 <= r.xcap);
+}
+// matrix instructions of a step [a][pd][a2] x [b][pd][b2] (padded bonds) with true bonds at, bt on its left: phase 1 pd mt nt tiles of
+// ceil(bt / 4) k-steps, phase 2 pd nt nn tiles of ceil(at / 4) k-steps over the blocks of rows, three real products each
+QK_HD static inline long long qk_step_instr(const int pd, const int a, const int a2, const int b, const int b2, const int at, const int bt) {
+  return 3ll * pd * (b2 / QK_TILE) * ((long long)(a / QK_TILE) * ((bt + 3) >> 2) + (long long)(a2 / QK_TILE) * ((at + 3) >> 2));
+}
+// xd / yd: padded bond rows of the two states (n_sites + 1 entries); the merge of sites e, e + 1 (the caller keeps e + 2 inside the chain).
+// (measured on the two headline sets, same box: allowing 1/8 or 1/4 more padded work per merged step loses what the saved barriers
+// gain -- 397.4 / 400.0 against 395.7 ms; merging LDS-resident steps only when that saves 6 % of the work: 406 ms)
+QK_HD static inline bool qk_merge_admissible(const QkSegRule& r, const int32_t* const xd, const int32_t* const yd, const int e) {
+  const int a = xd[e], am = xd[e + 1], a2 = xd[e + 2], b = yd[e], bm = yd[e + 1], b2 = yd[e + 2];
+  const long long work_m = 4ll * a * b2 * (b + a2), work_p = 2ll * a * bm * (b + am) + 2ll * am * b2 * (bm + a2);
+  return (qk_seg_small(r, a, a2, b, b2, 4) || (!qk_seg_small(r, a, am, b, bm, 2) && !qk_seg_small(r, am, a2, bm, b2, 2))) && work_m <= work_p;
+}
+// parities: bit 0 = merges may start at even i (site ek + i), bit 1 = at odd i.  objective / steps (optional): instructions + price per
+// step and the number of steps of the segmentation returned.
+QK_HD static inline QkSegMask qk_segment_chain(const int32_t* const xd, const int32_t* const xt, const int32_t* const yd, const int32_t* const yt, const int n_sites, const int ek,
+                                               const QkSegRule& rule, const int parities, const bool greedy, long long* const objective = nullptr, int* const steps = nullptr) {
+  const int m = n_sites - 2 * ek;
+  auto may = [&](const int i) { return i + 1 < m && i < QK_SEG_BITS && ((parities >> (i & 1)) & 1) != 0 && qk_merge_admissible(rule, xd, yd, ek + i); };
+  auto plain_cost = [&](const int i) { return qk_step_instr(2, xd[ek + i], xd[ek + i + 1], yd[ek + i], yd[ek + i + 1], xt[ek + i], yt[ek + i]) + QK_STEP_PRICE; };
+  auto merged_cost = [&](const int i) { return qk_step_instr(4, xd[ek + i], xd[ek + i + 2], yd[ek + i], yd[ek + i + 2], xt[ek + i], yt[ek + i]) + QK_STEP_PRICE; };
+  QkSegMask take{{0ull, 0ull}};  // bit i: a step that starts at i is a merged one
+  if (greedy) {
+    for (int i = 0; i < m && i < QK_SEG_BITS; ++i)
+      if (may(i)) take.w[i >> 6] |= 1ull << (i & 63);
+  } else {
+    long long c1 = 0, c2 = 0;  // best cost of the sites [i + 1, m), [i + 2, m)
+    int s1 = 0, s2 = 0;        // and its steps
+    for (int i = m - 1; i >= 0; --i) {
+      long long c = plain_cost(i) + c1;
+      int s = s1 + 1;
+      if (may(i)) {
+        const long long cm = merged_cost(i) + c2;
+        const int sm = s2 + 1;
+        if (cm < c || (cm == c && (sm < s || (sm == s && (i & 1) == 0)))) c = cm, s = sm, take.w[i >> 6] |= 1ull << (i & 63);
+      }
+      c2 = c1, s2 = s1, c1 = c, s1 = s;
+    }
+  }
+  QkSegMask out{{0ull, 0ull}};
+  long long obj = 0;
+  int n_steps = 0;
+  for (int i = 0; i < m; ++n_steps) {
+    if (qk_seg_bit(take.w[0], take.w[1], i)) out.w[i >> 6] |= 1ull << (i & 63), obj += merged_cost(i), i += 2;
+    else obj += plain_cost(i), i += 1;
+  }
+  if (objective) *objective = obj;
+  if (steps) *steps = n_steps;
+  return out;
+}
+
 struct qk_ctx;
 
 struct qk_plan {
@@ -128,6 +209,10 @@ struct qk_plan {
   qk_ctx* up_ctx = nullptr;
   int32_t* d_pairs = nullptr;
   int32_t* d_groups = nullptr;
+  // the segmentation masks of this plan's pairs (qk_segment_chain; two words per pair), made on the device by the first Gram and kept
+  // while the sets, the run-time edge_k, the rule and the launches stay the same (seg_key; qkgram.hip: ensure_segments)
+  unsigned long long* d_seg = nullptr;
+  unsigned long long seg_key[8] = {0};
 };
 
 // ----------------------------------------------------------------------------------------
@@ -146,7 +231,7 @@ struct QkSweepPolicy {
   int fused_split = 1;     // sweep the plan's two runs of pairs with the two shapes of the site-fused kernel: 1 = when the share is long enough for two launches (default), 2 = always, 0 = one shape (QK_FUSED_SPLIT)
   int fused_wgs = 0;       // workgroups per CU of the site-fused sweep: 0 = chosen per launch from the plan, 1 / 2 forced (QK_FUSED_WGS)
   bool deterministic = false;  // QK_DETERMINISTIC=1: only kernels that add in a fixed order (no LDS atomics)
-  bool merge_sites = true;     // QK_MERGE (0 disables): the site-fused sweep walks the chain in merged steps of two sites (qk_device.h: SweepArgs.merge_steps)
+  int merge_mode = 2;          // QK_MERGE: the site-fused sweep walks the chain in merged steps of two sites (qk_segment_chain) -- 0 = never, 1 = every admissible merge of the fixed pairs (k + 2 t, k + 2 t + 1), 2 = at either parity, chosen per pair by dynamic programming
   bool fused_dual = true;      // QK_FUSED_DUAL (0: single tiles): the 12-wave site-fused shape in its dual form (pairs of tiles per wave)
   bool gang = false;           // QK_GANG=1: gang start of the site-fused launches (qk_device.h: qk_gang_sync)
 };
@@ -174,7 +259,7 @@ struct QkSweepChoice {
   int turn_ints = 0;                   // SweepArgs
   size_t scratch_bytes = 0;            // global X / T buffers of the launches
   bool interleaved = false;   // the sweep reads the sets' interleaved images
-  bool fused_images = false;  // ... and the site-fused sweep's edge blocks and merged steps (as far as the plan's edge_k and merge_sites ask)
+  bool fused_images = false;  // ... and the site-fused sweep's edge blocks and merged steps (as far as the plan's edge_k and merge_mode ask)
   int queues = 1;             // qk_stats.queues (8: the plan's XCD queues)
   bool tails = false;         // the launches record tail clocks
 };

@@ -189,7 +189,7 @@ static int choose_edge_k(const int n_sites, const int32_t* x_dims, const int32_t
   if (np == 0 || n_sites < 2 * KMIN + 2) return 0;
   const int stride = n_sites + 1;
   const int64_t step = std::max<int64_t>(1, np / 512);
-  const double over = 375.0;
+  const double over = QK_STEP_PRICE;  // (qk_plan.h: the price qk_segment_chain puts on a step)
   auto t16 = [](const int v) { return (double)((v + 15) / 16); };
   std::vector<double> total((size_t)KMAX + 1, 0.0);
   std::vector<double> site((size_t)n_sites);

@@ -177,6 +177,7 @@ extern "C" int qk_plan_destroy(qk_plan* plan) {
   if (!plan) return QK_OK;
   if (plan->d_pairs) (void)hipFree(plan->d_pairs);
   if (plan->d_groups) (void)hipFree(plan->d_groups);
+  if (plan->d_seg) (void)hipFree(plan->d_seg);
   delete plan;
   return QK_OK;
 }
@@ -267,14 +268,14 @@ __global__ __launch_bounds__(256) void qk_edge_kernel(const qk_v2d* __restrict__
   }
 }
 
-// Merged image of a set (SweepArgs.merge_steps; qk_fused.h): step t of state st = the chain's sites s = k + 2 t and s + 1 contracted over
-// the bond between them, M[l][2 p1 + p2][r] = sum_m A_s[l][p1][m] A_{s+1}[m][p2][r] (padded bonds; the padding of the image is zero,
-// so is M's).  A UNIT is one 16 x 16 block (tl, tr) of one step with its four physical combinations: the two fragments of A_s and the two
+// Merged image of a set (SweepArgs.merge_steps; qk_fused.h): task t of state st = the chain's sites s = k + stride t and s + 1 contracted
+// over the bond between them (stride 1: every start; 2: the even starts only), written at out_offs[st][s - k]:
+// M[l][2 p1 + p2][r] = sum_m A_s[l][p1][m] A_{s+1}[m][p2][r] (padded bonds; the padding of the image is zero, so is M's).  A UNIT is one 16 x 16 block (tl, tr) of one step with its four physical combinations: the two fragments of A_s and the two
 // of A_{s+1} of a k-step feed four complex products (12 matrix instructions per 4 loads), K up to the true bond between the sites.  Units
 // of all steps and states are numbered through a prefix table (unit_start) and dealt to the wavefronts of the grid, so the launch
 // does not end with the largest state.  Reads and writes interleaved complex.  Once per set: not part of a sweep.
 __global__ __launch_bounds__(256, 2) void qk_merge_kernel(const qk_v2d* __restrict__ il, const int32_t* __restrict__ dims, const int32_t* __restrict__ dtrue, const int64_t* __restrict__ offs,
-                                                          const int n_sites, const int k, const int steps, const long long n_tasks, const long long* __restrict__ unit_start,
+                                                          const int n_sites, const int k, const int steps, const int stride, const int n_starts, const long long n_tasks, const long long* __restrict__ unit_start,
                                                           qk_v2d* __restrict__ out, const int64_t* __restrict__ out_offs) {
   const int n1 = n_sites + 1, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, j = lane & 15, q = lane >> 4;
   const long long n_units = unit_start[n_tasks];
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(256, 2) void qk_merge_kernel(const qk_v2d* __restri
       else hi = mid;
     }
     const long long t = lo, st = t / steps;
-    const int step = (int)(t - st * steps), s_ = k + 2 * step, v = (int)(u - unit_start[t]);
+    const int step = (int)(t - st * steps), s_ = k + stride * step, v = (int)(u - unit_start[t]);
     const int32_t* d = dims + st * n1;
     const int lp = d[s_], mp = d[s_ + 1], rp = d[s_ + 2], ntr = rp >> 4, tl = v / ntr, tr = v - tl * ntr;
     (void)lp;
@@ -313,7 +314,7 @@ __global__ __launch_bounds__(256, 2) void qk_merge_kernel(const qk_v2d* __restri
       qkf_kstep<false>(acc[2][0], acc[2][1], acc[2][2], x1.x, x1.y, y0.x, y0.y);
       qkf_kstep<false>(acc[3][0], acc[3][1], acc[3][2], x1.x, x1.y, y1.x, y1.y);
     }
-    qk_v2d* const dst = out + (out_offs[t] >> 1);
+    qk_v2d* const dst = out + (out_offs[st * n_starts + stride * step] >> 1);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const v4d re = acc[c][0] - acc[c][1], im = acc[c][2] - acc[c][0] - acc[c][1];
@@ -321,6 +322,18 @@ __global__ __launch_bounds__(256, 2) void qk_merge_kernel(const qk_v2d* __restri
       for (int r = 0; r < 4; ++r) dst[(long)(4 * (tl * 16 + q + 4 * r) + c) * rp + tr * 16 + j] = (qk_v2d){re[r], im[r]};
     }
   }
+}
+
+// The segmentation masks of a launch's pairs (SweepArgs.seg; qk_plan.h: qk_segment_chain): one thread per pair.  Once per plan, sets and
+// launch shape (ensure_segments): not part of a steady-state sweep.
+__global__ __launch_bounds__(256) void qk_segment_kernel(const int32_t* __restrict__ xdims, const int32_t* __restrict__ xtrue, const int32_t* __restrict__ ydims, const int32_t* __restrict__ ytrue,
+                                                         const int n_sites, const int ek, const int32_t* __restrict__ pairs, const long long npairs, const QkSegRule rule, const int parities,
+                                                         const bool greedy, unsigned long long* __restrict__ seg) {
+  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npairs) return;
+  const long long xo = (long long)pairs[2 * p] * (n_sites + 1), yo = (long long)pairs[2 * p + 1] * (n_sites + 1);
+  const QkSegMask m = qk_segment_chain(xdims + xo, xtrue + xo, ydims + yo, ytrue + yo, n_sites, ek, rule, parities, greedy);
+  seg[2 * p] = m.w[0], seg[2 * p + 1] = m.w[1];
 }
 
 #ifdef QK_LAB
@@ -411,7 +424,7 @@ static int ctx_init(qk_ctx* c, int device_id, int num_cus) {
   if (const char* v = std::getenv("QK_WAVE")) p.wave_path = std::atoi(v) != 0;
   if (const char* v = std::getenv("QK_WAVE2")) p.wave2_path = std::atoi(v) != 0, p.wave2_ring = std::atoi(v) != 2;
   if (const char* v = std::getenv("QK_FUSED")) p.fused_path = std::atoi(v);
-  if (const char* v = std::getenv("QK_MERGE")) p.merge_sites = std::atoi(v) != 0;
+  if (const char* v = std::getenv("QK_MERGE")) p.merge_mode = std::max(0, std::min(2, std::atoi(v)));
   // QK_DETERMINISTIC=1: bit-reproducible Grams.  By default the site-fused sweep sums the tiles of a column with LDS atomics in arrival
   // order (two launches on the same inputs differ in the last bits, <= 9e-16); in this mode it takes its DET forms, which add in a fixed
   // order (qk_fused.h: qkf_turn_add); the ring sweep, the small-bond sweep and the one-wave sweeps add in a fixed order anyway.  The order
@@ -699,46 +712,57 @@ static int ensure_edges(qk_ctx* c, qk_mps_set* m, const int k) {
 }
 
 static void free_merged(qk_mps_set* m) {
-  m->d_mg.reset(), m->d_mg_offs.reset(), m->d_mg_units.reset(), m->mg_k = -1, m->mg_steps = 0, m->mg_bytes = 0;
+  m->d_mg.reset(), m->d_mg_offs.reset(), m->d_mg_units.reset(), m->mg_k = -1, m->mg_steps = 0, m->mg_stride = 0, m->mg_bytes = 0;
 }
 
-// the merged image of a set for a chain that starts `k` sites in (made once per set and k; fp64 sets; needs the interleaved image).
+// the merged image of a set for a chain that starts `k` sites in (made once per set and k; fp64 sets; needs the interleaved image):
+// every start (stride 1) or the even starts only (stride 2).  An image of every start serves a call that asks for the even ones; when
+// the image of every start does not fit the device, the set gets the even starts (the caller then restricts the segmentation to them).
 // Asynchronous like ensure_edges.
-static int ensure_merged(qk_ctx* c, qk_mps_set* m, const int k) {
-  if (m->d_mg && m->mg_k == k) return QK_OK;
+static int ensure_merged(qk_ctx* c, qk_mps_set* m, const int k, int stride) {
+  if (m->mg_full_failed) stride = 2;
+  if (m->d_mg && m->mg_k == k && m->mg_stride <= stride) return QK_OK;
   if (m->d_mg) HIP_TRY(hipStreamSynchronize(c->stream));
   free_merged(m);
-  const int n = m->n_sites, stride = n + 1, steps = (n - 2 * k) / 2;
-  if (steps < 1) return fail(QK_EINVAL, "ensure_merged: a chain of %d sites", n - 2 * k);
+  const int n = m->n_sites, n1 = n + 1, starts = n - 2 * k - 1;
+  if (starts < 1) return fail(QK_EINVAL, "ensure_merged: a chain of %d sites", n - 2 * k);
   std::vector<int64_t>& mo = m->h_mg_offs;
   std::vector<long long>& us = m->h_mg_units;
-  mo.assign((size_t)m->n_states * steps, 0);
-  us.assign((size_t)m->n_states * steps + 1, 0);
-  long long total = 0, units = 0;  // complex elements; 16 x 16 blocks (with their four physical combinations)
-  for (int s_ = 0; s_ < m->n_states; ++s_) {
-    const int32_t* d = m->dims_true.data() + (size_t)s_ * stride;
-    for (int t = 0; t < steps; ++t) {
-      const long long lp = pad16(d[k + 2 * t]), rp = pad16(d[k + 2 * t + 2]);
-      mo[(size_t)s_ * steps + t] = 2 * total;
-      us[(size_t)s_ * steps + t] = units;
-      total += 4ll * lp * rp;
-      units += (lp / 16) * (rp / 16);
-    }
-  }
-  us.back() = units;
   QkDevBuf ib, ob, ub;
-  HIP_TRY(ib.alloc((size_t)total * 2 * sizeof(double)));
+  int steps = 0;
+  long long total = 0, units = 0;  // complex elements; 16 x 16 blocks (with their four physical combinations)
+  for (;; stride = 2) {
+    steps = (starts + stride - 1) / stride;
+    mo.assign((size_t)m->n_states * starts, 0);
+    us.assign((size_t)m->n_states * steps + 1, 0);
+    total = units = 0;
+    for (int s_ = 0; s_ < m->n_states; ++s_) {
+      const int32_t* d = m->dims_true.data() + (size_t)s_ * n1;
+      for (int t = 0; t < steps; ++t) {
+        const long long lp = pad16(d[k + stride * t]), rp = pad16(d[k + stride * t + 2]);
+        mo[(size_t)s_ * starts + stride * t] = 2 * total;
+        us[(size_t)s_ * steps + t] = units;
+        total += 4ll * lp * rp;
+        units += (lp / 16) * (rp / 16);
+      }
+    }
+    us.back() = units;
+    if (ib.alloc((size_t)total * 2 * sizeof(double)) == hipSuccess) break;
+    (void)hipGetLastError();  // (the failed allocation's sticky error)
+    if (stride == 2) return fail(QK_EDEVICE, "ensure_merged: no device memory for %lld bytes of merged steps", total * 2 * (long long)sizeof(double));
+    m->mg_full_failed = true;
+  }
   HIP_TRY(ob.alloc(mo.size() * sizeof(int64_t)));
   HIP_TRY(ub.alloc(us.size() * sizeof(long long)));
   HIP_TRY(hipMemcpyAsync(ob.get(), mo.data(), mo.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(ub.get(), us.data(), us.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
   const long long tasks = (long long)m->n_states * steps;
   const unsigned grid = (unsigned)std::min<long long>((units + 3) / 4, 4ll * c->num_cus);  // 4 wavefronts per workgroup, two workgroups per SIMD row
-  qk_merge_kernel<<<dim3(grid), dim3(256), 0, c->stream>>>(m->d_il.get<qk_v2d>(), m->d_dims.get<int32_t>(), m->d_true.get<int32_t>(), m->d_offs.get<int64_t>(), n, k, steps, tasks, ub.get<long long>(),
-                                                          ib.get<qk_v2d>(), ob.get<int64_t>());
+  qk_merge_kernel<<<dim3(grid), dim3(256), 0, c->stream>>>(m->d_il.get<qk_v2d>(), m->d_dims.get<int32_t>(), m->d_true.get<int32_t>(), m->d_offs.get<int64_t>(), n, k, steps, stride, starts, tasks,
+                                                          ub.get<long long>(), ib.get<qk_v2d>(), ob.get<int64_t>());
   HIP_TRY(hipGetLastError());
   m->d_mg = std::move(ib), m->d_mg_offs = std::move(ob), m->d_mg_units = std::move(ub);
-  m->mg_k = k, m->mg_steps = steps, m->mg_bytes = total * 2 * (long long)sizeof(double);
+  m->mg_k = k, m->mg_steps = starts, m->mg_stride = stride, m->mg_bytes = total * 2 * (long long)sizeof(double);
   return QK_OK;
 }
 
@@ -746,7 +770,8 @@ static int ensure_plan_uploaded(qk_ctx* c, qk_plan* p) {
   if (p->d_pairs && p->up_ctx == c) return QK_OK;
   if (p->d_pairs) (void)hipFree(p->d_pairs);
   if (p->d_groups) (void)hipFree(p->d_groups);
-  p->d_pairs = nullptr, p->d_groups = nullptr, p->up_ctx = nullptr;
+  if (p->d_seg) (void)hipFree(p->d_seg);
+  p->d_pairs = nullptr, p->d_groups = nullptr, p->d_seg = nullptr, p->up_ctx = nullptr;
   if (p->pairs.empty()) return QK_OK;
   QkDevBuf pairs, groups;  // published together, once both copies are on the device (the plan keeps raw pointers: qk_plan.h has no HIP type)
   HIP_TRY(pairs.alloc(p->pairs.size() * sizeof(int32_t)));
@@ -758,7 +783,7 @@ static int ensure_plan_uploaded(qk_ctx* c, qk_plan* p) {
 }
 
 // the site-fused sweep's derived images of the two sets (edge blocks, merged steps) as the plan asks for them, into the launch's arguments
-static int derive_fused_images(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set* ys, const qk_plan* plan, const bool merge_sites, SweepArgs& a) {
+static int derive_fused_images(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set* ys, const qk_plan* plan, const int merge_mode, SweepArgs& a) {
   // the ends of the chain from the sets' edge blocks: k chosen by the planner -- unless a set already holds blocks for another k
   // (made for an earlier plan, e.g. the training Gram before the test Gram on the same X): any k gives the same overlaps and the
   // model's choices lie within 0.5 % of each other, so the set keeps the k of its first use instead of being rebuilt per call
@@ -770,9 +795,9 @@ static int derive_fused_images(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set
       if ((rc = ensure_edges(c, const_cast<qk_mps_set*>(m), ek)) != QK_OK) return rc;
     a.xedge = xs->d_edge.get<double>(), a.xedge_offs = xs->d_edge_offs.get<long long>(), a.yedge = ys->d_edge.get<double>(), a.yedge_offs = ys->d_edge_offs.get<long long>(), a.edge_k = ek;
   }
-  if (merge_sites && xs->n_sites - 2 * ek >= 2) {  // the chain's sites contracted in twos: a workgroup picks per pair and step
+  if (merge_mode > 0 && xs->n_sites - 2 * ek >= 2) {  // neighbouring sites of the chain contracted in twos: the pair's mask says which steps walk them (ensure_segments)
     for (const qk_mps_set* m : {xs, ys})
-      if ((rc = ensure_merged(c, const_cast<qk_mps_set*>(m), ek)) != QK_OK) return rc;
+      if ((rc = ensure_merged(c, const_cast<qk_mps_set*>(m), ek, merge_mode >= 2 ? 1 : 2)) != QK_OK) return rc;
     a.xmg = xs->d_mg.get<double>(), a.xmg_offs = xs->d_mg_offs.get<int64_t>(), a.ymg = ys->d_mg.get<double>(), a.ymg_offs = ys->d_mg_offs.get<int64_t>(), a.merge_steps = xs->mg_steps;
   }
 #ifdef QK_LAB  // TIMING EXPERIMENT (wrong results): every tensor read from the first MiB of its image -- what would perfect L2 hits buy?
@@ -792,6 +817,61 @@ static int derive_fused_images(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set
     }
   }
 #endif
+  return QK_OK;
+}
+
+// the shape of a site-fused launch as the segmentation sees it (cap 0: not a site-fused kernel)
+static QkSegRule seg_rule_of(const int kernel) {
+  switch (kernel) {
+    case QK_KERNEL_FUSED1: case QK_KERNEL_FUSED1_DET: return {QKF_XCAP_ONE, QKF_ONE_NW * QKF_ONE_S, false};
+    case QK_KERNEL_FUSED2: case QK_KERNEL_FUSED2_DET: return {QKF_XCAP_TWO, QKF_TWO_NW * QKF_TWO_S, false};
+#if QKF_QUAD
+    case QK_KERNEL_FUSED_DUAL: return {QKF_XCAP_ONE, QKF_QUAD_NW, true};
+#else
+    case QK_KERNEL_FUSED_DUAL: return {QKF_XCAP_ONE, QKF_DUAL_NW, true};
+#endif
+    case QK_KERNEL_FUSED_DUAL_DET: return {QKF_XCAP_ONE, QKF_DUAL_NW, true};
+    default: return {0, 0, false};
+  }
+}
+
+// the segmentation masks of the plan's pairs for the launches of `ch` (a.merge_steps > 0: the sets hold merged images for a.edge_k), into
+// a.seg.  Made on the sweep's stream by qk_segment_kernel, one launch per site-fused run with that run's shape, and kept in the plan: a
+// later call with the same sets, edge_k, rule and launches finds them there.
+static int ensure_segments(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set* ys, qk_plan* plan, const QkSweepChoice& ch, const int merge_mode, SweepArgs& a) {
+  const long long np = (long long)plan->pairs.size() / 2;
+  const bool both = merge_mode >= 2 && xs->mg_stride == 1 && ys->mg_stride == 1;  // else the even starts only: QK_MERGE=1, or a set without the image of every start
+  const unsigned long long key[8] = {1ull,
+                                     xs->uid,
+                                     ys->uid,
+                                     (unsigned long long)a.edge_k,
+                                     both ? 3ull : 1ull,
+                                     merge_mode == 1 ? 1ull : 0ull,
+                                     (unsigned long long)ch.run[0].kernel | ((unsigned long long)(ch.n_runs > 1 ? ch.run[1].kernel : 0) << 32),
+                                     (unsigned long long)ch.run[0].count};
+  if (plan->d_seg && std::equal(key, key + 8, plan->seg_key)) return a.seg = plan->d_seg, QK_OK;
+  if (plan->d_seg) {
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (a sweep may still read the old masks)
+    (void)hipFree(plan->d_seg), plan->d_seg = nullptr;
+  }
+  QkDevBuf seg;
+  HIP_TRY(seg.alloc((size_t)np * 2 * sizeof(unsigned long long)));
+  unsigned long long* const d = seg.get<unsigned long long>();
+  for (int i = 0; i < ch.n_runs; ++i) {
+    const QkSweepRun& r = ch.run[i];
+    const QkSegRule rule = seg_rule_of(r.kernel);
+    if (r.count <= 0) continue;
+    if (rule.cap == 0) {  // (the one-wave launch of a mixed sweep reads no mask)
+      HIP_TRY(hipMemsetAsync(d + 2 * r.first, 0, (size_t)r.count * 2 * sizeof(unsigned long long), c->stream));
+      continue;
+    }
+    qk_segment_kernel<<<dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, c->stream>>>(a.xdims, a.xtrue, a.ydims, a.ytrue, a.n_sites, a.edge_k, a.pairs + 2 * r.first, r.count, rule, both ? 3 : 1,
+                                                                                            merge_mode == 1, d + 2 * r.first);
+  }
+  HIP_TRY(hipGetLastError());
+  plan->d_seg = static_cast<unsigned long long*>(seg.release());
+  std::copy(key, key + 8, plan->seg_key);
+  a.seg = plan->d_seg;
   return QK_OK;
 }
 
@@ -874,7 +954,8 @@ extern "C" int qk_gram_values(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set*
       if ((rc = ensure_interleaved(c, const_cast<qk_mps_set*>(m))) != QK_OK) return rc;
     a.xdata = xs->d_il.get<double>(), a.ydata = ys->d_il.get<double>();
   }
-  if (ch.fused_images && (rc = derive_fused_images(c, xs, ys, plan, pol.merge_sites, a)) != QK_OK) return rc;
+  if (ch.fused_images && (rc = derive_fused_images(c, xs, ys, plan, pol.merge_mode, a)) != QK_OK) return rc;
+  if (a.merge_steps > 0 && (rc = ensure_segments(c, xs, ys, plan, ch, pol.merge_mode, a)) != QK_OK) return rc;
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
   for (int i = 0; i < ch.n_runs; ++i) {
     const QkSweepRun& r = ch.run[i];
@@ -882,7 +963,7 @@ extern "C" int qk_gram_values(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set*
     ar.npairs = r.count, ar.nq = r.nq, ar.gang_n = r.gang_n;
     if (i == 1) {  // the second class of pairs: its part of the list, and queue heads, tail clocks (and gang words) behind the first launch's
       HIP_TRY(hipEventRecord(c->ev_mid, c->stream));
-      ar.pairs = a.pairs + 2 * r.first, ar.values = a.values + r.first, ar.z = a.z ? a.z + 2 * r.first : nullptr;
+      ar.pairs = a.pairs + 2 * r.first, ar.values = a.values + r.first, ar.z = a.z ? a.z + 2 * r.first : nullptr, ar.seg = a.seg ? a.seg + 2 * r.first : nullptr;
       ar.counter = counter + 8 * QK_QSTRIDE, ar.tail = a.tail + 2;
       if (plan->nq > 1)
         for (int s_ = 0; s_ <= 8; ++s_) ar.qstart[s_] = plan->qstart[8 + s_] - r.first;

@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""What the segmentation of the site-fused sweep's chains executes, per launch of a bench config: steps and matrix instructions per
+pair with no merged steps (QK_MERGE=0), with every admissible merge of the fixed pairs (k + 2 t, k + 2 t + 1) (QK_MERGE=1) and with
+merges at either parity chosen per pair by dynamic programming (QK_MERGE=2, the default) -- and the device bytes of the merged images
+the last two need.
+
+The numbers come from the function the device runs (qk_segment_chain, csrc/qk_plan.h), compiled for the host from
+tools/segment_capi.cpp and called through ctypes, over ALL pairs of the config's real plan (the host planner: class split, orientation
+and edge_k as a Gram of the set gets them).  Matrix instructions as the kernels issue them: tiles of 16, K trimmed to the true bond in
+steps of 4, three real products per complex one; the edge products (the same under every rule) are listed beside the steps.
+
+    python tools/merge_potential.py [cfg4] [edge_k]     (CPU only; builds or loads the config's states like bench.py)
+"""
+import ctypes as C
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = {  # launch shape -> (elements of the LDS X buffer, units of one round, pairs of tiles per unit): csrc/qkgram.hip, seg_rule_of
+    "12-wave dual (XCAP 8192)": (8192, 12, 1),
+    "12-wave one-tile (XCAP 8192)": (8192, 24, 0),
+    "8-wave one-tile (XCAP 4608)": (4608, 8, 0),
+}
+_lib = None
+
+
+def segment_lib():
+    """The host build of tools/segment_capi.cpp (made once per process in a temporary directory)."""
+    global _lib
+    if _lib is None:
+        tmp = tempfile.mkdtemp(prefix="qk_segment_")
+        so = os.path.join(tmp, "libqksegment.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tools", "segment_capi.cpp")], check=True)
+        _lib = C.CDLL(so)
+        _lib.qk_segment_pairs.restype = None
+        _lib.qk_segment_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 3
+    return _lib
+
+
+def segment_pairs(x_true, y_true, pairs, ek, shape, parities, greedy):
+    """(masks [pairs][2] uint64, matrix instructions [pairs], steps [pairs]) of the pairs (x state, y state) under a launch shape."""
+    x_true = np.ascontiguousarray(x_true, dtype=np.int32)
+    y_true = np.ascontiguousarray(y_true, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    n = pairs.shape[0]
+    masks, instr, steps = np.zeros((n, 2), dtype=np.uint64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    xcap, cap, dual = SHAPES[shape]
+    segment_lib().qk_segment_pairs(x_true.ctypes.data, y_true.ctypes.data, x_true.shape[1] - 1, pairs.ctypes.data, n, int(ek), xcap, cap, dual, int(parities), int(bool(greedy)),
+                                   masks.ctypes.data, instr.ctypes.data, steps.ctypes.data)
+    return masks, instr, steps
+
+
+def merged_steps(masks):
+    """merged steps per pair: the bits of its mask"""
+    return np.array([bin(int(a)).count("1") + bin(int(b)).count("1") for a, b in masks])
+
+
+RULES = (("QK_MERGE=0", 0, True), ("QK_MERGE=1", 1, True), ("QK_MERGE=2", 3, False))  # name, allowed parities, every admissible merge / dynamic programme
+
+
+def main():
+    import bench
+    from qml_cutensornet_amd import engine
+
+    cfg = sys.argv[1] if len(sys.argv) > 1 else "cfg4"
+    n, reps, d, npts = bench.CONFIGS[cfg]
+    gamma = 0.1 if cfg == "cfg5" else 1.0
+    states, _ = bench.build_or_load_states(cfg, n, reps, d, gamma, npts, 5, 0, 1, os.cpu_count() or 1)
+    dims = np.array([m.bond_dims() for m in states], dtype=np.int32)
+    plan = engine.Plan(dims, None, 1, 0, 0, False)
+    pairs, n_first = plan.pairs(), plan.first_run
+    n_first = n_first() if callable(n_first) else n_first
+    ek = int(sys.argv[2]) if len(sys.argv) > 2 else plan.edge_sites
+    ek = ek() if callable(ek) else ek
+    np_ = pairs.shape[0]
+    print(f"{cfg}: {npts} states, {n} sites, max bond mean {dims.max(axis=1).mean():.1f} max {dims.max()}, {np_} pairs, first run {n_first}, edge_k {ek}")
+    p16 = lambda v: (v.astype(np.int64) + 15) // 16 * 16  # noqa: E731
+    pd = p16(dims)
+    starts = n - 2 * ek - 1
+    img = {1: sum(int((4 * pd[:, ek + s] * pd[:, ek + s + 2]).sum()) for s in range(starts)) * 16,
+           2: sum(int((4 * pd[:, ek + s] * pd[:, ek + s + 2]).sum()) for s in range(0, starts, 2)) * 16}
+    print(f"merged image of the set: even starts {img[2] / 2**30:.3f} GiB, every start {img[1] / 2**30:.3f} GiB (+{(img[1] - img[2]) / 2**30:.3f} GiB)")
+    if ek > 0:  # the two edge products of a pair: tiles(a) tiles(b) 2^k / 4 k-steps x 3, at either end
+        t = lambda v: (v.astype(np.int64) + 15) // 16  # noqa: E731
+        edge = 3 * (2**ek // 4) * (t(dims[pairs[:, 0], ek]) * t(dims[pairs[:, 1], ek]) + t(dims[pairs[:, 0], n - ek]) * t(dims[pairs[:, 1], n - ek]))
+    else:
+        edge = np.zeros(np_, dtype=np.int64)
+    split = 0 < n_first < np_
+    runs = [("12-wave dual (XCAP 8192)", slice(0, n_first)), ("8-wave one-tile (XCAP 4608)", slice(n_first, np_))] if split else [(s, slice(0, np_)) for s in SHAPES]
+    if not split:
+        print("(one class of pairs: every shape is listed over all pairs; the launch takes one of them)")
+    for shape, sl in runs:
+        print(f"{shape}: {pairs[sl].shape[0]} pairs, edge products {edge[sl].mean():.0f} matrix instructions per pair")
+        base = None
+        for name, par, greedy in RULES:
+            masks, instr, steps = segment_pairs(dims, dims, pairs[sl], ek, shape, par, greedy)
+            cost = instr.mean() + 375.0 * steps.mean()
+            if name == "QK_MERGE=1":
+                base = (instr.mean(), cost, (instr + edge[sl]).mean())
+            rel = "" if base is None or name == "QK_MERGE=1" else (f"  ({(instr.mean() / base[0] - 1) * 100:+.2f} % instr., {(cost / base[1] - 1) * 100:+.2f} % modelled cost, "
+                                                                   f"{((instr + edge[sl]).mean() / base[2] - 1) * 100:+.2f} % instr. with the edges, against QK_MERGE=1)")
+            odd = int(sum(bin(int(a) & 0xAAAAAAAAAAAAAAAA).count("1") + bin(int(b) & 0xAAAAAAAAAAAAAAAA).count("1") for a, b in masks))
+            print(f"  {name}: steps/pair {steps.mean():6.2f}  merged {merged_steps(masks).mean():6.2f} (odd starts {odd / masks.shape[0]:5.2f})  matrix instr./pair {instr.mean():9.0f}"
+                  f"  instr. + 375/step {cost:9.0f}{rel}")
+    plan.close()
+
+
+if __name__ == "__main__":
+    main()
