@@ -184,3 +184,70 @@ def environments(tensors):
 def capped_dims(n, caps):
     """The bond table [len(caps), n + 1] of capped chains (what the planner needs: no tensors)."""
     return np.array([[min(2 ** min(k, n - k), c) for k in range(n + 1)] for c in caps], dtype=np.int32)
+
+
+# ------------------------------------------------------------------ canary states: a hostile neighbour, a hostile history
+# (tests/test_gpu_canary.py on the GPU, tests/test_canary_host.py on the CPU).  A canary has the bond table of a clean state and NaN in
+# every tensor element.  Plans, kernel choice, tiling, segmentation, queues and batch cuts depend on the bond tables alone, so a run with
+# canaries walks the steps of the clean run: a result that involves no canary must be the clean run's, a result that involves one is NaN.
+CANARY = complex(float("nan"), float("nan"))
+CANARY_X_PERIOD, CANARY_Y_PERIOD, CANARY_Y_RESIDUE, CANARY_GRAM_PERIOD = 5, 3, 1, 5
+# the canaries among the six twins of ``gauge_sets`` (local sweeps): states 1 and 4 (PROFILES[1]: bonds up to 65, one of them scaled by
+# 3.7), and as a placement of its own state 3, which has the profile that reaches 128; of the two twins of ``gauge_set_300`` the first
+LOCAL_CANARY_PLACEMENTS = {"1-4": (1, 4), "3": (3,)}
+LOCAL_CANARIES_300 = (0,)
+
+
+def canary_copy(mps):
+    """A state of the same shapes with nan + 1j nan in every element."""
+    import qml_cutensornet_amd as Q
+
+    return Q.MPS([np.full(np.shape(t), CANARY, dtype=np.complex128) for t in mps.tensors])
+
+
+def canary_indices(n_states, caps, period, residue=2):
+    """The states of a set that become canaries: i % period == residue, never the first or the last state (the duplicates of the
+    many-pairs sets stay clean), and the first inner state of the set's largest cap if none of the chosen has it."""
+    caps = [int(c) for c in caps]
+    assert len(caps) == n_states >= 3
+    idx = [i for i in range(1, n_states - 1) if i % period == residue]
+    big = max(caps)
+    if not any(caps[i] == big for i in idx):
+        idx.append(next(i for i in range(1, n_states - 1) if caps[i] == big))
+    return sorted(idx)
+
+
+def with_canaries(states, idx):
+    """The list ``states`` with the entries ``idx`` replaced by their canary copies (the other entries are the same objects)."""
+    idx = set(int(i) for i in idx)
+    assert all(0 <= i < len(states) for i in idx)
+    return [canary_copy(m) if i in idx else m for i, m in enumerate(states)]
+
+
+def many_pair_canaries(name):
+    """(x indices, y indices) of the canaries of MANY_PAIR_SETS[name]."""
+    cx, cy = many_pair_caps(name)
+    return canary_indices(len(cx), cx, CANARY_X_PERIOD), canary_indices(len(cy), cy, CANARY_Y_PERIOD, CANARY_Y_RESIDUE)
+
+
+def many_pair_symmetric_canaries(name):
+    """The canaries of ``many_pair_symmetric(name, xs, ys)``: those of xs, and those of ys among the states it takes."""
+    cx, cy = many_pair_caps(name)
+    ix, iy = many_pair_canaries(name)
+    ns = len(many_pair_symmetric(name, list(range(len(cx))), list(range(len(cy)))))
+    return ix + [len(cx) + j for j in iy if len(cx) + j < ns]
+
+
+def many_pair_gram_canaries(name):
+    """The canaries of MANY_PAIR_GRAMS[name]: period 5 and a state of the largest cap."""
+    caps = many_pair_gram_caps(name)
+    return canary_indices(len(caps), caps, CANARY_GRAM_PERIOD)
+
+
+def canary_pair_mask(nx, ix, ny=None, iy=None):
+    """bool [ny, nx]: entry (j, i) involves a canary (row j = y state, or x state of a symmetric set; column i = x state)."""
+    sym = ny is None
+    m = np.zeros((nx if sym else ny, nx), dtype=bool)
+    m[:, list(ix)] = True
+    m[list(ix if sym else iy), :] = True
+    return m
