@@ -240,7 +240,11 @@ int qk_plan_cost(const qk_plan* plan, double* plan_ms, int32_t* threads, double*
  * padded work than the two sites; among the admissible segmentations the one with the fewest executed matrix instructions plus a fixed
  * price per step is taken (QK_MERGE=1: every admissible merge of the fixed pairs (k + 2 t, k + 2 t + 1)).  A merged step neither pads
  * its middle bond to 16 nor walks it, and saves the barriers, set-ups and stream turn-arounds of a step; again a host-prepared choice of
- * the contraction order (reference call site G:380).  qk_stats' algorithmic flops and bytes stay those of the plain chain.          */
+ * the contraction order (reference call site G:380).  qk_stats' algorithmic flops and bytes stay those of the plain chain.
+ * THE ASSOCIATION OF A STEP (QK_ASSOC=0 disables, 1 = default; with QK_MERGE=2): the same programme also chooses, per step, whether the
+ * step contracts the y tensor first (T = X^T B, X' = T^T conj(A)) or, with the two states exchanged, the x tensor first on W = X^H; a
+ * second mask of 128 bits per pair holds the choice.  A step may end with a switch only where it is LDS-resident (its phase 2 then leaves
+ * X'^H), at QK_SWITCH_PRICE matrix instructions' worth.  Results are those of the plain chain; QK_DETERMINISTIC=1 keeps "y first".   */
 
 /* ---- the hot path -----------------------------------------------------------
  * qk_gram_values: for every pair p of the plan compute z_p = <x_i|y_j> and write

@@ -44,9 +44,12 @@ struct SweepArgs {
   // MERGED STEPS (site-fused sweep; seg = null: none): xmg / ymg hold, per state, neighbouring sites of the chain [edge_k, n - edge_k)
   // contracted in twos -- tensors [l][4][r], physical index 2 p1 + p2, interleaved complex; the tensor of the sites s, s + 1 lies at
   // offset (doubles) x/ymg_offs[state][merge_steps] entry s - edge_k, merge_steps = n - 2 edge_k - 1 (an image of the even starts only
-  // leaves the odd entries unused).  seg[2 pair], seg[2 pair + 1]: the pair's segmentation mask (qk_plan.h: qk_segment_chain, made per
+  // leaves the odd entries unused).  seg[4 pair], seg[4 pair + 1]: the pair's segmentation mask (qk_plan.h: qk_segment_chain, made per
   // launch by qk_segment_kernel) -- bit i set = the step at site edge_k + i walks the merged tensor (half the barriers, set-ups and load
-  // latencies, and the middle bond neither padded nor walked), else the plain site (qk_fused.h: qkf_step_table).
+  // latencies, and the middle bond neither padded nor walked), else the plain site (qk_fused.h: qkf_step_table).  seg[4 pair + 2],
+  // seg[4 pair + 3]: the orientations -- bit i set = that step runs with the two states exchanged ("A first", on X^H), bit n - 2 edge_k =
+  // the orientation the chain ends in; a step whose successor bit differs ends with a switch (qk_fused.h: qkf_p2_switch).  All zero for
+  // a launch whose kernel has no switch step.
   const double* xmg;
   const double* ymg;
   const int64_t* xmg_offs;

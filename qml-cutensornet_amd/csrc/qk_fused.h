@@ -41,7 +41,10 @@
 //   * the chain is walked in STEPS: the first and last k sites of both states come as edge blocks (one product each), a step in
 //     between is one site or two neighbouring sites contracted into one tensor of physical dimension 4 (merged image of the set),
 //     as the pair's segmentation mask says (qk_plan.h: qk_segment_chain, made once per plan by qk_segment_kernel); per-step control
-//     is a 48-byte record, the step table of the pair, built by all threads at pair set-up (qkf_step_table).
+//     is a 48-byte record, the step table of the pair, built by all threads at pair set-up (qkf_step_table);
+//   * every step has an ORIENTATION, chosen with the segmentation: 0 = as written above ("B first"), 1 = the two states exchanged, the
+//     same code working on W = X^H ("A first").  A step that is followed by one of the other orientation ends with a SWITCH: its phase 2
+//     runs with the source operands of the matrix instructions exchanged and leaves X'^H (qkf_p2_switch; plain forms only).
 // Two launch shapes (chosen per launch -- or per run of pairs of a split plan -- in qkgram.hip): one 12-wave workgroup per CU
 // (three waves per SIMD at 168 VGPRs, two tiles per wave) with an 8192-element X buffer -- by default in its DUAL form
 // (qk_sweep_fused_dual_kernel below: the two tiles of a wave share the rows of X and of A, so every A and X fragment feeds
@@ -367,6 +370,69 @@ __device__ __forceinline__ void qkf_p2_item(const QkfTile& t, v2d (&fr)[4], cons
   }
 }
 
+// Phase 2 of a SWITCH step (qk_plan.h: the association of a step): the chain goes on in the other orientation, so the step leaves
+// X'^H instead of X'.  On v_mfma_f64_16x16x4_f64 the A and the B operand have the same lane layout (lane (q, j) holds [k = q][m or n = j]),
+// so the two source operands of every matrix instruction are EXCHANGED -- the fragment of A_k is the A operand, the T tile the B operand --
+// and the accumulators hold the tile [a' of block tn][b' of block tb] of X'^T in the usual C layout.  It goes to block (tn, tb) of the
+// output in the other orientation's panels (16 columns of b', a2 rows: the caller's `d` points at block tb's panel, a block of rows tn is
+// QKF_XBLOCK elements further on, the second tile of a pair `d1off` doubles = one panel) with the ordinary in-tile lane pattern.  The
+// conjugation moves from A to T and rides on the per-tile sums of T:  X'^H = conj(T)^T A,
+//     k1 = sum tr (Ar + Ai),   re = k1 + sum (ti - tr) Ai,   im = k1 + sum (-tr - ti) Ar
+// -- one operand sum per fragment element, the registers of T's imaginary part and of tr + ti become ti - tr and -tr - ti.  It is ONE
+// simple loop, that of the ordered forms: three chains per tile and k-step, the registers of a k-step reloaded behind them, the sums
+// k1 + . taken behind the block, the last block reloading from `nxt`, no specialisation for full blocks; `lim` as in qkf_p2_item (4 in the
+// dual kernel, whose streams load whole groups).  It hands fr to the next unit exactly as the tuned loops do.  On the headline set a
+// fifth of the steps take it; its tuned form (chains started on k1) is the open item of lab/NOTES_r09.md.
+template <bool HAS1>
+__device__ __forceinline__ void qkf_p2_switch(const QkfTile& t0, const QkfTile& t1, v2d (&fr)[4], const bool primed, QkfStream cur, const int lim, const int nn, const int kmax,
+                                              __attribute__((address_space(3))) double* d, const int d1off, const QkfStream nxt) {
+  if (!primed) qkf_load4(fr, cur);
+  const v4d dm0 = t0.im - t0.re, ng0 = -t0.re - t0.im, dm1 = HAS1 ? t1.im - t1.re : dm0, ng1 = HAS1 ? -t1.re - t1.im : ng0;
+#pragma unroll 1
+  for (int tn = 0; tn < nn; ++tn) {
+    v4d p1 = {0, 0, 0, 0}, p2 = {0, 0, 0, 0}, p3 = {0, 0, 0, 0}, r1 = {0, 0, 0, 0}, r2 = {0, 0, 0, 0}, r3 = {0, 0, 0, 0};
+    const bool fin = tn + 1 == nn;
+    const v2d* const rb = fin ? nxt.base : cur.base;
+    const int rs = fin ? nxt.step : cur.step, rl = fin ? nxt.lim : lim;
+    cur.off = fin ? nxt.off : cur.off + TILE;
+    QKF_PRIO_LO();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (i < kmax) {
+        const double sa = QKF_SUM(fr[i].x, fr[i].y);
+        p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(sa, t0.re[i], p1, 0, 0, 0);
+        p2 = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[i].y, dm0[i], p2, 0, 0, 0);
+        p3 = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[i].x, ng0[i], p3, 0, 0, 0);
+        if (HAS1) {
+          r1 = __builtin_amdgcn_mfma_f64_16x16x4f64(sa, t1.re[i], r1, 0, 0, 0);
+          r2 = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[i].y, dm1[i], r2, 0, 0, 0);
+          r3 = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[i].x, ng1[i], r3, 0, 0, 0);
+        }
+      }
+      fr[i] = qkf_ldg_a(qkf_kbase(rb, rs, i, rl), cur.off);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    QKF_PRIO_HI();
+    {
+      const v4d re = p1 + p2, im = p1 + p3;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        __hip_atomic_fetch_add(d + r * 2 * QKF_XSTEP, re[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(d + r * 2 * QKF_XSTEP + 1, im[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+    if (HAS1) {
+      const v4d re = r1 + r2, im = r1 + r3;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        __hip_atomic_fetch_add(d + d1off + r * 2 * QKF_XSTEP, re[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(d + d1off + r * 2 * QKF_XSTEP + 1, im[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+    d += 2 * QKF_XBLOCK;  // the next block of rows of a'
+  }
+}
+
 // The T tiles of a wave live in registers, S slots.  The slot loops are NOT unrolled (unrolled, every slot drags ~50
 // VGPRs of hoisted address state through the whole sweep) and the working slot is always T[S-1]: when a round gives
 // the waves up to L > 1 items each, the last L slots are turned by one before each item (phase 1 makes all L turns, so
@@ -512,9 +578,10 @@ __device__ __forceinline__ QkEdgeUnit qkf_edge_unit_of(const int u, const int mt
 // 16 columns to LDS (`xl`) or, when it does not fit, to the global X buffer (`xg`); units dealt round-robin to the NW wavefronts.
 template <int NW, bool PAIRS, int SETS>
 __device__ __forceinline__ void qkf_edge_prefix(const SweepArgs& g, const int xi, const int yj, const int a, const int b, lds_v2d* const xl, v2d* const xg, const bool to_global, const int wave,
-                                                const int q, const int j) {
-  const v2d* const Lx = reinterpret_cast<const v2d*>(g.xedge) + qkf_uniform(g.xedge_offs[2 * (long long)xi]);
-  const v2d* const Ly = reinterpret_cast<const v2d*>(g.yedge) + qkf_uniform(g.yedge_offs[2 * (long long)yj]);
+                                                const int q, const int j, const bool swap = false) {
+  // (swap: a chain that starts in orientation 1 -- xi is then a state of the y set and yj one of the x set, a / b their bonds)
+  const v2d* const Lx = reinterpret_cast<const v2d*>(swap ? g.yedge : g.xedge) + qkf_uniform((swap ? g.yedge_offs : g.xedge_offs)[2 * (long long)xi]);
+  const v2d* const Ly = reinterpret_cast<const v2d*>(swap ? g.xedge : g.yedge) + qkf_uniform((swap ? g.xedge_offs : g.yedge_offs)[2 * (long long)yj]);
   const int mt = a / TILE, nt = b / TILE, ng = (1 << g.edge_k) >> 4, inv = qk_recip20(mt), units = PAIRS ? qk_edge_units(mt, nt, NW) : mt * nt;  // (K = 2^k >= 16)
   for (int u = wave; u < units; u += NW) {
     const QkEdgeUnit un = qkf_edge_unit_of<NW, PAIRS>(u, mt, nt, inv);
@@ -547,9 +614,10 @@ __device__ __forceinline__ void qkf_edge_prefix(const SweepArgs& g, const int xi
 // wavefront order behind a barrier.  Which tiles a wavefront takes is a pure function of the shape (qk_edge_unit), so the sum is reproducible.
 template <int NW, bool PAIRS, int SETS>
 __device__ __forceinline__ void qkf_edge_suffix(const SweepArgs& g, const int xi, const int yj, const int a, const int b, const lds_v2d* const xl, const v2d* const xg, const bool from_global,
-                                                __attribute__((address_space(3))) double* zacc, const int wave, const int q, const int j) {
-  const v2d* const Rx = reinterpret_cast<const v2d*>(g.xedge) + qkf_uniform(g.xedge_offs[2 * (long long)xi + 1]);
-  const v2d* const Ry = reinterpret_cast<const v2d*>(g.yedge) + qkf_uniform(g.yedge_offs[2 * (long long)yj + 1]);
+                                                __attribute__((address_space(3))) double* zacc, const int wave, const int q, const int j, const bool swap = false) {
+  // (swap: a chain that ends in orientation 1, as in qkf_edge_prefix; the sum is then conj(z))
+  const v2d* const Rx = reinterpret_cast<const v2d*>(swap ? g.yedge : g.xedge) + qkf_uniform((swap ? g.yedge_offs : g.xedge_offs)[2 * (long long)xi + 1]);
+  const v2d* const Ry = reinterpret_cast<const v2d*>(swap ? g.xedge : g.yedge) + qkf_uniform((swap ? g.xedge_offs : g.yedge_offs)[2 * (long long)yj + 1]);
   const int mt = a / TILE, nt = b / TILE, ng = (1 << g.edge_k) >> 4, inv = qk_recip20(mt), units = PAIRS ? qk_edge_units(mt, nt, NW) : mt * nt;
   double zr = 0, zi = 0;
   for (int u = wave; u < units; u += NW) {
@@ -581,14 +649,14 @@ __device__ __forceinline__ void qkf_edge_suffix(const SweepArgs& g, const int xi
 // What a site needs: bonds, tile counts, where its X / X' live and how its items are cut into strips.
 struct QkfSite {
   int a, a2, b, b2, at, nks, mt, nt, nn, W, inv, inv2, pd, ps, next;  // inv2 = the two reciprocals of the strips' column units (qk_unit_recips); next = the table entry of the step after this one; pd = physical dimension of the step (2, or 4 for two merged sites), ps = log2 pd; inv = ceil(2^20 / mt): u / mt == (u * inv) >> 20 for u < 2048, mt <= 32 (checked exhaustively)
-  bool small;
+  bool small, sw;  // sw: the step ends with a switch of orientation (qkf_p2_switch)
   const v2d *Ak, *Bk;
 };
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4i lds_v4i;
 
 // The step table of a pair, built by all threads at pair set-up: per step 12 ints (48 bytes)
-//   [0] a  [1] a2  [2] b  [3] b2  [4] true a  [5] k-steps of b  [6] W  [7] small  [8] ceil(2^20 / mt)  [9] log2 pd  [10] next step
+//   [0] a  [1] a2  [2] b  [3] b2  [4] true a  [5] k-steps of b  [6] W  [7] small | orientation << 1 | switch << 2  [8] ceil(2^20 / mt)  [9] log2 pd  [10] next step
 //   [11] ITEM_RECIPS (the one-tile kernel's order of items): ceil(2^15 / column blocks) of a full strip | of the last strip << 16 (qk_unit_recips)
 // and the addresses of the step's two tensors ([a][pd][a2] of x, [b][pd][b2] of y) in a second table.  A step is one site (pd = 2,
 // entry = the site's index, next = + 1) or, with a merged image, two sites contracted into one tensor of physical dimension 4 (entry =
@@ -597,6 +665,9 @@ typedef __attribute__((address_space(3))) v4i lds_v4i;
 // have been padded.  Which steps are merged is the pair's segmentation mask (SweepArgs.seg; qk_plan.h: qk_segment_chain, where the rule
 // lives): one thread per site, a site whose bit is set writes the merged entry, any other site the plain one (the second site of a
 // merged step is then never visited).  `rule`: the launch's shape, as the mask was made with -- here it tells the LDS-resident steps.
+// The pair's second mask holds the ORIENTATION of every step (qk_plan.h: the association of a step): a step in orientation 1 gets the
+// record of the exchanged states (qk_step_record) and its two tensor offsets exchanged -- still offsets from xdata and ydata --, and a
+// step whose successor has the other orientation is flagged as a switch step (qkf_p2_switch).
 template <int XCAP, int NT, bool ITEM_RECIPS = false>
 __device__ __forceinline__ void qkf_step_table(const SweepArgs& g, const int xi, const int yj, const long long pair, lds_v4i* const rec, long long* const m_off, const int tid, const QkSegRule rule) {
   const int ns = g.n_sites, n1 = ns + 1;
@@ -606,36 +677,38 @@ __device__ __forceinline__ void qkf_step_table(const SweepArgs& g, const int xi,
   const int32_t* const yt = g.ytrue + (long long)yj * n1;
   const v2d* const xdata = reinterpret_cast<const v2d*>(g.xdata);
   const v2d* const ydata = reinterpret_cast<const v2d*>(g.ydata);
-  auto put = [&](const int e, const int a, const int a2, const int b, const int b2, const int ps, const int next, const bool small, const v2d* const A, const v2d* const B)
-                 __attribute__((always_inline)) {
-    const int mt = a / TILE, nt = b2 / TILE;
-    const int W = small ? nt : max(1, min(nt, XCAP / (TILE * a2)));  // X' in strips of W blocks of b' (the strip's rows must fit the LDS)
-    rec[3 * e] = (v4i){a, a2, b, b2};
-    rec[3 * e + 1] = (v4i){xt[e], (yt[e] + 3) >> 2, W, small ? 1 : 0};
-    rec[3 * e + 2] = (v4i){qk_recip20(mt), ps, next, ITEM_RECIPS ? qk_unit_recips(nt, W, false) : 0};
+  // the record (qk_plan.h: qk_step_record) and the step's two tensors: X of the state that plays x, Y of the one that plays y -- exchanged in
+  // orientation 1, where the first offset still counts from xdata and the second from ydata
+  auto put = [&](const int e, const int len, const int o, const bool sw, const v2d* const X, const v2d* const Y) __attribute__((always_inline)) {
+    const QkStepRec r = qk_step_record(xd, xt, yd, yt, e, len, o, sw, rule, ITEM_RECIPS);
+    rec[3 * e] = (v4i){r.w[0], r.w[1], r.w[2], r.w[3]};
+    rec[3 * e + 1] = (v4i){r.w[4], r.w[5], r.w[6], r.w[7]};
+    rec[3 * e + 2] = (v4i){r.w[8], r.w[9], r.w[10], r.w[11]};
     // (as element offsets from the sets' plain images, whatever buffer the tensor lives in: the kernels add them to their pointer
     //  ARGUMENTS, which keeps the fragment loads global_load -- an address that comes out of the table as an integer makes them
     //  flat_load, whose waits cover the LDS counter as well)
-    m_off[2 * e] = (long long)(((const char*)A - (const char*)xdata) / 16);
-    m_off[2 * e + 1] = (long long)(((const char*)B - (const char*)ydata) / 16);
+    m_off[2 * e] = (long long)(((const char*)(o ? Y : X) - (const char*)xdata) / 16);
+    m_off[2 * e + 1] = (long long)(((const char*)(o ? X : Y) - (const char*)ydata) / 16);
   };
-  auto plain = [&](const int e, const int next) __attribute__((always_inline)) {
-    const int a = xd[e], a2 = xd[e + 1], b = yd[e], b2 = yd[e + 1];
-    put(e, a, a2, b, b2, 1, next, qk_seg_small(rule, a, a2, b, b2, 2), xdata + (g.xoffs[(long long)xi * ns + e] >> 1), ydata + (g.yoffs[(long long)yj * ns + e] >> 1));
+  auto plain = [&](const int e, const int o, const bool sw) __attribute__((always_inline)) {
+    put(e, 1, o, sw, xdata + (g.xoffs[(long long)xi * ns + e] >> 1), ydata + (g.yoffs[(long long)yj * ns + e] >> 1));
   };
   if (g.seg == nullptr) {
-    for (int e = tid; e < ns; e += NT) plain(e, e + 1);
+    for (int e = tid; e < ns; e += NT) plain(e, 0, false);
     return;
   }
   const int ek = g.edge_k, k_hi = ns - ek;
-  const unsigned long long w0 = g.seg[2 * pair], w1 = g.seg[2 * pair + 1];
+  // the pair's four words: the merges, then the orientations (all zero for a launch whose kernel has no switch step)
+  const unsigned long long w0 = g.seg[4 * pair], w1 = g.seg[4 * pair + 1], o0 = g.seg[4 * pair + 2], o1 = g.seg[4 * pair + 3];
   for (int e = ek + tid; e < k_hi; e += NT) {
     const int i = e - ek;
-    if (qk_seg_bit(w0, w1, i) && e + 1 < k_hi) {
-      const int a = xd[e], a2 = xd[e + 2], b = yd[e], b2 = yd[e + 2];
-      put(e, a, a2, b, b2, 2, e + 2, qk_seg_small(rule, a, a2, b, b2, 4), reinterpret_cast<const v2d*>(g.xmg) + (g.xmg_offs[(long long)xi * g.merge_steps + i] >> 1),
+    const bool merged = qk_seg_bit(w0, w1, i) && e + 1 < k_hi;
+    const int len = merged ? 2 : 1, o = qk_seg_bit(o0, o1, i) ? 1 : 0;
+    const bool sw = qk_seg_bit(o0, o1, i + len) != (o != 0);  // the successor (or the chain's end) has the other orientation
+    if (merged)
+      put(e, 2, o, sw, reinterpret_cast<const v2d*>(g.xmg) + (g.xmg_offs[(long long)xi * g.merge_steps + i] >> 1),
           reinterpret_cast<const v2d*>(g.ymg) + (g.ymg_offs[(long long)yj * g.merge_steps + i] >> 1));
-    } else plain(e, e + 1);
+    else plain(e, o, sw);
   }
 }
 
@@ -703,7 +776,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
     const v4i r0 = rec[3 * k], r1 = rec[3 * k + 1], r2 = rec[3 * k + 2];  // every lane reads the same 48 bytes
     QkfSite s;
     s.a = rfl(r0.x), s.a2 = rfl(r0.y), s.b = rfl(r0.z), s.b2 = rfl(r0.w);
-    s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.small = rfl(r1.w) != 0;
+    s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.small = (rfl(r1.w) & QK_REC_SMALL) != 0, s.sw = (rfl(r1.w) & QK_REC_SWITCH) != 0;
     s.inv = rfl(r2.x), s.inv2 = rfl(r2.w);
     s.ps = rfl(r2.y), s.pd = 1 << s.ps, s.next = rfl(r2.z);
     s.mt = s.a / TILE, s.nt = s.b2 / TILE, s.nn = s.a2 / TILE;
@@ -756,9 +829,10 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
     int cur = 0, xb = 0;
     if (edges) {  // X behind the left edge: one product of the two left blocks
       const v4i r0 = rec[3 * ek];
-      const int a_e = rfl(r0.x), b_e = rfl(r0.z);
+      const int a_e = rfl(r0.x), b_e = rfl(r0.z);  // (of a chain that starts in orientation 1: the record of the exchanged states)
+      const bool o1 = !DET && (rfl(rec[3 * ek + 1].w) & QK_REC_ORIENT) != 0;  // (the ordered forms run orientation 0 throughout)
       xg = a_e * b_e > XCAP;
-      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, xi, yj, a_e, b_e, XL, G0, xg, wave, q, j);
+      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o1 ? yj : xi, o1 ? xi : yj, a_e, b_e, XL, G0, xg, wave, q, j, o1);
       __syncthreads();
     }
     QKF_STAMP(0);  // pair set-up
@@ -850,7 +924,9 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
             const QkfStream nxt = more ? a_stream(sc, w, it + NW) : chain ? b_stream(sn, 0, wn, wave) : a_stream(sc, w, it);
             const int tix = sc.pd * ta + un.p;  // (ordered form) this contribution's place in the order of its block of rows
             const QkfTurn turn{tcur + tbl * sc.nn, tix, tbroken, g.err};
-            if (kmax == 4) qkf_p2_item<true, DET>(T[S - 1], fr, primed, a_stream(sc, w, it), w * QKF_XBLOCK, sc.nn, 4, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
+            if (!DET && sc.sw)  // the step ends with a switch: the tile of X'^H, to block tbl's panel of the other orientation (LDS-resident: w = nt)
+              qkf_p2_switch<false>(T[S - 1], T[S - 1], fr, primed, a_stream(sc, w, it), kmax, sc.nn, kmax, (__attribute__((address_space(3))) double*)(XL + ob + tbl * (a2 * TILE) + q * TILE + j), 0, nxt);
+            else if (kmax == 4) qkf_p2_item<true, DET>(T[S - 1], fr, primed, a_stream(sc, w, it), w * QKF_XBLOCK, sc.nn, 4, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
             else qkf_p2_item<false, DET>(T[S - 1], fr, primed, a_stream(sc, w, it), w * QKF_XBLOCK, sc.nn, kmax, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
             primed = more || chain;
           }
@@ -873,10 +949,14 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
         xb = ob;
       }
     }
+    // the orientation the chain ends in: that of its last step (whose second site, if it is a merged one, carries the same flags), switched once more if that step switches
+    const int fl_end = DET ? 0 : rfl(rec[3 * (k_hi - 1) + 1].w);
+    const bool sw_end = (fl_end & QK_REC_SWITCH) != 0, o_end = ((fl_end & QK_REC_ORIENT) != 0) != sw_end;
     if (edges) {  // the overlap: X against the product of the two right blocks
       const v4i r0 = rec[3 * (k_hi - 1)];
-      const int a_e = rfl(r0.y), b_e = rfl(r0.w);
-      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, xi, yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), xg, zacc, wave, q, j);
+      const int a_l = rfl(r0.y), b_l = rfl(r0.w), a_e = sw_end ? b_l : a_l, b_e = sw_end ? a_l : b_l;  // (the last record is in the last step's orientation)
+      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o_end ? yj : xi, o_end ? xi : yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), xg, zacc, wave,
+                                                                   q, j, o_end);
       __syncthreads();
     }
     if (tid == 0) {
@@ -884,6 +964,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
       if (edges)
         for (int w_ = 0; w_ < NW; ++w_) zz.x += zacc[2 * w_], zz.y += zacc[2 * w_ + 1];
       else zz = xg ? G0[(long long)cur * g.x_plane] : (v2d)XL[xb];
+      if (o_end) zz.y = -zz.y;  // a chain that ends in orientation 1 yields conj(z)
       g.values[p] = zz.x * zz.x + zz.y * zz.y;
       if (g.z) {
         g.z[2 * p] = zz.x;
@@ -1139,7 +1220,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
     const v4i r0 = rec[3 * k], r1 = rec[3 * k + 1], r2 = rec[3 * k + 2];
     QkfSite s;
     s.a = rfl(r0.x), s.a2 = rfl(r0.y), s.b = rfl(r0.z), s.b2 = rfl(r0.w);
-    s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.small = rfl(r1.w) != 0;
+    s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.small = (rfl(r1.w) & QK_REC_SMALL) != 0, s.sw = (rfl(r1.w) & QK_REC_SWITCH) != 0;
     s.inv = rfl(r2.x);
     s.ps = rfl(r2.y), s.pd = 1 << s.ps, s.next = rfl(r2.z);
     s.mt = s.a / TILE, s.nt = s.b2 / TILE, s.nn = s.a2 / TILE;
@@ -1216,9 +1297,10 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
     int cur = 0, xb = 0;
     if (edges) {  // X behind the left edge: one product of the two left blocks
       const v4i r0 = rec[3 * ek];
-      const int a_e = rfl(r0.x), b_e = rfl(r0.z);
+      const int a_e = rfl(r0.x), b_e = rfl(r0.z);  // (of a chain that starts in orientation 1: the record of the exchanged states)
+      const bool o1 = !DET && (rfl(rec[3 * ek + 1].w) & QK_REC_ORIENT) != 0;  // (the ordered form runs orientation 0 throughout)
       xg = a_e * b_e > XCAP;
-      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, xi, yj, a_e, b_e, XL, G0, xg, wave, q, j);
+      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o1 ? yj : xi, o1 ? xi : yj, a_e, b_e, XL, G0, xg, wave, q, j, o1);
       __syncthreads();
     }
     QKF_STAMP(0);  // pair set-up (queue, step table, left edge)
@@ -1306,7 +1388,11 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
             lds_v2d* const xo = XL + ob + (2 * tp + un.half) * QKF_XBLOCK;
             // the turn counters of this block of rows and this contribution's place in their order
             const QkfTurn tp_turn{tcur + (2 * tp + un.half) * sc.nn, sc.pd * ta + pr.p, tbroken, g.err};
-            if (has1) {
+            if (!DET && sc.sw) {  // the step ends with a switch: the tiles of X'^H, to the panels 2 tp (+ half), + 1 of the other orientation (LDS-resident: w = nt)
+              lds_double* const dsw = (lds_double*)(XL + ob + (2 * tp + un.half) * (a2 * TILE) + q * TILE + j);
+              if (has1) qkf_p2_switch<true>(T0, T1, fr, true, a_stream(sc, v), 4, sc.nn, kmax, dsw, 2 * a2 * TILE, nxt);
+              else qkf_p2_switch<false>(T0, T1, fr, true, a_stream(sc, v), 4, sc.nn, kmax, dsw, 0, nxt);
+            } else if (has1) {
               if (kmax == 4) qkf_p2_dual<true, true, DET>(T0, T1, fr, fs, a_stream(sc, v), w * QKF_XBLOCK, sc.nn, 4, xo, q, j, nxt, np1, nd1, tp_turn);
               else qkf_p2_dual<false, true, DET>(T0, T1, fr, fs, a_stream(sc, v), w * QKF_XBLOCK, sc.nn, kmax, xo, q, j, nxt, np1, nd1, tp_turn);
             } else {
@@ -1334,10 +1420,14 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
       }
     }
     if (tid == QKF_PULLER(NT)) qkf_pull_next(g, xcc, gang_round, slot + (psel ^ 1));  // the next pair, while the other wavefronts run the right edge
+    // the orientation the chain ends in: that of its last step (whose second site, if it is a merged one, carries the same flags), switched once more if that step switches
+    const int fl_end = DET ? 0 : rfl(rec[3 * (k_hi - 1) + 1].w);
+    const bool sw_end = (fl_end & QK_REC_SWITCH) != 0, o_end = ((fl_end & QK_REC_ORIENT) != 0) != sw_end;
     if (edges) {  // the overlap: X against the product of the two right blocks
       const v4i r0 = rec[3 * (k_hi - 1)];
-      const int a_e = rfl(r0.y), b_e = rfl(r0.w);
-      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, xi, yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), xg, zacc, wave, q, j);
+      const int a_l = rfl(r0.y), b_l = rfl(r0.w), a_e = sw_end ? b_l : a_l, b_e = sw_end ? a_l : b_l;  // (the last record is in the last step's orientation)
+      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o_end ? yj : xi, o_end ? xi : yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), xg, zacc, wave,
+                                                                   q, j, o_end);
     }
     __syncthreads();  // the partial sums and the next pair's index are in LDS; nobody reads this pair's step table any more
     const long long pn = slot[psel ^ 1];
@@ -1346,6 +1436,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
       if (edges)
         for (int w_ = 0; w_ < NW; ++w_) zz.x += zacc[2 * w_], zz.y += zacc[2 * w_ + 1];
       else zz = xg ? G0[(long long)cur * g.x_plane] : (v2d)XL[xb];
+      if (o_end) zz.y = -zz.y;  // a chain that ends in orientation 1 yields conj(z)
       g.values[p] = zz.x * zz.x + zz.y * zz.y;
       if (g.z) {
         g.z[2 * p] = zz.x;

@@ -144,42 +144,132 @@ QK_HD static inline bool qk_merge_admissible(const QkSegRule& r, const int32_t* 
   const long long work_m = 4ll * a * b2 * (b + a2), work_p = 2ll * a * bm * (b + am) + 2ll * am * b2 * (bm + a2);
   return (qk_seg_small(r, a, a2, b, b2, 4) || (!qk_seg_small(r, a, am, b, bm, 2) && !qk_seg_small(r, am, a2, bm, b2, 2))) && work_m <= work_p;
 }
+// THE ASSOCIATION OF A STEP.  A step is contracted "B first": T = X^T B, then X' = T^T conj(A) (orientation 0).  "A first" is the same code
+// with the two states exchanged, working on W = X^H (orientation 1): the same qk_step_instr, qk_seg_small and qk_merge_admissible with the
+// two bond rows exchanged.  A step may END WITH A SWITCH: phase 2 then leaves the block of X'^H (qk_fused.h: the source operands of its
+// matrix instructions exchanged) and the chain goes on in the other orientation.  Only an LDS-resident step (qk_seg_small in its own
+// orientation: X' is written in one strip) may switch; it then costs QK_SWITCH_PRICE more.  With `assoc`
+//   0  every step runs in orientation 0 (the masks of the segmentation alone);
+//   1  the dynamic programme runs over (site, orientation); the chain may start in either orientation.  Ties: fewer switches, then fewer
+//      steps in orientation 1, then the ties of the merges (fewer steps, the even start);
+//   2  a test pattern: orientation 0 first, every admissible merge of the orientation at hand, a switch behind every step that may switch;
+//   3  the same pattern starting in orientation 1.
+// The orientations come back in a second mask: bit i = the step that starts at site ek + i runs in orientation 1 (the second site of a
+// merged step repeats its step's bit), bit m = n_sites - 2 ek, one past the chain, = the orientation the chain ENDS in (the right edge is
+// then taken with the states exchanged and the chain yields conj(z)).  A step whose successor bit differs is a switch step.  A chain that
+// does not leave room for bit m (m >= QK_SEG_BITS) and the greedy rule keep orientation 0.
+static constexpr int QK_SWITCH_PRICE = 40;  // matrix instructions' worth of a switch: the switch variant of phase 2 is the simpler loop (qk_fused.h: qkf_p2_switch)
+QK_HD static inline bool qk_seg_small_o(const QkSegRule& r, const int o, const int a, const int a2, const int b, const int b2, const int pd) {
+  return o ? qk_seg_small(r, b, b2, a, a2, pd) : qk_seg_small(r, a, a2, b, b2, pd);
+}
 // parities: bit 0 = merges may start at even i (site ek + i), bit 1 = at odd i.  objective / steps (optional): instructions + price per
-// step and the number of steps of the segmentation returned.
+// step (+ price per switch) and the number of steps of the segmentation returned.  assoc / switch_price / orient / switches: see above.
 QK_HD static inline QkSegMask qk_segment_chain(const int32_t* const xd, const int32_t* const xt, const int32_t* const yd, const int32_t* const yt, const int n_sites, const int ek,
-                                               const QkSegRule& rule, const int parities, const bool greedy, long long* const objective = nullptr, int* const steps = nullptr) {
+                                               const QkSegRule& rule, const int parities, const bool greedy, long long* const objective = nullptr, int* const steps = nullptr,
+                                               const int assoc = 0, const int switch_price = QK_SWITCH_PRICE, QkSegMask* const orient = nullptr, int* const switches = nullptr) {
   const int m = n_sites - 2 * ek;
-  auto may = [&](const int i) { return i + 1 < m && i < QK_SEG_BITS && ((parities >> (i & 1)) & 1) != 0 && qk_merge_admissible(rule, xd, yd, ek + i); };
-  auto plain_cost = [&](const int i) { return qk_step_instr(2, xd[ek + i], xd[ek + i + 1], yd[ek + i], yd[ek + i + 1], xt[ek + i], yt[ek + i]) + QK_STEP_PRICE; };
-  auto merged_cost = [&](const int i) { return qk_step_instr(4, xd[ek + i], xd[ek + i + 2], yd[ek + i], yd[ek + i + 2], xt[ek + i], yt[ek + i]) + QK_STEP_PRICE; };
-  QkSegMask take{{0ull, 0ull}};  // bit i: a step that starts at i is a merged one
+  const int mode = (greedy || m + 1 > QK_SEG_BITS) ? 0 : assoc;
+  // (rows of the state that plays x / y in orientation o)
+  auto may = [&](const int i, const int o) {
+    return i + 1 < m && i < QK_SEG_BITS && ((parities >> (i & 1)) & 1) != 0 && qk_merge_admissible(rule, o ? yd : xd, o ? xd : yd, ek + i);
+  };
+  auto step_cost = [&](const int i, const int o, const int len) {
+    const int e = ek + i;
+    return (o ? qk_step_instr(2 * len, yd[e], yd[e + len], xd[e], xd[e + len], yt[e], xt[e]) : qk_step_instr(2 * len, xd[e], xd[e + len], yd[e], yd[e + len], xt[e], yt[e])) + QK_STEP_PRICE;
+  };
+  auto may_switch = [&](const int i, const int o, const int len) {
+    const int e = ek + i;
+    return qk_seg_small_o(rule, o, xd[e], xd[e + len], yd[e], yd[e + len], 2 * len);
+  };
+  auto bit = [](const QkSegMask& k, const int i) { return qk_seg_bit(k.w[0], k.w[1], i); };
+  auto set = [](QkSegMask& k, const int i) { k.w[i >> 6] |= 1ull << (i & 63); };
+  QkSegMask take[2] = {{{0ull, 0ull}}, {{0ull, 0ull}}};  // [o] bit i: a step that starts at i in orientation o is a merged one
+  QkSegMask swit[2] = {{{0ull, 0ull}}, {{0ull, 0ull}}};  // [o] bit i: ... and ends with a switch
+  int o_start = 0;
   if (greedy) {
     for (int i = 0; i < m && i < QK_SEG_BITS; ++i)
-      if (may(i)) take.w[i >> 6] |= 1ull << (i & 63);
-  } else {
-    long long c1 = 0, c2 = 0;  // best cost of the sites [i + 1, m), [i + 2, m)
-    int s1 = 0, s2 = 0;        // and its steps
+      if (may(i, 0)) set(take[0], i);
+  } else if (mode <= 1) {
+    struct Best {  // of the sites [i, m) when the step at i runs in orientation o: cost, switches, steps in orientation 1, steps
+      long long c;
+      int sw, n1, st;
+    };
+    auto less = [](const Best& a, const Best& b) { return a.c != b.c ? a.c < b.c : a.sw != b.sw ? a.sw < b.sw : a.n1 != b.n1 ? a.n1 < b.n1 : a.st < b.st; };
+    auto same = [](const Best& a, const Best& b) { return a.c == b.c && a.sw == b.sw && a.n1 == b.n1 && a.st == b.st; };
+    Best f1[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, f2[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};  // of the sites [i + 1, m), [i + 2, m)
+    const int no = mode == 1 ? 2 : 1;
     for (int i = m - 1; i >= 0; --i) {
-      long long c = plain_cost(i) + c1;
-      int s = s1 + 1;
-      if (may(i)) {
-        const long long cm = merged_cost(i) + c2;
-        const int sm = s2 + 1;
-        if (cm < c || (cm == c && (sm < s || (sm == s && (i & 1) == 0)))) c = cm, s = sm, take.w[i >> 6] |= 1ull << (i & 63);
+      Best f0[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+      for (int o = 0; o < no; ++o) {
+        // a step of `len` sites at i, followed by the best of the rest in this orientation or, behind a switch, in the other one
+        auto cand = [&](const int len, bool& sw) {
+          const Best* const rest = len == 2 ? f2 : f1;
+          const long long c = step_cost(i, o, len);
+          Best b{c + rest[o].c, rest[o].sw, rest[o].n1 + o, rest[o].st + 1};
+          sw = false;
+          if (mode == 1 && may_switch(i, o, len)) {
+            const Best s{c + switch_price + rest[1 - o].c, rest[1 - o].sw + 1, rest[1 - o].n1 + o, rest[1 - o].st + 1};
+            if (less(s, b)) b = s, sw = true;
+          }
+          return b;
+        };
+        bool sw = false, swm = false;
+        Best b = cand(1, sw);
+        if (may(i, o)) {
+          const Best bm = cand(2, swm);
+          if (less(bm, b) || (same(bm, b) && (i & 1) == 0)) b = bm, sw = swm, set(take[o], i);
+        }
+        if (sw) set(swit[o], i);
+        f0[o] = b;
       }
-      c2 = c1, s2 = s1, c1 = c, s1 = s;
+      for (int o = 0; o < 2; ++o) f2[o] = f1[o], f1[o] = f0[o];
     }
+    if (mode == 1 && less(f1[1], f1[0])) o_start = 1;
+  } else {
+    o_start = mode == 3 ? 1 : 0;
   }
-  QkSegMask out{{0ull, 0ull}};
+  QkSegMask out{{0ull, 0ull}}, ori{{0ull, 0ull}};
   long long obj = 0;
-  int n_steps = 0;
+  int n_steps = 0, n_sw = 0, o = o_start;
   for (int i = 0; i < m; ++n_steps) {
-    if (qk_seg_bit(take.w[0], take.w[1], i)) out.w[i >> 6] |= 1ull << (i & 63), obj += merged_cost(i), i += 2;
-    else obj += plain_cost(i), i += 1;
+    const bool mg = mode >= 2 ? may(i, o) : bit(take[o], i);
+    const int len = mg ? 2 : 1;
+    const bool sw = mode >= 2 ? may_switch(i, o, len) : bit(swit[o], i);
+    if (mg) set(out, i);
+    if (o)
+      for (int s = i; s < i + len; ++s) set(ori, s);
+    obj += step_cost(i, o, len) + (sw ? switch_price : 0);
+    if (sw) o ^= 1, ++n_sw;
+    i += len;
   }
+  if (o) set(ori, m);  // (o != 0 only with room for this bit)
   if (objective) *objective = obj;
   if (steps) *steps = n_steps;
+  if (orient) *orient = ori;
+  if (switches) *switches = n_sw;
   return out;
+}
+
+// The record of a step in the pair's step table (qk_fused.h: qkf_step_table), 12 ints:
+//   [0] a  [1] a2  [2] b  [3] b2  [4] true a  [5] k-steps of b  [6] W  [7] small | orientation << 1 | switch << 2  [8] ceil(2^20 / mt)
+//   [9] log2 pd  [10] next step  [11] item_recips: the reciprocals of the strips' column units (qk_unit_recips), else 0
+// of the step of `len` sites (1, or 2: merged) that starts at site e.  A step in orientation 1 gets the record of the exchanged states.
+struct QkStepRec {
+  int w[12];
+};
+static constexpr int QK_REC_SMALL = 1, QK_REC_ORIENT = 2, QK_REC_SWITCH = 4;
+QK_HD static inline QkStepRec qk_step_record(const int32_t* xd, const int32_t* xt, const int32_t* yd, const int32_t* yt, const int e, const int len, const int o, const bool sw,
+                                             const QkSegRule& rule, const bool item_recips) {
+  if (o) {
+    const int32_t* t = xd;
+    xd = yd, yd = t, t = xt, xt = yt, yt = t;
+  }
+  const int a = xd[e], a2 = xd[e + len], b = yd[e], b2 = yd[e + len];
+  const bool small = qk_seg_small(rule, a, a2, b, b2, 2 * len);
+  const int mt = a / QK_TILE, nt = b2 / QK_TILE;
+  const int lim = rule.xcap / (QK_TILE * a2), W = small ? nt : (lim < 1 ? 1 : lim < nt ? lim : nt);  // X' in strips of W blocks of b' (the strip's rows must fit the LDS)
+  return QkStepRec{{a, a2, b, b2, xt[e], (yt[e] + 3) >> 2, W, (small ? QK_REC_SMALL : 0) | (o ? QK_REC_ORIENT : 0) | (sw ? QK_REC_SWITCH : 0), qk_recip20(mt), len == 2 ? 2 : 1, e + len,
+                    item_recips ? qk_unit_recips(nt, W, false) : 0}};
 }
 
 struct qk_ctx;
@@ -209,7 +299,7 @@ struct qk_plan {
   qk_ctx* up_ctx = nullptr;
   int32_t* d_pairs = nullptr;
   int32_t* d_groups = nullptr;
-  // the segmentation masks of this plan's pairs (qk_segment_chain; two words per pair), made on the device by the first Gram and kept
+  // the segmentation masks of this plan's pairs (qk_segment_chain; four words per pair: merges, orientations), made on the device by the first Gram and kept
   // while the sets, the run-time edge_k, the rule and the launches stay the same (seg_key; qkgram.hip: ensure_segments)
   unsigned long long* d_seg = nullptr;
   unsigned long long seg_key[8] = {0};
@@ -232,6 +322,8 @@ struct QkSweepPolicy {
   int fused_wgs = 0;       // workgroups per CU of the site-fused sweep: 0 = chosen per launch from the plan, 1 / 2 forced (QK_FUSED_WGS)
   bool deterministic = false;  // QK_DETERMINISTIC=1: only kernels that add in a fixed order (no LDS atomics)
   int merge_mode = 2;          // QK_MERGE: the site-fused sweep walks the chain in merged steps of two sites (qk_segment_chain) -- 0 = never, 1 = every admissible merge of the fixed pairs (k + 2 t, k + 2 t + 1), 2 = at either parity, chosen per pair by dynamic programming
+  int assoc_mode = 1;          // QK_ASSOC: the association of the steps of the site-fused sweep (qk_segment_chain; with merge_mode 2 only) -- 0 = "B first" throughout, 1 = chosen per step and pair by the dynamic programme, 2 / 3 = test patterns that switch wherever a switch is allowed; QK_DETERMINISTIC=1 forces 0
+  int switch_price = QK_SWITCH_PRICE;  // QK_SWITCH_PRICE: what the programme charges for a switch, in matrix instructions
   bool fused_dual = true;      // QK_FUSED_DUAL (0: single tiles): the 12-wave site-fused shape in its dual form (pairs of tiles per wave)
   bool gang = false;           // QK_GANG=1: gang start of the site-fused launches (qk_device.h: qk_gang_sync)
 };

@@ -324,16 +324,17 @@ __global__ __launch_bounds__(256, 2) void qk_merge_kernel(const qk_v2d* __restri
   }
 }
 
-// The segmentation masks of a launch's pairs (SweepArgs.seg; qk_plan.h: qk_segment_chain): one thread per pair.  Once per plan, sets and
+// The segmentation masks of a launch's pairs (SweepArgs.seg; qk_plan.h: qk_segment_chain; four words per pair: merges, orientations): one thread per pair.  Once per plan, sets and
 // launch shape (ensure_segments): not part of a steady-state sweep.
 __global__ __launch_bounds__(256) void qk_segment_kernel(const int32_t* __restrict__ xdims, const int32_t* __restrict__ xtrue, const int32_t* __restrict__ ydims, const int32_t* __restrict__ ytrue,
                                                          const int n_sites, const int ek, const int32_t* __restrict__ pairs, const long long npairs, const QkSegRule rule, const int parities,
-                                                         const bool greedy, unsigned long long* __restrict__ seg) {
+                                                         const bool greedy, const int assoc, const int switch_price, unsigned long long* __restrict__ seg) {
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npairs) return;
   const long long xo = (long long)pairs[2 * p] * (n_sites + 1), yo = (long long)pairs[2 * p + 1] * (n_sites + 1);
-  const QkSegMask m = qk_segment_chain(xdims + xo, xtrue + xo, ydims + yo, ytrue + yo, n_sites, ek, rule, parities, greedy);
-  seg[2 * p] = m.w[0], seg[2 * p + 1] = m.w[1];
+  QkSegMask o{{0ull, 0ull}};  // the orientations of the steps (qk_plan.h: the association of a step)
+  const QkSegMask m = qk_segment_chain(xdims + xo, xtrue + xo, ydims + yo, ytrue + yo, n_sites, ek, rule, parities, greedy, nullptr, nullptr, assoc, switch_price, &o);
+  seg[4 * p] = m.w[0], seg[4 * p + 1] = m.w[1], seg[4 * p + 2] = o.w[0], seg[4 * p + 3] = o.w[1];
 }
 
 #ifdef QK_LAB
@@ -425,12 +426,14 @@ static int ctx_init(qk_ctx* c, int device_id, int num_cus) {
   if (const char* v = std::getenv("QK_WAVE2")) p.wave2_path = std::atoi(v) != 0, p.wave2_ring = std::atoi(v) != 2;
   if (const char* v = std::getenv("QK_FUSED")) p.fused_path = std::atoi(v);
   if (const char* v = std::getenv("QK_MERGE")) p.merge_mode = std::max(0, std::min(2, std::atoi(v)));
+  if (const char* v = std::getenv("QK_ASSOC")) p.assoc_mode = std::max(0, std::min(3, std::atoi(v)));
+  if (const char* v = std::getenv("QK_SWITCH_PRICE")) p.switch_price = std::max(0, std::min(100000, std::atoi(v)));
   // QK_DETERMINISTIC=1: bit-reproducible Grams.  By default the site-fused sweep sums the tiles of a column with LDS atomics in arrival
   // order (two launches on the same inputs differ in the last bits, <= 9e-16); in this mode it takes its DET forms, which add in a fixed
   // order (qk_fused.h: qkf_turn_add); the ring sweep, the small-bond sweep and the one-wave sweeps add in a fixed order anyway.  The order
   // in which workgroups pull pairs never matters (a pair's result does not depend on the workgroup that sweeps it).
   if (const char* v = std::getenv("QK_DETERMINISTIC"))
-    if (std::atoi(v) != 0) p.deterministic = true;
+    if (std::atoi(v) != 0) p.deterministic = true, p.assoc_mode = 0;  // (the ordered forms have no switch step: orientation 0 throughout)
   if (const char* v = std::getenv("QK_FUSED_SPLIT")) p.fused_split = std::max(0, std::min(2, std::atoi(v)));
   if (const char* v = std::getenv("QK_FUSED_WGS")) p.fused_wgs = std::max(0, std::min(2, std::atoi(v)));
   if (const char* v = std::getenv("QK_WGS_PER_CU")) p.wgs_per_cu = std::max(1, std::min(4, std::atoi(v)));
@@ -835,13 +838,23 @@ static QkSegRule seg_rule_of(const int kernel) {
   }
 }
 
+// whether a launch's kernel has the switch step (qk_fused.h: qkf_p2_switch): the plain forms of the shipped site-fused kernels.  The masks
+// of any other launch are made with orientation 0 throughout.
+static bool seg_assoc_of(const int kernel) {
+#if QKF_QUAD  // (lab builds: the quad form stands in for the plain dual form and has no switch step)
+  if (kernel == QK_KERNEL_FUSED_DUAL) return false;
+#endif
+  return kernel == QK_KERNEL_FUSED_DUAL || kernel == QK_KERNEL_FUSED1 || kernel == QK_KERNEL_FUSED2;
+}
+
 // the segmentation masks of the plan's pairs for the launches of `ch` (a.merge_steps > 0: the sets hold merged images for a.edge_k), into
 // a.seg.  Made on the sweep's stream by qk_segment_kernel, one launch per site-fused run with that run's shape, and kept in the plan: a
-// later call with the same sets, edge_k, rule and launches finds them there.
+// later call with the same sets, edge_k, rule, launches, QK_ASSOC and switch price finds them there.
 static int ensure_segments(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set* ys, qk_plan* plan, const QkSweepChoice& ch, const int merge_mode, SweepArgs& a) {
   const long long np = (long long)plan->pairs.size() / 2;
   const bool both = merge_mode >= 2 && xs->mg_stride == 1 && ys->mg_stride == 1;  // else the even starts only: QK_MERGE=1, or a set without the image of every start
-  const unsigned long long key[8] = {1ull,
+  const int assoc = merge_mode >= 2 ? c->policy.assoc_mode : 0, switch_price = c->policy.switch_price;  // (the orientations are chosen by the programme that chooses the merges)
+  const unsigned long long key[8] = {2ull | ((unsigned long long)assoc << 8) | ((unsigned long long)switch_price << 16),
                                      xs->uid,
                                      ys->uid,
                                      (unsigned long long)a.edge_k,
@@ -855,18 +868,18 @@ static int ensure_segments(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set* ys
     (void)hipFree(plan->d_seg), plan->d_seg = nullptr;
   }
   QkDevBuf seg;
-  HIP_TRY(seg.alloc((size_t)np * 2 * sizeof(unsigned long long)));
+  HIP_TRY(seg.alloc((size_t)np * 4 * sizeof(unsigned long long)));
   unsigned long long* const d = seg.get<unsigned long long>();
   for (int i = 0; i < ch.n_runs; ++i) {
     const QkSweepRun& r = ch.run[i];
     const QkSegRule rule = seg_rule_of(r.kernel);
     if (r.count <= 0) continue;
     if (rule.cap == 0) {  // (the one-wave launch of a mixed sweep reads no mask)
-      HIP_TRY(hipMemsetAsync(d + 2 * r.first, 0, (size_t)r.count * 2 * sizeof(unsigned long long), c->stream));
+      HIP_TRY(hipMemsetAsync(d + 4 * r.first, 0, (size_t)r.count * 4 * sizeof(unsigned long long), c->stream));
       continue;
     }
     qk_segment_kernel<<<dim3((unsigned)((r.count + 255) / 256)), dim3(256), 0, c->stream>>>(a.xdims, a.xtrue, a.ydims, a.ytrue, a.n_sites, a.edge_k, a.pairs + 2 * r.first, r.count, rule, both ? 3 : 1,
-                                                                                            merge_mode == 1, d + 2 * r.first);
+                                                                                            merge_mode == 1, seg_assoc_of(r.kernel) ? assoc : 0, switch_price, d + 4 * r.first);
   }
   HIP_TRY(hipGetLastError());
   plan->d_seg = static_cast<unsigned long long*>(seg.release());
@@ -963,7 +976,7 @@ extern "C" int qk_gram_values(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set*
     ar.npairs = r.count, ar.nq = r.nq, ar.gang_n = r.gang_n;
     if (i == 1) {  // the second class of pairs: its part of the list, and queue heads, tail clocks (and gang words) behind the first launch's
       HIP_TRY(hipEventRecord(c->ev_mid, c->stream));
-      ar.pairs = a.pairs + 2 * r.first, ar.values = a.values + r.first, ar.z = a.z ? a.z + 2 * r.first : nullptr, ar.seg = a.seg ? a.seg + 2 * r.first : nullptr;
+      ar.pairs = a.pairs + 2 * r.first, ar.values = a.values + r.first, ar.z = a.z ? a.z + 2 * r.first : nullptr, ar.seg = a.seg ? a.seg + 4 * r.first : nullptr;
       ar.counter = counter + 8 * QK_QSTRIDE, ar.tail = a.tail + 2;
       if (plan->nq > 1)
         for (int s_ = 0; s_ <= 8; ++s_) ar.qstart[s_] = plan->qstart[8 + s_] - r.first;

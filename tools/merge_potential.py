@@ -2,7 +2,9 @@
 """What the segmentation of the site-fused sweep's chains executes, per launch of a bench config: steps and matrix instructions per
 pair with no merged steps (QK_MERGE=0), with every admissible merge of the fixed pairs (k + 2 t, k + 2 t + 1) (QK_MERGE=1) and with
 merges at either parity chosen per pair by dynamic programming (QK_MERGE=2, the default) -- and the device bytes of the merged images
-the last two need.
+the last two need.  On top of QK_MERGE=2: the association of the steps (QK_ASSOC; tools/assoc_capi.cpp) -- matrix instructions, steps and
+switches per pair with orientation 0 throughout (QK_ASSOC=0) and with the orientation chosen per step (the default), at the shipped
+switch price and at 0 and 150.
 
 The numbers come from the function the device runs (qk_segment_chain, csrc/qk_plan.h), compiled for the host from
 tools/segment_capi.cpp and called through ctypes, over ALL pairs of the config's real plan (the host planner: class split, orientation
@@ -56,9 +58,42 @@ def segment_pairs(x_true, y_true, pairs, ek, shape, parities, greedy):
     return masks, instr, steps
 
 
+_assoc = None
+ASSOC_FLAGS = {"starts_o1": 1, "ends_o1": 2, "first_step": 4, "last_step": 8, "merged_step": 16, "strip_between": 32, "one_round_step": 64, "pingpong_step": 128}  # tools/assoc_capi.cpp
+SWITCH_PRICE = 40  # csrc/qk_plan.h: QK_SWITCH_PRICE
+
+
+def assoc_lib():
+    """The host build of tools/assoc_capi.cpp (made once per process in a temporary directory)."""
+    global _assoc
+    if _assoc is None:
+        tmp = tempfile.mkdtemp(prefix="qk_assoc_")
+        so = os.path.join(tmp, "libqkassoc.so")
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tools", "assoc_capi.cpp")], check=True)
+        _assoc = C.CDLL(so)
+        _assoc.qk_assoc_pairs.restype = None
+        _assoc.qk_assoc_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 5
+    return _assoc
+
+
+def assoc_pairs(x_true, y_true, pairs, ek, shape, assoc, switch_price=SWITCH_PRICE):
+    """The segmentation WITH the association of the steps (QK_MERGE=2; assoc as QK_ASSOC): (masks [pairs][4] uint64 -- merges, orientations --,
+    matrix instructions [pairs], steps [pairs], switches [pairs], flags [pairs]: ASSOC_FLAGS) under a launch shape."""
+    x_true = np.ascontiguousarray(x_true, dtype=np.int32)
+    y_true = np.ascontiguousarray(y_true, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    n = pairs.shape[0]
+    masks, instr = np.zeros((n, 4), dtype=np.uint64), np.zeros(n, dtype=np.int64)
+    steps, switches, flags = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    xcap, cap, dual = SHAPES[shape]
+    assoc_lib().qk_assoc_pairs(x_true.ctypes.data, y_true.ctypes.data, x_true.shape[1] - 1, pairs.ctypes.data, n, int(ek), xcap, cap, dual, int(assoc), int(switch_price),
+                               masks.ctypes.data, instr.ctypes.data, steps.ctypes.data, switches.ctypes.data, flags.ctypes.data)
+    return masks, instr, steps, switches, flags
+
+
 def merged_steps(masks):
-    """merged steps per pair: the bits of its mask"""
-    return np.array([bin(int(a)).count("1") + bin(int(b)).count("1") for a, b in masks])
+    """merged steps per pair: the bits of its mask (the first two words)"""
+    return np.array([bin(int(r[0])).count("1") + bin(int(r[1])).count("1") for r in masks])
 
 
 RULES = (("QK_MERGE=0", 0, True), ("QK_MERGE=1", 1, True), ("QK_MERGE=2", 3, False))  # name, allowed parities, every admissible merge / dynamic programme
@@ -108,6 +143,17 @@ def main():
             odd = int(sum(bin(int(a) & 0xAAAAAAAAAAAAAAAA).count("1") + bin(int(b) & 0xAAAAAAAAAAAAAAAA).count("1") for a, b in masks))
             print(f"  {name}: steps/pair {steps.mean():6.2f}  merged {merged_steps(masks).mean():6.2f} (odd starts {odd / masks.shape[0]:5.2f})  matrix instr./pair {instr.mean():9.0f}"
                   f"  instr. + 375/step {cost:9.0f}{rel}")
+        # the association of the steps (QK_ASSOC; on top of QK_MERGE=2): orientation 0 throughout against the choice per step
+        base = None
+        for name, assoc, price in (("QK_ASSOC=0", 0, SWITCH_PRICE), ("QK_ASSOC=1", 1, SWITCH_PRICE), ("QK_ASSOC=1 price 0", 1, 0), ("QK_ASSOC=1 price 150", 1, 150)):
+            masks, instr, steps, switches, flags = assoc_pairs(dims, dims, pairs[sl], ek, shape, assoc, price)
+            cost = instr.mean() + 375.0 * steps.mean() + price * switches.mean()
+            if base is None:
+                base = (instr.mean(), cost, (instr + edge[sl]).mean())
+            rel = "" if assoc == 0 else (f"  ({(instr.mean() / base[0] - 1) * 100:+.2f} % instr., {(cost / base[1] - 1) * 100:+.2f} % modelled cost, "
+                                         f"{((instr + edge[sl]).mean() / base[2] - 1) * 100:+.2f} % instr. with the edges, against QK_ASSOC=0)")
+            print(f"  {name:20s}: steps/pair {steps.mean():6.2f}  merged {merged_steps(masks).mean():6.2f}  switches/pair {switches.mean():5.2f} (pairs that switch {(switches > 0).mean() * 100:5.1f} %, "
+                  f"start in orientation 1 {((flags & 1) != 0).mean() * 100:5.1f} %, end in it {((flags & 2) != 0).mean() * 100:5.1f} %)  matrix instr./pair {instr.mean():9.0f}{rel}")
     plan.close()
 
 
