@@ -32,9 +32,10 @@
 //     fragments that several items share are re-read through the caches (which catch a fifth to a quarter of them: the rest comes
 //     back over the fabric -- DESIGN.md, cache counters);
 //   * K is walked in units of 4 up to the TRUE bond; the complex product is the 3M form of the ring kernel.  In phase 2 of the plain
-//     forms the three partial products are not re-combined by vector additions: k1 = sum (tr + ti) Ar is formed first and the chains of
-//     re = k1 + sum ti (Ai - Ar) and im = k1 - sum tr (Ar + Ai) START on it (the C operand of their first matrix instruction), so a
-//     column block ends in its ds_add_f64 with no v_add_f64 behind the matrix instructions (qkf_p2_block; lab/NOTES_r07.md);
+//     forms the three partial products are not re-combined by vector additions: with S = Ar + Ai, k1 = sum ti S is formed first and the
+//     chains of re = k1 + sum (tr - ti) Ar and im = k1 + sum (-tr - ti) Ai START on it (the C operand of their first matrix instruction),
+//     so a column block ends in its ds_add_f64 with no v_add_f64 behind the matrix instructions and forms ONE operand sum per fragment
+//     element (qkf_p2_onesum; lab/NOTES_r07.md, lab/NOTES_r10.md);
 //   * sites too large for the LDS run in STRIPS: X is read from a per-workgroup global buffer (A-operand fragments
 //     loaded like the site tensors), X' is accumulated a block of b' rows at a time (as many as fit the LDS), items in
 //     rounds of (waves x slots), and written to the other global buffer;
@@ -295,18 +296,156 @@ __device__ __forceinline__ void qkf_turn_add(__attribute__((address_space(3))) d
   __hip_atomic_store(turn, t.idx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// ---- Phase 2 of the plain forms: ONE column block for both kinds of step, one operand sum per fragment element (lab/NOTES_r10.md).
+// With S = Ar + Ai the products are
+//     ordinary (X' += T^T conj(A)):   k1 = sum ti S,   re = k1 + sum (tr - ti) Ar,   im = k1 + sum (-tr - ti) Ai
+//     switch   (X'^H = conj(T)^T A):  k1 = sum S tr,   re = k1 + sum Ai (ti - tr),   im = k1 + sum Ar (-tr - ti)
+// (tests/host_san/onesum_main.cpp), so the chains of re and im run on the RAW parts of the fragment and a column block forms one sum
+// per fragment element and k-step -- 4 v_add_f64 -- where the first tuned form (qkf_p2_block) has 8 and the simple switch loop
+// (qkf_p2_switch_simple) 4 and 16 additions behind its matrix instructions.  Everything else rides on the T side: three register sets per
+// tile as before, QkfTSet: k (feeds k1), a (feeds re), b (feeds im), taken once per unit (qkf_tset) from the tile phase 1 left.  The two
+// kinds of step differ only in which part of T is in which set, in which raw part of the fragment a chain reads, and in the order of the
+// two source operands of every matrix instruction (SWITCH: the fragment is the A operand and the accumulators hold the tile of X'^T --
+// the A and the B operand of v_mfma_f64_16x16x4_f64 have the same lane layout).
+// As in the first tuned form k1 of the block's k-steps is formed first (k-step 0 starts the chain on the literal zero; the sum of k-step
+// i + 1 is taken while the matrix instruction of k-step i runs) and the chains of re and im START on it: the first matrix instruction of
+// `re` reads k1 as its C operand and writes other registers, `im` goes on in k1's, and the block ends in its ds_add_f64 with no addition
+// behind the matrix instructions.
+// The reload: the chains read the raw fragment, so the registers of a k-step cannot be reloaded behind its k1 as in the first tuned form.
+// fr[i] is reloaded LATE, behind the last chain instruction that reads it (in a pair of tiles: the second tile's): one set, one block
+// body, 6 - 12 matrix instructions between a load and its first use instead of a whole block -- the other waves of the SIMD cover it:
+// cfg4, one box, parent against this form twice each: dual launch 277.7 / 278.3 -> 273.3 / 273.3 ms, 8-wave launch 46.93 / 46.94 ->
+// 46.29 / 46.27 ms.  (A ping-pong form -- the next block's loads into a second set behind k1_i, a whole block ahead -- needed eight
+// registers more than the dual kernel has and lost 11 ms: lab/dropped/r10_p2_pingpong.patch.)
+// QKF_P2_FORM_* = 1 selects this block per launch shape (the shipped setting for all three); 0 keeps the first tuned form (qkf_p2_block /
+// the plain loop of qkf_p2_item) and the simple switch loop, for A/B builds.
+#ifndef QKF_P2_FORM_DUAL  // the 12-wave dual kernel
+#define QKF_P2_FORM_DUAL 1
+#endif
+#ifndef QKF_P2_FORM_ONE   // the 12-wave one-tile kernel (two slots, 168 registers)
+#define QKF_P2_FORM_ONE 1
+#endif
+#ifndef QKF_P2_FORM_TWO   // the 8-wave one-tile kernel (128 registers)
+#define QKF_P2_FORM_TWO 1
+#endif
+typedef __attribute__((address_space(3))) double lds_double;
+struct QkfTSet {
+  v4d k, a, b;
+};
+template <bool SWITCH>
+__device__ __forceinline__ QkfTSet qkf_tset(const QkfTile& t) {
+  return SWITCH ? QkfTSet{t.re, t.im - t.re, -t.re - t.im} : QkfTSet{t.im, t.re - t.im, -t.re - t.im};
+}
+// one matrix instruction of the block: the T-side value first, the fragment's second; SWITCH exchanges them
+template <bool SWITCH>
+__device__ __forceinline__ v4d qkf_p2_mma(const double t, const double f, const v4d& c) {
+  return SWITCH ? __builtin_amdgcn_mfma_f64_16x16x4f64(f, t, c, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(t, f, c, 0, 0, 0);
+}
+// (Late reload: a matrix builtin carries no order against a load, and the compiler, left alone, issues the reload of a k-step ahead of the chain
+// instructions that still read it and pays with eight register copies per block.  So the chains' results pass through an empty statement
+// -- no instruction -- that the load cannot cross.)
+#define QKF_PIN2(a, b) asm volatile("" : "+v"(a), "+v"(b) : : "memory")
+// One column block: the chains on the fragment in `fa`, whose k-step i is reloaded from (b_i, off) behind its last reader; then the results
+// are added to X' at d (and d1 for the second tile), the rows q + 4 r of a tile 2 QKF_XSTEP doubles apart.
+template <bool FULL, bool HAS1, bool SWITCH>
+__device__ __forceinline__ void qkf_p2_onesum(const QkfTSet& u0, const QkfTSet& u1, v2d (&fa)[4], const int kmax, const v2d* const b0, const v2d* const b1, const v2d* const b2,
+                                              const v2d* const b3, const unsigned off, lds_double* const d, lds_double* const d1) {
+  constexpr long rs = 2 * QKF_XSTEP;
+  const v4d z = {0, 0, 0, 0};
+  v4d p1 = z, r1 = z, re, im, re1, im1;
+  QKF_PRIO_LO();
+  double s = QKF_SUM(fa[0].x, fa[0].y);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (FULL || i == 0 || i < kmax) {
+      p1 = qkf_p2_mma<SWITCH>(u0.k[i], s, i == 0 ? z : p1);
+      if (HAS1) r1 = qkf_p2_mma<SWITCH>(u1.k[i], s, i == 0 ? z : r1);
+    }
+    if (i < 3) s = QKF_SUM(fa[i + 1].x, fa[i + 1].y);  // (a k-step at or above the bond: loaded from the last one's address, the sum is not used)
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (FULL || i == 0 || i < kmax) {
+      const double fre = SWITCH ? fa[i].y : fa[i].x, fim = SWITCH ? fa[i].x : fa[i].y;  // the raw part the chain of re / of im reads
+      re = qkf_p2_mma<SWITCH>(u0.a[i], fre, i == 0 ? p1 : re);
+      im = qkf_p2_mma<SWITCH>(u0.b[i], fim, i == 0 ? p1 : im);
+    }
+    if (!HAS1 && !(QKF_ABL & 2)) {
+      QKF_PIN2(re, im);
+      fa[i] = qkf_ldg_a(i == 0 ? b0 : i == 1 ? b1 : i == 2 ? b2 : b3, off);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (HAS1) {  // the second tile's chains stand behind the first tile's (whose ds_add_f64 then run beside them); they are the last to read fr[i]
+    QKF_PIN2(re, im);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (FULL || i == 0 || i < kmax) {
+        const double fre = SWITCH ? fa[i].y : fa[i].x, fim = SWITCH ? fa[i].x : fa[i].y;
+        re1 = qkf_p2_mma<SWITCH>(u1.a[i], fre, i == 0 ? r1 : re1);
+        im1 = qkf_p2_mma<SWITCH>(u1.b[i], fim, i == 0 ? r1 : im1);
+      }
+      if (!(QKF_ABL & 2)) {
+        QKF_PIN2(re1, im1);
+        fa[i] = qkf_ldg_a(i == 0 ? b0 : i == 1 ? b1 : i == 2 ? b2 : b3, off);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  QKF_PRIO_HI();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    __hip_atomic_fetch_add(d + r * rs, re[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(d + r * rs + 1, im[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  if (HAS1) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      __hip_atomic_fetch_add(d1 + r * rs, re1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(d1 + r * rs + 1, im1[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+}
+// The column blocks of a unit: `fr` holds the first group of stream `cur` (k-steps of it below `lim` are fetched, qkf_kbase) and leaves
+// with the first group of `nxt`; block tn adds to d + tn * dstep, the second tile of a pair d1off further on (a constant in the ordinary
+// step: an immediate offset).  The bases of a stream are wave-uniform and do not change, so the loop runs over the blocks that are
+// followed by another block of the stream, and the last block, which reloads from `nxt`, stands behind it.
+template <bool FULL, bool HAS1, bool SWITCH>
+__device__ __forceinline__ void qkf_p2_blocks(const QkfTile& t0, const QkfTile& t1, v2d (&fr)[4], const QkfStream cur, const int lim, const QkfStream nxt, const int nn, const int kmax,
+                                              lds_double* d, const int d1off, const int dstep) {
+  const QkfTSet u0 = qkf_tset<SWITCH>(t0), u1 = HAS1 ? qkf_tset<SWITCH>(t1) : u0;
+  const v2d *const c0 = qkf_kbase(cur.base, cur.step, 0, lim), *const c1 = qkf_kbase(cur.base, cur.step, 1, lim), *const c2 = qkf_kbase(cur.base, cur.step, 2, lim),
+            *const c3 = qkf_kbase(cur.base, cur.step, 3, lim);
+  unsigned off = cur.off;
+#pragma unroll 1
+  for (int tn = 0; tn + 1 < nn; ++tn) {
+    off += TILE;
+    qkf_p2_onesum<FULL, HAS1, SWITCH>(u0, u1, fr, kmax, c0, c1, c2, c3, off, d, d + d1off);
+    d += dstep;
+  }
+  qkf_p2_onesum<FULL, HAS1, SWITCH>(u0, u1, fr, kmax, qkf_kbase(nxt.base, nxt.step, 0, nxt.lim), qkf_kbase(nxt.base, nxt.step, 1, nxt.lim), qkf_kbase(nxt.base, nxt.step, 2, nxt.lim),
+                                    qkf_kbase(nxt.base, nxt.step, 3, nxt.lim), nxt.off, d, d + d1off);
+}
+
 // Phase 2, one item: X'[tb rows, tn cols] += T^T conj(A[16 ta + ., p, 16 tn + .]) for every column block tn, added into
 // the LDS image `xo` (row stride a2, this item's 16 rows start at xo) with ds_add_f64.  A operand: stream `cur` (group
 // = column block tn: off advances by 16 per group; step = one k-step = 4 rows of a).  FULL: all four k-steps of this ta
 // block lie below the true bond (every block but the last one of a ragged bond); otherwise kmax of them do.  The last
 // group reloads the registers with the first group of `nxt` (the wave's next item, or its first tile of the next site).
-template <bool FULL, bool DET = false>
+// The plain form is the single-tile instantiation of the one-sum block (FORM 1, shipped), or the first tuned form's loop (FORM 0); the
+// ordered form (DET) keeps the product's first 3M form, its additions and its bits.
+template <bool FULL, bool DET = false, int FORM = 0>
 __device__ __forceinline__ void qkf_p2_item(const QkfTile& t, v2d (&fr)[4], const bool primed, QkfStream cur, const int ps, const int nn, const int kmax, lds_v2d* xo, const int q,
                                             const int j, const QkfStream nxt, const QkfTurn turn = QkfTurn{nullptr, 0, nullptr, nullptr}) {
   if (!primed) qkf_load4(fr, cur);
   __attribute__((address_space(3))) double* d = (__attribute__((address_space(3))) double*)(xo + q * TILE + j);
+  if constexpr (!DET && FORM != 0) {  // the one-sum block (above), single tile
+    qkf_p2_blocks<FULL, false, false>(t, t, fr, cur, FULL ? 4 : kmax, nxt, nn, kmax, d, 0, 2 * ps);
+    return;
+  }
   if constexpr (!DET) {
-    // The plain form: k1 = sum (tr + ti) Ar first, then the chains of re = k1 + sum ti (Ai - Ar) and im = k1 - sum tr (Ar + Ai) START on it
+    // (FORM 0, A/B builds: the first tuned form)  k1 = sum (tr + ti) Ar first, then the chains of re = k1 + sum ti (Ai - Ar) and im = k1 - sum tr (Ar + Ai) START on it
     // (qkf_p2_block has the reasoning): 8 v_add_f64 per column block -- the operand sums, formed while k1 runs so that the registers of a
     // k-step are reloaded right behind its k1 -- instead of 17; the sums tr + ti are taken once per item (the register allocator of the
     // 128-register shape keeps seven of the eight registers and forms the last sum again per block: 9 per block there).
@@ -378,15 +517,15 @@ __device__ __forceinline__ void qkf_p2_item(const QkfTile& t, v2d (&fr)[4], cons
 // QKF_XBLOCK elements further on, the second tile of a pair `d1off` doubles = one panel) with the ordinary in-tile lane pattern.  The
 // conjugation moves from A to T and rides on the per-tile sums of T:  X'^H = conj(T)^T A,
 //     k1 = sum tr (Ar + Ai),   re = k1 + sum (ti - tr) Ai,   im = k1 + sum (-tr - ti) Ar
-// -- one operand sum per fragment element, the registers of T's imaginary part and of tr + ti become ti - tr and -tr - ti.  It is ONE
-// simple loop, that of the ordered forms: three chains per tile and k-step, the registers of a k-step reloaded behind them, the sums
-// k1 + . taken behind the block, the last block reloading from `nxt`, no specialisation for full blocks; `lim` as in qkf_p2_item (4 in the
-// dual kernel, whose streams load whole groups).  It hands fr to the next unit exactly as the tuned loops do.  On the headline set a
-// fifth of the steps take it; its tuned form (chains started on k1) is the open item of lab/NOTES_r09.md.
+// -- one operand sum per fragment element, the registers of T's imaginary part and of tr + ti become ti - tr and -tr - ti.  The shipped
+// form is the SWITCH instantiation of the one-sum block (qkf_p2_onesum above: chains started on k1, a specialisation for full blocks, the
+// reload of the kernel's form); `lim` as in qkf_p2_item (4 in the dual kernel, whose streams load whole groups).  It hands fr to the next
+// unit exactly as the ordinary blocks do.  On the headline set a fifth of the steps take it.
+// FORM 0 is the simple loop round 9 shipped (kept for the A/B): that of the ordered forms -- three chains per tile and k-step, the registers
+// of a k-step reloaded behind them, the sums k1 + . taken behind the block, no specialisation for full blocks.
 template <bool HAS1>
-__device__ __forceinline__ void qkf_p2_switch(const QkfTile& t0, const QkfTile& t1, v2d (&fr)[4], const bool primed, QkfStream cur, const int lim, const int nn, const int kmax,
-                                              __attribute__((address_space(3))) double* d, const int d1off, const QkfStream nxt) {
-  if (!primed) qkf_load4(fr, cur);
+__device__ __forceinline__ void qkf_p2_switch_simple(const QkfTile& t0, const QkfTile& t1, v2d (&fr)[4], QkfStream cur, const int lim, const int nn, const int kmax,
+                                                     __attribute__((address_space(3))) double* d, const int d1off, const QkfStream nxt) {
   const v4d dm0 = t0.im - t0.re, ng0 = -t0.re - t0.im, dm1 = HAS1 ? t1.im - t1.re : dm0, ng1 = HAS1 ? -t1.re - t1.im : ng0;
 #pragma unroll 1
   for (int tn = 0; tn < nn; ++tn) {
@@ -431,6 +570,13 @@ __device__ __forceinline__ void qkf_p2_switch(const QkfTile& t0, const QkfTile& 
     }
     d += 2 * QKF_XBLOCK;  // the next block of rows of a'
   }
+}
+template <bool FULL, bool HAS1, int FORM>
+__device__ __forceinline__ void qkf_p2_switch(const QkfTile& t0, const QkfTile& t1, v2d (&fr)[4], const bool primed, const QkfStream cur, const int lim, const int nn, const int kmax,
+                                              lds_double* const d, const int d1off, const QkfStream nxt) {
+  if (!primed) qkf_load4(fr, cur);
+  if constexpr (FORM == 0) qkf_p2_switch_simple<HAS1>(t0, t1, fr, cur, lim, nn, kmax, d, d1off, nxt);
+  else qkf_p2_blocks<FULL, HAS1, true>(t0, t1, fr, cur, lim, nxt, nn, kmax, d, d1off, 2 * QKF_XBLOCK);  // (tn: the next block of rows of a')
 }
 
 // The T tiles of a wave live in registers, S slots.  The slot loops are NOT unrolled (unrolled, every slot drags ~50
@@ -924,10 +1070,13 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
             const QkfStream nxt = more ? a_stream(sc, w, it + NW) : chain ? b_stream(sn, 0, wn, wave) : a_stream(sc, w, it);
             const int tix = sc.pd * ta + un.p;  // (ordered form) this contribution's place in the order of its block of rows
             const QkfTurn turn{tcur + tbl * sc.nn, tix, tbroken, g.err};
-            if (!DET && sc.sw)  // the step ends with a switch: the tile of X'^H, to block tbl's panel of the other orientation (LDS-resident: w = nt)
-              qkf_p2_switch<false>(T[S - 1], T[S - 1], fr, primed, a_stream(sc, w, it), kmax, sc.nn, kmax, (__attribute__((address_space(3))) double*)(XL + ob + tbl * (a2 * TILE) + q * TILE + j), 0, nxt);
-            else if (kmax == 4) qkf_p2_item<true, DET>(T[S - 1], fr, primed, a_stream(sc, w, it), w * QKF_XBLOCK, sc.nn, 4, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
-            else qkf_p2_item<false, DET>(T[S - 1], fr, primed, a_stream(sc, w, it), w * QKF_XBLOCK, sc.nn, kmax, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
+            constexpr int FORM = DET ? 0 : WPS >= 4 ? QKF_P2_FORM_TWO : QKF_P2_FORM_ONE;  // the form of the plain column blocks (qkf_p2_onesum)
+            if (!DET && sc.sw) {  // the step ends with a switch: the tile of X'^H, to block tbl's panel of the other orientation (LDS-resident: w = nt)
+              lds_double* const dsw = (lds_double*)(XL + ob + tbl * (a2 * TILE) + q * TILE + j);
+              if (FORM != 0 && kmax == 4) qkf_p2_switch<true, false, FORM>(T[S - 1], T[S - 1], fr, primed, a_stream(sc, w, it), 4, sc.nn, 4, dsw, 0, nxt);
+              else qkf_p2_switch<false, false, FORM>(T[S - 1], T[S - 1], fr, primed, a_stream(sc, w, it), kmax, sc.nn, kmax, dsw, 0, nxt);
+            } else if (kmax == 4) qkf_p2_item<true, DET, FORM>(T[S - 1], fr, primed, a_stream(sc, w, it), w * QKF_XBLOCK, sc.nn, 4, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
+            else qkf_p2_item<false, DET, FORM>(T[S - 1], fr, primed, a_stream(sc, w, it), w * QKF_XBLOCK, sc.nn, kmax, XL + ob + tbl * QKF_XBLOCK, q, j, nxt, turn);
             primed = more || chain;
           }
           QKF_STAMP(4);  // phase 2
@@ -1062,6 +1211,9 @@ __device__ __forceinline__ void qkf_p1_dual(QkfTile& t0, QkfTile& t1, v2d (&fr)[
 // last block, which reloads the registers with the first group of `nxt`, stands behind it; the product's second 3M form saves a third of
 // the additions behind a block.  cfg4, one box, step by step: 374.4 -> 370.6 (this loop) -> 368.0 (3M form) -> 364.3 (phase 1 started by its
 // first k-step) -> 363.9 ms (the same in the one-tile kernel).
+// (What follows describes the FIRST tuned form, qkf_p2_block: round 7's, two operand sums per fragment element.  The shipped plain form is
+// the one-sum block qkf_p2_onesum above, which keeps its order -- k1 first, the chains started on it -- and halves its additions;
+// qkf_p2_block stays for A/B builds, -DQKF_P2_FORM_DUAL=0.)
 // The additions BEHIND a block are gone altogether (lab/NOTES_r07.md): with  k1 = (tr + ti) Ar,  k2 = tr (Ar + Ai),  k3 = ti (Ar - Ai)  the
 // product is re = k1 - k3, im = k1 - k2, and a matrix instruction adds its C operand for nothing.  So k1 of the block's k-steps is formed
 // first (chain started on the literal zero), and the chains of re = k1 + sum ti (Ai - Ar) and im = k1 - sum tr (Ar + Ai) START on it: the
@@ -1069,7 +1221,6 @@ __device__ __forceinline__ void qkf_p1_dual(QkfTile& t0, QkfTile& t1, v2d (&fr)[
 // sets per tile, as before.  The signs ride on the operand sums (source modifiers of the v_add_f64), which are formed while k1 runs, so the
 // registers of a k-step are reloaded right behind its k1: the loads keep their distance of a whole block.  Per block of a pair: 24 matrix
 // instructions, 8 v_add_f64 (16 tail additions gone), 16 ds_add_f64.
-typedef __attribute__((address_space(3))) double lds_double;
 // one column block: k1 of the k-steps in `fr`, each followed by the reload of its registers from (b_i, off); the chains of re and im; then the
 // results added to X' at d (and d1 for the second tile)
 template <bool FULL, bool HAS1>
@@ -1178,6 +1329,10 @@ __device__ __forceinline__ void qkf_p2_dual(const QkfTile& t0, const QkfTile& t1
   }
   lds_double* d = (lds_double*)(xo + q * TILE + j);
   lds_double* d1 = d + 2 * QKF_XBLOCK;  // the second tile's rows: 16 rows further down
+  if constexpr (QKF_P2_FORM_DUAL != 0) {  // the one-sum block
+    qkf_p2_blocks<FULL, HAS1, false>(t0, t1, fr, cur, 4, nxt, nn, kmax, d, 2 * QKF_XBLOCK, 2 * ps);
+    return;
+  }
   constexpr long rs = 2 * QKF_XSTEP;
   const v4d s0 = t0.re + t0.im, s1 = HAS1 ? t1.re + t1.im : s0;
   const v2d *const c0 = cur.base, *const c1 = cur.base + cur.step, *const c2 = cur.base + 2 * cur.step, *const c3 = cur.base + 3 * cur.step;
@@ -1390,8 +1545,14 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
             const QkfTurn tp_turn{tcur + (2 * tp + un.half) * sc.nn, sc.pd * ta + pr.p, tbroken, g.err};
             if (!DET && sc.sw) {  // the step ends with a switch: the tiles of X'^H, to the panels 2 tp (+ half), + 1 of the other orientation (LDS-resident: w = nt)
               lds_double* const dsw = (lds_double*)(XL + ob + (2 * tp + un.half) * (a2 * TILE) + q * TILE + j);
-              if (has1) qkf_p2_switch<true>(T0, T1, fr, true, a_stream(sc, v), 4, sc.nn, kmax, dsw, 2 * a2 * TILE, nxt);
-              else qkf_p2_switch<false>(T0, T1, fr, true, a_stream(sc, v), 4, sc.nn, kmax, dsw, 0, nxt);
+              constexpr int FORM = QKF_P2_FORM_DUAL;
+              if (FORM != 0 && kmax == 4) {
+                if (has1) qkf_p2_switch<true, true, FORM>(T0, T1, fr, true, a_stream(sc, v), 4, sc.nn, 4, dsw, 2 * a2 * TILE, nxt);
+                else qkf_p2_switch<true, false, FORM>(T0, T1, fr, true, a_stream(sc, v), 4, sc.nn, 4, dsw, 0, nxt);
+              } else {
+                if (has1) qkf_p2_switch<false, true, FORM>(T0, T1, fr, true, a_stream(sc, v), 4, sc.nn, kmax, dsw, 2 * a2 * TILE, nxt);
+                else qkf_p2_switch<false, false, FORM>(T0, T1, fr, true, a_stream(sc, v), 4, sc.nn, kmax, dsw, 0, nxt);
+              }
             } else if (has1) {
               if (kmax == 4) qkf_p2_dual<true, true, DET>(T0, T1, fr, fs, a_stream(sc, v), w * QKF_XBLOCK, sc.nn, 4, xo, q, j, nxt, np1, nd1, tp_turn);
               else qkf_p2_dual<false, true, DET>(T0, T1, fr, fs, a_stream(sc, v), w * QKF_XBLOCK, sc.nn, kmax, xo, q, j, nxt, np1, nd1, tp_turn);

@@ -91,6 +91,27 @@ def assoc_pairs(x_true, y_true, pairs, ek, shape, assoc, switch_price=SWITCH_PRI
     return masks, instr, steps, switches, flags
 
 
+ONESUM_CASES = {"nn_1": 1, "nn_2": 2, "nn_odd": 4, "nn_even": 8, "kmax_1": 16, "kmax_2": 32, "kmax_3": 64, "kmax_4": 128, "single_tile": 256, "tile_pair": 512,
+                "plain_step": 1024, "merged_step": 2048, "strip_step": 4096}  # tools/assoc_capi.cpp: qk_onesum_pairs
+
+
+def onesum_pairs(x_true, y_true, pairs, ek, shape, assoc, switch_price=SWITCH_PRICE):
+    """What the column blocks of phase 2 meet on the chains of the pairs (segmentation and association as assoc_pairs makes them):
+    (cases [pairs][2] -- ONESUM_CASES of the ordinary steps, of the switch steps --, blocks [pairs][2]: column blocks of the ordinary and of
+    the switch steps, per unit of the shape) under a launch shape."""
+    x_true = np.ascontiguousarray(x_true, dtype=np.int32)
+    y_true = np.ascontiguousarray(y_true, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    n = pairs.shape[0]
+    cases, blocks = np.zeros((n, 2), dtype=np.int32), np.zeros((n, 2), dtype=np.int64)
+    xcap, cap, dual = SHAPES[shape]
+    fn = assoc_lib().qk_onesum_pairs
+    fn.restype = None
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + [C.c_int32] * 6 + [C.c_void_p] * 2
+    fn(x_true.ctypes.data, y_true.ctypes.data, x_true.shape[1] - 1, pairs.ctypes.data, n, int(ek), xcap, cap, dual, int(assoc), int(switch_price), cases.ctypes.data, blocks.ctypes.data)
+    return cases, blocks
+
+
 def merged_steps(masks):
     """merged steps per pair: the bits of its mask (the first two words)"""
     return np.array([bin(int(r[0])).count("1") + bin(int(r[1])).count("1") for r in masks])
