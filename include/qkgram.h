@@ -374,6 +374,30 @@ int qk_pauli_strings_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_strings,
                           const uint8_t* strings /* [n_strings][n_sites], codes 0..3 = I, X, Y, Z */,
                           double* out /* [n_states][n_strings] */, double* norms /* [n_states], may be NULL */);
 
+/* Expectation values of strings of single-site operators for every state of a set, synchronous on the context's stream: the
+ * Pauli strings above with any 2 x 2 complex matrix at a site.  The call brings a table of n_ops operators, 1 <= n_ops <= 255,
+ * ops[c - 1][s'][s] = (Re, Im) of <s'| O_c |s> for the code c = 1 .. n_ops; code 0 is the identity and costs no work.  A string
+ * is c[0 .. n_sites - 1] (site k = qubit k, physical index 0 = |0>; the states need not be normalised):
+ *     out[state][m] = <psi| O_c[0] (x) ... (x) O_c[n-1] |psi> / <psi|psi>                                     (complex: Re, Im)
+ *                   = sum psi(..s_k..) conj(psi(..s'_k..)) prod_k O_c[k][s'_k][s_k] / <psi|psi>
+ * With the table (X, Y, Z) it is qk_pauli_strings_host's value, to rounding, and an imaginary part of rounding size; with
+ * projectors it is the probability of an outcome on the measured qubits, the others traced out (the real part; a probability
+ * of exactly 0 may come out as rounding noise of either sign).  The operators need not be Hermitian or unitary.  The chain is
+ * that of the Pauli strings: L_a, per site of the support [a, b] the two GEMMs of a transfer step and, where the code is not 0,
+ * an elementwise pass T'[(a, s')] = sum_s O[s'][s] T[(a, s)], then the complex sum of E_{b+1} R_{b+1}.  A string costs work on
+ * its support only, whatever its operators: the cost of a Pauli string of the same support.  An all-identity string is written
+ * as exactly (1.0, 0.0); duplicates are allowed.  n_sites = 1 is valid.  norms, when given, are the bits qk_local_paulis_host
+ * returns.  The value of a (state, string) is the same bits whatever the other states of the set, the other strings of the
+ * call and their order, the other operators of the table, however the call was cut into batches, and from run to run.
+ * Device scratch, batching and qk_ctx_trim are those of qk_pauli_strings_host (a chain's chunk sums are two doubles wide);
+ * QK_OPSTR_BATCH=<k> (read per call) caps the (state, string) chains of a batch at k.
+ * QK_EINVAL: a null ctx, set, ops, strings or out; a set of another context; a complex64 set; n_strings < 1; n_ops outside
+ * 1 .. 255; a table entry that is not finite (the message names the operator and the position); a code above n_ops (the message
+ * names the string and the site); QK_OPSTR_BATCH < 1.  QK_EDEVICE: a state of norm 0 (the message names the state).          */
+int qk_operator_strings_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_ops, const double* ops /* [n_ops][2][2][2] re, im */,
+                             int32_t n_strings, const uint8_t* strings /* [n_strings][n_sites], codes 0 .. n_ops */,
+                             double* out /* [n_states][n_strings][2] */, double* norms /* [n_states], may be NULL */);
+
 /* The Gram of any real feature columns (host arrays [n][n_features], for instance qk_pauli_strings_host's output), synchronous:
  *     out[j * ld + i] = exp(-g * sum_m (fx[i][m] - fy[j][m])^2)
  * Rows, columns, fy = NULL, the fixed summation order (exact symmetry, unit diagonal) and the argument errors are those of

@@ -3,7 +3,7 @@
 // libqkgram.so; entry points qk_local_paulis_host, qk_projected_gram_host, qk_local_pair_paulis_host,
 // qk_projected_pair_gram_host and their forms for pairs up to a chosen distance, qk_local_pair_paulis_dist_host and
 // qk_projected_pair_gram_dist_host, and the general form, expectation values of Pauli strings and the Gram of any feature columns,
-// qk_pauli_strings_host and qk_feature_gram_host, and the entanglement across every bond of a state from the same environments,
+// qk_pauli_strings_host and qk_feature_gram_host, strings of any single-site operators, qk_operator_strings_host, and the entanglement across every bond of a state from the same environments,
 // qk_bond_purities_host and qk_bond_spectra_host (definitions above bond_call below), and the block kernels -- reduced-state
 // overlaps of the first or last w qubits for every pair of two sets -- qk_block_values_host and qk_block_self_host (definitions
 // above BlkSet below), and measurement shots of every state of a set, each shot and qubit in its own Pauli basis, qk_sample_host
@@ -79,6 +79,14 @@
 // names the chain.  4 n_sites launches per chain batch, whatever the number of strings; a string costs work on its support only.  The
 // chunk sums of a chain are added in a fixed order and nothing of a chain depends on another chain, so a value is the same bits
 // whatever the other states and strings, their order and the cut of the batches (QK_STRINGS_BATCH caps the chains of one).
+//
+// Strings of single-site operators (qk_operator_strings_host).  The same chain with any 2 x 2 complex matrix at a site: codes
+// 1 .. n_ops name the operators O_c[s'][s] of a table that comes with the call, 0 is the identity,
+//     E_{k+1}[b'][a'] = sum_{s, s'} O_{c_k}[s'][s] sum_{b,a} E_k[b][a] A_k[b][s][b'] conj(A_k[a][s'][a'])           (k = a .. b)
+//     value = sum_{b', a'} E_{b+1}[b'][a'] R_{b+1}[b'][a'] / L_n[0][0]                                              (complex)
+// The launches, the tasks, the slots and the cut are those of the Pauli strings (one driver, string_chains); the elementwise launch
+// is qk_str_op_kernel (T'[(a, s')] = sum_s O[s'][s] T[(a, s)]) and the closing sum keeps Re and Im (qk_str_closez_kernel,
+// qk_str_valuesz_kernel).  QK_OPSTR_BATCH caps the chains of a batch.
 //
 // The launch kinds, the layout of a state's scratch and of a chain's slot, the pair index, the sizes, the cut into batches and the
 // task lists are host-side planning, in qk_local_plan.h (tested on the CPU).  Every entry point runs on one driver: env_sizes,
@@ -642,6 +650,80 @@ __global__ __launch_bounds__(256) void qk_str_values_kernel(const StrArgs g, con
   out[st * n_strings + m] = v / g.e.scratch[g.e.sbase[i]];
 }
 
+// ---- strings of single-site operators (qk_operator_strings_host) ------------------------------------------------------------------
+// The chain of the Pauli strings with a general 2 x 2 complex matrix at a site and a complex closing sum.
+struct OpArgs {
+  StrArgs s;
+  const double* ops;  // [n_ops][2][2][2]: (re, im) of O_c[s'][s], c = code - 1
+};
+
+// The operator of site k on the ket index of T, in place, rows a of one 16-row chunk: T'[(a, s')] = sum_s O[s'][s] T[(a, s)], both
+// halves of a row pair read, then both written.  Each component is one chain of fused multiply-adds in the written order (s = 0
+// before s = 1, the imaginary factor before the real one), so it is the same bits wherever the chain runs.
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_op_kernel(const OpArgs a) {
+  const StrArgs& g = a.s;
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = t.x, c = t.y;
+  const int i = g.cent[ch], m = g.cstr[ch];
+  const int n = g.e.n_sites, n1 = n + 1, k = g.step;
+  const long long st = g.e.states[i];
+  const int r = g.e.dims[st * n1 + k + 1];
+  const int code = g.strings[(long long)m * n + k];  // 1 .. n_ops: a chain has a task here only where its code is not 0
+  const double* const o = a.ops + 8 * (code - 1);
+  const double ar = o[0], ai = o[1], br = o[2], bi = o[3], cr = o[4], ci = o[5], dr = o[6], di = o[7];  // O = [[a, b], [c, d]]
+  const long long P = g.e.pmax[i], P2 = P * P, tpl = 2 * P2;
+  double* const T = g.slots + g.cbase[ch] + chain_T() * P2;
+  const int cnt = LOC_CHUNK * r;
+  for (int e = threadIdx.x; e < cnt; e += LOC_RED_THREADS) {
+    const long long q0 = (long long)(c * LOC_CHUNK + e / r) * 2 * r + e % r, q1 = q0 + r;
+    const double r0 = T[q0], i0 = T[q0 + tpl], r1 = T[q1], i1 = T[q1 + tpl];
+    T[q0] = fma(br, r1, fma(-bi, i1, fma(ar, r0, -(ai * i0))));
+    T[q0 + tpl] = fma(br, i1, fma(bi, r1, fma(ar, i0, ai * r0)));
+    T[q1] = fma(dr, r1, fma(-di, i1, fma(cr, r0, -(ci * i0))));
+    T[q1 + tpl] = fma(dr, i1, fma(di, r1, fma(cr, i0, ci * r0)));
+  }
+}
+
+// sum_{b', a'} E_{b+1}[b'][a'] R_{b+1}[b'][a'] over one 16-row chunk of b', Re and Im, unnormalised: part[(chain, chunk)][2].  The
+// order of the sum is qk_str_close_kernel's.
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_str_closez_kernel(const OpArgs a) {
+  __shared__ double red[2][LOC_RED_THREADS];
+  const StrArgs& g = a.s;
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = t.x, c = t.y;
+  const int i = g.cent[ch];
+  const int n1 = g.e.n_sites + 1, k = g.step;
+  const long long st = g.e.states[i];
+  const int r = g.e.dims[st * n1 + k + 1];
+  const long long P = g.e.pmax[i], P2 = P * P, rpl = (long long)r * r;
+  const double* const E = g.slots + g.cbase[ch];
+  const double* const R = g.e.scratch + g.e.sbase[i] + g.e.rmul * P2 + g.e.roff[(long long)i * n1 + k + 1];
+  double acc[2] = {};
+  const int rows = LOC_CHUNK * r;
+  for (int e = threadIdx.x; e < rows; e += LOC_RED_THREADS) {
+    const long long q = (long long)c * rows + e;
+    acc[0] += E[q] * R[q] - E[q + P2] * R[q + rpl];
+    acc[1] += E[q] * R[q + rpl] + E[q + P2] * R[q];
+  }
+  tree_sum(red, acc);
+  if (threadIdx.x < 2) g.part[((long long)ch * g.e.max_chunks + c) * 2 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// The values of a chain batch: the chunk sums of each chain in ascending order, divided by L_n[0][0], as (Re, Im).
+__global__ __launch_bounds__(256) void qk_str_valuesz_kernel(const StrArgs g, const int nc, const int n_strings, double* out) {
+  const int ch = blockIdx.x * 256 + threadIdx.x;
+  if (ch >= nc) return;
+  const int i = g.cent[ch], m = g.cstr[ch];
+  const long long st = g.e.states[i];
+  const int chunks = g.e.dims[st * (g.e.n_sites + 1) + g.supp[2 * m + 1] + 1] / LOC_CHUNK;
+  const double* p = g.part + (long long)ch * g.e.max_chunks * 2;
+  double vr = 0, vi = 0;
+  for (int c = 0; c < chunks; ++c) vr += p[2 * c], vi += p[2 * c + 1];
+  const double nrm = g.e.scratch[g.e.sbase[i]];
+  out[2 * (st * n_strings + m)] = vr / nrm;
+  out[2 * (st * n_strings + m) + 1] = vi / nrm;
+}
+
 // tr(M_k^2) = sum_{a, a'} M_k[a][a'] M_k[a'][a] over one 16-row chunk of a (the imaginary parts cancel between (a, a') and its
 // image, so only Re is summed), unnormalised: part[(i, k, chunk)].  M_k is in the T planes, ld = the padded bond.
 __global__ __launch_bounds__(LOC_RED_THREADS) void qk_bond_trace_kernel(const LocArgs g) {
@@ -798,42 +880,59 @@ int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* 
   return QK_OK;
 }
 
-// Pauli strings.  Per state batch the environment pass -- the reversed chain and the forward T / W launches of the one-qubit sweep,
-// then L_{k+1} from W by the sum the rho kernel makes (so L_n[0][0] is that sweep's norm bit for bit), every R_k (k = 1 .. n) and
-// every L_k (k = 0 .. n-1) kept -- then its chains in chain batches (qk_local_plan.h: list_chains, chain_cut, chain_lists).
-int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, const uint8_t* strings, double* out, double* norms) {
-  static const char* what = "qk_pauli_strings_host";
+// Pauli strings and strings of single-site operators: one driver.  Per state batch the environment pass -- the reversed chain and
+// the forward T / W launches of the one-qubit sweep, then L_{k+1} from W by the sum the rho kernel makes (so L_n[0][0] is that
+// sweep's norm bit for bit), every R_k (k = 1 .. n) and every L_k (k = 0 .. n-1) kept -- then its chains in chain batches
+// (qk_local_plan.h: list_chains, chain_cut, chain_lists).  ops == NULL: Pauli strings (codes 0..3, the real part of the closing
+// sum, out [n_states][n_strings]).  ops != NULL: the table [n_ops][2][2][2] of the operator strings (codes 0 .. n_ops, the complex
+// closing sum, out [n_states][n_strings][2]); the two forms differ in the elementwise kernel, the closing kernels and the width of
+// a chain's partial sums, nothing else.
+int string_chains(qk_ctx* c, const qk_mps_set* set, const char* what, const char* range, const char* batch_var, const int32_t n_ops, const double* ops,
+                  const int32_t n_strings, const uint8_t* strings, double* out, double* norms) {
+  const bool general = ops != nullptr;
+  const int vals = general ? 2 : 1;  // doubles of a value and of a chunk sum
   if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
   if (!set) return qk_fail(QK_EINVAL, "%s: set is null", what);
   if (!strings) return qk_fail(QK_EINVAL, "%s: strings is null", what);
   if (!out) return qk_fail(QK_EINVAL, "%s: out is null", what);
   if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
-  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; Pauli strings need an fp64 set", what);
+  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; %s need an fp64 set", what, general ? "operator strings" : "Pauli strings");
   if (n_strings < 1) return qk_fail(QK_EINVAL, "%s: n_strings must be >= 1 (got %d)", what, n_strings);
+  if (general && (n_ops < 1 || n_ops > OPSTR_MAX_OPS)) return qk_fail(QK_EINVAL, "%s: n_ops must be in 1 .. %d (got %d)", what, OPSTR_MAX_OPS, n_ops);
+  for (long long e = 0; general && e < 8ll * n_ops; ++e)
+    if (!std::isfinite(ops[e]))
+      return qk_fail(QK_EINVAL, "%s: ops[%d][%d][%d] (code %d) has a %s part that is not finite", what, (int)(e / 8), (int)(e / 4 % 2), (int)(e / 2 % 2), (int)(e / 8) + 1,
+                     e % 2 ? "imaginary" : "real");
   const int ns = set->n_states, n = set->n_sites;
   if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
   std::vector<int32_t> supp;  // a, b of each string; -1: all identity
-  if (const long long bad = string_supports(strings, n_strings, n, supp); bad >= 0)
+  if (const long long bad = operator_supports(strings, n_strings, n, general ? n_ops : 3, supp); bad >= 0) {
+    if (general) return qk_fail(QK_EINVAL, "%s: strings[%d][%d] = %d is above n_ops = %d (0 = identity, c = ops[c - 1])", what, (int)(bad / n), (int)(bad % n), strings[bad], n_ops);
     return qk_fail(QK_EINVAL, "%s: strings[%d][%d] = %d is not a Pauli code (0..3 = I, X, Y, Z)", what, (int)(bad / n), (int)(bad % n), strings[bad]);
-  long long cap = 0;  // chains per batch; 0: the memory rule alone
-  if (const char* v = std::getenv("QK_STRINGS_BATCH")) {
-    cap = std::atoll(v);
-    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_STRINGS_BATCH must be >= 1 (got \"%s\")", what, v);
   }
-  QkRangeGuard range_("qk:pauli_strings");
+  long long cap = 0;  // chains per batch; 0: the memory rule alone
+  if (const char* v = std::getenv(batch_var)) {
+    cap = std::atoll(v);
+    if (cap < 1) return qk_fail(QK_EINVAL, "%s: %s must be >= 1 (got \"%s\")", what, batch_var, v);
+  }
+  QkRangeGuard range_(range);
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   EnvSizes z;
   env_sizes(set->dims_true.data(), ns, n, set->max_pad, LOC_RMUL, true, z);
   const int max_chunks = z.max_chunks;
   const size_t b_str = al256((size_t)n_strings * n), b_supp = al256(supp.size() * sizeof(int32_t));
-  QkDevBuf rev, dout, dnorm, dstr;
+  QkDevBuf rev, dout, dnorm, dstr, dops;
   HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
-  HIP_TRY_AS(what, dout.alloc((size_t)ns * n_strings * sizeof(double)));
+  HIP_TRY_AS(what, dout.alloc((size_t)ns * n_strings * vals * sizeof(double)));
   HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
   HIP_TRY_AS(what, dstr.alloc(b_str + b_supp));
   HIP_TRY_AS(what, hipMemcpy(dstr.get<char>(), strings, (size_t)n_strings * n, hipMemcpyHostToDevice));
   HIP_TRY_AS(what, hipMemcpy(dstr.get<char>() + b_str, supp.data(), supp.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (general) {
+    HIP_TRY_AS(what, dops.alloc((size_t)n_ops * 8 * sizeof(double)));
+    HIP_TRY_AS(what, hipMemcpy(dops.get(), ops, (size_t)n_ops * 8 * sizeof(double), hipMemcpyHostToDevice));
+  }
   // memory bound of a state batch (environments and the slots of its live chains): a quarter of what is free; the environments
   // of a batch take at most half of that (at least one state per batch), the chains of a batch the rest (at least one chain)
   long long budget = 0;
@@ -848,7 +947,9 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
     env_tables(z, plan, s0, nb, 0, eb);
     // the chains of the state batch, cut into chain batches: consecutive chains while their slots, partial sums and tasks fit
     // what the environments leave, and at most QK_STRINGS_BATCH of them
-    const Chains ch = list_chains(z, s0, nb, n_strings, strings, supp);
+    Chains ch = list_chains(z, s0, nb, n_strings, strings, supp);
+    if (general)
+      for (long long& w : ch.weight) w += max_chunks;  // a chunk sum is (Re, Im)
     const std::vector<size_t> cstart = chain_cut(ch.weight, budget - eb.tot, cap);
     struct ChainBytes { size_t cent, cstr, cbase, tasks, part, slots; size_t tab() const { return cent + cstr + cbase + tasks; } };
     auto slot = [&](const size_t e) { return (long long)chain_size() * z.pmax[s0 + ch.cent[e]] * z.pmax[s0 + ch.cent[e]]; };
@@ -857,7 +958,7 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
       for (size_t e = c0; e < c1; ++e) nt += ch.ntasks[e], sl += slot(e);
       const size_t nc = c1 - c0;
       return ChainBytes{al256(nc * sizeof(int32_t)), al256(nc * sizeof(int32_t)), al256(nc * sizeof(int64_t)), al256((size_t)nt * sizeof(int2)),
-                        al256(nc * max_chunks * sizeof(double)), (size_t)sl * sizeof(double)};
+                        al256(nc * max_chunks * vals * sizeof(double)), (size_t)sl * sizeof(double)};
     };
     size_t b_chain = 0;
     for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
@@ -868,7 +969,9 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
     if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, b_chain)) return rc;
     qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(eb.g, nb, dnorm.get<double>());
     HIP_TRY_AS(what, hipGetLastError());
-    StrArgs q{};
+    OpArgs qa{};
+    qa.ops = dops.get<double>();
+    StrArgs& q = qa.s;
     q.e = eb.g;
     q.strings = dstr.get<uint8_t>();
     q.supp = reinterpret_cast<const int32_t*>(dstr.get<char>() + b_str);
@@ -903,20 +1006,32 @@ int pauli_strings(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, con
         const dim3 grid((unsigned)(first[li + 1] - first[li]));
         if (kind == STR_T) qk_str_gemm_kernel<false><<<grid, dim3(512), 0, c->stream>>>(q);
         else if (kind == STR_X) qk_str_gemm_kernel<true><<<grid, dim3(512), 0, c->stream>>>(q);
-        else if (kind == STR_PAULI) qk_str_pauli_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
-        else qk_str_close_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+        else if (kind == STR_PAULI && !general) qk_str_pauli_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+        else if (kind == STR_PAULI) qk_str_op_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(qa);
+        else if (!general) qk_str_close_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+        else qk_str_closez_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(qa);
       }
-      qk_str_values_kernel<<<dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)nc, n_strings, dout.get<double>());
+      if (!general) qk_str_values_kernel<<<dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)nc, n_strings, dout.get<double>());
+      else qk_str_valuesz_kernel<<<dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)nc, n_strings, dout.get<double>());
       HIP_TRY_AS(what, hipGetLastError());
       HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
     }
     HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   }
-  HIP_TRY_AS(what, hipMemcpy(out, dout.get(), (size_t)ns * n_strings * sizeof(double), hipMemcpyDeviceToHost));
+  if (general) {  // a value divides by <psi|psi> (a norm that is NaN marks its own row, as the Pauli strings do)
+    std::vector<double> h_norm((size_t)ns);
+    HIP_TRY_AS(what, hipMemcpy(h_norm.data(), dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+    for (int s = 0; s < ns; ++s)
+      if (h_norm[s] == 0.0) return qk_fail(QK_EDEVICE, "%s: state %d has norm 0: its expectation values are undefined", what, s);
+  }
+  HIP_TRY_AS(what, hipMemcpy(out, dout.get(), (size_t)ns * n_strings * vals * sizeof(double), hipMemcpyDeviceToHost));
   if (norms) HIP_TRY_AS(what, hipMemcpy(norms, dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
   for (int m = 0; m < n_strings; ++m)  // an all-identity string is exactly 1
     if (supp[2 * m] < 0)
-      for (int s = 0; s < ns; ++s) out[(size_t)s * n_strings + m] = 1.0;
+      for (int s = 0; s < ns; ++s) {
+        out[((size_t)s * n_strings + m) * vals] = 1.0;
+        if (general) out[((size_t)s * n_strings + m) * vals + 1] = 0.0;
+      }
   return QK_OK;
 }
 
@@ -2894,7 +3009,12 @@ extern "C" int qk_bond_spectra_host(qk_ctx* c, const qk_mps_set* set, int32_t ma
 }
 
 extern "C" int qk_pauli_strings_host(qk_ctx* c, const qk_mps_set* set, int32_t n_strings, const uint8_t* strings, double* out, double* norms) {
-  return pauli_strings(c, set, n_strings, strings, out, norms);
+  return string_chains(c, set, "qk_pauli_strings_host", "qk:pauli_strings", "QK_STRINGS_BATCH", 0, nullptr, n_strings, strings, out, norms);
+}
+extern "C" int qk_operator_strings_host(qk_ctx* c, const qk_mps_set* set, int32_t n_ops, const double* ops, int32_t n_strings, const uint8_t* strings, double* out,
+                                        double* norms) {
+  if (!ops) return qk_fail(QK_EINVAL, "qk_operator_strings_host: ops is null");
+  return string_chains(c, set, "qk_operator_strings_host", "qk:operator_strings", "QK_OPSTR_BATCH", n_ops, ops, n_strings, strings, out, norms);
 }
 
 extern "C" int qk_feature_gram_host(qk_ctx* c, int32_t n_features, int32_t nx, const double* fx, int32_t ny, const double* fy, double g, double* out, int64_t ld) {

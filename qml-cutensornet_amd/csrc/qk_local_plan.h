@@ -44,7 +44,9 @@ enum LocKind : int {
   LOC_BOND_TR = -5,   // qk_bond_trace_kernel: tr(M_k^2) of bond k = step in 16-row chunks
   STR_LNEXT = -6,     // qk_str_lnext_kernel (environment pass): L_{k+1} = W_0[.][(0, .)] + W_1[.][(1, .)], kept
   STR_PAULI = -7,     // qk_str_pauli_kernel: T[a][(s ^ f, b')] <- i^e(s) T[a][(s, b')] of the chains whose code at site k is not I
-  STR_CLOSE = -8,     // qk_str_close_kernel: sum E_{b+1} R_{b+1} of the chains whose support ends at site k
+                      // (operator strings: qk_str_op_kernel, T[a][(s', b')] <- sum_s O[s'][s] T[a][(s, b')], on the same tasks)
+  STR_CLOSE = -8,     // qk_str_close_kernel: sum E_{b+1} R_{b+1} of the chains whose support ends at site k (operator strings:
+                      // qk_str_closez_kernel, Re and Im, on the same tasks)
   BLK_RED = -9,       // qk_blk_reduce_kernel: Re sum Rx[a][a'] conj(W[a][a']) of a chosen cut in 16-row chunks
   SMP_W = 15,         // shot chain (state, shot tile), site k: W[row][(t, b')] = sum_b V[b][row] A_k[b][(t, b')], shot rows as M
   SMP_Q = 16,         // shot chain: Q[(o, row)][a'] = sum_b' W'_o[row][b'] R_{k+1}[b'][a'], the stacked operand [W'_0 ; W'_1] as M
@@ -252,17 +254,24 @@ inline void env_tables(const EnvSizes& z, const Plan& plan, const int s0, const 
 // A string is codes[0 .. n-1], 0..3 = I, X, Y, Z; its support [a, b] = its first and last non-identity sites.  A chain is one
 // (state, string) with a non-identity site.
 // supp[2m], supp[2m + 1] = a, b of string m (-1, -1: all identity).  Returns -1, or the index m n + k of the first code above 3.
-inline long long string_supports(const uint8_t* strings, const int n_strings, const int n, std::vector<int32_t>& supp) {
+// operator_supports is the same for the strings of single-site operators (qk_operator_strings_host): code c = 1 .. n_ops names the
+// 2 x 2 matrix ops[c] of the call's table, 0 the identity; it returns -1, or the index m n + k of the first code above n_ops.  The
+// chains below ask only whether a code is 0, so they serve both kinds of string.
+inline long long operator_supports(const uint8_t* strings, const int n_strings, const int n, const int n_ops, std::vector<int32_t>& supp) {
   supp.assign((size_t)2 * n_strings, -1);
   for (int m = 0; m < n_strings; ++m)
     for (int k = 0; k < n; ++k) {
       const int code = strings[(size_t)m * n + k];
-      if (code > 3) return (long long)m * n + k;
+      if (code > n_ops) return (long long)m * n + k;
       if (code && supp[2 * m] < 0) supp[2 * m] = k;
       if (code) supp[2 * m + 1] = k;
     }
   return -1;
 }
+inline long long string_supports(const uint8_t* strings, const int n_strings, const int n, std::vector<int32_t>& supp) {
+  return operator_supports(strings, n_strings, n, 3, supp);
+}
+constexpr int OPSTR_MAX_OPS = 255;  // operators of a table: the codes of a string are bytes
 constexpr int CHAIN_KINDS[4] = {STR_T, STR_PAULI, STR_X, STR_CLOSE};  // the launches of a site of the chain pass, in stream order
 // the blocks of a chain (p = its state's padded bonds, codes = its string, [a, b] its support) in the launch `kind` of site k
 inline int chain_task_count(const int kind, const int k, const int32_t* p, const uint8_t* codes, const int a, const int b, const int n) {

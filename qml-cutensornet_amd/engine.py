@@ -102,6 +102,7 @@ _SIGNATURES = [
     ("qk_local_pair_paulis_dist_host", C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     ("qk_projected_pair_gram_dist_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_pauli_strings_host", C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
+    ("qk_operator_strings_host", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     ("qk_feature_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_bond_purities_host", C.c_int, [_P, _P, _P, _P]),
     ("qk_bond_spectra_host", C.c_int, [_P, _P, C.c_int32, _P, _P]),
@@ -661,6 +662,133 @@ def pauli_strings(n_sites: int, specs) -> np.ndarray:
     if not rows:
         raise ValueError("the list of Pauli strings is empty")
     return np.ascontiguousarray(np.stack(rows))
+
+
+def _local_ops() -> dict:
+    h = 0.5
+    return {
+        "I": [[1, 0], [0, 1]], "X": [[0, 1], [1, 0]], "Y": [[0, -1j], [1j, 0]], "Z": [[1, 0], [0, -1]],
+        "0": [[1, 0], [0, 0]], "1": [[0, 0], [0, 1]],            # (I +- Z) / 2
+        "+": [[h, h], [h, h]], "-": [[h, -h], [-h, h]],          # (I +- X) / 2
+        "R": [[h, -h * 1j], [h * 1j, h]], "L": [[h, h * 1j], [-h * 1j, h]],  # (I +- Y) / 2
+        "01": [[0, 1], [0, 0]], "10": [[0, 0], [1, 0]],          # |0><1|, |1><0|
+    }
+
+
+# Named single-site operators, O[s'][s] = <s'|O|s>: the Paulis, the six projectors onto the +1 / -1 eigenstates of Z ("0", "1"), X
+# ("+", "-") and Y ("R", "L") -- eigenvalue +1 is outcome bit 0, as in the sampler -- and the two ladder operators.
+LOCAL_OPS = {name: np.array(m, dtype=np.complex128) for name, m in _local_ops().items()}
+OPERATOR_TABLE_MAX = 255  # operators of one table (qk_operator_strings_host): a code is a byte
+_PROJECTOR_NAMES = (("+", "-"), ("R", "L"), ("0", "1"))  # basis code 1..3 = X, Y, Z -> the names of outcome bit 0, 1
+
+
+def _operator_table(table) -> np.ndarray:
+    try:
+        t = np.asarray(table, dtype=np.complex128)
+    except (TypeError, ValueError):
+        raise ValueError("the operator table is not an array of 2 x 2 complex matrices") from None
+    if t.ndim != 3 or t.shape[1:] != (2, 2) or not 1 <= t.shape[0] <= OPERATOR_TABLE_MAX:
+        raise ValueError(f"the operator table must have shape (n_ops, 2, 2) with 1 <= n_ops <= {OPERATOR_TABLE_MAX}, got {t.shape}")
+    if not np.isfinite(t).all():
+        c, sp, s0 = (int(v) for v in np.argwhere(~np.isfinite(t.real) | ~np.isfinite(t.imag))[0])
+        raise ValueError(f"operator {c + 1} of the table has an entry [{sp}][{s0}] that is not finite")
+    return np.ascontiguousarray(t)
+
+
+def operator_strings(n_sites: int, specs, ops=None):
+    """Strings of single-site operators as ``(table, codes)`` for ``Context.operator_expectations`` and
+    ``MPS.operator_expectation``: ``table`` complex128 (n_ops, 2, 2) with ``table[c - 1][s'][s] = <s'|O_c|s>`` and ``codes`` uint8
+    (m, n_sites), code 0 = the identity, code c = ``table[c - 1]`` on qubit k.  A spec is a pair ``(names, qubits)`` with distinct
+    qubits in range, identity elsewhere: ``names`` is a ``str`` of one-letter names (``("0+R", (1, 4, 5))``) or a sequence of
+    names (``(("01", "10"), (2, 7))``), taken from ``ops`` first -- a dict ``{name: 2 x 2 array}`` -- and then from ``LOCAL_OPS``;
+    the table holds the operators that are used, in the order of first use, and ``"I"`` is code 0.  With ``ops`` an array
+    (n_ops, 2, 2), a spec is an integer row of ``n_sites`` codes 0 .. n_ops into that table (an integer array (m, n_sites) is a
+    list of rows) and the table is returned as it is.  Raises ``ValueError`` that names the offending spec otherwise."""
+    n = int(n_sites)
+    if n < 1:
+        raise ValueError(f"n_sites must be >= 1 (got {n_sites!r})")
+    if isinstance(specs, str) or (isinstance(specs, tuple) and len(specs) == 2 and isinstance(specs[0], str) and not isinstance(specs[1], str)):
+        raise ValueError(f"operator_strings takes a list of specs, got the single spec {specs!r}")
+    user_table = None
+    named = {}
+    if isinstance(ops, dict):
+        for name, mat in ops.items():
+            try:
+                m = np.asarray(mat, dtype=np.complex128)
+            except (TypeError, ValueError):
+                m = None
+            if not isinstance(name, str) or not name or m is None or m.shape != (2, 2) or not np.isfinite(m).all():
+                raise ValueError(f"ops[{name!r}] is not a finite 2 x 2 matrix under a non-empty str name")
+            named[name] = m
+    elif ops is not None:
+        user_table = _operator_table(ops)
+    table, code_of, rows = [], {}, []
+
+    def code(name, bad):
+        if name not in named and name not in LOCAL_OPS:
+            raise bad
+        if name not in named and name == "I":
+            return 0
+        if name not in code_of:
+            if len(table) == OPERATOR_TABLE_MAX:
+                raise ValueError(f"the specs use more than {OPERATOR_TABLE_MAX} distinct operators (at {name!r})")
+            table.append(named[name] if name in named else LOCAL_OPS[name])
+            code_of[name] = len(table)
+        return code_of[name]
+
+    for spec in specs:
+        top = len(user_table) if user_table is not None else 0
+        bad = ValueError(f"bad operator string {spec!r}: want a pair (names, qubits) with distinct qubits in 0 .. {n - 1} and names from ops or LOCAL_OPS"
+                         + (f", or {n} integer codes 0..{top} into the table" if user_table is not None else ""))
+        row = np.zeros(n, dtype=np.uint8)
+        if isinstance(spec, tuple) and len(spec) == 2 and (isinstance(spec[0], str) or (isinstance(spec[0], (tuple, list)) and all(isinstance(v, str) for v in spec[0]))):
+            if user_table is not None:
+                raise bad
+            names, qubits = spec
+            try:
+                qubits = [int(q) for q in qubits]
+            except (TypeError, ValueError):
+                raise bad from None
+            if len(qubits) != len(names) or len(set(qubits)) != len(qubits) or any(not 0 <= q < n for q in qubits):
+                raise bad
+            for name, q in zip(names, qubits):
+                row[q] = code(name, bad)
+        else:
+            try:
+                codes = np.asarray(spec)
+            except (TypeError, ValueError):
+                raise bad from None
+            if user_table is None or codes.dtype.kind not in "iu" or codes.shape != (n,) or codes.min() < 0 or codes.max() > top:
+                raise bad
+            row[:] = codes
+        rows.append(row)
+    if not rows:
+        raise ValueError("the list of operator strings is empty")
+    if user_table is None:
+        user_table = np.stack(table) if table else LOCAL_OPS["I"][None].copy()  # only identities: a table must not be empty
+    return np.ascontiguousarray(user_table), np.ascontiguousarray(np.stack(rows))
+
+
+def marginal_strings(bits, bases, n_sites: int):
+    """The projector strings of outcome marginals, as ``(table, codes)`` of ``operator_strings``: ``bits`` (n_strings, n_sites) of
+    0 / 1, ``bases`` (n_strings, n_sites) or one shared row of codes 0..3 -- 0: not measured (traced out; the bit there is
+    ignored), 1, 2, 3: measured in X, Y, Z.  The table is the six projectors in the order ``+ - R L 0 1``: code ``2 (basis - 1) +
+    bit + 1``.  Raises ``ValueError`` that names ``bits`` or ``bases`` otherwise."""
+    n = int(n_sites)
+    b = np.asarray(bits)
+    if b.dtype.kind not in "iub" or b.ndim != 2 or b.shape[1] != n or b.shape[0] < 1:
+        raise ValueError(f"bits must be an integer array of shape (n_strings >= 1, {n}); got shape {b.shape}, dtype {b.dtype}")
+    B = np.asarray(bases)
+    if B.dtype.kind not in "iu" or B.shape not in ((n,), b.shape):
+        raise ValueError(f"bases must be an integer row of length {n} or an integer array of shape {b.shape}; got shape {B.shape}, dtype {B.dtype}")
+    if B.min() < 0 or B.max() > 3:
+        raise ValueError(f"bases holds a code outside 0..3 = not measured, X, Y, Z ({int(B.min() if B.min() < 0 else B.max())})")
+    B = np.broadcast_to(B, b.shape)
+    if ((b < 0) | (b > 1))[B > 0].any():
+        raise ValueError("bits holds a value that is not 0 or 1 on a measured qubit")
+    table = np.stack([LOCAL_OPS[name] for pair in _PROJECTOR_NAMES for name in pair])
+    codes = np.where(B > 0, 2 * (B.astype(np.int64) - 1) + (b.astype(np.int64) & 1) + 1, 0).astype(np.uint8)
+    return table, np.ascontiguousarray(codes)
 
 
 def _spectra_array(spectra) -> np.ndarray:
@@ -1699,6 +1827,36 @@ class Context:
         nrm = np.zeros(ns, dtype=np.float64)
         _check(lib().qk_pauli_strings_host(self._h, mps_set.handle, S.shape[0], S.ctypes.data, V.ctypes.data, nrm.ctypes.data), "qk_pauli_strings_host")
         return (V, nrm) if norms else V
+
+    def operator_expectations(self, xs: MpsSet, strings, ops=None, norms: bool = False):
+        """Expectation values ``<psi| O_0 (x) ... (x) O_{n-1} |psi> / <psi|psi>`` of strings of single-site operators for every
+        state of an fp64 set: complex128 of shape (n_states, m), column j the j-th string; with ``norms=True`` also <psi|psi> of
+        each state (the bits of ``local_paulis``), as ``(V, norms)``.  ``strings`` and ``ops`` are what
+        ``operator_strings(n_sites, strings, ops)`` takes: specs ``(names, qubits)`` over ``LOCAL_OPS`` and a dict of 2 x 2
+        matrices, or rows of codes into a table ``ops`` of shape (n_ops, 2, 2) (code c = ``ops[c - 1]``, 0 = identity).  The
+        operators need not be Hermitian.  A string costs the work of a Pauli string of the same support; an all-identity row is
+        exactly 1 + 0j; a value is the same bits whatever the other states, strings and operators of the call.  Synchronous."""
+        info = xs.info()
+        ns, n = info["n_states"], info["n_sites"]
+        table, codes = operator_strings(n, strings, ops)
+        planes = np.ascontiguousarray(table).view(np.float64)
+        V = np.zeros((ns, codes.shape[0], 2), dtype=np.float64)
+        nrm = np.zeros(ns, dtype=np.float64)
+        _check(lib().qk_operator_strings_host(self._h, xs.handle, table.shape[0], planes.ctypes.data, codes.shape[0], codes.ctypes.data, V.ctypes.data,
+                                               nrm.ctypes.data), "qk_operator_strings_host")
+        V = V[..., 0] + 1j * V[..., 1]
+        return (V, nrm) if norms else V
+
+    def marginals(self, xs: MpsSet, bits, bases):
+        """Probabilities of partial outcomes for every state of an fp64 set, the unmeasured qubits traced out: float64 of shape
+        (n_states, n_strings).  ``bits`` is (n_strings, n_sites) of 0 / 1 (bit 0 = eigenvalue +1, as in ``sample``); ``bases`` is
+        (n_strings, n_sites), or one row shared by every string, of codes 0..3: 0 = not measured (the bit there is ignored), 1,
+        2, 3 = measured in X, Y, Z.  The result is the real part of the projector string (``operator_expectations`` with
+        ``marginal_strings``) and is not clipped: a probability of exactly 0 may come out as rounding noise of either sign.  A
+        row with no measured qubit is exactly 1.0.  Synchronous."""
+        n = xs.info()["n_sites"]
+        table, codes = marginal_strings(bits, bases, n)
+        return np.ascontiguousarray(self.operator_expectations(xs, codes, ops=table).real)
 
     def sample(self, xs: MpsSet, shots: int, bases=None, seed: int = 0, first_state: int = 0, logp: bool = False):
         """Measurement shots of every state of an fp64 set, by perfect sampling along the chain: ``bits``, uint8 of shape

@@ -824,6 +824,44 @@ def build_outcome_likelihoods(mpi_comm, ansatz, X, bits, bases=None, per_state=F
     return out if is_root else None
 
 
+def build_outcome_marginals(mpi_comm, ansatz, X, bits, bases, truncation_error=None):
+    """Probabilities of partial outcomes under the states of ``X`` -- hardware shots read out on a subset of the qubits, in any
+    bases, the other qubits traced out: ``p[i, j] = <psi(x_i)| prod_k P_k |psi(x_i)> / <psi|psi>`` with ``P_k`` the projector of
+    bit ``bits[j, k]`` in the basis ``bases[j, k]`` on every measured qubit.  Each rank builds its share of the states (same
+    builders, same ``QK_BUILDER`` rules as ``build_projected_kernel_matrix``), computes the marginals of its states on its device
+    (``Context.marginals``) and the rows are all-gathered, never an MPS.  ``bits`` is (n_strings, n_qubits) of 0 / 1, ``bases``
+    (n_strings, n_qubits) or one shared row of codes 0..3 (0 = not measured, 1, 2, 3 = X, Y, Z), both shared by every state.  Rank
+    0 returns float64 (len(X), n_strings), the other ranks ``None``; a row is the same bits for any number of ranks.  The values
+    are not clipped: a probability of exactly 0 may come out as rounding noise of either sign."""
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    X = np.asarray(X, dtype=np.float64)
+    n_qubits = int(ansatz.num_qubits)
+    table, codes = _engine.marginal_strings(bits, bases, n_qubits)  # raises ValueError that names bits or bases
+    n_strings = codes.shape[0]
+    fidelity = 1.0 - float(truncation_error)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: outcome marginals have no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    ctx = _engine.default_context(device_id)
+    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
+    lo, local, _, _ = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers)
+    ctx.trim()  # the device builder's arena goes back before the chains need memory
+    if local is None:
+        p = np.zeros((0, n_strings), dtype=np.float64)
+    else:
+        p = np.ascontiguousarray(ctx.operator_expectations(local, codes, ops=table).real)
+        local.close()
+    out = _gather_features(mpi_comm, lo, p, len(X))
+    return out if is_root else None
+
+
 def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64), max_discard=0.0, truncation_error=None, info_file=None, loglevel=30):
     """The Gram ``K`` of ``build_kernel_matrix`` and, from the SAME states, the Gram under each bond cap of ``caps``: one build, then
     per cap every rank compresses its share on its device (``Context.compress``: one canonical truncation sweep per state, at

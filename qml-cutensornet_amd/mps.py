@@ -212,6 +212,62 @@ class MPS:
         rho = np.einsum("ab,asc,cd,btd->st", L, M, R, M.conj(), optimize=True)
         return rho / np.trace(rho).real
 
+    def operator_expectation(self, table, codes) -> np.ndarray:
+        """Expectation values ``<psi| O_0 (x) ... (x) O_{n-1} |psi> / <psi|psi>`` of strings of single-site operators on the host,
+        complex128 of shape (m,) (``()`` for a single row of codes): the numpy mirror of ``Context.operator_expectations``.
+        ``table`` is (n_ops, 2, 2) with ``table[c - 1][s'][s] = <s'|O_c|s>``, ``codes`` (n,) or (m, n) of codes 0 .. n_ops (0 =
+        identity), as ``engine.operator_strings`` makes them.  A plain environment loop: every L_k and R_k in the X[ket][bra]
+        orientation, then per string ``E = L_a``, ``E <- sum_{s,s'} O[s'][s] A^s^T E conj(A^s')`` over the support [a, b] and
+        ``sum E R_{b+1} / <psi|psi>``.  An all-identity row is exactly 1 + 0j.  The state need not be normalised; a state of norm 0
+        raises ``ValueError``."""
+        from .engine import _operator_table
+
+        n = len(self.tensors)
+        t = _operator_table(table)
+        c = np.asarray(codes)
+        single = c.ndim == 1
+        if single:
+            c = c[None, :]
+        if c.dtype.kind not in "iu" or c.ndim != 2 or c.shape[1] != n or c.shape[0] < 1:
+            raise ValueError(f"codes must be an integer array of shape ({n},) or (m >= 1, {n}); got shape {np.shape(codes)}, dtype {c.dtype}")
+        if c.min() < 0 or c.max() > len(t):
+            raise ValueError(f"codes holds a value outside 0 .. n_ops = {len(t)} ({int(c.min() if c.min() < 0 else c.max())})")
+        ts = [np.asarray(a, dtype=np.complex128) for a in self.tensors]
+        L, R = [None] * (n + 1), [None] * (n + 1)  # [ket][bra] at bond k
+        L[0] = np.ones((1, 1), dtype=np.complex128)
+        R[n] = np.ones((1, 1), dtype=np.complex128)
+        for k in range(n):
+            L[k + 1] = np.einsum("ab,asc,bsd->cd", L[k], ts[k], ts[k].conj(), optimize=True)
+        for k in range(n - 1, -1, -1):
+            R[k] = np.einsum("asc,cd,bsd->ab", ts[k], R[k + 1], ts[k].conj(), optimize=True)
+        norm = float(L[n][0, 0].real)
+        if norm == 0.0:
+            raise ValueError("operator_expectation: the state has norm 0")
+        out = np.ones(c.shape[0], dtype=np.complex128)
+        for m, row in enumerate(c):
+            supp = np.flatnonzero(row)
+            if supp.size == 0:
+                continue
+            E = L[supp[0]]
+            for k in range(supp[0], supp[-1] + 1):
+                if row[k]:
+                    E = np.einsum("ab,asc,ts,btd->cd", E, ts[k], t[row[k] - 1], ts[k].conj(), optimize=True)
+                else:
+                    E = np.einsum("ab,asc,bsd->cd", E, ts[k], ts[k].conj(), optimize=True)
+            out[m] = (E * R[supp[-1] + 1]).sum() / norm
+        return out[0] if single else out
+
+    def marginal(self, bits, bases) -> np.ndarray:
+        """Probabilities of partial outcomes on the host, float64 of shape (n_strings,): the numpy mirror of ``Context.marginals``.
+        ``bits`` is (n_strings, n) of 0 / 1 (bit 0 = eigenvalue +1), ``bases`` (n_strings, n) or one shared row of codes 0..3: 0 =
+        not measured (traced out; the bit there is ignored), 1, 2, 3 = X, Y, Z.  The real part of ``operator_expectation`` on
+        ``engine.marginal_strings(bits, bases, n)``; not clipped, so a probability of exactly 0 may come out as rounding noise of
+        either sign.  A row with no measured qubit is exactly 1.0."""
+        from .engine import marginal_strings
+
+        table, codes = marginal_strings(bits, bases, len(self.tensors))
+        return np.ascontiguousarray(self.operator_expectation(table, codes).real)
+
     def sample(self, shots: int, bases=None, seed: int = 0, state_index: int = 0, logp: bool = False, margin: bool = False):
         """Measurement shots of the state on the host, the numpy mirror of ``Context.sample``: ``bits`` uint8 (shots, n), bit 0 =
         eigenvalue +1 of the Pauli (``bases``, anything ``engine.bases_table`` takes; codes 1..3 = X, Y, Z) the qubit was measured

@@ -46,8 +46,14 @@ and amp_over_sample = amplitudes_ms / amp_sample_ms of the same run, and max_abs
 logp_sample|.  amp_flops, from the true bonds at 8 flops per complex multiply-add: per state, site and string the row of W = V (A^0 |
 A^1) (1 x 2 chi_k+1 over chi_k), i.e. S sum 8 (2 chi_k+1 chi_k), plus the environment pass that gives <psi|psi> for logp
 (``local_sweep_flops``).
+``--marginals N`` (with ``--strings`` or ``--strings-file``) adds the marginals of partial outcomes: N projector strings on the
+supports of the tool's Pauli strings (string j takes the support of Pauli string j mod n_strings), random bases X, Y, Z and random bits
+on the measured qubits (seeded), through ctx.marginals(xs, bits, bases), after a warm-up: marginals_ms (the median; marginals_ms_min
+and _max give the spread over the repetitions), n_marginals and sum_support (of the marginal strings: marginals_sum_support), and
+opstr_over_pauli = the time of the Pauli table sent through ctx.operator_expectations on the tool's own strings (opstr_pauli_ms, with
+_min and _max) over pauli_strings_ms of the same run, with max_abs_d_opstr_pauli = max |value - pauli_expectations|.
 usage: python tools/pqk_time.py --config cfg3|cfg4|cfg5 [--gamma G] [--reps N] [--pair-distance D] [--strings N | --strings-file F] [--entanglement] [--compress CHI]
-                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S [--shadow-shots T] [--shot-strings W]] [--window W] [--amplitudes S]"""
+                                [--block-widths W1,W2,... [--block-shots U,M]] [--shots S [--shadow-shots T] [--shot-strings W]] [--window W] [--amplitudes S] [--marginals N]"""
 import argparse
 import json
 import os
@@ -162,11 +168,14 @@ def main():
     ap.add_argument("--shot-strings", type=int, default=0, metavar="W", help="with --shots: also time estimate_window_rdms at width W on the sampled shots")
     ap.add_argument("--window", type=int, default=0, metavar="W", help="also time window_rdms on all windows of W qubits and projected_window_gram")
     ap.add_argument("--amplitudes", type=int, default=0, metavar="S", help="also time amplitudes() with logp on S shots per state drawn with sample()")
+    ap.add_argument("--marginals", type=int, default=0, metavar="N", help="with --strings: also time marginals() on N projector strings on the supports of those strings")
     args = ap.parse_args()
     if args.block_shots and not args.block_widths:
         ap.error("--block-shots needs --block-widths")
     if args.shadow_shots and args.shots <= 0:
         ap.error("--shadow-shots needs --shots (shadow_over_sample compares with its sample_ms)")
+    if args.marginals and not (args.strings > 0 or args.strings_file):
+        ap.error("--marginals needs --strings or --strings-file (it measures on their supports, and opstr_over_pauli compares with their pauli_strings_ms)")
     if args.shot_strings and args.shots <= 0:
         ap.error("--shot-strings needs --shots (it estimates from those shots, and shot_strings_over_sample compares with their sample_ms)")
     if args.shot_strings and not 1 <= args.shot_strings <= engine.WINDOW_MAX_WIDTH:
@@ -215,6 +224,32 @@ def main():
             "n_strings": int(len(S)), "sum_support": int(sum(support)), "pauli_strings_ms": round(strings_ms, 3),
             "feature_gram_ms": round(fgram_ms, 3), "strings_over_local": round(strings_ms / local_ms, 4),
             "median_offdiag_feature_K": float(np.median(KO[off])),
+        })
+    if args.marginals > 0:
+        rng = np.random.default_rng(1)
+        mask = S[np.arange(args.marginals) % len(S)] != 0
+        m_bases = np.where(mask, rng.integers(1, 4, size=mask.shape), 0).astype(np.uint8)
+        m_bits = np.where(mask, rng.integers(0, 2, size=mask.shape), 0).astype(np.uint8)
+
+        def spread(fn):
+            fn()  # warm-up
+            ts = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                out = fn()
+                ts.append(1e3 * (time.perf_counter() - t0))
+            return out, ts
+
+        Pm, ts_m = spread(lambda: ctx.marginals(xs, m_bits, m_bases))
+        pauli_table = np.stack([engine.LOCAL_OPS[name] for name in "XYZ"])
+        Vo, ts_o = spread(lambda: ctx.operator_expectations(xs, S, ops=pauli_table))
+        m_support = [int(np.flatnonzero(c)[-1] - np.flatnonzero(c)[0] + 1) if c.any() else 0 for c in mask]
+        dist.update({
+            "n_marginals": int(args.marginals), "marginals_sum_support": int(sum(m_support)), "marginals_reps": args.reps,
+            "marginals_ms": round(float(np.median(ts_m)), 3), "marginals_ms_min": round(min(ts_m), 3), "marginals_ms_max": round(max(ts_m), 3),
+            "opstr_pauli_ms": round(float(np.median(ts_o)), 3), "opstr_pauli_ms_min": round(min(ts_o), 3), "opstr_pauli_ms_max": round(max(ts_o), 3),
+            "opstr_over_pauli": round(float(np.median(ts_o)) / strings_ms, 4), "max_abs_d_opstr_pauli": float(np.abs(Vo - V).max()),
+            "min_marginal": float(Pm.min()), "max_marginal": float(Pm.max()),
         })
     if args.entanglement:
         P, pur_ms = timed(lambda: ctx.bond_purities(xs), args.reps)
