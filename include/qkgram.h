@@ -758,7 +758,8 @@ int qk_selftest_mfma(qk_ctx* ctx);
  * ansatz gate program: all data points share the gate structure (op, q0: n_ops entries; 0 = H, 1 = Rz,
  * 2 = XXPhase on (q0, q0+1), 3 = SWAP on (q0, q0+1), 4 = Rx, 5 = Ry, 6 = YYPhase on (q0, q0+1), 7 = ZZPhase on
  * (q0, q0+1); TKET matrices, theta = pi alpha / 2) and differ in the half-turn angles alpha[n_states][n_ops].
- * Any other op code is QK_EINVAL before anything runs.
+ * Op codes 8 (a 2x2 on q0) and 9 (a 4x4 on (q0, q0+1)) are the matrix gates of qk_build_mps_gates below: valid only in a call that
+ * comes with a matrix table.  An op code outside 0..7 -- outside 0..9 with a table -- is QK_EINVAL before anything runs.
  * One persistent launch; per two-qubit gate a one-sided Jacobi SVD and the truncation rule of the host builder:
  * drop the trailing singular values whose squared weight stays <= trunc_budget (= 1 - truncation_fidelity,
  * G:141-144; criterion as KernelPkg.jl:68), values <= value_of_zero never count.  max_bond bounds every bond
@@ -796,6 +797,22 @@ int qk_build_mps_scan(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n
                       const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
                       int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
                       qk_built** out);
+/* Matrix gates.  qk_build_mps_gates is qk_build_mps_scan (its arguments in their order) plus a matrix table: with n_mats > 0 the
+ * program may hold op code 8, a 2x2 unitary on qubit q0, and op code 9, a 4x4 unitary on (q0, q0+1).  The matrix of gate i is entry
+ * mat[i] of the table: complex128 [n_mats][4][4] row-major, (re, im) interleaved; a 2x2 sits in [:2][:2] of its slot.  The 4x4 index
+ * is (s_q0, s_q0+1) with qubit q0 most significant (TKET's order), and new[(p,p')] = sum M[(p,p')][(s,s')] old[(s,s')].  alpha[i] is
+ * ignored at these codes; mat is read only where op is 8 or 9.  mats_state_stride (in matrices) is 0 -- one table shared by all
+ * states -- or n_mats -- state s reads mats + s * n_mats * 32 doubles: a gate that depends on the data point.
+ * Before anything runs, QK_EINVAL with the gate's position in the message for: mat[i] outside 0..n_mats-1; a matrix with an entry that
+ * is not finite; a matrix that is not unitary, max |M^H M - 1| > 1e-12 (the canonical-form bookkeeping assumes unitary gates: a
+ * one-qubit gate never moves the orthogonality centre); a matrix gate past the last qubit (pair).  With n_mats = 0 the call IS
+ * qk_build_mps_scan: codes 8 and 9 are unknown op codes.  Snapshots and resume work unchanged; a resumed build is handed the table
+ * of the gates that follow.                                                                                                        */
+int qk_build_mps_gates(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
+                       const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
+                       int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
+                       int32_t n_mats, const double* mats /* [stride ? n_states : 1][n_mats][4][4][2] */, int32_t mats_state_stride,
+                       const int32_t* mat /* [n_ops] */, qk_built** out);
 int qk_built_num_snapshots(const qk_built* built);                        /* 1 for qk_build_mps */
 int qk_built_checkpoints(const qk_built* built, int32_t* checkpoints);    /* [num_snapshots] gates done at each snapshot */
 /* Snapshot j: dims[n_states][n_qubits+1], fidelity so far [n_states], offsets[n_states] into the one heap (complex elements),

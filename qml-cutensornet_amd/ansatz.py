@@ -19,6 +19,13 @@ Angles are pytket half-turns (theta = pi*alpha/2), the convention spelled out in
 Custom feature maps (``CircuitAnsatz``, ``BoundCircuit.from_gates``) add Rx, Ry,
 YYPhase and ZZPhase (op codes 4-7) to the four gates above; the matrices are
 TKET's, as in KernelPkg.jl and the reference's CPU gate list.
+
+Matrix gates (op codes 8 and 9) close the vocabulary: a 2x2 unitary on one qubit
+(``Unitary1q``) and a 4x4 unitary on an adjacent pair (``Unitary2q``), read from a
+table ``mats`` (complex128 [n_mats][4][4]; a 2x2 sits in ``[:2, :2]``) through a
+per-gate index ``mat``.  The 4x4 index is (s_q, s_{q+1}) with qubit q most
+significant (TKET's order).  The named constants X, Y, Z, S, Sdg, T, Tdg, V, Vdg,
+SX, SXdg, CX, CY, CZ are entries of that table.
 """
 from __future__ import annotations
 
@@ -28,24 +35,88 @@ import numpy as np
 
 OP_H, OP_RZ, OP_XX, OP_SWAP = 0, 1, 2, 3
 OP_RX, OP_RY, OP_YY, OP_ZZ = 4, 5, 6, 7  # custom feature maps (CircuitAnsatz, BoundCircuit.from_gates)
-N_OPS = 8  # codes 0 .. N_OPS-1 are valid; every builder rejects any other
-_OP_NAMES = {OP_H: "H", OP_RZ: "Rz", OP_XX: "XXPhase", OP_SWAP: "SWAP", OP_RX: "Rx", OP_RY: "Ry", OP_YY: "YYPhase", OP_ZZ: "ZZPhase"}
+OP_M1, OP_M2 = 8, 9  # matrix gates: a 2x2 on q0, a 4x4 on (q0, q0+1); the matrix of gate i is mats[mat[i]]
+N_OPS = 8  # codes 0 .. N_OPS-1 are valid without a matrix table; every builder rejects any other
+N_OPS_MAT = 10  # codes 0 .. N_OPS_MAT-1 are valid in a program that comes with a matrix table
+UNITARY_TOL = 1e-12  # max |M^H M - 1| a matrix gate may have: the builders' canonical-form bookkeeping assumes unitary gates
+_OP_NAMES = {OP_H: "H", OP_RZ: "Rz", OP_XX: "XXPhase", OP_SWAP: "SWAP", OP_RX: "Rx", OP_RY: "Ry", OP_YY: "YYPhase", OP_ZZ: "ZZPhase",
+             OP_M1: "Unitary1q", OP_M2: "Unitary2q"}
 _OP_CODES = {name: code for code, name in _OP_NAMES.items()}
-_TWO_QUBIT = (OP_XX, OP_SWAP, OP_YY, OP_ZZ)
+_TWO_QUBIT = (OP_XX, OP_SWAP, OP_YY, OP_ZZ, OP_M2)
 _PARAMETRISED = (OP_RZ, OP_XX, OP_RX, OP_RY, OP_YY, OP_ZZ)
+_MATRIX = (OP_M1, OP_M2)
+
+_R2 = 0.7071067811865476
+_NAMED_1Q = {  # TKET's matrices
+    "X": [[0, 1], [1, 0]], "Y": [[0, -1j], [1j, 0]], "Z": [[1, 0], [0, -1]],
+    "S": [[1, 0], [0, 1j]], "Sdg": [[1, 0], [0, -1j]],
+    "T": [[1, 0], [0, complex(_R2, _R2)]], "Tdg": [[1, 0], [0, complex(_R2, -_R2)]],
+    "V": [[_R2, -1j * _R2], [-1j * _R2, _R2]], "Vdg": [[_R2, 1j * _R2], [1j * _R2, _R2]],
+    "SX": [[0.5 + 0.5j, 0.5 - 0.5j], [0.5 - 0.5j, 0.5 + 0.5j]], "SXdg": [[0.5 - 0.5j, 0.5 + 0.5j], [0.5 + 0.5j, 0.5 - 0.5j]],
+}
+_NAMED_2Q = {  # control first: index (s_control, s_target)
+    "CX": [[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, 1], [0, 0, 1, 0]],
+    "CY": [[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, -1j], [0, 0, 1j, 0]],
+    "CZ": [[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, -1]],
+}
+_NAMED = {**_NAMED_1Q, **_NAMED_2Q}
 
 
 def is_two_qubit(o) -> bool:
-    """Does op code ``o`` act on the pair (q0, q0+1)?  XXPhase, SWAP, YYPhase and ZZPhase do."""
+    """Does op code ``o`` act on the pair (q0, q0+1)?  XXPhase, SWAP, YYPhase, ZZPhase and the 4x4 matrix gate do."""
     return o in _TWO_QUBIT
 
 
-def check_op_codes(op) -> None:
-    """``ValueError`` unless every code of ``op`` is one of the N_OPS gates."""
+def check_op_codes(op, with_table: bool = False) -> None:
+    """``ValueError`` unless every code of ``op`` is one of the N_OPS gates -- or, in a program that comes with a matrix table
+    (``with_table``), one of the N_OPS_MAT."""
     op = np.asarray(op)
-    bad = (op < 0) | (op >= N_OPS)
+    top = N_OPS_MAT if with_table else N_OPS
+    bad = (op < 0) | (op >= top)
     if bad.any():
-        raise ValueError(f"unknown gate op code {int(op[bad][0])} (valid: 0..{N_OPS - 1})")
+        raise ValueError(f"unknown gate op code {int(op[bad][0])} (valid: 0..{top - 1})")
+
+
+def exchange_qubits(m4) -> np.ndarray:
+    """A 4x4 with the roles of its two qubits exchanged: M'[(t,s)][(t',s')] = M[(s,t)][(s',t')]."""
+    return np.ascontiguousarray(np.asarray(m4, dtype=np.complex128).reshape(2, 2, 2, 2).transpose(1, 0, 3, 2).reshape(4, 4))
+
+
+def check_unitary(m, where) -> None:
+    """``ValueError`` unless the square matrix ``m`` is finite and max |M^H M - 1| <= UNITARY_TOL; ``where`` names the gate."""
+    if not np.all(np.isfinite(m)):
+        raise ValueError(f"{where}: the matrix has an entry that is not finite")
+    dev = float(np.abs(m.conj().T @ m - np.eye(m.shape[0])).max())
+    if not dev <= UNITARY_TOL:
+        raise ValueError(f"{where}: the matrix is not unitary (max |M^H M - 1| = {dev:.3e} > {UNITARY_TOL:g})")
+
+
+def check_matrix_gates(op, mat, mats):
+    """The matrix table of a program, validated: ``(mat int32 [n_gates], mats complex128 [n_mats, 4, 4])``, or ``(None, None)``
+    for a program without one (its codes 8 and 9 are then unknown: ``check_op_codes``).  ``ValueError`` when the table is not
+    [n_mats][4][4], when ``mat`` of a matrix gate lies outside 0 .. n_mats-1, or when the 2x2 (``[:2, :2]`` of the slot) or 4x4
+    the gate reads is not finite and unitary to UNITARY_TOL; the message names the gate's position in the program."""
+    op = np.asarray(op)
+    if mats is None or mat is None:
+        check_op_codes(op)
+        return None, None
+    check_op_codes(op, with_table=True)
+    mats = np.asarray(mats)
+    if mats.ndim != 3 or mats.shape[1:] != (4, 4):
+        raise ValueError(f"the matrix table must be [n_mats][4][4], got shape {mats.shape}")
+    mats = np.ascontiguousarray(mats, dtype=np.complex128)
+    mat = np.ascontiguousarray(mat, dtype=np.int32)
+    if mat.shape != op.shape:
+        raise ValueError(f"mat must hold one index per gate of the program ({op.shape[0]}), got shape {mat.shape}")
+    seen = set()
+    for i in np.flatnonzero(op >= OP_M1):
+        k, d = int(mat[i]), 2 if op[i] == OP_M1 else 4
+        if not 0 <= k < mats.shape[0]:
+            raise ValueError(f"gate {int(i)}: matrix index {k} outside 0..{mats.shape[0] - 1}")
+        if (k, d) not in seen:
+            check_unitary(mats[k, :d, :d], f"gate {int(i)} ({_OP_NAMES[int(op[i])]}, table entry {k})")
+            seen.add((k, d))
+    return mat, mats
 
 
 def entanglement_graph(nq: int, nn: int) -> list[tuple[int, int]]:
@@ -78,6 +149,8 @@ class BoundCircuit:
     op: np.ndarray  # int8   [n_gates]
     q0: np.ndarray  # int32  [n_gates]   (for 2-qubit gates the pair is (q0, q0+1))
     alpha: np.ndarray  # float64 [n_gates] half-turns (0 where unused)
+    mat: np.ndarray | None = None  # int32 [n_gates] index into mats of a matrix gate (op 8, 9), -1 at the named gates
+    mats: np.ndarray | None = None  # complex128 [n_mats, 4, 4]: the matrix table (a 2x2 sits in [:2, :2], the rest of its slot 0)
 
     @property
     def n_gates(self) -> int:
@@ -86,11 +159,15 @@ class BoundCircuit:
     def as_tuples(self):
         """(name, qubits, params) triples in the shape of the reference's CPU gate list
         (/root/reference/cpu_backend/kernel_state_ansatz.py:113-131)."""
-        check_op_codes(self.op)
+        mat, mats = check_matrix_gates(self.op, self.mat, self.mats)
         out = []
-        for o, q, a in zip(self.op.tolist(), self.q0.tolist(), self.alpha.tolist()):
+        for i, (o, q, a) in enumerate(zip(self.op.tolist(), self.q0.tolist(), self.alpha.tolist())):
             qubits = [q, q + 1] if is_two_qubit(o) else [q]
-            out.append((_OP_NAMES[o], qubits, [a] if o in _PARAMETRISED else []))
+            if o in _MATRIX:  # ("Unitary1q", [q], [M2x2]) / ("Unitary2q", [q, q+1], [M4x4])
+                d = 2 if o == OP_M1 else 4
+                out.append((_OP_NAMES[o], qubits, [mats[mat[i], :d, :d].copy()]))
+            else:
+                out.append((_OP_NAMES[o], qubits, [a] if o in _PARAMETRISED else []))
         return out
 
     def sliced(self, a, b) -> "BoundCircuit":
@@ -99,32 +176,59 @@ class BoundCircuit:
         a, b = int(a), int(b)
         if not 0 <= a <= b <= self.n_gates:
             raise ValueError(f"sliced({a}, {b}): want 0 <= a <= b <= {self.n_gates} gates")
-        return BoundCircuit(self.n_qubits, self.op[a:b], self.q0[a:b], self.alpha[a:b])
+        return BoundCircuit(self.n_qubits, self.op[a:b], self.q0[a:b], self.alpha[a:b], None if self.mat is None else self.mat[a:b], self.mats)
 
     @classmethod
-    def from_gates(cls, n_qubits, gates) -> "BoundCircuit":
+    def from_gates(cls, n_qubits, gates, named_constants: bool = False) -> "BoundCircuit":
         """A gate list in the shape of the reference's CPU backend -- ``(name, qubits, params)`` with the names of
         ``_OP_NAMES`` and ``params`` the half-turn angle in a one-element list (empty for H and SWAP) -- as a program.
         A two-qubit gate on non-adjacent or reversed qubits is routed like KernelStateAnsatz's XXPhase: SWAP chain up,
-        the gate on (hi-1, hi), the chain back (exact: every two-qubit gate here is symmetric in its qubits)."""
+        the gate on (hi-1, hi), the chain back.  The named two-qubit rotations and SWAP are symmetric in their qubits; a matrix
+        gate need not be: on qubits ``[a, b]`` with a > b the matrix is applied with the two qubit roles exchanged
+        (``exchange_qubits``), so ``("CX", [3, 2], [])`` has its control on qubit 3.
+
+        Matrix gates: ``("Unitary1q", [q], [M])`` and ``("Unitary2q", [a, b], [M])`` with M a unitary 2x2 / 4x4 (index (s_a, s_b),
+        a most significant), and -- with ``named_constants=True`` -- the named constants X, Y, Z, S, Sdg, T, Tdg, V, Vdg, SX, SXdg,
+        CX, CY, CZ (control first) without parameters.  The constants are opt-in here because the vocabulary of a plain
+        ``from_gates(n, gates)`` is pinned to the op-code names (any other name, CX included, stays the ``ValueError`` it has always
+        been); ``as_bound_circuit`` -- the way a gate-list ansatz enters ``build_kernel_matrix`` and the builder pools -- and
+        ``CircuitAnsatz`` templates take them without asking.
+
+        Table slots are assigned by structure only: every explicit unitary gets its own slot in order of appearance,
+        a named constant one slot per name (and, for CX and CY, per orientation) at its first use -- so the circuits of the data
+        points of one gate-list ansatz share ``op``, ``q0`` and ``mat`` and differ in ``alpha`` and ``mats``.  ``ValueError`` for a
+        matrix of the wrong shape or one that is not unitary to UNITARY_TOL."""
         n = int(n_qubits)
-        op, q0, alpha = [], [], []
-        for g in gates:
+        op, q0, alpha, mat = [], [], [], []
+        table = _MatTable()
+        for pos, g in enumerate(gates):
             name, qubits, params = g
-            code = _gate_code(name)
+            code = _gate_code(name, named_constants)
             qubits = [int(q) for q in qubits]
+            if _arity(code) != len(qubits):
+                raise ValueError(f"{name} acts on {_arity(code)} qubit(s), got {qubits}")
+            if code in _MATRIX:
+                if name in _NAMED:
+                    if params is not None and np.size(params) != 0:
+                        raise ValueError(f"{name}: expected 0 parameter(s), got {list(params)}")
+                    params = None
+                slot = table.slot(name, qubits, params, f"gate {pos}")
+                for o, q, k in _route(code, qubits, n):
+                    op.append(o), q0.append(q), alpha.append(0.0), mat.append(slot if k else -1)
+                continue
             if params is None:
                 params = []
             elif np.ndim(params) == 0:
                 params = [params]
-            if _arity(code) != len(qubits):
-                raise ValueError(f"{name} acts on {_arity(code)} qubit(s), got {qubits}")
             if len(params) != (1 if code in _PARAMETRISED else 0):
                 raise ValueError(f"{name}: expected {1 if code in _PARAMETRISED else 0} parameter(s), got {list(params)}")
             a = float(params[0]) if params else 0.0
             for o, q, k in _route(code, qubits, n):
-                op.append(o), q0.append(q), alpha.append(a if k else 0.0)
-        return cls(n, np.asarray(op, dtype=np.int8), np.asarray(q0, dtype=np.int32), np.asarray(alpha, dtype=np.float64))
+                op.append(o), q0.append(q), alpha.append(a if k else 0.0), mat.append(-1)
+        core = (n, np.asarray(op, dtype=np.int8), np.asarray(q0, dtype=np.int32), np.asarray(alpha, dtype=np.float64))
+        if not table.entries:
+            return cls(*core)
+        return cls(*core, np.asarray(mat, dtype=np.int32), table.array())
 
 
 def check_checkpoints(checkpoints, n_gates) -> list:
@@ -161,11 +265,54 @@ def _arity(o) -> int:
     return 2 if is_two_qubit(o) else 1
 
 
-def _gate_code(name) -> int:
+def _gate_code(name, named_constants: bool = True) -> int:
+    if isinstance(name, str) and name in _NAMED:
+        if not named_constants:
+            also = f"from_gates(..., named_constants=True) also takes {', '.join(_NAMED)}"
+            raise ValueError(f"unknown gate {name!r} (supported: {', '.join(_OP_CODES)}; {also})")
+        return OP_M1 if name in _NAMED_1Q else OP_M2
     try:
         return _OP_CODES[name]
-    except KeyError:
-        raise ValueError(f"unknown gate {name!r} (supported: {', '.join(_OP_CODES)})") from None
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown gate {name!r} (supported: {', '.join(list(_OP_CODES) + list(_NAMED))})") from None
+
+
+class _MatTable:
+    """The matrix table of a program under construction: slots by structure only (see ``BoundCircuit.from_gates``)."""
+
+    def __init__(self):
+        self.entries, self._named = [], {}
+
+    def slot(self, name, qubits, params, where) -> int:
+        """The table slot of one matrix gate as given (unrouted): ``params`` is ``None`` for a named constant, else the matrix (or
+        a one-element list holding it).  On reversed qubits the 4x4 goes in with its qubit roles exchanged."""
+        d = 2 if len(qubits) == 1 else 4
+        reverse = d == 4 and qubits[0] > qubits[1]
+        if name in _NAMED:
+            m = np.array(_NAMED[name], dtype=np.complex128)
+            key = (name, bool(reverse and not np.array_equal(exchange_qubits(m), m)))
+            if key in self._named:
+                return self._named[key]
+        else:
+            try:
+                m = np.asarray(params, dtype=np.complex128)
+            except (TypeError, ValueError):
+                raise ValueError(f"{where} ({name}): the parameter must be one {d}x{d} complex matrix") from None
+            if m.shape == (1, d, d):
+                m = m[0]
+            if m.shape != (d, d):
+                raise ValueError(f"{where} ({name}): expected one {d}x{d} matrix, got shape {m.shape}")
+            check_unitary(m, f"{where} ({name})")
+            key = None
+        full = np.zeros((4, 4), dtype=np.complex128)
+        full[:d, :d] = exchange_qubits(m) if reverse else m
+        self.entries.append(full)
+        if key is not None:
+            self._named[key] = len(self.entries) - 1
+        return len(self.entries) - 1
+
+    def array(self) -> np.ndarray:
+        return np.stack(self.entries) if self.entries else np.zeros((0, 4, 4), dtype=np.complex128)
 
 
 def _route(code, qubits, n):
@@ -185,10 +332,10 @@ def _route(code, qubits, n):
 
 def as_bound_circuit(circuit, ansatz) -> BoundCircuit:
     """What ``ansatz.circuit_for_data`` returned, as a program: a reference-style gate list ``(name, qubits, params)``
-    through ``BoundCircuit.from_gates`` with ``n_qubits`` from ``ansatz.ansatz_circ.n_qubits`` (as reference G:147); a
-    BoundCircuit as it is."""
+    through ``BoundCircuit.from_gates`` (named constants included) with ``n_qubits`` from ``ansatz.ansatz_circ.n_qubits``
+    (as reference G:147); a BoundCircuit as it is."""
     if isinstance(circuit, (list, tuple)):
-        return BoundCircuit.from_gates(ansatz.ansatz_circ.n_qubits, circuit)
+        return BoundCircuit.from_gates(ansatz.ansatz_circ.n_qubits, circuit, named_constants=True)
     return circuit
 
 
@@ -279,10 +426,11 @@ class CircuitProgram:
     """The compiled (unbound) gate program of a ``CircuitAnsatz``: per routed gate an op code, a pair / qubit and the
     angle form alpha = s (c_a + d_a x[a]) (c_b + d_b x[b]) (s = 0 for H and SWAP; c = 1, d = 0 for an absent factor)."""
 
-    def __init__(self, n_qubits, op, q0, s, fa, ca, da, fb, cb, db):
+    def __init__(self, n_qubits, op, q0, s, fa, ca, da, fb, cb, db, mat=None, mats=None):
         self.n_qubits = int(n_qubits)
         self.op, self.q0 = op, q0
         self.s, self.fa, self.ca, self.da, self.fb, self.cb, self.db = s, fa, ca, da, fb, cb, db
+        self.mat, self.mats = mat, mats  # constant matrix gates: the table is the same array for every data point
 
     @property
     def n_gates(self) -> int:
@@ -290,7 +438,7 @@ class CircuitProgram:
 
     def bind(self, x: np.ndarray) -> BoundCircuit:
         alpha = self.s * (self.ca + self.da * x[self.fa]) * (self.cb + self.db * x[self.fb])
-        return BoundCircuit(self.n_qubits, self.op, self.q0, alpha)
+        return BoundCircuit(self.n_qubits, self.op, self.q0, alpha, self.mat, self.mats)
 
 
 def _factor(spec, n_features):
@@ -311,8 +459,10 @@ class CircuitAnsatz:
       * ``(s, (a, c_a, d_a), (b, c_b, d_b))``: alpha = s (c_a + d_a x[a]) (c_b + d_b x[b]).
     The reference ansatz is Rz ``((2/pi) gamma, (i, 0, 1))`` and XXPhase ``(gamma^2, (a, 1, -1), (b, 1, -1))``; a
     Havlicek-style ZZ map is ZZPhase ``(s, (a, pi, -1), (b, pi, -1))``.  Two-qubit gates on non-adjacent or reversed
-    qubits are routed as in ``BoundCircuit.from_gates``.  ``num_features`` defaults to ``num_qubits`` (one feature per
-    qubit, as the reference's ``feature_symbol_list``).  Picklable: plain numpy arrays only."""
+    qubits are routed as in ``BoundCircuit.from_gates``.  Constant matrix gates: the named constants of ``from_gates`` (X, Y, Z, S,
+    Sdg, T, Tdg, V, Vdg, SX, SXdg, CX, CY, CZ) with angle ``None``, and ``("Unitary1q" | "Unitary2q", qubits, M)`` with a constant
+    unitary M in the place of the angle; every data point shares the one table.  ``num_features`` defaults to ``num_qubits``
+    (one feature per qubit, as the reference's ``feature_symbol_list``).  Picklable: plain numpy arrays only."""
 
     def __init__(self, num_qubits, gates, num_features=None):
         n = int(num_qubits)
@@ -322,13 +472,20 @@ class CircuitAnsatz:
         self.num_qubits, self.num_features = n, nf
         self.feature_symbol_list = [f"f_{i}" for i in range(nf)]
         cols = {k: [] for k in ("op", "q0", "s", "fa", "ca", "da", "fb", "cb", "db")}
-        for name, qubits, angle in gates:
+        mat, table = [], _MatTable()
+        for pos, (name, qubits, angle) in enumerate(gates):
             code = _gate_code(name)
             qubits = [int(q) for q in (qubits if np.ndim(qubits) else [qubits])]
             if _arity(code) != len(qubits):
                 raise ValueError(f"{name} acts on {_arity(code)} qubit(s), got {qubits}")
             one = (0, 1.0, 0.0)
-            if code not in _PARAMETRISED:
+            slot = -1
+            if code in _MATRIX:
+                if name in _NAMED and angle is not None:
+                    raise ValueError(f"{name} takes no angle, got {angle!r}")
+                slot = table.slot(name, qubits, angle, f"gate {pos}")
+                s, fa, fb = 0.0, one, one
+            elif code not in _PARAMETRISED:
                 if angle is not None:
                     raise ValueError(f"{name} takes no angle, got {angle!r}")
                 s, fa, fb = 0.0, one, one
@@ -345,8 +502,11 @@ class CircuitAnsatz:
                 row = (o, q, s, *fa, *fb) if is_gate else (o, q, 0.0, *one, *one)
                 for k, v in zip(cols, row):
                     cols[k].append(v)
+                mat.append(slot if is_gate else -1)
         dt = {"op": np.int8, "q0": np.int32, "fa": np.int32, "fb": np.int32}
         arr = {k: np.asarray(v, dtype=dt.get(k, np.float64)) for k, v in cols.items()}
+        if table.entries:
+            arr["mat"], arr["mats"] = np.asarray(mat, dtype=np.int32), table.array()
         self.ansatz_circ = CircuitProgram(n, **arr)
 
     def layer_ends(self) -> list:

@@ -1,7 +1,8 @@
 // qk_build.hip -- device MPS builder: the input producer of the Gram path on the GPU.
 // Replaces simulate(libhandle, circ, SimulationAlgorithm.MPSxGate, config) of the reference
 // (gpu_backend/kernel_state_ansatz.py:141-144, 221, 263; truncation criterion as KernelPkg.jl:68) for the ansatz gate
-// program (H, Rz, Rx, Ry; XXPhase, YYPhase, ZZPhase, SWAP on adjacent qubits: qml-cutensornet_amd/ansatz.py).  Same algorithm as the host
+// program (H, Rz, Rx, Ry; XXPhase, YYPhase, ZZPhase, SWAP on adjacent qubits; 2x2 and 4x4 unitaries from a matrix table:
+// qml-cutensornet_amd/ansatz.py).  Same algorithm as the host
 // builder (csrc/qk_builder.cpp, mps.py:_simulate) -- orthogonality centre carried along, one SVD per two-qubit gate,
 // fewest singular values whose weight keeps the fidelity -- restated for the device:
 //   * all data points share ONE gate structure and differ only in the angles, so the whole list is one persistent
@@ -33,9 +34,10 @@ typedef double cd __attribute__((ext_vector_type(2)));  // complex128 as (re, im
 
 constexpr int MAX_SWEEPS = 40;
 
-enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8 };  // ansatz.py
+// ansatz.py.  Codes 8 and 9 are the matrix gates: valid only in a program that comes with a matrix table (N_OPS_MAT codes then).
+enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10 };
 
-__host__ __device__ inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ; }
+__host__ __device__ inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ || o == OP_M2; }
 
 enum { ERR_BOND = 1, ERR_HEAP = 2, ERR_SWEEPS = 4, ERR_GATE = 8, ERR_OP = 16, ERR_NORM0 = 32 };
 
@@ -44,6 +46,9 @@ struct BuildArgs {
   const int8_t* op;
   const int32_t* q0;
   const double* alpha;  // [n_states][n_ops] half-turns
+  const cd* mats;       // [mats_stride ? n_states : 1][n_mats][4][4] the matrix table of op codes 8 and 9 (null: no table, the codes are unknown)
+  const int32_t* mat;   // [n_ops] table entry of a matrix gate (validated by the host: 0 .. n_mats-1 where op is 8 or 9)
+  int mats_stride;      // matrices from one state's table to the next: 0 (one table for all states) or n_mats
   double budget, zero;
   cd* arena;  // per workgroup: n_qubits slots of 2 cap^2
   cd* work;   // per workgroup: 4 buffers of (2 cap + 32)^2
@@ -565,19 +570,79 @@ struct qk_built {
   int n_snapshots() const { return (int)checkpoints.size(); }
 };
 
+struct MatTable {  // the matrix table of op codes 8 and 9 as the caller gave it (n_mats = 0: none)
+  int32_t n_mats = 0;
+  const double* mats = nullptr;
+  int32_t stride = 0;
+  const int32_t* mat = nullptr;
+};
+
 static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, qk_built** out);
+                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, const MatTable& tab, qk_built** out);
+// the body of qk_build_mps_scan and qk_build_mps_gates; `what` is the entry point the caller came through, for its error messages
+static int build_gates(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                       double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
+                       int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, qk_built** out);
 
 extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
                             const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, qk_built** out) {
   const int32_t last = n_ops;  // the one-checkpoint scan: a snapshot after the whole program
-  return build_impl("qk_build_mps", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, 1, &last, nullptr, 0, out);
+  return build_impl("qk_build_mps", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, 1, &last, nullptr, 0, MatTable{}, out);
 }
 
 extern "C" int qk_build_mps_scan(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
                                  double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
                                  int32_t initial_snapshot, qk_built** out) {
-  static const char* what = "qk_build_mps_scan";
+  return build_gates("qk_build_mps_scan", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
+                     0, nullptr, 0, nullptr, out);
+}
+
+// The matrix table of a program, checked before anything runs: every matrix gate's index inside 0..n_mats-1 and, in each of the
+// `tables` tables, its 2x2 ([:2][:2] of the slot) or 4x4 finite and unitary, max |M^H M - 1| <= 1e-12.
+static int check_mat_table(const char* what, int n_ops, const int8_t* op, int tables, const MatTable& tab) {
+  std::vector<char> seen((size_t)tab.n_mats, 0);  // bit 0: checked as a 2x2, bit 1: as a 4x4 -- an entry many gates read is checked once
+  for (int i = 0; i < n_ops; ++i) {
+    if (op[i] != OP_M1 && op[i] != OP_M2) continue;
+    const int k = tab.mat[i], d = op[i] == OP_M1 ? 2 : 4;
+    if (k < 0 || k >= tab.n_mats) return qk_fail(QK_EINVAL, "%s: gate %d: matrix index %d outside 0..%d", what, i, k, (int)tab.n_mats - 1);
+    if (seen[(size_t)k] & (d == 2 ? 1 : 2)) continue;
+    seen[(size_t)k] |= (d == 2 ? 1 : 2);
+    for (int s = 0; s < tables; ++s) {
+      const double* m = tab.mats + ((size_t)s * tab.n_mats + k) * 32;  // [4][4][2]
+      double dev = 0;
+      bool finite = true;
+      for (int a = 0; a < d; ++a)
+        for (int b = 0; b < d; ++b) {
+          finite = finite && std::isfinite(m[(a * 4 + b) * 2]) && std::isfinite(m[(a * 4 + b) * 2 + 1]);
+          double gr = (a == b) ? -1.0 : 0.0, gi = 0.0;  // (M^H M - 1)[a][b] = sum_r conj(M[r][a]) M[r][b] - delta
+          for (int r = 0; r < d; ++r) {
+            const double xr = m[(r * 4 + a) * 2], xi = m[(r * 4 + a) * 2 + 1], yr = m[(r * 4 + b) * 2], yi = m[(r * 4 + b) * 2 + 1];
+            gr += xr * yr + xi * yi, gi += xr * yi - xi * yr;
+          }
+          dev = std::max(dev, std::hypot(gr, gi));
+        }
+      if (!finite) return qk_fail(QK_EINVAL, "%s: gate %d: the matrix of table entry %d (state %d) has an entry that is not finite", what, i, k, s);
+      if (!(dev <= 1e-12)) return qk_fail(QK_EINVAL, "%s: gate %d: the matrix of table entry %d (state %d) is not unitary: max |M^H M - 1| = %.3e > 1e-12", what, i, k, s, dev);
+    }
+  }
+  return QK_OK;
+}
+
+extern "C" int qk_build_mps_gates(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                                  double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                                  int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, qk_built** out) {
+  return build_gates("qk_build_mps_gates", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
+                     n_mats, mats, mats_state_stride, mat, out);
+}
+
+static int build_gates(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                       double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
+                       int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, qk_built** out) {
+  MatTable tab;
+  if (n_mats < 0 || (n_mats > 0 && (!mats || !mat))) return qk_fail(QK_EINVAL, "%s: a matrix table needs n_mats >= 0, mats and mat", what);
+  if (n_mats > 0 && mats_state_stride != 0 && mats_state_stride != n_mats)
+    return qk_fail(QK_EINVAL, "%s: mats_state_stride must be 0 (one table for all states) or n_mats = %d, got %d", what, (int)n_mats, (int)mats_state_stride);
+  if (n_mats > 0) tab.n_mats = n_mats, tab.mats = mats, tab.stride = mats_state_stride, tab.mat = mat;
   if (!checkpoints || n_checkpoints < 1) return qk_fail(QK_EINVAL, "%s: no checkpoints", what);
   for (int j = 0; j < n_checkpoints; ++j)
     if (checkpoints[j] < 1 || checkpoints[j] > n_ops || (j > 0 && checkpoints[j] <= checkpoints[j - 1]))
@@ -585,16 +650,25 @@ extern "C" int qk_build_mps_scan(qk_ctx* c, int32_t n_states, int32_t n_qubits, 
   if (checkpoints[n_checkpoints - 1] != n_ops) return qk_fail(QK_EINVAL, "%s: the last checkpoint must be the whole program (%d gates), got %d", what, n_ops, (int)checkpoints[n_checkpoints - 1]);
   if ((flags & QK_BUILD_PARTIAL) && (n_checkpoints > 1 || initial))
     return qk_fail(QK_EINVAL, "%s: QK_BUILD_PARTIAL goes with one checkpoint and no initial snapshot (a dropped state has no snapshots)", what);
-  return build_impl(what, c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot, out);
+  return build_impl(what, c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot, tab, out);
 }
 
 static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, qk_built** out) {
+                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, const MatTable& tab, qk_built** out) {
   if (!c || !op || !q0 || !alpha || !out) return qk_fail(QK_EINVAL, "%s: null argument", what);
   if (n_states <= 0 || n_qubits <= 0 || n_ops < 0) return qk_fail(QK_EINVAL, "%s: empty problem (%d states, %d qubits, %d gates)", what, n_states, n_qubits, n_ops);
   if (max_bond < 2 || max_bond > 1024) return qk_fail(QK_EINVAL, "%s: max_bond %d outside 2..1024", what, max_bond);
+  const int n_codes = tab.n_mats > 0 ? N_OPS_MAT : N_OPS;  // without a table codes 8 and 9 are unknown
   for (int i = 0; i < n_ops; ++i)
-    if (op[i] < 0 || op[i] >= N_OPS) return qk_fail(QK_EINVAL, "%s: unknown gate op code %d at position %d (valid: 0..%d)", what, (int)op[i], i, N_OPS - 1);
+    if (op[i] < 0 || op[i] >= n_codes) return qk_fail(QK_EINVAL, "%s: unknown gate op code %d at position %d (valid: 0..%d)", what, (int)op[i], i, n_codes - 1);
+  for (int i = 0; i < n_ops; ++i)  // (the kernel checks this too; a matrix gate past the last pair is refused before anything runs)
+    if ((op[i] == OP_M1 || op[i] == OP_M2) && (q0[i] < 0 || q0[i] + (op[i] == OP_M2 ? 1 : 0) >= n_qubits))
+      return qk_fail(QK_EINVAL, "%s: gate %d on a qubit outside the register", what, i);
+  const int n_tables = tab.n_mats > 0 ? (tab.stride ? n_states : 1) : 0;
+  if (n_tables) {
+    const int rc = check_mat_table(what, n_ops, op, n_tables, tab);
+    if (rc != QK_OK) return rc;
+  }
   if (init) {  // a resumed build starts from snapshot init_j of `init`, which is only read
     if (init->ctx != c) return qk_fail(QK_EINVAL, "%s: the initial snapshot was built in another context", what);
     if (init_j < 0 || init_j >= init->n_snapshots()) return qk_fail(QK_EINVAL, "%s: initial snapshot %d outside 0..%d", what, init_j, init->n_snapshots() - 1);
@@ -657,7 +731,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   HIP_TRY_AS(what, c->build_arena.ensure((size_t)grid * n_qubits * 2 * cap * cap * sizeof(cd)));
   HIP_TRY_AS(what, c->build_work.ensure((size_t)grid * (4 * wslot + wtab) * sizeof(cd)));
   QkDevBuf heap, d_op, d_q0, d_alpha, d_fid, d_secs, d_dims, d_offs, d_ctr, d_err, d_order;  // d_ctr: [0] state counter, [1] heap top
-  QkDevBuf d_ckpt, d_centre, d_ioffs, d_idims, d_ifid, d_icentre;
+  QkDevBuf d_ckpt, d_centre, d_ioffs, d_idims, d_ifid, d_icentre, d_mats, d_mat;
   const size_t n_rec = (size_t)n_ckpt * n_states;  // (snapshot, state) records
   HIP_TRY_AS(what, heap.alloc(heap_cap * sizeof(cd)));
   HIP_TRY_AS(what, d_op.alloc(std::max(1, n_ops)));
@@ -682,6 +756,13 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
     HIP_TRY_AS(what, hipMemcpy(d_ifid.get(), init->all_fidelity.data() + r0, (size_t)n_states * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY_AS(what, hipMemcpy(d_icentre.get(), init->all_centre.data() + r0, (size_t)n_states * sizeof(int32_t), hipMemcpyHostToDevice));
   }
+  if (n_tables) {
+    const size_t mats_bytes = (size_t)n_tables * tab.n_mats * 16 * sizeof(cd);
+    HIP_TRY_AS(what, d_mats.alloc(mats_bytes));
+    HIP_TRY_AS(what, d_mat.alloc((size_t)std::max(1, n_ops) * sizeof(int32_t)));
+    HIP_TRY_AS(what, hipMemcpy(d_mats.get(), tab.mats, mats_bytes, hipMemcpyHostToDevice));
+    if (n_ops > 0) HIP_TRY_AS(what, hipMemcpy(d_mat.get(), tab.mat, (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
   HIP_TRY_AS(what, d_ctr.alloc(2 * sizeof(unsigned long long)));
   HIP_TRY_AS(what, d_err.alloc(32 * sizeof(int)));
   if (n_ops > 0) {
@@ -693,6 +774,8 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   HIP_TRY_AS(what, hipMemsetAsync(d_err.get(), 0, 32 * sizeof(int), c->stream));
   // Queue order: longest expected first.  The cost of a state grows with its bonds, and those with the entangling power
   // of its XXPhase / YYPhase / ZZPhase gates, sin^2(pi alpha) summed over the gates -- a cheap proxy that keeps the tail of the launch short.
+  // Matrix gates (op codes 8 and 9) add nothing to it: a shared table costs every state the same, and the entangling power of a
+  // per-state 4x4 is not worth a factorisation on the host.
   std::vector<int32_t> order(n_states);
   {
     std::vector<double> proxy(n_states, 0.0);
@@ -711,6 +794,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   a.order = d_order.get<int32_t>();
   a.n_states = n_states, a.n_qubits = n_qubits, a.n_ops = n_ops, a.cap = cap;
   a.op = d_op.get<int8_t>(), a.q0 = d_q0.get<int32_t>(), a.alpha = d_alpha.get<double>();
+  a.mats = n_tables ? d_mats.get<cd>() : nullptr, a.mat = n_tables ? d_mat.get<int32_t>() : nullptr, a.mats_stride = n_tables > 1 ? tab.n_mats : 0;
   a.budget = trunc_budget, a.zero = value_of_zero;
   a.arena = c->build_arena.get<cd>(), a.work = c->build_work.get<cd>(), a.heap = heap.get<cd>(), a.heap_cap = heap_cap;
   a.counter = d_ctr.get<unsigned long long>(), a.heap_top = a.counter + 1;
@@ -786,7 +870,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
                  steps ? (double)ticks / 100.0 / (double)steps : 0.0, steps);
   }
   if (err) {
-    if (err & ERR_OP) return qk_fail(QK_EINVAL, "%s: unknown gate op code (valid: 0..%d)", what, N_OPS - 1);
+    if (err & ERR_OP) return qk_fail(QK_EINVAL, "%s: unknown gate op code (valid: 0..%d)", what, n_codes - 1);
     if (err & ERR_GATE) return qk_fail(QK_EINVAL, "%s: gate on a qubit outside the register", what);
     if (err & ERR_BOND) return qk_fail(QK_EINVAL, "%s: a bond grew beyond max_bond = %d", what, cap);
     if (err & ERR_HEAP) return qk_fail(QK_EDEVICE, "%s: the packed states (%d snapshots each) need %llu complex numbers, the heap holds %zu", what, n_ckpt, ctr[1], heap_cap);

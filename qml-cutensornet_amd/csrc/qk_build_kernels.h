@@ -1113,6 +1113,66 @@ __device__ __noinline__ void wg_load_snapshot(const cd* src, const int32_t* src_
   __syncthreads();
 }
 
+// ---- matrix gates (op codes 8 and 9): a 2x2 / 4x4 unitary from the table
+// sum_s m[s] t[s] over N terms in the fixed order of the matrix gates: column 0 first, ascending, the real and the imaginary part each
+// one chain of fused multiply-adds -- the arithmetic of mat_dot in the native host builder (qk_builder.cpp), so the two builders
+// differ only where they already do.
+template <int N>
+__device__ __forceinline__ cd mat_dot(const cd* m, const cd* t) {
+  double re = m[0].x * t[0].x, im = m[0].x * t[0].y;
+  re = fma(-m[0].y, t[0].y, re);
+  im = fma(m[0].y, t[0].x, im);
+#pragma unroll
+  for (int s = 1; s < N; ++s) {
+    re = fma(m[s].x, t[s].x, re);
+    re = fma(-m[s].y, t[s].y, re);
+    im = fma(m[s].x, t[s].y, im);
+    im = fma(m[s].y, t[s].x, im);
+  }
+  return cd{re, im};
+}
+
+// The address of a gate's matrix is uniform across the workgroup: 16 threads fetch its slot once into LDS (`stage`: the Jacobi working
+// set, idle between factorisations; every caller arrives behind a barrier), every thread reads its coefficients from there into
+// registers, and the element loop touches the table no more.  Kept out of line: the coefficients (16 or 64 registers) must not
+// count against the kernel's loops.
+__device__ __noinline__ void wg_matrix_1q(cd* t, const int l, const int r, const cd* M, cd* stage) {
+  const int tid = threadIdx.x;
+  if (tid < 16) stage[tid] = M[tid];
+  __syncthreads();
+  const cd m0[2] = {stage[0], stage[1]}, m1[2] = {stage[4], stage[5]};  // the 2x2 sits in [:2][:2] of the 4x4 slot
+  for (int e = tid; e < l * r; e += BT) {
+    const int a = e / r, c = e - a * r;
+    const cd v[2] = {t[(a * 2) * r + c], t[(a * 2 + 1) * r + c]};
+    t[(a * 2) * r + c] = mat_dot<2>(m0, v);
+    t[(a * 2 + 1) * r + c] = mat_dot<2>(m1, v);
+  }
+  __syncthreads();
+}
+
+// theta[(a,p)][(p',c)] (row length nn = 2 r): the four entries (p00, p01, p10, p11) of every (a, c) through the 4x4
+__device__ __noinline__ void wg_matrix_2q(cd* TH, const int l, const int r, const cd* M, cd* stage) {
+  const int tid = threadIdx.x, nn = 2 * r;
+  if (tid < 16) stage[tid] = M[tid];
+  __syncthreads();
+  cd m[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) m[k] = stage[k];
+  for (int e = tid; e < l * r; e += BT) {
+    const int a = e / r, c = e - a * r;
+    cd* p00 = TH + (long)(a * 2) * nn + c;
+    cd* p01 = p00 + r;
+    cd* p10 = TH + (long)(a * 2 + 1) * nn + c;
+    cd* p11 = p10 + r;
+    const cd v[4] = {*p00, *p01, *p10, *p11};
+    *p00 = mat_dot<4>(m, v);
+    *p01 = mat_dot<4>(m + 4, v);
+    *p10 = mat_dot<4>(m + 8, v);
+    *p11 = mat_dot<4>(m + 12, v);
+  }
+  __syncthreads();
+}
+
 template <int MINWG>  // resident workgroups per CU the register budget is cut for: 256 threads: 2 (76 KiB of LDS each) or 4 (38 KiB); 512 threads: 1 (152 KiB)
 __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) {
   extern __shared__ double sh_raw[];
@@ -1166,7 +1226,7 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
         ++ck;
       }
       const int o = g.op[i], q = g.q0[i];
-      if (o < 0 || o >= N_OPS) {
+      if (o < 0 || o >= (g.mats ? N_OPS_MAT : N_OPS)) {  // the matrix gates need their table
         if (tid == 0) atomicOr(g.error, ERR_OP);
         continue;
       }
@@ -1191,6 +1251,10 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
           }
         }
         __syncthreads();
+        continue;
+      }
+      if (o == OP_M1) {  // a 2x2 from the table (unitary: the centre stays where it is)
+        wg_matrix_1q(sites + q * slot, dims[q], dims[q + 1], g.mats + ((long)st * g.mats_stride + g.mat[i]) * 16, jl);
         continue;
       }
       if (!is_two_qubit(o)) {  // Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
@@ -1305,7 +1369,9 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
       const int m = 2 * l, nn = 2 * r;
       if (mid >= 32) wg_gemm_mfma(TH, m, nn, mid, a0, mid, 1, a1, nn, 1);  // theta[(a,p)][(p',c)]: on the matrix cores from bond 32 on
       else wg_gemm<false, false>(TH, m, nn, mid, a0, mid, 1, a1, nn, 1);
-      {
+      if (o == OP_M2) {  // a 4x4 from the table: one pass over theta
+        wg_matrix_2q(TH, l, r, g.mats + ((long)st * g.mats_stride + g.mat[i]) * 16, jl);
+      } else {
         const double th = 0.5 * M_PI * alpha[i];
         const double cs = cos(th), sn = sin(th);
         for (int e = tid; e < l * r; e += BT) {

@@ -33,9 +33,48 @@ zgeqrf_t p_zgeqrf = nullptr;
 zungqr_t p_zungqr = nullptr;
 zgemm_t p_zgemm = nullptr;
 
-enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8 };  // ansatz.py
+// ansatz.py.  Codes 8 and 9 are the matrix gates: valid only in a program that comes with a matrix table (N_OPS_MAT codes then).
+enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10 };
 
-inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ; }
+inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ || o == OP_M2; }
+
+// sum_s m[s] t[s] over n terms in the fixed order of the matrix gates: column 0 first, ascending, the real and the imaginary part
+// each one chain of fused multiply-adds (the device builder's mat_dot, qk_build_kernels.h, does the same arithmetic)
+inline cd mat_dot(const cd* m, const cd* t, int n) {
+  double re = m[0].real() * t[0].real(), im = m[0].real() * t[0].imag();
+  re = std::fma(-m[0].imag(), t[0].imag(), re);
+  im = std::fma(m[0].imag(), t[0].real(), im);
+  for (int s = 1; s < n; ++s) {
+    re = std::fma(m[s].real(), t[s].real(), re);
+    re = std::fma(-m[s].imag(), t[s].imag(), re);
+    im = std::fma(m[s].real(), t[s].imag(), im);
+    im = std::fma(m[s].imag(), t[s].real(), im);
+  }
+  return cd(re, im);
+}
+
+// The matrix table of a program: every matrix gate's index inside 0..n_mats-1, its 2x2 ([:2][:2] of the slot) or 4x4 finite and
+// unitary, max |M^H M - 1| <= 1e-12 (the canonical-form bookkeeping assumes unitary gates).  Empty string, or what is wrong.
+std::string check_table(int n_ops, const int8_t* op, int n_mats, const cd* mats, const int32_t* mat) {
+  for (int i = 0; i < n_ops; ++i) {
+    if (op[i] != OP_M1 && op[i] != OP_M2) continue;
+    const int k = mat[i], d = op[i] == OP_M1 ? 2 : 4;
+    if (k < 0 || k >= n_mats) return "gate " + std::to_string(i) + ": matrix index " + std::to_string(k) + " outside 0.." + std::to_string(n_mats - 1);
+    const cd* m = mats + (size_t)k * 16;
+    double dev = 0;
+    bool finite = true;
+    for (int a = 0; a < d; ++a)
+      for (int b = 0; b < d; ++b) {
+        finite = finite && std::isfinite(m[a * 4 + b].real()) && std::isfinite(m[a * 4 + b].imag());
+        cd g = (a == b) ? cd(-1, 0) : cd(0, 0);
+        for (int r = 0; r < d; ++r) g += std::conj(m[r * 4 + a]) * m[r * 4 + b];
+        dev = std::max(dev, std::abs(g));
+      }
+    if (!finite || !(dev <= 1e-12))
+      return "gate " + std::to_string(i) + ": the matrix of table entry " + std::to_string(k) + (finite ? " is not unitary (max |M^H M - 1| > 1e-12)" : " has an entry that is not finite");
+  }
+  return "";
+}
 
 // row-major C[m x n] = A[m x k] * B[k x n]  (as column-major C^T = B^T A^T)
 void gemm_rm(int m, int n, int k, const cd* A, const cd* B, cd* C) {
@@ -135,26 +174,47 @@ int qkb_init(const char* openblas_path) {
 // [l][2][r] row-major (free it with qkb_free), and *fidelity.  Returns 0, or a negative code with qkb_last_error().
 // Op codes: 0 H, 1 Rz, 2 XXPhase, 3 SWAP, 4 Rx, 5 Ry, 6 YYPhase, 7 ZZPhase (two-qubit gates on (q0, q0+1)); any other
 // code fails the call with -7 before a gate is applied.
-int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                     double value_of_zero, int32_t max_bond, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out, double* fidelity_out);
+int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
+                       int32_t max_bond, int32_t n_mats, const double* mats, const int32_t* mat, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out,
+                       double* fidelity_out);
 int qkb_simulate(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
                  double value_of_zero, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out, double* fidelity_out) {
-  return qkb_simulate_chi(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, 0, dims_out, tensors_out, n_complex_out, fidelity_out);
+  return qkb_simulate_gates(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, 0, 0, nullptr, nullptr, dims_out, tensors_out, n_complex_out, fidelity_out);
 }
 // max_bond > 0: at most that many singular values survive a gate (the chi of pytket-cutensornet's Config, reference
 // gpu_backend/kernel_state_ansatz.py:141-144); the lost weight goes into the fidelity like any other truncation.
 int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
                      double value_of_zero, int32_t max_bond, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out, double* fidelity_out) {
+  return qkb_simulate_gates(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, 0, nullptr, nullptr, dims_out, tensors_out, n_complex_out, fidelity_out);
+}
+// qkb_simulate_chi with a matrix table: with n_mats > 0 the program may also hold op codes 8 (a 2x2 on q0) and 9 (a 4x4 on (q0, q0+1),
+// index (s_q0, s_q0+1), q0 most significant); the matrix of gate i is mats[mat[i]], complex128 [n_mats][4][4] row-major (re, im), a 2x2 in
+// [:2][:2]; alpha[i] is ignored there, mat[i] is read at those codes only.  new[(p,p')] = sum M[(p,p')][(s,s')] old[(s,s')].  A mat[i] outside
+// 0..n_mats-1 or a matrix that is not finite and unitary to 1e-12 fails the call with -8 before a gate is applied; with n_mats = 0
+// codes 8 and 9 are unknown (-7).
+int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
+                       int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out,
+                       double* fidelity_out) {
   if (!p_zgesdd) {
     g_err = "qkb_init has not been called";
     return -1;
   }
   const int n = n_qubits;
+  const cd* mats = reinterpret_cast<const cd*>(mats_raw);
+  if (n_mats < 0 || (n_mats > 0 && (!mats || !mat))) {
+    g_err = "a matrix table needs n_mats >= 0, mats and mat";
+    return -8;
+  }
+  const int n_codes = n_mats > 0 ? N_OPS_MAT : N_OPS;
   for (int i = 0; i < n_ops; ++i)
-    if (op[i] < 0 || op[i] >= N_OPS) {
-      g_err = "unknown gate op code " + std::to_string((int)op[i]) + " (valid: 0.." + std::to_string(N_OPS - 1) + ")";
+    if (op[i] < 0 || op[i] >= n_codes) {
+      g_err = "unknown gate op code " + std::to_string((int)op[i]) + " (valid: 0.." + std::to_string(n_codes - 1) + ")";
       return -7;
     }
+  if (n_mats > 0) {
+    g_err = check_table(n_ops, op, n_mats, mats, mat);
+    if (!g_err.empty()) return -8;
+  }
   std::vector<Tensor> A(n);
   for (auto& t : A) t.v = {cd(1, 0), cd(0, 0)};
   std::vector<int> two_q_pos;
@@ -192,6 +252,17 @@ int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const in
         for (int c = 0; c < t.r; ++c) {
           t.at(a, 0, c) *= std::conj(ph);
           t.at(a, 1, c) *= ph;
+        }
+      continue;
+    }
+    if (o == OP_M1) {  // a 2x2 from the table
+      const cd* M = mats + (size_t)mat[i] * 16;
+      Tensor& t = A[q];
+      for (int a = 0; a < t.l; ++a)
+        for (int c = 0; c < t.r; ++c) {
+          const cd v[2] = {t.at(a, 0, c), t.at(a, 1, c)};
+          t.at(a, 0, c) = mat_dot(M, v, 2);
+          t.at(a, 1, c) = mat_dot(M + 4, v, 2);
         }
       continue;
     }
@@ -283,6 +354,16 @@ int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const in
           TH(a, 0, 1, c) *= ph;
           TH(a, 1, 0, c) *= ph;
           TH(a, 1, 1, c) *= phc;
+        }
+    } else if (o == OP_M2) {  // a 4x4 from the table on (t00, t01, t10, t11)
+      const cd* M = mats + (size_t)mat[i] * 16;
+      for (int a = 0; a < l; ++a)
+        for (int c = 0; c < r; ++c) {
+          const cd v[4] = {TH(a, 0, 0, c), TH(a, 0, 1, c), TH(a, 1, 0, c), TH(a, 1, 1, c)};
+          TH(a, 0, 0, c) = mat_dot(M, v, 4);
+          TH(a, 0, 1, c) = mat_dot(M + 4, v, 4);
+          TH(a, 1, 0, c) = mat_dot(M + 8, v, 4);
+          TH(a, 1, 1, c) = mat_dot(M + 12, v, 4);
         }
     } else {  // XXPhase: cos(th) 1 - i sin(th) X(x)X
       const double th = 0.5 * M_PI * alpha[i];

@@ -122,6 +122,8 @@ _SIGNATURES = [
     ("qk_built_destroy", C.c_int, [_P]),
     ("qk_mps_set_from_built", C.c_int, [_P, _P, C.POINTER(_P)]),
     ("qk_build_mps_scan", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.POINTER(_P)]),
+    ("qk_build_mps_gates", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
+                                     C.POINTER(_P)]),
     ("qk_built_num_snapshots", C.c_int, [_P]),
     ("qk_built_checkpoints", C.c_int, [_P, _P]),
     ("qk_built_info_at", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
@@ -1342,6 +1344,56 @@ class MpsSet:
             pass
 
 
+class _GateProgram:
+    """The circuits of one device-builder call as the arrays of ``qk_build_mps_gates``: the shared gate structure (``op``, ``q0`` and,
+    with a matrix table, ``mat``), the per-state angles, and the matrix table of op codes 8 and 9 -- shared (stride 0) when every
+    circuit's ``mats`` is the same array bit for bit, otherwise stacked per state (stride n_mats).  ``QkError`` when the circuits do
+    not share their gate structure.  The table goes to the C entry as it is: it validates indices and unitarity."""
+
+    def __init__(self, what, circuits):
+        c0 = circuits[0]
+        self.what = what
+        self.n, self.ns = int(c0.n_qubits), len(circuits)
+        self.op = np.ascontiguousarray(c0.op, dtype=np.int8)
+        self.q0 = np.ascontiguousarray(c0.q0, dtype=np.int32)
+        with_table = getattr(c0, "mats", None) is not None and getattr(c0, "mat", None) is not None
+        for c in circuits[1:]:
+            same = c.n_qubits == c0.n_qubits and np.array_equal(c.op, c0.op) and np.array_equal(c.q0, c0.q0)
+            has = getattr(c, "mats", None) is not None and getattr(c, "mat", None) is not None
+            if same and (has != with_table or (has and not (np.array_equal(c.mat, c0.mat) and np.shape(c.mats) == np.shape(c0.mats)))):
+                same = False
+            if not same:
+                raise QkError(f"{what}: the circuits of one call must share their gate structure")
+        self.alpha = np.ascontiguousarray(np.stack([np.asarray(c.alpha, dtype=np.float64) for c in circuits]))
+        self.n_mats, self.stride, self.mats, self.mat = 0, 0, None, None
+        if with_table:
+            m0 = np.asarray(c0.mats)
+            if m0.ndim != 3 or m0.shape[1:] != (4, 4) or np.shape(c0.mat) != self.op.shape:
+                raise QkError(f"{what}: the matrix table must be [n_mats][4][4] with one index per gate, got shapes {m0.shape} and {np.shape(c0.mat)}")
+            self.n_mats = int(m0.shape[0])
+            self.mat = np.ascontiguousarray(c0.mat, dtype=np.int32)
+            tables = [np.ascontiguousarray(c.mats, dtype=np.complex128) for c in circuits]
+            if all(t is tables[0] or t.tobytes() == tables[0].tobytes() for t in tables[1:]):
+                self.mats = tables[0]
+            else:
+                self.mats, self.stride = np.ascontiguousarray(np.stack(tables)), self.n_mats
+
+    def build(self, ctx, truncation_fidelity, value_of_zero, max_bond, flags, cps=None, src=None, src_j=0):
+        """One launch of the device builder: the handle of the built states (``qk_built``)."""
+        n_ops = int(self.op.shape[0])
+        h = _P()
+        head = (ctx._h, self.ns, self.n, n_ops, self.op.ctypes.data, self.q0.ctypes.data, self.alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero),
+                int(max_bond), flags)
+        if cps is None and (self.n_mats == 0 or n_ops == 0):  # no snapshots, no table: the plain entry
+            _check(lib().qk_build_mps(*head, C.byref(h)), "qk_build_mps")
+            return h
+        if cps is None:
+            cps = np.array([n_ops], dtype=np.int32)  # the one-checkpoint scan: a snapshot after the whole program
+        _check(lib().qk_build_mps_gates(*head, int(cps.shape[0]), cps.ctypes.data, src, src_j, self.n_mats, self.mats.ctypes.data if self.n_mats else None, self.stride,
+                                        self.mat.ctypes.data if self.n_mats else None, C.byref(h)), "qk_build_mps_gates" if self.n_mats else "qk_build_mps_scan")
+        return h
+
+
 class BuiltScan:
     """The snapshots of ``Context.build_mps_scan``: owns the builder's handle (one device heap with every snapshot of every state)
     until ``close()``; a context manager.  ``checkpoints[j]`` gates were done at snapshot j; the last snapshot is the finished
@@ -1520,17 +1572,9 @@ class Context:
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_mps needs at least one circuit")
-        c0 = circuits[0]
-        op = np.ascontiguousarray(c0.op, dtype=np.int8)
-        q0 = np.ascontiguousarray(c0.q0, dtype=np.int32)
-        for c in circuits[1:]:
-            if c.n_qubits != c0.n_qubits or not np.array_equal(c.op, c0.op) or not np.array_equal(c.q0, c0.q0):
-                raise QkError("build_mps: the circuits of one call must share their gate structure")
-        alpha = np.ascontiguousarray(np.stack([np.asarray(c.alpha, dtype=np.float64) for c in circuits]))
-        n, ns = int(c0.n_qubits), len(circuits)
-        h = _P()
-        _check(lib().qk_build_mps(self._h, ns, n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data,
-                                  max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero), int(max_bond), (1 if partial else 0) | (2 if truncate else 0), C.byref(h)), "qk_build_mps")
+        prog = _GateProgram("build_mps", circuits)
+        n, ns = prog.n, prog.ns
+        h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0))
         try:
             dims = np.zeros((ns, n + 1), dtype=np.int32)
             fid = np.zeros(ns, dtype=np.float64)
@@ -1561,17 +1605,10 @@ class Context:
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_mps_set needs at least one circuit")
-        c0 = circuits[0]
-        op = np.ascontiguousarray(c0.op, dtype=np.int8)
-        q0 = np.ascontiguousarray(c0.q0, dtype=np.int32)
-        for c in circuits[1:]:
-            if c.n_qubits != c0.n_qubits or not np.array_equal(c.op, c0.op) or not np.array_equal(c.q0, c0.q0):
-                raise QkError("build_mps_set: the circuits of one call must share their gate structure")
-        alpha = np.ascontiguousarray(np.stack([np.asarray(c.alpha, dtype=np.float64) for c in circuits]))
-        n, ns = int(c0.n_qubits), len(circuits)
-        h, hs = _P(), _P()
-        _check(lib().qk_build_mps(self._h, ns, n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data,
-                                  max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero), int(max_bond), 2 if truncate else 0, C.byref(h)), "qk_build_mps")
+        prog = _GateProgram("build_mps_set", circuits)
+        n, ns = prog.n, prog.ns
+        hs = _P()
+        h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, 2 if truncate else 0)
         try:
             dims = np.zeros((ns, n + 1), dtype=np.int32)
             fid = np.zeros(ns, dtype=np.float64)
@@ -1599,25 +1636,16 @@ class Context:
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_mps_scan needs at least one circuit")
-        c0 = circuits[0]
-        op = np.ascontiguousarray(c0.op, dtype=np.int8)
-        q0 = np.ascontiguousarray(c0.q0, dtype=np.int32)
-        cps = np.ascontiguousarray(check_checkpoints(checkpoints, int(op.shape[0])), dtype=np.int32)
-        for c in circuits[1:]:
-            if c.n_qubits != c0.n_qubits or not np.array_equal(c.op, c0.op) or not np.array_equal(c.q0, c0.q0):
-                raise QkError("build_mps_scan: the circuits of one call must share their gate structure")
-        alpha = np.ascontiguousarray(np.stack([np.asarray(c.alpha, dtype=np.float64) for c in circuits]))
-        n, ns = int(c0.n_qubits), len(circuits)
+        cps = np.ascontiguousarray(check_checkpoints(checkpoints, int(np.shape(circuits[0].op)[0])), dtype=np.int32)
+        prog = _GateProgram("build_mps_scan", circuits)
+        n, ns = prog.n, prog.ns
         src, src_j = None, 0
         if initial is not None:
             scan, j = initial
             if not isinstance(scan, BuiltScan):
                 raise ValueError(f"initial must be (BuiltScan, snapshot index), got {initial!r}")
             src, src_j = scan.handle, scan._index(j)
-        h = _P()
-        _check(lib().qk_build_mps_scan(self._h, ns, n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
-                                       float(value_of_zero), int(max_bond), (1 if partial else 0) | (2 if truncate else 0), int(cps.shape[0]), cps.ctypes.data, src, src_j, C.byref(h)),
-               "qk_build_mps_scan")
+        h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0), cps, src, src_j)
         return BuiltScan(self, h, ns, n)
 
     def set_from_packed(self, dims_true, offsets, planes_ptr: int, n_doubles: int) -> MpsSet:
@@ -1640,17 +1668,9 @@ class Context:
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_share needs at least one circuit")
-        c0 = circuits[0]
-        op = np.ascontiguousarray(c0.op, dtype=np.int8)
-        q0 = np.ascontiguousarray(c0.q0, dtype=np.int32)
-        for c in circuits[1:]:
-            if c.n_qubits != c0.n_qubits or not np.array_equal(c.op, c0.op) or not np.array_equal(c.q0, c0.q0):
-                raise QkError("build_share: the circuits of one call must share their gate structure")
-        alpha = np.ascontiguousarray(np.stack([np.asarray(c.alpha, dtype=np.float64) for c in circuits]))
-        n, ns = int(c0.n_qubits), len(circuits)
-        h = _P()
-        _check(lib().qk_build_mps(self._h, ns, n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data,
-                                  max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero), int(max_bond), (1 if partial else 0) | (2 if truncate else 0), C.byref(h)), "qk_build_mps")
+        prog = _GateProgram("build_share", circuits)
+        n, ns = prog.n, prog.ns
+        h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0))
         try:
             dims = np.zeros((ns, n + 1), dtype=np.int32)
             fid = np.zeros(ns, dtype=np.float64)

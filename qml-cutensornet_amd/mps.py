@@ -22,7 +22,7 @@ import numpy as np
 from scipy.linalg import qr as _qr
 from scipy.linalg import svd as _svd
 
-from .ansatz import OP_H, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_checkpoints, check_op_codes, is_two_qubit
+from .ansatz import OP_H, OP_M1, OP_M2, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_checkpoints, check_matrix_gates, is_two_qubit
 
 _SQRT_HALF = 0.7071067811865476
 _YY_SIGN = np.array([[1.0, -1.0], [-1.0, 1.0]])[None, :, :, None]  # c 1 - i s Y(x)Y: +i s on |00>,|11>, -i s on |01>,|10>
@@ -450,6 +450,8 @@ def _native_builder():
             lib.qkb_init.argtypes = [C.c_char_p]
             lib.qkb_simulate_chi.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                              C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+            lib.qkb_simulate_gates.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
             lib.qkb_free.argtypes = [C.c_void_p]
             if blas and lib.qkb_init(os.path.realpath(blas[0]).encode()) == 0:
                 _NATIVE = lib
@@ -471,9 +473,18 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
     alpha = np.ascontiguousarray(circuit.alpha, dtype=np.float64)
     dims = np.zeros(n + 1, dtype=np.int32)
     block, count, fid = C.c_void_p(), C.c_int64(), C.c_double()
-    rc = lib.qkb_simulate_chi(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
-                              float(value_of_zero), int(max_bond or 0), dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid))
-    if rc == -7:  # an op code outside 0..7
+    # the matrix table of codes 8 and 9, handed over as it is: the native builder validates it (range of mat, finite, unitary)
+    n_mats, mats, mat = 0, None, None
+    if circuit.mats is not None and circuit.mat is not None:
+        mats = np.ascontiguousarray(circuit.mats, dtype=np.complex128)
+        mat = np.ascontiguousarray(circuit.mat, dtype=np.int32)
+        if mats.ndim != 3 or mats.shape[1:] != (4, 4) or mat.shape != op.shape:
+            raise ValueError(f"the matrix table must be [n_mats][4][4] with one index per gate, got shapes {mats.shape} and {mat.shape}")
+        n_mats = int(mats.shape[0])
+    rc = lib.qkb_simulate_gates(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
+                                float(value_of_zero), int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None,
+                                dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid))
+    if rc in (-7, -8):  # an op code outside 0..7 (0..9 with a table); a matrix gate whose index or matrix is bad
         raise ValueError(f"native MPS builder: {lib.qkb_last_error().decode()}")
     if rc != 0:
         raise RuntimeError(f"native MPS builder failed: {lib.qkb_last_error().decode()}")
@@ -644,9 +655,14 @@ def _use_native() -> bool:
 
 def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: float, max_bond: int | None = None, checkpoints=None):
     """The numpy loop.  With ``checkpoints`` (validated gate counts) the return value is the list of snapshots: copies, the run itself
-    is the one without them."""
+    is the one without them.  A circuit with a matrix table (``circuit.mat``, ``circuit.mats``) may hold op codes 8 and 9, a 2x2 on q0
+    and a 4x4 on (q0, q0+1); ``ValueError`` for a table entry that is not unitary, an index outside the table or a gate outside
+    the register."""
     n = circuit.n_qubits
-    check_op_codes(circuit.op)
+    mat, mats = check_matrix_gates(circuit.op, circuit.mat, circuit.mats)  # (None, None): no table, codes 8 and 9 are unknown
+    for i, (o, q) in enumerate(zip(circuit.op.tolist(), circuit.q0.tolist())):
+        if not 0 <= q < n - (1 if is_two_qubit(o) else 0):
+            raise ValueError(f"gate {i} on a qubit outside the register of {n}")
     budget = max(0.0, 1.0 - float(truncation_fidelity))
     A = []
     for _ in range(n):
@@ -676,6 +692,11 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             t[:, 0] *= ph.conjugate()
             t[:, 1] *= ph
             A[q] = t
+            continue
+        if o == OP_M1:  # a 2x2 from the table: new[p] = sum_s M[p][s] old[s]
+            m = mats[mat[i]]
+            t = A[q]
+            A[q] = np.stack((m[0, 0] * t[:, 0] + m[0, 1] * t[:, 1], m[1, 0] * t[:, 0] + m[1, 1] * t[:, 1]), axis=1)
             continue
         if not is_two_qubit(o):  # Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
             th = 0.5 * np.pi * a
@@ -711,6 +732,8 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             th = 0.5 * np.pi * a
             ph = np.exp(1j * th)
             theta = theta * np.array([[ph.conjugate(), ph], [ph, ph.conjugate()]])[None, :, :, None]
+        elif o == OP_M2:  # a 4x4 from the table: new[(p,p')] = sum M[(p,p')][(s,s')] old[(s,s')]
+            theta = np.einsum("pqst,lstr->lpqr", mats[mat[i]].reshape(2, 2, 2, 2), theta)
         else:  # XXPhase: cos(th) 1 - i sin(th) X(x)X
             th = 0.5 * np.pi * a
             theta = np.cos(th) * theta - 1j * np.sin(th) * theta[:, ::-1, ::-1, :]
