@@ -759,7 +759,9 @@ int qk_selftest_mfma(qk_ctx* ctx);
  * 2 = XXPhase on (q0, q0+1), 3 = SWAP on (q0, q0+1), 4 = Rx, 5 = Ry, 6 = YYPhase on (q0, q0+1), 7 = ZZPhase on
  * (q0, q0+1); TKET matrices, theta = pi alpha / 2) and differ in the half-turn angles alpha[n_states][n_ops].
  * Op codes 8 (a 2x2 on q0) and 9 (a 4x4 on (q0, q0+1)) are the matrix gates of qk_build_mps_gates below: valid only in a call that
- * comes with a matrix table.  An op code outside 0..7 -- outside 0..9 with a table -- is QK_EINVAL before anything runs.
+ * comes with a matrix table; op code 10 (a one-qubit Kraus channel on q0) belongs to qk_build_mps_channels: valid only in a call that
+ * comes with a channel table.  An op code outside 0..7 -- outside 0..9 with a matrix table, and 10 with a channel table -- is QK_EINVAL
+ * before anything runs.
  * One persistent launch; per two-qubit gate a one-sided Jacobi SVD and the truncation rule of the host builder:
  * drop the trailing singular values whose squared weight stays <= trunc_budget (= 1 - truncation_fidelity,
  * G:141-144; criterion as KernelPkg.jl:68), values <= value_of_zero never count.  max_bond bounds every bond
@@ -805,7 +807,8 @@ int qk_build_mps_scan(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n
  * states -- or n_mats -- state s reads mats + s * n_mats * 32 doubles: a gate that depends on the data point.
  * Before anything runs, QK_EINVAL with the gate's position in the message for: mat[i] outside 0..n_mats-1; a matrix with an entry that
  * is not finite; a matrix that is not unitary, max |M^H M - 1| > 1e-12 (the canonical-form bookkeeping assumes unitary gates: a
- * one-qubit gate never moves the orthogonality centre); a matrix gate past the last qubit (pair).  With n_mats = 0 the call IS
+ * one-qubit gate never moves the orthogonality centre; what is not unitary -- a projector, a post-selection, noise -- is a channel of
+ * qk_build_mps_channels); a matrix gate past the last qubit (pair).  With n_mats = 0 the call IS
  * qk_build_mps_scan: codes 8 and 9 are unknown op codes.  Snapshots and resume work unchanged; a resumed build is handed the table
  * of the gates that follow.                                                                                                        */
 int qk_build_mps_gates(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
@@ -813,6 +816,42 @@ int qk_build_mps_gates(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t 
                        int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
                        int32_t n_mats, const double* mats /* [stride ? n_states : 1][n_mats][4][4][2] */, int32_t mats_state_stride,
                        const int32_t* mat /* [n_ops] */, qk_built** out);
+/* Kraus channels.  qk_build_mps_channels is qk_build_mps_gates (its arguments in their order) plus a channel table: with n_channels > 0
+ * the program may hold op code 10, a one-qubit Kraus channel on qubit q0, run as a quantum trajectory or with a forced branch
+ * (projectors, post-selection, a mid-circuit measurement with a chosen outcome, replay of a recorded trajectory).  Channel c is
+ * n_kraus[c] (1..4) matrices kraus[c][k][s'][s] = <s'|K_k|s>: complex128 [n_channels][4][2][2], (re, im) interleaved.  Gate i reads
+ * channel channel[i] and branch[i]: -1 draws the branch, k >= 0 forces branch k; both rows are read only where op is 10, alpha[i] and
+ * mat[i] are ignored there.  branch_state_stride is 0 -- one row for all states -- or n_ops -- state s reads branch + s * n_ops.
+ * The step on A_q = t[l][2][r]: the orthogonality centre is brought onto site q exactly (the centre moves of the two-qubit gates; no
+ * truncation); N = sum |t|^2, p_k = sum_{a,c} |K_k t[a][.][c]|^2, tot = p_0 + .. + p_{m-1} in ascending order; b = branch[i], or drawn:
+ * the first k with p_k > 0 and u tot < p_0 + .. + p_k (none: the last k with p_k > 0), u the uniform of Philox4x32-10 with counter
+ * (first_gate + i, trajectory[s], state_index[s], 2) and key (seed & 0xffffffff, seed >> 32), made from the first two output words
+ * as the sampler's (qk_sample_host; stream 0 draws shots, stream 1 bases, stream 2 branches); A_q <- K_b A_q / sqrt(p_b), and log(p_b
+ * / N) is added to the state's log-weight.  The centre stays on q, the bonds do not change.  state_index and trajectory
+ * ([n_states]) may be NULL: 0 .. n_states-1 and all 0.  A state's result depends on seed, its two indices, its gates and the table
+ * only -- not on the other states of the call, their number, their order, or the launch; the sums use no atomics.  To that end a
+ * call with a channel table, and a build resumed from a snapshot of one, takes its workgroup shape from max_bond alone (the switch
+ * to 512 threads for at most one state per CU at max_bond 33..64 is for programs without channels); QK_BUILD_WGS overrides the shape
+ * and with it the bits.  first_gate is the position of gate 0 in the uninterrupted program: a resumed build (`initial`) is handed
+ * the gates done so far and draws what the uninterrupted run draws; its log-weight goes on from the snapshot's, through any entry
+ * point, also when the gates that remain hold no code 10 (every record then carries the snapshot's).
+ * Before anything runs, QK_EINVAL with the gate's position for: channel[i] outside the table; n_kraus outside 1..4; an entry that is
+ * not finite; branch[i] outside -1 .. m-1; a DRAWN channel that is not trace preserving, max |sum_k K_k^H K_k - 1| > 1e-12 (a forced
+ * branch may be any finite matrix); a channel gate outside the register.  At run time QK_EDEVICE, naming the state and the gate, when
+ * p_b is 0 or not finite (an impossible outcome was post-selected) or tot is 0 in a draw.  With n_channels = 0 the call IS
+ * qk_build_mps_gates: code 10 is an unknown op code.                                                                                 */
+int qk_build_mps_channels(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
+                          const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
+                          int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
+                          int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
+                          const double* kraus /* [n_channels][4][2][2][2] */, const int32_t* n_kraus /* [n_channels] */,
+                          const int32_t* channel /* [n_ops] */, const int32_t* branch /* [stride ? n_states : 1][n_ops] */,
+                          int32_t branch_state_stride, uint64_t seed, const uint32_t* state_index, const uint32_t* trajectory,
+                          uint32_t first_gate, qk_built** out);
+int qk_built_logw_at(const qk_built* built, int32_t j, double* logw /* [n_states] */); /* log-weights at snapshot j (0 without channels) */
+int qk_built_num_channel_gates(const qk_built* built);                    /* op-code-10 gates of the program */
+/* The branch every channel gate took, in program order: [n_states][n_channel_gates]; -1 where a dropped state stopped early */
+int qk_built_branches(const qk_built* built, int8_t* branches);
 int qk_built_num_snapshots(const qk_built* built);                        /* 1 for qk_build_mps */
 int qk_built_checkpoints(const qk_built* built, int32_t* checkpoints);    /* [num_snapshots] gates done at each snapshot */
 /* Snapshot j: dims[n_states][n_qubits+1], fidelity so far [n_states], offsets[n_states] into the one heap (complex elements),

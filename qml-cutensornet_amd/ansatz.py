@@ -26,6 +26,14 @@ table ``mats`` (complex128 [n_mats][4][4]; a 2x2 sits in ``[:2, :2]``) through a
 per-gate index ``mat``.  The 4x4 index is (s_q, s_{q+1}) with qubit q most
 significant (TKET's order).  The named constants X, Y, Z, S, Sdg, T, Tdg, V, Vdg,
 SX, SXdg, CX, CY, CZ are entries of that table.
+
+Op code 10 (``Kraus1q``) is a one-qubit Kraus channel applied at the orthogonality
+centre: channel c is 1 <= m_c <= 4 complex 2x2 matrices ``kraus[c][:m_c]`` (table
+complex128 [n_channels][4][2][2] plus ``n_kraus``), gate i reads channel
+``channel[i]`` and either draws its branch as a quantum trajectory (``branch[i]`` =
+-1) or takes the forced branch ``branch[i]`` (projectors, post-selection, replay).
+Project, Measure, PostSelect, AmplitudeDamping, PhaseDamping, Depolarizing, BitFlip
+and PhaseFlip are entries of that table.
 """
 from __future__ import annotations
 
@@ -38,9 +46,12 @@ OP_RX, OP_RY, OP_YY, OP_ZZ = 4, 5, 6, 7  # custom feature maps (CircuitAnsatz, B
 OP_M1, OP_M2 = 8, 9  # matrix gates: a 2x2 on q0, a 4x4 on (q0, q0+1); the matrix of gate i is mats[mat[i]]
 N_OPS = 8  # codes 0 .. N_OPS-1 are valid without a matrix table; every builder rejects any other
 N_OPS_MAT = 10  # codes 0 .. N_OPS_MAT-1 are valid in a program that comes with a matrix table
+OP_K1 = 10  # a one-qubit Kraus channel on q0, drawn or forced: valid only in a program that comes with a channel table
+MAX_KRAUS = 4  # matrices per channel
+TRACE_TOL = 1e-12  # max |sum_k K_k^H K_k - 1| a drawn channel may have
 UNITARY_TOL = 1e-12  # max |M^H M - 1| a matrix gate may have: the builders' canonical-form bookkeeping assumes unitary gates
 _OP_NAMES = {OP_H: "H", OP_RZ: "Rz", OP_XX: "XXPhase", OP_SWAP: "SWAP", OP_RX: "Rx", OP_RY: "Ry", OP_YY: "YYPhase", OP_ZZ: "ZZPhase",
-             OP_M1: "Unitary1q", OP_M2: "Unitary2q"}
+             OP_M1: "Unitary1q", OP_M2: "Unitary2q", OP_K1: "Kraus1q"}
 _OP_CODES = {name: code for code, name in _OP_NAMES.items()}
 _TWO_QUBIT = (OP_XX, OP_SWAP, OP_YY, OP_ZZ, OP_M2)
 _PARAMETRISED = (OP_RZ, OP_XX, OP_RX, OP_RY, OP_YY, OP_ZZ)
@@ -60,6 +71,90 @@ _NAMED_2Q = {  # control first: index (s_control, s_target)
     "CZ": [[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, -1]],
 }
 _NAMED = {**_NAMED_1Q, **_NAMED_2Q}
+_CHANNEL_NAMES = ("Kraus1q", "Project", "Measure", "PostSelect", "AmplitudeDamping", "PhaseDamping", "Depolarizing", "BitFlip", "PhaseFlip")
+
+
+def channel_kraus(name, params, where="channel"):
+    """The Kraus matrices and the forced branch of a named channel: ``(K complex128 [m, 2, 2], branch)`` with ``branch`` -1 for a
+    channel that is drawn.  ``K[k][s'][s] = <s'|K_k|s>``.
+      * ``Kraus1q  [[K0, ..]]``: 1 .. 4 matrices as given, drawn;
+      * ``Project  [M]``: the one matrix M, forced (any finite 2x2: a projector, a weak measurement's operator);
+      * ``Measure  []``: P0 = |0><0|, P1 = |1><1|, drawn;
+      * ``PostSelect [bit]``: P0, P1 with the branch ``bit`` forced;
+      * ``AmplitudeDamping [g]``: [[1, 0], [0, sqrt(1-g)]], [[0, sqrt g], [0, 0]];
+      * ``PhaseDamping [lam]``: [[1, 0], [0, sqrt(1-lam)]], [[0, 0], [0, sqrt lam]];
+      * ``Depolarizing [p]``: sqrt(1 - 3p/4) I, sqrt(p/4) X, sqrt(p/4) Y, sqrt(p/4) Z;
+      * ``BitFlip [p]``: sqrt(1-p) I, sqrt p X;   ``PhaseFlip [p]``: sqrt(1-p) I, sqrt p Z.
+    ``ValueError`` for a wrong parameter count, a probability outside [0, 1] or matrices of the wrong shape."""
+    if name not in _CHANNEL_NAMES:
+        raise ValueError(f"unknown channel {name!r} (supported: {', '.join(_CHANNEL_NAMES)})")
+    I2, X, Y, Z = np.eye(2), np.array(_NAMED_1Q["X"]), np.array(_NAMED_1Q["Y"]), np.array(_NAMED_1Q["Z"])
+    P0, P1 = np.diag([1.0, 0.0]), np.diag([0.0, 1.0])
+    if name in ("Kraus1q", "Project"):
+        try:
+            K = np.asarray(params, dtype=np.complex128)
+        except (TypeError, ValueError):
+            raise ValueError(f"{where} ({name}): the parameter must be a list of complex 2x2 matrices") from None
+        if K.ndim == 4 and K.shape[0] == 1:
+            K = K[0]
+        if name == "Project":
+            if K.shape == (2, 2):
+                K = K[None]
+            if K.shape != (1, 2, 2):
+                raise ValueError(f"{where} (Project): expected one 2x2 matrix, got shape {K.shape}")
+            return np.ascontiguousarray(K), 0
+        if K.ndim != 3 or K.shape[1:] != (2, 2) or not 1 <= K.shape[0] <= MAX_KRAUS:
+            raise ValueError(f"{where} (Kraus1q): expected a list of 1..{MAX_KRAUS} 2x2 matrices, got shape {K.shape}")
+        return np.ascontiguousarray(K), -1
+    params = [] if params is None else list(np.ravel(params))
+    want = 0 if name == "Measure" else 1
+    if len(params) != want:
+        raise ValueError(f"{where} ({name}): expected {want} parameter(s), got {params}")
+    if name == "Measure":
+        return np.stack([P0, P1]).astype(np.complex128), -1
+    if name == "PostSelect":
+        if params[0] not in (0, 1):
+            raise ValueError(f"{where} (PostSelect): the bit must be 0 or 1, got {params[0]!r}")
+        return np.stack([P0, P1]).astype(np.complex128), int(params[0])
+    p = float(params[0])
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"{where} ({name}): the parameter must lie in [0, 1], got {p!r}")
+    if name == "AmplitudeDamping":
+        K = [np.diag([1.0, np.sqrt(1.0 - p)]), np.array([[0.0, np.sqrt(p)], [0.0, 0.0]])]
+    elif name == "PhaseDamping":
+        K = [np.diag([1.0, np.sqrt(1.0 - p)]), np.diag([0.0, np.sqrt(p)])]
+    elif name == "Depolarizing":
+        K = [np.sqrt(1.0 - 0.75 * p) * I2, np.sqrt(0.25 * p) * X, np.sqrt(0.25 * p) * Y, np.sqrt(0.25 * p) * Z]
+    elif name == "BitFlip":
+        K = [np.sqrt(1.0 - p) * I2, np.sqrt(p) * X]
+    else:
+        K = [np.sqrt(1.0 - p) * I2, np.sqrt(p) * Z]
+    return np.stack(K).astype(np.complex128), -1
+
+
+class _ChannelTable:
+    """The channel table of a program under construction: every channel gate takes a slot of its own, by structure."""
+
+    def __init__(self):
+        self.entries = []
+
+    def slot(self, name, params, where):
+        """(slot, forced branch or -1) of one channel gate as given."""
+        K, branch = channel_kraus(name, params, where)
+        if not np.all(np.isfinite(K)):
+            raise ValueError(f"{where} ({name}): a Kraus matrix has an entry that is not finite")
+        if branch < 0:
+            dev = float(np.abs(np.einsum("kba,kbc->ac", K.conj(), K) - np.eye(2)).max())
+            if not dev <= TRACE_TOL:
+                raise ValueError(f"{where} ({name}): the channel is not trace preserving (max |sum K^H K - 1| = {dev:.3e} > {TRACE_TOL:g})")
+        self.entries.append(K)
+        return len(self.entries) - 1, branch
+
+    def arrays(self):
+        kraus = np.zeros((len(self.entries), MAX_KRAUS, 2, 2), dtype=np.complex128)
+        for c, K in enumerate(self.entries):
+            kraus[c, : K.shape[0]] = K
+        return kraus, np.asarray([K.shape[0] for K in self.entries], dtype=np.int32)
 
 
 def is_two_qubit(o) -> bool:
@@ -67,14 +162,16 @@ def is_two_qubit(o) -> bool:
     return o in _TWO_QUBIT
 
 
-def check_op_codes(op, with_table: bool = False) -> None:
+def check_op_codes(op, with_table: bool = False, with_channels: bool = False) -> None:
     """``ValueError`` unless every code of ``op`` is one of the N_OPS gates -- or, in a program that comes with a matrix table
-    (``with_table``), one of the N_OPS_MAT."""
+    (``with_table``), one of the N_OPS_MAT; code 10 is valid in a program that comes with a channel table (``with_channels``)."""
     op = np.asarray(op)
     top = N_OPS_MAT if with_table else N_OPS
     bad = (op < 0) | (op >= top)
+    if with_channels:
+        bad &= op != OP_K1
     if bad.any():
-        raise ValueError(f"unknown gate op code {int(op[bad][0])} (valid: 0..{top - 1})")
+        raise ValueError(f"unknown gate op code {int(op[bad][0])} (valid: 0..{top - 1}{', 10' if with_channels else ''})")
 
 
 def exchange_qubits(m4) -> np.ndarray:
@@ -91,16 +188,16 @@ def check_unitary(m, where) -> None:
         raise ValueError(f"{where}: the matrix is not unitary (max |M^H M - 1| = {dev:.3e} > {UNITARY_TOL:g})")
 
 
-def check_matrix_gates(op, mat, mats):
+def check_matrix_gates(op, mat, mats, with_channels: bool = False):
     """The matrix table of a program, validated: ``(mat int32 [n_gates], mats complex128 [n_mats, 4, 4])``, or ``(None, None)``
     for a program without one (its codes 8 and 9 are then unknown: ``check_op_codes``).  ``ValueError`` when the table is not
     [n_mats][4][4], when ``mat`` of a matrix gate lies outside 0 .. n_mats-1, or when the 2x2 (``[:2, :2]`` of the slot) or 4x4
     the gate reads is not finite and unitary to UNITARY_TOL; the message names the gate's position in the program."""
     op = np.asarray(op)
     if mats is None or mat is None:
-        check_op_codes(op)
+        check_op_codes(op, with_channels=with_channels)
         return None, None
-    check_op_codes(op, with_table=True)
+    check_op_codes(op, with_table=True, with_channels=with_channels)
     mats = np.asarray(mats)
     if mats.ndim != 3 or mats.shape[1:] != (4, 4):
         raise ValueError(f"the matrix table must be [n_mats][4][4], got shape {mats.shape}")
@@ -109,7 +206,7 @@ def check_matrix_gates(op, mat, mats):
     if mat.shape != op.shape:
         raise ValueError(f"mat must hold one index per gate of the program ({op.shape[0]}), got shape {mat.shape}")
     seen = set()
-    for i in np.flatnonzero(op >= OP_M1):
+    for i in np.flatnonzero((op == OP_M1) | (op == OP_M2)):
         k, d = int(mat[i]), 2 if op[i] == OP_M1 else 4
         if not 0 <= k < mats.shape[0]:
             raise ValueError(f"gate {int(i)}: matrix index {k} outside 0..{mats.shape[0] - 1}")
@@ -117,6 +214,59 @@ def check_matrix_gates(op, mat, mats):
             check_unitary(mats[k, :d, :d], f"gate {int(i)} ({_OP_NAMES[int(op[i])]}, table entry {k})")
             seen.add((k, d))
     return mat, mats
+
+
+def check_channel_gates(op, q0, n_qubits, channel, branch, kraus, n_kraus):
+    """The channel table of a program, validated: ``(channel int32 [n_gates], branch int32 [n_gates], kraus complex128
+    [n_channels, 4, 2, 2], n_kraus int32 [n_channels])``, or ``None`` for a program without one (its code 10 is then unknown).
+    ``ValueError``, naming the gate's position, when a channel gate's ``channel`` lies outside the table, its ``n_kraus`` outside
+    1 .. 4, one of its matrices has an entry that is not finite, its ``branch`` lies outside -1 .. m-1, a drawn channel is not trace
+    preserving (max |sum_k K_k^H K_k - 1| > TRACE_TOL; a forced branch may be any finite matrix) or the gate lies outside the
+    register."""
+    if kraus is None or n_kraus is None or channel is None:
+        return None
+    op = np.asarray(op)
+    kraus = np.asarray(kraus)
+    if kraus.ndim != 4 or kraus.shape[1:] != (MAX_KRAUS, 2, 2):
+        raise ValueError(f"the channel table must be [n_channels][4][2][2], got shape {kraus.shape}")
+    kraus = np.ascontiguousarray(kraus, dtype=np.complex128)
+    n_kraus = np.ascontiguousarray(n_kraus, dtype=np.int32)
+    channel = np.ascontiguousarray(channel, dtype=np.int32)
+    branch = np.full(op.shape, -1, dtype=np.int32) if branch is None else np.ascontiguousarray(branch, dtype=np.int32)
+    if n_kraus.shape != kraus.shape[:1] or channel.shape != op.shape or branch.shape != op.shape:
+        raise ValueError(f"n_kraus must hold one count per channel ({kraus.shape[0]}), channel and branch one entry per gate ({op.shape[0]}); "
+                         f"got shapes {n_kraus.shape}, {channel.shape}, {branch.shape}")
+    q0 = np.asarray(q0)
+    for i in np.flatnonzero(op == OP_K1):
+        i, c, b = int(i), int(channel[i]), int(branch[i])
+        if not 0 <= c < kraus.shape[0]:
+            raise ValueError(f"gate {i}: channel index {c} outside 0..{kraus.shape[0] - 1}")
+        m = int(n_kraus[c])
+        if not 1 <= m <= MAX_KRAUS:
+            raise ValueError(f"gate {i}: channel {c} has {m} Kraus matrices (1..{MAX_KRAUS})")
+        K = kraus[c, :m]
+        if not np.all(np.isfinite(K)):
+            raise ValueError(f"gate {i}: a Kraus matrix of channel {c} has an entry that is not finite")
+        if not -1 <= b < m:
+            raise ValueError(f"gate {i}: branch {b} outside -1..{m - 1}")
+        if b < 0:
+            dev = float(np.abs(np.einsum("kba,kbc->ac", K.conj(), K) - np.eye(2)).max())
+            if not dev <= TRACE_TOL:
+                raise ValueError(f"gate {i}: the drawn channel {c} is not trace preserving (max |sum K^H K - 1| = {dev:.3e} > {TRACE_TOL:g})")
+        if not 0 <= int(q0[i]) < int(n_qubits):
+            raise ValueError(f"gate {i}: channel on a qubit outside the register of {int(n_qubits)}")
+    return channel, branch, kraus, n_kraus
+
+
+def reject_channels(circuits, what) -> None:
+    """``ValueError`` if one of ``circuits`` holds a drawn channel gate: ``what`` builds its states without a seed, state indices
+    and trajectories, so every state would draw as state 0 (or as its position in a rank's share) of trajectory 0.  Forced
+    branches (``Project``, ``PostSelect``) draw nothing and pass."""
+    for c in circuits:
+        k = np.asarray(c.op) == OP_K1
+        if k.any() and (c.branch is None or np.any(np.asarray(c.branch)[k] < 0)):
+            raise ValueError(f"{what}: the circuit holds drawn Kraus channels (op code 10), which this path would run without a seed, state indices and "
+                             f"trajectories; use build_noisy_kernel_matrix / build_noisy_projected_kernel_matrix, or simulate / Context.build_mps_set with them")
 
 
 def entanglement_graph(nq: int, nn: int) -> list[tuple[int, int]]:
@@ -151,6 +301,25 @@ class BoundCircuit:
     alpha: np.ndarray  # float64 [n_gates] half-turns (0 where unused)
     mat: np.ndarray | None = None  # int32 [n_gates] index into mats of a matrix gate (op 8, 9), -1 at the named gates
     mats: np.ndarray | None = None  # complex128 [n_mats, 4, 4]: the matrix table (a 2x2 sits in [:2, :2], the rest of its slot 0)
+    channel: np.ndarray | None = None  # int32 [n_gates] index into kraus of a channel gate (op 10), -1 elsewhere
+    branch: np.ndarray | None = None  # int32 [n_gates] -1: the branch is drawn; k >= 0: branch k is forced (read where op is 10)
+    kraus: np.ndarray | None = None  # complex128 [n_channels, 4, 2, 2]: the channel table, K[s'][s] = <s'|K|s>
+    n_kraus: np.ndarray | None = None  # int32 [n_channels] Kraus matrices of each channel (1..4)
+
+    @property
+    def n_channel_gates(self) -> int:
+        return int(np.count_nonzero(np.asarray(self.op) == OP_K1))
+
+    def with_branches(self, branches) -> "BoundCircuit":
+        """The same program with the branch of its j-th channel gate forced to ``branches[j]`` (-1 leaves it drawn): what replays
+        the recorded ``branches`` of a trajectory."""
+        b = np.asarray(branches, dtype=np.int32).ravel()
+        at = np.flatnonzero(np.asarray(self.op) == OP_K1)
+        if b.shape[0] != at.shape[0]:
+            raise ValueError(f"the program has {at.shape[0]} channel gates, got {b.shape[0]} branches")
+        row = np.full(self.op.shape, -1, dtype=np.int32)
+        row[at] = b
+        return BoundCircuit(self.n_qubits, self.op, self.q0, self.alpha, self.mat, self.mats, self.channel, row, self.kraus, self.n_kraus)
 
     @property
     def n_gates(self) -> int:
@@ -158,12 +327,21 @@ class BoundCircuit:
 
     def as_tuples(self):
         """(name, qubits, params) triples in the shape of the reference's CPU gate list
-        (/root/reference/cpu_backend/kernel_state_ansatz.py:113-131)."""
-        mat, mats = check_matrix_gates(self.op, self.mat, self.mats)
+        (/root/reference/cpu_backend/kernel_state_ansatz.py:113-131).  A drawn channel gate comes out as ``Kraus1q`` with all its
+        matrices; one with a forced branch b (``Project``, ``PostSelect``, a replay) as ``Project`` with the one matrix K_b, which
+        gives the same state and ``logw`` when read back (its recorded branch is then 0, the only one ``Project`` has)."""
+        chan = check_channel_gates(self.op, self.q0, self.n_qubits, self.channel, self.branch, self.kraus, self.n_kraus)
+        mat, mats = check_matrix_gates(self.op, self.mat, self.mats, with_channels=chan is not None)
         out = []
         for i, (o, q, a) in enumerate(zip(self.op.tolist(), self.q0.tolist(), self.alpha.tolist())):
             qubits = [q, q + 1] if is_two_qubit(o) else [q]
-            if o in _MATRIX:  # ("Unitary1q", [q], [M2x2]) / ("Unitary2q", [q, q+1], [M4x4])
+            if o == OP_K1:  # drawn: ("Kraus1q", [q], [[K0, ..]]); forced: ("Project", [q], [K_b]), the same state and logw
+                c, b = int(chan[0][i]), int(chan[1][i])
+                if b >= 0:
+                    out.append(("Project", qubits, [chan[2][c, b].copy()]))
+                else:
+                    out.append((_OP_NAMES[o], qubits, [chan[2][c, : int(chan[3][c])].copy()]))
+            elif o in _MATRIX:  # ("Unitary1q", [q], [M2x2]) / ("Unitary2q", [q, q+1], [M4x4])
                 d = 2 if o == OP_M1 else 4
                 out.append((_OP_NAMES[o], qubits, [mats[mat[i], :d, :d].copy()]))
             else:
@@ -176,7 +354,8 @@ class BoundCircuit:
         a, b = int(a), int(b)
         if not 0 <= a <= b <= self.n_gates:
             raise ValueError(f"sliced({a}, {b}): want 0 <= a <= b <= {self.n_gates} gates")
-        return BoundCircuit(self.n_qubits, self.op[a:b], self.q0[a:b], self.alpha[a:b], None if self.mat is None else self.mat[a:b], self.mats)
+        cut = lambda v: None if v is None else v[a:b]  # noqa: E731
+        return BoundCircuit(self.n_qubits, self.op[a:b], self.q0[a:b], self.alpha[a:b], cut(self.mat), self.mats, cut(self.channel), cut(self.branch), self.kraus, self.n_kraus)
 
     @classmethod
     def from_gates(cls, n_qubits, gates, named_constants: bool = False) -> "BoundCircuit":
@@ -199,14 +378,20 @@ class BoundCircuit:
         points of one gate-list ansatz share ``op``, ``q0`` and ``mat`` and differ in ``alpha`` and ``mats``.  ``ValueError`` for a
         matrix of the wrong shape or one that is not unitary to UNITARY_TOL."""
         n = int(n_qubits)
-        op, q0, alpha, mat = [], [], [], []
-        table = _MatTable()
+        op, q0, alpha, mat, channel, branch = [], [], [], [], [], []
+        table, chans = _MatTable(), _ChannelTable()
         for pos, g in enumerate(gates):
             name, qubits, params = g
             code = _gate_code(name, named_constants)
             qubits = [int(q) for q in qubits]
             if _arity(code) != len(qubits):
                 raise ValueError(f"{name} acts on {_arity(code)} qubit(s), got {qubits}")
+            if code == OP_K1:
+                if not 0 <= qubits[0] < n:
+                    raise ValueError(f"gate on qubits {qubits} outside a register of {n}")
+                slot, forced = chans.slot(name, params, f"gate {pos}")
+                op.append(OP_K1), q0.append(qubits[0]), alpha.append(0.0), mat.append(-1), channel.append(slot), branch.append(forced)
+                continue
             if code in _MATRIX:
                 if name in _NAMED:
                     if params is not None and np.size(params) != 0:
@@ -214,7 +399,7 @@ class BoundCircuit:
                     params = None
                 slot = table.slot(name, qubits, params, f"gate {pos}")
                 for o, q, k in _route(code, qubits, n):
-                    op.append(o), q0.append(q), alpha.append(0.0), mat.append(slot if k else -1)
+                    op.append(o), q0.append(q), alpha.append(0.0), mat.append(slot if k else -1), channel.append(-1), branch.append(-1)
                 continue
             if params is None:
                 params = []
@@ -224,11 +409,12 @@ class BoundCircuit:
                 raise ValueError(f"{name}: expected {1 if code in _PARAMETRISED else 0} parameter(s), got {list(params)}")
             a = float(params[0]) if params else 0.0
             for o, q, k in _route(code, qubits, n):
-                op.append(o), q0.append(q), alpha.append(a if k else 0.0), mat.append(-1)
+                op.append(o), q0.append(q), alpha.append(a if k else 0.0), mat.append(-1), channel.append(-1), branch.append(-1)
         core = (n, np.asarray(op, dtype=np.int8), np.asarray(q0, dtype=np.int32), np.asarray(alpha, dtype=np.float64))
-        if not table.entries:
-            return cls(*core)
-        return cls(*core, np.asarray(mat, dtype=np.int32), table.array())
+        mt = (np.asarray(mat, dtype=np.int32), table.array()) if table.entries else (None, None)
+        if not chans.entries:
+            return cls(*core) if not table.entries else cls(*core, *mt)
+        return cls(*core, *mt, np.asarray(channel, dtype=np.int32), np.asarray(branch, dtype=np.int32), *chans.arrays())
 
 
 def check_checkpoints(checkpoints, n_gates) -> list:
@@ -266,6 +452,8 @@ def _arity(o) -> int:
 
 
 def _gate_code(name, named_constants: bool = True) -> int:
+    if isinstance(name, str) and name in _CHANNEL_NAMES:
+        return OP_K1
     if isinstance(name, str) and name in _NAMED:
         if not named_constants:
             also = f"from_gates(..., named_constants=True) also takes {', '.join(_NAMED)}"
@@ -426,11 +614,12 @@ class CircuitProgram:
     """The compiled (unbound) gate program of a ``CircuitAnsatz``: per routed gate an op code, a pair / qubit and the
     angle form alpha = s (c_a + d_a x[a]) (c_b + d_b x[b]) (s = 0 for H and SWAP; c = 1, d = 0 for an absent factor)."""
 
-    def __init__(self, n_qubits, op, q0, s, fa, ca, da, fb, cb, db, mat=None, mats=None):
+    def __init__(self, n_qubits, op, q0, s, fa, ca, da, fb, cb, db, mat=None, mats=None, channel=None, branch=None, kraus=None, n_kraus=None):
         self.n_qubits = int(n_qubits)
         self.op, self.q0 = op, q0
         self.s, self.fa, self.ca, self.da, self.fb, self.cb, self.db = s, fa, ca, da, fb, cb, db
         self.mat, self.mats = mat, mats  # constant matrix gates: the table is the same array for every data point
+        self.channel, self.branch, self.kraus, self.n_kraus = channel, branch, kraus, n_kraus  # channels are constants of the ansatz too
 
     @property
     def n_gates(self) -> int:
@@ -438,7 +627,7 @@ class CircuitProgram:
 
     def bind(self, x: np.ndarray) -> BoundCircuit:
         alpha = self.s * (self.ca + self.da * x[self.fa]) * (self.cb + self.db * x[self.fb])
-        return BoundCircuit(self.n_qubits, self.op, self.q0, alpha, self.mat, self.mats)
+        return BoundCircuit(self.n_qubits, self.op, self.q0, alpha, self.mat, self.mats, self.channel, self.branch, self.kraus, self.n_kraus)
 
 
 def _factor(spec, n_features):
@@ -473,14 +662,18 @@ class CircuitAnsatz:
         self.feature_symbol_list = [f"f_{i}" for i in range(nf)]
         cols = {k: [] for k in ("op", "q0", "s", "fa", "ca", "da", "fb", "cb", "db")}
         mat, table = [], _MatTable()
+        channel, branch, chans = [], [], _ChannelTable()
         for pos, (name, qubits, angle) in enumerate(gates):
             code = _gate_code(name)
             qubits = [int(q) for q in (qubits if np.ndim(qubits) else [qubits])]
             if _arity(code) != len(qubits):
                 raise ValueError(f"{name} acts on {_arity(code)} qubit(s), got {qubits}")
             one = (0, 1.0, 0.0)
-            slot = -1
-            if code in _MATRIX:
+            slot, cslot, forced = -1, -1, -1
+            if code == OP_K1:  # the channel's parameters stand in the place of the angle: constants of the ansatz
+                cslot, forced = chans.slot(name, angle, f"gate {pos}")
+                s, fa, fb = 0.0, one, one
+            elif code in _MATRIX:
                 if name in _NAMED and angle is not None:
                     raise ValueError(f"{name} takes no angle, got {angle!r}")
                 slot = table.slot(name, qubits, angle, f"gate {pos}")
@@ -503,10 +696,14 @@ class CircuitAnsatz:
                 for k, v in zip(cols, row):
                     cols[k].append(v)
                 mat.append(slot if is_gate else -1)
+                channel.append(cslot if is_gate else -1), branch.append(forced if is_gate else -1)
         dt = {"op": np.int8, "q0": np.int32, "fa": np.int32, "fb": np.int32}
         arr = {k: np.asarray(v, dtype=dt.get(k, np.float64)) for k, v in cols.items()}
         if table.entries:
             arr["mat"], arr["mats"] = np.asarray(mat, dtype=np.int32), table.array()
+        if chans.entries:
+            arr["channel"], arr["branch"] = np.asarray(channel, dtype=np.int32), np.asarray(branch, dtype=np.int32)
+            arr["kraus"], arr["n_kraus"] = chans.arrays()
         self.ansatz_circ = CircuitProgram(n, **arr)
 
     def layer_ends(self) -> list:

@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from .ansatz import as_bound_circuit
+from .ansatz import as_bound_circuit, reject_channels
 from .mps import MPS, simulate
 
 _G = {}
@@ -34,7 +34,9 @@ def _init(ansatz, fidelity, max_bond=None):
 def _one(x):
     t0 = time.perf_counter()
     ansatz = _G["ansatz"]
-    m = simulate(as_bound_circuit(ansatz.circuit_for_data(x), ansatz), _G["fid"], max_bond=_G.get("chi"))
+    circuit = as_bound_circuit(ansatz.circuit_for_data(x), ansatz)
+    reject_channels([circuit], "build_states")
+    m = simulate(circuit, _G["fid"], max_bond=_G.get("chi"))
     return m.tensors, m.fidelity, time.perf_counter() - t0
 
 

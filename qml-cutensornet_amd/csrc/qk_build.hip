@@ -19,6 +19,7 @@
 // beyond bond ~64 (a block Jacobi on the matrix cores is the missing piece); build_kernel_matrix uses it only where no
 // state can outgrow its bond cap (QK_BUILDER=auto).
 #include "qk_host.h"
+#include "qk_local_plan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -35,11 +36,30 @@ typedef double cd __attribute__((ext_vector_type(2)));  // complex128 as (re, im
 constexpr int MAX_SWEEPS = 40;
 
 // ansatz.py.  Codes 8 and 9 are the matrix gates: valid only in a program that comes with a matrix table (N_OPS_MAT codes then).
-enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10 };
+// Code 10 is the one-qubit Kraus channel: valid only in a program that comes with a channel table.
+enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10, OP_K1 = 10 };
 
 __host__ __device__ inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ || o == OP_M2; }
 
-enum { ERR_BOND = 1, ERR_HEAP = 2, ERR_SWEEPS = 4, ERR_GATE = 8, ERR_OP = 16, ERR_NORM0 = 32 };
+enum { ERR_BOND = 1, ERR_HEAP = 2, ERR_SWEEPS = 4, ERR_GATE = 8, ERR_OP = 16, ERR_NORM0 = 32, ERR_CHANNEL = 64 };
+
+// What the channel step (op code 10) reads and writes: one instance in device memory behind BuildArgs::chan, so that a program
+// without channels pays one pointer.
+struct ChanArgs {
+  const cd* kraus;          // [n_channels][4][2][2] the channel table
+  const int32_t* n_kraus;   // [n_channels] matrices of each channel (validated by the host: 1..4)
+  const int32_t* channel;   // [n_ops] channel of a channel gate (validated: inside the table where op is 10)
+  const int32_t* branch;    // [branch_stride ? n_states : 1][n_ops] -1: the branch is drawn, k: branch k is forced
+  const int32_t* kgate;     // [n_ops] how many channel gates precede gate i: the column of its branch in branch_out
+  int branch_stride;        // 0 (one row for all states) or n_ops
+  int n_kgates;             // channel gates of the program
+  unsigned seed_lo, seed_hi, first_gate;  // the Philox key; the position of gate 0 in the uninterrupted program
+  const uint32_t* state_index;  // [n_states] the names of the trajectories: Philox counter (first_gate + i, trajectory, state_index, 2)
+  const uint32_t* trajectory;   // [n_states]
+  int8_t* branch_out;       // [n_states][n_kgates] the branch taken (-1 where the state's program stopped early)
+  double* logw_out;         // [n_ckpt][n_states] sum of log(p_b / N) so far
+  const double* init_logw;  // [n_states] of the initial snapshot (read when init_heap is set)
+};
 
 struct BuildArgs {
   int n_states, n_qubits, n_ops, cap;
@@ -75,6 +95,7 @@ struct BuildArgs {
   int partial;    // a state that outgrows cap is dropped (fidelity -1) instead of failing the call
   int truncate;   // bonds are cut at cap (the chi of pytket-cutensornet's Config) instead
   const int32_t* order;  // queue position -> state index: states expected to be expensive first
+  const ChanArgs* chan;  // the channel table of op code 10 and the trajectories' names (null: the program holds no channel gate, the code is unknown)
 };
 
 
@@ -84,7 +105,11 @@ struct WgShared {
   double frac, nrm;
   unsigned long long off;
   unsigned long long worst;  // bits of the largest squared relative inner product rotated in the current sweep
+  double logw;               // the log-weight of the trajectory so far (channels, op code 10)
+  double pad16;              // the struct stays a multiple of 16 bytes: the dynamic LDS behind it holds complex numbers read 16 bytes at a time, and
+                             // 8 bytes more of static LDS cost the builder 5 % (bonds <= 32) to 47 % (cfg4) until this field restored the alignment
 };
+static_assert(sizeof(WgShared) % 16 == 0, "WgShared must keep the dynamic LDS 16-byte aligned");
 
 
 // Built states -> the Gram engine's set image: site (s, k) of the heap ([l][2][r] complex, interleaved) becomes two planes
@@ -561,6 +586,10 @@ struct qk_built {
   std::vector<double> all_fidelity;
   std::vector<int64_t> all_offsets;
   std::vector<int32_t> all_centre;
+  std::vector<double> all_logw;      // the log-weight of the trajectory so far (0 for a program without channels)
+  int n_kgates = 0;                  // channel gates (op code 10) of the program
+  bool noisy = false;                // built with a channel table, or resumed from such a build: pins the launch shape
+  std::vector<int8_t> branches;      // [n_states][n_kgates] the branch every channel gate took (-1: the state stopped before it)
   std::vector<int32_t> dims;  // the last snapshot, the finished states: what qk_built_info and qk_mps_set_from_built read
   std::vector<double> fidelity;
   std::vector<double> secs;  // workgroup time per state
@@ -577,24 +606,38 @@ struct MatTable {  // the matrix table of op codes 8 and 9 as the caller gave it
   const int32_t* mat = nullptr;
 };
 
+struct ChanTable {  // the channel table of op code 10 and the names of the trajectories as the caller gave them (n_channels = 0: none)
+  int32_t n_channels = 0;
+  const double* kraus = nullptr;     // [n_channels][4][2][2][2]
+  const int32_t* n_kraus = nullptr;  // [n_channels]
+  const int32_t* channel = nullptr;  // [n_ops]
+  const int32_t* branch = nullptr;   // [stride ? n_states : 1][n_ops]
+  int32_t stride = 0;
+  uint64_t seed = 0;
+  const uint32_t* state_index = nullptr;  // [n_states], null: 0 .. n_states-1
+  const uint32_t* trajectory = nullptr;   // [n_states], null: all 0
+  uint32_t first_gate = 0;
+};
+
 static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, const MatTable& tab, qk_built** out);
+                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, const MatTable& tab,
+                      const ChanTable& cht, qk_built** out);
 // the body of qk_build_mps_scan and qk_build_mps_gates; `what` is the entry point the caller came through, for its error messages
 static int build_gates(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
                        double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
-                       int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, qk_built** out);
+                       int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, const ChanTable& cht, qk_built** out);
 
 extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
                             const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, qk_built** out) {
   const int32_t last = n_ops;  // the one-checkpoint scan: a snapshot after the whole program
-  return build_impl("qk_build_mps", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, 1, &last, nullptr, 0, MatTable{}, out);
+  return build_impl("qk_build_mps", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, 1, &last, nullptr, 0, MatTable{}, ChanTable{}, out);
 }
 
 extern "C" int qk_build_mps_scan(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
                                  double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
                                  int32_t initial_snapshot, qk_built** out) {
   return build_gates("qk_build_mps_scan", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
-                     0, nullptr, 0, nullptr, out);
+                     0, nullptr, 0, nullptr, ChanTable{}, out);
 }
 
 // The matrix table of a program, checked before anything runs: every matrix gate's index inside 0..n_mats-1 and, in each of the
@@ -632,12 +675,68 @@ extern "C" int qk_build_mps_gates(qk_ctx* c, int32_t n_states, int32_t n_qubits,
                                   double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
                                   int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, qk_built** out) {
   return build_gates("qk_build_mps_gates", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
-                     n_mats, mats, mats_state_stride, mat, out);
+                     n_mats, mats, mats_state_stride, mat, ChanTable{}, out);
+}
+
+// The channel gates of a program, checked before anything runs (in each of the `rows` branch rows): the channel inside the table,
+// 1..4 matrices, finite entries, the branch inside -1..m-1, a drawn channel trace preserving, max |sum_k K_k^H K_k - 1| <= 1e-12 (a
+// forced branch may be any finite matrix), the qubit inside the register.
+static int check_chan_table(const char* what, int n_qubits, int n_ops, const int8_t* op, const int32_t* q0, int rows, const ChanTable& t) {
+  for (int i = 0; i < n_ops; ++i) {
+    if (op[i] != OP_K1) continue;
+    const int ch = t.channel[i];
+    if (ch < 0 || ch >= t.n_channels) return qk_fail(QK_EINVAL, "%s: gate %d: channel index %d outside 0..%d", what, i, ch, (int)t.n_channels - 1);
+    const int m = t.n_kraus[ch];
+    if (m < 1 || m > 4) return qk_fail(QK_EINVAL, "%s: gate %d: channel %d has %d Kraus matrices (1..4)", what, i, ch, m);
+    const double* K = t.kraus + (size_t)ch * 32;  // [4][2][2][2]
+    for (int e = 0; e < 8 * m; ++e)
+      if (!std::isfinite(K[e])) return qk_fail(QK_EINVAL, "%s: gate %d: a Kraus matrix of channel %d has an entry that is not finite", what, i, ch);
+    bool drawn = false;
+    for (int s = 0; s < rows; ++s) {
+      const int b = t.branch[(size_t)s * n_ops + i];
+      if (b < -1 || b >= m) return qk_fail(QK_EINVAL, "%s: gate %d: branch %d (row %d) outside -1..%d", what, i, b, s, m - 1);
+      drawn = drawn || b < 0;
+    }
+    if (drawn) {
+      double dev = 0;
+      for (int a = 0; a < 2; ++a)
+        for (int d = 0; d < 2; ++d) {
+          double gr = (a == d) ? -1.0 : 0.0, gi = 0.0;  // (sum_k K_k^H K_k - 1)[a][d] = sum_{k,r} conj(K_k[r][a]) K_k[r][d] - delta
+          for (int k = 0; k < m; ++k)
+            for (int r = 0; r < 2; ++r) {
+              const double xr = K[((k * 2 + r) * 2 + a) * 2], xi = K[((k * 2 + r) * 2 + a) * 2 + 1], yr = K[((k * 2 + r) * 2 + d) * 2], yi = K[((k * 2 + r) * 2 + d) * 2 + 1];
+              gr += xr * yr + xi * yi, gi += xr * yi - xi * yr;
+            }
+          dev = std::max(dev, std::hypot(gr, gi));
+        }
+      if (!(dev <= 1e-12)) return qk_fail(QK_EINVAL, "%s: gate %d: the drawn channel %d is not trace preserving: max |sum K^H K - 1| = %.3e > 1e-12", what, i, ch, dev);
+    }
+    if (q0[i] < 0 || q0[i] >= n_qubits) return qk_fail(QK_EINVAL, "%s: gate %d: channel on a qubit outside the register", what, i);
+  }
+  return QK_OK;
+}
+
+extern "C" int qk_build_mps_channels(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                                     double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                                     int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
+                                     const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
+                                     const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, qk_built** out) {
+  static const char* what = "qk_build_mps_channels";
+  ChanTable t;
+  if (n_channels < 0 || (n_channels > 0 && (!kraus || !n_kraus || !channel || !branch))) return qk_fail(QK_EINVAL, "%s: a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch", what);
+  if (n_channels > 0 && branch_state_stride != 0 && branch_state_stride != n_ops)
+    return qk_fail(QK_EINVAL, "%s: branch_state_stride must be 0 (one row for all states) or n_ops = %d, got %d", what, (int)n_ops, (int)branch_state_stride);
+  if (n_channels > 0) {
+    t.n_channels = n_channels, t.kraus = kraus, t.n_kraus = n_kraus, t.channel = channel, t.branch = branch, t.stride = branch_state_stride;
+    t.seed = seed, t.state_index = state_index, t.trajectory = trajectory, t.first_gate = first_gate;
+  }
+  return build_gates(n_channels > 0 ? what : "qk_build_mps_gates", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial,
+                     initial_snapshot, n_mats, mats, mats_state_stride, mat, t, out);
 }
 
 static int build_gates(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
                        double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
-                       int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, qk_built** out) {
+                       int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, const ChanTable& cht, qk_built** out) {
   MatTable tab;
   if (n_mats < 0 || (n_mats > 0 && (!mats || !mat))) return qk_fail(QK_EINVAL, "%s: a matrix table needs n_mats >= 0, mats and mat", what);
   if (n_mats > 0 && mats_state_stride != 0 && mats_state_stride != n_mats)
@@ -650,17 +749,20 @@ static int build_gates(const char* what, qk_ctx* c, int32_t n_states, int32_t n_
   if (checkpoints[n_checkpoints - 1] != n_ops) return qk_fail(QK_EINVAL, "%s: the last checkpoint must be the whole program (%d gates), got %d", what, n_ops, (int)checkpoints[n_checkpoints - 1]);
   if ((flags & QK_BUILD_PARTIAL) && (n_checkpoints > 1 || initial))
     return qk_fail(QK_EINVAL, "%s: QK_BUILD_PARTIAL goes with one checkpoint and no initial snapshot (a dropped state has no snapshots)", what);
-  return build_impl(what, c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot, tab, out);
+  return build_impl(what, c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot, tab, cht, out);
 }
 
 static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, const MatTable& tab, qk_built** out) {
+                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, const MatTable& tab,
+                      const ChanTable& cht, qk_built** out) {
   if (!c || !op || !q0 || !alpha || !out) return qk_fail(QK_EINVAL, "%s: null argument", what);
   if (n_states <= 0 || n_qubits <= 0 || n_ops < 0) return qk_fail(QK_EINVAL, "%s: empty problem (%d states, %d qubits, %d gates)", what, n_states, n_qubits, n_ops);
   if (max_bond < 2 || max_bond > 1024) return qk_fail(QK_EINVAL, "%s: max_bond %d outside 2..1024", what, max_bond);
   const int n_codes = tab.n_mats > 0 ? N_OPS_MAT : N_OPS;  // without a table codes 8 and 9 are unknown
+  const bool with_chan = cht.n_channels > 0;  // without a channel table code 10 is unknown
   for (int i = 0; i < n_ops; ++i)
-    if (op[i] < 0 || op[i] >= n_codes) return qk_fail(QK_EINVAL, "%s: unknown gate op code %d at position %d (valid: 0..%d)", what, (int)op[i], i, n_codes - 1);
+    if ((op[i] < 0 || op[i] >= n_codes) && !(with_chan && op[i] == OP_K1))
+      return qk_fail(QK_EINVAL, "%s: unknown gate op code %d at position %d (valid: 0..%d%s)", what, (int)op[i], i, n_codes - 1, with_chan ? ", 10" : "");
   for (int i = 0; i < n_ops; ++i)  // (the kernel checks this too; a matrix gate past the last pair is refused before anything runs)
     if ((op[i] == OP_M1 || op[i] == OP_M2) && (q0[i] < 0 || q0[i] + (op[i] == OP_M2 ? 1 : 0) >= n_qubits))
       return qk_fail(QK_EINVAL, "%s: gate %d on a qubit outside the register", what, i);
@@ -668,6 +770,16 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   if (n_tables) {
     const int rc = check_mat_table(what, n_ops, op, n_tables, tab);
     if (rc != QK_OK) return rc;
+  }
+  std::vector<int32_t> kgate((size_t)std::max(1, n_ops), 0);  // channel gates before gate i
+  int n_kgates = 0;
+  if (with_chan) {
+    const int rc = check_chan_table(what, n_qubits, n_ops, op, q0, cht.stride ? n_states : 1, cht);
+    if (rc != QK_OK) return rc;
+    for (int i = 0; i < n_ops; ++i) {
+      kgate[i] = n_kgates;
+      n_kgates += (op[i] == OP_K1);
+    }
   }
   if (init) {  // a resumed build starts from snapshot init_j of `init`, which is only read
     if (init->ctx != c) return qk_fail(QK_EINVAL, "%s: the initial snapshot was built in another context", what);
@@ -699,16 +811,27 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   // a share with a workgroup slot per state even in the 512-thread shape (<= one state per CU) ends with its slowest state either
   // way, and a state is built faster by 512 threads with the whole CU's LDS: 96 states of 100 qubits x 10 layers cut at bond 64,
   // 60.7 s in the 256-thread shape, 46.8 s in this one (profiles/r03/builder_capped_cfg5_gamma0.5_chi64.txt)
-  if (wgs_variant == 2 && n_states <= c->num_cus) wgs_variant = 1;
+  // -- but not for a program of trajectories (a channel table, or a snapshot of such a build): the two shapes add the channel
+  // step's sums and run the factorisations in different orders, and a trajectory's bits must not depend on how many states
+  // share its launch (alone, in a set, in one rank's share of many).  Its shape follows from max_bond alone.
+  const bool noisy = with_chan || (init && init->noisy);
+  if (wgs_variant == 2 && n_states <= c->num_cus && !noisy) wgs_variant = 1;
   if (const char* v = std::getenv("QK_BUILD_WGS")) wgs_variant = (std::atoi(v) >= 4) ? 4 : (std::atoi(v) <= 1 ? 1 : 2);
   const int bt = wgs_variant == 1 ? 512 : 256;
   size_t lds_total = (wgs_variant == 4 ? 38 : wgs_variant == 2 ? 76 : 152) * 1024;
   if (const char* v = std::getenv("QK_BUILD_LDS_KB")) lds_total = (size_t)std::max(32, std::min(wgs_variant == 4 ? 38 : 156, std::atoi(v))) * 1024;
   const int jl_elems = (int)((lds_total - lds_meta) / sizeof(cd));
+  if (n_kgates > 0 && jl_elems < 16 + (5 * bt + 6) / 2)  // wg_channel: the staged matrices and five partial sums per thread
+    return qk_fail(QK_EINVAL, "%s: the channel step needs %d complex numbers of LDS working set, this shape leaves %d", what, 16 + (5 * bt + 6) / 2, jl_elems);
   const size_t lds = lds_total;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb256::qk_build_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb256::qk_build_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 38 * 1024));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb512::qk_build_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb256::qk_build_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb256::qk_build_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 38 * 1024));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb512::qk_build_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+  if (n_kgates > 0) {  // the instantiations with the channel step: a program without channel gates never launches them
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb256::qk_build_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb256::qk_build_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 38 * 1024));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb512::qk_build_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+  }
   const int wgs_per_cu = std::min(wgs_variant, (int)((160 * 1024) / (lds_total + 1024)));  // + the static LDS of the kernel
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
@@ -732,6 +855,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   HIP_TRY_AS(what, c->build_work.ensure((size_t)grid * (4 * wslot + wtab) * sizeof(cd)));
   QkDevBuf heap, d_op, d_q0, d_alpha, d_fid, d_secs, d_dims, d_offs, d_ctr, d_err, d_order;  // d_ctr: [0] state counter, [1] heap top
   QkDevBuf d_ckpt, d_centre, d_ioffs, d_idims, d_ifid, d_icentre, d_mats, d_mat;
+  QkDevBuf d_logw, d_ilogw, d_kraus, d_nkraus, d_channel, d_branch, d_kgate, d_sidx, d_traj, d_bout, d_chan;
   const size_t n_rec = (size_t)n_ckpt * n_states;  // (snapshot, state) records
   HIP_TRY_AS(what, heap.alloc(heap_cap * sizeof(cd)));
   HIP_TRY_AS(what, d_op.alloc(std::max(1, n_ops)));
@@ -755,6 +879,41 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
     HIP_TRY_AS(what, hipMemcpy(d_idims.get(), init->all_dims.data() + r0 * (n_qubits + 1), (size_t)n_states * (n_qubits + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
     HIP_TRY_AS(what, hipMemcpy(d_ifid.get(), init->all_fidelity.data() + r0, (size_t)n_states * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY_AS(what, hipMemcpy(d_icentre.get(), init->all_centre.data() + r0, (size_t)n_states * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (n_kgates > 0) {
+      HIP_TRY_AS(what, d_ilogw.alloc((size_t)n_states * sizeof(double)));
+      HIP_TRY_AS(what, hipMemcpy(d_ilogw.get(), init->all_logw.data() + r0, (size_t)n_states * sizeof(double), hipMemcpyHostToDevice));
+    }
+  }
+  if (n_kgates > 0) {  // the channel table, the branch rows and the names of the trajectories
+    const size_t rows = cht.stride ? (size_t)n_states : 1;
+    std::vector<uint32_t> sidx(n_states), traj(n_states, 0u);
+    for (int s = 0; s < n_states; ++s) sidx[s] = cht.state_index ? cht.state_index[s] : (uint32_t)s;
+    if (cht.trajectory) traj.assign(cht.trajectory, cht.trajectory + n_states);
+    HIP_TRY_AS(what, d_kraus.alloc((size_t)cht.n_channels * 16 * sizeof(cd)));
+    HIP_TRY_AS(what, d_nkraus.alloc((size_t)cht.n_channels * sizeof(int32_t)));
+    HIP_TRY_AS(what, d_channel.alloc((size_t)n_ops * sizeof(int32_t)));
+    HIP_TRY_AS(what, d_branch.alloc(rows * n_ops * sizeof(int32_t)));
+    HIP_TRY_AS(what, d_kgate.alloc((size_t)n_ops * sizeof(int32_t)));
+    HIP_TRY_AS(what, d_sidx.alloc((size_t)n_states * sizeof(uint32_t)));
+    HIP_TRY_AS(what, d_traj.alloc((size_t)n_states * sizeof(uint32_t)));
+    HIP_TRY_AS(what, d_bout.alloc((size_t)n_states * n_kgates));
+    HIP_TRY_AS(what, hipMemcpy(d_kraus.get(), cht.kraus, (size_t)cht.n_channels * 16 * sizeof(cd), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_nkraus.get(), cht.n_kraus, (size_t)cht.n_channels * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_channel.get(), cht.channel, (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_branch.get(), cht.branch, rows * n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_kgate.get(), kgate.data(), (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_sidx.get(), sidx.data(), (size_t)n_states * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_traj.get(), traj.data(), (size_t)n_states * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemset(d_bout.get(), 0xFF, (size_t)n_states * n_kgates));  // -1: not reached
+    HIP_TRY_AS(what, d_logw.alloc(n_rec * sizeof(double)));
+    ChanArgs ca;
+    ca.kraus = d_kraus.get<cd>(), ca.n_kraus = d_nkraus.get<int32_t>(), ca.channel = d_channel.get<int32_t>(), ca.branch = d_branch.get<int32_t>();
+    ca.kgate = d_kgate.get<int32_t>(), ca.branch_stride = cht.stride ? n_ops : 0, ca.n_kgates = n_kgates;
+    ca.seed_lo = (unsigned)cht.seed, ca.seed_hi = (unsigned)(cht.seed >> 32), ca.first_gate = cht.first_gate;
+    ca.state_index = d_sidx.get<uint32_t>(), ca.trajectory = d_traj.get<uint32_t>(), ca.branch_out = d_bout.get<int8_t>();
+    ca.logw_out = d_logw.get<double>(), ca.init_logw = d_ilogw.get<double>();
+    HIP_TRY_AS(what, d_chan.alloc(sizeof(ChanArgs)));
+    HIP_TRY_AS(what, hipMemcpy(d_chan.get(), &ca, sizeof(ChanArgs), hipMemcpyHostToDevice));
   }
   if (n_tables) {
     const size_t mats_bytes = (size_t)n_tables * tab.n_mats * 16 * sizeof(cd);
@@ -795,6 +954,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   a.n_states = n_states, a.n_qubits = n_qubits, a.n_ops = n_ops, a.cap = cap;
   a.op = d_op.get<int8_t>(), a.q0 = d_q0.get<int32_t>(), a.alpha = d_alpha.get<double>();
   a.mats = n_tables ? d_mats.get<cd>() : nullptr, a.mat = n_tables ? d_mat.get<int32_t>() : nullptr, a.mats_stride = n_tables > 1 ? tab.n_mats : 0;
+  a.chan = n_kgates ? d_chan.get<ChanArgs>() : nullptr;
   a.budget = trunc_budget, a.zero = value_of_zero;
   a.arena = c->build_arena.get<cd>(), a.work = c->build_work.get<cd>(), a.heap = heap.get<cd>(), a.heap_cap = heap_cap;
   a.counter = d_ctr.get<unsigned long long>(), a.heap_top = a.counter + 1;
@@ -808,9 +968,13 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   a.block = 1;
   if (const char* v = std::getenv("QK_BUILD_BLOCK")) a.block = std::atoi(v) != 0;
   HIP_TRY_AS(what, hipEventRecord(c->ev0, c->stream));
-  if (wgs_variant == 4) qkb256::qk_build_kernel<4><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
-  else if (wgs_variant == 2) qkb256::qk_build_kernel<2><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
-  else qkb512::qk_build_kernel<1><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
+  if (n_kgates > 0) {
+    if (wgs_variant == 4) qkb256::qk_build_kernel<4, true><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
+    else if (wgs_variant == 2) qkb256::qk_build_kernel<2, true><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
+    else qkb512::qk_build_kernel<1, true><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
+  } else if (wgs_variant == 4) qkb256::qk_build_kernel<4, false><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
+  else if (wgs_variant == 2) qkb256::qk_build_kernel<2, false><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
+  else qkb512::qk_build_kernel<1, false><<<dim3((unsigned)grid), dim3(bt), lds, c->stream>>>(a);
   HIP_TRY_AS(what, hipGetLastError());
   HIP_TRY_AS(what, hipEventRecord(c->ev1, c->stream));
   std::unique_ptr<qk_built> b(new (std::nothrow) qk_built);
@@ -821,6 +985,12 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   b->all_fidelity.resize(n_rec);
   b->all_offsets.resize(n_rec);
   b->all_centre.resize(n_rec);
+  b->all_logw.assign(n_rec, 0.0);
+  if (init && n_kgates == 0)  // a resumed tail without channel gates: every record keeps the log-weight of the snapshot
+    for (size_t r = 0; r < n_rec; ++r) b->all_logw[r] = init->all_logw[(size_t)init_j * n_states + r % n_states];
+  b->n_kgates = n_kgates;
+  b->noisy = noisy;
+  b->branches.assign((size_t)n_states * n_kgates, (int8_t)-1);
   std::vector<long long> offs(n_rec);
   int errv[32] = {0};
   unsigned long long ctr[2] = {0, 0};
@@ -828,6 +998,8 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   if (e == hipSuccess) e = hipMemcpy(b->all_dims.data(), d_dims.get(), b->all_dims.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(b->all_fidelity.data(), d_fid.get(), n_rec * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(b->all_centre.data(), d_centre.get(), n_rec * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && n_kgates > 0) e = hipMemcpy(b->all_logw.data(), d_logw.get(), n_rec * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && n_kgates > 0) e = hipMemcpy(b->branches.data(), d_bout.get(), b->branches.size(), hipMemcpyDeviceToHost);
   b->secs.resize(n_states);
   if (e == hipSuccess) e = hipMemcpy(b->secs.data(), d_secs.get(), (size_t)n_states * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(offs.data(), d_offs.get(), n_rec * sizeof(long long), hipMemcpyDeviceToHost);
@@ -871,6 +1043,9 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   }
   if (err) {
     if (err & ERR_OP) return qk_fail(QK_EINVAL, "%s: unknown gate op code (valid: 0..%d)", what, n_codes - 1);
+    if (err & ERR_CHANNEL)
+      return qk_fail(QK_EDEVICE, "%s: state %d (state_index %u), gate %u: the branch of the channel has probability 0 or one that is not finite (an impossible outcome was post-selected?)",
+                     what, errv[26] - 1, cht.state_index ? cht.state_index[std::max(0, errv[26] - 1)] : (uint32_t)std::max(0, errv[26] - 1), cht.first_gate + (unsigned)errv[27]);
     if (err & ERR_GATE) return qk_fail(QK_EINVAL, "%s: gate on a qubit outside the register", what);
     if (err & ERR_BOND) return qk_fail(QK_EINVAL, "%s: a bond grew beyond max_bond = %d", what, cap);
     if (err & ERR_HEAP) return qk_fail(QK_EDEVICE, "%s: the packed states (%d snapshots each) need %llu complex numbers, the heap holds %zu", what, n_ckpt, ctr[1], heap_cap);
@@ -940,6 +1115,22 @@ extern "C" int qk_built_info_at(const qk_built* b, int32_t j, int32_t* dims, dou
     for (int s = 0; s < b->n_states; ++s) t += state_elems(b, j, s);
     *total_complex = t;
   }
+  return QK_OK;
+}
+
+extern "C" int qk_built_logw_at(const qk_built* b, int32_t j, double* logw) {
+  if (const int rc = snapshot_index(b, j, "qk_built_logw_at")) return rc;
+  if (!logw) return qk_fail(QK_EINVAL, "qk_built_logw_at: null argument");
+  std::copy(b->all_logw.begin() + (size_t)j * b->n_states, b->all_logw.begin() + (size_t)(j + 1) * b->n_states, logw);
+  return QK_OK;
+}
+
+extern "C" int qk_built_num_channel_gates(const qk_built* b) { return b ? b->n_kgates : 0; }
+
+extern "C" int qk_built_branches(const qk_built* b, int8_t* branches) {
+  if (!b) return qk_fail(QK_EINVAL, "qk_built_branches: null handle");
+  if (b->n_kgates > 0 && !branches) return qk_fail(QK_EINVAL, "qk_built_branches: null argument");
+  std::copy(b->branches.begin(), b->branches.end(), branches);
   return QK_OK;
 }
 

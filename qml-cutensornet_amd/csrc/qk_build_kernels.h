@@ -1173,7 +1173,97 @@ __device__ __noinline__ void wg_matrix_2q(cd* TH, const int l, const int r, cons
   __syncthreads();
 }
 
-template <int MINWG>  // resident workgroups per CU the register budget is cut for: 256 threads: 2 (76 KiB of LDS each) or 4 (38 KiB); 512 threads: 1 (152 KiB)
+// ---- Kraus channel (op code 10) on the site t = A_q [l][2][r] that holds the orthogonality centre
+// The channel's matrices K[4][2][2] (slots >= m read as 0) are staged once in `stage` (the Jacobi working set, idle between
+// factorisations; every caller arrives behind a barrier), the per-thread sums behind them.  Every thread adds its strided elements of
+// N = sum |t|^2 and p_k = sum |K_k t|^2 in ascending order; the partials go through LDS and threads 0..4 add one quantity each in
+// ascending thread order: no atomics, so the sums are the same bits from run to run.  Thread 0 picks the branch -- forced, or the
+// first k with p_k > 0 and u tot < p_0 + .. + p_k (none: the last k with p_k > 0) for the Philox uniform of counter (first_gate + i, trajectory,
+// state index, 2) -- and records it and log(p_b / N); then all threads apply K_b / sqrt(p_b) in the fixed order of mat_dot<2>.  sh->flag = 0 when
+// the outcome is impossible (p_b 0 or not finite, tot 0 in a draw): the site is left as it is.  Kept out of line: the gate loop of
+// the kernel is cut to a register budget, and this code must not take part in its allocation -- which is also why everything the
+// step reads sits behind the one pointer `ca` and is fetched here.
+__device__ __noinline__ void wg_channel(cd* t, const int l, const int r, const ChanArgs* ca, const int st, const int i, cd* stage, WgShared* sh) {
+  const int tid = threadIdx.x;
+  const int ch = ca->channel[i];
+  const cd* K = ca->kraus + (long)ch * 16;
+  const int m = ca->n_kraus[ch], forced = ca->branch[(long)st * ca->branch_stride + i];
+  double* part = reinterpret_cast<double*>(stage + 16);  // [5][BT] per-thread partials, then [5] the sums
+  double* red = part + 5 * BT;
+  if (tid < 16) stage[tid] = (tid < 4 * m) ? K[tid] : cd{0.0, 0.0};
+  __syncthreads();
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int e = tid; e < l * r; e += BT) {
+    const int a = e / r, c = e - a * r;
+    const cd v[2] = {t[(a * 2) * r + c], t[(a * 2 + 1) * r + c]};
+    acc[0] += v[0].x * v[0].x + v[0].y * v[0].y + v[1].x * v[1].x + v[1].y * v[1].y;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < m) {
+        const cd y0 = mat_dot<2>(stage + 4 * k, v), y1 = mat_dot<2>(stage + 4 * k + 2, v);
+        acc[1 + k] += y0.x * y0.x + y0.y * y0.y + y1.x * y1.x + y1.y * y1.y;
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < 5; ++j) part[j * BT + tid] = acc[j];
+  __syncthreads();
+  if (tid < 5) {
+    double s = 0.0;
+    for (int j = 0; j < BT; ++j) s += part[tid * BT + j];
+    red[tid] = s;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const double N = red[0];
+    double tot = 0.0;
+    for (int k = 0; k < m; ++k) tot += red[1 + k];
+    int b = forced;
+    bool ok = true;
+    if (forced < 0) {
+      ok = (tot > 0.0) && (tot <= 1.79e308);
+      const qkl::Philox4 x = qkl::smp_philox(ca->first_gate + (unsigned)i, ca->trajectory[st], ca->state_index[st], 2u, ca->seed_lo, ca->seed_hi);
+      const double u = (double)(((uint64_t)(x.x[0] >> 5) << 26) + (uint64_t)(x.x[1] >> 6)) * (1.0 / 9007199254740992.0);
+      double cum = 0.0;
+      int last = 0;
+      for (int k = 0; k < m; ++k) {
+        const double pk = red[1 + k];
+        cum += pk;
+        if (pk > 0.0) {
+          last = k;
+          if (b < 0 && u * tot < cum) b = k;
+        }
+      }
+      if (b < 0) b = last;
+    }
+    const double pb = red[1 + b];
+    ok = ok && (pb > 0.0) && (pb <= 1.79e308);
+    sh->flag = ok ? 1 : 0;
+    sh->keep = b;
+    sh->nrm = sqrt(pb);
+    if (ok) {
+      sh->logw += log(pb / N);
+      ca->branch_out[(long)st * ca->n_kgates + ca->kgate[i]] = (int8_t)b;
+    }
+  }
+  __syncthreads();
+  if (!sh->flag) return;
+  const double s = sh->nrm;
+  const cd* Kb = stage + 4 * sh->keep;
+  const cd m0[2] = {cd{Kb[0].x / s, Kb[0].y / s}, cd{Kb[1].x / s, Kb[1].y / s}}, m1[2] = {cd{Kb[2].x / s, Kb[2].y / s}, cd{Kb[3].x / s, Kb[3].y / s}};
+  for (int e = tid; e < l * r; e += BT) {
+    const int a = e / r, c = e - a * r;
+    const cd v[2] = {t[(a * 2) * r + c], t[(a * 2 + 1) * r + c]};
+    t[(a * 2) * r + c] = mat_dot<2>(m0, v);
+    t[(a * 2 + 1) * r + c] = mat_dot<2>(m1, v);
+  }
+  __syncthreads();
+}
+
+// MINWG: resident workgroups per CU the register budget is cut for: 256 threads: 2 (76 KiB of LDS each) or 4 (38 KiB); 512 threads: 1 (152 KiB).
+// CHAN: the program holds channel gates (op code 10).  A program without them runs the instantiation that has none of their code, so
+// its registers, its spills and its arithmetic are those of the kernel before the channels (the compiler's resource report of the
+// four-workgroup shape is the same line as before; with the step compiled in, the allocation of the whole gate loop changes).
+template <int MINWG, bool CHAN>
 __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) {
   extern __shared__ double sh_raw[];
   const int n = g.n_qubits, cap = g.cap, tid = threadIdx.x;
@@ -1213,6 +1303,9 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
         sites[k * slot + 1] = cd{0.0, 0.0};
       }
     }
+    if constexpr (CHAN) {
+      if (tid == 0) sh.logw = g.init_heap ? g.chan->init_logw[st] : 0.0;  // the log-weight travels with the fidelity
+    }
     __syncthreads();
     const long long st_begin = wall_clock64();
     const double* alpha = g.alpha + (long)st * g.n_ops;
@@ -1223,10 +1316,13 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
         const long rec = (long)ck * g.n_states + st;
         wg_snapshot(g.heap, g.heap_cap, g.heap_top, g.error, g.dims_out + rec * (n + 1), g.fid_out + rec, g.offs_out + rec, g.centre_out + rec, dims, sites, slot, n, fidelity, centre,
                     false, &sh);
+        if constexpr (CHAN) {
+          if (tid == 0) g.chan->logw_out[rec] = sh.logw;
+        }
         ++ck;
       }
       const int o = g.op[i], q = g.q0[i];
-      if (o < 0 || o >= (g.mats ? N_OPS_MAT : N_OPS)) {  // the matrix gates need their table
+      if ((o < 0 || o >= (g.mats ? N_OPS_MAT : N_OPS)) && !(CHAN && o == OP_K1)) {  // the matrix gates and the channels need their tables
         if (tid == 0) atomicOr(g.error, ERR_OP);
         continue;
       }
@@ -1257,7 +1353,7 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
         wg_matrix_1q(sites + q * slot, dims[q], dims[q + 1], g.mats + ((long)st * g.mats_stride + g.mat[i]) * 16, jl);
         continue;
       }
-      if (!is_two_qubit(o)) {  // Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
+      if (!is_two_qubit(o) && !(CHAN && o == OP_K1)) {  // Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
         cd* t = sites + q * slot;
         const int l = dims[q], r = dims[q + 1];
         const double th = 0.5 * M_PI * alpha[i];
@@ -1276,7 +1372,8 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
         __syncthreads();
         continue;
       }
-      // ---- two-qubit gate on (q, q+1): bring the orthogonality centre onto the pair
+      // ---- two-qubit gate on (q, q+1): bring the orthogonality centre onto the pair [q, hi = q+1]; a channel on q: onto the site, hi = q
+      const int hi = (CHAN && o == OP_K1) ? q : q + 1;
       while (centre < q) {  // t = (W/s), next <- (s V^H) next
         cd* t = sites + centre * slot;
         cd* u = sites + (centre + 1) * slot;
@@ -1321,7 +1418,7 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
         __syncthreads();
         ++centre;
       }
-      while (centre > q + 1) {  // t^T = (W/s)(s V^H): t <- (W/s)^T, previous <- previous (s V^H)^T
+      while (centre > hi) {  // t^T = (W/s)(s V^H): t <- (W/s)^T, previous <- previous (s V^H)^T
         cd* t = sites + centre * slot;
         cd* d = sites + (centre - 1) * slot;
         const int l = dims[centre], r = dims[centre + 1], l0 = dims[centre - 1];
@@ -1362,6 +1459,17 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
         if (tid == 0) dims[centre] = k;
         __syncthreads();
         --centre;
+      }
+      if (CHAN && o == OP_K1) {  // the channel step: the centre stays on q, the bonds do not change
+        wg_channel(sites + q * slot, dims[q], dims[q + 1], g.chan, st, i, jl, &sh);
+        if (!sh.flag) {  // an impossible outcome: the program of this state stops here, the call fails naming it
+          if (tid == 0) {
+            atomicOr(g.error, ERR_CHANNEL);
+            if (atomicCAS(g.error + 26, 0, st + 1) == 0) g.error[27] = i;
+          }
+          outgrown = true;
+        }
+        continue;
       }
       cd* a0 = sites + q * slot;
       cd* a1 = sites + (q + 1) * slot;
@@ -1464,6 +1572,9 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
       const long rec = (long)(g.n_ckpt - 1) * g.n_states + st;
       wg_snapshot(g.heap, g.heap_cap, g.heap_top, g.error, g.dims_out + rec * (n + 1), g.fid_out + rec, g.offs_out + rec, g.centre_out + rec, dims, sites, slot, n, fidelity, centre,
                   outgrown, &sh);
+      if constexpr (CHAN) {
+        if (tid == 0) g.chan->logw_out[rec] = sh.logw;
+      }
       if (tid == 0) g.secs_out[st] = (double)(wall_clock64() - st_begin) * 1e-8;
     }
   }

@@ -34,7 +34,8 @@ zungqr_t p_zungqr = nullptr;
 zgemm_t p_zgemm = nullptr;
 
 // ansatz.py.  Codes 8 and 9 are the matrix gates: valid only in a program that comes with a matrix table (N_OPS_MAT codes then).
-enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10 };
+// Code 10 is the one-qubit Kraus channel: valid only in a program that comes with a channel table.
+enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10, OP_K1 = 10 };
 
 inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ || o == OP_M2; }
 
@@ -72,6 +73,63 @@ std::string check_table(int n_ops, const int8_t* op, int n_mats, const cd* mats,
       }
     if (!finite || !(dev <= 1e-12))
       return "gate " + std::to_string(i) + ": the matrix of table entry " + std::to_string(k) + (finite ? " is not unitary (max |M^H M - 1| > 1e-12)" : " has an entry that is not finite");
+  }
+  return "";
+}
+
+// The channel table of a program and the names of one trajectory (qkb_simulate_channels); n_channels = 0: none, code 10 is unknown.
+struct Channels {
+  int n_channels = 0;
+  const cd* kraus = nullptr;        // [n_channels][4][2][2], K[s'][s]
+  const int32_t* n_kraus = nullptr; // [n_channels] 1..4
+  const int32_t* channel = nullptr; // [n_ops], read where op is 10
+  const int32_t* branch = nullptr;  // [n_ops] -1: drawn, k: forced
+  uint64_t seed = 0;
+  uint32_t state_index = 0, trajectory = 0, first_gate = 0;
+  double* logw_out = nullptr;
+  int8_t* branches_out = nullptr;   // [channel gates of the program]
+  double* margin_out = nullptr;
+};
+
+// Philox4x32-10 and the uniform of its first two words, written out as in qk_local_plan.h (smp_philox, smp_uniform) and
+// engine.philox4x32: counter (gate, trajectory, state, 2), key = the two halves of the seed.
+double channel_uniform(uint64_t seed, uint32_t gate, uint32_t trajectory, uint32_t state) {
+  uint32_t c0 = gate, c1 = trajectory, c2 = state, c3 = 2u, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int r = 0; r < 10; ++r) {
+    if (r > 0) k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+    c0 = n0, c1 = n1, c2 = n2, c3 = n3;
+  }
+  return (double)(((uint64_t)(c0 >> 5) << 26) + (uint64_t)(c1 >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+// The channel gates of a program, checked before anything runs: the channel inside the table, 1..4 matrices, finite entries, the
+// branch inside -1..m-1, a drawn channel trace preserving to 1e-12, the qubit inside the register.  Empty string, or what is wrong.
+std::string check_channels(int n_qubits, int n_ops, const int8_t* op, const int32_t* q0, const Channels& ch) {
+  for (int i = 0; i < n_ops; ++i) {
+    if (op[i] != OP_K1) continue;
+    const std::string at = "gate " + std::to_string(i) + ": ";
+    const int c = ch.channel[i], b = ch.branch[i];
+    if (c < 0 || c >= ch.n_channels) return at + "channel index " + std::to_string(c) + " outside 0.." + std::to_string(ch.n_channels - 1);
+    const int m = ch.n_kraus[c];
+    if (m < 1 || m > 4) return at + "channel " + std::to_string(c) + " has " + std::to_string(m) + " Kraus matrices (1..4)";
+    const cd* K = ch.kraus + (size_t)c * 16;
+    for (int e = 0; e < 4 * m; ++e)
+      if (!std::isfinite(K[e].real()) || !std::isfinite(K[e].imag())) return at + "a Kraus matrix of channel " + std::to_string(c) + " has an entry that is not finite";
+    if (b < -1 || b >= m) return at + "branch " + std::to_string(b) + " outside -1.." + std::to_string(m - 1);
+    if (b < 0) {
+      double dev = 0;
+      for (int a = 0; a < 2; ++a)
+        for (int d = 0; d < 2; ++d) {
+          cd g = (a == d) ? cd(-1, 0) : cd(0, 0);
+          for (int k = 0; k < m; ++k)
+            for (int r = 0; r < 2; ++r) g += std::conj(K[k * 4 + r * 2 + a]) * K[k * 4 + r * 2 + d];
+          dev = std::max(dev, std::abs(g));
+        }
+      if (!(dev <= 1e-12)) return at + "the drawn channel " + std::to_string(c) + " is not trace preserving (max |sum K^H K - 1| > 1e-12)";
+    }
+    if (q0[i] < 0 || q0[i] >= n_qubits) return at + "channel on a qubit outside the register";
   }
   return "";
 }
@@ -177,6 +235,9 @@ int qkb_init(const char* openblas_path) {
 int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
                        int32_t max_bond, int32_t n_mats, const double* mats, const int32_t* mat, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out,
                        double* fidelity_out);
+static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
+                         int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, const Channels& ch, int32_t* dims_out, double** tensors_out,
+                         int64_t* n_complex_out, double* fidelity_out);
 int qkb_simulate(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
                  double value_of_zero, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out, double* fidelity_out) {
   return qkb_simulate_gates(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, 0, 0, nullptr, nullptr, dims_out, tensors_out, n_complex_out, fidelity_out);
@@ -195,6 +256,38 @@ int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const in
 int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
                        int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out,
                        double* fidelity_out) {
+  return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, Channels{}, dims_out, tensors_out, n_complex_out, fidelity_out);
+}
+// qkb_simulate_gates with a channel table: with n_channels > 0 the program may also hold op code 10, a one-qubit Kraus channel on q0.
+// Channel c is n_kraus[c] (1..4) matrices kraus[c][k][s'][s] (complex128 [n_channels][4][2][2], (re, im)); gate i reads channel
+// channel[i] and draws its branch (branch[i] = -1) or takes branch[i]; alpha[i] and mat[i] are ignored there.  The step: the centre
+// is brought onto q exactly, N = sum |A_q|^2, p_k = sum |K_k A_q|^2 and tot = p_0 + .. in ascending order of elements and of k; drawn:
+// u = uniform of Philox counter (first_gate + i, trajectory, state_index, 2) and key (seed), b the first k with p_k > 0 and
+// u tot < p_0 + .. + p_k, else the last k with p_k > 0; A_q <- (K_b / sqrt(p_b)) A_q; logw += log(p_b / N).  *logw_out, branches_out
+// [channel gates] and *margin_out (the smallest |u tot - cum| / tot over the thresholds of all draws, inf without one) may be null.
+// -8 before a gate is applied for a bad channel gate (check_channels); -9 when p_b is 0 or not finite or tot is 0 in a draw, naming
+// the state and the gate.  With n_channels = 0 the call IS qkb_simulate_gates.
+int qkb_simulate_channels(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
+                          int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
+                          const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate, int32_t* dims_out,
+                          double** tensors_out, int64_t* n_complex_out, double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out) {
+  Channels ch;
+  if (n_channels < 0 || (n_channels > 0 && (!kraus || !n_kraus || !channel || !branch))) {
+    g_err = "a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch";
+    return -8;
+  }
+  if (n_channels > 0) {
+    ch.n_channels = n_channels, ch.kraus = reinterpret_cast<const cd*>(kraus), ch.n_kraus = n_kraus, ch.channel = channel, ch.branch = branch;
+    ch.seed = seed, ch.state_index = state_index, ch.trajectory = trajectory, ch.first_gate = first_gate;
+  }
+  ch.logw_out = logw_out, ch.branches_out = branches_out, ch.margin_out = margin_out;
+  return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, ch, dims_out, tensors_out, n_complex_out, fidelity_out);
+}
+}  // extern "C"
+
+static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
+                         int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, const Channels& ch, int32_t* dims_out, double** tensors_out,
+                         int64_t* n_complex_out, double* fidelity_out) {
   if (!p_zgesdd) {
     g_err = "qkb_init has not been called";
     return -1;
@@ -207,14 +300,20 @@ int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const 
   }
   const int n_codes = n_mats > 0 ? N_OPS_MAT : N_OPS;
   for (int i = 0; i < n_ops; ++i)
-    if (op[i] < 0 || op[i] >= n_codes) {
-      g_err = "unknown gate op code " + std::to_string((int)op[i]) + " (valid: 0.." + std::to_string(n_codes - 1) + ")";
+    if ((op[i] < 0 || op[i] >= n_codes) && !(ch.n_channels > 0 && op[i] == OP_K1)) {
+      g_err = "unknown gate op code " + std::to_string((int)op[i]) + " (valid: 0.." + std::to_string(n_codes - 1) + (ch.n_channels > 0 ? ", 10)" : ")");
       return -7;
     }
   if (n_mats > 0) {
     g_err = check_table(n_ops, op, n_mats, mats, mat);
     if (!g_err.empty()) return -8;
   }
+  if (ch.n_channels > 0) {
+    g_err = check_channels(n, n_ops, op, q0, ch);
+    if (!g_err.empty()) return -8;
+  }
+  double logw = 0.0, margin = INFINITY;
+  int n_drawn = 0;  // channel gates done: the index into branches_out
   std::vector<Tensor> A(n);
   for (auto& t : A) t.v = {cd(1, 0), cd(0, 0)};
   std::vector<int> two_q_pos;
@@ -266,7 +365,7 @@ int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const 
         }
       continue;
     }
-    if (!is_two_qubit(o)) {  // Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
+    if (!is_two_qubit(o) && o != OP_K1) {  // Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
       const double th = 0.5 * M_PI * alpha[i];
       const double cs = std::cos(th), sn = std::sin(th);
       const cd m01 = o == OP_RX ? cd(0.0, -sn) : cd(-sn, 0.0), m10 = o == OP_RX ? cd(0.0, -sn) : cd(sn, 0.0);
@@ -279,8 +378,9 @@ int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const 
         }
       continue;
     }
-    // ---- two-qubit gate on (q, q+1): bring the orthogonality centre onto the pair
-    while (centre < q) {
+    // ---- two-qubit gate on (q, q+1): bring the orthogonality centre onto the pair; a channel on q: onto the site
+    const int lo = q, hi = (o == OP_K1) ? q : q + 1;
+    while (centre < lo) {
       Tensor& t = A[centre];
       const int m = t.l * 2, nn = t.r;
       if (qr_economic(m, nn, t.v.data(), Q, R, work, cm) != 0) {
@@ -297,7 +397,7 @@ int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const 
       t.r = k;
       ++centre;
     }
-    while (centre > q + 1) {
+    while (centre > hi) {
       Tensor& t = A[centre];  // [l][2 r] -> QR of its transpose [2r x l]
       const int l = t.l, w = 2 * t.r;
       cm.resize(0);
@@ -322,6 +422,56 @@ int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const 
         for (int c = 0; c < w; ++c) t.v[(size_t)jj * w + c] = Q[(size_t)c * k + jj];
       t.l = k;
       --centre;
+    }
+    if (o == OP_K1) {  // the channel step: the centre stays on q, the bonds do not change
+      const int c = ch.channel[i], forced = ch.branch[i], m = ch.n_kraus[c];
+      const cd* K = ch.kraus + (size_t)c * 16;
+      Tensor& t = A[q];
+      double N = 0, p[4] = {0, 0, 0, 0};
+      for (int a = 0; a < t.l; ++a)  // every sum in ascending order of (a, c)
+        for (int x = 0; x < t.r; ++x) {
+          const cd v[2] = {t.at(a, 0, x), t.at(a, 1, x)};
+          N += std::norm(v[0]) + std::norm(v[1]);
+          for (int k = 0; k < m; ++k) p[k] += std::norm(mat_dot(K + k * 4, v, 2)) + std::norm(mat_dot(K + k * 4 + 2, v, 2));
+        }
+      double tot = 0;
+      for (int k = 0; k < m; ++k) tot += p[k];
+      const auto at = [&] { return "state " + std::to_string(ch.state_index) + ", gate " + std::to_string(ch.first_gate + (uint32_t)i) + ": "; };  // error paths only
+      int b = forced;
+      if (forced < 0) {
+        if (!(tot > 0.0) || !std::isfinite(tot)) {
+          g_err = at() + "the branch probabilities of the channel sum to 0 or are not finite";
+          return -9;
+        }
+        const double u = channel_uniform(ch.seed, ch.first_gate + (uint32_t)i, ch.trajectory, ch.state_index);
+        double cum = 0;
+        int last = -1;
+        for (int k = 0; k < m; ++k) {
+          cum += p[k];
+          if (k < m - 1) margin = std::min(margin, std::fabs(u * tot - cum) / tot);
+          if (p[k] > 0.0) {
+            last = k;
+            if (b < 0 && u * tot < cum) b = k;
+          }
+        }
+        if (b < 0) b = last;
+      }
+      if (!(p[b] > 0.0) || !std::isfinite(p[b])) {
+        g_err = at() + "branch " + std::to_string(b) + " of the channel has probability 0 or one that is not finite (an impossible outcome was post-selected?)";
+        return -9;
+      }
+      const double s = std::sqrt(p[b]);
+      const cd Kb[4] = {K[b * 4] / s, K[b * 4 + 1] / s, K[b * 4 + 2] / s, K[b * 4 + 3] / s};
+      for (int a = 0; a < t.l; ++a)
+        for (int x = 0; x < t.r; ++x) {
+          const cd v[2] = {t.at(a, 0, x), t.at(a, 1, x)};
+          t.at(a, 0, x) = mat_dot(Kb, v, 2);
+          t.at(a, 1, x) = mat_dot(Kb + 2, v, 2);
+        }
+      logw += std::log(p[b] / N);
+      if (ch.branches_out) ch.branches_out[n_drawn] = (int8_t)b;
+      ++n_drawn;
+      continue;
     }
     Tensor& a0 = A[q];
     Tensor& a1 = A[q + 1];
@@ -446,9 +596,12 @@ int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const 
   *tensors_out = reinterpret_cast<double*>(block);
   *n_complex_out = total;
   *fidelity_out = fidelity;
+  if (ch.logw_out) *ch.logw_out = logw;
+  if (ch.margin_out) *ch.margin_out = margin;
   return 0;
 }
 
+extern "C" {
 void qkb_free(double* p) { std::free(p); }
 
 }  // extern "C"

@@ -124,6 +124,11 @@ _SIGNATURES = [
     ("qk_build_mps_scan", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.POINTER(_P)]),
     ("qk_build_mps_gates", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
                                      C.POINTER(_P)]),
+    ("qk_build_mps_channels", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
+                                        C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(_P)]),
+    ("qk_built_logw_at", C.c_int, [_P, C.c_int32, _P]),
+    ("qk_built_num_channel_gates", C.c_int, [_P]),
+    ("qk_built_branches", C.c_int, [_P, _P]),
     ("qk_built_num_snapshots", C.c_int, [_P]),
     ("qk_built_checkpoints", C.c_int, [_P, _P]),
     ("qk_built_info_at", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
@@ -292,6 +297,37 @@ def sample_uniform(seed, state, shot, site):
     u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 from the first two output words."""
     x = _philox_stream(seed, state, shot, site, 0).astype(np.uint64)
     return ((x[..., 0] >> np.uint64(5)) * np.uint64(1 << 26) + (x[..., 1] >> np.uint64(6))).astype(np.float64) * 2.0 ** -53
+
+
+def channel_uniform(seed, gate, trajectory, state):
+    """The uniform in [0, 1) that draws the branch of the Kraus channel at position ``gate`` of the program (counted from the start
+    of the uninterrupted circuit: ``first_gate + i``) in trajectory ``trajectory`` of the state with index ``state`` (arrays
+    broadcast): Philox counter (gate, trajectory, state, 2), key (seed & 0xffffffff, seed >> 32), u made from the first two output
+    words as ``sample_uniform`` makes it.  Stream 2: stream 0 draws shots, stream 1 bases."""
+    x = _philox_stream(seed, state, trajectory, gate, 2).astype(np.uint64)
+    return ((x[..., 0] >> np.uint64(5)) * np.uint64(1 << 26) + (x[..., 1] >> np.uint64(6))).astype(np.float64) * 2.0 ** -53
+
+
+def with_noise(gates, channel_name, params, after="all"):
+    """A gate list ``(name, qubits, params)`` with the channel ``(channel_name, [q], params)`` behind every gate (``after="all"``) or
+    behind every two-qubit gate (``after="two_qubit"``), on each qubit the gate touches, in the order the gate names them.  Gates
+    that are channels themselves get none.  The list goes to ``BoundCircuit.from_gates`` / ``as_bound_circuit`` or, with the
+    parameters in the place of the angle, to ``CircuitAnsatz``."""
+    from .ansatz import _CHANNEL_NAMES
+
+    if channel_name not in _CHANNEL_NAMES:
+        raise ValueError(f"unknown channel {channel_name!r} (supported: {', '.join(_CHANNEL_NAMES)})")
+    if after not in ("all", "two_qubit"):
+        raise ValueError(f"after must be 'all' or 'two_qubit', got {after!r}")
+    out = []
+    for g in gates:
+        out.append(g)
+        name, qubits = g[0], g[1]
+        qs = [int(q) for q in (qubits if np.ndim(qubits) else [qubits])]
+        if (isinstance(name, str) and name in _CHANNEL_NAMES) or (after == "two_qubit" and len(qs) != 2):
+            continue
+        out.extend((channel_name, [q], params) for q in qs)
+    return out
 
 
 def random_bases(shots: int, n_qubits: int, seed=0) -> np.ndarray:
@@ -1348,9 +1384,14 @@ class _GateProgram:
     """The circuits of one device-builder call as the arrays of ``qk_build_mps_gates``: the shared gate structure (``op``, ``q0`` and,
     with a matrix table, ``mat``), the per-state angles, and the matrix table of op codes 8 and 9 -- shared (stride 0) when every
     circuit's ``mats`` is the same array bit for bit, otherwise stacked per state (stride n_mats).  ``QkError`` when the circuits do
-    not share their gate structure.  The table goes to the C entry as it is: it validates indices and unitarity."""
+    not share their gate structure.  The table goes to the C entry as it is: it validates indices and unitarity.
 
-    def __init__(self, what, circuits):
+    A channel table (op code 10) belongs to the gate structure: ``channel``, ``kraus`` and ``n_kraus`` must be the same for every
+    circuit; ``branch`` may differ per state (one row for all when they agree, stride 0, otherwise a row per state).  ``seed``,
+    ``state_index`` and ``trajectory`` (a scalar for all states, or one per state; ``None``: 0 .. n-1 and 0) name the trajectories,
+    ``first_gate`` the position of the first gate in the uninterrupted program."""
+
+    def __init__(self, what, circuits, seed=0, state_index=None, trajectory=None, first_gate=0):
         c0 = circuits[0]
         self.what = what
         self.n, self.ns = int(c0.n_qubits), len(circuits)
@@ -1377,6 +1418,41 @@ class _GateProgram:
                 self.mats = tables[0]
             else:
                 self.mats, self.stride = np.ascontiguousarray(np.stack(tables)), self.n_mats
+        self.n_channels, self.bstride, self.kraus, self.n_kraus, self.channel, self.branch = 0, 0, None, None, None, None
+        has_chan = [getattr(c, "kraus", None) is not None and getattr(c, "n_kraus", None) is not None and getattr(c, "channel", None) is not None for c in circuits]
+        if any(has_chan):
+            k0 = np.ascontiguousarray(c0.kraus, dtype=np.complex128) if has_chan[0] else None
+            for c, h in zip(circuits, has_chan):
+                if not h or np.shape(c.kraus) != k0.shape or not (np.array_equal(c.channel, c0.channel) and np.array_equal(c.n_kraus, c0.n_kraus)
+                                                                    and np.ascontiguousarray(c.kraus, dtype=np.complex128).tobytes() == k0.tobytes()):
+                    raise QkError(f"{what}: the circuits of one call must share their gate structure (the channels of op code 10 and their table included)")
+            if k0.ndim != 4 or k0.shape[1:] != (4, 2, 2) or np.shape(c0.n_kraus) != k0.shape[:1] or np.shape(c0.channel) != self.op.shape:
+                raise QkError(f"{what}: the channel table must be [n_channels][4][2][2] with a count per channel and a channel per gate, got shapes {k0.shape}, "
+                              f"{np.shape(c0.n_kraus)} and {np.shape(c0.channel)}")
+            self.n_channels, self.kraus = int(k0.shape[0]), k0
+            self.n_kraus = np.ascontiguousarray(c0.n_kraus, dtype=np.int32)
+            self.channel = np.ascontiguousarray(c0.channel, dtype=np.int32)
+            rows = [np.full(self.op.shape, -1, dtype=np.int32) if c.branch is None else np.ascontiguousarray(c.branch, dtype=np.int32) for c in circuits]
+            if any(r.shape != self.op.shape for r in rows):
+                raise QkError(f"{what}: branch must hold one entry per gate of the program")
+            if all(np.array_equal(r, rows[0]) for r in rows[1:]):
+                self.branch = rows[0]
+            else:
+                self.branch, self.bstride = np.ascontiguousarray(np.stack(rows)), int(self.op.shape[0])
+        self.seed = int(_seed_key(seed)[0]) | (int(_seed_key(seed)[1]) << 32)
+        self.state_index = self._ids("state_index", state_index, np.arange(self.ns))
+        self.trajectory = self._ids("trajectory", trajectory, np.zeros(self.ns, dtype=np.int64))
+        if isinstance(first_gate, bool) or not isinstance(first_gate, (int, np.integer)) or not 0 <= int(first_gate) < 1 << 32:
+            raise ValueError(f"first_gate must be an int in 0 .. 2^32 - 1 (got {first_gate!r})")
+        self.first_gate = int(first_gate)
+
+    def _ids(self, name, v, default):
+        a = np.asarray(default if v is None else v)
+        if a.ndim == 0:
+            a = np.full(self.ns, a)
+        if a.shape != (self.ns,) or a.dtype.kind not in "iu" or a.min() < 0 or a.max() >= 1 << 32:
+            raise ValueError(f"{name} must be an int or one int per state ({self.ns}) in 0 .. 2^32 - 1, got {v!r}")
+        return np.ascontiguousarray(a, dtype=np.uint32)
 
     def build(self, ctx, truncation_fidelity, value_of_zero, max_bond, flags, cps=None, src=None, src_j=0):
         """One launch of the device builder: the handle of the built states (``qk_built``)."""
@@ -1384,6 +1460,14 @@ class _GateProgram:
         h = _P()
         head = (ctx._h, self.ns, self.n, n_ops, self.op.ctypes.data, self.q0.ctypes.data, self.alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero),
                 int(max_bond), flags)
+        if self.n_channels and n_ops:
+            if cps is None:
+                cps = np.array([n_ops], dtype=np.int32)
+            _check(lib().qk_build_mps_channels(*head, int(cps.shape[0]), cps.ctypes.data, src, src_j, self.n_mats, self.mats.ctypes.data if self.n_mats else None, self.stride,
+                                               self.mat.ctypes.data if self.n_mats else None, self.n_channels, self.kraus.ctypes.data, self.n_kraus.ctypes.data,
+                                               self.channel.ctypes.data, self.branch.ctypes.data, self.bstride, self.seed, self.state_index.ctypes.data,
+                                               self.trajectory.ctypes.data, self.first_gate, C.byref(h)), "qk_build_mps_channels")
+            return h
         if cps is None and (self.n_mats == 0 or n_ops == 0):  # no snapshots, no table: the plain entry
             _check(lib().qk_build_mps(*head, C.byref(h)), "qk_build_mps")
             return h
@@ -1394,13 +1478,28 @@ class _GateProgram:
         return h
 
 
+def _built_trajectories(h, ns, j=-1):
+    """``(logw float64 (ns,), branches int8 (ns, n_channel_gates))`` of a built handle: the log-weights at snapshot j (-1: the last)
+    and the branch every channel gate of the program took (-1 where a dropped state stopped early)."""
+    if j < 0:
+        j += int(lib().qk_built_num_snapshots(h))
+    logw = np.zeros(ns, dtype=np.float64)
+    _check(lib().qk_built_logw_at(h, j, logw.ctypes.data), "qk_built_logw_at")
+    nk = int(lib().qk_built_num_channel_gates(h))
+    branches = np.full((ns, nk), -1, dtype=np.int8)
+    if nk:
+        _check(lib().qk_built_branches(h, branches.ctypes.data), "qk_built_branches")
+    return logw, branches
+
+
 class BuiltScan:
     """The snapshots of ``Context.build_mps_scan``: owns the builder's handle (one device heap with every snapshot of every state)
     until ``close()``; a context manager.  ``checkpoints[j]`` gates were done at snapshot j; the last snapshot is the finished
     circuit.  ``set(j)`` / ``states(j)`` are independent of the scan afterwards."""
 
-    def __init__(self, ctx, handle, n_states, n_qubits):
+    def __init__(self, ctx, handle, n_states, n_qubits, kgate_at=None):
         self.ctx, self._h, self.n_states, self.n_qubits = ctx, handle, int(n_states), int(n_qubits)
+        self._kgate_at = kgate_at  # positions of the channel gates in the program: a snapshot's states carry the branches taken so far
         ns = int(lib().qk_built_num_snapshots(handle))
         cps = np.zeros(ns, dtype=np.int32)
         _check(lib().qk_built_checkpoints(handle, cps.ctypes.data), "qk_built_checkpoints")
@@ -1408,6 +1507,7 @@ class BuiltScan:
         ms = C.c_double()
         _check(lib().qk_built_info(handle, None, None, None, None, C.byref(ms)), "qk_built_info")
         self.kernel_ms = ms.value
+        self.first_gate = 0  # position of the program's first gate in the uninterrupted circuit (build_mps_scan sets it)
         ctx._adopt(self)  # closed with the context: the heap lives on its device
 
     @property
@@ -1439,9 +1539,12 @@ class BuiltScan:
 
     def info(self, j) -> dict:
         """Snapshot j: {"dims": bond tables (n_states, n_qubits + 1), "fidelity": the fidelity product so far (n_states,),
-        "centre": site of the orthogonality centre (n_states,), "heap_bytes": bytes of the snapshot's tensors in the heap}."""
-        _, dims, fid, _, centre, total = self._info(j)
-        return {"dims": dims, "fidelity": fid, "centre": centre, "heap_bytes": 16 * total}
+        "centre": site of the orthogonality centre (n_states,), "heap_bytes": bytes of the snapshot's tensors in the heap,
+        "logw": the log-weights of the trajectories so far (n_states,), "branches": the branch of every channel gate of the whole
+        program (n_states, n_channel_gates), whichever snapshot is asked}."""
+        k, dims, fid, _, centre, total = self._info(j)
+        logw, branches = _built_trajectories(self._h, self.n_states, k)
+        return {"dims": dims, "fidelity": fid, "centre": centre, "heap_bytes": 16 * total, "logw": logw, "branches": branches}
 
     def set(self, j) -> "MpsSet":
         """Snapshot j as a device-resident set (packed on the device: nothing is downloaded); feeds ``gram``, ``local_paulis``,
@@ -1456,6 +1559,8 @@ class BuiltScan:
         from .mps import MPS
 
         j, dims, fid, _, _, total = self._info(j)
+        logw, branches = _built_trajectories(self._h, self.n_states, j)
+        done = np.count_nonzero(np.asarray(self._kgate_at) < self.checkpoints[j]) if self._kgate_at is not None else branches.shape[1]
         flat = np.empty(max(total, 1), dtype=np.complex128)
         _check(lib().qk_built_download_at(self._h, j, flat.ctypes.data), "qk_built_download_at")
         out, pos = [], 0
@@ -1465,7 +1570,7 @@ class BuiltScan:
                 sz = int(dims[s_, k]) * 2 * int(dims[s_, k + 1])
                 tensors.append(flat[pos : pos + sz].reshape(int(dims[s_, k]), 2, int(dims[s_, k + 1])).copy())
                 pos += sz
-            out.append(MPS(tensors, float(fid[s_])))
+            out.append(MPS(tensors, float(fid[s_]), float(logw[s_]), branches[s_, :done]))
         return out
 
     def close(self):
@@ -1561,18 +1666,24 @@ class Context:
         self.last_precond_ms = [float(np.uint32(t)) / 1e5 for t in st[1:]]  # all, sort + copy, Gram-Schmidt, sweeps, V and W = A V
         return a, v, sig, ord_, int(st[0]), self.last_precond_ms[0]
 
-    def build_mps(self, circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, partial: bool = False, truncate: bool = False):
+    def build_mps(self, circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, partial: bool = False, truncate: bool = False,
+                  seed=0, state_index=None, trajectory=None):
         """Device MPS builder (/root/reference/gpu_backend/kernel_state_ansatz.py:221, 263): the MPS of every
         bound circuit of the list (``ansatz.BoundCircuit``; they must share one gate structure, as the data points of one
         ansatz do) in ONE launch.  Returns (list[MPS], info) with info = {"kernel_ms", "total_complex", "dropped"}.  With
         ``partial`` a state that outgrows ``max_bond`` does not fail the call: its entry in the list is ``None`` and its index is
-        in info["dropped"] (build it with the host builder)."""
+        in info["dropped"] (build it with the host builder).
+
+        Circuits with Kraus channels (op code 10) are run as quantum trajectories: state s draws its branches from ``seed``,
+        ``state_index[s]`` and ``trajectory[s]`` (an int for all, or one per state; ``None``: 0 .. n-1 and 0; see
+        ``channel_uniform``), so its result does not depend on what else the call builds.  info["logw"] (n,) and info["branches"]
+        (n, n_channel_gates) record the log-probability and the branches; the states carry them too."""
         from .mps import MPS
 
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_mps needs at least one circuit")
-        prog = _GateProgram("build_mps", circuits)
+        prog = _GateProgram("build_mps", circuits, seed, state_index, trajectory)
         n, ns = prog.n, prog.ns
         h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0))
         try:
@@ -1583,6 +1694,7 @@ class Context:
             _check(lib().qk_built_info(h, dims.ctypes.data, fid.ctypes.data, offs.ctypes.data, C.byref(total), C.byref(ms)), "qk_built_info")
             flat = np.empty(total.value, dtype=np.complex128)
             _check(lib().qk_built_download(h, flat.ctypes.data), "qk_built_download")
+            logw, branches = _built_trajectories(h, ns)
         finally:
             lib().qk_built_destroy(h)
         states, dropped = [], []
@@ -1596,16 +1708,17 @@ class Context:
                 sz = int(dims[s_, k]) * 2 * int(dims[s_, k + 1])
                 tensors.append(flat[pos : pos + sz].reshape(int(dims[s_, k]), 2, int(dims[s_, k + 1])))
                 pos += sz
-            states.append(MPS(tensors, float(fid[s_])))
-        return states, {"kernel_ms": ms.value, "total_complex": int(total.value), "dropped": dropped}
+            states.append(MPS(tensors, float(fid[s_]), float(logw[s_]), branches[s_]))
+        return states, {"kernel_ms": ms.value, "total_complex": int(total.value), "dropped": dropped, "logw": logw, "branches": branches}
 
-    def build_mps_set(self, circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, truncate: bool = False):
+    def build_mps_set(self, circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, truncate: bool = False, seed=0,
+                      state_index=None, trajectory=None):
         """Like ``build_mps`` but the states never leave the device: returns (MpsSet, info) with info = {"kernel_ms", "dims",
-        "fidelity"}; the set feeds ``gram`` / ``gram_values`` directly."""
+        "fidelity", "logw", "branches"}; the set feeds ``gram`` / ``gram_values`` directly."""
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_mps_set needs at least one circuit")
-        prog = _GateProgram("build_mps_set", circuits)
+        prog = _GateProgram("build_mps_set", circuits, seed, state_index, trajectory)
         n, ns = prog.n, prog.ns
         hs = _P()
         h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, 2 if truncate else 0)
@@ -1614,13 +1727,14 @@ class Context:
             fid = np.zeros(ns, dtype=np.float64)
             ms = C.c_double()
             _check(lib().qk_built_info(h, dims.ctypes.data, fid.ctypes.data, None, None, C.byref(ms)), "qk_built_info")
+            logw, branches = _built_trajectories(h, ns)
             _check(lib().qk_mps_set_from_built(self._h, h, C.byref(hs)), "qk_mps_set_from_built")
         finally:
             lib().qk_built_destroy(h)
-        return MpsSet(self, hs, dims), {"kernel_ms": ms.value, "dims": dims, "fidelity": fid}
+        return MpsSet(self, hs, dims), {"kernel_ms": ms.value, "dims": dims, "fidelity": fid, "logw": logw, "branches": branches}
 
     def build_mps_scan(self, circuits, checkpoints, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, truncate: bool = False,
-                       initial=None, partial: bool = False) -> BuiltScan:
+                       initial=None, partial: bool = False, seed=0, state_index=None, trajectory=None, first_gate=None) -> BuiltScan:
         """``build_mps_set`` that also keeps every state after ``checkpoints[j]`` gates (gate counts: strictly increasing, in
         1 .. n_gates, the last one n_gates; ``KernelStateAnsatz.layer_ends()`` for a scan over depth): ONE launch, the snapshots are
         copies and the run does the arithmetic of a run without them, so the last snapshot is what ``build_mps`` returns.  Returns a
@@ -1630,23 +1744,32 @@ class Context:
         ``initial=(scan, j)`` resumes: the states start as snapshot j of an earlier scan of this context (same number of states and
         qubits, no bond above ``max_bond``) and ``circuits`` are the gates that follow it -- ``c.sliced(scan.checkpoints[j],
         c.n_gates)`` continues the same circuits, gate for gate the arithmetic of the uninterrupted run.  ``scan`` is left untouched.
-        ``ValueError`` for bad checkpoints; ``partial`` goes with one checkpoint and no ``initial`` only (``QkError`` otherwise)."""
+        ``ValueError`` for bad checkpoints; ``partial`` goes with one checkpoint and no ``initial`` only (``QkError`` otherwise).
+
+        ``seed``, ``state_index`` and ``trajectory`` name the trajectories of circuits with Kraus channels as in ``build_mps``.
+        ``first_gate`` is the position of the first gate of ``circuits`` in the uninterrupted program; ``None`` takes it from
+        ``initial`` (``scan.checkpoints[j]`` plus the ``first_gate`` that scan was given; 0 without one), so a resumed build draws
+        what the uninterrupted run draws and its log-weights go on from the snapshot's.  ``info(j)`` and ``states(j)`` carry
+        ``logw`` and ``branches``."""
         from .ansatz import check_checkpoints
 
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_mps_scan needs at least one circuit")
         cps = np.ascontiguousarray(check_checkpoints(checkpoints, int(np.shape(circuits[0].op)[0])), dtype=np.int32)
-        prog = _GateProgram("build_mps_scan", circuits)
-        n, ns = prog.n, prog.ns
-        src, src_j = None, 0
+        src, src_j, base = None, 0, 0
         if initial is not None:
             scan, j = initial
             if not isinstance(scan, BuiltScan):
                 raise ValueError(f"initial must be (BuiltScan, snapshot index), got {initial!r}")
             src, src_j = scan.handle, scan._index(j)
+            base = scan.first_gate + scan.checkpoints[src_j]
+        prog = _GateProgram("build_mps_scan", circuits, seed, state_index, trajectory, base if first_gate is None else first_gate)
+        n, ns = prog.n, prog.ns
         h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0), cps, src, src_j)
-        return BuiltScan(self, h, ns, n)
+        scan = BuiltScan(self, h, ns, n, np.flatnonzero(prog.op == 10) if prog.n_channels else None)
+        scan.first_gate = prog.first_gate
+        return scan
 
     def set_from_packed(self, dims_true, offsets, planes_ptr: int, n_doubles: int) -> MpsSet:
         """A set assembled from packed images (``MpsSet.image`` of several ranks, gathered into one buffer on the device or
@@ -1658,17 +1781,19 @@ class Context:
                "qk_mps_set_from_packed")
         return MpsSet(self, h, dims)
 
-    def build_share(self, circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, partial: bool = False, truncate: bool = False):
+    def build_share(self, circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, partial: bool = False, truncate: bool = False,
+                    seed=0, state_index=None, trajectory=None):
         """Device builder for one rank's share of a data set, the states staying on the device whenever possible: returns
         (MpsSet, None, info) when every state fitted ``max_bond`` (packed on the device by ``qk_mps_set_from_built``: nothing
         is downloaded), else (None, list[MPS | None], info) with the dropped states ``None`` (``partial`` only), to be
-        completed by the host builder.  info = {"kernel_ms", "dims", "fidelity", "dropped"}."""
+        completed by the host builder.  info = {"kernel_ms", "dims", "fidelity", "dropped", "logw", "branches"}; ``seed``,
+        ``state_index`` and ``trajectory`` as in ``build_mps``."""
         from .mps import MPS
 
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_share needs at least one circuit")
-        prog = _GateProgram("build_share", circuits)
+        prog = _GateProgram("build_share", circuits, seed, state_index, trajectory)
         n, ns = prog.n, prog.ns
         h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0))
         try:
@@ -1678,7 +1803,8 @@ class Context:
             total, ms = C.c_int64(), C.c_double()
             _check(lib().qk_built_info(h, dims.ctypes.data, fid.ctypes.data, offs.ctypes.data, C.byref(total), C.byref(ms)), "qk_built_info")
             dropped = [int(k) for k in np.nonzero(fid < 0)[0]]
-            info = {"kernel_ms": ms.value, "dims": dims, "fidelity": fid, "dropped": dropped}
+            logw, branches = _built_trajectories(h, ns)
+            info = {"kernel_ms": ms.value, "dims": dims, "fidelity": fid, "dropped": dropped, "logw": logw, "branches": branches}
             if not dropped:
                 hs = _P()
                 _check(lib().qk_mps_set_from_built(self._h, h, C.byref(hs)), "qk_mps_set_from_built")
@@ -1697,7 +1823,7 @@ class Context:
                 sz = int(dims[s_, k]) * 2 * int(dims[s_, k + 1])
                 tensors.append(flat[pos : pos + sz].reshape(int(dims[s_, k]), 2, int(dims[s_, k + 1])))
                 pos += sz
-            states.append(MPS(tensors, float(fid[s_])))
+            states.append(MPS(tensors, float(fid[s_]), float(logw[s_]), branches[s_]))
         return None, states, info
 
     def upload(self, states, layout=QK_LAYOUT_LPR) -> MpsSet:

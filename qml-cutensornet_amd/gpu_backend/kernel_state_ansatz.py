@@ -26,13 +26,13 @@ from statistics import mean, median
 import numpy as np
 
 try:  # normal case: imported as qml_cutensornet_amd.gpu_backend.kernel_state_ansatz
-    from ..ansatz import OP_M2, OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit, check_depths  # noqa: F401
+    from ..ansatz import OP_M2, OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit, check_depths, reject_channels  # noqa: F401
     from .. import engine as _engine
     from ..dist import assemble_gram, comm_allgather, exchange_sets
     from ..mps import MPS, simulate, simulate_many  # noqa: F401
 except ImportError:  # imported top-level as gpu_backend.kernel_state_ansatz
     import qml_cutensornet_amd as _pkg  # noqa: F401
-    from qml_cutensornet_amd.ansatz import OP_M2, OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit, check_depths  # noqa: F401
+    from qml_cutensornet_amd.ansatz import OP_M2, OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit, check_depths, reject_channels  # noqa: F401
     from qml_cutensornet_amd import engine as _engine
     from qml_cutensornet_amd.dist import assemble_gram, comm_allgather, exchange_sets
     from qml_cutensornet_amd.mps import MPS, simulate, simulate_many  # noqa: F401
@@ -189,6 +189,7 @@ def _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, dev
     forced = which  # what the caller asked for: only a FORCED device build may fail the call
     # an ansatz may return a BoundCircuit or a reference-style gate list (name, qubits, params)
     circuits = [as_bound_circuit(ansatz.circuit_for_data(points[k, :]), ansatz) for k in range(lo, hi)] if hi > lo else []
+    reject_channels(circuits, "a driver without trajectories")
     if which == "auto":
         try:
             which = _auto_builder(circuits, host_workers)
@@ -1285,6 +1286,7 @@ def _depth_scan_share(ctx, ansatz, points, rank, n_procs, fidelity, depths, ends
         return lo, {r: None for r in depths}, {r: [] for r in depths}
     deepest = ends[depths[-1] - 1]
     circuits = [as_bound_circuit(ansatz.circuit_for_data(points[k, :]), ansatz).sliced(0, deepest) for k in range(lo, hi)]
+    reject_channels(circuits, "build_depth_scan_kernel_matrices")
     chi = int(os.environ.get("QK_MAX_BOND", "0")) or None
     cap = chi or int(os.environ.get("QK_BUILDER_MAX_BOND", "320"))
     sets, fids = {}, {}
@@ -1380,3 +1382,151 @@ def build_depth_scan_kernel_matrices(mpi_comm, ansatz, X, Y=None, depths=(1,), t
         with open(info_file + ".json", "w") as fp:
             json.dump(prof, fp, indent=4)
     return out
+
+
+def _noisy_share(ansatz, points, first_index, trajectories, noise_seed, rank, n_procs, fidelity, is_root, label, device_id):
+    """This rank's slice of a data set, every point as ``trajectories`` quantum trajectories -> (first point, the states as one
+    device set in the order (point, trajectory) -- ``None`` for an empty share --, the log-weights (m, T), does the ansatz hold
+    channels).  Data point p of the slice's data set has state index ``first_index + p`` and its trajectories are 0 .. T-1, so the
+    draws do not depend on the number of ranks.  QK_BUILDER=host builds on the host (``mps.simulate`` with the same seed and
+    indices); any other value on the device, bonds up to QK_BUILDER_MAX_BOND (320) or QK_MAX_BOND (a cap), and a share the device
+    gives up on is rebuilt on the host with the same seed and indices unless the device was forced."""
+    import os
+
+    T = int(trajectories)
+    per_rank = -(-len(points) // n_procs)
+    lo = min(len(points), rank * per_rank)
+    hi = min(len(points), lo + per_rank)
+    if hi <= lo:
+        return lo, None, np.zeros((0, T)), False
+    circuits = [as_bound_circuit(ansatz.circuit_for_data(points[k, :]), ansatz) for k in range(lo, hi)]
+    noisy = any(c.n_channel_gates > 0 for c in circuits)
+    expanded = [c for c in circuits for _ in range(T)]
+    sidx = np.repeat(np.arange(lo, hi, dtype=np.int64) + int(first_index), T)
+    traj = np.tile(np.arange(T, dtype=np.int64), hi - lo)
+    chi = int(os.environ.get("QK_MAX_BOND", "0")) or None
+    which = os.environ.get("QK_BUILDER", "auto")
+    ctx = _engine.default_context(device_id)
+    if which != "host":
+        cap = chi or int(os.environ.get("QK_BUILDER_MAX_BOND", "320"))
+        try:
+            dset, info = ctx.build_mps_set(expanded, fidelity, max_bond=cap, truncate=chi is not None, seed=noise_seed, state_index=sidx, trajectory=traj)
+            _say(is_root, f"{label}: 100%")
+            return lo, dset, np.asarray(info["logw"]).reshape(hi - lo, T), noisy
+        except _engine.QkError as exc:
+            if which == "device":
+                raise
+            _say(is_root, f"{label}: device builder gave up ({exc}); building on the host")
+    states = [simulate(c, fidelity, max_bond=chi, seed=noise_seed, state_index=int(s), trajectory=int(t)) for c, s, t in zip(expanded, sidx, traj)]
+    _say(is_root, f"{label}: 100%")
+    return lo, ctx.upload(states), np.array([m.logw for m in states]).reshape(hi - lo, T), noisy
+
+
+def _noisy_arguments(X, Y, trajectories, noise_seed, truncation_error):
+    if Y is not None and len(X) < len(Y):
+        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    if isinstance(trajectories, bool) or not isinstance(trajectories, (int, np.integer)) or trajectories < 1:
+        raise ValueError(f"trajectories must be an int >= 1 (got {trajectories!r})")
+    _engine._seed_key(noise_seed)
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: the noisy kernels have no CPU fallback")
+    return np.asarray(X, dtype=np.float64), None if Y is None else np.asarray(Y, dtype=np.float64), int(trajectories), n_dev
+
+
+def build_noisy_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, trajectories=1, noise_seed=0, rdm=1, pair_distance=1, pqk_gamma=None, truncation_error=None):
+    """The projected kernel of ``build_projected_kernel_matrix`` (``rdm=1`` or ``rdm=2`` with ``pair_distance``) for an ansatz with
+    Kraus channels (``engine.with_noise``, the channel names of ``BoundCircuit.from_gates``): every data point is run as
+    ``trajectories`` quantum trajectories and its features are the mean over them of ``local_paulis`` / ``local_pair_paulis`` -- the
+    Bloch vectors / pair correlators of the trajectory-averaged state rho = mean |psi_a><psi_a|, an unbiased estimate of the noisy
+    state's (the features are linear in rho: the cost is linear in T).  Then the existing Gram.  Data point p (Y after X) has state
+    index p and its trajectories are 0 .. T-1 (``channel_uniform(noise_seed, gate, trajectory, p)``), so any number of ranks gives
+    the same bits; ``trajectories=1`` with an ansatz without channels is ``build_projected_kernel_matrix`` to rounding.  Returns
+    the ``len(Y) x len(X)`` matrix on rank 0, ``None`` elsewhere."""
+    if rdm not in (1, 2):
+        raise ValueError(f"rdm must be 1 or 2, got {rdm!r}")
+    n_qubits = int(ansatz.num_qubits)
+    if isinstance(pair_distance, bool) or not isinstance(pair_distance, (int, np.integer)) or not 1 <= pair_distance <= max(1, n_qubits - 1):
+        raise ValueError(f"pair_distance must be an int in 1 .. n_qubits - 1 = {n_qubits - 1}, got {pair_distance!r}")
+    if rdm == 1 and pair_distance != 1:
+        raise ValueError(f"pair_distance={pair_distance!r} needs rdm=2: the one-qubit form has no pairs")
+    if rdm == 2 and n_qubits < 2:
+        raise ValueError("rdm=2 compares reduced density matrices of qubit pairs: the ansatz needs at least 2 qubits")
+    if pqk_gamma is not None:
+        _engine.projected_gamma(pqk_gamma, 1)
+    X, Y, T, n_dev = _noisy_arguments(X, Y, trajectories, noise_seed, truncation_error)
+    pair_distance = int(pair_distance)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    device_id = rank % n_dev
+    ctx = _engine.default_context(device_id)
+    n_pairs = pair_distance * n_qubits - pair_distance * (pair_distance + 1) // 2
+    feats = []
+    for label, points, first in (("X", X, 0), ("Y", Y, len(X))):
+        if points is None:
+            continue
+        lo, local, _, _ = _noisy_share(ansatz, points, first, T, noise_seed, rank, n_procs, 1.0 - float(truncation_error), is_root, label, device_id)
+        ctx.trim()
+        if local is None:
+            F = np.zeros((0, n_qubits, 3) if rdm == 1 else (0, n_pairs, 4, 4), dtype=np.float64)
+        else:
+            F = ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local, max_dist=pair_distance)
+            local.close()
+            F = np.asarray(F, dtype=np.float64)
+            F = F.reshape((F.shape[0] // T, T) + F.shape[1:]).mean(axis=1)  # the features of the trajectory-averaged state
+        feats.append(_gather_features(mpi_comm, lo, F, len(points)))
+    if not is_root:
+        return None
+    g = _engine.projected_gamma(pqk_gamma, n_qubits * pair_distance)
+    if rdm == 1:
+        return ctx.projected_gram(feats[0], None if Y is None else feats[1], g)
+    return ctx.projected_pair_gram(feats[0], None if Y is None else feats[1], g, max_dist=pair_distance)
+
+
+def build_noisy_kernel_matrix(mpi_comm, ansatz, X, Y=None, trajectories=2, noise_seed=0, truncation_error=None):
+    """The fidelity kernel of noisy states from quantum trajectories: ``K[j, i] = mean_{a,b} |<psi_a(X_i)|psi_b(Y_j)>|^2``, an
+    unbiased estimate of ``tr(rho(X_i) rho(Y_j))`` for rho = the trajectory-averaged state, taken from ONE fidelity Gram of the
+    expanded sets (T states per point) and averaged on the host.  ``Y=None`` means ``Y = X``; on its diagonal the a = b terms (which
+    are 1) are left out -- the unbiased estimate of the purity tr(rho^2) -- so a symmetric call on an ansatz with channels needs
+    ``trajectories >= 2``.  State indices and trajectories as in ``build_noisy_projected_kernel_matrix``: the same bits for any
+    number of ranks; ``trajectories=1`` with an ansatz without channels is ``build_kernel_matrix`` to rounding.  Returns the
+    ``len(Y) x len(X)`` matrix on rank 0, ``None`` elsewhere."""
+    X, Y, T, n_dev = _noisy_arguments(X, Y, trajectories, noise_seed, truncation_error)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    device_id = rank % n_dev
+    ctx = _engine.default_context(device_id)
+    fidelity = 1.0 - float(truncation_error)
+    x_lo, x_local, _, noisy = _noisy_share(ansatz, X, 0, T, noise_seed, rank, n_procs, fidelity, is_root, "X", device_id)
+    if Y is None and T < 2 and any(comm_allgather(mpi_comm, bool(noisy))):
+        if x_local is not None:
+            x_local.close()
+        raise ValueError("a symmetric noisy kernel leaves the a = b terms out of its diagonal: it needs trajectories >= 2")
+    y_lo, y_local = 0, None
+    if Y is not None:
+        y_lo, y_local, _, _ = _noisy_share(ansatz, Y, len(X), T, noise_seed, rank, n_procs, fidelity, is_root, "Y", device_id)
+    ctx.trim()
+    xset, _ = exchange_sets(mpi_comm, ctx, x_local, x_lo * T, len(X) * T)
+    yset = None
+    if Y is not None:
+        yset, _ = exchange_sets(mpi_comm, ctx, y_local, y_lo * T, len(Y) * T)
+    for loc, full in ((x_local, xset), (y_local, yset)):
+        if loc is not None and loc is not full:
+            loc.close()
+    try:
+        full, _ = _gram_on_device(mpi_comm, rank, n_procs, ctx, xset, yset)
+    finally:
+        xset.close()
+        if yset is not None:
+            yset.close()
+    if not is_root:
+        return None
+    ny = len(X) if Y is None else len(Y)
+    blocks = np.asarray(full, dtype=np.float64).reshape(ny, T, len(X), T)  # [j][b][i][a]
+    K = blocks.sum(axis=(1, 3)) / float(T * T)
+    if Y is None and T >= 2:
+        for i in range(len(X)):
+            K[i, i] = (blocks[i, :, i, :].sum() - np.trace(blocks[i, :, i, :])) / float(T * (T - 1))
+    return K

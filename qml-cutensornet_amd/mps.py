@@ -22,7 +22,8 @@ import numpy as np
 from scipy.linalg import qr as _qr
 from scipy.linalg import svd as _svd
 
-from .ansatz import OP_H, OP_M1, OP_M2, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_checkpoints, check_matrix_gates, is_two_qubit
+from .ansatz import (OP_H, OP_K1, OP_M1, OP_M2, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_channel_gates, check_checkpoints, check_matrix_gates,
+                     is_two_qubit, reject_channels)
 
 _SQRT_HALF = 0.7071067811865476
 _YY_SIGN = np.array([[1.0, -1.0], [-1.0, 1.0]])[None, :, :, None]  # c 1 - i s Y(x)Y: +i s on |00>,|11>, -i s on |01>,|10>
@@ -31,11 +32,15 @@ _YY_SIGN = np.array([[1.0, -1.0], [-1.0, 1.0]])[None, :, :, None]  # c 1 - i s Y
 class MPS:
     """n-site matrix-product state, open boundaries, physical dimension 2."""
 
-    __slots__ = ("tensors", "fidelity", "_handle")
+    __slots__ = ("tensors", "fidelity", "logw", "branches", "_handle")
 
-    def __init__(self, tensors, fidelity: float = 1.0):
+    def __init__(self, tensors, fidelity: float = 1.0, logw: float = 0.0, branches=None):
         self.tensors = list(tensors)
         self.fidelity = float(fidelity)
+        # a trajectory of a program with Kraus channels: the log of the probability of its branches, sum log(p_b / N), and the
+        # branch of every channel gate in program order (int8; empty for a program without channels)
+        self.logw = float(logw)
+        self.branches = np.zeros(0, dtype=np.int8) if branches is None else np.asarray(branches, dtype=np.int8).copy()
         self._handle = None
         left = 1
         for k, t in enumerate(self.tensors):
@@ -63,7 +68,7 @@ class MPS:
         return int(sum(t.nbytes for t in self.tensors))
 
     def copy(self) -> "MPS":
-        return MPS([t.copy() for t in self.tensors], self.fidelity)
+        return MPS([t.copy() for t in self.tensors], self.fidelity, self.logw, self.branches)
 
     def update_libhandle(self, handle) -> None:
         """Accepted for interface parity (ref :370,:374); states are immutable host
@@ -452,6 +457,10 @@ def _native_builder():
                                              C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
             lib.qkb_simulate_gates.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+            lib.qkb_simulate_channels.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p,
+                                                  C.POINTER(C.c_double)]
             lib.qkb_free.argtypes = [C.c_void_p]
             if blas and lib.qkb_init(os.path.realpath(blas[0]).encode()) == 0:
                 _NATIVE = lib
@@ -460,8 +469,10 @@ def _native_builder():
     return _NATIVE or None
 
 
-def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None) -> MPS:
-    """``simulate`` through the native builder: same algorithm and LAPACK routines, no interpreter in the gate loop."""
+def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None, seed=0, state_index=0,
+                    trajectory=0, first_gate=0, margin=False):
+    """``simulate`` through the native builder: same algorithm and LAPACK routines, no interpreter in the gate loop.  A circuit with
+    a channel table goes through ``qkb_simulate_channels`` (the trajectory arguments and ``margin`` as in ``simulate``)."""
     import ctypes as C
 
     lib = _native_builder()
@@ -481,10 +492,29 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
         if mats.ndim != 3 or mats.shape[1:] != (4, 4) or mat.shape != op.shape:
             raise ValueError(f"the matrix table must be [n_mats][4][4] with one index per gate, got shapes {mats.shape} and {mat.shape}")
         n_mats = int(mats.shape[0])
-    rc = lib.qkb_simulate_gates(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
-                                float(value_of_zero), int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None,
-                                dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid))
-    if rc in (-7, -8):  # an op code outside 0..7 (0..9 with a table); a matrix gate whose index or matrix is bad
+    seed, state_index, trajectory, first_gate = _trajectory_ids(seed, state_index, trajectory, first_gate)
+    logw, worst, branches = C.c_double(0.0), C.c_double(np.inf), np.zeros(0, dtype=np.int8)
+    if circuit.kraus is not None and circuit.n_kraus is not None and circuit.channel is not None:
+        # the channel table, handed over as it is: the native builder validates it
+        kraus = np.ascontiguousarray(circuit.kraus, dtype=np.complex128)
+        n_kraus = np.ascontiguousarray(circuit.n_kraus, dtype=np.int32)
+        channel = np.ascontiguousarray(circuit.channel, dtype=np.int32)
+        branch = np.full(op.shape, -1, dtype=np.int32) if circuit.branch is None else np.ascontiguousarray(circuit.branch, dtype=np.int32)
+        if kraus.ndim != 4 or kraus.shape[1:] != (4, 2, 2) or n_kraus.shape != kraus.shape[:1] or channel.shape != op.shape or branch.shape != op.shape:
+            raise ValueError(f"the channel table must be [n_channels][4][2][2] with a count per channel and a channel and a branch per gate, got shapes "
+                             f"{kraus.shape}, {n_kraus.shape}, {channel.shape}, {branch.shape}")
+        branches = np.full(max(1, int(np.count_nonzero(op == OP_K1))), -1, dtype=np.int8)
+        rc = lib.qkb_simulate_channels(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
+                                       float(value_of_zero), int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None,
+                                       int(kraus.shape[0]), kraus.ctypes.data, n_kraus.ctypes.data, channel.ctypes.data, branch.ctypes.data, seed, state_index,
+                                       trajectory, first_gate, dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid), C.byref(logw), branches.ctypes.data,
+                                       C.byref(worst))
+        branches = branches[: int(np.count_nonzero(op == OP_K1))]
+    else:
+        rc = lib.qkb_simulate_gates(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
+                                    float(value_of_zero), int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None,
+                                    dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid))
+    if rc in (-7, -8, -9):  # an op code outside the program's vocabulary; a bad matrix or channel gate; an impossible outcome of a channel
         raise ValueError(f"native MPS builder: {lib.qkb_last_error().decode()}")
     if rc != 0:
         raise RuntimeError(f"native MPS builder failed: {lib.qkb_last_error().decode()}")
@@ -497,10 +527,12 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
         sz = int(dims[k]) * 2 * int(dims[k + 1])
         tensors.append(flat[pos : pos + sz].reshape(int(dims[k]), 2, int(dims[k + 1])))
         pos += sz
-    return MPS(tensors, fid.value)
+    out = MPS(tensors, fid.value, logw.value, branches)
+    return (out, float(worst.value)) if margin else out
 
 
-def simulate(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None, checkpoints=None):
+def simulate(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None, checkpoints=None, seed=0,
+             state_index=0, trajectory=0, first_gate=0, margin=False):
     """MPS of circuit|0...0>, "MPSxGate" style: one SVD per two-qubit gate (ref :221).  ``max_bond``: at most that many singular
     values survive a gate -- the ``chi`` of pytket-cutensornet's ``Config`` (ref :141-144 is where it would go); the weight it
     costs goes into ``fidelity`` like any other truncation.
@@ -510,6 +542,11 @@ def simulate(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, va
     far, in the mixed-canonical gauge the run left it in; the last entry is ``simulate(circuit)`` of the numpy loop bit for bit.  It
     always runs the numpy loop (the native builder keeps no snapshots), whatever QK_NATIVE_BUILDER says.
 
+    A circuit with Kraus channels (op code 10) is run as one quantum trajectory: the branch of a drawn channel gate i comes from
+    ``engine.channel_uniform(seed, first_gate + i, trajectory, state_index)``, so a (state, trajectory) pair names its draws whatever
+    else is built with it, and a run resumed at gate ``first_gate`` draws what the uninterrupted one draws.  The result carries
+    ``logw`` and ``branches``; ``margin=True`` returns ``(result, margin)`` (see ``_simulate``).
+
     The matrices are small (tens to a few hundred rows): a multi-threaded BLAS spends its time waking
     threads (measured 24 s instead of 0.9 s per 60-qubit state on 8 cores), so the LAPACK calls run
     single-threaded here; parallelism is across states (``builder_pool.build_states``)."""
@@ -518,13 +555,13 @@ def simulate(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, va
     try:
         from threadpoolctl import threadpool_limits
     except ImportError:  # pragma: no cover - optional dependency
-        return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, checkpoints)
+        return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, checkpoints, seed, state_index, trajectory, first_gate, margin)
     with threadpool_limits(limits=1):
         if checkpoints is not None:
-            return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, checkpoints)
+            return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, checkpoints, seed, state_index, trajectory, first_gate, margin)
         if _use_native():
-            return simulate_native(circuit, truncation_fidelity, value_of_zero, max_bond)
-        return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond)
+            return simulate_native(circuit, truncation_fidelity, value_of_zero, max_bond, seed, state_index, trajectory, first_gate, margin)
+        return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, None, seed, state_index, trajectory, first_gate, margin)
 
 
 def simulate_many(circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, workers: int | None = None, progress=None, max_bond: int | None = None):
@@ -537,6 +574,7 @@ def simulate_many(circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_z
     import time
 
     circuits = list(circuits)
+    reject_channels(circuits, "simulate_many")
     if not circuits:
         return [], []
     if workers is None:
@@ -653,13 +691,35 @@ def _use_native() -> bool:
     return os.environ.get("QK_NATIVE_BUILDER", "1") != "0" and _native_builder() is not None
 
 
-def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: float, max_bond: int | None = None, checkpoints=None):
+def _trajectory_ids(seed, state_index, trajectory, first_gate):
+    from .engine import _seed_key
+
+    _seed_key(seed)
+    for name, v in (("state_index", state_index), ("trajectory", trajectory), ("first_gate", first_gate)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 1 << 32:
+            raise ValueError(f"{name} must be an int in 0 .. 2^32 - 1 (got {v!r})")
+    return int(seed), int(state_index), int(trajectory), int(first_gate)
+
+
+def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: float, max_bond: int | None = None, checkpoints=None, seed=0, state_index=0, trajectory=0,
+              first_gate=0, margin=False):
     """The numpy loop.  With ``checkpoints`` (validated gate counts) the return value is the list of snapshots: copies, the run itself
     is the one without them.  A circuit with a matrix table (``circuit.mat``, ``circuit.mats``) may hold op codes 8 and 9, a 2x2 on q0
     and a 4x4 on (q0, q0+1); ``ValueError`` for a table entry that is not unitary, an index outside the table or a gate outside
-    the register."""
+    the register.
+
+    A circuit with a channel table (``channel``, ``branch``, ``kraus``, ``n_kraus``) may hold op code 10, a one-qubit Kraus channel:
+    the centre is brought onto site q exactly, ``N = sum |A_q|^2``, ``p_k = sum |K_k A_q|^2``, ``tot = p_0 + .. + p_{m-1}``; the branch b
+    is ``branch[i]`` or, drawn, the first k with ``p_k > 0`` and ``u tot < p_0 + .. + p_k`` (none: the last k with ``p_k > 0``) for
+    ``u = engine.channel_uniform(seed, first_gate + i, trajectory, state_index)``; ``A_q <- (K_b / sqrt(p_b)) A_q`` and ``logw +=
+    log(p_b / N)``.  The result carries ``logw`` and ``branches``; with ``margin`` the return value is ``(result, margin)``, the
+    smallest ``|u tot - cum| / tot`` over the thresholds of all draws (inf without one).  ``ValueError`` naming the state and the gate
+    for an impossible outcome (``p_b`` 0 or not finite, ``tot`` 0 in a draw)."""
     n = circuit.n_qubits
-    mat, mats = check_matrix_gates(circuit.op, circuit.mat, circuit.mats)  # (None, None): no table, codes 8 and 9 are unknown
+    chan = check_channel_gates(circuit.op, circuit.q0, n, circuit.channel, circuit.branch, circuit.kraus, circuit.n_kraus)
+    mat, mats = check_matrix_gates(circuit.op, circuit.mat, circuit.mats, with_channels=chan is not None)  # (None, None): no table, codes 8 and 9 are unknown
+    seed, state_index, trajectory, first_gate = _trajectory_ids(seed, state_index, trajectory, first_gate)
+    logw, branches, worst = 0.0, [], np.inf
     for i, (o, q) in enumerate(zip(circuit.op.tolist(), circuit.q0.tolist())):
         if not 0 <= q < n - (1 if is_two_qubit(o) else 0):
             raise ValueError(f"gate {i} on a qubit outside the register of {n}")
@@ -680,7 +740,7 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
 
     for i, (o, q, a) in enumerate(zip(ops, qs, alphas)):
         if i in marks:  # i gates done
-            snaps.append(MPS([t.copy() for t in A], fidelity))
+            snaps.append(MPS([t.copy() for t in A], fidelity, logw, branches))
         if o == OP_H:
             t = A[q]
             A[q] = np.stack((t[:, 0] + t[:, 1], t[:, 0] - t[:, 1]), axis=1) * _SQRT_HALF
@@ -698,7 +758,7 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             t = A[q]
             A[q] = np.stack((m[0, 0] * t[:, 0] + m[0, 1] * t[:, 1], m[1, 0] * t[:, 0] + m[1, 1] * t[:, 1]), axis=1)
             continue
-        if not is_two_qubit(o):  # Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
+        if not is_two_qubit(o) and o != OP_K1:  # Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
             th = 0.5 * np.pi * a
             c, sn = np.cos(th), np.sin(th)
             m01, m10 = (-1j * sn, -1j * sn) if o == OP_RX else (-sn, sn)
@@ -706,19 +766,62 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             A[q] = np.stack((c * t[:, 0] + m01 * t[:, 1], m10 * t[:, 0] + c * t[:, 1]), axis=1)
             continue
 
-        # ---- two-qubit gate on (q, q+1): bring the orthogonality centre onto the pair
-        while centre < q:
+        # ---- two-qubit gate on (q, q+1): bring the orthogonality centre onto the pair; a channel on q: onto the site
+        lo, hi = (q, q) if o == OP_K1 else (q, q + 1)
+        while centre < lo:
             l, _, r = A[centre].shape
             qq, rr = _qr(A[centre].reshape(l * 2, r), mode="economic", check_finite=False)
             A[centre] = qq.reshape(l, 2, -1)
             A[centre + 1] = np.tensordot(rr, A[centre + 1], axes=(1, 0))
             centre += 1
-        while centre > q + 1:
+        while centre > hi:
             l, _, r = A[centre].shape
             qq, rr = _qr(A[centre].reshape(l, 2 * r).T, mode="economic", check_finite=False)
             A[centre] = qq.T.reshape(-1, 2, r)
             A[centre - 1] = np.tensordot(A[centre - 1], rr.T, axes=(2, 0))
             centre -= 1
+
+        if o == OP_K1:  # the channel step: the centre stays on q, the bonds do not change
+            from .engine import channel_uniform
+
+            c, forced = int(chan[0][i]), int(chan[1][i])
+            m = int(chan[3][c])
+            K = chan[2][c]
+            t = A[q]
+            t0, t1 = t[:, 0], t[:, 1]
+            N = float((t.real * t.real + t.imag * t.imag).sum())
+            p = []
+            for k in range(m):
+                y0, y1 = K[k, 0, 0] * t0 + K[k, 0, 1] * t1, K[k, 1, 0] * t0 + K[k, 1, 1] * t1
+                p.append(float((y0.real * y0.real + y0.imag * y0.imag + y1.real * y1.real + y1.imag * y1.imag).sum()))
+            tot = 0.0
+            for k in range(m):
+                tot += p[k]
+            where = f"state {state_index}, gate {first_gate + i}"
+            if forced >= 0:
+                b = forced
+            else:
+                if not (tot > 0.0 and np.isfinite(tot)):
+                    raise ValueError(f"simulate: {where}: the branch probabilities of the channel sum to {tot!r}")
+                u = float(channel_uniform(seed, first_gate + i, trajectory, state_index))
+                b, cum, last = -1, 0.0, -1
+                for k in range(m):
+                    cum += p[k]
+                    if k < m - 1:
+                        worst = min(worst, abs(u * tot - cum) / tot)
+                    if p[k] > 0.0:
+                        last = k
+                        if b < 0 and u * tot < cum:
+                            b = k
+                if b < 0:
+                    b = last
+            if not (p[b] > 0.0 and np.isfinite(p[b])):
+                raise ValueError(f"simulate: {where}: branch {b} of the channel has probability {p[b]!r} (an impossible outcome was post-selected?)")
+            Kb = K[b] / np.sqrt(p[b])
+            A[q] = np.stack((Kb[0, 0] * t0 + Kb[0, 1] * t1, Kb[1, 0] * t0 + Kb[1, 1] * t1), axis=1)
+            logw += float(np.log(p[b] / N))
+            branches.append(b)
+            continue
 
         l = A[q].shape[0]
         r = A[q + 1].shape[2]
@@ -762,6 +865,5 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             A[q] = (u[:, :keep] * s[None, :]).reshape(l, 2, keep)
             A[q + 1] = vh[:keep].reshape(keep, 2, r)
             centre = q
-    if checkpoints is not None:
-        return snaps + [MPS(A, fidelity)]
-    return MPS(A, fidelity)
+    out = snaps + [MPS(A, fidelity, logw, branches)] if checkpoints is not None else MPS(A, fidelity, logw, branches)
+    return (out, float(worst)) if margin else out
