@@ -91,6 +91,11 @@
 // The launch kinds, the layout of a state's scratch and of a chain's slot, the pair index, the sizes, the cut into batches and the
 // task lists are host-side planning, in qk_local_plan.h (tested on the CPU).  Every entry point runs on one driver: env_sizes,
 // env_tables (the batch's tables and the task lists of its plan) and env_run (upload, reverse, init, then the plan on the stream).
+// The chain families (strings, block, sample, amplitude, window) cut the chains of a state batch into chain batches below that:
+// chain_stage (qk_local_plan.h) owns the layout of a chain batch's device buffer -- the offsets, the slot bases and the host image
+// of its tables, chain_stage_max the room a cut needs behind the state batch -- and chain_run the loop over the chain batches of a
+// cut: per batch the family's task lists, the stage, the upload, the family's pointers and launches (each_launch walks a task list
+// and skips its empty launches), hipGetLastError, the synchronise.  batch_cap reads a QK_*_BATCH variable.
 #include "qk_host.h"
 #include "qk_local_plan.h"
 #include "qk_ring.h"
@@ -98,6 +103,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <vector>
 
@@ -833,6 +839,50 @@ int quarter_of_free(qk_ctx* c, const char* what, long long& budget) {
   return QK_OK;
 }
 
+// ---- the driver of a chain batch, shared by the five chain families (strings, block, sample, amplitude, window) -------------------
+// the launches of a task list that have tasks: launch(li, first task, grid)
+template <class Launch>
+void each_launch(const std::vector<long long>& first, Launch&& launch) {
+  for (size_t li = 0; li + 1 < first.size(); ++li)
+    if (first[li + 1] > first[li]) launch(li, first[li], dim3((unsigned)(first[li + 1] - first[li])));
+}
+struct ChainBatch {  // the chain batch at hand, as its family sees it: the chains [c0, c0 + nc) in the device buffer at base, offsets in st
+  char* base;
+  const ChainStage& st;
+  size_t c0, nc;
+  const std::vector<long long>& first;  // of its task list, per launch
+};
+using ChainLists = std::function<void(size_t c0, size_t nc, std::vector<Task2>& tasks, std::vector<long long>& first)>;
+using ChainHook = std::function<int(const ChainBatch&)>;
+// The chain batches of a cut, one after the other, in the device buffer at `base` (NULL: the start of the context's scratch, made
+// large enough here).  Per batch: the family's task lists, the stage (chain_stage), the upload of its table image on the context's
+// stream, `enqueue` -- the family sets its pointers from base + the offsets and enqueues its launches -- then `before_sync` (what
+// the family must still enqueue), the synchronise -- the staged tables are reused by the next batch -- and `after_sync` (what the
+// family reads back).
+int chain_run(qk_ctx* c, const char* what, char* base, const std::vector<ChainCol>& cols, const ChainCore& ch, const std::vector<size_t>& cstart, const long long width,
+              const ChainLists& lists, const std::function<void(const ChainBatch&)>& enqueue, const ChainHook& before_sync = nullptr, const ChainHook& after_sync = nullptr) {
+  std::vector<Task2> tasks;
+  std::vector<long long> first;
+  ChainStage st;
+  for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
+    const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
+    if (nc == 0) continue;
+    lists(c0, nc, tasks, first);
+    chain_stage(cols, ch, c0, c0 + nc, width, tasks, st);
+    if (!base) HIP_TRY_AS(what, c->local_scratch.ensure(st.total));
+    const ChainBatch b{base ? base : c->local_scratch.get<char>(), st, c0, nc, first};
+    HIP_TRY_AS(what, hipMemcpyAsync(b.base, st.image.data(), st.part, hipMemcpyHostToDevice, c->stream));
+    enqueue(b);
+    HIP_TRY_AS(what, hipGetLastError());
+    if (before_sync)
+      if (const int rc = before_sync(b)) return rc;
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+    if (after_sync)
+      if (const int rc = after_sync(b)) return rc;
+  }
+  return QK_OK;
+}
+
 // The local sweep of a set.  out1 = Bloch vectors [n_states][n_sites][3] (may be NULL when out2 is given), norms (may be NULL);
 // out2 = Pauli correlators of the pairs up to distance max_dist [n_states][n_pairs][4][4] (NULL: the one-qubit sweep alone).
 int local_sweep(qk_ctx* c, const qk_mps_set* set, const char* what, const char* range, double* out1, double* norms, double* out2, const int max_dist) {
@@ -910,11 +960,8 @@ int string_chains(qk_ctx* c, const qk_mps_set* set, const char* what, const char
     if (general) return qk_fail(QK_EINVAL, "%s: strings[%d][%d] = %d is above n_ops = %d (0 = identity, c = ops[c - 1])", what, (int)(bad / n), (int)(bad % n), strings[bad], n_ops);
     return qk_fail(QK_EINVAL, "%s: strings[%d][%d] = %d is not a Pauli code (0..3 = I, X, Y, Z)", what, (int)(bad / n), (int)(bad % n), strings[bad]);
   }
-  long long cap = 0;  // chains per batch; 0: the memory rule alone
-  if (const char* v = std::getenv(batch_var)) {
-    cap = std::atoll(v);
-    if (cap < 1) return qk_fail(QK_EINVAL, "%s: %s must be >= 1 (got \"%s\")", what, batch_var, v);
-  }
+  long long cap = 0;  // chains per batch
+  if (const int rc = batch_cap(what, batch_var, cap)) return rc;
   QkRangeGuard range_(range);
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
@@ -939,8 +986,6 @@ int string_chains(qk_ctx* c, const qk_mps_set* set, const char* what, const char
   if (const int rc = quarter_of_free(c, what, budget)) return rc;
   const std::vector<int> bstart = batch_cut(z.need, 0, budget / 2);
   const Plan plan = env_plan(n);
-  std::vector<Task2> tasks;
-  std::vector<long long> first;
   EnvBatch eb;
   for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
     const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
@@ -951,22 +996,9 @@ int string_chains(qk_ctx* c, const qk_mps_set* set, const char* what, const char
     if (general)
       for (long long& w : ch.weight) w += max_chunks;  // a chunk sum is (Re, Im)
     const std::vector<size_t> cstart = chain_cut(ch.weight, budget - eb.tot, cap);
-    struct ChainBytes { size_t cent, cstr, cbase, tasks, part, slots; size_t tab() const { return cent + cstr + cbase + tasks; } };
-    auto slot = [&](const size_t e) { return (long long)chain_size() * z.pmax[s0 + ch.cent[e]] * z.pmax[s0 + ch.cent[e]]; };
-    auto chain_bytes = [&](const size_t c0, const size_t c1) {
-      long long nt = 0, sl = 0;
-      for (size_t e = c0; e < c1; ++e) nt += ch.ntasks[e], sl += slot(e);
-      const size_t nc = c1 - c0;
-      return ChainBytes{al256(nc * sizeof(int32_t)), al256(nc * sizeof(int32_t)), al256(nc * sizeof(int64_t)), al256((size_t)nt * sizeof(int2)),
-                        al256(nc * max_chunks * vals * sizeof(double)), (size_t)sl * sizeof(double)};
-    };
-    size_t b_chain = 0;
-    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
-      const ChainBytes cbz = chain_bytes(cstart[cb], cstart[cb + 1]);
-      b_chain = std::max(b_chain, cbz.tab() + cbz.part + cbz.slots);
-    }
-    // one device buffer for the state batch: [tables | tasks | environments] then the chain batch's [tables | tasks | partials | slots]
-    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, b_chain)) return rc;
+    const std::vector<ChainCol> cols{{ch.cent.data(), sizeof(int32_t), 1}, {ch.cstr.data(), sizeof(int32_t), 1}};
+    const long long width = (long long)max_chunks * vals;  // of a chain's partial sums
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, chain_stage_max(cols, ch, cstart, width))) return rc;
     qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(eb.g, nb, dnorm.get<double>());
     HIP_TRY_AS(what, hipGetLastError());
     OpArgs qa{};
@@ -975,47 +1007,31 @@ int string_chains(qk_ctx* c, const qk_mps_set* set, const char* what, const char
     q.e = eb.g;
     q.strings = dstr.get<uint8_t>();
     q.supp = reinterpret_cast<const int32_t*>(dstr.get<char>() + b_str);
-    char* const cbase0 = eb.base + eb.used();
-    std::vector<char> cstage;
-    std::vector<int64_t> h_cbase;
-    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
-      const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
-      if (nc == 0) continue;
-      const ChainBytes cbz = chain_bytes(c0, c0 + nc);
-      h_cbase.resize(nc);
-      long long sl = 0;
-      for (size_t e = 0; e < nc; ++e) h_cbase[e] = sl, sl += slot(c0 + e);
-      chain_lists(z, s0, ch, c0, nc, strings, supp, tasks, first);
-      cstage.resize(cbz.tab());
-      std::memcpy(cstage.data(), ch.cent.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + cbz.cent, ch.cstr.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + cbz.cent + cbz.cstr, h_cbase.data(), nc * sizeof(int64_t));
-      std::memcpy(cstage.data() + cbz.cent + cbz.cstr + cbz.cbase, tasks.data(), tasks.size() * sizeof(int2));
-      q.cent = reinterpret_cast<const int32_t*>(cbase0);
-      q.cstr = reinterpret_cast<const int32_t*>(cbase0 + cbz.cent);
-      q.cbase = reinterpret_cast<const int64_t*>(cbase0 + cbz.cent + cbz.cstr);
-      const int2* d_ctasks = reinterpret_cast<const int2*>(cbase0 + cbz.cent + cbz.cstr + cbz.cbase);
-      q.part = reinterpret_cast<double*>(cbase0 + cbz.tab());
-      q.slots = reinterpret_cast<double*>(cbase0 + cbz.tab() + cbz.part);
-      HIP_TRY_AS(what, hipMemcpyAsync(cbase0, cstage.data(), cbz.tab(), hipMemcpyHostToDevice, c->stream));
-      for (size_t li = 0; li + 1 < first.size(); ++li) {
-        const int kind = CHAIN_KINDS[li % 4];
-        q.tasks = d_ctasks + first[li];
-        q.step = (int)(li / 4);
-        if (first[li + 1] <= first[li]) continue;
-        const dim3 grid((unsigned)(first[li + 1] - first[li]));
-        if (kind == STR_T) qk_str_gemm_kernel<false><<<grid, dim3(512), 0, c->stream>>>(q);
-        else if (kind == STR_X) qk_str_gemm_kernel<true><<<grid, dim3(512), 0, c->stream>>>(q);
-        else if (kind == STR_PAULI && !general) qk_str_pauli_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
-        else if (kind == STR_PAULI) qk_str_op_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(qa);
-        else if (!general) qk_str_close_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
-        else qk_str_closez_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(qa);
-      }
-      if (!general) qk_str_values_kernel<<<dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)nc, n_strings, dout.get<double>());
-      else qk_str_valuesz_kernel<<<dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)nc, n_strings, dout.get<double>());
-      HIP_TRY_AS(what, hipGetLastError());
-      HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
-    }
+    const int rc = chain_run(
+        c, what, eb.base + eb.used(), cols, ch, cstart, width,
+        [&](size_t c0, size_t nc, std::vector<Task2>& tasks, std::vector<long long>& first) { chain_lists(z, s0, ch, c0, nc, strings, supp, tasks, first); },
+        [&](const ChainBatch& b) {
+          q.cent = reinterpret_cast<const int32_t*>(b.base + b.st.col[0]);
+          q.cstr = reinterpret_cast<const int32_t*>(b.base + b.st.col[1]);
+          q.cbase = reinterpret_cast<const int64_t*>(b.base + b.st.col[2]);
+          const int2* d_ctasks = reinterpret_cast<const int2*>(b.base + b.st.tasks);
+          q.part = reinterpret_cast<double*>(b.base + b.st.part);
+          q.slots = reinterpret_cast<double*>(b.base + b.st.slots);
+          each_launch(b.first, [&](const size_t li, const long long t0, const dim3 grid) {
+            const int kind = CHAIN_KINDS[li % 4];
+            q.tasks = d_ctasks + t0;
+            q.step = (int)(li / 4);
+            if (kind == STR_T) qk_str_gemm_kernel<false><<<grid, dim3(512), 0, c->stream>>>(q);
+            else if (kind == STR_X) qk_str_gemm_kernel<true><<<grid, dim3(512), 0, c->stream>>>(q);
+            else if (kind == STR_PAULI && !general) qk_str_pauli_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+            else if (kind == STR_PAULI) qk_str_op_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(qa);
+            else if (!general) qk_str_close_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+            else qk_str_closez_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(qa);
+          });
+          if (!general) qk_str_values_kernel<<<dim3((unsigned)((b.nc + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)b.nc, n_strings, dout.get<double>());
+          else qk_str_valuesz_kernel<<<dim3((unsigned)((b.nc + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)b.nc, n_strings, dout.get<double>());
+        });
+    if (rc) return rc;
     HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   }
   if (general) {  // a value divides by <psi|psi> (a norm that is NaN marks its own row, as the Pauli strings do)
@@ -1300,11 +1316,8 @@ int blk_env_pass(qk_ctx* c, const char* what, BlkHostSet& h, const int side, con
 int block_run(qk_ctx* c, const char* what, const qk_mps_set* xset, const qk_mps_set* yset, const long long n_pairs, const int32_t* pairs, const int side, const int nw,
               const int32_t* widths, double* values_host, double* norms_host) {
   const int n = xset->n_sites;
-  long long cap = 0;  // pair chains per batch; 0: the memory rule alone
-  if (const char* v = std::getenv("QK_BLOCK_BATCH")) {
-    cap = std::atoll(v);
-    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_BLOCK_BATCH must be >= 1 (got \"%s\")", what, v);
-  }
+  long long cap = 0;  // pair chains per batch
+  if (const int rc = batch_cap(what, "QK_BLOCK_BATCH", cap)) return rc;
   if (n_pairs == 0) return QK_OK;
   QkRangeGuard range_("qk:block_values");
   HIP_TRY_AS(what, hipSetDevice(c->device));
@@ -1362,53 +1375,31 @@ int block_run(qk_ctx* c, const char* what, const qk_mps_set* xset, const qk_mps_
   q.x = side_of(hx), q.y = side_of(hy);
   q.widths = d_widths, q.kept = kept.get<double>();
   q.n_sites = n, q.side = side, q.n_widths = nw, q.max_chunks = max_chunks;
-  std::vector<Task2> tasks;
-  std::vector<long long> first;
-  std::vector<char> stage;
-  std::vector<int32_t> h_cpm;
-  std::vector<int64_t> h_cbase;
-  for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
-    const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
-    if (nc == 0) continue;
-    h_cpm.resize(nc), h_cbase.resize(nc);
-    long long sl = 0;
-    for (size_t e = 0; e < nc; ++e) {
-      h_cpm[e] = std::max(hx.z.pmax[pairs[2 * (c0 + e)]], hy.z.pmax[pairs[2 * (c0 + e) + 1]]);
-      h_cbase[e] = sl, sl += chains.slot[c0 + e];
-    }
-    blk_lists(hx.z, hy.z, pairs, c0, nc, side, plan, tasks, first);
-    // one device buffer for the pair batch: [pairs | P | slot bases | tasks | partial sums | slots]
-    const size_t b_pairs = al256(2 * nc * sizeof(int32_t)), b_cpm = al256(nc * sizeof(int32_t)), b_cbase = al256(nc * sizeof(int64_t));
-    const size_t b_tasks = al256(tasks.size() * sizeof(int2)), b_tab = b_pairs + b_cpm + b_cbase + b_tasks;
-    const size_t b_part = al256(nc * (size_t)nw * max_chunks * sizeof(double)), b_slots = (size_t)sl * sizeof(double);
-    HIP_TRY_AS(what, c->local_scratch.ensure(b_tab + b_part + b_slots));
-    char* const base = c->local_scratch.get<char>();
-    stage.assign(b_tab, 0);
-    std::memcpy(stage.data(), pairs + 2 * c0, 2 * nc * sizeof(int32_t));
-    std::memcpy(stage.data() + b_pairs, h_cpm.data(), nc * sizeof(int32_t));
-    std::memcpy(stage.data() + b_pairs + b_cpm, h_cbase.data(), nc * sizeof(int64_t));
-    std::memcpy(stage.data() + b_pairs + b_cpm + b_cbase, tasks.data(), tasks.size() * sizeof(int2));
-    q.pairs = reinterpret_cast<const int32_t*>(base);
-    q.cpm = reinterpret_cast<const int32_t*>(base + b_pairs);
-    q.cbase = reinterpret_cast<const int64_t*>(base + b_pairs + b_cpm);
-    const int2* d_tasks = reinterpret_cast<const int2*>(base + b_pairs + b_cpm + b_cbase);
-    q.part = reinterpret_cast<double*>(base + b_tab);
-    q.slots = reinterpret_cast<double*>(base + b_tab + b_part);
-    HIP_TRY_AS(what, hipMemcpyAsync(base, stage.data(), b_tab, hipMemcpyHostToDevice, c->stream));
-    for (size_t li = 0; li < plan.size(); ++li) {
-      const int kind = plan[li].kind;
-      q.tasks = d_tasks + first[li];
-      q.step = plan[li].step, q.cut = plan[li].cut;
-      if (first[li + 1] <= first[li]) continue;
-      const dim3 grid((unsigned)(first[li + 1] - first[li]));
-      if (kind == BLK_RED) qk_blk_reduce_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
-      else if (conj_b(kind)) qk_blk_gemm_kernel<true><<<grid, dim3(512), 0, c->stream>>>(q, kind);
-      else qk_blk_gemm_kernel<false><<<grid, dim3(512), 0, c->stream>>>(q, kind);
-    }
-    qk_blk_values_kernel<<<dim3((unsigned)((nc * nw + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)nc, (long long)c0, n_pairs, dout.get<double>());
-    HIP_TRY_AS(what, hipGetLastError());
-    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
-  }
+  std::vector<int32_t> h_cpm((size_t)n_pairs);  // P of every pair chain
+  for (long long e = 0; e < n_pairs; ++e) h_cpm[e] = std::max(hx.z.pmax[pairs[2 * e]], hy.z.pmax[pairs[2 * e + 1]]);
+  const std::vector<ChainCol> cols{{pairs, sizeof(int32_t), 2}, {h_cpm.data(), sizeof(int32_t), 1}};
+  // no state batch is around a pair batch: its buffer is the start of the context's scratch
+  const int rc = chain_run(
+      c, what, nullptr, cols, chains, cstart, (long long)nw * max_chunks,
+      [&](size_t c0, size_t nc, std::vector<Task2>& tasks, std::vector<long long>& first) { blk_lists(hx.z, hy.z, pairs, c0, nc, side, plan, tasks, first); },
+      [&](const ChainBatch& b) {
+        q.pairs = reinterpret_cast<const int32_t*>(b.base + b.st.col[0]);
+        q.cpm = reinterpret_cast<const int32_t*>(b.base + b.st.col[1]);
+        q.cbase = reinterpret_cast<const int64_t*>(b.base + b.st.col[2]);
+        const int2* d_tasks = reinterpret_cast<const int2*>(b.base + b.st.tasks);
+        q.part = reinterpret_cast<double*>(b.base + b.st.part);
+        q.slots = reinterpret_cast<double*>(b.base + b.st.slots);
+        each_launch(b.first, [&](const size_t li, const long long t0, const dim3 grid) {
+          const int kind = plan[li].kind;
+          q.tasks = d_tasks + t0;
+          q.step = plan[li].step, q.cut = plan[li].cut;
+          if (kind == BLK_RED) qk_blk_reduce_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+          else if (conj_b(kind)) qk_blk_gemm_kernel<true><<<grid, dim3(512), 0, c->stream>>>(q, kind);
+          else qk_blk_gemm_kernel<false><<<grid, dim3(512), 0, c->stream>>>(q, kind);
+        });
+        qk_blk_values_kernel<<<dim3((unsigned)((b.nc * nw + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)b.nc, (long long)b.c0, n_pairs, dout.get<double>());
+      });
+  if (rc) return rc;
   HIP_TRY_AS(what, hipMemcpy(values_host, dout.get(), (size_t)nw * n_pairs * sizeof(double), hipMemcpyDeviceToHost));
   if (norms_host) HIP_TRY_AS(what, hipMemcpy(norms_host, hx.dnorm.get(), (size_t)xset->n_states * sizeof(double), hipMemcpyDeviceToHost));
   return QK_OK;
@@ -1627,11 +1618,8 @@ int sample_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_shots, const ui
   if (bases)
     if (const long long bad = smp_bad_basis(bases, (long long)n_shots * n); bad >= 0)
       return qk_fail(QK_EINVAL, "%s: bases[%lld][%lld] = %d is not a basis code (1..3 = X, Y, Z)", what, bad / n, bad % n, bases[bad]);
-  long long cap = 0;  // shot chains per batch; 0: the memory rule alone
-  if (const char* v = std::getenv("QK_SAMPLE_BATCH")) {
-    cap = std::atoll(v);
-    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_SAMPLE_BATCH must be >= 1 (got \"%s\")", what, v);
-  }
+  long long cap = 0;  // shot chains per batch
+  if (const int rc = batch_cap(what, "QK_SAMPLE_BATCH", cap)) return rc;
   QkRangeGuard range_("qk:sample");
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
@@ -1652,10 +1640,6 @@ int sample_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_shots, const ui
   if (const int rc = quarter_of_free(c, what, budget)) return rc;
   const std::vector<int> bstart = batch_cut(z.need, 0, budget / 2);
   const Plan plan = sample_env_plan(n);
-  std::vector<Task2> tasks;
-  std::vector<long long> first;
-  std::vector<char> cstage;
-  std::vector<int64_t> h_cbase;
   std::vector<int32_t> h_bad;
   EnvBatch eb;
   for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
@@ -1663,66 +1647,47 @@ int sample_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_shots, const ui
     env_tables(z, plan, s0, nb, 0, eb);
     const SmpChains ch = list_smp_chains(z, s0, nb, n_shots, SMP_TILE);
     const std::vector<size_t> cstart = chain_cut(ch.weight, budget - eb.tot, cap);
-    struct ChainBytes { size_t i32, cbase, tasks, slots; size_t tab() const { return 4 * i32 + cbase + tasks; } };  // cent | shot0 | rows | bad | cbase | tasks
-    auto chain_bytes = [&](const size_t c0, const size_t c1) {
-      long long nt = 0, sl = 0;
-      for (size_t e = c0; e < c1; ++e) nt += ch.ntasks[e], sl += ch.slot[e];
-      return ChainBytes{al256((c1 - c0) * sizeof(int32_t)), al256((c1 - c0) * sizeof(int64_t)), al256((size_t)nt * sizeof(int2)), (size_t)sl * sizeof(double)};
-    };
-    size_t b_chain = 0;
-    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
-      const ChainBytes cbz = chain_bytes(cstart[cb], cstart[cb + 1]);
-      b_chain = std::max(b_chain, cbz.tab() + cbz.slots);
-    }
-    // one device buffer for the state batch: [tables | tasks | environments] then the chain batch's [tables | tasks | slots]
-    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, b_chain)) return rc;
+    // bad: the device raises a chain's entry where a shot has no outcome to draw, and the host reads the column back
+    const std::vector<ChainCol> cols{{ch.cent.data(), sizeof(int32_t), 1}, {ch.shot0.data(), sizeof(int32_t), 1}, {ch.rows.data(), sizeof(int32_t), 1}, {nullptr, sizeof(int32_t), 1}};
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, chain_stage_max(cols, ch, cstart, 0))) return rc;
     SmpArgs q{};
     q.e = eb.g;
     q.bases = bases ? dbases.get<uint8_t>() : nullptr;
     q.bits = dbits.get<uint8_t>(), q.logp = dlogp.get<double>();
     q.seed = seed, q.first_state = first_state, q.n_shots = n_shots;
-    char* const cbase0 = eb.base + eb.used();
-    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
-      const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
-      if (nc == 0) continue;
-      const ChainBytes cbz = chain_bytes(c0, c0 + nc);
-      h_cbase.resize(nc);
-      long long sl = 0;
-      for (size_t e = 0; e < nc; ++e) h_cbase[e] = sl, sl += ch.slot[c0 + e];
-      smp_lists(z, s0, ch, c0, nc, tasks, first);
-      cstage.assign(cbz.tab(), 0);
-      std::memcpy(cstage.data(), ch.cent.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + cbz.i32, ch.shot0.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + 2 * cbz.i32, ch.rows.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + 4 * cbz.i32, h_cbase.data(), nc * sizeof(int64_t));
-      std::memcpy(cstage.data() + 4 * cbz.i32 + cbz.cbase, tasks.data(), tasks.size() * sizeof(int2));
-      q.cent = reinterpret_cast<const int32_t*>(cbase0);
-      q.shot0 = reinterpret_cast<const int32_t*>(cbase0 + cbz.i32);
-      q.rows = reinterpret_cast<const int32_t*>(cbase0 + 2 * cbz.i32);
-      q.bad = reinterpret_cast<int32_t*>(cbase0 + 3 * cbz.i32);
-      q.cbase = reinterpret_cast<const int64_t*>(cbase0 + 4 * cbz.i32);
-      const int2* d_ctasks = reinterpret_cast<const int2*>(cbase0 + 4 * cbz.i32 + cbz.cbase);
-      q.slots = reinterpret_cast<double*>(cbase0 + cbz.tab());
-      HIP_TRY_AS(what, hipMemcpyAsync(cbase0, cstage.data(), cbz.tab(), hipMemcpyHostToDevice, c->stream));
-      qk_smp_init_kernel<<<dim3((unsigned)nc), dim3(256), 0, c->stream>>>(q);
-      for (size_t li = 0; li + 1 < first.size(); ++li) {
-        const int kind = SMP_KINDS[li % 4];
-        q.tasks = d_ctasks + first[li];
-        q.step = (int)(li / 4);
-        if (first[li + 1] <= first[li]) continue;
-        const dim3 grid((unsigned)(first[li + 1] - first[li]));
-        if (kind >= 0) qk_smp_gemm_kernel<<<grid, dim3(512), 0, c->stream>>>(q, kind);
-        else if (kind == SMP_ROT) qk_smp_rotate_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
-        else qk_smp_draw_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
-      }
-      HIP_TRY_AS(what, hipGetLastError());
-      h_bad.resize(nc);
-      HIP_TRY_AS(what, hipMemcpyAsync(h_bad.data(), q.bad, nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
-      for (size_t e = 0; e < nc; ++e)
-        if (h_bad[e])
-          return qk_fail(QK_EDEVICE, "%s: state %d has a shot whose outcome probabilities sum to 0 or are not finite (a state of norm 0?)", what, s0 + ch.cent[c0 + e]);
-    }
+    const int rc = chain_run(
+        c, what, eb.base + eb.used(), cols, ch, cstart, 0,
+        [&](size_t c0, size_t nc, std::vector<Task2>& tasks, std::vector<long long>& first) { smp_lists(z, s0, ch, c0, nc, tasks, first); },
+        [&](const ChainBatch& b) {
+          q.cent = reinterpret_cast<const int32_t*>(b.base + b.st.col[0]);
+          q.shot0 = reinterpret_cast<const int32_t*>(b.base + b.st.col[1]);
+          q.rows = reinterpret_cast<const int32_t*>(b.base + b.st.col[2]);
+          q.bad = reinterpret_cast<int32_t*>(b.base + b.st.col[3]);
+          q.cbase = reinterpret_cast<const int64_t*>(b.base + b.st.col[4]);
+          const int2* d_ctasks = reinterpret_cast<const int2*>(b.base + b.st.tasks);
+          q.slots = reinterpret_cast<double*>(b.base + b.st.slots);
+          qk_smp_init_kernel<<<dim3((unsigned)b.nc), dim3(256), 0, c->stream>>>(q);
+          each_launch(b.first, [&](const size_t li, const long long t0, const dim3 grid) {
+            const int kind = SMP_KINDS[li % 4];
+            q.tasks = d_ctasks + t0;
+            q.step = (int)(li / 4);
+            if (kind >= 0) qk_smp_gemm_kernel<<<grid, dim3(512), 0, c->stream>>>(q, kind);
+            else if (kind == SMP_ROT) qk_smp_rotate_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+            else qk_smp_draw_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+          });
+        },
+        [&](const ChainBatch& b) {  // the device wrote the bad column: back to the host behind the launches
+          h_bad.resize(b.nc);
+          HIP_TRY_AS(what, hipMemcpyAsync(h_bad.data(), q.bad, b.nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+          return (int)QK_OK;
+        },
+        [&](const ChainBatch& b) {
+          for (size_t e = 0; e < b.nc; ++e)
+            if (h_bad[e])
+              return qk_fail(QK_EDEVICE, "%s: state %d has a shot whose outcome probabilities sum to 0 or are not finite (a state of norm 0?)", what, s0 + ch.cent[b.c0 + e]);
+          return (int)QK_OK;
+        });
+    if (rc) return rc;
     HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   }
   HIP_TRY_AS(what, hipMemcpy(bits, dbits.get(), n_rows * n, hipMemcpyDeviceToHost));
@@ -1873,11 +1838,8 @@ int amplitudes_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, co
   if (bases)
     if (const long long bad = smp_bad_basis(bases, row_bytes); bad >= 0)
       return qk_fail(QK_EINVAL, "%s: bases[%lld][%lld] = %d is not a basis code (1..3 = X, Y, Z)", what, bad / n, bad % n, bases[bad]);
-  long long cap = 0;  // amplitude chains per batch; 0: the memory rule alone
-  if (const char* v = std::getenv("QK_AMP_BATCH")) {
-    cap = std::atoll(v);
-    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_AMP_BATCH must be >= 1 (got \"%s\")", what, v);
-  }
+  long long cap = 0;  // amplitude chains per batch
+  if (const int rc = batch_cap(what, "QK_AMP_BATCH", cap)) return rc;
   QkRangeGuard range_("qk:amplitudes");
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
@@ -1904,29 +1866,14 @@ int amplitudes_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, co
   if (const int rc = quarter_of_free(c, what, budget)) return rc;
   const std::vector<int> bstart = batch_cut(z.need, 0, budget / 2);
   const Plan plan = want_norm ? env_plan(n) : Plan{};
-  std::vector<Task2> tasks;
-  std::vector<long long> first;
-  std::vector<char> cstage;
-  std::vector<int64_t> h_cbase;
   EnvBatch eb;
   for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
     const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
     env_tables(z, plan, s0, nb, 0, eb);
     const SmpChains ch = list_amp_chains(z, s0, nb, n_strings, AMP_TILE);
     const std::vector<size_t> cstart = chain_cut(ch.weight, budget - eb.tot, cap);
-    struct ChainBytes { size_t i32, cbase, tasks, slots; size_t tab() const { return 3 * i32 + cbase + tasks; } };  // cent | str0 | rows | cbase | tasks
-    auto chain_bytes = [&](const size_t c0, const size_t c1) {
-      long long nt = 0, sl = 0;
-      for (size_t e = c0; e < c1; ++e) nt += ch.ntasks[e], sl += ch.slot[e];
-      return ChainBytes{al256((c1 - c0) * sizeof(int32_t)), al256((c1 - c0) * sizeof(int64_t)), al256((size_t)nt * sizeof(int2)), (size_t)sl * sizeof(double)};
-    };
-    size_t b_chain = 0;
-    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
-      const ChainBytes cbz = chain_bytes(cstart[cb], cstart[cb + 1]);
-      b_chain = std::max(b_chain, cbz.tab() + cbz.slots);
-    }
-    // one device buffer for the state batch: [tables | tasks | scratch] then the chain batch's [tables | tasks | slots]
-    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, b_chain)) return rc;
+    const std::vector<ChainCol> cols{{ch.cent.data(), sizeof(int32_t), 1}, {ch.shot0.data(), sizeof(int32_t), 1}, {ch.rows.data(), sizeof(int32_t), 1}};
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, chain_stage_max(cols, ch, cstart, 0))) return rc;
     if (want_norm) qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(eb.g, nb, dnorm.get<double>());
     HIP_TRY_AS(what, hipGetLastError());
     AmpArgs q{};
@@ -1935,40 +1882,25 @@ int amplitudes_run(qk_ctx* c, const qk_mps_set* set, const int32_t n_strings, co
     q.bases = bases ? dbases.get<uint8_t>() : nullptr;
     q.mant = dmant.get<double>(), q.expo = dexpo.get<int32_t>();
     q.n_strings = n_strings, q.per_state = bits_per_state;
-    char* const cbase0 = eb.base + eb.used();
-    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
-      const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
-      if (nc == 0) continue;
-      const ChainBytes cbz = chain_bytes(c0, c0 + nc);
-      h_cbase.resize(nc);
-      long long sl = 0;
-      for (size_t e = 0; e < nc; ++e) h_cbase[e] = sl, sl += ch.slot[c0 + e];
-      amp_lists(z, s0, ch, c0, nc, tasks, first);
-      cstage.assign(cbz.tab(), 0);
-      std::memcpy(cstage.data(), ch.cent.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + cbz.i32, ch.shot0.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + 2 * cbz.i32, ch.rows.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + 3 * cbz.i32, h_cbase.data(), nc * sizeof(int64_t));
-      std::memcpy(cstage.data() + 3 * cbz.i32 + cbz.cbase, tasks.data(), tasks.size() * sizeof(int2));
-      q.cent = reinterpret_cast<const int32_t*>(cbase0);
-      q.str0 = reinterpret_cast<const int32_t*>(cbase0 + cbz.i32);
-      q.rows = reinterpret_cast<const int32_t*>(cbase0 + 2 * cbz.i32);
-      q.cbase = reinterpret_cast<const int64_t*>(cbase0 + 3 * cbz.i32);
-      const int2* d_ctasks = reinterpret_cast<const int2*>(cbase0 + 3 * cbz.i32 + cbz.cbase);
-      q.slots = reinterpret_cast<double*>(cbase0 + cbz.tab());
-      HIP_TRY_AS(what, hipMemcpyAsync(cbase0, cstage.data(), cbz.tab(), hipMemcpyHostToDevice, c->stream));
-      qk_amp_init_kernel<<<dim3((unsigned)nc), dim3(256), 0, c->stream>>>(q);
-      for (size_t li = 0; li + 1 < first.size(); ++li) {
-        q.tasks = d_ctasks + first[li];
-        q.step = (int)(li / 2);
-        if (first[li + 1] <= first[li]) continue;
-        const dim3 grid((unsigned)(first[li + 1] - first[li]));
-        if (AMP_KINDS[li % 2] == AMP_W) qk_amp_gemm_kernel<<<grid, dim3(512), 0, c->stream>>>(q);
-        else qk_amp_pick_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
-      }
-      HIP_TRY_AS(what, hipGetLastError());
-      HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
-    }
+    const int rc = chain_run(
+        c, what, eb.base + eb.used(), cols, ch, cstart, 0,
+        [&](size_t c0, size_t nc, std::vector<Task2>& tasks, std::vector<long long>& first) { amp_lists(z, s0, ch, c0, nc, tasks, first); },
+        [&](const ChainBatch& b) {
+          q.cent = reinterpret_cast<const int32_t*>(b.base + b.st.col[0]);
+          q.str0 = reinterpret_cast<const int32_t*>(b.base + b.st.col[1]);
+          q.rows = reinterpret_cast<const int32_t*>(b.base + b.st.col[2]);
+          q.cbase = reinterpret_cast<const int64_t*>(b.base + b.st.col[3]);
+          const int2* d_ctasks = reinterpret_cast<const int2*>(b.base + b.st.tasks);
+          q.slots = reinterpret_cast<double*>(b.base + b.st.slots);
+          qk_amp_init_kernel<<<dim3((unsigned)b.nc), dim3(256), 0, c->stream>>>(q);
+          each_launch(b.first, [&](const size_t li, const long long t0, const dim3 grid) {
+            q.tasks = d_ctasks + t0;
+            q.step = (int)(li / 2);
+            if (AMP_KINDS[li % 2] == AMP_W) qk_amp_gemm_kernel<<<grid, dim3(512), 0, c->stream>>>(q);
+            else qk_amp_pick_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+          });
+        });
+    if (rc) return rc;
     HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   }
   HIP_TRY_AS(what, hipMemcpy(mant, dmant.get(), n_rows * 2 * sizeof(double), hipMemcpyDeviceToHost));
@@ -2168,11 +2100,8 @@ int window_rdms(qk_ctx* c, const qk_mps_set* set, const int32_t width, const int
     for (int a = 0; a + w <= n; ++a) starts.push_back(a);
   }
   const int nw = (int)starts.size();
-  long long cap = 0;  // chains per batch; 0: the memory rule alone
-  if (const char* v = std::getenv("QK_WINDOW_BATCH")) {
-    cap = std::atoll(v);
-    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_WINDOW_BATCH must be >= 1 (got \"%s\")", what, v);
-  }
+  long long cap = 0;  // window chains per batch
+  if (const int rc = batch_cap(what, "QK_WINDOW_BATCH", cap)) return rc;
   QkRangeGuard range_("qk:window_rdms");
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
@@ -2192,72 +2121,42 @@ int window_rdms(qk_ctx* c, const qk_mps_set* set, const int32_t width, const int
   if (const int rc = quarter_of_free(c, what, budget)) return rc;
   const std::vector<int> bstart = batch_cut(z.need, 0, budget / 2);
   const Plan plan = env_plan(n), wplan = win_plan(w);
-  std::vector<Task2> tasks;
-  std::vector<long long> first;
   EnvBatch eb;
   for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
     const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
     env_tables(z, plan, s0, nb, 0, eb);
     const WinChains ch = list_win_chains(z, s0, nb, w, nw, starts.data());
     const std::vector<size_t> cstart = chain_cut(ch.weight, budget - eb.tot, cap);
-    struct ChainBytes { size_t cent, cwin, cbase, tasks, part, slots; size_t tab() const { return cent + cwin + cbase + tasks; } };
-    auto chain_bytes = [&](const size_t c0, const size_t c1) {
-      long long nt = 0, sl = 0;
-      for (size_t e = c0; e < c1; ++e) nt += ch.ntasks[e], sl += ch.slot[e];
-      const size_t nc = c1 - c0;
-      return ChainBytes{al256(nc * sizeof(int32_t)), al256(nc * sizeof(int32_t)), al256(nc * sizeof(int64_t)), al256((size_t)nt * sizeof(int2)),
-                        al256(nc * max_chunks * nvals * sizeof(double)), (size_t)sl * sizeof(double)};
-    };
-    size_t b_chain = 0;
-    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
-      const ChainBytes cbz = chain_bytes(cstart[cb], cstart[cb + 1]);
-      b_chain = std::max(b_chain, cbz.tab() + cbz.part + cbz.slots);
-    }
-    // one device buffer for the state batch: [tables | tasks | environments] then the chain batch's [tables | tasks | partials | slots]
-    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, b_chain)) return rc;
+    const std::vector<ChainCol> cols{{ch.cent.data(), sizeof(int32_t), 1}, {ch.cwin.data(), sizeof(int32_t), 1}};
+    const long long width = (long long)max_chunks * nvals;  // of a chain's partial sums
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, chain_stage_max(cols, ch, cstart, width))) return rc;
     qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(eb.g, nb, dnorm.get<double>());
     HIP_TRY_AS(what, hipGetLastError());
     WinArgs q{};
     q.e = eb.g;
     q.starts = dstarts.get<int32_t>();
     q.width = w, q.n_windows = nw;
-    char* const cbase0 = eb.base + eb.used();
-    std::vector<char> cstage;
-    std::vector<int64_t> h_cbase;
-    for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) {
-      const size_t c0 = cstart[cb], nc = cstart[cb + 1] - c0;
-      if (nc == 0) continue;
-      const ChainBytes cbz = chain_bytes(c0, c0 + nc);
-      h_cbase.resize(nc);
-      long long sl = 0;
-      for (size_t e = 0; e < nc; ++e) h_cbase[e] = sl, sl += ch.slot[c0 + e];
-      win_lists(z, s0, ch, c0, nc, w, starts.data(), tasks, first);
-      cstage.assign(cbz.tab(), 0);
-      std::memcpy(cstage.data(), ch.cent.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + cbz.cent, ch.cwin.data() + c0, nc * sizeof(int32_t));
-      std::memcpy(cstage.data() + cbz.cent + cbz.cwin, h_cbase.data(), nc * sizeof(int64_t));
-      std::memcpy(cstage.data() + cbz.cent + cbz.cwin + cbz.cbase, tasks.data(), tasks.size() * sizeof(int2));
-      q.cent = reinterpret_cast<const int32_t*>(cbase0);
-      q.cwin = reinterpret_cast<const int32_t*>(cbase0 + cbz.cent);
-      q.cbase = reinterpret_cast<const int64_t*>(cbase0 + cbz.cent + cbz.cwin);
-      const int2* d_ctasks = reinterpret_cast<const int2*>(cbase0 + cbz.cent + cbz.cwin + cbz.cbase);
-      q.part = reinterpret_cast<double*>(cbase0 + cbz.tab());
-      q.slots = reinterpret_cast<double*>(cbase0 + cbz.tab() + cbz.part);
-      HIP_TRY_AS(what, hipMemcpyAsync(cbase0, cstage.data(), cbz.tab(), hipMemcpyHostToDevice, c->stream));
-      for (size_t li = 0; li < wplan.size(); ++li) {
-        const int kind = wplan[li].first;
-        q.tasks = d_ctasks + first[li];
-        q.step = wplan[li].second;
-        if (first[li + 1] <= first[li]) continue;
-        const dim3 grid((unsigned)(first[li + 1] - first[li]));
-        if (kind >= 0) qk_win_gemm_kernel<<<grid, dim3(512), 0, c->stream>>>(q, kind);
-        else qk_win_close_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
-      }
-      const long long nv = (long long)nc * win_pairs(w);
-      qk_win_rho_kernel<<<dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream>>>(q, (long long)nc, dout.get<double>());
-      HIP_TRY_AS(what, hipGetLastError());
-      HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staged tables are reused by the next batch
-    }
+    const int rc = chain_run(
+        c, what, eb.base + eb.used(), cols, ch, cstart, width,
+        [&](size_t c0, size_t nc, std::vector<Task2>& tasks, std::vector<long long>& first) { win_lists(z, s0, ch, c0, nc, w, starts.data(), tasks, first); },
+        [&](const ChainBatch& b) {
+          q.cent = reinterpret_cast<const int32_t*>(b.base + b.st.col[0]);
+          q.cwin = reinterpret_cast<const int32_t*>(b.base + b.st.col[1]);
+          q.cbase = reinterpret_cast<const int64_t*>(b.base + b.st.col[2]);
+          const int2* d_ctasks = reinterpret_cast<const int2*>(b.base + b.st.tasks);
+          q.part = reinterpret_cast<double*>(b.base + b.st.part);
+          q.slots = reinterpret_cast<double*>(b.base + b.st.slots);
+          each_launch(b.first, [&](const size_t li, const long long t0, const dim3 grid) {
+            const int kind = wplan[li].first;
+            q.tasks = d_ctasks + t0;
+            q.step = wplan[li].second;
+            if (kind >= 0) qk_win_gemm_kernel<<<grid, dim3(512), 0, c->stream>>>(q, kind);
+            else qk_win_close_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(q);
+          });
+          const long long nv = (long long)b.nc * win_pairs(w);
+          qk_win_rho_kernel<<<dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream>>>(q, (long long)b.nc, dout.get<double>());
+        });
+    if (rc) return rc;
     HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
   }
   std::vector<double> h_norm((size_t)ns);
@@ -2714,11 +2613,8 @@ int shadow_hist(qk_ctx* c, const int32_t n, const int32_t nx, const int32_t shot
     const int i = pairs[2 * e], j = pairs[2 * e + 1];
     if (i < 0 || i >= nx || j < 0 || j >= ny) return qk_fail(QK_EINVAL, "%s: pairs[%lld] is (%d, %d), the tables hold %d x %d states", what, e, i, j, nx, ny);
   }
-  long long cap = 0;  // pairs per batch; 0: the memory rule alone
-  if (const char* v = std::getenv("QK_SHADOW_BATCH")) {
-    cap = std::atoll(v);
-    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_SHADOW_BATCH must be >= 1 (got \"%s\")", what, v);
-  }
+  long long cap = 0;  // pairs per batch
+  if (const int rc = batch_cap(what, "QK_SHADOW_BATCH", cap)) return rc;
   QkRangeGuard range_("qk:shadow_hist");
   HIP_TRY_AS(what, hipSetDevice(c->device));
   HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
@@ -2877,11 +2773,8 @@ int shot_strings(qk_ctx* c, const int32_t n, const int32_t ns, const int32_t sho
   if (shots < 1) return qk_fail(QK_EINVAL, "%s: shots must be >= 1 (got %d)", what, shots);
   if (m < 1) return qk_fail(QK_EINVAL, "%s: n_strings must be >= 1 (got %d)", what, m);
   if (per_state != 0 && per_state != 1) return qk_fail(QK_EINVAL, "%s: bases_per_state must be 0 or 1 (got %d)", what, per_state);
-  long long cap = 0;  // strings per batch; 0: the memory rule alone
-  if (const char* v = std::getenv("QK_SHOT_STRINGS_BATCH")) {
-    cap = std::atoll(v);
-    if (cap < 1) return qk_fail(QK_EINVAL, "%s: QK_SHOT_STRINGS_BATCH must be >= 1 (got \"%s\")", what, v);
-  }
+  long long cap = 0;  // strings per batch
+  if (const int rc = batch_cap(what, "QK_SHOT_STRINGS_BATCH", cap)) return rc;
   const int groups = shk_groups(n), words = shk_words(n), sw = sst_words(n);
   // the string records, whole blocks of them: what lies beyond the last string is the identity
   std::vector<uint32_t> srec((size_t)sst_blocks(m) * SST_BLOCK * sw, 0u);

@@ -1,6 +1,7 @@
 // qk_local_plan.h -- the host-side plan of the local sweeps (qk_local.hip): the launch kinds, the scratch layout, the pair index, the
 // sizes and the cut into state batches, the tables and task lists of a batch, the plans of the entry points, the chain side of the
-// Pauli strings, of the block kernels, of the sampler, of the amplitude chains and of the k-qubit windows, the integer side of the shot-based block overlaps , of the shadow kernel's shot-pair histograms and of the Pauli strings estimated from shots.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
+// Pauli strings, of the block kernels, of the sampler, of the amplitude chains and of the k-qubit windows, the device buffer of a chain
+// batch (chain_stage, tests/host_san/chain_stage_main.cpp) and the batch cap of the environment (batch_cap), the integer side of the shot-based block overlaps , of the shadow kernel's shot-pair histograms and of the Pauli strings estimated from shots.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
 // -fsanitize=address,undefined); the few functions the kernels also call are QK_HD.
 #pragma once
 #include "qk_plan.h"
@@ -9,6 +10,8 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <utility>
 #include <vector>
@@ -278,9 +281,11 @@ inline int chain_task_count(const int kind, const int k, const int32_t* p, const
   if (k < a || k > b || (kind == STR_PAULI && !codes[k]) || (kind == STR_CLOSE && k != b)) return 0;
   return task_count(kind, k, p, n, 1);
 }
-struct Chains {  // the chains of a state batch, state-major in string order
-  std::vector<int32_t> cent, cstr;       // chain -> batch entry, string
-  std::vector<long long> ntasks, weight;  // its tasks over all launches; its doubles: slot, partial sums, tasks and table entries
+struct ChainCore {  // what every chain list has, per chain
+  std::vector<long long> slot, ntasks, weight;  // doubles of its slot; its tasks over all launches; its doubles: slot, partial sums, tasks and table entries
+};
+struct Chains : ChainCore {  // the chains of a state batch, state-major in string order
+  std::vector<int32_t> cent, cstr;  // chain -> batch entry, string
 };
 inline Chains list_chains(const EnvSizes& z, const int s0, const int nb, const int n_strings, const uint8_t* strings, const std::vector<int32_t>& supp) {
   const int n = z.n_sites;
@@ -292,7 +297,8 @@ inline Chains list_chains(const EnvSizes& z, const int s0, const int nb, const i
         for (int k = supp[2 * m]; k <= supp[2 * m + 1]; ++k)
           for (const int kind : CHAIN_KINDS) nt += chain_task_count(kind, k, &z.pad[(size_t)(s0 + i) * (n + 1)], strings + (size_t)m * n, supp[2 * m], supp[2 * m + 1], n);
         c.cent.push_back(i), c.cstr.push_back(m), c.ntasks.push_back(nt);
-        c.weight.push_back((long long)chain_size() * z.pmax[s0 + i] * z.pmax[s0 + i] + z.max_chunks + nt + 2);
+        c.slot.push_back((long long)chain_size() * z.pmax[s0 + i] * z.pmax[s0 + i]);
+        c.weight.push_back(c.slot.back() + z.max_chunks + nt + 2);
       }
   return c;
 }
@@ -324,6 +330,73 @@ inline void chain_lists(const EnvSizes& z, const int s0, const Chains& c, const 
       }
     }
   first.push_back((long long)tasks.size());
+}
+
+// ---- the device buffer of a chain batch -------------------------------------------------------------------------------------------
+// [the family's table columns, in the order listed | slot bases (int64) | tasks | partial sums | slots], every region but the slots
+// rounded up with al256; the part before the partial sums is staged on the host and uploaded.  The families:
+//   strings    cent, cstr                      | cbase | tasks | part  | slots
+//   block      pairs (2 per chain), cpm        | cbase | tasks | part  | slots
+//   sample     cent, shot0, rows, bad (zeros)  | cbase | tasks |       | slots     (no partial sums: width 0)
+//   amplitude  cent, str0, rows                | cbase | tasks |       | slots
+//   window     cent, cwin                      | cbase | tasks | part  | slots
+// A column holds `per` elements of `elem` bytes per chain; src points at the element of chain 0 of the whole list (a range takes
+// its own part), NULL: the column is staged as zeros (the device writes it).
+struct ChainCol {
+  const void* src;
+  size_t elem, per;
+};
+struct ChainStage {
+  std::vector<size_t> col;    // byte offset of every column, then of the slot bases
+  size_t tasks = 0, part = 0, slots = 0, total = 0;  // byte offsets; part is also the size of the table part, total the end of the slots
+  std::vector<int64_t> cbase;  // chain of the range -> first double of its slot
+  std::vector<char> image;     // host image of the table part, pad bytes zero: alive until the stream has taken it
+};
+// the offsets of the chains [c0, c1), `width` doubles of partial sums per chain; returns the total
+inline size_t chain_offsets(const std::vector<ChainCol>& cols, const ChainCore& c, const size_t c0, const size_t c1, const long long width, ChainStage& st) {
+  const size_t nc = c1 - c0;
+  long long nt = 0, sl = 0;
+  for (size_t e = c0; e < c1; ++e) nt += c.ntasks[e], sl += c.slot[e];
+  st.col.clear();
+  size_t at = 0;
+  for (const ChainCol& k : cols) st.col.push_back(at), at += al256(nc * k.per * k.elem);
+  st.col.push_back(at), at += al256(nc * sizeof(int64_t));
+  st.tasks = at, at += al256((size_t)nt * sizeof(Task2));
+  st.part = at, at += al256(nc * (size_t)width * sizeof(double));
+  st.slots = at;
+  return st.total = at + (size_t)sl * sizeof(double);
+}
+// offsets, slot bases and the filled image of the chains [c0, c1) with their task list
+inline void chain_stage(const std::vector<ChainCol>& cols, const ChainCore& c, const size_t c0, const size_t c1, const long long width, const std::vector<Task2>& tasks, ChainStage& st) {
+  chain_offsets(cols, c, c0, c1, width, st);
+  const size_t nc = c1 - c0;
+  st.cbase.resize(nc);
+  long long sl = 0;
+  for (size_t e = 0; e < nc; ++e) st.cbase[e] = sl, sl += c.slot[c0 + e];
+  st.image.assign(st.part, 0);
+  auto put = [&](const size_t at, const void* src, const size_t bytes) {
+    if (bytes) std::memcpy(st.image.data() + at, src, bytes);
+  };
+  for (size_t k = 0; k < cols.size(); ++k)
+    if (cols[k].src) put(st.col[k], static_cast<const char*>(cols[k].src) + c0 * cols[k].per * cols[k].elem, nc * cols[k].per * cols[k].elem);
+  put(st.col[cols.size()], st.cbase.data(), nc * sizeof(int64_t));
+  put(st.tasks, tasks.data(), std::min(tasks.size() * sizeof(Task2), st.part - st.tasks));  // the lists hold the chains' ntasks tasks (tested on the CPU)
+}
+// the largest total over the chain batches of a cut (cstart of chain_cut): what a state batch's buffer must have behind its own part
+inline size_t chain_stage_max(const std::vector<ChainCol>& cols, const ChainCore& c, const std::vector<size_t>& cstart, const long long width) {
+  ChainStage st;
+  size_t most = 0;
+  for (size_t cb = 0; cb + 1 < cstart.size(); ++cb) most = std::max(most, chain_offsets(cols, c, cstart[cb], cstart[cb + 1], width, st));
+  return most;
+}
+// The chains (pairs, strings) of a batch at most, from the environment: unset gives 0, the memory rule alone.
+inline int batch_cap(const char* what, const char* variable, long long& cap) {
+  cap = 0;
+  if (const char* v = std::getenv(variable)) {
+    cap = std::atoll(v);
+    if (cap < 1) return qk_fail(QK_EINVAL, "%s: %s must be >= 1 (got \"%s\")", what, variable, v);
+  }
+  return QK_OK;
 }
 
 // ---- the pair chains of the block kernels (qk_block_values_host) ------------------------------------------------------------------
@@ -392,9 +465,7 @@ inline long long blk_kept_offsets(const EnvSizes& z, const int side, const int n
   return at;
 }
 
-struct BlkChains {  // the pair chains of a call, in the order of its pair list
-  std::vector<long long> slot, ntasks, weight;  // doubles of its slot; its tasks over all launches; slot, partial sums, tasks and table entries
-};
+using BlkChains = ChainCore;  // the pair chains of a call, in the order of its pair list
 inline BlkChains list_blk_chains(const EnvSizes& zx, const EnvSizes& zy, const long long n_pairs, const int32_t* pairs, const int side,
                                  const std::vector<BlkLaunch>& plan, const int n_widths) {
   const int n = zx.n_sites, max_chunks = std::max(zx.max_chunks, zy.max_chunks);
@@ -477,9 +548,8 @@ inline int smp_task_count(const int kind, const int k, const int32_t* p, const i
     default: return R / LOC_CHUNK;  // SMP_ROT, SMP_DRAW
   }
 }
-struct SmpChains {  // the shot chains of a state batch, state-major in shot order
-  std::vector<int32_t> cent, shot0, rows;       // chain -> batch entry, first shot, shots
-  std::vector<long long> slot, ntasks, weight;  // doubles of its slot; its tasks over all launches; slot, tasks and table entries
+struct SmpChains : ChainCore {  // the shot chains of a state batch, state-major in shot order
+  std::vector<int32_t> cent, shot0, rows;  // chain -> batch entry, first shot, shots
 };
 inline SmpChains list_smp_chains(const EnvSizes& z, const int s0, const int nb, const int n_shots, const int tile) {
   const int n = z.n_sites;
@@ -631,9 +701,8 @@ inline int win_task_count(const int kind, const int j, const int32_t* p, const i
     default: return p[a] / LOC_CHUNK;  // WIN_CLOSE
   }
 }
-struct WinChains {  // the window chains of a state batch, state-major in window order
-  std::vector<int32_t> cent, cwin;              // chain -> batch entry, window (index into the starts)
-  std::vector<long long> slot, ntasks, weight;  // doubles of its slot; its tasks over all launches; slot, partial sums, tasks and table entries
+struct WinChains : ChainCore {  // the window chains of a state batch, state-major in window order
+  std::vector<int32_t> cent, cwin;  // chain -> batch entry, window (index into the starts)
 };
 inline WinChains list_win_chains(const EnvSizes& z, const int s0, const int nb, const int w, const int n_windows, const int32_t* starts) {
   const int n = z.n_sites;

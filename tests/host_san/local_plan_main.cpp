@@ -262,6 +262,7 @@ void test_chains() {
     for (int k = 0; k < N; ++k)
       for (const int kind : {STR_T, STR_PAULI, STR_X, STR_CLOSE}) nt += expected_chain_tasks(kind, k, &PAD[(s0 + i) * N1], &codes[m * N], SUPP[m][0], SUPP[m][1]);
     CHECK(ch.ntasks[e] == nt);
+    CHECK(ch.slot.size() == nch && ch.slot[e] == 6ll * PMAX[s0 + i] * PMAX[s0 + i]);
     CHECK(ch.weight[e] == 6ll * PMAX[s0 + i] * PMAX[s0 + i] + MAX_PAD / 16 + nt + 2);
   }
   const long long all = std::accumulate(ch.weight.begin(), ch.weight.end(), 0ll);
