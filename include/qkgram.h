@@ -760,8 +760,9 @@ int qk_selftest_mfma(qk_ctx* ctx);
  * (q0, q0+1); TKET matrices, theta = pi alpha / 2) and differ in the half-turn angles alpha[n_states][n_ops].
  * Op codes 8 (a 2x2 on q0) and 9 (a 4x4 on (q0, q0+1)) are the matrix gates of qk_build_mps_gates below: valid only in a call that
  * comes with a matrix table; op code 10 (a one-qubit Kraus channel on q0) belongs to qk_build_mps_channels: valid only in a call that
- * comes with a channel table.  An op code outside 0..7 -- outside 0..9 with a matrix table, and 10 with a channel table -- is QK_EINVAL
- * before anything runs.
+ * comes with a channel table; op code 11 (a two-qubit Kraus channel on (q0, q0+1)) belongs to qk_build_mps_channels2: valid only in a
+ * call that comes with a two-qubit channel table.  An op code outside 0..7 -- outside 0..9 with a matrix table, and 10 / 11 with
+ * their channel tables -- is QK_EINVAL before anything runs.
  * One persistent launch; per two-qubit gate a one-sided Jacobi SVD and the truncation rule of the host builder:
  * drop the trailing singular values whose squared weight stays <= trunc_budget (= 1 - truncation_fidelity,
  * G:141-144; criterion as KernelPkg.jl:68), values <= value_of_zero never count.  max_bond bounds every bond
@@ -848,8 +849,32 @@ int qk_build_mps_channels(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32
                           const int32_t* channel /* [n_ops] */, const int32_t* branch /* [stride ? n_states : 1][n_ops] */,
                           int32_t branch_state_stride, uint64_t seed, const uint32_t* state_index, const uint32_t* trajectory,
                           uint32_t first_gate, qk_built** out);
+/* Two-qubit Kraus channels.  qk_build_mps_channels2 is qk_build_mps_channels (its arguments in their order) plus a two-qubit channel
+ * table: with n_channels2 > 0 the program may hold op code 11, a Kraus channel on the pair (q0, q0+1) -- two-qubit depolarising noise,
+ * correlated dephasing, projectors on a pair, joint post-selection.  Channel c is n_kraus2[c] (1..16) matrices
+ * kraus2[c][k][(p,p')][(s,s')]: complex128 [n_channels2][16][4][4], (re, im) interleaved, the index convention of the 4x4 matrix
+ * gates (q0 most significant).  channel[i] and branch[i] are read where op is 10 or 11; where it is 11, channel[i] indexes kraus2.
+ * Either table may be absent (n_channels = 0 or n_channels2 = 0) when its code does not occur.  The step: the centre is brought
+ * into the pair by the moves of a two-qubit gate and theta[(a,p)][(p',c)] = A_q A_q+1 is formed; N = sum |theta|^2,
+ * p_k = sum_{a,c} |K_k theta[a,(.,.),c]|^2, tot, the branch b and the uniform as for code 10 (same counter, stream 2);
+ * theta <- K_b theta / sqrt(p_b); then the SVD, truncation, fidelity product, bond cap and centre placement of any two-qubit gate
+ * (the bond may shrink or be cut), and log(p_b / N) is added to the log-weight.  The device adds the sums per thread over its
+ * strided (a, c) in ascending order and the threads' partials in ascending thread order, the Kraus matrices in groups of four per
+ * pass over theta; a forced branch takes one pass (N and p_b).  branches and qk_built_num_channel_gates count the gates of codes 10
+ * and 11 together in program order.  QK_EINVAL before anything runs, naming the gate, for: channel[i] outside kraus2; n_kraus2
+ * outside 1..16; an entry that is not finite; branch[i] outside -1 .. m-1; a drawn channel with max |sum_k K_k^H K_k - 1| > 1e-12;
+ * q0[i] + 1 outside the register; a launch shape whose LDS cannot hold the staging.  QK_EDEVICE as for code 10.  With
+ * n_channels2 = 0 the call IS qk_build_mps_channels: code 11 is an unknown op code.                                                   */
+int qk_build_mps_channels2(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
+                           const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
+                           int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
+                           int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
+                           const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch,
+                           int32_t branch_state_stride, uint64_t seed, const uint32_t* state_index, const uint32_t* trajectory,
+                           uint32_t first_gate, int32_t n_channels2, const double* kraus2 /* [n_channels2][16][4][4][2] */,
+                           const int32_t* n_kraus2 /* [n_channels2] */, qk_built** out);
 int qk_built_logw_at(const qk_built* built, int32_t j, double* logw /* [n_states] */); /* log-weights at snapshot j (0 without channels) */
-int qk_built_num_channel_gates(const qk_built* built);                    /* op-code-10 gates of the program */
+int qk_built_num_channel_gates(const qk_built* built);                    /* gates of op codes 10 and 11 of the program */
 /* The branch every channel gate took, in program order: [n_states][n_channel_gates]; -1 where a dropped state stopped early */
 int qk_built_branches(const qk_built* built, int8_t* branches);
 int qk_built_num_snapshots(const qk_built* built);                        /* 1 for qk_build_mps */

@@ -34,6 +34,14 @@ complex128 [n_channels][4][2][2] plus ``n_kraus``), gate i reads channel
 -1) or takes the forced branch ``branch[i]`` (projectors, post-selection, replay).
 Project, Measure, PostSelect, AmplitudeDamping, PhaseDamping, Depolarizing, BitFlip
 and PhaseFlip are entries of that table.
+
+Op code 11 (``Kraus2q``) is a two-qubit Kraus channel on the pair (q0, q0+1): channel
+c is 1 <= m_c <= 16 complex 4x4 matrices ``kraus2[c][:m_c]`` (table complex128
+[n_channels2][16][4][4] plus ``n_kraus2``; the index convention of ``Unitary2q``),
+applied to theta = A_q A_{q+1} in front of the SVD of a two-qubit gate.  ``channel``
+and ``branch`` are shared with code 10: where ``op`` is 11, ``channel[i]`` indexes
+``kraus2``.  Project2q, Depolarizing2q, CorrelatedPhaseFlip, Measure2q and
+PostSelect2q are entries of that table.
 """
 from __future__ import annotations
 
@@ -47,13 +55,16 @@ OP_M1, OP_M2 = 8, 9  # matrix gates: a 2x2 on q0, a 4x4 on (q0, q0+1); the matri
 N_OPS = 8  # codes 0 .. N_OPS-1 are valid without a matrix table; every builder rejects any other
 N_OPS_MAT = 10  # codes 0 .. N_OPS_MAT-1 are valid in a program that comes with a matrix table
 OP_K1 = 10  # a one-qubit Kraus channel on q0, drawn or forced: valid only in a program that comes with a channel table
+OP_K2 = 11  # a two-qubit Kraus channel on (q0, q0+1), drawn or forced: valid only in a program that comes with a two-qubit channel table
 MAX_KRAUS = 4  # matrices per channel
+MAX_KRAUS2 = 16  # matrices per two-qubit channel
 TRACE_TOL = 1e-12  # max |sum_k K_k^H K_k - 1| a drawn channel may have
 UNITARY_TOL = 1e-12  # max |M^H M - 1| a matrix gate may have: the builders' canonical-form bookkeeping assumes unitary gates
 _OP_NAMES = {OP_H: "H", OP_RZ: "Rz", OP_XX: "XXPhase", OP_SWAP: "SWAP", OP_RX: "Rx", OP_RY: "Ry", OP_YY: "YYPhase", OP_ZZ: "ZZPhase",
-             OP_M1: "Unitary1q", OP_M2: "Unitary2q", OP_K1: "Kraus1q"}
+             OP_M1: "Unitary1q", OP_M2: "Unitary2q", OP_K1: "Kraus1q", OP_K2: "Kraus2q"}
 _OP_CODES = {name: code for code, name in _OP_NAMES.items()}
-_TWO_QUBIT = (OP_XX, OP_SWAP, OP_YY, OP_ZZ, OP_M2)
+_TWO_QUBIT = (OP_XX, OP_SWAP, OP_YY, OP_ZZ, OP_M2, OP_K2)
+_CHANNEL = (OP_K1, OP_K2)
 _PARAMETRISED = (OP_RZ, OP_XX, OP_RX, OP_RY, OP_YY, OP_ZZ)
 _MATRIX = (OP_M1, OP_M2)
 
@@ -72,6 +83,7 @@ _NAMED_2Q = {  # control first: index (s_control, s_target)
 }
 _NAMED = {**_NAMED_1Q, **_NAMED_2Q}
 _CHANNEL_NAMES = ("Kraus1q", "Project", "Measure", "PostSelect", "AmplitudeDamping", "PhaseDamping", "Depolarizing", "BitFlip", "PhaseFlip")
+_CHANNEL2_NAMES = ("Kraus2q", "Project2q", "Depolarizing2q", "CorrelatedPhaseFlip", "Measure2q", "PostSelect2q")
 
 
 def channel_kraus(name, params, where="channel"):
@@ -132,46 +144,106 @@ def channel_kraus(name, params, where="channel"):
     return np.stack(K).astype(np.complex128), -1
 
 
+def channel_kraus2(name, params, where="channel"):
+    """The Kraus matrices and the forced branch of a named two-qubit channel on the pair [a, b]: ``(K complex128 [m, 4, 4], branch)``
+    with ``branch`` -1 for a channel that is drawn.  ``K[k][(p,p')][(s,s')]``, qubit a most significant (the order of ``Unitary2q``).
+      * ``Kraus2q  [[K0, ..]]``: 1 .. 16 matrices as given, drawn;
+      * ``Project2q  [M]``: the one matrix M, forced (any finite 4x4);
+      * ``Depolarizing2q [p]``: sqrt(1 - 15p/16) I(x)I and sqrt(p/16) P(x)Q for the 15 other Pauli pairs, P-major over I, X, Y, Z;
+      * ``CorrelatedPhaseFlip [p]``: sqrt(1-p) I(x)I, sqrt p Z(x)Z;
+      * ``Measure2q  []``: the four projectors |ss'><ss'|, drawn;
+      * ``PostSelect2q [bits]``: the four projectors with the branch ``bits`` (0..3, qubit a most significant) forced.
+    ``ValueError`` for a wrong parameter count, a probability outside [0, 1] or matrices of the wrong shape."""
+    if name not in _CHANNEL2_NAMES:
+        raise ValueError(f"unknown two-qubit channel {name!r} (supported: {', '.join(_CHANNEL2_NAMES)})")
+    if name in ("Kraus2q", "Project2q"):
+        try:
+            K = np.asarray(params, dtype=np.complex128)
+        except (TypeError, ValueError):
+            raise ValueError(f"{where} ({name}): the parameter must be a list of complex 4x4 matrices") from None
+        if K.ndim == 4 and K.shape[0] == 1:
+            K = K[0]
+        if name == "Project2q":
+            if K.shape == (4, 4):
+                K = K[None]
+            if K.shape != (1, 4, 4):
+                raise ValueError(f"{where} (Project2q): expected one 4x4 matrix, got shape {K.shape}")
+            return np.ascontiguousarray(K), 0
+        if K.ndim != 3 or K.shape[1:] != (4, 4) or not 1 <= K.shape[0] <= MAX_KRAUS2:
+            raise ValueError(f"{where} (Kraus2q): expected a list of 1..{MAX_KRAUS2} 4x4 matrices, got shape {K.shape}")
+        return np.ascontiguousarray(K), -1
+    params = [] if params is None else list(np.ravel(params))
+    want = 0 if name == "Measure2q" else 1
+    if len(params) != want:
+        raise ValueError(f"{where} ({name}): expected {want} parameter(s), got {params}")
+    proj = np.zeros((4, 4, 4), dtype=np.complex128)
+    proj[np.arange(4), np.arange(4), np.arange(4)] = 1.0
+    if name == "Measure2q":
+        return proj, -1
+    if name == "PostSelect2q":
+        if params[0] not in (0, 1, 2, 3):
+            raise ValueError(f"{where} (PostSelect2q): the bits must be 0..3, got {params[0]!r}")
+        return proj, int(params[0])
+    p = float(params[0])
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"{where} ({name}): the parameter must lie in [0, 1], got {p!r}")
+    pauli = [np.eye(2), np.array(_NAMED_1Q["X"]), np.array(_NAMED_1Q["Y"]), np.array(_NAMED_1Q["Z"])]
+    if name == "Depolarizing2q":
+        K = [np.sqrt(p / 16.0) * np.kron(P, Q) for P in pauli for Q in pauli]
+        K[0] = np.sqrt(1.0 - 15.0 * p / 16.0) * np.eye(4)
+    else:
+        K = [np.sqrt(1.0 - p) * np.eye(4), np.sqrt(p) * np.kron(pauli[3], pauli[3])]
+    return np.stack(K).astype(np.complex128), -1
+
+
 class _ChannelTable:
-    """The channel table of a program under construction: every channel gate takes a slot of its own, by structure."""
+    """The channel table of a program under construction: every channel gate takes a slot of its own, by structure.  ``d`` = 2: the
+    one-qubit channels of op code 10; ``d`` = 4: the two-qubit channels of op code 11."""
 
-    def __init__(self):
-        self.entries = []
+    def __init__(self, d=2):
+        self.entries, self.d = [], d
 
-    def slot(self, name, params, where):
-        """(slot, forced branch or -1) of one channel gate as given."""
-        K, branch = channel_kraus(name, params, where)
+    def slot(self, name, params, where, exchange=False):
+        """(slot, forced branch or -1) of one channel gate as given; ``exchange``: a two-qubit channel named on [a, b] with a > b,
+        every matrix with the roles of its qubits exchanged (the rule of ``Unitary2q``)."""
+        K, branch = channel_kraus(name, params, where) if self.d == 2 else channel_kraus2(name, params, where)
         if not np.all(np.isfinite(K)):
             raise ValueError(f"{where} ({name}): a Kraus matrix has an entry that is not finite")
         if branch < 0:
-            dev = float(np.abs(np.einsum("kba,kbc->ac", K.conj(), K) - np.eye(2)).max())
+            dev = float(np.abs(np.einsum("kba,kbc->ac", K.conj(), K) - np.eye(self.d)).max())
             if not dev <= TRACE_TOL:
                 raise ValueError(f"{where} ({name}): the channel is not trace preserving (max |sum K^H K - 1| = {dev:.3e} > {TRACE_TOL:g})")
+        if exchange:
+            K = np.stack([exchange_qubits(k) for k in K])
         self.entries.append(K)
         return len(self.entries) - 1, branch
 
     def arrays(self):
-        kraus = np.zeros((len(self.entries), MAX_KRAUS, 2, 2), dtype=np.complex128)
+        kraus = np.zeros((len(self.entries), self.d * self.d, self.d, self.d), dtype=np.complex128)
         for c, K in enumerate(self.entries):
             kraus[c, : K.shape[0]] = K
         return kraus, np.asarray([K.shape[0] for K in self.entries], dtype=np.int32)
 
 
 def is_two_qubit(o) -> bool:
-    """Does op code ``o`` act on the pair (q0, q0+1)?  XXPhase, SWAP, YYPhase, ZZPhase and the 4x4 matrix gate do."""
+    """Does op code ``o`` act on the pair (q0, q0+1)?  XXPhase, SWAP, YYPhase, ZZPhase, the 4x4 matrix gate and the two-qubit
+    Kraus channel do."""
     return o in _TWO_QUBIT
 
 
-def check_op_codes(op, with_table: bool = False, with_channels: bool = False) -> None:
+def check_op_codes(op, with_table: bool = False, with_channels: bool = False, with_channels2: bool = False) -> None:
     """``ValueError`` unless every code of ``op`` is one of the N_OPS gates -- or, in a program that comes with a matrix table
-    (``with_table``), one of the N_OPS_MAT; code 10 is valid in a program that comes with a channel table (``with_channels``)."""
+    (``with_table``), one of the N_OPS_MAT; code 10 is valid in a program that comes with a channel table (``with_channels``), code
+    11 in one that comes with a two-qubit channel table (``with_channels2``)."""
     op = np.asarray(op)
     top = N_OPS_MAT if with_table else N_OPS
     bad = (op < 0) | (op >= top)
     if with_channels:
         bad &= op != OP_K1
+    if with_channels2:
+        bad &= op != OP_K2
     if bad.any():
-        raise ValueError(f"unknown gate op code {int(op[bad][0])} (valid: 0..{top - 1}{', 10' if with_channels else ''})")
+        raise ValueError(f"unknown gate op code {int(op[bad][0])} (valid: 0..{top - 1}{', 10' if with_channels else ''}{', 11' if with_channels2 else ''})")
 
 
 def exchange_qubits(m4) -> np.ndarray:
@@ -188,16 +260,16 @@ def check_unitary(m, where) -> None:
         raise ValueError(f"{where}: the matrix is not unitary (max |M^H M - 1| = {dev:.3e} > {UNITARY_TOL:g})")
 
 
-def check_matrix_gates(op, mat, mats, with_channels: bool = False):
+def check_matrix_gates(op, mat, mats, with_channels: bool = False, with_channels2: bool = False):
     """The matrix table of a program, validated: ``(mat int32 [n_gates], mats complex128 [n_mats, 4, 4])``, or ``(None, None)``
     for a program without one (its codes 8 and 9 are then unknown: ``check_op_codes``).  ``ValueError`` when the table is not
     [n_mats][4][4], when ``mat`` of a matrix gate lies outside 0 .. n_mats-1, or when the 2x2 (``[:2, :2]`` of the slot) or 4x4
     the gate reads is not finite and unitary to UNITARY_TOL; the message names the gate's position in the program."""
     op = np.asarray(op)
     if mats is None or mat is None:
-        check_op_codes(op, with_channels=with_channels)
+        check_op_codes(op, with_channels=with_channels, with_channels2=with_channels2)
         return None, None
-    check_op_codes(op, with_table=True, with_channels=with_channels)
+    check_op_codes(op, with_table=True, with_channels=with_channels, with_channels2=with_channels2)
     mats = np.asarray(mats)
     if mats.ndim != 3 or mats.shape[1:] != (4, 4):
         raise ValueError(f"the matrix table must be [n_mats][4][4], got shape {mats.shape}")
@@ -216,56 +288,69 @@ def check_matrix_gates(op, mat, mats, with_channels: bool = False):
     return mat, mats
 
 
-def check_channel_gates(op, q0, n_qubits, channel, branch, kraus, n_kraus):
-    """The channel table of a program, validated: ``(channel int32 [n_gates], branch int32 [n_gates], kraus complex128
-    [n_channels, 4, 2, 2], n_kraus int32 [n_channels])``, or ``None`` for a program without one (its code 10 is then unknown).
-    ``ValueError``, naming the gate's position, when a channel gate's ``channel`` lies outside the table, its ``n_kraus`` outside
-    1 .. 4, one of its matrices has an entry that is not finite, its ``branch`` lies outside -1 .. m-1, a drawn channel is not trace
-    preserving (max |sum_k K_k^H K_k - 1| > TRACE_TOL; a forced branch may be any finite matrix) or the gate lies outside the
-    register."""
-    if kraus is None or n_kraus is None or channel is None:
+def check_channel_gates(op, q0, n_qubits, channel, branch, kraus, n_kraus, kraus2=None, n_kraus2=None):
+    """The channel tables of a program, validated: ``(channel int32 [n_gates], branch int32 [n_gates], kraus complex128
+    [n_channels, 4, 2, 2], n_kraus int32 [n_channels], kraus2 complex128 [n_channels2, 16, 4, 4], n_kraus2 int32 [n_channels2])``
+    -- a table that is absent comes back as ``None, None``, its code (10 / 11) is then unknown --, or ``None`` for a program with
+    neither.  ``ValueError``, naming the gate's position, when a channel gate's ``channel`` lies outside its table, its count of
+    matrices outside 1 .. 4 (1 .. 16 for code 11), one of its matrices has an entry that is not finite, its ``branch`` lies outside
+    -1 .. m-1, a drawn channel is not trace preserving (max |sum_k K_k^H K_k - 1| > TRACE_TOL; a forced branch may be any finite
+    matrix) or the gate lies outside the register."""
+    one = kraus is not None and n_kraus is not None
+    two = kraus2 is not None and n_kraus2 is not None
+    if channel is None or not (one or two):
         return None
     op = np.asarray(op)
-    kraus = np.asarray(kraus)
-    if kraus.ndim != 4 or kraus.shape[1:] != (MAX_KRAUS, 2, 2):
-        raise ValueError(f"the channel table must be [n_channels][4][2][2], got shape {kraus.shape}")
-    kraus = np.ascontiguousarray(kraus, dtype=np.complex128)
-    n_kraus = np.ascontiguousarray(n_kraus, dtype=np.int32)
+    tables = {}
+    for code, d, k, nk in ((OP_K1, 2, kraus, n_kraus), (OP_K2, 4, kraus2, n_kraus2)):
+        if k is None or nk is None:
+            tables[code] = (d, None, None)
+            continue
+        k = np.asarray(k)
+        if k.ndim != 4 or k.shape[1:] != (d * d, d, d):
+            raise ValueError(f"the {'two-qubit ' if d == 4 else ''}channel table must be [n_channels][{d * d}][{d}][{d}], got shape {k.shape}")
+        k, nk = np.ascontiguousarray(k, dtype=np.complex128), np.ascontiguousarray(nk, dtype=np.int32)
+        if nk.shape != k.shape[:1]:
+            raise ValueError(f"n_kraus{'2' if d == 4 else ''} must hold one count per channel ({k.shape[0]}), got shape {nk.shape}")
+        tables[code] = (d, k, nk)
     channel = np.ascontiguousarray(channel, dtype=np.int32)
     branch = np.full(op.shape, -1, dtype=np.int32) if branch is None else np.ascontiguousarray(branch, dtype=np.int32)
-    if n_kraus.shape != kraus.shape[:1] or channel.shape != op.shape or branch.shape != op.shape:
-        raise ValueError(f"n_kraus must hold one count per channel ({kraus.shape[0]}), channel and branch one entry per gate ({op.shape[0]}); "
-                         f"got shapes {n_kraus.shape}, {channel.shape}, {branch.shape}")
+    if channel.shape != op.shape or branch.shape != op.shape:
+        raise ValueError(f"channel and branch must hold one entry per gate ({op.shape[0]}); got shapes {channel.shape}, {branch.shape}")
     q0 = np.asarray(q0)
-    for i in np.flatnonzero(op == OP_K1):
+    for i in np.flatnonzero((op == OP_K1) | (op == OP_K2)):
+        d, table, counts = tables[int(op[i])]
+        if table is None:
+            continue  # the code is unknown in this program: check_op_codes names it
+        kind = "two-qubit channel" if d == 4 else "channel"
         i, c, b = int(i), int(channel[i]), int(branch[i])
-        if not 0 <= c < kraus.shape[0]:
-            raise ValueError(f"gate {i}: channel index {c} outside 0..{kraus.shape[0] - 1}")
-        m = int(n_kraus[c])
-        if not 1 <= m <= MAX_KRAUS:
-            raise ValueError(f"gate {i}: channel {c} has {m} Kraus matrices (1..{MAX_KRAUS})")
-        K = kraus[c, :m]
+        if not 0 <= c < table.shape[0]:
+            raise ValueError(f"gate {i}: {kind} index {c} outside 0..{table.shape[0] - 1}")
+        m = int(counts[c])
+        if not 1 <= m <= d * d:
+            raise ValueError(f"gate {i}: {kind} {c} has {m} Kraus matrices (1..{d * d})")
+        K = table[c, :m]
         if not np.all(np.isfinite(K)):
-            raise ValueError(f"gate {i}: a Kraus matrix of channel {c} has an entry that is not finite")
+            raise ValueError(f"gate {i}: a Kraus matrix of {kind} {c} has an entry that is not finite")
         if not -1 <= b < m:
             raise ValueError(f"gate {i}: branch {b} outside -1..{m - 1}")
         if b < 0:
-            dev = float(np.abs(np.einsum("kba,kbc->ac", K.conj(), K) - np.eye(2)).max())
+            dev = float(np.abs(np.einsum("kba,kbc->ac", K.conj(), K) - np.eye(d)).max())
             if not dev <= TRACE_TOL:
-                raise ValueError(f"gate {i}: the drawn channel {c} is not trace preserving (max |sum K^H K - 1| = {dev:.3e} > {TRACE_TOL:g})")
-        if not 0 <= int(q0[i]) < int(n_qubits):
-            raise ValueError(f"gate {i}: channel on a qubit outside the register of {int(n_qubits)}")
-    return channel, branch, kraus, n_kraus
+                raise ValueError(f"gate {i}: the drawn {kind} {c} is not trace preserving (max |sum K^H K - 1| = {dev:.3e} > {TRACE_TOL:g})")
+        if not 0 <= int(q0[i]) < int(n_qubits) - (d == 4):
+            raise ValueError(f"gate {i}: {kind} on a qubit outside the register of {int(n_qubits)}")
+    return (channel, branch) + tables[OP_K1][1:] + tables[OP_K2][1:]
 
 
 def reject_channels(circuits, what) -> None:
     """``ValueError`` if one of ``circuits`` holds a drawn channel gate: ``what`` builds its states without a seed, state indices
     and trajectories, so every state would draw as state 0 (or as its position in a rank's share) of trajectory 0.  Forced
-    branches (``Project``, ``PostSelect``) draw nothing and pass."""
+    branches (``Project``, ``PostSelect`` and their two-qubit forms) draw nothing and pass."""
     for c in circuits:
-        k = np.asarray(c.op) == OP_K1
+        k = np.isin(np.asarray(c.op), _CHANNEL)
         if k.any() and (c.branch is None or np.any(np.asarray(c.branch)[k] < 0)):
-            raise ValueError(f"{what}: the circuit holds drawn Kraus channels (op code 10), which this path would run without a seed, state indices and "
+            raise ValueError(f"{what}: the circuit holds drawn Kraus channels (op codes 10, 11), which this path would run without a seed, state indices and "
                              f"trajectories; use build_noisy_kernel_matrix / build_noisy_projected_kernel_matrix, or simulate / Context.build_mps_set with them")
 
 
@@ -301,25 +386,30 @@ class BoundCircuit:
     alpha: np.ndarray  # float64 [n_gates] half-turns (0 where unused)
     mat: np.ndarray | None = None  # int32 [n_gates] index into mats of a matrix gate (op 8, 9), -1 at the named gates
     mats: np.ndarray | None = None  # complex128 [n_mats, 4, 4]: the matrix table (a 2x2 sits in [:2, :2], the rest of its slot 0)
-    channel: np.ndarray | None = None  # int32 [n_gates] index into kraus of a channel gate (op 10), -1 elsewhere
-    branch: np.ndarray | None = None  # int32 [n_gates] -1: the branch is drawn; k >= 0: branch k is forced (read where op is 10)
+    channel: np.ndarray | None = None  # int32 [n_gates] index into kraus (op 10) or kraus2 (op 11) of a channel gate, -1 elsewhere
+    branch: np.ndarray | None = None  # int32 [n_gates] -1: the branch is drawn; k >= 0: branch k is forced (read where op is 10 or 11)
     kraus: np.ndarray | None = None  # complex128 [n_channels, 4, 2, 2]: the channel table, K[s'][s] = <s'|K|s>
     n_kraus: np.ndarray | None = None  # int32 [n_channels] Kraus matrices of each channel (1..4)
+    kraus2: np.ndarray | None = None  # complex128 [n_channels2, 16, 4, 4]: the two-qubit channel table, K[(p,p')][(s,s')], q0 most significant
+    n_kraus2: np.ndarray | None = None  # int32 [n_channels2] Kraus matrices of each two-qubit channel (1..16)
 
     @property
     def n_channel_gates(self) -> int:
-        return int(np.count_nonzero(np.asarray(self.op) == OP_K1))
+        return int(np.count_nonzero(np.isin(np.asarray(self.op), _CHANNEL)))
+
+    def _with(self, op, q0, alpha, mat, channel, branch) -> "BoundCircuit":
+        return BoundCircuit(self.n_qubits, op, q0, alpha, mat, self.mats, channel, branch, self.kraus, self.n_kraus, self.kraus2, self.n_kraus2)
 
     def with_branches(self, branches) -> "BoundCircuit":
         """The same program with the branch of its j-th channel gate forced to ``branches[j]`` (-1 leaves it drawn): what replays
         the recorded ``branches`` of a trajectory."""
         b = np.asarray(branches, dtype=np.int32).ravel()
-        at = np.flatnonzero(np.asarray(self.op) == OP_K1)
+        at = np.flatnonzero(np.isin(np.asarray(self.op), _CHANNEL))
         if b.shape[0] != at.shape[0]:
             raise ValueError(f"the program has {at.shape[0]} channel gates, got {b.shape[0]} branches")
         row = np.full(self.op.shape, -1, dtype=np.int32)
         row[at] = b
-        return BoundCircuit(self.n_qubits, self.op, self.q0, self.alpha, self.mat, self.mats, self.channel, row, self.kraus, self.n_kraus)
+        return self._with(self.op, self.q0, self.alpha, self.mat, self.channel, row)
 
     @property
     def n_gates(self) -> int:
@@ -327,20 +417,23 @@ class BoundCircuit:
 
     def as_tuples(self):
         """(name, qubits, params) triples in the shape of the reference's CPU gate list
-        (/root/reference/cpu_backend/kernel_state_ansatz.py:113-131).  A drawn channel gate comes out as ``Kraus1q`` with all its
-        matrices; one with a forced branch b (``Project``, ``PostSelect``, a replay) as ``Project`` with the one matrix K_b, which
-        gives the same state and ``logw`` when read back (its recorded branch is then 0, the only one ``Project`` has)."""
-        chan = check_channel_gates(self.op, self.q0, self.n_qubits, self.channel, self.branch, self.kraus, self.n_kraus)
-        mat, mats = check_matrix_gates(self.op, self.mat, self.mats, with_channels=chan is not None)
+        (/root/reference/cpu_backend/kernel_state_ansatz.py:113-131).  A drawn channel gate comes out as ``Kraus1q`` (``Kraus2q``
+        for code 11) with all its matrices; one with a forced branch b (``Project``, ``PostSelect``, a replay) as ``Project``
+        (``Project2q``) with the one matrix K_b, which gives the same state and ``logw`` when read back (its recorded branch is then
+        0, the only one ``Project`` has)."""
+        chan = check_channel_gates(self.op, self.q0, self.n_qubits, self.channel, self.branch, self.kraus, self.n_kraus, self.kraus2, self.n_kraus2)
+        mat, mats = check_matrix_gates(self.op, self.mat, self.mats, with_channels=chan is not None and chan[2] is not None,
+                                       with_channels2=chan is not None and chan[4] is not None)
         out = []
         for i, (o, q, a) in enumerate(zip(self.op.tolist(), self.q0.tolist(), self.alpha.tolist())):
             qubits = [q, q + 1] if is_two_qubit(o) else [q]
-            if o == OP_K1:  # drawn: ("Kraus1q", [q], [[K0, ..]]); forced: ("Project", [q], [K_b]), the same state and logw
+            if o in _CHANNEL:  # drawn: ("Kraus1q", [q], [[K0, ..]]); forced: ("Project", [q], [K_b]), the same state and logw
                 c, b = int(chan[0][i]), int(chan[1][i])
+                table, counts = (chan[2], chan[3]) if o == OP_K1 else (chan[4], chan[5])
                 if b >= 0:
-                    out.append(("Project", qubits, [chan[2][c, b].copy()]))
+                    out.append(("Project" if o == OP_K1 else "Project2q", qubits, [table[c, b].copy()]))
                 else:
-                    out.append((_OP_NAMES[o], qubits, [chan[2][c, : int(chan[3][c])].copy()]))
+                    out.append((_OP_NAMES[o], qubits, [table[c, : int(counts[c])].copy()]))
             elif o in _MATRIX:  # ("Unitary1q", [q], [M2x2]) / ("Unitary2q", [q, q+1], [M4x4])
                 d = 2 if o == OP_M1 else 4
                 out.append((_OP_NAMES[o], qubits, [mats[mat[i], :d, :d].copy()]))
@@ -355,7 +448,7 @@ class BoundCircuit:
         if not 0 <= a <= b <= self.n_gates:
             raise ValueError(f"sliced({a}, {b}): want 0 <= a <= b <= {self.n_gates} gates")
         cut = lambda v: None if v is None else v[a:b]  # noqa: E731
-        return BoundCircuit(self.n_qubits, self.op[a:b], self.q0[a:b], self.alpha[a:b], cut(self.mat), self.mats, cut(self.channel), cut(self.branch), self.kraus, self.n_kraus)
+        return self._with(self.op[a:b], self.q0[a:b], self.alpha[a:b], cut(self.mat), cut(self.channel), cut(self.branch))
 
     @classmethod
     def from_gates(cls, n_qubits, gates, named_constants: bool = False) -> "BoundCircuit":
@@ -379,7 +472,7 @@ class BoundCircuit:
         matrix of the wrong shape or one that is not unitary to UNITARY_TOL."""
         n = int(n_qubits)
         op, q0, alpha, mat, channel, branch = [], [], [], [], [], []
-        table, chans = _MatTable(), _ChannelTable()
+        table, chans, chans2 = _MatTable(), _ChannelTable(), _ChannelTable(4)
         for pos, g in enumerate(gates):
             name, qubits, params = g
             code = _gate_code(name, named_constants)
@@ -391,6 +484,12 @@ class BoundCircuit:
                     raise ValueError(f"gate on qubits {qubits} outside a register of {n}")
                 slot, forced = chans.slot(name, params, f"gate {pos}")
                 op.append(OP_K1), q0.append(qubits[0]), alpha.append(0.0), mat.append(-1), channel.append(slot), branch.append(forced)
+                continue
+            if code == OP_K2:  # routed like a matrix gate; on [a, b] with a > b the matrices go in with the qubit roles exchanged
+                route = _route(code, qubits, n)
+                slot, forced = chans2.slot(name, params, f"gate {pos}", exchange=qubits[0] > qubits[1])
+                for o, q, k in route:
+                    op.append(o), q0.append(q), alpha.append(0.0), mat.append(-1), channel.append(slot if k else -1), branch.append(forced if k else -1)
                 continue
             if code in _MATRIX:
                 if name in _NAMED:
@@ -412,9 +511,10 @@ class BoundCircuit:
                 op.append(o), q0.append(q), alpha.append(a if k else 0.0), mat.append(-1), channel.append(-1), branch.append(-1)
         core = (n, np.asarray(op, dtype=np.int8), np.asarray(q0, dtype=np.int32), np.asarray(alpha, dtype=np.float64))
         mt = (np.asarray(mat, dtype=np.int32), table.array()) if table.entries else (None, None)
-        if not chans.entries:
+        if not chans.entries and not chans2.entries:
             return cls(*core) if not table.entries else cls(*core, *mt)
-        return cls(*core, *mt, np.asarray(channel, dtype=np.int32), np.asarray(branch, dtype=np.int32), *chans.arrays())
+        rows = (np.asarray(channel, dtype=np.int32), np.asarray(branch, dtype=np.int32))
+        return cls(*core, *mt, *rows, *(chans.arrays() if chans.entries else (None, None)), *(chans2.arrays() if chans2.entries else (None, None)))
 
 
 def check_checkpoints(checkpoints, n_gates) -> list:
@@ -454,6 +554,8 @@ def _arity(o) -> int:
 def _gate_code(name, named_constants: bool = True) -> int:
     if isinstance(name, str) and name in _CHANNEL_NAMES:
         return OP_K1
+    if isinstance(name, str) and name in _CHANNEL2_NAMES:
+        return OP_K2
     if isinstance(name, str) and name in _NAMED:
         if not named_constants:
             also = f"from_gates(..., named_constants=True) also takes {', '.join(_NAMED)}"
@@ -614,12 +716,14 @@ class CircuitProgram:
     """The compiled (unbound) gate program of a ``CircuitAnsatz``: per routed gate an op code, a pair / qubit and the
     angle form alpha = s (c_a + d_a x[a]) (c_b + d_b x[b]) (s = 0 for H and SWAP; c = 1, d = 0 for an absent factor)."""
 
-    def __init__(self, n_qubits, op, q0, s, fa, ca, da, fb, cb, db, mat=None, mats=None, channel=None, branch=None, kraus=None, n_kraus=None):
+    def __init__(self, n_qubits, op, q0, s, fa, ca, da, fb, cb, db, mat=None, mats=None, channel=None, branch=None, kraus=None, n_kraus=None, kraus2=None,
+                 n_kraus2=None):
         self.n_qubits = int(n_qubits)
         self.op, self.q0 = op, q0
         self.s, self.fa, self.ca, self.da, self.fb, self.cb, self.db = s, fa, ca, da, fb, cb, db
         self.mat, self.mats = mat, mats  # constant matrix gates: the table is the same array for every data point
         self.channel, self.branch, self.kraus, self.n_kraus = channel, branch, kraus, n_kraus  # channels are constants of the ansatz too
+        self.kraus2, self.n_kraus2 = kraus2, n_kraus2
 
     @property
     def n_gates(self) -> int:
@@ -627,7 +731,7 @@ class CircuitProgram:
 
     def bind(self, x: np.ndarray) -> BoundCircuit:
         alpha = self.s * (self.ca + self.da * x[self.fa]) * (self.cb + self.db * x[self.fb])
-        return BoundCircuit(self.n_qubits, self.op, self.q0, alpha, self.mat, self.mats, self.channel, self.branch, self.kraus, self.n_kraus)
+        return BoundCircuit(self.n_qubits, self.op, self.q0, alpha, self.mat, self.mats, self.channel, self.branch, self.kraus, self.n_kraus, self.kraus2, self.n_kraus2)
 
 
 def _factor(spec, n_features):
@@ -662,7 +766,7 @@ class CircuitAnsatz:
         self.feature_symbol_list = [f"f_{i}" for i in range(nf)]
         cols = {k: [] for k in ("op", "q0", "s", "fa", "ca", "da", "fb", "cb", "db")}
         mat, table = [], _MatTable()
-        channel, branch, chans = [], [], _ChannelTable()
+        channel, branch, chans, chans2 = [], [], _ChannelTable(), _ChannelTable(4)
         for pos, (name, qubits, angle) in enumerate(gates):
             code = _gate_code(name)
             qubits = [int(q) for q in (qubits if np.ndim(qubits) else [qubits])]
@@ -672,6 +776,10 @@ class CircuitAnsatz:
             slot, cslot, forced = -1, -1, -1
             if code == OP_K1:  # the channel's parameters stand in the place of the angle: constants of the ansatz
                 cslot, forced = chans.slot(name, angle, f"gate {pos}")
+                s, fa, fb = 0.0, one, one
+            elif code == OP_K2:
+                if len(set(qubits)) == 2:  # (a pair on one qubit is refused by the routing below)
+                    cslot, forced = chans2.slot(name, angle, f"gate {pos}", exchange=qubits[0] > qubits[1])
                 s, fa, fb = 0.0, one, one
             elif code in _MATRIX:
                 if name in _NAMED and angle is not None:
@@ -701,9 +809,12 @@ class CircuitAnsatz:
         arr = {k: np.asarray(v, dtype=dt.get(k, np.float64)) for k, v in cols.items()}
         if table.entries:
             arr["mat"], arr["mats"] = np.asarray(mat, dtype=np.int32), table.array()
-        if chans.entries:
+        if chans.entries or chans2.entries:
             arr["channel"], arr["branch"] = np.asarray(channel, dtype=np.int32), np.asarray(branch, dtype=np.int32)
+        if chans.entries:
             arr["kraus"], arr["n_kraus"] = chans.arrays()
+        if chans2.entries:
+            arr["kraus2"], arr["n_kraus2"] = chans2.arrays()
         self.ansatz_circ = CircuitProgram(n, **arr)
 
     def layer_ends(self) -> list:

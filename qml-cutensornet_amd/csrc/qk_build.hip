@@ -36,23 +36,29 @@ typedef double cd __attribute__((ext_vector_type(2)));  // complex128 as (re, im
 constexpr int MAX_SWEEPS = 40;
 
 // ansatz.py.  Codes 8 and 9 are the matrix gates: valid only in a program that comes with a matrix table (N_OPS_MAT codes then).
-// Code 10 is the one-qubit Kraus channel: valid only in a program that comes with a channel table.
-enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10, OP_K1 = 10 };
+// Code 10 is the one-qubit Kraus channel: valid only in a program that comes with a channel table; code 11 the two-qubit Kraus
+// channel on (q0, q0+1): valid only in a program that comes with a two-qubit channel table.
+enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10, OP_K1 = 10, OP_K2 = 11 };
 
-__host__ __device__ inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ || o == OP_M2; }
+// CHAN = false: the question as a kernel instantiation without the channel steps asks it (code 11 cannot occur there: the host
+// refuses it before the launch), so that its code is that of the kernel before the channels
+template <bool CHAN = true>
+__host__ __device__ inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ || o == OP_M2 || (CHAN && o == OP_K2); }
 
 enum { ERR_BOND = 1, ERR_HEAP = 2, ERR_SWEEPS = 4, ERR_GATE = 8, ERR_OP = 16, ERR_NORM0 = 32, ERR_CHANNEL = 64 };
 
-// What the channel step (op code 10) reads and writes: one instance in device memory behind BuildArgs::chan, so that a program
+// What the channel steps (op codes 10 and 11) read and write: one instance in device memory behind BuildArgs::chan, so that a program
 // without channels pays one pointer.
 struct ChanArgs {
   const cd* kraus;          // [n_channels][4][2][2] the channel table
   const int32_t* n_kraus;   // [n_channels] matrices of each channel (validated by the host: 1..4)
-  const int32_t* channel;   // [n_ops] channel of a channel gate (validated: inside the table where op is 10)
+  const cd* kraus2;         // [n_channels2][16][4][4] the two-qubit channel table (null: none, code 11 is unknown)
+  const int32_t* n_kraus2;  // [n_channels2] matrices of each two-qubit channel (validated by the host: 1..16)
+  const int32_t* channel;   // [n_ops] channel of a channel gate (validated: inside kraus where op is 10, inside kraus2 where op is 11)
   const int32_t* branch;    // [branch_stride ? n_states : 1][n_ops] -1: the branch is drawn, k: branch k is forced
   const int32_t* kgate;     // [n_ops] how many channel gates precede gate i: the column of its branch in branch_out
   int branch_stride;        // 0 (one row for all states) or n_ops
-  int n_kgates;             // channel gates of the program
+  int n_kgates;             // channel gates of the program, codes 10 and 11 together
   unsigned seed_lo, seed_hi, first_gate;  // the Philox key; the position of gate 0 in the uninterrupted program
   const uint32_t* state_index;  // [n_states] the names of the trajectories: Philox counter (first_gate + i, trajectory, state_index, 2)
   const uint32_t* trajectory;   // [n_states]
@@ -587,7 +593,7 @@ struct qk_built {
   std::vector<int64_t> all_offsets;
   std::vector<int32_t> all_centre;
   std::vector<double> all_logw;      // the log-weight of the trajectory so far (0 for a program without channels)
-  int n_kgates = 0;                  // channel gates (op code 10) of the program
+  int n_kgates = 0;                  // channel gates (op codes 10 and 11) of the program
   bool noisy = false;                // built with a channel table, or resumed from such a build: pins the launch shape
   std::vector<int8_t> branches;      // [n_states][n_kgates] the branch every channel gate took (-1: the state stopped before it)
   std::vector<int32_t> dims;  // the last snapshot, the finished states: what qk_built_info and qk_mps_set_from_built read
@@ -606,10 +612,13 @@ struct MatTable {  // the matrix table of op codes 8 and 9 as the caller gave it
   const int32_t* mat = nullptr;
 };
 
-struct ChanTable {  // the channel table of op code 10 and the names of the trajectories as the caller gave them (n_channels = 0: none)
+struct ChanTable {  // the channel tables of op codes 10 and 11 and the names of the trajectories as the caller gave them (n_channels = 0, n_channels2 = 0: none)
   int32_t n_channels = 0;
   const double* kraus = nullptr;     // [n_channels][4][2][2][2]
   const int32_t* n_kraus = nullptr;  // [n_channels]
+  int32_t n_channels2 = 0;
+  const double* kraus2 = nullptr;    // [n_channels2][16][4][4][2]
+  const int32_t* n_kraus2 = nullptr; // [n_channels2]
   const int32_t* channel = nullptr;  // [n_ops]
   const int32_t* branch = nullptr;   // [stride ? n_states : 1][n_ops]
   int32_t stride = 0;
@@ -678,19 +687,22 @@ extern "C" int qk_build_mps_gates(qk_ctx* c, int32_t n_states, int32_t n_qubits,
                      n_mats, mats, mats_state_stride, mat, ChanTable{}, out);
 }
 
-// The channel gates of a program, checked before anything runs (in each of the `rows` branch rows): the channel inside the table,
-// 1..4 matrices, finite entries, the branch inside -1..m-1, a drawn channel trace preserving, max |sum_k K_k^H K_k - 1| <= 1e-12 (a
-// forced branch may be any finite matrix), the qubit inside the register.
+// The channel gates of a program, checked before anything runs (in each of the `rows` branch rows): the channel inside its table,
+// 1..4 matrices (1..16 for the two-qubit channel of code 11), finite entries, the branch inside -1..m-1, a drawn channel trace
+// preserving, max |sum_k K_k^H K_k - 1| <= 1e-12 (a forced branch may be any finite matrix), the qubit (pair) inside the register.
 static int check_chan_table(const char* what, int n_qubits, int n_ops, const int8_t* op, const int32_t* q0, int rows, const ChanTable& t) {
   for (int i = 0; i < n_ops; ++i) {
-    if (op[i] != OP_K1) continue;
+    if (op[i] != OP_K1 && op[i] != OP_K2) continue;
+    const bool two = op[i] == OP_K2;
+    const int d = two ? 4 : 2, n_table = two ? t.n_channels2 : t.n_channels;  // d x d matrices, at most d * d of them
+    const char* kind = two ? "two-qubit channel" : "channel";
     const int ch = t.channel[i];
-    if (ch < 0 || ch >= t.n_channels) return qk_fail(QK_EINVAL, "%s: gate %d: channel index %d outside 0..%d", what, i, ch, (int)t.n_channels - 1);
-    const int m = t.n_kraus[ch];
-    if (m < 1 || m > 4) return qk_fail(QK_EINVAL, "%s: gate %d: channel %d has %d Kraus matrices (1..4)", what, i, ch, m);
-    const double* K = t.kraus + (size_t)ch * 32;  // [4][2][2][2]
-    for (int e = 0; e < 8 * m; ++e)
-      if (!std::isfinite(K[e])) return qk_fail(QK_EINVAL, "%s: gate %d: a Kraus matrix of channel %d has an entry that is not finite", what, i, ch);
+    if (ch < 0 || ch >= n_table) return qk_fail(QK_EINVAL, "%s: gate %d: %s index %d outside 0..%d", what, i, kind, ch, n_table - 1);
+    const int m = (two ? t.n_kraus2 : t.n_kraus)[ch];
+    if (m < 1 || m > d * d) return qk_fail(QK_EINVAL, "%s: gate %d: %s %d has %d Kraus matrices (1..%d)", what, i, kind, ch, m, d * d);
+    const double* K = (two ? t.kraus2 : t.kraus) + (size_t)ch * d * d * d * d * 2;  // [d * d][d][d][2]
+    for (int e = 0; e < 2 * d * d * m; ++e)
+      if (!std::isfinite(K[e])) return qk_fail(QK_EINVAL, "%s: gate %d: a Kraus matrix of %s %d has an entry that is not finite", what, i, kind, ch);
     bool drawn = false;
     for (int s = 0; s < rows; ++s) {
       const int b = t.branch[(size_t)s * n_ops + i];
@@ -699,21 +711,44 @@ static int check_chan_table(const char* what, int n_qubits, int n_ops, const int
     }
     if (drawn) {
       double dev = 0;
-      for (int a = 0; a < 2; ++a)
-        for (int d = 0; d < 2; ++d) {
-          double gr = (a == d) ? -1.0 : 0.0, gi = 0.0;  // (sum_k K_k^H K_k - 1)[a][d] = sum_{k,r} conj(K_k[r][a]) K_k[r][d] - delta
+      for (int a = 0; a < d; ++a)
+        for (int e = 0; e < d; ++e) {
+          double gr = (a == e) ? -1.0 : 0.0, gi = 0.0;  // (sum_k K_k^H K_k - 1)[a][e] = sum_{k,r} conj(K_k[r][a]) K_k[r][e] - delta
           for (int k = 0; k < m; ++k)
-            for (int r = 0; r < 2; ++r) {
-              const double xr = K[((k * 2 + r) * 2 + a) * 2], xi = K[((k * 2 + r) * 2 + a) * 2 + 1], yr = K[((k * 2 + r) * 2 + d) * 2], yi = K[((k * 2 + r) * 2 + d) * 2 + 1];
+            for (int r = 0; r < d; ++r) {
+              const double xr = K[((k * d + r) * d + a) * 2], xi = K[((k * d + r) * d + a) * 2 + 1], yr = K[((k * d + r) * d + e) * 2], yi = K[((k * d + r) * d + e) * 2 + 1];
               gr += xr * yr + xi * yi, gi += xr * yi - xi * yr;
             }
           dev = std::max(dev, std::hypot(gr, gi));
         }
-      if (!(dev <= 1e-12)) return qk_fail(QK_EINVAL, "%s: gate %d: the drawn channel %d is not trace preserving: max |sum K^H K - 1| = %.3e > 1e-12", what, i, ch, dev);
+      if (!(dev <= 1e-12)) return qk_fail(QK_EINVAL, "%s: gate %d: the drawn %s %d is not trace preserving: max |sum K^H K - 1| = %.3e > 1e-12", what, i, kind, ch, dev);
     }
-    if (q0[i] < 0 || q0[i] >= n_qubits) return qk_fail(QK_EINVAL, "%s: gate %d: channel on a qubit outside the register", what, i);
+    if (q0[i] < 0 || q0[i] + (two ? 1 : 0) >= n_qubits) return qk_fail(QK_EINVAL, "%s: gate %d: %s on a qubit outside the register", what, i, kind);
   }
   return QK_OK;
+}
+
+// the body of qk_build_mps_channels (n_channels2 = 0) and qk_build_mps_channels2
+static int build_channels(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                          double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                          int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
+                          const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
+                          const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const double* kraus2,
+                          const int32_t* n_kraus2, qk_built** out) {
+  ChanTable t;
+  if (n_channels2 < 0 || (n_channels2 > 0 && (!kraus2 || !n_kraus2 || !channel || !branch)))
+    return qk_fail(QK_EINVAL, "%s: a two-qubit channel table needs n_channels2 >= 0, kraus2, n_kraus2, channel and branch", what);
+  if (n_channels < 0 || (n_channels > 0 && (!kraus || !n_kraus || !channel || !branch))) return qk_fail(QK_EINVAL, "%s: a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch", what);
+  if ((n_channels > 0 || n_channels2 > 0) && branch_state_stride != 0 && branch_state_stride != n_ops)
+    return qk_fail(QK_EINVAL, "%s: branch_state_stride must be 0 (one row for all states) or n_ops = %d, got %d", what, (int)n_ops, (int)branch_state_stride);
+  if (n_channels > 0) t.n_channels = n_channels, t.kraus = kraus, t.n_kraus = n_kraus;
+  if (n_channels2 > 0) t.n_channels2 = n_channels2, t.kraus2 = kraus2, t.n_kraus2 = n_kraus2;
+  if (n_channels > 0 || n_channels2 > 0) {
+    t.channel = channel, t.branch = branch, t.stride = branch_state_stride;
+    t.seed = seed, t.state_index = state_index, t.trajectory = trajectory, t.first_gate = first_gate;
+  }
+  return build_gates(n_channels > 0 || n_channels2 > 0 ? what : "qk_build_mps_gates", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial,
+                     initial_snapshot, n_mats, mats, mats_state_stride, mat, t, out);
 }
 
 extern "C" int qk_build_mps_channels(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
@@ -721,17 +756,23 @@ extern "C" int qk_build_mps_channels(qk_ctx* c, int32_t n_states, int32_t n_qubi
                                      int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
                                      const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
                                      const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, qk_built** out) {
-  static const char* what = "qk_build_mps_channels";
-  ChanTable t;
-  if (n_channels < 0 || (n_channels > 0 && (!kraus || !n_kraus || !channel || !branch))) return qk_fail(QK_EINVAL, "%s: a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch", what);
-  if (n_channels > 0 && branch_state_stride != 0 && branch_state_stride != n_ops)
-    return qk_fail(QK_EINVAL, "%s: branch_state_stride must be 0 (one row for all states) or n_ops = %d, got %d", what, (int)n_ops, (int)branch_state_stride);
-  if (n_channels > 0) {
-    t.n_channels = n_channels, t.kraus = kraus, t.n_kraus = n_kraus, t.channel = channel, t.branch = branch, t.stride = branch_state_stride;
-    t.seed = seed, t.state_index = state_index, t.trajectory = trajectory, t.first_gate = first_gate;
-  }
-  return build_gates(n_channels > 0 ? what : "qk_build_mps_gates", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial,
-                     initial_snapshot, n_mats, mats, mats_state_stride, mat, t, out);
+  return build_channels("qk_build_mps_channels", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
+                        n_mats, mats, mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate, 0, nullptr,
+                        nullptr, out);
+}
+
+extern "C" int qk_build_mps_channels2(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                                      int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
+                                      const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
+                                      const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const double* kraus2,
+                                      const int32_t* n_kraus2, qk_built** out) {
+  if (n_channels2 == 0)  // without a two-qubit table the call IS qk_build_mps_channels
+    return qk_build_mps_channels(c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot, n_mats, mats,
+                                 mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate, out);
+  return build_channels("qk_build_mps_channels2", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
+                        n_mats, mats, mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate, n_channels2, kraus2,
+                        n_kraus2, out);
 }
 
 static int build_gates(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
@@ -759,10 +800,11 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   if (n_states <= 0 || n_qubits <= 0 || n_ops < 0) return qk_fail(QK_EINVAL, "%s: empty problem (%d states, %d qubits, %d gates)", what, n_states, n_qubits, n_ops);
   if (max_bond < 2 || max_bond > 1024) return qk_fail(QK_EINVAL, "%s: max_bond %d outside 2..1024", what, max_bond);
   const int n_codes = tab.n_mats > 0 ? N_OPS_MAT : N_OPS;  // without a table codes 8 and 9 are unknown
-  const bool with_chan = cht.n_channels > 0;  // without a channel table code 10 is unknown
+  const bool with_k1 = cht.n_channels > 0, with_k2 = cht.n_channels2 > 0;  // without a channel table code 10 is unknown, without a two-qubit one code 11
+  const bool with_chan = with_k1 || with_k2;
   for (int i = 0; i < n_ops; ++i)
-    if ((op[i] < 0 || op[i] >= n_codes) && !(with_chan && op[i] == OP_K1))
-      return qk_fail(QK_EINVAL, "%s: unknown gate op code %d at position %d (valid: 0..%d%s)", what, (int)op[i], i, n_codes - 1, with_chan ? ", 10" : "");
+    if ((op[i] < 0 || op[i] >= n_codes) && !(with_k1 && op[i] == OP_K1) && !(with_k2 && op[i] == OP_K2))
+      return qk_fail(QK_EINVAL, "%s: unknown gate op code %d at position %d (valid: 0..%d%s%s)", what, (int)op[i], i, n_codes - 1, with_k1 ? ", 10" : "", with_k2 ? ", 11" : "");
   for (int i = 0; i < n_ops; ++i)  // (the kernel checks this too; a matrix gate past the last pair is refused before anything runs)
     if ((op[i] == OP_M1 || op[i] == OP_M2) && (q0[i] < 0 || q0[i] + (op[i] == OP_M2 ? 1 : 0) >= n_qubits))
       return qk_fail(QK_EINVAL, "%s: gate %d on a qubit outside the register", what, i);
@@ -772,13 +814,14 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
     if (rc != QK_OK) return rc;
   }
   std::vector<int32_t> kgate((size_t)std::max(1, n_ops), 0);  // channel gates before gate i
-  int n_kgates = 0;
+  int n_kgates = 0, n_k2gates = 0;
   if (with_chan) {
     const int rc = check_chan_table(what, n_qubits, n_ops, op, q0, cht.stride ? n_states : 1, cht);
     if (rc != QK_OK) return rc;
     for (int i = 0; i < n_ops; ++i) {
       kgate[i] = n_kgates;
-      n_kgates += (op[i] == OP_K1);
+      n_kgates += (op[i] == OP_K1 || op[i] == OP_K2);
+      n_k2gates += (op[i] == OP_K2);
     }
   }
   if (init) {  // a resumed build starts from snapshot init_j of `init`, which is only read
@@ -821,8 +864,11 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   size_t lds_total = (wgs_variant == 4 ? 38 : wgs_variant == 2 ? 76 : 152) * 1024;
   if (const char* v = std::getenv("QK_BUILD_LDS_KB")) lds_total = (size_t)std::max(32, std::min(wgs_variant == 4 ? 38 : 156, std::atoi(v))) * 1024;
   const int jl_elems = (int)((lds_total - lds_meta) / sizeof(cd));
-  if (n_kgates > 0 && jl_elems < 16 + (5 * bt + 6) / 2)  // wg_channel: the staged matrices and five partial sums per thread
+  if (n_kgates > n_k2gates && jl_elems < 16 + (5 * bt + 6) / 2)  // wg_channel: the staged matrices and five partial sums per thread
     return qk_fail(QK_EINVAL, "%s: the channel step needs %d complex numbers of LDS working set, this shape leaves %d", what, 16 + (5 * bt + 6) / 2, jl_elems);
+  // wg_channel_2q: four staged 4x4 matrices, five partial sums per thread, N and the sixteen p_k
+  if (n_k2gates > 0 && jl_elems < 64 + (5 * bt + 18) / 2)
+    return qk_fail(QK_EINVAL, "%s: the two-qubit channel step needs %d complex numbers of LDS working set, this shape leaves %d", what, 64 + (5 * bt + 18) / 2, jl_elems);
   const size_t lds = lds_total;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb256::qk_build_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(qkb256::qk_build_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 38 * 1024));
@@ -855,7 +901,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   HIP_TRY_AS(what, c->build_work.ensure((size_t)grid * (4 * wslot + wtab) * sizeof(cd)));
   QkDevBuf heap, d_op, d_q0, d_alpha, d_fid, d_secs, d_dims, d_offs, d_ctr, d_err, d_order;  // d_ctr: [0] state counter, [1] heap top
   QkDevBuf d_ckpt, d_centre, d_ioffs, d_idims, d_ifid, d_icentre, d_mats, d_mat;
-  QkDevBuf d_logw, d_ilogw, d_kraus, d_nkraus, d_channel, d_branch, d_kgate, d_sidx, d_traj, d_bout, d_chan;
+  QkDevBuf d_logw, d_ilogw, d_kraus, d_nkraus, d_kraus2, d_nkraus2, d_channel, d_branch, d_kgate, d_sidx, d_traj, d_bout, d_chan;
   const size_t n_rec = (size_t)n_ckpt * n_states;  // (snapshot, state) records
   HIP_TRY_AS(what, heap.alloc(heap_cap * sizeof(cd)));
   HIP_TRY_AS(what, d_op.alloc(std::max(1, n_ops)));
@@ -889,16 +935,24 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
     std::vector<uint32_t> sidx(n_states), traj(n_states, 0u);
     for (int s = 0; s < n_states; ++s) sidx[s] = cht.state_index ? cht.state_index[s] : (uint32_t)s;
     if (cht.trajectory) traj.assign(cht.trajectory, cht.trajectory + n_states);
-    HIP_TRY_AS(what, d_kraus.alloc((size_t)cht.n_channels * 16 * sizeof(cd)));
-    HIP_TRY_AS(what, d_nkraus.alloc((size_t)cht.n_channels * sizeof(int32_t)));
+    HIP_TRY_AS(what, d_kraus.alloc(std::max<size_t>(1, cht.n_channels) * 16 * sizeof(cd)));
+    HIP_TRY_AS(what, d_nkraus.alloc(std::max<size_t>(1, cht.n_channels) * sizeof(int32_t)));
+    if (with_k2) {
+      HIP_TRY_AS(what, d_kraus2.alloc((size_t)cht.n_channels2 * 256 * sizeof(cd)));
+      HIP_TRY_AS(what, d_nkraus2.alloc((size_t)cht.n_channels2 * sizeof(int32_t)));
+      HIP_TRY_AS(what, hipMemcpy(d_kraus2.get(), cht.kraus2, (size_t)cht.n_channels2 * 256 * sizeof(cd), hipMemcpyHostToDevice));
+      HIP_TRY_AS(what, hipMemcpy(d_nkraus2.get(), cht.n_kraus2, (size_t)cht.n_channels2 * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
     HIP_TRY_AS(what, d_channel.alloc((size_t)n_ops * sizeof(int32_t)));
     HIP_TRY_AS(what, d_branch.alloc(rows * n_ops * sizeof(int32_t)));
     HIP_TRY_AS(what, d_kgate.alloc((size_t)n_ops * sizeof(int32_t)));
     HIP_TRY_AS(what, d_sidx.alloc((size_t)n_states * sizeof(uint32_t)));
     HIP_TRY_AS(what, d_traj.alloc((size_t)n_states * sizeof(uint32_t)));
     HIP_TRY_AS(what, d_bout.alloc((size_t)n_states * n_kgates));
-    HIP_TRY_AS(what, hipMemcpy(d_kraus.get(), cht.kraus, (size_t)cht.n_channels * 16 * sizeof(cd), hipMemcpyHostToDevice));
-    HIP_TRY_AS(what, hipMemcpy(d_nkraus.get(), cht.n_kraus, (size_t)cht.n_channels * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (with_k1) {
+      HIP_TRY_AS(what, hipMemcpy(d_kraus.get(), cht.kraus, (size_t)cht.n_channels * 16 * sizeof(cd), hipMemcpyHostToDevice));
+      HIP_TRY_AS(what, hipMemcpy(d_nkraus.get(), cht.n_kraus, (size_t)cht.n_channels * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
     HIP_TRY_AS(what, hipMemcpy(d_channel.get(), cht.channel, (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
     HIP_TRY_AS(what, hipMemcpy(d_branch.get(), cht.branch, rows * n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
     HIP_TRY_AS(what, hipMemcpy(d_kgate.get(), kgate.data(), (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -907,6 +961,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
     HIP_TRY_AS(what, hipMemset(d_bout.get(), 0xFF, (size_t)n_states * n_kgates));  // -1: not reached
     HIP_TRY_AS(what, d_logw.alloc(n_rec * sizeof(double)));
     ChanArgs ca;
+    ca.kraus2 = with_k2 ? d_kraus2.get<cd>() : nullptr, ca.n_kraus2 = with_k2 ? d_nkraus2.get<int32_t>() : nullptr;
     ca.kraus = d_kraus.get<cd>(), ca.n_kraus = d_nkraus.get<int32_t>(), ca.channel = d_channel.get<int32_t>(), ca.branch = d_branch.get<int32_t>();
     ca.kgate = d_kgate.get<int32_t>(), ca.branch_stride = cht.stride ? n_ops : 0, ca.n_kgates = n_kgates;
     ca.seed_lo = (unsigned)cht.seed, ca.seed_hi = (unsigned)(cht.seed >> 32), ca.first_gate = cht.first_gate;

@@ -1259,8 +1259,123 @@ __device__ __noinline__ void wg_channel(cd* t, const int l, const int r, const C
   __syncthreads();
 }
 
+// ---- two-qubit Kraus channel (op code 11) on theta[(a,p)][(p',c)] (row length nn = 2 r), between the theta product and its SVD
+// Code 10's branch logic on the four entries (p00, p01, p10, p11) of every (a, c).  LDS (`stage`: the Jacobi working set, idle here;
+// the caller arrives behind the barrier of the theta product): 64 staged complex numbers -- four 4x4 matrices --, [5][BT] per-thread
+// partials as in wg_channel, then red[17] = N, p_0 .. p_15.  Sixteen matrices and seventeen partials per thread do not fit the
+// four-workgroup shape, so a drawn channel takes its matrices in groups of four, one pass over theta per group: pass g stages
+// K_4g .. K_4g+3 and adds p_4g .. p_4g+3 (pass 0 also N).  A forced branch takes one pass with two sums, N and p_b, through the very
+// same loop (K_b staged in slot 0), so it gives the bits of the drawn run that drew b.  Every thread adds its strided (a, c) in
+// ascending order, each |.|^2 sum one chain of fused multiply-adds; threads 0..4 add one quantity each over the partials in
+// ascending thread order: no atomics.  Thread 0 picks the branch as in wg_channel (same uniform) and records it and log(p_b / N);
+// then all threads apply K_b / sqrt(p_b), the loop of wg_matrix_2q.  sh->flag = 0 when the outcome is impossible: theta is left as
+// it is.  Kept out of line and behind the one pointer `ca`, like wg_channel.
+__device__ __forceinline__ double norm2_4(const cd y0, const cd y1, const cd y2, const cd y3) {
+  double s = y0.x * y0.x;
+  s = fma(y0.y, y0.y, s);
+  s = fma(y1.x, y1.x, s);
+  s = fma(y1.y, y1.y, s);
+  s = fma(y2.x, y2.x, s);
+  s = fma(y2.y, y2.y, s);
+  s = fma(y3.x, y3.x, s);
+  s = fma(y3.y, y3.y, s);
+  return s;
+}
+
+__device__ __noinline__ void wg_channel_2q(cd* TH, const int l, const int r, const ChanArgs* ca, const int st, const int i, cd* stage, WgShared* sh) {
+  const int tid = threadIdx.x, nn = 2 * r;
+  const int ch = ca->channel[i];
+  const cd* K = ca->kraus2 + (long)ch * 256;
+  const int m = ca->n_kraus2[ch], forced = ca->branch[(long)st * ca->branch_stride + i];
+  double* part = reinterpret_cast<double*>(stage + 64);  // [5][BT] per-thread partials
+  double* red = part + 5 * BT;                            // [17] N, p_0 .. p_15
+  const int n_pass = forced >= 0 ? 1 : (m + 3) / 4;
+  for (int pass = 0; pass < n_pass; ++pass) {
+    const int k0 = forced >= 0 ? forced : 4 * pass;      // the first matrix of this pass
+    const int nk = forced >= 0 ? 1 : min(4, m - k0);     // and how many
+    if (tid < 64) stage[tid] = (tid < 16 * nk) ? K[k0 * 16 + tid] : cd{0.0, 0.0};
+    __syncthreads();
+    double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int e = tid; e < l * r; e += BT) {
+      const int a = e / r, c = e - a * r;
+      const cd* p00 = TH + (long)(a * 2) * nn + c;
+      const cd* p10 = TH + (long)(a * 2 + 1) * nn + c;
+      const cd v[4] = {p00[0], p00[r], p10[0], p10[r]};
+      if (pass == 0) acc[0] += norm2_4(v[0], v[1], v[2], v[3]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < nk) {
+          const cd* Kk = stage + 16 * k;
+          acc[1 + k] += norm2_4(mat_dot<4>(Kk, v), mat_dot<4>(Kk + 4, v), mat_dot<4>(Kk + 8, v), mat_dot<4>(Kk + 12, v));
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 5; ++j) part[j * BT + tid] = acc[j];
+    __syncthreads();
+    if (tid < 5 && (tid == 0 ? pass == 0 : tid - 1 < nk)) {
+      double s = 0.0;
+      for (int j = 0; j < BT; ++j) s += part[tid * BT + j];
+      red[tid == 0 ? 0 : k0 + tid] = s;
+    }
+    __syncthreads();  // the sums are out: the next pass may overwrite the staged matrices and the partials
+  }
+  if (tid == 0) {
+    const double N = red[0];
+    int b = forced;
+    bool ok = true;
+    if (forced < 0) {
+      double tot = 0.0;
+      for (int k = 0; k < m; ++k) tot += red[1 + k];
+      ok = (tot > 0.0) && (tot <= 1.79e308);
+      const qkl::Philox4 x = qkl::smp_philox(ca->first_gate + (unsigned)i, ca->trajectory[st], ca->state_index[st], 2u, ca->seed_lo, ca->seed_hi);
+      const double u = (double)(((uint64_t)(x.x[0] >> 5) << 26) + (uint64_t)(x.x[1] >> 6)) * (1.0 / 9007199254740992.0);
+      double cum = 0.0;
+      int last = 0;
+      for (int k = 0; k < m; ++k) {
+        const double pk = red[1 + k];
+        cum += pk;
+        if (pk > 0.0) {
+          last = k;
+          if (b < 0 && u * tot < cum) b = k;
+        }
+      }
+      if (b < 0) b = last;
+    }
+    const double pb = red[1 + b];
+    ok = ok && (pb > 0.0) && (pb <= 1.79e308);
+    sh->flag = ok ? 1 : 0;
+    sh->keep = b;
+    sh->nrm = sqrt(pb);
+    if (ok) {
+      sh->logw += log(pb / N);
+      ca->branch_out[(long)st * ca->n_kgates + ca->kgate[i]] = (int8_t)b;
+    }
+  }
+  __syncthreads();
+  if (!sh->flag) return;
+  const double s = sh->nrm;
+  if (tid < 16) stage[tid] = K[sh->keep * 16 + tid];
+  __syncthreads();
+  cd mk[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) mk[k] = cd{stage[k].x / s, stage[k].y / s};
+  for (int e = tid; e < l * r; e += BT) {
+    const int a = e / r, c = e - a * r;
+    cd* p00 = TH + (long)(a * 2) * nn + c;
+    cd* p01 = p00 + r;
+    cd* p10 = TH + (long)(a * 2 + 1) * nn + c;
+    cd* p11 = p10 + r;
+    const cd v[4] = {*p00, *p01, *p10, *p11};
+    *p00 = mat_dot<4>(mk, v);
+    *p01 = mat_dot<4>(mk + 4, v);
+    *p10 = mat_dot<4>(mk + 8, v);
+    *p11 = mat_dot<4>(mk + 12, v);
+  }
+  __syncthreads();
+}
+
 // MINWG: resident workgroups per CU the register budget is cut for: 256 threads: 2 (76 KiB of LDS each) or 4 (38 KiB); 512 threads: 1 (152 KiB).
-// CHAN: the program holds channel gates (op code 10).  A program without them runs the instantiation that has none of their code, so
+// CHAN: the program holds channel gates (op codes 10 and 11).  A program without them runs the instantiation that has none of their code, so
 // its registers, its spills and its arithmetic are those of the kernel before the channels (the compiler's resource report of the
 // four-workgroup shape is the same line as before; with the step compiled in, the allocation of the whole gate loop changes).
 template <int MINWG, bool CHAN>
@@ -1322,11 +1437,11 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
         ++ck;
       }
       const int o = g.op[i], q = g.q0[i];
-      if ((o < 0 || o >= (g.mats ? N_OPS_MAT : N_OPS)) && !(CHAN && o == OP_K1)) {  // the matrix gates and the channels need their tables
+      if ((o < 0 || o >= (g.mats ? N_OPS_MAT : N_OPS)) && !(CHAN && (o == OP_K1 || o == OP_K2))) {  // the matrix gates and the channels need their tables
         if (tid == 0) atomicOr(g.error, ERR_OP);
         continue;
       }
-      if (q < 0 || q >= n || (is_two_qubit(o) && q + 1 >= n)) {
+      if (q < 0 || q >= n || (is_two_qubit<CHAN>(o) && q + 1 >= n)) {
         if (tid == 0) atomicOr(g.error, ERR_GATE);
         continue;
       }
@@ -1353,7 +1468,7 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
         wg_matrix_1q(sites + q * slot, dims[q], dims[q + 1], g.mats + ((long)st * g.mats_stride + g.mat[i]) * 16, jl);
         continue;
       }
-      if (!is_two_qubit(o) && !(CHAN && o == OP_K1)) {  // Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
+      if (!is_two_qubit<CHAN>(o) && !(CHAN && o == OP_K1)) {  // Rx: [[c, -i s], [-i s, c]];  Ry: [[c, -s], [s, c]]
         cd* t = sites + q * slot;
         const int l = dims[q], r = dims[q + 1];
         const double th = 0.5 * M_PI * alpha[i];
@@ -1477,7 +1592,17 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
       const int m = 2 * l, nn = 2 * r;
       if (mid >= 32) wg_gemm_mfma(TH, m, nn, mid, a0, mid, 1, a1, nn, 1);  // theta[(a,p)][(p',c)]: on the matrix cores from bond 32 on
       else wg_gemm<false, false>(TH, m, nn, mid, a0, mid, 1, a1, nn, 1);
-      if (o == OP_M2) {  // a 4x4 from the table: one pass over theta
+      if (CHAN && o == OP_K2) {  // a two-qubit Kraus channel: the branch is chosen and applied on theta, the SVD below is the gate's
+        wg_channel_2q(TH, l, r, g.chan, st, i, jl, &sh);
+        if (!sh.flag) {  // an impossible outcome: the program of this state stops here (the sites are as they were), the call fails naming it
+          if (tid == 0) {
+            atomicOr(g.error, ERR_CHANNEL);
+            if (atomicCAS(g.error + 26, 0, st + 1) == 0) g.error[27] = i;
+          }
+          outgrown = true;
+          continue;
+        }
+      } else if (o == OP_M2) {  // a 4x4 from the table: one pass over theta
         wg_matrix_2q(TH, l, r, g.mats + ((long)st * g.mats_stride + g.mat[i]) * 16, jl);
       } else {
         const double th = 0.5 * M_PI * alpha[i];
@@ -1527,7 +1652,7 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
       }
       int nxt = q;
       for (int j2 = i + 1; j2 < g.n_ops; ++j2)
-        if (is_two_qubit(g.op[j2])) {
+        if (is_two_qubit<CHAN>(g.op[j2])) {
           nxt = g.q0[j2];
           break;
         }

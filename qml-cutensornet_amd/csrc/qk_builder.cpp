@@ -34,10 +34,11 @@ zungqr_t p_zungqr = nullptr;
 zgemm_t p_zgemm = nullptr;
 
 // ansatz.py.  Codes 8 and 9 are the matrix gates: valid only in a program that comes with a matrix table (N_OPS_MAT codes then).
-// Code 10 is the one-qubit Kraus channel: valid only in a program that comes with a channel table.
-enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10, OP_K1 = 10 };
+// Code 10 is the one-qubit Kraus channel: valid only in a program that comes with a channel table; code 11 the two-qubit Kraus
+// channel on (q0, q0+1): valid only in a program that comes with a two-qubit channel table.
+enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10, OP_K1 = 10, OP_K2 = 11 };
 
-inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ || o == OP_M2; }
+inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ || o == OP_M2 || o == OP_K2; }
 
 // sum_s m[s] t[s] over n terms in the fixed order of the matrix gates: column 0 first, ascending, the real and the imaginary part
 // each one chain of fused multiply-adds (the device builder's mat_dot, qk_build_kernels.h, does the same arithmetic)
@@ -77,18 +78,23 @@ std::string check_table(int n_ops, const int8_t* op, int n_mats, const cd* mats,
   return "";
 }
 
-// The channel table of a program and the names of one trajectory (qkb_simulate_channels); n_channels = 0: none, code 10 is unknown.
+// The channel tables of a program and the names of one trajectory (qkb_simulate_channels2); n_channels = 0: no one-qubit table, code 10
+// is unknown; n_channels2 = 0: no two-qubit table, code 11 is unknown.
 struct Channels {
   int n_channels = 0;
   const cd* kraus = nullptr;        // [n_channels][4][2][2], K[s'][s]
   const int32_t* n_kraus = nullptr; // [n_channels] 1..4
-  const int32_t* channel = nullptr; // [n_ops], read where op is 10
+  int n_channels2 = 0;
+  const cd* kraus2 = nullptr;        // [n_channels2][16][4][4], K[(p,p')][(s,s')], qubit q0 most significant
+  const int32_t* n_kraus2 = nullptr; // [n_channels2] 1..16
+  const int32_t* channel = nullptr; // [n_ops], read where op is 10 (index into kraus) or 11 (into kraus2)
   const int32_t* branch = nullptr;  // [n_ops] -1: drawn, k: forced
   uint64_t seed = 0;
   uint32_t state_index = 0, trajectory = 0, first_gate = 0;
   double* logw_out = nullptr;
-  int8_t* branches_out = nullptr;   // [channel gates of the program]
+  int8_t* branches_out = nullptr;   // [channel gates of the program, codes 10 and 11 in program order]
   double* margin_out = nullptr;
+  bool any() const { return n_channels > 0 || n_channels2 > 0; }
 };
 
 // Philox4x32-10 and the uniform of its first two words, written out as in qk_local_plan.h (smp_philox, smp_uniform) and
@@ -104,34 +110,71 @@ double channel_uniform(uint64_t seed, uint32_t gate, uint32_t trajectory, uint32
   return (double)(((uint64_t)(c0 >> 5) << 26) + (uint64_t)(c1 >> 6)) * (1.0 / 9007199254740992.0);
 }
 
-// The channel gates of a program, checked before anything runs: the channel inside the table, 1..4 matrices, finite entries, the
-// branch inside -1..m-1, a drawn channel trace preserving to 1e-12, the qubit inside the register.  Empty string, or what is wrong.
+// The channel gates of a program, checked before anything runs: the channel inside its table, 1..4 matrices (1..16 for the two-qubit
+// channel of code 11), finite entries, the branch inside -1..m-1, a drawn channel trace preserving to 1e-12, the qubit (pair) inside
+// the register.  Empty string, or what is wrong.
 std::string check_channels(int n_qubits, int n_ops, const int8_t* op, const int32_t* q0, const Channels& ch) {
   for (int i = 0; i < n_ops; ++i) {
-    if (op[i] != OP_K1) continue;
-    const std::string at = "gate " + std::to_string(i) + ": ";
+    if (op[i] != OP_K1 && op[i] != OP_K2) continue;
+    const bool two = op[i] == OP_K2;
+    const int d = two ? 4 : 2, n_table = two ? ch.n_channels2 : ch.n_channels;  // d x d matrices, at most d * d of them
+    const std::string at = "gate " + std::to_string(i) + ": ", kind = two ? "two-qubit channel " : "channel ";
     const int c = ch.channel[i], b = ch.branch[i];
-    if (c < 0 || c >= ch.n_channels) return at + "channel index " + std::to_string(c) + " outside 0.." + std::to_string(ch.n_channels - 1);
-    const int m = ch.n_kraus[c];
-    if (m < 1 || m > 4) return at + "channel " + std::to_string(c) + " has " + std::to_string(m) + " Kraus matrices (1..4)";
-    const cd* K = ch.kraus + (size_t)c * 16;
-    for (int e = 0; e < 4 * m; ++e)
-      if (!std::isfinite(K[e].real()) || !std::isfinite(K[e].imag())) return at + "a Kraus matrix of channel " + std::to_string(c) + " has an entry that is not finite";
+    if (c < 0 || c >= n_table) return at + kind + "index " + std::to_string(c) + " outside 0.." + std::to_string(n_table - 1);
+    const int m = (two ? ch.n_kraus2 : ch.n_kraus)[c];
+    if (m < 1 || m > d * d) return at + kind + std::to_string(c) + " has " + std::to_string(m) + " Kraus matrices (1.." + std::to_string(d * d) + ")";
+    const cd* K = (two ? ch.kraus2 : ch.kraus) + (size_t)c * d * d * d * d;
+    for (int e = 0; e < d * d * m; ++e)
+      if (!std::isfinite(K[e].real()) || !std::isfinite(K[e].imag())) return at + "a Kraus matrix of " + kind + std::to_string(c) + " has an entry that is not finite";
     if (b < -1 || b >= m) return at + "branch " + std::to_string(b) + " outside -1.." + std::to_string(m - 1);
     if (b < 0) {
       double dev = 0;
-      for (int a = 0; a < 2; ++a)
-        for (int d = 0; d < 2; ++d) {
-          cd g = (a == d) ? cd(-1, 0) : cd(0, 0);
+      for (int a = 0; a < d; ++a)
+        for (int e = 0; e < d; ++e) {
+          cd g = (a == e) ? cd(-1, 0) : cd(0, 0);
           for (int k = 0; k < m; ++k)
-            for (int r = 0; r < 2; ++r) g += std::conj(K[k * 4 + r * 2 + a]) * K[k * 4 + r * 2 + d];
+            for (int r = 0; r < d; ++r) g += std::conj(K[(k * d + r) * d + a]) * K[(k * d + r) * d + e];
           dev = std::max(dev, std::abs(g));
         }
-      if (!(dev <= 1e-12)) return at + "the drawn channel " + std::to_string(c) + " is not trace preserving (max |sum K^H K - 1| > 1e-12)";
+      if (!(dev <= 1e-12)) return at + "the drawn " + kind + std::to_string(c) + " is not trace preserving (max |sum K^H K - 1| > 1e-12)";
     }
-    if (q0[i] < 0 || q0[i] >= n_qubits) return at + "channel on a qubit outside the register";
+    if (q0[i] < 0 || q0[i] + (two ? 1 : 0) >= n_qubits) return at + kind + "on a qubit outside the register";
   }
   return "";
+}
+
+// The branch of channel gate i with the probabilities p[m] (tot = p_0 + .. in ascending order): the forced one, or drawn: the first k
+// with p_k > 0 and u tot < p_0 + .. + p_k, else the last k with p_k > 0, u the uniform of counter (first_gate + i, trajectory,
+// state_index, 2); `margin` takes the smallest |u tot - cum| / tot over the thresholds.  -1 with g_err set when the outcome is
+// impossible: tot 0 or not finite in a draw, p_b 0 or not finite.
+int channel_branch(const Channels& ch, int i, int forced, int m, const double* p, double* margin) {
+  double tot = 0;
+  for (int k = 0; k < m; ++k) tot += p[k];
+  const auto at = [&] { return "state " + std::to_string(ch.state_index) + ", gate " + std::to_string(ch.first_gate + (uint32_t)i) + ": "; };  // error paths only
+  int b = forced;
+  if (forced < 0) {
+    if (!(tot > 0.0) || !std::isfinite(tot)) {
+      g_err = at() + "the branch probabilities of the channel sum to 0 or are not finite";
+      return -1;
+    }
+    const double u = channel_uniform(ch.seed, ch.first_gate + (uint32_t)i, ch.trajectory, ch.state_index);
+    double cum = 0;
+    int last = -1;
+    for (int k = 0; k < m; ++k) {
+      cum += p[k];
+      if (k < m - 1) *margin = std::min(*margin, std::fabs(u * tot - cum) / tot);
+      if (p[k] > 0.0) {
+        last = k;
+        if (b < 0 && u * tot < cum) b = k;
+      }
+    }
+    if (b < 0) b = last;
+  }
+  if (!(p[b] > 0.0) || !std::isfinite(p[b])) {
+    g_err = at() + "branch " + std::to_string(b) + " of the channel has probability 0 or one that is not finite (an impossible outcome was post-selected?)";
+    return -1;
+  }
+  return b;
 }
 
 // row-major C[m x n] = A[m x k] * B[k x n]  (as column-major C^T = B^T A^T)
@@ -283,6 +326,33 @@ int qkb_simulate_channels(int32_t n_qubits, int32_t n_ops, const int8_t* op, con
   ch.logw_out = logw_out, ch.branches_out = branches_out, ch.margin_out = margin_out;
   return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, ch, dims_out, tensors_out, n_complex_out, fidelity_out);
 }
+// qkb_simulate_channels with a two-qubit channel table: with n_channels2 > 0 the program may also hold op code 11, a two-qubit Kraus
+// channel on (q0, q0+1).  Channel c is n_kraus2[c] (1..16) matrices kraus2[c][k][(p,p')][(s,s')] (complex128 [n_channels2][16][4][4],
+// (re, im); the index convention of the 4x4 matrix gates, q0 most significant); gate i reads channel[i] -- an index into kraus2 where
+// op is 11 -- and branch[i].  The step: the centre is brought onto the pair and theta = A_q A_q+1 formed as for any two-qubit gate;
+// N = sum |theta|^2, p_k = sum_{a,c} |K_k theta[a,(.,.),c]|^2 in ascending order of (a, c), the branch as for code 10 (same uniform);
+// theta <- (K_b / sqrt(p_b)) theta, then the SVD, truncation, fidelity product and centre placement of a two-qubit gate; logw +=
+// log(p_b / N).  branches_out counts the gates of codes 10 and 11 together in program order.  Errors as qkb_simulate_channels.  Either
+// table may be absent; with n_channels2 = 0 the call IS qkb_simulate_channels.
+int qkb_simulate_channels2(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
+                           int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
+                           const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate,
+                           int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out,
+                           double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out) {
+  if (n_channels2 == 0)
+    return qkb_simulate_channels(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, n_channels, kraus, n_kraus, channel, branch, seed,
+                                 state_index, trajectory, first_gate, dims_out, tensors_out, n_complex_out, fidelity_out, logw_out, branches_out, margin_out);
+  Channels ch;
+  if (n_channels < 0 || n_channels2 < 0 || !kraus2 || !n_kraus2 || !channel || !branch || (n_channels > 0 && (!kraus || !n_kraus))) {
+    g_err = "a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch; a two-qubit one n_channels2 >= 0, kraus2 and n_kraus2";
+    return -8;
+  }
+  if (n_channels > 0) ch.n_channels = n_channels, ch.kraus = reinterpret_cast<const cd*>(kraus), ch.n_kraus = n_kraus;
+  ch.n_channels2 = n_channels2, ch.kraus2 = reinterpret_cast<const cd*>(kraus2), ch.n_kraus2 = n_kraus2, ch.channel = channel, ch.branch = branch;
+  ch.seed = seed, ch.state_index = state_index, ch.trajectory = trajectory, ch.first_gate = first_gate;
+  ch.logw_out = logw_out, ch.branches_out = branches_out, ch.margin_out = margin_out;
+  return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, ch, dims_out, tensors_out, n_complex_out, fidelity_out);
+}
 }  // extern "C"
 
 static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
@@ -300,15 +370,15 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
   }
   const int n_codes = n_mats > 0 ? N_OPS_MAT : N_OPS;
   for (int i = 0; i < n_ops; ++i)
-    if ((op[i] < 0 || op[i] >= n_codes) && !(ch.n_channels > 0 && op[i] == OP_K1)) {
-      g_err = "unknown gate op code " + std::to_string((int)op[i]) + " (valid: 0.." + std::to_string(n_codes - 1) + (ch.n_channels > 0 ? ", 10)" : ")");
+    if ((op[i] < 0 || op[i] >= n_codes) && !(ch.n_channels > 0 && op[i] == OP_K1) && !(ch.n_channels2 > 0 && op[i] == OP_K2)) {
+      g_err = "unknown gate op code " + std::to_string((int)op[i]) + " (valid: 0.." + std::to_string(n_codes - 1) + (ch.n_channels > 0 ? ", 10" : "") + (ch.n_channels2 > 0 ? ", 11)" : ")");
       return -7;
     }
   if (n_mats > 0) {
     g_err = check_table(n_ops, op, n_mats, mats, mat);
     if (!g_err.empty()) return -8;
   }
-  if (ch.n_channels > 0) {
+  if (ch.any()) {
     g_err = check_channels(n, n_ops, op, q0, ch);
     if (!g_err.empty()) return -8;
   }
@@ -434,32 +504,8 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
           N += std::norm(v[0]) + std::norm(v[1]);
           for (int k = 0; k < m; ++k) p[k] += std::norm(mat_dot(K + k * 4, v, 2)) + std::norm(mat_dot(K + k * 4 + 2, v, 2));
         }
-      double tot = 0;
-      for (int k = 0; k < m; ++k) tot += p[k];
-      const auto at = [&] { return "state " + std::to_string(ch.state_index) + ", gate " + std::to_string(ch.first_gate + (uint32_t)i) + ": "; };  // error paths only
-      int b = forced;
-      if (forced < 0) {
-        if (!(tot > 0.0) || !std::isfinite(tot)) {
-          g_err = at() + "the branch probabilities of the channel sum to 0 or are not finite";
-          return -9;
-        }
-        const double u = channel_uniform(ch.seed, ch.first_gate + (uint32_t)i, ch.trajectory, ch.state_index);
-        double cum = 0;
-        int last = -1;
-        for (int k = 0; k < m; ++k) {
-          cum += p[k];
-          if (k < m - 1) margin = std::min(margin, std::fabs(u * tot - cum) / tot);
-          if (p[k] > 0.0) {
-            last = k;
-            if (b < 0 && u * tot < cum) b = k;
-          }
-        }
-        if (b < 0) b = last;
-      }
-      if (!(p[b] > 0.0) || !std::isfinite(p[b])) {
-        g_err = at() + "branch " + std::to_string(b) + " of the channel has probability 0 or one that is not finite (an impossible outcome was post-selected?)";
-        return -9;
-      }
+      const int b = channel_branch(ch, i, forced, m, p, &margin);
+      if (b < 0) return -9;
       const double s = std::sqrt(p[b]);
       const cd Kb[4] = {K[b * 4] / s, K[b * 4 + 1] / s, K[b * 4 + 2] / s, K[b * 4 + 3] / s};
       for (int a = 0; a < t.l; ++a)
@@ -505,6 +551,35 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
           TH(a, 1, 0, c) *= ph;
           TH(a, 1, 1, c) *= phc;
         }
+    } else if (o == OP_K2) {  // a two-qubit Kraus channel: code 10's branch logic on theta, then the SVD of any two-qubit gate
+      const int c = ch.channel[i], forced = ch.branch[i], nk = ch.n_kraus2[c];
+      const cd* K = ch.kraus2 + (size_t)c * 256;
+      double N = 0, p[16] = {0};
+      for (int a = 0; a < l; ++a)  // every sum in ascending order of (a, c)
+        for (int x = 0; x < r; ++x) {
+          const cd v[4] = {TH(a, 0, 0, x), TH(a, 0, 1, x), TH(a, 1, 0, x), TH(a, 1, 1, x)};
+          N += std::norm(v[0]) + std::norm(v[1]) + std::norm(v[2]) + std::norm(v[3]);
+          for (int k = forced < 0 ? 0 : forced; k < (forced < 0 ? nk : forced + 1); ++k) {  // a forced branch needs p_b only
+            const cd* Kk = K + k * 16;
+            p[k] += std::norm(mat_dot(Kk, v, 4)) + std::norm(mat_dot(Kk + 4, v, 4)) + std::norm(mat_dot(Kk + 8, v, 4)) + std::norm(mat_dot(Kk + 12, v, 4));
+          }
+        }
+      const int b = channel_branch(ch, i, forced, nk, p, &margin);
+      if (b < 0) return -9;
+      const double s = std::sqrt(p[b]);
+      cd Kb[16];
+      for (int e = 0; e < 16; ++e) Kb[e] = K[b * 16 + e] / s;
+      for (int a = 0; a < l; ++a)
+        for (int x = 0; x < r; ++x) {
+          const cd v[4] = {TH(a, 0, 0, x), TH(a, 0, 1, x), TH(a, 1, 0, x), TH(a, 1, 1, x)};
+          TH(a, 0, 0, x) = mat_dot(Kb, v, 4);
+          TH(a, 0, 1, x) = mat_dot(Kb + 4, v, 4);
+          TH(a, 1, 0, x) = mat_dot(Kb + 8, v, 4);
+          TH(a, 1, 1, x) = mat_dot(Kb + 12, v, 4);
+        }
+      logw += std::log(p[b] / N);
+      if (ch.branches_out) ch.branches_out[n_drawn] = (int8_t)b;
+      ++n_drawn;
     } else if (o == OP_M2) {  // a 4x4 from the table on (t00, t01, t10, t11)
       const cd* M = mats + (size_t)mat[i] * 16;
       for (int a = 0; a < l; ++a)

@@ -126,6 +126,8 @@ _SIGNATURES = [
                                      C.POINTER(_P)]),
     ("qk_build_mps_channels", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
                                         C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(_P)]),
+    ("qk_build_mps_channels2", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
+                                         C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.c_int32, _P, _P, C.POINTER(_P)]),
     ("qk_built_logw_at", C.c_int, [_P, C.c_int32, _P]),
     ("qk_built_num_channel_gates", C.c_int, [_P]),
     ("qk_built_branches", C.c_int, [_P, _P]),
@@ -310,23 +312,32 @@ def channel_uniform(seed, gate, trajectory, state):
 
 def with_noise(gates, channel_name, params, after="all"):
     """A gate list ``(name, qubits, params)`` with the channel ``(channel_name, [q], params)`` behind every gate (``after="all"``) or
-    behind every two-qubit gate (``after="two_qubit"``), on each qubit the gate touches, in the order the gate names them.  Gates
-    that are channels themselves get none.  The list goes to ``BoundCircuit.from_gates`` / ``as_bound_circuit`` or, with the
-    parameters in the place of the angle, to ``CircuitAnsatz``."""
-    from .ansatz import _CHANNEL_NAMES
+    behind every two-qubit gate (``after="two_qubit"``), on each qubit the gate touches, in the order the gate names them.  With
+    the name of a two-qubit channel (``Depolarizing2q``, ``CorrelatedPhaseFlip``, ..) and ``after="two_qubit"``, ONE channel
+    ``(channel_name, [a, b], params)`` goes behind every two-qubit gate, on its pair as the gate names it: correlated gate noise,
+    which no pair of one-qubit channels expresses (``after="all"`` is a ``ValueError`` then).  Gates that are channels themselves
+    get none.  The list goes to ``BoundCircuit.from_gates`` / ``as_bound_circuit`` or, with the parameters in the place of the
+    angle, to ``CircuitAnsatz``."""
+    from .ansatz import _CHANNEL2_NAMES, _CHANNEL_NAMES
 
-    if channel_name not in _CHANNEL_NAMES:
-        raise ValueError(f"unknown channel {channel_name!r} (supported: {', '.join(_CHANNEL_NAMES)})")
+    if channel_name not in _CHANNEL_NAMES and channel_name not in _CHANNEL2_NAMES:
+        raise ValueError(f"unknown channel {channel_name!r} (supported: {', '.join(_CHANNEL_NAMES + _CHANNEL2_NAMES)})")
     if after not in ("all", "two_qubit"):
         raise ValueError(f"after must be 'all' or 'two_qubit', got {after!r}")
+    pair = channel_name in _CHANNEL2_NAMES
+    if pair and after == "all":
+        raise ValueError(f"the two-qubit channel {channel_name!r} goes behind two-qubit gates only: after must be 'two_qubit'")
     out = []
     for g in gates:
         out.append(g)
         name, qubits = g[0], g[1]
         qs = [int(q) for q in (qubits if np.ndim(qubits) else [qubits])]
-        if (isinstance(name, str) and name in _CHANNEL_NAMES) or (after == "two_qubit" and len(qs) != 2):
+        if (isinstance(name, str) and (name in _CHANNEL_NAMES or name in _CHANNEL2_NAMES)) or (after == "two_qubit" and len(qs) != 2):
             continue
-        out.extend((channel_name, [q], params) for q in qs)
+        if pair:
+            out.append((channel_name, qs, params))
+        else:
+            out.extend((channel_name, [q], params) for q in qs)
     return out
 
 
@@ -1386,8 +1397,8 @@ class _GateProgram:
     circuit's ``mats`` is the same array bit for bit, otherwise stacked per state (stride n_mats).  ``QkError`` when the circuits do
     not share their gate structure.  The table goes to the C entry as it is: it validates indices and unitarity.
 
-    A channel table (op code 10) belongs to the gate structure: ``channel``, ``kraus`` and ``n_kraus`` must be the same for every
-    circuit; ``branch`` may differ per state (one row for all when they agree, stride 0, otherwise a row per state).  ``seed``,
+    The channel tables (op codes 10 and 11) belong to the gate structure: ``channel``, ``kraus`` and ``n_kraus``, ``kraus2`` and
+    ``n_kraus2`` must be the same for every circuit; ``branch`` may differ per state (one row for all when they agree, stride 0, otherwise a row per state).  ``seed``,
     ``state_index`` and ``trajectory`` (a scalar for all states, or one per state; ``None``: 0 .. n-1 and 0) name the trajectories,
     ``first_gate`` the position of the first gate in the uninterrupted program."""
 
@@ -1419,18 +1430,31 @@ class _GateProgram:
             else:
                 self.mats, self.stride = np.ascontiguousarray(np.stack(tables)), self.n_mats
         self.n_channels, self.bstride, self.kraus, self.n_kraus, self.channel, self.branch = 0, 0, None, None, None, None
-        has_chan = [getattr(c, "kraus", None) is not None and getattr(c, "n_kraus", None) is not None and getattr(c, "channel", None) is not None for c in circuits]
-        if any(has_chan):
-            k0 = np.ascontiguousarray(c0.kraus, dtype=np.complex128) if has_chan[0] else None
-            for c, h in zip(circuits, has_chan):
-                if not h or np.shape(c.kraus) != k0.shape or not (np.array_equal(c.channel, c0.channel) and np.array_equal(c.n_kraus, c0.n_kraus)
-                                                                    and np.ascontiguousarray(c.kraus, dtype=np.complex128).tobytes() == k0.tobytes()):
-                    raise QkError(f"{what}: the circuits of one call must share their gate structure (the channels of op code 10 and their table included)")
-            if k0.ndim != 4 or k0.shape[1:] != (4, 2, 2) or np.shape(c0.n_kraus) != k0.shape[:1] or np.shape(c0.channel) != self.op.shape:
-                raise QkError(f"{what}: the channel table must be [n_channels][4][2][2] with a count per channel and a channel per gate, got shapes {k0.shape}, "
-                              f"{np.shape(c0.n_kraus)} and {np.shape(c0.channel)}")
-            self.n_channels, self.kraus = int(k0.shape[0]), k0
-            self.n_kraus = np.ascontiguousarray(c0.n_kraus, dtype=np.int32)
+        self.n_channels2, self.kraus2, self.n_kraus2 = 0, None, None
+
+        def table(c, d):  # the table of d x d channels of circuit c: (kraus, n_kraus) or None
+            k, nk = (getattr(c, "kraus", None), getattr(c, "n_kraus", None)) if d == 2 else (getattr(c, "kraus2", None), getattr(c, "n_kraus2", None))
+            return None if k is None or nk is None or getattr(c, "channel", None) is None else (np.ascontiguousarray(k, dtype=np.complex128), nk)
+
+        for d in (2, 4):
+            tabs = [table(c, d) for c in circuits]
+            if not any(t is not None for t in tabs):
+                continue
+            code = 10 if d == 2 else 11
+            t0 = tabs[0]
+            for c, t in zip(circuits, tabs):
+                if t is None or t0 is None or t[0].shape != t0[0].shape or not (np.array_equal(c.channel, c0.channel) and np.array_equal(t[1], t0[1])
+                                                                                 and t[0].tobytes() == t0[0].tobytes()):
+                    raise QkError(f"{what}: the circuits of one call must share their gate structure (the channels of op code {code} and their table included)")
+            k0 = t0[0]
+            if k0.ndim != 4 or k0.shape[1:] != (d * d, d, d) or np.shape(t0[1]) != k0.shape[:1] or np.shape(c0.channel) != self.op.shape:
+                raise QkError(f"{what}: the {'two-qubit ' if d == 4 else ''}channel table must be [n_channels][{d * d}][{d}][{d}] with a count per channel and a channel per gate, "
+                              f"got shapes {k0.shape}, {np.shape(t0[1])} and {np.shape(c0.channel)}")
+            if d == 2:
+                self.n_channels, self.kraus, self.n_kraus = int(k0.shape[0]), k0, np.ascontiguousarray(t0[1], dtype=np.int32)
+            else:
+                self.n_channels2, self.kraus2, self.n_kraus2 = int(k0.shape[0]), k0, np.ascontiguousarray(t0[1], dtype=np.int32)
+        if self.n_channels or self.n_channels2:
             self.channel = np.ascontiguousarray(c0.channel, dtype=np.int32)
             rows = [np.full(self.op.shape, -1, dtype=np.int32) if c.branch is None else np.ascontiguousarray(c.branch, dtype=np.int32) for c in circuits]
             if any(r.shape != self.op.shape for r in rows):
@@ -1460,13 +1484,17 @@ class _GateProgram:
         h = _P()
         head = (ctx._h, self.ns, self.n, n_ops, self.op.ctypes.data, self.q0.ctypes.data, self.alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero),
                 int(max_bond), flags)
-        if self.n_channels and n_ops:
+        if (self.n_channels or self.n_channels2) and n_ops:
             if cps is None:
                 cps = np.array([n_ops], dtype=np.int32)
-            _check(lib().qk_build_mps_channels(*head, int(cps.shape[0]), cps.ctypes.data, src, src_j, self.n_mats, self.mats.ctypes.data if self.n_mats else None, self.stride,
-                                               self.mat.ctypes.data if self.n_mats else None, self.n_channels, self.kraus.ctypes.data, self.n_kraus.ctypes.data,
-                                               self.channel.ctypes.data, self.branch.ctypes.data, self.bstride, self.seed, self.state_index.ctypes.data,
-                                               self.trajectory.ctypes.data, self.first_gate, C.byref(h)), "qk_build_mps_channels")
+            chan = (int(cps.shape[0]), cps.ctypes.data, src, src_j, self.n_mats, self.mats.ctypes.data if self.n_mats else None, self.stride,
+                    self.mat.ctypes.data if self.n_mats else None, self.n_channels, self.kraus.ctypes.data if self.n_channels else None,
+                    self.n_kraus.ctypes.data if self.n_channels else None, self.channel.ctypes.data, self.branch.ctypes.data, self.bstride, self.seed,
+                    self.state_index.ctypes.data, self.trajectory.ctypes.data, self.first_gate)
+            if self.n_channels2:
+                _check(lib().qk_build_mps_channels2(*head, *chan, self.n_channels2, self.kraus2.ctypes.data, self.n_kraus2.ctypes.data, C.byref(h)), "qk_build_mps_channels2")
+            else:
+                _check(lib().qk_build_mps_channels(*head, *chan, C.byref(h)), "qk_build_mps_channels")
             return h
         if cps is None and (self.n_mats == 0 or n_ops == 0):  # no snapshots, no table: the plain entry
             _check(lib().qk_build_mps(*head, C.byref(h)), "qk_build_mps")
@@ -1767,7 +1795,7 @@ class Context:
         prog = _GateProgram("build_mps_scan", circuits, seed, state_index, trajectory, base if first_gate is None else first_gate)
         n, ns = prog.n, prog.ns
         h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0), cps, src, src_j)
-        scan = BuiltScan(self, h, ns, n, np.flatnonzero(prog.op == 10) if prog.n_channels else None)
+        scan = BuiltScan(self, h, ns, n, np.flatnonzero((prog.op == 10) | (prog.op == 11)) if prog.n_channels or prog.n_channels2 else None)
         scan.first_gate = prog.first_gate
         return scan
 

@@ -26,13 +26,13 @@ from statistics import mean, median
 import numpy as np
 
 try:  # normal case: imported as qml_cutensornet_amd.gpu_backend.kernel_state_ansatz
-    from ..ansatz import OP_M2, OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit, check_depths, reject_channels  # noqa: F401
+    from ..ansatz import OP_K2, OP_M2, OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit, check_depths, reject_channels  # noqa: F401
     from .. import engine as _engine
     from ..dist import assemble_gram, comm_allgather, exchange_sets
     from ..mps import MPS, simulate, simulate_many  # noqa: F401
 except ImportError:  # imported top-level as gpu_backend.kernel_state_ansatz
     import qml_cutensornet_amd as _pkg  # noqa: F401
-    from qml_cutensornet_amd.ansatz import OP_M2, OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit, check_depths, reject_channels  # noqa: F401
+    from qml_cutensornet_amd.ansatz import OP_K2, OP_M2, OP_XX, OP_YY, OP_ZZ, KernelStateAnsatz, as_bound_circuit, check_depths, reject_channels  # noqa: F401
     from qml_cutensornet_amd import engine as _engine
     from qml_cutensornet_amd.dist import assemble_gram, comm_allgather, exchange_sets
     from qml_cutensornet_amd.mps import MPS, simulate, simulate_many  # noqa: F401
@@ -51,7 +51,8 @@ _PILOT_MIN_STATES = 24  # below this a share goes to the device builder as a who
 
 def _entangling_weight(circuit):
     """Cost proxy of a circuit: sum of sin^2(pi alpha) over its XXPhase, YYPhase and ZZPhase gates (alpha in half-turns:
-    0 and 1 do not entangle), plus 1 -- the most such a gate can add -- for every 4x4 matrix gate (op code 9: its entangling
+    0 and 1 do not entangle), plus 1 -- the most such a gate can add -- for every 4x4 matrix gate and every two-qubit Kraus channel (op
+    codes 9 and 11: their entangling
     power is not worth a decomposition here, and without the term a circuit of matrix gates would weigh 0 and always be
     expected to keep small bonds).  It tracks the bonds a state will reach.  The device builder orders its queue by the
     first part alone: the matrix gates of the states of one call share their positions, so the constant would not reorder them.
@@ -60,7 +61,7 @@ def _entangling_weight(circuit):
     does not outweigh to the host -- all of them, if the pilot drops any."""
     op = np.asarray(circuit.op)
     xx = np.isin(op, (OP_XX, OP_YY, OP_ZZ))
-    return float((np.sin(np.pi * np.asarray(circuit.alpha)[xx]) ** 2).sum()) + float(np.count_nonzero(op == OP_M2))
+    return float((np.sin(np.pi * np.asarray(circuit.alpha)[xx]) ** 2).sum()) + float(np.count_nonzero((op == OP_M2) | (op == OP_K2)))
 
 
 def _hybrid_build(ctx, circuits, fidelity, cap, host_workers, is_root, label):

@@ -22,7 +22,7 @@ import numpy as np
 from scipy.linalg import qr as _qr
 from scipy.linalg import svd as _svd
 
-from .ansatz import (OP_H, OP_K1, OP_M1, OP_M2, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_channel_gates, check_checkpoints, check_matrix_gates,
+from .ansatz import (OP_H, OP_K1, OP_K2, OP_M1, OP_M2, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_channel_gates, check_checkpoints, check_matrix_gates,
                      is_two_qubit, reject_channels)
 
 _SQRT_HALF = 0.7071067811865476
@@ -461,6 +461,7 @@ def _native_builder():
                                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p,
                                                   C.POINTER(C.c_double)]
+            lib.qkb_simulate_channels2.argtypes = lib.qkb_simulate_channels.argtypes[:20] + [C.c_int32, C.c_void_p, C.c_void_p] + lib.qkb_simulate_channels.argtypes[20:]
             lib.qkb_free.argtypes = [C.c_void_p]
             if blas and lib.qkb_init(os.path.realpath(blas[0]).encode()) == 0:
                 _NATIVE = lib
@@ -472,7 +473,7 @@ def _native_builder():
 def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None, seed=0, state_index=0,
                     trajectory=0, first_gate=0, margin=False):
     """``simulate`` through the native builder: same algorithm and LAPACK routines, no interpreter in the gate loop.  A circuit with
-    a channel table goes through ``qkb_simulate_channels`` (the trajectory arguments and ``margin`` as in ``simulate``)."""
+    a channel table goes through ``qkb_simulate_channels``, one with a two-qubit channel table through ``qkb_simulate_channels2`` (the trajectory arguments and ``margin`` as in ``simulate``)."""
     import ctypes as C
 
     lib = _native_builder()
@@ -494,22 +495,35 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
         n_mats = int(mats.shape[0])
     seed, state_index, trajectory, first_gate = _trajectory_ids(seed, state_index, trajectory, first_gate)
     logw, worst, branches = C.c_double(0.0), C.c_double(np.inf), np.zeros(0, dtype=np.int8)
-    if circuit.kraus is not None and circuit.n_kraus is not None and circuit.channel is not None:
-        # the channel table, handed over as it is: the native builder validates it
-        kraus = np.ascontiguousarray(circuit.kraus, dtype=np.complex128)
-        n_kraus = np.ascontiguousarray(circuit.n_kraus, dtype=np.int32)
+    one = circuit.kraus is not None and circuit.n_kraus is not None
+    two = circuit.kraus2 is not None and circuit.n_kraus2 is not None
+    if circuit.channel is not None and (one or two):
+        # the channel tables, handed over as they are: the native builder validates them
+        tables = []
+        for d, k, nk in ((2, circuit.kraus, circuit.n_kraus) if one else (None,) * 3, (4, circuit.kraus2, circuit.n_kraus2) if two else (None,) * 3):
+            if d is None:
+                tables.append((0, None, None))
+                continue
+            k, nk = np.ascontiguousarray(k, dtype=np.complex128), np.ascontiguousarray(nk, dtype=np.int32)
+            if k.ndim != 4 or k.shape[1:] != (d * d, d, d) or nk.shape != k.shape[:1]:
+                raise ValueError(f"the channel table must be [n_channels][{d * d}][{d}][{d}] with a count per channel, got shapes {k.shape}, {nk.shape}")
+            tables.append((int(k.shape[0]), k, nk))
+        (n1, kraus, n_kraus), (n2, kraus2, n_kraus2) = tables
         channel = np.ascontiguousarray(circuit.channel, dtype=np.int32)
         branch = np.full(op.shape, -1, dtype=np.int32) if circuit.branch is None else np.ascontiguousarray(circuit.branch, dtype=np.int32)
-        if kraus.ndim != 4 or kraus.shape[1:] != (4, 2, 2) or n_kraus.shape != kraus.shape[:1] or channel.shape != op.shape or branch.shape != op.shape:
-            raise ValueError(f"the channel table must be [n_channels][4][2][2] with a count per channel and a channel and a branch per gate, got shapes "
-                             f"{kraus.shape}, {n_kraus.shape}, {channel.shape}, {branch.shape}")
-        branches = np.full(max(1, int(np.count_nonzero(op == OP_K1))), -1, dtype=np.int8)
-        rc = lib.qkb_simulate_channels(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
-                                       float(value_of_zero), int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None,
-                                       int(kraus.shape[0]), kraus.ctypes.data, n_kraus.ctypes.data, channel.ctypes.data, branch.ctypes.data, seed, state_index,
-                                       trajectory, first_gate, dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid), C.byref(logw), branches.ctypes.data,
-                                       C.byref(worst))
-        branches = branches[: int(np.count_nonzero(op == OP_K1))]
+        if channel.shape != op.shape or branch.shape != op.shape:
+            raise ValueError(f"a program with a channel table needs a channel and a branch per gate, got shapes {channel.shape}, {branch.shape}")
+        n_kgates = int(np.count_nonzero((op == OP_K1) | (op == OP_K2)))
+        branches = np.full(max(1, n_kgates), -1, dtype=np.int8)
+        head = (n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero), int(max_bond or 0),
+                n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None, n1, kraus.ctypes.data if n1 else None,
+                n_kraus.ctypes.data if n1 else None, channel.ctypes.data, branch.ctypes.data, seed, state_index, trajectory, first_gate)
+        tail = (dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid), C.byref(logw), branches.ctypes.data, C.byref(worst))
+        if n2:
+            rc = lib.qkb_simulate_channels2(*head, n2, kraus2.ctypes.data, n_kraus2.ctypes.data, *tail)
+        else:
+            rc = lib.qkb_simulate_channels(*head, *tail)
+        branches = branches[:n_kgates]
     else:
         rc = lib.qkb_simulate_gates(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
                                     float(value_of_zero), int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None,
@@ -708,6 +722,12 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
     and a 4x4 on (q0, q0+1); ``ValueError`` for a table entry that is not unitary, an index outside the table or a gate outside
     the register.
 
+    A circuit with a two-qubit channel table (``kraus2``, ``n_kraus2``) may hold op code 11, a two-qubit Kraus channel on (q, q+1):
+    the centre is brought into the pair and ``theta = A_q A_{q+1}`` formed as for any two-qubit gate; ``N = sum |theta|^2``, ``p_k = sum
+    |K_k theta|^2``, the branch as for code 10 below (same uniform); ``theta <- (K_b / sqrt(p_b)) theta``, then the SVD, truncation,
+    fidelity product and centre placement of a two-qubit gate -- the bond may shrink or be cut --, and ``logw += log(p_b / N)``.
+    ``branches`` counts the gates of both codes in program order.
+
     A circuit with a channel table (``channel``, ``branch``, ``kraus``, ``n_kraus``) may hold op code 10, a one-qubit Kraus channel:
     the centre is brought onto site q exactly, ``N = sum |A_q|^2``, ``p_k = sum |K_k A_q|^2``, ``tot = p_0 + .. + p_{m-1}``; the branch b
     is ``branch[i]`` or, drawn, the first k with ``p_k > 0`` and ``u tot < p_0 + .. + p_k`` (none: the last k with ``p_k > 0``) for
@@ -716,10 +736,42 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
     smallest ``|u tot - cum| / tot`` over the thresholds of all draws (inf without one).  ``ValueError`` naming the state and the gate
     for an impossible outcome (``p_b`` 0 or not finite, ``tot`` 0 in a draw)."""
     n = circuit.n_qubits
-    chan = check_channel_gates(circuit.op, circuit.q0, n, circuit.channel, circuit.branch, circuit.kraus, circuit.n_kraus)
-    mat, mats = check_matrix_gates(circuit.op, circuit.mat, circuit.mats, with_channels=chan is not None)  # (None, None): no table, codes 8 and 9 are unknown
+    chan = check_channel_gates(circuit.op, circuit.q0, n, circuit.channel, circuit.branch, circuit.kraus, circuit.n_kraus, circuit.kraus2, circuit.n_kraus2)
+    mat, mats = check_matrix_gates(circuit.op, circuit.mat, circuit.mats, with_channels=chan is not None and chan[2] is not None,
+                                   with_channels2=chan is not None and chan[4] is not None)  # (None, None): no table, codes 8 and 9 are unknown
     seed, state_index, trajectory, first_gate = _trajectory_ids(seed, state_index, trajectory, first_gate)
     logw, branches, worst = 0.0, [], np.inf
+
+    def take_branch(i, forced, p):
+        """The branch of channel gate i with probabilities p (the forced one, or drawn), and the running margin."""
+        from .engine import channel_uniform
+
+        m, low = len(p), worst
+        tot = 0.0
+        for k in range(m):
+            tot += p[k]
+        where = f"state {state_index}, gate {first_gate + i}"
+        if forced >= 0:
+            b = forced
+        else:
+            if not (tot > 0.0 and np.isfinite(tot)):
+                raise ValueError(f"simulate: {where}: the branch probabilities of the channel sum to {tot!r}")
+            u = float(channel_uniform(seed, first_gate + i, trajectory, state_index))
+            b, cum, last = -1, 0.0, -1
+            for k in range(m):
+                cum += p[k]
+                if k < m - 1:
+                    low = min(low, abs(u * tot - cum) / tot)
+                if p[k] > 0.0:
+                    last = k
+                    if b < 0 and u * tot < cum:
+                        b = k
+            if b < 0:
+                b = last
+        if not (p[b] > 0.0 and np.isfinite(p[b])):
+            raise ValueError(f"simulate: {where}: branch {b} of the channel has probability {p[b]!r} (an impossible outcome was post-selected?)")
+        return b, low
+
     for i, (o, q) in enumerate(zip(circuit.op.tolist(), circuit.q0.tolist())):
         if not 0 <= q < n - (1 if is_two_qubit(o) else 0):
             raise ValueError(f"gate {i} on a qubit outside the register of {n}")
@@ -782,8 +834,6 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             centre -= 1
 
         if o == OP_K1:  # the channel step: the centre stays on q, the bonds do not change
-            from .engine import channel_uniform
-
             c, forced = int(chan[0][i]), int(chan[1][i])
             m = int(chan[3][c])
             K = chan[2][c]
@@ -794,29 +844,7 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             for k in range(m):
                 y0, y1 = K[k, 0, 0] * t0 + K[k, 0, 1] * t1, K[k, 1, 0] * t0 + K[k, 1, 1] * t1
                 p.append(float((y0.real * y0.real + y0.imag * y0.imag + y1.real * y1.real + y1.imag * y1.imag).sum()))
-            tot = 0.0
-            for k in range(m):
-                tot += p[k]
-            where = f"state {state_index}, gate {first_gate + i}"
-            if forced >= 0:
-                b = forced
-            else:
-                if not (tot > 0.0 and np.isfinite(tot)):
-                    raise ValueError(f"simulate: {where}: the branch probabilities of the channel sum to {tot!r}")
-                u = float(channel_uniform(seed, first_gate + i, trajectory, state_index))
-                b, cum, last = -1, 0.0, -1
-                for k in range(m):
-                    cum += p[k]
-                    if k < m - 1:
-                        worst = min(worst, abs(u * tot - cum) / tot)
-                    if p[k] > 0.0:
-                        last = k
-                        if b < 0 and u * tot < cum:
-                            b = k
-                if b < 0:
-                    b = last
-            if not (p[b] > 0.0 and np.isfinite(p[b])):
-                raise ValueError(f"simulate: {where}: branch {b} of the channel has probability {p[b]!r} (an impossible outcome was post-selected?)")
+            b, worst = take_branch(i, forced, p)
             Kb = K[b] / np.sqrt(p[b])
             A[q] = np.stack((Kb[0, 0] * t0 + Kb[0, 1] * t1, Kb[1, 0] * t0 + Kb[1, 1] * t1), axis=1)
             logw += float(np.log(p[b] / N))
@@ -837,6 +865,18 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             theta = theta * np.array([[ph.conjugate(), ph], [ph, ph.conjugate()]])[None, :, :, None]
         elif o == OP_M2:  # a 4x4 from the table: new[(p,p')] = sum M[(p,p')][(s,s')] old[(s,s')]
             theta = np.einsum("pqst,lstr->lpqr", mats[mat[i]].reshape(2, 2, 2, 2), theta)
+        elif o == OP_K2:  # a two-qubit Kraus channel: code 10's branch logic on theta, then the SVD of any two-qubit gate
+            c, forced = int(chan[0][i]), int(chan[1][i])
+            K = chan[4][c, : int(chan[5][c])].reshape(-1, 2, 2, 2, 2)
+            N = float((theta.real * theta.real + theta.imag * theta.imag).sum())
+            p = [0.0] * K.shape[0]
+            for k in range(K.shape[0]) if forced < 0 else [forced]:  # a forced branch needs p_b only
+                y = np.einsum("pqst,lstr->lpqr", K[k], theta)
+                p[k] = float((y.real * y.real + y.imag * y.imag).sum())
+            b, worst = take_branch(i, forced, p)
+            theta = np.einsum("pqst,lstr->lpqr", K[b] / np.sqrt(p[b]), theta)
+            logw += float(np.log(p[b] / N))
+            branches.append(b)
         else:  # XXPhase: cos(th) 1 - i sin(th) X(x)X
             th = 0.5 * np.pi * a
             theta = np.cos(th) * theta - 1j * np.sin(th) * theta[:, ::-1, ::-1, :]
