@@ -781,6 +781,10 @@ int qk_build_mps(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops,
 /* dims[n_states][n_qubits+1], fidelity[n_states], offsets[n_states], total complex elements, kernel time; any may be NULL */
 int qk_built_info(const qk_built* built, int32_t* dims, double* fidelity, int64_t* offsets, int64_t* total_complex,
                   double* kernel_ms);
+/* What the build launched (read-only; any pointer may be NULL): `grid` workgroups of `threads` threads each (512: one workgroup per
+ * CU, 256: two or four), and `slots` = workgroups per CU x CUs, the number the grid was clipped to (free memory can clip it further).
+ * The kernel is persistent: with grid < n_states workgroups take further states from the queue after their first.                    */
+int qk_built_launch(const qk_built* built, int32_t* grid, int32_t* threads, int32_t* slots);
 int qk_built_download(const qk_built* built, double* host /* 2 * total_complex doubles (re, im interleaved) */);
 /* The built states as a set of the Gram engine (the image qk_mps_set_create makes from host tensors), packed on the
  * device: nothing crosses PCIe between the builder and the sweep.  The set is independent of `built` afterwards.  */

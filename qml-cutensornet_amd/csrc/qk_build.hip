@@ -602,6 +602,7 @@ struct qk_built {
   std::vector<int64_t> offsets;
   int64_t total = 0;  // complex elements of the heap in use
   double kernel_ms = 0;
+  int32_t grid = 0, threads = 0, slots = 0;  // the launch: workgroups, threads of each, and the slots (workgroups per CU x CUs) the grid was clipped to
   int n_snapshots() const { return (int)checkpoints.size(); }
 };
 
@@ -1114,6 +1115,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   b->heap = std::move(heap);
   b->total = (int64_t)ctr[1];
   b->kernel_ms = ms;
+  b->grid = (int32_t)grid, b->threads = bt, b->slots = (int32_t)std::min<long long>(INT32_MAX, (long long)wgs_per_cu * c->num_cus);
   *out = b.release();
   return QK_OK;
 }
@@ -1125,6 +1127,14 @@ extern "C" int qk_built_info(const qk_built* b, int32_t* dims, double* fidelity,
   if (offsets) std::copy(b->offsets.begin(), b->offsets.end(), offsets);
   if (total_complex) *total_complex = b->total;
   if (kernel_ms) *kernel_ms = b->kernel_ms;
+  return QK_OK;
+}
+
+extern "C" int qk_built_launch(const qk_built* b, int32_t* grid, int32_t* threads, int32_t* slots) {
+  if (!b) return qk_fail(QK_EINVAL, "qk_built_launch: null handle");
+  if (grid) *grid = b->grid;
+  if (threads) *threads = b->threads;
+  if (slots) *slots = b->slots;
   return QK_OK;
 }
 

@@ -118,6 +118,7 @@ _SIGNATURES = [
     ("qk_selftest_mfma", C.c_int, [_P]),
     ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
     ("qk_built_info", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    ("qk_built_launch", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("qk_built_download", C.c_int, [_P, _P]),
     ("qk_built_destroy", C.c_int, [_P]),
     ("qk_mps_set_from_built", C.c_int, [_P, _P, C.POINTER(_P)]),
@@ -1520,6 +1521,14 @@ def _built_trajectories(h, ns, j=-1):
     return logw, branches
 
 
+def _built_launch(h) -> dict:
+    """What the builder launched for a built handle: {"grid": workgroups, "threads": threads of each, "slots": workgroups per CU x
+    CUs, what the grid was clipped to}.  grid == slots < n_states: workgroups took more than one state."""
+    g, t, sl = C.c_int32(), C.c_int32(), C.c_int32()
+    _check(lib().qk_built_launch(h, C.byref(g), C.byref(t), C.byref(sl)), "qk_built_launch")
+    return {"grid": int(g.value), "threads": int(t.value), "slots": int(sl.value)}
+
+
 class BuiltScan:
     """The snapshots of ``Context.build_mps_scan``: owns the builder's handle (one device heap with every snapshot of every state)
     until ``close()``; a context manager.  ``checkpoints[j]`` gates were done at snapshot j; the last snapshot is the finished
@@ -1535,6 +1544,7 @@ class BuiltScan:
         ms = C.c_double()
         _check(lib().qk_built_info(handle, None, None, None, None, C.byref(ms)), "qk_built_info")
         self.kernel_ms = ms.value
+        self.launch = _built_launch(handle)  # {"grid", "threads", "slots"} of the scan's one launch
         self.first_gate = 0  # position of the program's first gate in the uninterrupted circuit (build_mps_scan sets it)
         ctx._adopt(self)  # closed with the context: the heap lives on its device
 
@@ -1569,10 +1579,10 @@ class BuiltScan:
         """Snapshot j: {"dims": bond tables (n_states, n_qubits + 1), "fidelity": the fidelity product so far (n_states,),
         "centre": site of the orthogonality centre (n_states,), "heap_bytes": bytes of the snapshot's tensors in the heap,
         "logw": the log-weights of the trajectories so far (n_states,), "branches": the branch of every channel gate of the whole
-        program (n_states, n_channel_gates), whichever snapshot is asked}."""
+        program (n_states, n_channel_gates), whichever snapshot is asked, "grid", "threads", "slots": the scan's launch}."""
         k, dims, fid, _, centre, total = self._info(j)
         logw, branches = _built_trajectories(self._h, self.n_states, k)
-        return {"dims": dims, "fidelity": fid, "centre": centre, "heap_bytes": 16 * total, "logw": logw, "branches": branches}
+        return {"dims": dims, "fidelity": fid, "centre": centre, "heap_bytes": 16 * total, "logw": logw, "branches": branches, **self.launch}
 
     def set(self, j) -> "MpsSet":
         """Snapshot j as a device-resident set (packed on the device: nothing is downloaded); feeds ``gram``, ``local_paulis``,
@@ -1698,7 +1708,8 @@ class Context:
                   seed=0, state_index=None, trajectory=None):
         """Device MPS builder (/root/reference/gpu_backend/kernel_state_ansatz.py:221, 263): the MPS of every
         bound circuit of the list (``ansatz.BoundCircuit``; they must share one gate structure, as the data points of one
-        ansatz do) in ONE launch.  Returns (list[MPS], info) with info = {"kernel_ms", "total_complex", "dropped"}.  With
+        ansatz do) in ONE launch.  Returns (list[MPS], info) with info = {"kernel_ms", "total_complex", "dropped", and the launch:
+        "grid" workgroups of "threads" threads, clipped to "slots" = workgroups per CU x CUs}.  With
         ``partial`` a state that outgrows ``max_bond`` does not fail the call: its entry in the list is ``None`` and its index is
         in info["dropped"] (build it with the host builder).
 
@@ -1723,6 +1734,7 @@ class Context:
             flat = np.empty(total.value, dtype=np.complex128)
             _check(lib().qk_built_download(h, flat.ctypes.data), "qk_built_download")
             logw, branches = _built_trajectories(h, ns)
+            launch = _built_launch(h)
         finally:
             lib().qk_built_destroy(h)
         states, dropped = [], []
@@ -1737,12 +1749,12 @@ class Context:
                 tensors.append(flat[pos : pos + sz].reshape(int(dims[s_, k]), 2, int(dims[s_, k + 1])))
                 pos += sz
             states.append(MPS(tensors, float(fid[s_]), float(logw[s_]), branches[s_]))
-        return states, {"kernel_ms": ms.value, "total_complex": int(total.value), "dropped": dropped, "logw": logw, "branches": branches}
+        return states, {"kernel_ms": ms.value, "total_complex": int(total.value), "dropped": dropped, "logw": logw, "branches": branches, **launch}
 
     def build_mps_set(self, circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, truncate: bool = False, seed=0,
                       state_index=None, trajectory=None):
         """Like ``build_mps`` but the states never leave the device: returns (MpsSet, info) with info = {"kernel_ms", "dims",
-        "fidelity", "logw", "branches"}; the set feeds ``gram`` / ``gram_values`` directly."""
+        "fidelity", "logw", "branches", "grid", "threads", "slots"}; the set feeds ``gram`` / ``gram_values`` directly."""
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_mps_set needs at least one circuit")
@@ -1756,10 +1768,11 @@ class Context:
             ms = C.c_double()
             _check(lib().qk_built_info(h, dims.ctypes.data, fid.ctypes.data, None, None, C.byref(ms)), "qk_built_info")
             logw, branches = _built_trajectories(h, ns)
+            launch = _built_launch(h)
             _check(lib().qk_mps_set_from_built(self._h, h, C.byref(hs)), "qk_mps_set_from_built")
         finally:
             lib().qk_built_destroy(h)
-        return MpsSet(self, hs, dims), {"kernel_ms": ms.value, "dims": dims, "fidelity": fid, "logw": logw, "branches": branches}
+        return MpsSet(self, hs, dims), {"kernel_ms": ms.value, "dims": dims, "fidelity": fid, "logw": logw, "branches": branches, **launch}
 
     def build_mps_scan(self, circuits, checkpoints, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, truncate: bool = False,
                        initial=None, partial: bool = False, seed=0, state_index=None, trajectory=None, first_gate=None) -> BuiltScan:
@@ -1814,7 +1827,7 @@ class Context:
         """Device builder for one rank's share of a data set, the states staying on the device whenever possible: returns
         (MpsSet, None, info) when every state fitted ``max_bond`` (packed on the device by ``qk_mps_set_from_built``: nothing
         is downloaded), else (None, list[MPS | None], info) with the dropped states ``None`` (``partial`` only), to be
-        completed by the host builder.  info = {"kernel_ms", "dims", "fidelity", "dropped", "logw", "branches"}; ``seed``,
+        completed by the host builder.  info = {"kernel_ms", "dims", "fidelity", "dropped", "logw", "branches", "grid", "threads", "slots"}; ``seed``,
         ``state_index`` and ``trajectory`` as in ``build_mps``."""
         from .mps import MPS
 
@@ -1832,7 +1845,7 @@ class Context:
             _check(lib().qk_built_info(h, dims.ctypes.data, fid.ctypes.data, offs.ctypes.data, C.byref(total), C.byref(ms)), "qk_built_info")
             dropped = [int(k) for k in np.nonzero(fid < 0)[0]]
             logw, branches = _built_trajectories(h, ns)
-            info = {"kernel_ms": ms.value, "dims": dims, "fidelity": fid, "dropped": dropped, "logw": logw, "branches": branches}
+            info = {"kernel_ms": ms.value, "dims": dims, "fidelity": fid, "dropped": dropped, "logw": logw, "branches": branches, **_built_launch(h)}
             if not dropped:
                 hs = _P()
                 _check(lib().qk_mps_set_from_built(self._h, h, C.byref(hs)), "qk_mps_set_from_built")

@@ -251,3 +251,90 @@ def canary_pair_mask(nx, ix, ny=None, iy=None):
     m[:, list(ix)] = True
     m[list(ix if sym else iy), :] = True
     return m
+
+
+# ------------------------------------------------------------------ sets that make every workgroup of the device builder take a second state
+# (tests/test_gpu_builder_turns.py on the GPU, tests/test_builder_turns_host.py on the CPU).  qk_build_kernel is persistent: it launches
+# min(n_states, slots) workgroups, slots = workgroups per CU x CUs, and a workgroup that has packed its state draws the next number
+# from the queue -- onto the arena, the workspaces and the LDS of the state before.  A case holds slots + BUILDER_TURN_EXTRA states
+# of the reference ansatz at gamma = 1 on ``R.synthetic_features(n_states, qubits, 7)``; the queue is ordered by descending proxy
+# (``queue_proxy``) unless QK_BUILD_NO_ORDER is set, so which states come on a later turn is known.
+BUILDER_TURN_EXTRA = 40
+BUILDER_TURN_SETS = {  # name: (qubits, layers, distance, max_bond, QK_BUILD_WGS or None, workgroups per CU, threads, bond a later-turn state must reach)
+    # 512 threads, the whole CU's LDS: later-turn states at bond >= 48 run the preconditioned block factorisation, the Gram-Schmidt
+    # centre moves and the theta product on the matrix cores
+    "wide": (12, 4, 3, 64, "1", 1, 512, 48),
+    # two workgroups of 256 threads: the block path at >= 48 columns (bond >= 24)
+    "two": (10, 3, 3, 64, "2", 2, 256, 24),
+    # four workgroups, the default at max_bond <= 32: a 48-column theta no longer fits the 38 KiB and is factorised from L2
+    "four": (10, 3, 3, 32, None, 4, 256, 24),
+}
+# the partial build: the circuits of "two" in the 512-thread shape with a cap that some states outgrow and some do not, so that on
+# one workgroup a dropped state is followed by an ordinary one and the other way round.  (circuits of, QK_BUILD_WGS, workgroups per
+# CU, threads, max_bond, least number of dropped and of ordinary states among the later-turn positions and of dropped ones among
+# the first slots.)  A state is dropped when a bond outgrows the cap at ANY gate (``outgrows``), not only when a final bond does: by
+# final bonds 210 of the 256 heaviest states and 14 of the 40 lightest lie above 28, by the largest bond on the way 225 and 21.
+BUILDER_TURN_PARTIAL = ("two", "1", 1, 512, 28, 16)
+# a build that truncates, beyond the slots: the circuits of "two" in the two-workgroup shape cut at bond 8 (``truncate=True``).  In the
+# default order nearly every first-turn state loses more than 1e-6 of fidelity and about half of the later-turn states lose less, so a
+# fidelity carried from one state of a workgroup into the next is wrong by far more than any tolerance, whether or not the builder
+# repeats its bits.  (circuits of, max_bond, least share of first-turn states and least number of later-turn states below 1 - 1e-6)
+BUILDER_TURN_TRUNCATE = ("two", 8, 0.75, 16)
+BUILDER_TURN_SEED = 7
+
+
+def builder_turn_circuits(name, slots, extra=BUILDER_TURN_EXTRA):
+    """The slots + extra bound circuits of BUILDER_TURN_SETS[name]."""
+    import qml_cutensornet_amd as Q
+    from oracle import restatement as R
+
+    n, reps, d = BUILDER_TURN_SETS[name][:3]
+    ans = Q.KernelStateAnsatz(n, reps, 1.0, Q.entanglement_graph(n, d))
+    return [ans.circuit_for_data(x) for x in R.synthetic_features(slots + extra, n, BUILDER_TURN_SEED)]
+
+
+def queue_proxy(circuit):
+    """The cost proxy the device builder orders its queue by: sin^2(pi alpha) summed over the XXPhase, YYPhase and ZZPhase gates."""
+    op, alpha = np.asarray(circuit.op), np.asarray(circuit.alpha, dtype=np.float64)
+    return float((np.sin(np.pi * alpha[(op == 2) | (op == 6) | (op == 7)]) ** 2).sum())
+
+
+def queue_order(circuits, ordered=True):
+    """The state at every queue position: by descending proxy, ties in input order (``ordered``), or the input order
+    (QK_BUILD_NO_ORDER)."""
+    if not ordered:
+        return np.arange(len(circuits))
+    return np.argsort(-np.array([queue_proxy(c) for c in circuits]), kind="stable")
+
+
+def later_turn_states(circuits, slots, ordered=True):
+    """The states at queue positions >= slots: whoever takes them has built a state before."""
+    return queue_order(circuits, ordered)[slots:]
+
+
+def ascending_by_proxy(circuits):
+    """The permutation that sorts the circuits by ascending proxy: under QK_BUILD_NO_ORDER the heavy states then come last, onto
+    arenas that held light ones."""
+    return np.argsort(np.array([queue_proxy(c) for c in circuits]), kind="stable")
+
+
+def host_states(circuits, max_bond=None):
+    """The host builder's states of the circuits (``simulate_many`` on up to 16 cores)."""
+    from qml_cutensornet_amd import mps
+
+    return mps.simulate_many(circuits, 1 - 1e-16, workers=min(16, os.cpu_count() or 1), max_bond=max_bond)[0]
+
+
+def outgrows(circuits, cap, host=None):
+    """bool per circuit: does a bond of the host builder's state exceed ``cap`` after any gate -- what makes the device builder drop
+    the state in a partial build.  ``host``: the finished host states, if at hand (a final bond above the cap settles it; the others
+    are walked with a checkpoint behind every two-qubit gate)."""
+    import qml_cutensornet_amd as Q
+
+    host = host_states(circuits) if host is None else host
+    out = np.array([m.max_bond() > cap for m in host])
+    for k, c in enumerate(circuits):
+        if not out[k]:
+            cps = sorted(set((np.flatnonzero(np.isin(np.asarray(c.op), (2, 3, 6, 7, 9, 11))) + 1).tolist()) | {c.n_gates})
+            out[k] = max(m.max_bond() for m in Q.simulate(c, 1 - 1e-16, checkpoints=cps)) > cap
+    return out

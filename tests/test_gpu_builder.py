@@ -291,17 +291,23 @@ def test_bond_cap_on_the_block_path(gpu_ctx, monkeypatch, shape):
     import qml_cutensornet_amd as Q
     from oracle import restatement as R
 
-    if shape:
-        monkeypatch.setenv("QK_BUILD_WGS", shape)
     n, chi = 18, 32
     X = R.synthetic_features(6, n, 11)
     ans = Q.KernelStateAnsatz(n, 4, 1.0, Q.entanglement_graph(n, 3))
     circuits = [ans.circuit_for_data(x) for x in X]
+    monkeypatch.setenv("QK_BUILD_WGS", "1")
+    cus = gpu_ctx.build_mps(circuits[:1], max_bond=chi, truncate=True)[1]["slots"]  # one 512-thread workgroup per CU: the slots are the CUs
+    if shape:
+        monkeypatch.setenv("QK_BUILD_WGS", shape)
+    else:
+        monkeypatch.delenv("QK_BUILD_WGS")
     host = [Q.simulate(c, 1 - 1e-16, max_bond=chi) for c in circuits]
     free = Q.simulate(circuits[0], 1 - 1e-16)
     assert free.max_bond() > chi and max(m.max_bond() for m in host) == chi and min(m.fidelity for m in host) < 1 - 1e-6
     dev, info = gpu_ctx.build_mps(circuits, max_bond=chi, truncate=True)
     assert not info["dropped"]
+    per_cu = {None: 4, "2": 2, "1": 1}[shape]  # the launch record: the shape the docstring claims
+    assert info["threads"] == (512 if shape == "1" else 256) and info["slots"] == per_cu * cus and info["grid"] == len(circuits)
     for d, h in zip(dev, host):
         assert np.array_equal(d.bond_dims(), h.bond_dims())
         assert abs(d.fidelity - h.fidelity) < 1e-9 * max(1.0, h.fidelity)

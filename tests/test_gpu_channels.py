@@ -198,13 +198,15 @@ def test_at_bond_cap_64_a_state_does_not_depend_on_the_size_of_its_set(gpu_ctx, 
     x = features(3, 12, 41)
     circuits = [from_gates(12, noisy_12_gates(x[k], measure=False)) for k in (1, 0, 1)]
     kw = dict(max_bond=64, seed=SEED)
-    alone, _ = gpu_ctx.build_mps([circuits[0]], state_index=0, trajectory=0, **kw)
+    alone, info = gpu_ctx.build_mps([circuits[0]], state_index=0, trajectory=0, **kw)
     assert alone[0].max_bond() == 64 and alone[0].logw < 0
+    assert info["threads"] == 256 and info["grid"] == 1  # one state, and still the 256-thread shape
     some, _ = gpu_ctx.build_mps(circuits, state_index=np.array([0, 1, 0]), trajectory=np.array([0, 0, 3]), **kw)
     assert same_bits(alone[0], some[0])
     monkeypatch.setenv("QK_BUILD_WGS", "2")
-    pinned, _ = gpu_ctx.build_mps([circuits[0]], state_index=0, trajectory=0, **kw)
+    pinned, pinned_info = gpu_ctx.build_mps([circuits[0]], state_index=0, trajectory=0, **kw)
     assert same_bits(alone[0], pinned[0])
+    assert (pinned_info["threads"], pinned_info["slots"]) == (info["threads"], info["slots"])  # the shape it took on its own is the two-workgroup one
 
 
 def test_capped_device_build_with_channels(gpu_ctx, noisy_12):

@@ -91,13 +91,16 @@ def test_four_workgroup_shape_capped_at_bond_32(gpu_ctx, noisy2_12, monkeypatch)
     """QK_BUILD_WGS=4: 38 KiB of LDS per workgroup, the shape the grouping of the Kraus matrices is made for.  The Measure2q in
     mid-chain keeps the bonds of this circuit at 32, so the cap admits the shape and cuts nothing: beside the checks of the capped
     build, the states are those of the host."""
-    monkeypatch.setenv("QK_BUILD_WGS", "4")
     circuits = noisy2_12[0]
+    monkeypatch.setenv("QK_BUILD_WGS", "1")
+    cus = gpu_ctx.build_mps(circuits[:1], max_bond=32, truncate=True, seed=SEED, state_index=STATE_INDEX[:1], trajectory=TRAJECTORY[:1])[1]["slots"]  # one workgroup per CU
+    monkeypatch.setenv("QK_BUILD_WGS", "4")
     host, margin = host_states(circuits, max_bond=32)
     assert margin >= 1e-6 and all(h.max_bond() == 32 and h.fidelity == 1.0 for h in host)
     dev, info = gpu_ctx.build_mps(circuits, max_bond=32, truncate=True, seed=SEED, state_index=STATE_INDEX, trajectory=TRAJECTORY)
     print(f"two-qubit channels capped at 32, QK_BUILD_WGS=4: kernel_ms = {info['kernel_ms']:.3f}")
     assert not info["dropped"]
+    assert info["threads"] == 256 and info["slots"] == 4 * cus and info["grid"] == len(circuits)  # the launch record: the four-workgroup shape
     for d, h in zip(dev, host):
         print(f"capped at 32: device fidelity {d.fidelity:.15e}, host {h.fidelity:.15e}, difference {d.fidelity - h.fidelity:.3e}; logw {d.logw:.12f} / {h.logw:.12f}")
         assert np.array_equal(d.branches, h.branches)

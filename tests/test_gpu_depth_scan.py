@@ -125,6 +125,7 @@ def test_set_a_reaches_the_block_factorisation(scan_a, case_a, plain_a):
     print(f"set A: largest bonds {top}; plain builds repeat bit for bit: {plain_a[1]}")
     assert top[0] <= 4 and top[1] <= 16 and top[2] >= 24 and top[3] >= 48
     assert scan_a.checkpoints == case_a.ends and len(scan_a) == 4 and scan_a.kernel_ms > 0
+    assert scan_a.launch["threads"] == 512 and scan_a.launch["grid"] == 3 and scan_a.info(0)["threads"] == 512  # the default max_bond: the 512-thread shape
 
 
 # ---- 1. the last snapshot is the plain build
@@ -133,17 +134,21 @@ def test_last_snapshot_is_the_plain_build_a(scan_a, plain_a, reproducible):
     _assert_same(scan_a.states(-1), plain_a[0], reproducible, "set A, index -1")
 
 
-def test_last_snapshot_is_the_plain_build_b(gpu_ctx, scan_b, case_b, reproducible):
-    plain, _ = gpu_ctx.build_mps(case_b.circuits, **case_b.kw)
+def test_last_snapshot_is_the_plain_build_b(gpu_ctx, scan_a, scan_b, case_b, reproducible):
+    plain, info = gpu_ctx.build_mps(case_b.circuits, **case_b.kw)
+    for launch in (scan_b.launch, info):  # max_bond=32: four 256-thread workgroups per CU (set A's shape has one per CU)
+        assert launch["threads"] == 256 and launch["slots"] == 4 * scan_a.launch["slots"] and launch["grid"] == 5
     _assert_same(scan_b.states(2), plain, reproducible, "set B")
 
 
-def test_two_workgroup_shape_with_a_cap_that_bites(gpu_ctx, case_a, reproducible, monkeypatch):
+def test_two_workgroup_shape_with_a_cap_that_bites(gpu_ctx, scan_a, case_a, reproducible, monkeypatch):
     """QK_BUILD_WGS=2, max_bond=64, truncate: the last snapshot is the plain build, the earlier ones the shallower builds"""
     monkeypatch.setenv("QK_BUILD_WGS", "2")
     kw = dict(max_bond=64, truncate=True)
-    plain, _ = gpu_ctx.build_mps(case_a.circuits, **kw)
+    plain, info = gpu_ctx.build_mps(case_a.circuits, **kw)
     with gpu_ctx.build_mps_scan(case_a.circuits, case_a.ends, **kw) as scan:
+        for launch in (scan.launch, info):  # two 256-thread workgroups per CU
+            assert launch["threads"] == 256 and launch["slots"] == 2 * scan_a.launch["slots"]
         snaps = [scan.states(j) for j in range(4)]
         grams = []
         for j in range(4):
