@@ -877,9 +877,31 @@ int qk_build_mps_channels2(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int3
                            int32_t branch_state_stride, uint64_t seed, const uint32_t* state_index, const uint32_t* trajectory,
                            uint32_t first_gate, int32_t n_channels2, const double* kraus2 /* [n_channels2][16][4][4][2] */,
                            const int32_t* n_kraus2 /* [n_channels2] */, qk_built** out);
+/* Classical control.  qk_build_mps_conditions is qk_build_mps_channels2 (its arguments in their order) plus two rows in front of
+ * `out`, one entry per gate: cond_gate[i] is -1 (gate i is unconditional) or the position g < i, in this program, of a gate of op
+ * code 10 or 11; cond_mask[i] (read where cond_gate[i] >= 0) has bit v set when branch v of gate g lets gate i run.  With b the
+ * branch recorded for gate g of this state, gate i runs when b >= 0 and bit b of cond_mask[i] is set; else it is skipped: no centre
+ * move, no theta, no SVD, no change of a bond, of the fidelity or of the log-weight, no draw.  A skipped gate is a done gate all the
+ * same (checkpoints, first_gate + i and the positions conditions name count it), and the look-ahead that places the centre behind a
+ * two-qubit gate reads the op codes alone.  A skipped gate of code 10 or 11 records branch -2, so a condition on it is false; the
+ * gate conditioned on may itself be conditional; any op code may be conditional; cond_mask = 0 is "never".  The persistent kernel
+ * decides per state and gate by one load of the state's branch record: no atomics, no barrier between workgroups.  Positions are
+ * those of the program of the call: a resumed build (`initial`) conditions only on gates it runs itself.  QK_EINVAL before
+ * anything runs, naming the gate, for: rows in a call without a channel table; cond_gate[i] < -1 or >= i; op[cond_gate[i]] not 10 or
+ * 11; a mask bit at or above the number of Kraus matrices of that gate's channel; cond_mask NULL.  With cond_gate NULL the call IS
+ * qk_build_mps_channels2.                                                                                                          */
+int qk_build_mps_conditions(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
+                            const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
+                            int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
+                            int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
+                            const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch,
+                            int32_t branch_state_stride, uint64_t seed, const uint32_t* state_index, const uint32_t* trajectory,
+                            uint32_t first_gate, int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2,
+                            const int32_t* cond_gate /* [n_ops] */, const uint32_t* cond_mask /* [n_ops] */, qk_built** out);
 int qk_built_logw_at(const qk_built* built, int32_t j, double* logw /* [n_states] */); /* log-weights at snapshot j (0 without channels) */
 int qk_built_num_channel_gates(const qk_built* built);                    /* gates of op codes 10 and 11 of the program */
-/* The branch every channel gate took, in program order: [n_states][n_channel_gates]; -1 where a dropped state stopped early */
+/* The branch every channel gate took, in program order: [n_states][n_channel_gates]; -1 where a dropped state stopped early, -2
+ * where the gate was skipped because its condition was false (qk_build_mps_conditions) */
 int qk_built_branches(const qk_built* built, int8_t* branches);
 int qk_built_num_snapshots(const qk_built* built);                        /* 1 for qk_build_mps */
 int qk_built_checkpoints(const qk_built* built, int32_t* checkpoints);    /* [num_snapshots] gates done at each snapshot */

@@ -42,6 +42,15 @@ applied to theta = A_q A_{q+1} in front of the SVD of a two-qubit gate.  ``chann
 and ``branch`` are shared with code 10: where ``op`` is 11, ``channel[i]`` indexes
 ``kraus2``.  Project2q, Depolarizing2q, CorrelatedPhaseFlip, Measure2q and
 PostSelect2q are entries of that table.
+
+Classical control: two optional rows ride with a program that has a channel table.
+``cond_gate[i]`` is -1 (gate i is unconditional) or the position g < i of a gate of op
+code 10 or 11; ``cond_mask[i]`` (uint32) has bit v set when branch v of gate g lets
+gate i run.  With b the branch recorded for gate g, gate i runs when b >= 0 and bit b of
+the mask is set; else it is skipped: it does nothing at all (no centre move, no SVD, no
+draw, no change of ``logw``), and a skipped channel gate records branch -2.  In gate
+lists a fourth element ``(g, values)`` names the list position of an earlier channel
+gate and the branches that let the gate run.
 """
 from __future__ import annotations
 
@@ -343,6 +352,104 @@ def check_channel_gates(op, q0, n_qubits, channel, branch, kraus, n_kraus, kraus
     return (channel, branch) + tables[OP_K1][1:] + tables[OP_K2][1:]
 
 
+def check_condition_gates(op, chan, cond_gate, cond_mask):
+    """The condition rows of a program, validated: ``(cond_gate int32 [n_gates], cond_mask uint32 [n_gates])``, or ``None`` for a
+    program without them or with every gate unconditional.  ``chan`` is what ``check_channel_gates`` returned.  ``ValueError``,
+    naming the gate's position, for rows in a program without a channel table, ``cond_mask`` missing, ``cond_gate[i]`` outside
+    -1 .. i-1, a gate named that is not of op code 10 or 11, or a mask bit at or above the number of Kraus matrices of that gate's
+    channel."""
+    if cond_gate is None:
+        if cond_mask is not None:
+            raise ValueError("a program with cond_mask needs cond_gate")
+        return None
+    op = np.asarray(op)
+    if cond_mask is None:
+        raise ValueError("a program with cond_gate needs cond_mask")
+    if chan is None:
+        raise ValueError("gate 0: condition rows need a program with a channel table")
+    cond_gate = np.ascontiguousarray(cond_gate, dtype=np.int32)
+    mask = np.asarray(cond_mask)
+    if mask.shape != op.shape or cond_gate.shape != op.shape:
+        raise ValueError(f"cond_gate and cond_mask must hold one entry per gate ({op.shape[0]}); got shapes {cond_gate.shape}, {mask.shape}")
+    if mask.size and (np.any(mask.astype(np.int64) < 0) or np.any(mask.astype(np.int64) > 0xFFFFFFFF)):
+        raise ValueError("cond_mask must hold uint32 values")
+    mask = np.ascontiguousarray(mask.astype(np.uint32))
+    for i in np.flatnonzero(cond_gate != -1):
+        i, g = int(i), int(cond_gate[i])
+        if not -1 <= g < i:
+            raise ValueError(f"gate {i}: condition on gate {g} outside -1..{i - 1}")
+        if int(op[g]) not in _CHANNEL:
+            raise ValueError(f"gate {i}: condition on gate {g}, which is no channel gate (op code {int(op[g])})")
+        counts = chan[3] if int(op[g]) == OP_K1 else chan[5]
+        m = int(counts[int(chan[0][g])])
+        if int(mask[i]) >> m:
+            raise ValueError(f"gate {i}: condition mask names a branch at or above the {m} of gate {g}")
+    return (cond_gate, mask) if np.any(cond_gate >= 0) else None
+
+
+def _condition_mask(values, where) -> int:
+    """The mask of the ``values`` of a gate-list condition: an int or an iterable of ints (empty: never)."""
+    try:
+        vals = [values] if np.ndim(values) == 0 else list(values)
+        ok = all(int(v) == v and 0 <= int(v) < 32 for v in vals)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{where}: the values of a condition must be branches 0..31, got {values!r}")
+    mask = 0
+    for v in vals:
+        mask |= 1 << int(v)
+    return mask
+
+
+def _split_gate(g, where):
+    """``(name, qubits, params, condition or None)`` of a gate-list entry of three or four elements."""
+    if len(g) == 3:
+        return g[0], g[1], g[2], None
+    if len(g) != 4:
+        raise ValueError(f"{where}: a gate is (name, qubits, params[, (g, values)]), got {len(g)} elements")
+    cond = g[3]
+    if cond is None:
+        return g[0], g[1], g[2], None
+    try:
+        at, values = cond
+        at = int(at)
+    except (TypeError, ValueError):
+        raise ValueError(f"{where}: a condition is (g, values), got {cond!r}") from None
+    return g[0], g[1], g[2], (at, _condition_mask(values, where))
+
+
+class _Conditions:
+    """The condition rows of a program under construction from a gate list: ``core[p]`` is the program position of the core op of
+    list gate p when that is a channel gate; a routed gate carries its condition on every op it expands to."""
+
+    def __init__(self):
+        self.core, self.gate, self.mask, self.any = {}, [], [], False
+
+    def resolve(self, pos, cond):
+        """(cond_gate, cond_mask) of list gate ``pos`` with the condition ``cond`` = (list position, mask) or None."""
+        if cond is None:
+            return -1, 0
+        g, mask = cond
+        if not 0 <= g < pos:
+            raise ValueError(f"gate {pos}: condition on gate {g} outside 0..{pos - 1}")
+        if g not in self.core:
+            raise ValueError(f"gate {pos}: condition on gate {g}, which is no channel gate")
+        self.any = True
+        return self.core[g], mask
+
+    def add(self, pos, route_len, core_at, is_channel, cg, cm):
+        """List gate ``pos`` takes ``route_len`` ops from here on, its core op being the ``core_at``-th of them."""
+        if is_channel:
+            self.core[pos] = len(self.gate) + core_at
+        self.gate.extend([cg] * route_len), self.mask.extend([cm] * route_len)
+
+    def arrays(self):
+        if not self.any:
+            return None, None
+        return np.asarray(self.gate, dtype=np.int32), np.asarray(self.mask, dtype=np.uint32)
+
+
 def reject_channels(circuits, what) -> None:
     """``ValueError`` if one of ``circuits`` holds a drawn channel gate: ``what`` builds its states without a seed, state indices
     and trajectories, so every state would draw as state 0 (or as its position in a rank's share) of trajectory 0.  Forced
@@ -392,24 +499,28 @@ class BoundCircuit:
     n_kraus: np.ndarray | None = None  # int32 [n_channels] Kraus matrices of each channel (1..4)
     kraus2: np.ndarray | None = None  # complex128 [n_channels2, 16, 4, 4]: the two-qubit channel table, K[(p,p')][(s,s')], q0 most significant
     n_kraus2: np.ndarray | None = None  # int32 [n_channels2] Kraus matrices of each two-qubit channel (1..16)
+    cond_gate: np.ndarray | None = None  # int32 [n_gates] -1: unconditional; g < i: the channel gate whose recorded branch decides whether gate i runs
+    cond_mask: np.ndarray | None = None  # uint32 [n_gates] bit v: branch v of gate cond_gate[i] lets gate i run (read where cond_gate[i] >= 0)
 
     @property
     def n_channel_gates(self) -> int:
         return int(np.count_nonzero(np.isin(np.asarray(self.op), _CHANNEL)))
 
-    def _with(self, op, q0, alpha, mat, channel, branch) -> "BoundCircuit":
-        return BoundCircuit(self.n_qubits, op, q0, alpha, mat, self.mats, channel, branch, self.kraus, self.n_kraus, self.kraus2, self.n_kraus2)
+    def _with(self, op, q0, alpha, mat, channel, branch, cond_gate=None, cond_mask=None) -> "BoundCircuit":
+        return BoundCircuit(self.n_qubits, op, q0, alpha, mat, self.mats, channel, branch, self.kraus, self.n_kraus, self.kraus2, self.n_kraus2, cond_gate, cond_mask)
 
     def with_branches(self, branches) -> "BoundCircuit":
         """The same program with the branch of its j-th channel gate forced to ``branches[j]`` (-1 leaves it drawn): what replays
-        the recorded ``branches`` of a trajectory."""
+        the recorded ``branches`` of a trajectory.  -2 (the gate was skipped: its condition was false) keeps the program's own entry:
+        the replay skips the gate again, as the branches its condition reads are replayed too."""
         b = np.asarray(branches, dtype=np.int32).ravel()
         at = np.flatnonzero(np.isin(np.asarray(self.op), _CHANNEL))
         if b.shape[0] != at.shape[0]:
             raise ValueError(f"the program has {at.shape[0]} channel gates, got {b.shape[0]} branches")
         row = np.full(self.op.shape, -1, dtype=np.int32)
-        row[at] = b
-        return self._with(self.op, self.q0, self.alpha, self.mat, self.channel, row)
+        own = np.full(at.shape, -1, dtype=np.int32) if self.branch is None else np.asarray(self.branch, dtype=np.int32)[at]
+        row[at] = np.where(b == -2, own, b)
+        return self._with(self.op, self.q0, self.alpha, self.mat, self.channel, row, self.cond_gate, self.cond_mask)
 
     @property
     def n_gates(self) -> int:
@@ -420,8 +531,11 @@ class BoundCircuit:
         (/root/reference/cpu_backend/kernel_state_ansatz.py:113-131).  A drawn channel gate comes out as ``Kraus1q`` (``Kraus2q``
         for code 11) with all its matrices; one with a forced branch b (``Project``, ``PostSelect``, a replay) as ``Project``
         (``Project2q``) with the one matrix K_b, which gives the same state and ``logw`` when read back (its recorded branch is then
-        0, the only one ``Project`` has)."""
+        0, the only one ``Project`` has).  A conditional gate comes out as the 4-tuple ``(name, qubits, params, (g, values))``, g the
+        position in this list (one tuple per op) of the gate its condition reads; a condition on a gate that comes out as
+        ``Project`` / ``Project2q`` (forced branch b) reads ``[0]`` where bit b of the mask is set and ``[]`` where it is not."""
         chan = check_channel_gates(self.op, self.q0, self.n_qubits, self.channel, self.branch, self.kraus, self.n_kraus, self.kraus2, self.n_kraus2)
+        cond = check_condition_gates(self.op, chan, self.cond_gate, self.cond_mask)
         mat, mats = check_matrix_gates(self.op, self.mat, self.mats, with_channels=chan is not None and chan[2] is not None,
                                        with_channels2=chan is not None and chan[4] is not None)
         out = []
@@ -439,6 +553,11 @@ class BoundCircuit:
                 out.append((_OP_NAMES[o], qubits, [mats[mat[i], :d, :d].copy()]))
             else:
                 out.append((_OP_NAMES[o], qubits, [a] if o in _PARAMETRISED else []))
+            if cond is not None and cond[0][i] >= 0:
+                g, mask = int(cond[0][i]), int(cond[1][i])
+                forced = int(chan[1][g])
+                values = [v for v in range(32) if (mask >> v) & 1] if forced < 0 else ([0] if (mask >> forced) & 1 else [])
+                out[-1] = out[-1] + ((g, values),)
         return out
 
     def sliced(self, a, b) -> "BoundCircuit":
@@ -448,7 +567,14 @@ class BoundCircuit:
         if not 0 <= a <= b <= self.n_gates:
             raise ValueError(f"sliced({a}, {b}): want 0 <= a <= b <= {self.n_gates} gates")
         cut = lambda v: None if v is None else v[a:b]  # noqa: E731
-        return self._with(self.op[a:b], self.q0[a:b], self.alpha[a:b], cut(self.mat), cut(self.channel), cut(self.branch))
+        cg, cm = cut(self.cond_gate), cut(self.cond_mask)
+        if cg is not None:  # positions are relative to the program of a call: a kept gate may read kept gates only
+            cg = np.asarray(cg, dtype=np.int32)
+            behind = np.flatnonzero((cg >= 0) & (cg < a))
+            if behind.size:
+                raise ValueError(f"sliced({a}, {b}): gate {a + int(behind[0])} is conditioned on gate {int(cg[behind[0]])}, which lies in front of the slice")
+            cg = np.where(cg >= 0, cg - a, cg).astype(np.int32)
+        return self._with(self.op[a:b], self.q0[a:b], self.alpha[a:b], cut(self.mat), cut(self.channel), cut(self.branch), cg, cm)
 
     @classmethod
     def from_gates(cls, n_qubits, gates, named_constants: bool = False) -> "BoundCircuit":
@@ -458,6 +584,10 @@ class BoundCircuit:
         the gate on (hi-1, hi), the chain back.  The named two-qubit rotations and SWAP are symmetric in their qubits; a matrix
         gate need not be: on qubits ``[a, b]`` with a > b the matrix is applied with the two qubit roles exchanged
         (``exchange_qubits``), so ``("CX", [3, 2], [])`` has its control on qubit 3.
+
+        Classical control: a gate may carry a fourth element ``(g, values)``: g is the list position of an earlier channel gate
+        (code 10 or 11), ``values`` an int or an iterable of ints, the branches of that gate that let this one run (empty: never).
+        A routed gate carries the condition on every op it expands to; g is mapped to the program position of the core op.
 
         Matrix gates: ``("Unitary1q", [q], [M])`` and ``("Unitary2q", [a, b], [M])`` with M a unitary 2x2 / 4x4 (index (s_a, s_b),
         a most significant), and -- with ``named_constants=True`` -- the named constants X, Y, Z, S, Sdg, T, Tdg, V, Vdg, SX, SXdg,
@@ -472,22 +602,25 @@ class BoundCircuit:
         matrix of the wrong shape or one that is not unitary to UNITARY_TOL."""
         n = int(n_qubits)
         op, q0, alpha, mat, channel, branch = [], [], [], [], [], []
-        table, chans, chans2 = _MatTable(), _ChannelTable(), _ChannelTable(4)
+        table, chans, chans2, conds = _MatTable(), _ChannelTable(), _ChannelTable(4), _Conditions()
         for pos, g in enumerate(gates):
-            name, qubits, params = g
+            name, qubits, params, cond = _split_gate(g, f"gate {pos}")
             code = _gate_code(name, named_constants)
             qubits = [int(q) for q in qubits]
             if _arity(code) != len(qubits):
                 raise ValueError(f"{name} acts on {_arity(code)} qubit(s), got {qubits}")
+            cg, cm = conds.resolve(pos, cond)
             if code == OP_K1:
                 if not 0 <= qubits[0] < n:
                     raise ValueError(f"gate on qubits {qubits} outside a register of {n}")
                 slot, forced = chans.slot(name, params, f"gate {pos}")
+                conds.add(pos, 1, 0, True, cg, cm)
                 op.append(OP_K1), q0.append(qubits[0]), alpha.append(0.0), mat.append(-1), channel.append(slot), branch.append(forced)
                 continue
             if code == OP_K2:  # routed like a matrix gate; on [a, b] with a > b the matrices go in with the qubit roles exchanged
                 route = _route(code, qubits, n)
                 slot, forced = chans2.slot(name, params, f"gate {pos}", exchange=qubits[0] > qubits[1])
+                conds.add(pos, len(route), len(route) // 2, True, cg, cm)
                 for o, q, k in route:
                     op.append(o), q0.append(q), alpha.append(0.0), mat.append(-1), channel.append(slot if k else -1), branch.append(forced if k else -1)
                 continue
@@ -497,7 +630,9 @@ class BoundCircuit:
                         raise ValueError(f"{name}: expected 0 parameter(s), got {list(params)}")
                     params = None
                 slot = table.slot(name, qubits, params, f"gate {pos}")
-                for o, q, k in _route(code, qubits, n):
+                route = _route(code, qubits, n)
+                conds.add(pos, len(route), 0, False, cg, cm)
+                for o, q, k in route:
                     op.append(o), q0.append(q), alpha.append(0.0), mat.append(slot if k else -1), channel.append(-1), branch.append(-1)
                 continue
             if params is None:
@@ -507,14 +642,16 @@ class BoundCircuit:
             if len(params) != (1 if code in _PARAMETRISED else 0):
                 raise ValueError(f"{name}: expected {1 if code in _PARAMETRISED else 0} parameter(s), got {list(params)}")
             a = float(params[0]) if params else 0.0
-            for o, q, k in _route(code, qubits, n):
+            route = _route(code, qubits, n)
+            conds.add(pos, len(route), 0, False, cg, cm)
+            for o, q, k in route:
                 op.append(o), q0.append(q), alpha.append(a if k else 0.0), mat.append(-1), channel.append(-1), branch.append(-1)
         core = (n, np.asarray(op, dtype=np.int8), np.asarray(q0, dtype=np.int32), np.asarray(alpha, dtype=np.float64))
         mt = (np.asarray(mat, dtype=np.int32), table.array()) if table.entries else (None, None)
         if not chans.entries and not chans2.entries:
             return cls(*core) if not table.entries else cls(*core, *mt)
         rows = (np.asarray(channel, dtype=np.int32), np.asarray(branch, dtype=np.int32))
-        return cls(*core, *mt, *rows, *(chans.arrays() if chans.entries else (None, None)), *(chans2.arrays() if chans2.entries else (None, None)))
+        return cls(*core, *mt, *rows, *(chans.arrays() if chans.entries else (None, None)), *(chans2.arrays() if chans2.entries else (None, None)), *conds.arrays())
 
 
 def check_checkpoints(checkpoints, n_gates) -> list:
@@ -717,13 +854,14 @@ class CircuitProgram:
     angle form alpha = s (c_a + d_a x[a]) (c_b + d_b x[b]) (s = 0 for H and SWAP; c = 1, d = 0 for an absent factor)."""
 
     def __init__(self, n_qubits, op, q0, s, fa, ca, da, fb, cb, db, mat=None, mats=None, channel=None, branch=None, kraus=None, n_kraus=None, kraus2=None,
-                 n_kraus2=None):
+                 n_kraus2=None, cond_gate=None, cond_mask=None):
         self.n_qubits = int(n_qubits)
         self.op, self.q0 = op, q0
         self.s, self.fa, self.ca, self.da, self.fb, self.cb, self.db = s, fa, ca, da, fb, cb, db
         self.mat, self.mats = mat, mats  # constant matrix gates: the table is the same array for every data point
         self.channel, self.branch, self.kraus, self.n_kraus = channel, branch, kraus, n_kraus  # channels are constants of the ansatz too
         self.kraus2, self.n_kraus2 = kraus2, n_kraus2
+        self.cond_gate, self.cond_mask = cond_gate, cond_mask  # classical control is gate structure: the same for every data point
 
     @property
     def n_gates(self) -> int:
@@ -731,7 +869,8 @@ class CircuitProgram:
 
     def bind(self, x: np.ndarray) -> BoundCircuit:
         alpha = self.s * (self.ca + self.da * x[self.fa]) * (self.cb + self.db * x[self.fb])
-        return BoundCircuit(self.n_qubits, self.op, self.q0, alpha, self.mat, self.mats, self.channel, self.branch, self.kraus, self.n_kraus, self.kraus2, self.n_kraus2)
+        return BoundCircuit(self.n_qubits, self.op, self.q0, alpha, self.mat, self.mats, self.channel, self.branch, self.kraus, self.n_kraus, self.kraus2, self.n_kraus2,
+                            self.cond_gate, self.cond_mask)
 
 
 def _factor(spec, n_features):
@@ -754,7 +893,8 @@ class CircuitAnsatz:
     Havlicek-style ZZ map is ZZPhase ``(s, (a, pi, -1), (b, pi, -1))``.  Two-qubit gates on non-adjacent or reversed
     qubits are routed as in ``BoundCircuit.from_gates``.  Constant matrix gates: the named constants of ``from_gates`` (X, Y, Z, S,
     Sdg, T, Tdg, V, Vdg, SX, SXdg, CX, CY, CZ) with angle ``None``, and ``("Unitary1q" | "Unitary2q", qubits, M)`` with a constant
-    unitary M in the place of the angle; every data point shares the one table.  ``num_features`` defaults to ``num_qubits``
+    unitary M in the place of the angle; every data point shares the one table.  A gate may carry a fourth element ``(g, values)``,
+    the condition of ``from_gates``: it runs only where the channel gate at list position g took one of ``values``.  ``num_features`` defaults to ``num_qubits``
     (one feature per qubit, as the reference's ``feature_symbol_list``).  Picklable: plain numpy arrays only."""
 
     def __init__(self, num_qubits, gates, num_features=None):
@@ -766,8 +906,9 @@ class CircuitAnsatz:
         self.feature_symbol_list = [f"f_{i}" for i in range(nf)]
         cols = {k: [] for k in ("op", "q0", "s", "fa", "ca", "da", "fb", "cb", "db")}
         mat, table = [], _MatTable()
-        channel, branch, chans, chans2 = [], [], _ChannelTable(), _ChannelTable(4)
-        for pos, (name, qubits, angle) in enumerate(gates):
+        channel, branch, chans, chans2, conds = [], [], _ChannelTable(), _ChannelTable(4), _Conditions()
+        for pos, g in enumerate(gates):
+            name, qubits, angle, cond = _split_gate(g, f"gate {pos}")
             code = _gate_code(name)
             qubits = [int(q) for q in (qubits if np.ndim(qubits) else [qubits])]
             if _arity(code) != len(qubits):
@@ -799,7 +940,9 @@ class CircuitAnsatz:
                     raise ValueError(f"{name}: angle {angle!r} is not (s, (a, c_a, d_a)[, (b, c_b, d_b)])")
                 s, fa = float(angle[0]), _factor(angle[1], nf)
                 fb = _factor(angle[2], nf) if len(angle) == 3 else one
-            for o, q, is_gate in _route(code, qubits, n):
+            route = _route(code, qubits, n)
+            conds.add(pos, len(route), len(route) // 2, code in _CHANNEL, *conds.resolve(pos, cond))
+            for o, q, is_gate in route:
                 row = (o, q, s, *fa, *fb) if is_gate else (o, q, 0.0, *one, *one)
                 for k, v in zip(cols, row):
                     cols[k].append(v)
@@ -815,6 +958,8 @@ class CircuitAnsatz:
             arr["kraus"], arr["n_kraus"] = chans.arrays()
         if chans2.entries:
             arr["kraus2"], arr["n_kraus2"] = chans2.arrays()
+        if conds.any:
+            arr["cond_gate"], arr["cond_mask"] = conds.arrays()
         self.ansatz_circ = CircuitProgram(n, **arr)
 
     def layer_ends(self) -> list:

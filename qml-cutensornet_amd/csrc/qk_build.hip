@@ -62,7 +62,9 @@ struct ChanArgs {
   unsigned seed_lo, seed_hi, first_gate;  // the Philox key; the position of gate 0 in the uninterrupted program
   const uint32_t* state_index;  // [n_states] the names of the trajectories: Philox counter (first_gate + i, trajectory, state_index, 2)
   const uint32_t* trajectory;   // [n_states]
-  int8_t* branch_out;       // [n_states][n_kgates] the branch taken (-1 where the state's program stopped early)
+  const int32_t* cond_col;  // [n_ops] classical control: the column kgate[cond_gate[i]] of branch_out that decides whether gate i runs, -1: unconditional (null: no conditions)
+  const uint32_t* cond_mask; // [n_ops] bit v: branch v lets gate i run (read where cond_col[i] >= 0)
+  int8_t* branch_out;       // [n_states][n_kgates] the branch taken (-1 where the state's program stopped early, -2 where the gate was skipped)
   double* logw_out;         // [n_ckpt][n_states] sum of log(p_b / N) so far
   const double* init_logw;  // [n_states] of the initial snapshot (read when init_heap is set)
 };
@@ -627,6 +629,8 @@ struct ChanTable {  // the channel tables of op codes 10 and 11 and the names of
   const uint32_t* state_index = nullptr;  // [n_states], null: 0 .. n_states-1
   const uint32_t* trajectory = nullptr;   // [n_states], null: all 0
   uint32_t first_gate = 0;
+  const int32_t* cond_gate = nullptr;   // [n_ops] classical control (qk_build_mps_conditions), null: none
+  const uint32_t* cond_mask = nullptr;  // [n_ops]
 };
 
 static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
@@ -729,14 +733,31 @@ static int check_chan_table(const char* what, int n_qubits, int n_ops, const int
   return QK_OK;
 }
 
-// the body of qk_build_mps_channels (n_channels2 = 0) and qk_build_mps_channels2
+// The condition rows of a program, checked before anything runs (check_chan_table has passed): cond_gate[i] inside -1 .. i-1, the gate
+// it names of op code 10 or 11, no mask bit at or above the number of Kraus matrices of that gate's channel.
+static int check_conditions(const char* what, int n_ops, const int8_t* op, const ChanTable& t) {
+  for (int i = 0; i < n_ops; ++i) {
+    const int g = t.cond_gate[i];
+    if (g == -1) continue;
+    if (g < -1 || g >= i) return qk_fail(QK_EINVAL, "%s: gate %d: condition on gate %d outside -1..%d", what, i, g, i - 1);
+    if (op[g] != OP_K1 && op[g] != OP_K2) return qk_fail(QK_EINVAL, "%s: gate %d: condition on gate %d, which is no channel gate (op code %d)", what, i, g, (int)op[g]);
+    const int m = (op[g] == OP_K2 ? t.n_kraus2 : t.n_kraus)[t.channel[g]];
+    if (m < 32 && (t.cond_mask[i] >> m) != 0u) return qk_fail(QK_EINVAL, "%s: gate %d: condition mask names a branch at or above the %d of gate %d", what, i, m, g);
+  }
+  return QK_OK;
+}
+
+// the body of qk_build_mps_channels (n_channels2 = 0), qk_build_mps_channels2 and qk_build_mps_conditions (cond_gate set)
 static int build_channels(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
                           double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
                           int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
                           const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
                           const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const double* kraus2,
-                          const int32_t* n_kraus2, qk_built** out) {
+                          const int32_t* n_kraus2, qk_built** out, const int32_t* cond_gate = nullptr, const uint32_t* cond_mask = nullptr) {
   ChanTable t;
+  if (cond_gate && !cond_mask) return qk_fail(QK_EINVAL, "%s: condition rows need cond_gate and cond_mask", what);
+  if (cond_gate && n_channels <= 0 && n_channels2 <= 0) return qk_fail(QK_EINVAL, "%s: gate 0: condition rows need a program with a channel table", what);
+  t.cond_gate = cond_gate, t.cond_mask = cond_gate ? cond_mask : nullptr;
   if (n_channels2 < 0 || (n_channels2 > 0 && (!kraus2 || !n_kraus2 || !channel || !branch)))
     return qk_fail(QK_EINVAL, "%s: a two-qubit channel table needs n_channels2 >= 0, kraus2, n_kraus2, channel and branch", what);
   if (n_channels < 0 || (n_channels > 0 && (!kraus || !n_kraus || !channel || !branch))) return qk_fail(QK_EINVAL, "%s: a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch", what);
@@ -774,6 +795,21 @@ extern "C" int qk_build_mps_channels2(qk_ctx* c, int32_t n_states, int32_t n_qub
   return build_channels("qk_build_mps_channels2", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
                         n_mats, mats, mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate, n_channels2, kraus2,
                         n_kraus2, out);
+}
+
+extern "C" int qk_build_mps_conditions(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                                       double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                                       int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
+                                       const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
+                                       const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const double* kraus2,
+                                       const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, qk_built** out) {
+  if (!cond_gate)  // without condition rows the call IS qk_build_mps_channels2
+    return qk_build_mps_channels2(c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot, n_mats, mats,
+                                  mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate, n_channels2, kraus2,
+                                  n_kraus2, out);
+  return build_channels("qk_build_mps_conditions", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial,
+                        initial_snapshot, n_mats, mats, mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate,
+                        n_channels2, kraus2, n_kraus2, out, cond_gate, cond_mask);
 }
 
 static int build_gates(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
@@ -823,6 +859,10 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
       kgate[i] = n_kgates;
       n_kgates += (op[i] == OP_K1 || op[i] == OP_K2);
       n_k2gates += (op[i] == OP_K2);
+    }
+    if (cht.cond_gate) {
+      const int rc2 = check_conditions(what, n_ops, op, cht);
+      if (rc2 != QK_OK) return rc2;
     }
   }
   if (init) {  // a resumed build starts from snapshot init_j of `init`, which is only read
@@ -902,7 +942,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   HIP_TRY_AS(what, c->build_work.ensure((size_t)grid * (4 * wslot + wtab) * sizeof(cd)));
   QkDevBuf heap, d_op, d_q0, d_alpha, d_fid, d_secs, d_dims, d_offs, d_ctr, d_err, d_order;  // d_ctr: [0] state counter, [1] heap top
   QkDevBuf d_ckpt, d_centre, d_ioffs, d_idims, d_ifid, d_icentre, d_mats, d_mat;
-  QkDevBuf d_logw, d_ilogw, d_kraus, d_nkraus, d_kraus2, d_nkraus2, d_channel, d_branch, d_kgate, d_sidx, d_traj, d_bout, d_chan;
+  QkDevBuf d_logw, d_ilogw, d_kraus, d_nkraus, d_kraus2, d_nkraus2, d_channel, d_branch, d_kgate, d_sidx, d_traj, d_bout, d_chan, d_ccol, d_cmask;
   const size_t n_rec = (size_t)n_ckpt * n_states;  // (snapshot, state) records
   HIP_TRY_AS(what, heap.alloc(heap_cap * sizeof(cd)));
   HIP_TRY_AS(what, d_op.alloc(std::max(1, n_ops)));
@@ -964,6 +1004,18 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
     ChanArgs ca;
     ca.kraus2 = with_k2 ? d_kraus2.get<cd>() : nullptr, ca.n_kraus2 = with_k2 ? d_nkraus2.get<int32_t>() : nullptr;
     ca.kraus = d_kraus.get<cd>(), ca.n_kraus = d_nkraus.get<int32_t>(), ca.channel = d_channel.get<int32_t>(), ca.branch = d_branch.get<int32_t>();
+    ca.cond_col = nullptr, ca.cond_mask = nullptr;
+    bool conditional = false;
+    for (int i = 0; cht.cond_gate && i < n_ops; ++i) conditional = conditional || cht.cond_gate[i] >= 0;
+    if (conditional) {  // rows whose gates are all unconditional are no rows: the kernel then does what it does without them
+      std::vector<int32_t> ccol((size_t)n_ops);
+      for (int i = 0; i < n_ops; ++i) ccol[i] = cht.cond_gate[i] >= 0 ? kgate[cht.cond_gate[i]] : -1;
+      HIP_TRY_AS(what, d_ccol.alloc((size_t)n_ops * sizeof(int32_t)));
+      HIP_TRY_AS(what, d_cmask.alloc((size_t)n_ops * sizeof(uint32_t)));
+      HIP_TRY_AS(what, hipMemcpy(d_ccol.get(), ccol.data(), (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
+      HIP_TRY_AS(what, hipMemcpy(d_cmask.get(), cht.cond_mask, (size_t)n_ops * sizeof(uint32_t), hipMemcpyHostToDevice));
+      ca.cond_col = d_ccol.get<int32_t>(), ca.cond_mask = d_cmask.get<uint32_t>();
+    }
     ca.kgate = d_kgate.get<int32_t>(), ca.branch_stride = cht.stride ? n_ops : 0, ca.n_kgates = n_kgates;
     ca.seed_lo = (unsigned)cht.seed, ca.seed_hi = (unsigned)(cht.seed >> 32), ca.first_gate = cht.first_gate;
     ca.state_index = d_sidx.get<uint32_t>(), ca.trajectory = d_traj.get<uint32_t>(), ca.branch_out = d_bout.get<int8_t>();

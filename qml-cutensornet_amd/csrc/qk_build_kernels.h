@@ -1374,6 +1374,23 @@ __device__ __noinline__ void wg_channel_2q(cd* TH, const int l, const int r, con
   __syncthreads();
 }
 
+// ---- classical control: is the condition of gate i of state st false?  One load of the branch the channel gate cond_gate[i] of this
+// state recorded (column cond_col[i] of its row of branch_out), the same value in every thread.  A skipped channel gate records -2
+// (thread 0, in front of a barrier: a condition on it reads -2, "no").  Kept out of line and behind the one pointer `ca`, like the
+// channel steps, so that the gate loop keeps its register allocation.
+__device__ __noinline__ bool wg_condition_false(const ChanArgs* ca, const int st, const int i, const int o) {
+  const int col = ca->cond_col[i];
+  if (col < 0) return false;
+  int8_t* row = ca->branch_out + (long)st * ca->n_kgates;
+  const int b = row[col];
+  if (b >= 0 && ((ca->cond_mask[i] >> b) & 1u)) return false;
+  if (o == OP_K1 || o == OP_K2) {
+    if (threadIdx.x == 0) row[ca->kgate[i]] = (int8_t)-2;
+    __syncthreads();
+  }
+  return true;
+}
+
 // MINWG: resident workgroups per CU the register budget is cut for: 256 threads: 2 (76 KiB of LDS each) or 4 (38 KiB); 512 threads: 1 (152 KiB).
 // CHAN: the program holds channel gates (op codes 10 and 11).  A program without them runs the instantiation that has none of their code, so
 // its registers, its spills and its arithmetic are those of the kernel before the channels (the compiler's resource report of the
@@ -1435,6 +1452,13 @@ __global__ __launch_bounds__(BT, MINWG) void qk_build_kernel(const BuildArgs g) 
           if (tid == 0) g.chan->logw_out[rec] = sh.logw;
         }
         ++ck;
+      }
+      if constexpr (CHAN) {
+        // Classical control: gate i runs only where the branch that channel gate cond_gate[i] of this state recorded is one of its
+        // mask; else it does nothing at all, and is a done gate all the same.  The branch was stored by thread 0 inside wg_channel /
+        // wg_channel_2q in front of a barrier every thread has passed (a skipped channel gate: the barrier of wg_condition_false), so the load is
+        // the same value in every thread.  Rows of branch_out are per state and preset to -1 per call: -1 and -2 both read "no".
+        if (g.chan->cond_col && wg_condition_false(g.chan, st, i, g.op[i])) continue;
       }
       const int o = g.op[i], q = g.q0[i];
       if ((o < 0 || o >= (g.mats ? N_OPS_MAT : N_OPS)) && !(CHAN && (o == OP_K1 || o == OP_K2))) {  // the matrix gates and the channels need their tables

@@ -94,6 +94,8 @@ struct Channels {
   double* logw_out = nullptr;
   int8_t* branches_out = nullptr;   // [channel gates of the program, codes 10 and 11 in program order]
   double* margin_out = nullptr;
+  const int32_t* cond_gate = nullptr;  // [n_ops] -1: unconditional; g < i: the channel gate whose branch decides (qkb_simulate_conditions)
+  const uint32_t* cond_mask = nullptr; // [n_ops] bit v: branch v of gate cond_gate[i] lets gate i run
   bool any() const { return n_channels > 0 || n_channels2 > 0; }
 };
 
@@ -139,6 +141,21 @@ std::string check_channels(int n_qubits, int n_ops, const int8_t* op, const int3
       if (!(dev <= 1e-12)) return at + "the drawn " + kind + std::to_string(c) + " is not trace preserving (max |sum K^H K - 1| > 1e-12)";
     }
     if (q0[i] < 0 || q0[i] + (two ? 1 : 0) >= n_qubits) return at + kind + "on a qubit outside the register";
+  }
+  return "";
+}
+
+// The condition rows of a program, checked before anything runs: cond_gate[i] inside -1 .. i-1, the gate it names of code 10 or 11, no
+// mask bit at or above the number of Kraus matrices of that gate's channel (check_channels has passed: the channel is valid).
+std::string check_conditions(int n_ops, const int8_t* op, const Channels& ch) {
+  for (int i = 0; i < n_ops; ++i) {
+    const int g = ch.cond_gate[i];
+    if (g == -1) continue;
+    const std::string at = "gate " + std::to_string(i) + ": ";
+    if (g < -1 || g >= i) return at + "condition on gate " + std::to_string(g) + " outside -1.." + std::to_string(i - 1);
+    if (op[g] != OP_K1 && op[g] != OP_K2) return at + "condition on gate " + std::to_string(g) + ", which is no channel gate (op code " + std::to_string((int)op[g]) + ")";
+    const int m = (op[g] == OP_K2 ? ch.n_kraus2 : ch.n_kraus)[ch.channel[g]];
+    if (m < 32 && (ch.cond_mask[i] >> m) != 0u) return at + "condition mask names a branch at or above the " + std::to_string(m) + " of gate " + std::to_string(g);
   }
   return "";
 }
@@ -353,6 +370,42 @@ int qkb_simulate_channels2(int32_t n_qubits, int32_t n_ops, const int8_t* op, co
   ch.logw_out = logw_out, ch.branches_out = branches_out, ch.margin_out = margin_out;
   return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, ch, dims_out, tensors_out, n_complex_out, fidelity_out);
 }
+// qkb_simulate_channels2 with condition rows: gate i with cond_gate[i] = g >= 0 (g < i, a gate of op code 10 or 11 of this program) runs
+// when the branch b recorded for gate g is >= 0 and bit b of cond_mask[i] is set; else it is skipped: no centre move, no theta, no SVD,
+// no change of a bond, of the fidelity or of logw, no draw, no contribution to the margin; a skipped channel gate records branch -2 (a
+// condition on it is false).  The look-ahead that places the centre behind a two-qubit gate counts skipped gates as present.  -8
+// before a gate is applied, naming the gate, for rows without a channel table, cond_gate[i] outside -1 .. i-1, a gate named that is
+// not of code 10 or 11, a mask bit at or above the number of that gate's Kraus matrices, cond_mask null.  With cond_gate null the
+// call IS qkb_simulate_channels2.
+int qkb_simulate_conditions(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
+                            int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
+                            const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate,
+                            int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, int32_t* dims_out,
+                            double** tensors_out, int64_t* n_complex_out, double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out) {
+  if (!cond_gate)
+    return qkb_simulate_channels2(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, n_channels, kraus, n_kraus, channel, branch, seed,
+                                  state_index, trajectory, first_gate, n_channels2, kraus2, n_kraus2, dims_out, tensors_out, n_complex_out, fidelity_out, logw_out, branches_out,
+                                  margin_out);
+  if (!cond_mask) {
+    g_err = "condition rows need cond_gate and cond_mask";
+    return -8;
+  }
+  if (n_channels <= 0 && n_channels2 <= 0) {
+    g_err = "gate 0: condition rows need a program with a channel table";
+    return -8;
+  }
+  Channels ch;
+  if ((n_channels > 0 && (!kraus || !n_kraus)) || (n_channels2 > 0 && (!kraus2 || !n_kraus2)) || !channel || !branch) {
+    g_err = "a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch; a two-qubit one n_channels2 >= 0, kraus2 and n_kraus2";
+    return -8;
+  }
+  if (n_channels > 0) ch.n_channels = n_channels, ch.kraus = reinterpret_cast<const cd*>(kraus), ch.n_kraus = n_kraus;
+  if (n_channels2 > 0) ch.n_channels2 = n_channels2, ch.kraus2 = reinterpret_cast<const cd*>(kraus2), ch.n_kraus2 = n_kraus2;
+  ch.channel = channel, ch.branch = branch, ch.cond_gate = cond_gate, ch.cond_mask = cond_mask;
+  ch.seed = seed, ch.state_index = state_index, ch.trajectory = trajectory, ch.first_gate = first_gate;
+  ch.logw_out = logw_out, ch.branches_out = branches_out, ch.margin_out = margin_out;
+  return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, ch, dims_out, tensors_out, n_complex_out, fidelity_out);
+}
 }  // extern "C"
 
 static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
@@ -381,9 +434,14 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
   if (ch.any()) {
     g_err = check_channels(n, n_ops, op, q0, ch);
     if (!g_err.empty()) return -8;
+    if (ch.cond_gate) {
+      g_err = check_conditions(n_ops, op, ch);
+      if (!g_err.empty()) return -8;
+    }
   }
   double logw = 0.0, margin = INFINITY;
   int n_drawn = 0;  // channel gates done: the index into branches_out
+  std::vector<int> taken(ch.cond_gate ? n_ops : 0, -1);  // the branch every channel gate of this state took (-2: skipped), by position
   std::vector<Tensor> A(n);
   for (auto& t : A) t.v = {cd(1, 0), cd(0, 0)};
   std::vector<int> two_q_pos;
@@ -402,6 +460,18 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
     if (q < 0 || q >= n || (is_two_qubit(o) && q + 1 >= n)) {
       g_err = "gate on a qubit outside the register";
       return -3;
+    }
+    if (ch.cond_gate && ch.cond_gate[i] >= 0) {  // a gate whose condition is false does nothing at all; it is a done gate all the same
+      const int b = taken[ch.cond_gate[i]];
+      if (b < 0 || !((ch.cond_mask[i] >> b) & 1u)) {
+        if (o == OP_K1 || o == OP_K2) {
+          taken[i] = -2;
+          if (ch.branches_out) ch.branches_out[n_drawn] = -2;
+          ++n_drawn;
+        }
+        g2 += is_two_qubit(o);  // the look-ahead is a function of the op codes alone
+        continue;
+      }
     }
     if (o == OP_H) {
       Tensor& t = A[q];
@@ -516,6 +586,7 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
         }
       logw += std::log(p[b] / N);
       if (ch.branches_out) ch.branches_out[n_drawn] = (int8_t)b;
+      if (ch.cond_gate) taken[i] = b;
       ++n_drawn;
       continue;
     }
@@ -579,6 +650,7 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
         }
       logw += std::log(p[b] / N);
       if (ch.branches_out) ch.branches_out[n_drawn] = (int8_t)b;
+      if (ch.cond_gate) taken[i] = b;
       ++n_drawn;
     } else if (o == OP_M2) {  // a 4x4 from the table on (t00, t01, t10, t11)
       const cd* M = mats + (size_t)mat[i] * 16;

@@ -129,6 +129,8 @@ _SIGNATURES = [
                                         C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(_P)]),
     ("qk_build_mps_channels2", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
                                          C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.c_int32, _P, _P, C.POINTER(_P)]),
+    ("qk_build_mps_conditions", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
+                                          C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.c_int32, _P, _P, _P, _P, C.POINTER(_P)]),
     ("qk_built_logw_at", C.c_int, [_P, C.c_int32, _P]),
     ("qk_built_num_channel_gates", C.c_int, [_P]),
     ("qk_built_branches", C.c_int, [_P, _P]),
@@ -317,7 +319,8 @@ def with_noise(gates, channel_name, params, after="all"):
     the name of a two-qubit channel (``Depolarizing2q``, ``CorrelatedPhaseFlip``, ..) and ``after="two_qubit"``, ONE channel
     ``(channel_name, [a, b], params)`` goes behind every two-qubit gate, on its pair as the gate names it: correlated gate noise,
     which no pair of one-qubit channels expresses (``after="all"`` is a ``ValueError`` then).  Gates that are channels themselves
-    get none.  The list goes to ``BoundCircuit.from_gates`` / ``as_bound_circuit`` or, with the parameters in the place of the
+    get none.  A conditional gate ``(name, qubits, params, (g, values))`` passes through with g remapped over the channels put
+    in, and the channel behind it takes the gate's condition (noise of a gate that did not run does not act).  The list goes to ``BoundCircuit.from_gates`` / ``as_bound_circuit`` or, with the parameters in the place of the
     angle, to ``CircuitAnsatz``."""
     from .ansatz import _CHANNEL2_NAMES, _CHANNEL_NAMES
 
@@ -328,17 +331,25 @@ def with_noise(gates, channel_name, params, after="all"):
     pair = channel_name in _CHANNEL2_NAMES
     if pair and after == "all":
         raise ValueError(f"the two-qubit channel {channel_name!r} goes behind two-qubit gates only: after must be 'two_qubit'")
-    out = []
-    for g in gates:
+    out, moved = [], []  # moved[p]: the position in `out` of gate p of `gates`
+    for pos, g in enumerate(gates):
+        cond = ()
+        if len(g) == 4 and g[3] is not None:
+            at, values = g[3]
+            if not 0 <= int(at) < pos:
+                raise ValueError(f"gate {pos}: condition on gate {at} outside 0..{pos - 1}")
+            cond = ((moved[int(at)], values),)
+            g = (g[0], g[1], g[2]) + cond
+        moved.append(len(out))
         out.append(g)
         name, qubits = g[0], g[1]
         qs = [int(q) for q in (qubits if np.ndim(qubits) else [qubits])]
         if (isinstance(name, str) and (name in _CHANNEL_NAMES or name in _CHANNEL2_NAMES)) or (after == "two_qubit" and len(qs) != 2):
             continue
         if pair:
-            out.append((channel_name, qs, params))
+            out.append((channel_name, qs, params) + cond)
         else:
-            out.extend((channel_name, [q], params) for q in qs)
+            out.extend((channel_name, [q], params) + cond for q in qs)
     return out
 
 
@@ -1401,7 +1412,8 @@ class _GateProgram:
     The channel tables (op codes 10 and 11) belong to the gate structure: ``channel``, ``kraus`` and ``n_kraus``, ``kraus2`` and
     ``n_kraus2`` must be the same for every circuit; ``branch`` may differ per state (one row for all when they agree, stride 0, otherwise a row per state).  ``seed``,
     ``state_index`` and ``trajectory`` (a scalar for all states, or one per state; ``None``: 0 .. n-1 and 0) name the trajectories,
-    ``first_gate`` the position of the first gate in the uninterrupted program."""
+    ``first_gate`` the position of the first gate in the uninterrupted program.  The condition rows ``cond_gate`` and ``cond_mask``
+    are gate structure too: the same for every circuit; a call with them goes through ``qk_build_mps_conditions``."""
 
     def __init__(self, what, circuits, seed=0, state_index=None, trajectory=None, first_gate=0):
         c0 = circuits[0]
@@ -1464,6 +1476,17 @@ class _GateProgram:
                 self.branch = rows[0]
             else:
                 self.branch, self.bstride = np.ascontiguousarray(np.stack(rows)), int(self.op.shape[0])
+        self.cond_gate, self.cond_mask = None, None
+        conds = [(getattr(c, "cond_gate", None), getattr(c, "cond_mask", None)) for c in circuits]
+        if any(g is not None for g, _ in conds):
+            g0, m0 = conds[0]
+            same = lambda a, b: (a is None) == (b is None) and (a is None or np.array_equal(a, b))  # noqa: E731
+            if not all(same(g, g0) and same(m, m0) for g, m in conds[1:]):
+                raise QkError(f"{what}: the circuits of one call must share their gate structure (the condition rows included)")
+            if np.shape(g0) != self.op.shape or (m0 is not None and np.shape(m0) != self.op.shape):
+                raise QkError(f"{what}: cond_gate and cond_mask must hold one entry per gate, got shapes {np.shape(g0)}, {np.shape(m0)}")
+            self.cond_gate = np.ascontiguousarray(g0, dtype=np.int32)  # the C entry validates the rows
+            self.cond_mask = None if m0 is None else np.ascontiguousarray(np.asarray(m0).astype(np.uint32))
         self.seed = int(_seed_key(seed)[0]) | (int(_seed_key(seed)[1]) << 32)
         self.state_index = self._ids("state_index", state_index, np.arange(self.ns))
         self.trajectory = self._ids("trajectory", trajectory, np.zeros(self.ns, dtype=np.int64))
@@ -1485,14 +1508,20 @@ class _GateProgram:
         h = _P()
         head = (ctx._h, self.ns, self.n, n_ops, self.op.ctypes.data, self.q0.ctypes.data, self.alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero),
                 int(max_bond), flags)
-        if (self.n_channels or self.n_channels2) and n_ops:
+        if (self.n_channels or self.n_channels2 or self.cond_gate is not None) and n_ops:
             if cps is None:
                 cps = np.array([n_ops], dtype=np.int32)
             chan = (int(cps.shape[0]), cps.ctypes.data, src, src_j, self.n_mats, self.mats.ctypes.data if self.n_mats else None, self.stride,
                     self.mat.ctypes.data if self.n_mats else None, self.n_channels, self.kraus.ctypes.data if self.n_channels else None,
-                    self.n_kraus.ctypes.data if self.n_channels else None, self.channel.ctypes.data, self.branch.ctypes.data, self.bstride, self.seed,
+                    self.n_kraus.ctypes.data if self.n_channels else None, None if self.channel is None else self.channel.ctypes.data,
+                    None if self.branch is None else self.branch.ctypes.data, self.bstride, self.seed,
                     self.state_index.ctypes.data, self.trajectory.ctypes.data, self.first_gate)
-            if self.n_channels2:
+            if self.cond_gate is not None:
+                _check(lib().qk_build_mps_conditions(*head, *chan, self.n_channels2, self.kraus2.ctypes.data if self.n_channels2 else None,
+                                                     self.n_kraus2.ctypes.data if self.n_channels2 else None, self.cond_gate.ctypes.data,
+                                                     None if self.cond_mask is None else self.cond_mask.ctypes.data, C.byref(h)),
+                       "qk_build_mps_conditions")
+            elif self.n_channels2:
                 _check(lib().qk_build_mps_channels2(*head, *chan, self.n_channels2, self.kraus2.ctypes.data, self.n_kraus2.ctypes.data, C.byref(h)), "qk_build_mps_channels2")
             else:
                 _check(lib().qk_build_mps_channels(*head, *chan, C.byref(h)), "qk_build_mps_channels")

@@ -22,7 +22,7 @@ import numpy as np
 from scipy.linalg import qr as _qr
 from scipy.linalg import svd as _svd
 
-from .ansatz import (OP_H, OP_K1, OP_K2, OP_M1, OP_M2, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_channel_gates, check_checkpoints, check_matrix_gates,
+from .ansatz import (OP_H, OP_K1, OP_K2, OP_M1, OP_M2, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_channel_gates, check_checkpoints, check_condition_gates, check_matrix_gates,
                      is_two_qubit, reject_channels)
 
 _SQRT_HALF = 0.7071067811865476
@@ -462,6 +462,7 @@ def _native_builder():
                                                   C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p,
                                                   C.POINTER(C.c_double)]
             lib.qkb_simulate_channels2.argtypes = lib.qkb_simulate_channels.argtypes[:20] + [C.c_int32, C.c_void_p, C.c_void_p] + lib.qkb_simulate_channels.argtypes[20:]
+            lib.qkb_simulate_conditions.argtypes = lib.qkb_simulate_channels2.argtypes[:23] + [C.c_void_p, C.c_void_p] + lib.qkb_simulate_channels2.argtypes[23:]
             lib.qkb_free.argtypes = [C.c_void_p]
             if blas and lib.qkb_init(os.path.realpath(blas[0]).encode()) == 0:
                 _NATIVE = lib
@@ -470,10 +471,20 @@ def _native_builder():
     return _NATIVE or None
 
 
+def _condition_rows(circuit, op):
+    """The condition rows of ``circuit`` as the native entries take them: (cond_gate int32, cond_mask uint32 or None)."""
+    cg = np.ascontiguousarray(circuit.cond_gate, dtype=np.int32)
+    cm = None if circuit.cond_mask is None else np.ascontiguousarray(np.asarray(circuit.cond_mask).astype(np.uint32))
+    if cg.shape != op.shape or (cm is not None and cm.shape != op.shape):
+        raise ValueError(f"a program with conditions needs a cond_gate and a cond_mask per gate, got shapes {cg.shape}, {None if cm is None else cm.shape}")
+    return cg, cm
+
+
 def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None, seed=0, state_index=0,
                     trajectory=0, first_gate=0, margin=False):
     """``simulate`` through the native builder: same algorithm and LAPACK routines, no interpreter in the gate loop.  A circuit with
-    a channel table goes through ``qkb_simulate_channels``, one with a two-qubit channel table through ``qkb_simulate_channels2`` (the trajectory arguments and ``margin`` as in ``simulate``)."""
+    a channel table goes through ``qkb_simulate_channels``, one with a two-qubit channel table through ``qkb_simulate_channels2``, one with condition rows
+    through ``qkb_simulate_conditions`` (the trajectory arguments and ``margin`` as in ``simulate``)."""
     import ctypes as C
 
     lib = _native_builder()
@@ -519,15 +530,28 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
                 n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None, n1, kraus.ctypes.data if n1 else None,
                 n_kraus.ctypes.data if n1 else None, channel.ctypes.data, branch.ctypes.data, seed, state_index, trajectory, first_gate)
         tail = (dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid), C.byref(logw), branches.ctypes.data, C.byref(worst))
-        if n2:
+        if circuit.cond_gate is not None:  # the native builder validates the rows
+            cg, cm = _condition_rows(circuit, op)
+            rc = lib.qkb_simulate_conditions(*head, n2, kraus2.ctypes.data if n2 else None, n_kraus2.ctypes.data if n2 else None, cg.ctypes.data,
+                                             None if cm is None else cm.ctypes.data, *tail)
+        elif n2:
             rc = lib.qkb_simulate_channels2(*head, n2, kraus2.ctypes.data, n_kraus2.ctypes.data, *tail)
         else:
             rc = lib.qkb_simulate_channels(*head, *tail)
         branches = branches[:n_kgates]
     else:
-        rc = lib.qkb_simulate_gates(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
-                                    float(value_of_zero), int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None,
-                                    dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid))
+        if circuit.cond_gate is not None:  # condition rows without a channel table: handed over as they are, the native builder refuses them
+            cg, cm = _condition_rows(circuit, op)
+            rc = lib.qkb_simulate_conditions(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero),
+                                             int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None, 0, None, None, None, None, seed,
+                                             state_index, trajectory, first_gate, 0, None, None, cg.ctypes.data, None if cm is None else cm.ctypes.data, dims.ctypes.data,
+                                             C.byref(block), C.byref(count), C.byref(fid), None, None, None)
+            if rc == 0:
+                rc = -8  # (not reached: the entry refuses rows without a table)
+        else:
+            rc = lib.qkb_simulate_gates(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
+                                        float(value_of_zero), int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None,
+                                        dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid))
     if rc in (-7, -8, -9):  # an op code outside the program's vocabulary; a bad matrix or channel gate; an impossible outcome of a channel
         raise ValueError(f"native MPS builder: {lib.qkb_last_error().decode()}")
     if rc != 0:
@@ -734,13 +758,21 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
     ``u = engine.channel_uniform(seed, first_gate + i, trajectory, state_index)``; ``A_q <- (K_b / sqrt(p_b)) A_q`` and ``logw +=
     log(p_b / N)``.  The result carries ``logw`` and ``branches``; with ``margin`` the return value is ``(result, margin)``, the
     smallest ``|u tot - cum| / tot`` over the thresholds of all draws (inf without one).  ``ValueError`` naming the state and the gate
-    for an impossible outcome (``p_b`` 0 or not finite, ``tot`` 0 in a draw)."""
+    for an impossible outcome (``p_b`` 0 or not finite, ``tot`` 0 in a draw).
+
+    Classical control (``cond_gate``, ``cond_mask``; a channel table is needed): gate i with ``cond_gate[i] = g >= 0`` runs when the
+    branch b recorded for gate g is ``>= 0`` and bit b of ``cond_mask[i]`` is set; else it is skipped -- no centre move, no theta, no
+    SVD, no draw, nothing added to ``logw`` or the margin -- and a skipped channel gate records branch -2.  A skipped gate is a done
+    gate for the checkpoints, and the look-ahead ``two_q_pos`` counts it: where a two-qubit gate leaves the centre is a function of
+    the op codes alone."""
     n = circuit.n_qubits
     chan = check_channel_gates(circuit.op, circuit.q0, n, circuit.channel, circuit.branch, circuit.kraus, circuit.n_kraus, circuit.kraus2, circuit.n_kraus2)
     mat, mats = check_matrix_gates(circuit.op, circuit.mat, circuit.mats, with_channels=chan is not None and chan[2] is not None,
                                    with_channels2=chan is not None and chan[4] is not None)  # (None, None): no table, codes 8 and 9 are unknown
     seed, state_index, trajectory, first_gate = _trajectory_ids(seed, state_index, trajectory, first_gate)
+    cond = check_condition_gates(circuit.op, chan, circuit.cond_gate, circuit.cond_mask)  # None: no gate is conditional
     logw, branches, worst = 0.0, [], np.inf
+    taken = {}  # the branch every channel gate took, by position (-2: skipped): what conditions read
 
     def take_branch(i, forced, p):
         """The branch of channel gate i with probabilities p (the forced one, or drawn), and the running margin."""
@@ -793,6 +825,14 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
     for i, (o, q, a) in enumerate(zip(ops, qs, alphas)):
         if i in marks:  # i gates done
             snaps.append(MPS([t.copy() for t in A], fidelity, logw, branches))
+        if cond is not None and cond[0][i] >= 0:  # a gate whose condition is false does nothing at all; it is a done gate all the same
+            b = taken[int(cond[0][i])]
+            if b < 0 or not (int(cond[1][i]) >> b) & 1:
+                if o in (OP_K1, OP_K2):
+                    taken[i] = -2
+                    branches.append(-2)
+                g2 += is_two_qubit(o)  # the look-ahead is a function of the op codes alone
+                continue
         if o == OP_H:
             t = A[q]
             A[q] = np.stack((t[:, 0] + t[:, 1], t[:, 0] - t[:, 1]), axis=1) * _SQRT_HALF
@@ -849,6 +889,7 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             A[q] = np.stack((Kb[0, 0] * t0 + Kb[0, 1] * t1, Kb[1, 0] * t0 + Kb[1, 1] * t1), axis=1)
             logw += float(np.log(p[b] / N))
             branches.append(b)
+            taken[i] = b
             continue
 
         l = A[q].shape[0]
@@ -877,6 +918,7 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
             theta = np.einsum("pqst,lstr->lpqr", K[b] / np.sqrt(p[b]), theta)
             logw += float(np.log(p[b] / N))
             branches.append(b)
+            taken[i] = b
         else:  # XXPhase: cos(th) 1 - i sin(th) X(x)X
             th = 0.5 * np.pi * a
             theta = np.cos(th) * theta - 1j * np.sin(th) * theta[:, ::-1, ::-1, :]
