@@ -912,6 +912,26 @@ int qk_built_info_at(const qk_built* built, int32_t j, int32_t* dims, double* fi
 /* The states of snapshot j, packed back to back in state order (2 * total_complex doubles of qk_built_info_at) */
 int qk_built_download_at(const qk_built* built, int32_t j, double* host);
 int qk_mps_set_from_built_at(qk_ctx* ctx, const qk_built* built, int32_t j, qk_mps_set** out); /* qk_mps_set_from_built of snapshot j */
+/* Building from given states: an fp64 set of this context becomes a qk_built with ONE snapshot of zero gates (qk_built_num_snapshots
+ * 1, qk_built_checkpoints [0], no channel gates), from which every build entry above resumes through initial, initial_snapshot = 0.
+ * index[s] (NULL: identity, n_states must be the set's) names the set state build state s starts from: the heap holds each set state
+ * once, the per-state tables repeat (broadcast, trajectories).
+ *   - Verbatim path (qk_mps_set_centre(set) >= 0 and QK_SEED_SWEEP not set): the true-bond corners are copied bit for bit, nothing is
+ *     rescaled; fidelity 1, log-weight 0, the centre the recorded one, norms 1 (not computed); qk_built_launch reports zeros.
+ *   - Sweep path (any gauge, any norm, bonds <= 512): a finite check (a state with an element that is not finite: QK_EDEVICE naming
+ *     the first), the canonical sweep of qk_mps_set_compress with max_bond = 0, max_discard = 0 and value_of_zero (a bond whose rank
+ *     is below its dimension shrinks to its rank; the centre ends on the last site), and the last site divided by its Frobenius norm,
+ *     which goes to norms (0 or not finite: QK_EDEVICE naming the state).  fidelity is the sweep's; qk_built_launch its grid.
+ * norms and fidelity ([set states], may be NULL) are indexed by the SET's states.  QK_EINVAL: a null argument, a set of another context, a
+ * complex64 set, n_states < 1, an index entry outside the set, value_of_zero negative or not finite, a bond beyond 512 (sweep path).
+ * A bond above a later build's max_bond is refused by that build.                                                                  */
+#define QK_SEED_SWEEP 1u /* take the sweep path even where the set records its centre */
+int qk_built_from_set(qk_ctx* ctx, const qk_mps_set* set, int32_t n_states, const int32_t* index, double value_of_zero, uint32_t flags,
+                      qk_built** out, double* norms, double* fidelity);
+/* The orthogonality centre a set records: the common centre of a snapshot of the device builder (qk_mps_set_from_built,
+ * qk_mps_set_from_built_at), -1 where the gauge is unknown: every other origin (upload, from_packed, all-gather, to_f32, compress)
+ * and a snapshot whose states do not share their centre.                                                                          */
+int qk_mps_set_centre(const qk_mps_set* set);
 /* Diagnostic: the builder's Jacobi primitive on one host matrix a[p][q] (complex128 row-major, overwritten by A V);
  * v_out[q][q], sig_out[q] = column norms of A V, ord_out[q] = columns by decreasing norm.                          */
 int qk_debug_jacobi(qk_ctx* ctx, int32_t p, int32_t q, double* a_inout, double* v_out, double* sig_out, int32_t* ord_out);

@@ -19,7 +19,7 @@ from .mps import MPS, simulate
 _G = {}
 
 
-def _init(ansatz, fidelity, max_bond=None):
+def _init(ansatz, fidelity, max_bond=None, initial=None):
     for v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
         os.environ[v] = "1"
     try:
@@ -28,7 +28,7 @@ def _init(ansatz, fidelity, max_bond=None):
         _G["tp"] = threadpool_limits(1)
     except Exception:  # pragma: no cover - threadpoolctl is optional
         pass
-    _G["ansatz"], _G["fid"], _G["chi"] = ansatz, fidelity, max_bond
+    _G["ansatz"], _G["fid"], _G["chi"], _G["initial"] = ansatz, fidelity, max_bond, initial
 
 
 def _one(x):
@@ -37,6 +37,17 @@ def _one(x):
     circuit = as_bound_circuit(ansatz.circuit_for_data(x), ansatz)
     reject_channels([circuit], "build_states")
     m = simulate(circuit, _G["fid"], max_bond=_G.get("chi"))
+    return m.tensors, m.fidelity, time.perf_counter() - t0
+
+
+def _one_from(item):
+    """``_one`` for row ``item[0]`` of X, started from its given state."""
+    t0 = time.perf_counter()
+    k, x = item
+    ansatz, initial = _G["ansatz"], _G["initial"]
+    circuit = as_bound_circuit(ansatz.circuit_for_data(x), ansatz)
+    reject_channels([circuit], "build_states")
+    m = simulate(circuit, _G["fid"], max_bond=_G.get("chi"), initial=initial if isinstance(initial, MPS) else initial[k])
     return m.tensors, m.fidelity, time.perf_counter() - t0
 
 
@@ -59,16 +70,20 @@ def default_workers() -> int:
     return max(1, min(n, cap))
 
 
-def build_states(ansatz, X, truncation_fidelity, workers=None, max_bond=None):
-    """Return (list[MPS], per-state build seconds) for the rows of ``X``."""
+def build_states(ansatz, X, truncation_fidelity, workers=None, max_bond=None, initial=None):
+    """Return (list[MPS], per-state build seconds) for the rows of ``X``.  ``initial`` (one ``MPS`` for all rows, or a list with
+    one per row) starts the circuits from given states instead of |0...0> (``simulate(..., initial=)``)."""
     X = np.asarray(X, dtype=np.float64)
     workers = default_workers() if workers is None else int(workers)
     workers = min(workers, len(X)) or 1
+    if initial is not None and not isinstance(initial, MPS) and len(initial) != len(X):
+        raise ValueError(f"build_states: {len(initial)} initial states for {len(X)} data points")
+    fn, jobs = (_one, list(X)) if initial is None else (_one_from, list(enumerate(X)))
     if workers <= 1:
-        _init(ansatz, truncation_fidelity, max_bond)
-        res = [_one(x) for x in X]
+        _init(ansatz, truncation_fidelity, max_bond, initial)
+        res = [fn(x) for x in jobs]
     else:
         ctx = mp.get_context("fork")
-        with ctx.Pool(workers, initializer=_init, initargs=(ansatz, truncation_fidelity, max_bond)) as pool:
-            res = pool.map(_one, list(X), chunksize=1)
+        with ctx.Pool(workers, initializer=_init, initargs=(ansatz, truncation_fidelity, max_bond, initial)) as pool:
+            res = pool.map(fn, jobs, chunksize=1)
     return [MPS(t, f) for t, f, _ in res], [dt for _, _, dt in res]

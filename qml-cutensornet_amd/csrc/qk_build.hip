@@ -139,6 +139,41 @@ __global__ __launch_bounds__(256) void qk_pack_built_kernel(const cd* __restrict
   }
 }
 
+// The inverse (qk_built_from_set, verbatim path): site (s, k) of a set's image, two planes [pad16(l)][2][pad16(r)], becomes the
+// interleaved packed [l][2][r] of a builder's heap.  One workgroup per (state, site); true bonds only, nothing is rescaled: the bits
+// of the heap are the bits of the set.
+__global__ __launch_bounds__(256) void qk_unpack_set_kernel(const double* __restrict__ data, const long long* __restrict__ src_offs,
+                                                            const long long* __restrict__ dst_offs, const int32_t* __restrict__ dims_true,
+                                                            const int32_t* __restrict__ dims_pad, int n_sites, cd* __restrict__ heap) {
+  const int s = blockIdx.x / n_sites, k = blockIdx.x - s * n_sites;
+  const int cl = dims_true[(long)s * (n_sites + 1) + k], cr = dims_true[(long)s * (n_sites + 1) + k + 1];
+  const int pl = dims_pad[(long)s * (n_sites + 1) + k], pr = dims_pad[(long)s * (n_sites + 1) + k + 1];
+  const double* re = data + src_offs[blockIdx.x];
+  const double* im = re + (long)pl * 2 * pr;
+  cd* dst = heap + dst_offs[blockIdx.x];
+  for (int e = threadIdx.x; e < cl * 2 * cr; e += 256) {
+    const int row = e / cr, c = e - row * cr;
+    dst[e] = cd{re[(long)row * pr + c], im[(long)row * pr + c]};
+  }
+}
+
+// The finite check of the sweep path: one workgroup per (state, site) reads the true-bond corner of the site's planes and raises the
+// state's flag (zeroed by the host) when an element is not finite.  Every writer of a flag writes the same 1.
+__global__ __launch_bounds__(256) void qk_seed_finite_kernel(const double* __restrict__ data, const long long* __restrict__ src_offs,
+                                                             const int32_t* __restrict__ dims_true, const int32_t* __restrict__ dims_pad, int n_sites,
+                                                             int32_t* __restrict__ flags) {
+  const int s = blockIdx.x / n_sites, k = blockIdx.x - s * n_sites;
+  const int cl = dims_true[(long)s * (n_sites + 1) + k], cr = dims_true[(long)s * (n_sites + 1) + k + 1];
+  const int pl = dims_pad[(long)s * (n_sites + 1) + k], pr = dims_pad[(long)s * (n_sites + 1) + k + 1];
+  const double* re = data + src_offs[blockIdx.x];
+  const double* im = re + (long)pl * 2 * pr;
+  int bad = 0;
+  for (int e = threadIdx.x; e < cl * 2 * cr; e += 256) {
+    const int row = e / cr, c = e - row * cr;
+    bad |= !(isfinite(re[(long)row * pr + c]) && isfinite(im[(long)row * pr + c]));
+  }
+  if (__syncthreads_or(bad) && threadIdx.x == 0) flags[s] = 1;
+}
 
 }  // namespace
 
@@ -152,6 +187,115 @@ __global__ __launch_bounds__(256) void qk_pack_built_kernel(const cd* __restrict
 #include "qk_build_kernels.h"
 #undef QKB_NS
 #undef QK_BUILD_BT
+
+// The gather of the sweep path: one workgroup per state of a compress batch.  The state's sites lie compact at the start of their
+// staging slots (sized by the INPUT bonds: gaps where a bond shrank); they become one contiguous heap record with the new bond table.
+//
+// Then the sites are polished, left to right.  From 48 columns on the sweep's factorisation forms an isometry as (A V) / sigma, which
+// leaves a column sigma_max / sigma roundings from orthogonal to the others (1e-9 measured at bond 70).  With E = U^H U - 1 of site k
+// (U as [2 l][r]) one Newton-Schulz step of the polar factor, U <- U (1 - E/2), squares the defect, and site k+1 <- (1 + E/2) site k+1
+// keeps the state: (1 - E/2)(1 + E/2) = 1 - E^2/4.  A site is polished when max|E| lies above SEED_POLISH_TOL (below it E is the
+// rounding of its own product) and not above SEED_POLISH_MAX (beyond it E^2 would show in the state: such a site stays as the sweep
+// left it); a defect above SEED_POLISH_SURE is looked at again, at most three times.  The three products (U^H U, U E, E site k+1)
+// are the builder's wg_gemm_mfma through `scratch` (E: the largest bond squared, then a product or conj(U): the largest site): one
+// wavefront per tile in a fixed order, so the bits do not depend on the launch.
+//
+// The centre is the last site: its Frobenius norm is summed per thread over its strided elements in ascending order as one chain of
+// fused multiply-adds, the partial sums go through LDS and are added in ascending thread order (no atomics), the site is divided by
+// the norm and the norm written to norms[state].  A norm that is 0 or not finite is left for the host to name: the site then stays
+// as it is.
+constexpr double SEED_POLISH_TOL = 1e-13, SEED_POLISH_SURE = 1e-8, SEED_POLISH_MAX = 1e-6;
+
+__global__ __launch_bounds__(256) void qk_seed_gather_kernel(const cd* __restrict__ stage, const long long* __restrict__ stage_offs,
+                                                             const int32_t* __restrict__ dims_new, const long long* __restrict__ heap_offs, int s0,
+                                                             int n_sites, cd* __restrict__ heap, double* __restrict__ norms, cd* __restrict__ scratch,
+                                                             const long long* __restrict__ scratch_offs) {
+  using namespace qkb256;
+  __shared__ double part[256];
+  const int tid = threadIdx.x, n = n_sites;
+  const long long st = (long long)s0 + blockIdx.x;
+  const int32_t* const dn = dims_new + st * (n + 1);
+  const long long* const so = stage_offs + (long long)blockIdx.x * n;
+  cd* const rec = heap + heap_offs[st];
+  cd* site = rec;
+  long rmax2 = 1;
+  for (int k = 0; k < n; ++k) {
+    const cd* const src = stage + so[k];
+    const long cnt = 2L * dn[k] * dn[k + 1];
+    for (long e = tid; e < cnt; e += 256) site[e] = src[e];
+    site += cnt;
+    rmax2 = max(rmax2, (long)dn[k + 1] * dn[k + 1]);
+  }
+  __syncthreads();
+  cd* const E = scratch + scratch_offs[blockIdx.x];
+  cd* const D = E + rmax2;
+  site = rec;
+  for (int k = 0; k + 1 < n; ++k) {
+    const int m = 2 * dn[k], r = dn[k + 1], c2 = 2 * dn[k + 2];
+    cd* const U = site;             // [m][r]
+    cd* const N = site + (long)m * r;  // [r][c2]
+    for (int it = 0; it < 3; ++it) {
+      for (long e = tid; e < (long)m * r; e += 256) D[e] = cd{U[e].x, -U[e].y};
+      __syncthreads();
+      wg_gemm_mfma(E, r, r, m, D, 1, r, U, r, 1);  // U^H U
+      double big = 0.0;
+      for (long e = tid; e < (long)r * r; e += 256) {
+        cd g = E[e];
+        if (e / r == e % r) g.x -= 1.0, E[e] = g;
+        big = fmax(big, fmax(fabs(g.x), fabs(g.y)));
+      }
+      part[tid] = big;
+      __syncthreads();
+      if (tid == 0) {
+        double top = 0.0;
+        for (int t = 0; t < 256; ++t) top = fmax(top, part[t]);
+        part[0] = top;
+      }
+      __syncthreads();
+      big = part[0];
+      __syncthreads();
+      if (!(big > SEED_POLISH_TOL) || !(big <= SEED_POLISH_MAX)) break;  // the same for every thread
+      wg_gemm_mfma(D, m, r, r, U, r, 1, E, r, 1);
+      for (long e = tid; e < (long)m * r; e += 256) {
+        const cd u = U[e], d = D[e];
+        U[e] = cd{u.x - 0.5 * d.x, u.y - 0.5 * d.y};
+      }
+      __syncthreads();
+      wg_gemm_mfma(D, r, c2, r, E, r, 1, N, c2, 1);
+      for (long e = tid; e < (long)r * c2; e += 256) {
+        const cd v = N[e], d = D[e];
+        N[e] = cd{v.x + 0.5 * d.x, v.y + 0.5 * d.y};
+      }
+      __syncthreads();
+      if (big <= SEED_POLISH_SURE) break;  // its square is rounding: no second look
+    }
+    site += (long)m * r;
+  }
+  cd* const last = site;
+  const long cnt = 2L * dn[n - 1] * dn[n];
+  double acc = 0.0;
+  for (long e = tid; e < cnt; e += 256) {
+    const cd v = last[e];
+    acc = fma(v.x, v.x, acc);
+    acc = fma(v.y, v.y, acc);
+  }
+  part[tid] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double tot = 0.0;
+    for (int t = 0; t < 256; ++t) tot += part[t];
+    part[0] = sqrt(tot);
+  }
+  __syncthreads();
+  const double nrm = part[0];
+  if (nrm > 0.0 && isfinite(nrm))
+    for (long e = tid; e < cnt; e += 256) {
+      const cd v = last[e];
+      last[e] = cd{v.x / nrm, v.y / nrm};
+    }
+  if (tid == 0) norms[st] = nrm;
+}
+
 
 // ---- entanglement spectra of a bond (qk_bond_spectra_host, qk_local.hip) ------------------------------------------------------
 // One (state, bond k) per workgroup at a time, true bond q >= 2.  With the kept environments L_k, R_k (X[ket][bra] orientation,
@@ -1312,6 +1456,9 @@ static int set_from_snapshot(qk_ctx* c, const qk_built* b, const int32_t j, qk_m
   if (rc != QK_OK) return rc;
   m->max_pad = max_pad;
   m->dims_true.assign(bdims, bdims + (size_t)ns * stride);
+  m->centre = b->all_centre[r0];  // the states of a snapshot share their centre unless conditional gates moved it apart: then the gauge counts as unknown
+  for (int s = 1; s < ns; ++s)
+    if (b->all_centre[r0 + s] != m->centre) m->centre = -1;
   QkDevBuf d_src;
   hipError_t e = hipMemsetAsync(m->d_data.get(), 0, (size_t)m->bytes, c->stream);
   if (e == hipSuccess) e = d_src.alloc(src.size() * sizeof(long long));
@@ -1330,6 +1477,199 @@ static int set_from_snapshot(qk_ctx* c, const qk_built* b, const int32_t j, qk_m
     return qk_fail(QK_EDEVICE, "%s: %s", what, hipGetErrorString(e));
   }
   *out = m;
+  return QK_OK;
+}
+
+extern "C" int qk_mps_set_centre(const qk_mps_set* m) { return m ? m->centre : -1; }
+
+// ---- building from given states (qk_built_from_set) ---------------------------------------------------------------------------------
+// A set becomes a qk_built with ONE snapshot of zero gates; every build entry resumes from it through initial, initial_snapshot.
+// The heap holds each set state once; the per-state tables repeat by `index`, so one state may start many builds.
+//   verbatim (the set records its centre, QK_SEED_SWEEP not set): qk_unpack_set_kernel copies the true-bond corners, bit for bit;
+//   sweep (everything else): finite check, qk_compress_kernel with cap 0 and budget 0 (left-canonical, centre on the last site, bonds
+//   shrunk to their ranks), then qk_seed_gather_kernel packs the batch's staging slots into the heap, polishes the isometries
+//   and normalises the centre.
+extern "C" int qk_built_from_set(qk_ctx* c, const qk_mps_set* set, int32_t n_states, const int32_t* index, double value_of_zero, uint32_t flags, qk_built** out, double* norms,
+                                 double* fidelity) {
+  static const char* what = "qk_built_from_set";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!set) return qk_fail(QK_EINVAL, "%s: set is null", what);
+  if (!out) return qk_fail(QK_EINVAL, "%s: out is null", what);
+  *out = nullptr;
+  if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
+  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; building from a set needs an fp64 set", what);
+  if (n_states < 1) return qk_fail(QK_EINVAL, "%s: n_states must be >= 1, got %d", what, (int)n_states);
+  if (!(value_of_zero >= 0.0) || !std::isfinite(value_of_zero)) return qk_fail(QK_EINVAL, "%s: value_of_zero must be >= 0 and finite (got %g)", what, value_of_zero);
+  if (flags & ~(uint32_t)QK_SEED_SWEEP) return qk_fail(QK_EINVAL, "%s: unknown flags 0x%x (valid: QK_SEED_SWEEP)", what, (unsigned)flags);
+  const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
+  if (!index && n_states != ns) return qk_fail(QK_EINVAL, "%s: without an index n_states must be the set's %d, got %d", what, ns, (int)n_states);
+  for (int s = 0; index && s < n_states; ++s)
+    if (index[s] < 0 || index[s] >= ns) return qk_fail(QK_EINVAL, "%s: index[%d] = %d outside the set's 0..%d", what, s, (int)index[s], ns - 1);
+  const bool sweep = (flags & QK_SEED_SWEEP) || set->centre < 0;
+  const int32_t* tru = set->dims_true.data();
+  int qall = 1;
+  for (size_t e = 0; e < (size_t)ns * n1; ++e) qall = std::max(qall, (int)tru[e]);
+  if (sweep && qall > SPEC_QMAX) return qk_fail(QK_EINVAL, "%s: a bond of %d is beyond the %d the factorisation's LDS bookkeeping holds", what, qall, SPEC_QMAX);
+  QkRangeGuard range_("qk:seed");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  std::vector<long long> need(ns, 0);  // complex elements of a state at its input bonds
+  long long heap_elems = 0;
+  for (int s = 0; s < ns; ++s) {
+    for (int k = 0; k < n; ++k) need[s] += 2ll * tru[(size_t)s * n1 + k] * tru[(size_t)s * n1 + k + 1];
+    heap_elems += need[s];
+  }
+  // what the set's states become: bond tables, offsets into the heap, fidelity, centre, norm
+  std::vector<int32_t> sdims(set->dims_true), scentre(ns, sweep ? n - 1 : set->centre);
+  std::vector<long long> soffs(ns, 0);
+  std::vector<double> sfid(ns, 1.0), snorm(ns, 1.0);
+  QkDevBuf heap;
+  HIP_TRY_AS(what, heap.alloc((size_t)heap_elems * sizeof(cd)));  // no bond grows: the input sizes bound the heap
+  long long top = 0;
+  float ms = 0;
+  int launch_grid = 0;
+  if (!sweep) {
+    std::vector<long long> dst((size_t)ns * n);
+    for (int s = 0; s < ns; ++s) {
+      soffs[s] = top;
+      for (int k = 0; k < n; ++k) {
+        dst[(size_t)s * n + k] = top;
+        top += 2ll * tru[(size_t)s * n1 + k] * tru[(size_t)s * n1 + k + 1];
+      }
+    }
+    QkDevBuf d_dst;
+    HIP_TRY_AS(what, d_dst.alloc(dst.size() * sizeof(long long)));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_dst.get(), dst.data(), dst.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    qk_unpack_set_kernel<<<dim3((unsigned)(ns * n)), dim3(256), 0, c->stream>>>(set->d_data.get<double>(), set->d_offs.get<long long>(), d_dst.get<long long>(), set->d_true.get<int32_t>(),
+                                                                              set->d_dims.get<int32_t>(), n, heap.get<cd>());
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  } else {
+    // 1. the finite check: one flag per state, no factorisation is launched on a state that holds a NaN or an infinity
+    {
+      QkDevBuf d_flags;
+      std::vector<int32_t> flg(ns, 0);
+      HIP_TRY_AS(what, d_flags.alloc((size_t)ns * sizeof(int32_t)));
+      HIP_TRY_AS(what, hipMemsetAsync(d_flags.get(), 0, (size_t)ns * sizeof(int32_t), c->stream));
+      qk_seed_finite_kernel<<<dim3((unsigned)(ns * n)), dim3(256), 0, c->stream>>>(set->d_data.get<double>(), set->d_offs.get<long long>(), set->d_true.get<int32_t>(),
+                                                                                 set->d_dims.get<int32_t>(), n, d_flags.get<int32_t>());
+      HIP_TRY_AS(what, hipGetLastError());
+      HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+      HIP_TRY_AS(what, hipMemcpy(flg.data(), d_flags.get(), (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost));
+      for (int s = 0; s < ns; ++s)
+        if (flg[s]) return qk_fail(QK_EDEVICE, "%s: state %d holds an element that is not finite", what, s);
+    }
+    // 2. the canonical sweep, in the batches of qk_mps_set_compress (the quarter-of-free-memory rule), 3. the gather of each batch
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY_AS(what, hipMemGetInfo(&free_b, &total_b));
+    const long long budget = (long long)(free_b / 4);
+    std::vector<int> bstart{0};
+    for (long long acc = 0, s = 0; s < ns; ++s) {
+      const long long w = need[s] * (long long)sizeof(cd);
+      if (acc > 0 && acc + w > budget / 2) bstart.push_back((int)s), acc = 0;
+      acc += w;
+    }
+    bstart.push_back(ns);
+    QkDevBuf d_new, d_fid, d_disc, d_err, d_so, d_ho, d_norm;
+    const size_t n_disc = std::max<size_t>(1, (size_t)ns * (n - 1));
+    HIP_TRY_AS(what, d_new.alloc((size_t)ns * n1 * sizeof(int32_t)));
+    HIP_TRY_AS(what, d_fid.alloc((size_t)ns * sizeof(double)));
+    HIP_TRY_AS(what, d_disc.alloc(n_disc * sizeof(double)));
+    HIP_TRY_AS(what, d_err.alloc(32 * sizeof(int)));
+    HIP_TRY_AS(what, d_so.alloc((size_t)ns * n * sizeof(long long)));
+    HIP_TRY_AS(what, d_ho.alloc((size_t)ns * sizeof(long long)));
+    HIP_TRY_AS(what, d_norm.alloc((size_t)ns * sizeof(double)));
+    std::vector<long long> so((size_t)ns * n);
+    HIP_TRY_AS(what, hipEventRecord(c->ev0, c->stream));
+    for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+      const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+      long long stage_elems = 0;
+      int qmax = 1;
+      for (int s = s0; s < s0 + nb; ++s)
+        for (int k = 0; k < n; ++k) {
+          so[(size_t)s * n + k] = stage_elems;
+          stage_elems += 2ll * tru[(size_t)s * n1 + k] * tru[(size_t)s * n1 + k + 1];
+          qmax = std::max(qmax, (int)tru[(size_t)s * n1 + k]);
+        }
+      const size_t per_wg = qk_compress_work_bytes(qmax);
+      const long long room = budget - stage_elems * (long long)sizeof(cd);
+      const int grid = (int)std::max<long long>(1, std::min<long long>({(long long)nb, 2ll * c->num_cus, room / (long long)per_wg}));
+      launch_grid = std::max(launch_grid, grid);
+      QkDevBuf stage, work;
+      HIP_TRY_AS(what, stage.alloc((size_t)stage_elems * sizeof(cd)));
+      HIP_TRY_AS(what, work.alloc((size_t)grid * per_wg));
+      HIP_TRY_AS(what, hipMemcpyAsync(d_so.get<long long>() + (size_t)s0 * n, so.data() + (size_t)s0 * n, (size_t)nb * n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+      QkCompressArgs a{};
+      a.planes = set->d_data.get<double>(), a.pad = set->d_dims.get<int32_t>(), a.tru = set->d_true.get<int32_t>(), a.offs = set->d_offs.get<int64_t>();
+      a.s0 = s0, a.n_batch = nb, a.n_sites = n;
+      a.stage = stage.get<double>(), a.stage_offs = d_so.get<long long>() + (size_t)s0 * n;
+      a.dims_new = d_new.get<int32_t>(), a.fidelity = d_fid.get<double>(), a.discarded = d_disc.get<double>();
+      a.cap = 0, a.budget = 0.0, a.zero = value_of_zero;
+      a.work = work.get<char>(), a.work_bytes = (long long)per_wg, a.qmax = qmax, a.error = d_err.get<int>();
+      if (const int rc = qk_compress_launch(c, a, grid, what)) return rc;  // synchronises; a state of norm 0 is named there
+      HIP_TRY_AS(what, hipMemcpy(sdims.data() + (size_t)s0 * n1, d_new.get<int32_t>() + (size_t)s0 * n1, (size_t)nb * n1 * sizeof(int32_t), hipMemcpyDeviceToHost));
+      for (int s = s0; s < s0 + nb; ++s) {
+        for (int k = 0; k <= n; ++k) {
+          const int32_t x = sdims[(size_t)s * n1 + k];
+          if (x < 1 || x > tru[(size_t)s * n1 + k]) return qk_fail(QK_EDEVICE, "%s: state %d came back with bond %d of %d (was %d)", what, s, k, (int)x, (int)tru[(size_t)s * n1 + k]);
+        }
+        soffs[s] = top;
+        for (int k = 0; k < n; ++k) top += 2ll * sdims[(size_t)s * n1 + k] * sdims[(size_t)s * n1 + k + 1];
+      }
+      // the polish's scratch of a state: E (the largest bond squared) and one product (the largest site), at the new bonds
+      std::vector<long long> po(nb);
+      long long polish_elems = 0;
+      for (int s = s0; s < s0 + nb; ++s) {
+        long long r2 = 1, site = 1;
+        for (int k = 0; k < n; ++k) {
+          const long long l = sdims[(size_t)s * n1 + k], r = sdims[(size_t)s * n1 + k + 1];
+          r2 = std::max(r2, r * r), site = std::max(site, 2 * l * r);
+        }
+        po[s - s0] = polish_elems;
+        polish_elems += r2 + site;
+      }
+      QkDevBuf polish, d_po;
+      HIP_TRY_AS(what, polish.alloc((size_t)polish_elems * sizeof(cd)));
+      HIP_TRY_AS(what, d_po.alloc((size_t)nb * sizeof(long long)));
+      HIP_TRY_AS(what, hipMemcpyAsync(d_po.get(), po.data(), (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY_AS(what, hipMemcpyAsync(d_ho.get<long long>() + s0, soffs.data() + s0, (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+      qk_seed_gather_kernel<<<dim3((unsigned)nb), dim3(256), 0, c->stream>>>(stage.get<cd>(), d_so.get<long long>() + (size_t)s0 * n, d_new.get<int32_t>(), d_ho.get<long long>(), s0, n,
+                                                                           heap.get<cd>(), d_norm.get<double>(), polish.get<cd>(), d_po.get<long long>());
+      HIP_TRY_AS(what, hipGetLastError());
+      HIP_TRY_AS(what, hipStreamSynchronize(c->stream));  // the staging buffer and the workspaces go before the next batch
+    }
+    HIP_TRY_AS(what, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+    HIP_TRY_AS(what, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    HIP_TRY_AS(what, hipMemcpy(sfid.data(), d_fid.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY_AS(what, hipMemcpy(snorm.data(), d_norm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+    for (int s = 0; s < ns; ++s)
+      if (!(snorm[s] > 0.0) || !std::isfinite(snorm[s])) return qk_fail(QK_EDEVICE, "%s: state %d has a norm of %g after the sweep: nothing to build from", what, s, snorm[s]);
+  }
+  std::unique_ptr<qk_built> b(new (std::nothrow) qk_built);
+  if (!b) return qk_fail(QK_ENOMEM, "%s: out of memory", what);
+  b->ctx = c, b->n_states = n_states, b->n_qubits = n;
+  b->checkpoints.assign(1, 0);
+  b->all_dims.resize((size_t)n_states * n1);
+  b->all_fidelity.resize(n_states);
+  b->all_offsets.resize(n_states);
+  b->all_centre.resize(n_states);
+  b->all_logw.assign(n_states, 0.0);
+  for (int s = 0; s < n_states; ++s) {
+    const int src = index ? index[s] : s;
+    std::copy(sdims.begin() + (size_t)src * n1, sdims.begin() + (size_t)(src + 1) * n1, b->all_dims.begin() + (size_t)s * n1);
+    b->all_fidelity[s] = sfid[src], b->all_offsets[s] = soffs[src], b->all_centre[s] = scentre[src];
+  }
+  b->dims = b->all_dims, b->fidelity = b->all_fidelity, b->offsets = b->all_offsets;
+  b->secs.assign(n_states, 0.0);
+  b->heap = std::move(heap);
+  b->total = top;
+  b->kernel_ms = ms;
+  if (sweep) b->grid = launch_grid, b->threads = 256, b->slots = 2 * c->num_cus;
+  if (norms) std::copy(snorm.begin(), snorm.end(), norms);
+  if (fidelity) std::copy(sfid.begin(), sfid.end(), fidelity);
+  *out = b.release();
   return QK_OK;
 }
 

@@ -200,6 +200,17 @@ void gemm_rm(int m, int n, int k, const cd* A, const cd* B, cd* C) {
   p_zgemm("N", "N", &n, &m, &k, &one, B, &n, A, &k, &zero, C, &n);
 }
 
+// The state a run starts from instead of |0...0> (qkb_simulate_initial): already canonical with the centre on `centre`, validated by
+// the entry.  It reaches simulate_impl through t_initial, set for the duration of one call on the calling thread: the entries between
+// the two keep their signatures.
+struct Initial {
+  const int32_t* dims = nullptr;  // [n_qubits + 1]
+  const cd* tensors = nullptr;    // the sites [l][2][r] row-major, back to back
+  int centre = 0;
+  double fidelity = 1.0, logw = 0.0;
+};
+thread_local const Initial* t_initial = nullptr;
+
 struct Tensor {  // [l][2][r], row-major
   int l = 1, r = 1;
   std::vector<cd> v;
@@ -406,6 +417,57 @@ int qkb_simulate_conditions(int32_t n_qubits, int32_t n_ops, const int8_t* op, c
   ch.logw_out = logw_out, ch.branches_out = branches_out, ch.margin_out = margin_out;
   return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, ch, dims_out, tensors_out, n_complex_out, fidelity_out);
 }
+// qkb_simulate_conditions from a given state: init_dims [n_qubits + 1] and init_tensors (the sites [l][2][r] complex128 row-major, back to
+// back) replace |0...0>; the state is taken as it stands -- canonical with its orthogonality centre on init_centre -- and the run begins
+// with init_fidelity and init_logw.  -8 before a gate is applied for a bond table that does not chain (dims[0] != 1, dims[n] != 1, an
+// entry that is not positive), a centre outside the register, or an entry (tensor, fidelity, log-weight) that is not finite.  With
+// init_dims null the call IS qkb_simulate_conditions.
+int qkb_simulate_initial(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
+                         int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
+                         const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate,
+                         int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, const int32_t* init_dims,
+                         const double* init_tensors, int32_t init_centre, double init_fidelity, double init_logw, int32_t* dims_out, double** tensors_out,
+                         int64_t* n_complex_out, double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out) {
+  Initial init;
+  if (init_dims) {
+    if (!init_tensors || n_qubits < 1) {
+      g_err = "an initial state needs init_dims and init_tensors";
+      return -8;
+    }
+    if (init_dims[0] != 1 || init_dims[n_qubits] != 1) {
+      g_err = "the initial state's boundary bonds must be 1";
+      return -8;
+    }
+    size_t total = 0;
+    for (int k = 0; k <= n_qubits; ++k) {
+      if (init_dims[k] <= 0) {
+        g_err = "the initial state's bond " + std::to_string(k) + " is " + std::to_string((int)init_dims[k]) + ": bonds must be positive";
+        return -8;
+      }
+      if (k < n_qubits) total += (size_t)init_dims[k] * 2 * (size_t)std::max(init_dims[k + 1], 0);
+    }
+    if (init_centre < 0 || init_centre >= n_qubits) {
+      g_err = "the initial state's centre " + std::to_string((int)init_centre) + " lies outside the register of " + std::to_string((int)n_qubits);
+      return -8;
+    }
+    for (size_t e = 0; e < 2 * total; ++e)
+      if (!std::isfinite(init_tensors[e])) {
+        g_err = "the initial state has an entry that is not finite";
+        return -8;
+      }
+    if (!std::isfinite(init_fidelity) || !std::isfinite(init_logw)) {
+      g_err = "the initial state's fidelity or log-weight is not finite";
+      return -8;
+    }
+    init.dims = init_dims, init.tensors = reinterpret_cast<const cd*>(init_tensors), init.centre = init_centre, init.fidelity = init_fidelity, init.logw = init_logw;
+    t_initial = &init;
+  }
+  const int rc = qkb_simulate_conditions(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, n_channels, kraus, n_kraus, channel, branch, seed,
+                                         state_index, trajectory, first_gate, n_channels2, kraus2, n_kraus2, cond_gate, cond_mask, dims_out, tensors_out, n_complex_out, fidelity_out,
+                                         logw_out, branches_out, margin_out);
+  t_initial = nullptr;
+  return rc;
+}
 }  // extern "C"
 
 static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
@@ -444,11 +506,22 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
   std::vector<int> taken(ch.cond_gate ? n_ops : 0, -1);  // the branch every channel gate of this state took (-2: skipped), by position
   std::vector<Tensor> A(n);
   for (auto& t : A) t.v = {cd(1, 0), cd(0, 0)};
+  const Initial* const init = t_initial;
   std::vector<int> two_q_pos;
   for (int i = 0; i < n_ops; ++i)
     if (is_two_qubit(op[i])) two_q_pos.push_back(q0[i]);
   double fidelity = 1.0;
   int centre = 0;  // sites < centre are left-orthonormal, sites > centre right-orthonormal
+  if (init) {  // the run goes on from a given state: its sites, centre, fidelity and log-weight
+    const cd* src = init->tensors;
+    for (int k = 0; k < n; ++k) {
+      A[k].l = init->dims[k], A[k].r = init->dims[k + 1];
+      const size_t cnt = (size_t)A[k].l * 2 * A[k].r;
+      A[k].v.assign(src, src + cnt);
+      src += cnt;
+    }
+    centre = init->centre, fidelity = init->fidelity, logw = init->logw;
+  }
   size_t g2 = 0;
   std::vector<cd> Q, R, work, cm, theta, U, VT, tmp;
   std::vector<double> S, rwork;

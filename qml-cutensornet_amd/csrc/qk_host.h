@@ -70,6 +70,7 @@ struct qk_mps_set {
   QkDevBuf d_true;  // int32_t: true bonds   [n_states][n_sites+1]
   QkDevBuf d_offs;  // int64_t: re-plane offsets (doubles) [n_states][n_sites]
   std::vector<int32_t> dims_true;
+  int centre = -1;  // provenance: the orthogonality centre every state has (a snapshot of the device builder), -1: gauge unknown (every other origin)
   int64_t bytes = 0;
   // edge blocks of the site-fused sweep (made on first use for the plan's edge_k; qk_device.h: SweepArgs.edge_k)
   QkDevBuf d_edge;       // double: interleaved complex: per state the left block [2^k][pad(chi_k)], then the right block [2^k][pad(chi_{n-k})]

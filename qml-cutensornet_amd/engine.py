@@ -139,6 +139,8 @@ _SIGNATURES = [
     ("qk_built_info_at", C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     ("qk_built_download_at", C.c_int, [_P, C.c_int32, _P]),
     ("qk_mps_set_from_built_at", C.c_int, [_P, _P, C.c_int32, C.POINTER(_P)]),
+    ("qk_built_from_set", C.c_int, [_P, _P, C.c_int32, _P, C.c_double, C.c_uint32, C.POINTER(_P), _P, _P]),
+    ("qk_mps_set_centre", C.c_int, [_P]),
     ("qk_debug_jacobi", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("qk_debug_jacobi_precond", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("qk_range_push", C.c_int, [C.c_char_p]),
@@ -1378,6 +1380,12 @@ class MpsSet:
         """Bits of a real of the device image: 64 (complex128) or 32 (complex64)."""
         return int(lib().qk_mps_set_precision(self._h))
 
+    @property
+    def centre(self) -> int:
+        """The orthogonality centre the set records: the common centre of a snapshot of the device builder (``BuiltScan.set``,
+        ``build_mps_set``, ``build_share``), -1 where the gauge is unknown -- an uploaded, gathered, converted or compressed set."""
+        return int(lib().qk_mps_set_centre(self._h))
+
     def to_f32(self) -> "MpsSet":
         """A complex64 copy of this set on the same device; sweeps over fp32 sets run the
         fp32-MFMA kernel.  Both sets of a Gram must have the same precision."""
@@ -1575,6 +1583,7 @@ class BuiltScan:
         self.kernel_ms = ms.value
         self.launch = _built_launch(handle)  # {"grid", "threads", "slots"} of the scan's one launch
         self.first_gate = 0  # position of the program's first gate in the uninterrupted circuit (build_mps_scan sets it)
+        self._norms = None  # Context.seed: the norm every state came with
         ctx._adopt(self)  # closed with the context: the heap lives on its device
 
     @property
@@ -1611,7 +1620,8 @@ class BuiltScan:
         program (n_states, n_channel_gates), whichever snapshot is asked, "grid", "threads", "slots": the scan's launch}."""
         k, dims, fid, _, centre, total = self._info(j)
         logw, branches = _built_trajectories(self._h, self.n_states, k)
-        return {"dims": dims, "fidelity": fid, "centre": centre, "heap_bytes": 16 * total, "logw": logw, "branches": branches, **self.launch}
+        seed = {} if self._norms is None else {"norm": self._norms.copy()}  # a seed (``Context.seed``): the norms the states came with
+        return {"dims": dims, "fidelity": fid, "centre": centre, "heap_bytes": 16 * total, "logw": logw, "branches": branches, **seed, **self.launch}
 
     def set(self, j) -> "MpsSet":
         """Snapshot j as a device-resident set (packed on the device: nothing is downloaded); feeds ``gram``, ``local_paulis``,
@@ -1733,8 +1743,87 @@ class Context:
         self.last_precond_ms = [float(np.uint32(t)) / 1e5 for t in st[1:]]  # all, sort + copy, Gram-Schmidt, sweeps, V and W = A V
         return a, v, sig, ord_, int(st[0]), self.last_precond_ms[0]
 
+    def seed(self, xs, index=None, value_of_zero: float = 1e-16, sweep: bool = False) -> BuiltScan:
+        """Given states as the starting point of a build: a ``BuiltScan`` with ONE snapshot of zero gates (``.checkpoints == [0]``)
+        that every build call resumes from through ``initial=(seed, 0)``.  ``xs`` is a device-resident ``MpsSet`` of this context
+        (fp64) or a ``list[MPS]`` (uploaded for the call).  ``index[s]`` names the state of ``xs`` that build state s starts from
+        (``None``: one build state per state of ``xs``): the heap holds each state once, so one state may start many circuits
+        (broadcast) or T trajectories.
+
+        A set that records its centre (``MpsSet.centre >= 0``: a snapshot of the device builder) is taken verbatim, bit for bit,
+        with fidelity 1 -- unless ``sweep`` asks for the other path.  Every other set may be in any gauge and of any norm (bonds up
+        to 512): after a finite check it goes through the canonical sweep of ``compress(xs, max_discard=0)`` (a bond whose rank is
+        below its dimension shrinks to its rank), the centre ends on the last site and is divided by its norm.  ``info(0)`` carries
+        ``norm`` (per build state: the norm the state came with; 1 on the verbatim path), ``fidelity``, ``centre`` and ``dims``.
+        ``QkError`` naming the state for a state of norm 0 or with an entry that is not finite.  Close it, or use ``with``."""
+        from .mps import MPS
+
+        own = None
+        if isinstance(xs, MPS):
+            xs = [xs]
+        if not isinstance(xs, MpsSet):
+            own = xs = self.upload(list(xs))
+        try:
+            ns_set, n = xs.dims.shape[0], xs.dims.shape[1] - 1
+            idx = None
+            if index is not None:
+                idx = np.asarray(index)
+                if idx.ndim != 1 or idx.dtype.kind not in "iu" or idx.shape[0] < 1:
+                    raise ValueError(f"index must be a non-empty 1-D array of ints, got {index!r}")
+                idx = np.ascontiguousarray(idx, dtype=np.int32)
+            n_states = ns_set if idx is None else int(idx.shape[0])
+            norms, fid = np.zeros(ns_set, dtype=np.float64), np.zeros(ns_set, dtype=np.float64)
+            h = _P()
+            _check(lib().qk_built_from_set(self._h, xs.handle, n_states, None if idx is None else idx.ctypes.data, float(value_of_zero), 1 if sweep else 0, C.byref(h),
+                                           norms.ctypes.data, fid.ctypes.data), "qk_built_from_set")
+        finally:
+            if own is not None:
+                own.close()
+        scan = BuiltScan(self, h, n_states, n)
+        scan._norms = norms if idx is None else norms[idx]
+        return scan
+
+    def _resume(self, what, initial, ns, initial_index, value_of_zero):
+        """What ``initial=`` of a build call means: ``(seed to close or None, handle, snapshot, first gate)``.  ``(scan, j)`` is a
+        snapshot of an earlier scan; an ``MpsSet``, a ``list[MPS]`` or one ``MPS`` (for all ``ns`` states) is seeded for the call,
+        with ``initial_index`` as the ``index`` of ``seed``."""
+        from .mps import MPS
+
+        if initial is None:
+            if initial_index is not None:
+                raise ValueError(f"{what}: initial_index goes with initial states")
+            return None, None, 0, 0
+        if isinstance(initial, tuple) and len(initial) == 2 and isinstance(initial[0], BuiltScan):
+            if initial_index is not None:
+                raise ValueError(f"{what}: initial_index goes with given states, not with a snapshot (seed them with Context.seed(xs, index))")
+            scan, j = initial
+            k = scan._index(j)
+            return None, scan.handle, k, scan.first_gate + scan.checkpoints[k]
+        if isinstance(initial, MPS):
+            if initial_index is not None:
+                raise ValueError(f"{what}: one initial MPS starts every state; initial_index goes with a set or a list")
+            initial, initial_index = [initial], np.zeros(ns, dtype=np.int32)
+        if not isinstance(initial, MpsSet) and not (isinstance(initial, (list, tuple)) and len(initial) and all(isinstance(m, MPS) for m in initial)):
+            raise ValueError(f"{what}: initial must be (BuiltScan, snapshot index), an MpsSet, a list of MPS or one MPS, got {initial!r}")
+        seed = self.seed(initial, initial_index, value_of_zero)
+        if seed.n_states != ns:
+            seed.close()
+            raise ValueError(f"{what}: the initial states start {seed.n_states} builds, the call has {ns} circuits")
+        return seed, seed.handle, 0, 0
+
+    def _build_from(self, what, circuits, seed, state_index, trajectory, truncation_fidelity, value_of_zero, max_bond, flags, initial, initial_index):
+        """One launch of a one-snapshot build call, from |0...0> or from ``initial``: ``(built handle, gate program)``."""
+        own, src, src_j, base = self._resume(what, initial, len(circuits), initial_index, value_of_zero)
+        try:
+            prog = _GateProgram(what, circuits, seed, state_index, trajectory, base)
+            cps = None if src is None else np.array([int(prog.op.shape[0])], dtype=np.int32)  # a resumed build goes through the scan entries
+            return prog.build(self, truncation_fidelity, value_of_zero, max_bond, flags, cps, src, src_j), prog
+        finally:
+            if own is not None:
+                own.close()
+
     def build_mps(self, circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, partial: bool = False, truncate: bool = False,
-                  seed=0, state_index=None, trajectory=None):
+                  seed=0, state_index=None, trajectory=None, initial=None, initial_index=None):
         """Device MPS builder (/root/reference/gpu_backend/kernel_state_ansatz.py:221, 263): the MPS of every
         bound circuit of the list (``ansatz.BoundCircuit``; they must share one gate structure, as the data points of one
         ansatz do) in ONE launch.  Returns (list[MPS], info) with info = {"kernel_ms", "total_complex", "dropped", and the launch:
@@ -1745,15 +1834,17 @@ class Context:
         Circuits with Kraus channels (op code 10) are run as quantum trajectories: state s draws its branches from ``seed``,
         ``state_index[s]`` and ``trajectory[s]`` (an int for all, or one per state; ``None``: 0 .. n-1 and 0; see
         ``channel_uniform``), so its result does not depend on what else the call builds.  info["logw"] (n,) and info["branches"]
-        (n, n_channel_gates) record the log-probability and the branches; the states carry them too."""
+        (n, n_channel_gates) record the log-probability and the branches; the states carry them too.
+
+        ``initial`` / ``initial_index``: the circuits are applied to given states instead of |0...0>, as in ``build_mps_scan``."""
         from .mps import MPS
 
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_mps needs at least one circuit")
-        prog = _GateProgram("build_mps", circuits, seed, state_index, trajectory)
+        h, prog = self._build_from("build_mps", circuits, seed, state_index, trajectory, truncation_fidelity, value_of_zero, max_bond,
+                                   (1 if partial else 0) | (2 if truncate else 0), initial, initial_index)
         n, ns = prog.n, prog.ns
-        h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0))
         try:
             dims = np.zeros((ns, n + 1), dtype=np.int32)
             fid = np.zeros(ns, dtype=np.float64)
@@ -1781,16 +1872,16 @@ class Context:
         return states, {"kernel_ms": ms.value, "total_complex": int(total.value), "dropped": dropped, "logw": logw, "branches": branches, **launch}
 
     def build_mps_set(self, circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, truncate: bool = False, seed=0,
-                      state_index=None, trajectory=None):
+                      state_index=None, trajectory=None, initial=None, initial_index=None):
         """Like ``build_mps`` but the states never leave the device: returns (MpsSet, info) with info = {"kernel_ms", "dims",
         "fidelity", "logw", "branches", "grid", "threads", "slots"}; the set feeds ``gram`` / ``gram_values`` directly."""
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_mps_set needs at least one circuit")
-        prog = _GateProgram("build_mps_set", circuits, seed, state_index, trajectory)
+        h, prog = self._build_from("build_mps_set", circuits, seed, state_index, trajectory, truncation_fidelity, value_of_zero, max_bond, 2 if truncate else 0, initial,
+                                   initial_index)
         n, ns = prog.n, prog.ns
         hs = _P()
-        h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, 2 if truncate else 0)
         try:
             dims = np.zeros((ns, n + 1), dtype=np.int32)
             fid = np.zeros(ns, dtype=np.float64)
@@ -1804,7 +1895,7 @@ class Context:
         return MpsSet(self, hs, dims), {"kernel_ms": ms.value, "dims": dims, "fidelity": fid, "logw": logw, "branches": branches, **launch}
 
     def build_mps_scan(self, circuits, checkpoints, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, truncate: bool = False,
-                       initial=None, partial: bool = False, seed=0, state_index=None, trajectory=None, first_gate=None) -> BuiltScan:
+                       initial=None, partial: bool = False, seed=0, state_index=None, trajectory=None, first_gate=None, initial_index=None) -> BuiltScan:
         """``build_mps_set`` that also keeps every state after ``checkpoints[j]`` gates (gate counts: strictly increasing, in
         1 .. n_gates, the last one n_gates; ``KernelStateAnsatz.layer_ends()`` for a scan over depth): ONE launch, the snapshots are
         copies and the run does the arithmetic of a run without them, so the last snapshot is what ``build_mps`` returns.  Returns a
@@ -1814,6 +1905,8 @@ class Context:
         ``initial=(scan, j)`` resumes: the states start as snapshot j of an earlier scan of this context (same number of states and
         qubits, no bond above ``max_bond``) and ``circuits`` are the gates that follow it -- ``c.sliced(scan.checkpoints[j],
         c.n_gates)`` continues the same circuits, gate for gate the arithmetic of the uninterrupted run.  ``scan`` is left untouched.
+        ``initial`` may also be given states -- an ``MpsSet``, a ``list[MPS]`` (one per circuit, or picked by ``initial_index`` as
+        the ``index`` of ``Context.seed``) or one ``MPS`` for all circuits: they are seeded by ``Context.seed`` for the call.
         ``ValueError`` for bad checkpoints; ``partial`` goes with one checkpoint and no ``initial`` only (``QkError`` otherwise).
 
         ``seed``, ``state_index`` and ``trajectory`` name the trajectories of circuits with Kraus channels as in ``build_mps``.
@@ -1827,16 +1920,14 @@ class Context:
         if not circuits:
             raise QkError("build_mps_scan needs at least one circuit")
         cps = np.ascontiguousarray(check_checkpoints(checkpoints, int(np.shape(circuits[0].op)[0])), dtype=np.int32)
-        src, src_j, base = None, 0, 0
-        if initial is not None:
-            scan, j = initial
-            if not isinstance(scan, BuiltScan):
-                raise ValueError(f"initial must be (BuiltScan, snapshot index), got {initial!r}")
-            src, src_j = scan.handle, scan._index(j)
-            base = scan.first_gate + scan.checkpoints[src_j]
-        prog = _GateProgram("build_mps_scan", circuits, seed, state_index, trajectory, base if first_gate is None else first_gate)
-        n, ns = prog.n, prog.ns
-        h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0), cps, src, src_j)
+        own, src, src_j, base = self._resume("build_mps_scan", initial, len(circuits), initial_index, value_of_zero)
+        try:
+            prog = _GateProgram("build_mps_scan", circuits, seed, state_index, trajectory, base if first_gate is None else first_gate)
+            n, ns = prog.n, prog.ns
+            h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0), cps, src, src_j)
+        finally:
+            if own is not None:
+                own.close()
         scan = BuiltScan(self, h, ns, n, np.flatnonzero((prog.op == 10) | (prog.op == 11)) if prog.n_channels or prog.n_channels2 else None)
         scan.first_gate = prog.first_gate
         return scan
@@ -1852,7 +1943,7 @@ class Context:
         return MpsSet(self, h, dims)
 
     def build_share(self, circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int = 256, partial: bool = False, truncate: bool = False,
-                    seed=0, state_index=None, trajectory=None):
+                    seed=0, state_index=None, trajectory=None, initial=None, initial_index=None):
         """Device builder for one rank's share of a data set, the states staying on the device whenever possible: returns
         (MpsSet, None, info) when every state fitted ``max_bond`` (packed on the device by ``qk_mps_set_from_built``: nothing
         is downloaded), else (None, list[MPS | None], info) with the dropped states ``None`` (``partial`` only), to be
@@ -1863,9 +1954,9 @@ class Context:
         circuits = list(circuits)
         if not circuits:
             raise QkError("build_share needs at least one circuit")
-        prog = _GateProgram("build_share", circuits, seed, state_index, trajectory)
+        h, prog = self._build_from("build_share", circuits, seed, state_index, trajectory, truncation_fidelity, value_of_zero, max_bond,
+                                   (1 if partial else 0) | (2 if truncate else 0), initial, initial_index)
         n, ns = prog.n, prog.ns
-        h = prog.build(self, truncation_fidelity, value_of_zero, max_bond, (1 if partial else 0) | (2 if truncate else 0))
         try:
             dims = np.zeros((ns, n + 1), dtype=np.int32)
             fid = np.zeros(ns, dtype=np.float64)

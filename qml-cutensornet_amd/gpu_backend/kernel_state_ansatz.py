@@ -174,12 +174,41 @@ def _expect_small_bonds(ansatz, circuits):
     return max(_entangling_weight(c) for c in circuits) <= 10.0
 
 
-def _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, device_id=0, host_workers=1, want_set=True):
+def _initial_states(initial_states, n_points, ansatz, name="initial_states"):
+    """``initial_states`` of a driver, checked: ``None``, one ``MPS`` for every data point, or a list of ``MPS``, one per point, each
+    with as many sites as the ansatz has qubits (an ansatz that does not say is checked by the builder)."""
+    from qml_cutensornet_amd.mps import MPS
+
+    if initial_states is None:
+        return None
+    n_qubits = getattr(ansatz, "num_qubits", None)
+    if isinstance(initial_states, MPS):
+        states = [initial_states]
+    else:
+        states = list(initial_states)
+        if len(states) != n_points or not all(isinstance(m, MPS) for m in states):
+            raise ValueError(f"{name} must be one MPS, or a list of MPS with one per data point ({n_points})")
+        initial_states = states
+    if n_qubits is not None and any(len(m) != int(n_qubits) for m in states):
+        raise ValueError(f"{name}: every initial state needs {n_qubits} sites, as many as the ansatz has qubits")
+    return initial_states
+
+
+def _share_of(initial, lo, hi):
+    """The initial states of the points lo .. hi-1: the one state for all, or the slice of the list."""
+    return initial if initial is None or not isinstance(initial, list) else initial[lo:hi]
+
+
+def _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, device_id=0, host_workers=1, want_set=True, initial=None):
     """This rank's slice of the data set (contiguous chunks of ceil(N/P), as ref :154,:171-174) -> (first index, the
     states as ONE packed device set -- ``None`` for an empty share --, seconds per state, fidelities).  ``want_set=False``
     (host-only callers: the CPU tests) keeps the host builder's list of MPS instead of uploading it.
     QK_MAX_BOND (environment): a bond cap for either builder -- the ``chi`` pytket-cutensornet's ``Config`` would take at
-    ref :141-144 (the reference leaves it unset: the default is no cap)."""
+    ref :141-144 (the reference leaves it unset: the default is no cap).
+
+    ``initial`` (``_initial_states``: one MPS, or one per point of ``points``) starts the circuits from given states instead of
+    |0...0>.  Then "auto" and "hybrid" build the whole share on the device, and a share the device gives up on is rebuilt on the
+    host as a whole (the rule of the noisy drivers: no per-state hand-over); "host" is ``simulate(..., initial=)``."""
     import os
 
     per_rank = -(-len(points) // n_procs)
@@ -191,7 +220,21 @@ def _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, dev
     # an ansatz may return a BoundCircuit or a reference-style gate list (name, qubits, params)
     circuits = [as_bound_circuit(ansatz.circuit_for_data(points[k, :]), ansatz) for k in range(lo, hi)] if hi > lo else []
     reject_channels(circuits, "a driver without trajectories")
-    if which == "auto":
+    inits = _share_of(initial, lo, hi)
+    if inits is not None and hi > lo:
+        if which != "host":
+            t0 = time.perf_counter()
+            cap = chi or int(os.environ.get("QK_BUILDER_MAX_BOND", "320"))
+            try:
+                dset, _, binfo = _engine.default_context(device_id).build_share(circuits, fidelity, max_bond=cap, truncate=chi is not None, initial=inits)
+                _say(is_root, f"{label}: 100%")
+                return lo, dset, [(time.perf_counter() - t0) / (hi - lo)] * (hi - lo), [float(f) for f in binfo["fidelity"]]
+            except _engine.QkError as exc:
+                if forced == "device":
+                    raise
+                _say(is_root, f"{label}: device builder gave up ({exc}); building on the host")
+        which = "host"
+    elif which == "auto":
         try:
             which = _auto_builder(circuits, host_workers)
         except (AttributeError, TypeError, ValueError):  # an ansatz without a compiled gate program: the host loop handles it
@@ -248,7 +291,7 @@ def _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, dev
         if (done[0] - 1) % tick == 0:
             _say(is_root, f"{label}: {10 * ((done[0] - 1) // tick)}%")
 
-    states, secs = simulate_many(circuits, fidelity, workers=host_workers, progress=progress, max_bond=chi)
+    states, secs = simulate_many(circuits, fidelity, workers=host_workers, progress=progress, max_bond=chi, initial=inits)
     if not want_set:
         return lo, states, secs, [m.fidelity for m in states]
     if not states:
@@ -296,11 +339,14 @@ def _set_mib(dims):
     return float((32.0 * d[:, :-1] * d[:, 1:]).sum() / 2**20)
 
 
-def build_kernel_matrix(mpi_comm, ansatz, X, Y=None, info_file=None, truncation_error=None, loglevel=30):
+def build_kernel_matrix(mpi_comm, ansatz, X, Y=None, info_file=None, truncation_error=None, loglevel=30, initial_states=None, initial_states_Y=None):
     """Fill the kernel (Gram) matrix ``K[j, i] = |<psi(X_i)|psi(Y_j)>|^2``; ``Y=None`` means ``Y = X``.
 
     Returns the ``len(Y) x len(X)`` float64 matrix on rank 0 and ``None`` elsewhere (the reference
     returns the result of ``reduce(..., root=0)``, ref :428,:452).
+
+    ``initial_states`` (one ``MPS`` for all, or a list with one per data point of X; ``initial_states_Y`` for Y) applies the circuits
+    to given states instead of |0...0> -- any gauge, any norm (``Context.seed``, ``mps.seed_state``).  ``None`` is the call without it.
     """
     if Y is not None and len(X) < len(Y):
         raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
@@ -309,6 +355,8 @@ def build_kernel_matrix(mpi_comm, ansatz, X, Y=None, info_file=None, truncation_
     X = np.asarray(X, dtype=np.float64)
     Y = None if Y is None else np.asarray(Y, dtype=np.float64)
     fidelity = 1.0 - float(truncation_error)
+    init_x = _initial_states(initial_states, len(X), ansatz)
+    init_y = _initial_states(initial_states_Y if Y is not None else None, 0 if Y is None else len(Y), ansatz, "initial_states_Y")
 
     rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
     is_root = rank == ROOT_RANK
@@ -330,11 +378,11 @@ def build_kernel_matrix(mpi_comm, ansatz, X, Y=None, info_file=None, truncation_
     prof["r0_circ_gen"] = [0.0, "seconds"]
     _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
     ctx = _engine.default_context(device_id)
-    x_lo, x_local, x_secs, x_fid = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers)
+    x_lo, x_local, x_secs, x_fid = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers, initial=init_x)
     y_lo, y_local, y_secs, y_fid = (0, None, [], [])
     if Y is not None:
         _say(is_root, "\nContracting the MPS of the circuits from the Y dataset...")
-        y_lo, y_local, y_secs, y_fid = _simulate_share(ansatz, Y, rank, n_procs, fidelity, is_root, "Y", device_id, host_workers)
+        y_lo, y_local, y_secs, y_fid = _simulate_share(ansatz, Y, rank, n_procs, fidelity, is_root, "Y", device_id, host_workers, initial=init_y)
     sim_secs = x_secs + y_secs
     # the device builder keeps its per-workgroup arena and workspace on the context (tens of GB at large bond caps): they go back before
     # the exchange and the sweep need the memory (several ranks may share one GPU: device = rank % n_devices, ref :152)
@@ -408,7 +456,7 @@ def _gather_features(comm, lo, F, total):
 
 
 def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, info_file=None, truncation_error=None, loglevel=30, rdm=1, pair_distance=1, observables=None,
-                                  shots=None, shot_seed=0, window=False):
+                                  shots=None, shot_seed=0, window=False, initial_states=None, initial_states_Y=None):
     """Projected quantum kernel (Huang et al., Nat. Commun. 12, 2631 (2021)) of the same states as ``build_kernel_matrix``:
         K[j, i] = exp(-g sum_k ||rho_k(X_i) - rho_k(Y_j)||_F^2) = exp(-g/2 sum_k |F(X_i)[k] - F(Y_j)[k]|^2),
     rho_k = the one-qubit reduced density matrix of qubit k, F[k] = its Bloch vector (<X_k>, <Y_k>, <Z_k>); ``Y=None`` means
@@ -445,7 +493,9 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     same bits for any number of ranks; ``pqk_gamma=None`` means g = 1 / n_qubits.  It takes neither ``pair_distance`` other than
     1, nor ``shots``, nor ``observables`` (each a ``ValueError``): finite-shot window RDMs are out of scope.  ``window`` is the
     switch of this form: ``rdm >= 3`` without it stays the ``ValueError`` it has always been, and ``window=True`` with ``rdm`` 1 or 2
-    is one too (those two keep their own routes)."""
+    is one too (those two keep their own routes).
+
+    ``initial_states`` / ``initial_states_Y`` as in ``build_kernel_matrix``: the circuits are applied to given states."""
     strings = None
     if not isinstance(window, (bool, np.bool_)):
         raise ValueError(f"window must be True or False (got {window!r})")
@@ -492,6 +542,8 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     X = np.asarray(X, dtype=np.float64)
     Y = None if Y is None else np.asarray(Y, dtype=np.float64)
     fidelity = 1.0 - float(truncation_error)
+    inits = {"X": _initial_states(initial_states, len(X), ansatz),
+             "Y": _initial_states(initial_states_Y if Y is not None else None, 0 if Y is None else len(Y), ansatz, "initial_states_Y")}
 
     rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
     is_root = rank == ROOT_RANK
@@ -517,7 +569,7 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         if points is None:
             continue
         _say(is_root, f"\nContracting the MPS of the circuits from the {label} dataset...")
-        lo, local, secs, fid = _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, device_id, host_workers)
+        lo, local, secs, fid = _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, device_id, host_workers, initial=inits[label])
         sim_secs += secs
         fids += fid
         ctx.trim()  # the device builder's arena goes back before the local sweep needs memory
@@ -1385,13 +1437,14 @@ def build_depth_scan_kernel_matrices(mpi_comm, ansatz, X, Y=None, depths=(1,), t
     return out
 
 
-def _noisy_share(ansatz, points, first_index, trajectories, noise_seed, rank, n_procs, fidelity, is_root, label, device_id):
+def _noisy_share(ansatz, points, first_index, trajectories, noise_seed, rank, n_procs, fidelity, is_root, label, device_id, initial=None):
     """This rank's slice of a data set, every point as ``trajectories`` quantum trajectories -> (first point, the states as one
     device set in the order (point, trajectory) -- ``None`` for an empty share --, the log-weights (m, T), does the ansatz hold
     channels).  Data point p of the slice's data set has state index ``first_index + p`` and its trajectories are 0 .. T-1, so the
     draws do not depend on the number of ranks.  QK_BUILDER=host builds on the host (``mps.simulate`` with the same seed and
     indices); any other value on the device, bonds up to QK_BUILDER_MAX_BOND (320) or QK_MAX_BOND (a cap), and a share the device
-    gives up on is rebuilt on the host with the same seed and indices unless the device was forced."""
+    gives up on is rebuilt on the host with the same seed and indices unless the device was forced.  ``initial`` (``_initial_states``)
+    starts the circuits from given states: the T trajectories of a point share its one input state (``index`` of ``Context.seed``)."""
     import os
 
     T = int(trajectories)
@@ -1408,17 +1461,23 @@ def _noisy_share(ansatz, points, first_index, trajectories, noise_seed, rank, n_
     chi = int(os.environ.get("QK_MAX_BOND", "0")) or None
     which = os.environ.get("QK_BUILDER", "auto")
     ctx = _engine.default_context(device_id)
+    inits = _share_of(initial, lo, hi)
     if which != "host":
         cap = chi or int(os.environ.get("QK_BUILDER_MAX_BOND", "320"))
         try:
-            dset, info = ctx.build_mps_set(expanded, fidelity, max_bond=cap, truncate=chi is not None, seed=noise_seed, state_index=sidx, trajectory=traj)
+            given = {}
+            if inits is not None:  # one seed state per point (or one for all), T builds each
+                given = {"initial": inits if isinstance(inits, list) else [inits],
+                         "initial_index": np.repeat(np.arange(hi - lo, dtype=np.int32), T) if isinstance(inits, list) else np.zeros((hi - lo) * T, dtype=np.int32)}
+            dset, info = ctx.build_mps_set(expanded, fidelity, max_bond=cap, truncate=chi is not None, seed=noise_seed, state_index=sidx, trajectory=traj, **given)
             _say(is_root, f"{label}: 100%")
             return lo, dset, np.asarray(info["logw"]).reshape(hi - lo, T), noisy
         except _engine.QkError as exc:
             if which == "device":
                 raise
             _say(is_root, f"{label}: device builder gave up ({exc}); building on the host")
-    states = [simulate(c, fidelity, max_bond=chi, seed=noise_seed, state_index=int(s), trajectory=int(t)) for c, s, t in zip(expanded, sidx, traj)]
+    per_state = [None] * len(expanded) if inits is None else [inits[k // T] if isinstance(inits, list) else inits for k in range(len(expanded))]
+    states = [simulate(c, fidelity, max_bond=chi, seed=noise_seed, state_index=int(s), trajectory=int(t), initial=m) for c, s, t, m in zip(expanded, sidx, traj, per_state)]
     _say(is_root, f"{label}: 100%")
     return lo, ctx.upload(states), np.array([m.logw for m in states]).reshape(hi - lo, T), noisy
 
@@ -1437,7 +1496,8 @@ def _noisy_arguments(X, Y, trajectories, noise_seed, truncation_error):
     return np.asarray(X, dtype=np.float64), None if Y is None else np.asarray(Y, dtype=np.float64), int(trajectories), n_dev
 
 
-def build_noisy_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, trajectories=1, noise_seed=0, rdm=1, pair_distance=1, pqk_gamma=None, truncation_error=None):
+def build_noisy_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, trajectories=1, noise_seed=0, rdm=1, pair_distance=1, pqk_gamma=None, truncation_error=None,
+                                        initial_states=None, initial_states_Y=None):
     """The projected kernel of ``build_projected_kernel_matrix`` (``rdm=1`` or ``rdm=2`` with ``pair_distance``) for an ansatz with
     Kraus channels (``engine.with_noise``, the channel names of ``BoundCircuit.from_gates``): every data point is run as
     ``trajectories`` quantum trajectories and its features are the mean over them of ``local_paulis`` / ``local_pair_paulis`` -- the
@@ -1445,7 +1505,8 @@ def build_noisy_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, trajectorie
     state's (the features are linear in rho: the cost is linear in T).  Then the existing Gram.  Data point p (Y after X) has state
     index p and its trajectories are 0 .. T-1 (``channel_uniform(noise_seed, gate, trajectory, p)``), so any number of ranks gives
     the same bits; ``trajectories=1`` with an ansatz without channels is ``build_projected_kernel_matrix`` to rounding.  Returns
-    the ``len(Y) x len(X)`` matrix on rank 0, ``None`` elsewhere."""
+    the ``len(Y) x len(X)`` matrix on rank 0, ``None`` elsewhere.  ``initial_states`` / ``initial_states_Y`` as in
+    ``build_kernel_matrix``: every trajectory of a point starts from the point's given state."""
     if rdm not in (1, 2):
         raise ValueError(f"rdm must be 1 or 2, got {rdm!r}")
     n_qubits = int(ansatz.num_qubits)
@@ -1465,10 +1526,12 @@ def build_noisy_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, trajectorie
     ctx = _engine.default_context(device_id)
     n_pairs = pair_distance * n_qubits - pair_distance * (pair_distance + 1) // 2
     feats = []
+    inits = {"X": _initial_states(initial_states, len(X), ansatz),
+             "Y": _initial_states(initial_states_Y if Y is not None else None, 0 if Y is None else len(Y), ansatz, "initial_states_Y")}
     for label, points, first in (("X", X, 0), ("Y", Y, len(X))):
         if points is None:
             continue
-        lo, local, _, _ = _noisy_share(ansatz, points, first, T, noise_seed, rank, n_procs, 1.0 - float(truncation_error), is_root, label, device_id)
+        lo, local, _, _ = _noisy_share(ansatz, points, first, T, noise_seed, rank, n_procs, 1.0 - float(truncation_error), is_root, label, device_id, inits[label])
         ctx.trim()
         if local is None:
             F = np.zeros((0, n_qubits, 3) if rdm == 1 else (0, n_pairs, 4, 4), dtype=np.float64)

@@ -432,6 +432,46 @@ def _kept(s: np.ndarray, discard_budget: float, zero: float) -> tuple[int, float
     return keep, float(w[:keep].sum()) / total
 
 
+def seed_state(state: MPS, value_of_zero: float = 1e-16):
+    """A given state made ready for the builders: ``(MPS, norm)``, the numpy mirror of the sweep path of ``Context.seed``.  The
+    state may be in any gauge and of any norm: ``MPS.compress(max_discard=0)`` takes it to left-canonical form with the centre on
+    the last site (a bond whose rank is below its dimension shrinks to its rank), then the last site is divided by its Frobenius
+    norm ``norm`` = sqrt(<psi|psi>).  The result has norm 1, centre n - 1 and carries the sweep's fidelity.  ``ValueError`` for a
+    state of norm 0 or with an entry that is not finite."""
+    if not isinstance(state, MPS):
+        raise ValueError(f"seed_state needs an MPS, got {type(state).__name__}")
+    if not all(np.isfinite(t).all() for t in state.tensors):
+        raise ValueError("seed_state: the state has an entry that is not finite")
+    out, _ = state.compress(None, 0.0, value_of_zero)
+    last = out.tensors[-1]
+    norm = float(np.sqrt(float((last.real * last.real + last.imag * last.imag).sum())))
+    if not (norm > 0.0 and np.isfinite(norm)):
+        raise ValueError(f"seed_state: the state has norm {norm!r}")
+    out.tensors[-1] = last / norm
+    return out, norm
+
+
+def _initial_state(circuit, initial, initial_centre, value_of_zero):
+    """The state a host build starts from: ``None`` (|0...0>), or ``(MPS, centre)`` -- ``initial`` as it stands with its centre on
+    ``initial_centre``, or, without one, seeded by ``seed_state``.  ``ValueError`` by name for what cannot be built from."""
+    if initial is None:
+        if initial_centre is not None:
+            raise ValueError("initial_centre goes with an initial state")
+        return None
+    if not isinstance(initial, MPS):
+        raise ValueError(f"initial must be an MPS, got {type(initial).__name__}")
+    n = circuit.n_qubits
+    if len(initial) != n:
+        raise ValueError(f"the initial state has {len(initial)} sites, the circuit {n} qubits")
+    if initial_centre is None:
+        return seed_state(initial, value_of_zero)[0], n - 1
+    if isinstance(initial_centre, bool) or not isinstance(initial_centre, (int, np.integer)) or not 0 <= int(initial_centre) < n:
+        raise ValueError(f"initial_centre must be a site in 0 .. {n - 1} (got {initial_centre!r})")
+    if not all(np.isfinite(t).all() for t in initial.tensors) or not (np.isfinite(initial.fidelity) and np.isfinite(initial.logw)):
+        raise ValueError("the initial state has an entry that is not finite")
+    return initial, int(initial_centre)
+
+
 _NATIVE = None  # ctypes handle of libqkbuilder.so, False once loading has failed
 
 
@@ -463,6 +503,8 @@ def _native_builder():
                                                   C.POINTER(C.c_double)]
             lib.qkb_simulate_channels2.argtypes = lib.qkb_simulate_channels.argtypes[:20] + [C.c_int32, C.c_void_p, C.c_void_p] + lib.qkb_simulate_channels.argtypes[20:]
             lib.qkb_simulate_conditions.argtypes = lib.qkb_simulate_channels2.argtypes[:23] + [C.c_void_p, C.c_void_p] + lib.qkb_simulate_channels2.argtypes[23:]
+            lib.qkb_simulate_initial.argtypes = (lib.qkb_simulate_conditions.argtypes[:25] + [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double]
+                                                 + lib.qkb_simulate_conditions.argtypes[25:])
             lib.qkb_free.argtypes = [C.c_void_p]
             if blas and lib.qkb_init(os.path.realpath(blas[0]).encode()) == 0:
                 _NATIVE = lib
@@ -481,10 +523,12 @@ def _condition_rows(circuit, op):
 
 
 def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None, seed=0, state_index=0,
-                    trajectory=0, first_gate=0, margin=False):
+                    trajectory=0, first_gate=0, margin=False, initial=None, initial_centre=None):
     """``simulate`` through the native builder: same algorithm and LAPACK routines, no interpreter in the gate loop.  A circuit with
     a channel table goes through ``qkb_simulate_channels``, one with a two-qubit channel table through ``qkb_simulate_channels2``, one with condition rows
-    through ``qkb_simulate_conditions`` (the trajectory arguments and ``margin`` as in ``simulate``)."""
+    through ``qkb_simulate_conditions`` (the trajectory arguments and ``margin`` as in ``simulate``).  With ``initial`` (and
+    ``initial_centre``, as in ``simulate``) the call goes through ``qkb_simulate_initial``: the state is seeded here, the native
+    builder only loads it."""
     import ctypes as C
 
     lib = _native_builder()
@@ -506,6 +550,12 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
         n_mats = int(mats.shape[0])
     seed, state_index, trajectory, first_gate = _trajectory_ids(seed, state_index, trajectory, first_gate)
     logw, worst, branches = C.c_double(0.0), C.c_double(np.inf), np.zeros(0, dtype=np.int8)
+    start = _initial_state(circuit, initial, initial_centre, value_of_zero)
+    init = ()
+    if start is not None:  # (init_dims, init_tensors, init_centre, init_fidelity, init_logw) of qkb_simulate_initial
+        init_dims = np.ascontiguousarray(start[0].bond_dims(), dtype=np.int32)
+        init_flat = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.complex128).ravel() for t in start[0].tensors]))
+        init = (init_dims.ctypes.data, init_flat.ctypes.data, start[1], start[0].fidelity, start[0].logw)
     one = circuit.kraus is not None and circuit.n_kraus is not None
     two = circuit.kraus2 is not None and circuit.n_kraus2 is not None
     if circuit.channel is not None and (one or two):
@@ -530,7 +580,11 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
                 n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None, n1, kraus.ctypes.data if n1 else None,
                 n_kraus.ctypes.data if n1 else None, channel.ctypes.data, branch.ctypes.data, seed, state_index, trajectory, first_gate)
         tail = (dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid), C.byref(logw), branches.ctypes.data, C.byref(worst))
-        if circuit.cond_gate is not None:  # the native builder validates the rows
+        if init:
+            cg, cm = _condition_rows(circuit, op) if circuit.cond_gate is not None else (None, None)
+            rc = lib.qkb_simulate_initial(*head, n2, kraus2.ctypes.data if n2 else None, n_kraus2.ctypes.data if n2 else None, None if cg is None else cg.ctypes.data,
+                                          None if cm is None else cm.ctypes.data, *init, *tail)
+        elif circuit.cond_gate is not None:  # the native builder validates the rows
             cg, cm = _condition_rows(circuit, op)
             rc = lib.qkb_simulate_conditions(*head, n2, kraus2.ctypes.data if n2 else None, n_kraus2.ctypes.data if n2 else None, cg.ctypes.data,
                                              None if cm is None else cm.ctypes.data, *tail)
@@ -548,6 +602,11 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
                                              C.byref(block), C.byref(count), C.byref(fid), None, None, None)
             if rc == 0:
                 rc = -8  # (not reached: the entry refuses rows without a table)
+        elif init:  # no channel table: the log-weight of the initial state comes back unchanged
+            rc = lib.qkb_simulate_initial(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero),
+                                          int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None, 0, None, None, None, None, seed,
+                                          state_index, trajectory, first_gate, 0, None, None, None, None, *init, dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid),
+                                          C.byref(logw), None, None)
         else:
             rc = lib.qkb_simulate_gates(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
                                         float(value_of_zero), int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None,
@@ -570,7 +629,7 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
 
 
 def simulate(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None, checkpoints=None, seed=0,
-             state_index=0, trajectory=0, first_gate=0, margin=False):
+             state_index=0, trajectory=0, first_gate=0, margin=False, initial=None, initial_centre=None):
     """MPS of circuit|0...0>, "MPSxGate" style: one SVD per two-qubit gate (ref :221).  ``max_bond``: at most that many singular
     values survive a gate -- the ``chi`` of pytket-cutensornet's ``Config`` (ref :141-144 is where it would go); the weight it
     costs goes into ``fidelity`` like any other truncation.
@@ -585,6 +644,12 @@ def simulate(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, va
     else is built with it, and a run resumed at gate ``first_gate`` draws what the uninterrupted one draws.  The result carries
     ``logw`` and ``branches``; ``margin=True`` returns ``(result, margin)`` (see ``_simulate``).
 
+    ``initial`` (an ``MPS`` of ``n_qubits`` sites) replaces |0...0>: the circuit is applied to that state.  With
+    ``initial_centre=None`` the state may be in any gauge and of any norm and is seeded by ``seed_state`` first (canonical, norm 1,
+    centre n - 1, the sweep's fidelity); with ``initial_centre=k`` it is taken as it stands, canonical with its centre on site k, and
+    the run begins with ``initial.fidelity`` and ``initial.logw`` -- the host form of resuming from ``scan.states(j)``, whose centre
+    ``scan.info(j)`` reports.  Conditions may not reach behind the initial state.  ``initial=None`` is the code path without it.
+
     The matrices are small (tens to a few hundred rows): a multi-threaded BLAS spends its time waking
     threads (measured 24 s instead of 0.9 s per 60-qubit state on 8 cores), so the LAPACK calls run
     single-threaded here; parallelism is across states (``builder_pool.build_states``)."""
@@ -593,22 +658,24 @@ def simulate(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, va
     try:
         from threadpoolctl import threadpool_limits
     except ImportError:  # pragma: no cover - optional dependency
-        return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, checkpoints, seed, state_index, trajectory, first_gate, margin)
+        return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, checkpoints, seed, state_index, trajectory, first_gate, margin, initial, initial_centre)
     with threadpool_limits(limits=1):
         if checkpoints is not None:
-            return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, checkpoints, seed, state_index, trajectory, first_gate, margin)
+            return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, checkpoints, seed, state_index, trajectory, first_gate, margin, initial, initial_centre)
         if _use_native():
-            return simulate_native(circuit, truncation_fidelity, value_of_zero, max_bond, seed, state_index, trajectory, first_gate, margin)
-        return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, None, seed, state_index, trajectory, first_gate, margin)
+            return simulate_native(circuit, truncation_fidelity, value_of_zero, max_bond, seed, state_index, trajectory, first_gate, margin, initial, initial_centre)
+        return _simulate(circuit, truncation_fidelity, value_of_zero, max_bond, None, seed, state_index, trajectory, first_gate, margin, initial, initial_centre)
 
 
-def simulate_many(circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, workers: int | None = None, progress=None, max_bond: int | None = None):
+def simulate_many(circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, workers: int | None = None, progress=None, max_bond: int | None = None,
+                  initial=None):
     """``simulate`` for a list of circuits on several host cores **without forking** (safe once the GPU is initialised).
     The first circuit is built in this process and sizes the job: long jobs go to one worker *process* per core
     (``builder_worker.py`` over pipes: 10.8x on 16 cores for cfg4-shaped circuits, where threads in one process reach 2x
     because concurrent LAPACK calls contend inside OpenBLAS), medium ones to a thread pool (the native builder is a ctypes
     call that releases the GIL), short ones stay serial.  QK_BUILDER_POOL=procs|threads|serial overrides the choice.
-    Returns (list[MPS], seconds per circuit)."""
+    ``initial`` (one ``MPS`` for all circuits, or a list with one per circuit) starts them from given states (``simulate``); such
+    a job stays in this process (threads or serial).  Returns (list[MPS], seconds per circuit)."""
     import time
 
     circuits = list(circuits)
@@ -620,10 +687,15 @@ def simulate_many(circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_z
 
         workers = default_workers()
     workers = max(1, min(int(workers), len(circuits) - 1))
+    if initial is not None:
+        inits = [initial] * len(circuits) if isinstance(initial, MPS) else list(initial)
+        if len(inits) != len(circuits):
+            raise ValueError(f"simulate_many: {len(inits)} initial states for {len(circuits)} circuits")
+        circuits = list(zip(circuits, inits))  # a job is (circuit, initial state)
 
     def one(c):
         t0 = time.perf_counter()
-        m = simulate(c, truncation_fidelity, value_of_zero, max_bond)
+        m = simulate(c, truncation_fidelity, value_of_zero, max_bond) if initial is None else simulate(c[0], truncation_fidelity, value_of_zero, max_bond, initial=c[1])
         if progress is not None:
             progress()
         return m, time.perf_counter() - t0
@@ -636,6 +708,8 @@ def simulate_many(circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_z
         mode = "procs" if estimate / max(1, workers) > 2.0 else ("threads" if estimate > 0.5 else "serial")
     if not rest or workers <= 1:
         mode = "serial"
+    if mode == "procs" and initial is not None:
+        mode = "threads"
     if mode == "threads" and not _use_native():
         mode = "serial"
     if mode == "procs":
@@ -645,7 +719,7 @@ def simulate_many(circuits, truncation_fidelity: float = 1.0 - 1e-16, value_of_z
 
         def one_native(c):  # simulate() would enter / leave the BLAS thread limit per call, racing across threads
             t0 = time.perf_counter()
-            m = simulate_native(c, truncation_fidelity, value_of_zero, max_bond)
+            m = simulate_native(c, truncation_fidelity, value_of_zero, max_bond) if initial is None else simulate_native(c[0], truncation_fidelity, value_of_zero, max_bond, initial=c[1])
             if progress is not None:
                 progress()
             return m, time.perf_counter() - t0
@@ -740,7 +814,7 @@ def _trajectory_ids(seed, state_index, trajectory, first_gate):
 
 
 def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: float, max_bond: int | None = None, checkpoints=None, seed=0, state_index=0, trajectory=0,
-              first_gate=0, margin=False):
+              first_gate=0, margin=False, initial=None, initial_centre=None):
     """The numpy loop.  With ``checkpoints`` (validated gate counts) the return value is the list of snapshots: copies, the run itself
     is the one without them.  A circuit with a matrix table (``circuit.mat``, ``circuit.mats``) may hold op codes 8 and 9, a 2x2 on q0
     and a 4x4 on (q0, q0+1); ``ValueError`` for a table entry that is not unitary, an index outside the table or a gate outside
@@ -819,6 +893,10 @@ def _simulate(circuit: BoundCircuit, truncation_fidelity: float, value_of_zero: 
     two_q_pos = [q for o, q in zip(ops, qs) if is_two_qubit(o)]
     fidelity = 1.0
     centre = 0  # sites < centre are left-orthonormal, sites > centre right-orthonormal
+    start = _initial_state(circuit, initial, initial_centre, value_of_zero)
+    if start is not None:  # the run goes on from a given state (``simulate``): its sites, centre, fidelity and log-weight
+        A = [np.array(t, dtype=np.complex128) for t in start[0].tensors]
+        centre, fidelity, logw = start[1], start[0].fidelity, start[0].logw
     g2 = 0  # running index into two_q_pos
     snaps, marks = [], set(checkpoints or ())
 
