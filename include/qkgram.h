@@ -754,20 +754,12 @@ int qk_comm_stats(const qk_comm* comm, int32_t rank, qk_stats* out, double* allg
 int qk_selftest_mfma(qk_ctx* ctx);
 
 /* ---- device MPS builder ------------------------------------------------------------
- * Replaces simulate(libhandle, circ, SimulationAlgorithm.MPSxGate, config) (G:141-144, 221, 263) for the
- * ansatz gate program: all data points share the gate structure (op, q0: n_ops entries; 0 = H, 1 = Rz,
- * 2 = XXPhase on (q0, q0+1), 3 = SWAP on (q0, q0+1), 4 = Rx, 5 = Ry, 6 = YYPhase on (q0, q0+1), 7 = ZZPhase on
- * (q0, q0+1); TKET matrices, theta = pi alpha / 2) and differ in the half-turn angles alpha[n_states][n_ops].
- * Op codes 8 (a 2x2 on q0) and 9 (a 4x4 on (q0, q0+1)) are the matrix gates of qk_build_mps_gates below: valid only in a call that
- * comes with a matrix table; op code 10 (a one-qubit Kraus channel on q0) belongs to qk_build_mps_channels: valid only in a call that
- * comes with a channel table; op code 11 (a two-qubit Kraus channel on (q0, q0+1)) belongs to qk_build_mps_channels2: valid only in a
- * call that comes with a two-qubit channel table.  An op code outside 0..7 -- outside 0..9 with a matrix table, and 10 / 11 with
- * their channel tables -- is QK_EINVAL before anything runs.
- * One persistent launch; per two-qubit gate a one-sided Jacobi SVD and the truncation rule of the host builder:
- * drop the trailing singular values whose squared weight stays <= trunc_budget (= 1 - truncation_fidelity,
- * G:141-144; criterion as KernelPkg.jl:68), values <= value_of_zero never count.  max_bond bounds every bond
- * (QK_EINVAL if a state outgrows it).  The result stays on the device until downloaded: per state and site a
- * complex128 tensor [chi_l][2][chi_r] row-major, sites back to back, state s at offsets[s] (complex elements).    */
+ * Replaces simulate(libhandle, circ, SimulationAlgorithm.MPSxGate, config) (G:141-144, 221, 263) for a gate program (qk_program below): all
+ * data points share the gate structure and differ in the half-turn angles.  One persistent launch; per two-qubit gate a one-sided Jacobi
+ * SVD and the truncation rule of the host builder: drop the trailing singular values whose squared weight stays <= trunc_budget (= 1 -
+ * truncation_fidelity, G:141-144; criterion as KernelPkg.jl:68), values <= value_of_zero never count.  max_bond bounds every bond (QK_EINVAL
+ * if a state outgrows it).  The result stays on the device until downloaded: per state and site a complex128 tensor [chi_l][2][chi_r]
+ * row-major, sites back to back, state s at offsets[s] (complex elements). */
 typedef struct qk_built qk_built;
 #define QK_BUILD_PARTIAL 1u /* a state that outgrows max_bond is dropped (its fidelity reads -1, it has no tensors: build it
                              * elsewhere) instead of failing the call; its workgroup stops at the offending gate        */
@@ -775,9 +767,91 @@ typedef struct qk_built qk_built;
                              * Config, reference G:141-144, which the reference leaves unset); the weight it costs goes into the
                              * state's fidelity like any other truncation.  Without it a state that needs more is an error (or, with
                              * QK_BUILD_PARTIAL, dropped).                                                                          */
-int qk_build_mps(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
-                 const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
-                 qk_built** out);
+/* What to build: the gate program.  A table whose count is 0 is absent: its pointers are not read and its op codes are unknown.  Before
+ * anything runs the program is checked (csrc/qk_program.h; the host builder, csrc/qk_builder.cpp, runs the same struct with n_states = 1
+ * through the same checks), QK_EINVAL with the gate's position in the message: an op code outside the vocabulary, then what each table lists. */
+typedef struct qk_program {
+  uint32_t size;  int32_t n_states, n_qubits, n_ops;  /* size = sizeof(qk_program); the data points share op, q0 and every table without a state stride; n_ops = 0: every state stays |0...0> (or the snapshot) */
+  /* op[n_ops]: 0 = H, 1 = Rz, 2 = XXPhase on (q0, q0+1), 3 = SWAP on (q0, q0+1), 4 = Rx, 5 = Ry, 6 = YYPhase on (q0, q0+1), 7 = ZZPhase on
+   * (q0, q0+1); TKET matrices, theta = pi alpha / 2.  With the matrix table: 8 = a 2x2 unitary on q0, 9 = a 4x4 unitary on (q0, q0+1).
+   * With n_channels > 0: 10 = a one-qubit Kraus channel on q0.  With n_channels2 > 0: 11 = a two-qubit Kraus channel on (q0, q0+1) --
+   * two-qubit depolarising noise, correlated dephasing, projectors on a pair, joint post-selection. A channel gate runs as a quantum
+   * trajectory or with a forced branch (projectors, post-selection, a mid-circuit measurement with a chosen outcome, replay of a trajectory). */
+  const int8_t* op;  const int32_t* q0;  /* [n_ops] each */
+  const double* alpha;  /* [n_states][n_ops] half-turn angles; ignored at codes 8 to 11 */
+  /* The matrix table of codes 8 and 9.  The matrix of gate i is entry mat[i]: complex128 [n_mats][4][4] row-major, (re, im) interleaved; a
+   * 2x2 sits in [:2][:2] of its slot.  The 4x4 index is (s_q0, s_q0+1) with qubit q0 most significant (TKET's order), and new[(p,p')] = sum
+   * M[(p,p')][(s,s')] old[(s,s')].  Checked: a matrix gate past the last qubit (pair); mat[i] outside 0..n_mats-1; a matrix with an entry
+   * that is not finite; a matrix that is not unitary, max |M^H M - 1| > 1e-12 (the canonical-form bookkeeping assumes unitary gates: a
+   * one-qubit gate never moves the orthogonality centre; what is not unitary -- a projector, a post-selection, noise -- is a channel). */
+  int32_t n_mats, mats_state_stride; /* the stride: 0 -- one table for all states -- or n_mats -- state s reads mats + s * n_mats * 32 doubles (a data-dependent gate) */
+  const double* mats;  const int32_t* mat;  /* [mats_state_stride ? n_states : 1][n_mats][4][4][2]; [n_ops], read only where op is 8 or 9 */
+  /* The channel tables of codes 10 and 11; either may be absent when its code does not occur.  Channel c of code 10 is n_kraus[c] (1..4)
+   * matrices kraus[c][k][s'][s] = <s'|K_k|s>; of code 11, n_kraus2[c] (1..16) matrices kraus2[c][k][(p,p')][(s,s')], the index convention
+   * of the 4x4 matrix gates.  Checked: channel[i] outside its table; a count outside 1..4 (1..16); an entry that is not finite; branch[i]
+   * outside -1 .. m-1; a DRAWN channel that is not trace preserving, max |sum_k K_k^H K_k - 1| > 1e-12 (a forced branch may be any finite
+   * matrix); a channel gate outside the register.
+   * Code 10 on A_q = t[l][2][r]: the orthogonality centre is brought onto site q exactly (the centre moves of the two-qubit gates; no
+   * truncation); N = sum |t|^2, p_k = sum_{a,c} |K_k t[a][.][c]|^2, tot = p_0 + .. + p_{m-1} in ascending order; b = branch[i], or drawn:
+   * the first k with p_k > 0 and u tot < p_0 + .. + p_k (none: the last k with p_k > 0), u the uniform of Philox4x32-10 with counter
+   * (first_gate + i, trajectory[s], state_index[s], 2) and key (seed & 0xffffffff, seed >> 32), made from the first two output words as the
+   * sampler's (qk_sample_host; stream 0 draws shots, stream 1 bases, stream 2 branches); A_q <- K_b A_q / sqrt(p_b), and log(p_b / N) is
+   * added to the state's log-weight.  The centre stays on q, the bonds do not change.
+   * Code 11: the centre is brought into the pair by the moves of a two-qubit gate and theta[(a,p)][(p',c)] = A_q A_q+1 is formed; N = sum
+   * |theta|^2, p_k = sum_{a,c} |K_k theta[a,(.,.),c]|^2, tot, the branch b and the uniform as for code 10 (same counter); theta <- K_b
+   * theta / sqrt(p_b); then the SVD, truncation, fidelity product, bond cap and centre placement of any two-qubit gate (the bond may shrink
+   * or be cut), and log(p_b / N) is added to the log-weight.  The device adds the sums per thread over its strided (a, c) in ascending
+   * order and the threads' partials in ascending thread order, the Kraus matrices in groups of four per pass over theta; a forced branch
+   * takes one pass (N and p_b).  At run time QK_EDEVICE, naming the state and the gate, when p_b is 0 or not finite (an impossible outcome was post-selected) or tot is
+   * 0 in a draw.  A state's result depends on seed, its two indices, its gates and the tables only -- not on the other states of the call,
+   * their number, their order, or the launch; the sums use no atomics.  To that end a program with a channel table, and a build resumed
+   * from a snapshot of one, takes its workgroup shape from max_bond alone (the switch to 512 threads for at most one state per CU at
+   * max_bond 33..64 is for programs without channels); QK_BUILD_WGS overrides the shape and with it the bits.  A launch shape whose LDS
+   * cannot hold the staging of a channel step is QK_EINVAL. */
+  int32_t n_channels, n_channels2;
+  const double* kraus;   const int32_t* n_kraus;   /* [n_channels][4][2][2][2] complex128, (re, im) interleaved; [n_channels] */
+  const double* kraus2;  const int32_t* n_kraus2;  /* [n_channels2][16][4][4][2]; [n_channels2] */
+  const int32_t* channel;  /* [n_ops], read where op is 10 (an index into kraus) or 11 (into kraus2); alpha[i] and mat[i] are ignored there */
+  const int32_t* branch;   /* [branch_state_stride ? n_states : 1][n_ops], read where op is 10 or 11: -1 draws the branch, k >= 0 forces branch k */
+  int32_t branch_state_stride; /* 0 -- one row for all states -- or n_ops -- state s reads branch + s * n_ops */
+  uint32_t first_gate;  uint64_t seed;  /* first_gate: the position of gate 0 in the uninterrupted program: a resumed build, handed it, draws what that run draws */
+  const uint32_t *state_index, *trajectory; /* [n_states] each; NULL: 0 .. n_states-1, and all 0 */
+  /* Classical control, one entry per gate; cond_gate NULL: none.  cond_gate[i] is -1 (gate i is unconditional) or the position g < i, in
+   * this program, of a gate of op code 10 or 11; cond_mask[i] (read where cond_gate[i] >= 0) has bit v set when branch v of gate g lets
+   * gate i run.  With b the branch recorded for gate g of this state, gate i runs when b >= 0 and bit b of cond_mask[i] is set; else it is
+   * skipped: no centre move, no theta, no SVD, no change of a bond, of the fidelity or of the log-weight, no draw.  A skipped gate is a
+   * done gate all the same (checkpoints, first_gate + i and the positions conditions name count it), and the look-ahead that places the
+   * centre behind a two-qubit gate reads the op codes alone.  A skipped gate of code 10 or 11 records branch -2, so a condition on it is
+   * false; the gate conditioned on may itself be conditional; any op code may be conditional; cond_mask = 0 is "never".  The persistent
+   * kernel decides per state and gate by one load of the state's branch record: no atomics, no barrier between workgroups.  Positions are
+   * those of this program: a resumed build conditions only on gates it runs itself.  Checked: rows in a program without a channel table;
+   * cond_gate[i] < -1 or >= i; op[cond_gate[i]] not 10 or 11; a mask bit at or above the number of Kraus matrices of that gate's channel; cond_mask NULL. */
+  const int32_t* cond_gate;  const uint32_t* cond_mask;
+} qk_program;
+typedef struct qk_build_run { /* how to run it */
+  uint32_t size, flags; /* sizeof(qk_build_run); QK_BUILD_PARTIAL, QK_BUILD_TRUNCATE */
+  double trunc_budget, value_of_zero;  int32_t max_bond; /* 2..1024 */
+  /* Snapshots, for scans over the depth of a circuit: the state after checkpoints[j] gates (counted from 1) is kept as well, j = 0 ..
+   * n_checkpoints-1: strictly increasing, each in 1..n_ops, the last one n_ops.  n_checkpoints = 0 or checkpoints NULL: one snapshot after
+   * the whole program (n_checkpoints < 0 is QK_EINVAL).  A snapshot is a copy: the run does the arithmetic of a run without checkpoints,
+   * and the accessors without a snapshot index read the last one.  A snapshot is in mixed-canonical gauge, with its orthogonality centre
+   * recorded.  All snapshots share the one heap, so it is sized for n_checkpoints states per state (QK_EDEVICE if it turns out too small). */
+  int32_t n_checkpoints;  const int32_t* checkpoints;
+  /* Resume (NULL: from |0...0>): every state starts as snapshot initial_snapshot of `initial` -- same context, n_states and n_qubits, no
+   * dropped state, no bond above max_bond, else QK_EINVAL -- and the program holds the gates that FOLLOW it (with their tables); the
+   * fidelity and the log-weight go on from the snapshot's, also when the gates that remain hold no channel (every record then carries the
+   * snapshot's log-weight).  `initial` is only read.  Resuming snapshot j of a run with that run's gates from checkpoints[j] on is gate for
+   * gate the arithmetic of the uninterrupted run.  QK_BUILD_PARTIAL with more than one checkpoint or with `initial` is QK_EINVAL. */
+  const qk_built* initial;  int32_t initial_snapshot;
+} qk_build_run;
+/* The builder.  A struct whose size field is not its sizeof here is QK_EINVAL naming both sizes, before anything else is looked at;
+ * qk_program_size and qk_build_run_size return the two sizeofs of this library, for bindings that mirror the structs. */
+int qk_build_program(qk_ctx* ctx, const qk_program* program, const qk_build_run* run, qk_built** out);
+uint32_t qk_program_size(void), qk_build_run_size(void);
+/* The entries from before qk_program, their arguments in its fields' names: each fills the two structs and calls qk_build_program; every one
+ * after qk_build_mps needs checkpoints (NULL or n_checkpoints < 1: QK_EINVAL).  qk_build_mps: op, q0, alpha, the budget, zero, max_bond, flags. */
+int qk_build_mps(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha,
+                 double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, qk_built** out);
 /* dims[n_states][n_qubits+1], fidelity[n_states], offsets[n_states], total complex elements, kernel time; any may be NULL */
 int qk_built_info(const qk_built* built, int32_t* dims, double* fidelity, int64_t* offsets, int64_t* total_complex,
                   double* kernel_ms);
@@ -790,114 +864,39 @@ int qk_built_download(const qk_built* built, double* host /* 2 * total_complex d
  * device: nothing crosses PCIe between the builder and the sweep.  The set is independent of `built` afterwards.  */
 int qk_mps_set_from_built(qk_ctx* ctx, const qk_built* built, qk_mps_set** out);
 int qk_built_destroy(qk_built* built);
-/* Snapshots and resume, for scans over the depth of a circuit.  qk_build_mps_scan is qk_build_mps that ALSO keeps the state after
- * checkpoints[j] gates (counted from 1), j = 0 .. n_checkpoints-1: strictly increasing, each in 1..n_ops, the last one n_ops.  A
- * snapshot is a copy: the run does the arithmetic of a run without checkpoints, and its last snapshot is the result of qk_build_mps
- * (whose accessors above read the last snapshot).  A snapshot is in mixed-canonical gauge, with its orthogonality centre recorded.
- * All snapshots share the one heap, so it is sized for n_checkpoints states per state (QK_EDEVICE if it turns out too small).
- * `initial` (may be NULL) resumes: every state starts as snapshot `initial_snapshot` of `initial` -- same context, n_states and
- * n_qubits, no dropped state, no bond above max_bond, else QK_EINVAL -- instead of |0...0>, and op / q0 / alpha are the gates that
- * FOLLOW it; the fidelity goes on from the snapshot's.  `initial` is only read.  Resuming snapshot j of a run with that run's gates
- * from checkpoints[j] on is gate for gate the arithmetic of the uninterrupted run.  QK_BUILD_PARTIAL with more than one
- * checkpoint or with `initial` is QK_EINVAL.                                                                                      */
-int qk_build_mps_scan(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
-                      const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
-                      int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
-                      qk_built** out);
-/* Matrix gates.  qk_build_mps_gates is qk_build_mps_scan (its arguments in their order) plus a matrix table: with n_mats > 0 the
- * program may hold op code 8, a 2x2 unitary on qubit q0, and op code 9, a 4x4 unitary on (q0, q0+1).  The matrix of gate i is entry
- * mat[i] of the table: complex128 [n_mats][4][4] row-major, (re, im) interleaved; a 2x2 sits in [:2][:2] of its slot.  The 4x4 index
- * is (s_q0, s_q0+1) with qubit q0 most significant (TKET's order), and new[(p,p')] = sum M[(p,p')][(s,s')] old[(s,s')].  alpha[i] is
- * ignored at these codes; mat is read only where op is 8 or 9.  mats_state_stride (in matrices) is 0 -- one table shared by all
- * states -- or n_mats -- state s reads mats + s * n_mats * 32 doubles: a gate that depends on the data point.
- * Before anything runs, QK_EINVAL with the gate's position in the message for: mat[i] outside 0..n_mats-1; a matrix with an entry that
- * is not finite; a matrix that is not unitary, max |M^H M - 1| > 1e-12 (the canonical-form bookkeeping assumes unitary gates: a
- * one-qubit gate never moves the orthogonality centre; what is not unitary -- a projector, a post-selection, noise -- is a channel of
- * qk_build_mps_channels); a matrix gate past the last qubit (pair).  With n_mats = 0 the call IS
- * qk_build_mps_scan: codes 8 and 9 are unknown op codes.  Snapshots and resume work unchanged; a resumed build is handed the table
- * of the gates that follow.                                                                                                        */
-int qk_build_mps_gates(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
-                       const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
-                       int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
-                       int32_t n_mats, const double* mats /* [stride ? n_states : 1][n_mats][4][4][2] */, int32_t mats_state_stride,
-                       const int32_t* mat /* [n_ops] */, qk_built** out);
-/* Kraus channels.  qk_build_mps_channels is qk_build_mps_gates (its arguments in their order) plus a channel table: with n_channels > 0
- * the program may hold op code 10, a one-qubit Kraus channel on qubit q0, run as a quantum trajectory or with a forced branch
- * (projectors, post-selection, a mid-circuit measurement with a chosen outcome, replay of a recorded trajectory).  Channel c is
- * n_kraus[c] (1..4) matrices kraus[c][k][s'][s] = <s'|K_k|s>: complex128 [n_channels][4][2][2], (re, im) interleaved.  Gate i reads
- * channel channel[i] and branch[i]: -1 draws the branch, k >= 0 forces branch k; both rows are read only where op is 10, alpha[i] and
- * mat[i] are ignored there.  branch_state_stride is 0 -- one row for all states -- or n_ops -- state s reads branch + s * n_ops.
- * The step on A_q = t[l][2][r]: the orthogonality centre is brought onto site q exactly (the centre moves of the two-qubit gates; no
- * truncation); N = sum |t|^2, p_k = sum_{a,c} |K_k t[a][.][c]|^2, tot = p_0 + .. + p_{m-1} in ascending order; b = branch[i], or drawn:
- * the first k with p_k > 0 and u tot < p_0 + .. + p_k (none: the last k with p_k > 0), u the uniform of Philox4x32-10 with counter
- * (first_gate + i, trajectory[s], state_index[s], 2) and key (seed & 0xffffffff, seed >> 32), made from the first two output words
- * as the sampler's (qk_sample_host; stream 0 draws shots, stream 1 bases, stream 2 branches); A_q <- K_b A_q / sqrt(p_b), and log(p_b
- * / N) is added to the state's log-weight.  The centre stays on q, the bonds do not change.  state_index and trajectory
- * ([n_states]) may be NULL: 0 .. n_states-1 and all 0.  A state's result depends on seed, its two indices, its gates and the table
- * only -- not on the other states of the call, their number, their order, or the launch; the sums use no atomics.  To that end a
- * call with a channel table, and a build resumed from a snapshot of one, takes its workgroup shape from max_bond alone (the switch
- * to 512 threads for at most one state per CU at max_bond 33..64 is for programs without channels); QK_BUILD_WGS overrides the shape
- * and with it the bits.  first_gate is the position of gate 0 in the uninterrupted program: a resumed build (`initial`) is handed
- * the gates done so far and draws what the uninterrupted run draws; its log-weight goes on from the snapshot's, through any entry
- * point, also when the gates that remain hold no code 10 (every record then carries the snapshot's).
- * Before anything runs, QK_EINVAL with the gate's position for: channel[i] outside the table; n_kraus outside 1..4; an entry that is
- * not finite; branch[i] outside -1 .. m-1; a DRAWN channel that is not trace preserving, max |sum_k K_k^H K_k - 1| > 1e-12 (a forced
- * branch may be any finite matrix); a channel gate outside the register.  At run time QK_EDEVICE, naming the state and the gate, when
- * p_b is 0 or not finite (an impossible outcome was post-selected) or tot is 0 in a draw.  With n_channels = 0 the call IS
- * qk_build_mps_gates: code 10 is an unknown op code.                                                                                 */
-int qk_build_mps_channels(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
-                          const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
-                          int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
-                          int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
-                          const double* kraus /* [n_channels][4][2][2][2] */, const int32_t* n_kraus /* [n_channels] */,
-                          const int32_t* channel /* [n_ops] */, const int32_t* branch /* [stride ? n_states : 1][n_ops] */,
-                          int32_t branch_state_stride, uint64_t seed, const uint32_t* state_index, const uint32_t* trajectory,
-                          uint32_t first_gate, qk_built** out);
-/* Two-qubit Kraus channels.  qk_build_mps_channels2 is qk_build_mps_channels (its arguments in their order) plus a two-qubit channel
- * table: with n_channels2 > 0 the program may hold op code 11, a Kraus channel on the pair (q0, q0+1) -- two-qubit depolarising noise,
- * correlated dephasing, projectors on a pair, joint post-selection.  Channel c is n_kraus2[c] (1..16) matrices
- * kraus2[c][k][(p,p')][(s,s')]: complex128 [n_channels2][16][4][4], (re, im) interleaved, the index convention of the 4x4 matrix
- * gates (q0 most significant).  channel[i] and branch[i] are read where op is 10 or 11; where it is 11, channel[i] indexes kraus2.
- * Either table may be absent (n_channels = 0 or n_channels2 = 0) when its code does not occur.  The step: the centre is brought
- * into the pair by the moves of a two-qubit gate and theta[(a,p)][(p',c)] = A_q A_q+1 is formed; N = sum |theta|^2,
- * p_k = sum_{a,c} |K_k theta[a,(.,.),c]|^2, tot, the branch b and the uniform as for code 10 (same counter, stream 2);
- * theta <- K_b theta / sqrt(p_b); then the SVD, truncation, fidelity product, bond cap and centre placement of any two-qubit gate
- * (the bond may shrink or be cut), and log(p_b / N) is added to the log-weight.  The device adds the sums per thread over its
- * strided (a, c) in ascending order and the threads' partials in ascending thread order, the Kraus matrices in groups of four per
- * pass over theta; a forced branch takes one pass (N and p_b).  branches and qk_built_num_channel_gates count the gates of codes 10
- * and 11 together in program order.  QK_EINVAL before anything runs, naming the gate, for: channel[i] outside kraus2; n_kraus2
- * outside 1..16; an entry that is not finite; branch[i] outside -1 .. m-1; a drawn channel with max |sum_k K_k^H K_k - 1| > 1e-12;
- * q0[i] + 1 outside the register; a launch shape whose LDS cannot hold the staging.  QK_EDEVICE as for code 10.  With
- * n_channels2 = 0 the call IS qk_build_mps_channels: code 11 is an unknown op code.                                                   */
-int qk_build_mps_channels2(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
-                           const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
-                           int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
-                           int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
-                           const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch,
-                           int32_t branch_state_stride, uint64_t seed, const uint32_t* state_index, const uint32_t* trajectory,
-                           uint32_t first_gate, int32_t n_channels2, const double* kraus2 /* [n_channels2][16][4][4][2] */,
-                           const int32_t* n_kraus2 /* [n_channels2] */, qk_built** out);
-/* Classical control.  qk_build_mps_conditions is qk_build_mps_channels2 (its arguments in their order) plus two rows in front of
- * `out`, one entry per gate: cond_gate[i] is -1 (gate i is unconditional) or the position g < i, in this program, of a gate of op
- * code 10 or 11; cond_mask[i] (read where cond_gate[i] >= 0) has bit v set when branch v of gate g lets gate i run.  With b the
- * branch recorded for gate g of this state, gate i runs when b >= 0 and bit b of cond_mask[i] is set; else it is skipped: no centre
- * move, no theta, no SVD, no change of a bond, of the fidelity or of the log-weight, no draw.  A skipped gate is a done gate all the
- * same (checkpoints, first_gate + i and the positions conditions name count it), and the look-ahead that places the centre behind a
- * two-qubit gate reads the op codes alone.  A skipped gate of code 10 or 11 records branch -2, so a condition on it is false; the
- * gate conditioned on may itself be conditional; any op code may be conditional; cond_mask = 0 is "never".  The persistent kernel
- * decides per state and gate by one load of the state's branch record: no atomics, no barrier between workgroups.  Positions are
- * those of the program of the call: a resumed build (`initial`) conditions only on gates it runs itself.  QK_EINVAL before
- * anything runs, naming the gate, for: rows in a call without a channel table; cond_gate[i] < -1 or >= i; op[cond_gate[i]] not 10 or
- * 11; a mask bit at or above the number of Kraus matrices of that gate's channel; cond_mask NULL.  With cond_gate NULL the call IS
- * qk_build_mps_channels2.                                                                                                          */
-int qk_build_mps_conditions(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
-                            const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags,
-                            int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
-                            int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
-                            const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch,
-                            int32_t branch_state_stride, uint64_t seed, const uint32_t* state_index, const uint32_t* trajectory,
-                            uint32_t first_gate, int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2,
-                            const int32_t* cond_gate /* [n_ops] */, const uint32_t* cond_mask /* [n_ops] */, qk_built** out);
+/* qk_build_mps_scan: qk_build_mps plus n_checkpoints, checkpoints, initial, initial_snapshot */
+int qk_build_mps_scan(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double*
+                      alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const
+                      int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot, qk_built** out);
+/* qk_build_mps_gates: qk_build_mps_scan plus n_mats, mats, mats_state_stride, mat */
+int qk_build_mps_gates(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double*
+                       alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const
+                       int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t
+                       mats_state_stride, const int32_t* mat, qk_built** out);
+/* qk_build_mps_channels: qk_build_mps_gates plus n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index,
+ * trajectory, first_gate */
+int qk_build_mps_channels(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double*
+                          alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const
+                          int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot, int32_t n_mats, const double* mats,
+                          int32_t mats_state_stride, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
+                          const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed, const uint32_t*
+                          state_index, const uint32_t* trajectory, uint32_t first_gate, qk_built** out);
+/* qk_build_mps_channels2: qk_build_mps_channels plus n_channels2, kraus2, n_kraus2 */
+int qk_build_mps_channels2(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const
+                           double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, int32_t
+                           n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot, int32_t n_mats,
+                           const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels, const double* kraus, const
+                           int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
+                           const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const double*
+                           kraus2, const int32_t* n_kraus2, qk_built** out);
+/* qk_build_mps_conditions: qk_build_mps_channels2 plus cond_gate, cond_mask */
+int qk_build_mps_conditions(qk_ctx* ctx, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const
+                            double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, int32_t
+                            n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot, int32_t n_mats,
+                            const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels, const double* kraus,
+                            const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t
+                            seed, const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const
+                            double* kraus2, const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, qk_built** out);
 int qk_built_logw_at(const qk_built* built, int32_t j, double* logw /* [n_states] */); /* log-weights at snapshot j (0 without channels) */
 int qk_built_num_channel_gates(const qk_built* built);                    /* gates of op codes 10 and 11 of the program */
 /* The branch every channel gate took, in program order: [n_states][n_channel_gates]; -1 where a dropped state stopped early, -2

@@ -20,6 +20,7 @@
 // state can outgrow its bond cap (QK_BUILDER=auto).
 #include "qk_host.h"
 #include "qk_local_plan.h"
+#include "qk_program.h"
 
 #include <algorithm>
 #include <chrono>
@@ -29,16 +30,13 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <string>
 
 namespace {
 typedef double cd __attribute__((ext_vector_type(2)));  // complex128 as (re, im); a native vector so that LDS-typed pointers work
 
 constexpr int MAX_SWEEPS = 40;
 
-// ansatz.py.  Codes 8 and 9 are the matrix gates: valid only in a program that comes with a matrix table (N_OPS_MAT codes then).
-// Code 10 is the one-qubit Kraus channel: valid only in a program that comes with a channel table; code 11 the two-qubit Kraus
-// channel on (q0, q0+1): valid only in a program that comes with a two-qubit channel table.
-enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10, OP_K1 = 10, OP_K2 = 11 };
 
 // CHAN = false: the question as a kernel instantiation without the channel steps asks it (code 11 cannot occur there: the host
 // refuses it before the launch), so that its code is that of the kernel before the channels
@@ -752,262 +750,43 @@ struct qk_built {
   int n_snapshots() const { return (int)checkpoints.size(); }
 };
 
-struct MatTable {  // the matrix table of op codes 8 and 9 as the caller gave it (n_mats = 0: none)
-  int32_t n_mats = 0;
-  const double* mats = nullptr;
-  int32_t stride = 0;
-  const int32_t* mat = nullptr;
-};
+static const char* const what = "qk_build_program";  // in front of every message of build_impl
 
-struct ChanTable {  // the channel tables of op codes 10 and 11 and the names of the trajectories as the caller gave them (n_channels = 0, n_channels2 = 0: none)
-  int32_t n_channels = 0;
-  const double* kraus = nullptr;     // [n_channels][4][2][2][2]
-  const int32_t* n_kraus = nullptr;  // [n_channels]
-  int32_t n_channels2 = 0;
-  const double* kraus2 = nullptr;    // [n_channels2][16][4][4][2]
-  const int32_t* n_kraus2 = nullptr; // [n_channels2]
-  const int32_t* channel = nullptr;  // [n_ops]
-  const int32_t* branch = nullptr;   // [stride ? n_states : 1][n_ops]
-  int32_t stride = 0;
-  uint64_t seed = 0;
-  const uint32_t* state_index = nullptr;  // [n_states], null: 0 .. n_states-1
-  const uint32_t* trajectory = nullptr;   // [n_states], null: all 0
-  uint32_t first_gate = 0;
-  const int32_t* cond_gate = nullptr;   // [n_ops] classical control (qk_build_mps_conditions), null: none
-  const uint32_t* cond_mask = nullptr;  // [n_ops]
-};
-
-static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, const MatTable& tab,
-                      const ChanTable& cht, qk_built** out);
-// the body of qk_build_mps_scan and qk_build_mps_gates; `what` is the entry point the caller came through, for its error messages
-static int build_gates(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                       double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
-                       int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, const ChanTable& cht, qk_built** out);
-
-extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
-                            const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, qk_built** out) {
-  const int32_t last = n_ops;  // the one-checkpoint scan: a snapshot after the whole program
-  return build_impl("qk_build_mps", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, 1, &last, nullptr, 0, MatTable{}, ChanTable{}, out);
-}
-
-extern "C" int qk_build_mps_scan(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                                 double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
-                                 int32_t initial_snapshot, qk_built** out) {
-  return build_gates("qk_build_mps_scan", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
-                     0, nullptr, 0, nullptr, ChanTable{}, out);
-}
-
-// The matrix table of a program, checked before anything runs: every matrix gate's index inside 0..n_mats-1 and, in each of the
-// `tables` tables, its 2x2 ([:2][:2] of the slot) or 4x4 finite and unitary, max |M^H M - 1| <= 1e-12.
-static int check_mat_table(const char* what, int n_ops, const int8_t* op, int tables, const MatTable& tab) {
-  std::vector<char> seen((size_t)tab.n_mats, 0);  // bit 0: checked as a 2x2, bit 1: as a 4x4 -- an entry many gates read is checked once
-  for (int i = 0; i < n_ops; ++i) {
-    if (op[i] != OP_M1 && op[i] != OP_M2) continue;
-    const int k = tab.mat[i], d = op[i] == OP_M1 ? 2 : 4;
-    if (k < 0 || k >= tab.n_mats) return qk_fail(QK_EINVAL, "%s: gate %d: matrix index %d outside 0..%d", what, i, k, (int)tab.n_mats - 1);
-    if (seen[(size_t)k] & (d == 2 ? 1 : 2)) continue;
-    seen[(size_t)k] |= (d == 2 ? 1 : 2);
-    for (int s = 0; s < tables; ++s) {
-      const double* m = tab.mats + ((size_t)s * tab.n_mats + k) * 32;  // [4][4][2]
-      double dev = 0;
-      bool finite = true;
-      for (int a = 0; a < d; ++a)
-        for (int b = 0; b < d; ++b) {
-          finite = finite && std::isfinite(m[(a * 4 + b) * 2]) && std::isfinite(m[(a * 4 + b) * 2 + 1]);
-          double gr = (a == b) ? -1.0 : 0.0, gi = 0.0;  // (M^H M - 1)[a][b] = sum_r conj(M[r][a]) M[r][b] - delta
-          for (int r = 0; r < d; ++r) {
-            const double xr = m[(r * 4 + a) * 2], xi = m[(r * 4 + a) * 2 + 1], yr = m[(r * 4 + b) * 2], yi = m[(r * 4 + b) * 2 + 1];
-            gr += xr * yr + xi * yi, gi += xr * yi - xi * yr;
-          }
-          dev = std::max(dev, std::hypot(gr, gi));
-        }
-      if (!finite) return qk_fail(QK_EINVAL, "%s: gate %d: the matrix of table entry %d (state %d) has an entry that is not finite", what, i, k, s);
-      if (!(dev <= 1e-12)) return qk_fail(QK_EINVAL, "%s: gate %d: the matrix of table entry %d (state %d) is not unitary: max |M^H M - 1| = %.3e > 1e-12", what, i, k, s, dev);
-    }
-  }
-  return QK_OK;
-}
-
-extern "C" int qk_build_mps_gates(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                                  double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
-                                  int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, qk_built** out) {
-  return build_gates("qk_build_mps_gates", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
-                     n_mats, mats, mats_state_stride, mat, ChanTable{}, out);
-}
-
-// The channel gates of a program, checked before anything runs (in each of the `rows` branch rows): the channel inside its table,
-// 1..4 matrices (1..16 for the two-qubit channel of code 11), finite entries, the branch inside -1..m-1, a drawn channel trace
-// preserving, max |sum_k K_k^H K_k - 1| <= 1e-12 (a forced branch may be any finite matrix), the qubit (pair) inside the register.
-static int check_chan_table(const char* what, int n_qubits, int n_ops, const int8_t* op, const int32_t* q0, int rows, const ChanTable& t) {
-  for (int i = 0; i < n_ops; ++i) {
-    if (op[i] != OP_K1 && op[i] != OP_K2) continue;
-    const bool two = op[i] == OP_K2;
-    const int d = two ? 4 : 2, n_table = two ? t.n_channels2 : t.n_channels;  // d x d matrices, at most d * d of them
-    const char* kind = two ? "two-qubit channel" : "channel";
-    const int ch = t.channel[i];
-    if (ch < 0 || ch >= n_table) return qk_fail(QK_EINVAL, "%s: gate %d: %s index %d outside 0..%d", what, i, kind, ch, n_table - 1);
-    const int m = (two ? t.n_kraus2 : t.n_kraus)[ch];
-    if (m < 1 || m > d * d) return qk_fail(QK_EINVAL, "%s: gate %d: %s %d has %d Kraus matrices (1..%d)", what, i, kind, ch, m, d * d);
-    const double* K = (two ? t.kraus2 : t.kraus) + (size_t)ch * d * d * d * d * 2;  // [d * d][d][d][2]
-    for (int e = 0; e < 2 * d * d * m; ++e)
-      if (!std::isfinite(K[e])) return qk_fail(QK_EINVAL, "%s: gate %d: a Kraus matrix of %s %d has an entry that is not finite", what, i, kind, ch);
-    bool drawn = false;
-    for (int s = 0; s < rows; ++s) {
-      const int b = t.branch[(size_t)s * n_ops + i];
-      if (b < -1 || b >= m) return qk_fail(QK_EINVAL, "%s: gate %d: branch %d (row %d) outside -1..%d", what, i, b, s, m - 1);
-      drawn = drawn || b < 0;
-    }
-    if (drawn) {
-      double dev = 0;
-      for (int a = 0; a < d; ++a)
-        for (int e = 0; e < d; ++e) {
-          double gr = (a == e) ? -1.0 : 0.0, gi = 0.0;  // (sum_k K_k^H K_k - 1)[a][e] = sum_{k,r} conj(K_k[r][a]) K_k[r][e] - delta
-          for (int k = 0; k < m; ++k)
-            for (int r = 0; r < d; ++r) {
-              const double xr = K[((k * d + r) * d + a) * 2], xi = K[((k * d + r) * d + a) * 2 + 1], yr = K[((k * d + r) * d + e) * 2], yi = K[((k * d + r) * d + e) * 2 + 1];
-              gr += xr * yr + xi * yi, gi += xr * yi - xi * yr;
-            }
-          dev = std::max(dev, std::hypot(gr, gi));
-        }
-      if (!(dev <= 1e-12)) return qk_fail(QK_EINVAL, "%s: gate %d: the drawn %s %d is not trace preserving: max |sum K^H K - 1| = %.3e > 1e-12", what, i, kind, ch, dev);
-    }
-    if (q0[i] < 0 || q0[i] + (two ? 1 : 0) >= n_qubits) return qk_fail(QK_EINVAL, "%s: gate %d: %s on a qubit outside the register", what, i, kind);
-  }
-  return QK_OK;
-}
-
-// The condition rows of a program, checked before anything runs (check_chan_table has passed): cond_gate[i] inside -1 .. i-1, the gate
-// it names of op code 10 or 11, no mask bit at or above the number of Kraus matrices of that gate's channel.
-static int check_conditions(const char* what, int n_ops, const int8_t* op, const ChanTable& t) {
-  for (int i = 0; i < n_ops; ++i) {
-    const int g = t.cond_gate[i];
-    if (g == -1) continue;
-    if (g < -1 || g >= i) return qk_fail(QK_EINVAL, "%s: gate %d: condition on gate %d outside -1..%d", what, i, g, i - 1);
-    if (op[g] != OP_K1 && op[g] != OP_K2) return qk_fail(QK_EINVAL, "%s: gate %d: condition on gate %d, which is no channel gate (op code %d)", what, i, g, (int)op[g]);
-    const int m = (op[g] == OP_K2 ? t.n_kraus2 : t.n_kraus)[t.channel[g]];
-    if (m < 32 && (t.cond_mask[i] >> m) != 0u) return qk_fail(QK_EINVAL, "%s: gate %d: condition mask names a branch at or above the %d of gate %d", what, i, m, g);
-  }
-  return QK_OK;
-}
-
-// the body of qk_build_mps_channels (n_channels2 = 0), qk_build_mps_channels2 and qk_build_mps_conditions (cond_gate set)
-static int build_channels(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                          double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
-                          int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
-                          const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
-                          const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const double* kraus2,
-                          const int32_t* n_kraus2, qk_built** out, const int32_t* cond_gate = nullptr, const uint32_t* cond_mask = nullptr) {
-  ChanTable t;
-  if (cond_gate && !cond_mask) return qk_fail(QK_EINVAL, "%s: condition rows need cond_gate and cond_mask", what);
-  if (cond_gate && n_channels <= 0 && n_channels2 <= 0) return qk_fail(QK_EINVAL, "%s: gate 0: condition rows need a program with a channel table", what);
-  t.cond_gate = cond_gate, t.cond_mask = cond_gate ? cond_mask : nullptr;
-  if (n_channels2 < 0 || (n_channels2 > 0 && (!kraus2 || !n_kraus2 || !channel || !branch)))
-    return qk_fail(QK_EINVAL, "%s: a two-qubit channel table needs n_channels2 >= 0, kraus2, n_kraus2, channel and branch", what);
-  if (n_channels < 0 || (n_channels > 0 && (!kraus || !n_kraus || !channel || !branch))) return qk_fail(QK_EINVAL, "%s: a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch", what);
-  if ((n_channels > 0 || n_channels2 > 0) && branch_state_stride != 0 && branch_state_stride != n_ops)
-    return qk_fail(QK_EINVAL, "%s: branch_state_stride must be 0 (one row for all states) or n_ops = %d, got %d", what, (int)n_ops, (int)branch_state_stride);
-  if (n_channels > 0) t.n_channels = n_channels, t.kraus = kraus, t.n_kraus = n_kraus;
-  if (n_channels2 > 0) t.n_channels2 = n_channels2, t.kraus2 = kraus2, t.n_kraus2 = n_kraus2;
-  if (n_channels > 0 || n_channels2 > 0) {
-    t.channel = channel, t.branch = branch, t.stride = branch_state_stride;
-    t.seed = seed, t.state_index = state_index, t.trajectory = trajectory, t.first_gate = first_gate;
-  }
-  return build_gates(n_channels > 0 || n_channels2 > 0 ? what : "qk_build_mps_gates", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial,
-                     initial_snapshot, n_mats, mats, mats_state_stride, mat, t, out);
-}
-
-extern "C" int qk_build_mps_channels(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                                     double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
-                                     int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
-                                     const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
-                                     const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, qk_built** out) {
-  return build_channels("qk_build_mps_channels", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
-                        n_mats, mats, mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate, 0, nullptr,
-                        nullptr, out);
-}
-
-extern "C" int qk_build_mps_channels2(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
-                                      int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
-                                      const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
-                                      const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const double* kraus2,
-                                      const int32_t* n_kraus2, qk_built** out) {
-  if (n_channels2 == 0)  // without a two-qubit table the call IS qk_build_mps_channels
-    return qk_build_mps_channels(c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot, n_mats, mats,
-                                 mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate, out);
-  return build_channels("qk_build_mps_channels2", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot,
-                        n_mats, mats, mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate, n_channels2, kraus2,
-                        n_kraus2, out);
-}
-
-extern "C" int qk_build_mps_conditions(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                                       double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
-                                       int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
-                                       const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
-                                       const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const double* kraus2,
-                                       const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, qk_built** out) {
-  if (!cond_gate)  // without condition rows the call IS qk_build_mps_channels2
-    return qk_build_mps_channels2(c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot, n_mats, mats,
-                                  mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate, n_channels2, kraus2,
-                                  n_kraus2, out);
-  return build_channels("qk_build_mps_conditions", c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial,
-                        initial_snapshot, n_mats, mats, mats_state_stride, mat, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate,
-                        n_channels2, kraus2, n_kraus2, out, cond_gate, cond_mask);
-}
-
-static int build_gates(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                       double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial, int32_t initial_snapshot,
-                       int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, const ChanTable& cht, qk_built** out) {
-  MatTable tab;
-  if (n_mats < 0 || (n_mats > 0 && (!mats || !mat))) return qk_fail(QK_EINVAL, "%s: a matrix table needs n_mats >= 0, mats and mat", what);
-  if (n_mats > 0 && mats_state_stride != 0 && mats_state_stride != n_mats)
-    return qk_fail(QK_EINVAL, "%s: mats_state_stride must be 0 (one table for all states) or n_mats = %d, got %d", what, (int)n_mats, (int)mats_state_stride);
-  if (n_mats > 0) tab.n_mats = n_mats, tab.mats = mats, tab.stride = mats_state_stride, tab.mat = mat;
-  if (!checkpoints || n_checkpoints < 1) return qk_fail(QK_EINVAL, "%s: no checkpoints", what);
-  for (int j = 0; j < n_checkpoints; ++j)
-    if (checkpoints[j] < 1 || checkpoints[j] > n_ops || (j > 0 && checkpoints[j] <= checkpoints[j - 1]))
-      return qk_fail(QK_EINVAL, "%s: checkpoints must be strictly increasing gate counts in 1..%d (checkpoint %d is %d)", what, n_ops, j, (int)checkpoints[j]);
-  if (checkpoints[n_checkpoints - 1] != n_ops) return qk_fail(QK_EINVAL, "%s: the last checkpoint must be the whole program (%d gates), got %d", what, n_ops, (int)checkpoints[n_checkpoints - 1]);
-  if ((flags & QK_BUILD_PARTIAL) && (n_checkpoints > 1 || initial))
+// the body of qk_build_program (which has compared the sizes); the QK_EINVAL checks come in the order of the entries this one replaced
+static int build_impl(qk_ctx* c, const qk_program& prog, const qk_build_run& run, qk_built** out) {
+  const int32_t n_states = prog.n_states, n_qubits = prog.n_qubits, n_ops = prog.n_ops, max_bond = run.max_bond, init_j = run.initial_snapshot;
+  const int8_t* const op = prog.op;
+  const int32_t* const q0 = prog.q0;
+  const double* const alpha = prog.alpha;
+  const double trunc_budget = run.trunc_budget, value_of_zero = run.value_of_zero;
+  const uint32_t flags = run.flags;
+  const qk_built* const init = run.initial;
+  std::string wrong;
+  if (!qk_program_check_tables(prog, &wrong)) return qk_fail(QK_EINVAL, "%s: %s", what, wrong.c_str());
+  const int32_t whole = n_ops;  // without checkpoints: one snapshot after the whole program, which may be empty
+  const bool scan = run.checkpoints && run.n_checkpoints > 0;
+  const int32_t n_ckpt = scan ? run.n_checkpoints : 1;
+  const int32_t* const ckpt = scan ? run.checkpoints : &whole;
+  if (run.n_checkpoints < 0) return qk_fail(QK_EINVAL, "%s: no checkpoints", what);
+  for (int j = 0; scan && j < n_ckpt; ++j)
+    if (ckpt[j] < 1 || ckpt[j] > n_ops || (j > 0 && ckpt[j] <= ckpt[j - 1]))
+      return qk_fail(QK_EINVAL, "%s: checkpoints must be strictly increasing gate counts in 1..%d (checkpoint %d is %d)", what, n_ops, j, (int)ckpt[j]);
+  if (ckpt[n_ckpt - 1] != n_ops) return qk_fail(QK_EINVAL, "%s: the last checkpoint must be the whole program (%d gates), got %d", what, n_ops, (int)ckpt[n_ckpt - 1]);
+  if ((flags & QK_BUILD_PARTIAL) && (n_ckpt > 1 || init))
     return qk_fail(QK_EINVAL, "%s: QK_BUILD_PARTIAL goes with one checkpoint and no initial snapshot (a dropped state has no snapshots)", what);
-  return build_impl(what, c, n_states, n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot, tab, cht, out);
-}
-
-static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_ckpt, const int32_t* ckpt, const qk_built* init, int32_t init_j, const MatTable& tab,
-                      const ChanTable& cht, qk_built** out) {
   if (!c || !op || !q0 || !alpha || !out) return qk_fail(QK_EINVAL, "%s: null argument", what);
   if (n_states <= 0 || n_qubits <= 0 || n_ops < 0) return qk_fail(QK_EINVAL, "%s: empty problem (%d states, %d qubits, %d gates)", what, n_states, n_qubits, n_ops);
   if (max_bond < 2 || max_bond > 1024) return qk_fail(QK_EINVAL, "%s: max_bond %d outside 2..1024", what, max_bond);
-  const int n_codes = tab.n_mats > 0 ? N_OPS_MAT : N_OPS;  // without a table codes 8 and 9 are unknown
-  const bool with_k1 = cht.n_channels > 0, with_k2 = cht.n_channels2 > 0;  // without a channel table code 10 is unknown, without a two-qubit one code 11
-  const bool with_chan = with_k1 || with_k2;
-  for (int i = 0; i < n_ops; ++i)
-    if ((op[i] < 0 || op[i] >= n_codes) && !(with_k1 && op[i] == OP_K1) && !(with_k2 && op[i] == OP_K2))
-      return qk_fail(QK_EINVAL, "%s: unknown gate op code %d at position %d (valid: 0..%d%s%s)", what, (int)op[i], i, n_codes - 1, with_k1 ? ", 10" : "", with_k2 ? ", 11" : "");
-  for (int i = 0; i < n_ops; ++i)  // (the kernel checks this too; a matrix gate past the last pair is refused before anything runs)
-    if ((op[i] == OP_M1 || op[i] == OP_M2) && (q0[i] < 0 || q0[i] + (op[i] == OP_M2 ? 1 : 0) >= n_qubits))
-      return qk_fail(QK_EINVAL, "%s: gate %d on a qubit outside the register", what, i);
-  const int n_tables = tab.n_mats > 0 ? (tab.stride ? n_states : 1) : 0;
-  if (n_tables) {
-    const int rc = check_mat_table(what, n_ops, op, n_tables, tab);
-    if (rc != QK_OK) return rc;
-  }
+  if (qk_program_check(prog, &wrong) != QK_PROGRAM_OK) return qk_fail(QK_EINVAL, "%s: %s", what, wrong.c_str());
+  const int n_codes = prog.n_mats > 0 ? N_OPS_MAT : N_OPS;
+  const bool with_k1 = prog.n_channels > 0, with_k2 = prog.n_channels2 > 0, with_chan = with_k1 || with_k2;
+  const int n_tables = prog.n_mats > 0 ? (prog.mats_state_stride ? n_states : 1) : 0;
   std::vector<int32_t> kgate((size_t)std::max(1, n_ops), 0);  // channel gates before gate i
   int n_kgates = 0, n_k2gates = 0;
-  if (with_chan) {
-    const int rc = check_chan_table(what, n_qubits, n_ops, op, q0, cht.stride ? n_states : 1, cht);
-    if (rc != QK_OK) return rc;
-    for (int i = 0; i < n_ops; ++i) {
-      kgate[i] = n_kgates;
-      n_kgates += (op[i] == OP_K1 || op[i] == OP_K2);
-      n_k2gates += (op[i] == OP_K2);
-    }
-    if (cht.cond_gate) {
-      const int rc2 = check_conditions(what, n_ops, op, cht);
-      if (rc2 != QK_OK) return rc2;
-    }
+  for (int i = 0; with_chan && i < n_ops; ++i) {
+    kgate[i] = n_kgates;
+    n_kgates += (op[i] == OP_K1 || op[i] == OP_K2);
+    n_k2gates += (op[i] == OP_K2);
   }
   if (init) {  // a resumed build starts from snapshot init_j of `init`, which is only read
     if (init->ctx != c) return qk_fail(QK_EINVAL, "%s: the initial snapshot was built in another context", what);
@@ -1116,17 +895,17 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
     }
   }
   if (n_kgates > 0) {  // the channel table, the branch rows and the names of the trajectories
-    const size_t rows = cht.stride ? (size_t)n_states : 1;
+    const size_t rows = prog.branch_state_stride ? (size_t)n_states : 1;
     std::vector<uint32_t> sidx(n_states), traj(n_states, 0u);
-    for (int s = 0; s < n_states; ++s) sidx[s] = cht.state_index ? cht.state_index[s] : (uint32_t)s;
-    if (cht.trajectory) traj.assign(cht.trajectory, cht.trajectory + n_states);
-    HIP_TRY_AS(what, d_kraus.alloc(std::max<size_t>(1, cht.n_channels) * 16 * sizeof(cd)));
-    HIP_TRY_AS(what, d_nkraus.alloc(std::max<size_t>(1, cht.n_channels) * sizeof(int32_t)));
+    for (int s = 0; s < n_states; ++s) sidx[s] = prog.state_index ? prog.state_index[s] : (uint32_t)s;
+    if (prog.trajectory) traj.assign(prog.trajectory, prog.trajectory + n_states);
+    HIP_TRY_AS(what, d_kraus.alloc(std::max<size_t>(1, prog.n_channels) * 16 * sizeof(cd)));
+    HIP_TRY_AS(what, d_nkraus.alloc(std::max<size_t>(1, prog.n_channels) * sizeof(int32_t)));
     if (with_k2) {
-      HIP_TRY_AS(what, d_kraus2.alloc((size_t)cht.n_channels2 * 256 * sizeof(cd)));
-      HIP_TRY_AS(what, d_nkraus2.alloc((size_t)cht.n_channels2 * sizeof(int32_t)));
-      HIP_TRY_AS(what, hipMemcpy(d_kraus2.get(), cht.kraus2, (size_t)cht.n_channels2 * 256 * sizeof(cd), hipMemcpyHostToDevice));
-      HIP_TRY_AS(what, hipMemcpy(d_nkraus2.get(), cht.n_kraus2, (size_t)cht.n_channels2 * sizeof(int32_t), hipMemcpyHostToDevice));
+      HIP_TRY_AS(what, d_kraus2.alloc((size_t)prog.n_channels2 * 256 * sizeof(cd)));
+      HIP_TRY_AS(what, d_nkraus2.alloc((size_t)prog.n_channels2 * sizeof(int32_t)));
+      HIP_TRY_AS(what, hipMemcpy(d_kraus2.get(), prog.kraus2, (size_t)prog.n_channels2 * 256 * sizeof(cd), hipMemcpyHostToDevice));
+      HIP_TRY_AS(what, hipMemcpy(d_nkraus2.get(), prog.n_kraus2, (size_t)prog.n_channels2 * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     HIP_TRY_AS(what, d_channel.alloc((size_t)n_ops * sizeof(int32_t)));
     HIP_TRY_AS(what, d_branch.alloc(rows * n_ops * sizeof(int32_t)));
@@ -1135,11 +914,11 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
     HIP_TRY_AS(what, d_traj.alloc((size_t)n_states * sizeof(uint32_t)));
     HIP_TRY_AS(what, d_bout.alloc((size_t)n_states * n_kgates));
     if (with_k1) {
-      HIP_TRY_AS(what, hipMemcpy(d_kraus.get(), cht.kraus, (size_t)cht.n_channels * 16 * sizeof(cd), hipMemcpyHostToDevice));
-      HIP_TRY_AS(what, hipMemcpy(d_nkraus.get(), cht.n_kraus, (size_t)cht.n_channels * sizeof(int32_t), hipMemcpyHostToDevice));
+      HIP_TRY_AS(what, hipMemcpy(d_kraus.get(), prog.kraus, (size_t)prog.n_channels * 16 * sizeof(cd), hipMemcpyHostToDevice));
+      HIP_TRY_AS(what, hipMemcpy(d_nkraus.get(), prog.n_kraus, (size_t)prog.n_channels * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    HIP_TRY_AS(what, hipMemcpy(d_channel.get(), cht.channel, (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY_AS(what, hipMemcpy(d_branch.get(), cht.branch, rows * n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_channel.get(), prog.channel, (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_branch.get(), prog.branch, rows * n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
     HIP_TRY_AS(what, hipMemcpy(d_kgate.get(), kgate.data(), (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
     HIP_TRY_AS(what, hipMemcpy(d_sidx.get(), sidx.data(), (size_t)n_states * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY_AS(what, hipMemcpy(d_traj.get(), traj.data(), (size_t)n_states * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -1150,29 +929,29 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
     ca.kraus = d_kraus.get<cd>(), ca.n_kraus = d_nkraus.get<int32_t>(), ca.channel = d_channel.get<int32_t>(), ca.branch = d_branch.get<int32_t>();
     ca.cond_col = nullptr, ca.cond_mask = nullptr;
     bool conditional = false;
-    for (int i = 0; cht.cond_gate && i < n_ops; ++i) conditional = conditional || cht.cond_gate[i] >= 0;
+    for (int i = 0; prog.cond_gate && i < n_ops; ++i) conditional = conditional || prog.cond_gate[i] >= 0;
     if (conditional) {  // rows whose gates are all unconditional are no rows: the kernel then does what it does without them
       std::vector<int32_t> ccol((size_t)n_ops);
-      for (int i = 0; i < n_ops; ++i) ccol[i] = cht.cond_gate[i] >= 0 ? kgate[cht.cond_gate[i]] : -1;
+      for (int i = 0; i < n_ops; ++i) ccol[i] = prog.cond_gate[i] >= 0 ? kgate[prog.cond_gate[i]] : -1;
       HIP_TRY_AS(what, d_ccol.alloc((size_t)n_ops * sizeof(int32_t)));
       HIP_TRY_AS(what, d_cmask.alloc((size_t)n_ops * sizeof(uint32_t)));
       HIP_TRY_AS(what, hipMemcpy(d_ccol.get(), ccol.data(), (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
-      HIP_TRY_AS(what, hipMemcpy(d_cmask.get(), cht.cond_mask, (size_t)n_ops * sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_TRY_AS(what, hipMemcpy(d_cmask.get(), prog.cond_mask, (size_t)n_ops * sizeof(uint32_t), hipMemcpyHostToDevice));
       ca.cond_col = d_ccol.get<int32_t>(), ca.cond_mask = d_cmask.get<uint32_t>();
     }
-    ca.kgate = d_kgate.get<int32_t>(), ca.branch_stride = cht.stride ? n_ops : 0, ca.n_kgates = n_kgates;
-    ca.seed_lo = (unsigned)cht.seed, ca.seed_hi = (unsigned)(cht.seed >> 32), ca.first_gate = cht.first_gate;
+    ca.kgate = d_kgate.get<int32_t>(), ca.branch_stride = prog.branch_state_stride ? n_ops : 0, ca.n_kgates = n_kgates;
+    ca.seed_lo = (unsigned)prog.seed, ca.seed_hi = (unsigned)(prog.seed >> 32), ca.first_gate = prog.first_gate;
     ca.state_index = d_sidx.get<uint32_t>(), ca.trajectory = d_traj.get<uint32_t>(), ca.branch_out = d_bout.get<int8_t>();
     ca.logw_out = d_logw.get<double>(), ca.init_logw = d_ilogw.get<double>();
     HIP_TRY_AS(what, d_chan.alloc(sizeof(ChanArgs)));
     HIP_TRY_AS(what, hipMemcpy(d_chan.get(), &ca, sizeof(ChanArgs), hipMemcpyHostToDevice));
   }
   if (n_tables) {
-    const size_t mats_bytes = (size_t)n_tables * tab.n_mats * 16 * sizeof(cd);
+    const size_t mats_bytes = (size_t)n_tables * prog.n_mats * 16 * sizeof(cd);
     HIP_TRY_AS(what, d_mats.alloc(mats_bytes));
     HIP_TRY_AS(what, d_mat.alloc((size_t)std::max(1, n_ops) * sizeof(int32_t)));
-    HIP_TRY_AS(what, hipMemcpy(d_mats.get(), tab.mats, mats_bytes, hipMemcpyHostToDevice));
-    if (n_ops > 0) HIP_TRY_AS(what, hipMemcpy(d_mat.get(), tab.mat, (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY_AS(what, hipMemcpy(d_mats.get(), prog.mats, mats_bytes, hipMemcpyHostToDevice));
+    if (n_ops > 0) HIP_TRY_AS(what, hipMemcpy(d_mat.get(), prog.mat, (size_t)n_ops * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   HIP_TRY_AS(what, d_ctr.alloc(2 * sizeof(unsigned long long)));
   HIP_TRY_AS(what, d_err.alloc(32 * sizeof(int)));
@@ -1205,7 +984,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   a.order = d_order.get<int32_t>();
   a.n_states = n_states, a.n_qubits = n_qubits, a.n_ops = n_ops, a.cap = cap;
   a.op = d_op.get<int8_t>(), a.q0 = d_q0.get<int32_t>(), a.alpha = d_alpha.get<double>();
-  a.mats = n_tables ? d_mats.get<cd>() : nullptr, a.mat = n_tables ? d_mat.get<int32_t>() : nullptr, a.mats_stride = n_tables > 1 ? tab.n_mats : 0;
+  a.mats = n_tables ? d_mats.get<cd>() : nullptr, a.mat = n_tables ? d_mat.get<int32_t>() : nullptr, a.mats_stride = n_tables > 1 ? prog.n_mats : 0;
   a.chan = n_kgates ? d_chan.get<ChanArgs>() : nullptr;
   a.budget = trunc_budget, a.zero = value_of_zero;
   a.arena = c->build_arena.get<cd>(), a.work = c->build_work.get<cd>(), a.heap = heap.get<cd>(), a.heap_cap = heap_cap;
@@ -1297,7 +1076,7 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
     if (err & ERR_OP) return qk_fail(QK_EINVAL, "%s: unknown gate op code (valid: 0..%d)", what, n_codes - 1);
     if (err & ERR_CHANNEL)
       return qk_fail(QK_EDEVICE, "%s: state %d (state_index %u), gate %u: the branch of the channel has probability 0 or one that is not finite (an impossible outcome was post-selected?)",
-                     what, errv[26] - 1, cht.state_index ? cht.state_index[std::max(0, errv[26] - 1)] : (uint32_t)std::max(0, errv[26] - 1), cht.first_gate + (unsigned)errv[27]);
+                     what, errv[26] - 1, prog.state_index ? prog.state_index[std::max(0, errv[26] - 1)] : (uint32_t)std::max(0, errv[26] - 1), prog.first_gate + (unsigned)errv[27]);
     if (err & ERR_GATE) return qk_fail(QK_EINVAL, "%s: gate on a qubit outside the register", what);
     if (err & ERR_BOND) return qk_fail(QK_EINVAL, "%s: a bond grew beyond max_bond = %d", what, cap);
     if (err & ERR_HEAP) return qk_fail(QK_EDEVICE, "%s: the packed states (%d snapshots each) need %llu complex numbers, the heap holds %zu", what, n_ckpt, ctr[1], heap_cap);
@@ -1314,6 +1093,116 @@ static int build_impl(const char* what, qk_ctx* c, int32_t n_states, int32_t n_q
   b->grid = (int32_t)grid, b->threads = bt, b->slots = (int32_t)std::min<long long>(INT32_MAX, (long long)wgs_per_cu * c->num_cus);
   *out = b.release();
   return QK_OK;
+}
+
+extern "C" uint32_t qk_program_size(void) { return (uint32_t)sizeof(qk_program); }
+extern "C" uint32_t qk_build_run_size(void) { return (uint32_t)sizeof(qk_build_run); }
+
+extern "C" int qk_build_program(qk_ctx* c, const qk_program* prog, const qk_build_run* run, qk_built** out) {
+  if (!prog || !run) return qk_fail(QK_EINVAL, "%s: null argument", what);
+  if (prog->size != sizeof(qk_program)) return qk_fail(QK_EINVAL, "%s: qk_program.size is %u, this library's is %zu", what, prog->size, sizeof(qk_program));
+  if (run->size != sizeof(qk_build_run)) return qk_fail(QK_EINVAL, "%s: qk_build_run.size is %u, this library's is %zu", what, run->size, sizeof(qk_build_run));
+  return build_impl(c, *prog, *run, out);
+}
+
+// ---- the entries from before qk_program: each fills the two structs, calls qk_build_program and puts its own name in front of an error
+static qk_program plain_program(int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha) {
+  qk_program p{};
+  p.size = sizeof p, p.n_states = n_states, p.n_qubits = n_qubits, p.n_ops = n_ops, p.op = op, p.q0 = q0, p.alpha = alpha;
+  return p;
+}
+
+static qk_build_run plain_run(double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags) {
+  qk_build_run r{};
+  r.size = sizeof r, r.trunc_budget = trunc_budget, r.value_of_zero = value_of_zero, r.max_bond = max_bond, r.flags = flags;
+  return r;
+}
+
+// plain_run with the checkpoints these entries insist on (a negative count is refused as "no checkpoints") and the snapshot to resume
+static qk_build_run scan_run(double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                             int32_t initial_snapshot) {
+  qk_build_run r = plain_run(trunc_budget, value_of_zero, max_bond, flags);
+  r.n_checkpoints = checkpoints && n_checkpoints >= 1 ? n_checkpoints : -1, r.checkpoints = checkpoints, r.initial = initial, r.initial_snapshot = initial_snapshot;
+  return r;
+}
+
+static void set_mats(qk_program& p, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat) {
+  p.n_mats = n_mats, p.mats = mats, p.mats_state_stride = mats_state_stride, p.mat = mat;
+}
+
+static void set_channels(qk_program& p, int32_t n_channels, const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride,
+                         uint64_t seed, const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate) {
+  p.n_channels = n_channels, p.kraus = kraus, p.n_kraus = n_kraus, p.channel = channel, p.branch = branch, p.branch_state_stride = branch_state_stride;
+  p.seed = seed, p.state_index = state_index, p.trajectory = trajectory, p.first_gate = first_gate;
+}
+
+static int as_entry(const char* name, int rc) {  // rc of qk_build_program, its message under the name of the entry the caller came through
+  const std::string msg = qk_last_error();
+  return rc != QK_OK && msg.rfind(what, 0) == 0 ? qk_fail(rc, "%s%s", name, msg.c_str() + std::strlen(what)) : rc;
+}
+
+extern "C" int qk_build_mps(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0,
+                            const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond, uint32_t flags, qk_built** out) {
+  const qk_program p = plain_program(n_states, n_qubits, n_ops, op, q0, alpha);
+  const qk_build_run r = plain_run(trunc_budget, value_of_zero, max_bond, flags);
+  return as_entry("qk_build_mps", qk_build_program(c, &p, &r, out));
+}
+
+extern "C" int qk_build_mps_scan(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                                 double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                                 int32_t initial_snapshot, qk_built** out) {
+  const qk_program p = plain_program(n_states, n_qubits, n_ops, op, q0, alpha);
+  const qk_build_run r = scan_run(trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot);
+  return as_entry("qk_build_mps_scan", qk_build_program(c, &p, &r, out));
+}
+
+extern "C" int qk_build_mps_gates(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                                  double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                                  int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, qk_built** out) {
+  qk_program p = plain_program(n_states, n_qubits, n_ops, op, q0, alpha);
+  set_mats(p, n_mats, mats, mats_state_stride, mat);
+  const qk_build_run r = scan_run(trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot);
+  return as_entry("qk_build_mps_gates", qk_build_program(c, &p, &r, out));
+}
+
+extern "C" int qk_build_mps_channels(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                                     double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                                     int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
+                                     const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
+                                     const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, qk_built** out) {
+  qk_program p = plain_program(n_states, n_qubits, n_ops, op, q0, alpha);
+  set_mats(p, n_mats, mats, mats_state_stride, mat);
+  set_channels(p, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate);
+  const qk_build_run r = scan_run(trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot);
+  return as_entry("qk_build_mps_channels", qk_build_program(c, &p, &r, out));
+}
+
+extern "C" int qk_build_mps_channels2(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                                      double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                                      int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
+                                      const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
+                                      const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const double* kraus2,
+                                      const int32_t* n_kraus2, qk_built** out) {
+  qk_program p = plain_program(n_states, n_qubits, n_ops, op, q0, alpha);
+  set_mats(p, n_mats, mats, mats_state_stride, mat);
+  set_channels(p, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate);
+  p.n_channels2 = n_channels2, p.kraus2 = kraus2, p.n_kraus2 = n_kraus2;
+  const qk_build_run r = scan_run(trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot);
+  return as_entry("qk_build_mps_channels2", qk_build_program(c, &p, &r, out));
+}
+
+extern "C" int qk_build_mps_conditions(qk_ctx* c, int32_t n_states, int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
+                                       double value_of_zero, int32_t max_bond, uint32_t flags, int32_t n_checkpoints, const int32_t* checkpoints, const qk_built* initial,
+                                       int32_t initial_snapshot, int32_t n_mats, const double* mats, int32_t mats_state_stride, const int32_t* mat, int32_t n_channels,
+                                       const double* kraus, const int32_t* n_kraus, const int32_t* channel, const int32_t* branch, int32_t branch_state_stride, uint64_t seed,
+                                       const uint32_t* state_index, const uint32_t* trajectory, uint32_t first_gate, int32_t n_channels2, const double* kraus2,
+                                       const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, qk_built** out) {
+  qk_program p = plain_program(n_states, n_qubits, n_ops, op, q0, alpha);
+  set_mats(p, n_mats, mats, mats_state_stride, mat);
+  set_channels(p, n_channels, kraus, n_kraus, channel, branch, branch_state_stride, seed, state_index, trajectory, first_gate);
+  p.n_channels2 = n_channels2, p.kraus2 = kraus2, p.n_kraus2 = n_kraus2, p.cond_gate = cond_gate, p.cond_mask = cond_mask;
+  const qk_build_run r = scan_run(trunc_budget, value_of_zero, max_bond, flags, n_checkpoints, checkpoints, initial, initial_snapshot);
+  return as_entry("qk_build_mps_conditions", qk_build_program(c, &p, &r, out));
 }
 
 extern "C" int qk_built_info(const qk_built* b, int32_t* dims, double* fidelity, int64_t* offsets, int64_t* total_complex, double* kernel_ms) {

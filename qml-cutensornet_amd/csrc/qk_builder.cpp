@@ -5,6 +5,9 @@
 // (symbols scipy_zgesdd_, scipy_zgeqrf_, scipy_zungqr_, scipy_zgemm_), resolved at run time with dlopen: the Python
 // side passes the library's path (qkb_init).  Reference semantics: gpu_backend/kernel_state_ansatz.py:141-144, 221
 // (MPSxGate, truncation_fidelity) and KernelPkg.jl:68 (cutoff).
+#include "qk_builder.h"
+#include "qk_program.h"
+
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -33,11 +36,6 @@ zgeqrf_t p_zgeqrf = nullptr;
 zungqr_t p_zungqr = nullptr;
 zgemm_t p_zgemm = nullptr;
 
-// ansatz.py.  Codes 8 and 9 are the matrix gates: valid only in a program that comes with a matrix table (N_OPS_MAT codes then).
-// Code 10 is the one-qubit Kraus channel: valid only in a program that comes with a channel table; code 11 the two-qubit Kraus
-// channel on (q0, q0+1): valid only in a program that comes with a two-qubit channel table.
-enum { OP_H = 0, OP_RZ = 1, OP_XX = 2, OP_SWAP = 3, OP_RX = 4, OP_RY = 5, OP_YY = 6, OP_ZZ = 7, N_OPS = 8, OP_M1 = 8, OP_M2 = 9, N_OPS_MAT = 10, OP_K1 = 10, OP_K2 = 11 };
-
 inline bool is_two_qubit(int o) { return o == OP_XX || o == OP_SWAP || o == OP_YY || o == OP_ZZ || o == OP_M2 || o == OP_K2; }
 
 // sum_s m[s] t[s] over n terms in the fixed order of the matrix gates: column 0 first, ascending, the real and the imaginary part
@@ -55,50 +53,6 @@ inline cd mat_dot(const cd* m, const cd* t, int n) {
   return cd(re, im);
 }
 
-// The matrix table of a program: every matrix gate's index inside 0..n_mats-1, its 2x2 ([:2][:2] of the slot) or 4x4 finite and
-// unitary, max |M^H M - 1| <= 1e-12 (the canonical-form bookkeeping assumes unitary gates).  Empty string, or what is wrong.
-std::string check_table(int n_ops, const int8_t* op, int n_mats, const cd* mats, const int32_t* mat) {
-  for (int i = 0; i < n_ops; ++i) {
-    if (op[i] != OP_M1 && op[i] != OP_M2) continue;
-    const int k = mat[i], d = op[i] == OP_M1 ? 2 : 4;
-    if (k < 0 || k >= n_mats) return "gate " + std::to_string(i) + ": matrix index " + std::to_string(k) + " outside 0.." + std::to_string(n_mats - 1);
-    const cd* m = mats + (size_t)k * 16;
-    double dev = 0;
-    bool finite = true;
-    for (int a = 0; a < d; ++a)
-      for (int b = 0; b < d; ++b) {
-        finite = finite && std::isfinite(m[a * 4 + b].real()) && std::isfinite(m[a * 4 + b].imag());
-        cd g = (a == b) ? cd(-1, 0) : cd(0, 0);
-        for (int r = 0; r < d; ++r) g += std::conj(m[r * 4 + a]) * m[r * 4 + b];
-        dev = std::max(dev, std::abs(g));
-      }
-    if (!finite || !(dev <= 1e-12))
-      return "gate " + std::to_string(i) + ": the matrix of table entry " + std::to_string(k) + (finite ? " is not unitary (max |M^H M - 1| > 1e-12)" : " has an entry that is not finite");
-  }
-  return "";
-}
-
-// The channel tables of a program and the names of one trajectory (qkb_simulate_channels2); n_channels = 0: no one-qubit table, code 10
-// is unknown; n_channels2 = 0: no two-qubit table, code 11 is unknown.
-struct Channels {
-  int n_channels = 0;
-  const cd* kraus = nullptr;        // [n_channels][4][2][2], K[s'][s]
-  const int32_t* n_kraus = nullptr; // [n_channels] 1..4
-  int n_channels2 = 0;
-  const cd* kraus2 = nullptr;        // [n_channels2][16][4][4], K[(p,p')][(s,s')], qubit q0 most significant
-  const int32_t* n_kraus2 = nullptr; // [n_channels2] 1..16
-  const int32_t* channel = nullptr; // [n_ops], read where op is 10 (index into kraus) or 11 (into kraus2)
-  const int32_t* branch = nullptr;  // [n_ops] -1: drawn, k: forced
-  uint64_t seed = 0;
-  uint32_t state_index = 0, trajectory = 0, first_gate = 0;
-  double* logw_out = nullptr;
-  int8_t* branches_out = nullptr;   // [channel gates of the program, codes 10 and 11 in program order]
-  double* margin_out = nullptr;
-  const int32_t* cond_gate = nullptr;  // [n_ops] -1: unconditional; g < i: the channel gate whose branch decides (qkb_simulate_conditions)
-  const uint32_t* cond_mask = nullptr; // [n_ops] bit v: branch v of gate cond_gate[i] lets gate i run
-  bool any() const { return n_channels > 0 || n_channels2 > 0; }
-};
-
 // Philox4x32-10 and the uniform of its first two words, written out as in qk_local_plan.h (smp_philox, smp_uniform) and
 // engine.philox4x32: counter (gate, trajectory, state, 2), key = the two halves of the seed.
 double channel_uniform(uint64_t seed, uint32_t gate, uint32_t trajectory, uint32_t state) {
@@ -112,69 +66,22 @@ double channel_uniform(uint64_t seed, uint32_t gate, uint32_t trajectory, uint32
   return (double)(((uint64_t)(c0 >> 5) << 26) + (uint64_t)(c1 >> 6)) * (1.0 / 9007199254740992.0);
 }
 
-// The channel gates of a program, checked before anything runs: the channel inside its table, 1..4 matrices (1..16 for the two-qubit
-// channel of code 11), finite entries, the branch inside -1..m-1, a drawn channel trace preserving to 1e-12, the qubit (pair) inside
-// the register.  Empty string, or what is wrong.
-std::string check_channels(int n_qubits, int n_ops, const int8_t* op, const int32_t* q0, const Channels& ch) {
-  for (int i = 0; i < n_ops; ++i) {
-    if (op[i] != OP_K1 && op[i] != OP_K2) continue;
-    const bool two = op[i] == OP_K2;
-    const int d = two ? 4 : 2, n_table = two ? ch.n_channels2 : ch.n_channels;  // d x d matrices, at most d * d of them
-    const std::string at = "gate " + std::to_string(i) + ": ", kind = two ? "two-qubit channel " : "channel ";
-    const int c = ch.channel[i], b = ch.branch[i];
-    if (c < 0 || c >= n_table) return at + kind + "index " + std::to_string(c) + " outside 0.." + std::to_string(n_table - 1);
-    const int m = (two ? ch.n_kraus2 : ch.n_kraus)[c];
-    if (m < 1 || m > d * d) return at + kind + std::to_string(c) + " has " + std::to_string(m) + " Kraus matrices (1.." + std::to_string(d * d) + ")";
-    const cd* K = (two ? ch.kraus2 : ch.kraus) + (size_t)c * d * d * d * d;
-    for (int e = 0; e < d * d * m; ++e)
-      if (!std::isfinite(K[e].real()) || !std::isfinite(K[e].imag())) return at + "a Kraus matrix of " + kind + std::to_string(c) + " has an entry that is not finite";
-    if (b < -1 || b >= m) return at + "branch " + std::to_string(b) + " outside -1.." + std::to_string(m - 1);
-    if (b < 0) {
-      double dev = 0;
-      for (int a = 0; a < d; ++a)
-        for (int e = 0; e < d; ++e) {
-          cd g = (a == e) ? cd(-1, 0) : cd(0, 0);
-          for (int k = 0; k < m; ++k)
-            for (int r = 0; r < d; ++r) g += std::conj(K[(k * d + r) * d + a]) * K[(k * d + r) * d + e];
-          dev = std::max(dev, std::abs(g));
-        }
-      if (!(dev <= 1e-12)) return at + "the drawn " + kind + std::to_string(c) + " is not trace preserving (max |sum K^H K - 1| > 1e-12)";
-    }
-    if (q0[i] < 0 || q0[i] + (two ? 1 : 0) >= n_qubits) return at + kind + "on a qubit outside the register";
-  }
-  return "";
-}
-
-// The condition rows of a program, checked before anything runs: cond_gate[i] inside -1 .. i-1, the gate it names of code 10 or 11, no
-// mask bit at or above the number of Kraus matrices of that gate's channel (check_channels has passed: the channel is valid).
-std::string check_conditions(int n_ops, const int8_t* op, const Channels& ch) {
-  for (int i = 0; i < n_ops; ++i) {
-    const int g = ch.cond_gate[i];
-    if (g == -1) continue;
-    const std::string at = "gate " + std::to_string(i) + ": ";
-    if (g < -1 || g >= i) return at + "condition on gate " + std::to_string(g) + " outside -1.." + std::to_string(i - 1);
-    if (op[g] != OP_K1 && op[g] != OP_K2) return at + "condition on gate " + std::to_string(g) + ", which is no channel gate (op code " + std::to_string((int)op[g]) + ")";
-    const int m = (op[g] == OP_K2 ? ch.n_kraus2 : ch.n_kraus)[ch.channel[g]];
-    if (m < 32 && (ch.cond_mask[i] >> m) != 0u) return at + "condition mask names a branch at or above the " + std::to_string(m) + " of gate " + std::to_string(g);
-  }
-  return "";
-}
-
 // The branch of channel gate i with the probabilities p[m] (tot = p_0 + .. in ascending order): the forced one, or drawn: the first k
 // with p_k > 0 and u tot < p_0 + .. + p_k, else the last k with p_k > 0, u the uniform of counter (first_gate + i, trajectory,
 // state_index, 2); `margin` takes the smallest |u tot - cum| / tot over the thresholds.  -1 with g_err set when the outcome is
 // impossible: tot 0 or not finite in a draw, p_b 0 or not finite.
-int channel_branch(const Channels& ch, int i, int forced, int m, const double* p, double* margin) {
+int channel_branch(const qk_program& prog, int i, int forced, int m, const double* p, double* margin) {
   double tot = 0;
   for (int k = 0; k < m; ++k) tot += p[k];
-  const auto at = [&] { return "state " + std::to_string(ch.state_index) + ", gate " + std::to_string(ch.first_gate + (uint32_t)i) + ": "; };  // error paths only
+  const uint32_t state = prog.state_index ? prog.state_index[0] : 0u, trajectory = prog.trajectory ? prog.trajectory[0] : 0u;
+  const auto at = [&] { return "state " + std::to_string(state) + ", gate " + std::to_string(prog.first_gate + (uint32_t)i) + ": "; };  // error paths only
   int b = forced;
   if (forced < 0) {
     if (!(tot > 0.0) || !std::isfinite(tot)) {
       g_err = at() + "the branch probabilities of the channel sum to 0 or are not finite";
       return -1;
     }
-    const double u = channel_uniform(ch.seed, ch.first_gate + (uint32_t)i, ch.trajectory, ch.state_index);
+    const double u = channel_uniform(prog.seed, prog.first_gate + (uint32_t)i, trajectory, state);
     double cum = 0;
     int last = -1;
     for (int k = 0; k < m; ++k) {
@@ -199,17 +106,6 @@ void gemm_rm(int m, int n, int k, const cd* A, const cd* B, cd* C) {
   const cd one(1.0, 0.0), zero(0.0, 0.0);
   p_zgemm("N", "N", &n, &m, &k, &one, B, &n, A, &k, &zero, C, &n);
 }
-
-// The state a run starts from instead of |0...0> (qkb_simulate_initial): already canonical with the centre on `centre`, validated by
-// the entry.  It reaches simulate_impl through t_initial, set for the duration of one call on the calling thread: the entries between
-// the two keep their signatures.
-struct Initial {
-  const int32_t* dims = nullptr;  // [n_qubits + 1]
-  const cd* tensors = nullptr;    // the sites [l][2][r] row-major, back to back
-  int centre = 0;
-  double fidelity = 1.0, logw = 0.0;
-};
-thread_local const Initial* t_initial = nullptr;
 
 struct Tensor {  // [l][2][r], row-major
   int l = 1, r = 1;
@@ -298,229 +194,78 @@ int qkb_init(const char* openblas_path) {
   return 0;
 }
 
-// MPS of circuit |0...0>.  op/q0/alpha: the bound gate program (ansatz.py: BoundCircuit).  On success fills
-// dims_out[n_qubits + 1] and *tensors_out: ONE malloc'd block holding the site tensors back to back, complex128
-// [l][2][r] row-major (free it with qkb_free), and *fidelity.  Returns 0, or a negative code with qkb_last_error().
-// Op codes: 0 H, 1 Rz, 2 XXPhase, 3 SWAP, 4 Rx, 5 Ry, 6 YYPhase, 7 ZZPhase (two-qubit gates on (q0, q0+1)); any other
-// code fails the call with -7 before a gate is applied.
-int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                       int32_t max_bond, int32_t n_mats, const double* mats, const int32_t* mat, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out,
-                       double* fidelity_out);
-static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                         int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, const Channels& ch, int32_t* dims_out, double** tensors_out,
-                         int64_t* n_complex_out, double* fidelity_out);
-int qkb_simulate(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                 double value_of_zero, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out, double* fidelity_out) {
-  return qkb_simulate_gates(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, 0, 0, nullptr, nullptr, dims_out, tensors_out, n_complex_out, fidelity_out);
+uint32_t qkb_program_size(void) { return (uint32_t)sizeof(qk_program); }
+uint32_t qkb_run_size(void) { return (uint32_t)sizeof(qkb_run); }
+uint32_t qkb_result_size(void) { return (uint32_t)sizeof(qkb_result); }
+
+static int simulate_impl(const qk_program& prog, const qkb_run& run, qkb_result* res);
+
+// -8 with g_err set, for the checks in front of simulate_impl
+static int refuse(const std::string& why) {
+  g_err = why;
+  return -8;
 }
-// max_bond > 0: at most that many singular values survive a gate (the chi of pytket-cutensornet's Config, reference
-// gpu_backend/kernel_state_ansatz.py:141-144); the lost weight goes into the fidelity like any other truncation.
-int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget,
-                     double value_of_zero, int32_t max_bond, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out, double* fidelity_out) {
-  return qkb_simulate_gates(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, 0, nullptr, nullptr, dims_out, tensors_out, n_complex_out, fidelity_out);
-}
-// qkb_simulate_chi with a matrix table: with n_mats > 0 the program may also hold op codes 8 (a 2x2 on q0) and 9 (a 4x4 on (q0, q0+1),
-// index (s_q0, s_q0+1), q0 most significant); the matrix of gate i is mats[mat[i]], complex128 [n_mats][4][4] row-major (re, im), a 2x2 in
-// [:2][:2]; alpha[i] is ignored there, mat[i] is read at those codes only.  new[(p,p')] = sum M[(p,p')][(s,s')] old[(s,s')].  A mat[i] outside
-// 0..n_mats-1 or a matrix that is not finite and unitary to 1e-12 fails the call with -8 before a gate is applied; with n_mats = 0
-// codes 8 and 9 are unknown (-7).
-int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                       int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out,
-                       double* fidelity_out) {
-  return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, Channels{}, dims_out, tensors_out, n_complex_out, fidelity_out);
-}
-// qkb_simulate_gates with a channel table: with n_channels > 0 the program may also hold op code 10, a one-qubit Kraus channel on q0.
-// Channel c is n_kraus[c] (1..4) matrices kraus[c][k][s'][s] (complex128 [n_channels][4][2][2], (re, im)); gate i reads channel
-// channel[i] and draws its branch (branch[i] = -1) or takes branch[i]; alpha[i] and mat[i] are ignored there.  The step: the centre
-// is brought onto q exactly, N = sum |A_q|^2, p_k = sum |K_k A_q|^2 and tot = p_0 + .. in ascending order of elements and of k; drawn:
-// u = uniform of Philox counter (first_gate + i, trajectory, state_index, 2) and key (seed), b the first k with p_k > 0 and
-// u tot < p_0 + .. + p_k, else the last k with p_k > 0; A_q <- (K_b / sqrt(p_b)) A_q; logw += log(p_b / N).  *logw_out, branches_out
-// [channel gates] and *margin_out (the smallest |u tot - cum| / tot over the thresholds of all draws, inf without one) may be null.
-// -8 before a gate is applied for a bad channel gate (check_channels); -9 when p_b is 0 or not finite or tot is 0 in a draw, naming
-// the state and the gate.  With n_channels = 0 the call IS qkb_simulate_gates.
-int qkb_simulate_channels(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                          int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
-                          const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate, int32_t* dims_out,
-                          double** tensors_out, int64_t* n_complex_out, double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out) {
-  Channels ch;
-  if (n_channels < 0 || (n_channels > 0 && (!kraus || !n_kraus || !channel || !branch))) {
-    g_err = "a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch";
-    return -8;
-  }
-  if (n_channels > 0) {
-    ch.n_channels = n_channels, ch.kraus = reinterpret_cast<const cd*>(kraus), ch.n_kraus = n_kraus, ch.channel = channel, ch.branch = branch;
-    ch.seed = seed, ch.state_index = state_index, ch.trajectory = trajectory, ch.first_gate = first_gate;
-  }
-  ch.logw_out = logw_out, ch.branches_out = branches_out, ch.margin_out = margin_out;
-  return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, ch, dims_out, tensors_out, n_complex_out, fidelity_out);
-}
-// qkb_simulate_channels with a two-qubit channel table: with n_channels2 > 0 the program may also hold op code 11, a two-qubit Kraus
-// channel on (q0, q0+1).  Channel c is n_kraus2[c] (1..16) matrices kraus2[c][k][(p,p')][(s,s')] (complex128 [n_channels2][16][4][4],
-// (re, im); the index convention of the 4x4 matrix gates, q0 most significant); gate i reads channel[i] -- an index into kraus2 where
-// op is 11 -- and branch[i].  The step: the centre is brought onto the pair and theta = A_q A_q+1 formed as for any two-qubit gate;
-// N = sum |theta|^2, p_k = sum_{a,c} |K_k theta[a,(.,.),c]|^2 in ascending order of (a, c), the branch as for code 10 (same uniform);
-// theta <- (K_b / sqrt(p_b)) theta, then the SVD, truncation, fidelity product and centre placement of a two-qubit gate; logw +=
-// log(p_b / N).  branches_out counts the gates of codes 10 and 11 together in program order.  Errors as qkb_simulate_channels.  Either
-// table may be absent; with n_channels2 = 0 the call IS qkb_simulate_channels.
-int qkb_simulate_channels2(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                           int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
-                           const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate,
-                           int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out,
-                           double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out) {
-  if (n_channels2 == 0)
-    return qkb_simulate_channels(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, n_channels, kraus, n_kraus, channel, branch, seed,
-                                 state_index, trajectory, first_gate, dims_out, tensors_out, n_complex_out, fidelity_out, logw_out, branches_out, margin_out);
-  Channels ch;
-  if (n_channels < 0 || n_channels2 < 0 || !kraus2 || !n_kraus2 || !channel || !branch || (n_channels > 0 && (!kraus || !n_kraus))) {
-    g_err = "a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch; a two-qubit one n_channels2 >= 0, kraus2 and n_kraus2";
-    return -8;
-  }
-  if (n_channels > 0) ch.n_channels = n_channels, ch.kraus = reinterpret_cast<const cd*>(kraus), ch.n_kraus = n_kraus;
-  ch.n_channels2 = n_channels2, ch.kraus2 = reinterpret_cast<const cd*>(kraus2), ch.n_kraus2 = n_kraus2, ch.channel = channel, ch.branch = branch;
-  ch.seed = seed, ch.state_index = state_index, ch.trajectory = trajectory, ch.first_gate = first_gate;
-  ch.logw_out = logw_out, ch.branches_out = branches_out, ch.margin_out = margin_out;
-  return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, ch, dims_out, tensors_out, n_complex_out, fidelity_out);
-}
-// qkb_simulate_channels2 with condition rows: gate i with cond_gate[i] = g >= 0 (g < i, a gate of op code 10 or 11 of this program) runs
-// when the branch b recorded for gate g is >= 0 and bit b of cond_mask[i] is set; else it is skipped: no centre move, no theta, no SVD,
-// no change of a bond, of the fidelity or of logw, no draw, no contribution to the margin; a skipped channel gate records branch -2 (a
-// condition on it is false).  The look-ahead that places the centre behind a two-qubit gate counts skipped gates as present.  -8
-// before a gate is applied, naming the gate, for rows without a channel table, cond_gate[i] outside -1 .. i-1, a gate named that is
-// not of code 10 or 11, a mask bit at or above the number of that gate's Kraus matrices, cond_mask null.  With cond_gate null the
-// call IS qkb_simulate_channels2.
-int qkb_simulate_conditions(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                            int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
-                            const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate,
-                            int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, int32_t* dims_out,
-                            double** tensors_out, int64_t* n_complex_out, double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out) {
-  if (!cond_gate)
-    return qkb_simulate_channels2(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, n_channels, kraus, n_kraus, channel, branch, seed,
-                                  state_index, trajectory, first_gate, n_channels2, kraus2, n_kraus2, dims_out, tensors_out, n_complex_out, fidelity_out, logw_out, branches_out,
-                                  margin_out);
-  if (!cond_mask) {
-    g_err = "condition rows need cond_gate and cond_mask";
-    return -8;
-  }
-  if (n_channels <= 0 && n_channels2 <= 0) {
-    g_err = "gate 0: condition rows need a program with a channel table";
-    return -8;
-  }
-  Channels ch;
-  if ((n_channels > 0 && (!kraus || !n_kraus)) || (n_channels2 > 0 && (!kraus2 || !n_kraus2)) || !channel || !branch) {
-    g_err = "a channel table needs n_channels >= 0, kraus, n_kraus, channel and branch; a two-qubit one n_channels2 >= 0, kraus2 and n_kraus2";
-    return -8;
-  }
-  if (n_channels > 0) ch.n_channels = n_channels, ch.kraus = reinterpret_cast<const cd*>(kraus), ch.n_kraus = n_kraus;
-  if (n_channels2 > 0) ch.n_channels2 = n_channels2, ch.kraus2 = reinterpret_cast<const cd*>(kraus2), ch.n_kraus2 = n_kraus2;
-  ch.channel = channel, ch.branch = branch, ch.cond_gate = cond_gate, ch.cond_mask = cond_mask;
-  ch.seed = seed, ch.state_index = state_index, ch.trajectory = trajectory, ch.first_gate = first_gate;
-  ch.logw_out = logw_out, ch.branches_out = branches_out, ch.margin_out = margin_out;
-  return simulate_impl(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, ch, dims_out, tensors_out, n_complex_out, fidelity_out);
-}
-// qkb_simulate_conditions from a given state: init_dims [n_qubits + 1] and init_tensors (the sites [l][2][r] complex128 row-major, back to
-// back) replace |0...0>; the state is taken as it stands -- canonical with its orthogonality centre on init_centre -- and the run begins
-// with init_fidelity and init_logw.  -8 before a gate is applied for a bond table that does not chain (dims[0] != 1, dims[n] != 1, an
-// entry that is not positive), a centre outside the register, or an entry (tensor, fidelity, log-weight) that is not finite.  With
-// init_dims null the call IS qkb_simulate_conditions.
-int qkb_simulate_initial(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                         int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
-                         const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate,
-                         int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, const int32_t* init_dims,
-                         const double* init_tensors, int32_t init_centre, double init_fidelity, double init_logw, int32_t* dims_out, double** tensors_out,
-                         int64_t* n_complex_out, double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out) {
-  Initial init;
-  if (init_dims) {
-    if (!init_tensors || n_qubits < 1) {
-      g_err = "an initial state needs init_dims and init_tensors";
-      return -8;
-    }
-    if (init_dims[0] != 1 || init_dims[n_qubits] != 1) {
-      g_err = "the initial state's boundary bonds must be 1";
-      return -8;
-    }
+
+int qkb_simulate_program(const qk_program* program, const qkb_run* run, qkb_result* res) {
+  if (!program || !run || !res) return refuse("qkb_simulate_program: null argument");
+  if (program->size != sizeof(qk_program) || run->size != sizeof(qkb_run) || res->size != sizeof(qkb_result))
+    return refuse("qkb_simulate_program: the sizes of qk_program, qkb_run, qkb_result are " + std::to_string(program->size) + ", " + std::to_string(run->size) + ", " +
+                  std::to_string(res->size) + ", this library's are " + std::to_string(sizeof(qk_program)) + ", " + std::to_string(sizeof(qkb_run)) + ", " + std::to_string(sizeof(qkb_result)));
+  const qk_program& p = *program;
+  if (p.n_states != 1 || p.n_qubits < 1 || p.n_ops < 0 || !res->dims || (p.n_ops > 0 && (!p.op || !p.q0 || !p.alpha)))
+    return refuse("qkb_simulate_program: one state of at least one qubit, with op, q0, alpha and dims");
+  if (run->init_dims) {
+    const int n = p.n_qubits;
+    if (!run->init_tensors) return refuse("an initial state needs init_dims and init_tensors");
+    if (run->init_dims[0] != 1 || run->init_dims[n] != 1) return refuse("the initial state's boundary bonds must be 1");
     size_t total = 0;
-    for (int k = 0; k <= n_qubits; ++k) {
-      if (init_dims[k] <= 0) {
-        g_err = "the initial state's bond " + std::to_string(k) + " is " + std::to_string((int)init_dims[k]) + ": bonds must be positive";
-        return -8;
-      }
-      if (k < n_qubits) total += (size_t)init_dims[k] * 2 * (size_t)std::max(init_dims[k + 1], 0);
+    for (int k = 0; k <= n; ++k) {
+      if (run->init_dims[k] <= 0) return refuse("the initial state's bond " + std::to_string(k) + " is " + std::to_string((int)run->init_dims[k]) + ": bonds must be positive");
+      if (k < n) total += (size_t)run->init_dims[k] * 2 * (size_t)std::max(run->init_dims[k + 1], 0);
     }
-    if (init_centre < 0 || init_centre >= n_qubits) {
-      g_err = "the initial state's centre " + std::to_string((int)init_centre) + " lies outside the register of " + std::to_string((int)n_qubits);
-      return -8;
-    }
+    if (run->init_centre < 0 || run->init_centre >= n)
+      return refuse("the initial state's centre " + std::to_string((int)run->init_centre) + " lies outside the register of " + std::to_string(n));
     for (size_t e = 0; e < 2 * total; ++e)
-      if (!std::isfinite(init_tensors[e])) {
-        g_err = "the initial state has an entry that is not finite";
-        return -8;
-      }
-    if (!std::isfinite(init_fidelity) || !std::isfinite(init_logw)) {
-      g_err = "the initial state's fidelity or log-weight is not finite";
-      return -8;
-    }
-    init.dims = init_dims, init.tensors = reinterpret_cast<const cd*>(init_tensors), init.centre = init_centre, init.fidelity = init_fidelity, init.logw = init_logw;
-    t_initial = &init;
+      if (!std::isfinite(run->init_tensors[e])) return refuse("the initial state has an entry that is not finite");
+    if (!std::isfinite(run->init_fidelity) || !std::isfinite(run->init_logw)) return refuse("the initial state's fidelity or log-weight is not finite");
   }
-  const int rc = qkb_simulate_conditions(n_qubits, n_ops, op, q0, alpha, trunc_budget, value_of_zero, max_bond, n_mats, mats_raw, mat, n_channels, kraus, n_kraus, channel, branch, seed,
-                                         state_index, trajectory, first_gate, n_channels2, kraus2, n_kraus2, cond_gate, cond_mask, dims_out, tensors_out, n_complex_out, fidelity_out,
-                                         logw_out, branches_out, margin_out);
-  t_initial = nullptr;
-  return rc;
+  std::string wrong;
+  if (!qk_program_check_tables(p, &wrong)) return refuse(wrong);
+  return simulate_impl(p, *run, res);
 }
 }  // extern "C"
 
-static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                         int32_t max_bond, int32_t n_mats, const double* mats_raw, const int32_t* mat, const Channels& ch, int32_t* dims_out, double** tensors_out,
-                         int64_t* n_complex_out, double* fidelity_out) {
+// the gates of `prog` (its tables are there: qkb_simulate_program) on |0...0>, or on the initial state of `run`, which is valid
+static int simulate_impl(const qk_program& prog, const qkb_run& run, qkb_result* res) {
   if (!p_zgesdd) {
     g_err = "qkb_init has not been called";
     return -1;
   }
-  const int n = n_qubits;
-  const cd* mats = reinterpret_cast<const cd*>(mats_raw);
-  if (n_mats < 0 || (n_mats > 0 && (!mats || !mat))) {
-    g_err = "a matrix table needs n_mats >= 0, mats and mat";
-    return -8;
-  }
-  const int n_codes = n_mats > 0 ? N_OPS_MAT : N_OPS;
-  for (int i = 0; i < n_ops; ++i)
-    if ((op[i] < 0 || op[i] >= n_codes) && !(ch.n_channels > 0 && op[i] == OP_K1) && !(ch.n_channels2 > 0 && op[i] == OP_K2)) {
-      g_err = "unknown gate op code " + std::to_string((int)op[i]) + " (valid: 0.." + std::to_string(n_codes - 1) + (ch.n_channels > 0 ? ", 10" : "") + (ch.n_channels2 > 0 ? ", 11)" : ")");
-      return -7;
-    }
-  if (n_mats > 0) {
-    g_err = check_table(n_ops, op, n_mats, mats, mat);
-    if (!g_err.empty()) return -8;
-  }
-  if (ch.any()) {
-    g_err = check_channels(n, n_ops, op, q0, ch);
-    if (!g_err.empty()) return -8;
-    if (ch.cond_gate) {
-      g_err = check_conditions(n_ops, op, ch);
-      if (!g_err.empty()) return -8;
-    }
-  }
+  const int n = prog.n_qubits, n_ops = prog.n_ops;
+  const int8_t* const op = prog.op;
+  const int32_t *const q0 = prog.q0, *const mat = prog.mat;
+  const double* const alpha = prog.alpha;
+  const cd* const mats = reinterpret_cast<const cd*>(prog.mats);
+  if (const int bad = qk_program_check(prog, &g_err)) return bad == QK_PROGRAM_UNKNOWN_OP ? -7 : bad == QK_PROGRAM_MATRIX_GATE_OUTSIDE ? -3 : -8;
   double logw = 0.0, margin = INFINITY;
-  int n_drawn = 0;  // channel gates done: the index into branches_out
-  std::vector<int> taken(ch.cond_gate ? n_ops : 0, -1);  // the branch every channel gate of this state took (-2: skipped), by position
+  int n_drawn = 0;  // channel gates done: the index into res->branches
+  std::vector<int> taken(prog.cond_gate ? n_ops : 0, -1);  // the branch every channel gate of this state took (-2: skipped), by position
   std::vector<Tensor> A(n);
   for (auto& t : A) t.v = {cd(1, 0), cd(0, 0)};
-  const Initial* const init = t_initial;
   std::vector<int> two_q_pos;
   for (int i = 0; i < n_ops; ++i)
     if (is_two_qubit(op[i])) two_q_pos.push_back(q0[i]);
   double fidelity = 1.0;
   int centre = 0;  // sites < centre are left-orthonormal, sites > centre right-orthonormal
-  if (init) {  // the run goes on from a given state: its sites, centre, fidelity and log-weight
-    const cd* src = init->tensors;
+  if (run.init_dims) {  // the run goes on from a given state: its sites, centre, fidelity and log-weight
+    const cd* src = reinterpret_cast<const cd*>(run.init_tensors);
     for (int k = 0; k < n; ++k) {
-      A[k].l = init->dims[k], A[k].r = init->dims[k + 1];
+      A[k].l = run.init_dims[k], A[k].r = run.init_dims[k + 1];
       const size_t cnt = (size_t)A[k].l * 2 * A[k].r;
       A[k].v.assign(src, src + cnt);
       src += cnt;
     }
-    centre = init->centre, fidelity = init->fidelity, logw = init->logw;
+    centre = run.init_centre, fidelity = run.init_fidelity, logw = run.init_logw;
   }
   size_t g2 = 0;
   std::vector<cd> Q, R, work, cm, theta, U, VT, tmp;
@@ -534,12 +279,12 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
       g_err = "gate on a qubit outside the register";
       return -3;
     }
-    if (ch.cond_gate && ch.cond_gate[i] >= 0) {  // a gate whose condition is false does nothing at all; it is a done gate all the same
-      const int b = taken[ch.cond_gate[i]];
-      if (b < 0 || !((ch.cond_mask[i] >> b) & 1u)) {
+    if (prog.cond_gate && prog.cond_gate[i] >= 0) {  // a gate whose condition is false does nothing at all; it is a done gate all the same
+      const int b = taken[prog.cond_gate[i]];
+      if (b < 0 || !((prog.cond_mask[i] >> b) & 1u)) {
         if (o == OP_K1 || o == OP_K2) {
           taken[i] = -2;
-          if (ch.branches_out) ch.branches_out[n_drawn] = -2;
+          if (res->branches) res->branches[n_drawn] = -2;
           ++n_drawn;
         }
         g2 += is_two_qubit(o);  // the look-ahead is a function of the op codes alone
@@ -637,8 +382,8 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
       --centre;
     }
     if (o == OP_K1) {  // the channel step: the centre stays on q, the bonds do not change
-      const int c = ch.channel[i], forced = ch.branch[i], m = ch.n_kraus[c];
-      const cd* K = ch.kraus + (size_t)c * 16;
+      const int c = prog.channel[i], forced = prog.branch[i], m = prog.n_kraus[c];
+      const cd* K = reinterpret_cast<const cd*>(prog.kraus) + (size_t)c * 16;
       Tensor& t = A[q];
       double N = 0, p[4] = {0, 0, 0, 0};
       for (int a = 0; a < t.l; ++a)  // every sum in ascending order of (a, c)
@@ -647,7 +392,7 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
           N += std::norm(v[0]) + std::norm(v[1]);
           for (int k = 0; k < m; ++k) p[k] += std::norm(mat_dot(K + k * 4, v, 2)) + std::norm(mat_dot(K + k * 4 + 2, v, 2));
         }
-      const int b = channel_branch(ch, i, forced, m, p, &margin);
+      const int b = channel_branch(prog, i, forced, m, p, &margin);
       if (b < 0) return -9;
       const double s = std::sqrt(p[b]);
       const cd Kb[4] = {K[b * 4] / s, K[b * 4 + 1] / s, K[b * 4 + 2] / s, K[b * 4 + 3] / s};
@@ -658,8 +403,8 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
           t.at(a, 1, x) = mat_dot(Kb + 2, v, 2);
         }
       logw += std::log(p[b] / N);
-      if (ch.branches_out) ch.branches_out[n_drawn] = (int8_t)b;
-      if (ch.cond_gate) taken[i] = b;
+      if (res->branches) res->branches[n_drawn] = (int8_t)b;
+      if (prog.cond_gate) taken[i] = b;
       ++n_drawn;
       continue;
     }
@@ -696,8 +441,8 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
           TH(a, 1, 1, c) *= phc;
         }
     } else if (o == OP_K2) {  // a two-qubit Kraus channel: code 10's branch logic on theta, then the SVD of any two-qubit gate
-      const int c = ch.channel[i], forced = ch.branch[i], nk = ch.n_kraus2[c];
-      const cd* K = ch.kraus2 + (size_t)c * 256;
+      const int c = prog.channel[i], forced = prog.branch[i], nk = prog.n_kraus2[c];
+      const cd* K = reinterpret_cast<const cd*>(prog.kraus2) + (size_t)c * 256;
       double N = 0, p[16] = {0};
       for (int a = 0; a < l; ++a)  // every sum in ascending order of (a, c)
         for (int x = 0; x < r; ++x) {
@@ -708,7 +453,7 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
             p[k] += std::norm(mat_dot(Kk, v, 4)) + std::norm(mat_dot(Kk + 4, v, 4)) + std::norm(mat_dot(Kk + 8, v, 4)) + std::norm(mat_dot(Kk + 12, v, 4));
           }
         }
-      const int b = channel_branch(ch, i, forced, nk, p, &margin);
+      const int b = channel_branch(prog, i, forced, nk, p, &margin);
       if (b < 0) return -9;
       const double s = std::sqrt(p[b]);
       cd Kb[16];
@@ -722,8 +467,8 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
           TH(a, 1, 1, x) = mat_dot(Kb + 12, v, 4);
         }
       logw += std::log(p[b] / N);
-      if (ch.branches_out) ch.branches_out[n_drawn] = (int8_t)b;
-      if (ch.cond_gate) taken[i] = b;
+      if (res->branches) res->branches[n_drawn] = (int8_t)b;
+      if (prog.cond_gate) taken[i] = b;
       ++n_drawn;
     } else if (o == OP_M2) {  // a 4x4 from the table on (t00, t01, t10, t11)
       const cd* M = mats + (size_t)mat[i] * 16;
@@ -769,9 +514,9 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
       return -5;
     }
     double frac = 1.0;
-    int keep = kept(S, trunc_budget, value_of_zero, &frac);
-    if (max_bond > 0 && keep > max_bond) {  // the chi cap
-      keep = max_bond;
+    int keep = kept(S, run.trunc_budget, run.value_of_zero, &frac);
+    if (run.max_bond > 0 && keep > run.max_bond) {  // the chi cap
+      keep = run.max_bond;
       double tot = 0, w = 0;
       for (double x : S) tot += x * x;
       for (int j = 0; j < keep; ++j) w += S[j] * S[j];
@@ -798,9 +543,9 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
   }
   // ---- hand the tensors over as one block
   int64_t total = 0;
-  dims_out[0] = 1;
+  res->dims[0] = 1;
   for (int k2 = 0; k2 < n; ++k2) {
-    dims_out[k2 + 1] = A[k2].r;
+    res->dims[k2 + 1] = A[k2].r;
     total += (int64_t)A[k2].v.size();
   }
   cd* block = (cd*)std::malloc((size_t)total * sizeof(cd));
@@ -813,11 +558,8 @@ static int simulate_impl(int32_t n_qubits, int32_t n_ops, const int8_t* op, cons
     std::memcpy(block + pos, A[k2].v.data(), A[k2].v.size() * sizeof(cd));
     pos += (int64_t)A[k2].v.size();
   }
-  *tensors_out = reinterpret_cast<double*>(block);
-  *n_complex_out = total;
-  *fidelity_out = fidelity;
-  if (ch.logw_out) *ch.logw_out = logw;
-  if (ch.margin_out) *ch.margin_out = margin;
+  res->tensors = reinterpret_cast<double*>(block), res->n_complex = total;
+  res->fidelity = fidelity, res->logw = logw, res->margin = margin;
   return 0;
 }
 

@@ -13,6 +13,8 @@ from contextlib import contextmanager
 
 import numpy as np
 
+from . import program as _program
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libqkgram.so")
 
@@ -57,6 +59,12 @@ _lib = None
 
 # every symbol include/qkgram.h declares: (name, restype, argtypes)
 _P = C.c_void_p
+# the entries from before qk_build_program, each the one before it plus a group of arguments in front of `out`
+_BUILD_ARGS = [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32]  # ctx .. flags
+_SCAN_ARGS = [C.c_int32, _P, _P, C.c_int32]  # n_checkpoints, checkpoints, initial, initial_snapshot
+_MATS_ARGS = [C.c_int32, _P, C.c_int32, _P]  # n_mats, mats, mats_state_stride, mat
+_CHAN_ARGS = [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, C.c_uint32]  # n_channels .. first_gate
+_CHAN2_ARGS = [C.c_int32, _P, _P]  # n_channels2, kraus2, n_kraus2
 _SIGNATURES = [
     ("qk_last_error", C.c_char_p, []),
     ("qk_device_count", C.c_int, []),
@@ -116,21 +124,20 @@ _SIGNATURES = [
     ("qk_shot_strings_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("qk_kernel_name", C.c_char_p, [C.c_int32, C.c_int32]),
     ("qk_selftest_mfma", C.c_int, [_P]),
-    ("qk_build_mps", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.POINTER(_P)]),
+    ("qk_build_mps", C.c_int, _BUILD_ARGS + [C.POINTER(_P)]),
     ("qk_built_info", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     ("qk_built_launch", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("qk_built_download", C.c_int, [_P, _P]),
     ("qk_built_destroy", C.c_int, [_P]),
     ("qk_mps_set_from_built", C.c_int, [_P, _P, C.POINTER(_P)]),
-    ("qk_build_mps_scan", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.POINTER(_P)]),
-    ("qk_build_mps_gates", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
-                                     C.POINTER(_P)]),
-    ("qk_build_mps_channels", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
-                                        C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.POINTER(_P)]),
-    ("qk_build_mps_channels2", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
-                                         C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.c_int32, _P, _P, C.POINTER(_P)]),
-    ("qk_build_mps_conditions", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P,
-                                          C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, _P, _P, C.c_uint32, C.c_int32, _P, _P, _P, _P, C.POINTER(_P)]),
+    ("qk_build_program", C.c_int, [_P, _P, _P, C.POINTER(_P)]),
+    ("qk_program_size", C.c_uint32, []),
+    ("qk_build_run_size", C.c_uint32, []),
+    ("qk_build_mps_scan", C.c_int, _BUILD_ARGS + _SCAN_ARGS + [C.POINTER(_P)]),
+    ("qk_build_mps_gates", C.c_int, _BUILD_ARGS + _SCAN_ARGS + _MATS_ARGS + [C.POINTER(_P)]),
+    ("qk_build_mps_channels", C.c_int, _BUILD_ARGS + _SCAN_ARGS + _MATS_ARGS + _CHAN_ARGS + [C.POINTER(_P)]),
+    ("qk_build_mps_channels2", C.c_int, _BUILD_ARGS + _SCAN_ARGS + _MATS_ARGS + _CHAN_ARGS + _CHAN2_ARGS + [C.POINTER(_P)]),
+    ("qk_build_mps_conditions", C.c_int, _BUILD_ARGS + _SCAN_ARGS + _MATS_ARGS + _CHAN_ARGS + _CHAN2_ARGS + [_P, _P, C.POINTER(_P)]),
     ("qk_built_logw_at", C.c_int, [_P, C.c_int32, _P]),
     ("qk_built_num_channel_gates", C.c_int, [_P]),
     ("qk_built_branches", C.c_int, [_P, _P]),
@@ -208,6 +215,10 @@ def lib():
             if hasattr(L, name):
                 f = getattr(L, name)
                 f.restype, f.argtypes = res, args
+        try:
+            _program.check_sizes(L, {"qk_program_size": _program.QkProgram, "qk_build_run_size": _program.QkBuildRun})
+        except ImportError as e:
+            raise QkError(str(e)) from None
         _lib = L
     return _lib
 
@@ -1412,7 +1423,7 @@ class MpsSet:
 
 
 class _GateProgram:
-    """The circuits of one device-builder call as the arrays of ``qk_build_mps_gates``: the shared gate structure (``op``, ``q0`` and,
+    """The circuits of one device-builder call as the arrays of a ``qk_program``: the shared gate structure (``op``, ``q0`` and,
     with a matrix table, ``mat``), the per-state angles, and the matrix table of op codes 8 and 9 -- shared (stride 0) when every
     circuit's ``mats`` is the same array bit for bit, otherwise stacked per state (stride n_mats).  ``QkError`` when the circuits do
     not share their gate structure.  The table goes to the C entry as it is: it validates indices and unitarity.
@@ -1421,7 +1432,7 @@ class _GateProgram:
     ``n_kraus2`` must be the same for every circuit; ``branch`` may differ per state (one row for all when they agree, stride 0, otherwise a row per state).  ``seed``,
     ``state_index`` and ``trajectory`` (a scalar for all states, or one per state; ``None``: 0 .. n-1 and 0) name the trajectories,
     ``first_gate`` the position of the first gate in the uninterrupted program.  The condition rows ``cond_gate`` and ``cond_mask``
-    are gate structure too: the same for every circuit; a call with them goes through ``qk_build_mps_conditions``."""
+    are gate structure too: the same for every circuit."""
 
     def __init__(self, what, circuits, seed=0, state_index=None, trajectory=None, first_gate=0):
         c0 = circuits[0]
@@ -1512,35 +1523,16 @@ class _GateProgram:
 
     def build(self, ctx, truncation_fidelity, value_of_zero, max_bond, flags, cps=None, src=None, src_j=0):
         """One launch of the device builder: the handle of the built states (``qk_built``)."""
-        n_ops = int(self.op.shape[0])
+        tables = {}
+        if self.op.shape[0]:  # an empty program has no gate that reads a table or a condition: it is built as a plain one
+            tables = dict(mats=self.mats, mat=self.mat, mats_state_stride=self.stride, kraus=self.kraus, n_kraus=self.n_kraus, kraus2=self.kraus2, n_kraus2=self.n_kraus2,
+                          channel=self.channel, branch=self.branch, branch_state_stride=self.bstride, cond_gate=self.cond_gate, cond_mask=self.cond_mask)
+        prog = _program.fill_program(self.ns, self.n, self.op, self.q0, self.alpha, seed=self.seed, state_index=self.state_index, trajectory=self.trajectory,
+                                     first_gate=self.first_gate, **tables)
+        run = _program.sized(_program.QkBuildRun, flags=flags, trunc_budget=max(0.0, 1.0 - float(truncation_fidelity)), value_of_zero=float(value_of_zero), max_bond=int(max_bond),
+                             n_checkpoints=0 if cps is None else int(cps.shape[0]), checkpoints=None if cps is None else cps.ctypes.data, initial=src, initial_snapshot=src_j)
         h = _P()
-        head = (ctx._h, self.ns, self.n, n_ops, self.op.ctypes.data, self.q0.ctypes.data, self.alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero),
-                int(max_bond), flags)
-        if (self.n_channels or self.n_channels2 or self.cond_gate is not None) and n_ops:
-            if cps is None:
-                cps = np.array([n_ops], dtype=np.int32)
-            chan = (int(cps.shape[0]), cps.ctypes.data, src, src_j, self.n_mats, self.mats.ctypes.data if self.n_mats else None, self.stride,
-                    self.mat.ctypes.data if self.n_mats else None, self.n_channels, self.kraus.ctypes.data if self.n_channels else None,
-                    self.n_kraus.ctypes.data if self.n_channels else None, None if self.channel is None else self.channel.ctypes.data,
-                    None if self.branch is None else self.branch.ctypes.data, self.bstride, self.seed,
-                    self.state_index.ctypes.data, self.trajectory.ctypes.data, self.first_gate)
-            if self.cond_gate is not None:
-                _check(lib().qk_build_mps_conditions(*head, *chan, self.n_channels2, self.kraus2.ctypes.data if self.n_channels2 else None,
-                                                     self.n_kraus2.ctypes.data if self.n_channels2 else None, self.cond_gate.ctypes.data,
-                                                     None if self.cond_mask is None else self.cond_mask.ctypes.data, C.byref(h)),
-                       "qk_build_mps_conditions")
-            elif self.n_channels2:
-                _check(lib().qk_build_mps_channels2(*head, *chan, self.n_channels2, self.kraus2.ctypes.data, self.n_kraus2.ctypes.data, C.byref(h)), "qk_build_mps_channels2")
-            else:
-                _check(lib().qk_build_mps_channels(*head, *chan, C.byref(h)), "qk_build_mps_channels")
-            return h
-        if cps is None and (self.n_mats == 0 or n_ops == 0):  # no snapshots, no table: the plain entry
-            _check(lib().qk_build_mps(*head, C.byref(h)), "qk_build_mps")
-            return h
-        if cps is None:
-            cps = np.array([n_ops], dtype=np.int32)  # the one-checkpoint scan: a snapshot after the whole program
-        _check(lib().qk_build_mps_gates(*head, int(cps.shape[0]), cps.ctypes.data, src, src_j, self.n_mats, self.mats.ctypes.data if self.n_mats else None, self.stride,
-                                        self.mat.ctypes.data if self.n_mats else None, C.byref(h)), "qk_build_mps_gates" if self.n_mats else "qk_build_mps_scan")
+        _check(lib().qk_build_program(ctx._h, C.byref(prog), C.byref(run), C.byref(h)), "qk_build_program")
         return h
 
 

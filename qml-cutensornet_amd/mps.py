@@ -22,6 +22,7 @@ import numpy as np
 from scipy.linalg import qr as _qr
 from scipy.linalg import svd as _svd
 
+from . import program as _program
 from .ansatz import (OP_H, OP_K1, OP_K2, OP_M1, OP_M2, OP_RX, OP_RZ, OP_SWAP, OP_YY, OP_ZZ, BoundCircuit, check_channel_gates, check_checkpoints, check_condition_gates, check_matrix_gates,
                      is_two_qubit, reject_channels)
 
@@ -493,18 +494,8 @@ def _native_builder():
             lib = C.CDLL(os.path.join(here, "libqkbuilder.so"))
             lib.qkb_last_error.restype = C.c_char_p
             lib.qkb_init.argtypes = [C.c_char_p]
-            lib.qkb_simulate_chi.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32,
-                                             C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
-            lib.qkb_simulate_gates.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
-            lib.qkb_simulate_channels.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
-                                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                  C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p,
-                                                  C.POINTER(C.c_double)]
-            lib.qkb_simulate_channels2.argtypes = lib.qkb_simulate_channels.argtypes[:20] + [C.c_int32, C.c_void_p, C.c_void_p] + lib.qkb_simulate_channels.argtypes[20:]
-            lib.qkb_simulate_conditions.argtypes = lib.qkb_simulate_channels2.argtypes[:23] + [C.c_void_p, C.c_void_p] + lib.qkb_simulate_channels2.argtypes[23:]
-            lib.qkb_simulate_initial.argtypes = (lib.qkb_simulate_conditions.argtypes[:25] + [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double]
-                                                 + lib.qkb_simulate_conditions.argtypes[25:])
+            lib.qkb_simulate_program.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            _program.check_sizes(lib, {"qkb_program_size": _program.QkProgram, "qkb_run_size": _program.QkbRun, "qkb_result_size": _program.QkbResult})
             lib.qkb_free.argtypes = [C.c_void_p]
             if blas and lib.qkb_init(os.path.realpath(blas[0]).encode()) == 0:
                 _NATIVE = lib
@@ -524,11 +515,10 @@ def _condition_rows(circuit, op):
 
 def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None, seed=0, state_index=0,
                     trajectory=0, first_gate=0, margin=False, initial=None, initial_centre=None):
-    """``simulate`` through the native builder: same algorithm and LAPACK routines, no interpreter in the gate loop.  A circuit with
-    a channel table goes through ``qkb_simulate_channels``, one with a two-qubit channel table through ``qkb_simulate_channels2``, one with condition rows
-    through ``qkb_simulate_conditions`` (the trajectory arguments and ``margin`` as in ``simulate``).  With ``initial`` (and
-    ``initial_centre``, as in ``simulate``) the call goes through ``qkb_simulate_initial``: the state is seeded here, the native
-    builder only loads it."""
+    """``simulate`` through the native builder (``qkb_simulate_program``): same algorithm and LAPACK routines, no interpreter in the
+    gate loop.  The circuit's tables and condition rows go over as they are -- the native builder validates them -- with the
+    trajectory arguments and ``margin`` as in ``simulate``.  With ``initial`` (and ``initial_centre``, as in ``simulate``) the state
+    is seeded here, the native builder only loads it."""
     import ctypes as C
 
     lib = _native_builder()
@@ -536,96 +526,60 @@ def simulate_native(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e
         raise RuntimeError("native MPS builder unavailable (libqkbuilder.so or scipy's OpenBLAS not found)")
     n = circuit.n_qubits
     op = np.ascontiguousarray(circuit.op, dtype=np.int8)
-    q0 = np.ascontiguousarray(circuit.q0, dtype=np.int32)
-    alpha = np.ascontiguousarray(circuit.alpha, dtype=np.float64)
-    dims = np.zeros(n + 1, dtype=np.int32)
-    block, count, fid = C.c_void_p(), C.c_int64(), C.c_double()
-    # the matrix table of codes 8 and 9, handed over as it is: the native builder validates it (range of mat, finite, unitary)
-    n_mats, mats, mat = 0, None, None
-    if circuit.mats is not None and circuit.mat is not None:
+    tables = {}
+    if circuit.mats is not None and circuit.mat is not None:  # the matrix table of codes 8 and 9
         mats = np.ascontiguousarray(circuit.mats, dtype=np.complex128)
         mat = np.ascontiguousarray(circuit.mat, dtype=np.int32)
         if mats.ndim != 3 or mats.shape[1:] != (4, 4) or mat.shape != op.shape:
             raise ValueError(f"the matrix table must be [n_mats][4][4] with one index per gate, got shapes {mats.shape} and {mat.shape}")
-        n_mats = int(mats.shape[0])
+        tables.update(mats=mats, mat=mat)
     seed, state_index, trajectory, first_gate = _trajectory_ids(seed, state_index, trajectory, first_gate)
-    logw, worst, branches = C.c_double(0.0), C.c_double(np.inf), np.zeros(0, dtype=np.int8)
     start = _initial_state(circuit, initial, initial_centre, value_of_zero)
-    init = ()
-    if start is not None:  # (init_dims, init_tensors, init_centre, init_fidelity, init_logw) of qkb_simulate_initial
-        init_dims = np.ascontiguousarray(start[0].bond_dims(), dtype=np.int32)
-        init_flat = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.complex128).ravel() for t in start[0].tensors]))
-        init = (init_dims.ctypes.data, init_flat.ctypes.data, start[1], start[0].fidelity, start[0].logw)
-    one = circuit.kraus is not None and circuit.n_kraus is not None
-    two = circuit.kraus2 is not None and circuit.n_kraus2 is not None
-    if circuit.channel is not None and (one or two):
-        # the channel tables, handed over as they are: the native builder validates them
-        tables = []
-        for d, k, nk in ((2, circuit.kraus, circuit.n_kraus) if one else (None,) * 3, (4, circuit.kraus2, circuit.n_kraus2) if two else (None,) * 3):
-            if d is None:
-                tables.append((0, None, None))
+    n_kgates = 0
+    if circuit.channel is not None:  # the channel tables of codes 10 and 11
+        for d, names in ((2, ("kraus", "n_kraus")), (4, ("kraus2", "n_kraus2"))):
+            k, nk = (getattr(circuit, a) for a in names)
+            if k is None or nk is None:
                 continue
             k, nk = np.ascontiguousarray(k, dtype=np.complex128), np.ascontiguousarray(nk, dtype=np.int32)
             if k.ndim != 4 or k.shape[1:] != (d * d, d, d) or nk.shape != k.shape[:1]:
                 raise ValueError(f"the channel table must be [n_channels][{d * d}][{d}][{d}] with a count per channel, got shapes {k.shape}, {nk.shape}")
-            tables.append((int(k.shape[0]), k, nk))
-        (n1, kraus, n_kraus), (n2, kraus2, n_kraus2) = tables
-        channel = np.ascontiguousarray(circuit.channel, dtype=np.int32)
-        branch = np.full(op.shape, -1, dtype=np.int32) if circuit.branch is None else np.ascontiguousarray(circuit.branch, dtype=np.int32)
-        if channel.shape != op.shape or branch.shape != op.shape:
-            raise ValueError(f"a program with a channel table needs a channel and a branch per gate, got shapes {channel.shape}, {branch.shape}")
-        n_kgates = int(np.count_nonzero((op == OP_K1) | (op == OP_K2)))
-        branches = np.full(max(1, n_kgates), -1, dtype=np.int8)
-        head = (n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero), int(max_bond or 0),
-                n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None, n1, kraus.ctypes.data if n1 else None,
-                n_kraus.ctypes.data if n1 else None, channel.ctypes.data, branch.ctypes.data, seed, state_index, trajectory, first_gate)
-        tail = (dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid), C.byref(logw), branches.ctypes.data, C.byref(worst))
-        if init:
-            cg, cm = _condition_rows(circuit, op) if circuit.cond_gate is not None else (None, None)
-            rc = lib.qkb_simulate_initial(*head, n2, kraus2.ctypes.data if n2 else None, n_kraus2.ctypes.data if n2 else None, None if cg is None else cg.ctypes.data,
-                                          None if cm is None else cm.ctypes.data, *init, *tail)
-        elif circuit.cond_gate is not None:  # the native builder validates the rows
-            cg, cm = _condition_rows(circuit, op)
-            rc = lib.qkb_simulate_conditions(*head, n2, kraus2.ctypes.data if n2 else None, n_kraus2.ctypes.data if n2 else None, cg.ctypes.data,
-                                             None if cm is None else cm.ctypes.data, *tail)
-        elif n2:
-            rc = lib.qkb_simulate_channels2(*head, n2, kraus2.ctypes.data, n_kraus2.ctypes.data, *tail)
-        else:
-            rc = lib.qkb_simulate_channels(*head, *tail)
-        branches = branches[:n_kgates]
-    else:
-        if circuit.cond_gate is not None:  # condition rows without a channel table: handed over as they are, the native builder refuses them
-            cg, cm = _condition_rows(circuit, op)
-            rc = lib.qkb_simulate_conditions(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero),
-                                             int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None, 0, None, None, None, None, seed,
-                                             state_index, trajectory, first_gate, 0, None, None, cg.ctypes.data, None if cm is None else cm.ctypes.data, dims.ctypes.data,
-                                             C.byref(block), C.byref(count), C.byref(fid), None, None, None)
-            if rc == 0:
-                rc = -8  # (not reached: the entry refuses rows without a table)
-        elif init:  # no channel table: the log-weight of the initial state comes back unchanged
-            rc = lib.qkb_simulate_initial(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)), float(value_of_zero),
-                                          int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None, 0, None, None, None, None, seed,
-                                          state_index, trajectory, first_gate, 0, None, None, None, None, *init, dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid),
-                                          C.byref(logw), None, None)
-        else:
-            rc = lib.qkb_simulate_gates(n, int(op.shape[0]), op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, max(0.0, 1.0 - float(truncation_fidelity)),
-                                        float(value_of_zero), int(max_bond or 0), n_mats, mats.ctypes.data if n_mats else None, mat.ctypes.data if n_mats else None,
-                                        dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid))
+            tables.update(zip(names, (k, nk)))
+        if "kraus" in tables or "kraus2" in tables:
+            channel = np.ascontiguousarray(circuit.channel, dtype=np.int32)
+            branch = np.full(op.shape, -1, dtype=np.int32) if circuit.branch is None else np.ascontiguousarray(circuit.branch, dtype=np.int32)
+            if channel.shape != op.shape or branch.shape != op.shape:
+                raise ValueError(f"a program with a channel table needs a channel and a branch per gate, got shapes {channel.shape}, {branch.shape}")
+            tables.update(channel=channel, branch=branch)
+            n_kgates = int(np.count_nonzero((op == OP_K1) | (op == OP_K2)))
+    if circuit.cond_gate is not None:  # without a channel table the native builder refuses the rows
+        tables.update(zip(("cond_gate", "cond_mask"), _condition_rows(circuit, op)))
+    prog = _program.fill_program(1, n, op, np.ascontiguousarray(circuit.q0, dtype=np.int32), np.ascontiguousarray(circuit.alpha, dtype=np.float64), seed=seed,
+                                 state_index=np.array([state_index], dtype=np.uint32), trajectory=np.array([trajectory], dtype=np.uint32), first_gate=first_gate, **tables)
+    run = _program.sized(_program.QkbRun, max_bond=int(max_bond or 0), trunc_budget=max(0.0, 1.0 - float(truncation_fidelity)), value_of_zero=float(value_of_zero))
+    if start is not None:
+        init_dims = np.ascontiguousarray(start[0].bond_dims(), dtype=np.int32)
+        init_flat = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.complex128).ravel() for t in start[0].tensors]))
+        run.init_dims, run.init_tensors, run.init_centre, run.init_fidelity, run.init_logw = init_dims.ctypes.data, init_flat.ctypes.data, start[1], start[0].fidelity, start[0].logw
+    dims = np.zeros(n + 1, dtype=np.int32)
+    branches = np.full(max(1, n_kgates), -1, dtype=np.int8)
+    res = _program.sized(_program.QkbResult, dims=dims.ctypes.data, branches=branches.ctypes.data)
+    rc = lib.qkb_simulate_program(C.byref(prog), C.byref(run), C.byref(res))
     if rc in (-7, -8, -9):  # an op code outside the program's vocabulary; a bad matrix or channel gate; an impossible outcome of a channel
         raise ValueError(f"native MPS builder: {lib.qkb_last_error().decode()}")
     if rc != 0:
         raise RuntimeError(f"native MPS builder failed: {lib.qkb_last_error().decode()}")
     try:
-        flat = np.ctypeslib.as_array(C.cast(block, C.POINTER(C.c_double)), shape=(2 * count.value,)).view(np.complex128).copy()
+        flat = np.ctypeslib.as_array(C.cast(res.tensors, C.POINTER(C.c_double)), shape=(2 * res.n_complex,)).view(np.complex128).copy()
     finally:
-        lib.qkb_free(block)
+        lib.qkb_free(res.tensors)
     tensors, pos = [], 0
     for k in range(n):
         sz = int(dims[k]) * 2 * int(dims[k + 1])
         tensors.append(flat[pos : pos + sz].reshape(int(dims[k]), 2, int(dims[k + 1])))
         pos += sz
-    out = MPS(tensors, fid.value, logw.value, branches)
-    return (out, float(worst.value)) if margin else out
+    out = MPS(tensors, res.fidelity, res.logw, branches[:n_kgates])
+    return (out, float(res.margin)) if margin else out
 
 
 def simulate(circuit: BoundCircuit, truncation_fidelity: float = 1.0 - 1e-16, value_of_zero: float = 1e-16, max_bond: int | None = None, checkpoints=None, seed=0,

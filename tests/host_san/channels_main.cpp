@@ -1,4 +1,4 @@
-// Host-only sanitizer driver for the Kraus channels of the native host MPS builder (qk_builder.cpp: qkb_simulate_channels), built
+// Host-only sanitizer driver for the Kraus channels of the native host MPS builder (qk_builder.cpp: qkb_simulate_program, spelt qkb_simulate_channels in tests/host_san/qkb_calls.h), built
 // with -fsanitize=address,undefined and run by tests/test_channels_san.py in the CPU tier.  The enumeration case: a 6-qubit
 // entangling program with two amplitude-damping gates (one away from the orthogonality centre, one on the last qubit), its four
 // forced branch sequences summed to the density matrix of a dense Kraus map written in this file; then drawn trajectories and their
@@ -15,18 +15,7 @@
 
 using cd = std::complex<double>;
 
-extern "C" {
-const char* qkb_last_error(void);
-int qkb_init(const char* openblas_path);
-int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                       int32_t max_bond, int32_t n_mats, const double* mats, const int32_t* mat, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out,
-                       double* fidelity_out);
-int qkb_simulate_channels(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                          int32_t max_bond, int32_t n_mats, const double* mats, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
-                          const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate, int32_t* dims_out,
-                          double** tensors_out, int64_t* n_complex_out, double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out);
-void qkb_free(double* p);
-}
+#include "qkb_calls.h"
 
 namespace {
 constexpr int N = 6, DIM = 1 << N;

@@ -1,4 +1,4 @@
-// Host-only sanitizer driver for classical control in the native host MPS builder (qk_builder.cpp: qkb_simulate_conditions), built
+// Host-only sanitizer driver for classical control in the native host MPS builder (qk_builder.cpp: qkb_simulate_program, spelt qkb_simulate_conditions in tests/host_san/qkb_calls.h), built
 // with -fsanitize=address,undefined and run by tests/test_conditions_san.py in the CPU tier.  Teleportation on 3 qubits (the four
 // forced outcome patterns and drawn trajectories: qubit 2 carries the Bloch vector of the state prepared on qubit 0); the exact
 // enumeration of a 4-qubit program that mixes codes 10 and 11 with conditional gates and conditional channels, every classical
@@ -15,16 +15,7 @@
 
 using cd = std::complex<double>;
 
-extern "C" {
-const char* qkb_last_error(void);
-int qkb_init(const char* openblas_path);
-int qkb_simulate_conditions(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                            int32_t max_bond, int32_t n_mats, const double* mats, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
-                            const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate,
-                            int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, int32_t* dims_out,
-                            double** tensors_out, int64_t* n_complex_out, double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out);
-void qkb_free(double* p);
-}
+#include "qkb_calls.h"
 
 namespace {
 using M = std::vector<cd>;  // row-major d x d

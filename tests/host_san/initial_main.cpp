@@ -1,4 +1,4 @@
-// Host-only sanitizer driver for building from a given state in the native host MPS builder (qk_builder.cpp: qkb_simulate_initial),
+// Host-only sanitizer driver for building from a given state in the native host MPS builder (qk_builder.cpp: qkb_simulate_program, spelt qkb_simulate_initial in tests/host_san/qkb_calls.h),
 // built with -fsanitize=address,undefined and run by tests/test_initial_san.py in the CPU tier.  A 5-qubit program with a Unitary-like
 // 4x4, a Measure with a conditional X and a two-qubit dephasing channel is (a) run from a product state written out here against a
 // dense loop of this file, forced through every classical record, and (b) split behind a two-qubit gate: the second half, started from
@@ -16,22 +16,7 @@
 
 using cd = std::complex<double>;
 
-extern "C" {
-const char* qkb_last_error(void);
-int qkb_init(const char* openblas_path);
-int qkb_simulate_conditions(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                            int32_t max_bond, int32_t n_mats, const double* mats, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
-                            const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate,
-                            int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, int32_t* dims_out,
-                            double** tensors_out, int64_t* n_complex_out, double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out);
-int qkb_simulate_initial(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                         int32_t max_bond, int32_t n_mats, const double* mats, const int32_t* mat, int32_t n_channels, const double* kraus, const int32_t* n_kraus,
-                         const int32_t* channel, const int32_t* branch, uint64_t seed, uint32_t state_index, uint32_t trajectory, uint32_t first_gate,
-                         int32_t n_channels2, const double* kraus2, const int32_t* n_kraus2, const int32_t* cond_gate, const uint32_t* cond_mask, const int32_t* init_dims,
-                         const double* init_tensors, int32_t init_centre, double init_fidelity, double init_logw, int32_t* dims_out, double** tensors_out,
-                         int64_t* n_complex_out, double* fidelity_out, double* logw_out, int8_t* branches_out, double* margin_out);
-void qkb_free(double* p);
-}
+#include "qkb_calls.h"
 
 namespace {
 constexpr int N = 5;

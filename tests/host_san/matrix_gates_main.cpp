@@ -1,4 +1,4 @@
-// Host-only sanitizer driver for the matrix gates of the native host MPS builder (qk_builder.cpp: qkb_simulate_gates), built with
+// Host-only sanitizer driver for the matrix gates of the native host MPS builder (qk_builder.cpp: qkb_simulate_program, spelt qkb_simulate_gates in tests/host_san/qkb_calls.h), built with
 // -fsanitize=address,undefined and run by tests/test_matrix_gates_san.py in the CPU tier.  A 6-qubit program with both matrix codes
 // (8: a 2x2, 9: a 4x4), a pair given in reversed order and the named rotations in between is checked against a dense loop in this
 // file, then run with a bond cap, and every rejection must come back as its code.  argv[1]: the OpenBLAS scipy ships.
@@ -13,16 +13,7 @@
 
 using cd = std::complex<double>;
 
-extern "C" {
-const char* qkb_last_error(void);
-int qkb_init(const char* openblas_path);
-int qkb_simulate_gates(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero,
-                       int32_t max_bond, int32_t n_mats, const double* mats, const int32_t* mat, int32_t* dims_out, double** tensors_out, int64_t* n_complex_out,
-                       double* fidelity_out);
-int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond,
-                     int32_t* dims_out, double** tensors_out, int64_t* n_complex_out, double* fidelity_out);
-void qkb_free(double* p);
-}
+#include "qkb_calls.h"
 
 namespace {
 constexpr int N = 6, DIM = 1 << N;

@@ -25,13 +25,7 @@ extern "C" int qk_plan_destroy(qk_plan* p) {  // (the product's version also fre
   return QK_OK;
 }
 
-extern "C" {
-const char* qkb_last_error(void);
-int qkb_init(const char* openblas_path);
-int qkb_simulate_chi(int32_t n_qubits, int32_t n_ops, const int8_t* op, const int32_t* q0, const double* alpha, double trunc_budget, double value_of_zero, int32_t max_bond,
-                     int32_t* dims_out, double** tensors_out, int64_t* n_complex_out, double* fidelity_out);
-void qkb_free(double* p);
-}
+#include "qkb_calls.h"
 
 static std::vector<int32_t> table(std::mt19937& g, int n_states, int n_sites, int max_bond) {
   std::vector<int32_t> d((size_t)n_states * (n_sites + 1), 1);

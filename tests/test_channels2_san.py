@@ -1,4 +1,4 @@
-"""CPU tier: the two-qubit Kraus channels of the native host MPS builder (csrc/qk_builder.cpp: qkb_simulate_channels2) built with
+"""CPU tier: the two-qubit Kraus channels of the native host MPS builder (csrc/qk_builder.cpp: qkb_simulate_program, spelt qkb_simulate_channels2 in tests/host_san/qkb_calls.h) built with
 AddressSanitizer + UndefinedBehaviorSanitizer and driven by tests/host_san/channels2_main.cpp, a stand-alone program -- the recipe
 of tests/test_channels_san.py."""
 import glob

@@ -1,4 +1,4 @@
-"""CPU tier: the Kraus channels of the native host MPS builder (csrc/qk_builder.cpp: qkb_simulate_channels) built with AddressSanitizer
+"""CPU tier: the Kraus channels of the native host MPS builder (csrc/qk_builder.cpp: qkb_simulate_program, spelt qkb_simulate_channels in tests/host_san/qkb_calls.h) built with AddressSanitizer
 + UndefinedBehaviorSanitizer and driven by tests/host_san/channels_main.cpp, a stand-alone program -- the recipe of
 tests/test_matrix_gates_san.py."""
 import glob

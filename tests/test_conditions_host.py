@@ -348,10 +348,11 @@ def test_rejections_name_the_gate(built, builder):
 
 
 def test_the_native_entry_returns_minus_8(built):
-    """``qkb_simulate_conditions`` itself: -8 with the gate named, before a gate is applied."""
+    """``qkb_simulate_program`` itself: -8 with the gate named, before a gate is applied."""
     import ctypes as C
 
     from qml_cutensornet_amd import mps
+    from qml_cutensornet_amd import program as P
 
     lib = mps._native_builder()
     assert lib is not None
@@ -363,11 +364,11 @@ def test_the_native_entry_returns_minus_8(built):
         mats, mat = np.ascontiguousarray(c.mats, dtype=np.complex128), np.ascontiguousarray(c.mat, dtype=np.int32)
         cg = np.ascontiguousarray(c.cond_gate, dtype=np.int32)
         cm = None if c.cond_mask is None else np.ascontiguousarray(c.cond_mask, dtype=np.uint32)
-        dims, block, count, fid = np.full(5, -7, dtype=np.int32), C.c_void_p(), C.c_int64(), C.c_double()
-        rc = lib.qkb_simulate_conditions(4, c.n_gates, op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, 0.0, 1e-16, 0, mats.shape[0], mats.ctypes.data, mat.ctypes.data, kraus.shape[0], kraus.ctypes.data, nk.ctypes.data,
-                                         channel.ctypes.data, branch.ctypes.data, 0, 0, 0, 0, kraus2.shape[0], kraus2.ctypes.data, nk2.ctypes.data, cg.ctypes.data,
-                                         None if cm is None else cm.ctypes.data, dims.ctypes.data, C.byref(block), C.byref(count), C.byref(fid), None, None, None)
-        assert rc == -8 and block.value is None and dims.tolist() == [-7] * 5, label
+        dims = np.full(5, -7, dtype=np.int32)
+        prog = P.fill_program(1, 4, op, q0, alpha, mats=mats, mat=mat, kraus=kraus, n_kraus=nk, kraus2=kraus2, n_kraus2=nk2, channel=channel, branch=branch, cond_gate=cg, cond_mask=cm)
+        run, res = P.sized(P.QkbRun, trunc_budget=0.0, value_of_zero=1e-16), P.sized(P.QkbResult, dims=dims.ctypes.data)
+        rc = lib.qkb_simulate_program(C.byref(prog), C.byref(run), C.byref(res))
+        assert rc == -8 and res.tensors is None and dims.tolist() == [-7] * 5, label
         assert re.search(text, lib.qkb_last_error().decode()), (label, lib.qkb_last_error())
 
 

@@ -1,4 +1,4 @@
-"""CPU tier: classical control in the native host MPS builder (csrc/qk_builder.cpp: qkb_simulate_conditions) built with
+"""CPU tier: classical control in the native host MPS builder (csrc/qk_builder.cpp: qkb_simulate_program, spelt qkb_simulate_conditions in tests/host_san/qkb_calls.h) built with
 AddressSanitizer + UndefinedBehaviorSanitizer and driven by tests/host_san/conditions_main.cpp, a stand-alone program -- the recipe
 of tests/test_conditions_san.py."""
 import glob

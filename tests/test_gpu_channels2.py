@@ -306,10 +306,15 @@ def test_programs_without_code_11_download_the_bits_of_the_parent_build(gpu_ctx)
     assert state_digests(through_new_entry) == want["states"]
     circuits, kw = code10_program()
     assert set(circuits[0].op.tolist()) >= {9, 10} and 11 not in circuits[0].op
-    old, _ = gpu_ctx.build_mps(circuits, **kw)  # qk_build_mps_channels
-    new, _ = gpu_ctx.build_mps([dataclasses.replace(c, kraus2=table.kraus2, n_kraus2=table.n_kraus2) for c in circuits], **kw)  # qk_build_mps_channels2
-    for a, b in zip(old, new):
-        assert same_bits(a, b)
+    from test_gpu_program_entry import BUILD_MPS, build_legacy, gate_program
+
+    with_table = [dataclasses.replace(c, kraus2=table.kraus2, n_kraus2=table.n_kraus2) for c in circuits]
+    with build_legacy(gpu_ctx, "qk_build_mps_channels", gate_program(circuits, **kw), **BUILD_MPS) as scan:  # the C entries themselves, through ctypes
+        old = scan.states(0)
+    with build_legacy(gpu_ctx, "qk_build_mps_channels2", gate_program(with_table, **kw), **BUILD_MPS) as scan:
+        new = scan.states(0)
+    for a, b, c, d in zip(old, new, gpu_ctx.build_mps(circuits, **kw)[0], gpu_ctx.build_mps(with_table, **kw)[0]):
+        assert same_bits(a, b) and same_bits(a, c) and same_bits(a, d)
     with open(os.path.join(ROOT, "tests", "golden", "channels2_parent_bits.json")) as fp:
         want2 = json.load(fp)
     assert trajectory_digests(old) == want2["states"]

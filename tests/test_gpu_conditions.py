@@ -209,25 +209,23 @@ def test_device_entry_rejects_bad_condition_rows(gpu_ctx, case):
         gpu_ctx.build_mps([c, c])
 
 
-def test_device_entry_without_rows_is_the_two_qubit_channel_entry(gpu_ctx, monkeypatch):
-    from qml_cutensornet_amd import engine
+def test_device_entry_without_rows_is_the_two_qubit_channel_entry(gpu_ctx):
+    from test_gpu_program_entry import BUILD_MPS, build_legacy, gate_program
 
     ok = bad_condition_programs()[0][1]
     dev, info = gpu_ctx.build_mps([ok] * 4, seed=3)
     assert info["branches"].shape == (4, 2) and all(abs(m.fidelity - 1) < 1e-12 for m in dev)
     circuits = [from_gates(12, noisy2_12_gates(x)) for x in features(2, 12, 41)]
     kw = dict(seed=SEED, state_index=np.array([0, 1]), trajectory=np.array([1, 0]))
-    old, _ = gpu_ctx.build_mps(circuits, **kw)  # qk_build_mps_channels2
-    L, calls = engine.lib(), []
-
-    def through_new_entry(*a):
-        calls.append(len(a))
-        return L.qk_build_mps_conditions(*a[:-1], None, None, a[-1])
-
-    monkeypatch.setattr(L, "qk_build_mps_channels2", through_new_entry, raising=False)
-    new, _ = gpu_ctx.build_mps(circuits, **kw)  # qk_build_mps_conditions with cond_gate = NULL
-    monkeypatch.undo()
-    assert calls and all(same_bits(a, b) for a, b in zip(old, new))
+    gp = gate_program(circuits, **kw)
+    assert gp.cond_gate is None and gp.n_channels2 > 0
+    with build_legacy(gpu_ctx, "qk_build_mps_channels2", gp, **BUILD_MPS) as scan:  # the C entries themselves, through ctypes
+        old = scan.states(0)
+    with build_legacy(gpu_ctx, "qk_build_mps_conditions", gp, **BUILD_MPS) as scan:  # cond_gate = NULL
+        new = scan.states(0)
+    assert all(same_bits(a, b) for a, b in zip(old, new))
+    through_engine, _ = gpu_ctx.build_mps(circuits, **kw)
+    assert all(same_bits(a, b) for a, b in zip(old, through_engine))
     none = np.full(circuits[0].op.shape, -1, dtype=np.int32)
     import dataclasses
 

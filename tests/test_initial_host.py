@@ -263,32 +263,35 @@ def test_rejections_by_name(built, builder):
 
 
 def _native_initial(lib, dims, tensors, centre, fidelity=1.0, logw=0.0):
-    """``qkb_simulate_initial`` on a one-gate program without tables: (return code, error text)."""
+    """``qkb_simulate_program`` on a one-gate program without tables, from the given state: (return code, error text, ...)."""
+    from qml_cutensornet_amd import program as P
+
     op, q0, alpha = np.array([0], dtype=np.int8), np.array([0], dtype=np.int32), np.zeros(1)
     n = N
     dims = None if dims is None else np.ascontiguousarray(dims, dtype=np.int32)
     flat = np.ascontiguousarray(tensors, dtype=np.complex128)
     out_dims = np.zeros(n + 1, dtype=np.int32)
-    block, count, fid, lw = C.c_void_p(), C.c_int64(), C.c_double(), C.c_double()
-    rc = lib.qkb_simulate_initial(n, 1, op.ctypes.data, q0.ctypes.data, alpha.ctypes.data, 0.0, 1e-16, 0, 0, None, None, 0, None, None, None, None, 0, 0, 0, 0, 0, None, None, None,
-                                  None, None if dims is None else dims.ctypes.data, flat.ctypes.data, centre, fidelity, logw, out_dims.ctypes.data, C.byref(block), C.byref(count),
-                                  C.byref(fid), C.byref(lw), None, None)
+    prog = P.fill_program(1, n, op, q0, alpha)
+    run = P.sized(P.QkbRun, trunc_budget=0.0, value_of_zero=1e-16, init_dims=None if dims is None else dims.ctypes.data, init_tensors=flat.ctypes.data, init_centre=centre,
+                  init_fidelity=fidelity, init_logw=logw)
+    res = P.sized(P.QkbResult, dims=out_dims.ctypes.data)
+    rc = lib.qkb_simulate_program(C.byref(prog), C.byref(run), C.byref(res))
     if rc == 0:
-        lib.qkb_free(block)
-    return rc, lib.qkb_last_error().decode(), out_dims, fid.value, lw.value
+        lib.qkb_free(res.tensors)
+    return rc, lib.qkb_last_error().decode(), out_dims, res.fidelity, res.logw
 
 
 def test_native_entry_rejections_and_the_null_table(built):
     from qml_cutensornet_amd import mps
 
     lib = mps._native_builder()
-    assert lib is not None and hasattr(lib, "qkb_simulate_initial")
+    assert lib is not None and hasattr(lib, "qkb_simulate_program")
     s, _ = mps.seed_state(input_states(1)[0])
     dims = s.bond_dims()
     flat = np.concatenate([t.ravel() for t in s.tensors])
     rc, _, out_dims, fid, lw = _native_initial(lib, dims, flat, N - 1, 0.5, -0.25)
     assert rc == 0 and np.array_equal(out_dims, dims) and fid == 0.5 and lw == -0.25
-    rc, _, out_dims, fid, _ = _native_initial(lib, None, flat, 0)  # a null table: the call IS qkb_simulate_conditions, from |0...0>
+    rc, _, out_dims, fid, _ = _native_initial(lib, None, flat, 0)  # a null table: from |0...0>
     assert rc == 0 and out_dims.tolist() == [1] * (N + 1) and fid == 1.0
     for bad, text in ((0, "boundary bonds must be 1"), (N, "boundary bonds must be 1")):
         d = dims.copy()

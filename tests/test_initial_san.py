@@ -1,4 +1,4 @@
-"""CPU tier: building from a given state in the native host MPS builder (csrc/qk_builder.cpp: qkb_simulate_initial) built with
+"""CPU tier: building from a given state in the native host MPS builder (csrc/qk_builder.cpp: qkb_simulate_program, spelt qkb_simulate_initial in tests/host_san/qkb_calls.h) built with
 AddressSanitizer + UndefinedBehaviorSanitizer and driven by tests/host_san/initial_main.cpp, a stand-alone program -- the recipe
 of tests/test_conditions_san.py."""
 import glob

@@ -1,4 +1,4 @@
-"""CPU tier: the matrix gates of the native host MPS builder (csrc/qk_builder.cpp: qkb_simulate_gates) built with AddressSanitizer +
+"""CPU tier: the matrix gates of the native host MPS builder (csrc/qk_builder.cpp: qkb_simulate_program, spelt qkb_simulate_gates in tests/host_san/qkb_calls.h) built with AddressSanitizer +
 UndefinedBehaviorSanitizer and driven by tests/host_san/matrix_gates_main.cpp, a stand-alone program -- the recipe of
 tests/test_host_sanitizers.py."""
 import glob
