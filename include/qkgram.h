@@ -398,6 +398,34 @@ int qk_operator_strings_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_ops, 
                              int32_t n_strings, const uint8_t* strings /* [n_strings][n_sites], codes 0 .. n_ops */,
                              double* out /* [n_states][n_strings][2] */, double* norms /* [n_states], may be NULL */);
 
+/* Expectation values of matrix-product operators (sums of operator strings) for every state of a set, synchronous on the
+ * context's stream.  MPO m is n_sites tensors W_k of bonds[m][k] x bonds[m][k + 1] blocks of 2 x 2 complex matrices,
+ * W_k[u][v][s'][s] = (Re, Im) of <s'| . |s> (site k = qubit k, physical index 0 = |0>), bonds[m][0] = bonds[m][n_sites] = 1 and
+ * every bond in 1 .. 32; the tensors are packed MPO-major, then site-major, then [u][v][s'][s][re, im].  With
+ * H_m = sum_{u_1 .. u_{n-1}} (x)_k W_k[u_k][u_{k+1}], which need not be Hermitian,
+ *     out[state][m] = <psi| H_m |psi> / <psi|psi>                                                           (complex: Re, Im)
+ * in the conventions of qk_operator_strings_host (general-gauge and unnormalised states).  The support [a, b] of an MPO is the
+ * hull of the sites whose tensor is not exactly the 1 x 1 identity; its chain starts from L_a and closes with R_{b+1}.  Per site
+ * of the support: one GEMM over the w_k planes of the environment stacked along M, an elementwise mix of the planes by W_k, and
+ * one GEMM launch that contracts every new plane with the conjugated site -- about w times the cost of one string over the
+ * support, whatever the number of terms.  Per (MPO, site) the host lists the blocks (u, v) whose four entries are not all exactly
+ * zero, by v then u; a zero block costs nothing and adds nothing, and the sum of an element runs over the listed blocks in
+ * ascending u, s = 0 before s = 1, the imaginary factor before the real one, each component one chain of fused multiply-adds.
+ * A site inside the support whose tensor is the exact 1 x 1 identity has no mix.  A bond-1 MPO gives the bits of its operator
+ * string; an MPO whose tensors are all the 1 x 1 identity is written as exactly (1.0, 0.0); scaling one tensor by 2 scales the
+ * value by 2 bit for bit.  norms, when given, are the bits qk_local_paulis_host returns.  The value of a (state, MPO) is the same
+ * bits whatever the other states of the set, the other MPOs of the call and their order, however the call was cut into batches,
+ * and from run to run.  A chain's slot is 10 w P^2 doubles (w = the MPO's largest bond, P = the state's largest padded bond);
+ * device scratch, batching and qk_ctx_trim are those of qk_pauli_strings_host; QK_MPO_BATCH=<k> (read per call) caps the
+ * (state, MPO) chains of a batch at k.
+ * QK_EINVAL: a null ctx, set, bonds, tensors or out; a set of another context; a complex64 set; n_mpos < 1; a bond outside
+ * 1 .. 32 (the message names the MPO and the cut); bonds[m][0] or bonds[m][n_sites] not 1; a tensor entry that is not finite (the
+ * message names the MPO, the site and the indices); QK_MPO_BATCH < 1.  QK_EDEVICE: a state of norm 0 (the message names the
+ * state).                                                                                                                    */
+int qk_mpo_expectations_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_mpos, const int32_t* bonds /* [n_mpos][n_sites + 1] */,
+                             const double* tensors /* MPO-major, site-major: [w_k][w_{k+1}][2][2][2] (re, im), packed */,
+                             double* out /* [n_states][n_mpos][2] */, double* norms /* [n_states], may be NULL */);
+
 /* The Gram of any real feature columns (host arrays [n][n_features], for instance qk_pauli_strings_host's output), synchronous:
  *     out[j * ld + i] = exp(-g * sum_m (fx[i][m] - fy[j][m])^2)
  * Rows, columns, fy = NULL, the fixed summation order (exact symmetry, unit diagonal) and the argument errors are those of

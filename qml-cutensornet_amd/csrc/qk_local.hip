@@ -91,7 +91,7 @@
 // The launch kinds, the layout of a state's scratch and of a chain's slot, the pair index, the sizes, the cut into batches and the
 // task lists are host-side planning, in qk_local_plan.h (tested on the CPU).  Every entry point runs on one driver: env_sizes,
 // env_tables (the batch's tables and the task lists of its plan) and env_run (upload, reverse, init, then the plan on the stream).
-// The chain families (strings, block, sample, amplitude, window) cut the chains of a state batch into chain batches below that:
+// The chain families (strings, block, sample, amplitude, window, MPO) cut the chains of a state batch into chain batches below that:
 // chain_stage (qk_local_plan.h) owns the layout of a chain batch's device buffer -- the offsets, the slot bases and the host image
 // of its tables, chain_stage_max the room a cut needs behind the state batch -- and chain_run the loop over the chain batches of a
 // cut: per batch the family's task lists, the stage, the upload, the family's pointers and launches (each_launch walks a task list
@@ -839,7 +839,7 @@ int quarter_of_free(qk_ctx* c, const char* what, long long& budget) {
   return QK_OK;
 }
 
-// ---- the driver of a chain batch, shared by the five chain families (strings, block, sample, amplitude, window) -------------------
+// ---- the driver of a chain batch, shared by the six chain families (strings, block, sample, amplitude, window, MPO) ---------------
 // the launches of a task list that have tasks: launch(li, first task, grid)
 template <class Launch>
 void each_launch(const std::vector<long long>& first, Launch&& launch) {
@@ -1048,6 +1048,251 @@ int string_chains(qk_ctx* c, const qk_mps_set* set, const char* what, const char
         out[((size_t)s * n_strings + m) * vals] = 1.0;
         if (general) out[((size_t)s * n_strings + m) * vals + 1] = 0.0;
       }
+  return QK_OK;
+}
+
+// ---- MPO observables (qk_mpo_expectations_host) ---------------------------------------------------------------------------------
+// value = <psi| H |psi> / <psi|psi> of a matrix-product operator H = sum_{u_1 .. u_{n-1}} (x)_k W_k[u_k][u_{k+1}], W_k[u][v][s'][s] =
+// <s'| . |s>, with support [a, b] (the hull of the sites whose tensor is not the exact 1 x 1 identity): the chain of the operator
+// strings with w_k planes of E at the cut in front of site k,
+//     E_a = L_a                                                                                  (w_a = 1)
+//     T[u]  = E[u] . A_k                     one ring GEMM, the planes stacked along M = w_k pad_k                       (MPO_T)
+//     T'[v][(a, s')] = sum_u sum_s W_k[u][v][s'][s] T[u][(a, s)]     out of place, over the listed blocks of plane v    (MPO_MIX)
+//     E'[v] = T'[v] contracted with conj(A_k)  one ring GEMM launch, a plane per v, at column v pad_{k+1}              (MPO_X)
+//     value = sum_{b', a'} E_{b+1}[0][b'][a'] R_{b+1}[b'][a'] / L_n[0][0]                          (w_{b+1} = 1, MPO_CLOSE)
+// The environment pass, the chain driver and the closing kernels are those of the operator strings; the slot of a chain, the block
+// lists and the task lists are in qk_local_plan.h.  A site of the support whose tensor is the exact 1 x 1 identity has no mix
+// launch (the X-shaped product reads T).  The sum of a T' element runs over the listed blocks of its plane in ascending u, s = 0
+// before s = 1, the imaginary factor before the real one, each component one chain of fused multiply-adds whose first term is a
+// plain product -- with one block that is qk_str_op_kernel's expression, so a bond-1 MPO gives the bits of its operator string.  Every
+// u plane goes through the first GEMM and every v plane through the second, whether a block reads or writes it: a plane without a
+// block is written as zeros, so no element of a slot is read before this call wrote it.  4 launches per site of a chain batch,
+// no atomics, no grid barrier, no spin wait; nothing of a chain depends on another chain.  QK_MPO_BATCH caps the chains of a batch.
+struct MpoArgs {
+  OpArgs o;               // o.s: the chain batch as the string kernels see it (cstr = the MPO, supp = the MPO supports); o.ops is not used
+  const int32_t* bonds;   // [n_mpos][n_sites + 1]
+  const int32_t* wmax;    // [n_mpos]
+  const int32_t* vat;     // [n_mpos][n_sites]: first entry of the site in vfirst, -1: no mix launch
+  const int32_t* vfirst;  // per site with a mix launch: w_{k+1} + 1 block indices
+  const int32_t* blk_u;   // per listed block
+  const double* blk_w;    // per listed block: (re, im) of W[u][v][s'][s]
+};
+
+// One 64 x 64 output block of one chain's GEMM at site k.  CONJB = false: MPO_T, the stacked planes as one matrix (a row's sums
+// are those of its plane alone: the K order is fixed); true: MPO_X, block number = (v, block of the plane's product).
+template <bool CONJB>
+__global__ __launch_bounds__(512) void qk_mpo_gemm_kernel(const MpoArgs a) {
+  __shared__ __attribute__((aligned(16))) double lds[LOC_LDS_DOUBLES];
+  const StrArgs& g = a.o.s;
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = __builtin_amdgcn_readfirstlane(t.x);
+  int blk = __builtin_amdgcn_readfirstlane(t.y);
+  const int i = __builtin_amdgcn_readfirstlane(g.cent[ch]);
+  const int m = __builtin_amdgcn_readfirstlane(g.cstr[ch]);
+  const int n = g.e.n_sites, n1 = n + 1, k = g.step;
+  const long long st = __builtin_amdgcn_readfirstlane(g.e.states[i]);
+  const int l = __builtin_amdgcn_readfirstlane(g.e.dims[st * n1 + k]), r = __builtin_amdgcn_readfirstlane(g.e.dims[st * n1 + k + 1]);
+  const int lt = __builtin_amdgcn_readfirstlane(g.e.tru[st * n1 + k]);
+  const int wl = __builtin_amdgcn_readfirstlane(a.bonds[(long long)m * n1 + k]), wr = __builtin_amdgcn_readfirstlane(a.bonds[(long long)m * n1 + k + 1]);
+  const long long P = __builtin_amdgcn_readfirstlane(g.e.pmax[i]), P2 = P * P;
+  const long long U = P2 * __builtin_amdgcn_readfirstlane(a.wmax[m]);
+  double* const E = g.slots + uni64(g.cbase[ch]);
+  double* const T = E + mpo_T() * U;
+  const double* Bre = g.e.data + uni64(g.e.offs[st * n + k]);
+  const double* Bim = Bre + (long long)l * 2 * r;
+  const double *Are, *Aim;
+  double *Cre, *Cim;
+  int lda, ldb, ldc, M, N, K;
+  if (!CONJB) {
+    if (__builtin_amdgcn_readfirstlane(g.supp[2 * m]) == k) {  // the chain starts here: E_a = L_a, one plane
+      Are = g.e.scratch + uni64(g.e.sbase[i]) + g.e.rmul * P2 + uni64(g.e.loff[(long long)i * n1 + k]);
+      Aim = Are + (long long)l * l;
+      lda = l;
+    } else {
+      Are = E, Aim = E + wl * P2;
+      lda = wl * l;
+    }
+    Cre = T, Cim = T + 2 * U;
+    ldb = 2 * r, ldc = 2 * r, M = wl * l, N = 2 * r, K = lt;
+  } else {
+    const int per = ((r + 63) / 64) * ((r + 63) / 64);
+    const int v = blk / per;
+    blk -= v * per;
+    const double* const src = __builtin_amdgcn_readfirstlane(a.vat[(long long)m * n + k]) < 0 ? T : E + mpo_Tp() * U;
+    Are = src + (long long)v * l * 2 * r, Aim = Are + 2 * U;
+    Cre = E + (long long)v * r, Cim = Cre + wr * P2;
+    lda = r, ldb = r, ldc = wr * r, M = r, N = r, K = 2 * lt;
+  }
+  const int npm = (M + 63) / 64;
+  const int m0 = 64 * (blk % npm), n0 = 64 * (blk / npm);
+  zgemm_ring3<CONJB, LOC_KTL, LOC_NSLOT, true, 8, 64, double, 12>(Cre + (long long)m0 * ldc + n0, Cim + (long long)m0 * ldc + n0, ldc, Are + m0, Aim + m0, lda,
+                                                                   Bre + n0, Bim + n0, ldb, min(64, M - m0), min(64, N - n0), K, lds);
+}
+
+// The MPO tensor of site k on the ket index of T, out of place: rows a of one 16-row chunk of the plane T'[v], block number = (v,
+// chunk).  The coefficients of the plane's listed blocks are staged in LDS once per workgroup (at most MPO_MAX_BOND blocks, 2 KiB)
+// and read from there as broadcasts.  The first listed block starts each component with qk_str_op_kernel's expression, the others
+// continue the chain of fused multiply-adds; a plane without a block is written as zeros.
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_mpo_mix_kernel(const MpoArgs a) {
+  __shared__ double cw[MPO_MAX_BOND * 8];
+  __shared__ int cu[MPO_MAX_BOND];
+  const StrArgs& g = a.o.s;
+  const int2 t = g.tasks[blockIdx.x];
+  const int ch = t.x;
+  const int i = g.cent[ch], m = g.cstr[ch];
+  const int n = g.e.n_sites, n1 = n + 1, k = g.step;
+  const long long st = g.e.states[i];
+  const int l = g.e.dims[st * n1 + k], r = g.e.dims[st * n1 + k + 1];
+  const int chunks = l / LOC_CHUNK;
+  const int v = t.y / chunks, c = t.y % chunks;
+  const int at = a.vat[(long long)m * n + k];  // >= 0: a chain has a task here only where the site has a mix launch
+  const int f0 = a.vfirst[at + v], nblk = min(a.vfirst[at + v + 1] - f0, MPO_MAX_BOND);
+  for (int e = threadIdx.x; e < 8 * nblk; e += LOC_RED_THREADS) cw[e] = a.blk_w[8ll * f0 + e];
+  for (int e = threadIdx.x; e < nblk; e += LOC_RED_THREADS) cu[e] = a.blk_u[f0 + e];
+  __syncthreads();
+  const long long P = g.e.pmax[i], U = P * P * a.wmax[m], tpl = 2 * U, plane = (long long)l * 2 * r;
+  const double* const T = g.slots + g.cbase[ch] + mpo_T() * U;
+  double* const Tp = g.slots + g.cbase[ch] + mpo_Tp() * U + v * plane;
+  const int cnt = LOC_CHUNK * r;
+  for (int e = threadIdx.x; e < cnt; e += LOC_RED_THREADS) {
+    const long long q0 = (long long)(c * LOC_CHUNK + e / r) * 2 * r + e % r, q1 = q0 + r;
+    double o0r = 0, o0i = 0, o1r = 0, o1i = 0;
+    for (int j = 0; j < nblk; ++j) {
+      const double* const Tu = T + cu[j] * plane;
+      const double* const o = cw + 8 * j;
+      const double ar = o[0], ai = o[1], br = o[2], bi = o[3], cr = o[4], ci = o[5], dr = o[6], di = o[7];  // W[u][v] = [[a, b], [c, d]]
+      const double r0 = Tu[q0], i0 = Tu[q0 + tpl], r1 = Tu[q1], i1 = Tu[q1 + tpl];
+      if (j == 0) {
+        o0r = fma(br, r1, fma(-bi, i1, fma(ar, r0, -(ai * i0))));
+        o0i = fma(br, i1, fma(bi, r1, fma(ar, i0, ai * r0)));
+        o1r = fma(dr, r1, fma(-di, i1, fma(cr, r0, -(ci * i0))));
+        o1i = fma(dr, i1, fma(di, r1, fma(cr, i0, ci * r0)));
+      } else {
+        o0r = fma(br, r1, fma(-bi, i1, fma(ar, r0, fma(-ai, i0, o0r))));
+        o0i = fma(br, i1, fma(bi, r1, fma(ar, i0, fma(ai, r0, o0i))));
+        o1r = fma(dr, r1, fma(-di, i1, fma(cr, r0, fma(-ci, i0, o1r))));
+        o1i = fma(dr, i1, fma(di, r1, fma(cr, i0, fma(ci, r0, o1i))));
+      }
+    }
+    Tp[q0] = o0r, Tp[q0 + tpl] = o0i, Tp[q1] = o1r, Tp[q1 + tpl] = o1i;
+  }
+}
+
+int mpo_chains(qk_ctx* c, const qk_mps_set* set, const int32_t n_mpos, const int32_t* bonds, const double* tensors, double* out, double* norms) {
+  static const char* what = "qk_mpo_expectations_host";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!set) return qk_fail(QK_EINVAL, "%s: set is null", what);
+  if (!bonds) return qk_fail(QK_EINVAL, "%s: bonds is null", what);
+  if (!tensors) return qk_fail(QK_EINVAL, "%s: tensors is null", what);
+  if (!out) return qk_fail(QK_EINVAL, "%s: out is null", what);
+  if (set->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
+  if (set->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; MPO observables need an fp64 set", what);
+  if (n_mpos < 1) return qk_fail(QK_EINVAL, "%s: n_mpos must be >= 1 (got %d)", what, n_mpos);
+  const int ns = set->n_states, n = set->n_sites, n1 = n + 1;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
+  if (const long long bad = mpo_bad_bond(bonds, n_mpos, n); bad >= 0)
+    return qk_fail(QK_EINVAL, "%s: bonds[%d][%d] = %d is outside 1 .. %d (MPO %d, cut %d)", what, (int)(bad / n1), (int)(bad % n1), bonds[bad], MPO_MAX_BOND, (int)(bad / n1),
+                   (int)(bad % n1));
+  for (int m = 0; m < n_mpos; ++m)
+    for (const int k : {0, n})
+      if (bonds[(size_t)m * n1 + k] != 1) return qk_fail(QK_EINVAL, "%s: bonds[%d][%d] = %d must be 1 (the end of MPO %d)", what, m, k, bonds[(size_t)m * n1 + k], m);
+  {
+    long long e = 0;
+    for (int m = 0; m < n_mpos; ++m)
+      for (int k = 0; k < n; ++k) {
+        const int wr = bonds[(size_t)m * n1 + k + 1];
+        for (long long q = 0; q < 8ll * bonds[(size_t)m * n1 + k] * wr; ++q, ++e)
+          if (!std::isfinite(tensors[e]))
+            return qk_fail(QK_EINVAL, "%s: MPO %d, site %d: W[%d][%d][%d][%d] has a %s part that is not finite", what, m, k, (int)(q / 8 / wr), (int)(q / 8 % wr), (int)(q / 4 % 2),
+                           (int)(q / 2 % 2), q % 2 ? "imaginary" : "real");
+      }
+  }
+  long long cap = 0;  // chains per batch
+  if (const int rc = batch_cap(what, "QK_MPO_BATCH", cap)) return rc;
+  QkRangeGuard range_("qk:mpo_expectations");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  const MpoPlan mp = mpo_plan(bonds, tensors, n_mpos, n);
+  EnvSizes z;
+  env_sizes(set->dims_true.data(), ns, n, set->max_pad, LOC_RMUL, true, z);
+  const int max_chunks = z.max_chunks;
+  // the tables of the MPOs, uploaded once: bonds | wmax | supp | vat | vfirst | blk_u | blk_w (an empty region keeps one element)
+  const std::vector<std::pair<const void*, size_t>> regions{{mp.bonds.data(), mp.bonds.size() * sizeof(int32_t)},   {mp.wmax.data(), mp.wmax.size() * sizeof(int32_t)},
+                                                            {mp.supp.data(), mp.supp.size() * sizeof(int32_t)},     {mp.vat.data(), mp.vat.size() * sizeof(int32_t)},
+                                                            {mp.vfirst.data(), mp.vfirst.size() * sizeof(int32_t)}, {mp.blk_u.data(), mp.blk_u.size() * sizeof(int32_t)},
+                                                            {mp.blk_w.data(), mp.blk_w.size() * sizeof(double)}};
+  std::vector<size_t> rat;
+  size_t tab_bytes = 0;
+  for (const auto& rg : regions) rat.push_back(tab_bytes), tab_bytes += al256(std::max<size_t>(rg.second, 8));
+  std::vector<char> tab(tab_bytes, 0);
+  for (size_t e = 0; e < regions.size(); ++e)
+    if (regions[e].second) std::memcpy(tab.data() + rat[e], regions[e].first, regions[e].second);
+  QkDevBuf rev, dout, dnorm, dtab;
+  HIP_TRY_AS(what, rev.alloc((size_t)set->bytes));
+  HIP_TRY_AS(what, dout.alloc((size_t)ns * n_mpos * 2 * sizeof(double)));
+  HIP_TRY_AS(what, dnorm.alloc((size_t)ns * sizeof(double)));
+  HIP_TRY_AS(what, dtab.alloc(tab_bytes));
+  HIP_TRY_AS(what, hipMemcpy(dtab.get<char>(), tab.data(), tab_bytes, hipMemcpyHostToDevice));
+  // the memory rule of the strings: a quarter of what is free; the environments of a state batch take at most half of it, the
+  // chains of a chain batch the rest (at least one chain)
+  long long budget = 0;
+  if (const int rc = quarter_of_free(c, what, budget)) return rc;
+  const std::vector<int> bstart = batch_cut(z.need, 0, budget / 2);
+  const Plan plan = env_plan(n);
+  EnvBatch eb;
+  for (size_t bi = 0; bi + 1 < bstart.size(); ++bi) {
+    const int s0 = bstart[bi], nb = bstart[bi + 1] - s0;
+    env_tables(z, plan, s0, nb, 0, eb);
+    const Chains ch = list_mpo_chains(z, s0, nb, mp);
+    const std::vector<size_t> cstart = chain_cut(ch.weight, budget - eb.tot, cap);
+    const std::vector<ChainCol> cols{{ch.cent.data(), sizeof(int32_t), 1}, {ch.cstr.data(), sizeof(int32_t), 1}};
+    const long long width = 2ll * max_chunks;  // a chunk sum is (Re, Im)
+    if (const int rc = env_run(c, set, what, rev.get<double>(), z, plan, eb, chain_stage_max(cols, ch, cstart, width))) return rc;
+    qk_str_norms_kernel<<<dim3((nb + 255) / 256), dim3(256), 0, c->stream>>>(eb.g, nb, dnorm.get<double>());
+    HIP_TRY_AS(what, hipGetLastError());
+    MpoArgs qm{};
+    qm.bonds = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[0]);
+    qm.wmax = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[1]);
+    qm.vat = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[3]);
+    qm.vfirst = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[4]);
+    qm.blk_u = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[5]);
+    qm.blk_w = reinterpret_cast<const double*>(dtab.get<char>() + rat[6]);
+    StrArgs& q = qm.o.s;
+    q.e = eb.g;
+    q.supp = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[2]);
+    const int rc = chain_run(
+        c, what, eb.base + eb.used(), cols, ch, cstart, width,
+        [&](size_t c0, size_t nc, std::vector<Task2>& tasks, std::vector<long long>& first) { mpo_lists(z, s0, ch, c0, nc, mp, tasks, first); },
+        [&](const ChainBatch& b) {
+          q.cent = reinterpret_cast<const int32_t*>(b.base + b.st.col[0]);
+          q.cstr = reinterpret_cast<const int32_t*>(b.base + b.st.col[1]);
+          q.cbase = reinterpret_cast<const int64_t*>(b.base + b.st.col[2]);
+          const int2* d_ctasks = reinterpret_cast<const int2*>(b.base + b.st.tasks);
+          q.part = reinterpret_cast<double*>(b.base + b.st.part);
+          q.slots = reinterpret_cast<double*>(b.base + b.st.slots);
+          each_launch(b.first, [&](const size_t li, const long long t0, const dim3 grid) {
+            const int kind = MPO_KINDS[li % 4];
+            q.tasks = d_ctasks + t0;
+            q.step = (int)(li / 4);
+            if (kind == MPO_T) qk_mpo_gemm_kernel<false><<<grid, dim3(512), 0, c->stream>>>(qm);
+            else if (kind == MPO_X) qk_mpo_gemm_kernel<true><<<grid, dim3(512), 0, c->stream>>>(qm);
+            else if (kind == MPO_MIX) qk_mpo_mix_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(qm);
+            else qk_str_closez_kernel<<<grid, dim3(LOC_RED_THREADS), 0, c->stream>>>(qm.o);
+          });
+          qk_str_valuesz_kernel<<<dim3((unsigned)((b.nc + 255) / 256)), dim3(256), 0, c->stream>>>(q, (int)b.nc, n_mpos, dout.get<double>());
+        });
+    if (rc) return rc;
+    HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  }
+  std::vector<double> h_norm((size_t)ns);  // a value divides by <psi|psi> (a norm that is NaN marks its own row)
+  HIP_TRY_AS(what, hipMemcpy(h_norm.data(), dnorm.get(), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+  for (int s = 0; s < ns; ++s)
+    if (h_norm[s] == 0.0) return qk_fail(QK_EDEVICE, "%s: state %d has norm 0: its expectation values are undefined", what, s);
+  HIP_TRY_AS(what, hipMemcpy(out, dout.get(), (size_t)ns * n_mpos * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (norms) std::memcpy(norms, h_norm.data(), (size_t)ns * sizeof(double));
+  for (int m = 0; m < n_mpos; ++m)  // an all-identity MPO is exactly 1 + 0j
+    if (mp.supp[2 * m] < 0)
+      for (int s = 0; s < ns; ++s) out[((size_t)s * n_mpos + m) * 2] = 1.0, out[((size_t)s * n_mpos + m) * 2 + 1] = 0.0;
   return QK_OK;
 }
 
@@ -2908,6 +3153,9 @@ extern "C" int qk_operator_strings_host(qk_ctx* c, const qk_mps_set* set, int32_
                                         double* norms) {
   if (!ops) return qk_fail(QK_EINVAL, "qk_operator_strings_host: ops is null");
   return string_chains(c, set, "qk_operator_strings_host", "qk:operator_strings", "QK_OPSTR_BATCH", n_ops, ops, n_strings, strings, out, norms);
+}
+extern "C" int qk_mpo_expectations_host(qk_ctx* c, const qk_mps_set* set, int32_t n_mpos, const int32_t* bonds, const double* tensors, double* out, double* norms) {
+  return mpo_chains(c, set, n_mpos, bonds, tensors, out, norms);
 }
 
 extern "C" int qk_feature_gram_host(qk_ctx* c, int32_t n_features, int32_t nx, const double* fx, int32_t ny, const double* fy, double g, double* out, int64_t ld) {

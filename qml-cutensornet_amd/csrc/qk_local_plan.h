@@ -1,6 +1,6 @@
 // qk_local_plan.h -- the host-side plan of the local sweeps (qk_local.hip): the launch kinds, the scratch layout, the pair index, the
 // sizes and the cut into state batches, the tables and task lists of a batch, the plans of the entry points, the chain side of the
-// Pauli strings, of the block kernels, of the sampler, of the amplitude chains and of the k-qubit windows, the device buffer of a chain
+// Pauli strings, of the block kernels, of the sampler, of the amplitude chains, of the k-qubit windows and of the MPO observables, the device buffer of a chain
 // batch (chain_stage, tests/host_san/chain_stage_main.cpp) and the batch cap of the environment (batch_cap), the integer side of the shot-based block overlaps , of the shadow kernel's shot-pair histograms and of the Pauli strings estimated from shots.  Plain C++: no HIP type appears here, so all of it is tested on the CPU (tests/host_san/local_plan_main.cpp,
 // -fsanitize=address,undefined); the few functions the kernels also call are QK_HD.
 #pragma once
@@ -23,7 +23,8 @@ constexpr int LOC_CHUNK = 16;  // rows per reduction task
 // Every launch kind of qk_local.hip.  Kinds >= 0 are GEMM launches (64 x 64 output blocks), the others elementwise or reductions
 // in 16-row chunks.  LOC_*: tasks (batch entry, block), qk_local_gemm_kernel; STR_*: tasks (chain, block), qk_str_gemm_kernel;
 // BLK_*: tasks (pair chain, block), qk_blk_gemm_kernel; SMP_*: tasks (shot chain, block), qk_smp_gemm_kernel; WIN_*: tasks (window
-// chain, block), qk_win_gemm_kernel; AMP_*: tasks (amplitude chain, block), qk_amp_gemm_kernel.
+// chain, block), qk_win_gemm_kernel; AMP_*: tasks (amplitude chain, block), qk_amp_gemm_kernel; MPO_*: tasks (MPO chain, block),
+// qk_mpo_gemm_kernel.
 enum LocKind : int {
   LOC_REV_T = 0,   // reversed chain: T = Lr^T Ar_j              (Lr_j = R_{o+1}, o = n-1-j)
   LOC_REV_X = 1,   // reversed chain: R_o = T^T conj(Ar_j)
@@ -61,8 +62,12 @@ enum LocKind : int {
   WIN_CLOSE = -12,    // qk_win_close_kernel: sum Gr_w[alpha][(s, gamma')] conj(H[alpha][(s', gamma')]) of every s <= s' in 16-row chunks of alpha
   AMP_W = 19,         // amplitude chain (state, string tile), site k: W[row][(t, b')] = sum_b V[b][row] A_k[b][(t, b')] (the SMP_W shape)
   AMP_PICK = -13,     // qk_amp_pick_kernel: W'_{bit} of a row in its basis, its maximum, its exponent and the scaled next V, one wave per row
+  MPO_T = 20,         // MPO chain (state, MPO), site k: T[(u, a)][(s, b')] = sum_b E[u][b][a] A_k[b][(s, b')], the w_k planes of E stacked along M
+  MPO_X = 21,         // MPO chain: E'[v][b'][a'] = sum_{(a,s')} T'[v][(a, s')][b'] conj(A_k[(a, s')][a']) of every plane v (the STR_X shape), at column v pad_{k+1}
+  MPO_MIX = -14,      // qk_mpo_mix_kernel: T'[v][(a, s')] = sum_u sum_s W_k[u][v][s'][s] T[u][(a, s)] over the listed blocks, one 16-row chunk of one v plane
+  MPO_CLOSE = -15,    // qk_str_closez_kernel on the chains whose support ends at site k
 };
-QK_HD constexpr bool conj_b(const int kind) { return kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V || kind == LOC_DIST_X || kind == STR_X || kind == BLK_X || kind == BLK_W; }
+QK_HD constexpr bool conj_b(const int kind) { return kind == LOC_REV_X || kind == LOC_FWD_W || kind == LOC_PAIR_V || kind == LOC_DIST_X || kind == STR_X || kind == BLK_X || kind == BLK_W || kind == MPO_X; }
 
 // ---- the scratch layout ---------------------------------------------------------------------------------------------------------
 // Per-state scratch (doubles, every matrix as a re plane then an im plane), P = the state's largest padded bond, offsets in units
@@ -340,6 +345,7 @@ inline void chain_lists(const EnvSizes& z, const int s0, const Chains& c, const 
 //   sample     cent, shot0, rows, bad (zeros)  | cbase | tasks |       | slots     (no partial sums: width 0)
 //   amplitude  cent, str0, rows                | cbase | tasks |       | slots
 //   window     cent, cwin                      | cbase | tasks | part  | slots
+//   MPO        cent, cstr (the MPO)            | cbase | tasks | part  | slots
 // A column holds `per` elements of `elem` bytes per chain; src points at the element of chain 0 of the whole list (a range takes
 // its own part), NULL: the column is staged as zeros (the device writes it).
 struct ChainCol {
@@ -976,6 +982,131 @@ inline long long sst_batch_strings(const long long room, const int n, const long
   if (fit >= SST_BLOCK) fit -= fit % SST_BLOCK;
   fit = std::max(1ll, fit);
   return cap > 0 ? std::min(fit, cap) : fit;
+}
+
+// ---- MPO observables (qk_mpo_expectations_host) -------------------------------------------------------------------------------------
+// An MPO on n sites is n tensors W_k[u][v][s'][s] (complex, [w_k][w_{k+1}][2][2], w_0 = w_n = 1, 1 <= w_k <= MPO_MAX_BOND), packed
+// MPO-major and site-major as (re, im) doubles.  Its support [a, b] is the hull of the sites whose tensor is not exactly the 1 x 1
+// identity.  A chain is one (state, MPO) with a support; it starts from E_a = L_a and closes with R_{b+1} as a string chain does.
+// Its slot is mpo_size() U doubles, U = w P^2 (w = the MPO's largest bond, P = the state's largest padded bond), every matrix as a
+// re plane then an im plane, offsets in units of U:
+//   E  [pad_k][w_k pad_k]         at mpo_E()  = 0   the planes E[u] side by side (column u pad_k), ld = w_k pad_k; the im plane lies
+//                                                   w_k P^2 behind the re plane, so that of a closed chain (w = 1) lies where the
+//                                                   closing kernel of the operator strings reads it
+//   T  [w_k pad_k][2 pad_{k+1}]   at mpo_T()  = 2   the planes T[u] stacked (row u pad_k + a), ld = 2 pad_{k+1}; planes of 2 U
+//   T' [w_{k+1} pad_k][2 pad_{k+1}] at mpo_Tp() = 6 the planes T'[v] stacked, as T
+// Per (MPO, site) the host lists the blocks (u, v) whose four entries are not all exactly zero, sorted by v, then u; vfirst holds,
+// per site with a mix launch, w_{k+1} + 1 block indices (the blocks of plane v are [vfirst[v], vfirst[v + 1])).
+constexpr int MPO_MAX_BOND = 32;
+QK_HD constexpr int mpo_E() { return 0; }
+QK_HD constexpr int mpo_T() { return 2; }
+QK_HD constexpr int mpo_Tp() { return 6; }
+QK_HD constexpr int mpo_size() { return 10; }
+QK_HD constexpr long long mpo_unit(const long long P, const int w) { return P * P * w; }
+static_assert(mpo_T() >= mpo_E() + 2 && mpo_Tp() >= mpo_T() + 4 && mpo_size() >= mpo_Tp() + 4, "E (2 planes of U), T and T' (2 planes of 2 U each) do not overlap");
+constexpr int MPO_KINDS[4] = {MPO_T, MPO_MIX, MPO_X, MPO_CLOSE};  // the launches of a site, in stream order
+
+struct MpoPlan {
+  int n_mpos = 0, n_sites = 0;
+  std::vector<int32_t> bonds;   // [n_mpos][n_sites + 1]
+  std::vector<int64_t> toff;    // [n_mpos][n_sites]: first double of W_k in the packed tensors
+  std::vector<int32_t> supp;    // [n_mpos][2]: a, b (-1, -1: every tensor is the 1 x 1 identity)
+  std::vector<int32_t> wmax;    // [n_mpos]: the largest bond
+  std::vector<int32_t> vat;     // [n_mpos][n_sites]: where the site's w_{k+1} + 1 entries of vfirst start; -1: the exact 1 x 1 identity (no mix launch)
+  std::vector<int32_t> vfirst;  // block indices
+  std::vector<int32_t> blk_u, blk_v;  // per listed block (blk_v is host-only: the tests read it)
+  std::vector<double> blk_w;    // per listed block: (re, im) of W[u][v][s'][s], s' major
+};
+// bonds must be in 1 .. MPO_MAX_BOND: returns -1, or the index m (n + 1) + k of the first offender
+inline long long mpo_bad_bond(const int32_t* bonds, const int n_mpos, const int n) {
+  for (long long e = 0; e < (long long)n_mpos * (n + 1); ++e)
+    if (bonds[e] < 1 || bonds[e] > MPO_MAX_BOND) return e;
+  return -1;
+}
+// the doubles of the packed tensors of valid bonds
+inline long long mpo_doubles(const int32_t* bonds, const int n_mpos, const int n) {
+  long long tot = 0;
+  for (int m = 0; m < n_mpos; ++m)
+    for (int k = 0; k < n; ++k) tot += 8ll * bonds[(size_t)m * (n + 1) + k] * bonds[(size_t)m * (n + 1) + k + 1];
+  return tot;
+}
+inline bool mpo_is_identity(const double* w, const int wl, const int wr) {
+  return wl == 1 && wr == 1 && w[0] == 1.0 && w[1] == 0.0 && w[2] == 0.0 && w[3] == 0.0 && w[4] == 0.0 && w[5] == 0.0 && w[6] == 1.0 && w[7] == 0.0;
+}
+// supports, block lists and bond maxima of MPOs with valid bonds
+inline MpoPlan mpo_plan(const int32_t* bonds, const double* tensors, const int n_mpos, const int n) {
+  MpoPlan mp;
+  mp.n_mpos = n_mpos, mp.n_sites = n;
+  mp.bonds.assign(bonds, bonds + (size_t)n_mpos * (n + 1));
+  mp.toff.resize((size_t)n_mpos * n), mp.supp.assign((size_t)2 * n_mpos, -1), mp.wmax.assign(n_mpos, 1), mp.vat.assign((size_t)n_mpos * n, -1);
+  long long at = 0;
+  for (int m = 0; m < n_mpos; ++m)
+    for (int k = 0; k < n; ++k) {
+      const int wl = bonds[(size_t)m * (n + 1) + k], wr = bonds[(size_t)m * (n + 1) + k + 1];
+      const double* w = tensors + at;
+      mp.toff[(size_t)m * n + k] = at, at += 8ll * wl * wr;
+      mp.wmax[m] = std::max({mp.wmax[m], wl, wr});
+      if (mpo_is_identity(w, wl, wr)) continue;
+      if (mp.supp[2 * m] < 0) mp.supp[2 * m] = k;
+      mp.supp[2 * m + 1] = k;
+      mp.vat[(size_t)m * n + k] = (int32_t)mp.vfirst.size();
+      for (int v = 0; v < wr; ++v) {
+        mp.vfirst.push_back((int32_t)mp.blk_u.size());
+        for (int u = 0; u < wl; ++u) {
+          const double* b = w + 8 * ((size_t)u * wr + v);
+          bool zero = true;
+          for (int e = 0; e < 8; ++e) zero = zero && b[e] == 0.0;
+          if (zero) continue;
+          mp.blk_u.push_back(u), mp.blk_v.push_back(v);
+          mp.blk_w.insert(mp.blk_w.end(), b, b + 8);
+        }
+      }
+      mp.vfirst.push_back((int32_t)mp.blk_u.size());
+    }
+  return mp;
+}
+// the blocks of a chain (p = its state's padded bonds, m = its MPO) in the launch `kind` of site k
+inline int mpo_task_count(const int kind, const int k, const int32_t* p, const MpoPlan& mp, const int m) {
+  const int n = mp.n_sites, a = mp.supp[2 * m], b = mp.supp[2 * m + 1];
+  if (a < 0 || k < a || k > b) return 0;
+  const int wl = mp.bonds[(size_t)m * (n + 1) + k], wr = mp.bonds[(size_t)m * (n + 1) + k + 1];
+  switch (kind) {
+    case MPO_T: return (int)blocks64((long long)wl * p[k], 2ll * p[k + 1]);
+    case MPO_MIX: return mp.vat[(size_t)m * n + k] < 0 ? 0 : wr * (p[k] / LOC_CHUNK);
+    case MPO_X: return (int)(wr * blocks64(p[k + 1], p[k + 1]));
+    default: return k == b ? p[k + 1] / LOC_CHUNK : 0;  // MPO_CLOSE
+  }
+}
+// the chains of a state batch, state-major in MPO order (cstr = the MPO); a chunk sum is (Re, Im)
+inline Chains list_mpo_chains(const EnvSizes& z, const int s0, const int nb, const MpoPlan& mp) {
+  const int n = z.n_sites;
+  Chains c;
+  for (int i = 0; i < nb; ++i)
+    for (int m = 0; m < mp.n_mpos; ++m)
+      if (mp.supp[2 * m] >= 0) {
+        long long nt = 0;
+        for (int k = mp.supp[2 * m]; k <= mp.supp[2 * m + 1]; ++k)
+          for (const int kind : MPO_KINDS) nt += mpo_task_count(kind, k, &z.pad[(size_t)(s0 + i) * (n + 1)], mp, m);
+        c.cent.push_back(i), c.cstr.push_back(m), c.ntasks.push_back(nt);
+        c.slot.push_back(mpo_size() * mpo_unit(z.pmax[s0 + i], mp.wmax[m]));
+        c.weight.push_back(c.slot.back() + 2ll * z.max_chunks + nt + 2);
+      }
+  return c;
+}
+// Task lists (chain of the batch, block) of the chains [c0, c0 + nc): launch 4k + j is MPO_KINDS[j] at site k.  The cut into chain
+// batches is chain_cut (QK_MPO_BATCH caps the chains of one).
+inline void mpo_lists(const EnvSizes& z, const int s0, const Chains& c, const size_t c0, const size_t nc, const MpoPlan& mp, std::vector<Task2>& tasks, std::vector<long long>& first) {
+  const int n = z.n_sites;
+  tasks.clear(), first.clear();
+  for (int k = 0; k < n; ++k)
+    for (const int kind : MPO_KINDS) {
+      first.push_back((long long)tasks.size());
+      for (size_t e = 0; e < nc; ++e) {
+        const int nbk = mpo_task_count(kind, k, &z.pad[(size_t)(s0 + c.cent[c0 + e]) * (n + 1)], mp, c.cstr[c0 + e]);
+        for (int b = 0; b < nbk; ++b) tasks.push_back(Task2{(int)e, b});
+      }
+    }
+  first.push_back((long long)tasks.size());
 }
 
 }  // namespace qkl

@@ -111,6 +111,7 @@ _SIGNATURES = [
     ("qk_projected_pair_gram_dist_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_pauli_strings_host", C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     ("qk_operator_strings_host", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    ("qk_mpo_expectations_host", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     ("qk_feature_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_bond_purities_host", C.c_int, [_P, _P, _P, _P]),
     ("qk_bond_spectra_host", C.c_int, [_P, _P, C.c_int32, _P, _P]),
@@ -863,6 +864,212 @@ def marginal_strings(bits, bases, n_sites: int):
     table = np.stack([LOCAL_OPS[name] for pair in _PROJECTOR_NAMES for name in pair])
     codes = np.where(B > 0, 2 * (B.astype(np.int64) - 1) + (b.astype(np.int64) & 1) + 1, 0).astype(np.uint8)
     return table, np.ascontiguousarray(codes)
+
+
+MPO_MAX_BOND = 32  # the largest bond of an MPO (qk_mpo_expectations_host)
+_MPO_DENSE_MAX = 12  # sites of Mpo.to_dense
+
+
+class Mpo:
+    """A matrix-product operator on ``n_sites`` qubits: ``tensors[k]`` is complex128 of shape (w_k, w_{k+1}, 2, 2),
+    ``W_k[u][v][s'][s] = <s'| . |s>`` (physical index 0 = |0>, site k = qubit k), with w_0 = w_n = 1 and every bond in
+    1 .. ``MPO_MAX_BOND``.  The operator is ``H = sum_{u_1 .. u_{n-1}} (x)_k W_k[u_k][u_{k+1}]``; it need not be Hermitian.
+    ``bonds`` is the int32 row (w_0, .., w_n).  ``+`` is the direct sum of the bonds, ``@`` the operator product (bonds multiply),
+    ``scale(c)`` puts a factor on the first site, ``dagger()`` is the adjoint, ``to_dense()`` the 2^n x 2^n matrix (qubit 0 the
+    most significant bit) for n <= 12.  Evaluate with ``Context.mpo_expectations`` or ``MPS.mpo_expectation``."""
+
+    def __init__(self, tensors):
+        try:
+            ts = [np.ascontiguousarray(t, dtype=np.complex128) for t in tensors]
+        except (TypeError, ValueError):
+            raise ValueError("an Mpo takes a sequence of complex arrays of shape (w_k, w_k+1, 2, 2)") from None
+        if not ts:
+            raise ValueError("an Mpo needs at least one site")
+        for k, t in enumerate(ts):
+            if t.ndim != 4 or t.shape[2:] != (2, 2) or t.shape[0] < 1 or t.shape[1] < 1:
+                raise ValueError(f"Mpo tensor {k} must have shape (w_k, w_k+1, 2, 2), got {t.shape}")
+            if k and t.shape[0] != ts[k - 1].shape[1]:
+                raise ValueError(f"Mpo tensor {k} has left bond {t.shape[0]}, tensor {k - 1} has right bond {ts[k - 1].shape[1]} (cut {k})")
+            if not np.isfinite(t).all():
+                u, v, sp, s0 = (int(x) for x in np.argwhere(~np.isfinite(t.real) | ~np.isfinite(t.imag))[0])
+                raise ValueError(f"Mpo tensor {k} has an entry [{u}][{v}][{sp}][{s0}] that is not finite")
+        if ts[0].shape[0] != 1 or ts[-1].shape[1] != 1:
+            raise ValueError(f"an Mpo starts and ends with bond 1, got {ts[0].shape[0]} and {ts[-1].shape[1]}")
+        bonds = [1] + [t.shape[1] for t in ts]
+        for k, w in enumerate(bonds):
+            if w > MPO_MAX_BOND:
+                raise ValueError(f"the Mpo has bond {w} at cut {k}, above MPO_MAX_BOND = {MPO_MAX_BOND}")
+        self.tensors = ts
+        self.bonds = np.array(bonds, dtype=np.int32)
+        self.n_sites = len(ts)
+
+    def __len__(self):
+        return self.n_sites
+
+    def max_bond(self) -> int:
+        return int(self.bonds.max())
+
+    def packed(self) -> np.ndarray:
+        """The tensors as qk_mpo_expectations_host takes them: site-major [w_k][w_k+1][2][2][re, im], float64."""
+        return np.concatenate([t.reshape(-1) for t in self.tensors]).view(np.float64)
+
+    def to_dense(self) -> np.ndarray:
+        n = self.n_sites
+        if n > _MPO_DENSE_MAX:
+            raise ValueError(f"to_dense is for at most {_MPO_DENSE_MAX} sites, the Mpo has {n}")
+        M = np.ones((1, 1, 1), dtype=np.complex128)  # [row][column][bond]
+        for t in self.tensors:
+            M = np.einsum("rcu,uvps->rpcsv", M, t).reshape(M.shape[0] * 2, M.shape[1] * 2, t.shape[1])
+        return np.ascontiguousarray(M[:, :, 0])
+
+    def scale(self, c) -> "Mpo":
+        c = complex(c)
+        if not np.isfinite(c):
+            raise ValueError(f"scale takes a finite factor, got {c!r}")
+        return Mpo([self.tensors[0] * c] + self.tensors[1:])
+
+    def dagger(self) -> "Mpo":
+        return Mpo([t.conj().transpose(0, 1, 3, 2) for t in self.tensors])
+
+    def _same_sites(self, other, what):
+        if not isinstance(other, Mpo):
+            raise TypeError(f"{what} takes two Mpo, got {type(other).__name__}")
+        if other.n_sites != self.n_sites:
+            raise ValueError(f"{what}: the two Mpo have {self.n_sites} and {other.n_sites} sites")
+
+    def __add__(self, other) -> "Mpo":
+        self._same_sites(other, "+")
+        n, out = self.n_sites, []
+        for k, (a, b) in enumerate(zip(self.tensors, other.tensors)):
+            if n == 1:
+                out.append(a + b)
+                continue
+            la, ra = (0 if k == 0 else a.shape[0]), (0 if k == n - 1 else a.shape[1])
+            t = np.zeros(((1 if k == 0 else a.shape[0] + b.shape[0]), (1 if k == n - 1 else a.shape[1] + b.shape[1]), 2, 2), dtype=np.complex128)
+            t[: a.shape[0], : a.shape[1]] = a
+            t[la:, ra:] = b
+            out.append(t)
+        return Mpo(out)
+
+    def __matmul__(self, other) -> "Mpo":
+        self._same_sites(other, "@")
+        return Mpo([np.einsum("uvpq,xyqs->uxvyps", a, b).reshape(a.shape[0] * b.shape[0], a.shape[1] * b.shape[1], 2, 2) for a, b in zip(self.tensors, other.tensors)])
+
+
+def _mpo_list(mpos, n_sites: int):
+    if isinstance(mpos, Mpo):
+        raise ValueError("expected a list of Mpo, got a single Mpo")
+    ms = list(mpos)
+    if not ms:
+        raise ValueError("the list of MPOs is empty")
+    for j, m in enumerate(ms):
+        if not isinstance(m, Mpo):
+            raise ValueError(f"entry {j} of the list is not an Mpo ({type(m).__name__})")
+        if m.n_sites != n_sites:
+            raise ValueError(f"Mpo {j} has {m.n_sites} sites, the states have {n_sites}")
+    return ms
+
+
+def mpo_product(n_sites: int, names_or_table, qubits=None) -> Mpo:
+    """The bond-1 MPO of one operator string, in the specs of ``operator_strings``: ``mpo_product(n, names, qubits)`` with names
+    from ``LOCAL_OPS`` (a ``str`` of one-letter names or a sequence of names), or ``mpo_product(n, table, codes)`` with a table
+    (n_ops, 2, 2) and a row of ``n`` integer codes (0 = identity).  A site without an operator holds the exact 1 x 1 identity."""
+    if isinstance(names_or_table, str) or (isinstance(names_or_table, (tuple, list)) and all(isinstance(v, str) for v in names_or_table)):
+        table, codes = operator_strings(n_sites, [(names_or_table if isinstance(names_or_table, str) else tuple(names_or_table), tuple(qubits))])
+    else:
+        table, codes = operator_strings(n_sites, [np.asarray(qubits)], ops=names_or_table)
+    eye = np.eye(2, dtype=np.complex128)
+    return Mpo([(table[c - 1] if c else eye).reshape(1, 1, 2, 2) for c in codes[0]])
+
+
+def mpo_from_terms(n_sites: int, terms, ops=None) -> Mpo:
+    """The exact finite-state machine of ``sum_t coeff_t O_t``: ``terms = [(coeff, names, qubits), ...]`` with ``(names, qubits)`` a
+    spec of ``operator_strings`` (names from ``ops``, a dict, and ``LOCAL_OPS``).  The states at the cut in front of site k are, in
+    this order: ``start`` if a term begins at a site >= k, one state per term with first < k <= last in term order, then ``done``
+    if a term ends before k.  ``W[start][start] = W[done][done] = I``; the coefficient sits on the term's first site; identity
+    sits on the sites of a term's hull that it does not act on; one-site terms add into ``W[start][done]``.  Duplicate terms are
+    allowed.  A cut with more than ``MPO_MAX_BOND`` states is a ``ValueError`` that names the cut."""
+    n = int(n_sites)
+    terms = list(terms)
+    if not terms:
+        raise ValueError("the list of terms is empty")
+    specs, coeffs = [], []
+    for j, term in enumerate(terms):
+        if not isinstance(term, (tuple, list)) or len(term) != 3:
+            raise ValueError(f"term {j} is not a triple (coeff, names, qubits): {term!r}")
+        try:
+            c = complex(term[0])
+        except (TypeError, ValueError):
+            raise ValueError(f"term {j} has a coefficient that is not a number: {term[0]!r}") from None
+        if not np.isfinite(c):
+            raise ValueError(f"term {j} has a coefficient that is not finite: {term[0]!r}")
+        coeffs.append(c)
+        specs.append((term[1] if isinstance(term[1], str) else tuple(term[1]), tuple(term[2])))
+    table, codes = operator_strings(n, specs, ops)
+    eye = np.eye(2, dtype=np.complex128)
+    first, last = [], []
+    for j, row in enumerate(codes):
+        nz = np.flatnonzero(row)
+        if nz.size == 0:
+            raise ValueError(f"term {j} acts on no qubit: {terms[j]!r}")
+        first.append(int(nz[0])), last.append(int(nz[-1]))
+
+    def states(k):  # of the cut in front of site k
+        s = ["start"] if any(f >= k for f in first) else []
+        s += [j for j in range(len(terms)) if first[j] < k <= last[j]]
+        return s + (["done"] if any(e < k for e in last) else [])
+
+    cuts = [states(k) for k in range(n + 1)]
+    for k, s in enumerate(cuts):
+        if len(s) > MPO_MAX_BOND:
+            raise ValueError(f"the terms need {len(s)} states at cut {k}, above MPO_MAX_BOND = {MPO_MAX_BOND}")
+    tensors = []
+    for k in range(n):
+        li, ri = {s: i for i, s in enumerate(cuts[k])}, {s: i for i, s in enumerate(cuts[k + 1])}
+        W = np.zeros((len(li), len(ri), 2, 2), dtype=np.complex128)
+        if "start" in li and "start" in ri:
+            W[li["start"], ri["start"]] = eye
+        if "done" in li and "done" in ri:
+            W[li["done"], ri["done"]] = eye
+        for j, row in enumerate(codes):
+            if not first[j] <= k <= last[j]:
+                continue
+            o = table[row[k] - 1] if row[k] else eye
+            src = li["start"] if k == first[j] else li[j]
+            dst = ri["done"] if k == last[j] else ri[j]
+            W[src, dst] += coeffs[j] * o if k == first[j] else o
+        tensors.append(W)
+    return Mpo(tensors)
+
+
+def mpo_exponential(n_sites: int, a, b, J, lam) -> Mpo:
+    """``sum_{i<j} J lam^(j-i-1) a_i b_j`` as an MPO of bond 3 (states start, open, done): ``a`` and ``b`` are names of
+    ``LOCAL_OPS`` or 2 x 2 matrices.  ``n_sites >= 2``."""
+    n = int(n_sites)
+    if n < 2:
+        raise ValueError(f"mpo_exponential needs n_sites >= 2 (got {n_sites!r})")
+
+    def op(x, what):
+        if isinstance(x, str):
+            if x not in LOCAL_OPS:
+                raise ValueError(f"{what} = {x!r} is not a name of LOCAL_OPS")
+            return LOCAL_OPS[x]
+        m = np.asarray(x, dtype=np.complex128)
+        if m.shape != (2, 2) or not np.isfinite(m).all():
+            raise ValueError(f"{what} is not a finite 2 x 2 matrix")
+        return m
+
+    A, B, J, lam = op(a, "a"), op(b, "b"), complex(J), complex(lam)
+    if not (np.isfinite(J) and np.isfinite(lam)):
+        raise ValueError("J and lam must be finite")
+    eye = np.eye(2, dtype=np.complex128)
+    W = np.zeros((3, 3, 2, 2), dtype=np.complex128)
+    W[0, 0], W[0, 1], W[1, 1], W[1, 2], W[2, 2] = eye, J * A, lam * eye, B, eye
+
+    def states(k):  # of the cut in front of site k: start while a pair can still begin, open between the two ends, done behind an end
+        return [i for i, there in ((0, k <= n - 2), (1, 1 <= k <= n - 1), (2, k >= 2)) if there]
+
+    return Mpo([W[np.ix_(states(k), states(k + 1))] for k in range(n)])
 
 
 def _spectra_array(spectra) -> np.ndarray:
@@ -2143,6 +2350,25 @@ class Context:
         nrm = np.zeros(ns, dtype=np.float64)
         _check(lib().qk_operator_strings_host(self._h, xs.handle, table.shape[0], planes.ctypes.data, codes.shape[0], codes.ctypes.data, V.ctypes.data,
                                                nrm.ctypes.data), "qk_operator_strings_host")
+        V = V[..., 0] + 1j * V[..., 1]
+        return (V, nrm) if norms else V
+
+    def mpo_expectations(self, xs: MpsSet, mpos, norms: bool = False):
+        """Expectation values ``<psi| H_m |psi> / <psi|psi>`` of matrix-product operators (``Mpo``: sums of operator strings, see
+        ``mpo_from_terms``, ``mpo_exponential``, ``mpo_product``) for every state of an fp64 set: complex128 of shape (n_states,
+        n_mpos); with ``norms=True`` also <psi|psi> of each state (the bits of ``local_paulis``), as ``(V, norms)``.  One sweep
+        over an MPO's support costs about its bond times one operator string of that support, whatever the number of terms.  An
+        MPO whose tensors are all the 1 x 1 identity is exactly 1 + 0j; a bond-1 MPO gives the bits of its operator string; a value
+        is the same bits whatever the other states and MPOs of the call.  Synchronous."""
+        info = xs.info()
+        ns, n = info["n_states"], info["n_sites"]
+        ms = _mpo_list(mpos, n)
+        bonds = np.ascontiguousarray(np.stack([m.bonds for m in ms]), dtype=np.int32)
+        planes = np.ascontiguousarray(np.concatenate([m.packed() for m in ms]))
+        V = np.zeros((ns, len(ms), 2), dtype=np.float64)
+        nrm = np.zeros(ns, dtype=np.float64)
+        _check(lib().qk_mpo_expectations_host(self._h, xs.handle, len(ms), bonds.ctypes.data, planes.ctypes.data, V.ctypes.data, nrm.ctypes.data),
+               "qk_mpo_expectations_host")
         V = V[..., 0] + 1j * V[..., 1]
         return (V, nrm) if norms else V
 

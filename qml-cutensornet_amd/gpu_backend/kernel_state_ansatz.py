@@ -486,6 +486,10 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     rest of the route is the same, and K is the same bits for any number of ranks.  ``shots=None`` is the exact kernel.
     ``observables`` together with ``shots`` is a ``ValueError``.
 
+    ``observables=[Mpo, ...]`` (``engine.Mpo``: sums of operator strings such as a Hamiltonian, its square or a Hamming-weight
+    read-out) takes the real parts of ``Context.mpo_expectations`` as the feature columns of the same kernel.  A list that mixes
+    ``Mpo`` and Pauli strings is a ``ValueError``, and so are MPOs together with ``shots``.
+
     ``rdm=k, window=True`` for 3 <= k <= min(6, n_qubits) is the window form, the k-qubit member of the series:
         K_k[j, i] = exp(-g sum_a ||rho_{a,k}(X_i) - rho_{a,k}(Y_j)||_F^2),   a = 0 .. n_qubits - k,
     rho_{a,k} = the reduced density matrix of the qubits a .. a+k-1 (``Context.window_rdms``).  Each rank takes the window RDMs of
@@ -496,7 +500,7 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     is one too (those two keep their own routes).
 
     ``initial_states`` / ``initial_states_Y`` as in ``build_kernel_matrix``: the circuits are applied to given states."""
-    strings = None
+    strings = mpos = None
     if not isinstance(window, (bool, np.bool_)):
         raise ValueError(f"window must be True or False (got {window!r})")
     window = bool(window)
@@ -521,7 +525,15 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     if observables is not None:
         if rdm != 1 or pair_distance != 1:
             raise ValueError(f"observables chooses the features itself: leave rdm and pair_distance at 1 (got rdm={rdm!r}, pair_distance={pair_distance!r})")
-        strings = _engine.pauli_strings(int(ansatz.num_qubits), observables)  # ValueError: empty list, bad spec
+        obs = list(observables) if isinstance(observables, (list, tuple)) else observables
+        n_mpo = sum(isinstance(o, _engine.Mpo) for o in obs) if isinstance(obs, list) else 0
+        if n_mpo and n_mpo != len(obs):
+            raise ValueError("observables mixes Mpo and Pauli strings: give a list of one kind")
+        if n_mpo:
+            mpos = _engine._mpo_list(obs, int(ansatz.num_qubits))  # ValueError: an Mpo of another length
+        else:
+            strings = _engine.pauli_strings(int(ansatz.num_qubits), observables)  # ValueError: empty list, bad spec
+    n_obs = len(mpos) if mpos is not None else len(strings) if strings is not None else 0
     if not window and rdm not in (1, 2):
         raise ValueError(f"rdm must be 1 (one-qubit reduced density matrices), 2 (pairs) or, with window=True, 3 .. 6 (windows of that many qubits), got {rdm!r}")
     if rdm == 2 and int(ansatz.num_qubits) < 2:
@@ -575,13 +587,15 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         ctx.trim()  # the device builder's arena goes back before the local sweep needs memory
         t0 = time.perf_counter()
         if local is None:
-            shape = (0, len(strings)) if strings is not None else (0, n_qubits, 3) if rdm == 1 else (0, n_pairs, 4, 4)
+            shape = (0, n_obs) if n_obs else (0, n_qubits, 3) if rdm == 1 else (0, n_pairs, 4, 4)
             if window:
                 shape = (0, n_qubits - rdm + 1, 1 << rdm, 1 << rdm, 2)
             F, chi = np.zeros(shape, dtype=np.float64), np.zeros(0)
         else:
             if window:  # complex128 as (re, im) pairs of float64: the features travel as the other forms' do
                 F = np.ascontiguousarray(ctx.window_rdms(local, rdm)).view(np.float64).reshape(len(local), n_qubits - rdm + 1, 1 << rdm, 1 << rdm, 2)
+            elif mpos is not None:  # the real parts are the feature columns
+                F = np.ascontiguousarray(ctx.mpo_expectations(local, mpos).real)
             elif strings is not None:
                 F = ctx.pauli_expectations(local, strings)
             elif shots is not None:
@@ -602,13 +616,13 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     gather_secs = time.perf_counter() - t0
     if not is_root:
         return None
-    g = _engine.projected_gamma(pqk_gamma, len(strings) if strings is not None else n_qubits * pair_distance)  # (a window form has pair_distance 1)
+    g = _engine.projected_gamma(pqk_gamma, n_obs if n_obs else n_qubits * pair_distance)  # (a window form has pair_distance 1)
     _say(True, "\nFinished contracting all MPS.\n\nCalculating projected kernel matrix...")
     t0 = time.perf_counter()
     if window:
         rdms = [np.ascontiguousarray(f).view(np.complex128)[..., 0] for f in feats]
         kernel_mat = ctx.projected_window_gram(rdms[0], None if Y is None else rdms[1], g)
-    elif strings is not None:
+    elif n_obs:
         kernel_mat = ctx.feature_gram(feats[0], None if Y is None else feats[1], g)
     elif rdm == 1:
         kernel_mat = ctx.projected_gram(feats[0], None if Y is None else feats[1], g)
@@ -629,8 +643,8 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     prof["ave max chi y"] = (float(chi_y.mean()) if chi_y.size else 0.0, "chi y")
     prof["r0_RR_recv"] = [gather_secs, "seconds"]  # the all-gather of the Bloch vectors
     prof["pqk_gamma"] = [g, ""]
-    if strings is not None:
-        prof["pqk_observables"] = [len(strings), "strings"]
+    if n_obs:
+        prof["pqk_observables"] = [n_obs, "MPOs" if mpos is not None else "strings"]
     else:
         prof["pqk_rdm"] = [rdm, "qubits"]
     if rdm == 2:
@@ -920,6 +934,40 @@ def build_outcome_marginals(mpi_comm, ansatz, X, bits, bases, truncation_error=N
         local.close()
     out = _gather_features(mpi_comm, lo, p, len(X))
     return out if is_root else None
+
+
+def build_mpo_expectations(mpi_comm, ansatz, X, mpos, truncation_error=None):
+    """Expectation values of matrix-product operators under the states of ``X``: ``v[i, m] = <psi(x_i)| H_m |psi(x_i)> / <psi|psi>``
+    for a list of ``engine.Mpo`` shared by every state.  Each rank builds its share of the states (same builders, same
+    ``QK_BUILDER`` rules as ``build_projected_kernel_matrix``), evaluates the MPOs on its device (``Context.mpo_expectations``) and
+    the rows are all-gathered as (re, im) pairs, never an MPS.  Rank 0 returns complex128 (len(X), n_mpos), the other ranks
+    ``None``; a row is the same bits for any number of ranks."""
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    X = np.asarray(X, dtype=np.float64)
+    n_qubits = int(ansatz.num_qubits)
+    ms = _engine._mpo_list(mpos, n_qubits)  # raises ValueError that names the entry
+    fidelity = 1.0 - float(truncation_error)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: MPO observables have no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    ctx = _engine.default_context(device_id)
+    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
+    lo, local, _, _ = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers)
+    ctx.trim()  # the device builder's arena goes back before the chains need memory
+    if local is None:
+        v = np.zeros((0, len(ms), 2), dtype=np.float64)
+    else:
+        v = np.ascontiguousarray(ctx.mpo_expectations(local, ms)).view(np.float64).reshape(len(local), len(ms), 2)
+        local.close()
+    out = _gather_features(mpi_comm, lo, v, len(X))
+    return np.ascontiguousarray(out).view(np.complex128)[..., 0] if is_root else None
 
 
 def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64), max_discard=0.0, truncation_error=None, info_file=None, loglevel=30):

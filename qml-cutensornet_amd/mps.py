@@ -263,6 +263,42 @@ class MPS:
             out[m] = (E * R[supp[-1] + 1]).sum() / norm
         return out[0] if single else out
 
+    def mpo_expectation(self, mpo) -> complex:
+        """``<psi| H |psi> / <psi|psi>`` of an ``engine.Mpo`` on the host, complex: the numpy mirror of
+        ``Context.mpo_expectations`` and the oracle for sizes a dense matrix cannot reach.  A plain environment loop in the
+        X[ket][bra] orientation with one plane per MPO bond state: ``E[0] = L_a``, ``E'[v] = sum_{u,s,s'} W_k[u][v][s'][s] A^s^T
+        E[u] conj(A^s')`` over the support [a, b] (the hull of the sites whose tensor is not exactly the 1 x 1 identity), then
+        ``sum E[0] R_{b+1} / <psi|psi>``.  An MPO without a support is exactly 1 + 0j.  The state need not be normalised; a state
+        of norm 0 raises ``ValueError``."""
+        from .engine import Mpo
+
+        n = len(self.tensors)
+        if not isinstance(mpo, Mpo):
+            raise ValueError(f"mpo_expectation takes an engine.Mpo, got {type(mpo).__name__}")
+        if mpo.n_sites != n:
+            raise ValueError(f"the Mpo has {mpo.n_sites} sites, the state has {n}")
+        ts = [np.asarray(a, dtype=np.complex128) for a in self.tensors]
+        L, R = [None] * (n + 1), [None] * (n + 1)  # [ket][bra] at bond k
+        L[0] = np.ones((1, 1), dtype=np.complex128)
+        R[n] = np.ones((1, 1), dtype=np.complex128)
+        for k in range(n):
+            L[k + 1] = np.einsum("ab,asc,bsd->cd", L[k], ts[k], ts[k].conj(), optimize=True)
+        for k in range(n - 1, -1, -1):
+            R[k] = np.einsum("asc,cd,bsd->ab", ts[k], R[k + 1], ts[k].conj(), optimize=True)
+        norm = float(L[n][0, 0].real)
+        if norm == 0.0:
+            raise ValueError("mpo_expectation: the state has norm 0")
+        eye = np.eye(2, dtype=np.complex128).reshape(1, 1, 2, 2)
+        supp = [k for k, w in enumerate(mpo.tensors) if w.shape != eye.shape or not np.array_equal(w, eye)]
+        if not supp:
+            return 1.0 + 0.0j
+        E = L[supp[0]][None]  # [u][ket][bra]
+        for k in range(supp[0], supp[-1] + 1):
+            T = np.tensordot(E, ts[k], axes=(1, 0))                             # [u][b][s][c]
+            T = np.tensordot(mpo.tensors[k], T, axes=([0, 3], [0, 2]))          # [v][t][b][c]
+            E = np.tensordot(T, ts[k].conj(), axes=([1, 2], [1, 0]))            # [v][c][d]
+        return complex((E[0] * R[supp[-1] + 1]).sum() / norm)
+
     def marginal(self, bits, bases) -> np.ndarray:
         """Probabilities of partial outcomes on the host, float64 of shape (n_strings,): the numpy mirror of ``Context.marginals``.
         ``bits`` is (n_strings, n) of 0 / 1 (bit 0 = eigenvalue +1), ``bases`` (n_strings, n) or one shared row of codes 0..3: 0 =

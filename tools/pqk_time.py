@@ -169,6 +169,7 @@ def main():
     ap.add_argument("--window", type=int, default=0, metavar="W", help="also time window_rdms on all windows of W qubits and projected_window_gram")
     ap.add_argument("--amplitudes", type=int, default=0, metavar="S", help="also time amplitudes() with logp on S shots per state drawn with sample()")
     ap.add_argument("--marginals", type=int, default=0, metavar="N", help="with --strings: also time marginals() on N projector strings on the supports of those strings")
+    ap.add_argument("--mpo", default=None, choices=("heisenberg", "exponential"), help="also time mpo_expectations on this MPO (heisenberg: also its term list through operator_expectations)")
     args = ap.parse_args()
     if args.block_shots and not args.block_widths:
         ap.error("--block-shots needs --block-widths")
@@ -399,6 +400,38 @@ def main():
             "amp_sample_ms": round(amp_sample_ms, 3), "amp_over_sample": round(amp_ms / amp_sample_ms, 4),
             "max_abs_dlogp_amp_sample": float(np.abs(lp_amp - lp_sample).max()),
         })
+    if args.mpo:
+        def spread_ms(fn):
+            fn()  # warm-up
+            ts = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                out = fn()
+                ts.append(1e3 * (time.perf_counter() - t0))
+            return out, ts
+
+        if args.mpo == "heisenberg":  # J_x XX + J_y YY + J_z ZZ on neighbours and a field h Z: 3 (n - 1) + n terms, bond 5
+            terms = [(j, p + p, (k, k + 1)) for k in range(n - 1) for j, p in zip((1.0, 0.8, -0.6), "XYZ")] + [(0.5, "Z", (k,)) for k in range(n)]
+            H = engine.mpo_from_terms(n, terms)
+            n_terms, hulls = len(terms), sum(max(q) - min(q) + 1 for _, _, q in terms)
+        else:  # sum_{i<j} 0.7^(j-i-1) Z_i Z_j: n (n - 1) / 2 terms, bond 3
+            H = engine.mpo_exponential(n, "Z", "Z", 1.0, 0.7)
+            terms, n_terms, hulls = None, n * (n - 1) // 2, sum((n - d) * (d + 1) for d in range(1, n))
+        Vm, ts_h = spread_ms(lambda: ctx.mpo_expectations(xs, [H]))
+        planes = int(H.bonds[:-1].sum())  # stacked planes of the first GEMM, summed over the sites
+        dist.update({
+            "mpo": args.mpo, "mpo_bond": H.max_bond(), "mpo_terms": n_terms, "mpo_reps": args.reps, "mpo_ms": round(float(np.median(ts_h)), 3),
+            "mpo_ms_min": round(min(ts_h), 3), "mpo_ms_max": round(max(ts_h), 3), "mpo_plane_sites": planes, "mpo_terms_sum_hulls": int(hulls),
+            "mpo_expected_work_ratio": round(planes / hulls, 4), "mpo_max_abs_value": float(np.abs(Vm).max()),
+        })
+        if terms is not None:
+            coeff = np.array([c for c, _, _ in terms], dtype=np.complex128)
+            specs = [(names, qubits) for _, names, qubits in terms]
+            Vt, ts_t = spread_ms(lambda: ctx.operator_expectations(xs, specs) @ coeff)
+            dist.update({
+                "mpo_terms_ms": round(float(np.median(ts_t)), 3), "mpo_terms_ms_min": round(min(ts_t), 3), "mpo_terms_ms_max": round(max(ts_t), 3),
+                "mpo_over_terms": round(float(np.median(ts_h)) / float(np.median(ts_t)), 4), "max_abs_d_mpo_terms": float(np.abs(Vm[:, 0] - Vt).max()),
+            })
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
         "max_bond": int(info["dims"].max()), "build_s": round(build_s, 3),
