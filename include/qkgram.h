@@ -426,6 +426,27 @@ int qk_mpo_expectations_host(qk_ctx* ctx, const qk_mps_set* set, int32_t n_mpos,
                              const double* tensors /* MPO-major, site-major: [w_k][w_{k+1}][2][2][2] (re, im), packed */,
                              double* out /* [n_states][n_mpos][2] */, double* norms /* [n_states], may be NULL */);
 
+/* A new set O|psi> of one matrix-product operator and every state of an fp64 set, synchronous on the context's stream.  The MPO is
+ * given in the conventions and packing of qk_mpo_expectations_host (one MPO: bonds[n_sites + 1], tensors site-major).  With the
+ * source's site tensors A_k[a][s][b] of true bonds chi_k, the product has true bonds w_k chi_k and the sites
+ *     B_k[(u, a)][s'][(v, b)] = sum_s W_k[u][v][s'][s] A_k[a][s][b],     row u chi_k + a, column v chi_{k+1} + b
+ * in the padded split-plane layout of qk_mps_set_create (every new bond padded to a multiple of 16, states and sites in order), in a
+ * set that owns its memory.  Expression order: an element is the sum over s = 0 before s = 1 of its block (u, v), the imaginary
+ * factor before the real one, each real component one chain of fused multiply-adds that starts with a plain product -- the
+ * expression of one block of qk_mpo_expectations_host's mix.  A block (u, v) whose four entries are all exactly zero is not read
+ * and gives exact zeros, also against a NaN in the source; padding rows and columns are zero.  The kernel writes the zeros: there is
+ * no memset, and every double of the new image is written by this call, once.  A site whose W_k is the exact 1 x 1 identity is
+ * copied bit for bit, so an MPO of such sites gives an image bit-equal to qk_mps_set_copy_image of a source in that layout.  The
+ * result records no centre (qk_mps_set_centre = -1); the source is untouched.  A state's product is the same bits whatever the other
+ * states of the set and their order, and from run to run.  One launch of qk_mpo_apply_kernel per call; the new set is allocated
+ * whole (about max_k w_k w_{k+1} times the source).
+ * QK_EINVAL, before anything runs: a null ctx, src, bonds, tensors or out; a set of another context; a complex64 set; a bond
+ * outside 1 .. 32 (the message names the cut); bonds[0] or bonds[n_sites] not 1; a tensor entry that is not finite (site and
+ * indices); a product bond w_k chi_k above 512 (state and bond) -- 512 is the limit of qk_mps_set_compress and of the fused Gram
+ * sweep, so every consumer takes every result.  QK_EDEVICE: an allocation that fails (the message names the bytes asked for).   */
+int qk_mps_set_apply_mpo(qk_ctx* ctx, const qk_mps_set* src, const int32_t* bonds /* [n_sites + 1] */,
+                         const double* tensors /* site-major [w_k][w_{k+1}][2][2][2] */, qk_mps_set** out);
+
 /* The Gram of any real feature columns (host arrays [n][n_features], for instance qk_pauli_strings_host's output), synchronous:
  *     out[j * ld + i] = exp(-g * sum_m (fx[i][m] - fy[j][m])^2)
  * Rows, columns, fy = NULL, the fixed summation order (exact symmetry, unit diagonal) and the argument errors are those of

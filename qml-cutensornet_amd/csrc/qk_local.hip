@@ -1296,6 +1296,194 @@ int mpo_chains(qk_ctx* c, const qk_mps_set* set, const int32_t n_mpos, const int
   return QK_OK;
 }
 
+// ---- applying an MPO to a set (qk_mps_set_apply_mpo) ------------------------------------------------------------------------------
+// The new set O|psi> of one MPO and every state of a set, site by site:
+//     B_k[(u, a)][s'][(v, b)] = sum_s W_k[u][v][s'][s] A_k[a][s][b],   row u chi_k + a, column v chi_{k+1} + b
+// A write-bound expansion with no dependency between sites: one launch, no atomics, no grid barrier, no spin wait.  The bonds, the
+// offsets, the row lists of the blocks and the tasks are apply_plan's (qk_local_plan.h).  A workgroup takes one (state, site, u,
+// 16-row chunk of a): it stages the listed blocks of row W_k[u][.] in LDS (at most MPO_MAX_BOND blocks, 2 KiB, read as broadcasts),
+// a thread holds the A values of two neighbouring b of one row in registers and streams the column blocks v = 0 .. w_{k+1} - 1 out
+// with 16-byte stores where the column v chi_{k+1} + b is even, 8-byte stores where it is odd (odd chi_{k+1} and odd v) and for the
+// last b of an odd chi_{k+1}.  A v without a listed block, the padding columns and the padding rows are written as zeros by the
+// kernel: there is no memset, every double of the image is written once.  An element is qk_mpo_mix_kernel's expression of one
+// block; a site marked as a copy passes the source bits through.
+struct ApplyArgs {
+  const double* src;      // the source set's planes and its tables
+  const int32_t* spad;    // padded bonds [n_states][n_sites + 1]
+  const int32_t* stru;    // true bonds
+  const int64_t* soffs;   // re-plane offsets [n_states][n_sites]
+  double* dst;            // the new set's planes and its tables
+  const int32_t* dpad;
+  const int64_t* doffs;
+  const int32_t* wb;      // the MPO's bonds [n_sites + 1]
+  const int32_t* copy;    // [n_sites]
+  const int32_t* uat;     // [n_sites]
+  const int32_t* ufirst;
+  const int32_t* blk_v;
+  const double* blk_w;
+  const int2* tasks;
+  int n_sites;
+};
+
+__device__ __forceinline__ void apply_store2(double* const p, const double x, const double y, const bool wide, const bool two) {
+  if (wide) {
+    *reinterpret_cast<double2*>(p) = make_double2(x, y);
+  } else {
+    p[0] = x;
+    if (two) p[1] = y;
+  }
+}
+
+__global__ __launch_bounds__(LOC_RED_THREADS) void qk_mpo_apply_kernel(const ApplyArgs g) {
+  __shared__ double cw[MPO_MAX_BOND * 8];
+  __shared__ int cj[MPO_MAX_BOND];  // v -> its staged block, -1: none
+  const int2 t = g.tasks[blockIdx.x];
+  const int n = g.n_sites, n1 = n + 1;
+  const long long st = t.x / n;
+  const int k = t.x % n, u = apply_task_u(t.y), c = apply_task_chunk(t.y);
+  const int wl = g.wb[k], wr = min(g.wb[k + 1], MPO_MAX_BOND);
+  const int l = g.stru[st * n1 + k], r = g.stru[st * n1 + k + 1];
+  const long long pl = g.spad[st * n1 + k], pr = g.spad[st * n1 + k + 1];
+  const long long PL = g.dpad[st * n1 + k], PR = g.dpad[st * n1 + k + 1];
+  const bool copy = g.copy[k] != 0;
+  const int f0 = g.ufirst[g.uat[k] + u], nblk = min(g.ufirst[g.uat[k] + u + 1] - f0, MPO_MAX_BOND);
+  for (int e = threadIdx.x; e < MPO_MAX_BOND; e += LOC_RED_THREADS) cj[e] = -1;
+  for (int e = threadIdx.x; e < 8 * nblk; e += LOC_RED_THREADS) cw[e] = g.blk_w[8ll * f0 + e];
+  __syncthreads();
+  for (int e = threadIdx.x; e < nblk; e += LOC_RED_THREADS) cj[g.blk_v[f0 + e] & (MPO_MAX_BOND - 1)] = e;
+  __syncthreads();
+  const double* const Are = g.src + g.soffs[st * n + k];
+  const double* const Aim = Are + pl * 2 * pr;
+  double* const Bre = g.dst + g.doffs[st * n + k];
+  const long long dpl = PL * 2 * PR;  // the im plane lies dpl behind the re plane
+  const int a0 = LOC_CHUNK * c, rows = min(LOC_CHUNK, l - a0), half = (r + 1) / 2;
+  for (int e = threadIdx.x; e < rows * half; e += LOC_RED_THREADS) {
+    const int a = a0 + e / half, b = 2 * (e % half);
+    const bool two = b + 1 < r;
+    const long long q0 = (long long)a * 2 * pr + b, q1 = q0 + pr;  // even: pr is a multiple of 16, so b + 1 lies inside the padded row
+    const double2 r0 = *reinterpret_cast<const double2*>(Are + q0), i0 = *reinterpret_cast<const double2*>(Aim + q0);
+    const double2 r1 = *reinterpret_cast<const double2*>(Are + q1), i1 = *reinterpret_cast<const double2*>(Aim + q1);
+    double* const row = Bre + ((long long)u * l + a) * 2 * PR;
+    for (int v = 0; v < wr; ++v) {
+      const int j = cj[v], col = v * r + b;
+      const bool wide = two && !(col & 1);
+      double2 o0r = make_double2(0, 0), o0i = o0r, o1r = o0r, o1i = o0r;
+      if (copy) {
+        o0r = r0, o0i = i0, o1r = r1, o1i = i1;
+      } else if (j >= 0) {
+        const double* const o = cw + 8 * j;
+        const double ar = o[0], ai = o[1], br = o[2], bi = o[3], cr = o[4], ci = o[5], dr = o[6], di = o[7];  // W[u][v] = [[a, b], [c, d]]
+        o0r.x = fma(br, r1.x, fma(-bi, i1.x, fma(ar, r0.x, -(ai * i0.x))));
+        o0i.x = fma(br, i1.x, fma(bi, r1.x, fma(ar, i0.x, ai * r0.x)));
+        o1r.x = fma(dr, r1.x, fma(-di, i1.x, fma(cr, r0.x, -(ci * i0.x))));
+        o1i.x = fma(dr, i1.x, fma(di, r1.x, fma(cr, i0.x, ci * r0.x)));
+        o0r.y = fma(br, r1.y, fma(-bi, i1.y, fma(ar, r0.y, -(ai * i0.y))));
+        o0i.y = fma(br, i1.y, fma(bi, r1.y, fma(ar, i0.y, ai * r0.y)));
+        o1r.y = fma(dr, r1.y, fma(-di, i1.y, fma(cr, r0.y, -(ci * i0.y))));
+        o1i.y = fma(dr, i1.y, fma(di, r1.y, fma(cr, i0.y, ci * r0.y)));
+      }
+      apply_store2(row + col, o0r.x, o0r.y, wide, two);
+      apply_store2(row + col + dpl, o0i.x, o0i.y, wide, two);
+      apply_store2(row + col + PR, o1r.x, o1r.y, wide, two);
+      apply_store2(row + col + PR + dpl, o1i.x, o1i.y, wide, two);
+    }
+  }
+  // the padding columns of the task's rows (both s')
+  const int c0 = wr * r, npc = (int)PR - c0;
+  for (int e = threadIdx.x; e < rows * 2 * npc; e += LOC_RED_THREADS) {
+    double* const p = Bre + (((long long)u * l + a0) * 2 + e / npc) * PR + c0 + e % npc;
+    p[0] = 0.0, p[dpl] = 0.0;
+  }
+  // the padding rows of the site, by the task of the last u and the last chunk: one even run of doubles per plane
+  if (u == wl - 1 && a0 + LOC_CHUNK >= l) {
+    const long long z0 = (long long)wl * l * 2 * PR, nz = (dpl - z0) / 2;
+    for (long long e = threadIdx.x; e < nz; e += LOC_RED_THREADS) {
+      *reinterpret_cast<double2*>(Bre + z0 + 2 * e) = make_double2(0, 0);
+      *reinterpret_cast<double2*>(Bre + dpl + z0 + 2 * e) = make_double2(0, 0);
+    }
+  }
+}
+
+int apply_mpo(qk_ctx* c, const qk_mps_set* src, const int32_t* bonds, const double* tensors, qk_mps_set** out) {
+  static const char* what = "qk_mps_set_apply_mpo";
+  if (!c) return qk_fail(QK_EINVAL, "%s: ctx is null", what);
+  if (!src) return qk_fail(QK_EINVAL, "%s: src is null", what);
+  if (!bonds) return qk_fail(QK_EINVAL, "%s: bonds is null", what);
+  if (!tensors) return qk_fail(QK_EINVAL, "%s: tensors is null", what);
+  if (!out) return qk_fail(QK_EINVAL, "%s: out is null", what);
+  *out = nullptr;
+  if (src->ctx != c) return qk_fail(QK_EINVAL, "%s: set belongs to another context", what);
+  if (src->precision != 64) return qk_fail(QK_EINVAL, "%s: set is complex64; applying an MPO needs an fp64 set", what);
+  const int ns = src->n_states, n = src->n_sites, n1 = n + 1;
+  if (n < 1 || ns < 1) return qk_fail(QK_EINVAL, "%s: set is empty", what);
+  if ((long long)ns * n > std::numeric_limits<int32_t>::max()) return qk_fail(QK_EINVAL, "%s: %d states of %d sites are more (state, site) pairs than a task holds", what, ns, n);
+  if (const long long bad = mpo_bad_bond(bonds, 1, n); bad >= 0)
+    return qk_fail(QK_EINVAL, "%s: bonds[%d] = %d is outside 1 .. %d (cut %d)", what, (int)bad, bonds[bad], MPO_MAX_BOND, (int)bad);
+  for (const int k : {0, n})
+    if (bonds[k] != 1) return qk_fail(QK_EINVAL, "%s: bonds[%d] = %d must be 1 (the end of the MPO)", what, k, bonds[k]);
+  {
+    long long e = 0;
+    for (int k = 0; k < n; ++k) {
+      const int wr = bonds[k + 1];
+      for (long long q = 0; q < 8ll * bonds[k] * wr; ++q, ++e)
+        if (!std::isfinite(tensors[e]))
+          return qk_fail(QK_EINVAL, "%s: site %d: W[%d][%d][%d][%d] has a %s part that is not finite", what, k, (int)(q / 8 / wr), (int)(q / 8 % wr), (int)(q / 4 % 2), (int)(q / 2 % 2),
+                         q % 2 ? "imaginary" : "real");
+    }
+  }
+  const MpoPlan mp = mpo_plan(bonds, tensors, 1, n);
+  const ApplyPlan ap = apply_plan(src->dims_true.data(), ns, n, mp);
+  if (ap.bad_state >= 0)
+    return qk_fail(QK_EINVAL, "%s: state %d, bond %d: the product bond %d x %d = %d is above %d", what, ap.bad_state, ap.bad_bond, bonds[ap.bad_bond],
+                   (int)src->dims_true[(size_t)ap.bad_state * n1 + ap.bad_bond], bonds[ap.bad_bond] * (int)src->dims_true[(size_t)ap.bad_state * n1 + ap.bad_bond], APPLY_MAX_BOND);
+  if (ap.tasks.size() > (size_t)std::numeric_limits<int32_t>::max()) return qk_fail(QK_EINVAL, "%s: %zu tasks are more than one launch holds", what, ap.tasks.size());
+  QkRangeGuard range_("qk:apply_mpo");
+  HIP_TRY_AS(what, hipSetDevice(c->device));
+  HIP_TRY_AS(what, hipStreamSynchronize(c->stream));
+  // the tables of the MPO and the tasks, uploaded once: bonds | copy | uat | ufirst | blk_v | blk_w | tasks
+  const std::vector<std::pair<const void*, size_t>> regions{{mp.bonds.data(), mp.bonds.size() * sizeof(int32_t)},   {ap.copy.data(), ap.copy.size() * sizeof(int32_t)},
+                                                            {ap.uat.data(), ap.uat.size() * sizeof(int32_t)},       {ap.ufirst.data(), ap.ufirst.size() * sizeof(int32_t)},
+                                                            {ap.blk_v.data(), ap.blk_v.size() * sizeof(int32_t)},   {ap.blk_w.data(), ap.blk_w.size() * sizeof(double)},
+                                                            {ap.tasks.data(), ap.tasks.size() * sizeof(Task2)}};
+  std::vector<size_t> rat;
+  size_t tab_bytes = 0;
+  for (const auto& rg : regions) rat.push_back(tab_bytes), tab_bytes += al256(std::max<size_t>(rg.second, 8));
+  QkDevBuf dtab;
+  HIP_TRY_AS(what, dtab.alloc(tab_bytes));
+  qk_mps_set* m = nullptr;
+  if (const int rc = qk_mps_set_alloc(c, ns, n, ap.total * (long long)sizeof(double), 64, &m, what)) return rc;  // QK_EDEVICE names the bytes
+  m->max_pad = ap.max_pad;
+  m->dims_true = ap.tru;
+  hipError_t e = hipSuccess;
+  for (size_t i = 0; i < regions.size() && e == hipSuccess; ++i)
+    if (regions[i].second) e = hipMemcpyAsync(dtab.get<char>() + rat[i], regions[i].first, regions[i].second, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_dims.get(), ap.pad.data(), ap.pad.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_true.get(), ap.tru.data(), ap.tru.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(m->d_offs.get(), ap.offs.data(), ap.offs.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    ApplyArgs a{};
+    a.src = src->d_data.get<double>(), a.spad = src->d_dims.get<int32_t>(), a.stru = src->d_true.get<int32_t>(), a.soffs = src->d_offs.get<int64_t>();
+    a.dst = m->d_data.get<double>(), a.dpad = m->d_dims.get<int32_t>(), a.doffs = m->d_offs.get<int64_t>();
+    a.wb = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[0]);
+    a.copy = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[1]);
+    a.uat = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[2]);
+    a.ufirst = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[3]);
+    a.blk_v = reinterpret_cast<const int32_t*>(dtab.get<char>() + rat[4]);
+    a.blk_w = reinterpret_cast<const double*>(dtab.get<char>() + rat[5]);
+    a.tasks = reinterpret_cast<const int2*>(dtab.get<char>() + rat[6]);
+    a.n_sites = n;
+    qk_mpo_apply_kernel<<<dim3((unsigned)ap.tasks.size()), dim3(LOC_RED_THREADS), 0, c->stream>>>(a);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the host tables and dtab go when this returns
+  if (e != hipSuccess) {
+    qk_mps_set_destroy(m);
+    return qk_fail(QK_EDEVICE, "%s: %s", what, hipGetErrorString(e));
+  }
+  *out = m;
+  return QK_OK;
+}
+
 // ---- bond purities and entanglement spectra (qk_bond_purities_host, qk_bond_spectra_host) --------------------------------------
 // Bond k (k = 1 .. n-1) cuts the chain between sites k-1 and k.  With the kept environments of the environment pass,
 //     N_k = R_k L_k^T / <psi|psi>     (chi_k x chi_k, tr N_k = 1; its eigenvalues are the Schmidt weights of the cut)
@@ -3156,6 +3344,9 @@ extern "C" int qk_operator_strings_host(qk_ctx* c, const qk_mps_set* set, int32_
 }
 extern "C" int qk_mpo_expectations_host(qk_ctx* c, const qk_mps_set* set, int32_t n_mpos, const int32_t* bonds, const double* tensors, double* out, double* norms) {
   return mpo_chains(c, set, n_mpos, bonds, tensors, out, norms);
+}
+extern "C" int qk_mps_set_apply_mpo(qk_ctx* c, const qk_mps_set* src, const int32_t* bonds, const double* tensors, qk_mps_set** out) {
+  return apply_mpo(c, src, bonds, tensors, out);
 }
 
 extern "C" int qk_feature_gram_host(qk_ctx* c, int32_t n_features, int32_t nx, const double* fx, int32_t ny, const double* fy, double g, double* out, int64_t ld) {

@@ -1109,4 +1109,87 @@ inline void mpo_lists(const EnvSizes& z, const int s0, const Chains& c, const si
   first.push_back((long long)tasks.size());
 }
 
+// ---- applying an MPO to a set (qk_mps_set_apply_mpo) --------------------------------------------------------------------------------
+// The product of one MPO (an MpoPlan of one MPO) with every state of a set: site k of a state with true bonds chi_k becomes
+//     B_k[(u, a)][s'][(v, b)] = sum_s W_k[u][v][s'][s] A_k[a][s][b],   row u chi_k + a, column v chi_{k+1} + b
+// with true bonds w_k chi_k, each padded to a multiple of 16, in the split-plane layout of a set, states and sites in order without
+// gaps (the layout qk_mps_set_create makes).  A product bond above APPLY_MAX_BOND is refused: bad_state / bad_bond name the first
+// one and no table is made.  Per site the listed blocks of mpo_plan are listed again by row: the blocks of row u are
+// [ufirst[uat[k] + u], ufirst[uat[k] + u + 1]) in ascending v; a site that is the exact 1 x 1 identity is marked in `copy` and
+// keeps one block (0, 0) with the identity's entries.  A task is one (state, site, u, 16-row chunk of a): x = state n + site,
+// y = u << 8 | chunk.  It writes its rows over the whole padded width -- the columns of a v without a block and the padding columns
+// as zeros -- and the task of the last u and the last chunk also writes the padding rows, so the tasks of a call write every
+// double of the new image exactly once.  Offsets and the total are 64-bit.
+constexpr int APPLY_MAX_BOND = 512;  // SPEC_QMAX of the compress sweep and the limit of the fused Gram sweep: every consumer takes every product
+struct ApplyPlan {
+  int n_states = 0, n_sites = 0, max_pad = 0;
+  int bad_state = -1, bad_bond = -1;  // the first w_k chi_k above APPLY_MAX_BOND
+  long long total = 0;                // doubles of the new image
+  long long read = 0;                 // doubles of the source the tasks read: every true element of a site once per u
+  std::vector<int32_t> tru, pad;      // [n_states][n_sites + 1]: the new true and padded bonds
+  std::vector<int64_t> offs;          // [n_states][n_sites]: re-plane offsets (doubles) in the new image
+  std::vector<int32_t> copy;          // [n_sites]: 1 = W_k is the exact 1 x 1 identity (the site is copied bit for bit)
+  std::vector<int32_t> uat;           // [n_sites]: where the site's w_k + 1 entries of ufirst start
+  std::vector<int32_t> ufirst;        // block indices
+  std::vector<int32_t> blk_u, blk_v;  // per listed block, by site, then u, then v (blk_u is host-only: the tests read it)
+  std::vector<double> blk_w;          // per listed block: (re, im) of W[u][v][s'][s], s' major
+  std::vector<Task2> tasks;
+};
+QK_HD constexpr int apply_task_u(const int y) { return y >> 8; }
+QK_HD constexpr int apply_task_chunk(const int y) { return y & 255; }
+inline ApplyPlan apply_plan(const int32_t* src_tru, const int ns, const int n, const MpoPlan& mp) {
+  ApplyPlan ap;
+  ap.n_states = ns, ap.n_sites = n;
+  const int n1 = n + 1;
+  const int32_t* w = mp.bonds.data();  // MPO 0
+  for (int s = 0; s < ns && ap.bad_state < 0; ++s)
+    for (int k = 0; k <= n; ++k)
+      if ((long long)w[k] * src_tru[(size_t)s * n1 + k] > APPLY_MAX_BOND) {
+        ap.bad_state = s, ap.bad_bond = k;
+        break;
+      }
+  if (ap.bad_state >= 0) return ap;
+  ap.tru.resize((size_t)ns * n1), ap.pad.resize((size_t)ns * n1), ap.offs.resize((size_t)ns * n);
+  for (int s = 0; s < ns; ++s) {
+    for (int k = 0; k <= n; ++k) {
+      const int x = w[k] * src_tru[(size_t)s * n1 + k];
+      ap.tru[(size_t)s * n1 + k] = x, ap.pad[(size_t)s * n1 + k] = qk_pad16(x);
+      ap.max_pad = std::max(ap.max_pad, qk_pad16(x));
+    }
+    for (int k = 0; k < n; ++k) {
+      ap.offs[(size_t)s * n + k] = ap.total;
+      ap.total += 2ll * ap.pad[(size_t)s * n1 + k] * 2 * ap.pad[(size_t)s * n1 + k + 1];
+      ap.read += 4ll * w[k] * src_tru[(size_t)s * n1 + k] * src_tru[(size_t)s * n1 + k + 1];
+    }
+  }
+  ap.copy.assign(n, 0), ap.uat.resize(n);
+  for (int k = 0; k < n; ++k) {
+    ap.uat[k] = (int32_t)ap.ufirst.size();
+    const int at = mp.vat[k];
+    if (at < 0) {  // the exact 1 x 1 identity
+      ap.copy[k] = 1;
+      ap.ufirst.push_back((int32_t)ap.blk_v.size());
+      ap.blk_u.push_back(0), ap.blk_v.push_back(0);
+      const double eye[8] = {1, 0, 0, 0, 0, 0, 1, 0};
+      ap.blk_w.insert(ap.blk_w.end(), eye, eye + 8);
+    } else {
+      for (int u = 0; u < w[k]; ++u) {
+        ap.ufirst.push_back((int32_t)ap.blk_v.size());
+        for (int v = 0; v < w[k + 1]; ++v)
+          for (int j = mp.vfirst[at + v]; j < mp.vfirst[at + v + 1]; ++j)
+            if (mp.blk_u[j] == u) {
+              ap.blk_u.push_back(u), ap.blk_v.push_back(v);
+              ap.blk_w.insert(ap.blk_w.end(), mp.blk_w.begin() + 8 * (size_t)j, mp.blk_w.begin() + 8 * (size_t)j + 8);
+            }
+      }
+    }
+    ap.ufirst.push_back((int32_t)ap.blk_v.size());
+  }
+  for (int s = 0; s < ns; ++s)
+    for (int k = 0; k < n; ++k)
+      for (int u = 0; u < w[k]; ++u)
+        for (int c = 0; c < (src_tru[(size_t)s * n1 + k] + LOC_CHUNK - 1) / LOC_CHUNK; ++c) ap.tasks.push_back(Task2{s * n + k, u << 8 | c});
+  return ap;
+}
+
 }  // namespace qkl

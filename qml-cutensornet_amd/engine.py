@@ -112,6 +112,7 @@ _SIGNATURES = [
     ("qk_pauli_strings_host", C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     ("qk_operator_strings_host", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     ("qk_mpo_expectations_host", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("qk_mps_set_apply_mpo", C.c_int, [_P, _P, _P, _P, C.POINTER(_P)]),
     ("qk_feature_gram_host", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, C.c_int64]),
     ("qk_bond_purities_host", C.c_int, [_P, _P, _P, _P]),
     ("qk_bond_spectra_host", C.c_int, [_P, _P, C.c_int32, _P, _P]),
@@ -1070,6 +1071,89 @@ def mpo_exponential(n_sites: int, a, b, J, lam) -> Mpo:
         return [i for i, there in ((0, k <= n - 2), (1, 1 <= k <= n - 1), (2, k >= 2)) if there]
 
     return Mpo([W[np.ix_(states(k), states(k + 1))] for k in range(n)])
+
+
+def _mpo_qubits(n: int, qubits, what: str) -> list:
+    try:
+        qs = [int(q) for q in qubits]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: qubits must be a sequence of ints, got {qubits!r}") from None
+    if not qs:
+        raise ValueError(f"{what}: the list of qubits is empty")
+    if len(set(qs)) != len(qs):
+        raise ValueError(f"{what}: a qubit is named twice in {qs}")
+    for q in qs:
+        if not 0 <= q < n:
+            raise ValueError(f"{what}: qubit {q} is outside a register of {n}")
+    return qs
+
+
+def mpo_parity_projector(n_sites: int, sign=+1, qubits=None) -> Mpo:
+    """The projector ``(1 + sign prod_{q in qubits} Z_q) / 2`` on the even (sign = +1) or odd (sign = -1) parity sector of
+    ``qubits`` (default: all).  Bond 2 inside the hull of ``qubits`` (state 0 carries the identity, state 1 the Z string; both
+    factors 1/2 sit on the first site of the hull), the exact 1 x 1 identity outside; a single qubit gives bond 1."""
+    n = int(n_sites)
+    if n < 1:
+        raise ValueError(f"mpo_parity_projector needs n_sites >= 1 (got {n_sites!r})")
+    if isinstance(sign, bool) or sign not in (1, -1):
+        raise ValueError(f"sign must be +1 or -1, got {sign!r}")
+    qs = set(_mpo_qubits(n, range(n) if qubits is None else qubits, "mpo_parity_projector"))
+    lo, hi = min(qs), max(qs)
+    eye, Z = np.eye(2, dtype=np.complex128), LOCAL_OPS["Z"]
+    tensors = []
+    for k in range(n):
+        z = Z if k in qs else eye
+        if k < lo or k > hi:
+            W = eye.reshape(1, 1, 2, 2)
+        elif lo == hi:
+            W = (0.5 * (eye + sign * Z)).reshape(1, 1, 2, 2)
+        elif k == lo:
+            W = np.stack([0.5 * eye, 0.5 * sign * z]).reshape(1, 2, 2, 2)
+        elif k == hi:
+            W = np.stack([eye, z]).reshape(2, 1, 2, 2)
+        else:
+            W = np.zeros((2, 2, 2, 2), dtype=np.complex128)
+            W[0, 0], W[1, 1] = eye, z
+        tensors.append(W)
+    return Mpo(tensors)
+
+
+def mpo_two_qubit_gate(n_sites: int, a: int, b: int, U) -> Mpo:
+    """A 4 x 4 matrix on qubits (a, b), any distance apart, as an MPO in operator-Schmidt form: ``U = sum_j sigma_j L_j (x) R_j``
+    with ``U`` in the index convention of ``Unitary2q`` (index (s_a, s_b), a most significant; rows are the outcome).  Terms with
+    ``sigma_j <= 1e-14 sigma_0`` are dropped, so the bond is the operator-Schmidt rank (<= 4; 2 for CX); ``sigma_j L_j`` sits on
+    the lower qubit, ``R_j`` on the higher one, the identity carries each kept term over the sites between them, and the sites
+    outside hold the exact 1 x 1 identity.  For a > b the two qubit roles are exchanged, as ``Unitary2q`` does.  ``U`` need not be
+    unitary."""
+    n = int(n_sites)
+    a, b = _mpo_qubits(n, (a, b), "mpo_two_qubit_gate")
+    try:
+        M = np.asarray(U, dtype=np.complex128)
+    except (TypeError, ValueError):
+        raise ValueError("mpo_two_qubit_gate: U is not a 4 x 4 matrix") from None
+    if M.shape != (4, 4) or not np.isfinite(M).all():
+        raise ValueError(f"mpo_two_qubit_gate: U must be a finite 4 x 4 matrix, got shape {M.shape}")
+    T = M.reshape(2, 2, 2, 2)  # [p_a][p_b][s_a][s_b]
+    if a > b:
+        T, a, b = T.transpose(1, 0, 3, 2), b, a
+    u, sig, vh = np.linalg.svd(T.transpose(0, 2, 1, 3).reshape(4, 4))  # [(p_lo, s_lo)][(p_hi, s_hi)]
+    if not sig[0] > 0.0:
+        raise ValueError("mpo_two_qubit_gate: U is zero")
+    r = int((sig > 1e-14 * sig[0]).sum())
+    eye = np.eye(2, dtype=np.complex128)
+    tensors = []
+    for k in range(n):
+        if k < a or k > b:
+            W = eye.reshape(1, 1, 2, 2)
+        elif k == a:
+            W = (u[:, :r] * sig[:r]).T.reshape(1, r, 2, 2)
+        elif k == b:
+            W = vh[:r].reshape(r, 1, 2, 2)
+        else:
+            W = np.zeros((r, r, 2, 2), dtype=np.complex128)
+            W[np.arange(r), np.arange(r)] = eye
+        tensors.append(np.ascontiguousarray(W))
+    return Mpo(tensors)
 
 
 def _spectra_array(spectra) -> np.ndarray:
@@ -2371,6 +2455,49 @@ class Context:
                "qk_mpo_expectations_host")
         V = V[..., 0] + 1j * V[..., 1]
         return (V, nrm) if norms else V
+
+    def apply_mpo(self, xs: MpsSet, mpo, max_bond: int | None = None, max_discard: float | None = None, value_of_zero: float = 1e-16, info: bool = False):
+        """A new fp64 set with ``O|psi>`` for every state of ``xs`` and one ``Mpo`` (the device twin of ``MPS.apply_mpo``): true
+        bonds ``w_k chi_k``, site ``B_k[(u, a)][s'][(v, b)] = sum_s W_k[u][v][s'][s] A_k[a][s][b]`` (row ``u chi_k + a``, column
+        ``v chi_{k+1} + b``), general gauge (``centre`` = -1), not normalised; ``xs`` is left untouched.  With neither ``max_bond``
+        nor ``max_discard`` the exact product is returned; a product bond above 512 is an error.  Otherwise the product goes
+        through ``compress(max_bond, max_discard or 0, value_of_zero)`` and is closed.  ``info=True`` returns ``(set, info)`` with
+        the product's bond table as ``product_bond_dims`` and, where it was compressed, ``compress``'s info.  A state's product is
+        the same bits whatever the other states of the set.  Synchronous."""
+        if not isinstance(mpo, Mpo):
+            raise ValueError(f"apply_mpo takes one Mpo, got {type(mpo).__name__}")
+        st = xs.info()
+        ns, n = st["n_states"], st["n_sites"]
+        if mpo.n_sites != n:
+            raise ValueError(f"the Mpo has {mpo.n_sites} sites, the states have {n}")
+        bonds = np.ascontiguousarray(mpo.bonds, dtype=np.int32)
+        planes = np.ascontiguousarray(mpo.packed())
+        h = _P()
+        _check(lib().qk_mps_set_apply_mpo(self._h, xs.handle, bonds.ctypes.data, planes.ctypes.data, C.byref(h)), "qk_mps_set_apply_mpo")
+        out = MpsSet(self, h, np.zeros((ns, n + 1), dtype=np.int32))
+        out.dims = out.image()[2]
+        extra = {"product_bond_dims": out.dims.copy()}
+        if max_bond is not None or max_discard is not None:
+            try:
+                res = self.compress(out, max_bond, 0.0 if max_discard is None else max_discard, value_of_zero, info=True)
+            finally:
+                out.close()
+            out = res[0]
+            extra.update(res[1])
+        return (out, extra) if info else out
+
+    def operator_matrix(self, xs: MpsSet, mpo, ys: MpsSet | None = None, **compress_args) -> np.ndarray:
+        """``M[j][i] = <y_j| O |x_i>``, complex128 of shape (len(ys or xs), len(xs)), not normalised: the Hamiltonian and overlap
+        matrices of subspace methods, the off-diagonal partner of ``mpo_expectations``.  The MPO acts on the ket side, on ``xs``
+        (one ``apply_mpo(xs, mpo, **compress_args)``); the conjugate is taken on ``ys`` by one ``overlaps(ys, O xs)``, whose
+        ``z[i][j] = <y_j|O x_i>`` is returned transposed.  For ``<y|O^dagger|x>`` pass ``mpo.dagger()``.  Synchronous."""
+        if "info" in compress_args:
+            raise ValueError("operator_matrix returns the matrix alone: info is not an argument")
+        ox = self.apply_mpo(xs, mpo, **compress_args)
+        try:
+            return np.ascontiguousarray(self.overlaps(xs if ys is None else ys, ox).T)
+        finally:
+            ox.close()
 
     def marginals(self, xs: MpsSet, bits, bases):
         """Probabilities of partial outcomes for every state of an fp64 set, the unmeasured qubits traced out: float64 of shape

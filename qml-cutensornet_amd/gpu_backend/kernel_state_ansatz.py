@@ -1067,6 +1067,84 @@ def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64),
     return out
 
 
+def build_symmetrized_kernel_matrix(mpi_comm, ansatz, X, Y=None, projector=None, truncation_error=None, max_bond=None, min_weight=1e-12):
+    """The fidelity kernel of the feature states projected by an MPO ``P`` (``engine.Mpo``, for instance
+    ``engine.mpo_parity_projector``):
+        K[j][i] = |<psi(y_j)| P^dagger P |psi(x_i)>|^2 / (w(x_i) w(y_j)),      w(x) = <psi(x)| P^dagger P |psi(x)>
+    Each rank builds its share of the states (the builders of ``build_kernel_matrix``), applies ``P`` to it on its device
+    (``Context.apply_mpo``) and compresses the product with ``max_discard = 0`` (only rank-deficient bonds shrink) and the cap
+    ``max_bond`` (``None``: no cap), as ``build_capped_kernel_matrices`` compresses its shares; ``truncation_error`` is the
+    builder's, as in ``build_kernel_matrix``.  The projected shares are exchanged and swept like the plain ones.  The weights ``w`` are the squared norms of the exact product
+    states themselves.  A data point with ``w <= min_weight`` (a state outside the sector) is a ``ValueError`` that names it, on
+    every rank, before anything is compressed.  Rank 0 returns ``K`` (len(Y or X), len(X)), the other ranks ``None``; any number
+    of ranks gives the same bits."""
+    if Y is not None and len(X) < len(Y):
+        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
+    if not isinstance(projector, _engine.Mpo):
+        raise ValueError(f"projector must be an engine.Mpo, got {type(projector).__name__}")
+    n_qubits = int(ansatz.num_qubits)
+    if projector.n_sites != n_qubits:
+        raise ValueError(f"the projector has {projector.n_sites} sites, the ansatz has {n_qubits} qubits")
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    if not (float(min_weight) >= 0.0 and np.isfinite(float(min_weight))):
+        raise ValueError(f"min_weight must be >= 0 and finite, got {min_weight!r}")
+    X = np.asarray(X, dtype=np.float64)
+    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
+    fidelity = 1.0 - float(truncation_error)
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    is_root = rank == ROOT_RANK
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
+    device_id = rank % n_dev
+    from qml_cutensornet_amd.builder_pool import default_workers
+
+    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    ctx = _engine.default_context(device_id)
+    shares = []  # (name, total, lo, exact product of the share or None, weights of the whole data set)
+    small = []
+    try:
+        for name, pts in (("X", X), ("Y", Y)):
+            if pts is None:
+                continue
+            _say(is_root, f"\nContracting the MPS of the circuits from the {name} dataset...")
+            lo, local, _, _ = _simulate_share(ansatz, pts, rank, n_procs, fidelity, is_root, name, device_id, host_workers)
+            ctx.trim()
+            prod, w = None, np.zeros(0)
+            if local is not None:
+                try:
+                    prod = ctx.apply_mpo(local, projector)
+                finally:
+                    local.close()
+                shares.append([name, len(pts), lo, prod, None])
+                w = ctx.local_paulis(prod, norms=True)[1]
+            else:
+                shares.append([name, len(pts), lo, None, None])
+            shares[-1][4] = _gather_features(mpi_comm, lo, w, len(pts))
+        for name, _, _, _, w in shares:
+            bad = np.flatnonzero(~(w > float(min_weight)))
+            if bad.size:
+                raise ValueError(f"data point {int(bad[0])} of {name} has weight {w[bad[0]]:.3e} <= min_weight = {float(min_weight):.3e} in the projector's sector")
+        for _, _, _, prod, _ in shares:
+            small.append(None if prod is None else ctx.compress(prod, max_bond=max_bond, max_discard=0.0))
+        full = [exchange_sets(mpi_comm, ctx, cs, lo, total)[0] for cs, (_, total, lo, _, _) in zip(small, shares)]
+        try:
+            K, _ = _gram_on_device(mpi_comm, rank, n_procs, ctx, full[0], full[1] if len(full) > 1 else None)
+        finally:
+            for f, cs in zip(full, small):
+                if f is not cs:
+                    f.close()
+    finally:
+        for s in [sh[3] for sh in shares] + small:
+            if s is not None:
+                s.close()
+    if not is_root:
+        return None
+    wx = shares[0][4]
+    return K / np.outer(wx if Y is None else shares[1][4], wx)
+
+
 def _shot_block_share(mpi_comm, ctx, shares, n_qubits, n_procs, rank, widths, side, shots, shot_seed):
     """The finite-shot route of ``build_block_kernel_matrices``: (parts, self_x, self_y, err_x, err_y) with parts the all-gathered
     (pairs, estimates, standard errors) of every rank.  Each rank samples its share of the states, the packed words of the block (4

@@ -299,6 +299,25 @@ class MPS:
             E = np.tensordot(T, ts[k].conj(), axes=([1, 2], [1, 0]))            # [v][c][d]
         return complex((E[0] * R[supp[-1] + 1]).sum() / norm)
 
+    def apply_mpo(self, mpo) -> "MPS":
+        """``O|psi>`` of an ``engine.Mpo`` as a new ``MPS`` on the host: the numpy mirror of ``Context.apply_mpo`` and its oracle.
+        Site k of the product is ``B_k[(u, a)][s'][(v, b)] = sum_s W_k[u][v][s'][s] A_k[a][s][b]`` with row ``u chi_k + a`` and
+        column ``v chi_{k+1} + b`` (u and v major), so its bonds are ``w_k chi_k``.  Nothing is truncated or normalised and the
+        gauge is general; the state itself is untouched."""
+        from .engine import Mpo
+
+        n = len(self.tensors)
+        if not isinstance(mpo, Mpo):
+            raise ValueError(f"apply_mpo takes an engine.Mpo, got {type(mpo).__name__}")
+        if mpo.n_sites != n:
+            raise ValueError(f"the Mpo has {mpo.n_sites} sites, the state has {n}")
+        out = []
+        for W, A in zip(mpo.tensors, self.tensors):
+            A = np.asarray(A, dtype=np.complex128)
+            B = np.einsum("uvts,asb->uatvb", W, A)
+            out.append(np.ascontiguousarray(B.reshape(W.shape[0] * A.shape[0], 2, W.shape[1] * A.shape[2])))
+        return MPS(out)
+
     def marginal(self, bits, bases) -> np.ndarray:
         """Probabilities of partial outcomes on the host, float64 of shape (n_strings,): the numpy mirror of ``Context.marginals``.
         ``bits`` is (n_strings, n) of 0 / 1 (bit 0 = eigenvalue +1), ``bases`` (n_strings, n) or one shared row of codes 0..3: 0 =

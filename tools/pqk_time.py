@@ -170,6 +170,9 @@ def main():
     ap.add_argument("--amplitudes", type=int, default=0, metavar="S", help="also time amplitudes() with logp on S shots per state drawn with sample()")
     ap.add_argument("--marginals", type=int, default=0, metavar="N", help="with --strings: also time marginals() on N projector strings on the supports of those strings")
     ap.add_argument("--mpo", default=None, choices=("heisenberg", "exponential"), help="also time mpo_expectations on this MPO (heisenberg: also its term list through operator_expectations)")
+    ap.add_argument("--apply", default=None, choices=("parity", "heisenberg_step", "gate"),
+                    help="also time apply_mpo with this MPO (parity: the even projector; heisenberg_step: 1 - 0.05i H; gate: a Haar 4 x 4 on qubits (0, n - 1)) and the compress that follows")
+    ap.add_argument("--apply-max-gib", type=float, default=64.0, help="with --apply: the largest product image; wider states are capped first")
     args = ap.parse_args()
     if args.block_shots and not args.block_widths:
         ap.error("--block-shots needs --block-widths")
@@ -432,6 +435,58 @@ def main():
                 "mpo_terms_ms": round(float(np.median(ts_t)), 3), "mpo_terms_ms_min": round(min(ts_t), 3), "mpo_terms_ms_max": round(max(ts_t), 3),
                 "mpo_over_terms": round(float(np.median(ts_h)) / float(np.median(ts_t)), 4), "max_abs_d_mpo_terms": float(np.abs(Vm[:, 0] - Vt).max()),
             })
+    if args.apply:
+        def spread_apply(fn, keep=False):
+            """ms of `reps` calls after one warm-up call; the sets the calls return are closed outside the timed window"""
+            fn().close()
+            ts, out = [], None
+            for r in range(args.reps):
+                t0 = time.perf_counter()
+                out = fn()
+                ts.append(1e3 * (time.perf_counter() - t0))
+                if not (keep and r == args.reps - 1):
+                    out.close()
+            return out, ts
+
+        if args.apply == "parity":
+            O = engine.mpo_parity_projector(n, +1)
+        elif args.apply == "heisenberg_step":  # 1 - i tau H, tau = 0.05, H the chain of --mpo heisenberg: bond 6
+            terms = [(j, p + p, (k, k + 1)) for k in range(n - 1) for j, p in zip((1.0, 0.8, -0.6), "XYZ")] + [(0.5, "Z", (k,)) for k in range(n)]
+            O = engine.Mpo([np.eye(2).reshape(1, 1, 2, 2)] * n) + engine.mpo_from_terms(n, terms).scale(-0.05j)
+        else:
+            g = np.random.default_rng(7)
+            q, r = np.linalg.qr(g.standard_normal((4, 4)) + 1j * g.standard_normal((4, 4)))
+            O = engine.mpo_two_qubit_gate(n, 0, n - 1, q * (np.diag(r) / np.abs(np.diag(r)))[None, :])
+        # a product bond is at most 512 and the product is allocated whole: where the states are too wide for this MPO, or the
+        # product image would pass --apply-max-gib, the states are capped first (reported as apply_source_cap), halving the cap
+        def product_bytes(dims):
+            pad = (O.bonds[None, :].astype(np.int64) * dims + 15) // 16 * 16
+            return int(32 * (pad[:, :-1] * pad[:, 1:]).sum())
+
+        src, cap, dims_src = xs, None, info["dims"].astype(np.int64)
+        while int((O.bonds[None, :] * dims_src).max()) > 512 or product_bytes(dims_src) > args.apply_max_gib * 2**30:
+            cap = 512 // O.max_bond() if cap is None else cap // 2
+            if cap < 1:
+                raise SystemExit("--apply: no bond cap brings the product under --apply-max-gib")
+            dims_src = np.minimum(info["dims"].astype(np.int64), cap)
+        if cap is not None:
+            src = ctx.compress(xs, max_bond=cap)
+        ps, ts_a = spread_apply(lambda: ctx.apply_mpo(src, O), keep=True)
+        product_dims = ps.dims.copy()
+        written = 8 * ps.image()[0]
+        read = int(32 * (O.bonds[None, :-1].astype(np.int64) * src.dims[:, :-1].astype(np.int64) * src.dims[:, 1:]).sum())  # every true source element once per u
+        cs, ts_c = spread_apply(lambda: ctx.compress(ps, max_discard=0.0), keep=True)
+        apply_ms = float(np.median(ts_a))
+        dist.update({
+            "apply": args.apply, "apply_mpo_bond": O.max_bond(), "apply_source_cap": cap, "apply_source_max_bond": int(src.dims.max()), "apply_reps": args.reps,
+            "apply_ms": round(apply_ms, 3), "apply_ms_min": round(min(ts_a), 3), "apply_ms_max": round(max(ts_a), 3),
+            "apply_bytes_written": int(written), "apply_bytes_read": read, "apply_gbps": round(written / (apply_ms * 1e-3) / 1e9, 1),
+            "apply_compress_ms": round(float(np.median(ts_c)), 3), "apply_compress_ms_min": round(min(ts_c), 3), "apply_compress_ms_max": round(max(ts_c), 3),
+            "product_max_bond": int(product_dims.max()), "compressed_max_bond": int(cs.dims.max()),
+        })
+        cs.close(), ps.close()
+        if src is not xs:
+            src.close()
     print(json.dumps({
         "config": args.config, "n_qubits": n, "layers": reps, "gamma": gamma, "n_states": npts,
         "max_bond": int(info["dims"].max()), "build_s": round(build_s, 3),
