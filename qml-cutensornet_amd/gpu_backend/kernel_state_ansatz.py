@@ -15,13 +15,21 @@ RCCL all-gather, ``dist.exchange_sets``) so that every rank holds all MPS on its
 rank sweeps its share of the pairs in one persistent HIP kernel launch and the shares meet in a
 single all-gather (RCCL through torch.distributed when it is initialised with the nccl backend,
 the communicator's own ``allgather`` otherwise).
+
+The ``build_*`` drivers share their plumbing, each concern in one place: ``_checked_points`` raises the two argument errors every
+driver has and casts the data; ``_start`` is the run prologue (rank, device, host cores, context, clock: a ``_Run``), called after
+a driver's own argument checks; ``_chunk`` is the share arithmetic of the three share builders; ``_build_shares`` builds X then Y
+as device sets and ``_share_features`` turns one share into a feature array and closes it; ``_exchanged`` lends the full sets and
+closes what the exchange made; ``_profile_head``, ``_sim_stats``, ``_chi_stats`` and ``_write_profile`` make the profiling JSON.
 """
 from __future__ import annotations
 
 import json
 import sys
 import time
+from contextlib import contextmanager
 from statistics import mean, median
+from typing import NamedTuple
 
 import numpy as np
 
@@ -44,6 +52,52 @@ def _say(is_root, text):
     if is_root:
         print(text)
         sys.stdout.flush()
+
+
+class _Run(NamedTuple):
+    """What a driver knows once it has started: who this rank is, its device and context, its share of the host cores, the clock."""
+    rank: int
+    n_procs: int
+    is_root: bool
+    device_id: int
+    host_workers: int
+    ctx: object
+    t_start: float
+
+
+def _start(mpi_comm, what):
+    """The prologue of every driver, after its argument checks: ranks share the devices round robin (device = rank % n_devices,
+    ref :152) and the host cores of the node.  ``what`` is the subject of the error without a device ("the Gram path has")."""
+    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
+    n_dev = _engine.device_count()
+    if n_dev <= 0:
+        raise _engine.QkError(f"no gfx950 device visible: {what} no CPU fallback")
+    from qml_cutensornet_amd import builder_pool
+
+    host_workers = max(1, builder_pool.default_workers() // max(1, min(n_procs, n_dev)))  # host cores of this rank's share of the node
+    return _Run(rank, n_procs, rank == ROOT_RANK, rank % n_dev, host_workers, _engine.default_context(rank % n_dev), time.perf_counter())
+
+
+def _chunk(n, rank, n_procs):
+    """(lo, hi) of this rank's slice of n points: contiguous chunks of ceil(n / n_procs), as ref :154,:171-174."""
+    per_rank = -(-n // n_procs)
+    lo = min(n, rank * per_rank)
+    return lo, min(n, lo + per_rank)
+
+
+def _checked_points(X, Y, truncation_error):
+    """The two argument errors of the reference (ref :136-139) -> (X, Y or None, fidelity), the data as float64."""
+    if Y is not None and len(X) < len(Y):
+        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
+    if truncation_error is None:
+        raise ValueError("You must specify a truncation error.")
+    return np.asarray(X, dtype=np.float64), None if Y is None else np.asarray(Y, dtype=np.float64), 1.0 - float(truncation_error)
+
+
+def _close_all(sets):
+    for s in sets:
+        if s is not None:
+            s.close()
 
 
 _PILOT_MIN_STATES = 24  # below this a share goes to the device builder as a whole (states that outgrow the cap: host)
@@ -211,9 +265,7 @@ def _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, dev
     host as a whole (the rule of the noisy drivers: no per-state hand-over); "host" is ``simulate(..., initial=)``."""
     import os
 
-    per_rank = -(-len(points) // n_procs)
-    lo = min(len(points), rank * per_rank)
-    hi = min(len(points), lo + per_rank)
+    lo, hi = _chunk(len(points), rank, n_procs)
     chi = int(os.environ.get("QK_MAX_BOND", "0")) or None
     which = os.environ.get("QK_BUILDER", "auto") if want_set else "host"  # auto | device | hybrid | host
     forced = which  # what the caller asked for: only a FORCED device build may fail the call
@@ -284,7 +336,7 @@ def _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, dev
             return lo, ctx.upload(states), secs, [m.fidelity for m in states]
     # host builder: one circuit per core on a thread pool (no fork: the GPU may already be initialised; the native builder
     # releases the GIL) -- the reference's loop is serial because its simulate() runs on the GPU (ref :213-231)
-    tick, done = max(1, per_rank // 10), [0]
+    tick, done = max(1, (hi - lo) // 10), [0]  # (the root's share is a full chunk, and only the root prints)
 
     def progress():
         done[0] += 1
@@ -339,6 +391,125 @@ def _set_mib(dims):
     return float((32.0 * d[:, :-1] * d[:, 1:]).sum() / 2**20)
 
 
+def _initial_pair(initial_states, initial_states_Y, X, Y, ansatz):
+    """(``initial_states`` for X, ``initial_states_Y`` for Y), checked; the second is ``None`` without Y."""
+    return (_initial_states(initial_states, len(X), ansatz),
+            _initial_states(initial_states_Y if Y is not None else None, 0 if Y is None else len(Y), ansatz, "initial_states_Y"))
+
+
+class _Share(NamedTuple):
+    """This rank's share of a data set: the ``_simulate_share`` result behind its label and the size of the whole set.  ``_exchanged``
+    reads ``lo`` and ``total`` only, so the two drivers with shares of another kind count them in their own unit: the noisy kernel in
+    states (T per point), and the depth scan keeps {depth: set} and {depth: fidelities} where one set and one list stand here."""
+    label: str
+    total: int
+    lo: int
+    local: object  # the packed device set, None for an empty share
+    secs: list
+    fids: list
+
+
+def _build_shares(run, ansatz, X, Y, fidelity, inits=None):
+    """This rank's shares of X and Y (each unless None) as device sets, built in that order: [_Share, ...].  The caller closes the sets."""
+    shares = []
+    try:
+        for k, (label, points) in enumerate((("X", X), ("Y", Y))):
+            if points is not None:
+                _say(run.is_root, f"\nContracting the MPS of the circuits from the {label} dataset...")
+                built = _simulate_share(ansatz, points, run.rank, run.n_procs, fidelity, run.is_root, label, run.device_id, run.host_workers,
+                                        initial=None if inits is None else inits[k])
+                shares.append(_Share(label, len(points), *built))
+    except BaseException:
+        _close_all(s.local for s in shares)
+        raise
+    # the device builder keeps its per-workgroup arena and workspace on the context (tens of GB at large bond caps): they go back before
+    # the exchange and the sweep need the memory (several ranks may share one GPU)
+    run.ctx.trim()
+    return shares
+
+
+def _share_features(run, ansatz, points, label, fidelity, empty_shape, features_of, initial=None):
+    """One data set of a driver that exchanges features, never states: this rank's share is built, ``features_of(set, first
+    index)`` makes its float64 feature array (an empty share gets zeros of shape (0,) + empty_shape) and the set is closed.
+    Returns (features, first index, largest bond of every state, seconds per state, fidelities, seconds in ``features_of``)."""
+    _say(run.is_root, f"\nContracting the MPS of the circuits from the {label} dataset...")
+    lo, local, secs, fids = _simulate_share(ansatz, points, run.rank, run.n_procs, fidelity, run.is_root, label, run.device_id, run.host_workers, initial=initial)
+    run.ctx.trim()  # the device builder's arena goes back before the feature kernels need memory
+    t0 = time.perf_counter()
+    if local is None:
+        F, chi = np.zeros((0,) + tuple(empty_shape), dtype=np.float64), np.zeros(0)
+    else:
+        try:
+            F, chi = features_of(local, lo), local.dims.max(axis=1)
+        finally:
+            local.close()
+    return F, lo, chi, secs, fids, time.perf_counter() - t0
+
+
+def _gathered_features(run, mpi_comm, ansatz, X, Y, fidelity, empty_shape, features_of, inits=(None, None)):
+    """``_share_features`` of X and (unless None) Y with ``features_of(label, set, first index)``, then the all-gathers: ([features of
+    all of X, of all of Y], [largest bonds likewise], seconds per state, fidelities, seconds in the features, seconds in the gathers)."""
+    parts, sim_secs, fids, feat_secs = [], [], [], 0.0
+    for k, (label, points) in enumerate((("X", X), ("Y", Y))):
+        if points is None:
+            continue
+        F, lo, chi, secs, fid, dt = _share_features(run, ansatz, points, label, fidelity, empty_shape,
+                                                    lambda local, lo, label=label: features_of(label, local, lo), inits[k])
+        parts.append((lo, F, chi, len(points)))
+        sim_secs, fids, feat_secs = sim_secs + secs, fids + fid, feat_secs + dt
+    t0 = time.perf_counter()
+    feats = [_gather_features(mpi_comm, lo, F, total) for lo, F, _, total in parts]
+    chi_all = [np.concatenate([np.asarray(c, dtype=np.float64) for c in comm_allgather(mpi_comm, chi)]) for _, _, chi, _ in parts]
+    return feats, chi_all, sim_secs, fids, feat_secs, time.perf_counter() - t0
+
+
+@contextmanager
+def _exchanged(run, mpi_comm, locals_, shares):
+    """The full sets of the local ones (``exchange_sets`` with each share's first index and total): every rank holds all states
+    inside the block.  On exit the sets the exchange made are closed; a local set that came back as the full one (a single
+    rank) is its owner's to close."""
+    full = []
+    try:
+        for loc, s in zip(locals_, shares):
+            full.append(exchange_sets(mpi_comm, run.ctx, loc, s.lo, s.total)[0])
+        yield full
+    finally:
+        _close_all(f for f, loc in zip(full, locals_) if f is not loc)
+
+
+def _gram_of(run, mpi_comm, full):
+    """``_gram_on_device`` of the exchanged sets [X] or [X, Y]."""
+    return _gram_on_device(mpi_comm, run.rank, run.n_procs, run.ctx, full[0], full[1] if len(full) > 1 else None)
+
+
+def _profile_head(run, X, Y):
+    return {"n_procs": [run.n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"]}
+
+
+def _sim_stats(sim_secs, quartiles=True):
+    """The simulation entries of a profile.  (``quartiles=False``: ``build_shot_feature_kernel_matrix`` has never written q1 and
+    q3, unlike its siblings; its JSON keeps the keys it has.)"""
+    prof = {"r0_circ_sim": [sum(sim_secs), "seconds"]}
+    if sim_secs:
+        prof["avg_circ_sim"] = [mean(sim_secs), "seconds"]
+        prof["median_circ_sim"] = [median(sim_secs), "seconds"]
+        if quartiles:
+            prof["q1_circ_sim"] = [float(np.percentile(sim_secs, 25)), "seconds"]
+            prof["q3_circ_sim"] = [float(np.percentile(sim_secs, 75)), "seconds"]
+    return prof
+
+
+def _chi_stats(chi_all):
+    """The mean largest bond of the states of X and of Y (``chi_all``: one array per data set; without Y, Y is X)."""
+    return {f"ave max chi {v}": (float(chi.mean()) if chi.size else 0.0, f"chi {v}") for v, chi in (("x", chi_all[0]), ("y", chi_all[-1]))}
+
+
+def _write_profile(info_file, prof):
+    if info_file is not None:
+        with open(info_file + ".json", "w") as fp:
+            json.dump(prof, fp, indent=4)
+
+
 def build_kernel_matrix(mpi_comm, ansatz, X, Y=None, info_file=None, truncation_error=None, loglevel=30, initial_states=None, initial_states_Y=None):
     """Fill the kernel (Gram) matrix ``K[j, i] = |<psi(X_i)|psi(Y_j)>|^2``; ``Y=None`` means ``Y = X``.
 
@@ -348,100 +519,50 @@ def build_kernel_matrix(mpi_comm, ansatz, X, Y=None, info_file=None, truncation_
     ``initial_states`` (one ``MPS`` for all, or a list with one per data point of X; ``initial_states_Y`` for Y) applies the circuits
     to given states instead of |0...0> -- any gauge, any norm (``Context.seed``, ``mps.seed_state``).  ``None`` is the call without it.
     """
-    if Y is not None and len(X) < len(Y):
-        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
-    X = np.asarray(X, dtype=np.float64)
-    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
-    fidelity = 1.0 - float(truncation_error)
-    init_x = _initial_states(initial_states, len(X), ansatz)
-    init_y = _initial_states(initial_states_Y if Y is not None else None, 0 if Y is None else len(Y), ansatz, "initial_states_Y")
-
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))  # host cores of this rank's share of the node
-    prof = {}
-    t_start = time.perf_counter()
-    if is_root:
-        prof["n_procs"] = [n_procs, "gpus"]
-        prof["lenX"] = [len(X), "entries"]
-        prof["lenY"] = [None if Y is None else len(Y), "entries"]
-
-    # circuits are bound lazily inside the simulation loop; the reference times their generation apart
-    prof["r0_circ_gen"] = [0.0, "seconds"]
-    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
-    ctx = _engine.default_context(device_id)
-    x_lo, x_local, x_secs, x_fid = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers, initial=init_x)
-    y_lo, y_local, y_secs, y_fid = (0, None, [], [])
-    if Y is not None:
-        _say(is_root, "\nContracting the MPS of the circuits from the Y dataset...")
-        y_lo, y_local, y_secs, y_fid = _simulate_share(ansatz, Y, rank, n_procs, fidelity, is_root, "Y", device_id, host_workers, initial=init_y)
-    sim_secs = x_secs + y_secs
-    # the device builder keeps its per-workgroup arena and workspace on the context (tens of GB at large bond caps): they go back before
-    # the exchange and the sweep need the memory (several ranks may share one GPU: device = rank % n_devices, ref :152)
-    ctx.trim()
-
-    # every rank gets the whole set: the packed device images of the shares, one all-gather (ref :341-352, 415-419)
-    xset, gather_secs = exchange_sets(mpi_comm, ctx, x_local, x_lo, len(X))
-    yset = None
-    if Y is not None:
-        yset, dt = exchange_sets(mpi_comm, ctx, y_local, y_lo, len(Y))
-        gather_secs += dt
-    for loc, full in ((x_local, xset), (y_local, yset)):
-        if loc is not None and loc is not full:
-            loc.close()
-
+    X, Y, fidelity = _checked_points(X, Y, truncation_error)
+    inits = _initial_pair(initial_states, initial_states_Y, X, Y, ansatz)
+    run = _start(mpi_comm, "the Gram path has")
+    prof = _profile_head(run, X, Y)
+    prof["r0_circ_gen"] = [0.0, "seconds"]  # circuits are bound lazily inside the simulation loop; the reference times their generation apart
+    shares = _build_shares(run, ansatz, X, Y, fidelity, inits)
+    locals_ = [s.local for s in shares]
     try:
-        if is_root:
-            mine_fid = x_fid + y_fid
-            prof["r0_circ_sim"] = [sum(sim_secs), "seconds"]
-            if sim_secs:
-                prof["avg_circ_sim"] = [mean(sim_secs), "seconds"]
-                prof["median_circ_sim"] = [median(sim_secs), "seconds"]
-                prof["q1_circ_sim"] = [float(np.percentile(sim_secs, 25)), "seconds"]
-                prof["q3_circ_sim"] = [float(np.percentile(sim_secs, 75)), "seconds"]
-            total_mib = _set_mib(xset.dims) + (0.0 if yset is None else _set_mib(yset.dims))
-            n_all = len(xset) + (0 if yset is None else len(yset))
-            prof["gpu_mps_mem"] = [total_mib, "MiB"]  # every GPU holds the whole set here
-            prof["avg_mps_mem"] = [total_mib / n_all, "MiB"]
-            prof["avg_fidelity"] = [sum(mine_fid) / max(1, len(mine_fid)), ""]
-            chi_x = xset.dims.max(axis=1)
-            prof["ave max chi x"] = (float(chi_x.mean()), "chi x")
-            prof["ave max chi y"] = (float((chi_x if yset is None else yset.dims.max(axis=1)).mean()), "chi y")
-            prof["r_nonRR_recv"] = [0, "seconds"]  # no ranks outside a ring: there is no ring
-            prof["r0_RR_recv"] = [gather_secs, "seconds"]  # exchange of the packed sets; the Gram all-gather is added below
-            _say(True, "\nFinished contracting all MPS.\n\nCalculating kernel matrix...")
-
-        t_tiles = time.perf_counter()
-        kernel_mat, exchange = _gram_on_device(mpi_comm, rank, n_procs, ctx, xset, yset)
-        tiles = time.perf_counter() - t_tiles
+        t0 = time.perf_counter()
+        # every rank gets the whole set: the packed device images of the shares, one all-gather (ref :341-352, 415-419)
+        with _exchanged(run, mpi_comm, locals_, shares) as full:
+            gather_secs = time.perf_counter() - t0
+            if run.n_procs > 1:  # the full sets are copies: the shares go back before the sweep needs the memory
+                _close_all(locals_)
+            if run.is_root:
+                sim_secs, fids = [t for s in shares for t in s.secs], [f for s in shares for f in s.fids]
+                prof.update(_sim_stats(sim_secs))
+                total_mib = sum(_set_mib(f.dims) for f in full)
+                prof["gpu_mps_mem"] = [total_mib, "MiB"]  # every GPU holds the whole set here
+                prof["avg_mps_mem"] = [total_mib / sum(len(f) for f in full), "MiB"]
+                prof["avg_fidelity"] = [sum(fids) / max(1, len(fids)), ""]
+                prof.update(_chi_stats([f.dims.max(axis=1) for f in full]))
+                prof["r_nonRR_recv"] = [0, "seconds"]  # no ranks outside a ring: there is no ring
+                prof["r0_RR_recv"] = [gather_secs, "seconds"]  # exchange of the packed sets; the Gram all-gather is added below
+                _say(True, "\nFinished contracting all MPS.\n\nCalculating kernel matrix...")
+            t_tiles = time.perf_counter()
+            kernel_mat, exchange = _gram_of(run, mpi_comm, full)
+            tiles = time.perf_counter() - t_tiles
     finally:
-        xset.close()
-        if yset is not None:
-            yset.close()
+        _close_all(locals_)  # (a no-op for sets closed above: ``MpsSet.close`` may be called twice)
 
-    if not is_root:
+    if not run.is_root:
         return None
     n_entries = kernel_mat.size if Y is not None else len(X) * (len(X) + 1) // 2
     per_entry = tiles / max(1, n_entries)
     prof["r0_RR_recv"][0] += exchange
     prof["kernel_mat_time"] = [tiles, "seconds"]
-    prof["total_time"] = [time.perf_counter() - t_start, "seconds"]
+    prof["total_time"] = [time.perf_counter() - run.t_start, "seconds"]
     # one launch computes every overlap: per-product statistics collapse to the mean
     prof["r0_product"] = [tiles - exchange, "seconds"]
     for key in ("avg_product", "median_product", "q1_product", "q3_product"):
         prof[key] = [per_entry, "seconds"]
     _say(True, f"\nFinished calculating all inner products.\n\tAverage time per inner product: {per_entry:.3e} seconds.\n")
-    if info_file is not None:
-        with open(info_file + ".json", "w") as fp:
-            json.dump(prof, fp, indent=4)
+    _write_profile(info_file, prof)
     return kernel_mat
 
 
@@ -545,76 +666,34 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     if rdm == 1 and pair_distance != 1:
         raise ValueError(f"pair_distance={pair_distance!r} needs rdm=2: the one-qubit form has no pairs")
     pair_distance = int(pair_distance)
-    if Y is not None and len(X) < len(Y):
-        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
+    X, Y, fidelity = _checked_points(X, Y, truncation_error)
     if pqk_gamma is not None:
         _engine.projected_gamma(pqk_gamma, 1)  # ValueError unless > 0 and finite
-    X = np.asarray(X, dtype=np.float64)
-    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
-    fidelity = 1.0 - float(truncation_error)
-    inits = {"X": _initial_states(initial_states, len(X), ansatz),
-             "Y": _initial_states(initial_states_Y if Y is not None else None, 0 if Y is None else len(Y), ansatz, "initial_states_Y")}
-
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: the projected kernel has no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
+    inits = _initial_pair(initial_states, initial_states_Y, X, Y, ansatz)
+    run = _start(mpi_comm, "the projected kernel has")
+    ctx = run.ctx
     n_qubits = int(ansatz.num_qubits)
     n_pairs = pair_distance * n_qubits - pair_distance * (pair_distance + 1) // 2  # n_qubits - 1 at distance 1
-    prof = {}
-    t_start = time.perf_counter()
-    if is_root:
-        prof["n_procs"] = [n_procs, "gpus"]
-        prof["lenX"] = [len(X), "entries"]
-        prof["lenY"] = [None if Y is None else len(Y), "entries"]
+    prof = _profile_head(run, X, Y)
+    f_shape = (n_obs,) if n_obs else (n_qubits, 3) if rdm == 1 else (n_pairs, 4, 4)
+    if window:
+        f_shape = (n_qubits - rdm + 1, 1 << rdm, 1 << rdm, 2)
 
-    ctx = _engine.default_context(device_id)
-    shares, sim_secs, fids, chis, feat_secs = [], [], [], [], 0.0
-    for label, points in (("X", X), ("Y", Y)):
-        if points is None:
-            continue
-        _say(is_root, f"\nContracting the MPS of the circuits from the {label} dataset...")
-        lo, local, secs, fid = _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, device_id, host_workers, initial=inits[label])
-        sim_secs += secs
-        fids += fid
-        ctx.trim()  # the device builder's arena goes back before the local sweep needs memory
-        t0 = time.perf_counter()
-        if local is None:
-            shape = (0, n_obs) if n_obs else (0, n_qubits, 3) if rdm == 1 else (0, n_pairs, 4, 4)
-            if window:
-                shape = (0, n_qubits - rdm + 1, 1 << rdm, 1 << rdm, 2)
-            F, chi = np.zeros(shape, dtype=np.float64), np.zeros(0)
-        else:
-            if window:  # complex128 as (re, im) pairs of float64: the features travel as the other forms' do
-                F = np.ascontiguousarray(ctx.window_rdms(local, rdm)).view(np.float64).reshape(len(local), n_qubits - rdm + 1, 1 << rdm, 1 << rdm, 2)
-            elif mpos is not None:  # the real parts are the feature columns
-                F = np.ascontiguousarray(ctx.mpo_expectations(local, mpos).real)
-            elif strings is not None:
-                F = ctx.pauli_expectations(local, strings)
-            elif shots is not None:
-                shot_bases = _engine.random_bases(shots, n_qubits, shot_seed)
-                bits = ctx.sample(local, shots, bases=shot_bases, seed=shot_seed, first_state=int(lo) + (0 if label == "X" else len(X)))
-                F = _engine.estimate_paulis(bits, shot_bases)[0] if rdm == 1 else _engine.estimate_pair_paulis(bits, shot_bases, pair_distance)
-            else:
-                F = ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local, max_dist=pair_distance)
-            chi = local.dims.max(axis=1)
-            local.close()
-        feat_secs += time.perf_counter() - t0
-        shares.append((lo, F, len(points)))
-        chis.append(chi)
+    def features_of(label, local, lo):
+        if window:  # complex128 as (re, im) pairs of float64: the features travel as the other forms' do
+            return np.ascontiguousarray(ctx.window_rdms(local, rdm)).view(np.float64).reshape((len(local),) + f_shape)
+        if mpos is not None:  # the real parts are the feature columns
+            return np.ascontiguousarray(ctx.mpo_expectations(local, mpos).real)
+        if strings is not None:
+            return ctx.pauli_expectations(local, strings)
+        if shots is not None:
+            shot_bases = _engine.random_bases(shots, n_qubits, shot_seed)
+            bits = ctx.sample(local, shots, bases=shot_bases, seed=shot_seed, first_state=int(lo) + (0 if label == "X" else len(X)))
+            return _engine.estimate_paulis(bits, shot_bases)[0] if rdm == 1 else _engine.estimate_pair_paulis(bits, shot_bases, pair_distance)
+        return ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local, max_dist=pair_distance)
 
-    t0 = time.perf_counter()
-    feats = [_gather_features(mpi_comm, lo, F, total) for lo, F, total in shares]
-    chi_all = [np.concatenate([np.asarray(c, dtype=np.float64) for c in comm_allgather(mpi_comm, chi)]) for chi in chis]
-    gather_secs = time.perf_counter() - t0
-    if not is_root:
+    feats, chi_all, sim_secs, fids, feat_secs, gather_secs = _gathered_features(run, mpi_comm, ansatz, X, Y, fidelity, f_shape, features_of, inits)
+    if not run.is_root:
         return None
     g = _engine.projected_gamma(pqk_gamma, n_obs if n_obs else n_qubits * pair_distance)  # (a window form has pair_distance 1)
     _say(True, "\nFinished contracting all MPS.\n\nCalculating projected kernel matrix...")
@@ -631,16 +710,9 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
     tiles = time.perf_counter() - t0
 
     prof["r0_circ_gen"] = [0.0, "seconds"]
-    prof["r0_circ_sim"] = [sum(sim_secs), "seconds"]
-    if sim_secs:
-        prof["avg_circ_sim"] = [mean(sim_secs), "seconds"]
-        prof["median_circ_sim"] = [median(sim_secs), "seconds"]
-        prof["q1_circ_sim"] = [float(np.percentile(sim_secs, 25)), "seconds"]
-        prof["q3_circ_sim"] = [float(np.percentile(sim_secs, 75)), "seconds"]
+    prof.update(_sim_stats(sim_secs))
     prof["avg_fidelity"] = [sum(fids) / max(1, len(fids)), ""]
-    prof["ave max chi x"] = (float(chi_all[0].mean()) if chi_all[0].size else 0.0, "chi x")
-    chi_y = chi_all[-1] if Y is not None else chi_all[0]
-    prof["ave max chi y"] = (float(chi_y.mean()) if chi_y.size else 0.0, "chi y")
+    prof.update(_chi_stats(chi_all))
     prof["r0_RR_recv"] = [gather_secs, "seconds"]  # the all-gather of the Bloch vectors
     prof["pqk_gamma"] = [g, ""]
     if n_obs:
@@ -653,10 +725,8 @@ def build_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, pqk_gamma=None, i
         prof["pqk_shots"] = [shots, "shots"]
     prof["pqk_features_time"] = [feat_secs, "seconds"]
     prof["kernel_mat_time"] = [tiles, "seconds"]
-    prof["total_time"] = [time.perf_counter() - t_start, "seconds"]
-    if info_file is not None:
-        with open(info_file + ".json", "w") as fp:
-            json.dump(prof, fp, indent=4)
+    prof["total_time"] = [time.perf_counter() - run.t_start, "seconds"]
+    _write_profile(info_file, prof)
     return kernel_mat
 
 
@@ -702,65 +772,25 @@ def build_shot_feature_kernel_matrix(mpi_comm, ansatz, X, Y=None, observables=No
         window = int(window)
         if settings == "window" and shots < 3 ** window:
             raise ValueError(f"settings='window' needs shots >= 3^window = {3 ** window} (got {shots})")
-    if Y is not None and len(X) < len(Y):
-        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
+    X, Y, fidelity = _checked_points(X, Y, truncation_error)
     if pqk_gamma is not None:
         _engine.projected_gamma(pqk_gamma, 1)  # ValueError unless > 0 and finite
-    X = np.asarray(X, dtype=np.float64)
-    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
-    fidelity = 1.0 - float(truncation_error)
-
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: the shot-feature kernel has no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
-    prof = {}
-    t_start = time.perf_counter()
-    if is_root:
-        prof["n_procs"] = [n_procs, "gpus"]
-        prof["lenX"] = [len(X), "entries"]
-        prof["lenY"] = [None if Y is None else len(Y), "entries"]
-
-    ctx = _engine.default_context(device_id)
+    run = _start(mpi_comm, "the shot-feature kernel has")
+    ctx = run.ctx
+    prof = _profile_head(run, X, Y)
     shot_bases = _engine.window_settings(shots, n_qubits, window) if settings == "window" else _engine.random_bases(shots, n_qubits, shot_seed)
     n_windows = 0 if strings is not None else n_qubits - window + 1
     f_shape = (len(strings),) if strings is not None else (n_windows, 1 << window, 1 << window, 2)
-    shares, sim_secs, fids, chis, feat_secs = [], [], [], [], 0.0
-    for label, points in (("X", X), ("Y", Y)):
-        if points is None:
-            continue
-        _say(is_root, f"\nContracting the MPS of the circuits from the {label} dataset...")
-        lo, local, secs, fid = _simulate_share(ansatz, points, rank, n_procs, fidelity, is_root, label, device_id, host_workers)
-        sim_secs += secs
-        fids += fid
-        ctx.trim()  # the device builder's arena goes back before the sampler needs memory
-        t0 = time.perf_counter()
-        if local is None:
-            F, chi = np.zeros((0,) + f_shape, dtype=np.float64), np.zeros(0)
-        else:
-            bits = ctx.sample(local, shots, bases=shot_bases, seed=shot_seed, first_state=int(lo) + (0 if label == "X" else len(X)))
-            if strings is not None:
-                F = ctx.estimate_pauli_strings(bits, shot_bases, strings)[0]
-            else:  # complex128 as (re, im) pairs of float64: the features travel as the other forms' do
-                F = np.ascontiguousarray(ctx.estimate_window_rdms(bits, shot_bases, window)[0]).view(np.float64).reshape((len(local),) + f_shape)
-            chi = local.dims.max(axis=1)
-            local.close()
-        feat_secs += time.perf_counter() - t0
-        shares.append((lo, F, len(points)))
-        chis.append(chi)
 
-    t0 = time.perf_counter()
-    feats = [_gather_features(mpi_comm, lo, F, total) for lo, F, total in shares]
-    chi_all = [np.concatenate([np.asarray(c, dtype=np.float64) for c in comm_allgather(mpi_comm, chi)]) for chi in chis]
-    gather_secs = time.perf_counter() - t0
-    if not is_root:
+    def features_of(label, local, lo):
+        bits = ctx.sample(local, shots, bases=shot_bases, seed=shot_seed, first_state=int(lo) + (0 if label == "X" else len(X)))
+        if strings is not None:
+            return ctx.estimate_pauli_strings(bits, shot_bases, strings)[0]
+        # complex128 as (re, im) pairs of float64: the features travel as the other forms' do
+        return np.ascontiguousarray(ctx.estimate_window_rdms(bits, shot_bases, window)[0]).view(np.float64).reshape((len(local),) + f_shape)
+
+    feats, chi_all, sim_secs, fids, feat_secs, gather_secs = _gathered_features(run, mpi_comm, ansatz, X, Y, fidelity, f_shape, features_of)
+    if not run.is_root:
         return None
     g = _engine.projected_gamma(pqk_gamma, len(strings) if strings is not None else n_qubits)
     _say(True, "\nFinished contracting all MPS.\n\nCalculating the shot-feature kernel matrix...")
@@ -773,14 +803,9 @@ def build_shot_feature_kernel_matrix(mpi_comm, ansatz, X, Y=None, observables=No
     tiles = time.perf_counter() - t0
 
     prof["r0_circ_gen"] = [0.0, "seconds"]
-    prof["r0_circ_sim"] = [sum(sim_secs), "seconds"]
-    if sim_secs:
-        prof["avg_circ_sim"] = [mean(sim_secs), "seconds"]
-        prof["median_circ_sim"] = [median(sim_secs), "seconds"]
+    prof.update(_sim_stats(sim_secs, quartiles=False))
     prof["avg_fidelity"] = [sum(fids) / max(1, len(fids)), ""]
-    prof["ave max chi x"] = (float(chi_all[0].mean()) if chi_all[0].size else 0.0, "chi x")
-    chi_y = chi_all[-1] if Y is not None else chi_all[0]
-    prof["ave max chi y"] = (float(chi_y.mean()) if chi_y.size else 0.0, "chi y")
+    prof.update(_chi_stats(chi_all))
     prof["r0_RR_recv"] = [gather_secs, "seconds"]  # the all-gather of the estimates
     prof["pqk_gamma"] = [g, ""]
     if strings is not None:
@@ -791,10 +816,8 @@ def build_shot_feature_kernel_matrix(mpi_comm, ansatz, X, Y=None, observables=No
     prof["pqk_settings"] = [settings, ""]
     prof["pqk_features_time"] = [feat_secs, "seconds"]
     prof["kernel_mat_time"] = [tiles, "seconds"]
-    prof["total_time"] = [time.perf_counter() - t_start, "seconds"]
-    if info_file is not None:
-        with open(info_file + ".json", "w") as fp:
-            json.dump(prof, fp, indent=4)
+    prof["total_time"] = [time.perf_counter() - run.t_start, "seconds"]
+    _write_profile(info_file, prof)
     return kernel_mat
 
 
@@ -809,48 +832,34 @@ def build_entanglement_profile(mpi_comm, ansatz, X, truncation_error=None, max_v
         norms      (len(X),)            <psi|psi>
         bond_dims  (len(X), n + 1)      true bond dimensions
     ``engine.bond_entropies``, ``engine.cap_cost`` and ``engine.schmidt_rank`` read ``spectra``."""
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
+    X, _, fidelity = _checked_points(X, None, truncation_error)
     if max_values is not None and (isinstance(max_values, bool) or not isinstance(max_values, (int, np.integer)) or max_values < 1):
         raise ValueError(f"max_values must be an int >= 1 or None (every weight), got {max_values!r}")
-    X = np.asarray(X, dtype=np.float64)
-    fidelity = 1.0 - float(truncation_error)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: the entanglement profile has no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
-    n_qubits = int(ansatz.num_qubits)
-    t_start = time.perf_counter()
-    ctx = _engine.default_context(device_id)
-    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
-    lo, local, sim_secs, fids = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers)
-    ctx.trim()  # the device builder's arena goes back before the environments need memory
-    dims = np.zeros((0, n_qubits + 1), dtype=np.float64) if local is None else np.asarray(local.dims, dtype=np.float64)
-    widest = int(dims[:, 1:n_qubits].max()) if dims.size and n_qubits > 1 else 1
-    m = int(max_values) if max_values is not None else max(int(w) for w in comm_allgather(mpi_comm, widest))
-    t0 = time.perf_counter()
-    if local is None:
-        spectra, purities, norms = np.zeros((0, n_qubits - 1, m)), np.zeros((0, n_qubits - 1)), np.zeros(0)
-    else:
-        spectra, norms = ctx.bond_spectra(local, max_values=m, norms=True)
-        purities = ctx.bond_purities(local)
-        local.close()
+    run = _start(mpi_comm, "the entanglement profile has")
+    ctx, n_qubits = run.ctx, int(ansatz.num_qubits)
+    # (not ``_share_features``: the ranks agree on m between the build and the features, empty shares included, and there are four arrays)
+    (_, _, lo, local, sim_secs, fids), = _build_shares(run, ansatz, X, None, fidelity)
+    try:
+        dims = np.zeros((0, n_qubits + 1), dtype=np.float64) if local is None else np.asarray(local.dims, dtype=np.float64)
+        widest = int(dims[:, 1:n_qubits].max()) if dims.size and n_qubits > 1 else 1
+        m = int(max_values) if max_values is not None else max(int(w) for w in comm_allgather(mpi_comm, widest))
+        t0 = time.perf_counter()
+        if local is None:
+            spectra, purities, norms = np.zeros((0, n_qubits - 1, m)), np.zeros((0, n_qubits - 1)), np.zeros(0)
+        else:
+            spectra, norms = ctx.bond_spectra(local, max_values=m, norms=True)
+            purities = ctx.bond_purities(local)
+    finally:
+        _close_all([local])
     feat_secs = time.perf_counter() - t0
     t0 = time.perf_counter()
     out = {"spectra": _gather_features(mpi_comm, lo, spectra, len(X)), "purities": _gather_features(mpi_comm, lo, purities, len(X)),
            "norms": _gather_features(mpi_comm, lo, norms, len(X)), "bond_dims": _gather_features(mpi_comm, lo, dims, len(X)).astype(np.int32)}
     gather_secs = time.perf_counter() - t0
-    if is_root and info_file is not None:
-        prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "r0_circ_gen": [0.0, "seconds"], "r0_circ_sim": [sum(sim_secs), "seconds"],
-                "avg_fidelity": [sum(fids) / max(1, len(fids)), ""], "r0_RR_recv": [gather_secs, "seconds"],
-                "pqk_bond_values": [m, "weights"], "pqk_entanglement_time": [feat_secs, "seconds"], "total_time": [time.perf_counter() - t_start, "seconds"]}
-        with open(info_file + ".json", "w") as fp:
-            json.dump(prof, fp, indent=4)
+    if run.is_root:
+        _write_profile(info_file, {"n_procs": [run.n_procs, "gpus"], "lenX": [len(X), "entries"], "r0_circ_gen": [0.0, "seconds"], "r0_circ_sim": [sum(sim_secs), "seconds"],
+                                   "avg_fidelity": [sum(fids) / max(1, len(fids)), ""], "r0_RR_recv": [gather_secs, "seconds"], "pqk_bond_values": [m, "weights"],
+                                   "pqk_entanglement_time": [feat_secs, "seconds"], "total_time": [time.perf_counter() - run.t_start, "seconds"]})
     return out
 
 
@@ -863,9 +872,7 @@ def build_outcome_likelihoods(mpi_comm, ansatz, X, bits, bases=None, per_state=F
     the strings of state i under state i; ``bases`` is anything ``engine.bases_table`` takes, shared by every state.  Rank 0
     returns float64 (len(X), n_strings), the other ranks ``None``; a row is the same bits for any number of ranks.
     ``engine.xeb_fidelity`` reads the result."""
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
-    X = np.asarray(X, dtype=np.float64)
+    X, _, fidelity = _checked_points(X, None, truncation_error)
     n_qubits = int(ansatz.num_qubits)
     bits = np.asarray(bits)
     want = (len(X), n_qubits) if per_state else (n_qubits,)
@@ -874,28 +881,14 @@ def build_outcome_likelihoods(mpi_comm, ansatz, X, bits, bases=None, per_state=F
         raise ValueError(f"bits must be an integer array of shape {shape} with n_strings >= 1; got shape {bits.shape}, dtype {bits.dtype}")
     n_strings = bits.shape[-2]
     B = None if bases is None else _engine.bases_table(bases, n_strings, n_qubits)
-    fidelity = 1.0 - float(truncation_error)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: outcome likelihoods have no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
+    run = _start(mpi_comm, "outcome likelihoods have")
 
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
-    ctx = _engine.default_context(device_id)
-    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
-    lo, local, _, _ = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers)
-    ctx.trim()  # the device builder's arena goes back before the chains need memory
-    if local is None:
-        lp = np.zeros((0, n_strings), dtype=np.float64)
-    else:
-        share = bits[lo : lo + len(local)] if per_state else bits
-        lp = ctx.amplitudes(local, share, bases=B, per_state=per_state, logp=True)[1]
-        local.close()
+    def features_of(local, lo):
+        return run.ctx.amplitudes(local, bits[lo : lo + len(local)] if per_state else bits, bases=B, per_state=per_state, logp=True)[1]
+
+    lp, lo = _share_features(run, ansatz, X, "X", fidelity, (n_strings,), features_of)[:2]
     out = _gather_features(mpi_comm, lo, lp, len(X))
-    return out if is_root else None
+    return out if run.is_root else None
 
 
 def build_outcome_marginals(mpi_comm, ansatz, X, bits, bases, truncation_error=None):
@@ -907,33 +900,13 @@ def build_outcome_marginals(mpi_comm, ansatz, X, bits, bases, truncation_error=N
     (n_strings, n_qubits) or one shared row of codes 0..3 (0 = not measured, 1, 2, 3 = X, Y, Z), both shared by every state.  Rank
     0 returns float64 (len(X), n_strings), the other ranks ``None``; a row is the same bits for any number of ranks.  The values
     are not clipped: a probability of exactly 0 may come out as rounding noise of either sign."""
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
-    X = np.asarray(X, dtype=np.float64)
-    n_qubits = int(ansatz.num_qubits)
-    table, codes = _engine.marginal_strings(bits, bases, n_qubits)  # raises ValueError that names bits or bases
-    n_strings = codes.shape[0]
-    fidelity = 1.0 - float(truncation_error)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: outcome marginals have no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
-    ctx = _engine.default_context(device_id)
-    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
-    lo, local, _, _ = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers)
-    ctx.trim()  # the device builder's arena goes back before the chains need memory
-    if local is None:
-        p = np.zeros((0, n_strings), dtype=np.float64)
-    else:
-        p = np.ascontiguousarray(ctx.operator_expectations(local, codes, ops=table).real)
-        local.close()
+    X, _, fidelity = _checked_points(X, None, truncation_error)
+    table, codes = _engine.marginal_strings(bits, bases, int(ansatz.num_qubits))  # raises ValueError that names bits or bases
+    run = _start(mpi_comm, "outcome marginals have")
+    p, lo = _share_features(run, ansatz, X, "X", fidelity, (codes.shape[0],),
+                            lambda local, lo: np.ascontiguousarray(run.ctx.operator_expectations(local, codes, ops=table).real))[:2]
     out = _gather_features(mpi_comm, lo, p, len(X))
-    return out if is_root else None
+    return out if run.is_root else None
 
 
 def build_mpo_expectations(mpi_comm, ansatz, X, mpos, truncation_error=None):
@@ -942,32 +915,13 @@ def build_mpo_expectations(mpi_comm, ansatz, X, mpos, truncation_error=None):
     ``QK_BUILDER`` rules as ``build_projected_kernel_matrix``), evaluates the MPOs on its device (``Context.mpo_expectations``) and
     the rows are all-gathered as (re, im) pairs, never an MPS.  Rank 0 returns complex128 (len(X), n_mpos), the other ranks
     ``None``; a row is the same bits for any number of ranks."""
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
-    X = np.asarray(X, dtype=np.float64)
-    n_qubits = int(ansatz.num_qubits)
-    ms = _engine._mpo_list(mpos, n_qubits)  # raises ValueError that names the entry
-    fidelity = 1.0 - float(truncation_error)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: MPO observables have no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
-    ctx = _engine.default_context(device_id)
-    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
-    lo, local, _, _ = _simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers)
-    ctx.trim()  # the device builder's arena goes back before the chains need memory
-    if local is None:
-        v = np.zeros((0, len(ms), 2), dtype=np.float64)
-    else:
-        v = np.ascontiguousarray(ctx.mpo_expectations(local, ms)).view(np.float64).reshape(len(local), len(ms), 2)
-        local.close()
+    X, _, fidelity = _checked_points(X, None, truncation_error)
+    ms = _engine._mpo_list(mpos, int(ansatz.num_qubits))  # raises ValueError that names the entry
+    run = _start(mpi_comm, "MPO observables have")
+    v, lo = _share_features(run, ansatz, X, "X", fidelity, (len(ms), 2),
+                            lambda local, lo: np.ascontiguousarray(run.ctx.mpo_expectations(local, ms)).view(np.float64).reshape(len(local), len(ms), 2))[:2]
     out = _gather_features(mpi_comm, lo, v, len(X))
-    return np.ascontiguousarray(out).view(np.complex128)[..., 0] if is_root else None
+    return np.ascontiguousarray(out).view(np.complex128)[..., 0] if run.is_root else None
 
 
 def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64), max_discard=0.0, truncation_error=None, info_file=None, loglevel=30):
@@ -981,50 +935,22 @@ def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64),
         bond_dims  {cap: (len(X) [+ len(Y)], n+1)}  the new bond table
     and the other ranks ``None``.  |K_capped - K| is bounded absolutely, not relatively: for normalised states by d (2 + d), d =
     delta_i + delta_j + delta_i delta_j, delta = sqrt(2 - 2 sqrt(fidelity))."""
-    if Y is not None and len(X) < len(Y):
-        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
+    X, Y, fidelity = _checked_points(X, Y, truncation_error)
     caps = [c for c in caps]
     if not caps or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 1 for c in caps) or len(set(caps)) != len(caps):
         raise ValueError(f"caps must be distinct ints >= 1, got {caps!r}")
     if not (float(max_discard) >= 0.0 and np.isfinite(float(max_discard))):
         raise ValueError(f"max_discard must be >= 0 and finite, got {max_discard!r}")
-    X = np.asarray(X, dtype=np.float64)
-    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
-    fidelity = 1.0 - float(truncation_error)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
-    n_qubits = int(ansatz.num_qubits)
-    t_start = time.perf_counter()
-    ctx = _engine.default_context(device_id)
-    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
-    shares = [(len(X),) + tuple(_simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers))]
-    if Y is not None:
-        _say(is_root, "\nContracting the MPS of the circuits from the Y dataset...")
-        shares.append((len(Y),) + tuple(_simulate_share(ansatz, Y, rank, n_procs, fidelity, is_root, "Y", device_id, host_workers)))
-    ctx.trim()
-    build_secs = time.perf_counter() - t_start
+    run = _start(mpi_comm, "the Gram path has")
+    ctx, n_qubits = run.ctx, int(ansatz.num_qubits)
+    shares = _build_shares(run, ansatz, X, Y, fidelity)
+    build_secs = time.perf_counter() - run.t_start
 
     def gram_of(local_sets):
-        """exchange the shares, sweep, close what the exchange made"""
-        full = [exchange_sets(mpi_comm, ctx, loc, lo, total)[0] for loc, (total, lo, _, _, _) in zip(local_sets, shares)]
-        try:
-            K, _ = _gram_on_device(mpi_comm, rank, n_procs, ctx, full[0], full[1] if len(full) > 1 else None)
-        finally:
-            for f, loc in zip(full, local_sets):
-                if f is not loc:
-                    f.close()
-        return K
+        with _exchanged(run, mpi_comm, local_sets, shares) as full:
+            return _gram_of(run, mpi_comm, full)[0]
 
-    locals_ = [s[2] for s in shares]
+    locals_ = [s.local for s in shares]
     out = {"K": None, "K_capped": {}, "fidelity": {}, "bond_dims": {}}
     secs = {}
     try:
@@ -1033,37 +959,29 @@ def build_capped_kernel_matrices(mpi_comm, ansatz, X, Y=None, caps=(16, 32, 64),
             t0 = time.perf_counter()
             small, fids, dims = [], [], []
             try:
-                for (total, lo, loc, _, _) in shares:
-                    if loc is None:
+                for s in shares:
+                    if s.local is None:
                         small.append(None)
                         fid_s, dims_s = np.zeros(0), np.zeros((0, n_qubits + 1))
                     else:
-                        cs, info = ctx.compress(loc, max_bond=int(cap), max_discard=float(max_discard), info=True)
+                        cs, info = ctx.compress(s.local, max_bond=int(cap), max_discard=float(max_discard), info=True)
                         small.append(cs)
                         fid_s, dims_s = info["fidelity"], info["bond_dims"].astype(np.float64)
-                    fids.append(_gather_features(mpi_comm, lo, fid_s, total))
-                    dims.append(_gather_features(mpi_comm, lo, dims_s, total))
+                    fids.append(_gather_features(mpi_comm, s.lo, fid_s, s.total))
+                    dims.append(_gather_features(mpi_comm, s.lo, dims_s, s.total))
                 secs[cap] = time.perf_counter() - t0
                 out["K_capped"][cap] = gram_of(small)
             finally:
-                for cs in small:
-                    if cs is not None:
-                        cs.close()
+                _close_all(small)
             out["fidelity"][cap] = np.concatenate(fids)
             out["bond_dims"][cap] = np.concatenate(dims).astype(np.int32)
     finally:
-        for loc in locals_:
-            if loc is not None:
-                loc.close()
-    if not is_root:
+        _close_all(locals_)
+    if not run.is_root:
         return None
-    if info_file is not None:
-        prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"],
-                "r0_circ_sim": [build_secs, "seconds"], "caps": [[int(c) for c in caps], "chi"],
-                "r0_compress": [[secs[c] for c in caps], "seconds"], "min_fidelity": [[float(out["fidelity"][c].min()) for c in caps], ""],
-                "total_time": [time.perf_counter() - t_start, "seconds"]}
-        with open(info_file + ".json", "w") as fp:
-            json.dump(prof, fp, indent=4)
+    _write_profile(info_file, {**_profile_head(run, X, Y), "r0_circ_sim": [build_secs, "seconds"], "caps": [[int(c) for c in caps], "chi"],
+                               "r0_compress": [[secs[c] for c in caps], "seconds"], "min_fidelity": [[float(out["fidelity"][c].min()) for c in caps], ""],
+                               "total_time": [time.perf_counter() - run.t_start, "seconds"]})
     return out
 
 
@@ -1078,71 +996,40 @@ def build_symmetrized_kernel_matrix(mpi_comm, ansatz, X, Y=None, projector=None,
     states themselves.  A data point with ``w <= min_weight`` (a state outside the sector) is a ``ValueError`` that names it, on
     every rank, before anything is compressed.  Rank 0 returns ``K`` (len(Y or X), len(X)), the other ranks ``None``; any number
     of ranks gives the same bits."""
-    if Y is not None and len(X) < len(Y):
-        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
     if not isinstance(projector, _engine.Mpo):
         raise ValueError(f"projector must be an engine.Mpo, got {type(projector).__name__}")
     n_qubits = int(ansatz.num_qubits)
     if projector.n_sites != n_qubits:
         raise ValueError(f"the projector has {projector.n_sites} sites, the ansatz has {n_qubits} qubits")
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
+    X, Y, fidelity = _checked_points(X, Y, truncation_error)
     if not (float(min_weight) >= 0.0 and np.isfinite(float(min_weight))):
         raise ValueError(f"min_weight must be >= 0 and finite, got {min_weight!r}")
-    X = np.asarray(X, dtype=np.float64)
-    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
-    fidelity = 1.0 - float(truncation_error)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
-    ctx = _engine.default_context(device_id)
-    shares = []  # (name, total, lo, exact product of the share or None, weights of the whole data set)
-    small = []
+    run = _start(mpi_comm, "the Gram path has")
+    ctx = run.ctx
+    shares, prods, small, weights = [], [], [], []  # per data set: the share, its exact product or None, the compressed twin, the weights of the whole set
     try:
-        for name, pts in (("X", X), ("Y", Y)):
-            if pts is None:
-                continue
-            _say(is_root, f"\nContracting the MPS of the circuits from the {name} dataset...")
-            lo, local, _, _ = _simulate_share(ansatz, pts, rank, n_procs, fidelity, is_root, name, device_id, host_workers)
-            ctx.trim()
-            prod, w = None, np.zeros(0)
-            if local is not None:
-                try:
-                    prod = ctx.apply_mpo(local, projector)
-                finally:
-                    local.close()
-                shares.append([name, len(pts), lo, prod, None])
-                w = ctx.local_paulis(prod, norms=True)[1]
-            else:
-                shares.append([name, len(pts), lo, None, None])
-            shares[-1][4] = _gather_features(mpi_comm, lo, w, len(pts))
-        for name, _, _, _, w in shares:
+        for xs, ys in ((X, None), (None, Y)) if Y is not None else ((X, None),):  # one data set at a time: the share of X is closed before Y is built
+            shares += _build_shares(run, ansatz, xs, ys, fidelity)
+            s = shares[-1]
+            try:
+                prods.append(None if s.local is None else ctx.apply_mpo(s.local, projector))
+            finally:
+                _close_all([s.local])
+            w = np.zeros(0) if prods[-1] is None else ctx.local_paulis(prods[-1], norms=True)[1]
+            weights.append(_gather_features(mpi_comm, s.lo, w, s.total))
+        for s, w in zip(shares, weights):
             bad = np.flatnonzero(~(w > float(min_weight)))
             if bad.size:
-                raise ValueError(f"data point {int(bad[0])} of {name} has weight {w[bad[0]]:.3e} <= min_weight = {float(min_weight):.3e} in the projector's sector")
-        for _, _, _, prod, _ in shares:
+                raise ValueError(f"data point {int(bad[0])} of {s.label} has weight {w[bad[0]]:.3e} <= min_weight = {float(min_weight):.3e} in the projector's sector")
+        for prod in prods:
             small.append(None if prod is None else ctx.compress(prod, max_bond=max_bond, max_discard=0.0))
-        full = [exchange_sets(mpi_comm, ctx, cs, lo, total)[0] for cs, (_, total, lo, _, _) in zip(small, shares)]
-        try:
-            K, _ = _gram_on_device(mpi_comm, rank, n_procs, ctx, full[0], full[1] if len(full) > 1 else None)
-        finally:
-            for f, cs in zip(full, small):
-                if f is not cs:
-                    f.close()
+        with _exchanged(run, mpi_comm, small, shares) as full:
+            K, _ = _gram_of(run, mpi_comm, full)
     finally:
-        for s in [sh[3] for sh in shares] + small:
-            if s is not None:
-                s.close()
-    if not is_root:
+        _close_all(prods + small)
+    if not run.is_root:
         return None
-    wx = shares[0][4]
-    return K / np.outer(wx if Y is None else shares[1][4], wx)
+    return K / np.outer(weights[-1], weights[0])
 
 
 def _shot_block_share(mpi_comm, ctx, shares, n_qubits, n_procs, rank, widths, side, shots, shot_seed):
@@ -1153,7 +1040,7 @@ def _shot_block_share(mpi_comm, ctx, shares, n_qubits, n_procs, rank, widths, si
     bases = _engine.setting_bases(U, M, n_qubits, shot_seed)
     nbits = min(n_qubits, _engine.SHOT_BLOCK_MAX_WIDTH)
     tables, dims, first = [], [], 0
-    for total, lo, loc, _, _ in shares:  # X, then Y: the states of Y are indexed after those of X
+    for _, total, lo, loc, _, _ in shares:  # X, then Y: the states of Y are indexed after those of X
         if loc is None:
             words, d = np.zeros((0, U * M), dtype=np.uint32), np.zeros((0, n_qubits + 1), dtype=np.int32)
         else:
@@ -1216,10 +1103,7 @@ def build_block_kernel_matrices(mpi_comm, ansatz, X, Y=None, widths=None, side="
         stderr    {"overlap": {w: (len(Y), len(X))}, "self_x": (n_widths, len(X)), "self_y": (n_widths, len(Y))}
     The sums are integers, so ``K`` is the same bits for any number of ranks.  A width above 32 together with ``shots`` is a
     ``ValueError``.  ``shots=None`` is the exact family."""
-    if Y is not None and len(X) < len(Y):
-        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
+    X, Y, fidelity = _checked_points(X, Y, truncation_error)
     n_qubits = int(ansatz.num_qubits)
     if widths is None:
         widths = range(1, n_qubits + 1)
@@ -1243,40 +1127,22 @@ def build_block_kernel_matrices(mpi_comm, ansatz, X, Y=None, widths=None, side="
             raise ValueError(f"shots: a packed word holds {_engine.SHOT_BLOCK_MAX_WIDTH} qubits, so widths stop there (got {widths[-1]})")
         if Y is None and shots[1] < 2:
             raise ValueError("shots: the purity estimates of a symmetric call need shots_per_setting >= 2")
-    X = np.asarray(X, dtype=np.float64)
-    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
-    fidelity = 1.0 - float(truncation_error)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
-    t_start = time.perf_counter()
-    ctx = _engine.default_context(device_id)
-    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
-    shares = [(len(X),) + tuple(_simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers))]
-    if Y is not None:
-        _say(is_root, "\nContracting the MPS of the circuits from the Y dataset...")
-        shares.append((len(Y),) + tuple(_simulate_share(ansatz, Y, rank, n_procs, fidelity, is_root, "Y", device_id, host_workers)))
-    ctx.trim()
-    build_secs = time.perf_counter() - t_start
-    locals_ = [s[2] for s in shares]
+    run = _start(mpi_comm, "the Gram path has")
+    ctx, rank, n_procs = run.ctx, run.rank, run.n_procs
+    shares = _build_shares(run, ansatz, X, Y, fidelity)
+    build_secs = time.perf_counter() - run.t_start
+    locals_ = [s.local for s in shares]
+    prof = {**_profile_head(run, X, Y), "r0_circ_sim": [build_secs, "seconds"], "widths": [widths, "qubits"], "side": [side, ""]}
+    ny = len(X) if Y is None else len(Y)
     if shots is not None:
         try:
             t0 = time.perf_counter()
             parts, self_x, self_y, err_x, err_y = _shot_block_share(mpi_comm, ctx, shares, n_qubits, n_procs, rank, widths, side, shots, shot_seed)
             sweep_secs = time.perf_counter() - t0
         finally:
-            for loc in locals_:
-                if loc is not None:
-                    loc.close()
-        if not is_root:
+            _close_all(locals_)
+        if not run.is_root:
             return None
-        ny = len(X) if Y is None else len(Y)
         out = {"widths": widths, "K": {}, "overlap": {}, "self_x": self_x, "self_y": self_y, "shots": shots, "stderr": {"overlap": {}, "self_x": err_x, "self_y": err_y}}
         for wi, w in enumerate(widths):
             O = assemble_gram(ny, len(X), [p[0] for p in parts], [p[1][wi] for p in parts], Y is None)
@@ -1288,49 +1154,33 @@ def build_block_kernel_matrices(mpi_comm, ansatz, X, Y=None, widths=None, side="
             out["stderr"]["self_x"] = out["stderr"]["self_y"] = np.stack([out["stderr"]["overlap"][w][d, d] for w in widths])
         for wi, w in enumerate(widths):
             out["K"][w] = _engine.block_kernel(out["overlap"][w], out["self_x"][wi], None if Y is None else out["self_y"][wi], form=form, gamma=block_gamma)
-        if info_file is not None:
-            prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"],
-                    "r0_circ_sim": [build_secs, "seconds"], "widths": [widths, "qubits"], "side": [side, ""], "block_shots": [list(shots), "settings, shots"],
-                    "r0_block_sweep": [sweep_secs, "seconds"], "total_time": [time.perf_counter() - t_start, "seconds"]}
-            with open(info_file + ".json", "w") as fp:
-                json.dump(prof, fp, indent=4)
+        _write_profile(info_file, {**prof, "block_shots": [list(shots), "settings, shots"], "r0_block_sweep": [sweep_secs, "seconds"],
+                                   "total_time": [time.perf_counter() - run.t_start, "seconds"]})
         return out
-    full = []
     try:
-        full = [exchange_sets(mpi_comm, ctx, loc, lo, total)[0] for loc, (total, lo, _, _, _) in zip(locals_, shares)]
-        xset, yset = full[0], full[1] if len(full) > 1 else None
-        t0 = time.perf_counter()
-        # (orient=False: a symmetric plan lists i <= j for every world size, so a value is the same bits however many ranks share the pairs)
-        plan = _engine.Plan(xset.dims, None if yset is None else yset.dims, n_procs, rank, orient=False)
-        try:
-            vals = ctx.block_values_host(xset, yset, plan, widths, side)
-            parts = comm_allgather(mpi_comm, (plan.pairs(), vals))
-        finally:
-            plan.close()
-        self_x = ctx.block_self(xset, widths, side)
-        self_y = self_x if yset is None else ctx.block_self(yset, widths, side)
-        sweep_secs = time.perf_counter() - t0
+        with _exchanged(run, mpi_comm, locals_, shares) as full:
+            xset, yset = full[0], full[1] if len(full) > 1 else None
+            t0 = time.perf_counter()
+            # (orient=False: a symmetric plan lists i <= j for every world size, so a value is the same bits however many ranks share the pairs)
+            plan = _engine.Plan(xset.dims, None if yset is None else yset.dims, n_procs, rank, orient=False)
+            try:
+                vals = ctx.block_values_host(xset, yset, plan, widths, side)
+                parts = comm_allgather(mpi_comm, (plan.pairs(), vals))
+            finally:
+                plan.close()
+            self_x = ctx.block_self(xset, widths, side)
+            self_y = self_x if yset is None else ctx.block_self(yset, widths, side)
+            sweep_secs = time.perf_counter() - t0
     finally:
-        for f, loc in zip(full, locals_):
-            if f is not loc:
-                f.close()
-        for loc in locals_:
-            if loc is not None:
-                loc.close()
-    if not is_root:
+        _close_all(locals_)
+    if not run.is_root:
         return None
-    ny = len(X) if Y is None else len(Y)
     out = {"widths": widths, "K": {}, "overlap": {}, "self_x": self_x, "self_y": self_y}
     for wi, w in enumerate(widths):
         O = assemble_gram(ny, len(X), [p[0] for p in parts], [p[1][wi] for p in parts], Y is None)
         out["overlap"][w] = O
         out["K"][w] = _engine.block_kernel(O, self_x[wi], None if Y is None else self_y[wi], form=form, gamma=block_gamma)
-    if info_file is not None:
-        prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"],
-                "r0_circ_sim": [build_secs, "seconds"], "widths": [widths, "qubits"], "side": [side, ""], "r0_block_sweep": [sweep_secs, "seconds"],
-                "total_time": [time.perf_counter() - t_start, "seconds"]}
-        with open(info_file + ".json", "w") as fp:
-            json.dump(prof, fp, indent=4)
+    _write_profile(info_file, {**prof, "r0_block_sweep": [sweep_secs, "seconds"], "total_time": [time.perf_counter() - run.t_start, "seconds"]})
     return out
 
 
@@ -1340,7 +1190,7 @@ def _shadow_share(mpi_comm, ctx, shares, n_qubits, n_procs, rank, shots, shot_se
     all-gathered, and each rank counts its share of the pairs of ``Plan(orient=False)``."""
     groups = (n_qubits + 31) // 32
     tables, dims, first = [], [], 0
-    for total, lo, loc, _, _ in shares:  # X, then Y: the states of Y are indexed after those of X
+    for _, total, lo, loc, _, _ in shares:  # X, then Y: the states of Y are indexed after those of X
         if loc is None:
             recs, d = np.zeros((0, shots, groups, 3), dtype=np.uint32), np.zeros((0, n_qubits + 1), dtype=np.int32)
         else:
@@ -1391,10 +1241,7 @@ def build_shadow_kernel_matrix(mpi_comm, ansatz, X, Y=None, shots=None, shot_see
     itself.  ``skip_equal_shots=False`` keeps every pair: the Gram of the inner mean is then positive semi-definite exactly (an inner
     product of mean feature vectors).  Either way the diagonal of a symmetric K is the self pair's value, an estimate like the others,
     not exactly 1 or any other constant.  ``shots`` must be an int >= 2; ``num_qubits > 128`` is a ``ValueError``."""
-    if Y is not None and len(X) < len(Y):
-        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
+    X, Y, fidelity = _checked_points(X, Y, truncation_error)
     n_qubits = int(ansatz.num_qubits)
     if n_qubits > _engine.SHADOW_MAX_QUBITS:
         raise ValueError(f"the shadow kernel's records hold at most {_engine.SHADOW_MAX_QUBITS} qubits (num_qubits is {n_qubits})")
@@ -1404,36 +1251,16 @@ def build_shadow_kernel_matrix(mpi_comm, ansatz, X, Y=None, shots=None, shot_see
     for name, v in (("shadow_gamma", shadow_gamma), ("shadow_tau", shadow_tau)):
         if not np.isfinite(float(v)):
             raise ValueError(f"{name} must be finite, got {v!r}")
-    X = np.asarray(X, dtype=np.float64)
-    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
-    fidelity = 1.0 - float(truncation_error)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
-    t_start = time.perf_counter()
-    ctx = _engine.default_context(device_id)
-    _say(is_root, "\nContracting the MPS of the circuits from the X dataset...")
-    shares = [(len(X),) + tuple(_simulate_share(ansatz, X, rank, n_procs, fidelity, is_root, "X", device_id, host_workers))]
-    if Y is not None:
-        _say(is_root, "\nContracting the MPS of the circuits from the Y dataset...")
-        shares.append((len(Y),) + tuple(_simulate_share(ansatz, Y, rank, n_procs, fidelity, is_root, "Y", device_id, host_workers)))
-    ctx.trim()
-    build_secs = time.perf_counter() - t_start
+    run = _start(mpi_comm, "the Gram path has")
+    shares = _build_shares(run, ansatz, X, Y, fidelity)
+    build_secs = time.perf_counter() - run.t_start
     try:
         t0 = time.perf_counter()
-        parts = _shadow_share(mpi_comm, ctx, shares, n_qubits, n_procs, rank, shots, shot_seed, _engine.random_bases(shots, n_qubits, shot_seed))
+        parts = _shadow_share(mpi_comm, run.ctx, shares, n_qubits, run.n_procs, run.rank, shots, shot_seed, _engine.random_bases(shots, n_qubits, shot_seed))
         sweep_secs = time.perf_counter() - t0
     finally:
-        for s in shares:
-            if s[2] is not None:
-                s[2].close()
-    if not is_root:
+        _close_all(s.local for s in shares)
+    if not run.is_root:
         return None
     nx, ny = len(X), len(X) if Y is None else len(Y)
     hist, equal = np.zeros((ny, nx, 2 * n_qubits + 1), dtype=np.int64), np.zeros((ny, nx, 2 * n_qubits + 1), dtype=np.int64)
@@ -1443,12 +1270,8 @@ def build_shadow_kernel_matrix(mpi_comm, ansatz, X, Y=None, shots=None, shot_see
             if Y is None:
                 dst[pairs[:, 0], pairs[:, 1]] = src
     K = _engine.shadow_kernel(hist, n_qubits, shadow_gamma, shadow_tau, equal if skip_equal_shots else None)
-    if info_file is not None:
-        prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"],
-                "r0_circ_sim": [build_secs, "seconds"], "shadow_shots": [shots, "shots"], "r0_shadow_sweep": [sweep_secs, "seconds"],
-                "total_time": [time.perf_counter() - t_start, "seconds"]}
-        with open(info_file + ".json", "w") as fp:
-            json.dump(prof, fp, indent=4)
+    _write_profile(info_file, {**_profile_head(run, X, Y), "r0_circ_sim": [build_secs, "seconds"], "shadow_shots": [shots, "shots"], "r0_shadow_sweep": [sweep_secs, "seconds"],
+                               "total_time": [time.perf_counter() - run.t_start, "seconds"]})
     return (K, {"hist": hist, "equal": equal}) if return_hist else K
 
 
@@ -1458,9 +1281,7 @@ def _depth_scan_share(ctx, ansatz, points, rank, n_procs, fidelity, depths, ends
     depth with checkpoints at the layer ends; if the device gives up, one host build per depth on the sliced circuits."""
     import os
 
-    per_rank = -(-len(points) // n_procs)
-    lo = min(len(points), rank * per_rank)
-    hi = min(len(points), lo + per_rank)
+    lo, hi = _chunk(len(points), rank, n_procs)
     if hi <= lo:
         return lo, {r: None for r in depths}, {r: [] for r in depths}
     deepest = ends[depths[-1] - 1]
@@ -1497,69 +1318,42 @@ def build_depth_scan_kernel_matrices(mpi_comm, ansatz, X, Y=None, depths=(1,), t
     and the other ranks ``None``.  QK_MAX_BOND (a bond cap) and QK_BUILDER_MAX_BOND (the largest bond the device builder holds,
     320) mean what they mean for ``build_kernel_matrix``'s device builder; a state that outgrows the latter, or any other device
     failure, sends the share to the host builder, one build per depth (the log says so)."""
-    if Y is not None and len(X) < len(Y):
-        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
+    X, Y, fidelity = _checked_points(X, Y, truncation_error)
     depths = sorted(check_depths(depths, ansatz.reps))
     ends = [int(e) for e in ansatz.layer_ends()]
-    X = np.asarray(X, dtype=np.float64)
-    Y = None if Y is None else np.asarray(Y, dtype=np.float64)
-    fidelity = 1.0 - float(truncation_error)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: the Gram path has no CPU fallback")
-    device_id = rank % n_dev
-    from qml_cutensornet_amd.builder_pool import default_workers
-
-    host_workers = max(1, default_workers() // max(1, min(n_procs, n_dev)))
-    t_start = time.perf_counter()
-    ctx = _engine.default_context(device_id)
-    shares = []  # (total, first index, {depth: set}, {depth: fidelities})
+    run = _start(mpi_comm, "the Gram path has")
+    shares = []  # _Share with {depth: set} for the local set and {depth: fidelities} for the fidelities
     for label, points in (("X", X), ("Y", Y)):
         if points is None:
             continue
-        _say(is_root, f"\nContracting the MPS of the circuits from the {label} dataset at depths {depths}...")
-        shares.append((len(points),) + tuple(_depth_scan_share(ctx, ansatz, points, rank, n_procs, fidelity, depths, ends, is_root, label, host_workers)))
-    ctx.trim()
-    build_secs = time.perf_counter() - t_start
+        _say(run.is_root, f"\nContracting the MPS of the circuits from the {label} dataset at depths {depths}...")
+        lo, sets, fids = _depth_scan_share(run.ctx, ansatz, points, run.rank, run.n_procs, fidelity, depths, ends, run.is_root, label, run.host_workers)
+        shares.append(_Share(label, len(points), lo, sets, [], fids))
+    run.ctx.trim()
+    build_secs = time.perf_counter() - run.t_start
     out = {"depths": list(depths), "K": {}, "fidelity": {}, "bond_dims": {}}
     gram_secs = {}
     n_qubits = int(ansatz.num_qubits)
     try:
         for r in depths:
             t0 = time.perf_counter()
-            fids, dims, full = [], [], []
-            try:
-                for total, lo, sets, fid in shares:
-                    loc = sets[r]
-                    fids.append(_gather_features(mpi_comm, lo, np.asarray(fid[r], dtype=np.float64), total))
-                    d = np.zeros((0, n_qubits + 1)) if loc is None else np.asarray(loc.dims, dtype=np.float64)
-                    dims.append(_gather_features(mpi_comm, lo, d, total))
-                    full.append(exchange_sets(mpi_comm, ctx, loc, lo, total)[0])
-                out["K"][r], _ = _gram_on_device(mpi_comm, rank, n_procs, ctx, full[0], full[1] if len(full) > 1 else None)
-            finally:
-                for f, (_, _, sets, _) in zip(full, shares):
-                    if f is not sets[r]:
-                        f.close()
+            fids, dims = [], []
+            for s in shares:
+                fids.append(_gather_features(mpi_comm, s.lo, np.asarray(s.fids[r], dtype=np.float64), s.total))
+                d = np.zeros((0, n_qubits + 1)) if s.local[r] is None else np.asarray(s.local[r].dims, dtype=np.float64)
+                dims.append(_gather_features(mpi_comm, s.lo, d, s.total))
+            with _exchanged(run, mpi_comm, [s.local[r] for s in shares], shares) as full:
+                out["K"][r], _ = _gram_of(run, mpi_comm, full)
             out["fidelity"][r] = np.concatenate(fids)
             out["bond_dims"][r] = np.concatenate(dims).astype(np.int32)
             gram_secs[r] = time.perf_counter() - t0
     finally:
-        for _, _, sets, _ in shares:
-            for m in sets.values():
-                if m is not None:
-                    m.close()
-    if not is_root:
+        _close_all(m for s in shares for m in s.local.values())
+    if not run.is_root:
         return None
-    if info_file is not None:
-        prof = {"n_procs": [n_procs, "gpus"], "lenX": [len(X), "entries"], "lenY": [None if Y is None else len(Y), "entries"],
-                "depths": [list(depths), "layers"], "r0_circ_sim": [build_secs, "seconds"], "kernel_mat_time": [[gram_secs[r] for r in depths], "seconds"],
-                "max_chi": [[int(out["bond_dims"][r].max()) for r in depths], "chi"], "total_time": [time.perf_counter() - t_start, "seconds"]}
-        with open(info_file + ".json", "w") as fp:
-            json.dump(prof, fp, indent=4)
+    _write_profile(info_file, {**_profile_head(run, X, Y), "depths": [list(depths), "layers"], "r0_circ_sim": [build_secs, "seconds"],
+                               "kernel_mat_time": [[gram_secs[r] for r in depths], "seconds"], "max_chi": [[int(out["bond_dims"][r].max()) for r in depths], "chi"],
+                               "total_time": [time.perf_counter() - run.t_start, "seconds"]})
     return out
 
 
@@ -1574,9 +1368,7 @@ def _noisy_share(ansatz, points, first_index, trajectories, noise_seed, rank, n_
     import os
 
     T = int(trajectories)
-    per_rank = -(-len(points) // n_procs)
-    lo = min(len(points), rank * per_rank)
-    hi = min(len(points), lo + per_rank)
+    lo, hi = _chunk(len(points), rank, n_procs)
     if hi <= lo:
         return lo, None, np.zeros((0, T)), False
     circuits = [as_bound_circuit(ansatz.circuit_for_data(points[k, :]), ansatz) for k in range(lo, hi)]
@@ -1609,17 +1401,12 @@ def _noisy_share(ansatz, points, first_index, trajectories, noise_seed, rank, n_
 
 
 def _noisy_arguments(X, Y, trajectories, noise_seed, truncation_error):
-    if Y is not None and len(X) < len(Y):
-        raise ValueError("X must not be smaller than Y. Swap input order and transpose output.")
-    if truncation_error is None:
-        raise ValueError("You must specify a truncation error.")
+    """The argument checks the two noisy drivers share -> (X, Y, fidelity, trajectories)."""
+    X, Y, fidelity = _checked_points(X, Y, truncation_error)
     if isinstance(trajectories, bool) or not isinstance(trajectories, (int, np.integer)) or trajectories < 1:
         raise ValueError(f"trajectories must be an int >= 1 (got {trajectories!r})")
     _engine._seed_key(noise_seed)
-    n_dev = _engine.device_count()
-    if n_dev <= 0:
-        raise _engine.QkError("no gfx950 device visible: the noisy kernels have no CPU fallback")
-    return np.asarray(X, dtype=np.float64), None if Y is None else np.asarray(Y, dtype=np.float64), int(trajectories), n_dev
+    return X, Y, fidelity, int(trajectories)
 
 
 def build_noisy_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, trajectories=1, noise_seed=0, rdm=1, pair_distance=1, pqk_gamma=None, truncation_error=None,
@@ -1644,30 +1431,29 @@ def build_noisy_projected_kernel_matrix(mpi_comm, ansatz, X, Y=None, trajectorie
         raise ValueError("rdm=2 compares reduced density matrices of qubit pairs: the ansatz needs at least 2 qubits")
     if pqk_gamma is not None:
         _engine.projected_gamma(pqk_gamma, 1)
-    X, Y, T, n_dev = _noisy_arguments(X, Y, trajectories, noise_seed, truncation_error)
+    X, Y, fidelity, T = _noisy_arguments(X, Y, trajectories, noise_seed, truncation_error)
     pair_distance = int(pair_distance)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    device_id = rank % n_dev
-    ctx = _engine.default_context(device_id)
+    run = _start(mpi_comm, "the noisy kernels have")
+    ctx = run.ctx
     n_pairs = pair_distance * n_qubits - pair_distance * (pair_distance + 1) // 2
     feats = []
-    inits = {"X": _initial_states(initial_states, len(X), ansatz),
-             "Y": _initial_states(initial_states_Y if Y is not None else None, 0 if Y is None else len(Y), ansatz, "initial_states_Y")}
-    for label, points, first in (("X", X, 0), ("Y", Y, len(X))):
+    inits = _initial_pair(initial_states, initial_states_Y, X, Y, ansatz)
+    for label, points, first, initial in (("X", X, 0, inits[0]), ("Y", Y, len(X), inits[1])):
         if points is None:
             continue
-        lo, local, _, _ = _noisy_share(ansatz, points, first, T, noise_seed, rank, n_procs, 1.0 - float(truncation_error), is_root, label, device_id, inits[label])
+        lo, local, _, _ = _noisy_share(ansatz, points, first, T, noise_seed, run.rank, run.n_procs, fidelity, run.is_root, label, run.device_id, initial)
         ctx.trim()
         if local is None:
             F = np.zeros((0, n_qubits, 3) if rdm == 1 else (0, n_pairs, 4, 4), dtype=np.float64)
         else:
-            F = ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local, max_dist=pair_distance)
-            local.close()
+            try:
+                F = ctx.local_paulis(local) if rdm == 1 else ctx.local_pair_paulis(local, max_dist=pair_distance)
+            finally:
+                local.close()
             F = np.asarray(F, dtype=np.float64)
             F = F.reshape((F.shape[0] // T, T) + F.shape[1:]).mean(axis=1)  # the features of the trajectory-averaged state
         feats.append(_gather_features(mpi_comm, lo, F, len(points)))
-    if not is_root:
+    if not run.is_root:
         return None
     g = _engine.projected_gamma(pqk_gamma, n_qubits * pair_distance)
     if rdm == 1:
@@ -1683,38 +1469,29 @@ def build_noisy_kernel_matrix(mpi_comm, ansatz, X, Y=None, trajectories=2, noise
     ``trajectories >= 2``.  State indices and trajectories as in ``build_noisy_projected_kernel_matrix``: the same bits for any
     number of ranks; ``trajectories=1`` with an ansatz without channels is ``build_kernel_matrix`` to rounding.  Returns the
     ``len(Y) x len(X)`` matrix on rank 0, ``None`` elsewhere."""
-    X, Y, T, n_dev = _noisy_arguments(X, Y, trajectories, noise_seed, truncation_error)
-    rank, n_procs = mpi_comm.Get_rank(), mpi_comm.Get_size()
-    is_root = rank == ROOT_RANK
-    device_id = rank % n_dev
-    ctx = _engine.default_context(device_id)
-    fidelity = 1.0 - float(truncation_error)
-    x_lo, x_local, _, noisy = _noisy_share(ansatz, X, 0, T, noise_seed, rank, n_procs, fidelity, is_root, "X", device_id)
-    if Y is None and T < 2 and any(comm_allgather(mpi_comm, bool(noisy))):
-        if x_local is not None:
-            x_local.close()
-        raise ValueError("a symmetric noisy kernel leaves the a = b terms out of its diagonal: it needs trajectories >= 2")
-    y_lo, y_local = 0, None
-    if Y is not None:
-        y_lo, y_local, _, _ = _noisy_share(ansatz, Y, len(X), T, noise_seed, rank, n_procs, fidelity, is_root, "Y", device_id)
-    ctx.trim()
-    xset, _ = exchange_sets(mpi_comm, ctx, x_local, x_lo * T, len(X) * T)
-    yset = None
-    if Y is not None:
-        yset, _ = exchange_sets(mpi_comm, ctx, y_local, y_lo * T, len(Y) * T)
-    for loc, full in ((x_local, xset), (y_local, yset)):
-        if loc is not None and loc is not full:
-            loc.close()
+    X, Y, fidelity, T = _noisy_arguments(X, Y, trajectories, noise_seed, truncation_error)
+    run = _start(mpi_comm, "the noisy kernels have")
+    shares = []  # of the expanded sets: T states per point
     try:
-        full, _ = _gram_on_device(mpi_comm, rank, n_procs, ctx, xset, yset)
+        for label, points, first in (("X", X, 0), ("Y", Y, len(X))):
+            if points is None:
+                continue
+            lo, local, _, noisy = _noisy_share(ansatz, points, first, T, noise_seed, run.rank, run.n_procs, fidelity, run.is_root, label, run.device_id)
+            shares.append(_Share(label, len(points) * T, lo * T, local, [], []))
+            if Y is None and T < 2 and any(comm_allgather(mpi_comm, bool(noisy))):
+                raise ValueError("a symmetric noisy kernel leaves the a = b terms out of its diagonal: it needs trajectories >= 2")
+        run.ctx.trim()
+        locals_ = [s.local for s in shares]
+        with _exchanged(run, mpi_comm, locals_, shares) as full:
+            if run.n_procs > 1:  # the full sets are copies: the shares go back before the sweep needs the memory
+                _close_all(locals_)
+            gram, _ = _gram_of(run, mpi_comm, full)
     finally:
-        xset.close()
-        if yset is not None:
-            yset.close()
-    if not is_root:
+        _close_all(s.local for s in shares)  # (a no-op for sets closed above: ``MpsSet.close`` may be called twice)
+    if not run.is_root:
         return None
     ny = len(X) if Y is None else len(Y)
-    blocks = np.asarray(full, dtype=np.float64).reshape(ny, T, len(X), T)  # [j][b][i][a]
+    blocks = np.asarray(gram, dtype=np.float64).reshape(ny, T, len(X), T)  # [j][b][i][a]
     K = blocks.sum(axis=(1, 3)) / float(T * T)
     if Y is None and T >= 2:
         for i in range(len(X)):
