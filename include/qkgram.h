@@ -88,6 +88,10 @@ typedef struct qk_stats {
    * (interleaved image, edge blocks, merged steps) on the FIRST Gram of a set -- part of a cold Gram (the reference's
    * kernel_mat_time, G:322, 432-434, brackets set-up and tiles alike), ~0 afterwards.                                   */
   double derive_ms;
+  /* Dynamic LDS bytes per workgroup of the launch and of the second launch (0: none).  A 12-wave site-fused launch asks for its X buffer
+   * and the chain's tables behind it; the bytes tell the instantiation with the large X buffer (9728 elements) from the one with the
+   * segmentation's (8192), which qk_kernel_name does not: both carry the name of the shape.                                          */
+  int32_t lds_bytes, second_lds_bytes;
 } qk_stats;
 
 /* sweep kernels of qk_gram_values (qk_stats.kernel) */

@@ -227,7 +227,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_quad_kernel(const
     const v4i r0 = rec[3 * k], r1 = rec[3 * k + 1], r2 = rec[3 * k + 2];
     QkfSite s;
     s.a = rfl(r0.x), s.a2 = rfl(r0.y), s.b = rfl(r0.z), s.b2 = rfl(r0.w);
-    s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.small = rfl(r1.w) != 0;
+    s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.small = (rfl(r1.w) & QK_REC_SMALL) != 0;
     s.inv = rfl(r2.x);
     s.ps = rfl(r2.y), s.pd = 1 << s.ps, s.next = rfl(r2.z);
     s.mt = s.a / TILE, s.nt = s.b2 / TILE, s.nn = s.a2 / TILE;

@@ -7,8 +7,14 @@
 //
 //   * X lives in LDS (complex128 interleaved, [b][a] row-major = "k-major" for the next site) whenever it fits the
 //     workgroup's X buffer (98.7 % of the sites and 88 % of the matrix work of the 60-qubit x 6-layer headline workload
-//     at 8192 elements).  When X and X' fit side by side, X' is built at the other end of the buffer (zeroed while the
-//     previous site's result is consumed); otherwise it overwrites X after a barrier;
+//     at 8192 elements).  Where X' is built and which part of X stays in LDS through a step is ONE rule (qk_plan.h: qk_resident; the step
+//     table carries its answer).  X sits at one end of the buffer and X' is built at the other end whenever that keeps panels of X alive:
+//     when the two fit side by side every panel stays (X' zeroed while the previous site's result is consumed, one barrier between the
+//     phases); when each fits but not both, only the panels of X that X' overlaps are copied to the global buffer, the units of those row
+//     blocks run phase 1 in its global-X form and all the others in its LDS form -- a unit with row block ta reads only panel ta (the form
+//     is chosen per unit, not per step); a step that is LDS-resident by its single round alone overwrites X from element 0 behind a
+//     barrier.  The 12-wave shapes give the rule more elements than the segmentation counts on (QKF_RCAP_ONE against QKF_XCAP_ONE: the LDS
+//     the CU has beyond the buffer and the launch's tables), so more steps are side by side at the same plan, masks and step table;
 //   * the unit of work is an ITEM (ta, tb, p): one 16 x 16 tile T[ta, p, tb], dealt to the waves in rounds of consecutive indices.
 //     The order of the indices (qk_unit_decode, qk_plan.h: p slowest, ta fastest) decides what the waves of a round share: a round
 //     lies inside one p and covers a few column blocks tb with all their ta, so an A block (ta, p) is used by the tb of the round at
@@ -36,8 +42,8 @@
 //     chains of re = k1 + sum (tr - ti) Ar and im = k1 + sum (-tr - ti) Ai START on it (the C operand of their first matrix instruction),
 //     so a column block ends in its ds_add_f64 with no v_add_f64 behind the matrix instructions and forms ONE operand sum per fragment
 //     element (qkf_p2_onesum; lab/NOTES_r07.md, lab/NOTES_r10.md);
-//   * sites too large for the LDS run in STRIPS: X is read from a per-workgroup global buffer (A-operand fragments
-//     loaded like the site tensors), X' is accumulated a block of b' rows at a time (as many as fit the LDS), items in
+//   * sites whose X or X' is too large for the LDS run in STRIPS: X is read whole from a per-workgroup global buffer (A-operand
+//     fragments loaded like the site tensors), X' is accumulated a block of b' rows at a time (as many as fit the LDS), items in
 //     rounds of (waves x slots), and written to the other global buffer;
 //   * the chain is walked in STEPS: the first and last k sites of both states come as edge blocks (one product each), a step in
 //     between is one site or two neighbouring sites contracted into one tensor of physical dimension 4 (merged image of the set),
@@ -60,6 +66,9 @@
 #pragma once
 #include "qk_device.h"
 #include "qk_plan.h"  // the order of a step's units (qk_unit_decode)
+
+#include <cstddef>
+#include <type_traits>
 
 // Wave priority: a wave that is NOT in a matrix block (tile tails with their adds and LDS atomics, item set-up, barriers)
 // runs at raised priority, so that it gets the issue slots ahead of the other wave's matrix stream and is back at its own
@@ -795,6 +804,7 @@ __device__ __forceinline__ void qkf_edge_suffix(const SweepArgs& g, const int xi
 // What a site needs: bonds, tile counts, where its X / X' live and how its items are cut into strips.
 struct QkfSite {
   int a, a2, b, b2, at, nks, mt, nt, nn, W, inv, inv2, pd, ps, next;  // inv2 = the two reciprocals of the strips' column units (qk_unit_recips); next = the table entry of the step after this one; pd = physical dimension of the step (2, or 4 for two merged sites), ps = log2 pd; inv = ceil(2^20 / mt): u / mt == (u * inv) >> 20 for u < 2048, mt <= 32 (checked exhaustively)
+  int flags;  // word [7] of the record: LDS-resident, orientation, switch, and the residency of X (qk_plan.h: qk_rec_resident)
   bool small, sw;  // sw: the step ends with a switch of orientation (qkf_p2_switch)
   const v2d *Ak, *Bk;
 };
@@ -802,7 +812,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4i lds_v4i;
 
 // The step table of a pair, built by all threads at pair set-up: per step 12 ints (48 bytes)
-//   [0] a  [1] a2  [2] b  [3] b2  [4] true a  [5] k-steps of b  [6] W  [7] small | orientation << 1 | switch << 2  [8] ceil(2^20 / mt)  [9] log2 pd  [10] next step
+//   [0] a  [1] a2  [2] b  [3] b2  [4] true a  [5] k-steps of b  [6] W  [7] small | orientation << 1 | switch << 2 | the residency of X (qk_plan.h: qk_rec_resident)  [8] ceil(2^20 / mt)  [9] log2 pd  [10] next step
 //   [11] ITEM_RECIPS (the one-tile kernel's order of items): ceil(2^15 / column blocks) of a full strip | of the last strip << 16 (qk_unit_recips)
 // and the addresses of the step's two tensors ([a][pd][a2] of x, [b][pd][b2] of y) in a second table.  A step is one site (pd = 2,
 // entry = the site's index, next = + 1) or, with a merged image, two sites contracted into one tensor of physical dimension 4 (entry =
@@ -892,12 +902,13 @@ __device__ __forceinline__ void qkf_pull_next(const SweepArgs& g, const int xcc,
   *word = pp;
 }
 
-template <int NW, int S, int XCAP, int WPS, bool DET = false>  // waves per workgroup; T slots per wave (a round holds NW * S items); elements of the LDS X buffer; waves per SIMD (register budget); ordered accumulation (bit-reproducible)
+template <int NW, int S, int XCAP, int WPS, bool DET = false, int RCAP = XCAP>  // waves per workgroup; T slots per wave (a round holds NW * S items); elements of the LDS X buffer as the segmentation sees it; waves per SIMD (register budget); ordered accumulation (bit-reproducible); elements the buffer really has (the residency of X: qk_plan.h, qk_resident)
 __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const SweepArgs g) {
   constexpr int NT = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) double lds_raw[];
   lds_v2d* const XL = (lds_v2d*)lds_raw;  // (a C-style cast: the generic -> LDS address-space cast)
-  long long* const slot = reinterpret_cast<long long*>(lds_raw + 2 * XCAP);
+  static_assert(RCAP >= XCAP && RCAP % QKF_XBLOCK == 0, "the buffer holds what the segmentation counts on, in whole blocks");
+  long long* const slot = reinterpret_cast<long long*>(lds_raw + 2 * RCAP);
   const v2d* const xdata = reinterpret_cast<const v2d*>(g.xdata);  // interleaved complex128 images
   const v2d* const ydata = reinterpret_cast<const v2d*>(g.ydata);
   v2d* const G0 = reinterpret_cast<v2d*>(g.scratch) + (long long)blockIdx.x * 2 * g.x_plane;  // two global X buffers of x_plane complex
@@ -922,7 +933,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
     const v4i r0 = rec[3 * k], r1 = rec[3 * k + 1], r2 = rec[3 * k + 2];  // every lane reads the same 48 bytes
     QkfSite s;
     s.a = rfl(r0.x), s.a2 = rfl(r0.y), s.b = rfl(r0.z), s.b2 = rfl(r0.w);
-    s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.small = (rfl(r1.w) & QK_REC_SMALL) != 0, s.sw = (rfl(r1.w) & QK_REC_SWITCH) != 0;
+    s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.flags = rfl(r1.w), s.small = (s.flags & QK_REC_SMALL) != 0, s.sw = (s.flags & QK_REC_SWITCH) != 0;
     s.inv = rfl(r2.x), s.inv2 = rfl(r2.w);
     s.ps = rfl(r2.y), s.pd = 1 << s.ps, s.next = rfl(r2.z);
     s.mt = s.a / TILE, s.nt = s.b2 / TILE, s.nn = s.a2 / TILE;
@@ -962,7 +973,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
     // an item is (ta, tb, p): pd mt nt of them.  LDS-resident step: X and X' fit the buffer and either ONE round holds all items
     // (X' may then overwrite X) or X and X' fit side by side (any number of rounds: X stays intact);
     // otherwise X' is built in strips of W blocks of b' (the strip's rows must fit the LDS), items in rounds of NW * S
-    qkf_step_table<XCAP, NT, true>(g, xi, yj, p, rec, m_off, tid, QkSegRule{XCAP, NW * S, false});
+    qkf_step_table<XCAP, NT, true>(g, xi, yj, p, rec, m_off, tid, QkSegRule{XCAP, NW * S, false, RCAP, QKF_RES_PARTIAL != 0});
     const int ek = g.edge_k, k_hi = ns - ek;  // the chain runs over the sites [ek, k_hi): the ends are in the edge blocks
     const bool edges = ek > 0;
     if (!edges)
@@ -971,14 +982,12 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
       for (int e = tid; e < 2 * g.turn_ints + 2; e += NT) tbroken[e] = 0;
     int tsel = 0;  // DET: the set of turn counters in use (the other one is zeroed meanwhile for the next strip or step)
     __syncthreads();
-    bool xg = false;  // where X lives: LDS (at element xb, row stride a) or the global buffer G0 + cur * x_plane
-    int cur = 0, xb = 0;
+    int cur = 0, xb = 0;  // where X lives: LDS (at element xb, in panels) while it fits the segmentation's buffer, else the global buffer G0 + cur * x_plane
     if (edges) {  // X behind the left edge: one product of the two left blocks
       const v4i r0 = rec[3 * ek];
       const int a_e = rfl(r0.x), b_e = rfl(r0.z);  // (of a chain that starts in orientation 1: the record of the exchanged states)
       const bool o1 = !DET && (rfl(rec[3 * ek + 1].w) & QK_REC_ORIENT) != 0;  // (the ordered forms run orientation 0 throughout)
-      xg = a_e * b_e > XCAP;
-      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o1 ? yj : xi, o1 ? xi : yj, a_e, b_e, XL, G0, xg, wave, q, j, o1);
+      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o1 ? yj : xi, o1 ? xi : yj, a_e, b_e, XL, G0, a_e * b_e > XCAP, wave, q, j, o1);
       __syncthreads();
     }
     QKF_STAMP(0);  // pair set-up
@@ -994,22 +1003,23 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
       const bool small = sc.small;
       v2d* const Gc = G0 + (long long)cur * g.x_plane;
       v2d* const Gn = G0 + (long long)(cur ^ 1) * g.x_plane;
-      // ---- where X has to be for this site
-      if (small && xg) {  // global -> LDS
-        for (int e = tid; e < a * b; e += NT) XL[e] = Gc[e];
-        __syncthreads();
-        xg = false, xb = 0;
-      } else if (!small && !xg) {  // LDS -> global (the LDS is needed for the strips of X')
-        for (int e = tid; e < a * b; e += NT) Gc[e] = XL[xb + e];
-        __syncthreads();
-        xg = true;
-      }
-      // LDS-resident site: when X and X' fit the buffer side by side, X' goes to the other end and is zeroed right here
-      // (that region held the X of the previous site, dead since its last barrier): one barrier between the phases
-      // instead of barrier - zero - barrier.  Otherwise X' overwrites X from element 0.
+      // ---- where X has to be for this site: the residency rule (qk_plan.h: qk_resident) says where X' is built and which panels of X
+      // phase 1 reads from LDS -- [klo, khi), the others from the global buffer Gc
       const int n_out = sc.b2 * a2;
-      const bool pingpong = small && a * b + n_out <= XCAP;
-      const int ob = !small ? 0 : pingpong ? (xb == 0 ? XCAP - n_out : 0) : 0;  // where X' (or the strip of X') is built
+      // (X is in LDS exactly when it fits the segmentation's buffer: the left edge or the step before left it there whole, at xb; else it is in Gc, whole)
+      const QkResident rs = qk_rec_resident(sc.flags, mt, n_out, RCAP, xb != 0);
+      if (a * b <= XCAP && rs.khi - rs.klo < mt) {  // LDS -> global: the panels that X' (or its strips) will overlap -- all of them, or the ones outside [klo, khi)
+        const int e0 = (rs.klo == 0 ? rs.khi : 0) * (b * TILE), e1 = (rs.klo == 0 ? mt : rs.klo) * (b * TILE);
+        for (int e = e0 + tid; e < e1; e += NT) Gc[e] = XL[xb + e];
+        __syncthreads();
+      }
+      const unsigned xgm = qk_res_global_mask(rs);  // bit ta: the units of row block ta read their panel of X from Gc
+      // When X and X' fit the buffer side by side, X' goes to the other end and is zeroed right here
+      // (that region held the X of the previous site, dead since its last barrier): one barrier between the phases
+      // instead of barrier - zero - barrier.  A partially resident step builds X' at the other end too, in the manner of a single strip.
+      // Otherwise X' overwrites X from element 0.
+      const bool pingpong = rs.kind == QK_RES_SIDE;
+      const int ob = rs.ob;  // where X' (or the strip of X') is built
       if (pingpong && !DET)
         for (int e = tid; e < n_out; e += NT) XL[ob + e] = (v2d){0.0, 0.0};
       QKF_STAMP(1);  // X moved between LDS and the global buffer
@@ -1018,8 +1028,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
         lds_int* const tcur = turn0 + tsel * g.turn_ints;
         if constexpr (DET) {  // (ordered accumulation: the first contribution to a block stores, nothing is zeroed but the next set of counters)
           for (int e = tid; e < g.turn_ints; e += NT) turn0[(tsel ^ 1) * g.turn_ints + e] = 0;
-        } else if (!small) {  // zero this strip's X' rows (the LDS-resident path zeroes after phase 1: X is still being read)
-          for (int e = tid; e < w * TILE * a2; e += NT) XL[e] = (v2d){0.0, 0.0};
+        } else if (!small && !pingpong) {  // zero this strip's X' rows (the in-place path zeroes after phase 1: X is still being read)
+          for (int e = tid; e < w * TILE * a2; e += NT) XL[ob + e] = (v2d){0.0, 0.0};
           QKF_STEP_BARRIER();
         }
         QKF_STAMP(6);  // strip zeroing
@@ -1028,6 +1038,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
           const bool multi = L > 1;
           const int it0 = r0 + wave;          // this wave's items: it0, it0 + NW, ...
           // ---- phase 1: the T tile of each of this wave's items
+          // (xbase: where this wave's items read X -- the LDS, the global buffer, or, with more than one slot, nullptr: per item by its panel)
           auto phase1 = [&](auto xbase) __attribute__((always_inline)) {
 #pragma unroll 1
             for (int s = 0; s < L; ++s) {
@@ -1037,15 +1048,27 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
                 const int ta = item_of(sc, w, it).ta;
                 const bool more = s + 1 < L && it + NW < items;  // another tile follows in this phase; else phase 2 starts with item it0
                 const QkfStream nxt = more ? b_stream(sc, s0, w, it + NW) : a_stream(sc, w, it0);
-                qkf_p1_tile(T[S - 1], fr, primed, b_stream(sc, s0, w, it), xbase, (unsigned)(ta * (b * TILE) + q * TILE + j), sc.nks, nxt);
+                const unsigned xoff = (unsigned)(ta * (b * TILE) + q * TILE + j);
+                if constexpr (std::is_same<decltype(xbase), std::nullptr_t>::value) {
+                  if ((xgm >> ta) & 1u) qkf_p1_tile(T[S - 1], fr, primed, b_stream(sc, s0, w, it), (const v2d*)Gc, xoff, sc.nks, nxt);
+                  else qkf_p1_tile(T[S - 1], fr, primed, b_stream(sc, s0, w, it), (const lds_v2d*)(XL + xb), xoff, sc.nks, nxt);
+                } else {
+                  qkf_p1_tile(T[S - 1], fr, primed, b_stream(sc, s0, w, it), xbase, xoff, sc.nks, nxt);
+                }
                 primed = true;
               }
             }
           };
-          if (xg) phase1((const v2d*)Gc);
-          else phase1((const lds_v2d*)(XL + xb));
+          // one slot: the wave has one item per round, so its panel decides for the whole call (the loop then holds ONE form of the tile, as it
+          // did when the choice was per step: with both forms in the loop the 128-register kernel spills twice as much)
+          if constexpr (S == 1) {
+            if (it0 < items && ((xgm >> item_of(sc, w, it0).ta) & 1u)) phase1((const v2d*)Gc);
+            else phase1((const lds_v2d*)(XL + xb));
+          } else {
+            phase1(nullptr);
+          }
           QKF_STAMP(2);  // phase 1
-          if (small && r0 == 0 && !(DET && pingpong)) {
+          if ((small || pingpong) && r0 == 0 && !(DET && pingpong)) {
             QKF_STEP_BARRIER();  // ping-pong: X' is zero everywhere; in place (one round): every wave has read X, it becomes X'
             if (!pingpong && !DET) {
               for (int e = tid; e < n_out; e += NT) XL[e] = (v2d){0.0, 0.0};
@@ -1091,12 +1114,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
           QKF_STAMP(1);
         }
       }
-      if (!small) {
-        if (nt > W) cur ^= 1;      // X' was written strip by strip to Gn
-        else xg = false, xb = 0;   // a single strip: X' is complete in LDS
-      } else {
-        xb = ob;
-      }
+      if (nt > W) cur ^= 1, xb = 0;  // X' was written strip by strip to Gn
+      else xb = ob;                  // X' is complete in LDS
     }
     // the orientation the chain ends in: that of its last step (whose second site, if it is a merged one, carries the same flags), switched once more if that step switches
     const int fl_end = DET ? 0 : rfl(rec[3 * (k_hi - 1) + 1].w);
@@ -1104,7 +1123,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
     if (edges) {  // the overlap: X against the product of the two right blocks
       const v4i r0 = rec[3 * (k_hi - 1)];
       const int a_l = rfl(r0.y), b_l = rfl(r0.w), a_e = sw_end ? b_l : a_l, b_e = sw_end ? a_l : b_l;  // (the last record is in the last step's orientation)
-      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o_end ? yj : xi, o_end ? xi : yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), xg, zacc, wave,
+      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o_end ? yj : xi, o_end ? xi : yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), a_e * b_e > XCAP, zacc, wave,
                                                                    q, j, o_end);
       __syncthreads();
     }
@@ -1112,7 +1131,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_kernel(const Swee
       v2d zz = {0.0, 0.0};
       if (edges)
         for (int w_ = 0; w_ < NW; ++w_) zz.x += zacc[2 * w_], zz.y += zacc[2 * w_ + 1];
-      else zz = xg ? G0[(long long)cur * g.x_plane] : (v2d)XL[xb];
+      else zz = (v2d)XL[xb];  // (a chain without edge blocks ends in a 16 x 16 block: in LDS)
       if (o_end) zz.y = -zz.y;  // a chain that ends in orientation 1 yields conj(z)
       g.values[p] = zz.x * zz.x + zz.y * zz.y;
       if (g.z) {
@@ -1346,12 +1365,13 @@ __device__ __forceinline__ void qkf_p2_dual(const QkfTile& t0, const QkfTile& t1
   qkf_p2_block<FULL, HAS1>(t0, t1, s0, s1, fr, kmax, nxt.base, nxt.base + nxt.step, nxt.base + 2 * nxt.step, nxt.base + 3 * nxt.step, nxt.off, d, d1, rs);
 }
 
-template <int NW, int XCAP, int WPS, bool DET = false>  // waves per workgroup (a round holds NW pairs of tiles); elements of the LDS X buffer; waves per SIMD (register budget); ordered accumulation (bit-reproducible)
+template <int NW, int XCAP, int WPS, bool DET = false, int RCAP = XCAP>  // waves per workgroup (a round holds NW pairs of tiles); elements of the LDS X buffer as the segmentation sees it; waves per SIMD (register budget); ordered accumulation (bit-reproducible); elements the buffer really has (the residency of X)
 __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const SweepArgs g) {
   constexpr int NT = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) double lds_raw[];
   lds_v2d* const XL = (lds_v2d*)lds_raw;
-  long long* const slot = reinterpret_cast<long long*>(lds_raw + 2 * XCAP);
+  static_assert(RCAP >= XCAP && RCAP % QKF_XBLOCK == 0, "the buffer holds what the segmentation counts on, in whole blocks");
+  long long* const slot = reinterpret_cast<long long*>(lds_raw + 2 * RCAP);
   const v2d* const xdata = reinterpret_cast<const v2d*>(g.xdata);
   const v2d* const ydata = reinterpret_cast<const v2d*>(g.ydata);
   v2d* const G0 = reinterpret_cast<v2d*>(g.scratch) + (long long)blockIdx.x * 2 * g.x_plane;
@@ -1375,7 +1395,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
     const v4i r0 = rec[3 * k], r1 = rec[3 * k + 1], r2 = rec[3 * k + 2];
     QkfSite s;
     s.a = rfl(r0.x), s.a2 = rfl(r0.y), s.b = rfl(r0.z), s.b2 = rfl(r0.w);
-    s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.small = (rfl(r1.w) & QK_REC_SMALL) != 0, s.sw = (rfl(r1.w) & QK_REC_SWITCH) != 0;
+    s.at = rfl(r1.x), s.nks = rfl(r1.y), s.W = rfl(r1.z), s.flags = rfl(r1.w), s.small = (s.flags & QK_REC_SMALL) != 0, s.sw = (s.flags & QK_REC_SWITCH) != 0;
     s.inv = rfl(r2.x);
     s.ps = rfl(r2.y), s.pd = 1 << s.ps, s.next = rfl(r2.z);
     s.mt = s.a / TILE, s.nt = s.b2 / TILE, s.nn = s.a2 / TILE;
@@ -1433,7 +1453,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
   auto table_of = [&](const long long pp) __attribute__((always_inline)) {
     if (pp < 0) return;
     const int xi_ = g.pairs[2 * pp], yj_ = g.pairs[2 * pp + 1];
-    qkf_step_table<XCAP, NT>(g, xi_, yj_, pp, rec, m_off, tid, QkSegRule{XCAP, NW, true});
+    qkf_step_table<XCAP, NT>(g, xi_, yj_, pp, rec, m_off, tid, QkSegRule{XCAP, NW, true, RCAP, QKF_RES_PARTIAL != 0});
   };
   table_of(p);
   while (p >= 0) {
@@ -1448,14 +1468,12 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
       for (int e = tid; e < 2 * g.turn_ints + 2; e += NT) tbroken[e] = 0;
     int tsel = 0;  // DET: the set of turn counters in use (the other one is zeroed meanwhile for the next strip or step)
     __syncthreads();
-    bool xg = false;
     int cur = 0, xb = 0;
     if (edges) {  // X behind the left edge: one product of the two left blocks
       const v4i r0 = rec[3 * ek];
       const int a_e = rfl(r0.x), b_e = rfl(r0.z);  // (of a chain that starts in orientation 1: the record of the exchanged states)
       const bool o1 = !DET && (rfl(rec[3 * ek + 1].w) & QK_REC_ORIENT) != 0;  // (the ordered form runs orientation 0 throughout)
-      xg = a_e * b_e > XCAP;
-      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o1 ? yj : xi, o1 ? xi : yj, a_e, b_e, XL, G0, xg, wave, q, j, o1);
+      qkf_edge_prefix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o1 ? yj : xi, o1 ? xi : yj, a_e, b_e, XL, G0, a_e * b_e > XCAP, wave, q, j, o1);
       __syncthreads();
     }
     QKF_STAMP(0);  // pair set-up (queue, step table, left edge)
@@ -1471,18 +1489,17 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
       const bool small = sc.small;
       v2d* const Gc = G0 + (long long)cur * g.x_plane;
       v2d* const Gn = G0 + (long long)(cur ^ 1) * g.x_plane;
-      if (small && xg) {
-        for (int e = tid; e < a * b; e += NT) XL[e] = Gc[e];
-        __syncthreads();
-        xg = false, xb = 0;
-      } else if (!small && !xg) {
-        for (int e = tid; e < a * b; e += NT) Gc[e] = XL[xb + e];
-        __syncthreads();
-        xg = true;
-      }
+      // the residency of X (qk_plan.h: qk_resident), as in qk_sweep_fused_kernel: where X' is built, the panels [klo, khi) phase 1 reads from LDS
       const int n_out = sc.b2 * a2;
-      const bool pingpong = small && a * b + n_out <= XCAP;
-      const int ob = !small ? 0 : pingpong ? (xb == 0 ? XCAP - n_out : 0) : 0;
+      const QkResident rs = qk_rec_resident(sc.flags, mt, n_out, RCAP, xb != 0);
+      if (a * b <= XCAP && rs.khi - rs.klo < mt) {  // (X is in LDS exactly when it fits the segmentation's buffer) the panels that X' or its strips will overlap go to the global buffer
+        const int e0 = (rs.klo == 0 ? rs.khi : 0) * (b * TILE), e1 = (rs.klo == 0 ? mt : rs.klo) * (b * TILE);
+        for (int e = e0 + tid; e < e1; e += NT) Gc[e] = XL[xb + e];
+        __syncthreads();
+      }
+      const unsigned xgm = qk_res_global_mask(rs);  // bit ta: the units of row block ta read their panel of X from Gc
+      const bool pingpong = rs.kind == QK_RES_SIDE;
+      const int ob = rs.ob;
       if (pingpong && !DET)
         for (int e = tid; e < n_out; e += NT) XL[ob + e] = (v2d){0.0, 0.0};
       QKF_STAMP(1);  // step set-up: record decode, X moved between LDS and the global buffer, X' zeroed (ping-pong)
@@ -1491,8 +1508,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
         lds_int* const tcur = turn0 + tsel * g.turn_ints;
         if constexpr (DET) {  // (ordered accumulation: the first contribution to a block stores, nothing is zeroed but the next set of counters)
           for (int e = tid; e < g.turn_ints; e += NT) turn0[(tsel ^ 1) * g.turn_ints + e] = 0;
-        } else if (!small) {
-          for (int e = tid; e < w * TILE * a2; e += NT) XL[e] = (v2d){0.0, 0.0};
+        } else if (!small && !pingpong) {
+          for (int e = tid; e < w * TILE * a2; e += NT) XL[ob + e] = (v2d){0.0, 0.0};
           QKF_STEP_BARRIER();
         }
         for (int r0 = 0; r0 < units; r0 += NW) {  // (LDS-resident sites: one round, or several when X and X' sit side by side)
@@ -1504,7 +1521,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
           if (mine) {
             const QkfStream bs = b_stream(sc, s0, v, un.half), as = a_stream(sc, v);
             const unsigned xoff = (unsigned)(ta * (b * TILE) + q * TILE + j);
-            if (xg) {
+            if ((xgm >> ta) & 1u) {  // this unit's panel of X is in the global buffer
               if (has1) qkf_p1_dual<true>(T0, T1, fr, fs, primed, bs, (const v2d*)Gc, xoff, sc.nks, as);
               else qkf_p1_dual<false>(T0, T1, fr, fs, primed, bs, (const v2d*)Gc, xoff, sc.nks, as);
             } else {
@@ -1513,7 +1530,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
             }
           }
           QKF_STAMP(2);  // phase 1
-          if (small && r0 == 0 && !(DET && pingpong)) {
+          if ((small || pingpong) && r0 == 0 && !(DET && pingpong)) {
             QKF_STEP_BARRIER();  // ping-pong: X' is zero everywhere; in place (one round): every wave has read X, it becomes X'
             if (!pingpong && !DET) {
               for (int e = tid; e < n_out; e += NT) XL[e] = (v2d){0.0, 0.0};
@@ -1573,12 +1590,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
           __syncthreads();
         }
       }
-      if (!small) {
-        if (nt > W) cur ^= 1;
-        else xg = false, xb = 0;
-      } else {
-        xb = ob;
-      }
+      if (nt > W) cur ^= 1, xb = 0;
+      else xb = ob;
     }
     if (tid == QKF_PULLER(NT)) qkf_pull_next(g, xcc, gang_round, slot + (psel ^ 1));  // the next pair, while the other wavefronts run the right edge
     // the orientation the chain ends in: that of its last step (whose second site, if it is a merged one, carries the same flags), switched once more if that step switches
@@ -1587,7 +1600,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
     if (edges) {  // the overlap: X against the product of the two right blocks
       const v4i r0 = rec[3 * (k_hi - 1)];
       const int a_l = rfl(r0.y), b_l = rfl(r0.w), a_e = sw_end ? b_l : a_l, b_e = sw_end ? a_l : b_l;  // (the last record is in the last step's orientation)
-      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o_end ? yj : xi, o_end ? xi : yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), xg, zacc, wave,
+      qkf_edge_suffix<NW, QKF_EDGE_PAIRS(WPS), QKF_EDGE_SETS(WPS)>(g, o_end ? yj : xi, o_end ? xi : yj, a_e, b_e, (const lds_v2d*)(XL + xb), (const v2d*)(G0 + (long long)cur * g.x_plane), a_e * b_e > XCAP, zacc, wave,
                                                                    q, j, o_end);
     }
     __syncthreads();  // the partial sums and the next pair's index are in LDS; nobody reads this pair's step table any more
@@ -1596,7 +1609,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void qk_sweep_fused_dual_kernel(const
       v2d zz = {0.0, 0.0};
       if (edges)
         for (int w_ = 0; w_ < NW; ++w_) zz.x += zacc[2 * w_], zz.y += zacc[2 * w_ + 1];
-      else zz = xg ? G0[(long long)cur * g.x_plane] : (v2d)XL[xb];
+      else zz = (v2d)XL[xb];  // (a chain without edge blocks ends in a 16 x 16 block: in LDS)
       if (o_end) zz.y = -zz.y;  // a chain that ends in orientation 1 yields conj(z)
       g.values[p] = zz.x * zz.x + zz.y * zz.y;
       if (g.z) {

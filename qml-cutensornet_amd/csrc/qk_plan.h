@@ -24,6 +24,23 @@ int qk_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3))
 #endif
 static constexpr int QKF_XCAP_ONE = QKF_XCAP_ONE_V, QKF_XCAP_TWO = QKF_XCAP_TWO_V;  // elements of the fused sweep's LDS X buffer with one / two workgroups per CU
 static constexpr int QK_TILE = 16;                                        // M/N granule of v_mfma_f64_16x16x4_f64
+// The residency of X (qk_resident below), two parts behind compile-time switches for A/B builds, both on by default:
+//   QKF_RES_PARTIAL  a step whose X and X' each fit the buffer but not together evicts only the panels of X that X' overlaps (0: all of X);
+//   QKF_RES_BIG      the 12-wave shapes offer X and X' the LDS the CU has beyond the segmentation's buffer (0: QKF_XCAP_ONE).
+#ifndef QKF_RES_PARTIAL
+#define QKF_RES_PARTIAL 1
+#endif
+#ifndef QKF_RES_BIG
+#define QKF_RES_BIG 1
+#endif
+// The large buffer of the 12-wave shapes, from the kernels' static LDS layout: the X buffer first, behind it the queue slot, the overlap's
+// partial sums, the step table and (DET) the turn counters -- QKF_META_ROOM bytes are left for those, and a launch whose chain needs more
+// runs the instantiation with QKF_XCAP_ONE elements (qk_choose_sweep below: QkSweepRun.big).  The segmentation, the class split, the strip width and the
+// switch test keep QKF_XCAP_ONE: only qk_resident sees the larger number.
+static constexpr int QKF_LDS_BYTES = 160 * 1024, QKF_META_ROOM = 8 * 1024;
+static constexpr int QKF_RCAP_ONE = QKF_RES_BIG ? (QKF_LDS_BYTES - QKF_META_ROOM) / 16 / (QK_TILE * QK_TILE) * (QK_TILE * QK_TILE) : QKF_XCAP_ONE;
+static_assert(QKF_RCAP_ONE >= QKF_XCAP_ONE && (long long)QKF_RCAP_ONE * 16 + QKF_META_ROOM <= QKF_LDS_BYTES && QKF_RCAP_ONE % (QK_TILE * QK_TILE) == 0,
+              "the large X buffer and the room behind it fit the LDS of a CU; the buffer holds whole 16 x 16 blocks");
 static inline int qk_pad16(int x) { return (x + QK_TILE - 1) / QK_TILE * QK_TILE; }
 static constexpr int GMAX = 4;  // pairs per group of the group-sweep lab kernel (sizes its X/T scratch)
 
@@ -121,6 +138,8 @@ static constexpr int QK_SEG_BITS = 128;
 struct QkSegRule {  // a launch's shape: elements of its LDS X buffer; one round holds pd mt ceil(nt / 2) <= cap pairs of tiles (dual) or pd mt nt <= cap tiles
   int xcap, cap;
   bool dual;
+  int rcap = 0;          // elements the residency of X may use (qk_resident): the physical buffer, >= xcap; 0 = xcap.  The segmentation never reads it
+  bool partial = false;  // ... and whether a step may keep PART of X in LDS (QKF_RES_PARTIAL)
 };
 struct QkSegMask {
   unsigned long long w[2];
@@ -130,6 +149,55 @@ QK_HD static inline bool qk_seg_one_round(const QkSegRule& r, const int pmt, con
 // LDS-resident step: X and X' fit the buffer and either ONE round holds all units (X' may then overwrite X) or X and X' fit side by side
 QK_HD static inline bool qk_seg_small(const QkSegRule& r, const int a, const int a2, const int b, const int b2, const int pd) {
   return a * b <= r.xcap && a2 * b2 <= r.xcap && (qk_seg_one_round(r, pd * (a / QK_TILE), b2 / QK_TILE) || a * b + a2 * b2 <= r.xcap);
+}
+// THE RESIDENCY OF X IN A STEP: where X' is built and which panels of X (16 columns each, a / 16 of b * 16 elements: qk_fused.h) phase 1
+// reads from LDS.  X sits at one END of the buffer of qk_res_cap elements -- at element 0, or at the top (x_top: its last element is the
+// buffer's last) -- and X' is built at the other end whenever that lets panels of X live through the step:
+//   QK_RES_SIDE     X and X' fit side by side: X' at the other end, every panel stays, nothing is copied;
+//   QK_RES_INPLACE  LDS-resident by its single round alone (qk_seg_small, not side by side): every unit reads X from LDS in phase 1, then X'
+//                   overwrites it from element 0 behind a barrier;
+//   QK_RES_PART     X fits, X' fits, not together, more than one round: X' at the other end; the panels it overlaps go to the global buffer
+//                   and their units read them there, the panels [klo, khi) at the far end stay -- a unit with row block ta reads only
+//                   panel ta.  As many stay as fit (none when X' needs the whole buffer);
+//   QK_RES_NONE     anything else -- X or X' does not fit the segmentation's buffer (strips), or partial residency is off: X goes to the
+//                   global buffer whole, X' (or each strip of it) is built at element 0.
+// "Fits" is the segmentation's xcap throughout, so the plan, the masks, the strip width and what may switch do not depend on rcap; only
+// "together" and the place of X' see the larger buffer.  With rcap = xcap and partial off this is the classification the kernels had
+// before the rule (tests/host_san/resident_main.cpp).  Pure, host and device; the step table carries it (qk_step_record, word [7]).
+static constexpr int QK_RES_NONE = 0, QK_RES_SIDE = 1, QK_RES_PART = 2, QK_RES_INPLACE = 3;
+struct QkResident {
+  int kind, ob;  // QK_RES_*; the element of the buffer where X' (or a strip of it) is built
+  int klo, khi;  // phase 1 reads the panels [klo, khi) of X from LDS, the others from the global buffer
+};
+QK_HD static inline int qk_res_cap(const QkSegRule& r) { return r.rcap > r.xcap ? r.rcap : r.xcap; }
+// the same as one word for the kernels: bit ta set = the units of row block ta read their panel from the global buffer (a / 16 <= 32 panels)
+QK_HD static inline unsigned qk_res_global_mask(const QkResident& s) { return ~(unsigned)(((1ull << s.khi) - 1ull) & ~((1ull << s.klo) - 1ull)); }
+QK_HD static inline QkResident qk_resident(const QkSegRule& r, const int a, const int a2, const int b, const int b2, const int pd, const bool x_top) {
+  const int rcap = qk_res_cap(r), n_in = a * b, n_out = a2 * b2, mt = a / QK_TILE, panel = b * QK_TILE;
+  if (n_in > r.xcap || n_out > r.xcap) return QkResident{QK_RES_NONE, 0, 0, 0};
+  const int ob = x_top ? 0 : rcap - n_out;  // the other end
+  if (n_in + n_out <= rcap) return QkResident{QK_RES_SIDE, ob, 0, mt};
+  if (qk_seg_small(r, a, a2, b, b2, pd)) return QkResident{QK_RES_INPLACE, 0, 0, mt};
+  if (!r.partial) return QkResident{QK_RES_NONE, 0, 0, 0};
+  if (x_top) {  // X = [rcap - n_in, rcap), X' = [0, n_out): the panels from the first one that starts at or above n_out stay
+    const int over = n_out - (rcap - n_in), t0 = (over + panel - 1) / panel;  // (over > 0: they do not fit together)
+    return QkResident{QK_RES_PART, ob, t0 < mt ? t0 : mt, mt};
+  }
+  const int t0 = ob / panel;  // X = [0, n_in), X' = [rcap - n_out, rcap): the panels that end at or below ob stay
+  return QkResident{QK_RES_PART, ob, 0, t0 < mt ? t0 : mt};
+}
+// the rule in the step table's word [7]: the kind, and the boundary panel t0 of a partially resident step for X at the low end ([0, t0) stay)
+// and for X at the top ([t0, mt) stay) -- the kind does not depend on the end
+static constexpr int QK_REC_KIND_SHIFT = 3, QK_REC_T0_LOW_SHIFT = 8, QK_REC_T0_TOP_SHIFT = 16;
+QK_HD static inline int qk_rec_resident_bits(const QkSegRule& r, const int a, const int a2, const int b, const int b2, const int pd) {
+  const QkResident lo = qk_resident(r, a, a2, b, b2, pd, false), hi = qk_resident(r, a, a2, b, b2, pd, true);
+  return (lo.kind << QK_REC_KIND_SHIFT) | (lo.khi << QK_REC_T0_LOW_SHIFT) | (hi.klo << QK_REC_T0_TOP_SHIFT);
+}
+QK_HD static inline QkResident qk_rec_resident(const int word, const int mt, const int n_out, const int rcap, const bool x_top) {
+  const int kind = (word >> QK_REC_KIND_SHIFT) & 3, t0 = (word >> (x_top ? QK_REC_T0_TOP_SHIFT : QK_REC_T0_LOW_SHIFT)) & 63;
+  const bool other_end = kind == QK_RES_SIDE || kind == QK_RES_PART;
+  if (kind == QK_RES_NONE) return QkResident{QK_RES_NONE, 0, 0, 0};
+  return QkResident{kind, other_end && !x_top ? rcap - n_out : 0, x_top ? t0 : 0, x_top ? mt : t0};
 }
 // matrix instructions of a step [a][pd][a2] x [b][pd][b2] (padded bonds) with true bonds at, bt on its left: phase 1 pd mt nt tiles of
 // ceil(bt / 4) k-steps, phase 2 pd nt nn tiles of ceil(at / 4) k-steps over the blocks of rows, three real products each
@@ -251,7 +319,7 @@ QK_HD static inline QkSegMask qk_segment_chain(const int32_t* const xd, const in
 }
 
 // The record of a step in the pair's step table (qk_fused.h: qkf_step_table), 12 ints:
-//   [0] a  [1] a2  [2] b  [3] b2  [4] true a  [5] k-steps of b  [6] W  [7] small | orientation << 1 | switch << 2  [8] ceil(2^20 / mt)
+//   [0] a  [1] a2  [2] b  [3] b2  [4] true a  [5] k-steps of b  [6] W  [7] small | orientation << 1 | switch << 2 | the residency of X (qk_rec_resident_bits)  [8] ceil(2^20 / mt)
 //   [9] log2 pd  [10] next step  [11] item_recips: the reciprocals of the strips' column units (qk_unit_recips), else 0
 // of the step of `len` sites (1, or 2: merged) that starts at site e.  A step in orientation 1 gets the record of the exchanged states.
 struct QkStepRec {
@@ -268,7 +336,8 @@ QK_HD static inline QkStepRec qk_step_record(const int32_t* xd, const int32_t* x
   const bool small = qk_seg_small(rule, a, a2, b, b2, 2 * len);
   const int mt = a / QK_TILE, nt = b2 / QK_TILE;
   const int lim = rule.xcap / (QK_TILE * a2), W = small ? nt : (lim < 1 ? 1 : lim < nt ? lim : nt);  // X' in strips of W blocks of b' (the strip's rows must fit the LDS)
-  return QkStepRec{{a, a2, b, b2, xt[e], (yt[e] + 3) >> 2, W, (small ? QK_REC_SMALL : 0) | (o ? QK_REC_ORIENT : 0) | (sw ? QK_REC_SWITCH : 0), qk_recip20(mt), len == 2 ? 2 : 1, e + len,
+  return QkStepRec{{a, a2, b, b2, xt[e], (yt[e] + 3) >> 2, W, (small ? QK_REC_SMALL : 0) | (o ? QK_REC_ORIENT : 0) | (sw ? QK_REC_SWITCH : 0) | qk_rec_resident_bits(rule, a, a2, b, b2, 2 * len), qk_recip20(mt),
+                    len == 2 ? 2 : 1, e + len,
                     item_recips ? qk_unit_recips(nt, W, false) : 0}};
 }
 
@@ -326,6 +395,7 @@ struct QkSweepPolicy {
   int switch_price = QK_SWITCH_PRICE;  // QK_SWITCH_PRICE: what the programme charges for a switch, in matrix instructions
   bool fused_dual = true;      // QK_FUSED_DUAL (0: single tiles): the 12-wave site-fused shape in its dual form (pairs of tiles per wave)
   bool gang = false;           // QK_GANG=1: gang start of the site-fused launches (qk_device.h: qk_gang_sync)
+  bool fused_big = true;       // QK_FUSED_BIG (0: the instantiations with the segmentation's buffer): the 12-wave site-fused shapes with the large X buffer (QKF_RCAP_ONE) when the chain's tables leave it room
 };
 
 struct QkSetShape {  // what the choice needs of a set: its largest padded bond, bits of a real, sites
@@ -338,6 +408,8 @@ struct QkSweepRun {  // one launch
   size_t lds = 0;                  // dynamic LDS bytes
   long long first = 0, count = 0;  // pairs [first, first + count) of the plan's list
   int nq = 1, gang_n = 0;          // SweepArgs
+  bool big = false;                // a 12-wave site-fused launch runs the instantiation with the LARGE X buffer (QKF_RCAP_ONE): its tables fit behind it
+  size_t lds_launch = 0;           // the dynamic LDS bytes the launch really asks for (qk_stats.lds_bytes): `lds`, or with `big` the large buffer and the same tables
   bool gang2 = false;              // its gang words lie behind the first launch's (the second launch of a split sweep)
 };
 
@@ -418,6 +490,11 @@ static inline QkSweepChoice qk_choose_sweep(const QkSweepPolicy& p, const qk_pla
     ch.interleaved = ch.fused_images = ch.tails = true, ch.queues = plan.nq > 1 ? 8 : 1, r.nq = plan.nq;
     r.kernel = fused_two ? (det ? QK_KERNEL_FUSED2_DET : QK_KERNEL_FUSED2) : dual ? (det ? QK_KERNEL_FUSED_DUAL_DET : QK_KERNEL_FUSED_DUAL) : (det ? QK_KERNEL_FUSED1_DET : QK_KERNEL_FUSED1);
     r.lds = (size_t)(fused_two ? QKF_XCAP_TWO : QKF_XCAP_ONE) * 16 + lds_meta;
+    // the 12-wave shapes take the large buffer (the residency of X alone sees it: the same plan, masks and step table) whenever the launch's
+    // tables fit the room the kernels' LDS layout leaves behind it -- chains of up to about 120 sites; DET: fewer, the turn counters grow with
+    // the bonds -- else, and with QK_FUSED_BIG=0, the instantiation with the segmentation's buffer
+    r.big = !fused_two && p.fused_big && QKF_RCAP_ONE > QKF_XCAP_ONE && lds_meta <= (size_t)QKF_META_ROOM;
+    if (r.big) r.lds_launch = (size_t)QKF_RCAP_ONE * 16 + lds_meta;
     // gang start: the workgroups of an XCD begin their pairs together; workgroups per XCD = grid / 8 (round-robin dispatch)
     auto gang_of = [&](const long long g) { return p.gang && plan.nq > 1 && g >= 16 && g % 8 == 0 ? (int)(g / 8) : 0; };
     if (split || mixed) {  // the first class with the shape above, then the second class, back to back on the stream; 8 queues per class
@@ -443,5 +520,7 @@ static inline QkSweepChoice qk_choose_sweep(const QkSweepPolicy& p, const qk_pla
     ch.rc = QK_EINVAL, snprintf(ch.err, sizeof ch.err, "qk_gram_values: no kernel for this call");
 #endif
   }
+  for (int i = 0; i < ch.n_runs; ++i)
+    if (!ch.run[i].big) ch.run[i].lds_launch = ch.run[i].lds;
   return ch;
 }

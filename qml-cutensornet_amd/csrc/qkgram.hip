@@ -168,6 +168,12 @@ extern "C" int qk_pack_state(int32_t n_sites, const int32_t* bond_dims, const do
 #define QKF_KERNEL_ONE_DET qk_sweep_fused_kernel<QKF_ONE_NW, QKF_ONE_S, QKF_XCAP_ONE, QKF_ONE_WPS, true>
 #define QKF_KERNEL_TWO_DET qk_sweep_fused_kernel<QKF_TWO_NW, QKF_TWO_S, QKF_XCAP_TWO, QKF_TWO_WPS, true>
 #define QKF_KERNEL_DUAL_DET qk_sweep_fused_dual_kernel<QKF_DUAL_NW, QKF_XCAP_ONE, QKF_DUAL_WPS, true>
+// the 12-wave shapes with the large X buffer (qk_plan.h: QKF_RCAP_ONE; the segmentation still counts on QKF_XCAP_ONE): launch_sweep takes them
+// whenever the launch's tables fit behind the larger buffer
+#define QKF_KERNEL_ONE_BIG qk_sweep_fused_kernel<QKF_ONE_NW, QKF_ONE_S, QKF_XCAP_ONE, QKF_ONE_WPS, false, QKF_RCAP_ONE>
+#define QKF_KERNEL_DUAL_BIG qk_sweep_fused_dual_kernel<QKF_DUAL_NW, QKF_XCAP_ONE, QKF_DUAL_WPS, false, QKF_RCAP_ONE>
+#define QKF_KERNEL_ONE_DET_BIG qk_sweep_fused_kernel<QKF_ONE_NW, QKF_ONE_S, QKF_XCAP_ONE, QKF_ONE_WPS, true, QKF_RCAP_ONE>
+#define QKF_KERNEL_DUAL_DET_BIG qk_sweep_fused_dual_kernel<QKF_DUAL_NW, QKF_XCAP_ONE, QKF_DUAL_WPS, true, QKF_RCAP_ONE>
 #if QKF_QUAD  // (lab builds: lab/qk_quad.h, 2 x 2 tiles per wave, 8 waves at two per SIMD)
 #define QKF_QUAD_NW 8
 #define QKF_KERNEL_QUAD qk_sweep_fused_quad_kernel<QKF_QUAD_NW, QKF_XCAP_ONE, 2>
@@ -407,7 +413,8 @@ static int ctx_init(qk_ctx* c, int device_id, int num_cus) {
   // the dynamic LDS the sweep kernels may ask for: 80 KiB (two workgroups per CU), a whole CU's 160 KiB, or its share per workgroup of the small-site shape
   for (const void* k : {(const void*)qk_sweep_ring_kernel<float>, (const void*)qk_sweep_ring_kernel<double>, (const void*)qk_sweep_small_kernel<double>, (const void*)qk_sweep_small_kernel<float>})
     HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-  for (const void* k : {(const void*)QKF_KERNEL_ONE, (const void*)QKF_KERNEL_DUAL, (const void*)QKF_KERNEL_ONE_DET, (const void*)QKF_KERNEL_DUAL_DET})
+  for (const void* k : {(const void*)QKF_KERNEL_ONE, (const void*)QKF_KERNEL_DUAL, (const void*)QKF_KERNEL_ONE_DET, (const void*)QKF_KERNEL_DUAL_DET, (const void*)QKF_KERNEL_ONE_BIG,
+                        (const void*)QKF_KERNEL_DUAL_BIG, (const void*)QKF_KERNEL_ONE_DET_BIG, (const void*)QKF_KERNEL_DUAL_DET_BIG})
     HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   for (const void* k : {(const void*)QKF_KERNEL_TWO, (const void*)QKF_KERNEL_TWO_DET}) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / QKF_TWO_WGS));
 #if QKF_QUAD
@@ -888,9 +895,23 @@ static int ensure_segments(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set* ys
   return QK_OK;
 }
 
-// one launch of a product sweep kernel (QK_KERNEL_*; f32: the set's planes are complex64)
-static int launch_sweep(const int kernel, const bool f32, const long long grid_, const size_t lds, const hipStream_t s, const SweepArgs& a) {
+// one launch of a product sweep kernel (QK_KERNEL_*; f32: the set's planes are complex64) with `lds` bytes of dynamic LDS.  big: the choice
+// (qk_plan.h: qk_choose_sweep) gave a 12-wave site-fused launch the instantiation with QKF_RCAP_ONE elements -- the same plan, masks and step
+// table, more steps with X and X' side by side (qk_resident) -- and `lds` is sized for it.
+static int launch_sweep(const int kernel, const bool f32, const long long grid_, const size_t lds, const hipStream_t s, const SweepArgs& a, const bool big) {
   const dim3 grid((unsigned)grid_);
+  if (big) {
+    const size_t lds_big = lds;
+    switch (kernel) {
+      case QK_KERNEL_FUSED1: QKF_KERNEL_ONE_BIG<<<grid, dim3(64 * QKF_ONE_NW), lds_big, s>>>(a); return QK_OK;
+      case QK_KERNEL_FUSED1_DET: QKF_KERNEL_ONE_DET_BIG<<<grid, dim3(64 * QKF_ONE_NW), lds_big, s>>>(a); return QK_OK;
+#if !QKF_QUAD
+      case QK_KERNEL_FUSED_DUAL: QKF_KERNEL_DUAL_BIG<<<grid, dim3(64 * QKF_DUAL_NW), lds_big, s>>>(a); return QK_OK;
+#endif
+      case QK_KERNEL_FUSED_DUAL_DET: QKF_KERNEL_DUAL_DET_BIG<<<grid, dim3(64 * QKF_DUAL_NW), lds_big, s>>>(a); return QK_OK;
+      default: return fail(QK_EINVAL, "qk_gram_values: kernel %d has no instantiation with the large X buffer", kernel);
+    }
+  }
   switch (kernel) {
     case QK_KERNEL_WAVE: qk_sweep_wave_kernel<0><<<grid, dim3(64), lds, s>>>(a); break;
     case QK_KERNEL_WAVE2: if (f32) qk_sweep_wave2_kernel<3, float><<<grid, dim3(64), lds, s>>>(a); else qk_sweep_wave2_kernel<3, double><<<grid, dim3(64), lds, s>>>(a); break;  // (an fp32 set: complex64 storage, fp64 arithmetic)
@@ -933,8 +954,9 @@ extern "C" int qk_gram_values(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set*
   const bool f32 = (xs->precision == 32);
   if (f32) c->last.bytes *= 0.5;  // complex64 planes
 
-  QkSweepPolicy pol = c->policy;  // two of the switches are read per call
+  QkSweepPolicy pol = c->policy;  // three of the switches are read per call
   if (const char* v = std::getenv("QK_FUSED_DUAL")) pol.fused_dual = std::atoi(v) != 0;
+  if (const char* v = std::getenv("QK_FUSED_BIG")) pol.fused_big = std::atoi(v) != 0;
   if (const char* v = std::getenv("QK_GANG")) pol.gang = std::atoi(v) != 0;
   const QkSweepChoice ch = qk_choose_sweep(pol, *plan, {xs->max_pad, xs->precision, xs->n_sites}, {ys->max_pad, ys->precision, ys->n_sites}, c->num_cus);
   if (ch.rc != QK_OK) return fail(ch.rc, "%s", ch.err);
@@ -989,12 +1011,13 @@ extern "C" int qk_gram_values(qk_ctx* c, const qk_mps_set* xs, const qk_mps_set*
     if (r.kernel == QK_KERNEL_LAB) rc = plan->quad ? qk_lab_launch_quad(c, ar, (int)r.grid, xs->n_sites, f32) : qk_lab_launch(c, pol.variant, ar, (int)r.grid, xs->n_sites);
     else
 #endif
-      rc = launch_sweep(r.kernel, f32, r.grid, r.lds, c->stream, ar);
+      rc = launch_sweep(r.kernel, f32, r.grid, r.lds_launch, c->stream, ar, r.big);
     if (rc != QK_OK) return rc;
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   c->ev_pending = true;
+  c->last.lds_bytes = (int32_t)ch.run[0].lds_launch, c->last.second_lds_bytes = ch.n_runs > 1 ? (int32_t)ch.run[1].lds_launch : 0;
   c->last.kernel = ch.run[0].kernel, c->last.grid = (int)ch.launched_grid;
   c->tail_pending = ch.tails;
   return QK_OK;

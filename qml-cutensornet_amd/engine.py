@@ -49,6 +49,8 @@ class QkStats(C.Structure):
         ("tail_frac", C.c_double),
         ("second_tail_frac", C.c_double),
         ("derive_ms", C.c_double),
+        ("lds_bytes", C.c_int32),
+        ("second_lds_bytes", C.c_int32),
     ]
 
     def as_dict(self):

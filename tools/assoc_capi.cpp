@@ -77,3 +77,71 @@ extern "C" void qk_onesum_pairs(const int32_t* x_true, const int32_t* y_true, in
     }
   }
 }
+
+// The residency of X (csrc/qk_plan.h: qk_resident) along the chains of the same pairs, walked the way the kernels walk them: X behind the
+// left edge at element 0, behind a step at the end where that step built X' (or in the global buffer when X' left the LDS in strips).
+// rcap / partial: the elements the residency may use and whether a step may keep part of X (QkSegRule); parities: 3 = merged steps chosen by
+// the dynamic programme (QK_MERGE=2), 0 = every site a step of its own in orientation 0 (QK_MERGE=0).  Per pair one word of case bits and
+// QK_RESIDENT_STATS numbers:
+//   stats [0 .. 4]  matrix instructions of the steps that are side by side, in place (one round), partially resident, evicted whole with X'
+//                   whole in LDS (X or the rule's answer leaves no panel), in strips (X or X' does not fit the segmentation's buffer)
+//   stats [5]       phase-1 matrix instructions of the units of partially resident steps whose panel stays (they run the LDS form)
+//   stats [6]       elements of X copied from LDS to the global buffer
+//   stats [7], [8]  panels of X in the partially resident steps, and how many of them stay
+//   stats [9]       phase-1 matrix instructions of the partially resident steps
+// Case bits of a chain: bit 0 a partially resident step with X at the low end, bit 1 with X at the top, bit 2 two partially resident steps in
+// a row (X low, then top, or the reverse), bit 3 a partially resident step keeps exactly one panel, bit 4 all but one, bit 5 none, bit 6 a
+// merged step (pd = 4) is partially resident, bit 7 a partially resident step is directly followed by a step that is not LDS-resident and keeps
+// nothing, bit 8 directly preceded by one (its X came from the global buffer and its X' stayed whole in LDS), bit 9 the last block of rows of a
+// partially resident step has fewer than 4 k-steps (a ragged true bond), bit 10 that block's panel stays, bit 11 it is evicted, bit 12 a step
+// is side by side in `rcap` elements but not in the segmentation's xcap, bit 13 a partially resident step switches (never: a switch step is
+// LDS-resident).
+static constexpr int QK_RESIDENT_STATS = 10;
+extern "C" void qk_resident_pairs(const int32_t* x_true, const int32_t* y_true, int32_t n_sites, const int32_t* pairs, int64_t n_pairs, int32_t ek, int32_t xcap, int32_t cap, int32_t dual,
+                                  int32_t rcap, int32_t partial, int32_t parities, int32_t assoc, int32_t switch_price, int32_t* cases, int64_t* stats) {
+  const QkSegRule rule{xcap, cap, dual != 0, rcap, partial != 0};
+  const int n1 = n_sites + 1, m = n_sites - 2 * ek;
+  std::vector<int32_t> xd(n1), yd(n1);
+  for (int64_t p = 0; p < n_pairs; ++p) {
+    const int32_t* xt = x_true + (int64_t)pairs[2 * p] * n1;
+    const int32_t* yt = y_true + (int64_t)pairs[2 * p + 1] * n1;
+    for (int i = 0; i < n1; ++i) xd[i] = qk_pad16(xt[i]), yd[i] = qk_pad16(yt[i]);
+    QkSegMask o{{0ull, 0ull}};
+    const QkSegMask k = qk_segment_chain(xd.data(), xt, yd.data(), yt, n_sites, ek, rule, parities, false, nullptr, nullptr, parities ? assoc : 0, switch_price, &o, nullptr);
+    int64_t* const st = stats + QK_RESIDENT_STATS * p;
+    for (int i = 0; i < QK_RESIDENT_STATS; ++i) st[i] = 0;
+    int c = 0, xb = 0, prev = -1;  // prev: what the step before was -- 0 LDS-resident or side by side, 1 partially resident, 2 neither
+    bool prev_top = false;
+    for (int i = 0; i < m;) {
+      const int len = qk_seg_bit(k.w[0], k.w[1], i) ? 2 : 1, e = ek + i;
+      const bool o1 = qk_seg_bit(o.w[0], o.w[1], i), s = qk_seg_bit(o.w[0], o.w[1], i + len) != o1;
+      const int a = o1 ? yd[e] : xd[e], a2 = o1 ? yd[e + len] : xd[e + len], b = o1 ? xd[e] : yd[e], b2 = o1 ? xd[e + len] : yd[e + len];
+      const int at = o1 ? yt[e] : xt[e], bt = o1 ? xt[e] : yt[e];
+      const int mt = a / 16, nt = b2 / 16, pd = 2 * len;
+      const bool top = xb != 0, x_lds = a * b <= xcap;
+      const QkResident r = qk_resident(rule, a, a2, b, b2, pd, top);
+      const long long instr = qk_step_instr(pd, a, a2, b, b2, at, bt), p1_panel = 3ll * pd * nt * ((bt + 3) >> 2);  // phase 1 of the units of one row block
+      const bool strips = a * b > xcap || a2 * b2 > xcap;
+      st[r.kind == QK_RES_SIDE ? 0 : r.kind == QK_RES_INPLACE ? 1 : r.kind == QK_RES_PART ? 2 : strips ? 4 : 3] += instr;
+      if (x_lds) st[6] += (long long)(mt - (r.khi - r.klo)) * b * 16;
+      if (r.kind == QK_RES_SIDE && a * b + a2 * b2 > xcap) c |= 1 << 12;
+      if (r.kind == QK_RES_PART) {
+        const int keep = r.khi - r.klo, klast = (at - (mt - 1) * 16 + 3) >> 2;
+        st[5] += p1_panel * keep, st[7] += mt, st[8] += keep, st[9] += p1_panel * mt;
+        c |= (top ? 2 : 1) | (keep == 1 ? 8 : 0) | (keep == mt - 1 ? 16 : 0) | (keep == 0 ? 32 : 0) | (pd == 4 ? 64 : 0) | (s ? 1 << 13 : 0);
+        if (prev == 1 && prev_top != top) c |= 4;
+        if (prev == 2) c |= 1 << 8;
+        if (klast < 4) c |= (1 << 9) | (mt - 1 >= r.klo && mt - 1 < r.khi ? 1 << 10 : 1 << 11);
+      } else if (r.kind == QK_RES_NONE && prev == 1) {
+        c |= 1 << 7;
+      }
+      prev = r.kind == QK_RES_PART ? 1 : r.kind == QK_RES_NONE ? 2 : 0, prev_top = top;
+      if (a2 * b2 > xcap) xb = 0, prev = -1;  // X' left the LDS in strips: the next step finds X in the global buffer
+      else xb = r.ob;
+      i += len;
+    }
+    cases[p] = c;
+  }
+}
+
+extern "C" int32_t qk_rcap_one() { return QKF_RCAP_ONE; }  // the large buffer of the 12-wave shapes as the kernels are built

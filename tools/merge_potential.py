@@ -2,7 +2,8 @@
 """What the segmentation of the site-fused sweep's chains executes, per launch of a bench config: steps and matrix instructions per
 pair with no merged steps (QK_MERGE=0), with every admissible merge of the fixed pairs (k + 2 t, k + 2 t + 1) (QK_MERGE=1) and with
 merges at either parity chosen per pair by dynamic programming (QK_MERGE=2, the default) -- and the device bytes of the merged images
-the last two need.  On top of QK_MERGE=2: the association of the steps (QK_ASSOC; tools/assoc_capi.cpp) -- matrix instructions, steps and
+the last two need.  The residency of X per kind of step (qk_resident: side by side, in place, partially resident, evicted whole, strips), what the
+two parts of the rule move to the LDS form of phase 1 and what is still copied to the global buffer.  On top of QK_MERGE=2: the association of the steps (QK_ASSOC; tools/assoc_capi.cpp) -- matrix instructions, steps and
 switches per pair with orientation 0 throughout (QK_ASSOC=0) and with the orientation chosen per step (the default), at the shipped
 switch price and at 0 and 150.
 
@@ -112,6 +113,52 @@ def onesum_pairs(x_true, y_true, pairs, ek, shape, assoc, switch_price=SWITCH_PR
     return cases, blocks
 
 
+RESIDENT_CASES = {"part_x_low": 1, "part_x_top": 2, "part_low_top_in_a_row": 4, "keeps_one": 8, "keeps_all_but_one": 16, "keeps_none": 32, "merged_part": 64,
+                  "part_then_not_resident": 128, "not_resident_then_part": 256, "ragged_part": 512, "ragged_panel_stays": 1024, "ragged_panel_evicted": 2048,
+                  "side_by_side_in_large_only": 4096, "part_switches": 8192}  # tools/assoc_capi.cpp: qk_resident_pairs
+RESIDENT_STATS = ("side", "in_place", "partial", "evicted_whole", "strips", "p1_lds_of_partial", "copied", "panels_of_partial", "panels_kept", "p1_of_partial")
+RCAP = {"12-wave dual (XCAP 8192)": 9728, "12-wave one-tile (XCAP 8192)": 9728, "8-wave one-tile (XCAP 4608)": 4608}  # csrc/qk_plan.h: QKF_RCAP_ONE (checked in resident_pairs), QKF_XCAP_TWO
+
+
+def resident_pairs(x_true, y_true, pairs, ek, shape, assoc, rcap=None, partial=True, merge=True, switch_price=SWITCH_PRICE):
+    """The residency of X (csrc/qk_plan.h: qk_resident) along the chains of the pairs, walked as the kernels walk them: (cases [pairs] --
+    RESIDENT_CASES --, stats [pairs][10] -- RESIDENT_STATS: matrix instructions per kind of step, the phase-1 matrix instructions of partially
+    resident steps that run the LDS form, elements copied to the global buffer, panels of the partially resident steps and how many stay).
+    rcap: elements the residency may use (None: the shape's shipped buffer; the shape's XCAP: the fallback instantiation); partial: QKF_RES_PARTIAL;
+    merge False: QK_MERGE=0 (every site its own step, orientation 0)."""
+    x_true = np.ascontiguousarray(x_true, dtype=np.int32)
+    y_true = np.ascontiguousarray(y_true, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    n = pairs.shape[0]
+    cases, stats = np.zeros(n, dtype=np.int32), np.zeros((n, len(RESIDENT_STATS)), dtype=np.int64)
+    xcap, cap, dual = SHAPES[shape]
+    lib = assoc_lib()
+    fn = lib.qk_resident_pairs
+    fn.restype = None
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + [C.c_int32] * 9 + [C.c_void_p] * 2
+    lib.qk_rcap_one.restype = C.c_int32
+    assert lib.qk_rcap_one() == RCAP["12-wave dual (XCAP 8192)"], "RCAP is out of step with csrc/qk_plan.h"
+    fn(x_true.ctypes.data, y_true.ctypes.data, x_true.shape[1] - 1, pairs.ctypes.data, n, int(ek), xcap, cap, dual, int(RCAP[shape] if rcap is None else rcap), int(bool(partial)),
+       3 if merge else 0, int(assoc), int(switch_price), cases.ctypes.data, stats.ctypes.data)
+    return cases, stats
+
+
+def resident_table(dims, pairs, ek, shape, assoc=1):
+    """The lines of the residency table of one launch: the parent's rule (the segmentation's buffer, no partial residency), each part alone, both."""
+    xcap = SHAPES[shape][0]
+    out = []
+    for name, rcap, partial in (("parent", xcap, False), ("partial", xcap, True), ("large buffer", RCAP[shape], False), ("both (shipped)", RCAP[shape], True)):
+        if rcap == xcap and name == "large buffer":
+            continue  # (this shape has no larger buffer)
+        _, st = resident_pairs(dims, dims, pairs, ek, shape, assoc, rcap, partial)
+        t = st.sum(axis=0).astype(np.float64)
+        total = t[:5].sum()
+        out.append(f"  residency, {name:14s} (buffer {rcap}): matrix instr. side by side {t[0] / total * 100:5.1f} %, in place {t[1] / total * 100:6.3f} %, partially resident {t[2] / total * 100:5.1f} %, "
+                   f"evicted whole {t[3] / total * 100:5.1f} %, strips {t[4] / total * 100:5.1f} %; panels that stay {t[8] / max(t[7], 1) * 100:5.1f} %; phase-1 instr. moved to the LDS form "
+                   f"{t[5] / total * 100:5.2f} % of the launch ({t[5]:.3e}); elements copied per pair {t[6] / len(pairs):9.0f}")
+    return out
+
+
 def merged_steps(masks):
     """merged steps per pair: the bits of its mask (the first two words)"""
     return np.array([bin(int(r[0])).count("1") + bin(int(r[1])).count("1") for r in masks])
@@ -175,6 +222,9 @@ def main():
                                          f"{((instr + edge[sl]).mean() / base[2] - 1) * 100:+.2f} % instr. with the edges, against QK_ASSOC=0)")
             print(f"  {name:20s}: steps/pair {steps.mean():6.2f}  merged {merged_steps(masks).mean():6.2f}  switches/pair {switches.mean():5.2f} (pairs that switch {(switches > 0).mean() * 100:5.1f} %, "
                   f"start in orientation 1 {((flags & 1) != 0).mean() * 100:5.1f} %, end in it {((flags & 2) != 0).mean() * 100:5.1f} %)  matrix instr./pair {instr.mean():9.0f}{rel}")
+        # the residency of X (qk_resident; on top of QK_MERGE=2, QK_ASSOC=1): share of the matrix instructions per kind of step, under the parent's rule and the two parts
+        for line in resident_table(dims, pairs[sl], ek, shape):
+            print(line)
     plan.close()
 
 
